@@ -10,13 +10,17 @@ N>1: the pod axis is sharded over ranks with ONE all-reduce of the per-group adm
   --scaling weak   (default) N x 10k pods, N x 2k groups, the same 5k nodes replicated
   --scaling strong the configuration is FIXED (use --config cfg4: 50k / 5k / 20k) and split over the ranks.
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  Beside the contract's fields:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up (--warmup steps), times exactly --steps steps (one region between
+barrier + synchronize), writes the last timed step's results if --dump-outputs DIR is given, and prints a short line: metric, value,
+unit, higher_is_better, dtype, ms_per_step and the configuration.  Everything else is measured only with --full:
+  timed_regions   the same --steps region repeated (TIMED_REGIONS in all, the first is the headline's), their median beside it
   roofline        the longest launch of the step, priced on EXECUTED work (no figure can exceed 1); `roofline_launches`
                   has every launch; `work_avoided` says how much of the logical pods x nodes space was never evaluated
   host_cycle      SURVEY 8(d)'s host-observed scheduling cycle: group patch + pod H2D + batch + decision / Filter-row
                   D2H, p50 / p95, and the evals/s that corresponds to it (PCIe inclusive — never `value`)
   scenarios       cold / warm / busy / all-distinct requests / PreFilter-only, seeds 1..3
   cpu_baseline    the oracle (C port of the Go path) on 1 core and on all host cores
+--no-extras / --no-cpu-baseline / --no-pmc trim a --full run; a plain run does none of these anyway.
 """
 from __future__ import annotations
 
@@ -45,7 +49,9 @@ SIMDS, CLOCK_HZ = 1024, 2.4e9
 # (tools/ubench/lane_loop.hip, profiles/r06_lane_loop_ubench.txt: 8.35 cycles per SIMD at eight waves per SIMD, 8.8-9.6 at three): the bound the
 # throughput regime's launch B is priced against (roofline_throughput)
 CYCLES_PER_NODE_LANE = 8.35
-TIMED_REGIONS = 5           # the K-step timed region is run this many times (each bracketed by barrier + synchronize); ms_per_step = the median region
+TIMED_REGIONS = 5           # --full: the K-step timed region is run this many times (each bracketed by barrier + synchronize); ms_per_step = the first region
+DUMP_SAMPLE_PODS = 512      # --dump-outputs: the pods (fixed seeded sample) whose Filter row over every node is written out
+DUMP_MAX_BYTES = 64 << 20
 # the steady-state step's launches by the library's timing group -> kernel name in a rocprofv3 trace.  Two forms: the one-launch
 # form of launch A + the scan / Filter roles followed by the final launch (the default where it applies, round 6), or launches A and B+C
 LAUNCH_KERNELS_ONE = {"query": "k_fast_step_a", "resolve": "k_fast_final"}
@@ -69,7 +75,35 @@ def parse():
     ap.add_argument("--no-pmc", action="store_true", help="do not re-run under rocprofv3 --pmc for HBM traffic")
     ap.add_argument("--inner-pmc", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-reps", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: repeated regions, roofline (rocprofv3 passes), host cycle, scenarios, drain, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (float32 / float64, rank 0)")
     return ap.parse_args()
+
+
+def dump_outputs(bsa, ctx, stages, out_dir):
+    """The arrays a caller of the timed path receives after its last step (bs_batch_read), as float64 (exact for every
+    integer field), plus the pods x nodes Filter verdicts of a fixed seeded sample of pods as float32 0 / 1 (the whole bitmap
+    is p x n, gigabytes at the larger configs).  Call it right after the timed steps: nothing may run in between."""
+    soa = bsa.soa
+    with_filter = bool(stages & soa.STAGE_FILTER)
+    out = ctx.read(bitmap=False, rows=with_filter)
+    arrays = {name: getattr(out, name).astype(np.float64)
+              for name in ("pf_code", "pf_first_k", "pf_leader", "fl_code", "fl_feasible", "group_admit", "group_ready")}
+    if with_filter:
+        p, n = out.pf_code.shape[0], out.n
+        budget = DUMP_MAX_BYTES - sum(a.nbytes for a in arrays.values()) - 8 * DUMP_SAMPLE_PODS
+        k = min(p, DUMP_SAMPLE_PODS, max(budget, 0) // (4 * max(n, 1)))
+        pods = np.sort(np.random.default_rng(0).choice(p, k, replace=False))
+        words = out.bitmap_from_rows()[:, pods]                               # [ceil(n/64), k] uint64, bit j of word w = node 64 w + j
+        bits = np.unpackbits(np.ascontiguousarray(words.T).view(np.uint8), axis=1, bitorder="little")[:, :n]
+        arrays["fl_bitmap_sample"] = bits.astype(np.float32)                  # [k, n]
+        arrays["fl_bitmap_sample_pods"] = pods.astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------ CPU baseline
@@ -502,7 +536,7 @@ def main():
 
     force_dist = bool(int(os.environ.get("BS_FORCE_DIST", "0")))   # exercise the collective path at world size 1
     rank_report = None
-    if dist is not None:
+    if dist is not None and args.full:
         # self-check of the first multi-GPU run: what RCCL sees and how the pod axis was dealt
         owned = torch.tensor([pods.p if partitioned else int((importlib.import_module("batch-scheduler_amd.dist").owner_ranks(all_pods.group, groups.g, world) == rank).sum())],
                              dtype=torch.int64, device=f"cuda:{local_rank}")
@@ -536,11 +570,9 @@ def main():
         step()
     fence()
     ctx.timing_reset()
-    # EXACTLY K steps between a barrier + synchronize on both sides, MAX over ranks — TIMED_REGIONS times back to back, and the line reports the
-    # MEDIAN region (all of them are in `timed_regions_ms`): at K = 20 one region is 0.45 ms and the first one carries the clocks' ramp-up
-    # (22.4 vs 20.9 us per step between 20 and 200 steps in round 5).  `steps` stays what was asked for.
-    regions = []
-    for _ in range(TIMED_REGIONS):
+
+    def region():
+        """EXACTLY K steps between a barrier + synchronize on both sides, MAX over ranks"""
         t0 = time.perf_counter()
         for _ in range(args.steps):
             step()
@@ -550,8 +582,24 @@ def main():
             t = torch.tensor([el], dtype=torch.float64, device=f"cuda:{local_rank}")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
-        regions.append(el)
-    elapsed = float(np.median(regions))
+        return el
+
+    elapsed = region()                       # the headline: ms_per_step and value
+    logical = all_pods.p * nodes.n                    # whole job: every pending pod (all ranks) against every node
+    ms_per_step = elapsed / args.steps * 1e3
+    value = logical * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(bsa, ctx, stages, args.dump_outputs)
+    if not args.full:
+        result = None
+        if rank == 0:
+            result = headline(args, n_gpus, value, ms_per_step, logical, all_pods, groups, nodes, world, dist, partitioned)
+        finish(dist, ctx, rank, result)
+        return result
+
+    # --full: the same region TIMED_REGIONS - 1 more times (at K = 20 one region is 0.45 ms and the first one carries the clocks' ramp-up:
+    # 22.4 vs 20.9 us per step between 20 and 200 steps in round 5); all of them are in `timed_regions_ms`, their median beside the headline
+    regions = [elapsed] + [region() for _ in range(TIMED_REGIONS - 1)]
     timing = ctx.timing()
     if rank == 0 and not any(v[1] for v in timing.values()):
         # (single context on this rank's device; in a sharded run rank 0's own part of the queue)
@@ -563,10 +611,6 @@ def main():
     ctx.sync()
     stats = ctx.stats_read()
     out = ctx.read(bitmap=False, rows=False)
-
-    logical = all_pods.p * nodes.n                    # whole job: every pending pod (all ranks) against every node
-    ms_per_step = elapsed / args.steps * 1e3
-    value = logical * args.steps / elapsed
 
     result = None
     if rank == 0:
@@ -768,15 +812,8 @@ def main():
         if drain is not None:
             drain.pop("_cpu_sequential_pass", None)
         codes = np.bincount(out.pf_code, minlength=256)
-        result = {
-            "metric": "pod x node fit evals/sec", "value": value, "unit": "evals/s", "n_gpus": n_gpus,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None, "dtype": "int64", "data": "synthetic",
-            "config": {"workload": f"{args.config}/{args.scenario}: {all_pods.p} pods / {groups.g} groups / {nodes.n} nodes, "
-                                   f"{L} int64 lanes (cpu, mem, eph, pods{', gpu' if L > 4 else ''}), seed {args.seed}",
-                       "stages": "prefilter+filter+tally+ready" if args.stages == "all" else "prefilter+tally+ready",
-                       "parallelism": (f"pod-axis shard x{world}, " + ("pods partitioned by owning rank" if partitioned else "replicated batch, device-side ownership")
-                                       + ", 1 all-reduce of admit[G]") if dist is not None else "single GPU",
+        result = headline(args, n_gpus, value, ms_per_step, logical, all_pods, groups, nodes, world, dist, partitioned)
+        result["config"].update({
                        "value_definition": "`value` = LOGICAL pods x nodes per step / step time with every input already resident in HBM (the contract's definition); beside it "
                                            "`value_host_observed` = the same logical evals / the host-observed resident-queue cycle (SURVEY 8(d)'s own definition, PCIe inclusive) and "
                                            "`value_executed` = the pod x node compares the step REALLY executed / step time (request classes + pruning: a fraction of a percent of the logical space).  "
@@ -786,12 +823,15 @@ def main():
                                            "wall time, host-observed, including the per-batch inputs' way in and the decisions' way out, node SoA resident).  Both are "
                                            "LOGICAL rates: `work_avoided` says how little of the pods x nodes space is actually evaluated (`value_executed`), and the "
                                            "figure for real per-pair work is `roofline_throughput` (every pod its own request)",
-                       "logical_evals_per_step": logical, "fast_path": stats["fast_path"], "chain": stats["chain"], "launches_per_step": stats["launches"],
+                       "fast_path": stats["fast_path"], "chain": stats["chain"], "launches_per_step": stats["launches"],
                        "tables_built": stats["tables_built"],
                        "decisions": {soa.PF_NAMES.get(i, str(i)): int(c) for i, c in enumerate(codes) if c},
-                       "groups_ready": int(out.group_ready.sum())},
+                       "groups_ready": int(out.group_ready.sum())})
+        result.update({
             "timed_regions_ms": [r * 1e3 for r in regions],
-            "timed_regions_note": f"{TIMED_REGIONS} regions of exactly {args.steps} steps each, every one between barrier + synchronize (max over ranks); ms_per_step and value are the MEDIAN region's",
+            "ms_per_step_median_region": float(np.median(regions)) / args.steps * 1e3,
+            "timed_regions_note": f"{TIMED_REGIONS} regions of exactly {args.steps} steps each, every one between barrier + synchronize (max over ranks); ms_per_step and value are "
+                                  f"the FIRST region's (the one a plain run times), ms_per_step_median_region the median's",
             "value_resident": value,
             "value_executed": (stats["scan_evals_executed"] + stats["filter_evals_executed"]) / (ms_per_step * 1e-3),
             "value_note": "`value` is a LOGICAL rate (pods x nodes / step time); `value_executed` = pod x node compares the step really executed / step time",
@@ -812,9 +852,32 @@ def main():
             "scenarios": extras,
             "kernel_ms_per_step": {k: v[0] / v[1] for k, v in timing.items() if v[1]},
             "cpu_baseline": cpu,
-        }
+        })
         if dist is not None:
             result["ranks"] = rank_report
+    finish(dist, ctx, rank, result)
+    return result
+
+
+def headline(args, n_gpus, value, ms_per_step, logical, all_pods, groups, nodes, world, dist, partitioned):
+    """The fields of a plain run's line (a --full line adds to them)."""
+    L = nodes.lanes
+    return {
+        "metric": "pod x node fit evals/sec", "value": value, "unit": "evals/s", "n_gpus": n_gpus,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": args.scaling, "vs_baseline": None, "dtype": "int64", "data": "synthetic",
+        "config": {"workload": f"{args.config}/{args.scenario}: {all_pods.p} pods / {groups.g} groups / {nodes.n} nodes, "
+                               f"{L} int64 lanes (cpu, mem, eph, pods{', gpu' if L > 4 else ''}), seed {args.seed}",
+                   "stages": "prefilter+filter+tally+ready" if args.stages == "all" else "prefilter+tally+ready",
+                   "parallelism": (f"pod-axis shard x{world}, " + ("pods partitioned by owning rank" if partitioned else "replicated batch, device-side ownership")
+                                   + ", 1 all-reduce of admit[G]") if dist is not None else "single GPU",
+                   "value_definition": "LOGICAL pods x nodes per step / step time, every input resident in HBM; ms_per_step = one region of exactly `steps` steps "
+                                       "between barrier + synchronize / steps",
+                   "logical_evals_per_step": logical},
+    }
+
+
+def finish(dist, ctx, rank, result):
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
@@ -827,7 +890,6 @@ def main():
         except Exception:
             pass
         print(json.dumps(result), flush=True)
-    return result
 
 
 if __name__ == "__main__":

@@ -103,7 +103,7 @@ def test_bench_under_the_drivers_launcher_with_the_collective_path(scenario):
     bs_batch_finish, the max-over-ranks clock.  Its decisions must be the plain single-GPU run's."""
     import json
     root = os.path.dirname(HERE)
-    common = ["--gpus", "1", "--steps", "6", "--warmup", "2", "--config", "cfg2", "--scenario", scenario, "--no-extras", "--no-cpu-baseline", "--no-pmc"]
+    common = ["--gpus", "1", "--steps", "6", "--warmup", "2", "--config", "cfg2", "--scenario", scenario, "--full", "--no-extras", "--no-cpu-baseline", "--no-pmc"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", NCCL_SOCKET_IFNAME="lo")
     plain = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *common], capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert plain.returncode == 0, plain.stderr[-3000:]

@@ -7,8 +7,8 @@ mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 export BS_SKIP_SLOW_LIVE=${BS_SKIP_SLOW_LIVE:-1}
 timeout 900 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc $?" | tee -a $OUT/pytest_gpu.log; tail -3 $OUT/pytest_gpu.log
-timeout 600 python bench.py > $OUT/bench_default_N1.json.log 2> $OUT/bench_default.err; echo "bench rc $?"
-timeout 600 python bench.py --config cfg4 --no-pmc > $OUT/bench_cfg4_N1.json.log 2> $OUT/bench_cfg4.err; echo "bench cfg4 rc $?"
+timeout 600 python bench.py --full > $OUT/bench_default_N1.json.log 2> $OUT/bench_default.err; echo "bench rc $?"
+timeout 600 python bench.py --full --config cfg4 --no-pmc > $OUT/bench_cfg4_N1.json.log 2> $OUT/bench_cfg4.err; echo "bench cfg4 rc $?"
 timeout 600 bash tools/prof_all.sh $TAG > $OUT/prof_all.log 2>&1
 python tools/prof_summary.py gpurun_out/prof_$TAG $OUT/final_cfg3_tail > /dev/null 2>&1
 cd /tmp && export TMPDIR=/tmp

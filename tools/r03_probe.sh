@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage (GPU box): bash tools/r03_probe.sh <tag> — the resident cycle and the resident step, host-observed and per kernel
 TAG=${1:-p}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
@@ -8,7 +9,7 @@ python tools/cycle_probe.py cfg3 tail 300 | tee $OUT/cycle.json
 PROBE_FILTER=0 python tools/cycle_probe.py cfg3 tail 300 | tee $OUT/cycle_prefilter.json
 cd /tmp && export TMPDIR=/tmp
 timeout 200 rocprofv3 --kernel-trace --stats -d $OUT/trace_cycle -o t -- python $GRAFT_REPO_ROOT/tools/cycle_probe.py cfg3 tail 100 > $OUT/trace_cycle.log 2>&1
-timeout 200 rocprofv3 --kernel-trace --stats -d $OUT/trace_step -o t -- python $GRAFT_REPO_ROOT/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extras --no-pmc > $OUT/trace_step.log 2>&1
+timeout 200 rocprofv3 --kernel-trace --stats -d $OUT/trace_step -o t -- python $ROOT/bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extras --no-pmc > $OUT/trace_step.log 2>&1
 cd $GRAFT_REPO_ROOT
 python - <<PY
 import sqlite3, glob

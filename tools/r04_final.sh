@@ -6,7 +6,7 @@ OUT=$R/gpurun_out/r04
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # 1. the bench line (self-profiling: its own rocprofv3 passes for the roofline block)
-( cd $R && timeout 900 python bench.py > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err )
+( cd $R && timeout 900 python bench.py --full > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err )
 # 2. kernel trace + PMC of the batched step (as in earlier rounds)
 BENCH="python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras --no-pmc"
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- $BENCH > $OUT/trace.log 2>&1

@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd $R
 timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -15 > $OUT/pytest_gpu_final.log
 cd /tmp && export TMPDIR=/tmp
-( cd $R && timeout 600 python bench.py > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err )
+( cd $R && timeout 600 python bench.py --full > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err )
 BENCH="python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras --no-pmc"
 timeout 200 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- $BENCH > $OUT/trace.log 2>&1
 SEQ="python $R/tools/seq_bench.py cfg3 tail"

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 ( cd $R && timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log )
 ( cd $R && timeout 900 python -m pytest tests -m gpu -q -p no:cacheprovider 2>&1 | tail -8 > $OUT/pytest_gpu.log; tail -2 $OUT/pytest_gpu.log )
 # 1. the bench line (self-profiling: its own rocprofv3 passes for the roofline block)
-( cd $R && timeout 900 python bench.py > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err )
+( cd $R && timeout 900 python bench.py --full > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err )
 # 2. kernel trace + PMC of the batched step (as in earlier rounds)
 BENCH="python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras --no-pmc"
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- $BENCH > $OUT/trace.log 2>&1

@@ -19,7 +19,7 @@ import sys, json
 for l in sys.stdin:
     d = json.loads(l); print('BS_TP_SHARE=$SH', d['config'], 'shard', d['shard'], d['us_per_step_best'], 'us per step, Filter evals', d['filter_evals_executed'])" >> $OUT/shard_shares.txt
 done
-timeout 300 python bench.py > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err
+timeout 300 python bench.py --full > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err
 tail -n 3 $OUT/pytest_gpu.log
 cat $OUT/node_loop.txt | head -45
 cat $OUT/shard_shares.txt

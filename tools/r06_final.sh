@@ -7,8 +7,8 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 ( cd $R && timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log )
 ( cd $R && timeout 1800 python -m pytest tests -m gpu -q -n 2 -p no:cacheprovider 2>&1 | tail -8 > $OUT/pytest_gpu.log; tail -2 $OUT/pytest_gpu.log )
-( cd $R && timeout 900 python bench.py > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err )
-( cd $R && timeout 900 python bench.py --steps 20 --warmup 3 > $OUT/bench_steps20_N1.json.log 2> $OUT/bench_steps20_N1.err )
+( cd $R && timeout 900 python bench.py --full > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err )
+( cd $R && timeout 900 python bench.py --full --steps 20 --warmup 3 > $OUT/bench_steps20_N1.json.log 2> $OUT/bench_steps20_N1.err )
 BENCH="python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras --no-pmc"
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- $BENCH > $OUT/trace.log 2>&1
 timeout 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY -d $OUT/step_pmc_sq -o pmc -- $BENCH > $OUT/step_pmc_sq.log 2>&1

@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 ( cd $R && timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log )
 ( cd $R && timeout 900 python -m pytest tests/test_bench_and_errors.py -m gpu -x -q 2>&1 | tail -5 > $OUT/pytest_bench.log; tail -2 $OUT/pytest_bench.log )
-( cd $R && timeout 900 python bench.py > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err; tail -c 300 $OUT/bench_default_N1.err )
+( cd $R && timeout 900 python bench.py --full > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err; tail -c 300 $OUT/bench_default_N1.err )
 for K in 1 4; do
   DIST4="python $R/tools/step_time.py cfg4 tail --distinct --lanes $K --steps 40"
   timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/distinct4_k${K}_trace -o trace -- $DIST4 > $OUT/distinct4_k${K}_trace.log 2>&1

@@ -7,7 +7,7 @@ cd $R
 timeout 2400 python -m pytest tests -m gpu -x -q -n 2 > $OUT/pytest_gpu.log 2>&1
 tail -n 6 $OUT/pytest_gpu.log
 for A in "cfg3 tail" "cfg3 warm" "cfg3 busy" "cfg2 tail" "cfg3 cold" "cfg4 tail"; do timeout 200 python tools/step_time.py $A 2>&1 | tail -1; done | tee $OUT/step_times.txt
-timeout 900 python bench.py > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err; tail -c 300 $OUT/bench_default_N1.err
+timeout 900 python bench.py --full > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err; tail -c 300 $OUT/bench_default_N1.err
 python - <<'P'
 import json
 d = json.loads(open("/root/repo/gpurun_out/r06_n/bench_default_N1.json.log").read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ cd $R
 timeout 2400 python -m pytest tests -m gpu -x -q -n 2 > $OUT/pytest_gpu.log 2>&1
 tail -n 4 $OUT/pytest_gpu.log
 ( BS_HOST_PROBE=1 timeout 200 python tools/cycle_probe.py cfg3 2>&1 | tail -3 ) | tee $OUT/cycle_probe.txt
-timeout 900 python bench.py > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err; tail -c 300 $OUT/bench_default_N1.err
+timeout 900 python bench.py --full > $OUT/bench_default_N1.json.log 2> $OUT/bench_default_N1.err; tail -c 300 $OUT/bench_default_N1.err
 python - <<'P'
 import json
 d = json.loads(open("/root/repo/gpurun_out/r06_r/bench_default_N1.json.log").read().strip().splitlines()[-1])
