@@ -47,6 +47,14 @@ namespace bs {
 template <bool INL = false>
 __device__ __forceinline__ void arm_tally(const GroupsDev& gr, const BatchDev& b, const BatchParams& prm, uint32_t i, uint32_t nthreads);
 
+// BatchDev::pod_ranges: its three parts, and whether the local gangs are closed in LDS (wherever tally_tail would take its returning-atomic quorum)
+__device__ __forceinline__ const uint8_t* range_glocal(const BatchDev& b) { return reinterpret_cast<const uint8_t*>(b.pod_ranges); }
+__device__ __forceinline__ const uint32_t* range_start(const BatchDev& b, uint32_t G) { return b.pod_ranges + (G + 3u) / 4u; }
+__device__ __forceinline__ const uint32_t* range_lfirst(const BatchDev& b, uint32_t G, uint32_t pod_blocks) { return range_start(b, G) + pod_blocks + 1u; }
+__device__ __forceinline__ bool range_local_on(const BatchDev& b, const BatchParams& prm) {
+  return b.pod_ranges && prm.do_tally && prm.do_ready && !prm.filter_deny;
+}
+
 // ------------------------------------------------------------------------------------------------
 // bs_pods_load: what the batch needs from the pods alone.
 //   gstat[0][g] first pod of group g (shard ownership)           gstat[1][g] first pod without LAST_PERMITTED
@@ -435,11 +443,12 @@ __device__ __forceinline__ uint32_t class_scan_query(const Res& cur, const Leade
 //   round 1   the pod's own fields (group, flags, owner, request, class, pair) | the batch's leader and panic flag
 //   round 2   the pod's group (flags, OccupiedBy, first owner, first pod) | both leaders' resources (uniform)
 //   round 3   the owner of the group's first owning pod (only where OccupiedBy is still empty)
+// INL (the whole step in one launch): pod i of the block's range, which ends at `end` (bs_pod_ranges.hpp); `t` is the thread's index in the pod blocks' grid
 template <int TS, bool PUB = false, bool SLOTS = true, bool INL = false>
 __device__ __forceinline__ void fast_query_thread(const PodsDev& pods, const GroupsDev& gr, const BatchDev& b, const BatchParams& prm, uint32_t i,
-                                                  uint32_t nthreads) {
+                                                  uint32_t nthreads, uint32_t end = BS_INF, uint32_t t = BS_INF) {
   const Shape<TS> sh(prm.S);
-  const bool valid = i < pods.p;
+  const bool valid = i < pods.p && i < end;
   const uint32_t gate = prm.eph_gate;
   const uint32_t ii = valid ? i : 0u;                                 // (clamped loads: invalid lanes read pod 0 and store nothing)
   // ---- round 1
@@ -453,7 +462,7 @@ __device__ __forceinline__ void fast_query_thread(const PodsDev& pods, const Gro
   const uint32_t pp = pods.p ? b.ppair[ii] : BS_INF;
   Res cur;
   if (pods.p) pod_require(pods, ii, sh, gate, cur); else res_zero(cur, sh);
-  arm_tally<INL>(gr, b, prm, i, nthreads);                             // consumed by launch C (INL: by the second half of this launch)
+  arm_tally<INL>(gr, b, prm, t == BS_INF ? i : t, nthreads);           // consumed by launch C (INL: by the second half of this launch)
   if (i < 8 && prm.collect_stats) b.stats[i] = 0;
   // ---- round 2
   const bool grouped = valid && gi >= 0 && (uint32_t)gi < gr.g;
@@ -1191,6 +1200,9 @@ __device__ __forceinline__ void arm_tally(const GroupsDev& gr, const BatchDev& b
   // (a plain store parked in this XCD's L2 would be written back over the closing lane's value at the end of the launch)
   if (i == 0) __hip_atomic_store(&b.ticket[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // hand-over counter of the fused scan / final launch
   for (uint32_t g = i; g < gr.g; g += nthreads) {
+    // a gang closed in LDS by its pod block (tally_tail_whole): that block writes its words, once, and nobody else does — a zero from here, written
+    // through or not, could otherwise land behind the closing block's value
+    if (INL && range_local_on(b, prm) && range_glocal(b)[g]) continue;
     st_pub<INL>(&b.admit[g], 0u);
     if (prm.do_ready) {
       st_pub<INL>(&b.admit64[g], 0ull);
@@ -1228,6 +1240,42 @@ __device__ __forceinline__ void final_tail(const BatchDev& b, const BatchParams&
   }
 }
 
+// the quorum's returning atomics (tally_tail): want = the lane's group's gcount; ready = matched + admitted >= need (MinMember - Status.Scheduled)
+__device__ __forceinline__ void tally_quorum_atomic(const BatchDev& b, const BatchParams& prm, bool grouped, uint32_t g, bool admit, uint32_t want, uint32_t ma,
+                                                    uint32_t need) {
+  // who adds what: one lane per distinct group of the wave (the first kElectRounds groups; lanes left over add for themselves)
+  unsigned long long mine = 0;
+  bool asked = false;
+  unsigned long long todo = __ballot(grouped);
+  const unsigned long long adm = __ballot(grouped && admit);
+  for (int round = 0; todo && round < kElectRounds; ++round) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)g, leader);
+    const unsigned long long same = __ballot(grouped && g == k0) & todo;
+    if (lane_id() == leader) {
+      mine = ((unsigned long long)__popcll(same) << 32) | (unsigned long long)__popcll(same & adm);
+      asked = true;
+    }
+    todo &= ~same;
+  }
+  if (todo & (1ull << lane_id())) {
+    mine = (1ull << 32) | (admit ? 1ull : 0ull);
+    asked = true;
+  }
+  // ONE returning atomic instruction for all of them (a returning atomic per round would wait for the previous round's result)
+  unsigned long long got = 0;
+  if (asked) got = __hip_atomic_fetch_add(&b.admit64[g], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (asked) {
+    const unsigned long long tot = got + mine;
+    if ((uint32_t)(tot >> 32) == want) {           // every pod of the group has been counted: this lane closes it
+      const uint32_t ad = (uint32_t)tot;
+      const uint8_t rd = (ma + ad) >= need ? 1 : 0;
+      b.admit[g] = ad;
+      b.ready[g] = rd;
+      if (prm.host_tag) { st_home(&b.h_admit[g], ad); st_home(&b.h_ready[g], rd); }
+    }
+  }
+}
 // grouped: the pod names a group of the loaded state (g valid); admit: it passes PreFilter and, if Filter ran, has a feasible node
 template <bool WT = false>
 __device__ __forceinline__ void tally_tail(const GroupsDev& gr, const BatchDev& b, const BatchParams& prm, bool grouped, uint32_t g, bool admit,
@@ -1236,38 +1284,37 @@ __device__ __forceinline__ void tally_tail(const GroupsDev& gr, const BatchDev& 
     // what closing a group needs, fetched while the adds are in flight (the lane's own group: the leader of a key is one of its lanes)
     uint32_t want = 0, ma = 0, mm = 0, sc = 0;
     if (grouped) { want = b.gcount[g]; ma = gr.matched[g]; mm = gr.min_member[g]; sc = gr.status_scheduled[g]; }
-    // who adds what: one lane per distinct group of the wave (the first kElectRounds groups; lanes left over add for themselves)
-    unsigned long long mine = 0;
-    bool asked = false;
-    unsigned long long todo = __ballot(grouped);
-    const unsigned long long adm = __ballot(grouped && admit);
-    for (int round = 0; todo && round < kElectRounds; ++round) {
-      const int leader = __ffsll((long long)todo) - 1;
-      const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)g, leader);
-      const unsigned long long same = __ballot(grouped && g == k0) & todo;
-      if (lane_id() == leader) {
-        mine = ((unsigned long long)__popcll(same) << 32) | (unsigned long long)__popcll(same & adm);
-        asked = true;
-      }
-      todo &= ~same;
+    tally_quorum_atomic(b, prm, grouped, g, admit, want, ma, (uint32_t)(mm - sc));
+  } else if (prm.do_tally) {
+    wave_aggregated_add(b.admit, g, grouped && admit);
+  }
+  final_tail<WT>(b, prm, nblocks);
+}
+
+// The whole-step launch's tally (fast_final_block<true>).  What closing a group needs comes from the caller, fetched in its round trip 2a before the wait
+// for the producers (with the local gangs below no returning atomic hides that trip any more): ma = matched, need = MinMember - Status.Scheduled, and
+// gwant = the group's pod count, or kLocalTag | slot for a LOCAL gang — all of its pods in this block's range (range_lfirst), slot = the thread of its first
+// pod.  A local gang is counted with LDS atomics and closed by that thread after one barrier: no global atomic, no round trip.  The other grouped pods take
+// tally_tail's returning atomic; a wave without any skips it (its ballot is empty: a wave-uniform branch; a block-wide OR in the barrier
+// pushed k_fast_step_a into scratch).  s_adm: the block's [256] counters, zeroed by the caller
+// before an earlier barrier.
+constexpr uint32_t kLocalTag = 0x80000000u;
+template <bool WT = false>
+__device__ __forceinline__ void tally_tail_whole(const GroupsDev& gr, const BatchDev& b, const BatchParams& prm, bool grouped, uint32_t g, bool admit,
+                                                 uint32_t nblocks, uint32_t gwant, uint32_t ma, uint32_t need, uint32_t* s_adm) {
+  if (prm.do_tally && prm.do_ready) {
+    const bool local = grouped && (gwant & kLocalTag);
+    const uint32_t lslot = gwant & 0xFFu;
+    if (local && admit) atomicAdd(&s_adm[lslot], 1u);
+    __syncthreads();
+    if (local && lslot == threadIdx.x) {
+      const uint32_t ad = s_adm[lslot];
+      const uint8_t rd = (ma + ad) >= need ? 1 : 0;
+      b.admit[g] = ad;
+      b.ready[g] = rd;
+      if (prm.host_tag) { st_home(&b.h_admit[g], ad); st_home(&b.h_ready[g], rd); }
     }
-    if (todo & (1ull << lane_id())) {
-      mine = (1ull << 32) | (admit ? 1ull : 0ull);
-      asked = true;
-    }
-    // ONE returning atomic instruction for all of them (a returning atomic per round would wait for the previous round's result)
-    unsigned long long got = 0;
-    if (asked) got = __hip_atomic_fetch_add(&b.admit64[g], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (asked) {
-      const unsigned long long tot = got + mine;
-      if ((uint32_t)(tot >> 32) == want) {           // every pod of the group has been counted: this lane closes it
-        const uint32_t ad = (uint32_t)tot;
-        const uint8_t rd = (ma + ad) >= (uint32_t)(mm - sc) ? 1 : 0;
-        b.admit[g] = ad;
-        b.ready[g] = rd;
-        if (prm.host_tag) { st_home(&b.h_admit[g], ad); st_home(&b.h_ready[g], rd); }
-      }
-    }
+    tally_quorum_atomic(b, prm, grouped && !local, g, admit, gwant, ma, need);      // (a wave without such a pod issues no atomic: its ballot is empty)
   } else if (prm.do_tally) {
     wave_aggregated_add(b.admit, g, grouped && admit);
   }
@@ -1296,21 +1343,26 @@ __device__ __forceinline__ void tally_tail(const GroupsDev& gr, const BatchDev& 
 template <bool INL = false>
 __device__ __forceinline__ void fast_final_block(const PodsDev& pods, const GroupsDev& gr, const NodesDev& nd, const BatchDev& b, const BatchParams& prm,
                                                  uint32_t query_blocks, uint32_t bx, uint32_t nblocks, uint32_t producers, uint32_t tk_p1 = 0, uint32_t aux = 0,
-                                                 uint32_t tk_done = 0, uint32_t hint_blocks = 0) {
+                                                 uint32_t tk_done = 0, uint32_t hint_blocks = 0, uint32_t p0 = BS_INF, uint32_t p1 = BS_INF) {
   __shared__ uint32_t s_first_reach;
-  __shared__ uint32_t s_rowk[INL ? kStepSlotsMax : 1u], s_feask[INL ? 2u * kStepSlotsMax : 1u];
+  __shared__ uint32_t s_rowk[INL ? kStepSlotsMax : 1u], s_feask[INL ? 2u * kStepSlotsMax : 1u], s_ladm[INL ? 256u : 1u], s_gw[INL ? 3u : 1u][INL ? 256u : 1u];
   BS_STAMP(3, 0);
   if constexpr (INL) {
+    s_ladm[threadIdx.x] = 0u;                        // the local gangs' admit counters (tally_tail_whole)
     if (threadIdx.x < 64) (void)spread_wait(&b.ticket[kTkP1], tk_p1, query_blocks, b.h_err);
     __syncthreads();
   }
-  const uint32_t i = bx * 256u + threadIdx.x;
-  const bool valid = i < pods.p;
+  // INL: the block's pods are [p0, p1), the gang-aligned range of bs_pod_ranges.hpp (or 256 pods per block); dx: the thread's index in the grid of final blocks
+  const uint32_t dx = bx * 256u + threadIdx.x;
+  const uint32_t i = p0 == BS_INF ? dx : p0 + threadIdx.x;
+  const bool valid = i < pods.p && (p0 == BS_INF || i < p1);
   // ---- round trip 1: the pod's own fields, and the block's look at the first reaching pod
   uint8_t code0 = 0, st0 = 0;
   int32_t gi0 = BS_POD_NOT_GROUPED;
   uint32_t qpos0 = 0, pclass0 = 0, pair0 = BS_INF;
+  uint32_t lfirst = BS_INF;
   if (valid) { code0 = b.tcode[i]; st0 = b.stage[i]; gi0 = pods.group[i]; qpos0 = b.qpos[i]; pclass0 = b.pclass[i]; pair0 = b.ppair[i]; }
+  if (INL && valid && range_local_on(b, prm)) lfirst = range_lfirst(b, gr.g, query_blocks)[i];
   const uint32_t K = prm.k_host ? prm.k_host : *b.kclass;
   const int32_t leader_now = b.leader_epoch[0];
   // first pod that reaches findMaxPG = the candidate of the first block of launch A that has one (64 blocks per look)
@@ -1339,6 +1391,22 @@ __device__ __forceinline__ void fast_final_block(const PodsDev& pods, const Grou
   if (walk) {
     head = b.pair_head[gi0];
     if (pair0 != BS_INF) { own_fq = INL ? ld_agent64(&b.pair_firstq[pair0]) : b.pair_firstq[pair0]; own_next = b.pair_next[pair0]; }
+  }
+  // INL: what closing the pod's group needs (tally_tail_whole), in the same trip — three words, parked in LDS across the wait (in registers they push
+  // the kernel's footprint into scratch): the closing rule's two operands and either the gang's first pod in the block (local gang, kLocalTag) or the
+  // group's pod count
+  if constexpr (INL) {
+    if (prm.do_tally && prm.do_ready) {
+      uint32_t gwant = 0, gma = 0, gneed = 0;
+      if (grouped) {
+        gma = gr.matched[gi0];
+        gneed = (uint32_t)(gr.min_member[gi0] - gr.status_scheduled[gi0]);
+        gwant = lfirst != BS_INF ? kLocalTag | (lfirst - p0) : b.gcount[gi0];
+      }
+      s_gw[0][threadIdx.x] = gwant;
+      s_gw[1][threadIdx.x] = gma;
+      s_gw[2][threadIdx.x] = gneed;
+    }
   }
   if (producers) {                                   // the scan / Filter blocks of this launch have to be through
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (our own loads first: they overlap the producers, not the wait)
@@ -1495,14 +1563,19 @@ __device__ __forceinline__ void fast_final_block(const PodsDev& pods, const Grou
   }
   if (gathered) {                                    // the slots' counts, for whoever reads fu_feas[] after the launch (bs_fdeny.hpp, bs_batch_read)
     if (prm.run_filter)
-      for (uint32_t k = i; k < 2u * K; k += nblocks * 256u) b.fu_feas[k] = s_feask[INL ? k : 0u];
+      for (uint32_t k = dx; k < 2u * K; k += nblocks * 256u) b.fu_feas[k] = s_feask[INL ? k : 0u];
   }
   if (prm.host_tag && prm.run_filter) {             // per-row feasible counts of the slots in use
     const uint32_t U = min(2u * K, b.hstride);
-    for (uint32_t k = i; k < U; k += nblocks * 256u) st_home(&b.h_feas[k], gathered ? s_feask[INL ? k : 0u] : ld_agent(&b.fu_feas[k]));
+    for (uint32_t k = dx; k < U; k += nblocks * 256u) st_home(&b.h_feas[k], gathered ? s_feask[INL ? k : 0u] : ld_agent(&b.fu_feas[k]));
   }
   BS_STAMP(3, 2);
-  if (!prm.filter_deny) tally_tail<true>(gr, b, prm, grouped, grouped ? (uint32_t)gi0 : 0u, admit, nblocks);      // (else: k_fd_apply, bs_fdeny.hpp)
+  if (!prm.filter_deny) {                                                                                          // (else: k_fd_apply, bs_fdeny.hpp)
+    if constexpr (INL)
+      tally_tail_whole<true>(gr, b, prm, grouped, grouped ? (uint32_t)gi0 : 0u, admit, nblocks, s_gw[0][threadIdx.x], s_gw[1][threadIdx.x], s_gw[2][threadIdx.x], s_ladm);
+    else
+      tally_tail<true>(gr, b, prm, grouped, grouped ? (uint32_t)gi0 : 0u, admit, nblocks);
+  }
   BS_STAMP(3, 7);
 }
 
@@ -1639,11 +1712,14 @@ __global__ __launch_bounds__(kTblChunk) void k_fast_step_a(PodsDev pods, GroupsD
   const bool direct = query_blocks <= kGatherDirectBlocks;
   if (blockIdx.x < query_blocks) {
     if constexpr (WHOLE) {
-      fast_query_thread<TS, false, false, true>(pods, gr, b, prm, blockIdx.x * kTblChunk + threadIdx.x, query_blocks * kTblChunk);
+      // the block's pods: [p0, p1) — a gang-aligned range when bs_pods_load left them (b.pod_ranges, bs_pod_ranges.hpp), else 256 pods
+      const uint32_t p0 = b.pod_ranges ? range_start(b, gr.g)[blockIdx.x] : blockIdx.x * kTblChunk;
+      const uint32_t p1 = b.pod_ranges ? range_start(b, gr.g)[blockIdx.x + 1u] : pods.p;
+      fast_query_thread<TS, false, false, true>(pods, gr, b, prm, p0 + threadIdx.x, query_blocks * kTblChunk, p1, blockIdx.x * kTblChunk + threadIdx.x);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // first-reach word, armed counters, the pairs' minima: out before the ticket
       __syncthreads();
       if (threadIdx.x == 0) spread_add(&b.ticket[kTkP1], blockIdx.x);
-      fast_final_block<true>(pods, gr, nd, b, prm, query_blocks, blockIdx.x, query_blocks, nchunks, tk_p1, filter_waves, tk_done, tb + filter_blocks);
+      fast_final_block<true>(pods, gr, nd, b, prm, query_blocks, blockIdx.x, query_blocks, nchunks, tk_p1, filter_waves, tk_done, tb + filter_blocks, p0, p1);
     } else if (param_blocks) {
       fast_query_thread<TS, false, false>(pods, gr, b, prm, blockIdx.x * kTblChunk + threadIdx.x, query_blocks * kTblChunk);
     } else {

@@ -164,6 +164,10 @@ struct BatchDev {
   const uint32_t* own_start;// [P] sharded contexts only: pods owned before queue position i (see k_owner_starts); owner = own_start[anchor] * nranks / P
   const uint32_t* gcount;   // [G] pods of the group in the resident queue (bs_pods_load / bs_pods_apply keep it): the thread whose add
   unsigned long long* admit64;  // [G] brings (pods seen << 32 | pods admitted) up to gcount closes the group — quorum without a last-block pass
+  // the whole-step launch's gang-aligned pod ranges (bs_pod_ranges.hpp, from bs_pods_load; run_fast sets them for k_fast_step_a<TS, true> only; null: 256
+  // pods per block, no gang closed in LDS).  One allocation: [G bytes, padded to words] 1: the gang is local | [pod blocks + 1] first pod of each pod
+  // block, then P | [P] first pod of the pod's gang when the gang is local, BS_INF otherwise (pod_ranges_of, bs_fast.hpp)
+  const uint32_t* pod_ranges;
   // BS_BATCH_HOST_RESULTS: mirrors of the results in pinned host memory, written by the last launch (null = off)
   uint8_t* h_pf_code; uint32_t* h_pf_first_k; int32_t* h_pf_leader; uint8_t* h_fl_code; uint32_t* h_fl_feasible; uint32_t* h_fl_slot;
   uint32_t* h_admit; uint8_t* h_ready; uint32_t* h_feas; uint64_t* h_rows; int32_t* h_tag; uint32_t hstride;

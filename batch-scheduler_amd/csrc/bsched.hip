@@ -27,6 +27,7 @@
 #include "bs_fdeny.hpp"
 #include "bs_seq.hpp"
 #include "bs_launch.hpp"
+#include "bs_pod_ranges.hpp"
 #ifdef BS_UNITY   // one translation unit (the probe builds: g_probe / g_seq_scan_ph are per translation unit)
 #include "tu_fast.hip"
 #include "tu_seq.hip"
@@ -276,6 +277,13 @@ struct bs_ctx {
   uint32_t test_timeout_after = 0;   // BS_TEST_HANDOVER_TIMEOUT=n (test hook): the n-th one-launch step reports a timed-out hand-over as the device would
   uint32_t tk_pods = 0, tk_tab = 0;  // values of ticket[8] / ticket[9] the next k_fast_step_a starts from (never reset: wrap-safe differences)
   uint32_t tk_p1 = 0, tk_done = 0;   // ... of the spread counter at kTkP1 (form 3: the pod blocks' first halves); tk_done: of the counter at kTkDone (large queues: every table / Filter block adds once)
+  // form 3's gang-aligned pod ranges (bs_pod_ranges.hpp): computed by bs_pods_load, dropped by bs_pods_apply (256 pods per block until the next load)
+  bool pod_ranges_on = true;         // BS_POD_RANGES=0: 256 pods per block always (A/B switch)
+  bool ranges_valid = false;         // (also dropped by a bs_groups_load that changes the group count: the local flags are per group)
+  uint32_t nranges = 0;
+  PodRanges h_ranges;
+  std::vector<uint32_t> h_pod_ranges;  // BatchDev::pod_ranges as uploaded (the copy reads it: rewritten only after ev_stage)
+  DevBuf d_pod_ranges;
   bool last_step_a = false;
   uint32_t scan_share_override = 0, no_fuse_filter = 0, early_forced = 0, target_waves = 8192, filter_waves = 8192, collect_stats = 0;
   uint32_t general_waves = 4096;     // scan grid cap of the general chain (tools/cold_sweep.py)
@@ -1107,6 +1115,7 @@ int bs_create(const bs_config* cfg, bs_ctx** out) {
   if (const char* e = std::getenv("BS_TP_FILTER")) c->tp_filter = (uint32_t)std::min(8, std::max(0, std::atoi(e)));
   if (const char* e = std::getenv("BS_TEST_HANDOVER_TIMEOUT")) c->test_timeout_after = (uint32_t)std::atoi(e);
   if (const char* e = std::getenv("BS_STEP_A")) { c->step_a_on = std::atoi(e) != 0; c->step_a_form = (uint32_t)std::atoi(e); }
+  if (const char* e = std::getenv("BS_POD_RANGES")) c->pod_ranges_on = std::atoi(e) != 0;
   if (const char* e = std::getenv("BS_STEP_SHARES")) c->step_shares = (uint32_t)std::min(32, std::max(1, std::atoi(e)));
   if (const char* e = std::getenv("BS_TP_SHARE")) c->tp_share = (uint32_t)std::min(64, std::max(1, std::atoi(e)));
   if (const char* e = std::getenv("BS_TP_FWAVES")) c->tp_fwaves = (uint32_t)std::max(1, std::atoi(e));
@@ -1354,6 +1363,7 @@ int bs_groups_load(bs_ctx* c, const bs_groups_soa* g) {
   HIPCHK(c, c->d_leader_epoch.reserve((n + 1) * 4));
   HIPCHK(c, c->d_panic_epoch.reserve(n + 1));
   if (G != c->G) { c->pairs_ready = false; c->dirs_ready = false; }   // the per-group arrays of the pod load are sized by G
+  if (G != c->G) c->ranges_valid = false;         // (the pod ranges' local flags are per group: 256 pods per block until the next bs_pods_load)
   c->G = G;
   if ((rc = layout_out(c))) return rc;
   c->n_uncaptured = 0;
@@ -1496,6 +1506,33 @@ static int resize_queue(bs_ctx* c, uint32_t P) {
   return reserve_pod_scratch(c, P);
 }
 
+// The whole-step launch's gang-aligned pod ranges (bs_pod_ranges.hpp): O(P) on the host, once per load — nothing per step.  Group ids at or
+// beyond G count as no group (never local).  The upload is ordered before the batches on the stream; the host copy it reads is only rewritten by
+// the next load, after the previous load's copies are through (ev_stage).
+static int load_pod_ranges(bs_ctx* c, const int32_t* group, uint32_t P) {
+  int rc;
+  c->ranges_valid = false;
+  if (!c->pod_ranges_on || !P) return BS_OK;
+  if (c->stage_busy && c->ev_stage) { HIPCHK(c, hipEventSynchronize(c->ev_stage)); c->stage_busy = false; }
+  const uint32_t G = c->G;
+  PodRanges& r = c->h_ranges;
+  pod_ranges(group, P, kTblChunk, G, r);
+  c->nranges = (uint32_t)r.start.size() - 1u;
+  // one first-reach word per pod block (reserve_pod_scratch sizes it for 256 pods per block; short ranges can need up to twice as many)
+  if (c->d_first_reach.cap < ((size_t)c->nranges + 2) * 8 && (rc = reserve_filled(c, c->d_first_reach, ((size_t)c->nranges + c->nranges / 4 + 2) * 8, 0xFF))) return rc;
+  // BatchDev::pod_ranges: [G local flags, padded to words] | [ranges + 1 starts] | [P first pods]
+  const size_t gw = (G + 3u) / 4u, words = gw + r.start.size() + P;
+  std::vector<uint32_t>& h = c->h_pod_ranges;
+  h.assign(words, 0u);
+  std::memcpy(h.data(), r.glocal.data(), r.glocal.size());
+  std::memcpy(h.data() + gw, r.start.data(), r.start.size() * 4);
+  std::memcpy(h.data() + gw + r.start.size(), r.lfirst.data(), (size_t)P * 4);
+  HIPCHK(c, c->d_pod_ranges.reserve(words * 4));
+  HIPCHK(c, hipMemcpyAsync(c->d_pod_ranges.p, h.data(), words * 4, hipMemcpyHostToDevice, c->stream));
+  c->ranges_valid = true;
+  return BS_OK;
+}
+
 int bs_pods_load(bs_ctx* c, const bs_pods_soa* pods) {
   if (!c || !pods) return BS_ERR_INVALID;
   int rc = use_device(c);
@@ -1503,6 +1540,7 @@ int bs_pods_load(bs_ctx* c, const bs_pods_soa* pods) {
   const uint32_t P = pods->p, L = c->L;
   if (P && (!pods->group || !pods->req || !pods->req_present || !pods->cls || !pods->owner || !pods->flags)) return BS_ERR_INVALID;
   const PodLayout l = pod_layout(P, L);
+  c->ranges_valid = false;
   // the caller's arrays ARE the mapped staging buffer (bs_pods_map): nothing to pack.  Pointers into the staging buffer that
   // do not match the mapping (another p, a stale view) would make the packing copy overlap itself: refused.
   const uint8_t* sb = reinterpret_cast<const uint8_t*>(c->h_stage);
@@ -1541,6 +1579,7 @@ int bs_pods_load(bs_ctx* c, const bs_pods_soa* pods) {
     }
     HIPCHK(c, hipMemcpyAsync(c->d_pack[0].p, st, l.in_bytes, hipMemcpyHostToDevice, c->stream));
   }
+  if ((rc = load_pod_ranges(c, pods->group, P))) return rc;
   // request classes, per-group minima and (group, class) pairs of the pods: three launches behind the upload
   // (reset | first half of the class builder | second half + pairs); K reaches the host through pinned memory
   rc = derive_pods(c, false);
@@ -1651,6 +1690,7 @@ int bs_pods_read(bs_ctx* c, const bs_pods_out* out) {
 int bs_pods_apply(bs_ctx* c, const bs_pods_delta* d) {
   if (!c || !d) return BS_ERR_INVALID;
   if (!c->have_pods) { c->last_error = "bs_pods_apply before bs_pods_load"; return BS_ERR_STATE; }
+  c->ranges_valid = false;                           // positions move on the device: 256 pods per block until the next bs_pods_load
   int rc = use_device(c, false);                     // a deferred group patch rides in this call's launch when it can
   if (rc) return rc;
   const uint32_t P = c->P, L = c->L, R = d->n_remove, F = d->n_flags, I = d->insert.p;
@@ -2085,7 +2125,6 @@ static int run_fast(bs_ctx* c, uint32_t stages) {
   const bool k_known = !c->kinfo_pending;
   const uint32_t k_step = k_known ? prm.k_host : ((c->step_a_form >= 3u && c->dirs_ready) ? c->k_bound : 0u);
   if (step_a_possible(c, stages, k_step, nchunks) && (c->step_a_form == 1u || c->dirs_ready || (c->batch_since_pods && c->pairs_ready && c->rep_valid && c->have_groups))) {
-    const uint32_t qb = cdiv(P, kTblChunk);
     const uint32_t K = k_step;
     const uint32_t nshares = std::max<uint32_t>(1, std::min<uint32_t>(c->step_shares, cdiv(K, 8)));
     const uint32_t fblocks = run_filter ? cdiv(std::min<uint32_t>(c->filter_waves, cdiv(2 * K, 64) * std::max<uint32_t>(1, cdiv(W, 2))), 4) : 0u;
@@ -2102,6 +2141,11 @@ static int run_fast(bs_ctx* c, uint32_t stages) {
     const uint32_t nch_nodes = std::max<uint32_t>(1, cdiv(N, 256));
     const uint32_t whole = (c->step_a_form >= 3u && pb && nch_nodes <= 64 && c->d_first_row64.p && c->d_scan_rec.p && c->d_feas_rec.p && c->d_chunk_rec.p) ? 1u : 0u;
     const uint32_t nchunks_s = whole ? nch_nodes : nchunks;
+    // the whole-step form's pod blocks take bs_pods_load's gang-aligned ranges (bs_pod_ranges.hpp) when the queue is still the loaded one; a gang inside
+    // one range is closed in LDS by its block (tally_tail_whole) wherever the returning-atomic quorum would run: tally with ready, no Filter-deny pass
+    const bool ranges = whole && c->ranges_valid && c->nranges && c->d_pod_ranges.p;
+    const uint32_t qb = ranges ? c->nranges : cdiv(P, kTblChunk);
+    if (ranges) b.pod_ranges = c->d_pod_ranges.as<uint32_t>();
     const uint32_t grid = qb + pb + nchunks_s * nshares + fblocks;
     if ((k_known || whole) && (int)grid <= step_a_residency(c, whole != 0)) {
       TIMED(c, BS_KERNEL_QUERY, {
