@@ -32,7 +32,17 @@ ABI_SYMBOLS = [
     "bs_seq_run", "bs_nodes_read", "bs_first_reach_hint",
     "bs_nodes_load_flat", "bs_groups_load_flat", "bs_groups_read_flat", "bs_pods_load_flat", "bs_pods_apply_flat", "bs_pods_read_flat",
     "bs_batch_read_flat", "bs_seq_run_flat", "bs_fit_build_flat",
+    "bs_bound_load", "bs_bound_count", "bs_preempt_run", "bs_bound_load_flat", "bs_preempt_run_flat",
 ]
+
+# bsh_phase codes (include/bsched_host.h) of the phases whose gangs PreemptRemovePod protects: Running and Scheduled (core.go:235-238)
+PROTECTED_PHASES = (2, 5)
+
+
+def group_protected(phases) -> np.ndarray:
+    """bs_preempt_run's group_protected[g] from each group's bsh_phase code: 1 where the phase is Scheduled or Running."""
+    ph = np.asarray(phases, dtype=np.int64).reshape(-1)
+    return np.isin(ph, PROTECTED_PHASES).astype(np.uint8)
 
 
 class BsError(RuntimeError):
@@ -150,6 +160,11 @@ def load_library(path: str | None = None):
     L.bs_batch_stats_get.argtypes = [vp, P(BatchStats)]
     L.bs_seq_run.argtypes = [vp, u32, P(SeqOut)]
     L.bs_nodes_read.argtypes = [vp, P(C.c_int64), P(u32)]
+    L.bs_bound_load.argtypes = [vp, P(soa.BoundStruct)]
+    L.bs_bound_count.argtypes = [vp, P(u32)]
+    L.bs_preempt_run.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), u32, P(soa.PreemptOutStruct)]
+    L.bs_bound_load_flat.argtypes = [vp, u32, P(u32), P(i32), P(C.c_int64), P(i32), P(C.c_int64), P(u32)]
+    L.bs_preempt_run_flat.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), u32, P(i32), P(u32), P(u32), P(u32), P(i32), P(C.c_int64), P(C.c_int64)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:
@@ -492,6 +507,39 @@ class Context:
         pres = np.zeros(max(self.n, 1), np.uint32)
         self._chk(self._lib.bs_nodes_read(self._h, _i64p(req), _u32p(pres)), "bs_nodes_read")
         return req[:, : self.n], pres[: self.n]
+
+    # -- preemption
+    def load_bound(self, bound: soa.Bound):
+        """bs_bound_load: the pods bound to or assumed on the loaded nodes (resident until the next load)."""
+        assert bound.req.shape[0] == self.L, f"context has {self.L} lanes, bound pods have {bound.req.shape[0]}"
+        st = bound.as_struct()
+        self._chk(self._lib.bs_bound_load(self._h, C.byref(st)), "bs_bound_load")
+
+    def bound_count(self) -> int:
+        b = C.c_uint32()
+        self._chk(self._lib.bs_bound_count(self._h, C.byref(b)), "bs_bound_count")
+        return int(b.value)
+
+    def preempt(self, pod_index, priority, group_protected=None, victim_cap: int = 16, stages: int = soa.STAGE_PREFILTER) -> dict:
+        """bs_preempt_run: the victim search for every preemptor (resident-queue pod pod_index[q] at priority[q]); group_protected[g]
+        from `group_protected(phases)`.  Returns node, n_candidates, n_victims, victims [count, victim_cap] (zero beyond
+        min(n_victims, cap)), top_priority, priority_sum, earliest_start."""
+        pi = np.ascontiguousarray(np.asarray(pod_index, np.uint32).reshape(-1))
+        pr = np.ascontiguousarray(np.asarray(priority, np.int32).reshape(-1))
+        assert pi.shape == pr.shape
+        q = pi.shape[0]
+        n = max(q, 1)
+        gp = None if group_protected is None else np.ascontiguousarray(np.asarray(group_protected, np.uint8).reshape(-1))
+        node, ncand, nv = np.full(n, -1, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        vic = np.zeros((n, max(victim_cap, 1)), np.uint32)
+        top, ssum, est = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.int64)
+        o = soa.PreemptOutStruct(node.ctypes.data_as(C.POINTER(C.c_int32)), _u32p(ncand), _u32p(nv), _u32p(vic),
+                                 top.ctypes.data_as(C.POINTER(C.c_int32)), _i64p(ssum), _i64p(est))
+        gptr = gp.ctypes.data_as(C.POINTER(C.c_uint8)) if gp is not None and gp.size else None
+        self._chk(self._lib.bs_preempt_run(self._h, stages, q, _u32p(pi), pr.ctypes.data_as(C.POINTER(C.c_int32)), gptr, victim_cap, C.byref(o)),
+                  "bs_preempt_run")
+        return dict(node=node[:q], n_candidates=ncand[:q], n_victims=nv[:q], victims=vic[:q, :victim_cap], top_priority=top[:q],
+                    priority_sum=ssum[:q], earliest_start=est[:q])
 
     # -- sharding / measurement
     def set_shard(self, rank: int, nranks: int):

@@ -35,4 +35,8 @@ struct SeqDev;
 struct SeqParams;
 void launch_seq(hipStream_t stream, uint32_t S, size_t lds, const PodsDev& pd, const GroupsDev& gr, const NodesDev& nd, const SeqDev& sq, const SeqParams& prm);
 
+// the preemption victim search (tu_preempt.hip): k_preempt_scan<S> over scan_grid, then k_preempt_pick<S>, one wave per preemptor
+struct PreemptDev;
+void launch_preempt(hipStream_t stream, uint32_t S, dim3 scan_grid, const NodesDev& nd, const PodsDev& pd, const PreemptDev& pe);
+
 }  // namespace bs

@@ -28,9 +28,11 @@
 #include "bs_seq.hpp"
 #include "bs_launch.hpp"
 #include "bs_pod_ranges.hpp"
+#include "bs_preempt.hpp"
 #ifdef BS_UNITY   // one translation unit (the probe builds: g_probe / g_seq_scan_ph are per translation unit)
 #include "tu_fast.hip"
 #include "tu_seq.hip"
+#include "tu_preempt.hip"
 #endif
 
 using namespace bs;
@@ -309,6 +311,12 @@ struct bs_ctx {
   bool fd_in_live = false;           // a fixed-point re-run: the chains honour d_fd_in
   uint32_t fd_iter = 0, fd_stages = 0, fd_seq_inv = 0;
   uint64_t n_fd_reruns = 0;          // fixed-point re-runs so far (bs_batch_stats_get)
+  // preemption (bs_preempt.hpp): the bound-pod table, CSR by node in importance order, in one allocation; per-call scratch
+  bool have_bound = false;
+  uint32_t bound_b = 0, bound_n = 0;  // entries, node count at the load
+  int32_t bound_max_group = -1;      // largest group index the table names (checked against the group count per call)
+  DevBuf d_bound, d_pre;
+  size_t off_boff = 0, off_bprio = 0, off_bstart = 0, off_bgroup = 0, off_bid = 0, off_breq = 0;
 };
 
 namespace {
@@ -3841,6 +3849,214 @@ int bs_batch_stats_get(bs_ctx* c, bs_batch_stats* out) {
   }
   c->collect_stats = 0;
   return BS_OK;
+}
+
+
+// -------------------------------------------------------------------------------------------------
+// gang-aware preemption (bs_preempt.hpp): the resident bound-pod table and the batched victim search
+// -------------------------------------------------------------------------------------------------
+int bs_bound_load(bs_ctx* c, const bs_bound_soa* bd) {
+  if (!c || !bd) return BS_ERR_INVALID;
+  if (!c->have_nodes) { c->last_error = "bs_bound_load before bs_nodes_load"; return BS_ERR_STATE; }
+  const uint32_t B = bd->b, N = c->N, L = c->L;
+  if (B > BS_BOUND_MAX) { c->last_error = "bound table larger than BS_BOUND_MAX"; return BS_ERR_CAPACITY; }
+  if (B && (!bd->node || !bd->priority || !bd->start_ns || !bd->group || !bd->req || !bd->req_present)) return BS_ERR_INVALID;
+  std::vector<uint32_t> cnt((size_t)N + 1, 0);
+  int32_t gmax = -1;
+  for (uint32_t i = 0; i < B; ++i) {
+    if (bd->node[i] >= N) { c->last_error = "bound pod on a node index >= n"; return BS_ERR_INVALID; }
+    if (bd->group[i] < BS_POD_GROUP_MISSING) { c->last_error = "bound pod group index below BS_POD_GROUP_MISSING"; return BS_ERR_INVALID; }
+    gmax = std::max(gmax, bd->group[i]);
+    ++cnt[bd->node[i] + 1];
+  }
+  for (uint32_t k = 0; k < N; ++k) {
+    if (cnt[k + 1] > BS_BOUND_MAX_PER_NODE) { c->last_error = "more than BS_BOUND_MAX_PER_NODE bound pods on one node"; return BS_ERR_CAPACITY; }
+    cnt[k + 1] += cnt[k];
+  }
+  int rc = use_device(c);
+  if (rc) return rc;
+  // every node's pods in importance order: priority descending, start ascending, caller id ascending
+  std::vector<uint32_t> order(B), fill(cnt.begin(), cnt.end() - 1);
+  for (uint32_t i = 0; i < B; ++i) order[fill[bd->node[i]]++] = i;
+  for (uint32_t k = 0; k < N; ++k)
+    std::sort(order.begin() + cnt[k], order.begin() + cnt[k + 1], [&](uint32_t a, uint32_t b) {
+      if (bd->priority[a] != bd->priority[b]) return bd->priority[a] > bd->priority[b];
+      if (bd->start_ns[a] != bd->start_ns[b]) return bd->start_ns[a] < bd->start_ns[b];
+      return a < b;
+    });
+  const size_t nB = std::max<uint32_t>(B, 1);
+  size_t o = 0;
+  c->off_boff = o; o = align256(o + ((size_t)N + 1) * 4);
+  c->off_bprio = o; o = align256(o + nB * 4);
+  c->off_bstart = o; o = align256(o + nB * 8);
+  c->off_bgroup = o; o = align256(o + nB * 4);
+  c->off_bid = o; o = align256(o + nB * 4);
+  c->off_breq = o; o = align256(o + nB * L * 8);
+  std::vector<uint8_t> h(o, 0);
+  std::memcpy(h.data() + c->off_boff, cnt.data(), ((size_t)N + 1) * 4);
+  int32_t* prio = reinterpret_cast<int32_t*>(h.data() + c->off_bprio);
+  int64_t* start = reinterpret_cast<int64_t*>(h.data() + c->off_bstart);
+  int32_t* grp = reinterpret_cast<int32_t*>(h.data() + c->off_bgroup);
+  uint32_t* id = reinterpret_cast<uint32_t*>(h.data() + c->off_bid);
+  int64_t* req = reinterpret_cast<int64_t*>(h.data() + c->off_breq);
+  for (uint32_t r = 0; r < B; ++r) {
+    const uint32_t i = order[r];
+    prio[r] = bd->priority[i];
+    start[r] = bd->start_ns[i];
+    grp[r] = bd->group[i];
+    id[r] = i;
+    for (uint32_t l = 0; l < L; ++l) {
+      int64_t v = bd->req[(size_t)l * B + i];
+      if (l == BS_LANE_PODS) v = 1;                                        // RemovePod: one pod less
+      else if (l >= BS_FIXED_LANES && !((bd->req_present[i] >> (l - BS_FIXED_LANES)) & 1u)) v = 0;   // no key: nothing to subtract
+      req[(size_t)l * nB + r] = v;
+    }
+  }
+  c->have_bound = false;
+  HIPCHK(c, c->d_bound.reserve(o));
+  HIPCHK(c, hipMemcpyAsync(c->d_bound.p, h.data(), o, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));             // (h is a local buffer)
+  c->bound_b = B;
+  c->bound_n = N;
+  c->bound_max_group = gmax;
+  c->have_bound = true;
+  return BS_OK;
+}
+
+int bs_bound_count(const bs_ctx* c, uint32_t* b_out) {
+  if (!c || !b_out) return BS_ERR_INVALID;
+  *b_out = c->have_bound ? c->bound_b : 0u;
+  return BS_OK;
+}
+
+int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority, const uint8_t* group_protected,
+                   uint32_t victim_cap, const bs_preempt_out* out) {
+  if (!c || !out) return BS_ERR_INVALID;
+  if (stages & ~BS_STAGE_PREFILTER) { c->last_error = "bs_preempt_run takes BS_STAGE_PREFILTER only (the plugin's Filter takes no part)"; return BS_ERR_INVALID; }
+  if (!c->have_nodes || !c->have_fit || !c->have_pods || !c->have_bound) {
+    c->last_error = "bs_preempt_run needs nodes, fit, pods and the bound table loaded";
+    return BS_ERR_STATE;
+  }
+  if (c->nranks > 1 || c->reduce_external) { c->last_error = "bs_preempt_run is single-rank only"; return BS_ERR_STATE; }
+  if (c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
+  if (count > BS_PREEMPT_MAX || (uint64_t)count * victim_cap > (1ull << 28)) return BS_ERR_CAPACITY;
+  if (count == 0) return BS_OK;
+  if (!pod_index || !priority || !out->node || !out->n_victims || (victim_cap && !out->victims) || (c->G && !group_protected)) return BS_ERR_INVALID;
+  if (c->bound_max_group >= (int32_t)c->G) { c->last_error = "the bound table names a group index >= the loaded group count"; return BS_ERR_INVALID; }
+  const uint32_t P = c->P, N = c->N, G = c->G;
+  for (uint32_t i = 0; i < count; ++i)
+    if (pod_index[i] >= P) { c->last_error = "preemptor pod index >= p"; return BS_ERR_INVALID; }
+  int rc = use_device(c);
+  if (rc) return rc;
+  // slots in priority-descending order (stable): the tile's highest priority bounds its lanes' victim suffixes
+  std::vector<uint32_t> perm(count);
+  for (uint32_t i = 0; i < count; ++i) perm[i] = i;
+  std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return priority[a] > priority[b]; });
+  const uint32_t tiles = cdiv(count, 64);
+  // node chunks: about 4096 waves in the first launch (16 per CU), at least one node per chunk
+  uint32_t nchunks = std::max<uint32_t>(1, std::min<uint32_t>(std::max<uint32_t>(N, 1), cdiv(4096, tiles)));
+  const uint32_t chunk_nodes = std::max<uint32_t>(1, cdiv(N, nchunks));
+  nchunks = std::max<uint32_t>(1, cdiv(N, chunk_nodes));
+  const size_t nQ = count, nG = std::max<uint32_t>(G, 1), nR = (size_t)nchunks * nQ, nV = std::max<size_t>((size_t)nQ * victim_cap, 1);
+  size_t o = 0;
+  const size_t o_spod = o; o = align256(o + nQ * 4);
+  const size_t o_sprio = o; o = align256(o + nQ * 4);
+  const size_t o_sorig = o; o = align256(o + nQ * 4);
+  const size_t o_gprot = o; o = align256(o + nG);
+  const size_t in_bytes = o;
+  const size_t o_rnode = o; o = align256(o + nR * 4);
+  const size_t o_rnv = o; o = align256(o + nR * 4);
+  const size_t o_rtop = o; o = align256(o + nR * 4);
+  const size_t o_rsum = o; o = align256(o + nR * 8);
+  const size_t o_rest = o; o = align256(o + nR * 8);
+  const size_t o_rncand = o; o = align256(o + nR * 4);
+  const size_t o_res = o;                                 // results: one D2H
+  const size_t o_node = o; o = align256(o + nQ * 4);
+  const size_t o_ncand = o; o = align256(o + nQ * 4);
+  const size_t o_nv = o; o = align256(o + nQ * 4);
+  const size_t o_top = o; o = align256(o + nQ * 4);
+  const size_t o_sum = o; o = align256(o + nQ * 8);
+  const size_t o_est = o; o = align256(o + nQ * 8);
+  const size_t o_vic = o; o = align256(o + nV * 4);
+  HIPCHK(c, c->d_pre.reserve(o));
+  std::vector<uint8_t> in(in_bytes, 0);
+  uint32_t* spod = reinterpret_cast<uint32_t*>(in.data() + o_spod);
+  int32_t* sprio = reinterpret_cast<int32_t*>(in.data() + o_sprio);
+  uint32_t* sorig = reinterpret_cast<uint32_t*>(in.data() + o_sorig);
+  for (uint32_t s = 0; s < count; ++s) {
+    spod[s] = pod_index[perm[s]];
+    sprio[s] = priority[perm[s]];
+    sorig[s] = perm[s];
+  }
+  if (G) std::memcpy(in.data() + o_gprot, group_protected, G);
+  uint8_t* base = c->d_pre.as<uint8_t>();
+  HIPCHK(c, hipMemcpyAsync(base, in.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
+  const uint8_t* bb = c->d_bound.as<uint8_t>();
+  PreemptDev pe{};
+  pe.boff = reinterpret_cast<const uint32_t*>(bb + c->off_boff);
+  pe.bprio = reinterpret_cast<const int32_t*>(bb + c->off_bprio);
+  pe.bstart = reinterpret_cast<const int64_t*>(bb + c->off_bstart);
+  pe.bgroup = reinterpret_cast<const int32_t*>(bb + c->off_bgroup);
+  pe.bid = reinterpret_cast<const uint32_t*>(bb + c->off_bid);
+  pe.breq = reinterpret_cast<const int64_t*>(bb + c->off_breq);
+  pe.bstride = std::max<uint32_t>(c->bound_b, 1);
+  pe.q = count;
+  pe.nchunks = nchunks;
+  pe.chunk_nodes = chunk_nodes;
+  pe.cap = victim_cap;
+  pe.spod = reinterpret_cast<const uint32_t*>(base + o_spod);
+  pe.sprio = reinterpret_cast<const int32_t*>(base + o_sprio);
+  pe.sorig = reinterpret_cast<const uint32_t*>(base + o_sorig);
+  pe.gprot = base + o_gprot;
+  pe.r_node = reinterpret_cast<int32_t*>(base + o_rnode);
+  pe.r_nv = reinterpret_cast<uint32_t*>(base + o_rnv);
+  pe.r_top = reinterpret_cast<int32_t*>(base + o_rtop);
+  pe.r_sum = reinterpret_cast<int64_t*>(base + o_rsum);
+  pe.r_est = reinterpret_cast<int64_t*>(base + o_rest);
+  pe.r_ncand = reinterpret_cast<uint32_t*>(base + o_rncand);
+  pe.o_node = reinterpret_cast<int32_t*>(base + o_node);
+  pe.o_ncand = reinterpret_cast<uint32_t*>(base + o_ncand);
+  pe.o_nv = reinterpret_cast<uint32_t*>(base + o_nv);
+  pe.o_top = reinterpret_cast<int32_t*>(base + o_top);
+  pe.o_sum = reinterpret_cast<int64_t*>(base + o_sum);
+  pe.o_est = reinterpret_cast<int64_t*>(base + o_est);
+  pe.o_victims = reinterpret_cast<uint32_t*>(base + o_vic);
+  launch_preempt(c->stream, c->S, dim3(tiles, nchunks), nodes_dev(c), pods_dev(c), pe);
+  LAUNCHCHK(c, BS_KERNEL_QUERY);
+  std::vector<uint8_t> res(o - o_res);
+  HIPCHK(c, hipMemcpyAsync(res.data(), base + o_res, res.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint8_t* rb = res.data() - o_res;
+  std::memcpy(out->node, rb + o_node, nQ * 4);
+  std::memcpy(out->n_victims, rb + o_nv, nQ * 4);
+  if (out->n_candidates) std::memcpy(out->n_candidates, rb + o_ncand, nQ * 4);
+  if (out->top_priority) std::memcpy(out->top_priority, rb + o_top, nQ * 4);
+  if (out->priority_sum) std::memcpy(out->priority_sum, rb + o_sum, nQ * 8);
+  if (out->earliest_start) std::memcpy(out->earliest_start, rb + o_est, nQ * 8);
+  if (victim_cap) {
+    // rows are written up to min(n_victims, cap); the rest of a row is unspecified: zero it for the caller
+    const uint32_t* nv = reinterpret_cast<const uint32_t*>(rb + o_nv);
+    const uint32_t* vic = reinterpret_cast<const uint32_t*>(rb + o_vic);
+    for (size_t q = 0; q < nQ; ++q) {
+      const uint32_t k = std::min(nv[q], victim_cap);
+      std::memcpy(out->victims + q * victim_cap, vic + q * victim_cap, (size_t)k * 4);
+      std::memset(out->victims + q * victim_cap + k, 0, (size_t)(victim_cap - k) * 4);
+    }
+  }
+  return BS_OK;
+}
+
+int bs_bound_load_flat(bs_ctx* c, uint32_t b, const uint32_t* node, const int32_t* priority, const int64_t* start_ns, const int32_t* group,
+                       const int64_t* req, const uint32_t* req_present) {
+  const bs_bound_soa bd{b, node, priority, start_ns, group, req, req_present};
+  return bs_bound_load(c, &bd);
+}
+
+int bs_preempt_run_flat(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority, const uint8_t* group_protected,
+                        uint32_t victim_cap, int32_t* node, uint32_t* n_candidates, uint32_t* n_victims, uint32_t* victims, int32_t* top_priority,
+                        int64_t* priority_sum, int64_t* earliest_start) {
+  const bs_preempt_out o{node, n_candidates, n_victims, victims, top_priority, priority_sum, earliest_start};
+  return bs_preempt_run(c, stages, count, pod_index, priority, group_protected, victim_cap, &o);
 }
 
 }  // extern "C"

@@ -330,6 +330,62 @@ class Pods:
         return out
 
 
+class BoundStruct(C.Structure):
+    """bs_bound_soa"""
+    _fields_ = [("b", C.c_uint32),
+                ("node", C.POINTER(C.c_uint32)),
+                ("priority", C.POINTER(C.c_int32)),
+                ("start_ns", C.POINTER(C.c_int64)),
+                ("group", C.POINTER(C.c_int32)),
+                ("req", C.POINTER(C.c_int64)),
+                ("req_present", C.POINTER(C.c_uint32))]
+
+
+class PreemptOutStruct(C.Structure):
+    """bs_preempt_out"""
+    _fields_ = [("node", C.POINTER(C.c_int32)),
+                ("n_candidates", C.POINTER(C.c_uint32)),
+                ("n_victims", C.POINTER(C.c_uint32)),
+                ("victims", C.POINTER(C.c_uint32)),
+                ("top_priority", C.POINTER(C.c_int32)),
+                ("priority_sum", C.POINTER(C.c_int64)),
+                ("earliest_start", C.POINTER(C.c_int64))]
+
+
+@dataclass
+class Bound:
+    """Pods bound to or assumed on nodes (bs_bound_load): what NodeInfo.Pods() holds, one entry per pod; the entry's index is its id."""
+    node: np.ndarray
+    priority: np.ndarray
+    start_ns: np.ndarray
+    group: np.ndarray
+    req: np.ndarray            # [L, b]
+    req_present: np.ndarray
+
+    def __post_init__(self):
+        self.node = _arr(self.node, np.uint32)
+        b = self.node.shape[0]
+        self.priority = _arr(self.priority, np.int32, (b,))
+        self.start_ns = _arr(self.start_ns, np.int64, (b,))
+        self.group = _arr(self.group, np.int32, (b,))
+        self.req = _arr(self.req, np.int64)
+        assert self.req.shape[1] == b
+        self.req_present = _arr(self.req_present, np.uint32, (b,))
+
+    @property
+    def b(self) -> int:
+        return self.node.shape[0]
+
+    def as_struct(self) -> BoundStruct:
+        return BoundStruct(self.b, _ptr(self.node, C.c_uint32), _ptr(self.priority, C.c_int32), _ptr(self.start_ns, C.c_int64),
+                           _ptr(self.group, C.c_int32), _ptr(self.req, C.c_int64), _ptr(self.req_present, C.c_uint32))
+
+    @staticmethod
+    def empty(b: int, lanes: int) -> "Bound":
+        return Bound(np.zeros(b, np.uint32), np.zeros(b, np.int32), np.zeros(b, np.int64), np.full(b, POD_NOT_GROUPED, np.int32),
+                     np.zeros((lanes, b), np.int64), np.zeros(b, np.uint32))
+
+
 @dataclass
 class BatchOut:
     """Host-side result arrays of one batch.

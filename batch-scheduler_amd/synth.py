@@ -336,3 +336,94 @@ def all_distinct(pods, nodes, k_lanes: int = 1):
             span = max(1, min(hi - lo - 1, step[j] * (p.p if j != 3 else 64)))
             p.req[j, :] = lo + 1 + (idx * step[j]) % span
     return p
+
+
+# ---------------------------------------------------------------------------------------------------
+# preemption scenes (bs_bound_load / bs_preempt_run): pods bound to nodes, node requests consistent with them.  Own streams
+# (seed ^ a salt), so nothing above draws differently.
+# ---------------------------------------------------------------------------------------------------
+PRIORITY_LEVELS = np.array([-(1 << 31), -1000, 0, 0, 100, 100, 1000, 2000000000, (1 << 31) - 1], np.int64)
+
+
+def make_bound(seed: int, nodes: int, groups: int, per_node=(20, 110), scalars: int = 1, unlisted: bool = True, flagged: float = 0.02,
+               levels=PRIORITY_LEVELS, starts: int = 6, missing: float = 0.04, online: float = 0.3):
+    """-> (Bound, Nodes): `per_node` pods (an int, or an inclusive (lo, hi) range) bound on each of `nodes` nodes, priorities drawn
+    from `levels` (int32 extremes, many ties), `starts` distinct start times (ties), groups: `online` share ungrouped, `missing`
+    share BS_POD_GROUP_MISSING, the rest 0..groups-1.  Node requests = the sum of the bound pods (pods lane: their count) plus, with
+    `unlisted`, some load no listed pod accounts for; allocatable leaves the nodes nearly full, so that preemption has work."""
+    st = lambda k: Stream(seed ^ 0x5EED_B0D, k)                      # noqa: E731
+    L = 4 + scalars
+    lo, hi = (per_node, per_node) if np.isscalar(per_node) else per_node
+    cnt = st(1).integers(nodes, lo, hi) if nodes else np.zeros(0, np.int64)
+    b = int(cnt.sum())
+    node = np.repeat(np.arange(nodes, dtype=np.uint32), cnt)
+    prio = np.asarray(levels, np.int64)[st(2).integers(b, 0, len(levels) - 1)].astype(np.int32) if b else np.zeros(0, np.int32)
+    start = (st(3).integers(b, 0, starts - 1) * 1_000_000_000).astype(np.int64) if b else np.zeros(0, np.int64)
+    u = st(4).uniform(b)
+    grp = np.where(u < online, soa.POD_NOT_GROUPED, np.where(u < online + missing, soa.POD_GROUP_MISSING,
+                                                              st(5).integers(b, 0, max(groups - 1, 0)) if groups else soa.POD_NOT_GROUPED))
+    if not groups:
+        grp = np.where(grp >= 0, soa.POD_NOT_GROUPED, grp)
+    req = np.zeros((L, b), np.int64)
+    req[0] = st(6).choice(b, [100, 250, 500, 1000, 2000]) if b else 0
+    req[1] = (st(7).choice(b, [1, 2, 4]) * GI // 4) if b else 0
+    req[2] = np.where(st(8).uniform(b) < 0.3, GI, 0) if b else 0
+    req[3] = 1
+    pres = np.zeros(b, np.uint32)
+    for s in range(scalars):
+        has = st(9 + s).uniform(b) < 0.3
+        pres |= (has.astype(np.uint32) << np.uint32(s))
+        req[4 + s] = np.where(has, st(30 + s).integers(b, 0, 2), 0)
+    bound = soa.Bound(node, prio, start, grp.astype(np.int32), req, pres)
+    # node requests: the listed pods' sums (+ unlisted load), allocatable a little above
+    rq = np.zeros((L, nodes), np.int64)
+    for j in range(L):
+        rq[j] = np.bincount(node, weights=None if j == 3 else req[j], minlength=nodes).astype(np.int64) if b else 0
+    rp = np.zeros(nodes, np.uint32)
+    for s in range(scalars):
+        rp |= (np.bincount(node, weights=((pres >> np.uint32(s)) & 1).astype(np.float64), minlength=nodes) > 0).astype(np.uint32) << np.uint32(s)
+    if unlisted:
+        rq[0] += st(50).integers(nodes, 0, 2000)
+        rq[1] += st(51).integers(nodes, 0, 4) * (GI // 4)
+        rq[3] += st(52).integers(nodes, 0, 3)
+    al = np.zeros((L, nodes), np.int64)
+    al[0] = rq[0] + st(53).integers(nodes, -500, 1500)
+    al[1] = rq[1] + st(54).integers(nodes, -1, 4) * (GI // 4)
+    al[2] = rq[2] + st(55).integers(nodes, 0, 3) * GI
+    al[3] = np.maximum(rq[3] + st(56).integers(nodes, -1, 3), 1)
+    ap = np.zeros(nodes, np.uint32)
+    for s in range(scalars):
+        has = st(60 + s).uniform(nodes) < 0.7
+        ap |= has.astype(np.uint32) << np.uint32(s)
+        al[4 + s] = np.where(has, rq[4 + s] + st(70 + s).integers(nodes, 0, 2), 0)
+    fl = np.zeros(nodes, np.uint8)
+    f = st(80).uniform(nodes)
+    fl[f < flagged] = soa.NODE_UNSCHEDULABLE
+    fl[(f >= flagged) & (f < 1.5 * flagged)] = soa.NODE_TAINT_ERR
+    return bound, soa.Nodes(al, rq, ap, rp, fl)
+
+
+def make_preemptors(seed: int, q: int, p: int, groups: int, scalars: int = 1, classes: int = 4, levels=PRIORITY_LEVELS):
+    """-> (Pods [p], pod_index [q], priority [q]): a pending queue of p pods (ungrouped, missing and grouped, small requests) and q
+    preemptors drawn from it (repeats allowed) with priorities from `levels`."""
+    st = lambda k: Stream(seed ^ 0x0FF_1CE, k)                       # noqa: E731
+    L = 4 + scalars
+    u = st(1).uniform(p)
+    grp = np.where(u < 0.3, soa.POD_NOT_GROUPED, np.where(u < 0.35, soa.POD_GROUP_MISSING,
+                                                           st(2).integers(p, 0, max(groups - 1, 0)) if groups else soa.POD_NOT_GROUPED))
+    if not groups:
+        grp = np.where(grp >= 0, soa.POD_NOT_GROUPED, grp)
+    req = np.zeros((L, p), np.int64)
+    req[0] = st(3).choice(p, [0, 250, 1000, 3000])
+    req[1] = st(4).choice(p, [0, 1, 2, 8]) * GI // 4
+    req[2] = np.where(st(5).uniform(p) < 0.2, GI, 0)
+    pres = np.zeros(p, np.uint32)
+    for s in range(scalars):
+        has = st(6 + s).uniform(p) < 0.25
+        pres |= has.astype(np.uint32) << np.uint32(s)
+        req[4 + s] = np.where(has, st(20 + s).integers(p, 0, 2), 0)
+    cls = st(40).integers(p, 0, classes - 1).astype(np.uint32)
+    pods = soa.Pods(grp.astype(np.int32), req, pres, cls, np.zeros(p, np.uint64), np.zeros(p, np.uint8))
+    pod_index = st(41).integers(q, 0, p - 1).astype(np.uint32)
+    priority = np.asarray(levels, np.int64)[st(42).integers(q, 0, len(levels) - 1)].astype(np.int32)
+    return pods, pod_index, priority

@@ -542,6 +542,77 @@ int bs_seq_run(bs_ctx* ctx, uint32_t stages, bs_seq_out* out);
  * requested[L][n] lane-major, requested_present[n]; n = bs_nodes_count. */
 int bs_nodes_read(bs_ctx* ctx, int64_t* requested, uint32_t* requested_present);
 
+/* ---- gang-aware preemption: the victim search, batched ------------------------------------------------------------------
+ * The path of a pod that passed PreFilter and found no node.  The plugin's one hook there is PreFilterExtensions.RemovePod
+ * (batchscheduler.go:116-147) -> ScheduleOperation.PreemptRemovePod (core.go:197-260; AddPod -> PreemptAddPod, :194-196, always
+ * succeeds); upstream's preemption of k8s v1.17.5 (go.mod:102, not vendored) calls it from generic_scheduler.go: selectVictimsOnNode
+ * removes every lower-priority pod of a node through RunPreFilterExtensionRemovePod, checks the fit and reprieves victims in
+ * importance order, pickOneNodeForPreemption picks the node.  bs_preempt_run answers that search for `count` preemptors at once.
+ * Each preemptor is answered ON ITS OWN against the context's current state (the node requests as loads, applies, assumes and
+ * bs_seq_run left them, and the bound-pod table below), as upstream runs preemption for one pod per scheduling cycle.
+ * For preemptor q (resident-queue pod pod_index[q]: request lanes, req_present, fit class cls, group) with priority P = priority[q],
+ * on every node k:
+ *   1. skipped: k has any BS_NODE_* flag, or its checkFit bit for cls is clear (bs_seq_run's first-fit node rule; upstream's
+ *      unresolvable predicates, nodesWherePreemptionMightHelp).
+ *   2. potential victims: the bound pods of k with priority < P (equal priority never is a victim).
+ *   3. every potential victim goes through the policy; ONE refusal drops the node, even for a pod that would later be reprieved
+ *      (removePod errors, selectVictimsOnNode returns false).  Removal of victim v is allowed when:
+ *        v not grouped (BS_POD_NOT_GROUPED)        iff q is not grouped either (online preempts online, core.go:211-218)
+ *        v group BS_POD_GROUP_MISSING              never (core.go:223-225; the same-name test of :251 compares against "")
+ *        v's group protected (phase Scheduled or Running, group_protected[g] != 0)   never (core.go:235-238, :245-247)
+ *        otherwise                                 iff q is not grouped, or q's group index differs from v's (core.go:250-256)
+ *   4. fit after removing all: the node's requests minus every potential victim (pods lane - 1 per victim; scalar lanes as
+ *      NodeInfo.RemovePod: an absent key counts as 0) must hold the pod under bs_seq_run's fit rule (oracle/bs_oracle_seq.c:62-78
+ *      holds()); otherwise the node is no candidate.
+ *   5. reprieve: the potential victims in importance order — priority descending, start time ascending (MoreImportantPod), bound-pod
+ *      id ascending (this library's tie rule: upstream's sort.Slice is not stable) — are added back one by one; a pod after which the
+ *      preemptor no longer holds is taken out again and is a victim.  Victims come out in importance order; with no PDBs every
+ *      victim is "non-violating".
+ *   6. node pick (pickOneNodeForPreemption; upstream iterates a Go map, so its ties are random — here every tie goes to the lowest
+ *      node index): a candidate without victims wins outright (the lowest index among several); otherwise the smallest key
+ *      (highest victim priority, sum over victims of priority + 2^31, victim count, the LATEST "earliest start among the victims of
+ *      highest priority" (GetEarliestPodStartTime), node index).
+ * Restrictions: BS_STAGE_FILTER is refused (BS_ERR_INVALID: the plugin's Filter takes no part in the fit test; the shipped config
+ * does not enable Filter).  No nominated pods, no PDBs.  podEligibleToPreemptOthers (PreemptionPolicy Never, terminating pods on the
+ * nominated node) is the caller's business, and so is the choice of preemptors: upstream preempts only for a pod that passed
+ * PreFilter and then found no node (a PreFilter rejection is not a FitError).  Sharded contexts: BS_ERR_STATE, as bs_seq_run.
+ * The call is a what-if: node requests, groups and the queue are left as they were.  Synchronous. */
+#define BS_BOUND_MAX          (1u << 24)   /* entries of the bound-pod table                          */
+#define BS_BOUND_MAX_PER_NODE 2048u        /* bound pods per node                                     */
+#define BS_PREEMPT_MAX        (1u << 20)   /* preemptors per bs_preempt_run; count * victim_cap <= 2^28 */
+/* Pods bound to or assumed on nodes (what NodeInfo.Pods() holds).  Resident until the next bs_bound_load; valid while the node list
+ * keeps the count it had at the load (bs_preempt_run answers BS_ERR_STATE otherwise: reload it after list surgery).  Validated as a
+ * whole: node < n of the loaded nodes, group >= 0 or one of the two sentinels (BS_ERR_INVALID); more than BS_BOUND_MAX entries or
+ * BS_BOUND_MAX_PER_NODE on one node: BS_ERR_CAPACITY.  Needs bs_nodes_load first (BS_ERR_STATE).  A group index must be below the
+ * group count of the state loaded when bs_preempt_run is called (BS_ERR_INVALID there). */
+typedef struct bs_bound_soa {
+  uint32_t b;
+  const uint32_t* node;        /* [b] node list index                                                                     */
+  const int32_t*  priority;    /* [b] podutil.GetPodPriority                                                              */
+  const int64_t*  start_ns;    /* [b] Status.StartTime (the caller puts "now" for a nil StartTime, as GetPodStartTime does) */
+  const int32_t*  group;       /* [b] group index, BS_POD_NOT_GROUPED or BS_POD_GROUP_MISSING                              */
+  const int64_t*  req;         /* [L][b] what NodeInfo counted for the pod (the pods lane is ignored: one pod)            */
+  const uint32_t* req_present; /* [b] scalar keys of that request                                                         */
+} bs_bound_soa;
+int bs_bound_load(bs_ctx* ctx, const bs_bound_soa* bound);
+int bs_bound_count(const bs_ctx* ctx, uint32_t* b_out);
+/* Results per preemptor q (caller's order).  node and n_victims are required, the other arrays may be NULL; victims is required when
+ * victim_cap > 0. */
+typedef struct bs_preempt_out {
+  int32_t*  node;              /* [count] chosen node, -1 = none                                                          */
+  uint32_t* n_candidates;      /* [count] nodes that passed steps 1-4                                                     */
+  uint32_t* n_victims;         /* [count] victims on the chosen node (the true count: may exceed victim_cap)              */
+  uint32_t* victims;           /* [count][victim_cap] bound-pod ids (the caller's numbering), importance order            */
+  int32_t*  top_priority;      /* [count] pick key of the chosen node: highest victim priority (0 without victims)        */
+  int64_t*  priority_sum;      /* [count] ... sum over victims of priority + 2^31                                         */
+  int64_t*  earliest_start;    /* [count] ... earliest start among the victims of highest priority                        */
+} bs_preempt_out;
+/* stages: 0 or BS_STAGE_PREFILTER (room for a Filter-aware version).  pod_index[count] < p (resident queue), priority[count],
+ * group_protected[g] (g = loaded group count; may be NULL when g == 0).  BS_ERR_STATE when nodes, fit masks, pods or the bound table
+ * are not loaded; BS_ERR_INVALID for a pod index >= p, filter stages, NULL required arrays. */
+int bs_preempt_run(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
+                   const uint8_t* group_protected, uint32_t victim_cap, const bs_preempt_out* out);
+
 /* ---- batched queue ordering ---------------------------------------- */
 /* The permutation that sorts the pending pods the way the scheduling queue does through ScheduleOperation.Compare
  * (core.go:368-411; Less, batchscheduler.go:214): perm_out[k] = index of the pod at queue position k.  Key, ascending:
@@ -611,7 +682,7 @@ int bs_batch_finish(bs_ctx* ctx);
 /* ---- flat-argument forms (the cgo binding) -----------------------------------------------------------------------
  * cgo's pointer-passing rule: a Go pointer handed to C may not point at Go memory that itself holds Go pointers.  A
  * Go-allocated C.bs_nodes_soa / bs_groups_soa / bs_pods_soa / bs_pods_delta / bs_batch_out / bs_seq_out / bs_node_labels /
- * bs_fit_templates whose fields point at Go slices is exactly that, and `C.bs_nodes_load(ctx, &soa)` panics under the default
+ * bs_fit_templates / bs_bound_soa / bs_preempt_out whose fields point at Go slices is exactly that, and `C.bs_nodes_load(ctx, &soa)` panics under the default
  * cgocheck ("cgo argument has Go pointer to Go pointer").  The entry points below take every array as its OWN argument —
  * scalars and direct pointers to pointer-free arrays only — and forward to the struct forms on the C side; semantics, return
  * codes and NULL conventions are those of the struct forms.  The Go shim (go/pkg/scheduler/core) calls only these for the
@@ -650,6 +721,13 @@ int bs_fit_build_flat(bs_ctx* ctx, uint32_t n, const uint32_t* name, const uint3
                       uint32_t fd_count, const uint32_t* fd_key, const uint8_t* fd_op, const uint32_t* fd_val_off, const uint32_t* fd_val,
                       const int64_t* fd_val_int, const uint8_t* fd_val_int_ok,
                       const uint32_t* tol_off, const uint32_t* tol_key, const uint32_t* tol_val, const uint8_t* tol_op, const uint8_t* tol_effect);
+
+/* bs_bound_load / bs_preempt_run (bs_preempt_out's arrays one by one) */
+int bs_bound_load_flat(bs_ctx* ctx, uint32_t b, const uint32_t* node, const int32_t* priority, const int64_t* start_ns, const int32_t* group,
+                       const int64_t* req, const uint32_t* req_present);
+int bs_preempt_run_flat(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority, const uint8_t* group_protected,
+                        uint32_t victim_cap, int32_t* node, uint32_t* n_candidates, uint32_t* n_victims, uint32_t* victims, int32_t* top_priority,
+                        int64_t* priority_sum, int64_t* earliest_start);
 
 /* ---- measurement ------------------------------------------------------------------ */
 #define BS_KERNEL_PREPASS   0u

@@ -1,0 +1,250 @@
+"""GPU tests of bs_bound_load / bs_preempt_run (csrc/bs_preempt.hpp): every output bit-exact against the numpy restatement of
+tests/preempt_ref.py (itself held against an object-level restatement of core.go:203-260 and upstream's selectVictimsOnNode /
+pickOneNodeForPreemption by tests/test_preempt_cpu.py), the hand known answers on the device, relations (the free first fit equals
+bs_seq_run's, the chosen node holds the pod once its victims leave, every victim is needed), no side effects, error codes and one
+full-size case."""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+
+import preempt_ref as pr
+from preempt_scenes import groups_for, hand_kats, kat_scene, random_scene
+
+pytestmark = pytest.mark.gpu
+
+bsa = importlib.import_module("batch-scheduler_amd")
+soa, synth = bsa.soa, bsa.synth
+MAX_PER_NODE = 2048                                     # include/bsched.h BS_BOUND_MAX_PER_NODE
+FIELDS = ("node", "n_candidates", "n_victims", "victims", "top_priority", "priority_sum", "earliest_start")
+
+
+def _ctx(sc):
+    ctx = bsa.Context(scalar_lanes=sc["S"], device=0)
+    ctx.load_nodes(sc["nodes"], sc["fit"])
+    ctx.load_groups(groups_for(sc))
+    ctx.load_pods(sc["pods"])
+    ctx.load_bound(sc["bound"])
+    return ctx
+
+
+def _compare(got, exp, where):
+    for f in FIELDS:
+        if not np.array_equal(got[f], exp[f]):
+            bad = np.nonzero(np.any((got[f] != exp[f]).reshape(len(got[f]), -1), axis=1))[0]
+            i = int(bad[0])
+            pytest.fail(f"{where}: {f} differs at preemptor {i} of {len(bad)} bad: got {got[f][i]} expected {exp[f][i]} "
+                        f"(node {got['node'][i]} vs {exp['node'][i]})")
+
+
+def _run_and_check(sc, cap, where):
+    with _ctx(sc) as ctx:
+        got = ctx.preempt(sc["pod_index"], sc["priority"], sc["protected"], victim_cap=cap)
+    exp = pr.preempt_np(pr.Prep(sc["nodes"], sc["bound"], sc["S"]), sc["fit"], sc["pods"], sc["pod_index"], sc["priority"], sc["protected"], cap)
+    _compare(got, exp, where)
+    return got
+
+
+@pytest.mark.parametrize("sc", hand_kats(), ids=lambda s: s["name"])
+def test_hand_known_answers_on_device(sc):
+    from test_preempt_cpu import check_kat
+    s = kat_scene(sc)
+    with _ctx(s) as ctx:
+        got = ctx.preempt(s["pod_index"], s["priority"], s["protected"], victim_cap=8)
+    check_kat(got, sc, f"device {sc['name']} ({sc['cite']})")
+
+
+# (S, nodes, bound pods per node, preemptors): the sizes around a wave (63-65), the 255-257 and the documented maximum per node, one node
+CASES = [
+    (0, 1, (0, 0), 1), (1, 1, (255, 257), 65), (4, 1, (1, 1), 64), (12, 1, (63, 65), 1024),
+    (0, 63, (63, 65), 64), (1, 64, (0, 1), 65), (4, 65, (255, 257), 64), (12, 64, (2, 9), 1024),
+    (0, 1000, (0, 3), 1024), (1, 1000, (20, 40), 65), (4, 1000, (63, 65), 64), (12, 1000, (5, 12), 65),
+    (1, 3, (MAX_PER_NODE, MAX_PER_NODE), 64), (0, 5000, (0, 2), 64), (12, 5000, (1, 4), 1),
+]
+
+
+@pytest.mark.parametrize("S,n,per,q", CASES)
+def test_random_scenes_bit_exact(S, n, per, q):
+    sc = random_scene(7000 + 13 * n + S, n=n, per_node=per, S=S, q=q, groups=9, p=97, fit_density=0.6)
+    got = _run_and_check(sc, cap=6, where=f"S={S} n={n} per={per} q={q}")
+    if n >= 64 and q >= 64:
+        assert np.any(got["node"] >= 0)
+
+
+def test_documented_per_node_maximum():
+    import re
+    import os
+    h = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "bsched.h")).read()
+    assert int(re.search(r"#define BS_BOUND_MAX_PER_NODE (\d+)u", h).group(1)) == MAX_PER_NODE
+
+
+@pytest.mark.parametrize("S", [0, 1, 4, 12])
+def test_sparse_fit_and_flags_all_group_kinds(S):
+    sc = random_scene(31 + S, n=300, per_node=(0, 20), S=S, q=65, groups=5, p=50, fit_density=0.1, protected_share=0.5, flagged=0.3)
+    _run_and_check(sc, cap=32, where=f"sparse S={S}")
+
+
+def test_extreme_priorities_and_start_ties():
+    lv = np.array([-(1 << 31), -(1 << 31) + 1, (1 << 31) - 2, (1 << 31) - 1], np.int64)
+    sc = random_scene(99, n=200, per_node=(10, 40), S=1, q=1024, groups=4, p=60, levels=lv)
+    _run_and_check(sc, cap=64, where="extreme priorities")
+
+
+def test_full_size_cfg3_nodes_1024_preemptors():
+    cfg = synth.CONFIGS["cfg3"]
+    sc = random_scene(20260921, n=cfg["nodes"], per_node=(20, 110), S=cfg["scalars"], q=1024, groups=200, p=2000, classes=8, fit_density=0.95)
+    got = _run_and_check(sc, cap=16, where="cfg3 full size")
+    assert np.any(got["n_victims"] > 0) and np.any(got["node"] < 0)
+
+
+# ---- relations
+def _online_scene(seed, n=400, S=1, q=128):
+    sc = random_scene(seed, n=n, per_node=(0, 12), S=S, q=q, groups=3, p=64)
+    sc["bound"].group[:] = soa.POD_NOT_GROUPED            # online preempts online: nothing is ever refused
+    sc["pods"].group[:] = soa.POD_NOT_GROUPED
+    return sc
+
+
+def test_free_fit_is_bs_seq_runs_first_fit():
+    sc = _online_scene(5)
+    with _ctx(sc) as ctx:
+        got = ctx.preempt(sc["pod_index"], sc["priority"], sc["protected"], victim_cap=4)
+    free = np.nonzero((got["node"] >= 0) & (got["n_victims"] == 0))[0]
+    assert free.size >= 8
+    for i in free[:24]:
+        one = sc["pods"].take(np.array([sc["pod_index"][i]]))
+        with bsa.Context(scalar_lanes=sc["S"], device=0) as c2:
+            c2.load_nodes(sc["nodes"], sc["fit"])
+            c2.load_groups(groups_for(sc))
+            c2.load_pods(one)
+            r = c2.seq_run(soa.STAGE_PREFILTER)
+        assert int(r["pod_node"][0]) == int(got["node"][i]), f"preemptor {i}"
+
+
+def test_victims_are_enough_and_each_one_needed():
+    sc = random_scene(77, n=500, per_node=(5, 30), S=2, q=256, groups=6, p=80)
+    cap = 64
+    with _ctx(sc) as ctx:
+        got = ctx.preempt(sc["pod_index"], sc["priority"], sc["protected"], victim_cap=cap)
+    prep = pr.Prep(sc["nodes"], sc["bound"], sc["S"])
+    eff = prep.req.reshape(prep.L, -1)                      # [L, N*M] effective requests of the padded table
+    flat_id = prep.id.reshape(-1)
+    valid = prep.valid.reshape(-1)
+    pos = {int(flat_id[j]): j for j in np.nonzero(valid)[0]}
+    checked = 0
+    for i in np.nonzero((got["node"] >= 0) & (got["n_victims"] > 0) & (got["n_victims"] <= cap))[0]:
+        k, pi = int(got["node"][i]), int(sc["pod_index"][i])
+        req, pres = sc["pods"].req[:, pi].astype(np.int64), int(sc["pods"].req_present[pi])
+        vic = [pos[int(v)] for v in pr.victims_of(got, i)]
+        assert all(prep.prio.reshape(-1)[j] < sc["priority"][i] for j in vic)
+        base = prep.cur0[:, k:k + 1] - eff[:, vic].sum(axis=1, keepdims=True)
+        al, ap = prep.alloc[:, k:k + 1], prep.apres[k:k + 1]
+        assert pr.holds_np(al, ap, base, req, pres, sc["S"])[0], f"preemptor {i}: does not hold without its victims"
+        for j in vic:
+            assert not pr.holds_np(al, ap, base + eff[:, j:j + 1], req, pres, sc["S"])[0], f"preemptor {i}: victim {flat_id[j]} not needed"
+        checked += 1
+    assert checked >= 10
+
+
+def test_no_side_effects():
+    nodes, fit, groups, pods, _ = synth.make("tiny", "warm")
+    bound, _ = synth.make_bound(3, nodes.n, groups.g, (0, 20), 1)
+    pidx = np.arange(0, pods.p, 3, dtype=np.uint32)
+    prio = np.full(pidx.size, 1000, np.int32)
+    outs = []
+    for do_preempt in (False, True):
+        with bsa.Context(scalar_lanes=1, device=0) as ctx:
+            ctx.load_nodes(nodes, fit)
+            ctx.load_groups(groups)
+            ctx.load_pods(pods)
+            ctx.load_bound(bound)
+            req0, pres0 = ctx.read_node_requests()
+            g0 = ctx.read_groups()
+            if do_preempt:
+                r = ctx.preempt(pidx, prio, np.zeros(groups.g, np.uint8), victim_cap=8)
+                assert np.any(r["node"] >= 0)
+                req1, pres1 = ctx.read_node_requests()
+                assert np.array_equal(req0, req1) and np.array_equal(pres0, pres1)
+                assert ctx.read_groups().state_equal(g0)
+                assert ctx.read_pods().equal(pods)
+            outs.append(ctx.batch(soa.STAGE_ALL))
+    for name in ("pf_code", "pf_first_k", "pf_leader", "fl_code", "fl_feasible", "fl_bitmap", "group_admit", "group_ready"):
+        assert np.array_equal(getattr(outs[0], name), getattr(outs[1], name)), name
+
+
+def test_flat_forms_equal_struct_forms():
+    sc = random_scene(12, n=100, per_node=(0, 15), S=1, q=65, groups=4, p=30)
+    with _ctx(sc) as ctx:
+        a = ctx.preempt(sc["pod_index"], sc["priority"], sc["protected"], victim_cap=5)
+        lib, b = ctx._lib, sc["bound"]
+        u32, i32, i64 = (lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))), (lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))), \
+            (lambda x: x.ctypes.data_as(C.POINTER(C.c_int64)))
+        assert lib.bs_bound_load_flat(ctx._h, b.b, u32(b.node), i32(b.priority), i64(b.start_ns), i32(b.group), i64(b.req), u32(b.req_present)) == 0
+        assert ctx.bound_count() == b.b
+        q = len(sc["pod_index"])
+        node, nc, nv = np.zeros(q, np.int32), np.zeros(q, np.uint32), np.zeros(q, np.uint32)
+        vic, top, ssum, est = np.zeros((q, 5), np.uint32), np.zeros(q, np.int32), np.zeros(q, np.int64), np.zeros(q, np.int64)
+        rc = lib.bs_preempt_run_flat(ctx._h, soa.STAGE_PREFILTER, q, u32(sc["pod_index"]), i32(sc["priority"]),
+                                     sc["protected"].ctypes.data_as(C.POINTER(C.c_uint8)), 5, i32(node), u32(nc), u32(nv), u32(vic), i32(top),
+                                     i64(ssum), i64(est))
+        assert rc == 0
+    assert np.array_equal(a["node"], node) and np.array_equal(a["n_candidates"], nc) and np.array_equal(a["n_victims"], nv)
+    assert np.array_equal(a["victims"], vic) and np.array_equal(a["top_priority"], top)
+    assert np.array_equal(a["priority_sum"], ssum) and np.array_equal(a["earliest_start"], est)
+
+
+def test_error_codes():
+    sc = random_scene(4, n=50, per_node=(0, 5), S=1, q=8, groups=4, p=20)
+    B = bsa.BsError
+    with bsa.Context(scalar_lanes=1, device=0) as ctx:
+        with pytest.raises(B) as e:
+            ctx.load_bound(sc["bound"])                              # before the nodes
+        assert e.value.status == -4
+        ctx.load_nodes(sc["nodes"], sc["fit"])
+        ctx.load_groups(groups_for(sc))
+        ctx.load_pods(sc["pods"])
+        with pytest.raises(B) as e:
+            ctx.preempt(sc["pod_index"], sc["priority"], sc["protected"])   # no bound table
+        assert e.value.status == -4
+        assert ctx.bound_count() == 0
+        bad = soa.Bound(sc["bound"].node.copy(), sc["bound"].priority, sc["bound"].start_ns, sc["bound"].group, sc["bound"].req, sc["bound"].req_present)
+        bad.node[0] = 50
+        with pytest.raises(B) as e:
+            ctx.load_bound(bad)
+        assert e.value.status == -1
+        bad = soa.Bound(sc["bound"].node, sc["bound"].priority, sc["bound"].start_ns, sc["bound"].group.copy(), sc["bound"].req, sc["bound"].req_present)
+        bad.group[0] = -3
+        with pytest.raises(B) as e:
+            ctx.load_bound(bad)
+        assert e.value.status == -1
+        big = soa.Bound.empty(2049, 5)
+        with pytest.raises(B) as e:
+            ctx.load_bound(big)                                      # 2049 pods on node 0
+        assert e.value.status == -5
+        ctx.load_bound(sc["bound"])
+        assert ctx.bound_count() == sc["bound"].b
+        for stages in (soa.STAGE_FILTER, soa.STAGE_PREFILTER | soa.STAGE_FILTER):
+            with pytest.raises(B) as e:
+                ctx.preempt(sc["pod_index"], sc["priority"], sc["protected"], stages=stages)
+            assert e.value.status == -1
+        with pytest.raises(B) as e:
+            ctx.preempt([20], [5], sc["protected"])                  # pod index >= p
+        assert e.value.status == -1
+        with pytest.raises(B) as e:
+            ctx.preempt([0], [5], None)                              # group_protected NULL with g > 0
+        assert e.value.status == -1
+        ctx.load_groups(soa.Groups.empty(2, 5))                      # the table names groups >= 2
+        if sc["bound"].group.max() >= 2:
+            with pytest.raises(B) as e:
+                ctx.preempt([0], [5], np.zeros(2, np.uint8))
+            assert e.value.status == -1
+        ctx.load_groups(groups_for(sc))
+        ok = ctx.preempt(sc["pod_index"], sc["priority"], sc["protected"], victim_cap=0)
+        assert ok["victims"].shape == (8, 0)
+        nodes2 = soa.Nodes(sc["nodes"].allocatable[:, :40], sc["nodes"].requested[:, :40], sc["nodes"].allocatable_present[:40],
+                           sc["nodes"].requested_present[:40], sc["nodes"].flags[:40])
+        ctx.load_nodes(nodes2, soa.FitMasks.from_bool(sc["fit"].to_bool()[:, :40]))
+        with pytest.raises(B) as e:
+            ctx.preempt(sc["pod_index"], sc["priority"], sc["protected"])   # the node list changed its count
+        assert e.value.status == -4
