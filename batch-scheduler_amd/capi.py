@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "bs_nodes_load_flat", "bs_groups_load_flat", "bs_groups_read_flat", "bs_pods_load_flat", "bs_pods_apply_flat", "bs_pods_read_flat",
     "bs_batch_read_flat", "bs_seq_run_flat", "bs_fit_build_flat",
     "bs_bound_load", "bs_bound_count", "bs_preempt_run", "bs_bound_load_flat", "bs_preempt_run_flat",
+    "bs_preempt_commit", "bs_bound_read", "bs_preempt_commit_flat",
 ]
 
 # bsh_phase codes (include/bsched_host.h) of the phases whose gangs PreemptRemovePod protects: Running and Scheduled (core.go:235-238)
@@ -165,6 +166,10 @@ def load_library(path: str | None = None):
     L.bs_preempt_run.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), u32, P(soa.PreemptOutStruct)]
     L.bs_bound_load_flat.argtypes = [vp, u32, P(u32), P(i32), P(C.c_int64), P(i32), P(C.c_int64), P(u32)]
     L.bs_preempt_run_flat.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), u32, P(i32), P(u32), P(u32), P(u32), P(i32), P(C.c_int64), P(C.c_int64)]
+    L.bs_preempt_commit.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), u32, u32, P(soa.PreemptOutStruct)]
+    L.bs_bound_read.argtypes = [vp, P(u32), P(u32)]
+    L.bs_preempt_commit_flat.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), u32, u32, P(i32), P(u32), P(u32), P(u32), P(i32), P(C.c_int64),
+                                         P(C.c_int64)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:
@@ -524,6 +529,17 @@ class Context:
         """bs_preempt_run: the victim search for every preemptor (resident-queue pod pod_index[q] at priority[q]); group_protected[g]
         from `group_protected(phases)`.  Returns node, n_candidates, n_victims, victims [count, victim_cap] (zero beyond
         min(n_victims, cap)), top_priority, priority_sum, earliest_start."""
+        return self._preempt_call(None, pod_index, priority, group_protected, victim_cap, stages)
+
+    def preempt_commit(self, pod_index, priority, group_protected=None, victim_cap: int = 16, apply: bool = False, assume: bool = False,
+                       stages: int = soa.STAGE_PREFILTER) -> dict:
+        """bs_preempt_commit: the preemptors answered in sequence (priority descending, stable), each seeing the earlier slots' victims
+        gone and their preemptors nominated; apply=True writes the evictions into the bound table and the node requests, assume=True
+        (with apply) also adds each nominee's request to its node.  Returns the dict `preempt` returns."""
+        flags = (soa.PREEMPT_APPLY if apply else 0) | (soa.PREEMPT_ASSUME if assume else 0)
+        return self._preempt_call(flags, pod_index, priority, group_protected, victim_cap, stages)
+
+    def _preempt_call(self, flags, pod_index, priority, group_protected, victim_cap, stages) -> dict:
         pi = np.ascontiguousarray(np.asarray(pod_index, np.uint32).reshape(-1))
         pr = np.ascontiguousarray(np.asarray(priority, np.int32).reshape(-1))
         assert pi.shape == pr.shape
@@ -536,10 +552,21 @@ class Context:
         o = soa.PreemptOutStruct(node.ctypes.data_as(C.POINTER(C.c_int32)), _u32p(ncand), _u32p(nv), _u32p(vic),
                                  top.ctypes.data_as(C.POINTER(C.c_int32)), _i64p(ssum), _i64p(est))
         gptr = gp.ctypes.data_as(C.POINTER(C.c_uint8)) if gp is not None and gp.size else None
-        self._chk(self._lib.bs_preempt_run(self._h, stages, q, _u32p(pi), pr.ctypes.data_as(C.POINTER(C.c_int32)), gptr, victim_cap, C.byref(o)),
-                  "bs_preempt_run")
+        if flags is None:
+            self._chk(self._lib.bs_preempt_run(self._h, stages, q, _u32p(pi), pr.ctypes.data_as(C.POINTER(C.c_int32)), gptr, victim_cap, C.byref(o)),
+                      "bs_preempt_run")
+        else:
+            self._chk(self._lib.bs_preempt_commit(self._h, stages, q, _u32p(pi), pr.ctypes.data_as(C.POINTER(C.c_int32)), gptr, flags, victim_cap,
+                                                  C.byref(o)), "bs_preempt_commit")
         return dict(node=node[:q], n_candidates=ncand[:q], n_victims=nv[:q], victims=vic[:q, :victim_cap], top_priority=top[:q],
                     priority_sum=ssum[:q], earliest_start=est[:q])
+
+    def read_bound(self):
+        """bs_bound_read: the live bound table in table order (node ascending, importance order within a node) as (id, node)"""
+        b = self.bound_count()
+        ids, node = np.zeros(max(b, 1), np.uint32), np.zeros(max(b, 1), np.uint32)
+        self._chk(self._lib.bs_bound_read(self._h, _u32p(ids), _u32p(node)), "bs_bound_read")
+        return ids[:b], node[:b]
 
     # -- sharding / measurement
     def set_shard(self, rank: int, nranks: int):

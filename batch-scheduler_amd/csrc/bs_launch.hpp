@@ -39,4 +39,12 @@ void launch_seq(hipStream_t stream, uint32_t S, size_t lds, const PodsDev& pd, c
 struct PreemptDev;
 void launch_preempt(hipStream_t stream, uint32_t S, dim3 scan_grid, const NodesDev& nd, const PodsDev& pd, const PreemptDev& pe);
 
+// the sequential preemption plan (tu_preempt.hip): k_pc_scan<S> over scan_grid, then k_pc_resolve<S>, one workgroup; and what
+// BS_PREEMPT_APPLY launches after it: k_pc_nodes<S> (ndirty records into reqs), k_pc_boff<S> + k_pc_compact<S> when nw is set
+struct CommitDev;
+struct CompactDev;
+void launch_preempt_commit(hipStream_t stream, uint32_t S, dim3 scan_grid, const NodesDev& nd, const PodsDev& pd, const CommitDev& pe);
+void launch_preempt_apply(hipStream_t stream, uint32_t S, const NodesDev& nd, const CommitDev& pe, uint32_t ndirty, uint32_t assume, bs_node_request* reqs,
+                          const CompactDev* nw);
+
 }  // namespace bs

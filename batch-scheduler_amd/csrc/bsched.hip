@@ -29,6 +29,7 @@
 #include "bs_launch.hpp"
 #include "bs_pod_ranges.hpp"
 #include "bs_preempt.hpp"
+#include "bs_preempt_commit.hpp"
 #ifdef BS_UNITY   // one translation unit (the probe builds: g_probe / g_seq_scan_ph are per translation unit)
 #include "tu_fast.hip"
 #include "tu_seq.hip"
@@ -316,7 +317,8 @@ struct bs_ctx {
   uint32_t bound_b = 0, bound_n = 0;  // entries, node count at the load
   int32_t bound_max_group = -1;      // largest group index the table names (checked against the group count per call)
   DevBuf d_bound, d_pre;
-  size_t off_boff = 0, off_bprio = 0, off_bstart = 0, off_bgroup = 0, off_bid = 0, off_breq = 0;
+  DevBuf d_bound2;                   // bs_preempt_commit's compaction target (swapped with d_bound)
+  size_t off_boff = 0, off_bprio = 0, off_bstart = 0, off_bgroup = 0, off_bid = 0, off_breq = 0, off_bpres = 0;
 };
 
 namespace {
@@ -3855,6 +3857,25 @@ int bs_batch_stats_get(bs_ctx* c, bs_batch_stats* out) {
 // -------------------------------------------------------------------------------------------------
 // gang-aware preemption (bs_preempt.hpp): the resident bound-pod table and the batched victim search
 // -------------------------------------------------------------------------------------------------
+// the bound table's one allocation for N nodes and B entries (columns at 256-byte offsets; breq lane stride max(B, 1)); returns its size
+struct BoundLayout { size_t boff, prio, start, group, id, req, pres; };
+static size_t bound_layout(uint32_t L, uint32_t N, uint32_t B, BoundLayout& b) {
+  const size_t nB = std::max<uint32_t>(B, 1);
+  size_t o = 0;
+  b.boff = o; o = align256(o + ((size_t)N + 1) * 4);
+  b.prio = o; o = align256(o + nB * 4);
+  b.start = o; o = align256(o + nB * 8);
+  b.group = o; o = align256(o + nB * 4);
+  b.id = o; o = align256(o + nB * 4);
+  b.req = o; o = align256(o + nB * L * 8);
+  b.pres = o; o = align256(o + nB * 4);      // scalar keys of each entry (bs_preempt_commit sets them on the node)
+  return o;
+}
+static void bound_layout_set(bs_ctx* c, const BoundLayout& b) {
+  c->off_boff = b.boff; c->off_bprio = b.prio; c->off_bstart = b.start; c->off_bgroup = b.group; c->off_bid = b.id; c->off_breq = b.req;
+  c->off_bpres = b.pres;
+}
+
 int bs_bound_load(bs_ctx* c, const bs_bound_soa* bd) {
   if (!c || !bd) return BS_ERR_INVALID;
   if (!c->have_nodes) { c->last_error = "bs_bound_load before bs_nodes_load"; return BS_ERR_STATE; }
@@ -3885,13 +3906,9 @@ int bs_bound_load(bs_ctx* c, const bs_bound_soa* bd) {
       return a < b;
     });
   const size_t nB = std::max<uint32_t>(B, 1);
-  size_t o = 0;
-  c->off_boff = o; o = align256(o + ((size_t)N + 1) * 4);
-  c->off_bprio = o; o = align256(o + nB * 4);
-  c->off_bstart = o; o = align256(o + nB * 8);
-  c->off_bgroup = o; o = align256(o + nB * 4);
-  c->off_bid = o; o = align256(o + nB * 4);
-  c->off_breq = o; o = align256(o + nB * L * 8);
+  BoundLayout lay;
+  const size_t o = bound_layout(L, N, B, lay);
+  bound_layout_set(c, lay);
   std::vector<uint8_t> h(o, 0);
   std::memcpy(h.data() + c->off_boff, cnt.data(), ((size_t)N + 1) * 4);
   int32_t* prio = reinterpret_cast<int32_t*>(h.data() + c->off_bprio);
@@ -3899,8 +3916,11 @@ int bs_bound_load(bs_ctx* c, const bs_bound_soa* bd) {
   int32_t* grp = reinterpret_cast<int32_t*>(h.data() + c->off_bgroup);
   uint32_t* id = reinterpret_cast<uint32_t*>(h.data() + c->off_bid);
   int64_t* req = reinterpret_cast<int64_t*>(h.data() + c->off_breq);
+  uint32_t* pres = reinterpret_cast<uint32_t*>(h.data() + c->off_bpres);
+  const uint32_t smask = (uint32_t)((1ull << (L - BS_FIXED_LANES)) - 1ull);
   for (uint32_t r = 0; r < B; ++r) {
     const uint32_t i = order[r];
+    pres[r] = bd->req_present[i] & smask;
     prio[r] = bd->priority[i];
     start[r] = bd->start_ns[i];
     grp[r] = bd->group[i];
@@ -4057,6 +4077,225 @@ int bs_preempt_run_flat(bs_ctx* c, uint32_t stages, uint32_t count, const uint32
                         int64_t* priority_sum, int64_t* earliest_start) {
   const bs_preempt_out o{node, n_candidates, n_victims, victims, top_priority, priority_sum, earliest_start};
   return bs_preempt_run(c, stages, count, pod_index, priority, group_protected, victim_cap, &o);
+}
+
+
+// -------------------------------------------------------------------------------------------------
+// preemption plans answered in sequence (bs_preempt_commit.hpp), applied into the resident state on request
+// -------------------------------------------------------------------------------------------------
+int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority, const uint8_t* group_protected,
+                      uint32_t flags, uint32_t victim_cap, const bs_preempt_out* out) {
+  if (!c || !out) return BS_ERR_INVALID;
+  if (stages & ~BS_STAGE_PREFILTER) { c->last_error = "bs_preempt_commit takes BS_STAGE_PREFILTER only (the plugin's Filter takes no part)"; return BS_ERR_INVALID; }
+  if (flags & ~(BS_PREEMPT_APPLY | BS_PREEMPT_ASSUME)) { c->last_error = "bs_preempt_commit: unknown flags"; return BS_ERR_INVALID; }
+  if ((flags & BS_PREEMPT_ASSUME) && !(flags & BS_PREEMPT_APPLY)) { c->last_error = "BS_PREEMPT_ASSUME needs BS_PREEMPT_APPLY"; return BS_ERR_INVALID; }
+  if (!c->have_nodes || !c->have_fit || !c->have_pods || !c->have_bound) {
+    c->last_error = "bs_preempt_commit needs nodes, fit, pods and the bound table loaded";
+    return BS_ERR_STATE;
+  }
+  if (c->nranks > 1 || c->reduce_external) { c->last_error = "bs_preempt_commit is single-rank only"; return BS_ERR_STATE; }
+  if (c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
+  if (count > BS_PREEMPT_MAX || (uint64_t)count * victim_cap > (1ull << 28)) return BS_ERR_CAPACITY;
+  if (count == 0) return BS_OK;
+  if (!pod_index || !priority || !out->node || !out->n_victims || (victim_cap && !out->victims) || (c->G && !group_protected)) return BS_ERR_INVALID;
+  if (c->bound_max_group >= (int32_t)c->G) { c->last_error = "the bound table names a group index >= the loaded group count"; return BS_ERR_INVALID; }
+  const uint32_t P = c->P, N = c->N, G = c->G, L = c->L, B = c->bound_b;
+  for (uint32_t i = 0; i < count; ++i)
+    if (pod_index[i] >= P) { c->last_error = "preemptor pod index >= p"; return BS_ERR_INVALID; }
+  {
+    std::vector<uint32_t> seen(pod_index, pod_index + count);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { c->last_error = "bs_preempt_commit: a pod index appears twice (a pod is nominated once)"; return BS_ERR_INVALID; }
+  }
+  const bool apply = (flags & BS_PREEMPT_APPLY) != 0, assume = (flags & BS_PREEMPT_ASSUME) != 0;
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (apply && (rc = settle_pending(c))) return rc;
+  std::vector<uint32_t> perm(count);
+  for (uint32_t i = 0; i < count; ++i) perm[i] = i;
+  std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return priority[a] > priority[b]; });
+  const uint32_t tiles = cdiv(count, 64);
+  uint32_t nchunks = std::max<uint32_t>(1, std::min<uint32_t>(std::max<uint32_t>(N, 1), cdiv(4096, tiles)));
+  const uint32_t chunk_nodes = std::max<uint32_t>(1, cdiv(N, nchunks));
+  nchunks = std::max<uint32_t>(1, cdiv(N, chunk_nodes));
+  const size_t nQ = count, nG = std::max<uint32_t>(G, 1), nR = (size_t)nchunks * nQ, nV = std::max<size_t>((size_t)nQ * victim_cap, 1);
+  const size_t nN = std::max<uint32_t>(N, 1), nB = std::max<uint32_t>(B, 1);
+  size_t o = 0;
+  const size_t o_spod = o; o = align256(o + nQ * 4);
+  const size_t o_sprio = o; o = align256(o + nQ * 4);
+  const size_t o_sorig = o; o = align256(o + nQ * 4);
+  const size_t o_gprot = o; o = align256(o + nG);
+  const size_t in_bytes = o;
+  const size_t o_rnode = o; o = align256(o + nR * kPcK * 4);
+  const size_t o_rnv = o; o = align256(o + nR * kPcK * 4);
+  const size_t o_rtop = o; o = align256(o + nR * kPcK * 4);
+  const size_t o_rsum = o; o = align256(o + nR * kPcK * 8);
+  const size_t o_rest = o; o = align256(o + nR * kPcK * 8);
+  const size_t o_rncand = o; o = align256(o + nR * 4);
+  const size_t o_work = o;                                // zeroed working state
+  const size_t o_dv = o; o = align256(o + (size_t)L * nN * 8);
+  const size_t o_dn = o; o = align256(o + (size_t)L * nN * 8);
+  const size_t o_vbits = o; o = align256(o + nN * 4);
+  const size_t o_nbits = o; o = align256(o + nN * 4);
+  const size_t o_dirty = o; o = align256(o + nN);
+  const size_t o_dead = o; o = align256(o + nB);
+  const size_t work_bytes = o - o_work;
+  const size_t o_dlist = o; o = align256(o + nQ * 4);
+  const size_t o_nreq = o; o = align256(o + nQ * sizeof(bs_node_request));
+  const size_t o_res = o;                                 // results: one D2H
+  const size_t o_info = o; o = align256(o + 2 * 4);
+  const size_t o_node = o; o = align256(o + nQ * 4);
+  const size_t o_ncand = o; o = align256(o + nQ * 4);
+  const size_t o_nv = o; o = align256(o + nQ * 4);
+  const size_t o_top = o; o = align256(o + nQ * 4);
+  const size_t o_sum = o; o = align256(o + nQ * 8);
+  const size_t o_est = o; o = align256(o + nQ * 8);
+  const size_t o_vic = o; o = align256(o + nV * 4);
+  HIPCHK(c, c->d_pre.reserve(o));
+  std::vector<uint8_t> in(in_bytes, 0);
+  uint32_t* spod = reinterpret_cast<uint32_t*>(in.data() + o_spod);
+  int32_t* sprio = reinterpret_cast<int32_t*>(in.data() + o_sprio);
+  uint32_t* sorig = reinterpret_cast<uint32_t*>(in.data() + o_sorig);
+  for (uint32_t s = 0; s < count; ++s) {
+    spod[s] = pod_index[perm[s]];
+    sprio[s] = priority[perm[s]];
+    sorig[s] = perm[s];
+  }
+  if (G) std::memcpy(in.data() + o_gprot, group_protected, G);
+  uint8_t* base = c->d_pre.as<uint8_t>();
+  HIPCHK(c, hipMemcpyAsync(base, in.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(base + o_work, 0, work_bytes, c->stream));
+  const uint8_t* bb = c->d_bound.as<uint8_t>();
+  CommitDev pe{};
+  pe.boff = reinterpret_cast<const uint32_t*>(bb + c->off_boff);
+  pe.bprio = reinterpret_cast<const int32_t*>(bb + c->off_bprio);
+  pe.bstart = reinterpret_cast<const int64_t*>(bb + c->off_bstart);
+  pe.bgroup = reinterpret_cast<const int32_t*>(bb + c->off_bgroup);
+  pe.bid = reinterpret_cast<const uint32_t*>(bb + c->off_bid);
+  pe.breq = reinterpret_cast<const int64_t*>(bb + c->off_breq);
+  pe.bpres = reinterpret_cast<const uint32_t*>(bb + c->off_bpres);
+  pe.bstride = (uint32_t)nB;
+  pe.q = count;
+  pe.nchunks = nchunks;
+  pe.chunk_nodes = chunk_nodes;
+  pe.cap = victim_cap;
+  pe.spod = reinterpret_cast<const uint32_t*>(base + o_spod);
+  pe.sprio = reinterpret_cast<const int32_t*>(base + o_sprio);
+  pe.sorig = reinterpret_cast<const uint32_t*>(base + o_sorig);
+  pe.gprot = base + o_gprot;
+  pe.r_node = reinterpret_cast<int32_t*>(base + o_rnode);
+  pe.r_nv = reinterpret_cast<uint32_t*>(base + o_rnv);
+  pe.r_top = reinterpret_cast<int32_t*>(base + o_rtop);
+  pe.r_sum = reinterpret_cast<int64_t*>(base + o_rsum);
+  pe.r_est = reinterpret_cast<int64_t*>(base + o_rest);
+  pe.r_ncand = reinterpret_cast<uint32_t*>(base + o_rncand);
+  pe.dv = reinterpret_cast<int64_t*>(base + o_dv);
+  pe.dn = reinterpret_cast<int64_t*>(base + o_dn);
+  pe.vbits = reinterpret_cast<uint32_t*>(base + o_vbits);
+  pe.nbits = reinterpret_cast<uint32_t*>(base + o_nbits);
+  pe.dirty = base + o_dirty;
+  pe.dead = base + o_dead;
+  pe.dlist = reinterpret_cast<uint32_t*>(base + o_dlist);
+  pe.info = reinterpret_cast<uint32_t*>(base + o_info);
+  pe.o_node = reinterpret_cast<int32_t*>(base + o_node);
+  pe.o_ncand = reinterpret_cast<uint32_t*>(base + o_ncand);
+  pe.o_nv = reinterpret_cast<uint32_t*>(base + o_nv);
+  pe.o_top = reinterpret_cast<int32_t*>(base + o_top);
+  pe.o_sum = reinterpret_cast<int64_t*>(base + o_sum);
+  pe.o_est = reinterpret_cast<int64_t*>(base + o_est);
+  pe.o_victims = reinterpret_cast<uint32_t*>(base + o_vic);
+  const NodesDev nd = nodes_dev(c);
+  launch_preempt_commit(c->stream, c->S, dim3(tiles, nchunks), nd, pods_dev(c), pe);
+  LAUNCHCHK(c, BS_KERNEL_QUERY);
+  std::vector<uint8_t> res(o - o_res);
+  HIPCHK(c, hipMemcpyAsync(res.data(), base + o_res, res.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint8_t* rb = res.data() - o_res;
+  if (apply) {
+    const uint32_t* info = reinterpret_cast<const uint32_t*>(rb + o_info);
+    const uint32_t ndirty = info[0], nvall = info[1];
+    bs_node_request* dreq = reinterpret_cast<bs_node_request*>(base + o_nreq);
+    CompactDev nw{};
+    const uint32_t B2 = B - nvall;
+    BoundLayout lay{};
+    if (nvall) {                                          // the compacted table goes to the second buffer, swapped in below
+      HIPCHK(c, c->d_bound2.reserve(bound_layout(L, N, B2, lay)));
+      uint8_t* b2 = c->d_bound2.as<uint8_t>();
+      nw.boff = reinterpret_cast<uint32_t*>(b2 + lay.boff);
+      nw.bprio = reinterpret_cast<int32_t*>(b2 + lay.prio);
+      nw.bstart = reinterpret_cast<int64_t*>(b2 + lay.start);
+      nw.bgroup = reinterpret_cast<int32_t*>(b2 + lay.group);
+      nw.bid = reinterpret_cast<uint32_t*>(b2 + lay.id);
+      nw.breq = reinterpret_cast<int64_t*>(b2 + lay.req);
+      nw.bpres = reinterpret_cast<uint32_t*>(b2 + lay.pres);
+      nw.bstride = std::max<uint32_t>(B2, 1);
+    }
+    launch_preempt_apply(c->stream, c->S, nd, pe, ndirty, assume ? 1u : 0u, dreq, nvall ? &nw : nullptr);
+    LAUNCHCHK(c, BS_KERNEL_QUERY);
+    if (ndirty) {
+      static_assert(sizeof(bs_node_request) == sizeof(NodeRequest), "node request layout");
+      hipLaunchKernelGGL(k_nodes_assume, dim3(cdiv(ndirty, 256)), dim3(256), 0, c->stream, reinterpret_cast<const NodeRequest*>(dreq), ndirty, L, c->Ncap,
+                         c->d_alloc.as<int64_t>(), c->d_nreq.as<int64_t>(), c->d_rpres.as<uint32_t>(), c->d_nflags.as<uint8_t>(), c->d_left4.as<int64_t>(),
+                         c->d_lglob.as<int64_t>());
+      LAUNCHCHK(c, BS_KERNEL_PREPASS);
+      std::vector<bs_node_request> h(ndirty);             // the host mirror a later bs_nodes_apply starts from
+      HIPCHK(c, hipMemcpyAsync(h.data(), dreq, (size_t)ndirty * sizeof(bs_node_request), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      for (const bs_node_request& r : h) {
+        for (uint32_t j = 0; j < L; ++j) c->h_nreq[(size_t)j * N + r.index] = r.requested[j];
+        c->h_rpres[r.index] = r.requested_present;
+      }
+      c->bitmap_valid = false;
+    }
+    if (nvall) {
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      std::swap(c->d_bound.p, c->d_bound2.p);
+      std::swap(c->d_bound.cap, c->d_bound2.cap);
+      bound_layout_set(c, lay);
+      c->bound_b = B2;
+    }
+  }
+  std::memcpy(out->node, rb + o_node, nQ * 4);
+  std::memcpy(out->n_victims, rb + o_nv, nQ * 4);
+  if (out->n_candidates) std::memcpy(out->n_candidates, rb + o_ncand, nQ * 4);
+  if (out->top_priority) std::memcpy(out->top_priority, rb + o_top, nQ * 4);
+  if (out->priority_sum) std::memcpy(out->priority_sum, rb + o_sum, nQ * 8);
+  if (out->earliest_start) std::memcpy(out->earliest_start, rb + o_est, nQ * 8);
+  if (victim_cap) {
+    const uint32_t* nv = reinterpret_cast<const uint32_t*>(rb + o_nv);
+    const uint32_t* vic = reinterpret_cast<const uint32_t*>(rb + o_vic);
+    for (size_t q = 0; q < nQ; ++q) {
+      const uint32_t k = std::min(nv[q], victim_cap);
+      std::memcpy(out->victims + q * victim_cap, vic + q * victim_cap, (size_t)k * 4);
+      std::memset(out->victims + q * victim_cap + k, 0, (size_t)(victim_cap - k) * 4);
+    }
+  }
+  return BS_OK;
+}
+
+int bs_bound_read(bs_ctx* c, uint32_t* id_out, uint32_t* node_out) {
+  if (!c) return BS_ERR_INVALID;
+  if (!c->have_bound) { c->last_error = "bs_bound_read before bs_bound_load"; return BS_ERR_STATE; }
+  const uint32_t B = c->bound_b, N = c->bound_n;
+  if (B == 0) return BS_OK;
+  if (!id_out || !node_out) return BS_ERR_INVALID;
+  int rc = use_device(c);
+  if (rc) return rc;
+  std::vector<uint32_t> boff((size_t)N + 1);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint8_t* bb = c->d_bound.as<uint8_t>();
+  HIPCHK(c, hipMemcpy(boff.data(), bb + c->off_boff, ((size_t)N + 1) * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(id_out, bb + c->off_bid, (size_t)B * 4, hipMemcpyDeviceToHost));
+  for (uint32_t k = 0; k < N; ++k)
+    for (uint32_t j = boff[k]; j < boff[k + 1] && j < B; ++j) node_out[j] = k;
+  return BS_OK;
+}
+
+int bs_preempt_commit_flat(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority, const uint8_t* group_protected,
+                           uint32_t flags, uint32_t victim_cap, int32_t* node, uint32_t* n_candidates, uint32_t* n_victims, uint32_t* victims,
+                           int32_t* top_priority, int64_t* priority_sum, int64_t* earliest_start) {
+  const bs_preempt_out o{node, n_candidates, n_victims, victims, top_priority, priority_sum, earliest_start};
+  return bs_preempt_commit(c, stages, count, pod_index, priority, group_protected, flags, victim_cap, &o);
 }
 
 }  // extern "C"

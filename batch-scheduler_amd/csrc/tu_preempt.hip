@@ -1,9 +1,11 @@
-// tu_preempt.hip — translation unit of the preemption victim search (bs_preempt.hpp: k_preempt_scan / k_preempt_pick, one
-// instantiation per scalar-lane count 0..BS_MAX_SCALARS) and its launch wrapper; see tu_fast.hip for why.
+// tu_preempt.hip — translation unit of the preemption victim search (bs_preempt.hpp: k_preempt_scan / k_preempt_pick) and of the
+// sequential plans (bs_preempt_commit.hpp: k_pc_*), one instantiation per scalar-lane count 0..BS_MAX_SCALARS, and their launch
+// wrappers; see tu_fast.hip for why.
 #ifndef BS_UNITY
 #define BS_TU_PREEMPT
 #endif
 #include "bs_preempt.hpp"
+#include "bs_preempt_commit.hpp"
 #include "bs_launch.hpp"
 
 namespace bs {
@@ -31,5 +33,42 @@ void launch_preempt(hipStream_t stream, uint32_t S, dim3 scan_grid, const NodesD
     default: launch_preempt_s<12>(stream, scan_grid, nd, pd, pe); break;
   }
 }
+
+template <int S>
+static void launch_preempt_commit_s(hipStream_t stream, dim3 scan_grid, const NodesDev& nd, const PodsDev& pd, const CommitDev& pe) {
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pc_scan<S>), scan_grid, dim3(64), 0, stream, nd, pd, pe);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pc_resolve<S>), dim3(1), dim3(pc_threads<S>()), 0, stream, nd, pd, pe);
+}
+
+template <int S>
+static void launch_preempt_apply_s(hipStream_t stream, const NodesDev& nd, const CommitDev& pe, uint32_t ndirty, uint32_t assume, bs_node_request* reqs,
+                                   const CompactDev* nw) {
+  if (ndirty) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pc_nodes<S>), dim3((ndirty + 255) / 256), dim3(256), 0, stream, nd, pe, ndirty, assume, reqs);
+  if (nw) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pc_boff<S>), dim3(1), dim3(1024), 0, stream, pe, nd.n, nw->boff);
+    if (nd.n) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pc_compact<S>), dim3(nd.n), dim3(64), 0, stream, pe, *nw, nd.n);
+  }
+}
+
+#define BS_PC_CASES(CALL) \
+  switch (S) { \
+    case 0: CALL(0); break; case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break; \
+    case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; case 8: CALL(8); break; case 9: CALL(9); break; \
+    case 10: CALL(10); break; case 11: CALL(11); break; default: CALL(12); break; \
+  }
+
+void launch_preempt_commit(hipStream_t stream, uint32_t S, dim3 scan_grid, const NodesDev& nd, const PodsDev& pd, const CommitDev& pe) {
+#define BS_PC_PLAN(s) launch_preempt_commit_s<s>(stream, scan_grid, nd, pd, pe)
+  BS_PC_CASES(BS_PC_PLAN)
+#undef BS_PC_PLAN
+}
+
+void launch_preempt_apply(hipStream_t stream, uint32_t S, const NodesDev& nd, const CommitDev& pe, uint32_t ndirty, uint32_t assume, bs_node_request* reqs,
+                          const CompactDev* nw) {
+#define BS_PC_APPLY(s) launch_preempt_apply_s<s>(stream, nd, pe, ndirty, assume, reqs, nw)
+  BS_PC_CASES(BS_PC_APPLY)
+#undef BS_PC_APPLY
+}
+#undef BS_PC_CASES
 
 }  // namespace bs

@@ -613,6 +613,44 @@ typedef struct bs_preempt_out {
 int bs_preempt_run(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
                    const uint8_t* group_protected, uint32_t victim_cap, const bs_preempt_out* out);
 
+/* ---- preemption plans: the preemptors answered in sequence, optionally applied ---------------------------------------------
+ * bs_preempt_run answers every preemptor on its own, so its rows are no plan: two rows may name the same victim, count the same freed
+ * room, or send a pod to a node an earlier row just filled.  bs_preempt_commit takes bs_preempt_run's arguments plus `flags` and
+ * answers the preemptors IN SEQUENCE:
+ *   1. slot order: priority descending, equal priorities in the caller's order (a stable sort: bs_preempt_run's own permutation; a
+ *      caller that passes its preemptors in scheduling-queue order, bs_queue_sort, gets the queue's order).  Results come back in the
+ *      caller's order.
+ *   2. slot s sees the context's state (node requests, bound table) after every earlier slot t that got a node:
+ *        t's victims leave: they are removed from their node's bound list, and NodeInfo.RemovePod is applied to the node's requests
+ *        (lanes 0..2 minus the request, the pods lane minus 1, the scalar keys the victim has subtracted, setting the key's present bit);
+ *        t becomes a NOMINATED pod on its node: AddPod with its resident-queue request (lanes 0..2 plus the request, the pods lane plus
+ *        1, its scalar keys added, setting the present bit).  This is upstream's addNominatedPods inside podFitsOnNode: nominated pods
+ *        of priority >= the pod's count on the node, and in slot order every earlier nominee qualifies.  A nominee is never a victim
+ *        (it is not bound).
+ *      Library rule: evictions take effect at once for the later slots of the same call.  Upstream leaves a terminating victim in the
+ *      cache until its delete event arrives; modelling that would let two preemptors count the same pod, the conflict this call removes.
+ *   3. the search for slot s is bs_preempt_run's steps 1-6 on that state, unchanged (skip rule, policy, fit rule, reprieve order, pick
+ *      key, ties).  Slot 0's answer is exactly bs_preempt_run's answer for that preemptor.
+ *   4. flags: 0 = the plan only, nothing resident changes (as bs_preempt_run).  BS_PREEMPT_APPLY: after the pass the evictions are
+ *      written into the context: the bound table loses every victim of every slot (survivors keep their caller ids from the last
+ *      bs_bound_load and their per-node importance order; bs_bound_count falls by the number of victims), node requests lose the victims
+ *      (RemovePod as in 2), and the host mirror and the derived node data follow as after bs_nodes_assume.  BS_PREEMPT_ASSUME (only with
+ *      APPLY): each nominee's request is also added to its node (AddPod), as bs_nodes_assume would add it.  Other bits: BS_ERR_INVALID.
+ *   5. evictions ignore victim_cap: every victim is evicted even when victim_cap truncates the returned list; n_victims is the true count.
+ *   6. errors: whatever bs_preempt_run refuses, with the same code; also a pod_index that appears twice (a pod is nominated once) and
+ *      BS_PREEMPT_ASSUME without BS_PREEMPT_APPLY (BS_ERR_INVALID).  Everything is validated before anything is launched; on any error
+ *      no resident state changes.  Group state, the queue and the fit masks are never touched: a gang that loses pods keeps its
+ *      Status.Scheduled (updating it is the controller's job).  No nominated pods from earlier calls, no PDBs; sharded contexts:
+ *      BS_ERR_STATE.  Synchronous. */
+#define BS_PREEMPT_APPLY  1u   /* write the evictions into the bound table and the node requests */
+#define BS_PREEMPT_ASSUME 2u   /* with APPLY: also add each nominee's request to its node          */
+int bs_preempt_commit(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
+                      const uint8_t* group_protected, uint32_t flags, uint32_t victim_cap, const bs_preempt_out* out);
+/* The live bound table in table order: node ascending, importance order within a node; bs_bound_count entries.  id_out[i] = the
+ * entry's id (its index at the last bs_bound_load), node_out[i] = its node.  BS_ERR_STATE before bs_bound_load; the arrays may be NULL
+ * when the table is empty. */
+int bs_bound_read(bs_ctx* ctx, uint32_t* id_out, uint32_t* node_out);
+
 /* ---- batched queue ordering ---------------------------------------- */
 /* The permutation that sorts the pending pods the way the scheduling queue does through ScheduleOperation.Compare
  * (core.go:368-411; Less, batchscheduler.go:214): perm_out[k] = index of the pod at queue position k.  Key, ascending:
@@ -728,6 +766,10 @@ int bs_bound_load_flat(bs_ctx* ctx, uint32_t b, const uint32_t* node, const int3
 int bs_preempt_run_flat(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority, const uint8_t* group_protected,
                         uint32_t victim_cap, int32_t* node, uint32_t* n_candidates, uint32_t* n_victims, uint32_t* victims, int32_t* top_priority,
                         int64_t* priority_sum, int64_t* earliest_start);
+/* bs_preempt_commit (bs_preempt_out's arrays one by one) */
+int bs_preempt_commit_flat(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
+                           const uint8_t* group_protected, uint32_t flags, uint32_t victim_cap, int32_t* node, uint32_t* n_candidates,
+                           uint32_t* n_victims, uint32_t* victims, int32_t* top_priority, int64_t* priority_sum, int64_t* earliest_start);
 
 /* ---- measurement ------------------------------------------------------------------ */
 #define BS_KERNEL_PREPASS   0u

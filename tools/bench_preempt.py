@@ -1,6 +1,8 @@
 """Times bs_preempt_run (the batched gang-aware victim search, csrc/bs_preempt.hpp) at the cfg3 and cfg4 node counts with 20-110 bound
 pods per node, for 64 and 1024 preemptors.  Prints one JSON line: ms per call (median of --reps calls after --warmup), end to end
-through the C ABI (upload of the preemptor arrays, both launches, the result copy)."""
+through the C ABI (upload of the preemptor arrays, both launches, the result copy).  --commit times bs_preempt_commit instead (the
+plan answered in sequence, distinct preemptors) with flags 0 and BS_PREEMPT_APPLY; an APPLY call is timed from the state as loaded (the
+nodes and the bound table are reloaded, untimed, before every call)."""
 from __future__ import annotations
 
 import argparse
@@ -18,12 +20,14 @@ bsa = importlib.import_module("batch-scheduler_amd")
 soa, synth = bsa.soa, bsa.synth
 
 
-def one(config: str, q: int, reps: int, warmup: int) -> dict:
+def one(config: str, q: int, reps: int, warmup: int, commit: bool = False, apply: bool = False) -> dict:
     cfg = synth.CONFIGS[config]
     n, S = cfg["nodes"], cfg["scalars"]
     bound, nodes = synth.make_bound(20260921, n, cfg["groups"], (20, 110), S)
     fit = synth.make_fit(20260921, n, cfg["classes"])
     pods, pidx, prio = synth.make_preemptors(20260921, q, 4096, cfg["groups"], S, cfg["classes"])
+    if commit:                                             # a pod is nominated once
+        pidx = np.random.default_rng(20260921).permutation(4096)[:q].astype(np.uint32)
     groups = soa.Groups.empty(cfg["groups"], 4 + S)
     prot = (synth.Stream(20260921, 99).uniform(cfg["groups"]) < 0.3).astype(np.uint8)
     with bsa.Context(scalar_lanes=S, device=0) as ctx:
@@ -31,22 +35,37 @@ def one(config: str, q: int, reps: int, warmup: int) -> dict:
         ctx.load_groups(groups)
         ctx.load_pods(pods)
         ctx.load_bound(bound)
-        for _ in range(warmup):
-            r = ctx.preempt(pidx, prio, prot, victim_cap=16)
+        def call():
+            if not commit:
+                return ctx.preempt(pidx, prio, prot, victim_cap=16)
+            return ctx.preempt_commit(pidx, prio, prot, victim_cap=16, apply=apply)
+
         ts = []
-        for _ in range(reps):
+        for it in range(warmup + reps):
+            if apply and it:
+                ctx.load_nodes(nodes, fit)
+                ctx.load_bound(bound)
             t0 = time.perf_counter()
-            r = ctx.preempt(pidx, prio, prot, victim_cap=16)
-            ts.append((time.perf_counter() - t0) * 1e3)
-    return dict(config=config, nodes=n, bound=int(bound.b), preemptors=q, ms=round(float(np.median(ts)), 4), ms_min=round(float(min(ts)), 4),
-                placed=int((r["node"] >= 0).sum()), with_victims=int((r["n_victims"] > 0).sum()))
+            r = call()
+            if it >= warmup:
+                ts.append((time.perf_counter() - t0) * 1e3)
+    row = dict(config=config, nodes=n, bound=int(bound.b), preemptors=q, ms=round(float(np.median(ts)), 4), ms_min=round(float(min(ts)), 4),
+               placed=int((r["node"] >= 0).sum()), with_victims=int((r["n_victims"] > 0).sum()))
+    if commit:
+        row.update(flags="APPLY" if apply else "0", evicted=int(r["n_victims"].sum()))
+    return row
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--commit", action="store_true", help="bs_preempt_commit, flags 0 and APPLY")
     a = ap.parse_args()
+    if a.commit:
+        rows = [one(c, q, a.reps, a.warmup, True, ap_) for c in ("cfg3", "cfg4") for q in (64, 1024) for ap_ in (False, True)]
+        print(json.dumps(dict(metric="bs_preempt_commit ms per call", rows=rows)))
+        return
     rows = [one(c, q, a.reps, a.warmup) for c in ("cfg3", "cfg4") for q in (64, 1024)]
     print(json.dumps(dict(metric="bs_preempt_run ms per call", rows=rows)))
 
