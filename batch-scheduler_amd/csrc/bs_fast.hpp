@@ -606,7 +606,11 @@ template <int TS>
 __device__ __forceinline__ void node_words_block(const GroupsDev& gr, const NodesDev& nd, const BatchDev& b, const BatchParams& prm, uint32_t blk) {
   const Shape<TS> sh(prm.S);
   const uint32_t gate = prm.eph_gate;
-  const uint32_t n = blk * kTblChunk + threadIdx.x, w = n >> 6, stride = b.nodew_stride;
+  const uint32_t n = blk * kTblChunk + threadIdx.x, w = nodew_wave_word(blk, threadIdx.x), stride = b.nodew_stride;
+  // a wave of the last block that has no node at all stores nothing (bs_nodew_layout.hpp): with N mod 256 in [1, 64] its word index is the table's stride,
+  // and pair `stride` of a table is pair 0 of the next one (ref[0..1] behind table 2), which block 0 writes in this same launch.  The wave still takes
+  // part in the ballots (w is wave-uniform; its lanes hold no node and ballot zero).
+  const bool stores = nodew_wave_stores(nd.n, w) && lane_id() == 0;
   const int32_t leaders[2] = {b.leader_epoch[0], prm.sop_leader0};
   int64_t l[4] = {INT64_MIN, INT64_MIN, INT64_MIN, INT64_MIN};
   uint8_t fl = 0xFF;
@@ -616,9 +620,9 @@ __device__ __forceinline__ void node_words_block(const GroupsDev& gr, const Node
     fl = nd.flags[n];
   }
   const unsigned long long ok = __ballot(fl != 0xFF && !(fl & (BS_NODE_NIL | BS_NODE_NO_NODE)));
-  if (lane_id() == 0) {                                                   // table 2: a leader no node can hold a member of (scalar MinResources)
-    b.nodew[((size_t)2 * stride + w) * 2] = ok;
-    b.nodew[((size_t)2 * stride + w) * 2 + 1] = ~0ull;
+  if (stores) {                                                           // table 2: a leader no node can hold a member of (scalar MinResources)
+    b.nodew[nodew_pair(stride, 2, w)] = ok;
+    b.nodew[nodew_pair(stride, 2, w) + 1] = ~0ull;
   }
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
@@ -633,14 +637,14 @@ __device__ __forceinline__ void node_words_block(const GroupsDev& gr, const Node
     for (uint32_t q = 0; q < BS_MAX_SCALARS; ++q)
       if (q < sh.S() && (ms.present & (1u << q)) && ms.v[4 + q] != 0) ff |= 2u;
     const unsigned long long holds = __ballot(l[0] >= ms.v[0] && l[1] >= ms.v[1] && l[2] >= ms.v[2] && l[3] >= ms.v[3]);
-    if (lane_id() == 0) {
-      b.nodew[((size_t)s * stride + w) * 2] = ok;
-      b.nodew[((size_t)s * stride + w) * 2 + 1] = ~holds;
+    if (stores) {
+      b.nodew[nodew_pair(stride, s, w)] = ok;
+      b.nodew[nodew_pair(stride, s, w) + 1] = ~holds;
     }
     if (blk == 0 && threadIdx.x == 0) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) b.nodew[(size_t)6 * stride + 4 * s + j] = (uint64_t)ms.v[j];
-      b.nodew[(size_t)6 * stride + 8 + s] = ff;
+      for (int j = 0; j < 4; ++j) b.nodew[nodew_ref_lane(stride, s, j)] = (uint64_t)ms.v[j];
+      b.nodew[nodew_ref_flags(stride, s)] = ff;
     }
   }
 }
@@ -1871,10 +1875,14 @@ __global__ __launch_bounds__(kLeaderBlock) void k_leader_scan(GroupsDev gr, Batc
 // BS_BATCH_COMMIT on the fast path: every group has its pod and MinResources already, so what sequential
 // PreFilter calls would leave behind is OccupiedBy (core.go:494-500) and the deny entries (:142,:163).
 // gate: BS_BATCH_FILTER_DENY's flag word — a run that is not the fixed point (bs_fdeny.hpp) commits nothing
+// b.h_err: the context's hand-over error word (pinned, coherent host memory; raised by a block of this batch whose in-launch wait ran out, kSpinBound).
+// A batch that will be answered with BS_ERR_RETRY commits nothing either: its first_np_s / fast_reject are partial, and the caller runs it again from
+// the state it had.  One uncached read per wave, on the committing path only; the launches in front of this one on the stream have completed.
 #if BS_EMIT_MAIN
 __global__ void k_fast_commit(PodsDev pods, BatchDev b, uint8_t* gflags, uint64_t* gocc, uint32_t G, const uint32_t* gate) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= G || (gate && *gate)) return;
+  if (b.h_err && __hip_atomic_load(b.h_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) return;
   uint8_t fl = gflags[g];
   const uint32_t fe = ((fl & BS_GROUP_DENIED) || (b.fd_in && b.fd_in[g] < b.first_np_s[g])) ? BS_INF : b.first_np_s[g];
   const uint32_t fr = b.fast_reject[g];

@@ -413,10 +413,11 @@ __device__ __forceinline__ void lean_tile_head(const NodesDev& nd, const BatchDe
   if (b.nodew && !b.h_rows && uniformM) {
     if (lb0) sel = 2;
     else {
-      const cnode_t ref = (cnode_t)(uintptr_t)(b.nodew + (size_t)6 * b.nodew_stride);
+      const cnode_t ref = (cnode_t)(uintptr_t)(b.nodew + nodew_ref(b.nodew_stride));
 #pragma unroll
       for (int s2 = 1; s2 >= 0; --s2) {
-        const bool eq = (ref[8 + s2] & 3) == 1 && ref[4 * s2] == M0[0] && ref[4 * s2 + 1] == M0[1] && ref[4 * s2 + 2] == M0[2] && ref[4 * s2 + 3] == M0[3];
+        const bool eq = (ref[nodew_ref_flags_at(s2)] & 3) == 1 && ref[nodew_ref_lane_at(s2, 0)] == M0[0] && ref[nodew_ref_lane_at(s2, 1)] == M0[1] &&
+                        ref[nodew_ref_lane_at(s2, 2)] == M0[2] && ref[nodew_ref_lane_at(s2, 3)] == M0[3];
         if (__ballot(eq) != 0) sel = s2;
       }
     }
@@ -467,7 +468,7 @@ __device__ __forceinline__ void filter_item_multi(const NodesDev& nd, const Batc
     return;
   }
   const cnode_t L4 = (cnode_t)(uintptr_t)nd.left4;
-  const cword_t NW = (cword_t)(uintptr_t)(b.nodew + (size_t)sel * b.nodew_stride * 2);
+  const cword_t NW = (cword_t)(uintptr_t)(b.nodew + nodew_table(b.nodew_stride, sel));
 #pragma unroll
   for (int t = 0; t < T; ++t) {
     cnt[t] = 0u; live[t] = tsel[t] >= 0;
@@ -602,17 +603,18 @@ __device__ __forceinline__ void filter_item_t(const NodesDev& nd, const BatchDev
   if (b.nodew && !b.h_rows && uniformM) {
     if (lb0) sel = 2;
     else {
-      const cnode_t ref = (cnode_t)(uintptr_t)(b.nodew + (size_t)6 * b.nodew_stride);
+      const cnode_t ref = (cnode_t)(uintptr_t)(b.nodew + nodew_ref(b.nodew_stride));
 #pragma unroll
       for (int s2 = 1; s2 >= 0; --s2) {
-        const bool eq = (ref[8 + s2] & 3) == 1 && ref[4 * s2] == M0[0] && ref[4 * s2 + 1] == M0[1] && ref[4 * s2 + 2] == M0[2] && ref[4 * s2 + 3] == M0[3];
+        const bool eq = (ref[nodew_ref_flags_at(s2)] & 3) == 1 && ref[nodew_ref_lane_at(s2, 0)] == M0[0] && ref[nodew_ref_lane_at(s2, 1)] == M0[1] &&
+                        ref[nodew_ref_lane_at(s2, 2)] == M0[2] && ref[nodew_ref_lane_at(s2, 3)] == M0[3];
         if (__ballot(eq) != 0) sel = s2;              // (M0 is the same in every lane)
       }
     }
   }
   sel = __builtin_amdgcn_readfirstlane(sel);          // (uniform by construction; the compiler sees lb0's __shfl)
   if (sel >= 0) {
-    const cword_t NW = (cword_t)(uintptr_t)(b.nodew + (size_t)sel * b.nodew_stride * 2);
+    const cword_t NW = (cword_t)(uintptr_t)(b.nodew + nodew_table(b.nodew_stride, sel));
     uint64_t* out = b.fu_bitmap + (size_t)w0 * ustride + p0 + lane;
     if (ev) {                                         // EXEC = the evaluated slots, once for the whole run of blocks
       const uint32_t c2m = c2pod ? ~0u : 0u;

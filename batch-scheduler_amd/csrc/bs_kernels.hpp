@@ -34,6 +34,7 @@
 #pragma once
 
 #include "bs_common.hpp"
+#include "bs_nodew_layout.hpp"
 
 namespace bs {
 
@@ -141,11 +142,12 @@ struct BatchDev {
   uint32_t* fu_feas;        // [filter slots] feasible-node counts of the slots
   // node words of the batch (round 6, node_words_block in bs_fast.hpp; null = not built for this batch).  Three tables of [stride] word PAIRS, one
   // pair per 64-node block w — one s_load_dwordx4 of the Filter item:
-  //   nodew[(t * stride + w) * 2]       nodes Filter can evaluate (in range, neither nil nor without a Node object: core.go:442-449)
-  //   nodew[(t * stride + w) * 2 + 1]   nodes that can NOT hold one member of the leader's gang (left < maxSingle on some fixed lane): the nodes
+  // (indices: bs_nodew_layout.hpp, which every writer, reader and the allocation call)
+  //   nodew[nodew_pair(stride, t, w)]      nodes Filter can evaluate (in range, neither nil nor without a Node object: core.go:442-449)
+  //   nodew[nodew_pair(stride, t, w) + 1]  nodes that can NOT hold one member of the leader's gang (left < maxSingle on some fixed lane): the nodes
   //                                     case 3 (core.go:558-563) lets pass.  t = 0: the batch's findMaxPG result, t = 1: the leader carried in,
   //                                     t = 2: a leader whose MinResources names a scalar resource (no node holds a member: getLeftResource has no scalars, Q4)
-  //   nodew[6 * stride + 4 t + j]       the maxSingle the pairs of table t < 2 were built from (int64), [6 * stride + 8 + t] bit 0: built, bit 1: scalar MinResources
+  //   nodew[nodew_ref_lane(stride, t, j)]  the maxSingle the pairs of table t < 2 were built from (int64), [nodew_ref_flags(stride, t)] bit 0: built, bit 1: scalar MinResources
   uint64_t* nodew;
   uint32_t nodew_stride;
   uint32_t tiles2_min;      // the transposed Filter items take PAIRS of tiles from this many tiles of Filter slots on (filter_loop_t; run_fast: BS_TP_TMIN x ranks)
@@ -885,6 +887,7 @@ __global__ void k_query(PodsDev pods, GroupsDev gr, BatchDev b, BatchParams prm)
 // of the preceding chunks.  kp[s] = first row at which the running sum owns scalar key s.
 // ------------------------------------------------------------------------------------------------
 constexpr int kTblChunk = 256;
+static_assert(kTblChunk == (int)kNodewBlockThreads, "node_words_block runs in launch A's blocks: one thread per node (bs_nodew_layout.hpp)");
 
 // table id t: fit class t % C, percent 1 for t < C (core.go:140), 0.7 otherwise (core.go:161);
 // `forced` != null: a single explicit descriptor (single-query entry points).

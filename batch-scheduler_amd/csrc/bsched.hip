@@ -1981,7 +1981,7 @@ static int reserve_slots(bs_ctx* c, bool run_filter) {
     HIPCHK(c, c->d_uparams.reserve((size_t)filter_cap * 64));
     if ((rc = reserve_filled(c, c->d_uflags, (size_t)filter_cap * 4, 0))) return rc;
     if ((rc = reserve_filled(c, c->d_uclaim, (size_t)filter_cap * 4, 0))) return rc;
-    HIPCHK(c, c->d_nodew.reserve(((size_t)6 * (cdiv(c->N, 64) + 2) + 16) * 8));
+    HIPCHK(c, c->d_nodew.reserve(nodew_alloc_words(c->N) * 8));
   }
   c->scan_slots_cap = scan_cap;
   c->filter_slots_cap = filter_cap;
@@ -2044,6 +2044,12 @@ static int setup_host_out(bs_ctx* c, uint32_t stages, bool run_filter, BatchDev&
 static bool fd_commit_gated(const bs_ctx* c) {
   volatile const int32_t* hf = c->h_info + 14;
   return c->fd_on && (hf[0] || hf[1]);
+}
+// ... or because one of the batch's in-launch waits ran out (k_fast_commit reads the same word, h_info[12]): the batch will be answered with BS_ERR_RETRY
+// by whoever asks for its results (check_handover), so it leaves the group state and the carried leader as it found them — "run the batch again" holds
+// for a committing batch too
+static bool handover_commit_gated(const bs_ctx* c) {
+  return c->h_info && ((volatile const int32_t*)c->h_info)[12] != 0;
 }
 
 // BS_BATCH_FILTER_DENY: the two launches behind a chain's last one (bs_fdeny.hpp).  tail: this chain left tally and completion
@@ -2186,7 +2192,7 @@ static int run_fast(bs_ctx* c, uint32_t stages) {
         HIPCHK(c, hipMemcpyAsync(&last, b.pf_leader + (P - 1), 4, hipMemcpyDeviceToHost, c->stream));
         if (G) HIPCHK(c, hipMemcpyAsync(c->h_gflags.data(), gr.flags, G, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (!fd_commit_gated(c)) c->sop_leader0 = last;
+        if (!fd_commit_gated(c) && !handover_commit_gated(c)) c->sop_leader0 = last;
         c->launches++;
       }
       return batch_collective(c, stages, gr, b);
@@ -2199,13 +2205,13 @@ static int run_fast(bs_ctx* c, uint32_t stages) {
   const bool node_words = run_filter && cdiv(k_est, 64) > 16 && c->tp_filter >= 5u && !c->no_nodew && c->d_nodew.p;
   if (node_words) {
     b.nodew = bt.nodew = c->d_nodew.as<uint64_t>();
-    b.nodew_stride = bt.nodew_stride = W + 2;
+    b.nodew_stride = bt.nodew_stride = nodew_stride(N);
     b.tiles2_min = bt.tiles2_min = c->tp_tmin * std::max<uint32_t>(1u, c->nranks);
   }
   // ---- launch A: per-pod decisions, scan / Filter slots | chunk-local running sums of the table
   TIMED(c, BS_KERNEL_QUERY, {
     const uint32_t qb = cdiv(P, kTblChunk);
-    const dim3 qg(qb + nchunks + (node_words ? cdiv(N, kTblChunk) : 0u)), blk(kTblChunk);
+    const dim3 qg(qb + nchunks + (node_words ? nodew_blocks(N) : 0u)), blk(kTblChunk);
     switch (ts) {
       case 0: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fast_query_tables<0>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb); break;
       case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fast_query_tables<1>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb); break;
@@ -2297,7 +2303,7 @@ static int run_fast(bs_ctx* c, uint32_t stages) {
     HIPCHK(c, hipMemcpyAsync(&last, b.pf_leader + (P - 1), 4, hipMemcpyDeviceToHost, c->stream));
     if (G) HIPCHK(c, hipMemcpyAsync(c->h_gflags.data(), gr.flags, G, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (!fd_commit_gated(c)) c->sop_leader0 = last;   // findMaxPG ignores deny entries and OccupiedBy: the group analysis stays valid
+    if (!fd_commit_gated(c) && !handover_commit_gated(c)) c->sop_leader0 = last;   // findMaxPG ignores deny entries and OccupiedBy: the group analysis stays valid
     c->launches++;
   }
   return batch_collective(c, stages, gr, b);

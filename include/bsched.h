@@ -61,7 +61,8 @@ typedef enum bs_status {
   BS_ERR_COMM = -7,      /* RCCL failure                                              */
   BS_ERR_RETRY = -8      /* (ABI v7) the last batch's results are void for a reason the library has already repaired (the class / pair id
                           * space of a queue patch overflowed and the queue was re-derived; an in-launch hand-over timed out and the context
-                          * went over to separate launches): nothing is wrong with the caller's state — run the batch again.  Distinct from
+                          * went over to separate launches): nothing is wrong with the caller's state — run the batch again (a void BS_BATCH_COMMIT
+                          * batch has committed nothing: group state and the carried leader are those from before it).  Distinct from
                           * BS_ERR_STATE, which bs_batch_map answers for a VALID batch that merely wrote no host results               */
 } bs_status;
 

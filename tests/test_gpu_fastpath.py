@@ -294,3 +294,51 @@ def test_a_timed_out_hand_over_voids_the_batch_and_the_context_goes_back_to_sepa
         assert void_at in (1, 2), void_at
         for _ in range(3):
             assert_batch_equal(ctx.batch(soa.STAGE_ALL), exp, "after the time-out")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("filter_deny", [False, True], ids=["commit", "filter-deny+commit"])
+def test_a_voided_committing_batch_leaves_the_group_state_alone(filter_deny, monkeypatch, bsa, soa, orc):
+    """BS_ERR_RETRY promises that nothing is wrong with the caller's state: run the batch again.  For a BS_BATCH_COMMIT batch that means the void batch
+    committed NOTHING — k_fast_commit reads the context's error word and leaves flags, OccupiedBy and the deny marks alone, and the host does not carry the
+    void batch's leader.  Same test hook as above (it raises the word where the commit kernel looks, in front of its launch).  Committing batches run in step
+    with the oracle until one is answered with BS_ERR_RETRY; then the device's group state is the one from BEFORE that batch, and the batch run again — and the
+    state after it — equal the oracle's for ONE commit.  Between batches the deny entries expire and the gangs' owners let go, so that every commit has something to change."""
+    monkeypatch.setenv("BS_TEST_HANDOVER_TIMEOUT", "2")
+    monkeypatch.delenv("BS_STEP_A", raising=False)
+    nodes, fit, groups, pods, _ = bsa.synth.make("cfg2", "tail")
+    groups.occupied_by[:] = 0                                             # nobody holds a gang yet: the commit writes OccupiedBy (core.go:494-500)
+    what_if = soa.STAGE_ALL | (soa.BATCH_FILTER_DENY if filter_deny else 0)
+    snap = orc.Snapshot(nodes, fit)
+    before, leader = groups.copy(), -1
+
+    def commit_on_device(ctx):
+        ctx.run(what_if | soa.BATCH_COMMIT)
+        return ctx.read(bitmap=False, rows=False)
+
+    with load_ctx(bsa, nodes, fit, groups, pods) as ctx:
+        void_at = None
+        for k in range(4):
+            probe = orc.Sop(snap, before).carry(leader)
+            exp = probe.batch(pods, what_if, bitmap=False)                # (the oracle's Sop mutates its groups: the state ONE commit leaves)
+            assert not probe.groups.state_equal(before), f"batch {k}: the commit changes nothing: a void batch that committed would go unseen"
+            try:
+                got = commit_on_device(ctx)
+            except bsa.capi.BsError as e:
+                assert e.status == -8                                     # BS_ERR_RETRY (include/bsched.h)
+                void_at = k
+                break
+            assert_batch_equal(got, exp, f"batch {k} (in front of the time-out)", bitmap=False)
+            g = ctx.read_groups()
+            assert g.state_equal(probe.groups), f"batch {k}: committed group state"
+            g.flags &= ~np.uint8(soa.GROUP_DENIED)
+            g.occupied_by[:] = 0
+            ctx.load_groups(g)
+            before, leader = g.copy(), probe.leader
+        assert void_at is not None, "no batch was voided"
+        assert ctx.read_groups().state_equal(before), "the void batch changed the group state"
+        assert_batch_equal(commit_on_device(ctx), exp, "the batch again, after the time-out", bitmap=False)
+        assert ctx.read_groups().state_equal(probe.groups), "group state after the batch was run again: not ONE commit"
+        exp_next = probe.batch(pods, what_if, bitmap=False)               # the leader carried out of that ONE commit
+        ctx.run(what_if)
+        assert_batch_equal(ctx.read(bitmap=False, rows=False), exp_next, "the batch behind it", bitmap=False)
