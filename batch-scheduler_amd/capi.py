@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "bs_batch_read_flat", "bs_seq_run_flat", "bs_fit_build_flat",
     "bs_bound_load", "bs_bound_count", "bs_preempt_run", "bs_bound_load_flat", "bs_preempt_run_flat",
     "bs_preempt_commit", "bs_bound_read", "bs_preempt_commit_flat",
+    "bs_bound_pdb_set", "bs_preempt_pdb_read",
 ]
 
 # bsh_phase codes (include/bsched_host.h) of the phases whose gangs PreemptRemovePod protects: Running and Scheduled (core.go:235-238)
@@ -168,6 +169,8 @@ def load_library(path: str | None = None):
     L.bs_preempt_run_flat.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), u32, P(i32), P(u32), P(u32), P(u32), P(i32), P(C.c_int64), P(C.c_int64)]
     L.bs_preempt_commit.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), u32, u32, P(soa.PreemptOutStruct)]
     L.bs_bound_read.argtypes = [vp, P(u32), P(u32)]
+    L.bs_bound_pdb_set.argtypes = [vp, u32, P(u8)]
+    L.bs_preempt_pdb_read.argtypes = [vp, u32, P(u32)]
     L.bs_preempt_commit_flat.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), u32, u32, P(i32), P(u32), P(u32), P(u32), P(i32), P(C.c_int64),
                                          P(C.c_int64)]
     for name in ABI_SYMBOLS:
@@ -519,16 +522,30 @@ class Context:
         assert bound.req.shape[0] == self.L, f"context has {self.L} lanes, bound pods have {bound.req.shape[0]}"
         st = bound.as_struct()
         self._chk(self._lib.bs_bound_load(self._h, C.byref(st)), "bs_bound_load")
+        self._bound_ids = int(bound.b)
 
     def bound_count(self) -> int:
         b = C.c_uint32()
         self._chk(self._lib.bs_bound_count(self._h, C.byref(b)), "bs_bound_count")
         return int(b.value)
 
+    def bound_pdb_set(self, violating, b: int | None = None):
+        """bs_bound_pdb_set: violating[id] != 0 = evicting bound pod `id` (the numbering of the last load_bound) would violate a
+        PodDisruptionBudget (pdb.violating_bits builds the array); None clears every bit.  b defaults to the array's length (to the
+        last load's entry count for None)."""
+        if violating is None:
+            v, ptr = None, None
+        else:
+            v = np.ascontiguousarray(np.asarray(violating).reshape(-1) != 0, np.uint8)
+            ptr = v.ctypes.data_as(C.POINTER(C.c_uint8)) if v.size else None
+        if b is None:
+            b = getattr(self, "_bound_ids", 0) if v is None else int(v.size)
+        self._chk(self._lib.bs_bound_pdb_set(self._h, int(b), ptr), "bs_bound_pdb_set")
+
     def preempt(self, pod_index, priority, group_protected=None, victim_cap: int = 16, stages: int = soa.STAGE_PREFILTER) -> dict:
         """bs_preempt_run: the victim search for every preemptor (resident-queue pod pod_index[q] at priority[q]); group_protected[g]
         from `group_protected(phases)`.  Returns node, n_candidates, n_victims, victims [count, victim_cap] (zero beyond
-        min(n_victims, cap)), top_priority, priority_sum, earliest_start."""
+        min(n_victims, cap)), top_priority, priority_sum, earliest_start, n_pdb_violations (bs_preempt_pdb_read)."""
         return self._preempt_call(None, pod_index, priority, group_protected, victim_cap, stages)
 
     def preempt_commit(self, pod_index, priority, group_protected=None, victim_cap: int = 16, apply: bool = False, assume: bool = False,
@@ -558,8 +575,10 @@ class Context:
         else:
             self._chk(self._lib.bs_preempt_commit(self._h, stages, q, _u32p(pi), pr.ctypes.data_as(C.POINTER(C.c_int32)), gptr, flags, victim_cap,
                                                   C.byref(o)), "bs_preempt_commit")
+        npv = np.zeros(n, np.uint32)
+        self._chk(self._lib.bs_preempt_pdb_read(self._h, q, _u32p(npv)), "bs_preempt_pdb_read")
         return dict(node=node[:q], n_candidates=ncand[:q], n_victims=nv[:q], victims=vic[:q, :victim_cap], top_priority=top[:q],
-                    priority_sum=ssum[:q], earliest_start=est[:q])
+                    priority_sum=ssum[:q], earliest_start=est[:q], n_pdb_violations=npv[:q])
 
     def read_bound(self):
         """bs_bound_read: the live bound table in table order (node ascending, importance order within a node) as (id, node)"""

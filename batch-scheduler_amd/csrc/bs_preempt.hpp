@@ -8,10 +8,13 @@
 //                      list that lies below the tile's highest priority, and the node's bound pods are wave-uniform data (broadcast
 //                      loads).  Each lane keeps its running node requests in VGPRs, walks the suffix twice (remove-all + policy, then
 //                      the reprieve) and keeps its best pick key over the chunk in registers; one record per (preemptor, chunk).
+//                      On a node that holds a PDB-violating pod (bnviol[k] != 0, wave-uniform) the reprieve is two predicated passes
+//                      over the suffix: the violating entries first, then the others (pre_reprieve).
 //   k_preempt_pick<S>  one wave per preemptor: reduces the chunk records (lowest node index wins every tie: records hold node indices,
 //                      and the key ends in the node index), then recomputes the reprieve on the winning node to write the victim list —
 //                      64 bound pods are loaded at a time, one per lane, and every lane replays the same sequential decision from
-//                      broadcast lanes (v_readlane), so the walk costs no dependent memory trip per pod.
+//                      broadcast lanes (v_readlane), so the walk costs no dependent memory trip per pod.  With violating pods on
+//                      the node the same 64-entry windows are replayed twice, violating entries first: the list is in reprieve order.
 // S is a template parameter for EVERY scalar-lane count up to BS_MAX_SCALARS: the request vectors are register arrays indexed by
 // unrolled constants only (no scratch in any instantiation).
 #pragma once
@@ -31,6 +34,8 @@ struct PreemptDev {
   const int32_t* bgroup;    // [b] group index, BS_POD_NOT_GROUPED or BS_POD_GROUP_MISSING
   const int64_t* breq;      // [L][bstride]: lanes 0..2 as loaded, lane 3 = 1 (one pod), scalar lanes 0 where the key is absent
   const uint32_t* bid;      // [b] caller's numbering
+  const uint8_t* bpdb;      // [b] evicting the pod would violate a PodDisruptionBudget (bs_bound_pdb_set)
+  const uint32_t* bnviol;   // [n] entries of the node with that bit: 0 = the node takes the one-pass reprieve
   uint32_t bstride;
   // this call: preemptor slots in priority-descending order
   uint32_t q, nchunks, chunk_nodes, cap;
@@ -41,6 +46,7 @@ struct PreemptDev {
   // chunk records, [nchunks][q]
   int32_t* r_node;
   uint32_t* r_nv;
+  uint32_t* r_npv;
   int32_t* r_top;
   int64_t* r_sum;
   int64_t* r_est;
@@ -49,6 +55,7 @@ struct PreemptDev {
   int32_t* o_node;
   uint32_t* o_ncand;
   uint32_t* o_nv;
+  uint32_t* o_npv;          // PDB-violating victims (bs_preempt_pdb_read)
   int32_t* o_top;
   int64_t* o_sum;
   int64_t* o_est;
@@ -56,20 +63,26 @@ struct PreemptDev {
 };
 
 // pick key of one candidate node (pickOneNodeForPreemption): node < 0 = no candidate
+// top = priority of the FIRST LISTED victim (upstream reads victims.Pods[0]); est = earliest start among the victims of the true
+// maximum priority (GetEarliestPodStartTime walks every victim): with a violating victim in front the two look at different priorities
 struct PreKey {
   int32_t node;
   uint32_t nv;
+  uint32_t npv;             // victims that came from the violating list
   int32_t top;
   int64_t sum;
   int64_t est;
 };
+__device__ __forceinline__ PreKey pre_none() { return PreKey{-1, 0u, 0u, 0, 0, 0}; }
 
 // a strictly better than b: a node without victims wins outright (lowest index among several); otherwise the lexicographically
-// smallest (highest victim priority, sum of priority + 2^31, victim count, -earliest start of the top-priority victims, node index)
+// smallest (PDB violations, first listed victim's priority, sum of priority + 2^31, victim count, -earliest start of the
+// top-priority victims, node index)
 __device__ __forceinline__ bool pre_better(const PreKey& a, const PreKey& b) {
   if (a.node < 0) return false;
   if (b.node < 0) return true;
   if (a.nv == 0 || b.nv == 0) return (a.nv == 0 && b.nv == 0) ? a.node < b.node : a.nv == 0;
+  if (a.npv != b.npv) return a.npv < b.npv;
   if (a.top != b.top) return a.top < b.top;
   if (a.sum != b.sum) return a.sum < b.sum;
   if (a.nv != b.nv) return a.nv < b.nv;
@@ -128,6 +141,48 @@ __device__ __forceinline__ int64_t pre_readlane64(int64_t v, uint32_t i) {
   return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
+// step 5, the reprieve, on the entries [js, b1) of one node from the state `cur` with every potential victim (priority < P) removed;
+// fills kk's victim fields.  pdb = the node holds a violating pod: the entries are offered in two predicated passes, the violating
+// ones first (importance order inside a pass), as upstream's selectVictimsOnNode reprieves violatingVictims before
+// nonViolatingVictims.  Inside a pass the first victim is the most important one; across the passes it is not, so est follows
+// (mx = the true maximum victim priority, earliest start at mx) while top stays with the first listed victim.  Without pdb this is
+// the single pass and the loads it always was.  dead != nullptr: entries an earlier slot evicted (bs_preempt_commit's working
+// state, rewritten inside the launch: a vector load) are skipped.
+template <int S, class D>
+__device__ __forceinline__ void pre_reprieve(const D& pe, uint32_t js, uint32_t b1, int32_t P, bool pdb, const uint8_t* dead, int64_t (&cur)[4 + S],
+                                             const int64_t (&al)[4 + S], uint32_t apres, const int64_t (&rq)[4 + S], uint32_t rpq, PreKey& kk) {
+  constexpr int L = 4 + S;
+  int32_t mx = 0;
+  const uint32_t npass = pdb ? 2u : 1u;
+  for (uint32_t pass = 0; pass < npass; ++pass) {
+    for (uint32_t j = js; j < b1; ++j) {
+      const int32_t pj = pe.bprio[j];
+      if (pj >= P) continue;
+      if (dead && __hip_atomic_load(dead + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) continue;
+      if (pdb && (pe.bpdb[j] != 0) != (pass == 0)) continue;
+      int64_t t[L];
+#pragma unroll
+      for (int l = 0; l < L; ++l) t[l] = wadd(cur[l], pe.breq[(size_t)l * pe.bstride + j]);
+      if (pre_holds<S>(t, al, apres, rq, rpq)) {
+#pragma unroll
+        for (int l = 0; l < L; ++l) cur[l] = t[l];
+      } else {
+        if (kk.nv == 0) {
+          kk.top = pj;
+          mx = pj;
+          kk.est = pe.bstart[j];
+        } else if (pass && pj >= mx) {
+          const int64_t st = pe.bstart[j];
+          if (pj > mx || st < kk.est) { mx = pj; kk.est = st; }
+        }
+        ++kk.nv;
+        kk.npv += (pdb && pass == 0) ? 1u : 0u;
+        kk.sum += (int64_t)pj + 2147483648LL;
+      }
+    }
+  }
+}
+
 template <int S>
 __global__ __launch_bounds__(64) void k_preempt_scan(NodesDev nd, PodsDev pd, PreemptDev pe) {
   constexpr int L = 4 + S;
@@ -144,7 +199,7 @@ __global__ __launch_bounds__(64) void k_preempt_scan(NodesDev nd, PodsDev pd, Pr
   const int32_t qg = pd.group[pi];
   const bool q_grouped = qg != BS_POD_NOT_GROUPED;
   const uint32_t k0 = chunk * pe.chunk_nodes, k1 = min(nd.n, k0 + pe.chunk_nodes);
-  PreKey best{-1, 0u, 0, 0, 0};
+  PreKey best = pre_none();
   uint32_t ncand = 0;
   for (uint32_t k = k0; k < k1; ++k) {
     if (nd.flags[k]) continue;                                                       // step 1: flagged node
@@ -167,29 +222,17 @@ __global__ __launch_bounds__(64) void k_preempt_scan(NodesDev nd, PodsDev pd, Pr
     if (refused || !pre_holds<S>(cur, al, apres, rq, rpq)) continue;
     ++ncand;
     if (best.node >= 0 && best.nv == 0) continue;              // nothing later in the chunk beats a node without victims
-    // step 5: reprieve in importance order
-    PreKey kk{(int32_t)k, 0u, 0, 0, 0};
-    for (uint32_t j = js; j < b1; ++j) {
-      const int32_t pj = pe.bprio[j];
-      if (pj >= P) continue;
-      int64_t t[L];
-#pragma unroll
-      for (int l = 0; l < L; ++l) t[l] = wadd(cur[l], pe.breq[(size_t)l * pe.bstride + j]);
-      if (pre_holds<S>(t, al, apres, rq, rpq)) {
-#pragma unroll
-        for (int l = 0; l < L; ++l) cur[l] = t[l];
-      } else {
-        if (kk.nv == 0) { kk.top = pj; kk.est = pe.bstart[j]; }
-        ++kk.nv;
-        kk.sum += (int64_t)pj + 2147483648LL;
-      }
-    }
+    // step 5: reprieve in importance order, the violating entries first where the node has any.  (The early-out above stays valid
+    // with PDBs: a node without victims still wins outright, whatever the others' violation counts.)
+    PreKey kk{(int32_t)k, 0u, 0u, 0, 0, 0};
+    pre_reprieve<S>(pe, js, b1, P, pe.bnviol[k] != 0, nullptr, cur, al, apres, rq, rpq, kk);
     if (pre_better(kk, best)) best = kk;
   }
   if (valid) {
     const size_t r = (size_t)chunk * pe.q + slot;
     pe.r_node[r] = best.node;
     pe.r_nv[r] = best.nv;
+    pe.r_npv[r] = best.npv;
     pe.r_top[r] = best.top;
     pe.r_sum[r] = best.sum;
     pe.r_est[r] = best.est;
@@ -203,11 +246,11 @@ __global__ __launch_bounds__(64) void k_preempt_pick(NodesDev nd, PodsDev pd, Pr
   __shared__ PreKey sk[64];
   __shared__ uint32_t sc[64];
   const uint32_t slot = blockIdx.x, lane = threadIdx.x;
-  PreKey best{-1, 0u, 0, 0, 0};
+  PreKey best = pre_none();
   uint32_t ncand = 0;
   for (uint32_t c = lane; c < pe.nchunks; c += 64u) {
     const size_t r = (size_t)c * pe.q + slot;
-    const PreKey kk{pe.r_node[r], pe.r_nv[r], pe.r_top[r], pe.r_sum[r], pe.r_est[r]};
+    const PreKey kk{pe.r_node[r], pe.r_nv[r], pe.r_npv[r], pe.r_top[r], pe.r_sum[r], pe.r_est[r]};
     ncand += pe.r_ncand[r];
     if (pre_better(kk, best)) best = kk;
   }
@@ -229,6 +272,7 @@ __global__ __launch_bounds__(64) void k_preempt_pick(NodesDev nd, PodsDev pd, Pr
     pe.o_node[orig] = best.node;
     pe.o_ncand[orig] = ncand;
     pe.o_nv[orig] = none ? 0u : best.nv;
+    pe.o_npv[orig] = none ? 0u : best.npv;
     pe.o_top[orig] = none ? 0 : best.top;
     pe.o_sum[orig] = none ? 0 : best.sum;
     pe.o_est[orig] = none ? 0 : best.est;
@@ -258,25 +302,33 @@ __global__ __launch_bounds__(64) void k_preempt_pick(NodesDev nd, PodsDev pd, Pr
   }
   uint32_t nv = 0;
   uint32_t* vout = pe.o_victims + (size_t)orig * pe.cap;
-  for (uint32_t base = js; base < b1; base += 64u) {
-    const uint32_t j = base + lane;
-    const bool have = j < b1;
-    int64_t mine[L];
+  // two passes over the same windows where the node holds violating pods (the violating entries first): the list is in reprieve order
+  const bool pdb = pe.bnviol[k] != 0;
+  const uint32_t npass = pdb ? 2u : 1u;
+  for (uint32_t pass = 0; pass < npass; ++pass) {
+    for (uint32_t base = js; base < b1; base += 64u) {
+      const uint32_t j = base + lane;
+      const bool have = j < b1 && (!pdb || (pe.bpdb[j] != 0) == (pass == 0));
+      uint64_t live = __ballot(have);
+      if (!live) continue;
+      int64_t mine[L];
 #pragma unroll
-    for (int l = 0; l < L; ++l) mine[l] = have ? pe.breq[(size_t)l * pe.bstride + j] : 0;
-    const uint32_t myid = have ? pe.bid[j] : 0u;
-    const uint32_t cnt = min(64u, b1 - base);
-    for (uint32_t i = 0; i < cnt; ++i) {
-      int64_t t[L];
+      for (int l = 0; l < L; ++l) mine[l] = have ? pe.breq[(size_t)l * pe.bstride + j] : 0;
+      const uint32_t myid = have ? pe.bid[j] : 0u;
+      while (live) {
+        const uint32_t i = (uint32_t)__builtin_ctzll(live);
+        live &= live - 1;
+        int64_t t[L];
 #pragma unroll
-      for (int l = 0; l < L; ++l) t[l] = wadd(cur[l], pre_readlane64(mine[l], i));
-      if (pre_holds<S>(t, al, apres, rq, rpq)) {
+        for (int l = 0; l < L; ++l) t[l] = wadd(cur[l], pre_readlane64(mine[l], i));
+        if (pre_holds<S>(t, al, apres, rq, rpq)) {
 #pragma unroll
-        for (int l = 0; l < L; ++l) cur[l] = t[l];
-      } else {
-        const uint32_t vid = (uint32_t)__builtin_amdgcn_readlane((int)myid, (int)i);
-        if (lane == 0 && nv < pe.cap) vout[nv] = vid;
-        ++nv;
+          for (int l = 0; l < L; ++l) cur[l] = t[l];
+        } else {
+          const uint32_t vid = (uint32_t)__builtin_amdgcn_readlane((int)myid, (int)i);
+          if (lane == 0 && nv < pe.cap) vout[nv] = vid;
+          ++nv;
+        }
       }
     }
   }

@@ -19,6 +19,9 @@
 //   k_pc_nodes<S>    APPLY: the dirty nodes' new absolute request vectors (bs_node_request records) for k_nodes_assume.
 //   k_pc_boff<S>     APPLY: survivors per node (boff length minus the victims counted in dv's pods lane), exclusive scan: new CSR.
 //   k_pc_compact<S>  APPLY: one wave per node, a stable ballot compaction of every column into the new table.
+// PDB bits (bpdb, bnviol; include/bsched.h, bs_bound_pdb_set) are fixed for the whole call.  The records are ordered by pre_better with the
+// violation count in front, so the clean-chunk argument above holds for the widened key as it did for the old one; pc_eval and the victim
+// list use bs_preempt.hpp's two-pass reprieve; k_pc_compact carries the column and recounts bnviol for the survivors.
 // S is a template parameter for every scalar-lane count: register arrays are indexed by unrolled constants only (no scratch).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -42,6 +45,8 @@ struct CommitDev {
   const int64_t* breq;      // [L][bstride]
   const uint32_t* bid;
   const uint32_t* bpres;
+  const uint8_t* bpdb;      // [b] PDB-violating bit (bs_bound_pdb_set): fixed for the whole call, whatever earlier slots evict
+  const uint32_t* bnviol;   // [n] entries of the node with the bit in the table as loaded (dead ones included: a shortcut only)
   uint32_t bstride;
   // this call: slots in priority-descending order (stable)
   uint32_t q, nchunks, chunk_nodes, cap;
@@ -52,6 +57,7 @@ struct CommitDev {
   // records [nchunks][q][kPcK] (node -1 ends a record) and [nchunks][q] candidate counts
   int32_t* r_node;
   uint32_t* r_nv;
+  uint32_t* r_npv;
   int32_t* r_top;
   int64_t* r_sum;
   int64_t* r_est;
@@ -69,6 +75,7 @@ struct CommitDev {
   int32_t* o_node;
   uint32_t* o_ncand;
   uint32_t* o_nv;
+  uint32_t* o_npv;
   int32_t* o_top;
   int64_t* o_sum;
   int64_t* o_est;
@@ -84,6 +91,8 @@ struct CompactDev {
   int64_t* breq;
   uint32_t* bid;
   uint32_t* bpres;
+  uint8_t* bpdb;
+  uint32_t* bnviol;
   uint32_t bstride;
 };
 
@@ -122,7 +131,7 @@ __global__ __launch_bounds__(64) void k_pc_scan(NodesDev nd, PodsDev pd, CommitD
   const uint32_t k0 = chunk * pe.chunk_nodes, k1 = min(nd.n, k0 + pe.chunk_nodes);
   PreKey top[kPcK];
 #pragma unroll
-  for (int i = 0; i < kPcK; ++i) top[i] = PreKey{-1, 0u, 0, 0, 0};
+  for (int i = 0; i < kPcK; ++i) top[i] = pre_none();
   uint32_t ncand = 0;
   for (uint32_t k = k0; k < k1; ++k) {
     if (nd.flags[k]) continue;
@@ -144,22 +153,9 @@ __global__ __launch_bounds__(64) void k_pc_scan(NodesDev nd, PodsDev pd, CommitD
     if (refused || !pre_holds<S>(cur, al, apres, rq, rpq)) continue;
     ++ncand;
     if (top[kPcK - 1].node >= 0 && top[kPcK - 1].nv == 0) continue;   // kPcK nodes without victims: nothing later in the chunk enters
-    PreKey kk{(int32_t)k, 0u, 0, 0, 0};
-    for (uint32_t j = js; j < b1; ++j) {
-      const int32_t pj = pe.bprio[j];
-      if (pj >= P) continue;
-      int64_t t[L];
-#pragma unroll
-      for (int l = 0; l < L; ++l) t[l] = wadd(cur[l], pe.breq[(size_t)l * pe.bstride + j]);
-      if (pre_holds<S>(t, al, apres, rq, rpq)) {
-#pragma unroll
-        for (int l = 0; l < L; ++l) cur[l] = t[l];
-      } else {
-        if (kk.nv == 0) { kk.top = pj; kk.est = pe.bstart[j]; }
-        ++kk.nv;
-        kk.sum += (int64_t)pj + 2147483648LL;
-      }
-    }
+    // (kPcK victim-free nodes fill the record whatever violation counts later nodes have: a victim-free node wins outright)
+    PreKey kk{(int32_t)k, 0u, 0u, 0, 0, 0};
+    pre_reprieve<S>(pe, js, b1, P, pe.bnviol[k] != 0, nullptr, cur, al, apres, rq, rpq, kk);
     pc_insert(top, kk);
   }
   if (valid) {
@@ -168,6 +164,7 @@ __global__ __launch_bounds__(64) void k_pc_scan(NodesDev nd, PodsDev pd, CommitD
     for (int i = 0; i < kPcK; ++i) {
       pe.r_node[r * kPcK + i] = top[i].node;
       pe.r_nv[r * kPcK + i] = top[i].nv;
+      pe.r_npv[r * kPcK + i] = top[i].npv;
       pe.r_top[r * kPcK + i] = top[i].top;
       pe.r_sum[r * kPcK + i] = top[i].sum;
       pe.r_est[r * kPcK + i] = top[i].est;
@@ -182,7 +179,7 @@ template <int S>
 __device__ bool pc_eval(const NodesDev& nd, const CommitDev& pe, uint32_t k, int32_t P, const int64_t (&rq)[4 + S], uint32_t rpq, uint32_t cls,
                         int32_t qg, bool dirty, PreKey& key, int32_t& dcand) {
   constexpr int L = 4 + S;
-  key = PreKey{-1, 0u, 0, 0, 0};
+  key = pre_none();
   if (nd.flags[k]) return false;
   if (cls >= nd.n_classes || !((nd.fit[(size_t)cls * nd.fit_words + (k >> 5)] >> (k & 31u)) & 1u)) return false;
   const bool q_grouped = qg != BS_POD_NOT_GROUPED;
@@ -217,21 +214,7 @@ __device__ bool pc_eval(const NodesDev& nd, const CommitDev& pe, uint32_t k, int
   if (refused || !pre_holds<S>(cur, al, apres, rq, rpq)) return false;
   if (dirty) dcand += 1;
   key.node = (int32_t)k;
-  for (uint32_t j = js; j < b1; ++j) {
-    if (dirty && pc_ld8(pe.dead + j)) continue;
-    const int32_t pj = pe.bprio[j];
-    int64_t t[L];
-#pragma unroll
-    for (int l = 0; l < L; ++l) t[l] = wadd(cur[l], pe.breq[(size_t)l * pe.bstride + j]);
-    if (pre_holds<S>(t, al, apres, rq, rpq)) {
-#pragma unroll
-      for (int l = 0; l < L; ++l) cur[l] = t[l];
-    } else {
-      if (key.nv == 0) { key.top = pj; key.est = pe.bstart[j]; }
-      ++key.nv;
-      key.sum += (int64_t)pj + 2147483648LL;
-    }
-  }
+  pre_reprieve<S>(pe, js, b1, P, pe.bnviol[k] != 0, dirty ? pe.dead : nullptr, cur, al, apres, rq, rpq, key);
   return true;
 }
 
@@ -239,6 +222,7 @@ __device__ __forceinline__ PreKey pc_shfl(const PreKey& a, int off) {
   PreKey b;
   b.node = __shfl_xor(a.node, off, 64);
   b.nv = (uint32_t)__shfl_xor((int)a.nv, off, 64);
+  b.npv = (uint32_t)__shfl_xor((int)a.npv, off, 64);
   b.top = __shfl_xor(a.top, off, 64);
   b.sum = (int64_t)__shfl_xor((long long)a.sum, off, 64);
   b.est = (int64_t)__shfl_xor((long long)a.est, off, 64);
@@ -267,7 +251,7 @@ __global__ __launch_bounds__(pc_threads<S>()) void k_pc_resolve(NodesDev nd, Pod
     const uint32_t cls = pd.cls[pi];
     const int32_t qg = pd.group[pi];
     // A: the records.  A chunk's best clean entry; a chunk with no clean entry among more than kPcK candidates goes to the rescan list
-    PreKey best{-1, 0u, 0, 0, 0};
+    PreKey best = pre_none();
     int32_t dc = 0;
     uint32_t pending = 0;                          // rescans this thread could not list (list full): done by this thread below
     for (uint32_t c = t; c < pe.nchunks; c += kPcThreads) {
@@ -278,7 +262,7 @@ __global__ __launch_bounds__(pc_threads<S>()) void k_pc_resolve(NodesDev nd, Pod
       for (int i = 0; i < kPcK; ++i) {
         const int32_t node = pe.r_node[r * kPcK + i];
         if (!found && node >= 0 && !pc_ld8(pe.dirty + node)) {
-          const PreKey kk{node, pe.r_nv[r * kPcK + i], pe.r_top[r * kPcK + i], pe.r_sum[r * kPcK + i], pe.r_est[r * kPcK + i]};
+          const PreKey kk{node, pe.r_nv[r * kPcK + i], pe.r_npv[r * kPcK + i], pe.r_top[r * kPcK + i], pe.r_sum[r * kPcK + i], pe.r_est[r * kPcK + i]};
           if (pre_better(kk, best)) best = kk;
           found = true;
         }
@@ -339,7 +323,7 @@ __global__ __launch_bounds__(pc_threads<S>()) void k_pc_resolve(NodesDev nd, Pod
     if (lane == 0) { s_key[wave] = best; s_dc[wave] = dc; }
     __syncthreads();
     if (wave == 0) {
-      best = lane < (uint32_t)kWaves ? s_key[lane] : PreKey{-1, 0u, 0, 0, 0};
+      best = lane < (uint32_t)kWaves ? s_key[lane] : pre_none();
       dc = lane < (uint32_t)kWaves ? s_dc[lane] : 0;
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) {
@@ -353,6 +337,7 @@ __global__ __launch_bounds__(pc_threads<S>()) void k_pc_resolve(NodesDev nd, Pod
         pe.o_node[orig] = best.node;
         pe.o_ncand[orig] = (uint32_t)dc;
         pe.o_nv[orig] = none ? 0u : best.nv;
+        pe.o_npv[orig] = none ? 0u : best.npv;
         pe.o_top[orig] = none ? 0 : best.top;
         pe.o_sum[orig] = none ? 0 : best.sum;
         pe.o_est[orig] = none ? 0 : best.est;
@@ -393,35 +378,41 @@ __global__ __launch_bounds__(pc_threads<S>()) void k_pc_resolve(NodesDev nd, Pod
         }
         uint32_t nv = 0;
         uint32_t* vout = pe.o_victims + (size_t)orig * pe.cap;
-        for (uint32_t base = js; base < b1; base += 64u) {
-          const uint32_t j = base + lane;
-          const bool have = j < b1 && !pc_ld8(pe.dead + j);
-          int64_t mine[L];
+        // two passes over the same windows where the node holds violating pods (the violating entries first): reprieve order
+        const bool pdb = pe.bnviol[k] != 0;
+        const uint32_t npass = pdb ? 2u : 1u;
+        for (uint32_t pass = 0; pass < npass; ++pass) {
+          for (uint32_t base = js; base < b1; base += 64u) {
+            const uint32_t j = base + lane;
+            const bool have = j < b1 && !pc_ld8(pe.dead + j) && (!pdb || (pe.bpdb[j] != 0) == (pass == 0));
+            uint64_t live = __ballot(have);
+            if (!live) continue;
+            int64_t mine[L];
 #pragma unroll
-          for (int l = 0; l < L; ++l) mine[l] = have ? pe.breq[(size_t)l * pe.bstride + j] : 0;
-          const uint32_t myid = have ? pe.bid[j] : 0u, mypres = have ? pe.bpres[j] : 0u;
-          uint64_t live = __ballot(have);
-          uint64_t vmask = 0;
-          while (live) {
-            const uint32_t i = (uint32_t)__builtin_ctzll(live);
-            live &= live - 1;
-            int64_t tt[L];
+            for (int l = 0; l < L; ++l) mine[l] = have ? pe.breq[(size_t)l * pe.bstride + j] : 0;
+            const uint32_t myid = have ? pe.bid[j] : 0u, mypres = have ? pe.bpres[j] : 0u;
+            uint64_t vmask = 0;
+            while (live) {
+              const uint32_t i = (uint32_t)__builtin_ctzll(live);
+              live &= live - 1;
+              int64_t tt[L];
 #pragma unroll
-            for (int l = 0; l < L; ++l) tt[l] = wadd(cur[l], pre_readlane64(mine[l], i));
-            if (pre_holds<S>(tt, al, apres, rq, rpq)) {
+              for (int l = 0; l < L; ++l) tt[l] = wadd(cur[l], pre_readlane64(mine[l], i));
+              if (pre_holds<S>(tt, al, apres, rq, rpq)) {
 #pragma unroll
-              for (int l = 0; l < L; ++l) cur[l] = tt[l];
-            } else {
-              const uint32_t vid = (uint32_t)__builtin_amdgcn_readlane((int)myid, (int)i);
-              if (lane == 0 && nv < pe.cap) vout[nv] = vid;
-              ++nv;
-              vmask |= 1ull << i;
+                for (int l = 0; l < L; ++l) cur[l] = tt[l];
+              } else {
+                const uint32_t vid = (uint32_t)__builtin_amdgcn_readlane((int)myid, (int)i);
+                if (lane == 0 && nv < pe.cap) vout[nv] = vid;
+                ++nv;
+                vmask |= 1ull << i;
 #pragma unroll
-              for (int l = 0; l < L; ++l) vsum[l] = wadd(vsum[l], pre_readlane64(mine[l], i));
-              vb |= (uint32_t)__builtin_amdgcn_readlane((int)mypres, (int)i);
+                for (int l = 0; l < L; ++l) vsum[l] = wadd(vsum[l], pre_readlane64(mine[l], i));
+                vb |= (uint32_t)__builtin_amdgcn_readlane((int)mypres, (int)i);
+              }
             }
+            if ((vmask >> lane) & 1ull) pe.dead[j] = 1;
           }
-          if ((vmask >> lane) & 1ull) pe.dead[j] = 1;
         }
         // commit: the victims leave (RemovePod), the preemptor is nominated on the node (AddPod)
         const uint32_t smask = S > 0 ? (uint32_t)((1ull << S) - 1ull) : 0u;
@@ -516,10 +507,13 @@ __global__ __launch_bounds__(64) void k_pc_compact(CommitDev pe, CompactDev nw, 
   const uint32_t b0 = pe.boff[k], b1 = pe.boff[k + 1];
   uint32_t dst = nw.boff[k];
   const bool any_dead = pe.dirty[k] != 0;
+  uint32_t nviol = 0;
   for (uint32_t base = b0; base < b1; base += 64u) {
     const uint32_t j = base + lane;
     const bool keep = j < b1 && !(any_dead && pe.dead[j]);
+    const uint8_t pdb = keep ? pe.bpdb[j] : (uint8_t)0;
     const uint64_t m = __ballot(keep);
+    nviol += (uint32_t)__builtin_popcountll(__ballot(pdb != 0));
     const uint32_t rank = (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
     if (keep) {
       const uint32_t d = dst + rank;
@@ -528,11 +522,13 @@ __global__ __launch_bounds__(64) void k_pc_compact(CommitDev pe, CompactDev nw, 
       nw.bgroup[d] = pe.bgroup[j];
       nw.bid[d] = pe.bid[j];
       nw.bpres[d] = pe.bpres[j];
+      nw.bpdb[d] = pdb;
 #pragma unroll
       for (int l = 0; l < L; ++l) nw.breq[(size_t)l * nw.bstride + d] = pe.breq[(size_t)l * pe.bstride + j];
     }
     dst += (uint32_t)__builtin_popcountll(m);
   }
+  if (lane == 0) nw.bnviol[k] = nviol;        // the survivors' count: a node whose violating pods all left is one-pass again
 }
 
 }  // namespace bs

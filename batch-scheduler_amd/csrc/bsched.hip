@@ -318,7 +318,10 @@ struct bs_ctx {
   int32_t bound_max_group = -1;      // largest group index the table names (checked against the group count per call)
   DevBuf d_bound, d_pre;
   DevBuf d_bound2;                   // bs_preempt_commit's compaction target (swapped with d_bound)
-  size_t off_boff = 0, off_bprio = 0, off_bstart = 0, off_bgroup = 0, off_bid = 0, off_breq = 0, off_bpres = 0;
+  size_t off_boff = 0, off_bprio = 0, off_bstart = 0, off_bgroup = 0, off_bid = 0, off_breq = 0, off_bpres = 0, off_bpdb = 0, off_bnviol = 0;
+  uint32_t bound_ids = 0;            // entries at the last bs_bound_load: the id space of bs_bound_pdb_set
+  std::vector<uint32_t> pre_npv;     // PDB-violating victims per preemptor of the last preemption call (bs_preempt_pdb_read)
+  bool have_pre_npv = false;
 };
 
 namespace {
@@ -3864,7 +3867,7 @@ int bs_batch_stats_get(bs_ctx* c, bs_batch_stats* out) {
 // gang-aware preemption (bs_preempt.hpp): the resident bound-pod table and the batched victim search
 // -------------------------------------------------------------------------------------------------
 // the bound table's one allocation for N nodes and B entries (columns at 256-byte offsets; breq lane stride max(B, 1)); returns its size
-struct BoundLayout { size_t boff, prio, start, group, id, req, pres; };
+struct BoundLayout { size_t boff, prio, start, group, id, req, pres, pdb, nviol; };
 static size_t bound_layout(uint32_t L, uint32_t N, uint32_t B, BoundLayout& b) {
   const size_t nB = std::max<uint32_t>(B, 1);
   size_t o = 0;
@@ -3875,11 +3878,13 @@ static size_t bound_layout(uint32_t L, uint32_t N, uint32_t B, BoundLayout& b) {
   b.id = o; o = align256(o + nB * 4);
   b.req = o; o = align256(o + nB * L * 8);
   b.pres = o; o = align256(o + nB * 4);      // scalar keys of each entry (bs_preempt_commit sets them on the node)
+  b.pdb = o; o = align256(o + nB);           // PDB-violating bit of each entry (bs_bound_pdb_set)
+  b.nviol = o; o = align256(o + std::max<size_t>(N, 1) * 4);   // entries with the bit per node
   return o;
 }
 static void bound_layout_set(bs_ctx* c, const BoundLayout& b) {
   c->off_boff = b.boff; c->off_bprio = b.prio; c->off_bstart = b.start; c->off_bgroup = b.group; c->off_bid = b.id; c->off_breq = b.req;
-  c->off_bpres = b.pres;
+  c->off_bpres = b.pres; c->off_bpdb = b.pdb; c->off_bnviol = b.nviol;
 }
 
 int bs_bound_load(bs_ctx* c, const bs_bound_soa* bd) {
@@ -3943,9 +3948,50 @@ int bs_bound_load(bs_ctx* c, const bs_bound_soa* bd) {
   HIPCHK(c, hipMemcpyAsync(c->d_bound.p, h.data(), o, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));             // (h is a local buffer)
   c->bound_b = B;
+  c->bound_ids = B;
   c->bound_n = N;
   c->bound_max_group = gmax;
-  c->have_bound = true;
+  c->have_bound = true;                                   // (h was zeroed: every PDB bit is clear)
+  return BS_OK;
+}
+
+int bs_bound_pdb_set(bs_ctx* c, uint32_t b, const uint8_t* violating) {
+  if (!c) return BS_ERR_INVALID;
+  if (!c->have_bound) { c->last_error = "bs_bound_pdb_set before bs_bound_load"; return BS_ERR_STATE; }
+  if (b != c->bound_ids) { c->last_error = "bs_bound_pdb_set: b differs from the last bs_bound_load's entry count"; return BS_ERR_INVALID; }
+  const uint32_t B = c->bound_b, N = c->bound_n;
+  int rc = use_device(c);
+  if (rc) return rc;
+  uint8_t* bb = c->d_bound.as<uint8_t>();
+  const size_t nB = std::max<uint32_t>(B, 1), nN = std::max<uint32_t>(N, 1);
+  // the two columns are rebuilt on the host through the id column (the id -> position map; evicted ids are not in it) and copied in
+  // stream order, behind whatever preemption call is still running
+  std::vector<uint8_t> bits(nB, 0);
+  std::vector<uint32_t> nviol(nN, 0);
+  if (violating && B) {
+    std::vector<uint32_t> boff((size_t)N + 1), id(B);
+    HIPCHK(c, hipMemcpyAsync(boff.data(), bb + c->off_boff, ((size_t)N + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(id.data(), bb + c->off_bid, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t k = 0; k < N; ++k)
+      for (uint32_t j = boff[k]; j < boff[k + 1] && j < B; ++j) {
+        bits[j] = id[j] < b && violating[id[j]] ? 1 : 0;
+        nviol[k] += bits[j];
+      }
+  }
+  HIPCHK(c, hipMemcpyAsync(bb + c->off_bpdb, bits.data(), nB, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(bb + c->off_bnviol, nviol.data(), nN * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));             // (local buffers)
+  return BS_OK;
+}
+
+int bs_preempt_pdb_read(bs_ctx* c, uint32_t count, uint32_t* n_pdb_violations) {
+  if (!c) return BS_ERR_INVALID;
+  if (!c->have_pre_npv) { c->last_error = "bs_preempt_pdb_read before a successful bs_preempt_run / bs_preempt_commit"; return BS_ERR_STATE; }
+  if (count != c->pre_npv.size()) { c->last_error = "bs_preempt_pdb_read: count differs from the last preemption call's"; return BS_ERR_INVALID; }
+  if (count == 0) return BS_OK;
+  if (!n_pdb_violations) return BS_ERR_INVALID;
+  std::memcpy(n_pdb_violations, c->pre_npv.data(), (size_t)count * 4);
   return BS_OK;
 }
 
@@ -3966,7 +4012,7 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   if (c->nranks > 1 || c->reduce_external) { c->last_error = "bs_preempt_run is single-rank only"; return BS_ERR_STATE; }
   if (c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
   if (count > BS_PREEMPT_MAX || (uint64_t)count * victim_cap > (1ull << 28)) return BS_ERR_CAPACITY;
-  if (count == 0) return BS_OK;
+  if (count == 0) { c->pre_npv.clear(); c->have_pre_npv = true; return BS_OK; }
   if (!pod_index || !priority || !out->node || !out->n_victims || (victim_cap && !out->victims) || (c->G && !group_protected)) return BS_ERR_INVALID;
   if (c->bound_max_group >= (int32_t)c->G) { c->last_error = "the bound table names a group index >= the loaded group count"; return BS_ERR_INVALID; }
   const uint32_t P = c->P, N = c->N, G = c->G;
@@ -3992,6 +4038,7 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   const size_t in_bytes = o;
   const size_t o_rnode = o; o = align256(o + nR * 4);
   const size_t o_rnv = o; o = align256(o + nR * 4);
+  const size_t o_rnpv = o; o = align256(o + nR * 4);
   const size_t o_rtop = o; o = align256(o + nR * 4);
   const size_t o_rsum = o; o = align256(o + nR * 8);
   const size_t o_rest = o; o = align256(o + nR * 8);
@@ -4000,6 +4047,7 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   const size_t o_node = o; o = align256(o + nQ * 4);
   const size_t o_ncand = o; o = align256(o + nQ * 4);
   const size_t o_nv = o; o = align256(o + nQ * 4);
+  const size_t o_npv = o; o = align256(o + nQ * 4);
   const size_t o_top = o; o = align256(o + nQ * 4);
   const size_t o_sum = o; o = align256(o + nQ * 8);
   const size_t o_est = o; o = align256(o + nQ * 8);
@@ -4025,6 +4073,8 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   pe.bgroup = reinterpret_cast<const int32_t*>(bb + c->off_bgroup);
   pe.bid = reinterpret_cast<const uint32_t*>(bb + c->off_bid);
   pe.breq = reinterpret_cast<const int64_t*>(bb + c->off_breq);
+  pe.bpdb = bb + c->off_bpdb;
+  pe.bnviol = reinterpret_cast<const uint32_t*>(bb + c->off_bnviol);
   pe.bstride = std::max<uint32_t>(c->bound_b, 1);
   pe.q = count;
   pe.nchunks = nchunks;
@@ -4036,6 +4086,7 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   pe.gprot = base + o_gprot;
   pe.r_node = reinterpret_cast<int32_t*>(base + o_rnode);
   pe.r_nv = reinterpret_cast<uint32_t*>(base + o_rnv);
+  pe.r_npv = reinterpret_cast<uint32_t*>(base + o_rnpv);
   pe.r_top = reinterpret_cast<int32_t*>(base + o_rtop);
   pe.r_sum = reinterpret_cast<int64_t*>(base + o_rsum);
   pe.r_est = reinterpret_cast<int64_t*>(base + o_rest);
@@ -4043,6 +4094,7 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   pe.o_node = reinterpret_cast<int32_t*>(base + o_node);
   pe.o_ncand = reinterpret_cast<uint32_t*>(base + o_ncand);
   pe.o_nv = reinterpret_cast<uint32_t*>(base + o_nv);
+  pe.o_npv = reinterpret_cast<uint32_t*>(base + o_npv);
   pe.o_top = reinterpret_cast<int32_t*>(base + o_top);
   pe.o_sum = reinterpret_cast<int64_t*>(base + o_sum);
   pe.o_est = reinterpret_cast<int64_t*>(base + o_est);
@@ -4055,6 +4107,8 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   const uint8_t* rb = res.data() - o_res;
   std::memcpy(out->node, rb + o_node, nQ * 4);
   std::memcpy(out->n_victims, rb + o_nv, nQ * 4);
+  c->pre_npv.assign(reinterpret_cast<const uint32_t*>(rb + o_npv), reinterpret_cast<const uint32_t*>(rb + o_npv) + nQ);
+  c->have_pre_npv = true;
   if (out->n_candidates) std::memcpy(out->n_candidates, rb + o_ncand, nQ * 4);
   if (out->top_priority) std::memcpy(out->top_priority, rb + o_top, nQ * 4);
   if (out->priority_sum) std::memcpy(out->priority_sum, rb + o_sum, nQ * 8);
@@ -4102,7 +4156,7 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
   if (c->nranks > 1 || c->reduce_external) { c->last_error = "bs_preempt_commit is single-rank only"; return BS_ERR_STATE; }
   if (c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
   if (count > BS_PREEMPT_MAX || (uint64_t)count * victim_cap > (1ull << 28)) return BS_ERR_CAPACITY;
-  if (count == 0) return BS_OK;
+  if (count == 0) { c->pre_npv.clear(); c->have_pre_npv = true; return BS_OK; }
   if (!pod_index || !priority || !out->node || !out->n_victims || (victim_cap && !out->victims) || (c->G && !group_protected)) return BS_ERR_INVALID;
   if (c->bound_max_group >= (int32_t)c->G) { c->last_error = "the bound table names a group index >= the loaded group count"; return BS_ERR_INVALID; }
   const uint32_t P = c->P, N = c->N, G = c->G, L = c->L, B = c->bound_b;
@@ -4134,6 +4188,7 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
   const size_t in_bytes = o;
   const size_t o_rnode = o; o = align256(o + nR * kPcK * 4);
   const size_t o_rnv = o; o = align256(o + nR * kPcK * 4);
+  const size_t o_rnpv = o; o = align256(o + nR * kPcK * 4);
   const size_t o_rtop = o; o = align256(o + nR * kPcK * 4);
   const size_t o_rsum = o; o = align256(o + nR * kPcK * 8);
   const size_t o_rest = o; o = align256(o + nR * kPcK * 8);
@@ -4153,6 +4208,7 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
   const size_t o_node = o; o = align256(o + nQ * 4);
   const size_t o_ncand = o; o = align256(o + nQ * 4);
   const size_t o_nv = o; o = align256(o + nQ * 4);
+  const size_t o_npv = o; o = align256(o + nQ * 4);
   const size_t o_top = o; o = align256(o + nQ * 4);
   const size_t o_sum = o; o = align256(o + nQ * 8);
   const size_t o_est = o; o = align256(o + nQ * 8);
@@ -4180,6 +4236,8 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
   pe.bid = reinterpret_cast<const uint32_t*>(bb + c->off_bid);
   pe.breq = reinterpret_cast<const int64_t*>(bb + c->off_breq);
   pe.bpres = reinterpret_cast<const uint32_t*>(bb + c->off_bpres);
+  pe.bpdb = bb + c->off_bpdb;
+  pe.bnviol = reinterpret_cast<const uint32_t*>(bb + c->off_bnviol);
   pe.bstride = (uint32_t)nB;
   pe.q = count;
   pe.nchunks = nchunks;
@@ -4191,6 +4249,7 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
   pe.gprot = base + o_gprot;
   pe.r_node = reinterpret_cast<int32_t*>(base + o_rnode);
   pe.r_nv = reinterpret_cast<uint32_t*>(base + o_rnv);
+  pe.r_npv = reinterpret_cast<uint32_t*>(base + o_rnpv);
   pe.r_top = reinterpret_cast<int32_t*>(base + o_rtop);
   pe.r_sum = reinterpret_cast<int64_t*>(base + o_rsum);
   pe.r_est = reinterpret_cast<int64_t*>(base + o_rest);
@@ -4206,6 +4265,7 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
   pe.o_node = reinterpret_cast<int32_t*>(base + o_node);
   pe.o_ncand = reinterpret_cast<uint32_t*>(base + o_ncand);
   pe.o_nv = reinterpret_cast<uint32_t*>(base + o_nv);
+  pe.o_npv = reinterpret_cast<uint32_t*>(base + o_npv);
   pe.o_top = reinterpret_cast<int32_t*>(base + o_top);
   pe.o_sum = reinterpret_cast<int64_t*>(base + o_sum);
   pe.o_est = reinterpret_cast<int64_t*>(base + o_est);
@@ -4234,6 +4294,8 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
       nw.bid = reinterpret_cast<uint32_t*>(b2 + lay.id);
       nw.breq = reinterpret_cast<int64_t*>(b2 + lay.req);
       nw.bpres = reinterpret_cast<uint32_t*>(b2 + lay.pres);
+      nw.bpdb = b2 + lay.pdb;
+      nw.bnviol = reinterpret_cast<uint32_t*>(b2 + lay.nviol);
       nw.bstride = std::max<uint32_t>(B2, 1);
     }
     launch_preempt_apply(c->stream, c->S, nd, pe, ndirty, assume ? 1u : 0u, dreq, nvall ? &nw : nullptr);
@@ -4263,6 +4325,8 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
   }
   std::memcpy(out->node, rb + o_node, nQ * 4);
   std::memcpy(out->n_victims, rb + o_nv, nQ * 4);
+  c->pre_npv.assign(reinterpret_cast<const uint32_t*>(rb + o_npv), reinterpret_cast<const uint32_t*>(rb + o_npv) + nQ);
+  c->have_pre_npv = true;
   if (out->n_candidates) std::memcpy(out->n_candidates, rb + o_ncand, nQ * 4);
   if (out->top_priority) std::memcpy(out->top_priority, rb + o_top, nQ * 4);
   if (out->priority_sum) std::memcpy(out->priority_sum, rb + o_sum, nQ * 8);

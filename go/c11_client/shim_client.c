@@ -11,6 +11,7 @@
  *   clusterFits     bs_cluster_fits for the first pods of the queue              (bsched_cgo.go: clusterFits, core.go:595-632)
  *   next cycle      bs_groups_apply (patchGroups), bs_pods_apply_flat, bs_batch_run(| BS_BATCH_HOST_RESULTS), bs_batch_map
  *   Filter on       bs_batch_run(| BS_BATCH_FILTER_DENY), bs_batch_read_flat, bs_filter_deny_stats, bs_speculation_stats
+ *   PDB bits        bs_bound_pdb_set, bs_preempt_pdb_read (refused here: no bound table, no preemption call)
  *   close           bs_destroy
  * The struct-taking entry points are reached through their *_flat forms only, exactly as the Go files do (cgo pointer rule: no
  * Go-allocated struct of Go pointers crosses by pointer) — so the forms the shim binds are compiled, linked and run here.
@@ -207,6 +208,10 @@ int main(int argc, char** argv) {
   CHECK(bs_filter_deny_stats(ctx, &reruns));
   CHECK(bs_speculation_stats(ctx, &guessed, &missed));
   if (missed > guessed) return 8;
+  /* ---- the PDB entry points of the preemption path (setBoundPDBBits / preemptPDBViolations in bsched_cgo.go): this client loads no
+   * bound table and runs no preemption, so both must answer BS_ERR_STATE and leave everything alone */
+  if (bs_bound_pdb_set(ctx, 0, NULL) != BS_ERR_STATE) return 9;
+  if (bs_preempt_pdb_read(ctx, 0, NULL) != BS_ERR_STATE) return 9;
   fclose(o);
   CHECK(bs_destroy(ctx));
   printf("shim_client: ok (%" PRIu32 " pods, %" PRIu32 " groups, %" PRIu32 " nodes, %" PRIu32 " filter rows)\n", P, G, N, rows_n);

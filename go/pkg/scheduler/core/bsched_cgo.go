@@ -234,3 +234,41 @@ func (g *gpuCore) cycleCounters() (reruns, guessed, missed uint64) {
 	}
 	return uint64(r), uint64(a), uint64(m)
 }
+
+// setBoundPDBBits: bs_bound_pdb_set.  violating[id] != 0 marks bound pod id (the numbering of the last bs_bound_load) as covered by a
+// PodDisruptionBudget with no disruptions left; nil clears every bit (b is then the last load's entry count).
+func (g *gpuCore) setBoundPDBBits(b uint32, violating []uint8) error {
+	var p *C.uint8_t
+	if len(violating) > 0 {
+		bits := make([]C.uint8_t, len(violating))
+		for i, v := range violating {
+			bits[i] = C.uint8_t(v)
+		}
+		p = &bits[0]
+	}
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if rc := C.bs_bound_pdb_set(g.ctx, C.uint32_t(b), p); rc != C.BS_OK {
+		return fmt.Errorf("bs_bound_pdb_set: %s", C.GoString(C.bs_strerror(rc)))
+	}
+	return nil
+}
+
+// preemptPDBViolations: bs_preempt_pdb_read, the PDB-violating victims per preemptor of the last bs_preempt_run / bs_preempt_commit.
+func (g *gpuCore) preemptPDBViolations(count uint32) ([]uint32, error) {
+	raw := make([]C.uint32_t, count)
+	var p *C.uint32_t
+	if count > 0 {
+		p = &raw[0]
+	}
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if rc := C.bs_preempt_pdb_read(g.ctx, C.uint32_t(count), p); rc != C.BS_OK {
+		return nil, fmt.Errorf("bs_preempt_pdb_read: %s", C.GoString(C.bs_strerror(rc)))
+	}
+	out := make([]uint32, count)
+	for i, v := range raw {
+		out[i] = uint32(v)
+	}
+	return out, nil
+}

@@ -566,15 +566,32 @@ int bs_nodes_read(bs_ctx* ctx, int64_t* requested, uint32_t* requested_present);
  *      NodeInfo.RemovePod: an absent key counts as 0) must hold the pod under bs_seq_run's fit rule (oracle/bs_oracle_seq.c:62-78
  *      holds()); otherwise the node is no candidate.
  *   5. reprieve: the potential victims in importance order — priority descending, start time ascending (MoreImportantPod), bound-pod
- *      id ascending (this library's tie rule: upstream's sort.Slice is not stable) — are added back one by one; a pod after which the
- *      preemptor no longer holds is taken out again and is a victim.  Victims come out in importance order; with no PDBs every
- *      victim is "non-violating".
+ *      id ascending (this library's tie rule: upstream's sort.Slice is not stable) — are split by their PDB bit (bs_bound_pdb_set
+ *      below; clear after bs_bound_load) into the VIOLATING list and the NON-VIOLATING list, each keeping importance order.  All
+ *      violating pods are offered for reprieve first, in order, then all non-violating ones: a pod is added back; if the preemptor no
+ *      longer holds it is taken out again and is a victim.  n_pdb_violations = the victims that come from the violating list (a
+ *      violating pod that is reprieved counts nothing).  The victim list is in reprieve order: the violating victims (importance
+ *      order), then the non-violating victims (importance order).  With every bit clear this is one list in importance order.
  *   6. node pick (pickOneNodeForPreemption; upstream iterates a Go map, so its ties are random — here every tie goes to the lowest
  *      node index): a candidate without victims wins outright (the lowest index among several); otherwise the smallest key
- *      (highest victim priority, sum over victims of priority + 2^31, victim count, the LATEST "earliest start among the victims of
- *      highest priority" (GetEarliestPodStartTime), node index).
+ *      (n_pdb_violations,
+ *       top_priority = the priority of the FIRST LISTED victim — upstream reads victims.Pods[0] as "the highest priority", which with a
+ *         violating victim in front is not necessarily the maximum; the quirk is kept,
+ *       sum over victims of priority + 2^31, victim count,
+ *       the LATEST earliest_start = GetEarliestPodStartTime(victims), which does walk every victim: the earliest start among the
+ *         victims of the TRUE maximum priority,
+ *       node index).
+ * Recalled upstream semantics (k8s v1.17.5; its source is not vendored, so they are written out):
+ *   D1. filterPodsWithPDBViolation is a static test per pod: some PDB of the pod's namespace whose selector matches the pod's labels
+ *       has Status.PodDisruptionsAllowed <= 0.  No budget is counted down while victims are chosen (that came in later releases): the
+ *       bit depends neither on the preemptor nor on the other victims.
+ *   D2. selectVictimsOnNode reprieves violatingVictims first, then nonViolatingVictims, both sorted by MoreImportantPod, and counts
+ *       numViolatingVictim among the former only; Victims.Pods holds them in that order.
+ *   D3. pickOneNodeForPreemption: victim-free node first; then fewest NumPDBViolations; then lowest victims.Pods[0] priority; then the
+ *       smallest priority sum, the fewest victims, the latest GetEarliestPodStartTime; then the first left.
+ *   D4. A pod of priority >= the preemptor's is no potential victim; its PDBs are never looked at.
  * Restrictions: BS_STAGE_FILTER is refused (BS_ERR_INVALID: the plugin's Filter takes no part in the fit test; the shipped config
- * does not enable Filter).  No nominated pods, no PDBs.  podEligibleToPreemptOthers (PreemptionPolicy Never, terminating pods on the
+ * does not enable Filter).  No nominated pods from earlier calls.  podEligibleToPreemptOthers (PreemptionPolicy Never, terminating pods on the
  * nominated node) is the caller's business, and so is the choice of preemptors: upstream preempts only for a pod that passed
  * PreFilter and then found no node (a PreFilter rejection is not a FitError).  Sharded contexts: BS_ERR_STATE, as bs_seq_run.
  * The call is a what-if: node requests, groups and the queue are left as they were.  Synchronous. */
@@ -597,22 +614,32 @@ typedef struct bs_bound_soa {
 } bs_bound_soa;
 int bs_bound_load(bs_ctx* ctx, const bs_bound_soa* bound);
 int bs_bound_count(const bs_ctx* ctx, uint32_t* b_out);
+/* The PDB bit of every bound pod: violating[id] != 0 = "some PodDisruptionBudget of the pod's namespace whose selector matches its labels
+ * has Status.PodDisruptionsAllowed <= 0" (D1 above; matching labels is the caller's work).  ids are the caller's numbering at the last
+ * bs_bound_load and b is that load's entry count (BS_ERR_INVALID otherwise); entries evicted since by BS_PREEMPT_APPLY are skipped.
+ * violating == NULL clears every bit.  bs_bound_load clears them too.  BS_ERR_STATE before bs_bound_load.  The bits stay until the next
+ * bs_bound_pdb_set / bs_bound_load; a surviving entry keeps its bit through BS_PREEMPT_APPLY.  Synchronous. */
+int bs_bound_pdb_set(bs_ctx* ctx, uint32_t b, const uint8_t* violating);
 /* Results per preemptor q (caller's order).  node and n_victims are required, the other arrays may be NULL; victims is required when
  * victim_cap > 0. */
 typedef struct bs_preempt_out {
   int32_t*  node;              /* [count] chosen node, -1 = none                                                          */
   uint32_t* n_candidates;      /* [count] nodes that passed steps 1-4                                                     */
   uint32_t* n_victims;         /* [count] victims on the chosen node (the true count: may exceed victim_cap)              */
-  uint32_t* victims;           /* [count][victim_cap] bound-pod ids (the caller's numbering), importance order            */
-  int32_t*  top_priority;      /* [count] pick key of the chosen node: highest victim priority (0 without victims)        */
+  uint32_t* victims;           /* [count][victim_cap] bound-pod ids (the caller's numbering), reprieve order (step 5)     */
+  int32_t*  top_priority;      /* [count] pick key of the chosen node: the first listed victim's priority (0 without)     */
   int64_t*  priority_sum;      /* [count] ... sum over victims of priority + 2^31                                         */
-  int64_t*  earliest_start;    /* [count] ... earliest start among the victims of highest priority                        */
+  int64_t*  earliest_start;    /* [count] ... earliest start among the victims of the true maximum priority               */
 } bs_preempt_out;
 /* stages: 0 or BS_STAGE_PREFILTER (room for a Filter-aware version).  pod_index[count] < p (resident queue), priority[count],
  * group_protected[g] (g = loaded group count; may be NULL when g == 0).  BS_ERR_STATE when nodes, fit masks, pods or the bound table
  * are not loaded; BS_ERR_INVALID for a pod index >= p, filter stages, NULL required arrays. */
 int bs_preempt_run(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
                    const uint8_t* group_protected, uint32_t victim_cap, const bs_preempt_out* out);
+/* n_pdb_violations[count] per preemptor (caller's order) of the context's last successful bs_preempt_run / bs_preempt_commit: the
+ * first word of the chosen node's pick key, 0 where no node was chosen.  (bs_preempt_out keeps its layout, hence a getter, like
+ * bs_batch_stats.)  BS_ERR_STATE when there was no such call, BS_ERR_INVALID when count differs from that call's. */
+int bs_preempt_pdb_read(bs_ctx* ctx, uint32_t count, uint32_t* n_pdb_violations);
 
 /* ---- preemption plans: the preemptors answered in sequence, optionally applied ---------------------------------------------
  * bs_preempt_run answers every preemptor on its own, so its rows are no plan: two rows may name the same victim, count the same freed
@@ -631,7 +658,10 @@ int bs_preempt_run(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t*
  *      Library rule: evictions take effect at once for the later slots of the same call.  Upstream leaves a terminating victim in the
  *      cache until its delete event arrives; modelling that would let two preemptors count the same pod, the conflict this call removes.
  *   3. the search for slot s is bs_preempt_run's steps 1-6 on that state, unchanged (skip rule, policy, fit rule, reprieve order, pick
- *      key, ties).  Slot 0's answer is exactly bs_preempt_run's answer for that preemptor.
+ *      key with the PDB violations in front, ties).  Slot 0's answer is exactly bs_preempt_run's answer for that preemptor.
+ *      Library rule: the PDB bits are those of the last bs_bound_pdb_set for the WHOLE call — an earlier slot's evictions do not turn
+ *      further pods violating, as upstream v1.17.5 would not within one cycle either (D1).  The caller refreshes the bits from the
+ *      PDBs' status between calls.  With BS_PREEMPT_APPLY a surviving entry keeps its bit through the compaction.
  *   4. flags: 0 = the plan only, nothing resident changes (as bs_preempt_run).  BS_PREEMPT_APPLY: after the pass the evictions are
  *      written into the context: the bound table loses every victim of every slot (survivors keep their caller ids from the last
  *      bs_bound_load and their per-node importance order; bs_bound_count falls by the number of victims), node requests lose the victims
@@ -641,7 +671,7 @@ int bs_preempt_run(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t*
  *   6. errors: whatever bs_preempt_run refuses, with the same code; also a pod_index that appears twice (a pod is nominated once) and
  *      BS_PREEMPT_ASSUME without BS_PREEMPT_APPLY (BS_ERR_INVALID).  Everything is validated before anything is launched; on any error
  *      no resident state changes.  Group state, the queue and the fit masks are never touched: a gang that loses pods keeps its
- *      Status.Scheduled (updating it is the controller's job).  No nominated pods from earlier calls, no PDBs; sharded contexts:
+ *      Status.Scheduled (updating it is the controller's job).  No nominated pods from earlier calls; sharded contexts:
  *      BS_ERR_STATE.  Synchronous. */
 #define BS_PREEMPT_APPLY  1u   /* write the evictions into the bound table and the node requests */
 #define BS_PREEMPT_ASSUME 2u   /* with APPLY: also add each nominee's request to its node          */

@@ -2,7 +2,8 @@
 pods per node, for 64 and 1024 preemptors.  Prints one JSON line: ms per call (median of --reps calls after --warmup), end to end
 through the C ABI (upload of the preemptor arrays, both launches, the result copy).  --commit times bs_preempt_commit instead (the
 plan answered in sequence, distinct preemptors) with flags 0 and BS_PREEMPT_APPLY; an APPLY call is timed from the state as loaded (the
-nodes and the bound table are reloaded, untimed, before every call)."""
+nodes and the bound table are reloaded, untimed, before every call).  --pdb FRACTION marks that share of the bound pods (seeded) as
+PDB-violating through bs_bound_pdb_set before the timed calls; the default 0 sets no bits."""
 from __future__ import annotations
 
 import argparse
@@ -20,7 +21,7 @@ bsa = importlib.import_module("batch-scheduler_amd")
 soa, synth = bsa.soa, bsa.synth
 
 
-def one(config: str, q: int, reps: int, warmup: int, commit: bool = False, apply: bool = False) -> dict:
+def one(config: str, q: int, reps: int, warmup: int, commit: bool = False, apply: bool = False, pdb: float = 0.0) -> dict:
     cfg = synth.CONFIGS[config]
     n, S = cfg["nodes"], cfg["scalars"]
     bound, nodes = synth.make_bound(20260921, n, cfg["groups"], (20, 110), S)
@@ -30,11 +31,14 @@ def one(config: str, q: int, reps: int, warmup: int, commit: bool = False, apply
         pidx = np.random.default_rng(20260921).permutation(4096)[:q].astype(np.uint32)
     groups = soa.Groups.empty(cfg["groups"], 4 + S)
     prot = (synth.Stream(20260921, 99).uniform(cfg["groups"]) < 0.3).astype(np.uint8)
+    bits = (np.random.default_rng(20260921).random(bound.b) < pdb).astype(np.uint8) if pdb > 0 else None
     with bsa.Context(scalar_lanes=S, device=0) as ctx:
         ctx.load_nodes(nodes, fit)
         ctx.load_groups(groups)
         ctx.load_pods(pods)
         ctx.load_bound(bound)
+        if bits is not None:
+            ctx.bound_pdb_set(bits)
         def call():
             if not commit:
                 return ctx.preempt(pidx, prio, prot, victim_cap=16)
@@ -45,12 +49,16 @@ def one(config: str, q: int, reps: int, warmup: int, commit: bool = False, apply
             if apply and it:
                 ctx.load_nodes(nodes, fit)
                 ctx.load_bound(bound)
+                if bits is not None:
+                    ctx.bound_pdb_set(bits)
             t0 = time.perf_counter()
             r = call()
             if it >= warmup:
                 ts.append((time.perf_counter() - t0) * 1e3)
     row = dict(config=config, nodes=n, bound=int(bound.b), preemptors=q, ms=round(float(np.median(ts)), 4), ms_min=round(float(min(ts)), 4),
                placed=int((r["node"] >= 0).sum()), with_victims=int((r["n_victims"] > 0).sum()))
+    if pdb > 0:
+        row.update(pdb=pdb, pdb_violations=int(r["n_pdb_violations"].sum()))
     if commit:
         row.update(flags="APPLY" if apply else "0", evicted=int(r["n_victims"].sum()))
     return row
@@ -61,12 +69,13 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--commit", action="store_true", help="bs_preempt_commit, flags 0 and APPLY")
+    ap.add_argument("--pdb", type=float, default=0.0, metavar="FRACTION", help="share of the bound pods with the PDB-violating bit (seeded)")
     a = ap.parse_args()
     if a.commit:
-        rows = [one(c, q, a.reps, a.warmup, True, ap_) for c in ("cfg3", "cfg4") for q in (64, 1024) for ap_ in (False, True)]
+        rows = [one(c, q, a.reps, a.warmup, True, ap_, a.pdb) for c in ("cfg3", "cfg4") for q in (64, 1024) for ap_ in (False, True)]
         print(json.dumps(dict(metric="bs_preempt_commit ms per call", rows=rows)))
         return
-    rows = [one(c, q, a.reps, a.warmup) for c in ("cfg3", "cfg4") for q in (64, 1024)]
+    rows = [one(c, q, a.reps, a.warmup, pdb=a.pdb) for c in ("cfg3", "cfg4") for q in (64, 1024)]
     print(json.dumps(dict(metric="bs_preempt_run ms per call", rows=rows)))
 
 
