@@ -30,6 +30,7 @@
 #include "bs_pod_ranges.hpp"
 #include "bs_preempt.hpp"
 #include "bs_preempt_commit.hpp"
+#include "bs_preempt_geom.hpp"
 #ifdef BS_UNITY   // one translation unit (the probe builds: g_probe / g_seq_scan_ph are per translation unit)
 #include "tu_fast.hip"
 #include "tu_seq.hip"
@@ -278,6 +279,7 @@ struct bs_ctx {
   bool step_a_on = true;
   uint32_t step_shares = 8;          // BS_STEP_SHARES: blocks that share one table chunk's class slots (class-slot form, cfg3: 2 / 4 / 8 / 16 shares = 25.1 / 20.4 / 19.05 / 20.9 us per step)
   uint32_t test_timeout_after = 0;   // BS_TEST_HANDOVER_TIMEOUT=n (test hook): the n-th one-launch step reports a timed-out hand-over as the device would
+  uint32_t test_pc_chunk_nodes = 0;  // BS_TEST_PC_CHUNK_NODES=n (test hook): nodes per chunk of the preemption grids (bs_preempt_geom.hpp); 0 = the shipped geometry
   uint32_t tk_pods = 0, tk_tab = 0;  // values of ticket[8] / ticket[9] the next k_fast_step_a starts from (never reset: wrap-safe differences)
   uint32_t tk_p1 = 0, tk_done = 0;   // ... of the spread counter at kTkP1 (form 3: the pod blocks' first halves); tk_done: of the counter at kTkDone (large queues: every table / Filter block adds once)
   // form 3's gang-aligned pod ranges (bs_pod_ranges.hpp): computed by bs_pods_load, dropped by bs_pods_apply (256 pods per block until the next load)
@@ -1127,6 +1129,7 @@ int bs_create(const bs_config* cfg, bs_ctx** out) {
   if (const char* e = std::getenv("BS_NO_FUSE_FINAL")) c->no_fuse_final = std::atoi(e) ? 1u : 0u;
   if (const char* e = std::getenv("BS_TP_FILTER")) c->tp_filter = (uint32_t)std::min(8, std::max(0, std::atoi(e)));
   if (const char* e = std::getenv("BS_TEST_HANDOVER_TIMEOUT")) c->test_timeout_after = (uint32_t)std::atoi(e);
+  if (const char* e = std::getenv("BS_TEST_PC_CHUNK_NODES")) c->test_pc_chunk_nodes = (uint32_t)std::max(0, std::atoi(e));
   if (const char* e = std::getenv("BS_STEP_A")) { c->step_a_on = std::atoi(e) != 0; c->step_a_form = (uint32_t)std::atoi(e); }
   if (const char* e = std::getenv("BS_POD_RANGES")) c->pod_ranges_on = std::atoi(e) != 0;
   if (const char* e = std::getenv("BS_STEP_SHARES")) c->step_shares = (uint32_t)std::min(32, std::max(1, std::atoi(e)));
@@ -4024,11 +4027,8 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   std::vector<uint32_t> perm(count);
   for (uint32_t i = 0; i < count; ++i) perm[i] = i;
   std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return priority[a] > priority[b]; });
-  const uint32_t tiles = cdiv(count, 64);
-  // node chunks: about 4096 waves in the first launch (16 per CU), at least one node per chunk
-  uint32_t nchunks = std::max<uint32_t>(1, std::min<uint32_t>(std::max<uint32_t>(N, 1), cdiv(4096, tiles)));
-  const uint32_t chunk_nodes = std::max<uint32_t>(1, cdiv(N, nchunks));
-  nchunks = std::max<uint32_t>(1, cdiv(N, chunk_nodes));
+  const PreemptGeom geom = preempt_geom(N, count, c->test_pc_chunk_nodes);   // slot tiles x node chunks (bs_preempt_geom.hpp)
+  const uint32_t tiles = geom.tiles, nchunks = geom.nchunks, chunk_nodes = geom.chunk_nodes;
   const size_t nQ = count, nG = std::max<uint32_t>(G, 1), nR = (size_t)nchunks * nQ, nV = std::max<size_t>((size_t)nQ * victim_cap, 1);
   size_t o = 0;
   const size_t o_spod = o; o = align256(o + nQ * 4);
@@ -4174,10 +4174,8 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
   std::vector<uint32_t> perm(count);
   for (uint32_t i = 0; i < count; ++i) perm[i] = i;
   std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return priority[a] > priority[b]; });
-  const uint32_t tiles = cdiv(count, 64);
-  uint32_t nchunks = std::max<uint32_t>(1, std::min<uint32_t>(std::max<uint32_t>(N, 1), cdiv(4096, tiles)));
-  const uint32_t chunk_nodes = std::max<uint32_t>(1, cdiv(N, nchunks));
-  nchunks = std::max<uint32_t>(1, cdiv(N, chunk_nodes));
+  const PreemptGeom geom = preempt_geom(N, count, c->test_pc_chunk_nodes);   // slot tiles x node chunks (bs_preempt_geom.hpp)
+  const uint32_t tiles = geom.tiles, nchunks = geom.nchunks, chunk_nodes = geom.chunk_nodes;
   const size_t nQ = count, nG = std::max<uint32_t>(G, 1), nR = (size_t)nchunks * nQ, nV = std::max<size_t>((size_t)nQ * victim_cap, 1);
   const size_t nN = std::max<uint32_t>(N, 1), nB = std::max<uint32_t>(B, 1);
   size_t o = 0;
