@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "bs_bound_load", "bs_bound_count", "bs_preempt_run", "bs_bound_load_flat", "bs_preempt_run_flat",
     "bs_preempt_commit", "bs_bound_read", "bs_preempt_commit_flat",
     "bs_bound_pdb_set", "bs_preempt_pdb_read",
+    "bs_bound_apply", "bs_bound_apply_flat", "bs_bound_ids", "bs_bound_dump",
 ]
 
 # bsh_phase codes (include/bsched_host.h) of the phases whose gangs PreemptRemovePod protects: Running and Scheduled (core.go:235-238)
@@ -170,6 +171,10 @@ def load_library(path: str | None = None):
     L.bs_preempt_commit.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), u32, u32, P(soa.PreemptOutStruct)]
     L.bs_bound_read.argtypes = [vp, P(u32), P(u32)]
     L.bs_bound_pdb_set.argtypes = [vp, u32, P(u8)]
+    L.bs_bound_apply.argtypes = [vp, P(soa.BoundDeltaStruct), P(u32)]
+    L.bs_bound_apply_flat.argtypes = [vp, u32, P(u32), u32, P(u32), P(i32), P(C.c_int64), P(i32), P(C.c_int64), P(u32), P(u8), P(u32)]
+    L.bs_bound_ids.argtypes = [vp, P(u32)]
+    L.bs_bound_dump.argtypes = [vp, P(i32), P(C.c_int64), P(i32), P(C.c_int64), P(u32), P(u8)]
     L.bs_preempt_pdb_read.argtypes = [vp, u32, P(u32)]
     L.bs_preempt_commit_flat.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), u32, u32, P(i32), P(u32), P(u32), P(u32), P(i32), P(C.c_int64),
                                          P(C.c_int64)]
@@ -586,6 +591,48 @@ class Context:
         ids, node = np.zeros(max(b, 1), np.uint32), np.zeros(max(b, 1), np.uint32)
         self._chk(self._lib.bs_bound_read(self._h, _u32p(ids), _u32p(node)), "bs_bound_read")
         return ids[:b], node[:b]
+
+    def bound_ids(self) -> int:
+        """bs_bound_ids: the size of the bound table's id space (the last load's entry count plus what bound_apply inserted since)"""
+        v = C.c_uint32()
+        self._chk(self._lib.bs_bound_ids(self._h, C.byref(v)), "bs_bound_ids")
+        return int(v.value)
+
+    def bound_apply(self, remove=None, insert: "soa.Bound | None" = None, pdb=None, flat: bool = False) -> int:
+        """bs_bound_apply: entries `remove` (ids) leave the resident bound table, the entries of `insert` arrive with ids
+        first_id, first_id + 1, ... (pdb[i] != 0: inserted entry i is PDB-violating; None = clear).  Returns first_id.  flat=True goes
+        through bs_bound_apply_flat (the cgo form)."""
+        rem = np.ascontiguousarray(np.asarray([] if remove is None else remove, np.uint32).reshape(-1))
+        ni = 0 if insert is None else int(insert.b)
+        if ni:
+            assert insert.req.shape[0] == self.L, f"context has {self.L} lanes, inserted pods have {insert.req.shape[0]}"
+        pv = None if pdb is None or ni == 0 else np.ascontiguousarray(np.asarray(pdb).reshape(-1) != 0, np.uint8)
+        assert pv is None or pv.size == ni
+        u8p = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))
+        i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        cols = (None,) * 6 if ni == 0 else (_u32p(insert.node), i32p(insert.priority), _i64p(insert.start_ns), i32p(insert.group),
+                                            _i64p(np.ascontiguousarray(insert.req)), _u32p(insert.req_present))
+        first = C.c_uint32()
+        rp = _u32p(rem) if rem.size else None
+        pp = u8p(pv) if pv is not None else None
+        if flat:
+            self._chk(self._lib.bs_bound_apply_flat(self._h, int(rem.size), rp, ni, *cols, pp, C.byref(first)), "bs_bound_apply_flat")
+        else:
+            d = soa.BoundDeltaStruct(int(rem.size), rp, ni, *cols, pp)
+            self._chk(self._lib.bs_bound_apply(self._h, C.byref(d), C.byref(first)), "bs_bound_apply")
+        self._bound_ids = int(first.value) + ni
+        return int(first.value)
+
+    def bound_dump(self) -> dict:
+        """bs_bound_dump: the live table's columns as stored, in read_bound's order: priority, start_ns, group, req [L, count],
+        req_present, pdb"""
+        b = self.bound_count()
+        n = max(b, 1)
+        prio, start, grp = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.int32)
+        req, pres, pdb = np.zeros((self.L, n), np.int64), np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        self._chk(self._lib.bs_bound_dump(self._h, prio.ctypes.data_as(C.POINTER(C.c_int32)), _i64p(start), grp.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          _i64p(req), _u32p(pres), pdb.ctypes.data_as(C.POINTER(C.c_uint8))), "bs_bound_dump")
+        return dict(priority=prio[:b], start_ns=start[:b], group=grp[:b], req=req[:, :b], req_present=pres[:b], pdb=pdb[:b])
 
     # -- sharding / measurement
     def set_shard(self, rank: int, nranks: int):

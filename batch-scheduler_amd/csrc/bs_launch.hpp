@@ -47,4 +47,9 @@ void launch_preempt_commit(hipStream_t stream, uint32_t S, dim3 scan_grid, const
 void launch_preempt_apply(hipStream_t stream, uint32_t S, const NodesDev& nd, const CommitDev& pe, uint32_t ndirty, uint32_t assume, bs_node_request* reqs,
                           const CompactDev* nw);
 
+// the bound table's patch (tu_preempt.hip, bs_bound_apply.hpp): k_ba_scatter<S>, k_ba_mark<S>, k_ba_boff<S> (the new CSR into nw.boff),
+// k_ba_merge<S> (one wave per node into nw; writes nothing when the error word is set)
+struct BoundApplyDev;
+void launch_bound_apply(hipStream_t stream, uint32_t S, const BoundApplyDev& a, const CompactDev& nw);
+
 }  // namespace bs

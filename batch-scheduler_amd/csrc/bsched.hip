@@ -31,6 +31,7 @@
 #include "bs_preempt.hpp"
 #include "bs_preempt_commit.hpp"
 #include "bs_preempt_geom.hpp"
+#include "bs_bound_apply.hpp"
 #ifdef BS_UNITY   // one translation unit (the probe builds: g_probe / g_seq_scan_ph are per translation unit)
 #include "tu_fast.hip"
 #include "tu_seq.hip"
@@ -321,7 +322,7 @@ struct bs_ctx {
   DevBuf d_bound, d_pre;
   DevBuf d_bound2;                   // bs_preempt_commit's compaction target (swapped with d_bound)
   size_t off_boff = 0, off_bprio = 0, off_bstart = 0, off_bgroup = 0, off_bid = 0, off_breq = 0, off_bpres = 0, off_bpdb = 0, off_bnviol = 0;
-  uint32_t bound_ids = 0;            // entries at the last bs_bound_load: the id space of bs_bound_pdb_set
+  uint32_t bound_ids = 0;            // the id space of bs_bound_pdb_set: entries at the last bs_bound_load plus what bs_bound_apply inserted since
   std::vector<uint32_t> pre_npv;     // PDB-violating victims per preemptor of the last preemption call (bs_preempt_pdb_read)
   bool have_pre_npv = false;
 };
@@ -4356,6 +4357,195 @@ int bs_bound_read(bs_ctx* c, uint32_t* id_out, uint32_t* node_out) {
   HIPCHK(c, hipMemcpy(id_out, bb + c->off_bid, (size_t)B * 4, hipMemcpyDeviceToHost));
   for (uint32_t k = 0; k < N; ++k)
     for (uint32_t j = boff[k]; j < boff[k + 1] && j < B; ++j) node_out[j] = k;
+  return BS_OK;
+}
+
+// -------------------------------------------------------------------------------------------------
+// the bound table patched in place (bs_bound_apply.hpp): O(delta) on the host, one pass over the table on the device
+// -------------------------------------------------------------------------------------------------
+int bs_bound_ids(const bs_ctx* c, uint32_t* ids_out) {
+  if (!c || !ids_out) return BS_ERR_INVALID;
+  *ids_out = c->have_bound ? c->bound_ids : 0u;
+  return BS_OK;
+}
+
+int bs_bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t* first_id_out) {
+  if (!c || !d) return BS_ERR_INVALID;
+  if (!c->have_bound) { c->last_error = "bs_bound_apply before bs_bound_load"; return BS_ERR_STATE; }
+  if (c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
+  const uint32_t R = d->n_remove, I = d->n_insert, N = c->N, L = c->L, B = c->bound_b, ids = c->bound_ids;
+  if (R && !d->remove) return BS_ERR_INVALID;
+  if (I && (!d->node || !d->priority || !d->start_ns || !d->group || !d->req || !d->req_present)) return BS_ERR_INVALID;
+  if (R == 0 && I == 0) {
+    if (first_id_out) *first_id_out = ids;
+    return BS_OK;
+  }
+  int32_t gmax = c->bound_max_group;
+  for (uint32_t i = 0; i < I; ++i) {
+    if (d->node[i] >= N) { c->last_error = "bs_bound_apply: insert on a node index >= n"; return BS_ERR_INVALID; }
+    if (d->group[i] < BS_POD_GROUP_MISSING) { c->last_error = "bs_bound_apply: insert group index below BS_POD_GROUP_MISSING"; return BS_ERR_INVALID; }
+    gmax = std::max(gmax, d->group[i]);
+  }
+  for (uint32_t r = 0; r < R; ++r)
+    if (d->remove[r] >= ids) { c->last_error = "bs_bound_apply: remove id outside the id space"; return BS_ERR_INVALID; }
+  if (R > B) { c->last_error = "bs_bound_apply: more remove ids than live entries (an id is listed twice or is not live)"; return BS_ERR_INVALID; }
+  if ((uint64_t)ids + I > BS_BOUND_MAX) { c->last_error = "bs_bound_apply: the id space would pass BS_BOUND_MAX: reload the table"; return BS_ERR_CAPACITY; }
+  int rc = use_device(c);
+  if (rc) return rc;
+  // the inserts by (node, importance); their ids follow the delta's order, so equal keys keep it
+  std::vector<uint32_t> order(I);
+  for (uint32_t i = 0; i < I; ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+    if (d->node[a] != d->node[b]) return d->node[a] < d->node[b];
+    if (d->priority[a] != d->priority[b]) return d->priority[a] > d->priority[b];
+    if (d->start_ns[a] != d->start_ns[b]) return d->start_ns[a] < d->start_ns[b];
+    return a < b;
+  });
+  // one blob (8-byte columns first), then the scratch: pos_of (0xff), the zeroed words, the segment starts
+  const size_t nI = I, nR = R, nN = std::max<uint32_t>(N, 1);
+  size_t o = 0;
+  const size_t o_start = o; o += nI * 8;
+  const size_t o_req = o; o += nI * L * 8;
+  const size_t o_rem = o; o += nR * 4;
+  const size_t o_node = o; o += nI * 4;
+  const size_t o_prio = o; o += nI * 4;
+  const size_t o_group = o; o += nI * 4;
+  const size_t o_id = o; o += nI * 4;
+  const size_t o_pres = o; o += nI * 4;
+  const size_t o_pdb = o; o += nI;
+  const size_t blob_bytes = o;
+  o = align256(o);
+  const size_t o_posof = o; o = align256(o + (size_t)std::max<uint32_t>(ids, 1) * 4);
+  const size_t o_zero = o;
+  const size_t o_deadw = o; o = align256(o + ((size_t)B / 32 + 1) * 4);
+  const size_t o_dcnt = o; o = align256(o + nN * 4);
+  const size_t o_icnt = o; o = align256(o + nN * 4);
+  const size_t o_err = o; o = align256(o + 4);
+  const size_t zero_bytes = o - o_zero;
+  const size_t o_ifirst = o; o = align256(o + nN * 4);
+  // the id space grows with every call, and the table with every net insert: a quarter of headroom, so that a run of calls allocates rarely
+  if (o > c->d_pre.cap) HIPCHK(c, c->d_pre.reserve(o + o / 4));
+  std::vector<uint8_t> h(std::max<size_t>(blob_bytes, 1), 0);
+  {
+    int64_t* start = reinterpret_cast<int64_t*>(h.data() + o_start);
+    int64_t* req = reinterpret_cast<int64_t*>(h.data() + o_req);
+    uint32_t* node = reinterpret_cast<uint32_t*>(h.data() + o_node);
+    int32_t* prio = reinterpret_cast<int32_t*>(h.data() + o_prio);
+    int32_t* grp = reinterpret_cast<int32_t*>(h.data() + o_group);
+    uint32_t* id = reinterpret_cast<uint32_t*>(h.data() + o_id);
+    uint32_t* pres = reinterpret_cast<uint32_t*>(h.data() + o_pres);
+    uint8_t* pdb = h.data() + o_pdb;
+    if (R) std::memcpy(h.data() + o_rem, d->remove, nR * 4);
+    const uint32_t smask = (uint32_t)((1ull << (L - BS_FIXED_LANES)) - 1ull);
+    for (uint32_t r = 0; r < I; ++r) {                     // stored as bs_bound_load stores them
+      const uint32_t i = order[r];
+      node[r] = d->node[i];
+      prio[r] = d->priority[i];
+      start[r] = d->start_ns[i];
+      grp[r] = d->group[i];
+      id[r] = ids + i;
+      pres[r] = d->req_present[i] & smask;
+      pdb[r] = d->pdb_violating && d->pdb_violating[i] ? 1 : 0;
+      for (uint32_t l = 0; l < L; ++l) {
+        int64_t v = d->req[(size_t)l * I + i];
+        if (l == BS_LANE_PODS) v = 1;
+        else if (l >= BS_FIXED_LANES && !((d->req_present[i] >> (l - BS_FIXED_LANES)) & 1u)) v = 0;
+        req[(size_t)l * nI + r] = v;
+      }
+    }
+  }
+  uint8_t* base = c->d_pre.as<uint8_t>();
+  HIPCHK(c, hipMemcpyAsync(base, h.data(), h.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(base + o_posof, 0xff, (size_t)std::max<uint32_t>(ids, 1) * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(base + o_zero, 0, zero_bytes, c->stream));
+  const uint32_t B2 = B - R + I;                           // (when the error word stays clear)
+  BoundLayout lay{};
+  const size_t table_bytes = bound_layout(L, N, B2, lay);
+  if (table_bytes > c->d_bound2.cap) HIPCHK(c, c->d_bound2.reserve(table_bytes + table_bytes / 4));
+  const uint8_t* bb = c->d_bound.as<uint8_t>();
+  uint8_t* b2 = c->d_bound2.as<uint8_t>();
+  BoundApplyDev a{};
+  a.boff = reinterpret_cast<const uint32_t*>(bb + c->off_boff);
+  a.bprio = reinterpret_cast<const int32_t*>(bb + c->off_bprio);
+  a.bstart = reinterpret_cast<const int64_t*>(bb + c->off_bstart);
+  a.bgroup = reinterpret_cast<const int32_t*>(bb + c->off_bgroup);
+  a.breq = reinterpret_cast<const int64_t*>(bb + c->off_breq);
+  a.bid = reinterpret_cast<const uint32_t*>(bb + c->off_bid);
+  a.bpres = reinterpret_cast<const uint32_t*>(bb + c->off_bpres);
+  a.bpdb = bb + c->off_bpdb;
+  a.bstride = std::max<uint32_t>(B, 1);
+  a.b = B; a.n = N; a.ids = ids;
+  a.n_remove = R; a.n_insert = I;
+  a.rem = reinterpret_cast<const uint32_t*>(base + o_rem);
+  a.inode = reinterpret_cast<const uint32_t*>(base + o_node);
+  a.iprio = reinterpret_cast<const int32_t*>(base + o_prio);
+  a.istart = reinterpret_cast<const int64_t*>(base + o_start);
+  a.igroup = reinterpret_cast<const int32_t*>(base + o_group);
+  a.ireq = reinterpret_cast<const int64_t*>(base + o_req);
+  a.iid = reinterpret_cast<const uint32_t*>(base + o_id);
+  a.ipres = reinterpret_cast<const uint32_t*>(base + o_pres);
+  a.ipdb = base + o_pdb;
+  a.pos_of = reinterpret_cast<uint32_t*>(base + o_posof);
+  a.deadw = reinterpret_cast<uint32_t*>(base + o_deadw);
+  a.dcnt = reinterpret_cast<uint32_t*>(base + o_dcnt);
+  a.icnt = reinterpret_cast<uint32_t*>(base + o_icnt);
+  a.ifirst = reinterpret_cast<uint32_t*>(base + o_ifirst);
+  a.err = reinterpret_cast<uint32_t*>(base + o_err);
+  CompactDev nw{};
+  nw.boff = reinterpret_cast<uint32_t*>(b2 + lay.boff);
+  nw.bprio = reinterpret_cast<int32_t*>(b2 + lay.prio);
+  nw.bstart = reinterpret_cast<int64_t*>(b2 + lay.start);
+  nw.bgroup = reinterpret_cast<int32_t*>(b2 + lay.group);
+  nw.bid = reinterpret_cast<uint32_t*>(b2 + lay.id);
+  nw.breq = reinterpret_cast<int64_t*>(b2 + lay.req);
+  nw.bpres = reinterpret_cast<uint32_t*>(b2 + lay.pres);
+  nw.bpdb = b2 + lay.pdb;
+  nw.bnviol = reinterpret_cast<uint32_t*>(b2 + lay.nviol);
+  nw.bstride = std::max<uint32_t>(B2, 1);
+  launch_bound_apply(c->stream, c->S, a, nw);
+  LAUNCHCHK(c, BS_KERNEL_PREPASS);
+  uint32_t err = 0;                                        // read before the swap: the merge wrote nothing when it is set
+  HIPCHK(c, hipMemcpyAsync(&err, a.err, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (err & (kBaErrUnknown | kBaErrDead | kBaErrTwice | kBaErrNode)) {
+    c->last_error = (err & kBaErrTwice) ? "bs_bound_apply: a remove id is listed twice"
+                  : (err & kBaErrDead)  ? "bs_bound_apply: a remove id is not live (evicted or removed earlier)"
+                                        : "bs_bound_apply: a remove id or an insert node is out of range";
+    return BS_ERR_INVALID;
+  }
+  if (err & kBaErrFull) { c->last_error = "bs_bound_apply: more than BS_BOUND_MAX_PER_NODE bound pods on one node"; return BS_ERR_CAPACITY; }
+  std::swap(c->d_bound.p, c->d_bound2.p);
+  std::swap(c->d_bound.cap, c->d_bound2.cap);
+  bound_layout_set(c, lay);
+  c->bound_b = B2;
+  c->bound_ids = ids + I;
+  c->bound_max_group = gmax;
+  if (first_id_out) *first_id_out = ids;
+  return BS_OK;
+}
+
+int bs_bound_apply_flat(bs_ctx* c, uint32_t n_remove, const uint32_t* remove, uint32_t n_insert, const uint32_t* node, const int32_t* priority,
+                        const int64_t* start_ns, const int32_t* group, const int64_t* req, const uint32_t* req_present, const uint8_t* pdb_violating,
+                        uint32_t* first_id_out) {
+  const bs_bound_delta d{n_remove, remove, n_insert, node, priority, start_ns, group, req, req_present, pdb_violating};
+  return bs_bound_apply(c, &d, first_id_out);
+}
+
+int bs_bound_dump(bs_ctx* c, int32_t* priority, int64_t* start_ns, int32_t* group, int64_t* req, uint32_t* req_present, uint8_t* pdb) {
+  if (!c) return BS_ERR_INVALID;
+  if (!c->have_bound) { c->last_error = "bs_bound_dump before bs_bound_load"; return BS_ERR_STATE; }
+  const size_t B = c->bound_b;
+  if (B == 0) return BS_OK;
+  int rc = use_device(c);
+  if (rc) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint8_t* bb = c->d_bound.as<uint8_t>();
+  if (priority) HIPCHK(c, hipMemcpy(priority, bb + c->off_bprio, B * 4, hipMemcpyDeviceToHost));
+  if (start_ns) HIPCHK(c, hipMemcpy(start_ns, bb + c->off_bstart, B * 8, hipMemcpyDeviceToHost));
+  if (group) HIPCHK(c, hipMemcpy(group, bb + c->off_bgroup, B * 4, hipMemcpyDeviceToHost));
+  if (req) HIPCHK(c, hipMemcpy(req, bb + c->off_breq, B * c->L * 8, hipMemcpyDeviceToHost));   // the lane stride is the entry count
+  if (req_present) HIPCHK(c, hipMemcpy(req_present, bb + c->off_bpres, B * 4, hipMemcpyDeviceToHost));
+  if (pdb) HIPCHK(c, hipMemcpy(pdb, bb + c->off_bpdb, B, hipMemcpyDeviceToHost));
   return BS_OK;
 }
 

@@ -1,11 +1,12 @@
-// tu_preempt.hip — translation unit of the preemption victim search (bs_preempt.hpp: k_preempt_scan / k_preempt_pick) and of the
-// sequential plans (bs_preempt_commit.hpp: k_pc_*), one instantiation per scalar-lane count 0..BS_MAX_SCALARS, and their launch
-// wrappers; see tu_fast.hip for why.
+// tu_preempt.hip — translation unit of the preemption victim search (bs_preempt.hpp: k_preempt_scan / k_preempt_pick), of the
+// sequential plans (bs_preempt_commit.hpp: k_pc_*) and of the bound table's patch (bs_bound_apply.hpp: k_ba_*), one instantiation per
+// scalar-lane count 0..BS_MAX_SCALARS, and their launch wrappers; see tu_fast.hip for why.
 #ifndef BS_UNITY
 #define BS_TU_PREEMPT
 #endif
 #include "bs_preempt.hpp"
 #include "bs_preempt_commit.hpp"
+#include "bs_bound_apply.hpp"
 #include "bs_launch.hpp"
 
 namespace bs {
@@ -50,6 +51,15 @@ static void launch_preempt_apply_s(hipStream_t stream, const NodesDev& nd, const
   }
 }
 
+template <int S>
+static void launch_bound_apply_s(hipStream_t stream, const BoundApplyDev& a, const CompactDev& nw) {
+  const uint32_t items = a.n_remove > a.n_insert ? a.n_remove : a.n_insert;
+  if (a.b) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ba_scatter<S>), dim3((a.b + 255) / 256), dim3(256), 0, stream, a);
+  if (items) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ba_mark<S>), dim3((items + 255) / 256), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ba_boff<S>), dim3(1), dim3(1024), 0, stream, a, nw.boff);
+  if (a.n) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ba_merge<S>), dim3((a.n + 3) / 4), dim3(256), 0, stream, a, nw);
+}
+
 #define BS_PC_CASES(CALL) \
   switch (S) { \
     case 0: CALL(0); break; case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break; \
@@ -68,6 +78,12 @@ void launch_preempt_apply(hipStream_t stream, uint32_t S, const NodesDev& nd, co
 #define BS_PC_APPLY(s) launch_preempt_apply_s<s>(stream, nd, pe, ndirty, assume, reqs, nw)
   BS_PC_CASES(BS_PC_APPLY)
 #undef BS_PC_APPLY
+}
+
+void launch_bound_apply(hipStream_t stream, uint32_t S, const BoundApplyDev& a, const CompactDev& nw) {
+#define BS_BA_APPLY(s) launch_bound_apply_s<s>(stream, a, nw)
+  BS_PC_CASES(BS_BA_APPLY)
+#undef BS_BA_APPLY
 }
 #undef BS_PC_CASES
 

@@ -342,6 +342,20 @@ class BoundStruct(C.Structure):
                 ("req_present", C.POINTER(C.c_uint32))]
 
 
+class BoundDeltaStruct(C.Structure):
+    """bs_bound_delta"""
+    _fields_ = [("n_remove", C.c_uint32),
+                ("remove", C.POINTER(C.c_uint32)),
+                ("n_insert", C.c_uint32),
+                ("node", C.POINTER(C.c_uint32)),
+                ("priority", C.POINTER(C.c_int32)),
+                ("start_ns", C.POINTER(C.c_int64)),
+                ("group", C.POINTER(C.c_int32)),
+                ("req", C.POINTER(C.c_int64)),
+                ("req_present", C.POINTER(C.c_uint32)),
+                ("pdb_violating", C.POINTER(C.c_uint8))]
+
+
 class PreemptOutStruct(C.Structure):
     """bs_preempt_out"""
     _fields_ = [("node", C.POINTER(C.c_int32)),

@@ -616,7 +616,8 @@ int bs_bound_load(bs_ctx* ctx, const bs_bound_soa* bound);
 int bs_bound_count(const bs_ctx* ctx, uint32_t* b_out);
 /* The PDB bit of every bound pod: violating[id] != 0 = "some PodDisruptionBudget of the pod's namespace whose selector matches its labels
  * has Status.PodDisruptionsAllowed <= 0" (D1 above; matching labels is the caller's work).  ids are the caller's numbering at the last
- * bs_bound_load and b is that load's entry count (BS_ERR_INVALID otherwise); entries evicted since by BS_PREEMPT_APPLY are skipped.
+ * bs_bound_load and b is that load's entry count — the id space, which bs_bound_apply grows (bs_bound_ids) — (BS_ERR_INVALID
+ * otherwise); entries evicted since by BS_PREEMPT_APPLY or removed by bs_bound_apply are skipped.
  * violating == NULL clears every bit.  bs_bound_load clears them too.  BS_ERR_STATE before bs_bound_load.  The bits stay until the next
  * bs_bound_pdb_set / bs_bound_load; a surviving entry keeps its bit through BS_PREEMPT_APPLY.  Synchronous. */
 int bs_bound_pdb_set(bs_ctx* ctx, uint32_t b, const uint8_t* violating);
@@ -681,6 +682,49 @@ int bs_preempt_commit(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32
  * entry's id (its index at the last bs_bound_load), node_out[i] = its node.  BS_ERR_STATE before bs_bound_load; the arrays may be NULL
  * when the table is empty. */
 int bs_bound_read(bs_ctx* ctx, uint32_t* id_out, uint32_t* node_out);
+
+/* ---- the bound table patched in place ----------------------------------------------------------------------------------------
+ * bs_bound_load is for a fresh snapshot; between snapshots the table follows the cluster event by event: bs_bound_apply removes
+ * entries by id (pods deleted, or bound pods that left their node) and inserts new ones (pods that bound, a nominee of
+ * BS_PREEMPT_ASSUME among them once it binds).  Host work is proportional to the delta; the device makes one pass over the table.
+ *   ids:    the id space starts as the entry count of the last bs_bound_load.  Inserted entry i gets id ids + i, the space then grows by
+ *           n_insert and *first_id_out = ids (NULL ok).  An id is never used again before the next bs_bound_load, whether its entry
+ *           was removed here or evicted by BS_PREEMPT_APPLY.  bs_bound_ids returns the size of the id space (0 before a load);
+ *           bs_bound_pdb_set's b must equal it (for a context that never calls bs_bound_apply that is the load's entry count, as before).
+ *           Growing the id space past BS_BOUND_MAX: BS_ERR_CAPACITY (reload the table: a load starts a new id space).
+ *   order:  after the call every node's list is in the load's importance order — priority descending, start ascending, id ascending.
+ *           Inserted ids are larger than every existing id: at equal (priority, start) an inserted entry goes behind every survivor, and
+ *           inserted entries keep the delta's order among themselves.  This is exactly the table bs_bound_load would build from the
+ *           surviving and the new entries listed in ascending id order.
+ *   effect: removes are applied before inserts.  Only the bound table changes: node requests stay with bs_nodes_apply /
+ *           bs_nodes_assume, as bs_bound_load leaves them alone.  A surviving entry keeps its PDB bit, an inserted entry takes
+ *           pdb_violating[i] (NULL: every bit clear), and the per-node violating counts are recounted.  Columns are stored as bs_bound_load
+ *           stores them: the pods lane 1, an absent scalar key 0, req_present masked to the context's scalar lanes.  The largest group
+ *           index the table is held to name (checked against the group count by the preemption calls) becomes the maximum of its old
+ *           value and the inserted groups': it never shrinks when the entries naming it leave, which is conservative.
+ *   errors: all are found before anything resident changes; on any error the table, the id space and the bits are as before.
+ *           BS_ERR_STATE before bs_bound_load, or when the node count differs from the load's.  BS_ERR_INVALID: a remove id >= the id
+ *           space, a remove id that is not live (evicted by BS_PREEMPT_APPLY or removed earlier), a remove id listed twice, an insert
+ *           node >= n, an insert group below BS_POD_GROUP_MISSING, NULL required arrays.  BS_ERR_CAPACITY: a node that would hold more
+ *           than BS_BOUND_MAX_PER_NODE entries after the delta (exactly the limit is fine).  An empty delta is BS_OK and changes
+ *           nothing.  Works from an empty table (bs_bound_load with b = 0) and down to an empty one.  Synchronous. */
+typedef struct bs_bound_delta {
+  uint32_t n_remove;
+  const uint32_t* remove;        /* [n_remove] ids of LIVE entries, distinct                                              */
+  uint32_t n_insert;             /* new entries, columns as in bs_bound_soa:                                              */
+  const uint32_t* node;          /* [n_insert]                                                                            */
+  const int32_t*  priority;      /* [n_insert]                                                                            */
+  const int64_t*  start_ns;      /* [n_insert]                                                                            */
+  const int32_t*  group;         /* [n_insert]                                                                            */
+  const int64_t*  req;           /* [L][n_insert]                                                                         */
+  const uint32_t* req_present;   /* [n_insert]                                                                            */
+  const uint8_t*  pdb_violating; /* [n_insert] or NULL = every bit clear                                                  */
+} bs_bound_delta;
+int bs_bound_apply(bs_ctx* ctx, const bs_bound_delta* delta, uint32_t* first_id_out);
+int bs_bound_ids(const bs_ctx* ctx, uint32_t* ids_out);
+/* The live table's columns as stored, in the table order of bs_bound_read (bs_bound_count entries; req is [L][count]).  Any pointer may be
+ * NULL.  BS_ERR_STATE before bs_bound_load. */
+int bs_bound_dump(bs_ctx* ctx, int32_t* priority, int64_t* start_ns, int32_t* group, int64_t* req, uint32_t* req_present, uint8_t* pdb);
 
 /* ---- batched queue ordering ---------------------------------------- */
 /* The permutation that sorts the pending pods the way the scheduling queue does through ScheduleOperation.Compare
@@ -797,6 +841,10 @@ int bs_bound_load_flat(bs_ctx* ctx, uint32_t b, const uint32_t* node, const int3
 int bs_preempt_run_flat(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority, const uint8_t* group_protected,
                         uint32_t victim_cap, int32_t* node, uint32_t* n_candidates, uint32_t* n_victims, uint32_t* victims, int32_t* top_priority,
                         int64_t* priority_sum, int64_t* earliest_start);
+/* bs_bound_apply (bs_bound_delta's fields one by one) */
+int bs_bound_apply_flat(bs_ctx* ctx, uint32_t n_remove, const uint32_t* remove, uint32_t n_insert, const uint32_t* node, const int32_t* priority,
+                        const int64_t* start_ns, const int32_t* group, const int64_t* req, const uint32_t* req_present,
+                        const uint8_t* pdb_violating, uint32_t* first_id_out);
 /* bs_preempt_commit (bs_preempt_out's arrays one by one) */
 int bs_preempt_commit_flat(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
                            const uint8_t* group_protected, uint32_t flags, uint32_t victim_cap, int32_t* node, uint32_t* n_candidates,

@@ -3,7 +3,10 @@ pods per node, for 64 and 1024 preemptors.  Prints one JSON line: ms per call (m
 through the C ABI (upload of the preemptor arrays, both launches, the result copy).  --commit times bs_preempt_commit instead (the
 plan answered in sequence, distinct preemptors) with flags 0 and BS_PREEMPT_APPLY; an APPLY call is timed from the state as loaded (the
 nodes and the bound table are reloaded, untimed, before every call).  --pdb FRACTION marks that share of the bound pods (seeded) as
-PDB-violating through bs_bound_pdb_set before the timed calls; the default 0 sets no bits."""
+PDB-violating through bs_bound_pdb_set before the timed calls; the default 0 sets no bits.  --bound-apply K [K ...] times the bound
+table's patch instead: bs_bound_apply with K removes (seeded live ids) + K inserts (seeded nodes), next to bs_bound_load of a table of
+the same size (what a caller without the patch pays per event batch) and to a plain device-to-device copy of the table's allocation (the
+floor of any patch that forms a copy), all in one process."""
 from __future__ import annotations
 
 import argparse
@@ -64,13 +67,78 @@ def one(config: str, q: int, reps: int, warmup: int, commit: bool = False, apply
     return row
 
 
+def _table_bytes(L: int, n: int, b: int) -> int:
+    """the size of the bound table's one allocation (csrc/bsched.hip, bound_layout: columns at 256-byte offsets)"""
+    al = lambda x: (x + 255) // 256 * 256                     # noqa: E731
+    nb = max(b, 1)
+    return sum(al(x) for x in ((n + 1) * 4, nb * 4, nb * 8, nb * 4, nb * 4, nb * L * 8, nb * 4, nb, max(n, 1) * 4))
+
+
+def _median_ms(fn, reps: int, warmup: int) -> tuple:
+    ts = []
+    for it in range(warmup + reps):
+        t0 = time.perf_counter()
+        fn()
+        if it >= warmup:
+            ts.append((time.perf_counter() - t0) * 1e3)
+    return round(float(np.median(ts)), 4), round(float(min(ts)), 4)
+
+
+def bound_apply_rows(config: str, ks, reps: int, warmup: int) -> list:
+    import torch
+    cfg = synth.CONFIGS[config]
+    n, S = cfg["nodes"], cfg["scalars"]
+    bound, nodes = synth.make_bound(20260921, n, cfg["groups"], (20, 110), S)
+    fit = synth.make_fit(20260921, n, cfg["classes"])
+    rng = np.random.default_rng(20260921)
+    rows = []
+    with bsa.Context(scalar_lanes=S, device=0) as ctx:
+        ctx.load_nodes(nodes, fit)
+        ctx.load_bound(bound)
+        nbytes = _table_bytes(4 + S, n, bound.b)
+        src, dst = torch.zeros(nbytes, dtype=torch.uint8, device="cuda"), torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+
+        def copy():
+            dst.copy_(src)
+            torch.cuda.synchronize()
+
+        copy_ms, copy_min = _median_ms(copy, reps, warmup)
+        load_ms, load_min = _median_ms(lambda: ctx.load_bound(bound), reps, warmup)
+        for k in ks:
+            ctx.load_bound(bound)
+            live = np.arange(bound.b, dtype=np.uint32)
+            ts = []
+            for it in range(warmup + reps):
+                at = rng.permutation(live.size)[:k]
+                src_i = rng.integers(0, bound.b, k)
+                ins = soa.Bound(rng.integers(0, n, k).astype(np.uint32), bound.priority[src_i], bound.start_ns[src_i], bound.group[src_i],
+                                bound.req[:, src_i], bound.req_present[src_i])
+                rem = live[at]
+                t0 = time.perf_counter()
+                first = ctx.bound_apply(rem, ins)
+                if it >= warmup:
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                live = np.concatenate([np.delete(live, at), np.arange(first, first + k, dtype=np.uint32)])
+            assert ctx.bound_count() == bound.b and np.array_equal(np.sort(ctx.read_bound()[0]), np.sort(live))
+            ms = round(float(np.median(ts)), 4)
+            rows.append(dict(config=config, nodes=n, bound=int(bound.b), table_bytes=nbytes, k=k, apply_ms=ms, apply_ms_min=round(float(min(ts)), 4),
+                             reload_ms=load_ms, reload_ms_min=load_min, copy_ms=copy_ms, copy_ms_min=copy_min,
+                             reload_over_apply=round(load_ms / ms, 2), apply_over_copy=round(ms / copy_ms, 2)))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--commit", action="store_true", help="bs_preempt_commit, flags 0 and APPLY")
     ap.add_argument("--pdb", type=float, default=0.0, metavar="FRACTION", help="share of the bound pods with the PDB-violating bit (seeded)")
+    ap.add_argument("--bound-apply", type=int, nargs="+", default=None, metavar="K", help="bs_bound_apply with K removes + K inserts, vs the reload and a plain copy")
     a = ap.parse_args()
+    if a.bound_apply:
+        rows = [r for c in ("cfg3", "cfg4") for r in bound_apply_rows(c, a.bound_apply, a.reps, a.warmup)]
+        print(json.dumps(dict(metric="bs_bound_apply ms per call", rows=rows)))
+        return
     if a.commit:
         rows = [one(c, q, a.reps, a.warmup, True, ap_, a.pdb) for c in ("cfg3", "cfg4") for q in (64, 1024) for ap_ in (False, True)]
         print(json.dumps(dict(metric="bs_preempt_commit ms per call", rows=rows)))
