@@ -27,6 +27,7 @@
 #include "bs_fdeny.hpp"
 #include "bs_seq.hpp"
 #include "bs_launch.hpp"
+#include "bs_hostmem.hpp"
 #include "bs_pod_ranges.hpp"
 #include "bs_preempt.hpp"
 #include "bs_preempt_commit.hpp"
@@ -41,22 +42,6 @@
 using namespace bs;
 
 namespace {
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t reserve(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    size_t want = std::max<size_t>(bytes, 256);
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
-};
 
 struct EventPair { hipEvent_t a, b; uint32_t id; };
 
@@ -104,12 +89,14 @@ PodLayout pod_layout(uint32_t P, uint32_t L) {
   return l;
 }
 
+// the bound-pod table's columns in its one allocation (bound_layout)
+struct BoundLayout { size_t boff, prio, start, group, id, req, pres, pdb, nviol; };
+
 }  // namespace
 
 struct bs_ctx {
   bs_config cfg{};
   uint32_t L = 4, S = 0, LP = 4;
-  hipStream_t stream = nullptr;
   std::string last_error;
 
   // ---- nodes
@@ -141,17 +128,10 @@ struct bs_ctx {
   uint32_t host_probe = 0;
   uint64_t hp_ns[6] = {0, 0, 0, 0, 0, 0}, hp_n = 0, hp_t0 = 0, hp_t1 = 0;
   uint64_t early_filter_min = 200000000ull;   // pod x node pairs from which Filter overlaps the scan
-  hipStream_t stream3 = nullptr;    // early Filter: runs beside the node scan when no capture can occur
-  hipEvent_t ev_query = nullptr, ev_filter = nullptr;
   // groups live in ONE device allocation (one pinned-staged H2D per load); d_info / h_info carry what findMaxPG
   // found for the loaded state back to the host without a stream wait (see resolve_groups)
   DevBuf d_gpack, d_info, d_gdelta;
   size_t off_gmm = 0, off_gsc = 0, off_gmatched = 0, off_gflags = 0, off_gcls = 0, off_gminres = 0, off_gmrpres = 0, off_gocc = 0, gpack_bytes = 0;
-  void* h_gstage = nullptr;          // pinned: groups pack, then deltas
-  size_t h_gstage_cap = 0;
-  hipEvent_t ev_gstage = nullptr;
-  bool gstage_busy = false;
-  int32_t* h_info = nullptr;         // pinned [8]: leader, panic, steady table, tag | K of the loaded pods, tag
   int32_t info_tag = 0, kinfo_tag = 0;
   bool info_pending = false, kinfo_pending = false;
   uint32_t max_group_cls = 0, max_pod_cls = 0;   // largest fit class any HAS_POD group / grouped pod names (checked against C per batch)
@@ -164,11 +144,7 @@ struct bs_ctx {
   DevBuf d_pack[2], d_outpack;       // two pod packs: bs_pods_apply compacts from the current one into the other
   PodLayout lay[2], stage_lay;       // their layouts, and the staging buffer's own
   uint32_t cur_pack = 0;
-  void* h_stage = nullptr;           // pinned host staging
-  hipEvent_t ev_stage = nullptr;     // the last H2D out of the staging buffer (bs_pods_load does not wait for it)
-  bool stage_busy = false;
   bool last_use_classes = false;
-  size_t h_stage_cap = 0;
   uint32_t map_p = 0;                // pods the staging buffer is currently mapped for (bs_pods_map), 0 = not mapped
   // queue-resident cycle (bs_pods_apply, bs_queue.hpp)
   DevBuf d_gstat2, d_cdir, d_pdir, d_ckeys, d_cpres, d_pkeys;
@@ -179,14 +155,7 @@ struct bs_ctx {
   bool dirs_ready = false;           // the directories match the resident queue's classes and pairs
   uint32_t id_room = 0;              // BS_ID_ROOM: ids beyond the queue length (0 = the default: as many again + 1024)
   uint32_t serial_insert_max = 2048; // more inserted pods than this: re-derive in parallel instead of the insert wave
-  void* h_dstage = nullptr;          // pinned: the delta the apply kernel reads in place
-  size_t h_dstage_cap = 0;
-  bool dstage_busy = false;
   uint64_t n_applies = 0, n_rederives = 0;
-  void* h_nstage = nullptr;          // pinned: node requests of bs_nodes_assume
-  size_t h_nstage_cap = 0;
-  hipEvent_t ev_nstage = nullptr;
-  bool nstage_busy = false;
   size_t off_pf_code = 0, off_pf_first_k = 0, off_pf_leader = 0, off_fl_code = 0, off_fl_feasible = 0, off_fl_slot = 0, off_admit = 0, off_ready = 0, outpack_bytes = 0;
 
   // ---- batch scratch / outputs
@@ -215,12 +184,7 @@ struct bs_ctx {
   bool bitmap_valid = false;         // d_fl_bitmap holds the expanded rows of the last batch
   bool last_fast = false;
   bool batch_since_pods = false;     // a batch ran over the loaded pods (its slot mode is the one the rows have)
-  // result staging (bs_batch_read) and, in latency mode, the pinned result pack the last launch writes itself
-  void* h_rstage = nullptr;
-  size_t h_rstage_cap = 0;
-  uint8_t* h_hout = nullptr;         // [outpack layout | feas[hstride] | tag]
-  uint64_t* h_hrows = nullptr;       // [W + 1][hstride]
-  size_t h_hout_cap = 0, h_hrows_cap = 0, off_hfeas = 0, off_htag = 0;
+  size_t off_hfeas = 0, off_htag = 0; // in h_hout
   uint32_t hstride = 0;
   int32_t host_tag = 0;
   bool last_host_out = false;
@@ -273,12 +237,14 @@ struct bs_ctx {
   int fused_blocks_resident = -1;    // whole-chip residency of k_fast_scan_filter_final (blocks), -1 = not asked yet
   int step_a_resident[2] = {-1, -1};          // ... of k_fast_step_a
   // The one-launch form of launch A + the scan / Filter roles (k_fast_step_a, then k_fast_final), where it applies (the latency regime: at most 256
-  // classes, 64 table chunks, 4 scalar lanes; the second batch over a queue onwards).  BS_STEP_A=2, the DEFAULT since round 6: the class-slot form —
-  // class_slots_block publishes every class's slots from the class directory, the pod blocks gate nobody: 19.05-19.35 us per cfg3/tail step against
-  // 20.5-20.7 for the two-launch chain.  BS_STEP_A=1: round 5's form (every pod block publishes: 32 us, kept as a tested experiment).  BS_STEP_A=0: off.
+  // classes, 64 table chunks, 4 scalar lanes; the second batch over a queue onwards).  BS_STEP_A=3, the DEFAULT: the whole-step form — the class-slot
+  // form below whose pod blocks go on to the final verdicts inside the same launch (one launch per step; run_fast falls back to form 2 where it does not apply).
+  // BS_STEP_A=2: the class-slot form — class_slots_block publishes every class's slots from the class directory, the pod blocks gate nobody; k_fast_final
+  // follows as a second launch.  BS_STEP_A=1: every pod block publishes (kept as a tested experiment).  BS_STEP_A=0: off.  Step times: BASELINE.md.
   uint32_t step_a_form = 3;
   bool step_a_on = true;
-  uint32_t step_shares = 8;          // BS_STEP_SHARES: blocks that share one table chunk's class slots (class-slot form, cfg3: 2 / 4 / 8 / 16 shares = 25.1 / 20.4 / 19.05 / 20.9 us per step)
+  uint32_t step_shares = 8;          // BS_STEP_SHARES: blocks that share one table chunk's class slots (at most).  8 was the fastest of 2 / 4 / 8 / 16 under BS_STEP_A=2
+                                     // (profiles/r06_step_a_class_slots_shares.txt); the whole-step form has not been swept
   uint32_t test_timeout_after = 0;   // BS_TEST_HANDOVER_TIMEOUT=n (test hook): the n-th one-launch step reports a timed-out hand-over as the device would
   uint32_t test_pc_chunk_nodes = 0;  // BS_TEST_PC_CHUNK_NODES=n (test hook): nodes per chunk of the preemption grids (bs_preempt_geom.hpp); 0 = the shipped geometry
   uint32_t tk_pods = 0, tk_tab = 0;  // values of ticket[8] / ticket[9] the next k_fast_step_a starts from (never reset: wrap-safe differences)
@@ -288,7 +254,7 @@ struct bs_ctx {
   bool ranges_valid = false;         // (also dropped by a bs_groups_load that changes the group count: the local flags are per group)
   uint32_t nranges = 0;
   PodRanges h_ranges;
-  std::vector<uint32_t> h_pod_ranges;  // BatchDev::pod_ranges as uploaded (the copy reads it: rewritten only after ev_stage)
+  std::vector<uint32_t> h_pod_ranges;  // BatchDev::pod_ranges as uploaded (the copy reads it: rewritten only after h_stage.wait)
   DevBuf d_pod_ranges;
   bool last_step_a = false;
   uint32_t scan_share_override = 0, no_fuse_filter = 0, early_forced = 0, target_waves = 8192, filter_waves = 8192, collect_stats = 0;
@@ -321,10 +287,25 @@ struct bs_ctx {
   int32_t bound_max_group = -1;      // largest group index the table names (checked against the group count per call)
   DevBuf d_bound, d_pre;
   DevBuf d_bound2;                   // bs_preempt_commit's compaction target (swapped with d_bound)
-  size_t off_boff = 0, off_bprio = 0, off_bstart = 0, off_bgroup = 0, off_bid = 0, off_breq = 0, off_bpres = 0, off_bpdb = 0, off_bnviol = 0;
+  BoundLayout blay{};
   uint32_t bound_ids = 0;            // the id space of bs_bound_pdb_set: entries at the last bs_bound_load plus what bs_bound_apply inserted since
   std::vector<uint32_t> pre_npv;     // PDB-violating victims per preemptor of the last preemption call (bs_preempt_pdb_read)
   bool have_pre_npv = false;
+
+  // ---- streams, events, pinned host memory.  Declared LAST and in this order: members are destroyed in reverse, so the pinned buffers
+  // and events go first, then stream3, then stream, and only then the DevBufs above (bs_destroy has waited for both streams).
+  Stream stream;
+  Stream stream3;                    // early Filter: runs beside the node scan when no capture can occur
+  Event ev_query, ev_filter;
+  PinnedBuf<int32_t> h_info{PinWait::None, hipHostMallocMapped | hipHostMallocCoherent};   // [16], kernels write it directly: leader, panic, steady table, tag | K of the loaded pods, tag | ...
+  PinnedBuf<> h_gstage{PinWait::Event};   // groups pack, then deltas
+  PinnedBuf<> h_stage{PinWait::Event};    // pod staging; busy until the last H2D out of it is through (bs_pods_load does not wait for it)
+  PinnedBuf<> h_dstage{PinWait::Stream};  // the delta the apply kernel reads in place (no event per apply: bs_pods_apply)
+  PinnedBuf<> h_nstage{PinWait::Event};   // node requests of bs_nodes_assume
+  // result staging (bs_batch_read) and, in latency mode, the pinned result pack the last launch writes itself
+  PinnedBuf<> h_rstage;
+  PinnedBuf<> h_hout{PinWait::None, hipHostMallocMapped | hipHostMallocCoherent};            // [outpack layout | feas[hstride] | tag]
+  PinnedBuf<uint64_t> h_hrows{PinWait::None, hipHostMallocMapped | hipHostMallocCoherent};   // [W + 1][hstride]
 };
 
 namespace {
@@ -528,11 +509,11 @@ BatchDev batch_dev(const bs_ctx* c) {
   b.first_reach64 = c->d_first_reach.as<unsigned long long>();
   b.fast_reject = c->d_fast_reject.as<uint32_t>();
   b.epoch_group = c->d_epoch_group.as<uint32_t>();
-  b.h_err = c->h_info ? c->h_info + 12 : nullptr;
+  b.h_err = c->h_info.p ? c->h_info.p + 12 : nullptr;
   b.fd_event = c->d_fd_event.as<unsigned long long>();
   b.fd_in = c->fd_in_live ? c->d_fd_in.as<uint32_t>() : nullptr;
   b.fd_flag = c->d_fd_flag.as<uint32_t>();
-  b.h_fd = c->h_info ? c->h_info + 14 : nullptr;
+  b.h_fd = c->h_info.p ? c->h_info.p + 14 : nullptr;
   uint8_t* ok = c->d_outpack.as<uint8_t>();
   b.pf_code = at(ok, c->off_pf_code);
   b.pf_first_k = reinterpret_cast<uint32_t*>(at(ok, c->off_pf_first_k));
@@ -815,7 +796,7 @@ int analyse_groups(bs_ctx* c, bool rearm_scratch = true, const bs_group_delta* d
     c->groups_launch_pending = true;
     return BS_OK;
   }
-  hipLaunchKernelGGL(k_leader_info, dim3(1), dim3(kLeaderBlock), 0, c->stream, gr, b, (c->have_fit && c->have_nodes) ? c->C : 0u, c->info_tag, c->h_info,
+  hipLaunchKernelGGL(k_leader_info, dim3(1), dim3(kLeaderBlock), 0, c->stream, gr, b, (c->have_fit && c->have_nodes) ? c->C : 0u, c->info_tag, c->h_info.p,
                      dp, const_cast<uint32_t*>(gr.matched), const_cast<uint32_t*>(gr.status_scheduled), const_cast<uint8_t*>(gr.flags));
   LAUNCHCHK(c, BS_KERNEL_LEADER);
   return BS_OK;
@@ -827,7 +808,7 @@ int flush_groups(bs_ctx* c) {
   c->groups_launch_pending = false;
   GroupsDev gr = groups_dev(c);
   BatchDev b = batch_dev(c);
-  hipLaunchKernelGGL(k_leader_info, dim3(1), dim3(kLeaderBlock), 0, c->stream, gr, b, (c->have_fit && c->have_nodes) ? c->C : 0u, c->info_tag, c->h_info,
+  hipLaunchKernelGGL(k_leader_info, dim3(1), dim3(kLeaderBlock), 0, c->stream, gr, b, (c->have_fit && c->have_nodes) ? c->C : 0u, c->info_tag, c->h_info.p,
                      c->pending_dp, const_cast<uint32_t*>(gr.matched), const_cast<uint32_t*>(gr.status_scheduled), const_cast<uint8_t*>(gr.flags));
   LAUNCHCHK(c, BS_KERNEL_LEADER);
   return BS_OK;
@@ -836,7 +817,7 @@ int flush_groups(bs_ctx* c) {
 // Wait until the kernel that wrote h_info[tag_at] = tag has done so (it writes pinned host memory directly).  By
 // the time anybody asks, the kernel has normally finished long ago and this is one load.
 int wait_host_tag(bs_ctx* c, int tag_at, int32_t tag, const int32_t* base = nullptr) {
-  volatile const int32_t* info = base ? base : c->h_info;
+  volatile const int32_t* info = base ? base : c->h_info.p;
   for (uint32_t spin = 0; info[tag_at] != tag; ++spin) {
     if (spin == 2000) (void)hipStreamQuery(c->stream);                    // make sure the launch has left the host
     if (spin > 20000000u) { HIPCHK(c, hipStreamSynchronize(c->stream)); if (info[tag_at] != tag) { c->last_error = "host info tag never arrived"; return BS_ERR_HIP; } }
@@ -850,7 +831,7 @@ int resolve_groups(bs_ctx* c) {
   int rc = wait_host_tag(c, 3, c->info_tag);
   if (rc) return rc;
   c->info_pending = false;
-  c->steady_table = (c->n_uncaptured == 0 && c->h_info[2] >= 0) ? c->h_info[2] : -1;
+  c->steady_table = (c->n_uncaptured == 0 && c->h_info.p[2] >= 0) ? c->h_info.p[2] : -1;
   c->steady_prev = c->steady_table;
   return BS_OK;
 }
@@ -860,17 +841,8 @@ int resolve_pods(bs_ctx* c) {
   int rc = wait_host_tag(c, 5, c->kinfo_tag);
   if (rc) return rc;
   c->kinfo_pending = false;
-  c->h_K = (uint32_t)c->h_info[4];
+  c->h_K = (uint32_t)c->h_info.p[4];
   c->k_bound = c->h_K;
-  return BS_OK;
-}
-
-int ensure_gstage(bs_ctx* c, size_t bytes) {
-  if (c->gstage_busy) { HIPCHK(c, hipEventSynchronize(c->ev_gstage)); c->gstage_busy = false; }
-  if (bytes <= c->h_gstage_cap) return BS_OK;
-  if (c->h_gstage) { (void)hipHostFree(c->h_gstage); c->h_gstage = nullptr; c->h_gstage_cap = 0; }
-  HIPCHK(c, hipHostMalloc(&c->h_gstage, bytes, hipHostMallocDefault));
-  c->h_gstage_cap = bytes;
   return BS_OK;
 }
 
@@ -910,7 +882,7 @@ int derive_pods(bs_ctx* c, bool pairs_only) {
   c->kinfo_tag++;
   hipLaunchKernelGGL(k_pod_pairs, dim3(std::max<uint32_t>(1, cdiv(P, 256))), dim3(256), 0, c->stream, pods_dev(c), G, c->d_cls_rep.as<uint32_t>(),
                      c->d_cls_id.as<uint32_t>(), pclass_dev(c), ptab, c->cls_cap - 1, c->hash_keep, c->d_gstat.as<uint32_t>(),
-                     ppair_dev(c), c->d_pair_next.as<unsigned long long>(), kcount, c->kinfo_tag, c->h_info, gcount);
+                     ppair_dev(c), c->d_pair_next.as<unsigned long long>(), kcount, c->kinfo_tag, c->h_info.p, gcount);
   LAUNCHCHK(c, BS_KERNEL_PREPASS);
   c->kinfo_pending = true;
   c->k_bound = P;                                                    // a fresh derivation: no more classes than pods
@@ -1009,7 +981,7 @@ int analyse_epochs(bs_ctx* c) {
   hipLaunchKernelGGL(k_epochs2_b, dim3(cdiv(P, kScanBlock)), dim3(kScanBlock), 0, c->stream, pd, gr, b);
   hipLaunchKernelGGL(k_leader_scan, dim3(1), dim3(kLeaderBlock), 0, c->stream, gr, b);
   c->einfo_tag++;
-  hipLaunchKernelGGL(k_epoch_views, dim3(1), dim3(kLeaderBlock), 0, c->stream, pd, gr, b, ep, c->C, c->einfo_tag, c->h_info + 8);
+  hipLaunchKernelGGL(k_epoch_views, dim3(1), dim3(kLeaderBlock), 0, c->stream, pd, gr, b, ep, c->C, c->einfo_tag, c->h_info.p + 8);
   LAUNCHCHK(c, BS_KERNEL_LEADER);
   c->einfo_pending = true;
   c->epochs_ready = true;
@@ -1045,8 +1017,8 @@ int resolve_epochs(bs_ctx* c) {
   int rc = wait_host_tag(c, 11, c->einfo_tag);
   if (rc) return rc;
   c->einfo_pending = false;
-  c->h_R = (uint32_t)c->h_info[8];
-  c->h_eflags = (uint32_t)c->h_info[9];
+  c->h_R = (uint32_t)c->h_info.p[8];
+  c->h_eflags = (uint32_t)c->h_info.p[9];
   return BS_OK;
 }
 
@@ -1081,46 +1053,8 @@ const char* bs_strerror(int status) {
 const char* bs_last_error(const bs_ctx* ctx) { return ctx ? ctx->last_error.c_str() : ""; }
 const char* bs_kernel_name(uint32_t id) { return id < BS_KERNEL_COUNT ? kKernelNames[id] : "?"; }
 
-int bs_create(const bs_config* cfg, bs_ctx** out) {
-  if (!cfg || !out) return BS_ERR_INVALID;
-  *out = nullptr;
-  if (cfg->abi_version != BS_ABI_VERSION || cfg->scalar_lanes > BS_MAX_SCALARS) return BS_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return BS_ERR_NO_DEVICE;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess) return BS_ERR_NO_DEVICE;
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return BS_ERR_NO_DEVICE;   // gfx950-only code object
-  bs_ctx* c = new (std::nothrow) bs_ctx();
-  if (!c) return BS_ERR_NOMEM;
-  c->cfg = *cfg;
-  c->S = cfg->scalar_lanes;
-  c->L = BS_FIXED_LANES + c->S;
-  c->LP = c->S == 0 ? 4 : (c->S <= 4 ? 8 : 16);
-  if (hipSetDevice(cfg->device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete c;
-    return BS_ERR_NO_DEVICE;
-  }
-  if (hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_filter, hipEventDisableTiming) != hipSuccess) {
-    delete c;
-    return BS_ERR_NO_DEVICE;
-  }
-  // small counters every load / batch path touches: owned by the context from the start, so no call order
-  // between bs_pods_load and bs_groups_load is implied
-  if (c->d_nepochs.reserve(64) != hipSuccess || hipMemset(c->d_nepochs.p, 0, 64) != hipSuccess || c->d_ticket.reserve(kTkWords * 4) != hipSuccess ||
-      hipMemset(c->d_ticket.p, 0, kTkWords * 4) != hipSuccess) {
-    delete c;
-    return BS_ERR_NOMEM;
-  }
-  if (c->d_info.reserve(64) != hipSuccess || c->d_first_reach.reserve(64) != hipSuccess || hipMemset(c->d_first_reach.p, 0xFF, 64) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_info, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||   // kernels write it directly
-      hipEventCreateWithFlags(&c->ev_gstage, hipEventDisableTiming) != hipSuccess) {
-    delete c;
-    return BS_ERR_NOMEM;
-  }
-  std::memset(c->h_info, 0, 64);
-  c->batch_seq = 1;
+// the environment's A/B switches and test hooks, read once per context
+static void read_env_switches(bs_ctx* c) {
   // test hooks (tests/test_gpu_soak.py): start the wrapping counters just below their wrap points
   if (const char* e = std::getenv("BS_STAMP_START")) c->stamp_ctr = (uint32_t)(std::strtoul(e, nullptr, 0) % 65535u);
   if (const char* e = std::getenv("BS_KEYSEQ_START")) { c->key_seq = (uint32_t)std::strtoul(e, nullptr, 0); if (c->key_seq == 0u || c->key_seq == 0xFFFFFFFFu) c->key_seq = 1; }
@@ -1149,6 +1083,46 @@ int bs_create(const bs_config* cfg, bs_ctx** out) {
   if (const char* e = std::getenv("BS_FILTER_WAVES")) { c->filter_waves = std::max(1, std::atoi(e)); c->filter_waves_env = true; }
   if (const char* e = std::getenv("BS_SERIAL_INSERT_MAX")) c->serial_insert_max = (uint32_t)std::max(0, std::atoi(e));
   if (const char* e = std::getenv("BS_ID_ROOM")) c->id_room = (uint32_t)std::max(1, std::atoi(e));   // tests: a tiny id space forces re-derivations
+}
+
+int bs_create(const bs_config* cfg, bs_ctx** out) {
+  if (!cfg || !out) return BS_ERR_INVALID;
+  *out = nullptr;
+  if (cfg->abi_version != BS_ABI_VERSION || cfg->scalar_lanes > BS_MAX_SCALARS) return BS_ERR_INVALID;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return BS_ERR_NO_DEVICE;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess) return BS_ERR_NO_DEVICE;
+  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return BS_ERR_NO_DEVICE;   // gfx950-only code object
+  bs_ctx* c = new (std::nothrow) bs_ctx();
+  if (!c) return BS_ERR_NOMEM;
+  c->cfg = *cfg;
+  c->S = cfg->scalar_lanes;
+  c->L = BS_FIXED_LANES + c->S;
+  c->LP = c->S == 0 ? 4 : (c->S <= 4 ? 8 : 16);
+  // (every exit below: `delete c` releases whatever the context has got by then)
+  if (hipSetDevice(cfg->device) != hipSuccess || hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking) != hipSuccess ||
+      hipStreamCreateWithFlags(&c->stream3.h, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_query.h, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_filter.h, hipEventDisableTiming) != hipSuccess) {
+    delete c;
+    return BS_ERR_NO_DEVICE;
+  }
+  // small counters every load / batch path touches: owned by the context from the start, so no call order
+  // between bs_pods_load and bs_groups_load is implied
+  if (c->d_nepochs.reserve(64) != hipSuccess || hipMemset(c->d_nepochs.p, 0, 64) != hipSuccess || c->d_ticket.reserve(kTkWords * 4) != hipSuccess ||
+      hipMemset(c->d_ticket.p, 0, kTkWords * 4) != hipSuccess) {
+    delete c;
+    return BS_ERR_NOMEM;
+  }
+  if (c->d_info.reserve(64) != hipSuccess || c->d_first_reach.reserve(64) != hipSuccess || hipMemset(c->d_first_reach.p, 0xFF, 64) != hipSuccess ||
+      c->h_info.reserve(64) != hipSuccess) {
+    delete c;
+    return BS_ERR_NOMEM;
+  }
+  std::memset(c->h_info.p, 0, 64);
+  c->batch_seq = 1;
+  read_env_switches(c);
   *out = c;
   return BS_OK;
 }
@@ -1160,24 +1134,10 @@ int bs_destroy(bs_ctx* c) {
                  (unsigned long long)c->hp_n, c->hp_ns[0] / 1e3 / c->hp_n, c->hp_ns[1] / 1e3 / c->hp_n, c->hp_ns[2] / 1e3 / c->hp_n, c->hp_ns[3] / 1e3 / c->hp_n,
                  c->hp_ns[4] / 1e3 / c->hp_n, c->hp_ns[5] / 1e3 / c->hp_n);
   (void)hipSetDevice(c->cfg.device);
-  if (c->stream) { (void)hipStreamSynchronize(c->stream); }
+  (void)hipStreamSynchronize(c->stream);
+  (void)hipStreamSynchronize(c->stream3);
   for (auto& e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   if (c->comm && c->rccl_destroy) (void)c->rccl_destroy((ncclComm_t)c->comm);
-  if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
-  if (c->ev_gstage) (void)hipEventDestroy(c->ev_gstage);
-  if (c->h_info) (void)hipHostFree(c->h_info);
-  if (c->h_rstage) (void)hipHostFree(c->h_rstage);
-  if (c->h_hout) (void)hipHostFree(c->h_hout);
-  if (c->h_hrows) (void)hipHostFree(c->h_hrows);
-  if (c->h_gstage) (void)hipHostFree(c->h_gstage);
-  if (c->h_dstage) (void)hipHostFree(c->h_dstage);
-  if (c->h_nstage) (void)hipHostFree(c->h_nstage);
-  if (c->ev_nstage) (void)hipEventDestroy(c->ev_nstage);
-  if (c->stream3) { (void)hipStreamSynchronize(c->stream3); (void)hipStreamDestroy(c->stream3); }
-  if (c->ev_query) (void)hipEventDestroy(c->ev_query);
-  if (c->ev_filter) (void)hipEventDestroy(c->ev_filter);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return BS_OK;
 }
@@ -1387,9 +1347,8 @@ int bs_groups_load(bs_ctx* c, const bs_groups_soa* g) {
   c->n_nominres = 0;
   c->max_group_cls = 0;
   if (G) {
-    rc = ensure_gstage(c, c->gpack_bytes);
-    if (rc) return rc;
-    uint8_t* st = reinterpret_cast<uint8_t*>(c->h_gstage);
+    HIPCHK(c, c->h_gstage.reserve(c->gpack_bytes));
+    uint8_t* st = c->h_gstage.p;
     std::memcpy(st + c->off_gmm, g->min_member, (size_t)G * 4);
     std::memcpy(st + c->off_gsc, g->status_scheduled, (size_t)G * 4);
     std::memcpy(st + c->off_gmatched, g->matched, (size_t)G * 4);
@@ -1399,8 +1358,7 @@ int bs_groups_load(bs_ctx* c, const bs_groups_soa* g) {
     std::memcpy(st + c->off_gmrpres, g->min_resources_present, (size_t)G * 4);
     std::memcpy(st + c->off_gocc, g->occupied_by, (size_t)G * 8);
     HIPCHK(c, hipMemcpyAsync(c->d_gpack.p, st, c->gpack_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_gstage, c->stream));
-    c->gstage_busy = true;
+    HIPCHK(c, c->h_gstage.mark_busy(c->stream));
     for (uint32_t i = 0; i < G; ++i) {
       if (!(g->flags[i] & BS_GROUP_HAS_POD)) c->n_uncaptured++;
       else c->max_group_cls = std::max(c->max_group_cls, g->cls[i]);
@@ -1449,13 +1407,11 @@ int bs_groups_apply(bs_ctx* c, const bs_group_delta* deltas, uint32_t count) {
     return maybe_analyse_epochs(c);                  // (positional state: flushes the patch, the analysis reads the patched groups)
   }
   const size_t bytes = (size_t)count * sizeof(bs_group_delta);
-  rc = ensure_gstage(c, std::max(bytes, c->gpack_bytes));
-  if (rc) return rc;
+  HIPCHK(c, c->h_gstage.reserve(std::max(bytes, c->gpack_bytes)));
   HIPCHK(c, c->d_gdelta.reserve(bytes));
-  std::memcpy(c->h_gstage, deltas, bytes);
-  HIPCHK(c, hipMemcpyAsync(c->d_gdelta.p, c->h_gstage, bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->ev_gstage, c->stream));
-  c->gstage_busy = true;
+  std::memcpy(c->h_gstage.p, deltas, bytes);
+  HIPCHK(c, hipMemcpyAsync(c->d_gdelta.p, c->h_gstage.p, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, c->h_gstage.mark_busy(c->stream));
   GroupsDev gr = groups_dev(c);
   hipLaunchKernelGGL(k_groups_apply, dim3(cdiv(count, 256)), dim3(256), 0, c->stream, c->d_gdelta.as<GroupDelta>(), count,
                      const_cast<uint32_t*>(gr.matched), const_cast<uint32_t*>(gr.status_scheduled), const_cast<uint8_t*>(gr.flags));
@@ -1486,24 +1442,14 @@ int bs_groups_read(bs_ctx* c, bs_groups_soa* g) {
   return BS_OK;
 }
 
-static int ensure_stage(bs_ctx* c, size_t bytes) {
-  // the previous upload may still be reading the staging buffer
-  if (c->stage_busy) { HIPCHK(c, hipEventSynchronize(c->ev_stage)); c->stage_busy = false; }
-  if (bytes <= c->h_stage_cap) return BS_OK;
-  if (c->h_stage) { (void)hipHostFree(c->h_stage); c->h_stage = nullptr; c->h_stage_cap = 0; }
-  HIPCHK(c, hipHostMalloc(&c->h_stage, bytes, hipHostMallocDefault));
-  c->h_stage_cap = bytes;
-  return BS_OK;
-}
 int bs_pods_map(bs_ctx* c, uint32_t p, bs_pods_soa* view) {
   if (!c || !view || !p) return BS_ERR_INVALID;
   int rc = use_device(c);
   if (rc) return rc;
   const PodLayout l = pod_layout(p, c->L);           // the staging buffer's own layout: the resident queue is not touched
-  rc = ensure_stage(c, l.in_bytes);                  // waits until the previous upload has left the buffer
-  if (rc) return rc;
+  HIPCHK(c, c->h_stage.reserve(l.in_bytes));         // waits until the previous upload has left the buffer
   c->stage_lay = l;
-  uint8_t* st = reinterpret_cast<uint8_t*>(c->h_stage);
+  uint8_t* st = c->h_stage.p;
   view->p = p;
   view->group = reinterpret_cast<const int32_t*>(st + l.group);
   view->req = reinterpret_cast<const int64_t*>(st + l.req);
@@ -1525,12 +1471,12 @@ static int resize_queue(bs_ctx* c, uint32_t P) {
 
 // The whole-step launch's gang-aligned pod ranges (bs_pod_ranges.hpp): O(P) on the host, once per load — nothing per step.  Group ids at or
 // beyond G count as no group (never local).  The upload is ordered before the batches on the stream; the host copy it reads is only rewritten by
-// the next load, after the previous load's copies are through (ev_stage).
+// the next load, after the previous load's copies are through (h_stage.wait).
 static int load_pod_ranges(bs_ctx* c, const int32_t* group, uint32_t P) {
   int rc;
   c->ranges_valid = false;
   if (!c->pod_ranges_on || !P) return BS_OK;
-  if (c->stage_busy && c->ev_stage) { HIPCHK(c, hipEventSynchronize(c->ev_stage)); c->stage_busy = false; }
+  HIPCHK(c, c->h_stage.wait());
   const uint32_t G = c->G;
   PodRanges& r = c->h_ranges;
   pod_ranges(group, P, kTblChunk, G, r);
@@ -1560,16 +1506,13 @@ int bs_pods_load(bs_ctx* c, const bs_pods_soa* pods) {
   c->ranges_valid = false;
   // the caller's arrays ARE the mapped staging buffer (bs_pods_map): nothing to pack.  Pointers into the staging buffer that
   // do not match the mapping (another p, a stale view) would make the packing copy overlap itself: refused.
-  const uint8_t* sb = reinterpret_cast<const uint8_t*>(c->h_stage);
-  const bool inside = P && sb && (const uint8_t*)pods->group >= sb && (const uint8_t*)pods->group < sb + c->h_stage_cap;
+  const uint8_t* sb = c->h_stage.p;
+  const bool inside = P && sb && (const uint8_t*)pods->group >= sb && (const uint8_t*)pods->group < sb + c->h_stage.cap;
   const bool mapped = inside && c->map_p == P && (const uint8_t*)pods->group == sb + c->stage_lay.group && (const uint8_t*)pods->req == sb + c->stage_lay.req &&
                       (const uint8_t*)pods->req_present == sb + c->stage_lay.pres && (const uint8_t*)pods->cls == sb + c->stage_lay.cls &&
                       (const uint8_t*)pods->owner == sb + c->stage_lay.owner && pods->flags == sb + c->stage_lay.flags;
   if (inside && !mapped) { c->last_error = "bs_pods_load: pointers into the mapped staging buffer, but not the view bs_pods_map handed out for this p"; return BS_ERR_INVALID; }
-  if (!mapped) {
-    rc = ensure_stage(c, l.in_bytes);
-    if (rc) return rc;
-  }
+  if (!mapped) HIPCHK(c, c->h_stage.reserve(l.in_bytes));   // the previous upload may still be reading the staging buffer
   c->map_p = 0;
   // pod arrays: one allocation, one transfer (the load always lands in pack 0)
   c->cur_pack = 0;
@@ -1585,7 +1528,7 @@ int bs_pods_load(bs_ctx* c, const bs_pods_soa* pods) {
   for (uint32_t i = 0; i < P; ++i)
     if (pods->group[i] >= 0) c->max_pod_cls = std::max(c->max_pod_cls, pods->cls[i]);
   if (P) {
-    uint8_t* st = reinterpret_cast<uint8_t*>(c->h_stage);
+    uint8_t* st = c->h_stage.p;
     if (!mapped) {                                   // (bs_pods_map: the caller marshalled the queue in place)
       std::memcpy(st + l.group, pods->group, (size_t)P * 4);
       std::memcpy(st + l.req, pods->req, (size_t)P * L * 8);
@@ -1602,28 +1545,13 @@ int bs_pods_load(bs_ctx* c, const bs_pods_soa* pods) {
   rc = derive_pods(c, false);
   if (rc) return rc;
   // no wait here: the batch that follows is ordered behind the upload on the same stream; only the staging
-  // buffer must not be touched again before the copy has left it (ensure_stage / bs_batch_read wait for that)
-  if (!c->ev_stage) HIPCHK(c, hipEventCreateWithFlags(&c->ev_stage, hipEventDisableTiming));
-  HIPCHK(c, hipEventRecord(c->ev_stage, c->stream));
-  c->stage_busy = true;
+  // buffer must not be touched again before the copy has left it (h_stage.reserve / bs_batch_read wait for that)
+  HIPCHK(c, c->h_stage.mark_busy(c->stream));
   c->have_pods = true;
   return maybe_analyse_epochs(c);
 }
 
 // ---- bs_pods_apply: the resident queue patched on the device (bs_queue.hpp) ----------------------------------------------
-static int ensure_dstage(bs_ctx* c, size_t bytes) {
-  // the previous apply may still be reading the blob.  No event per apply (a record costs the cycle a microsecond of host time):
-  // the flag is cleared whenever the host has seen something later on the stream complete (the batch's completion word, a
-  // stream wait); two applies without that in between wait for the stream here.
-  if (c->dstage_busy) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->dstage_busy = false; }
-  if (bytes <= c->h_dstage_cap) return BS_OK;
-  if (c->h_dstage) { (void)hipHostFree(c->h_dstage); c->h_dstage = nullptr; c->h_dstage_cap = 0; }
-  const size_t want = std::max<size_t>(bytes + bytes / 2, 64 << 10);
-  HIPCHK(c, hipHostMalloc(&c->h_dstage, want, hipHostMallocDefault));
-  c->h_dstage_cap = want;
-  return BS_OK;
-}
-
 static QueueDirs queue_dirs(const bs_ctx* c) {
   QueueDirs q{};
   q.slot_keep = c->slot_keep;
@@ -1639,7 +1567,7 @@ static QueueDirs queue_dirs(const bs_ctx* c) {
   q.pair_head = reinterpret_cast<unsigned long long*>(c->d_gstat.as<uint32_t>() + (((size_t)3 * c->G + 1) & ~(size_t)1));
   q.pair_next = c->d_pair_next.as<unsigned long long>();
   q.pcap = c->pair_cap;
-  q.overflow = c->h_info ? c->h_info + 13 : nullptr;
+  q.overflow = c->h_info.p ? c->h_info.p + 13 : nullptr;
   return q;
 }
 
@@ -1744,8 +1672,12 @@ int bs_pods_apply(bs_ctx* c, const bs_pods_delta* d) {
   const size_t i_cls = o; o = a16(o + (size_t)I * 4);
   const size_t i_owner = o; o = a16(o + (size_t)I * 8);
   const size_t i_flags = o; o = a16(o + (size_t)I);
-  if ((rc = ensure_dstage(c, o + 16))) return rc;
-  uint8_t* st = reinterpret_cast<uint8_t*>(c->h_dstage);
+  // the previous apply may still be reading the blob.  No event per apply (a record costs the cycle a microsecond of host time):
+  // h_dstage.busy is cleared whenever the host has seen something later on the stream complete (the batch's completion word, a
+  // stream wait); two applies without that in between wait for the stream here.
+  const size_t blob = o + 16;
+  HIPCHK(c, c->h_dstage.reserve(blob, std::max<size_t>(blob + blob / 2, 64 << 10)));
+  uint8_t* st = c->h_dstage.p;
   if (R) std::memcpy(st + o_rem, d->remove, (size_t)R * 4);
   if (I) {
     uint32_t* at = reinterpret_cast<uint32_t*>(st + o_at);
@@ -1823,19 +1755,19 @@ int bs_pods_apply(bs_ctx* c, const bs_pods_delta* d) {
     gp.on = 1;
     gp.C = (c->have_fit && c->have_nodes) ? c->C : 0u;
     gp.tag = c->info_tag;
-    gp.info = c->h_info;
+    gp.info = c->h_info.p;
     gp.matched = const_cast<uint32_t*>(grp.matched);
     gp.status_scheduled = const_cast<uint32_t*>(grp.status_scheduled);
     gp.flags = const_cast<uint8_t*>(grp.flags);
     gp.dp = c->pending_dp;
   }
   hipLaunchKernelGGL(k_pods_apply, dim3(gb + 1 + gp.on), dim3(kApplyBlock), 0, c->stream, old, old_pclass, old_ppair, nw, dd, c->G, L, g_new, g_next,
-                     derive ? queue_dirs(c) : QueueDirs{}, c->hash_keep, derive ? 1u : 0u, gb, c->kinfo_tag, c->h_info, grp, gp.on ? batch_dev(c) : BatchDev{}, gp,
+                     derive ? queue_dirs(c) : QueueDirs{}, c->hash_keep, derive ? 1u : 0u, gb, c->kinfo_tag, c->h_info.p, grp, gp.on ? batch_dev(c) : BatchDev{}, gp,
                      c->d_gcount.as<uint32_t>());
   LAUNCHCHK(c, BS_KERNEL_PREPASS);
   restore.armed = false;                                             // the launch is out: the new queue is the queue
   if (gp.on) c->groups_launch_pending = false;                       // (the group patch went with it)
-  c->dstage_busy = true;
+  HIPCHK(c, c->h_dstage.mark_busy(c->stream));
   c->cur_pack = np;
   c->owner_ready = false;
   c->rep_valid = false;                                              // the queue was compacted: pod indices of the derivation are history
@@ -2001,19 +1933,11 @@ static int ensure_hout(bs_ctx* c) {
   const uint32_t hs = std::min<uint32_t>(c->filter_slots_cap, 1024u);
   const size_t off_feas = align256(c->outpack_bytes), off_tag = off_feas + align256((size_t)hs * 4), need = off_tag + 256;
   const size_t need_rows = (size_t)(cdiv(c->N, 64) + 1) * hs * 8;
-  if (need > c->h_hout_cap) {
-    if (c->h_hout) (void)hipHostFree(c->h_hout);
-    c->h_hout = nullptr; c->h_hout_cap = 0;
-    HIPCHK(c, hipHostMalloc((void**)&c->h_hout, need, hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(c->h_hout, 0, need);
-    c->h_hout_cap = need;
+  if (need > c->h_hout.cap) {
+    HIPCHK(c, c->h_hout.reserve(need));
+    std::memset(c->h_hout.p, 0, need);
   }
-  if (need_rows > c->h_hrows_cap) {
-    if (c->h_hrows) (void)hipHostFree(c->h_hrows);
-    c->h_hrows = nullptr; c->h_hrows_cap = 0;
-    HIPCHK(c, hipHostMalloc((void**)&c->h_hrows, need_rows, hipHostMallocMapped | hipHostMallocCoherent));
-    c->h_hrows_cap = need_rows;
-  }
+  HIPCHK(c, c->h_hrows.reserve(need_rows));
   c->hstride = hs;
   c->off_hfeas = off_feas;
   c->off_htag = off_tag;
@@ -2030,7 +1954,7 @@ static int setup_host_out(bs_ctx* c, uint32_t stages, bool run_filter, BatchDev&
   if (rc) return rc;
   c->host_tag = c->host_tag == 0x7FFFFFFF ? 1 : c->host_tag + 1;
   prm.host_tag = c->host_tag;
-  uint8_t* h = c->h_hout;
+  uint8_t* h = c->h_hout.p;
   b.h_pf_code = h + c->off_pf_code;
   b.h_pf_first_k = reinterpret_cast<uint32_t*>(h + c->off_pf_first_k);
   b.h_pf_leader = reinterpret_cast<int32_t*>(h + c->off_pf_leader);
@@ -2041,7 +1965,7 @@ static int setup_host_out(bs_ctx* c, uint32_t stages, bool run_filter, BatchDev&
   b.h_ready = h + c->off_ready;
   b.h_feas = reinterpret_cast<uint32_t*>(h + c->off_hfeas);
   b.h_tag = reinterpret_cast<int32_t*>(h + c->off_htag);
-  b.h_rows = run_filter ? c->h_hrows : nullptr;
+  b.h_rows = run_filter ? c->h_hrows.p : nullptr;
   b.hstride = c->hstride;
   return BS_OK;
 }
@@ -2049,14 +1973,14 @@ static int setup_host_out(bs_ctx* c, uint32_t stages, bool run_filter, BatchDev&
 // BS_BATCH_FILTER_DENY | BS_BATCH_COMMIT, after the stream has been waited for: did the device gate this run's commit kernels off
 // (its flag word is non-zero: the run is not the fixed point, fd_resolve runs the batch again)?
 static bool fd_commit_gated(const bs_ctx* c) {
-  volatile const int32_t* hf = c->h_info + 14;
+  volatile const int32_t* hf = c->h_info.p + 14;
   return c->fd_on && (hf[0] || hf[1]);
 }
 // ... or because one of the batch's in-launch waits ran out (k_fast_commit reads the same word, h_info[12]): the batch will be answered with BS_ERR_RETRY
 // by whoever asks for its results (check_handover), so it leaves the group state and the carried leader as it found them — "run the batch again" holds
 // for a committing batch too
 static bool handover_commit_gated(const bs_ctx* c) {
-  return c->h_info && ((volatile const int32_t*)c->h_info)[12] != 0;
+  return c->h_info.p && ((volatile const int32_t*)c->h_info.p)[12] != 0;
 }
 
 // BS_BATCH_FILTER_DENY: the two launches behind a chain's last one (bs_fdeny.hpp).  tail: this chain left tally and completion
@@ -2139,7 +2063,7 @@ static int run_fast(bs_ctx* c, uint32_t stages) {
 
   // K is known on the host once its copy from the pod load / queue patch has landed — never waited for here; when it is, the
   // kernels need not fetch it in front of everything else
-  if (c->kinfo_pending && ((volatile int32_t*)c->h_info)[5] == c->kinfo_tag && (rc = resolve_pods(c))) return rc;
+  if (c->kinfo_pending && ((volatile int32_t*)c->h_info.p)[5] == c->kinfo_tag && (rc = resolve_pods(c))) return rc;
   prm.k_host = c->kinfo_pending ? 0u : c->h_K;
   const uint64_t hp1 = c->host_probe ? host_ns() : 0;
   // ---- launch A and the scan / Filter roles of launch B as ONE launch (k_fast_step_a; round 6: its class-slot form is the default), then k_fast_final
@@ -2185,9 +2109,9 @@ static int run_fast(bs_ctx* c, uint32_t stages) {
       }
       c->launches = whole ? 1 : 2;
       c->last_step_a = true;
-      if (c->test_timeout_after && --c->test_timeout_after == 0 && c->h_info) {      // test hook: what a block whose wait ran out does (bs_fast.hpp, kSpinBound)
+      if (c->test_timeout_after && --c->test_timeout_after == 0 && c->h_info.p) {      // test hook: what a block whose wait ran out does (bs_fast.hpp, kSpinBound)
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        ((volatile int32_t*)c->h_info)[12] = 1;
+        ((volatile int32_t*)c->h_info.p)[12] = 1;
       }
       if (prm.filter_deny && (rc = launch_filter_deny(c, pd, gr, nd, b, prm, true))) return rc;
       if (commit) {
@@ -2455,8 +2379,8 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
     const size_t g1 = std::max<uint32_t>(c->G, 1);
     if ((rc = reserve_filled(c, c->d_fd_event, g1 * 8, 0xFF)) || (rc = reserve_filled(c, c->d_fd_in, g1 * 4, 0xFF)) || (rc = reserve_filled(c, c->d_fd_flag, 16, 0))) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_fd_flag.p, 0, 4, c->stream));
-    ((volatile int32_t*)c->h_info)[14] = 0;
-    ((volatile int32_t*)c->h_info)[15] = 0;
+    ((volatile int32_t*)c->h_info.p)[14] = 0;
+    ((volatile int32_t*)c->h_info.p)[15] = 0;
   }
   const uint32_t P = c->P, G = c->G, N = c->N, C = c->C;
   // fit-class indices address fit rows and running-sum tables on the device: out of range = refuse the batch
@@ -2467,7 +2391,7 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
   // findMaxPG's answer for the patched groups: taken if it has landed; guessed (last cycle's table) if it has not and the state is a
   // steady one — the guess is checked when the results are first asked for (batch_settle)
   c->spec_active = false;
-  if (c->info_pending && ((volatile int32_t*)c->h_info)[3] != c->info_tag && !c->no_spec && c->steady_prev >= 0 && (uint32_t)c->steady_prev < 2 * c->C && c->n_uncaptured == 0 &&
+  if (c->info_pending && ((volatile int32_t*)c->h_info.p)[3] != c->info_tag && !c->no_spec && c->steady_prev >= 0 && (uint32_t)c->steady_prev < 2 * c->C && c->n_uncaptured == 0 &&
       c->n_nominres == 0 && !(stages & BS_BATCH_COMMIT) && c->cfg.enable_timing < 2 && !c->collect_stats && c->nranks == 1 && !c->reduce_external &&
       c->fd_iter == 0 && !c->groups_launch_pending && !c->ext_admit) {
     c->steady_table = c->steady_prev;
@@ -2772,8 +2696,8 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
 // The results of a run that is thrown away (a wrong guess, a superseded fixed-point iteration) take their hand-over error word with them:
 // the re-run reports its own.  The lesson is kept: separate launches from now on.
 static void discard_handover(bs_ctx* c) {
-  if (c->h_info && ((volatile int32_t*)c->h_info)[12]) {
-    ((volatile int32_t*)c->h_info)[12] = 0;
+  if (c->h_info.p && ((volatile int32_t*)c->h_info.p)[12]) {
+    ((volatile int32_t*)c->h_info.p)[12] = 0;
     c->no_fuse_final = 1;
   }
 }
@@ -2782,7 +2706,7 @@ static int fd_resolve(bs_ctx* c) {
   if (!c->fd_active) return BS_OK;
   c->fd_active = false;
   c->fd_unsynced = false;                            // (every caller has waited for the batch)
-  volatile int32_t* hf = c->h_info + 14;
+  volatile int32_t* hf = c->h_info.p + 14;
   if (!hf[0]) return BS_OK;
   int rc = BS_OK;
   bool settled = false;
@@ -2821,7 +2745,7 @@ static int fd_settle(bs_ctx* c) {
   if (!c->batch_since_pods) { c->fd_active = false; c->spec_active = false; return BS_OK; }      // the queue changed since: those results are history
   int rc;
   if (c->last_host_out) {
-    if ((rc = wait_host_tag(c, 0, c->host_tag, reinterpret_cast<const int32_t*>(c->h_hout + c->off_htag)))) return rc;
+    if ((rc = wait_host_tag(c, 0, c->host_tag, reinterpret_cast<const int32_t*>(c->h_hout.p + c->off_htag)))) return rc;
   } else {
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
@@ -2890,8 +2814,8 @@ int bs_batch_finish(bs_ctx* c) {
 
 // a final block of a fused launch gave up waiting for its producers: the batch's results are not to be trusted
 static int check_handover(bs_ctx* c) {
-  if (c->h_info && ((volatile int32_t*)c->h_info)[13]) {   // the insert wave of a queue patch ran out of ids (the accounting should make that impossible)
-    ((volatile int32_t*)c->h_info)[13] = 0;
+  if (c->h_info.p && ((volatile int32_t*)c->h_info.p)[13]) {   // the insert wave of a queue patch ran out of ids (the accounting should make that impossible)
+    ((volatile int32_t*)c->h_info.p)[13] = 0;
     c->pairs_ready = false;                            // classes, pairs and directories are derived again from the resident queue
     c->dirs_ready = false;
     c->rep_valid = false;
@@ -2902,8 +2826,8 @@ static int check_handover(bs_ctx* c) {
     c->last_error = "bs_pods_apply: class / pair id space overflowed on the device; the queue was re-derived, run the batch again";
     return rc2 ? rc2 : BS_ERR_RETRY;
   }
-  if (c->h_info && ((volatile int32_t*)c->h_info)[12]) {
-    ((volatile int32_t*)c->h_info)[12] = 0;
+  if (c->h_info.p && ((volatile int32_t*)c->h_info.p)[12]) {
+    ((volatile int32_t*)c->h_info.p)[12] = 0;
     c->no_fuse_final = 1;                              // from now on: separate launches
     c->batch_void = true;
     c->last_error = "in-launch hand-over timed out (producer blocks not resident): batch void, run it again (the context now uses separate launches)";
@@ -2922,7 +2846,7 @@ int bs_batch_sync(bs_ctx* c) {
   if (rc) return rc;
   if ((rc = fd_settle(c))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->dstage_busy = false;
+  c->h_dstage.busy = false;
   return check_handover(c);
 }
 
@@ -2978,11 +2902,11 @@ int bs_batch_read(bs_ctx* c, const bs_batch_out* out) {
   }
   // latency mode: the batch wrote its results into pinned host memory itself — poll the completion word, copy out
   if (c->last_host_out && c->batch_since_pods && !(P && out->fl_bitmap && W && filtered)) {
-    rc = wait_host_tag(c, 0, c->host_tag, reinterpret_cast<const int32_t*>(c->h_hout + c->off_htag));
+    rc = wait_host_tag(c, 0, c->host_tag, reinterpret_cast<const int32_t*>(c->h_hout.p + c->off_htag));
     if (rc) return rc;
     if ((rc = check_handover(c))) return rc;
-    c->dstage_busy = false;                            // (the batch ran behind every earlier apply)
-    const uint8_t* st = c->h_hout;
+    c->h_dstage.busy = false;                            // (the batch ran behind every earlier apply)
+    const uint8_t* st = c->h_hout.p;
     if (want_pod) {
       if (out->pf_code) std::memcpy(out->pf_code, st + c->off_pf_code, P);
       if (out->pf_first_k) std::memcpy(out->pf_first_k, st + c->off_pf_first_k, (size_t)P * 4);
@@ -2998,7 +2922,7 @@ int bs_batch_read(bs_ctx* c, const bs_batch_out* out) {
     if ((want_rows || want_rfeas) && nrows <= c->hstride) {
       if (want_rfeas) std::memcpy(out->fl_rows_feasible, st + c->off_hfeas, (size_t)nrows * 4);
       if (want_rows)
-        for (uint32_t w = 0; w < W; ++w) std::memcpy(out->fl_rows + (size_t)w * out->fl_rows_cap, c->h_hrows + (size_t)w * c->hstride, (size_t)nrows * 8);
+        for (uint32_t w = 0; w < W; ++w) std::memcpy(out->fl_rows + (size_t)w * out->fl_rows_cap, c->h_hrows.p + (size_t)w * c->hstride, (size_t)nrows * 8);
       return BS_OK;
     }
     if (!(want_rows || want_rfeas)) return BS_OK;
@@ -3012,21 +2936,16 @@ int bs_batch_read(bs_ctx* c, const bs_batch_out* out) {
   const size_t off_rows = off_xadmit + align256((size_t)G * 4);
   const bool any_rows = want_rows || want_rfeas;
   const size_t rows_h = any_rows ? (size_t)W + 1 : 0, rows_bytes = rows_h * nrows * 8;
-  if (off_rows + rows_bytes + 256 > c->h_rstage_cap) {
-    if (c->h_rstage) (void)hipHostFree(c->h_rstage);
-    c->h_rstage = nullptr; c->h_rstage_cap = 0;
-    HIPCHK(c, hipHostMalloc(&c->h_rstage, off_rows + rows_bytes + 256, hipHostMallocDefault));
-    c->h_rstage_cap = off_rows + rows_bytes + 256;
-  }
-  uint8_t* st = reinterpret_cast<uint8_t*>(c->h_rstage);
+  HIPCHK(c, c->h_rstage.reserve(off_rows + rows_bytes + 256));
+  uint8_t* st = c->h_rstage.p;
   if (want_pod || want_grp) HIPCHK(c, hipMemcpyAsync(st, c->d_outpack.p, pack_bytes, hipMemcpyDeviceToHost, c->stream));
   if (want_grp && ext && out->group_admit) HIPCHK(c, hipMemcpyAsync(st + off_xadmit, c->ext_admit, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
   if (any_rows)
     HIPCHK(c, hipMemcpy2DAsync(st + off_rows, (size_t)nrows * 8, c->d_fu_bitmap.p, (size_t)c->filter_slots_cap * 8, (size_t)nrows * 8, rows_h,
                                hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->stage_busy = false;                             // (the stream is idle: the pod upload has left its buffer too)
-  c->dstage_busy = false;
+  c->h_stage.busy = false;                             // (the stream is idle: the pod upload has left its buffer too)
+  c->h_dstage.busy = false;
   if ((rc = check_handover(c))) return rc;
   if (want_pod) {
     if (out->pf_code) std::memcpy(out->pf_code, st + c->off_pf_code, P);
@@ -3065,10 +2984,10 @@ int bs_batch_map(bs_ctx* c, bs_batch_view* v) {
   const bool filtered = c->last_stages & BS_STAGE_FILTER;
   uint32_t nrows = 0;
   if (filtered && (rc = filter_rows_of(c, &nrows))) return rc;
-  if ((rc = wait_host_tag(c, 0, c->host_tag, reinterpret_cast<const int32_t*>(c->h_hout + c->off_htag)))) return rc;
+  if ((rc = wait_host_tag(c, 0, c->host_tag, reinterpret_cast<const int32_t*>(c->h_hout.p + c->off_htag)))) return rc;
   if ((rc = check_handover(c))) return rc;
-  c->dstage_busy = false;                              // (the batch ran behind every earlier apply)
-  const uint8_t* st = c->h_hout;
+  c->h_dstage.busy = false;                              // (the batch ran behind every earlier apply)
+  const uint8_t* st = c->h_hout.p;
   std::memset(v, 0, sizeof(*v));
   v->p = P; v->g = G; v->words = W;
   v->pf_code = st + c->off_pf_code;
@@ -3084,7 +3003,7 @@ int bs_batch_map(bs_ctx* c, bs_batch_view* v) {
   v->fl_rows_n = nrows;
   v->fl_rows_stride = c->hstride;
   if (filtered && nrows && nrows <= c->hstride) {
-    v->fl_rows = c->h_hrows;
+    v->fl_rows = c->h_hrows.p;
     v->fl_rows_feasible = reinterpret_cast<const uint32_t*>(st + c->off_hfeas);
   }
   return BS_OK;
@@ -3408,26 +3327,17 @@ int bs_nodes_assume(bs_ctx* c, const bs_node_request* reqs, uint32_t count) {
   }
   static_assert(sizeof(bs_node_request) == sizeof(NodeRequest), "node request layout");
   const size_t bytes = (size_t)count * sizeof(bs_node_request);
-  if (c->nstage_busy) { HIPCHK(c, hipEventSynchronize(c->ev_nstage)); c->nstage_busy = false; }
-  if (bytes > c->h_nstage_cap) {
-    if (c->h_nstage) (void)hipHostFree(c->h_nstage);
-    c->h_nstage = nullptr; c->h_nstage_cap = 0;
-    const size_t want = std::max<size_t>(2 * bytes, 16 << 10);
-    HIPCHK(c, hipHostMalloc(&c->h_nstage, want, hipHostMallocDefault));
-    c->h_nstage_cap = want;
-  }
-  std::memcpy(c->h_nstage, reqs, bytes);
+  HIPCHK(c, c->h_nstage.reserve(bytes, std::max<size_t>(2 * bytes, 16 << 10)));
+  std::memcpy(c->h_nstage.p, reqs, bytes);
   for (uint32_t d = 0; d < count; ++d) {                          // the host mirror a later bs_nodes_apply starts from
     for (uint32_t j = 0; j < L; ++j) c->h_nreq[(size_t)j * N + reqs[d].index] = reqs[d].requested[j];
     c->h_rpres[reqs[d].index] = reqs[d].requested_present;
   }
-  hipLaunchKernelGGL(k_nodes_assume, dim3(cdiv(count, 256)), dim3(256), 0, c->stream, reinterpret_cast<const NodeRequest*>(c->h_nstage), count, L, c->Ncap,
+  hipLaunchKernelGGL(k_nodes_assume, dim3(cdiv(count, 256)), dim3(256), 0, c->stream, reinterpret_cast<const NodeRequest*>(c->h_nstage.p), count, L, c->Ncap,
                      c->d_alloc.as<int64_t>(), c->d_nreq.as<int64_t>(), c->d_rpres.as<uint32_t>(), c->d_nflags.as<uint8_t>(), c->d_left4.as<int64_t>(),
                      c->d_lglob.as<int64_t>());
   LAUNCHCHK(c, BS_KERNEL_PREPASS);
-  if (!c->ev_nstage) HIPCHK(c, hipEventCreateWithFlags(&c->ev_nstage, hipEventDisableTiming));
-  HIPCHK(c, hipEventRecord(c->ev_nstage, c->stream));
-  c->nstage_busy = true;
+  HIPCHK(c, c->h_nstage.mark_busy(c->stream));
   c->bitmap_valid = false;
   return BS_OK;
 }
@@ -3871,7 +3781,6 @@ int bs_batch_stats_get(bs_ctx* c, bs_batch_stats* out) {
 // gang-aware preemption (bs_preempt.hpp): the resident bound-pod table and the batched victim search
 // -------------------------------------------------------------------------------------------------
 // the bound table's one allocation for N nodes and B entries (columns at 256-byte offsets; breq lane stride max(B, 1)); returns its size
-struct BoundLayout { size_t boff, prio, start, group, id, req, pres, pdb, nviol; };
 static size_t bound_layout(uint32_t L, uint32_t N, uint32_t B, BoundLayout& b) {
   const size_t nB = std::max<uint32_t>(B, 1);
   size_t o = 0;
@@ -3885,10 +3794,6 @@ static size_t bound_layout(uint32_t L, uint32_t N, uint32_t B, BoundLayout& b) {
   b.pdb = o; o = align256(o + nB);           // PDB-violating bit of each entry (bs_bound_pdb_set)
   b.nviol = o; o = align256(o + std::max<size_t>(N, 1) * 4);   // entries with the bit per node
   return o;
-}
-static void bound_layout_set(bs_ctx* c, const BoundLayout& b) {
-  c->off_boff = b.boff; c->off_bprio = b.prio; c->off_bstart = b.start; c->off_bgroup = b.group; c->off_bid = b.id; c->off_breq = b.req;
-  c->off_bpres = b.pres; c->off_bpdb = b.pdb; c->off_bnviol = b.nviol;
 }
 
 int bs_bound_load(bs_ctx* c, const bs_bound_soa* bd) {
@@ -3923,15 +3828,15 @@ int bs_bound_load(bs_ctx* c, const bs_bound_soa* bd) {
   const size_t nB = std::max<uint32_t>(B, 1);
   BoundLayout lay;
   const size_t o = bound_layout(L, N, B, lay);
-  bound_layout_set(c, lay);
+  c->blay = lay;
   std::vector<uint8_t> h(o, 0);
-  std::memcpy(h.data() + c->off_boff, cnt.data(), ((size_t)N + 1) * 4);
-  int32_t* prio = reinterpret_cast<int32_t*>(h.data() + c->off_bprio);
-  int64_t* start = reinterpret_cast<int64_t*>(h.data() + c->off_bstart);
-  int32_t* grp = reinterpret_cast<int32_t*>(h.data() + c->off_bgroup);
-  uint32_t* id = reinterpret_cast<uint32_t*>(h.data() + c->off_bid);
-  int64_t* req = reinterpret_cast<int64_t*>(h.data() + c->off_breq);
-  uint32_t* pres = reinterpret_cast<uint32_t*>(h.data() + c->off_bpres);
+  std::memcpy(h.data() + c->blay.boff, cnt.data(), ((size_t)N + 1) * 4);
+  int32_t* prio = reinterpret_cast<int32_t*>(h.data() + c->blay.prio);
+  int64_t* start = reinterpret_cast<int64_t*>(h.data() + c->blay.start);
+  int32_t* grp = reinterpret_cast<int32_t*>(h.data() + c->blay.group);
+  uint32_t* id = reinterpret_cast<uint32_t*>(h.data() + c->blay.id);
+  int64_t* req = reinterpret_cast<int64_t*>(h.data() + c->blay.req);
+  uint32_t* pres = reinterpret_cast<uint32_t*>(h.data() + c->blay.pres);
   const uint32_t smask = (uint32_t)((1ull << (L - BS_FIXED_LANES)) - 1ull);
   for (uint32_t r = 0; r < B; ++r) {
     const uint32_t i = order[r];
@@ -3974,8 +3879,8 @@ int bs_bound_pdb_set(bs_ctx* c, uint32_t b, const uint8_t* violating) {
   std::vector<uint32_t> nviol(nN, 0);
   if (violating && B) {
     std::vector<uint32_t> boff((size_t)N + 1), id(B);
-    HIPCHK(c, hipMemcpyAsync(boff.data(), bb + c->off_boff, ((size_t)N + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(id.data(), bb + c->off_bid, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(boff.data(), bb + c->blay.boff, ((size_t)N + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(id.data(), bb + c->blay.id, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (uint32_t k = 0; k < N; ++k)
       for (uint32_t j = boff[k]; j < boff[k + 1] && j < B; ++j) {
@@ -3983,8 +3888,8 @@ int bs_bound_pdb_set(bs_ctx* c, uint32_t b, const uint8_t* violating) {
         nviol[k] += bits[j];
       }
   }
-  HIPCHK(c, hipMemcpyAsync(bb + c->off_bpdb, bits.data(), nB, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(bb + c->off_bnviol, nviol.data(), nN * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(bb + c->blay.pdb, bits.data(), nB, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(bb + c->blay.nviol, nviol.data(), nN * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));             // (local buffers)
   return BS_OK;
 }
@@ -4068,14 +3973,14 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   HIPCHK(c, hipMemcpyAsync(base, in.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
   const uint8_t* bb = c->d_bound.as<uint8_t>();
   PreemptDev pe{};
-  pe.boff = reinterpret_cast<const uint32_t*>(bb + c->off_boff);
-  pe.bprio = reinterpret_cast<const int32_t*>(bb + c->off_bprio);
-  pe.bstart = reinterpret_cast<const int64_t*>(bb + c->off_bstart);
-  pe.bgroup = reinterpret_cast<const int32_t*>(bb + c->off_bgroup);
-  pe.bid = reinterpret_cast<const uint32_t*>(bb + c->off_bid);
-  pe.breq = reinterpret_cast<const int64_t*>(bb + c->off_breq);
-  pe.bpdb = bb + c->off_bpdb;
-  pe.bnviol = reinterpret_cast<const uint32_t*>(bb + c->off_bnviol);
+  pe.boff = reinterpret_cast<const uint32_t*>(bb + c->blay.boff);
+  pe.bprio = reinterpret_cast<const int32_t*>(bb + c->blay.prio);
+  pe.bstart = reinterpret_cast<const int64_t*>(bb + c->blay.start);
+  pe.bgroup = reinterpret_cast<const int32_t*>(bb + c->blay.group);
+  pe.bid = reinterpret_cast<const uint32_t*>(bb + c->blay.id);
+  pe.breq = reinterpret_cast<const int64_t*>(bb + c->blay.req);
+  pe.bpdb = bb + c->blay.pdb;
+  pe.bnviol = reinterpret_cast<const uint32_t*>(bb + c->blay.nviol);
   pe.bstride = std::max<uint32_t>(c->bound_b, 1);
   pe.q = count;
   pe.nchunks = nchunks;
@@ -4228,15 +4133,15 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
   HIPCHK(c, hipMemsetAsync(base + o_work, 0, work_bytes, c->stream));
   const uint8_t* bb = c->d_bound.as<uint8_t>();
   CommitDev pe{};
-  pe.boff = reinterpret_cast<const uint32_t*>(bb + c->off_boff);
-  pe.bprio = reinterpret_cast<const int32_t*>(bb + c->off_bprio);
-  pe.bstart = reinterpret_cast<const int64_t*>(bb + c->off_bstart);
-  pe.bgroup = reinterpret_cast<const int32_t*>(bb + c->off_bgroup);
-  pe.bid = reinterpret_cast<const uint32_t*>(bb + c->off_bid);
-  pe.breq = reinterpret_cast<const int64_t*>(bb + c->off_breq);
-  pe.bpres = reinterpret_cast<const uint32_t*>(bb + c->off_bpres);
-  pe.bpdb = bb + c->off_bpdb;
-  pe.bnviol = reinterpret_cast<const uint32_t*>(bb + c->off_bnviol);
+  pe.boff = reinterpret_cast<const uint32_t*>(bb + c->blay.boff);
+  pe.bprio = reinterpret_cast<const int32_t*>(bb + c->blay.prio);
+  pe.bstart = reinterpret_cast<const int64_t*>(bb + c->blay.start);
+  pe.bgroup = reinterpret_cast<const int32_t*>(bb + c->blay.group);
+  pe.bid = reinterpret_cast<const uint32_t*>(bb + c->blay.id);
+  pe.breq = reinterpret_cast<const int64_t*>(bb + c->blay.req);
+  pe.bpres = reinterpret_cast<const uint32_t*>(bb + c->blay.pres);
+  pe.bpdb = bb + c->blay.pdb;
+  pe.bnviol = reinterpret_cast<const uint32_t*>(bb + c->blay.nviol);
   pe.bstride = (uint32_t)nB;
   pe.q = count;
   pe.nchunks = nchunks;
@@ -4318,7 +4223,7 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
       HIPCHK(c, hipStreamSynchronize(c->stream));
       std::swap(c->d_bound.p, c->d_bound2.p);
       std::swap(c->d_bound.cap, c->d_bound2.cap);
-      bound_layout_set(c, lay);
+      c->blay = lay;
       c->bound_b = B2;
     }
   }
@@ -4353,8 +4258,8 @@ int bs_bound_read(bs_ctx* c, uint32_t* id_out, uint32_t* node_out) {
   std::vector<uint32_t> boff((size_t)N + 1);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint8_t* bb = c->d_bound.as<uint8_t>();
-  HIPCHK(c, hipMemcpy(boff.data(), bb + c->off_boff, ((size_t)N + 1) * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(id_out, bb + c->off_bid, (size_t)B * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(boff.data(), bb + c->blay.boff, ((size_t)N + 1) * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(id_out, bb + c->blay.id, (size_t)B * 4, hipMemcpyDeviceToHost));
   for (uint32_t k = 0; k < N; ++k)
     for (uint32_t j = boff[k]; j < boff[k + 1] && j < B; ++j) node_out[j] = k;
   return BS_OK;
@@ -4465,14 +4370,14 @@ int bs_bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t* first_id_out) {
   const uint8_t* bb = c->d_bound.as<uint8_t>();
   uint8_t* b2 = c->d_bound2.as<uint8_t>();
   BoundApplyDev a{};
-  a.boff = reinterpret_cast<const uint32_t*>(bb + c->off_boff);
-  a.bprio = reinterpret_cast<const int32_t*>(bb + c->off_bprio);
-  a.bstart = reinterpret_cast<const int64_t*>(bb + c->off_bstart);
-  a.bgroup = reinterpret_cast<const int32_t*>(bb + c->off_bgroup);
-  a.breq = reinterpret_cast<const int64_t*>(bb + c->off_breq);
-  a.bid = reinterpret_cast<const uint32_t*>(bb + c->off_bid);
-  a.bpres = reinterpret_cast<const uint32_t*>(bb + c->off_bpres);
-  a.bpdb = bb + c->off_bpdb;
+  a.boff = reinterpret_cast<const uint32_t*>(bb + c->blay.boff);
+  a.bprio = reinterpret_cast<const int32_t*>(bb + c->blay.prio);
+  a.bstart = reinterpret_cast<const int64_t*>(bb + c->blay.start);
+  a.bgroup = reinterpret_cast<const int32_t*>(bb + c->blay.group);
+  a.breq = reinterpret_cast<const int64_t*>(bb + c->blay.req);
+  a.bid = reinterpret_cast<const uint32_t*>(bb + c->blay.id);
+  a.bpres = reinterpret_cast<const uint32_t*>(bb + c->blay.pres);
+  a.bpdb = bb + c->blay.pdb;
   a.bstride = std::max<uint32_t>(B, 1);
   a.b = B; a.n = N; a.ids = ids;
   a.n_remove = R; a.n_insert = I;
@@ -4516,7 +4421,7 @@ int bs_bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t* first_id_out) {
   if (err & kBaErrFull) { c->last_error = "bs_bound_apply: more than BS_BOUND_MAX_PER_NODE bound pods on one node"; return BS_ERR_CAPACITY; }
   std::swap(c->d_bound.p, c->d_bound2.p);
   std::swap(c->d_bound.cap, c->d_bound2.cap);
-  bound_layout_set(c, lay);
+  c->blay = lay;
   c->bound_b = B2;
   c->bound_ids = ids + I;
   c->bound_max_group = gmax;
@@ -4540,12 +4445,12 @@ int bs_bound_dump(bs_ctx* c, int32_t* priority, int64_t* start_ns, int32_t* grou
   if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint8_t* bb = c->d_bound.as<uint8_t>();
-  if (priority) HIPCHK(c, hipMemcpy(priority, bb + c->off_bprio, B * 4, hipMemcpyDeviceToHost));
-  if (start_ns) HIPCHK(c, hipMemcpy(start_ns, bb + c->off_bstart, B * 8, hipMemcpyDeviceToHost));
-  if (group) HIPCHK(c, hipMemcpy(group, bb + c->off_bgroup, B * 4, hipMemcpyDeviceToHost));
-  if (req) HIPCHK(c, hipMemcpy(req, bb + c->off_breq, B * c->L * 8, hipMemcpyDeviceToHost));   // the lane stride is the entry count
-  if (req_present) HIPCHK(c, hipMemcpy(req_present, bb + c->off_bpres, B * 4, hipMemcpyDeviceToHost));
-  if (pdb) HIPCHK(c, hipMemcpy(pdb, bb + c->off_bpdb, B, hipMemcpyDeviceToHost));
+  if (priority) HIPCHK(c, hipMemcpy(priority, bb + c->blay.prio, B * 4, hipMemcpyDeviceToHost));
+  if (start_ns) HIPCHK(c, hipMemcpy(start_ns, bb + c->blay.start, B * 8, hipMemcpyDeviceToHost));
+  if (group) HIPCHK(c, hipMemcpy(group, bb + c->blay.group, B * 4, hipMemcpyDeviceToHost));
+  if (req) HIPCHK(c, hipMemcpy(req, bb + c->blay.req, B * c->L * 8, hipMemcpyDeviceToHost));   // the lane stride is the entry count
+  if (req_present) HIPCHK(c, hipMemcpy(req_present, bb + c->blay.pres, B * 4, hipMemcpyDeviceToHost));
+  if (pdb) HIPCHK(c, hipMemcpy(pdb, bb + c->blay.pdb, B, hipMemcpyDeviceToHost));
   return BS_OK;
 }
 
