@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "bs_preempt_commit", "bs_bound_read", "bs_preempt_commit_flat",
     "bs_bound_pdb_set", "bs_preempt_pdb_read",
     "bs_bound_apply", "bs_bound_apply_flat", "bs_bound_ids", "bs_bound_dump",
+    "bs_bound_nodes_apply",
 ]
 
 # bsh_phase codes (include/bsched_host.h) of the phases whose gangs PreemptRemovePod protects: Running and Scheduled (core.go:235-238)
@@ -174,6 +175,7 @@ def load_library(path: str | None = None):
     L.bs_bound_apply.argtypes = [vp, P(soa.BoundDeltaStruct), P(u32)]
     L.bs_bound_apply_flat.argtypes = [vp, u32, P(u32), u32, P(u32), P(i32), P(C.c_int64), P(i32), P(C.c_int64), P(u32), P(u8), P(u32)]
     L.bs_bound_ids.argtypes = [vp, P(u32)]
+    L.bs_bound_nodes_apply.argtypes = [vp, u32, P(u32), P(u32), u32, P(u32), P(u32)]
     L.bs_bound_dump.argtypes = [vp, P(i32), P(C.c_int64), P(i32), P(C.c_int64), P(u32), P(u8)]
     L.bs_preempt_pdb_read.argtypes = [vp, u32, P(u32)]
     L.bs_preempt_commit_flat.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), u32, u32, P(i32), P(u32), P(u32), P(u32), P(i32), P(C.c_int64),
@@ -622,6 +624,19 @@ class Context:
             self._chk(self._lib.bs_bound_apply(self._h, C.byref(d), C.byref(first)), "bs_bound_apply")
         self._bound_ids = int(first.value) + ni
         return int(first.value)
+
+    def bound_nodes_apply(self, kind, index, dropped_cap: int = 0):
+        """bs_bound_nodes_apply: the resident bound table follows the node-list surgery of the apply_node_deltas call(s) before it — kind
+        and index are those deltas' fields, in order.  Returns (n_dropped, ids): the true number of entries that left with their nodes and
+        the first min(n_dropped, dropped_cap) of their ids in the old table's order."""
+        kv = np.ascontiguousarray(np.asarray(kind, np.uint32).reshape(-1))
+        iv = np.ascontiguousarray(np.asarray(index, np.uint32).reshape(-1))
+        assert kv.size == iv.size
+        ids = np.zeros(max(int(dropped_cap), 1), np.uint32)
+        nd = C.c_uint32()
+        self._chk(self._lib.bs_bound_nodes_apply(self._h, int(kv.size), _u32p(kv) if kv.size else None, _u32p(iv) if iv.size else None,
+                                                 int(dropped_cap), _u32p(ids) if dropped_cap else None, C.byref(nd)), "bs_bound_nodes_apply")
+        return int(nd.value), ids[: min(int(nd.value), int(dropped_cap))].copy()
 
     def bound_dump(self) -> dict:
         """bs_bound_dump: the live table's columns as stored, in read_bound's order: priority, start_ns, group, req [L, count],

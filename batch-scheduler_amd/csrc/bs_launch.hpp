@@ -52,4 +52,9 @@ void launch_preempt_apply(hipStream_t stream, uint32_t S, const NodesDev& nd, co
 struct BoundApplyDev;
 void launch_bound_apply(hipStream_t stream, uint32_t S, const BoundApplyDev& a, const CompactDev& nw);
 
+// the bound table's remap after node-list surgery (tu_preempt.hip, bs_bound_nodes.hpp): k_bn_len<S>, k_bn_scan1<S> + k_bn_scan2<S> (the new
+// CSR and the dropped ids' offsets, a.nblk blocks each), k_bn_move<S> (one wave per new node, and per removed node when ids are asked for)
+struct BoundNodesDev;
+void launch_bound_nodes(hipStream_t stream, uint32_t S, const BoundNodesDev& a);
+
 }  // namespace bs

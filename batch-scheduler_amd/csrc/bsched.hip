@@ -33,6 +33,8 @@
 #include "bs_preempt_commit.hpp"
 #include "bs_preempt_geom.hpp"
 #include "bs_bound_apply.hpp"
+#include "bs_bound_nodes.hpp"
+#include "bs_bound_nodes_replay.hpp"
 #ifdef BS_UNITY   // one translation unit (the probe builds: g_probe / g_seq_scan_ph are per translation unit)
 #include "tu_fast.hip"
 #include "tu_seq.hip"
@@ -88,9 +90,6 @@ PodLayout pod_layout(uint32_t P, uint32_t L) {
   l.p = P;
   return l;
 }
-
-// the bound-pod table's columns in its one allocation (bound_layout)
-struct BoundLayout { size_t boff, prio, start, group, id, req, pres, pdb, nviol; };
 
 }  // namespace
 
@@ -3780,21 +3779,7 @@ int bs_batch_stats_get(bs_ctx* c, bs_batch_stats* out) {
 // -------------------------------------------------------------------------------------------------
 // gang-aware preemption (bs_preempt.hpp): the resident bound-pod table and the batched victim search
 // -------------------------------------------------------------------------------------------------
-// the bound table's one allocation for N nodes and B entries (columns at 256-byte offsets; breq lane stride max(B, 1)); returns its size
-static size_t bound_layout(uint32_t L, uint32_t N, uint32_t B, BoundLayout& b) {
-  const size_t nB = std::max<uint32_t>(B, 1);
-  size_t o = 0;
-  b.boff = o; o = align256(o + ((size_t)N + 1) * 4);
-  b.prio = o; o = align256(o + nB * 4);
-  b.start = o; o = align256(o + nB * 8);
-  b.group = o; o = align256(o + nB * 4);
-  b.id = o; o = align256(o + nB * 4);
-  b.req = o; o = align256(o + nB * L * 8);
-  b.pres = o; o = align256(o + nB * 4);      // scalar keys of each entry (bs_preempt_commit sets them on the node)
-  b.pdb = o; o = align256(o + nB);           // PDB-violating bit of each entry (bs_bound_pdb_set)
-  b.nviol = o; o = align256(o + std::max<size_t>(N, 1) * 4);   // entries with the bit per node
-  return o;
-}
+// (the bound table's one allocation: BoundLayout / bound_layout, bs_bound_nodes.hpp — k_bn_move lays the new table out with the same function)
 
 int bs_bound_load(bs_ctx* c, const bs_bound_soa* bd) {
   if (!c || !bd) return BS_ERR_INVALID;
@@ -4434,6 +4419,92 @@ int bs_bound_apply_flat(bs_ctx* c, uint32_t n_remove, const uint32_t* remove, ui
                         uint32_t* first_id_out) {
   const bs_bound_delta d{n_remove, remove, n_insert, node, priority, start_ns, group, req, req_present, pdb_violating};
   return bs_bound_apply(c, &d, first_id_out);
+}
+
+// -------------------------------------------------------------------------------------------------
+// the bound table follows node-list surgery (bs_bound_nodes.hpp): O(count) on the host, one pass over the table on the device
+// -------------------------------------------------------------------------------------------------
+int bs_bound_nodes_apply(bs_ctx* c, uint32_t count, const uint32_t* kind, const uint32_t* index, uint32_t dropped_cap, uint32_t* dropped_ids,
+                         uint32_t* n_dropped_out) {
+  if (!c) return BS_ERR_INVALID;
+  if (!c->have_bound) { c->last_error = "bs_bound_nodes_apply before bs_bound_load"; return BS_ERR_STATE; }
+  if (c->nranks > 1 || c->reduce_external) { c->last_error = "bs_bound_nodes_apply is single-rank only"; return BS_ERR_STATE; }
+  if ((count && (!kind || !index)) || (dropped_cap && !dropped_ids)) return BS_ERR_INVALID;
+  const uint32_t N0 = c->bound_n, L = c->L, B = c->bound_b;
+  NodeReplay rp;
+  if (bound_nodes_replay(N0, count, kind, index, rp)) {
+    c->last_error = "bs_bound_nodes_apply: a kind outside UPDATE / APPEND / REMOVE, or an index at or beyond the node count at its point of the replay";
+    return BS_ERR_INVALID;
+  }
+  if (rp.n_new != c->N) { c->last_error = "bs_bound_nodes_apply: the replay does not end at the node count: not the list bs_nodes_apply got"; return BS_ERR_STATE; }
+  const uint32_t N1 = rp.n_new, R = (uint32_t)rp.removed.size();
+  if (R == 0 && rp.appended == 0) {                        // updates, or appends removed again: the table stays as it is
+    if (n_dropped_out) *n_dropped_out = 0;
+    return BS_OK;
+  }
+  int rc = use_device(c);
+  if (rc) return rc;
+  // the removed list (one H2D), then the scratch of this call
+  const uint32_t nblk = std::max<uint32_t>(1u, cdiv(std::max(N1, R), 1024u)), ncap = std::min(dropped_cap, B);
+  const size_t nR = R, nN = N1;
+  size_t o = 0;
+  const size_t o_rem = o; o = align256(o + nR * 4);
+  const size_t o_len = o; o = align256(o + nN * 4);
+  const size_t o_src = o; o = align256(o + nN * 4);
+  const size_t o_dlen = o; o = align256(o + nR * 4);
+  const size_t o_doff = o; o = align256(o + (nR + 1) * 4);
+  const size_t o_bsum = o; o = align256(o + (size_t)2 * nblk * 4);
+  const size_t o_pair = o; o = align256(o + 8);
+  const size_t o_drop = o; o = align256(o + (size_t)ncap * 4);
+  if (o > c->d_pre.cap) HIPCHK(c, c->d_pre.reserve(o + o / 4));
+  // the new table holds at most the old entries: sized for them, laid out by k_bn_move for the count the scan finds (boff: N1 + 1 words,
+  // nviol: N1 words — appends grow both)
+  BoundLayout lay{};
+  const size_t table_bytes = bound_layout(L, N1, B, lay);
+  if (table_bytes > c->d_bound2.cap) HIPCHK(c, c->d_bound2.reserve(table_bytes + table_bytes / 4));
+  uint8_t* base = c->d_pre.as<uint8_t>();
+  if (R) HIPCHK(c, hipMemcpyAsync(base + o_rem, rp.removed.data(), nR * 4, hipMemcpyHostToDevice, c->stream));
+  const uint8_t* bb = c->d_bound.as<uint8_t>();
+  BoundNodesDev a{};
+  a.boff = reinterpret_cast<const uint32_t*>(bb + c->blay.boff);
+  a.bprio = reinterpret_cast<const int32_t*>(bb + c->blay.prio);
+  a.bstart = reinterpret_cast<const int64_t*>(bb + c->blay.start);
+  a.bgroup = reinterpret_cast<const int32_t*>(bb + c->blay.group);
+  a.breq = reinterpret_cast<const int64_t*>(bb + c->blay.req);
+  a.bid = reinterpret_cast<const uint32_t*>(bb + c->blay.id);
+  a.bpres = reinterpret_cast<const uint32_t*>(bb + c->blay.pres);
+  a.bpdb = bb + c->blay.pdb;
+  a.bstride = std::max<uint32_t>(B, 1);
+  a.n0 = N0; a.n1 = N1;
+  a.nrem = R; a.old_left = N0 - R;
+  a.rem = reinterpret_cast<const uint32_t*>(base + o_rem);
+  a.nbase = c->d_bound2.as<uint8_t>();
+  a.nboff = reinterpret_cast<uint32_t*>(a.nbase + lay.boff);
+  a.len = reinterpret_cast<uint32_t*>(base + o_len);
+  a.src = reinterpret_cast<uint32_t*>(base + o_src);
+  a.dlen = reinterpret_cast<uint32_t*>(base + o_dlen);
+  a.doff = reinterpret_cast<uint32_t*>(base + o_doff);
+  a.bsum = reinterpret_cast<uint32_t*>(base + o_bsum);
+  a.nblk = nblk;
+  a.pair = reinterpret_cast<uint32_t*>(base + o_pair);
+  a.dropped = reinterpret_cast<uint32_t*>(base + o_drop);
+  a.dropped_cap = ncap;
+  launch_bound_nodes(c->stream, c->S, a);
+  LAUNCHCHK(c, BS_KERNEL_PREPASS);
+  uint32_t pair[2] = {0, 0};                               // {new entry count, dropped count}: read before the swap
+  HIPCHK(c, hipMemcpyAsync(pair, a.pair, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));              // (rp.removed and pair are local buffers)
+  if ((uint64_t)pair[0] + pair[1] != B) { c->last_error = "bs_bound_nodes_apply: the resident table's offsets do not add up"; return BS_ERR_HIP; }
+  const uint32_t nd = std::min(pair[1], ncap);
+  if (nd) HIPCHK(c, hipMemcpy(dropped_ids, a.dropped, (size_t)nd * 4, hipMemcpyDeviceToHost));
+  std::swap(c->d_bound.p, c->d_bound2.p);
+  std::swap(c->d_bound.cap, c->d_bound2.cap);
+  bound_layout(L, N1, pair[0], lay);                       // as k_bn_move laid it out
+  c->blay = lay;
+  c->bound_b = pair[0];
+  c->bound_n = N1;
+  if (n_dropped_out) *n_dropped_out = pair[1];
+  return BS_OK;
 }
 
 int bs_bound_dump(bs_ctx* c, int32_t* priority, int64_t* start_ns, int32_t* group, int64_t* req, uint32_t* req_present, uint8_t* pdb) {

@@ -1,12 +1,14 @@
 // tu_preempt.hip — translation unit of the preemption victim search (bs_preempt.hpp: k_preempt_scan / k_preempt_pick), of the
-// sequential plans (bs_preempt_commit.hpp: k_pc_*) and of the bound table's patch (bs_bound_apply.hpp: k_ba_*), one instantiation per
-// scalar-lane count 0..BS_MAX_SCALARS, and their launch wrappers; see tu_fast.hip for why.
+// sequential plans (bs_preempt_commit.hpp: k_pc_*), of the bound table's patch (bs_bound_apply.hpp: k_ba_*) and of its remap after node-list
+// surgery (bs_bound_nodes.hpp: k_bn_*), one instantiation per scalar-lane count 0..BS_MAX_SCALARS, and their launch wrappers; see
+// tu_fast.hip for why.
 #ifndef BS_UNITY
 #define BS_TU_PREEMPT
 #endif
 #include "bs_preempt.hpp"
 #include "bs_preempt_commit.hpp"
 #include "bs_bound_apply.hpp"
+#include "bs_bound_nodes.hpp"
 #include "bs_launch.hpp"
 
 namespace bs {
@@ -60,6 +62,15 @@ static void launch_bound_apply_s(hipStream_t stream, const BoundApplyDev& a, con
   if (a.n) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ba_merge<S>), dim3((a.n + 3) / 4), dim3(256), 0, stream, a, nw);
 }
 
+template <int S>
+static void launch_bound_nodes_s(hipStream_t stream, const BoundNodesDev& a) {
+  const uint32_t items = a.n1 > a.nrem ? a.n1 : a.nrem, waves = a.n1 + (a.dropped_cap ? a.nrem : 0u);
+  if (items) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bn_len<S>), dim3((items + 255) / 256), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bn_scan1<S>), dim3(a.nblk, 2), dim3(1024), 0, stream, a);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bn_scan2<S>), dim3(a.nblk, 2), dim3(1024), 0, stream, a);
+  if (waves) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bn_move<S>), dim3((waves + 3) / 4), dim3(256), 0, stream, a);
+}
+
 #define BS_PC_CASES(CALL) \
   switch (S) { \
     case 0: CALL(0); break; case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break; \
@@ -84,6 +95,12 @@ void launch_bound_apply(hipStream_t stream, uint32_t S, const BoundApplyDev& a, 
 #define BS_BA_APPLY(s) launch_bound_apply_s<s>(stream, a, nw)
   BS_PC_CASES(BS_BA_APPLY)
 #undef BS_BA_APPLY
+}
+
+void launch_bound_nodes(hipStream_t stream, uint32_t S, const BoundNodesDev& a) {
+#define BS_BN_APPLY(s) launch_bound_nodes_s<s>(stream, a)
+  BS_PC_CASES(BS_BN_APPLY)
+#undef BS_BN_APPLY
 }
 #undef BS_PC_CASES
 

@@ -602,7 +602,11 @@ int bs_nodes_read(bs_ctx* ctx, int64_t* requested, uint32_t* requested_present);
  * keeps the count it had at the load (bs_preempt_run answers BS_ERR_STATE otherwise: reload it after list surgery).  Validated as a
  * whole: node < n of the loaded nodes, group >= 0 or one of the two sentinels (BS_ERR_INVALID); more than BS_BOUND_MAX entries or
  * BS_BOUND_MAX_PER_NODE on one node: BS_ERR_CAPACITY.  Needs bs_nodes_load first (BS_ERR_STATE).  A group index must be below the
- * group count of the state loaded when bs_preempt_run is called (BS_ERR_INVALID there). */
+ * group count of the state loaded when bs_preempt_run is called (BS_ERR_INVALID there).
+ * The stale-table test of bs_preempt_run, bs_preempt_commit and bs_bound_apply is a test of the node COUNT: the table's against
+ * bs_nodes_count.  Surgery that changes the list and keeps the count — one BS_DELTA_REMOVE and one BS_DELTA_APPEND — passes it, and
+ * every bound pod behind the removed node is then taken for a pod of the next node: wrong victims, no error.  A caller who changes the
+ * list must call bs_bound_nodes_apply with the same deltas, or reload, whether the count changed or not. */
 typedef struct bs_bound_soa {
   uint32_t b;
   const uint32_t* node;        /* [b] node list index                                                                     */
@@ -725,6 +729,35 @@ int bs_bound_ids(const bs_ctx* ctx, uint32_t* ids_out);
 /* The live table's columns as stored, in the table order of bs_bound_read (bs_bound_count entries; req is [L][count]).  Any pointer may be
  * NULL.  BS_ERR_STATE before bs_bound_load. */
 int bs_bound_dump(bs_ctx* ctx, int32_t* priority, int64_t* start_ns, int32_t* group, int64_t* req, uint32_t* req_present, uint8_t* pdb);
+
+/* ---- the bound table follows node-list surgery -------------------------------------------------------------------------------
+ * bs_nodes_apply with BS_DELTA_APPEND / BS_DELTA_REMOVE renumbers the nodes; bs_bound_nodes_apply gives the bound table the same delta
+ * list and the table is remapped on the device, instead of a bs_bound_load of the whole table.  kind[d] and index[d] are the `kind` and
+ * `index` fields of the bs_node_delta list bs_nodes_apply got; after several bs_nodes_apply calls since the table last matched the node
+ * list, their lists concatenated in order.  The arguments are flat: this form is also the cgo form.  Host work is proportional to count;
+ * the device makes one pass over the table.
+ *   order:   the call comes AFTER the bs_nodes_apply call or calls it mirrors.
+ *   replay:  the deltas are replayed in order on the table's node list, which holds the count of the last bs_bound_load or
+ *            bs_bound_nodes_apply.  BS_DELTA_UPDATE changes nothing in the table (bound pods are no node property).  BS_DELTA_APPEND
+ *            adds an empty node at the end.  BS_DELTA_REMOVE of index i drops that node's whole list — its pods are gone with the node —
+ *            and every later node moves down by one; i is the index current at that point of the replay, exactly as bs_nodes_apply
+ *            reads it.  A remove may name a node appended earlier in the same list: the two cancel.
+ *   result:  the table equals what bs_bound_load would build for the new node list from the surviving entries: they keep their ids, PDB
+ *            bits, columns and per-node importance order, and the per-node violating counts move with their nodes.  bs_bound_count falls
+ *            by the number of dropped entries; the id space (bs_bound_ids) is unchanged.  A dropped id is dead as one removed by
+ *            bs_bound_apply is: never used again before the next load, BS_ERR_INVALID for a later bs_bound_apply that removes it,
+ *            skipped by bs_bound_pdb_set.  The largest group index the table is held to name never shrinks (bs_bound_apply's rule).
+ *            Node requests are never touched.
+ *   outputs: *n_dropped_out (NULL ok) = the true number of dropped entries; dropped_ids[0 .. min(that, dropped_cap)) lists them in the OLD
+ *            table's order — old node ascending, importance order within a node.  dropped_ids may be NULL when dropped_cap == 0.
+ *   errors:  all are found before anything resident changes; on any error the table, the id space, the bits and the table's node count
+ *            are as before.  BS_ERR_STATE: before bs_bound_load; the node count the replay ends at differs from bs_nodes_count (the list
+ *            is not the one bs_nodes_apply got); a sharded context.  BS_ERR_INVALID: a kind outside the three, an UPDATE or REMOVE index at
+ *            or beyond the count current at its point of the replay, NULL arrays with count > 0, dropped_ids == NULL with dropped_cap > 0.
+ *            count == 0 is BS_OK when the counts already agree, and changes nothing.
+ *   edges:   works from an empty table and down to an empty one, and down to zero nodes where bs_nodes_apply went there.  Synchronous. */
+int bs_bound_nodes_apply(bs_ctx* ctx, uint32_t count, const uint32_t* kind, const uint32_t* index, uint32_t dropped_cap, uint32_t* dropped_ids,
+                         uint32_t* n_dropped_out);
 
 /* ---- batched queue ordering ---------------------------------------- */
 /* The permutation that sorts the pending pods the way the scheduling queue does through ScheduleOperation.Compare

@@ -6,7 +6,9 @@ nodes and the bound table are reloaded, untimed, before every call).  --pdb FRAC
 PDB-violating through bs_bound_pdb_set before the timed calls; the default 0 sets no bits.  --bound-apply K [K ...] times the bound
 table's patch instead: bs_bound_apply with K removes (seeded live ids) + K inserts (seeded nodes), next to bs_bound_load of a table of
 the same size (what a caller without the patch pays per event batch) and to a plain device-to-device copy of the table's allocation (the
-floor of any patch that forms a copy), all in one process."""
+floor of any patch that forms a copy), all in one process.  --nodes times bs_bound_nodes_apply (the table follows node-list surgery) for one
+remove + one append and for 16 removes, each next to bs_bound_load of the equivalent table (what the call replaces) in alternating order,
+and next to bs_bound_apply with 64 removes + 64 inserts on the same table."""
 from __future__ import annotations
 
 import argparse
@@ -127,6 +129,84 @@ def bound_apply_rows(config: str, ks, reps: int, warmup: int) -> list:
     return rows
 
 
+def bound_nodes_rows(config: str, reps: int, warmup: int) -> list:
+    capi = bsa.capi
+    cfg = synth.CONFIGS[config]
+    n, S = cfg["nodes"], cfg["scalars"]
+    bound, nodes = synth.make_bound(20260921, n, cfg["groups"], (20, 110), S)
+    fit = synth.make_fit(20260921, n, cfg["classes"])
+    rng = np.random.default_rng(20260921)
+
+    def delta(kind, index):
+        d = capi.NodeDelta()
+        d.kind, d.index, d.fit_default = kind, int(index), 1
+        if kind == capi.DELTA_APPEND:                          # a copy of node 0, empty
+            for j in range(4 + S):
+                d.allocatable[j] = int(nodes.allocatable[j, 0])
+            d.allocatable_present = int(nodes.allocatable_present[0])
+        return d
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t0) * 1e3
+
+    rows = []
+    with bsa.Context(scalar_lanes=S, device=0) as ctx:
+        ctx.load_nodes(nodes, fit)
+        ctx.load_bound(bound)
+        ts = []
+        for it in range(warmup + reps):                        # bs_bound_apply, 64 + 64, on the same table
+            src_i = rng.integers(0, bound.b, 64)
+            ins = soa.Bound(rng.integers(0, n, 64).astype(np.uint32), bound.priority[src_i], bound.start_ns[src_i], bound.group[src_i],
+                            bound.req[:, src_i], bound.req_present[src_i])
+            rem = ctx.read_bound()[0][rng.permutation(bound.b)[:64]]
+            ts.append(timed(lambda: ctx.bound_apply(rem, ins)))
+        apply_ms = float(np.median(ts[warmup:]))
+        for case, n_rem, n_app in (("1 remove + 1 append", 1, 1), ("16 removes", 16, 0)):
+            ctx.load_nodes(nodes, fit)
+            ctx.load_bound(bound)
+            cur, cur_n = bound, n
+
+            def surgery():
+                """one list surgery on the node list (untimed); returns (kinds, indices, the equivalent table after it)"""
+                nonlocal cur, cur_n
+                labels = np.arange(cur_n)
+                deltas = []
+                for _ in range(n_rem):
+                    i = int(rng.integers(0, labels.size))
+                    labels = np.delete(labels, i)
+                    deltas.append(delta(capi.DELTA_REMOVE, i))
+                deltas += [delta(capi.DELTA_APPEND, 0) for _ in range(n_app)]
+                ctx.apply_node_deltas(deltas)
+                new_of_old = np.full(cur_n, -1, np.int64)
+                new_of_old[labels] = np.arange(labels.size)
+                keep = new_of_old[cur.node] >= 0
+                cur = soa.Bound(new_of_old[cur.node[keep]].astype(np.uint32), cur.priority[keep], cur.start_ns[keep], cur.group[keep],
+                                cur.req[:, keep], cur.req_present[keep])
+                cur_n = labels.size + n_app
+                return [d.kind for d in deltas], [d.index for d in deltas]
+
+            t_nodes, t_load, dropped = [], [], 0
+            for it in range(warmup + reps):
+                kinds, idx = surgery()
+                if it % 2:                                     # the reload first; the call then follows a second surgery
+                    t_load.append(timed(lambda: ctx.load_bound(cur)))
+                    kinds, idx = surgery()
+                before = ctx.bound_count()
+                t_nodes.append(timed(lambda: ctx.bound_nodes_apply(kinds, idx)))
+                dropped += before - ctx.bound_count()
+                if not it % 2:
+                    t_load.append(timed(lambda: ctx.load_bound(cur)))
+            assert ctx.bound_count() == cur.b and ctx.n == cur_n and np.array_equal(np.sort(ctx.read_bound()[1]), np.sort(cur.node))
+            ms, load_ms = float(np.median(t_nodes[warmup:])), float(np.median(t_load[warmup:]))
+            rows.append(dict(config=config, nodes=n, bound=int(bound.b), case=case, nodes_apply_ms=round(ms, 4), nodes_apply_ms_min=round(min(t_nodes[warmup:]), 4),
+                             reload_ms=round(load_ms, 4), reload_ms_min=round(min(t_load[warmup:]), 4), bound_apply_64_64_ms=round(apply_ms, 4),
+                             dropped_per_call=round(dropped / (warmup + reps), 1), reload_over_nodes_apply=round(load_ms / ms, 2),
+                             nodes_apply_over_bound_apply=round(ms / apply_ms, 2)))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -134,7 +214,12 @@ def main():
     ap.add_argument("--commit", action="store_true", help="bs_preempt_commit, flags 0 and APPLY")
     ap.add_argument("--pdb", type=float, default=0.0, metavar="FRACTION", help="share of the bound pods with the PDB-violating bit (seeded)")
     ap.add_argument("--bound-apply", type=int, nargs="+", default=None, metavar="K", help="bs_bound_apply with K removes + K inserts, vs the reload and a plain copy")
+    ap.add_argument("--nodes", action="store_true", help="bs_bound_nodes_apply after 1 remove + 1 append and after 16 removes, vs the reload and bs_bound_apply")
     a = ap.parse_args()
+    if a.nodes:
+        rows = [r for c in ("cfg3", "cfg4") for r in bound_nodes_rows(c, a.reps, a.warmup)]
+        print(json.dumps(dict(metric="bs_bound_nodes_apply ms per call", rows=rows)))
+        return
     if a.bound_apply:
         rows = [r for c in ("cfg3", "cfg4") for r in bound_apply_rows(c, a.bound_apply, a.reps, a.warmup)]
         print(json.dumps(dict(metric="bs_bound_apply ms per call", rows=rows)))
