@@ -37,7 +37,10 @@ ABI_SYMBOLS = [
     "bs_bound_pdb_set", "bs_preempt_pdb_read",
     "bs_bound_apply", "bs_bound_apply_flat", "bs_bound_ids", "bs_bound_dump",
     "bs_bound_nodes_apply",
+    "bs_bound_apply_ex", "bs_bound_apply_ex_flat",
 ]
+
+BS_BOUND_NODES = soa.BS_BOUND_NODES     # bs_bound_apply_ex: the delta also moves the node requests
 
 # bsh_phase codes (include/bsched_host.h) of the phases whose gangs PreemptRemovePod protects: Running and Scheduled (core.go:235-238)
 PROTECTED_PHASES = (2, 5)
@@ -174,6 +177,8 @@ def load_library(path: str | None = None):
     L.bs_bound_pdb_set.argtypes = [vp, u32, P(u8)]
     L.bs_bound_apply.argtypes = [vp, P(soa.BoundDeltaStruct), P(u32)]
     L.bs_bound_apply_flat.argtypes = [vp, u32, P(u32), u32, P(u32), P(i32), P(C.c_int64), P(i32), P(C.c_int64), P(u32), P(u8), P(u32)]
+    L.bs_bound_apply_ex.argtypes = [vp, P(soa.BoundDeltaStruct), u32, P(u32)]
+    L.bs_bound_apply_ex_flat.argtypes = [vp, u32, u32, P(u32), u32, P(u32), P(i32), P(C.c_int64), P(i32), P(C.c_int64), P(u32), P(u8), P(u32)]
     L.bs_bound_ids.argtypes = [vp, P(u32)]
     L.bs_bound_nodes_apply.argtypes = [vp, u32, P(u32), P(u32), u32, P(u32), P(u32)]
     L.bs_bound_dump.argtypes = [vp, P(i32), P(C.c_int64), P(i32), P(C.c_int64), P(u32), P(u8)]
@@ -600,10 +605,16 @@ class Context:
         self._chk(self._lib.bs_bound_ids(self._h, C.byref(v)), "bs_bound_ids")
         return int(v.value)
 
-    def bound_apply(self, remove=None, insert: "soa.Bound | None" = None, pdb=None, flat: bool = False) -> int:
+    def bound_apply_ex(self, remove=None, insert: "soa.Bound | None" = None, pdb=None, flags: int = BS_BOUND_NODES, flat: bool = False) -> int:
+        """bs_bound_apply_ex: bound_apply with flags.  BS_BOUND_NODES (the default here): the node requests follow the delta on the
+        device, RemovePod per removed entry and AddPod per inserted one; 0: exactly bound_apply.  flat=True goes through
+        bs_bound_apply_ex_flat."""
+        return self.bound_apply(remove, insert, pdb, flat=flat, flags=int(flags))
+
+    def bound_apply(self, remove=None, insert: "soa.Bound | None" = None, pdb=None, flat: bool = False, flags: int | None = None) -> int:
         """bs_bound_apply: entries `remove` (ids) leave the resident bound table, the entries of `insert` arrive with ids
         first_id, first_id + 1, ... (pdb[i] != 0: inserted entry i is PDB-violating; None = clear).  Returns first_id.  flat=True goes
-        through bs_bound_apply_flat (the cgo form)."""
+        through bs_bound_apply_flat (the cgo form).  flags not None: through bs_bound_apply_ex / _ex_flat with these flags."""
         rem = np.ascontiguousarray(np.asarray([] if remove is None else remove, np.uint32).reshape(-1))
         ni = 0 if insert is None else int(insert.b)
         if ni:
@@ -617,7 +628,12 @@ class Context:
         first = C.c_uint32()
         rp = _u32p(rem) if rem.size else None
         pp = u8p(pv) if pv is not None else None
-        if flat:
+        if flags is not None and flat:
+            self._chk(self._lib.bs_bound_apply_ex_flat(self._h, flags, int(rem.size), rp, ni, *cols, pp, C.byref(first)), "bs_bound_apply_ex_flat")
+        elif flags is not None:
+            d = soa.BoundDeltaStruct(int(rem.size), rp, ni, *cols, pp)
+            self._chk(self._lib.bs_bound_apply_ex(self._h, C.byref(d), flags, C.byref(first)), "bs_bound_apply_ex")
+        elif flat:
             self._chk(self._lib.bs_bound_apply_flat(self._h, int(rem.size), rp, ni, *cols, pp, C.byref(first)), "bs_bound_apply_flat")
         else:
             d = soa.BoundDeltaStruct(int(rem.size), rp, ni, *cols, pp)

@@ -17,6 +17,12 @@
 //                    rank counting, 64 entries per step: a survivor moves back by the inserts strictly more important in (priority,
 //                    start), an insert lands at its rank in the segment plus the survivors at least as important (an insert's id is
 //                    larger than every survivor's, so a tie goes behind).  Every column moves; lane 0 writes the node's PDB count.
+// With BS_BOUND_NODES (bs_bound_apply_ex) a fifth launch follows once the host has read the error word clear:
+//   k_ba_nodes<S>    one wave per node, four nodes per workgroup; a node the delta does not touch returns at once.  The lanes stride over
+//                    the node's OLD list (still intact: the merge wrote the other allocation) and subtract the entries whose dead bit is
+//                    set, then over the node's insert segment and add; a wave reduction, and lane 0 writes the node's new absolute
+//                    request vector (k_pc_nodes' rule) as a bs_node_request record at a slot taken from a counter.  k_nodes_assume runs
+//                    over the records.
 // S is a template parameter as for every kernel of this code object (one symbol per translation unit that instantiates it); the request
 // lanes are moved by an unrolled loop, load to store: no register array, no scratch.
 #pragma once
@@ -234,6 +240,77 @@ __global__ __launch_bounds__(256) void k_ba_merge(BoundApplyDev a, CompactDev nw
     }
   }
   if (lane == 0) nw.bnviol[k] = nviol;
+}
+
+// what k_ba_nodes reads of the node table and where its records go
+struct BoundNodesReqDev {
+  const int64_t* nreq;      // [L][nstride] the nodes' requested lanes
+  const uint32_t* rpres;    // [n] their present bits
+  uint32_t nstride;
+  uint32_t cap;             // records `out` holds: min(n, n_remove + n_insert), which bounds the touched nodes
+  uint32_t* count;          // zeroed; the number of records written
+  bs_node_request* out;
+};
+
+// BS_BOUND_NODES: node k gets requested - (its removed entries) + (its inserted entries), wrapping; a scalar lane none of them has keeps
+// its word and its present bit, the others are set (an absent key counts as 0): k_pc_nodes' rule.  The lanes are summed through
+// unrolled constant indices only (registers, no scratch).
+template <int S>
+__global__ __launch_bounds__(256) void k_ba_nodes(BoundApplyDev a, BoundNodesReqDev o) {
+  constexpr int L = 4 + S;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t k = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+  if (k >= a.n) return;
+  const uint32_t nd = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.dcnt[k]), ni = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.icnt[k]);
+  if (nd == 0u && ni == 0u) return;
+  int64_t acc[L];                                          // inserts minus removes, this lane's share
+#pragma unroll
+  for (int l = 0; l < L; ++l) acc[l] = 0;
+  uint32_t bits = 0;
+  if (nd) {
+    const uint32_t b0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.boff[k]), b1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.boff[k + 1]);
+    for (uint32_t base = b0; base < b1; base += 64u) {
+      const uint32_t j = base + lane;
+      if (j < b1 && ((a.deadw[j >> 5] >> (j & 31u)) & 1u)) {
+        bits |= a.bpres[j];
+#pragma unroll
+        for (int l = 0; l < L; ++l) acc[l] = wsub(acc[l], a.breq[(size_t)l * a.bstride + j]);
+      }
+    }
+  }
+  if (ni) {
+    const uint32_t i0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.ifirst[k]);
+    for (uint32_t w = lane; w < ni; w += 64u) {
+      const uint32_t src = i0 + w;
+      bits |= a.ipres[src];
+#pragma unroll
+      for (int l = 0; l < L; ++l) acc[l] = wadd(acc[l], a.ireq[(size_t)l * a.n_insert + src]);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    bits |= (uint32_t)__shfl_xor((int)bits, off);
+#pragma unroll
+    for (int l = 0; l < L; ++l) acc[l] = wadd(acc[l], (int64_t)__shfl_xor((long long)acc[l], off));
+  }
+  if (lane != 0) return;
+  const uint32_t smask = S > 0 ? (uint32_t)((1ull << S) - 1ull) : 0u;
+  const uint32_t rp = o.rpres[k], touched = bits & smask;
+  bs_node_request r;
+  r.index = k;
+  r.requested_present = rp | touched;
+#pragma unroll
+  for (int l = 0; l < BS_MAX_LANES; ++l) r.requested[l] = 0;
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    const int64_t raw = o.nreq[(size_t)l * o.nstride + k];
+    const bool lane_on = l < 4 || ((touched >> (l - 4)) & 1u);
+    if (!lane_on) { r.requested[l] = raw; continue; }
+    const int64_t base = (l < 4 || ((rp >> (l - 4)) & 1u)) ? raw : 0;
+    r.requested[l] = wadd(base, acc[l]);
+  }
+  const uint32_t slot = atomicAdd(o.count, 1u);
+  if (slot < o.cap) o.out[slot] = r;
 }
 
 }  // namespace bs

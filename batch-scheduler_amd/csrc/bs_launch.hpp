@@ -51,6 +51,10 @@ void launch_preempt_apply(hipStream_t stream, uint32_t S, const NodesDev& nd, co
 // k_ba_merge<S> (one wave per node into nw; writes nothing when the error word is set)
 struct BoundApplyDev;
 void launch_bound_apply(hipStream_t stream, uint32_t S, const BoundApplyDev& a, const CompactDev& nw);
+// BS_BOUND_NODES, after the error word came back clear: k_ba_nodes<S> (one wave per node; the touched nodes' new request vectors as
+// bs_node_request records for k_nodes_assume, counted in o.count)
+struct BoundNodesReqDev;
+void launch_bound_apply_nodes(hipStream_t stream, uint32_t S, const BoundApplyDev& a, const BoundNodesReqDev& o);
 
 // the bound table's remap after node-list surgery (tu_preempt.hip, bs_bound_nodes.hpp): k_bn_len<S>, k_bn_scan1<S> + k_bn_scan2<S> (the new
 // CSR and the dropped ids' offsets, a.nblk blocks each), k_bn_move<S> (one wave per new node, and per removed node when ids are asked for)

@@ -4259,9 +4259,13 @@ int bs_bound_ids(const bs_ctx* c, uint32_t* ids_out) {
   return BS_OK;
 }
 
-int bs_bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t* first_id_out) {
+// flags: 0 = bs_bound_apply; BS_BOUND_NODES = the node requests follow (bs_bound_apply_ex)
+static int bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t flags, uint32_t* first_id_out) {
   if (!c || !d) return BS_ERR_INVALID;
+  if (flags & ~BS_BOUND_NODES) { c->last_error = "bs_bound_apply_ex: unknown flags"; return BS_ERR_INVALID; }
+  const bool with_nodes = (flags & BS_BOUND_NODES) != 0;
   if (!c->have_bound) { c->last_error = "bs_bound_apply before bs_bound_load"; return BS_ERR_STATE; }
+  if (with_nodes && !c->have_nodes) { c->last_error = "bs_bound_apply_ex(BS_BOUND_NODES) before bs_nodes_load"; return BS_ERR_STATE; }
   if (c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
   const uint32_t R = d->n_remove, I = d->n_insert, N = c->N, L = c->L, B = c->bound_b, ids = c->bound_ids;
   if (R && !d->remove) return BS_ERR_INVALID;
@@ -4282,6 +4286,7 @@ int bs_bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t* first_id_out) {
   if ((uint64_t)ids + I > BS_BOUND_MAX) { c->last_error = "bs_bound_apply: the id space would pass BS_BOUND_MAX: reload the table"; return BS_ERR_CAPACITY; }
   int rc = use_device(c);
   if (rc) return rc;
+  if (with_nodes && (rc = settle_pending(c))) return rc;   // as bs_nodes_assume: a pending batch is settled against the state it was launched on
   // the inserts by (node, importance); their ids follow the delta's order, so equal keys keep it
   std::vector<uint32_t> order(I);
   for (uint32_t i = 0; i < I; ++i) order[i] = i;
@@ -4311,7 +4316,10 @@ int bs_bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t* first_id_out) {
   const size_t o_dcnt = o; o = align256(o + nN * 4);
   const size_t o_icnt = o; o = align256(o + nN * 4);
   const size_t o_err = o; o = align256(o + 4);
+  const size_t o_nrec = o + 248; o = align256(o + 256);    // BS_BOUND_NODES: the record count, the last 8 bytes before the records (one D2H)
   const size_t zero_bytes = o - o_zero;
+  const size_t rec_cap = with_nodes ? std::min<size_t>(N, nR + nI) : 0;
+  const size_t o_rec = o; o = align256(o + rec_cap * sizeof(bs_node_request));
   const size_t o_ifirst = o; o = align256(o + nN * 4);
   // the id space grows with every call, and the table with every net insert: a quarter of headroom, so that a run of calls allocates rarely
   if (o > c->d_pre.cap) HIPCHK(c, c->d_pre.reserve(o + o / 4));
@@ -4411,7 +4419,50 @@ int bs_bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t* first_id_out) {
   c->bound_ids = ids + I;
   c->bound_max_group = gmax;
   if (first_id_out) *first_id_out = ids;
+  if (with_nodes && rec_cap) {
+    // the node requests follow: `a` still names the old table (now the second allocation, intact) and the scratch k_ba_mark left
+    BoundNodesReqDev o2{};
+    o2.nreq = c->d_nreq.as<int64_t>();
+    o2.rpres = c->d_rpres.as<uint32_t>();
+    o2.nstride = c->Ncap;
+    o2.cap = (uint32_t)rec_cap;
+    o2.count = reinterpret_cast<uint32_t*>(base + o_nrec);
+    o2.out = reinterpret_cast<bs_node_request*>(base + o_rec);
+    launch_bound_apply_nodes(c->stream, c->S, a, o2);
+    LAUNCHCHK(c, BS_KERNEL_PREPASS);
+    std::vector<uint8_t> hr(8 + rec_cap * sizeof(bs_node_request));   // count + records: the host mirror a later bs_nodes_apply starts from
+    HIPCHK(c, hipMemcpyAsync(hr.data(), base + o_nrec, hr.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    uint32_t nrec = 0;
+    std::memcpy(&nrec, hr.data(), 4);
+    if (nrec > rec_cap) { c->last_error = "bs_bound_apply_ex: more touched nodes than the delta can touch"; return BS_ERR_HIP; }
+    if (nrec) {
+      static_assert(sizeof(bs_node_request) == sizeof(NodeRequest), "node request layout");
+      hipLaunchKernelGGL(k_nodes_assume, dim3(cdiv(nrec, 256)), dim3(256), 0, c->stream, reinterpret_cast<const NodeRequest*>(o2.out), nrec, L, c->Ncap,
+                         c->d_alloc.as<int64_t>(), c->d_nreq.as<int64_t>(), c->d_rpres.as<uint32_t>(), c->d_nflags.as<uint8_t>(), c->d_left4.as<int64_t>(),
+                         c->d_lglob.as<int64_t>());
+      LAUNCHCHK(c, BS_KERNEL_PREPASS);
+      const bs_node_request* recs = reinterpret_cast<const bs_node_request*>(hr.data() + 8);
+      for (uint32_t i = 0; i < nrec; ++i) {
+        const bs_node_request& r = recs[i];
+        for (uint32_t j = 0; j < L; ++j) c->h_nreq[(size_t)j * N + r.index] = r.requested[j];
+        c->h_rpres[r.index] = r.requested_present;
+      }
+      c->bitmap_valid = false;
+    }
+  }
   return BS_OK;
+}
+
+int bs_bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t* first_id_out) { return bound_apply(c, d, 0u, first_id_out); }
+
+int bs_bound_apply_ex(bs_ctx* c, const bs_bound_delta* d, uint32_t flags, uint32_t* first_id_out) { return bound_apply(c, d, flags, first_id_out); }
+
+int bs_bound_apply_ex_flat(bs_ctx* c, uint32_t flags, uint32_t n_remove, const uint32_t* remove, uint32_t n_insert, const uint32_t* node,
+                           const int32_t* priority, const int64_t* start_ns, const int32_t* group, const int64_t* req, const uint32_t* req_present,
+                           const uint8_t* pdb_violating, uint32_t* first_id_out) {
+  const bs_bound_delta d{n_remove, remove, n_insert, node, priority, start_ns, group, req, req_present, pdb_violating};
+  return bound_apply(c, &d, flags, first_id_out);
 }
 
 int bs_bound_apply_flat(bs_ctx* c, uint32_t n_remove, const uint32_t* remove, uint32_t n_insert, const uint32_t* node, const int32_t* priority,

@@ -63,6 +63,11 @@ static void launch_bound_apply_s(hipStream_t stream, const BoundApplyDev& a, con
 }
 
 template <int S>
+static void launch_bound_apply_nodes_s(hipStream_t stream, const BoundApplyDev& a, const BoundNodesReqDev& o) {
+  if (a.n) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ba_nodes<S>), dim3((a.n + 3) / 4), dim3(256), 0, stream, a, o);
+}
+
+template <int S>
 static void launch_bound_nodes_s(hipStream_t stream, const BoundNodesDev& a) {
   const uint32_t items = a.n1 > a.nrem ? a.n1 : a.nrem, waves = a.n1 + (a.dropped_cap ? a.nrem : 0u);
   if (items) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bn_len<S>), dim3((items + 255) / 256), dim3(256), 0, stream, a);
@@ -95,6 +100,12 @@ void launch_bound_apply(hipStream_t stream, uint32_t S, const BoundApplyDev& a, 
 #define BS_BA_APPLY(s) launch_bound_apply_s<s>(stream, a, nw)
   BS_PC_CASES(BS_BA_APPLY)
 #undef BS_BA_APPLY
+}
+
+void launch_bound_apply_nodes(hipStream_t stream, uint32_t S, const BoundApplyDev& a, const BoundNodesReqDev& o) {
+#define BS_BA_NODES(s) launch_bound_apply_nodes_s<s>(stream, a, o)
+  BS_PC_CASES(BS_BA_NODES)
+#undef BS_BA_NODES
 }
 
 void launch_bound_nodes(hipStream_t stream, uint32_t S, const BoundNodesDev& a) {

@@ -701,7 +701,7 @@ int bs_bound_read(bs_ctx* ctx, uint32_t* id_out, uint32_t* node_out);
  *           inserted entries keep the delta's order among themselves.  This is exactly the table bs_bound_load would build from the
  *           surviving and the new entries listed in ascending id order.
  *   effect: removes are applied before inserts.  Only the bound table changes: node requests stay with bs_nodes_apply /
- *           bs_nodes_assume, as bs_bound_load leaves them alone.  A surviving entry keeps its PDB bit, an inserted entry takes
+ *           bs_nodes_assume, as bs_bound_load leaves them alone (bs_bound_apply_ex with BS_BOUND_NODES moves them too).  A surviving entry keeps its PDB bit, an inserted entry takes
  *           pdb_violating[i] (NULL: every bit clear), and the per-node violating counts are recounted.  Columns are stored as bs_bound_load
  *           stores them: the pods lane 1, an absent scalar key 0, req_present masked to the context's scalar lanes.  The largest group
  *           index the table is held to name (checked against the group count by the preemption calls) becomes the maximum of its old
@@ -726,6 +726,30 @@ typedef struct bs_bound_delta {
 } bs_bound_delta;
 int bs_bound_apply(bs_ctx* ctx, const bs_bound_delta* delta, uint32_t* first_id_out);
 int bs_bound_ids(const bs_ctx* ctx, uint32_t* ids_out);
+/* bs_bound_apply_ex: bs_bound_apply plus `flags`.  A bind or delete event then is ONE call: the caller names the ids that leave and the
+ * entries that arrive, and the node requests follow on the device (no bs_nodes_assume record with a vector computed by the caller).
+ *   flags == 0: the call IS bs_bound_apply: same table, same errors, node requests untouched.  Bits other than BS_BOUND_NODES:
+ *           BS_ERR_INVALID.
+ *   BS_BOUND_NODES: the table part is exactly bs_bound_apply's (id rule, order, errors, all or nothing).  After it, every node the
+ *           delta touches gets a new `requested` vector and new `requested_present` bits, by the rule of bs_preempt_commit step 2
+ *           (NodeInfo.RemovePod per removed entry, AddPod per inserted one).  For node k, with rem = the entries of k this delta
+ *           removes AS THE TABLE STORES THEM (pods lane 1, an absent scalar key 0), ins = the entries inserted on k as bs_bound_load
+ *           would store them, and touched = the OR of the req_present bits of rem and ins, masked to the context's scalar lanes:
+ *             lanes 0..3:               new = old - sum(rem) + sum(ins); the pods lane so moves by |ins| - |rem|;
+ *             scalar lane in touched:   new = (old if the node's present bit is set, else 0) - sum(rem) + sum(ins), the bit becomes set;
+ *             scalar lane not touched:  the word and the bit stay as they are.
+ *           All arithmetic is wrapping int64, so the result does not depend on the order of the entries.  For a delete the caller
+ *           names the id only: the removed entry's request lanes and key bits are columns of the table.  The derived node data
+ *           (left resources, their cluster-wide bounds, the host mirror a later bs_nodes_apply starts from) follows as after
+ *           bs_nodes_assume; allocatable, node flags and fit masks are untouched.
+ *   nominee: a nominee of BS_PREEMPT_ASSUME that binds on its nominated node is inserted WITHOUT the flag (bs_bound_apply, or flags 0):
+ *           its request is on the node already.
+ *   errors: bs_bound_apply's, with the same codes; on any error nothing resident changes, node requests included (they are written
+ *           only after the table part is known to succeed).  With BS_BOUND_NODES the call also refuses what bs_nodes_assume refuses in
+ *           the same context state, with the same code, before anything is launched (BS_ERR_STATE before bs_nodes_load).  An empty
+ *           delta is BS_OK and changes nothing.  Synchronous. */
+#define BS_BOUND_NODES 1u   /* the delta also moves the node requests: RemovePod per removed entry, AddPod per inserted one */
+int bs_bound_apply_ex(bs_ctx* ctx, const bs_bound_delta* delta, uint32_t flags, uint32_t* first_id_out);
 /* The live table's columns as stored, in the table order of bs_bound_read (bs_bound_count entries; req is [L][count]).  Any pointer may be
  * NULL.  BS_ERR_STATE before bs_bound_load. */
 int bs_bound_dump(bs_ctx* ctx, int32_t* priority, int64_t* start_ns, int32_t* group, int64_t* req, uint32_t* req_present, uint8_t* pdb);
@@ -878,6 +902,10 @@ int bs_preempt_run_flat(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint
 int bs_bound_apply_flat(bs_ctx* ctx, uint32_t n_remove, const uint32_t* remove, uint32_t n_insert, const uint32_t* node, const int32_t* priority,
                         const int64_t* start_ns, const int32_t* group, const int64_t* req, const uint32_t* req_present,
                         const uint8_t* pdb_violating, uint32_t* first_id_out);
+/* bs_bound_apply_ex (flags, then bs_bound_apply_flat's arguments in the same order) */
+int bs_bound_apply_ex_flat(bs_ctx* ctx, uint32_t flags, uint32_t n_remove, const uint32_t* remove, uint32_t n_insert, const uint32_t* node,
+                           const int32_t* priority, const int64_t* start_ns, const int32_t* group, const int64_t* req,
+                           const uint32_t* req_present, const uint8_t* pdb_violating, uint32_t* first_id_out);
 /* bs_preempt_commit (bs_preempt_out's arrays one by one) */
 int bs_preempt_commit_flat(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
                            const uint8_t* group_protected, uint32_t flags, uint32_t victim_cap, int32_t* node, uint32_t* n_candidates,

@@ -8,7 +8,10 @@ table's patch instead: bs_bound_apply with K removes (seeded live ids) + K inser
 the same size (what a caller without the patch pays per event batch) and to a plain device-to-device copy of the table's allocation (the
 floor of any patch that forms a copy), all in one process.  --nodes times bs_bound_nodes_apply (the table follows node-list surgery) for one
 remove + one append and for 16 removes, each next to bs_bound_load of the equivalent table (what the call replaces) in alternating order,
-and next to bs_bound_apply with 64 removes + 64 inserts on the same table."""
+and next to bs_bound_apply with 64 removes + 64 inserts on the same table.  --bound-nodes K times bs_bound_apply_ex with BS_BOUND_NODES (K removes +
+K inserts: table and node requests in one call) against the sequence it replaces, in alternating order on one context: the new absolute
+request vectors of the touched nodes computed on the host (numpy, from a host copy of the entries' requests), bs_bound_apply, then
+bs_nodes_assume; the three parts are also reported on their own."""
 from __future__ import annotations
 
 import argparse
@@ -207,6 +210,85 @@ def bound_nodes_rows(config: str, reps: int, warmup: int) -> list:
     return rows
 
 
+def bound_apply_nodes_rows(config: str, k: int, reps: int, warmup: int) -> list:
+    import ctypes as C
+    capi = bsa.capi
+    cfg = synth.CONFIGS[config]
+    n, S = cfg["nodes"], cfg["scalars"]
+    L = 4 + S
+    bound, nodes = synth.make_bound(20260921, n, cfg["groups"], (20, 110), S)
+    fit = synth.make_fit(20260921, n, cfg["classes"])
+    rng = np.random.default_rng(20260921)
+    smask = np.uint32((1 << S) - 1)
+
+    def stored(b):                                             # the columns as the table stores them
+        req = np.array(b.req, np.int64, copy=True)
+        pres = b.req_present & smask
+        req[3] = 1
+        for j in range(S):
+            req[4 + j] = np.where((pres >> np.uint32(j)) & 1, req[4 + j], 0)
+        return req, pres
+
+    rec = np.dtype([("index", np.uint32), ("requested_present", np.uint32), ("requested", np.int64, (soa.MAX_LANES,))])
+    assert rec.itemsize == C.sizeof(capi.NodeRequest)
+    h_req, h_pres = stored(bound)                              # the shim's copy of every entry, by id
+    h_node = bound.node.copy()
+    n_req, n_pres = np.array(nodes.requested, np.int64, copy=True), np.array(nodes.requested_present, np.uint32, copy=True)
+    t_ex, t_host, t_apply, t_assume = [], [], [], []
+    with bsa.Context(scalar_lanes=S, device=0) as ctx:
+        ctx.load_nodes(nodes, fit)
+        ctx.load_bound(bound)
+        live = np.arange(bound.b, dtype=np.uint32)
+        for it in range(2 * (warmup + reps)):
+            at = rng.permutation(live.size)[:k]
+            src_i = rng.integers(0, bound.b, k)
+            ins = soa.Bound(rng.integers(0, n, k).astype(np.uint32), bound.priority[src_i], bound.start_ns[src_i], bound.group[src_i],
+                            bound.req[:, src_i], bound.req_present[src_i])
+            rem = live[at]
+            t0 = time.perf_counter()                           # the host arithmetic of the two-call sequence (the flagged call needs none of it)
+            ireq, ipres = stored(ins)
+            d = np.zeros((L, n), np.int64)
+            bits = np.zeros(n, np.uint32)
+            with np.errstate(over="ignore"):
+                for j in range(L):
+                    np.subtract.at(d[j], h_node[rem], h_req[j, rem])
+                    np.add.at(d[j], ins.node, ireq[j])
+            np.bitwise_or.at(bits, h_node[rem], h_pres[rem])
+            np.bitwise_or.at(bits, ins.node, ipres)
+            hit = np.unique(np.concatenate([h_node[rem], ins.node]))
+            for j in range(L):
+                on = np.ones(hit.size, bool) if j < 4 else ((bits[hit] >> np.uint32(j - 4)) & 1) != 0
+                base = n_req[j, hit] if j < 4 else np.where((n_pres[hit] >> np.uint32(j - 4)) & 1, n_req[j, hit], 0)
+                with np.errstate(over="ignore"):
+                    n_req[j, hit] = np.where(on, base + d[j, hit], n_req[j, hit])
+            n_pres[hit] |= bits[hit]
+            recs = np.zeros(hit.size, rec)
+            recs["index"], recs["requested_present"] = hit, n_pres[hit]
+            recs["requested"][:, :L] = n_req[:, hit].T
+            t1 = time.perf_counter()
+            timed = it >= 2 * warmup
+            if it % 2:
+                first = ctx.bound_apply(rem, ins)
+                t2 = time.perf_counter()
+                ctx._chk(ctx._lib.bs_nodes_assume(ctx._h, recs.ctypes.data_as(C.POINTER(capi.NodeRequest)), int(hit.size)), "bs_nodes_assume")
+                t3 = time.perf_counter()
+                if timed:
+                    t_host.append((t1 - t0) * 1e3), t_apply.append((t2 - t1) * 1e3), t_assume.append((t3 - t2) * 1e3)
+            else:
+                first = ctx.bound_apply_ex(rem, ins, flags=capi.BS_BOUND_NODES)
+                if timed:
+                    t_ex.append((time.perf_counter() - t1) * 1e3)
+            h_req, h_pres, h_node = np.concatenate([h_req, ireq], axis=1), np.concatenate([h_pres, ipres]), np.concatenate([h_node, ins.node])
+            live = np.concatenate([np.delete(live, at), np.arange(first, first + k, dtype=np.uint32)])
+        got_req, got_pres = ctx.read_node_requests()
+        assert np.array_equal(got_req, n_req) and np.array_equal(got_pres, n_pres), "the two forms left different node requests"
+    med = lambda t: round(float(np.median(t)), 4)              # noqa: E731
+    two = [a + b + c for a, b, c in zip(t_host, t_apply, t_assume)]
+    return [dict(config=config, nodes=n, bound=int(bound.b), k=k, flagged_ms=med(t_ex), flagged_ms_min=round(min(t_ex), 4), two_call_ms=med(two),
+                 two_call_ms_min=round(min(two), 4), host_vectors_ms=med(t_host), bound_apply_ms=med(t_apply), nodes_assume_ms=med(t_assume),
+                 two_calls_without_host_ms=med([b + c for b, c in zip(t_apply, t_assume)]), two_call_over_flagged=round(med(two) / med(t_ex), 2))]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -215,7 +297,13 @@ def main():
     ap.add_argument("--pdb", type=float, default=0.0, metavar="FRACTION", help="share of the bound pods with the PDB-violating bit (seeded)")
     ap.add_argument("--bound-apply", type=int, nargs="+", default=None, metavar="K", help="bs_bound_apply with K removes + K inserts, vs the reload and a plain copy")
     ap.add_argument("--nodes", action="store_true", help="bs_bound_nodes_apply after 1 remove + 1 append and after 16 removes, vs the reload and bs_bound_apply")
+    ap.add_argument("--bound-nodes", type=int, default=None, metavar="K", help="bs_bound_apply_ex(BS_BOUND_NODES) with K removes + K inserts, vs bs_bound_apply + "
+                    "bs_nodes_assume with the vectors computed on the host")
     a = ap.parse_args()
+    if a.bound_nodes:
+        rows = [r for c in ("cfg3", "cfg4") for r in bound_apply_nodes_rows(c, a.bound_nodes, a.reps, a.warmup)]
+        print(json.dumps(dict(metric="bs_bound_apply_ex ms per call", rows=rows)))
+        return
     if a.nodes:
         rows = [r for c in ("cfg3", "cfg4") for r in bound_nodes_rows(c, a.reps, a.warmup)]
         print(json.dumps(dict(metric="bs_bound_nodes_apply ms per call", rows=rows)))
