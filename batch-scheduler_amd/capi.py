@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "bs_bound_apply", "bs_bound_apply_flat", "bs_bound_ids", "bs_bound_dump",
     "bs_bound_nodes_apply",
     "bs_bound_apply_ex", "bs_bound_apply_ex_flat",
+    "bs_pdb_load", "bs_pdb_members_append", "bs_pdb_allowed_apply", "bs_pdb_read",
 ]
 
 BS_BOUND_NODES = soa.BS_BOUND_NODES     # bs_bound_apply_ex: the delta also moves the node requests
@@ -183,6 +184,10 @@ def load_library(path: str | None = None):
     L.bs_bound_nodes_apply.argtypes = [vp, u32, P(u32), P(u32), u32, P(u32), P(u32)]
     L.bs_bound_dump.argtypes = [vp, P(i32), P(C.c_int64), P(i32), P(C.c_int64), P(u32), P(u8)]
     L.bs_preempt_pdb_read.argtypes = [vp, u32, P(u32)]
+    L.bs_pdb_load.argtypes = [vp, u32, P(i32), u32, P(u32), P(u32)]
+    L.bs_pdb_members_append.argtypes = [vp, u32, u32, P(u32), P(u32)]
+    L.bs_pdb_allowed_apply.argtypes = [vp, u32, P(u32), P(i32)]
+    L.bs_pdb_read.argtypes = [vp, P(u32), P(u32), P(i32), P(u32)]
     L.bs_preempt_commit_flat.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), u32, u32, P(i32), P(u32), P(u32), P(u32), P(i32), P(C.c_int64),
                                          P(C.c_int64)]
     for name in ABI_SYMBOLS:
@@ -653,6 +658,43 @@ class Context:
         self._chk(self._lib.bs_bound_nodes_apply(self._h, int(kv.size), _u32p(kv) if kv.size else None, _u32p(iv) if iv.size else None,
                                                  int(dropped_cap), _u32p(ids) if dropped_cap else None, C.byref(nd)), "bs_bound_nodes_apply")
         return int(nd.value), ids[: min(int(nd.value), int(dropped_cap))].copy()
+
+    # -- resident PodDisruptionBudgets: the PDB bits follow the budgets' status on the device
+    def pdb_load(self, allowed, member_off, member, b: int | None = None):
+        """bs_pdb_load: allowed[n_pdb] (Status.PodDisruptionsAllowed) and, per bound-pod id, the PDBs that select it as a CSR
+        (pdb.matching_members / pdb.allowed_vector build the arrays).  b defaults to len(member_off) - 1 and must equal bound_ids()."""
+        al = np.ascontiguousarray(allowed, np.int32).reshape(-1)
+        off = np.ascontiguousarray(member_off, np.uint32).reshape(-1)
+        mem = np.ascontiguousarray(member, np.uint32).reshape(-1)
+        b = max(off.size - 1, 0) if b is None else int(b)
+        self._chk(self._lib.bs_pdb_load(self._h, int(al.size), al.ctypes.data_as(C.POINTER(C.c_int32)) if al.size else None, b,
+                                        _u32p(off) if off.size else None, _u32p(mem) if mem.size else None), "bs_pdb_load")
+
+    def pdb_members_append(self, first_id: int, member_off, member):
+        """bs_pdb_members_append: the memberships of ids first_id .. first_id + len(member_off) - 2, the ids bound_apply created since
+        the CSR last covered the id space (member_off is the run's own, from 0)"""
+        off = np.ascontiguousarray(member_off, np.uint32).reshape(-1)
+        mem = np.ascontiguousarray(member, np.uint32).reshape(-1)
+        self._chk(self._lib.bs_pdb_members_append(self._h, int(first_id), max(off.size - 1, 0), _u32p(off) if off.size else None,
+                                                  _u32p(mem) if mem.size else None), "bs_pdb_members_append")
+
+    def pdb_allowed_apply(self, index, value):
+        """bs_pdb_allowed_apply: allowed[index[i]] = value[i], then the bits and per-node counts are recomputed on the device"""
+        ix = np.ascontiguousarray(index, np.uint32).reshape(-1)
+        va = np.ascontiguousarray(value, np.int32).reshape(-1)
+        assert ix.size == va.size
+        self._chk(self._lib.bs_pdb_allowed_apply(self._h, int(ix.size), _u32p(ix) if ix.size else None,
+                                                 va.ctypes.data_as(C.POINTER(C.c_int32)) if va.size else None), "bs_pdb_allowed_apply")
+
+    def pdb_read(self) -> dict:
+        """bs_pdb_read: n_pdb, covered, allowed[n_pdb] and the live table's per-node violating counts"""
+        n, cov = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self._lib.bs_pdb_read(self._h, C.byref(n), C.byref(cov), None, None), "bs_pdb_read")
+        nodes = C.c_uint32(0)
+        self._chk(self._lib.bs_nodes_count(self._h, C.byref(nodes)), "bs_nodes_count")
+        al, nv = np.zeros(max(n.value, 1), np.int32), np.zeros(max(nodes.value, 1), np.uint32)
+        self._chk(self._lib.bs_pdb_read(self._h, None, None, al.ctypes.data_as(C.POINTER(C.c_int32)), _u32p(nv)), "bs_pdb_read")
+        return dict(n_pdb=int(n.value), covered=int(cov.value), allowed=al[: n.value], node_violating=nv[: nodes.value])
 
     def bound_dump(self) -> dict:
         """bs_bound_dump: the live table's columns as stored, in read_bound's order: priority, start_ns, group, req [L, count],

@@ -61,4 +61,9 @@ void launch_bound_apply_nodes(hipStream_t stream, uint32_t S, const BoundApplyDe
 struct BoundNodesDev;
 void launch_bound_nodes(hipStream_t stream, uint32_t S, const BoundNodesDev& a);
 
+// resident PodDisruptionBudgets (tu_preempt.hip, bs_pdb.hpp): k_pdb_allowed when a.count pairs are staged, then k_pdb_bits, one wave per node
+// of the live table, rewrites its PDB byte column and per-node violating counts in place
+struct PdbDev;
+void launch_pdb(hipStream_t stream, const PdbDev& a);
+
 }  // namespace bs

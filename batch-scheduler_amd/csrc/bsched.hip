@@ -35,6 +35,7 @@
 #include "bs_bound_apply.hpp"
 #include "bs_bound_nodes.hpp"
 #include "bs_bound_nodes_replay.hpp"
+#include "bs_pdb.hpp"
 #ifdef BS_UNITY   // one translation unit (the probe builds: g_probe / g_seq_scan_ph are per translation unit)
 #include "tu_fast.hip"
 #include "tu_seq.hip"
@@ -290,6 +291,10 @@ struct bs_ctx {
   uint32_t bound_ids = 0;            // the id space of bs_bound_pdb_set: entries at the last bs_bound_load plus what bs_bound_apply inserted since
   std::vector<uint32_t> pre_npv;     // PDB-violating victims per preemptor of the last preemption call (bs_preempt_pdb_read)
   bool have_pre_npv = false;
+  // resident PodDisruptionBudgets (bs_pdb.hpp): allowed[pdb_n], and the PDBs of every covered bound-pod id as a CSR by id; dropped by bs_bound_load
+  bool have_pdb = false;
+  uint32_t pdb_n = 0, pdb_covered = 0, pdb_members = 0;   // PDBs, ids the CSR covers, membership entries (= moff[pdb_covered])
+  DevBuf d_pdb_allowed, d_pdb_moff, d_pdb_member;
 
   // ---- streams, events, pinned host memory.  Declared LAST and in this order: members are destroyed in reverse, so the pinned buffers
   // and events go first, then stream3, then stream, and only then the DevBufs above (bs_destroy has waited for both streams).
@@ -301,6 +306,7 @@ struct bs_ctx {
   PinnedBuf<> h_stage{PinWait::Event};    // pod staging; busy until the last H2D out of it is through (bs_pods_load does not wait for it)
   PinnedBuf<> h_dstage{PinWait::Stream};  // the delta the apply kernel reads in place (no event per apply: bs_pods_apply)
   PinnedBuf<> h_nstage{PinWait::Event};   // node requests of bs_nodes_assume
+  PinnedBuf<> h_pdbstage{PinWait::Stream};  // bs_pdb_allowed_apply's (index, value) pairs, read in place by k_pdb_allowed
   // result staging (bs_batch_read) and, in latency mode, the pinned result pack the last launch writes itself
   PinnedBuf<> h_rstage;
   PinnedBuf<> h_hout{PinWait::None, hipHostMallocMapped | hipHostMallocCoherent};            // [outpack layout | feas[hstride] | tag]
@@ -3846,6 +3852,8 @@ int bs_bound_load(bs_ctx* c, const bs_bound_soa* bd) {
   c->bound_n = N;
   c->bound_max_group = gmax;
   c->have_bound = true;                                   // (h was zeroed: every PDB bit is clear)
+  c->have_pdb = false;                                    // the id space restarts: the resident PDB state names the old one
+  c->pdb_n = c->pdb_covered = c->pdb_members = 0;
   return BS_OK;
 }
 
@@ -3876,6 +3884,155 @@ int bs_bound_pdb_set(bs_ctx* c, uint32_t b, const uint8_t* violating) {
   HIPCHK(c, hipMemcpyAsync(bb + c->blay.pdb, bits.data(), nB, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(bb + c->blay.nviol, nviol.data(), nN * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));             // (local buffers)
+  return BS_OK;
+}
+
+// -------------------------------------------------------------------------------------------------
+// resident PodDisruptionBudgets (bs_pdb.hpp): the PDB bits follow the budgets' status on the device
+// -------------------------------------------------------------------------------------------------
+namespace {
+
+// what every bs_pdb_* call refuses before it looks at its arguments
+int pdb_state(bs_ctx* c, const char* who, bool need_pdb) {
+  if (!c->have_bound) { c->last_error = std::string(who) + " before bs_bound_load"; return BS_ERR_STATE; }
+  if (c->nranks > 1 || c->reduce_external) { c->last_error = std::string(who) + " is single-rank only"; return BS_ERR_STATE; }
+  if (need_pdb && !c->have_pdb) { c->last_error = std::string(who) + " without a bs_pdb_load since the last bs_bound_load"; return BS_ERR_STATE; }
+  return BS_OK;
+}
+
+// member_off[n + 1] ascending from 0, every member < n_pdb, and the total within BS_PDB_MEMBERS_MAX on top of `have`
+int pdb_csr_check(bs_ctx* c, const char* who, uint32_t n, const uint32_t* member_off, const uint32_t* member, uint32_t n_pdb, uint32_t have) {
+  if (n && !member_off) return BS_ERR_INVALID;
+  const uint32_t total = n ? member_off[n] : 0u;
+  if (n && member_off[0] != 0u) { c->last_error = std::string(who) + ": member_off does not start at 0"; return BS_ERR_INVALID; }
+  for (uint32_t i = 0; i < n; ++i)
+    if (member_off[i + 1] < member_off[i]) { c->last_error = std::string(who) + ": member_off is not ascending"; return BS_ERR_INVALID; }
+  if ((uint64_t)have + total > BS_PDB_MEMBERS_MAX) { c->last_error = std::string(who) + ": more than BS_PDB_MEMBERS_MAX membership entries"; return BS_ERR_CAPACITY; }
+  if (total && !member) return BS_ERR_INVALID;
+  for (uint32_t x = 0; x < total; ++x)
+    if (member[x] >= n_pdb) { c->last_error = std::string(who) + ": a member index >= n_pdb"; return BS_ERR_INVALID; }
+  return BS_OK;
+}
+
+// the recompute behind whatever the caller enqueued (count staged pairs go into allowed[] first); waits for it
+int pdb_recompute(bs_ctx* c, uint32_t count, const uint32_t* index, const int32_t* value) {
+  uint8_t* bb = c->d_bound.as<uint8_t>();
+  PdbDev a{};
+  a.boff = reinterpret_cast<const uint32_t*>(bb + c->blay.boff);
+  a.bid = reinterpret_cast<const uint32_t*>(bb + c->blay.id);
+  a.bpdb = bb + c->blay.pdb;
+  a.bnviol = reinterpret_cast<uint32_t*>(bb + c->blay.nviol);
+  a.n = c->bound_n;
+  a.moff = c->d_pdb_moff.as<uint32_t>();
+  a.member = c->d_pdb_member.as<uint32_t>();
+  a.allowed = c->d_pdb_allowed.as<int32_t>();
+  a.covered = c->pdb_covered;
+  a.index = index;
+  a.value = value;
+  a.count = count;
+  launch_pdb(c->stream, a);
+  LAUNCHCHK(c, BS_KERNEL_PREPASS);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return BS_OK;
+}
+
+// room for `bytes` in a buffer whose first `keep` bytes stay: a buffer that has to grow gets a quarter of headroom (a run of appends
+// allocates rarely, as the bound table does)
+int pdb_grow(bs_ctx* c, DevBuf& buf, size_t bytes, size_t keep) {
+  if (bytes <= buf.cap) return BS_OK;
+  DevBuf nw;
+  HIPCHK(c, nw.reserve(bytes + bytes / 4));
+  if (keep) HIPCHK(c, hipMemcpyAsync(nw.p, buf.p, keep, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::swap(buf.p, nw.p);
+  std::swap(buf.cap, nw.cap);
+  return BS_OK;                                            // (nw frees the old allocation)
+}
+
+}  // namespace
+
+int bs_pdb_load(bs_ctx* c, uint32_t n_pdb, const int32_t* allowed, uint32_t b, const uint32_t* member_off, const uint32_t* member) {
+  if (!c) return BS_ERR_INVALID;
+  int rc = pdb_state(c, "bs_pdb_load", false);
+  if (rc) return rc;
+  if (n_pdb > BS_PDB_MAX) { c->last_error = "bs_pdb_load: more than BS_PDB_MAX PDBs"; return BS_ERR_CAPACITY; }
+  if (b != c->bound_ids) { c->last_error = "bs_pdb_load: b differs from bs_bound_ids"; return BS_ERR_INVALID; }
+  if (n_pdb && !allowed) return BS_ERR_INVALID;
+  if ((rc = pdb_csr_check(c, "bs_pdb_load", b, member_off, member, n_pdb, 0u))) return rc;
+  if ((rc = use_device(c))) return rc;
+  const uint32_t total = b ? member_off[b] : 0u, zero = 0;
+  c->have_pdb = false;
+  HIPCHK(c, c->d_pdb_allowed.reserve((size_t)std::max<uint32_t>(n_pdb, 1) * 4));
+  HIPCHK(c, c->d_pdb_moff.reserve(((size_t)b + 1) * 4));
+  HIPCHK(c, c->d_pdb_member.reserve((size_t)std::max<uint32_t>(total, 1) * 4));
+  if (n_pdb) HIPCHK(c, hipMemcpyAsync(c->d_pdb_allowed.p, allowed, (size_t)n_pdb * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_pdb_moff.p, b ? member_off : &zero, ((size_t)b + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  if (total) HIPCHK(c, hipMemcpyAsync(c->d_pdb_member.p, member, (size_t)total * 4, hipMemcpyHostToDevice, c->stream));
+  c->pdb_n = n_pdb;
+  c->pdb_covered = b;
+  c->pdb_members = total;
+  if ((rc = pdb_recompute(c, 0u, nullptr, nullptr))) return rc;   // (waits: the caller's arrays and `zero` are free again)
+  c->have_pdb = true;
+  return BS_OK;
+}
+
+int bs_pdb_members_append(bs_ctx* c, uint32_t first_id, uint32_t n, const uint32_t* member_off, const uint32_t* member) {
+  if (!c) return BS_ERR_INVALID;
+  int rc = pdb_state(c, "bs_pdb_members_append", true);
+  if (rc) return rc;
+  if (first_id != c->pdb_covered) { c->last_error = "bs_pdb_members_append: first_id differs from the number of ids covered so far"; return BS_ERR_INVALID; }
+  if ((uint64_t)first_id + n > c->bound_ids) { c->last_error = "bs_pdb_members_append: first_id + n passes bs_bound_ids"; return BS_ERR_INVALID; }
+  if ((rc = pdb_csr_check(c, "bs_pdb_members_append", n, member_off, member, c->pdb_n, c->pdb_members))) return rc;
+  if ((rc = use_device(c))) return rc;
+  const uint32_t total = n ? member_off[n] : 0u, have = c->pdb_members, cov = c->pdb_covered;
+  if (n) {
+    if ((rc = pdb_grow(c, c->d_pdb_moff, ((size_t)cov + n + 1) * 4, ((size_t)cov + 1) * 4))) return rc;
+    if ((rc = pdb_grow(c, c->d_pdb_member, ((size_t)have + total) * 4, (size_t)have * 4))) return rc;
+    std::vector<uint32_t> off(n);                          // the run's ends, moved behind the entries the CSR holds
+    for (uint32_t i = 0; i < n; ++i) off[i] = have + member_off[i + 1];
+    HIPCHK(c, hipMemcpyAsync(c->d_pdb_moff.as<uint32_t>() + cov + 1, off.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if (total) HIPCHK(c, hipMemcpyAsync(c->d_pdb_member.as<uint32_t>() + have, member, (size_t)total * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));            // (off is a local buffer)
+    c->pdb_covered = cov + n;
+    c->pdb_members = have + total;
+  }
+  return pdb_recompute(c, 0u, nullptr, nullptr);
+}
+
+int bs_pdb_allowed_apply(bs_ctx* c, uint32_t count, const uint32_t* index, const int32_t* value) {
+  if (!c) return BS_ERR_INVALID;
+  int rc = pdb_state(c, "bs_pdb_allowed_apply", true);
+  if (rc) return rc;
+  if (count == 0) return BS_OK;
+  if (!index || !value) return BS_ERR_INVALID;
+  if (count > c->pdb_n) { c->last_error = "bs_pdb_allowed_apply: more pairs than PDBs (an index is listed twice or is out of range)"; return BS_ERR_INVALID; }
+  std::vector<uint32_t> seen(index, index + count);
+  std::sort(seen.begin(), seen.end());
+  if (seen.back() >= c->pdb_n) { c->last_error = "bs_pdb_allowed_apply: an index >= n_pdb"; return BS_ERR_INVALID; }
+  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { c->last_error = "bs_pdb_allowed_apply: an index is listed twice"; return BS_ERR_INVALID; }
+  if ((rc = use_device(c))) return rc;
+  const size_t bytes = (size_t)count * 8;
+  HIPCHK(c, c->h_pdbstage.reserve(bytes, std::max<size_t>(bytes + bytes / 4, 4096)));
+  std::memcpy(c->h_pdbstage.p, index, (size_t)count * 4);
+  std::memcpy(c->h_pdbstage.p + (size_t)count * 4, value, (size_t)count * 4);
+  HIPCHK(c, c->h_pdbstage.mark_busy(c->stream));
+  rc = pdb_recompute(c, count, reinterpret_cast<const uint32_t*>(c->h_pdbstage.p), reinterpret_cast<const int32_t*>(c->h_pdbstage.p + (size_t)count * 4));
+  if (rc == BS_OK) c->h_pdbstage.busy = false;             // (the recompute waited for the stream)
+  return rc;
+}
+
+int bs_pdb_read(bs_ctx* c, uint32_t* n_pdb_out, uint32_t* covered_out, int32_t* allowed_out, uint32_t* node_violating_out) {
+  if (!c) return BS_ERR_INVALID;
+  int rc = pdb_state(c, "bs_pdb_read", true);
+  if (rc) return rc;
+  if (node_violating_out && c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
+  if ((rc = use_device(c))) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (n_pdb_out) *n_pdb_out = c->pdb_n;
+  if (covered_out) *covered_out = c->pdb_covered;
+  if (allowed_out && c->pdb_n) HIPCHK(c, hipMemcpy(allowed_out, c->d_pdb_allowed.p, (size_t)c->pdb_n * 4, hipMemcpyDeviceToHost));
+  if (node_violating_out && c->bound_n)
+    HIPCHK(c, hipMemcpy(node_violating_out, c->d_bound.as<uint8_t>() + c->blay.nviol, (size_t)c->bound_n * 4, hipMemcpyDeviceToHost));
   return BS_OK;
 }
 

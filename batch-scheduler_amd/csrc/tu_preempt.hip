@@ -1,7 +1,7 @@
 // tu_preempt.hip — translation unit of the preemption victim search (bs_preempt.hpp: k_preempt_scan / k_preempt_pick), of the
 // sequential plans (bs_preempt_commit.hpp: k_pc_*), of the bound table's patch (bs_bound_apply.hpp: k_ba_*) and of its remap after node-list
-// surgery (bs_bound_nodes.hpp: k_bn_*), one instantiation per scalar-lane count 0..BS_MAX_SCALARS, and their launch wrappers; see
-// tu_fast.hip for why.
+// surgery (bs_bound_nodes.hpp: k_bn_*), one instantiation per scalar-lane count 0..BS_MAX_SCALARS, of the resident PodDisruptionBudgets
+// (bs_pdb.hpp: k_pdb_*, no templates), and their launch wrappers; see tu_fast.hip for why.
 #ifndef BS_UNITY
 #define BS_TU_PREEMPT
 #endif
@@ -9,6 +9,7 @@
 #include "bs_preempt_commit.hpp"
 #include "bs_bound_apply.hpp"
 #include "bs_bound_nodes.hpp"
+#include "bs_pdb.hpp"
 #include "bs_launch.hpp"
 
 namespace bs {
@@ -114,5 +115,10 @@ void launch_bound_nodes(hipStream_t stream, uint32_t S, const BoundNodesDev& a) 
 #undef BS_BN_APPLY
 }
 #undef BS_PC_CASES
+
+void launch_pdb(hipStream_t stream, const PdbDev& a) {
+  if (a.count) hipLaunchKernelGGL(k_pdb_allowed, dim3((a.count + 255) / 256), dim3(256), 0, stream, a);
+  if (a.n) hipLaunchKernelGGL(k_pdb_bits, dim3((a.n + 3) / 4), dim3(256), 0, stream, a);
+}
 
 }  // namespace bs

@@ -92,3 +92,31 @@ def violating_bits(pdbs, bound_pods) -> np.ndarray:
         ns = pod.get("namespace", "")
         out[i] = any(pns == ns and selector_matches(reqs, labels) for pns, reqs in parsed)   # M1
     return out
+
+
+def matching_members(pdbs, bound_pods):
+    """(member_off, member) for Context.pdb_load / pdb_members_append: the PDBs that select each bound pod, by M1-M4 alone —
+    disruptions_allowed is not looked at, that is the device's half (M5 over Context.pdb_allowed_apply's vector).  member_off is
+    uint32 [len(bound_pods) + 1] from 0, member holds PDB indices, ascending within a pod.  A PDB whose selector is unparsable, nil
+    or empty keeps its index and matches nobody."""
+    parsed = []
+    for pdb in pdbs:
+        try:
+            reqs = parse_selector(pdb.get("selector"))
+        except ValueError:
+            reqs = None                                  # M3
+        parsed.append((pdb.get("namespace", ""), reqs or None))   # M4
+    off = np.zeros(len(bound_pods) + 1, np.uint32)
+    member = []
+    for i, pod in enumerate(bound_pods):
+        labels = pod.get("labels")
+        if labels:                                       # M2
+            ns = pod.get("namespace", "")
+            member += [m for m, (pns, reqs) in enumerate(parsed) if reqs is not None and pns == ns and selector_matches(reqs, labels)]   # M1
+        off[i + 1] = len(member)
+    return off, np.asarray(member, np.uint32)
+
+
+def allowed_vector(pdbs) -> np.ndarray:
+    """allowed[n_pdb] for Context.pdb_load: every PDB's Status.PodDisruptionsAllowed (absent: 0, as violating_bits reads it)"""
+    return np.asarray([int(pdb.get("disruptions_allowed", 0)) for pdb in pdbs], np.int32).reshape(-1)

@@ -75,3 +75,114 @@ func (g *gpuCore) applyBoundEvents(removed []uint32, bound []boundPodEvent, lane
 	}
 	return uint32(first), nil
 }
+
+// Resident PodDisruptionBudgets (include/bsched.h "resident PodDisruptionBudgets"): the shim matches a pod's labels against the selectors
+// once, when the pod binds, and hands the device the PDB indices; when a PDB's Status.PodDisruptionsAllowed changes, one
+// bs_pdb_allowed_apply call rewrites the PDB bits on the device.  The shim keeps no label record per bound pod for this.
+
+func u32s(v []uint32) ([]C.uint32_t, *C.uint32_t) {
+	out := make([]C.uint32_t, len(v))
+	for i, x := range v {
+		out[i] = C.uint32_t(x)
+	}
+	if len(out) == 0 {
+		return out, nil
+	}
+	return out, &out[0]
+}
+
+func i32s(v []int32) ([]C.int32_t, *C.int32_t) {
+	out := make([]C.int32_t, len(v))
+	for i, x := range v {
+		out[i] = C.int32_t(x)
+	}
+	if len(out) == 0 {
+		return out, nil
+	}
+	return out, &out[0]
+}
+
+func (g *gpuCore) pdbErr(what string, rc C.int) error {
+	return fmt.Errorf("%s: %s (%s)", what, C.GoString(C.bs_strerror(rc)), C.GoString(C.bs_last_error(g.ctx)))
+}
+
+// loadPDBs: after loadBound.  allowed[m] is PDB m's Status.PodDisruptionsAllowed; memberOff / member list, per bound-pod id, the PDBs
+// that select the pod (len(memberOff) == ids + 1, from 0).
+func (g *gpuCore) loadPDBs(allowed []int32, memberOff, member []uint32) error {
+	b := 0
+	if len(memberOff) > 0 {
+		b = len(memberOff) - 1
+	}
+	_, pAllowed := i32s(allowed)
+	_, pOff := u32s(memberOff)
+	_, pMember := u32s(member)
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if rc := C.bs_pdb_load(g.ctx, C.uint32_t(len(allowed)), pAllowed, C.uint32_t(b), pOff, pMember); rc != C.BS_OK {
+		return g.pdbErr("bs_pdb_load", rc)
+	}
+	return nil
+}
+
+// appendPDBMembers: after each applyBoundEvents that inserted pods: firstID is what it returned, memberOff (from 0) / member the PDBs
+// of the inserted pods in the order they were inserted.
+func (g *gpuCore) appendPDBMembers(firstID uint32, memberOff, member []uint32) error {
+	n := 0
+	if len(memberOff) > 0 {
+		n = len(memberOff) - 1
+	}
+	_, pOff := u32s(memberOff)
+	_, pMember := u32s(member)
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if rc := C.bs_pdb_members_append(g.ctx, C.uint32_t(firstID), C.uint32_t(n), pOff, pMember); rc != C.BS_OK {
+		return g.pdbErr("bs_pdb_members_append", rc)
+	}
+	return nil
+}
+
+// applyPDBStatus: the PDBs whose Status.PodDisruptionsAllowed changed, each index once.
+func (g *gpuCore) applyPDBStatus(index []uint32, allowed []int32) error {
+	if len(index) != len(allowed) {
+		return fmt.Errorf("applyPDBStatus: %d indices, %d values", len(index), len(allowed))
+	}
+	_, pIndex := u32s(index)
+	_, pValue := i32s(allowed)
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if rc := C.bs_pdb_allowed_apply(g.ctx, C.uint32_t(len(index)), pIndex, pValue); rc != C.BS_OK {
+		return g.pdbErr("bs_pdb_allowed_apply", rc)
+	}
+	return nil
+}
+
+// readPDBs: the resident budgets and the per-node violating counts (nodes = the node count), for reconciliation and tests.
+func (g *gpuCore) readPDBs(nodes int) (allowed []int32, covered uint32, nodeViolating []uint32, err error) {
+	var nPdb, cov C.uint32_t
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if rc := C.bs_pdb_read(g.ctx, &nPdb, &cov, nil, nil); rc != C.BS_OK {
+		return nil, 0, nil, g.pdbErr("bs_pdb_read", rc)
+	}
+	al := make([]C.int32_t, int(nPdb))
+	nv := make([]C.uint32_t, nodes)
+	var pAl *C.int32_t
+	var pNv *C.uint32_t
+	if len(al) > 0 {
+		pAl = &al[0]
+	}
+	if len(nv) > 0 {
+		pNv = &nv[0]
+	}
+	if rc := C.bs_pdb_read(g.ctx, nil, nil, pAl, pNv); rc != C.BS_OK {
+		return nil, 0, nil, g.pdbErr("bs_pdb_read", rc)
+	}
+	allowed, nodeViolating = make([]int32, len(al)), make([]uint32, len(nv))
+	for i, x := range al {
+		allowed[i] = int32(x)
+	}
+	for i, x := range nv {
+		nodeViolating[i] = uint32(x)
+	}
+	return allowed, uint32(cov), nodeViolating, nil
+}

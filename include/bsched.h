@@ -623,7 +623,8 @@ int bs_bound_count(const bs_ctx* ctx, uint32_t* b_out);
  * bs_bound_load and b is that load's entry count — the id space, which bs_bound_apply grows (bs_bound_ids) — (BS_ERR_INVALID
  * otherwise); entries evicted since by BS_PREEMPT_APPLY or removed by bs_bound_apply are skipped.
  * violating == NULL clears every bit.  bs_bound_load clears them too.  BS_ERR_STATE before bs_bound_load.  The bits stay until the next
- * bs_bound_pdb_set / bs_bound_load; a surviving entry keeps its bit through BS_PREEMPT_APPLY.  Synchronous. */
+ * bs_bound_pdb_set / bs_bound_load; a surviving entry keeps its bit through BS_PREEMPT_APPLY.  Synchronous.  (The bs_pdb_* calls below
+ * compute the bits on the device from resident PDBs instead; their recompute overwrites these bits.) */
 int bs_bound_pdb_set(bs_ctx* ctx, uint32_t b, const uint8_t* violating);
 /* Results per preemptor q (caller's order).  node and n_victims are required, the other arrays may be NULL; victims is required when
  * victim_cap > 0. */
@@ -666,7 +667,8 @@ int bs_preempt_pdb_read(bs_ctx* ctx, uint32_t count, uint32_t* n_pdb_violations)
  *      key with the PDB violations in front, ties).  Slot 0's answer is exactly bs_preempt_run's answer for that preemptor.
  *      Library rule: the PDB bits are those of the last bs_bound_pdb_set for the WHOLE call — an earlier slot's evictions do not turn
  *      further pods violating, as upstream v1.17.5 would not within one cycle either (D1).  The caller refreshes the bits from the
- *      PDBs' status between calls.  With BS_PREEMPT_APPLY a surviving entry keeps its bit through the compaction.
+ *      PDBs' status between calls (bs_bound_pdb_set, or bs_pdb_allowed_apply where the PDBs are resident: one of the two ways).  With
+ *      BS_PREEMPT_APPLY a surviving entry keeps its bit through the compaction.
  *   4. flags: 0 = the plan only, nothing resident changes (as bs_preempt_run).  BS_PREEMPT_APPLY: after the pass the evictions are
  *      written into the context: the bound table loses every victim of every slot (survivors keep their caller ids from the last
  *      bs_bound_load and their per-node importance order; bs_bound_count falls by the number of victims), node requests lose the victims
@@ -782,6 +784,42 @@ int bs_bound_dump(bs_ctx* ctx, int32_t* priority, int64_t* start_ns, int32_t* gr
  *   edges:   works from an empty table and down to an empty one, and down to zero nodes where bs_nodes_apply went there.  Synchronous. */
 int bs_bound_nodes_apply(bs_ctx* ctx, uint32_t count, const uint32_t* kind, const uint32_t* index, uint32_t dropped_cap, uint32_t* dropped_ids,
                          uint32_t* n_dropped_out);
+
+/* ---- resident PodDisruptionBudgets: the PDB bits follow the budgets' status on the device ------------------------------------
+ * bs_bound_pdb_set takes finished bits: the caller matches every bound pod against every exhausted PDB whenever a budget crosses zero.
+ * The two inputs of a bit change at different rates, so here they arrive apart.  WHICH PDBs select a pod (namespace and selector, D1) is
+ * string work the caller does once, when the pod binds: a CSR by bound-pod id.  WHETHER a PDB is exhausted is one int32 per PDB,
+ * Status.PodDisruptionsAllowed, and is patched per cycle by index.  The bits are then integer work over the resident table.
+ *   recompute: every call below ends with one: the live table's PDB bits and per-node violating counts are rewritten in place, in stream
+ *            order.  The entry with id i gets bit 1 iff i < covered and some m in member[member_off[i] .. member_off[i + 1]) has
+ *            allowed[m] <= 0 (a signed int32 compare); else 0 — an id not yet covered has no PDB.  A node's count is the number of set
+ *            bits in its list.  Rows of dead ids (removed, evicted, dropped) are never visited.
+ *   load:    bs_pdb_load replaces any earlier resident PDB state.  b must equal bs_bound_ids; member_off[b + 1] ascends from 0 and
+ *            member[x] < n_pdb; allowed[n_pdb].  n_pdb == 0 and an empty table are valid (member_off may be NULL when b == 0, member
+ *            when there is no entry).  covered becomes b.
+ *   append:  ids only grow, and the CSR is by id: the memberships of the ids bs_bound_apply created since are an append.  first_id must
+ *            equal covered, first_id + n <= bs_bound_ids; member_off[n + 1] ascends from 0 (the run's own offsets).  covered grows by n.
+ *   apply:   the per-cycle call: allowed[index[i]] = value[i]; an index may appear once.  count == 0 is BS_OK and launches nothing.
+ *   read:    any pointer may be NULL: the PDB count, covered, allowed[n_pdb], and the per-node violating counts of the live table
+ *            ([bs_nodes_count]; BS_ERR_STATE while the table's node count differs from it, as for bs_bound_apply).
+ *   interplay: no other call changes its behaviour.  bs_bound_load drops the resident PDB state (the id space restarts) and clears the
+ *            bits, as before.  bs_bound_pdb_set keeps writing bits directly and the last writer wins: its bits stand until the next
+ *            recompute, a recompute's until the next bs_bound_pdb_set.  A caller uses ONE of the two ways.  bs_bound_apply[_ex],
+ *            BS_PREEMPT_APPLY and bs_bound_nodes_apply carry bits as they always did; an inserted entry keeps pdb_violating[i] until the
+ *            next recompute, which gives it 0 while its id is not covered.  The preemption calls read the bits as before, and within one
+ *            bs_preempt_commit they are fixed (D1).  Budgets are NOT counted down as victims are chosen: two victims of one plan may
+ *            spend the same last disruption, as upstream v1.17.5 allows within one cycle; the caller writes the new status afterwards.
+ *   errors:  all are found on the host before anything is launched or changed.  BS_ERR_STATE: before bs_bound_load; a sharded context;
+ *            append / apply / read without a bs_pdb_load since the last bs_bound_load.  BS_ERR_INVALID: b != bs_bound_ids; an offset array
+ *            that does not start at 0 or descends; a member >= n_pdb; first_id != covered; first_id + n > bs_bound_ids; an index >=
+ *            n_pdb; an index listed twice; NULL required arrays.  BS_ERR_CAPACITY: more than BS_PDB_MAX PDBs or BS_PDB_MEMBERS_MAX
+ *            membership entries in all.  Synchronous, like bs_bound_pdb_set. */
+#define BS_PDB_MAX (1u << 20)          /* PDB objects */
+#define BS_PDB_MEMBERS_MAX (1u << 28)  /* total membership entries */
+int bs_pdb_load(bs_ctx* ctx, uint32_t n_pdb, const int32_t* allowed, uint32_t b, const uint32_t* member_off, const uint32_t* member);
+int bs_pdb_members_append(bs_ctx* ctx, uint32_t first_id, uint32_t n, const uint32_t* member_off, const uint32_t* member);
+int bs_pdb_allowed_apply(bs_ctx* ctx, uint32_t count, const uint32_t* index, const int32_t* value);
+int bs_pdb_read(bs_ctx* ctx, uint32_t* n_pdb_out, uint32_t* covered_out, int32_t* allowed_out, uint32_t* node_violating_out);
 
 /* ---- batched queue ordering ---------------------------------------- */
 /* The permutation that sorts the pending pods the way the scheduling queue does through ScheduleOperation.Compare

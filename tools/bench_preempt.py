@@ -11,7 +11,9 @@ remove + one append and for 16 removes, each next to bs_bound_load of the equiva
 and next to bs_bound_apply with 64 removes + 64 inserts on the same table.  --bound-nodes K times bs_bound_apply_ex with BS_BOUND_NODES (K removes +
 K inserts: table and node requests in one call) against the sequence it replaces, in alternating order on one context: the new absolute
 request vectors of the touched nodes computed on the host (numpy, from a host copy of the entries' requests), bs_bound_apply, then
-bs_nodes_assume; the three parts are also reported on their own."""
+bs_nodes_assume; the three parts are also reported on their own.  --pdb-resident times one bs_pdb_allowed_apply of 8 indices (64 resident
+PDBs, the bits recomputed on the device) and, in the same process, the path it replaces, its two parts reported separately:
+pdb.violating_bits over string records of every bound pod, then bs_bound_pdb_set."""
 from __future__ import annotations
 
 import argparse
@@ -289,6 +291,53 @@ def bound_apply_nodes_rows(config: str, k: int, reps: int, warmup: int) -> list:
                  two_calls_without_host_ms=med([b + c for b, c in zip(t_apply, t_assume)]), two_call_over_flagged=round(med(two) / med(t_ex), 2))]
 
 
+def pdb_resident_rows(config: str, reps: int, warmup: int, host_reps: int = 2) -> list:
+    pdbmod = bsa.pdb
+    cfg = synth.CONFIGS[config]
+    n, S, n_pdb = cfg["nodes"], cfg["scalars"], 64
+    bound, nodes = synth.make_bound(20260921, n, cfg["groups"], (20, 110), S)
+    fit = synth.make_fit(20260921, n, cfg["classes"])
+    rng = np.random.default_rng(20260921)
+    app = rng.integers(0, n_pdb + 16, bound.b)                 # PDB m selects app=a<m>: a fifth of the pods are selected by nobody
+    pods = [{"namespace": "default", "labels": {"app": f"a{j}"}} for j in app.tolist()]
+    allowed = np.where(rng.random(n_pdb) < 0.1, 0, 2).astype(np.int32)
+    pdbs = [{"namespace": "default", "selector": {"matchLabels": {"app": f"a{m}"}}, "disruptions_allowed": int(v)} for m, v in enumerate(allowed)]
+    sel = app < n_pdb                                          # the memberships, as matching_members gives them (held against it on a sample)
+    off = np.concatenate([[0], np.cumsum(sel)]).astype(np.uint32)
+    member = app[sel].astype(np.uint32)
+    s_off, s_member = pdbmod.matching_members(pdbs, pods[:2000])
+    assert np.array_equal(s_off, off[:2001]) and np.array_equal(s_member, member[: int(off[2000])])
+    t_apply, t_bits, t_set = [], [], []
+    with bsa.Context(scalar_lanes=S, device=0) as ctx:
+        ctx.load_nodes(nodes, fit)
+        ctx.load_bound(bound)
+        ctx.pdb_load(allowed, off, member)
+        ids, _ = ctx.read_bound()
+        for it in range(warmup + reps):
+            idx = rng.permutation(n_pdb)[:8]
+            val = np.where(allowed[idx] <= 0, 2, 0).astype(np.int32)
+            t0 = time.perf_counter()
+            ctx.pdb_allowed_apply(idx, val)
+            if it >= warmup:
+                t_apply.append((time.perf_counter() - t0) * 1e3)
+            allowed[idx] = val
+        resident = ctx.bound_dump()["pdb"]
+        for m, v in enumerate(allowed):
+            pdbs[m]["disruptions_allowed"] = int(v)
+        for it in range(host_reps):                            # the replaced path, on the same context (the last writer wins)
+            t0 = time.perf_counter()
+            bits = pdbmod.violating_bits(pdbs, pods)
+            t1 = time.perf_counter()
+            ctx.bound_pdb_set(bits)
+            t_bits.append((t1 - t0) * 1e3), t_set.append((time.perf_counter() - t1) * 1e3)
+        assert np.array_equal(resident, bits[ids]) and np.array_equal(ctx.bound_dump()["pdb"], resident), "the two paths left different bits"
+    med = lambda t: round(float(np.median(t)), 4)              # noqa: E731
+    return [dict(config=config, nodes=n, bound=int(bound.b), pdbs=n_pdb, members=int(member.size), indices=8, allowed_apply_ms=med(t_apply),
+                 allowed_apply_ms_min=round(min(t_apply), 4), violating_bits_ms=med(t_bits), bound_pdb_set_ms=med(t_set),
+                 bound_pdb_set_ms_min=round(min(t_set), 4), violating=int(resident.sum()),
+                 pdb_set_over_allowed_apply=round(med(t_set) / med(t_apply), 2))]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -299,7 +348,12 @@ def main():
     ap.add_argument("--nodes", action="store_true", help="bs_bound_nodes_apply after 1 remove + 1 append and after 16 removes, vs the reload and bs_bound_apply")
     ap.add_argument("--bound-nodes", type=int, default=None, metavar="K", help="bs_bound_apply_ex(BS_BOUND_NODES) with K removes + K inserts, vs bs_bound_apply + "
                     "bs_nodes_assume with the vectors computed on the host")
+    ap.add_argument("--pdb-resident", action="store_true", help="bs_pdb_allowed_apply of 8 indices, vs pdb.violating_bits + bs_bound_pdb_set")
     a = ap.parse_args()
+    if a.pdb_resident:
+        rows = [r for c in ("cfg3", "cfg4") for r in pdb_resident_rows(c, a.reps, a.warmup)]
+        print(json.dumps(dict(metric="bs_pdb_allowed_apply ms per call", rows=rows)))
+        return
     if a.bound_nodes:
         rows = [r for c in ("cfg3", "cfg4") for r in bound_apply_nodes_rows(c, a.bound_nodes, a.reps, a.warmup)]
         print(json.dumps(dict(metric="bs_bound_apply_ex ms per call", rows=rows)))
