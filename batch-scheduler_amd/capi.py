@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "bs_bound_nodes_apply",
     "bs_bound_apply_ex", "bs_bound_apply_ex_flat",
     "bs_pdb_load", "bs_pdb_members_append", "bs_pdb_allowed_apply", "bs_pdb_read",
+    "bs_preempt_commit_gang", "bs_preempt_commit_gang_flat", "bs_preempt_gang_read",
 ]
 
 BS_BOUND_NODES = soa.BS_BOUND_NODES     # bs_bound_apply_ex: the delta also moves the node requests
@@ -51,6 +52,30 @@ def group_protected(phases) -> np.ndarray:
     """bs_preempt_run's group_protected[g] from each group's bsh_phase code: 1 where the phase is Scheduled or Running."""
     ph = np.asarray(phases, dtype=np.int64).reshape(-1)
     return np.isin(ph, PROTECTED_PHASES).astype(np.uint8)
+
+
+def gang_order(pod_group, priority) -> np.ndarray:
+    """A permutation of the caller's preemptor list for bs_preempt_commit_gang: priority descending (stable), then by first appearance
+    of the group within the priority, members in the caller's order; preemptors without a group index >= 0 count as groups of their
+    own.  Every gang of equal-priority members becomes one run of slots."""
+    grp = np.asarray(pod_group, np.int64).reshape(-1)
+    pri = np.asarray(priority, np.int64).reshape(-1)
+    assert grp.shape == pri.shape
+    first: dict = {}
+    rank = np.zeros(grp.shape[0], np.int64)
+    for i in range(grp.shape[0]):
+        key = (int(pri[i]), int(grp[i])) if grp[i] >= 0 else (int(pri[i]), -1 - i)
+        rank[i] = first.setdefault(key, i)
+    return np.lexsort((np.arange(grp.shape[0]), rank, -pri)).astype(np.int64)
+
+
+def gang_need(groups, waiting=None) -> np.ndarray:
+    """bs_preempt_commit_gang's gang_need[g] from the loaded groups: MinMember minus Status.Scheduled minus the members already waiting
+    at Permit (waiting[g], default 0), never below 0: how many more members must get a node for the gang to pass its quorum."""
+    mm = np.asarray(groups.min_member, np.int64).reshape(-1)
+    w = np.zeros_like(mm) if waiting is None else np.asarray(waiting, np.int64).reshape(-1)
+    assert w.shape == mm.shape
+    return np.clip(mm - np.asarray(groups.status_scheduled, np.int64).reshape(-1) - w, 0, None).astype(np.uint32)
 
 
 class BsError(RuntimeError):
@@ -190,6 +215,10 @@ def load_library(path: str | None = None):
     L.bs_pdb_read.argtypes = [vp, P(u32), P(u32), P(i32), P(u32)]
     L.bs_preempt_commit_flat.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), u32, u32, P(i32), P(u32), P(u32), P(u32), P(i32), P(C.c_int64),
                                          P(C.c_int64)]
+    L.bs_preempt_commit_gang.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), P(u32), u32, u32, P(soa.PreemptOutStruct)]
+    L.bs_preempt_commit_gang_flat.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), P(u32), u32, u32, P(i32), P(u32), P(u32), P(u32), P(i32),
+                                              P(C.c_int64), P(C.c_int64)]
+    L.bs_preempt_gang_read.argtypes = [vp, u32, P(u8), u32, P(u32)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:
@@ -573,7 +602,22 @@ class Context:
         flags = (soa.PREEMPT_APPLY if apply else 0) | (soa.PREEMPT_ASSUME if assume else 0)
         return self._preempt_call(flags, pod_index, priority, group_protected, victim_cap, stages)
 
-    def _preempt_call(self, flags, pod_index, priority, group_protected, victim_cap, stages) -> dict:
+    def preempt_commit_gang(self, pod_index, priority, group_protected=None, gang_need=None, victim_cap: int = 16, apply: bool = False,
+                            assume: bool = False, stages: int = soa.STAGE_PREFILTER, flat: bool = False) -> dict:
+        """bs_preempt_commit_gang: preempt_commit, with each gang's quorum decided inside the pass: gang_need[g] members of group g must
+        get a node in this call (the module's gang_need builds it; gang_order makes each gang one run), or the gang's slots are voided
+        and their evictions taken back before the later slots are answered.  Returns preempt_commit's dict plus slot_voided [count]
+        and group_placed [g] (bs_preempt_gang_read).  flat=True goes through bs_preempt_commit_gang_flat."""
+        flags = (soa.PREEMPT_APPLY if apply else 0) | (soa.PREEMPT_ASSUME if assume else 0)
+        need = None if gang_need is None else np.ascontiguousarray(np.asarray(gang_need, np.uint32).reshape(-1))
+        res = self._preempt_call(flags, pod_index, priority, group_protected, victim_cap, stages, gang=(need, flat))
+        q, g = len(res["node"]), 0 if need is None else int(need.size)
+        voided, placed = np.zeros(max(q, 1), np.uint8), np.zeros(max(g, 1), np.uint32)
+        self._chk(self._lib.bs_preempt_gang_read(self._h, q, voided.ctypes.data_as(C.POINTER(C.c_uint8)), g, _u32p(placed)), "bs_preempt_gang_read")
+        res["slot_voided"], res["group_placed"] = voided[:q], placed[:g]
+        return res
+
+    def _preempt_call(self, flags, pod_index, priority, group_protected, victim_cap, stages, gang=None) -> dict:
         pi = np.ascontiguousarray(np.asarray(pod_index, np.uint32).reshape(-1))
         pr = np.ascontiguousarray(np.asarray(priority, np.int32).reshape(-1))
         assert pi.shape == pr.shape
@@ -589,6 +633,17 @@ class Context:
         if flags is None:
             self._chk(self._lib.bs_preempt_run(self._h, stages, q, _u32p(pi), pr.ctypes.data_as(C.POINTER(C.c_int32)), gptr, victim_cap, C.byref(o)),
                       "bs_preempt_run")
+        elif gang is not None:
+            need, flat = gang
+            nptr = _u32p(need) if need is not None and need.size else None
+            i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+            if flat:
+                self._chk(self._lib.bs_preempt_commit_gang_flat(self._h, stages, q, _u32p(pi), i32p(pr), gptr, nptr, flags, victim_cap, i32p(node),
+                                                                _u32p(ncand), _u32p(nv), _u32p(vic), i32p(top), _i64p(ssum), _i64p(est)),
+                          "bs_preempt_commit_gang_flat")
+            else:
+                self._chk(self._lib.bs_preempt_commit_gang(self._h, stages, q, _u32p(pi), i32p(pr), gptr, nptr, flags, victim_cap, C.byref(o)),
+                          "bs_preempt_commit_gang")
         else:
             self._chk(self._lib.bs_preempt_commit(self._h, stages, q, _u32p(pi), pr.ctypes.data_as(C.POINTER(C.c_int32)), gptr, flags, victim_cap,
                                                   C.byref(o)), "bs_preempt_commit")

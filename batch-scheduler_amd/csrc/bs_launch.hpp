@@ -46,6 +46,10 @@ struct CompactDev;
 void launch_preempt_commit(hipStream_t stream, uint32_t S, dim3 scan_grid, const NodesDev& nd, const PodsDev& pd, const CommitDev& pe);
 void launch_preempt_apply(hipStream_t stream, uint32_t S, const NodesDev& nd, const CommitDev& pe, uint32_t ndirty, uint32_t assume, bs_node_request* reqs,
                           const CompactDev* nw);
+// bs_preempt_commit_gang's plan: k_pc_scan<S> as above, then k_gang_resolve<S> (the quorum of each gang's run, the rollback)
+struct GangDev;
+void launch_preempt_commit_gang(hipStream_t stream, uint32_t S, dim3 scan_grid, const NodesDev& nd, const PodsDev& pd, const CommitDev& pe,
+                                const GangDev& gd);
 
 // the bound table's patch (tu_preempt.hip, bs_bound_apply.hpp): k_ba_scatter<S>, k_ba_mark<S>, k_ba_boff<S> (the new CSR into nw.boff),
 // k_ba_merge<S> (one wave per node into nw; writes nothing when the error word is set)

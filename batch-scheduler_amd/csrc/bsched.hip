@@ -31,6 +31,8 @@
 #include "bs_pod_ranges.hpp"
 #include "bs_preempt.hpp"
 #include "bs_preempt_commit.hpp"
+#include "bs_preempt_commit_gang.hpp"
+#include "bs_preempt_gang_runs.hpp"
 #include "bs_preempt_geom.hpp"
 #include "bs_bound_apply.hpp"
 #include "bs_bound_nodes.hpp"
@@ -291,6 +293,10 @@ struct bs_ctx {
   uint32_t bound_ids = 0;            // the id space of bs_bound_pdb_set: entries at the last bs_bound_load plus what bs_bound_apply inserted since
   std::vector<uint32_t> pre_npv;     // PDB-violating victims per preemptor of the last preemption call (bs_preempt_pdb_read)
   bool have_pre_npv = false;
+  // bs_preempt_gang_read: slot_voided[count] / group_placed[g] of the last bs_preempt_commit_gang, while it is the last preemption call
+  std::vector<uint8_t> gang_voided;
+  std::vector<uint32_t> gang_placed;
+  bool have_gang = false;
   // resident PodDisruptionBudgets (bs_pdb.hpp): allowed[pdb_n], and the PDBs of every covered bound-pod id as a CSR by id; dropped by bs_bound_load
   bool have_pdb = false;
   uint32_t pdb_n = 0, pdb_covered = 0, pdb_members = 0;   // PDBs, ids the CSR covers, membership entries (= moff[pdb_covered])
@@ -4063,7 +4069,7 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   if (c->nranks > 1 || c->reduce_external) { c->last_error = "bs_preempt_run is single-rank only"; return BS_ERR_STATE; }
   if (c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
   if (count > BS_PREEMPT_MAX || (uint64_t)count * victim_cap > (1ull << 28)) return BS_ERR_CAPACITY;
-  if (count == 0) { c->pre_npv.clear(); c->have_pre_npv = true; return BS_OK; }
+  if (count == 0) { c->pre_npv.clear(); c->have_pre_npv = true; c->have_gang = false; return BS_OK; }
   if (!pod_index || !priority || !out->node || !out->n_victims || (victim_cap && !out->victims) || (c->G && !group_protected)) return BS_ERR_INVALID;
   if (c->bound_max_group >= (int32_t)c->G) { c->last_error = "the bound table names a group index >= the loaded group count"; return BS_ERR_INVALID; }
   const uint32_t P = c->P, N = c->N, G = c->G;
@@ -4157,6 +4163,7 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   std::memcpy(out->n_victims, rb + o_nv, nQ * 4);
   c->pre_npv.assign(reinterpret_cast<const uint32_t*>(rb + o_npv), reinterpret_cast<const uint32_t*>(rb + o_npv) + nQ);
   c->have_pre_npv = true;
+  c->have_gang = false;
   if (out->n_candidates) std::memcpy(out->n_candidates, rb + o_ncand, nQ * 4);
   if (out->top_priority) std::memcpy(out->top_priority, rb + o_top, nQ * 4);
   if (out->priority_sum) std::memcpy(out->priority_sum, rb + o_sum, nQ * 8);
@@ -4191,8 +4198,12 @@ int bs_preempt_run_flat(bs_ctx* c, uint32_t stages, uint32_t count, const uint32
 // -------------------------------------------------------------------------------------------------
 // preemption plans answered in sequence (bs_preempt_commit.hpp), applied into the resident state on request
 // -------------------------------------------------------------------------------------------------
-int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority, const uint8_t* group_protected,
-                      uint32_t flags, uint32_t victim_cap, const bs_preempt_out* out) {
+// bs_preempt_commit (gang == false: gang_need is not looked at, k_pc_resolve<S> is launched, the blob holds no gang column) and
+// bs_preempt_commit_gang (gang == true: the run check on the sorted slots, k_gang_resolve<S>).  Validation, blob, scan launch, result
+// copy and the APPLY tail are one code path.
+static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
+                               const uint8_t* group_protected, const uint32_t* gang_need, bool gang, uint32_t flags, uint32_t victim_cap,
+                               const bs_preempt_out* out) {
   if (!c || !out) return BS_ERR_INVALID;
   if (stages & ~BS_STAGE_PREFILTER) { c->last_error = "bs_preempt_commit takes BS_STAGE_PREFILTER only (the plugin's Filter takes no part)"; return BS_ERR_INVALID; }
   if (flags & ~(BS_PREEMPT_APPLY | BS_PREEMPT_ASSUME)) { c->last_error = "bs_preempt_commit: unknown flags"; return BS_ERR_INVALID; }
@@ -4204,7 +4215,14 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
   if (c->nranks > 1 || c->reduce_external) { c->last_error = "bs_preempt_commit is single-rank only"; return BS_ERR_STATE; }
   if (c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
   if (count > BS_PREEMPT_MAX || (uint64_t)count * victim_cap > (1ull << 28)) return BS_ERR_CAPACITY;
-  if (count == 0) { c->pre_npv.clear(); c->have_pre_npv = true; return BS_OK; }
+  if (gang && c->G && !gang_need) { c->last_error = "bs_preempt_commit_gang: gang_need is NULL with g > 0"; return BS_ERR_INVALID; }
+  if (count == 0) {
+    c->pre_npv.clear();
+    c->have_pre_npv = true;
+    c->have_gang = gang;
+    if (gang) { c->gang_voided.clear(); c->gang_placed.assign(c->G, 0u); }
+    return BS_OK;
+  }
   if (!pod_index || !priority || !out->node || !out->n_victims || (victim_cap && !out->victims) || (c->G && !group_protected)) return BS_ERR_INVALID;
   if (c->bound_max_group >= (int32_t)c->G) { c->last_error = "the bound table names a group index >= the loaded group count"; return BS_ERR_INVALID; }
   const uint32_t P = c->P, N = c->N, G = c->G, L = c->L, B = c->bound_b;
@@ -4218,10 +4236,29 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
   const bool apply = (flags & BS_PREEMPT_APPLY) != 0, assume = (flags & BS_PREEMPT_ASSUME) != 0;
   int rc = use_device(c);
   if (rc) return rc;
-  if (apply && (rc = settle_pending(c))) return rc;
   std::vector<uint32_t> perm(count);
   for (uint32_t i = 0; i < count; ++i) perm[i] = i;
   std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return priority[a] > priority[b]; });
+  // gang: the runs of the sorted slots (bs_preempt_gang_runs.hpp).  The pods' group column lives on the device only (bs_pods_apply patches
+  // it there), so it is read back when some group has a requirement; a second run of one group is refused before anything is launched.
+  std::vector<uint32_t> g_need, g_rlen;
+  std::vector<int32_t> sgroup;
+  if (gang) {
+    bool any = false;
+    for (uint32_t g = 0; g < G; ++g) any |= gang_need[g] != 0;
+    sgroup.assign(count, BS_POD_NOT_GROUPED);
+    if (any) {
+      std::vector<int32_t> pgroup(P);
+      HIPCHK(c, hipMemcpyAsync(pgroup.data(), pods_dev(c).group, (size_t)P * 4, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      for (uint32_t s = 0; s < count; ++s) sgroup[s] = pgroup[pod_index[perm[s]]];
+    }
+    if (gang_runs(count, sgroup.data(), G, gang_need, g_need, g_rlen) >= 0) {
+      c->last_error = "bs_preempt_commit_gang: a group with a requirement forms more than one run of slots";
+      return BS_ERR_INVALID;
+    }
+  }
+  if (apply && (rc = settle_pending(c))) return rc;
   const PreemptGeom geom = preempt_geom(N, count, c->test_pc_chunk_nodes);   // slot tiles x node chunks (bs_preempt_geom.hpp)
   const uint32_t tiles = geom.tiles, nchunks = geom.nchunks, chunk_nodes = geom.chunk_nodes;
   const size_t nQ = count, nG = std::max<uint32_t>(G, 1), nR = (size_t)nchunks * nQ, nV = std::max<size_t>((size_t)nQ * victim_cap, 1);
@@ -4231,6 +4268,9 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
   const size_t o_sprio = o; o = align256(o + nQ * 4);
   const size_t o_sorig = o; o = align256(o + nQ * 4);
   const size_t o_gprot = o; o = align256(o + nG);
+  const size_t gQ = gang ? nQ : 0, gB = gang ? nB : 0;    // gang columns: no bytes in bs_preempt_commit's blob
+  const size_t o_gneed = o; o = align256(o + gQ * 4);
+  const size_t o_grlen = o; o = align256(o + gQ * 4);
   const size_t in_bytes = o;
   const size_t o_rnode = o; o = align256(o + nR * kPcK * 4);
   const size_t o_rnv = o; o = align256(o + nR * kPcK * 4);
@@ -4246,7 +4286,11 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
   const size_t o_nbits = o; o = align256(o + nN * 4);
   const size_t o_dirty = o; o = align256(o + nN);
   const size_t o_dead = o; o = align256(o + nB);
+  const size_t o_gtag = o; o = align256(o + gB * 4);
+  const size_t o_gplaced = o; o = align256(o + gQ * 4);
+  const size_t o_gvoided = o; o = align256(o + gQ);
   const size_t work_bytes = o - o_work;
+  const size_t o_gslog = o; o = align256(o + gQ * 3 * 4);
   const size_t o_dlist = o; o = align256(o + nQ * 4);
   const size_t o_nreq = o; o = align256(o + nQ * sizeof(bs_node_request));
   const size_t o_res = o;                                 // results: one D2H
@@ -4270,6 +4314,10 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
     sorig[s] = perm[s];
   }
   if (G) std::memcpy(in.data() + o_gprot, group_protected, G);
+  if (gang) {
+    std::memcpy(in.data() + o_gneed, g_need.data(), nQ * 4);
+    std::memcpy(in.data() + o_grlen, g_rlen.data(), nQ * 4);
+  }
   uint8_t* base = c->d_pre.as<uint8_t>();
   HIPCHK(c, hipMemcpyAsync(base, in.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(base + o_work, 0, work_bytes, c->stream));
@@ -4317,10 +4365,26 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
   pe.o_est = reinterpret_cast<int64_t*>(base + o_est);
   pe.o_victims = reinterpret_cast<uint32_t*>(base + o_vic);
   const NodesDev nd = nodes_dev(c);
-  launch_preempt_commit(c->stream, c->S, dim3(tiles, nchunks), nd, pods_dev(c), pe);
+  if (gang) {
+    GangDev gd{};
+    gd.s_need = reinterpret_cast<const uint32_t*>(base + o_gneed);
+    gd.s_rlen = reinterpret_cast<const uint32_t*>(base + o_grlen);
+    gd.tag = reinterpret_cast<uint32_t*>(base + o_gtag);
+    gd.slog = reinterpret_cast<uint32_t*>(base + o_gslog);
+    gd.o_placed = reinterpret_cast<uint32_t*>(base + o_gplaced);
+    gd.o_voided = base + o_gvoided;
+    launch_preempt_commit_gang(c->stream, c->S, dim3(tiles, nchunks), nd, pods_dev(c), pe, gd);
+  } else {
+    launch_preempt_commit(c->stream, c->S, dim3(tiles, nchunks), nd, pods_dev(c), pe);
+  }
   LAUNCHCHK(c, BS_KERNEL_QUERY);
   std::vector<uint8_t> res(o - o_res);
   HIPCHK(c, hipMemcpyAsync(res.data(), base + o_res, res.size(), hipMemcpyDeviceToHost, c->stream));
+  std::vector<uint8_t> gres;                              // gang: placed by slot, then voided by preemptor (adjacent in the blob)
+  if (gang) {
+    gres.resize(o_work + work_bytes - o_gplaced);
+    HIPCHK(c, hipMemcpyAsync(gres.data(), base + o_gplaced, gres.size(), hipMemcpyDeviceToHost, c->stream));
+  }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint8_t* rb = res.data() - o_res;
   if (apply) {
@@ -4373,6 +4437,15 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
   std::memcpy(out->n_victims, rb + o_nv, nQ * 4);
   c->pre_npv.assign(reinterpret_cast<const uint32_t*>(rb + o_npv), reinterpret_cast<const uint32_t*>(rb + o_npv) + nQ);
   c->have_pre_npv = true;
+  c->have_gang = gang;
+  if (gang) {
+    const uint32_t* placed = reinterpret_cast<const uint32_t*>(gres.data());
+    const uint8_t* voided = gres.data() + (o_gvoided - o_gplaced);
+    c->gang_voided.assign(voided, voided + nQ);
+    c->gang_placed.assign(G, 0u);
+    for (uint32_t s = 0; s < count; ++s)
+      if (g_rlen[s]) c->gang_placed[sgroup[s]] = placed[s];
+  }
   if (out->n_candidates) std::memcpy(out->n_candidates, rb + o_ncand, nQ * 4);
   if (out->top_priority) std::memcpy(out->top_priority, rb + o_top, nQ * 4);
   if (out->priority_sum) std::memcpy(out->priority_sum, rb + o_sum, nQ * 8);
@@ -4386,6 +4459,28 @@ int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t
       std::memset(out->victims + q * victim_cap + k, 0, (size_t)(victim_cap - k) * 4);
     }
   }
+  return BS_OK;
+}
+
+int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority, const uint8_t* group_protected,
+                      uint32_t flags, uint32_t victim_cap, const bs_preempt_out* out) {
+  return preempt_commit_call(c, stages, count, pod_index, priority, group_protected, nullptr, false, flags, victim_cap, out);
+}
+
+int bs_preempt_commit_gang(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
+                           const uint8_t* group_protected, const uint32_t* gang_need, uint32_t flags, uint32_t victim_cap, const bs_preempt_out* out) {
+  return preempt_commit_call(c, stages, count, pod_index, priority, group_protected, gang_need, true, flags, victim_cap, out);
+}
+
+int bs_preempt_gang_read(bs_ctx* c, uint32_t count, uint8_t* slot_voided, uint32_t g, uint32_t* group_placed) {
+  if (!c) return BS_ERR_INVALID;
+  if (!c->have_gang) { c->last_error = "bs_preempt_gang_read: the last preemption call was not a successful bs_preempt_commit_gang"; return BS_ERR_STATE; }
+  if (count != c->gang_voided.size() || g != c->gang_placed.size()) {
+    c->last_error = "bs_preempt_gang_read: count or g differ from the last bs_preempt_commit_gang's";
+    return BS_ERR_INVALID;
+  }
+  if (slot_voided && count) std::memcpy(slot_voided, c->gang_voided.data(), count);
+  if (group_placed && g) std::memcpy(group_placed, c->gang_placed.data(), (size_t)g * 4);
   return BS_OK;
 }
 
@@ -4738,6 +4833,14 @@ int bs_preempt_commit_flat(bs_ctx* c, uint32_t stages, uint32_t count, const uin
                            int32_t* top_priority, int64_t* priority_sum, int64_t* earliest_start) {
   const bs_preempt_out o{node, n_candidates, n_victims, victims, top_priority, priority_sum, earliest_start};
   return bs_preempt_commit(c, stages, count, pod_index, priority, group_protected, flags, victim_cap, &o);
+}
+
+int bs_preempt_commit_gang_flat(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
+                                const uint8_t* group_protected, const uint32_t* gang_need, uint32_t flags, uint32_t victim_cap, int32_t* node,
+                                uint32_t* n_candidates, uint32_t* n_victims, uint32_t* victims, int32_t* top_priority, int64_t* priority_sum,
+                                int64_t* earliest_start) {
+  const bs_preempt_out o{node, n_candidates, n_victims, victims, top_priority, priority_sum, earliest_start};
+  return bs_preempt_commit_gang(c, stages, count, pod_index, priority, group_protected, gang_need, flags, victim_cap, &o);
 }
 
 }  // extern "C"

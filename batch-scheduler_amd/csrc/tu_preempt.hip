@@ -7,6 +7,7 @@
 #endif
 #include "bs_preempt.hpp"
 #include "bs_preempt_commit.hpp"
+#include "bs_preempt_commit_gang.hpp"
 #include "bs_bound_apply.hpp"
 #include "bs_bound_nodes.hpp"
 #include "bs_pdb.hpp"
@@ -42,6 +43,12 @@ template <int S>
 static void launch_preempt_commit_s(hipStream_t stream, dim3 scan_grid, const NodesDev& nd, const PodsDev& pd, const CommitDev& pe) {
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pc_scan<S>), scan_grid, dim3(64), 0, stream, nd, pd, pe);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pc_resolve<S>), dim3(1), dim3(pc_threads<S>()), 0, stream, nd, pd, pe);
+}
+
+template <int S>
+static void launch_preempt_commit_gang_s(hipStream_t stream, dim3 scan_grid, const NodesDev& nd, const PodsDev& pd, const CommitDev& pe, const GangDev& gd) {
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pc_scan<S>), scan_grid, dim3(64), 0, stream, nd, pd, pe);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gang_resolve<S>), dim3(1), dim3(pc_threads<S>()), 0, stream, nd, pd, pe, gd);
 }
 
 template <int S>
@@ -88,6 +95,13 @@ void launch_preempt_commit(hipStream_t stream, uint32_t S, dim3 scan_grid, const
 #define BS_PC_PLAN(s) launch_preempt_commit_s<s>(stream, scan_grid, nd, pd, pe)
   BS_PC_CASES(BS_PC_PLAN)
 #undef BS_PC_PLAN
+}
+
+void launch_preempt_commit_gang(hipStream_t stream, uint32_t S, dim3 scan_grid, const NodesDev& nd, const PodsDev& pd, const CommitDev& pe,
+                                const GangDev& gd) {
+#define BS_PC_GANG(s) launch_preempt_commit_gang_s<s>(stream, scan_grid, nd, pd, pe, gd)
+  BS_PC_CASES(BS_PC_GANG)
+#undef BS_PC_GANG
 }
 
 void launch_preempt_apply(hipStream_t stream, uint32_t S, const NodesDev& nd, const CommitDev& pe, uint32_t ndirty, uint32_t assume, bs_node_request* reqs,

@@ -186,3 +186,60 @@ func (g *gpuCore) readPDBs(nodes int) (allowed []int32, covered uint32, nodeViol
 	}
 	return allowed, uint32(cov), nodeViolating, nil
 }
+
+// gangPlan is what preemptCommitGang returns per preemptor (the caller's order) and per group.
+type gangPlan struct {
+	node        []int32  // nominated node, -1: none (also for a slot whose run was voided)
+	nVictims    []uint32 // the true victim count; victims holds min(nVictims, victimCap) ids per row
+	victims     []uint32 // [count][victimCap] bound-pod ids, zero beyond the row's count
+	slotVoided  []uint8  // 1: the preemptor had a node and lost it to its gang's quorum
+	groupPlaced []uint32 // per group: members of its run that got a node, before the decision
+}
+
+// preemptCommitGang: bs_preempt_commit_gang_flat, then bs_preempt_gang_read.  podIndex / priority list the preemptors with every gang's
+// members next to each other (equal priorities: one run of slots per gang); gangNeed[g] is how many members of group g must get a node
+// in this call (MinMember - Scheduled - the members already waiting at Permit; 0: no requirement) — a gang that misses it evicts nobody
+// and holds no room.  flags: 0 (the plan), BS_PREEMPT_APPLY, BS_PREEMPT_APPLY | BS_PREEMPT_ASSUME, as for bs_preempt_commit.
+func (g *gpuCore) preemptCommitGang(podIndex []uint32, priority []int32, groupProtected []uint8, gangNeed []uint32, flags uint32, victimCap uint32) (*gangPlan, error) {
+	count := len(podIndex)
+	if len(priority) != count || len(gangNeed) != len(groupProtected) {
+		return nil, fmt.Errorf("preemptCommitGang: %d pod indices, %d priorities; %d needs, %d groups", count, len(priority), len(gangNeed), len(groupProtected))
+	}
+	_, pPod := u32s(podIndex)
+	_, pPrio := i32s(priority)
+	_, pNeed := u32s(gangNeed)
+	prot := make([]C.uint8_t, len(groupProtected))
+	var pProt *C.uint8_t
+	for i, v := range groupProtected {
+		prot[i] = C.uint8_t(v)
+	}
+	if len(prot) > 0 {
+		pProt = &prot[0]
+	}
+	node := make([]C.int32_t, count+1)
+	nv := make([]C.uint32_t, count+1)
+	vic := make([]C.uint32_t, count*int(victimCap)+1)
+	voided := make([]C.uint8_t, count+1)
+	placed := make([]C.uint32_t, len(gangNeed)+1)
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if rc := C.bs_preempt_commit_gang_flat(g.ctx, C.BS_STAGE_PREFILTER, C.uint32_t(count), pPod, pPrio, pProt, pNeed, C.uint32_t(flags), C.uint32_t(victimCap),
+		&node[0], nil, &nv[0], &vic[0], nil, nil, nil); rc != C.BS_OK {
+		return nil, fmt.Errorf("bs_preempt_commit_gang_flat: %s (%s)", C.GoString(C.bs_strerror(rc)), C.GoString(C.bs_last_error(g.ctx)))
+	}
+	if rc := C.bs_preempt_gang_read(g.ctx, C.uint32_t(count), &voided[0], C.uint32_t(len(gangNeed)), &placed[0]); rc != C.BS_OK {
+		return nil, fmt.Errorf("bs_preempt_gang_read: %s (%s)", C.GoString(C.bs_strerror(rc)), C.GoString(C.bs_last_error(g.ctx)))
+	}
+	p := &gangPlan{node: make([]int32, count), nVictims: make([]uint32, count), victims: make([]uint32, count*int(victimCap)),
+		slotVoided: make([]uint8, count), groupPlaced: make([]uint32, len(gangNeed))}
+	for i := 0; i < count; i++ {
+		p.node[i], p.nVictims[i], p.slotVoided[i] = int32(node[i]), uint32(nv[i]), uint8(voided[i])
+	}
+	for i := range p.victims {
+		p.victims[i] = uint32(vic[i])
+	}
+	for i := range p.groupPlaced {
+		p.groupPlaced[i] = uint32(placed[i])
+	}
+	return p, nil
+}

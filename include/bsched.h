@@ -684,6 +684,43 @@ int bs_preempt_pdb_read(bs_ctx* ctx, uint32_t count, uint32_t* n_pdb_violations)
 #define BS_PREEMPT_ASSUME 2u   /* with APPLY: also add each nominee's request to its node          */
 int bs_preempt_commit(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
                       const uint8_t* group_protected, uint32_t flags, uint32_t victim_cap, const bs_preempt_out* out);
+/* ---- preemption plans that void gangs which miss their quorum ----------------------------------------------------------------
+ * bs_preempt_commit evicts for every slot that found a node.  A gang that needs 8 more members and finds room for 3 still evicts for
+ * those 3: the victims are gone, the gang cannot pass Permit's quorum (core.go:303), and the freed room is held by nominees that will
+ * never run.  bs_preempt_commit_gang takes bs_preempt_commit's arguments plus gang_need[g] (g = the loaded group count) and decides
+ * each gang's quorum inside the pass.  Everything not stated here is bs_preempt_commit's, unchanged: slot order, steps 1-6 of the
+ * search, the PDB rule, the flags, victim_cap, the errors found before any launch, what-if versus BS_PREEMPT_APPLY / BS_PREEMPT_ASSUME.
+ *   gang_need[g]  the number of members of group g that must get a node IN THIS CALL for any of them to be worth evicting for; the
+ *                 caller computes it (MinMember minus Scheduled minus the members already waiting at Permit).  0 = no requirement.
+ *                 Preemptors that are not grouped, or whose group is BS_POD_GROUP_MISSING, never have one.  May be NULL when g == 0;
+ *                 NULL with g > 0 is BS_ERR_INVALID.
+ *   run           a maximal sequence of consecutive slots, in slot order, whose pods share one group index g >= 0 with
+ *                 gang_need[g] > 0.  A group with a requirement must form exactly ONE run; a second run of the same group is
+ *                 BS_ERR_INVALID, found on the host before anything is launched.  That includes a gang whose members have different
+ *                 priorities with another preemptor's priority in between: such a gang takes need 0, or a call of its own.  (A caller
+ *                 that lists each gang's members next to each other, equal priorities together, gets one run per gang: the slot
+ *                 order is stable.)
+ *   quorum        the slots of a run are answered one after another exactly as bs_preempt_commit answers them, each seeing the
+ *                 earlier slots of the run nominated and their victims gone.  After the run's last slot, placed = the slots of the
+ *                 run that got a node.  placed >= need: the run stands.  Otherwise the run is VOIDED: the working state becomes
+ *                 exactly what it was before the run's first slot (node request deltas, scalar-key bits, the bound entries the run's
+ *                 slots evicted, the victim total), and every slot of the run that got a node reports node -1, n_victims 0, an
+ *                 all-zero victim row and pick key, n_pdb_violations 0; n_candidates keeps the count the slot saw.  Later slots are
+ *                 answered on the restored state.  Evictions ignore victim_cap in both directions: a voided slot's victims beyond the
+ *                 cap come back too.
+ *   property      the answers of the slots that are not voided, and the state BS_PREEMPT_APPLY / BS_PREEMPT_ASSUME leave, are
+ *                 bit-identical to bs_preempt_commit on the same list with the voided runs' preemptors deleted.  With every need 0
+ *                 the call is bs_preempt_commit, field for field.
+ *   errors        bs_preempt_commit's with the same codes, plus the two above; on any error nothing resident changes.  Single-rank
+ *                 only.  Synchronous.  bs_preempt_pdb_read works after this call as after the other two.
+ * bs_preempt_gang_read reads the last successful bs_preempt_commit_gang: slot_voided[q] = 1 where preemptor q (caller's order) had a
+ * node and lost it to its run's quorum; group_placed[g] = placed of the group's run before the decision, 0 for a group without a run.
+ * Either pointer may be NULL.  BS_ERR_STATE when the context's last successful preemption call was not bs_preempt_commit_gang;
+ * BS_ERR_INVALID when count or g differ from that call's. */
+int bs_preempt_commit_gang(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
+                           const uint8_t* group_protected, const uint32_t* gang_need /*[g]*/, uint32_t flags, uint32_t victim_cap,
+                           const bs_preempt_out* out);
+int bs_preempt_gang_read(bs_ctx* ctx, uint32_t count, uint8_t* slot_voided /*[count]*/, uint32_t g, uint32_t* group_placed /*[g]*/);
 /* The live bound table in table order: node ascending, importance order within a node; bs_bound_count entries.  id_out[i] = the
  * entry's id (its index at the last bs_bound_load), node_out[i] = its node.  BS_ERR_STATE before bs_bound_load; the arrays may be NULL
  * when the table is empty. */
@@ -948,6 +985,11 @@ int bs_bound_apply_ex_flat(bs_ctx* ctx, uint32_t flags, uint32_t n_remove, const
 int bs_preempt_commit_flat(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
                            const uint8_t* group_protected, uint32_t flags, uint32_t victim_cap, int32_t* node, uint32_t* n_candidates,
                            uint32_t* n_victims, uint32_t* victims, int32_t* top_priority, int64_t* priority_sum, int64_t* earliest_start);
+/* bs_preempt_commit_gang (bs_preempt_out's arrays one by one) */
+int bs_preempt_commit_gang_flat(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
+                                const uint8_t* group_protected, const uint32_t* gang_need, uint32_t flags, uint32_t victim_cap,
+                                int32_t* node, uint32_t* n_candidates, uint32_t* n_victims, uint32_t* victims, int32_t* top_priority,
+                                int64_t* priority_sum, int64_t* earliest_start);
 
 /* ---- measurement ------------------------------------------------------------------ */
 #define BS_KERNEL_PREPASS   0u

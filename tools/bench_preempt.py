@@ -13,7 +13,10 @@ K inserts: table and node requests in one call) against the sequence it replaces
 request vectors of the touched nodes computed on the host (numpy, from a host copy of the entries' requests), bs_bound_apply, then
 bs_nodes_assume; the three parts are also reported on their own.  --pdb-resident times one bs_pdb_allowed_apply of 8 indices (64 resident
 PDBs, the bits recomputed on the device) and, in the same process, the path it replaces, its two parts reported separately:
-pdb.violating_bits over string records of every bound pod, then bs_bound_pdb_set."""
+pdb.violating_bits over string records of every bound pod, then bs_bound_pdb_set.  --gang FRACTION times bs_preempt_commit_gang (plan only)
+on cfg3 at 64 and 1024 preemptors listed in gang_order, with every need 0 and with needs drawn so that FRACTION of the runs that place
+a member miss their quorum by one (a run that places nobody misses its need of 1 anyway; the row reports the runs that missed in all), beside bs_preempt_commit on the same list in the same process: the plain call five times over (median of --reps calls
+each; their spread is the yardstick's noise), the three calls taking turns."""
 from __future__ import annotations
 
 import argparse
@@ -338,6 +341,62 @@ def pdb_resident_rows(config: str, reps: int, warmup: int, host_reps: int = 2) -
                  pdb_set_over_allowed_apply=round(med(t_set) / med(t_apply), 2))]
 
 
+def gang_rows(config: str, q: int, fraction: float, reps: int, warmup: int) -> list:
+    capi = bsa.capi
+    cfg = synth.CONFIGS[config]
+    n, S = cfg["nodes"], cfg["scalars"]
+    bound, nodes = synth.make_bound(20260921, n, cfg["groups"], (20, 110), S)
+    fit = synth.make_fit(20260921, n, cfg["classes"])
+    pods, _, prio = synth.make_preemptors(20260921, q, 4096, cfg["groups"], S, cfg["classes"])
+    rng = np.random.default_rng(20260921)
+    pidx = rng.permutation(4096)[:q].astype(np.uint32)
+    grp = np.asarray(pods.group)[pidx].astype(np.int64)
+    prio = prio.astype(np.int64)
+    for g in np.unique(grp[grp >= 0]):                         # one priority a gang: gang_order then makes it one run
+        prio[grp == g] = prio[grp == g][0]
+    o = capi.gang_order(grp, prio)
+    pidx, prio, grp = pidx[o], prio[o].astype(np.int32), grp[o]
+    groups = soa.Groups.empty(cfg["groups"], 4 + S)
+    prot = (synth.Stream(20260921, 99).uniform(cfg["groups"]) < 0.3).astype(np.uint8)
+    zero = np.zeros(cfg["groups"], np.uint32)
+    with bsa.Context(scalar_lanes=S, device=0) as ctx:
+        ctx.load_nodes(nodes, fit)
+        ctx.load_groups(groups)
+        ctx.load_pods(pods)
+        ctx.load_bound(bound)
+        # what each gang places when every run stands; a share of the gangs that place something then ask for one more than that
+        one_each = np.zeros(cfg["groups"], np.uint32)
+        one_each[np.unique(grp[grp >= 0])] = 1
+        placed = ctx.preempt_commit_gang(pidx, prio, prot, one_each, victim_cap=16)["group_placed"]
+        can = np.nonzero(placed > 0)[0]
+        miss = can[rng.random(can.size) < fraction]
+        need = np.where(one_each > 0, np.maximum(placed, 1), 0).astype(np.uint32)
+        need[miss] = placed[miss] + 1
+        calls = dict(plain=lambda: ctx.preempt_commit(pidx, prio, prot, victim_cap=16),
+                     gang0=lambda: ctx.preempt_commit_gang(pidx, prio, prot, zero, victim_cap=16),
+                     gang=lambda: ctx.preempt_commit_gang(pidx, prio, prot, need, victim_cap=16))
+        ts = {k: [] for k in calls}
+        for it in range(warmup + 5 * reps):                    # the three take turns; the plain call's samples are cut into five repeats
+            for k, fn in calls.items():
+                if k != "plain" and it >= warmup + reps:
+                    continue
+                t0 = time.perf_counter()
+                r = fn()
+                if it >= warmup:
+                    ts[k].append((time.perf_counter() - t0) * 1e3)
+                if k == "gang":
+                    last = r
+        r = last
+        runs = int((need > 0).sum())
+        missed = int(((need > 0) & (r["group_placed"] < need)).sum())
+        voided = int(r["slot_voided"].sum())
+    five = [float(np.median(ts["plain"][i * reps:(i + 1) * reps])) for i in range(5)]
+    plain, g0, g1 = float(np.median(five)), float(np.median(ts["gang0"])), float(np.median(ts["gang"]))
+    return [dict(config=config, nodes=n, bound=int(bound.b), preemptors=q, runs=runs, missed_runs=missed, voided_slots=voided, fraction=fraction,
+                 plain_ms=round(plain, 4), plain_five=[round(x, 4) for x in five], plain_spread_ms=round(max(five) - min(five), 4),
+                 gang_need0_ms=round(g0, 4), gang_ms=round(g1, 4), need0_over_plain=round(g0 / plain, 4), gang_over_plain=round(g1 / plain, 4))]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -349,7 +408,13 @@ def main():
     ap.add_argument("--bound-nodes", type=int, default=None, metavar="K", help="bs_bound_apply_ex(BS_BOUND_NODES) with K removes + K inserts, vs bs_bound_apply + "
                     "bs_nodes_assume with the vectors computed on the host")
     ap.add_argument("--pdb-resident", action="store_true", help="bs_pdb_allowed_apply of 8 indices, vs pdb.violating_bits + bs_bound_pdb_set")
+    ap.add_argument("--gang", type=float, default=None, metavar="FRACTION", help="bs_preempt_commit_gang on cfg3 (need 0, and FRACTION of the runs missing "
+                    "their quorum) beside bs_preempt_commit")
     a = ap.parse_args()
+    if a.gang is not None:
+        rows = [r for q in (64, 1024) for r in gang_rows("cfg3", q, a.gang, a.reps, a.warmup)]
+        print(json.dumps(dict(metric="bs_preempt_commit_gang ms per call", rows=rows)))
+        return
     if a.pdb_resident:
         rows = [r for c in ("cfg3", "cfg4") for r in pdb_resident_rows(c, a.reps, a.warmup)]
         print(json.dumps(dict(metric="bs_pdb_allowed_apply ms per call", rows=rows)))
