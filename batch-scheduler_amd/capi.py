@@ -40,7 +40,10 @@ ABI_SYMBOLS = [
     "bs_bound_apply_ex", "bs_bound_apply_ex_flat",
     "bs_pdb_load", "bs_pdb_members_append", "bs_pdb_allowed_apply", "bs_pdb_read",
     "bs_preempt_commit_gang", "bs_preempt_commit_gang_flat", "bs_preempt_gang_read",
+    "bs_seq_expire", "bs_seq_expire_flat", "bs_seq_waiting_read",
 ]
+
+SEQ_EXPIRE_DENY, SEQ_EXPIRE_ALL = 1, 2    # bs_seq_expire flags
 
 BS_BOUND_NODES = soa.BS_BOUND_NODES     # bs_bound_apply_ex: the delta also moves the node requests
 
@@ -123,6 +126,13 @@ class SeqOut(C.Structure):
                 ("n_released", C.c_uint32), ("total_ns", C.c_int64), ("node_picks", C.c_uint64), ("node_scans", C.c_uint64),
                 ("scan_rounds", C.c_uint64), ("pick_rounds", C.c_uint64), ("leader_folds", C.c_uint64), ("table_builds", C.c_uint64),
                 ("last_permitted", C.POINTER(C.c_uint8))]
+
+
+class SeqExpireOut(C.Structure):
+    """bs_seq_expire_out"""
+    _fields_ = [("n_groups", C.c_uint32), ("n_pods", C.c_uint32), ("group_cap", C.c_uint32), ("group", C.POINTER(C.c_uint32)),
+                ("group_pods", C.POINTER(C.c_uint32)), ("group_earlier", C.POINTER(C.c_uint32)), ("pod_cap", C.c_uint32),
+                ("pod", C.POINTER(C.c_uint32)), ("node", C.POINTER(C.c_uint32))]
 
 
 _lib = None
@@ -219,6 +229,9 @@ def load_library(path: str | None = None):
     L.bs_preempt_commit_gang_flat.argtypes = [vp, u32, u32, P(u32), P(i32), P(u8), P(u32), u32, u32, P(i32), P(u32), P(u32), P(u32), P(i32),
                                               P(C.c_int64), P(C.c_int64)]
     L.bs_preempt_gang_read.argtypes = [vp, u32, P(u8), u32, P(u32)]
+    L.bs_seq_expire.argtypes = [vp, u32, P(u32), u32, P(SeqExpireOut)]
+    L.bs_seq_expire_flat.argtypes = [vp, u32, P(u32), u32, u32, P(u32), P(u32), P(u32), u32, P(u32), P(u32), P(u32)]
+    L.bs_seq_waiting_read.argtypes = [vp, u32, P(i32)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:
@@ -554,6 +567,39 @@ class Context:
         return dict(pf_code=pf[:p], pf_first_k=fk[:p], pf_leader=ld[:p], pod_node=node[:p], last_permitted=lp[:p], released_group=rg[:k], released_pods=rp[:k],
                     first_ns=t0[:k], ready_ns=t1[:k], n_released=int(o.n_released), total_ns=int(o.total_ns), node_picks=int(o.node_picks),
                     node_scans=int(o.node_scans), scan_rounds=int(o.scan_rounds), pick_rounds=int(o.pick_rounds), leader_folds=int(o.leader_folds), table_builds=int(o.table_builds))
+
+    def seq_expire(self, groups=None, deny: bool = False, all: bool = False, group_cap: int | None = None, pod_cap: int | None = None,
+                   flat: bool = False, flags: int | None = None) -> dict:
+        """bs_seq_expire: the Permit timeout of the listed gangs (all=True: of every gang with waiting pods) — their waiting pods of the
+        last seq_run leave their nodes, matched returns to 0, deny=True deny-lists the groups.  Returns n_groups, n_pods (true counts) and
+        group, group_pods, group_earlier, pod, node (at most group_cap / pod_cap rows; the defaults hold everything).  flags overrides
+        the flag word built from deny / all; flat=True goes through bs_seq_expire_flat."""
+        gl = None if groups is None else np.ascontiguousarray(np.asarray(groups, np.uint32).reshape(-1))
+        fl = ((SEQ_EXPIRE_DENY if deny else 0) | (SEQ_EXPIRE_ALL if all else 0)) if flags is None else int(flags)
+        gcap = (self.g if gl is None else int(gl.size)) if group_cap is None else int(group_cap)
+        pcap = self.pods_count() if pod_cap is None else int(pod_cap)
+        g, gp, ge = (np.zeros(max(gcap, 1), np.uint32) for _ in range(3))
+        pod, node = np.zeros(max(pcap, 1), np.uint32), np.zeros(max(pcap, 1), np.uint32)
+        count = 0 if gl is None else int(gl.size)
+        gptr = None if gl is None else _u32p(gl if gl.size else np.zeros(1, np.uint32))
+        if flat:
+            cnt = np.zeros(2, np.uint32)
+            self._chk(self._lib.bs_seq_expire_flat(self._h, count, gptr, fl, gcap, _u32p(g), _u32p(gp), _u32p(ge), pcap, _u32p(pod), _u32p(node), _u32p(cnt)),
+                      "bs_seq_expire_flat")
+            ng, npods = int(cnt[0]), int(cnt[1])
+        else:
+            o = SeqExpireOut(0, 0, gcap, _u32p(g), _u32p(gp), _u32p(ge), pcap, _u32p(pod), _u32p(node))
+            self._chk(self._lib.bs_seq_expire(self._h, count, gptr, fl, C.byref(o)), "bs_seq_expire")
+            ng, npods = int(o.n_groups), int(o.n_pods)
+        kg, kp = min(ng, gcap), min(npods, pcap)
+        return dict(n_groups=ng, n_pods=npods, group=g[:kg], group_pods=gp[:kg], group_earlier=ge[:kg], pod=pod[:kp], node=node[:kp])
+
+    def seq_waiting_read(self) -> np.ndarray:
+        """bs_seq_waiting_read: per queue pod the node it still waits on after the last seq_run (and the expires since), else -1"""
+        p = self.pods_count()
+        wn = np.full(max(p, 1), -1, np.int32)
+        self._chk(self._lib.bs_seq_waiting_read(self._h, p, wn.ctypes.data_as(C.POINTER(C.c_int32))), "bs_seq_waiting_read")
+        return wn[:p]
 
     def read_node_requests(self):
         """bs_nodes_read: (requested [L][n], requested_present [n]) as the context holds them"""

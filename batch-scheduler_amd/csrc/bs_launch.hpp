@@ -35,6 +35,13 @@ struct SeqDev;
 struct SeqParams;
 void launch_seq(hipStream_t stream, uint32_t S, size_t lds, const PodsDev& pd, const GroupsDev& gr, const NodesDev& nd, const SeqDev& sq, const SeqParams& prm);
 
+// the Permit timeout (tu_seq_expire.hip, bs_seq_expire.hpp): k_se_scan1 + k_se_scan2 (counts, row offsets, the kept groups), k_se_walk (the rows),
+// k_se_sum<S> + k_se_nodes<S> (up to rec_cap bs_node_request records for k_nodes_assume, counted in a.info[2]), k_se_groups; nothing when the
+// call has no entries.  launch_seq_waiting: k_se_walk in its bs_seq_waiting_read form (wait_node pre-filled with -1)
+struct SeqExpireDev;
+void launch_seq_expire(hipStream_t stream, uint32_t S, const SeqExpireDev& a, const PodsDev& pd, const NodesDev& nd, bs_node_request* recs, uint32_t rec_cap);
+void launch_seq_waiting(hipStream_t stream, const SeqExpireDev& a, int32_t* wait_node);
+
 // the preemption victim search (tu_preempt.hip): k_preempt_scan<S> over scan_grid, then k_preempt_pick<S>, one wave per preemptor
 struct PreemptDev;
 void launch_preempt(hipStream_t stream, uint32_t S, dim3 scan_grid, const NodesDev& nd, const PodsDev& pd, const PreemptDev& pe);

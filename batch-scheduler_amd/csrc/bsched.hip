@@ -26,6 +26,8 @@
 #include "bs_queue.hpp"
 #include "bs_fdeny.hpp"
 #include "bs_seq.hpp"
+#include "bs_seq_expire.hpp"
+#include "bs_seq_expire_list.hpp"
 #include "bs_launch.hpp"
 #include "bs_hostmem.hpp"
 #include "bs_pod_ranges.hpp"
@@ -41,6 +43,7 @@
 #ifdef BS_UNITY   // one translation unit (the probe builds: g_probe / g_seq_scan_ph are per translation unit)
 #include "tu_fast.hip"
 #include "tu_seq.hip"
+#include "tu_seq_expire.hip"
 #include "tu_preempt.hip"
 #endif
 
@@ -201,6 +204,14 @@ struct bs_ctx {
   // single-query scratch
   DevBuf d_sq;
   DevBuf d_seq;                      // bs_seq_run: scaled allocatables, keys, per-gang / per-pod bookkeeping, results
+  // bs_seq_expire / bs_seq_waiting_read: the waiting state the last pass left in d_seq (chains, heads, counts) is valid from a successful
+  // bs_seq_run until the first call that renumbers what it indexes (queue loads / patches, node loads / APPEND / REMOVE, group loads)
+  bool seq_wait_valid = false;
+  size_t seq_o_wait = 0, seq_o_head = 0, seq_o_nwait = 0;
+  DevBuf d_sexp;                     // per-call scratch: block totals, slots, rows, dirty list, records
+  DevBuf d_sexp_nodes;               // per-node delta [L][N], key bits, dirty words: zero between calls (k_se_nodes re-zeroes what it read)
+  uint32_t sexp_n = 0, sexp_l = 0;   // the layout d_sexp_nodes was zeroed for
+  bool sexp_clean = false;
   uint32_t table_slots = 0, table_mcap = 0;
 
   uint32_t rank = 0, nranks = 1;
@@ -1154,6 +1165,7 @@ int bs_destroy(bs_ctx* c) {
 }
 
 int bs_nodes_load(bs_ctx* c, const bs_nodes_soa* nodes) {
+  if (c) c->seq_wait_valid = false;                 // node indices are renumbered
   if (!c || !nodes) return BS_ERR_INVALID;
   int rc = use_device(c);
   if (rc) return rc;
@@ -1321,6 +1333,7 @@ int bs_fit_read(bs_ctx* c, uint32_t* out) {
 
 int bs_groups_load(bs_ctx* c, const bs_groups_soa* g) {
   if (!c || !g) return BS_ERR_INVALID;
+  c->seq_wait_valid = false;                        // group indices are renumbered
   int rc = use_device(c);
   if (rc) return rc;
   if ((rc = settle_pending(c))) return rc;
@@ -1508,6 +1521,7 @@ static int load_pod_ranges(bs_ctx* c, const int32_t* group, uint32_t P) {
 }
 
 int bs_pods_load(bs_ctx* c, const bs_pods_soa* pods) {
+  if (c) c->seq_wait_valid = false;                 // pod indices are renumbered, request lanes change
   if (!c || !pods) return BS_ERR_INVALID;
   int rc = use_device(c);
   if (rc) return rc;
@@ -1644,6 +1658,7 @@ int bs_pods_read(bs_ctx* c, const bs_pods_out* out) {
 }
 
 int bs_pods_apply(bs_ctx* c, const bs_pods_delta* d) {
+  if (c) c->seq_wait_valid = false;                 // pod indices are renumbered, request lanes change
   if (!c || !d) return BS_ERR_INVALID;
   if (!c->have_pods) { c->last_error = "bs_pods_apply before bs_pods_load"; return BS_ERR_STATE; }
   c->ranges_valid = false;                           // positions move on the device: 256 pods per block until the next bs_pods_load
@@ -3245,6 +3260,8 @@ int bs_filter_one(bs_ctx* c, int32_t pod_group, const int64_t* pod_req, uint32_t
 int bs_nodes_apply(bs_ctx* c, const bs_node_delta* deltas, uint32_t count) {
   if (!c || (count && !deltas)) return BS_ERR_INVALID;
   if (!c->have_nodes || !c->have_fit) return BS_ERR_STATE;
+  for (uint32_t d = 0; d < count; ++d)
+    if (deltas[d].kind != BS_DELTA_UPDATE) c->seq_wait_valid = false;   // APPEND / REMOVE renumber the node list (an UPDATE commutes with bs_seq_expire's delta)
   int rc = use_device(c);
   if (rc) return rc;
   if ((rc = settle_pending(c))) return rc;
@@ -3388,6 +3405,7 @@ int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
     return BS_ERR_INVALID;
   }
   if (G > 0x7FFFFFF0u) return BS_ERR_CAPACITY;
+  c->seq_wait_valid = false;                                // the pass replaces the waiting state
   // the first-fit cursors are keyed by the resident queue's request classes: a queue patch whose insert wave ran out of class ids
   // (h_info[13], set by the device) left them unusable until the queue is re-derived — check_handover does that
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3559,6 +3577,173 @@ int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
     if ((rc = analyse_groups(c))) return rc;
     if ((rc = maybe_analyse_epochs(c))) return rc;
   }
+  c->seq_o_wait = o_wait;
+  c->seq_o_head = o_head;
+  c->seq_o_nwait = o_nwait;
+  c->seq_wait_valid = true;
+  return BS_OK;
+}
+
+// -------------------------------------------------------------------------------------------------
+// the Permit timeout (bs_seq_expire.hpp): the waiting gangs of the last pass leave their nodes and their groups on the device
+// -------------------------------------------------------------------------------------------------
+static int seq_wait_state(bs_ctx* c, const char* who) {
+  if (c->nranks > 1 || c->reduce_external) { c->last_error = std::string(who) + " is single-rank only (as bs_seq_run)"; return BS_ERR_STATE; }
+  if (!c->seq_wait_valid || !c->have_nodes || !c->have_groups || !c->have_pods) {
+    c->last_error = std::string(who) + ": no valid waiting state (needs a successful bs_seq_run with no queue / node-list / group load or renumbering since)";
+    return BS_ERR_STATE;
+  }
+  return BS_OK;
+}
+
+static SeqExpireDev seq_expire_dev(bs_ctx* c) {
+  SeqExpireDev a{};
+  uint8_t* base = c->d_seq.as<uint8_t>();
+  const GroupsDev gr = groups_dev(c);
+  a.wait_rec = reinterpret_cast<const unsigned long long*>(base + c->seq_o_wait);
+  a.head = reinterpret_cast<uint32_t*>(base + c->seq_o_head);
+  a.nwait = reinterpret_cast<uint32_t*>(base + c->seq_o_nwait);
+  a.P = c->P;
+  a.G = c->G;
+  a.g_matched = const_cast<uint32_t*>(gr.matched);
+  a.g_flags = const_cast<uint8_t*>(gr.flags);
+  a.N = c->N;
+  return a;
+}
+
+int bs_seq_expire(bs_ctx* c, uint32_t count, const uint32_t* group, uint32_t flags, bs_seq_expire_out* out) {
+  if (!c || !out) return BS_ERR_INVALID;
+  if ((out->group_cap && (!out->group || !out->group_pods || !out->group_earlier)) || (out->pod_cap && (!out->pod || !out->node))) {
+    c->last_error = "bs_seq_expire: a result array is NULL with a capacity above 0";
+    return BS_ERR_INVALID;
+  }
+  int rc = seq_wait_state(c, "bs_seq_expire");
+  if (rc) return rc;
+  if (const int bad = seq_expire_list_check(c->G, count, group, flags)) { c->last_error = seq_expire_list_text(bad); return BS_ERR_INVALID; }
+  if ((rc = use_device(c))) return rc;
+  if ((rc = settle_pending(c))) return rc;
+  out->n_groups = out->n_pods = 0;
+  const bool all = (flags & BS_SEQ_EXPIRE_ALL) != 0, deny = (flags & BS_SEQ_EXPIRE_DENY) != 0;
+  const uint32_t P = c->P, G = c->G, N = c->N, L = c->L;
+  const uint32_t M = all ? G : count;
+  if (!M) return BS_OK;
+  const uint32_t rec_cap = std::min(N, P), nblk = cdiv(M, kSeBlock);
+  // ---- the per-node scratch: zero between calls
+  {
+    const size_t bytes = align256((size_t)std::max<uint32_t>(N, 1) * L * 8) + 2 * align256((size_t)std::max<uint32_t>(N, 1) * 4);
+    const void* was = c->d_sexp_nodes.p;
+    HIPCHK(c, c->d_sexp_nodes.reserve(bytes));
+    if (!c->sexp_clean || was != c->d_sexp_nodes.p || c->sexp_n != N || c->sexp_l != L) {
+      HIPCHK(c, hipMemsetAsync(c->d_sexp_nodes.p, 0, bytes, c->stream));
+      c->sexp_n = N;
+      c->sexp_l = L;
+    }
+    c->sexp_clean = false;                                   // until this call's k_se_nodes is known to have run
+  }
+  size_t o = 0;
+  const size_t o_info = o; o = align256(o + 16);
+  const size_t o_list = o; o = align256(o + (size_t)M * 4);
+  const size_t o_bsum = o; o = align256(o + (size_t)nblk * 8);
+  const size_t o_group = o; o = align256(o + (size_t)M * 4);
+  const size_t o_gpods = o; o = align256(o + (size_t)M * 4);
+  const size_t o_gearl = o; o = align256(o + (size_t)M * 4);
+  const size_t o_off = o; o = align256(o + (size_t)M * 4);
+  const size_t o_pod = o; o = align256(o + (size_t)std::max<uint32_t>(P, 1) * 4);
+  const size_t o_node = o; o = align256(o + (size_t)std::max<uint32_t>(P, 1) * 4);
+  const size_t o_dlist = o; o = align256(o + (size_t)std::max<uint32_t>(rec_cap, 1) * 4);
+  const size_t o_rec = o; o = align256(o + (size_t)std::max<uint32_t>(rec_cap, 1) * sizeof(bs_node_request));
+  HIPCHK(c, c->d_sexp.reserve(o));
+  uint8_t* base = c->d_sexp.as<uint8_t>();
+  uint8_t* nb = c->d_sexp_nodes.as<uint8_t>();
+  SeqExpireDev a = seq_expire_dev(c);
+  a.M = M;
+  a.deny = deny ? 1u : 0u;
+  a.list = all ? nullptr : reinterpret_cast<const uint32_t*>(base + o_list);
+  a.bsum = reinterpret_cast<unsigned long long*>(base + o_bsum);
+  a.info = reinterpret_cast<uint32_t*>(base + o_info);
+  a.o_group = reinterpret_cast<uint32_t*>(base + o_group);
+  a.o_gpods = reinterpret_cast<uint32_t*>(base + o_gpods);
+  a.o_gearlier = reinterpret_cast<uint32_t*>(base + o_gearl);
+  a.o_off = reinterpret_cast<uint32_t*>(base + o_off);
+  a.o_pod = reinterpret_cast<uint32_t*>(base + o_pod);
+  a.o_node = reinterpret_cast<uint32_t*>(base + o_node);
+  a.dlist = reinterpret_cast<uint32_t*>(base + o_dlist);
+  a.delta = reinterpret_cast<unsigned long long*>(nb);
+  a.nbits = reinterpret_cast<uint32_t*>(nb + align256((size_t)std::max<uint32_t>(N, 1) * L * 8));
+  a.dirty = reinterpret_cast<uint32_t*>(nb + align256((size_t)std::max<uint32_t>(N, 1) * L * 8) + align256((size_t)std::max<uint32_t>(N, 1) * 4));
+  bs_node_request* recs = reinterpret_cast<bs_node_request*>(base + o_rec);
+  HIPCHK(c, hipMemsetAsync(base + o_info, 0, 16, c->stream));
+  if (!all) HIPCHK(c, hipMemcpyAsync(base + o_list, group, (size_t)M * 4, hipMemcpyHostToDevice, c->stream));
+  c->first_reach_hint = 0xFFFFFFFFu;                        // (as bs_groups_apply: deny entries decide which pod reaches findMaxPG first)
+  launch_seq_expire(c->stream, c->S, a, pods_dev(c), nodes_dev(c), recs, rec_cap);
+  LAUNCHCHK(c, BS_KERNEL_PREPASS);
+  uint32_t info[4] = {0, 0, 0, 0};
+  HIPCHK(c, hipMemcpyAsync(info, base + o_info, 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint32_t ng = info[0], np = info[1], nrec = info[2];
+  if (ng > M || np > P || nrec > rec_cap) { c->last_error = "bs_seq_expire: the waiting chains name more than the queue holds"; return BS_ERR_HIP; }
+  c->sexp_clean = true;
+  // ---- the node requests: k_nodes_assume over the records, the host mirror from their copy (as BS_PREEMPT_APPLY and bs_bound_apply_ex)
+  std::vector<uint8_t> hr((size_t)nrec * sizeof(bs_node_request));
+  std::vector<uint32_t> hg;
+  if (nrec) {
+    static_assert(sizeof(bs_node_request) == sizeof(NodeRequest), "node request layout");
+    hipLaunchKernelGGL(k_nodes_assume, dim3(cdiv(nrec, 256)), dim3(256), 0, c->stream, reinterpret_cast<const NodeRequest*>(recs), nrec, L, c->Ncap,
+                       c->d_alloc.as<int64_t>(), c->d_nreq.as<int64_t>(), c->d_rpres.as<uint32_t>(), c->d_nflags.as<uint8_t>(), c->d_left4.as<int64_t>(),
+                       c->d_lglob.as<int64_t>());
+    LAUNCHCHK(c, BS_KERNEL_PREPASS);
+    HIPCHK(c, hipMemcpyAsync(hr.data(), recs, hr.size(), hipMemcpyDeviceToHost, c->stream));
+    c->bitmap_valid = false;
+  }
+  const uint32_t kg = std::min(ng, out->group_cap), kp = std::min(np, out->pod_cap);
+  if (kg) {
+    HIPCHK(c, hipMemcpyAsync(out->group, base + o_group, (size_t)kg * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->group_pods, base + o_gpods, (size_t)kg * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->group_earlier, base + o_gearl, (size_t)kg * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (kp) {
+    HIPCHK(c, hipMemcpyAsync(out->pod, base + o_pod, (size_t)kp * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->node, base + o_node, (size_t)kp * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (deny && all && ng) {
+    hg.resize(ng);
+    HIPCHK(c, hipMemcpyAsync(hg.data(), base + o_group, (size_t)ng * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const bs_node_request* hrec = reinterpret_cast<const bs_node_request*>(hr.data());
+  for (uint32_t i = 0; i < nrec; ++i) {                     // the host mirror a later bs_nodes_apply starts from
+    const bs_node_request& r = hrec[i];
+    for (uint32_t j = 0; j < L; ++j) c->h_nreq[(size_t)j * N + r.index] = r.requested[j];
+    c->h_rpres[r.index] = r.requested_present;
+  }
+  if (deny) {
+    const uint32_t* gl = all ? hg.data() : group;
+    for (uint32_t i = 0; i < ng; ++i) c->h_gflags[gl[i]] |= (uint8_t)BS_GROUP_DENIED;
+  }
+  out->n_groups = ng;
+  out->n_pods = np;
+  // findMaxPG, the steady table and the epoch analysis follow the group words as after a bs_groups_apply of these values
+  if (ng) {
+    if ((rc = analyse_groups(c, false))) return rc;
+    if ((rc = maybe_analyse_epochs(c))) return rc;
+  }
+  return BS_OK;
+}
+
+int bs_seq_waiting_read(bs_ctx* c, uint32_t p, int32_t* wait_node) {
+  if (!c || (p && !wait_node)) return BS_ERR_INVALID;
+  int rc = seq_wait_state(c, "bs_seq_waiting_read");
+  if (rc) return rc;
+  if (p != c->P) { c->last_error = "bs_seq_waiting_read: p differs from the queue length"; return BS_ERR_INVALID; }
+  if ((rc = use_device(c))) return rc;
+  if (!p) return BS_OK;
+  HIPCHK(c, c->d_sexp.reserve(align256((size_t)p * 4)));
+  int32_t* wn = c->d_sexp.as<int32_t>();
+  HIPCHK(c, hipMemsetAsync(wn, 0xFF, (size_t)p * 4, c->stream));
+  launch_seq_waiting(c->stream, seq_expire_dev(c), wn);
+  LAUNCHCHK(c, BS_KERNEL_PREPASS);
+  HIPCHK(c, hipMemcpyAsync(wait_node, wn, (size_t)p * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return BS_OK;
 }
 
@@ -3633,6 +3818,18 @@ int bs_seq_run_flat(bs_ctx* c, uint32_t stages, uint8_t* pf_code, uint32_t* pf_f
   }
   return rc;
 }
+int bs_seq_expire_flat(bs_ctx* c, uint32_t count, const uint32_t* group, uint32_t flags, uint32_t group_cap, uint32_t* group_out, uint32_t* group_pods,
+                       uint32_t* group_earlier, uint32_t pod_cap, uint32_t* pod, uint32_t* node, uint32_t* counts_out) {
+  if (!counts_out) return BS_ERR_INVALID;
+  bs_seq_expire_out o{};
+  o.group_cap = group_cap; o.group = group_out; o.group_pods = group_pods; o.group_earlier = group_earlier;
+  o.pod_cap = pod_cap; o.pod = pod; o.node = node;
+  const int rc = bs_seq_expire(c, count, group, flags, &o);
+  counts_out[0] = o.n_groups;
+  counts_out[1] = o.n_pods;
+  return rc;
+}
+
 int bs_fit_build_flat(bs_ctx* c, uint32_t n, const uint32_t* name, const uint32_t* label_off, const uint32_t* label_key, const uint32_t* label_val,
                       const int64_t* label_int, const uint8_t* label_int_ok, const uint32_t* taint_off, const uint32_t* taint_key, const uint32_t* taint_val,
                       const uint8_t* taint_effect, uint32_t cn, uint32_t field_name_key, const uint8_t* tpl_flags, const uint32_t* sel_off,

@@ -243,3 +243,55 @@ func (g *gpuCore) preemptCommitGang(podIndex []uint32, priority []int32, groupPr
 	}
 	return p, nil
 }
+
+// expiredGangs is what expireGangs returns: per expired group and per forgotten pod, in the library's fixed order (groups in the caller's
+// order, or ascending in ALL mode; inside a group the pods in ascending queue index).
+type expiredGangs struct {
+	group        []uint32 // the expired groups
+	groupPods    []uint32 // waiting pods of the last pass forgotten for the group
+	groupEarlier []uint32 // MatchedPodNodes entries of earlier cycles (no queue index): the shim takes those off their nodes itself
+	pod          []uint32 // queue index of each forgotten pod
+	node         []uint32 // the node it had been assumed on
+}
+
+// expireGangs: bs_seq_expire_flat — the shim's OnEvicted hook (controller.go:322-332) for the gangs whose PodNameUIDs entry ran out since
+// the last seqPass: their waiting pods leave the nodes they were assumed on, matched returns to 0, and with deny the groups go onto the
+// deny list (addToBackOff).  groups == nil with all: every gang that still has waiting pods.  P and G are the queue length and the group
+// count of that pass (the result arrays' capacities).  It lives here and not beside seqPass in bsched_batch.go: the C11 client test
+// requires go/c11_client/shim_client.c to call whatever that file calls.
+func (g *gpuCore) expireGangs(groups []uint32, deny, all bool, P, G int) (*expiredGangs, error) {
+	var flags C.uint32_t
+	if deny {
+		flags |= C.BS_SEQ_EXPIRE_DENY
+	}
+	var none C.uint32_t
+	list, pList := u32s(groups)
+	if all {
+		flags |= C.BS_SEQ_EXPIRE_ALL
+		list, pList = nil, nil
+	} else if len(list) == 0 {
+		pList = &none // an empty list is not NULL
+	}
+	gcap := len(list)
+	if all {
+		gcap = G
+	}
+	og, ogp, oge := make([]C.uint32_t, gcap+1), make([]C.uint32_t, gcap+1), make([]C.uint32_t, gcap+1)
+	op, on := make([]C.uint32_t, P+1), make([]C.uint32_t, P+1)
+	var counts [2]C.uint32_t
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if rc := C.bs_seq_expire_flat(g.ctx, C.uint32_t(len(list)), pList, flags, C.uint32_t(gcap), &og[0], &ogp[0], &oge[0], C.uint32_t(P), &op[0], &on[0],
+		&counts[0]); rc != C.BS_OK {
+		return nil, fmt.Errorf("bs_seq_expire_flat: %s (%s)", C.GoString(C.bs_strerror(rc)), C.GoString(C.bs_last_error(g.ctx)))
+	}
+	ng, np := int(counts[0]), int(counts[1])
+	e := &expiredGangs{group: make([]uint32, ng), groupPods: make([]uint32, ng), groupEarlier: make([]uint32, ng), pod: make([]uint32, np), node: make([]uint32, np)}
+	for i := 0; i < ng; i++ {
+		e.group[i], e.groupPods[i], e.groupEarlier[i] = uint32(og[i]), uint32(ogp[i]), uint32(oge[i])
+	}
+	for i := 0; i < np; i++ {
+		e.pod[i], e.node[i] = uint32(op[i]), uint32(on[i])
+	}
+	return e, nil
+}

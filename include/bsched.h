@@ -501,7 +501,7 @@ int bs_filter_rows_count(bs_ctx* ctx, uint32_t* rows);
  * the pod's class, that pass the plugin's Filter when BS_STAGE_FILTER is on, and that hold the request (lane j in {cpu, mem,
  * eph} binds when the pod asks for it; pods lane: requested + 1 <= allocatable; a requested scalar needs the allocatable
  * key).  Assume: requested += request, pods lane + 1.  A pod that passes PreFilter but finds no node holds nothing; pods of
- * a gang that never reaches its quorum keep what they assumed (as the reference does until the Permit timeout).
+ * a gang that never reaches its quorum keep what they assumed (as the reference does until the Permit timeout: bs_seq_expire).
  * `stages`: BS_STAGE_PREFILTER (mandatory) [| BS_STAGE_FILTER [| BS_BATCH_FILTER_DENY]].  Single-rank contexts only.
  * With BS_STAGE_FILTER the plugin's Filter gates the node choice (a what-if: no TTL write).  With BS_BATCH_FILTER_DENY as well, Filter's
  * own TTL writes happen inside the pass under the batch form's offer rule — Filter is called on EVERY node of the list, with the node
@@ -542,6 +542,62 @@ int bs_seq_run(bs_ctx* ctx, uint32_t stages, bs_seq_out* out);
 /* The node requests as the context holds them (after bs_nodes_load / bs_nodes_apply / bs_nodes_assume / bs_seq_run):
  * requested[L][n] lane-major, requested_present[n]; n = bs_nodes_count. */
 int bs_nodes_read(bs_ctx* ctx, int64_t* requested, uint32_t* requested_present);
+
+/* ---- a gang's Permit timeout, undone on the device ------------------------------------------------------------------------
+ * bs_seq_run leaves the pods of a gang that has not reached its quorum assumed on their nodes and counted in `matched`: they wait at
+ * Permit.  In the reference that wait ends.  When a gang's PodNameUIDs entry runs out, OnEvicted rejects every entry of MatchedPodNodes
+ * (controller.go:322-331 -> batchscheduler.go:346-352, waitingPod.Reject), the framework unreserves each pod and the scheduler cache
+ * forgets it (NodeInfo.RemovePod), the entries are deleted (controller.go:328) and the group goes onto the deny list (controller.go:332
+ * -> core.go:422-425).  bs_seq_expire is that event for the waiting pods of the LAST pass: the clock — which gangs timed out — stays
+ * with the caller, as the 2 s and 20 s TTLs do.
+ *   waiting state   where the last pass's waiting pods sit (per gang a chain of (pod, node) the pass keeps resident).  It is valid from
+ *                   a successful bs_seq_run until the first call that renumbers what it indexes: bs_pods_load, bs_pods_apply,
+ *                   bs_nodes_load, a bs_nodes_apply with an APPEND or a REMOVE, bs_groups_load, the next bs_seq_run (which replaces
+ *                   it), bs_destroy.  bs_nodes_assume, a bs_nodes_apply of UPDATEs only, bs_groups_apply, batches, the preemption and
+ *                   bound-table calls leave it valid: what this call does to the nodes is a delta and commutes with them.  Outside the
+ *                   window, and on sharded / external-reduce contexts (as bs_seq_run), both calls answer BS_ERR_STATE.  The window opens
+ *                   only when bs_seq_run returns BS_OK: a pass that fails after its launch leaves no waiting state.  The ending calls
+ *                   end it conservatively, when they are ENTERED — one of them that is then refused (a NULL argument, a delta out of
+ *                   range) has ended it too; run the next pass.  bs_bound_nodes_apply neither ends nor reopens it: the bs_nodes_apply it
+ *                   follows decided that (UPDATEs only: still open).
+ *   count, group    the groups to expire.  A listed group is expired whether or not it has waiting pods.  With BS_SEQ_EXPIRE_ALL
+ *                   (group == NULL, count == 0): every group whose chain is not empty, ascending index.
+ *   node requests   each forgotten pod leaves the node it was assumed on by NodeInfo.RemovePod, the exact inverse of the pass's assume
+ *                   step: lanes cpu / memory / ephemeral lose the request, the pods lane loses 1, a scalar lane the pod has a present
+ *                   bit for loses the request AND KEEPS its node bit, every other scalar lane keeps its word and its bit.  Sums wrap.
+ *                   Several forgotten pods on one node, of one gang or of several, leave together.  Everything derived from the node
+ *                   requests follows as after bs_nodes_assume.
+ *   group state     for every expired group: matched = 0 — EVERY MatchedPodNodes entry is deleted, those of earlier cycles included,
+ *                   which have no queue index and whose nodes the library never knew: group_earlier[i] tells the caller how many of
+ *                   those it has to take off the nodes itself —; BS_GROUP_DENIED is set with BS_SEQ_EXPIRE_DENY; BS_GROUP_SCHEDULED_LATCH
+ *                   (never cleared, core.go:305) and BS_GROUP_PHASE_CLOSED keep their value; the chain becomes empty, so a second expire
+ *                   of the group forgets nothing and changes nothing.  A later bs_batch_run, bs_seq_run or bs_find_max_pg sees what it
+ *                   would see after a bs_groups_apply of these values.
+ *   results         groups in the caller's order (ascending index in ALL mode); inside a group the pods in ascending queue index, so
+ *                   that results compare bit for bit.  n_groups / n_pods are the true counts; at most group_cap / pod_cap rows are
+ *                   written, and the resident state is fully applied whatever the caps.
+ *   errors          BS_ERR_INVALID: a group index >= g, a group listed twice, group == NULL without BS_SEQ_EXPIRE_ALL,
+ *                   BS_SEQ_EXPIRE_ALL together with a list, unknown flag bits, a NULL result array with a capacity above 0.  All are
+ *                   found on the host before anything is launched; on any of these errors nothing resident changes.  (BS_ERR_HIP — a
+ *                   failed HIP call, or chains that name more than the queue holds, which a valid window cannot produce — may come
+ *                   after the launches: reload the state.)  Synchronous.
+ * bs_seq_waiting_read changes nothing: wait_node[i] = the node pod i of the last pass still waits on, -1 for every other pod.  p must
+ * equal the queue length (BS_ERR_INVALID). */
+#define BS_SEQ_EXPIRE_DENY 1u  /* addToBackOff: set BS_GROUP_DENIED on every expired group (controller.go:332) */
+#define BS_SEQ_EXPIRE_ALL  2u  /* group == NULL, count == 0: every group whose waiting chain is not empty, ascending index */
+typedef struct bs_seq_expire_out {
+  uint32_t  n_groups, n_pods;      /* out: groups expired; pods forgotten (true count, may exceed pod_cap) */
+  uint32_t  group_cap;             /* capacity of the three per-group arrays (NULL ok when 0) */
+  uint32_t* group;                 /* [group_cap] expired groups: the caller's order, or ascending in ALL mode */
+  uint32_t* group_pods;            /* [group_cap] pods of the pass forgotten for the group */
+  uint32_t* group_earlier;         /* [group_cap] MatchedPodNodes entries WITHOUT a queue index:
+                                      matched before the call minus group_pods, in uint32 arithmetic */
+  uint32_t  pod_cap;
+  uint32_t* pod;                   /* [pod_cap] queue index of each forgotten pod */
+  uint32_t* node;                  /* [pod_cap] node it had been assumed on */
+} bs_seq_expire_out;
+int bs_seq_expire(bs_ctx* ctx, uint32_t count, const uint32_t* group, uint32_t flags, bs_seq_expire_out* out);
+int bs_seq_waiting_read(bs_ctx* ctx, uint32_t p, int32_t* wait_node /*[p]*/);  /* node a pod of the last pass still waits on, else -1 */
 
 /* ---- gang-aware preemption: the victim search, batched ------------------------------------------------------------------
  * The path of a pod that passed PreFilter and found no node.  The plugin's one hook there is PreFilterExtensions.RemovePod
@@ -985,6 +1041,9 @@ int bs_bound_apply_ex_flat(bs_ctx* ctx, uint32_t flags, uint32_t n_remove, const
 int bs_preempt_commit_flat(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
                            const uint8_t* group_protected, uint32_t flags, uint32_t victim_cap, int32_t* node, uint32_t* n_candidates,
                            uint32_t* n_victims, uint32_t* victims, int32_t* top_priority, int64_t* priority_sum, int64_t* earliest_start);
+/* bs_seq_expire (bs_seq_expire_out's arrays one by one; counts_out = {n_groups, n_pods}) */
+int bs_seq_expire_flat(bs_ctx* ctx, uint32_t count, const uint32_t* group, uint32_t flags, uint32_t group_cap, uint32_t* group_out,
+                       uint32_t* group_pods, uint32_t* group_earlier, uint32_t pod_cap, uint32_t* pod, uint32_t* node, uint32_t* counts_out /*[2]*/);
 /* bs_preempt_commit_gang (bs_preempt_out's arrays one by one) */
 int bs_preempt_commit_gang_flat(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
                                 const uint8_t* group_protected, const uint32_t* gang_need, uint32_t flags, uint32_t victim_cap,
