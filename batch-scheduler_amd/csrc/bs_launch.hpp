@@ -1,13 +1,17 @@
 // bs_launch.hpp — the launch wrappers that live in translation units of their own (tu_fast.hip, tu_seq.hip), so that the library builds
 // in parallel and a change to one kernel family recompiles that family only.  Kernels in the shared headers are `inline __global__`:
 // each translation unit emits exactly the kernels it launches.
+// A wrapper picks the instantiation for the context's scalar-lane count by one of the three rules of bs_lanes.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "bs_kernels.hpp"
+#include "bs_lanes.hpp"
 
 namespace bs {
+
+inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
 // what the wrappers of the steady-state chain's second launch need from the context
 struct FastLaunch {

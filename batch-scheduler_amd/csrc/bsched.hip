@@ -343,8 +343,6 @@ const char* kKernelNames[BS_KERNEL_COUNT] = {"prepass", "leader", "query", "tabl
     }                                                                                             \
   } while (0)
 
-inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
-
 int timer_begin(bs_ctx* c, uint32_t id, size_t* slot, hipStream_t st = nullptr) {
   *slot = (size_t)-1;
   if (!c->cfg.enable_timing) return BS_OK;
@@ -666,33 +664,11 @@ void launch_scan_s(bs_ctx* c, dim3 grid, const BatchDev& b, const BatchParams& p
 // local: the tables are chunk-local (k_tables_local_nofix); otherwise final (k_tables_fix ran)
 void launch_scan(bs_ctx* c, dim3 grid, const BatchDev& b, const BatchParams& p, uint32_t m, uint32_t nseg, uint32_t nslots, uint32_t ng, uint32_t ts,
                  bool local = false) {
-  switch (c->S) {
-    case 0: launch_scan_s<0>(c, grid, b, p, m, nseg, nslots, ng, ts, local); break;
-    case 1: launch_scan_s<1>(c, grid, b, p, m, nseg, nslots, ng, ts, local); break;
-    case 2: launch_scan_s<2>(c, grid, b, p, m, nseg, nslots, ng, ts, local); break;
-    case 3: launch_scan_s<3>(c, grid, b, p, m, nseg, nslots, ng, ts, local); break;
-    case 4: launch_scan_s<4>(c, grid, b, p, m, nseg, nslots, ng, ts, local); break;
-    case 5: launch_scan_s<5>(c, grid, b, p, m, nseg, nslots, ng, ts, local); break;
-    case 6: launch_scan_s<6>(c, grid, b, p, m, nseg, nslots, ng, ts, local); break;
-    case 7: launch_scan_s<7>(c, grid, b, p, m, nseg, nslots, ng, ts, local); break;
-    case 8: launch_scan_s<8>(c, grid, b, p, m, nseg, nslots, ng, ts, local); break;
-    case 9: launch_scan_s<9>(c, grid, b, p, m, nseg, nslots, ng, ts, local); break;
-    case 10: launch_scan_s<10>(c, grid, b, p, m, nseg, nslots, ng, ts, local); break;
-    case 11: launch_scan_s<11>(c, grid, b, p, m, nseg, nslots, ng, ts, local); break;
-    default: launch_scan_s<12>(c, grid, b, p, m, nseg, nslots, ng, ts, local); break;
-  }
+  lanes_wide(c->S, [&](auto s) { launch_scan_s<decltype(s)::value>(c, grid, b, p, m, nseg, nslots, ng, ts, local); });
 }
 
 void launch_tables_local(bs_ctx* c, hipStream_t st, dim3 grid, const NodesDev& nd, const BatchDev& b, const BatchParams& p, const TableDesc* forced) {
-  const dim3 tb(kTblChunk);
-  switch (c->S <= 4 ? (int)c->S : -1) {
-    case 0: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables_local<0>), grid, tb, 0, st, nd, b, p, forced); break;
-    case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables_local<1>), grid, tb, 0, st, nd, b, p, forced); break;
-    case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables_local<2>), grid, tb, 0, st, nd, b, p, forced); break;
-    case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables_local<3>), grid, tb, 0, st, nd, b, p, forced); break;
-    case 4: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables_local<4>), grid, tb, 0, st, nd, b, p, forced); break;
-    default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables_local<-1>), grid, tb, 0, st, nd, b, p, forced); break;
-  }
+  lanes_narrow(c->S, [&](auto s) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables_local<decltype(s)::value>), grid, dim3(kTblChunk), 0, st, nd, b, p, forced); });
 }
 
 template <int S>
@@ -707,34 +683,14 @@ void launch_scan_filter_s(bs_ctx* c, uint32_t scan_blocks, uint32_t filter_block
 }
 void launch_scan_filter(bs_ctx* c, uint32_t scan_blocks, uint32_t filter_blocks, const PodsDev& pd, const NodesDev& nd, const BatchDev& b,
                         const BatchParams& p, uint32_t m, uint32_t jcap, uint32_t nslots, uint32_t ng, uint32_t ts, bool local) {
-  switch (c->S) {
-    case 0: launch_scan_filter_s<0>(c, scan_blocks, filter_blocks, pd, nd, b, p, m, jcap, nslots, ng, ts, local); break;
-    case 1: launch_scan_filter_s<1>(c, scan_blocks, filter_blocks, pd, nd, b, p, m, jcap, nslots, ng, ts, local); break;
-    case 2: launch_scan_filter_s<2>(c, scan_blocks, filter_blocks, pd, nd, b, p, m, jcap, nslots, ng, ts, local); break;
-    case 3: launch_scan_filter_s<3>(c, scan_blocks, filter_blocks, pd, nd, b, p, m, jcap, nslots, ng, ts, local); break;
-    case 4: launch_scan_filter_s<4>(c, scan_blocks, filter_blocks, pd, nd, b, p, m, jcap, nslots, ng, ts, local); break;
-    case 5: launch_scan_filter_s<5>(c, scan_blocks, filter_blocks, pd, nd, b, p, m, jcap, nslots, ng, ts, local); break;
-    case 6: launch_scan_filter_s<6>(c, scan_blocks, filter_blocks, pd, nd, b, p, m, jcap, nslots, ng, ts, local); break;
-    case 7: launch_scan_filter_s<7>(c, scan_blocks, filter_blocks, pd, nd, b, p, m, jcap, nslots, ng, ts, local); break;
-    case 8: launch_scan_filter_s<8>(c, scan_blocks, filter_blocks, pd, nd, b, p, m, jcap, nslots, ng, ts, local); break;
-    case 9: launch_scan_filter_s<9>(c, scan_blocks, filter_blocks, pd, nd, b, p, m, jcap, nslots, ng, ts, local); break;
-    case 10: launch_scan_filter_s<10>(c, scan_blocks, filter_blocks, pd, nd, b, p, m, jcap, nslots, ng, ts, local); break;
-    case 11: launch_scan_filter_s<11>(c, scan_blocks, filter_blocks, pd, nd, b, p, m, jcap, nslots, ng, ts, local); break;
-    default: launch_scan_filter_s<12>(c, scan_blocks, filter_blocks, pd, nd, b, p, m, jcap, nslots, ng, ts, local); break;
-  }
+  lanes_wide(c->S, [&](auto s) { launch_scan_filter_s<decltype(s)::value>(c, scan_blocks, filter_blocks, pd, nd, b, p, m, jcap, nslots, ng, ts, local); });
 }
 
 void launch_tables_nofix(bs_ctx* c, dim3 grid, const NodesDev& nd, const BatchDev& b, const BatchParams& p, uint32_t nchunks) {
-  const dim3 tb(kTblChunk);
-  const uint32_t cs = cdiv(c->Ncap, 256), gs = cdiv(c->Ncap, 64);
-  switch (c->S <= 4 ? (int)c->S : -1) {
-    case 0: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables_local_nofix<0>), grid, tb, 0, c->stream, nd, b, p, nchunks, cs, gs); break;
-    case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables_local_nofix<1>), grid, tb, 0, c->stream, nd, b, p, nchunks, cs, gs); break;
-    case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables_local_nofix<2>), grid, tb, 0, c->stream, nd, b, p, nchunks, cs, gs); break;
-    case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables_local_nofix<3>), grid, tb, 0, c->stream, nd, b, p, nchunks, cs, gs); break;
-    case 4: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables_local_nofix<4>), grid, tb, 0, c->stream, nd, b, p, nchunks, cs, gs); break;
-    default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables_local_nofix<-1>), grid, tb, 0, c->stream, nd, b, p, nchunks, cs, gs); break;
-  }
+  lanes_narrow(c->S, [&](auto s) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tables_local_nofix<decltype(s)::value>), grid, dim3(kTblChunk), 0, c->stream, nd, b, p, nchunks, cdiv(c->Ncap, 256),
+                       cdiv(c->Ncap, 64));
+  });
 }
 
 static FastLaunch fast_launch(const bs_ctx* c) {
@@ -1021,17 +977,20 @@ int maybe_analyse_epochs(bs_ctx* c) {
   return analyse_epochs(c);
 }
 
-template <int TS>
-void launch_epoch_a(bs_ctx* c, dim3 grid, const PodsDev& pd, const GroupsDev& gr, const NodesDev& nd, const BatchDev& b, const BatchParams& prm,
-                           const EpochDev& ep, uint32_t nchunks, uint32_t qb, uint32_t ntab) {
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_epoch_query_tables<TS>), grid, dim3(kTblChunk), 0, c->stream, pd, gr, nd, b, prm, ep, nchunks, cdiv(c->Ncap, 256),
-                     cdiv(c->Ncap, 64), qb, ntab);
+// k_nodes_assume over n records the device can read (pinned staging or device memory): the nodes' absolute request vectors
+void launch_nodes_assume(bs_ctx* c, const bs_node_request* records, uint32_t n) {
+  static_assert(sizeof(bs_node_request) == sizeof(NodeRequest), "node request layout");
+  hipLaunchKernelGGL(k_nodes_assume, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, reinterpret_cast<const NodeRequest*>(records), n, c->L, c->Ncap,
+                     c->d_alloc.as<int64_t>(), c->d_nreq.as<int64_t>(), c->d_rpres.as<uint32_t>(), c->d_nflags.as<uint8_t>(), c->d_left4.as<int64_t>(),
+                     c->d_lglob.as<int64_t>());
 }
-template <int S>
-void launch_epoch_b(bs_ctx* c, dim3 grid, const PodsDev& pd, const NodesDev& nd, const BatchDev& b, const BatchParams& prm, const EpochDev& ep,
-                           uint32_t nseg, uint32_t scan_blocks, uint32_t filter_slots) {
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_epoch_scan_filter<S>), grid, dim3(256), 0, c->stream, pd, nd, b, prm, ep, c->M, nseg, c->G, scan_blocks,
-                     c->filter_waves, c->filter_slots_cap, filter_slots);
+// ... and the same n records (a host copy) into the host mirror a later bs_nodes_apply starts from
+void mirror_node_requests(bs_ctx* c, const bs_node_request* records, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i) {
+    const bs_node_request& r = records[i];
+    for (uint32_t j = 0; j < c->L; ++j) c->h_nreq[(size_t)j * c->N + r.index] = r.requested[j];
+    c->h_rpres[r.index] = r.requested_present;
+  }
 }
 
 int resolve_epochs(bs_ctx* c) {
@@ -2084,7 +2043,6 @@ static int run_fast(bs_ctx* c, uint32_t stages) {
   bt.chunk_kp = b.chunk_kp + (size_t)side_slot * cdiv(c->Ncap, 256) * 16;
   bt.gmax = b.gmax + (size_t)side_slot * cdiv(c->Ncap, 64) * prm.LP;
   const TableDesc* forced = b.desc + side_slot;
-  const int ts = c->S <= 4 ? (int)c->S : -1;
   if (commit && G) HIPCHK(c, hipMemsetAsync(c->d_fast_reject.p, 0xFF, (size_t)G * 4, c->stream));
 
   // K is known on the host once its copy from the pod load / queue patch has landed — never waited for here; when it is, the
@@ -2169,14 +2127,9 @@ static int run_fast(bs_ctx* c, uint32_t stages) {
   TIMED(c, BS_KERNEL_QUERY, {
     const uint32_t qb = cdiv(P, kTblChunk);
     const dim3 qg(qb + nchunks + (node_words ? nodew_blocks(N) : 0u)), blk(kTblChunk);
-    switch (ts) {
-      case 0: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fast_query_tables<0>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb); break;
-      case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fast_query_tables<1>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb); break;
-      case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fast_query_tables<2>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb); break;
-      case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fast_query_tables<3>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb); break;
-      case 4: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fast_query_tables<4>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb); break;
-      default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fast_query_tables<-1>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb); break;
-    }
+    lanes_narrow(c->S, [&](auto s) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fast_query_tables<decltype(s)::value>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb);
+    });
   });
   const uint64_t hp2 = c->host_probe ? host_ns() : 0;
   bool fused = false, tp_split = false;
@@ -2334,20 +2287,15 @@ static int run_epoch(bs_ctx* c, uint32_t stages, bool* taken) {
   if ((rc = setup_host_out(c, stages, run_filter, b, prm))) return rc;
   c->last_rows = filter_slots;
   const uint32_t nchunks = std::max<uint32_t>(1, cdiv(c->M, 256));
-  const int ts = c->S <= 4 ? (int)c->S : -1;
   // ---- launch A: per-pod decisions, scan / Filter slots | chunk-local running sums of the tables the state can ask for
   TIMED(c, BS_KERNEL_QUERY, {
     const uint32_t qb = cdiv(P, kTblChunk);
     const uint32_t ntab = ep.has_reserve ? 2 * C : (ep.has_first ? C : 0u);       // percent-0.7 tables only behind a leader with matched pods
     const dim3 qg(qb + cdiv(ntab, kTableGroup) * nchunks);
-    switch (ts) {
-      case 0: launch_epoch_a<0>(c, qg, pd, gr, nd, b, prm, ep, nchunks, qb, ntab); break;
-      case 1: launch_epoch_a<1>(c, qg, pd, gr, nd, b, prm, ep, nchunks, qb, ntab); break;
-      case 2: launch_epoch_a<2>(c, qg, pd, gr, nd, b, prm, ep, nchunks, qb, ntab); break;
-      case 3: launch_epoch_a<3>(c, qg, pd, gr, nd, b, prm, ep, nchunks, qb, ntab); break;
-      case 4: launch_epoch_a<4>(c, qg, pd, gr, nd, b, prm, ep, nchunks, qb, ntab); break;
-      default: launch_epoch_a<-1>(c, qg, pd, gr, nd, b, prm, ep, nchunks, qb, ntab); break;
-    }
+    lanes_narrow(c->S, [&](auto s) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_epoch_query_tables<decltype(s)::value>), qg, dim3(kTblChunk), 0, c->stream, pd, gr, nd, b, prm, ep, nchunks,
+                         cdiv(c->Ncap, 256), cdiv(c->Ncap, 64), qb, ntab);
+    });
   });
   // ---- launch B: node scan over the live slots | Filter over the Filter slots
   TIMED(c, BS_KERNEL_SCAN, {
@@ -2361,21 +2309,10 @@ static int run_epoch(bs_ctx* c, uint32_t stages, bool* taken) {
     const uint32_t scan_blocks = std::max<uint32_t>(1, cdiv(std::min<uint32_t>(wave_cap, 2 * std::max<uint32_t>(tiles, 1) * std::min<uint32_t>(nseg, cdiv(c->M, 64))), 4));
     const uint32_t fblocks = run_filter ? std::max<uint32_t>(1, cdiv(std::min<uint32_t>(c->filter_waves, cdiv(filter_slots, 64) * std::max<uint32_t>(1, cdiv(W, 2))), 4)) : 0u;
     const dim3 grid(scan_blocks + fblocks);
-    switch (c->S) {
-      case 0: launch_epoch_b<0>(c, grid, pd, nd, b, prm, ep, nseg, scan_blocks, filter_slots); break;
-      case 1: launch_epoch_b<1>(c, grid, pd, nd, b, prm, ep, nseg, scan_blocks, filter_slots); break;
-      case 2: launch_epoch_b<2>(c, grid, pd, nd, b, prm, ep, nseg, scan_blocks, filter_slots); break;
-      case 3: launch_epoch_b<3>(c, grid, pd, nd, b, prm, ep, nseg, scan_blocks, filter_slots); break;
-      case 4: launch_epoch_b<4>(c, grid, pd, nd, b, prm, ep, nseg, scan_blocks, filter_slots); break;
-      case 5: launch_epoch_b<5>(c, grid, pd, nd, b, prm, ep, nseg, scan_blocks, filter_slots); break;
-      case 6: launch_epoch_b<6>(c, grid, pd, nd, b, prm, ep, nseg, scan_blocks, filter_slots); break;
-      case 7: launch_epoch_b<7>(c, grid, pd, nd, b, prm, ep, nseg, scan_blocks, filter_slots); break;
-      case 8: launch_epoch_b<8>(c, grid, pd, nd, b, prm, ep, nseg, scan_blocks, filter_slots); break;
-      case 9: launch_epoch_b<9>(c, grid, pd, nd, b, prm, ep, nseg, scan_blocks, filter_slots); break;
-      case 10: launch_epoch_b<10>(c, grid, pd, nd, b, prm, ep, nseg, scan_blocks, filter_slots); break;
-      case 11: launch_epoch_b<11>(c, grid, pd, nd, b, prm, ep, nseg, scan_blocks, filter_slots); break;
-      default: launch_epoch_b<12>(c, grid, pd, nd, b, prm, ep, nseg, scan_blocks, filter_slots); break;
-    }
+    lanes_wide(c->S, [&](auto s) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_epoch_scan_filter<decltype(s)::value>), grid, dim3(256), 0, c->stream, pd, nd, b, prm, ep, c->M, nseg, c->G, scan_blocks,
+                         c->filter_waves, c->filter_slots_cap, filter_slots);
+    });
   });
   // ---- launch C: final codes, stale leader, Filter code / slot / feasible count per pod, admit counts, quorum
   TIMED(c, BS_KERNEL_RESOLVE, hipLaunchKernelGGL(k_epoch_final, dim3(cdiv(P, 256)), dim3(256), 0, c->stream, pd, gr, nd, b, prm, ep));
@@ -2516,7 +2453,6 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
   prm.use_classes = use_classes ? 1u : 0u;
   prm.scan_slots_cap = scan_cap;
   prm.filter_slots_cap = filter_cap;
-  const int ts = c->S <= 4 ? (int)c->S : -1;
   bool commit_dirty = false;
   const uint32_t side_slot = inline_tables ? (uint32_t)c->steady_table : 0u;
   prm.early_filter = early_filter ? 1u : 0u;
@@ -2549,14 +2485,9 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
     if (inline_tables) {
       const uint32_t pre = cdiv(span, kPrepassBlock);
       const dim3 pg(pre + 1 + nchunks), pb(kPrepassBlock);
-      switch (ts) {
-        case 0: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prepass_tables<0>), pg, pb, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, pre); break;
-        case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prepass_tables<1>), pg, pb, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, pre); break;
-        case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prepass_tables<2>), pg, pb, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, pre); break;
-        case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prepass_tables<3>), pg, pb, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, pre); break;
-        case 4: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prepass_tables<4>), pg, pb, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, pre); break;
-        default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prepass_tables<-1>), pg, pb, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, pre); break;
-      }
+      lanes_narrow(c->S, [&](auto s) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prepass_tables<decltype(s)::value>), pg, pb, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, pre);
+      });
     } else
     hipLaunchKernelGGL(k_prepass, dim3(cdiv(span, kPrepassBlock) + fused), dim3(kPrepassBlock), 0, c->stream, pd, gr, b, prm,
                        captures_possible ? 0u : 1u, fused);
@@ -2578,25 +2509,13 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
     if (P && inline_tables) {
       const uint32_t qb = cdiv(P, 256);
       const dim3 qg(qb + (nchunks > 1 ? nchunks - 1 : 0));
-      switch (ts) {
-        case 0: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_query_tables<0>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb); break;
-        case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_query_tables<1>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb); break;
-        case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_query_tables<2>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb); break;
-        case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_query_tables<3>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb); break;
-        case 4: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_query_tables<4>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb); break;
-        default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_query_tables<-1>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb); break;
-      }
+      lanes_narrow(c->S, [&](auto s) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_query_tables<decltype(s)::value>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb);
+      });
       launches++;
     } else if (P) {
       const dim3 qg(cdiv(P, 256));
-      switch (ts) {
-        case 0: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_query<0>), qg, blk, 0, c->stream, pd, gr, b, prm); break;
-        case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_query<1>), qg, blk, 0, c->stream, pd, gr, b, prm); break;
-        case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_query<2>), qg, blk, 0, c->stream, pd, gr, b, prm); break;
-        case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_query<3>), qg, blk, 0, c->stream, pd, gr, b, prm); break;
-        case 4: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_query<4>), qg, blk, 0, c->stream, pd, gr, b, prm); break;
-        default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_query<-1>), qg, blk, 0, c->stream, pd, gr, b, prm); break;
-      }
+      lanes_narrow(c->S, [&](auto s) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_query<decltype(s)::value>), qg, blk, 0, c->stream, pd, gr, b, prm); });
       launches++;
     }
   });
@@ -2604,14 +2523,7 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
     HIPCHK(c, hipEventRecord(c->ev_query, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_query, 0));
     const dim3 fg(cdiv(P, 256));
-    switch (ts) {
-      case 0: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fparams_early<0>), fg, blk, 0, c->stream3, pd, gr, b, prm); break;
-      case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fparams_early<1>), fg, blk, 0, c->stream3, pd, gr, b, prm); break;
-      case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fparams_early<2>), fg, blk, 0, c->stream3, pd, gr, b, prm); break;
-      case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fparams_early<3>), fg, blk, 0, c->stream3, pd, gr, b, prm); break;
-      case 4: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fparams_early<4>), fg, blk, 0, c->stream3, pd, gr, b, prm); break;
-      default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fparams_early<-1>), fg, blk, 0, c->stream3, pd, gr, b, prm); break;
-    }
+    lanes_narrow(c->S, [&](auto s) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fparams_early<decltype(s)::value>), fg, blk, 0, c->stream3, pd, gr, b, prm); });
     TIMED_ON(c, BS_KERNEL_FILTER, c->stream3, launch_filter(c, c->stream3, pd, nd, b, use_classes));
     HIPCHK(c, hipEventRecord(c->ev_filter, c->stream3));
     launches += 2;
@@ -2648,14 +2560,7 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
     if (P) {
       hipLaunchKernelGGL(k_reject, dim3(cdiv(P, 256)), blk, 0, c->stream, pd, b);
       const dim3 fg(cdiv(P, 256));
-      switch (ts) {
-        case 0: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_final<0>), fg, blk, 0, c->stream, pd, gr, nd, b, prm); break;
-        case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_final<1>), fg, blk, 0, c->stream, pd, gr, nd, b, prm); break;
-        case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_final<2>), fg, blk, 0, c->stream, pd, gr, nd, b, prm); break;
-        case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_final<3>), fg, blk, 0, c->stream, pd, gr, nd, b, prm); break;
-        case 4: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_final<4>), fg, blk, 0, c->stream, pd, gr, nd, b, prm); break;
-        default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_final<-1>), fg, blk, 0, c->stream, pd, gr, nd, b, prm); break;
-      }
+      lanes_narrow(c->S, [&](auto s) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_final<decltype(s)::value>), fg, blk, 0, c->stream, pd, gr, nd, b, prm); });
       launches += 2;
     }
   });
@@ -3342,7 +3247,7 @@ int bs_nodes_assume(bs_ctx* c, const bs_node_request* reqs, uint32_t count) {
   if (rc) return rc;
   if ((rc = settle_pending(c))) return rc;
   if (!count) return BS_OK;
-  const uint32_t N = c->N, L = c->L;
+  const uint32_t N = c->N;
   {
     std::vector<uint32_t> seen(count);
     for (uint32_t d = 0; d < count; ++d) {
@@ -3353,17 +3258,11 @@ int bs_nodes_assume(bs_ctx* c, const bs_node_request* reqs, uint32_t count) {
     std::sort(seen.begin(), seen.end());
     if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { c->last_error = "bs_nodes_assume: a node index appears twice"; return BS_ERR_INVALID; }
   }
-  static_assert(sizeof(bs_node_request) == sizeof(NodeRequest), "node request layout");
   const size_t bytes = (size_t)count * sizeof(bs_node_request);
   HIPCHK(c, c->h_nstage.reserve(bytes, std::max<size_t>(2 * bytes, 16 << 10)));
   std::memcpy(c->h_nstage.p, reqs, bytes);
-  for (uint32_t d = 0; d < count; ++d) {                          // the host mirror a later bs_nodes_apply starts from
-    for (uint32_t j = 0; j < L; ++j) c->h_nreq[(size_t)j * N + reqs[d].index] = reqs[d].requested[j];
-    c->h_rpres[reqs[d].index] = reqs[d].requested_present;
-  }
-  hipLaunchKernelGGL(k_nodes_assume, dim3(cdiv(count, 256)), dim3(256), 0, c->stream, reinterpret_cast<const NodeRequest*>(c->h_nstage.p), count, L, c->Ncap,
-                     c->d_alloc.as<int64_t>(), c->d_nreq.as<int64_t>(), c->d_rpres.as<uint32_t>(), c->d_nflags.as<uint8_t>(), c->d_left4.as<int64_t>(),
-                     c->d_lglob.as<int64_t>());
+  mirror_node_requests(c, reqs, count);
+  launch_nodes_assume(c, reinterpret_cast<const bs_node_request*>(c->h_nstage.p), count);
   LAUNCHCHK(c, BS_KERNEL_PREPASS);
   HIPCHK(c, c->h_nstage.mark_busy(c->stream));
   c->bitmap_valid = false;
@@ -3687,10 +3586,7 @@ int bs_seq_expire(bs_ctx* c, uint32_t count, const uint32_t* group, uint32_t fla
   std::vector<uint8_t> hr((size_t)nrec * sizeof(bs_node_request));
   std::vector<uint32_t> hg;
   if (nrec) {
-    static_assert(sizeof(bs_node_request) == sizeof(NodeRequest), "node request layout");
-    hipLaunchKernelGGL(k_nodes_assume, dim3(cdiv(nrec, 256)), dim3(256), 0, c->stream, reinterpret_cast<const NodeRequest*>(recs), nrec, L, c->Ncap,
-                       c->d_alloc.as<int64_t>(), c->d_nreq.as<int64_t>(), c->d_rpres.as<uint32_t>(), c->d_nflags.as<uint8_t>(), c->d_left4.as<int64_t>(),
-                       c->d_lglob.as<int64_t>());
+    launch_nodes_assume(c, recs, nrec);
     LAUNCHCHK(c, BS_KERNEL_PREPASS);
     HIPCHK(c, hipMemcpyAsync(hr.data(), recs, hr.size(), hipMemcpyDeviceToHost, c->stream));
     c->bitmap_valid = false;
@@ -3710,12 +3606,7 @@ int bs_seq_expire(bs_ctx* c, uint32_t count, const uint32_t* group, uint32_t fla
     HIPCHK(c, hipMemcpyAsync(hg.data(), base + o_group, (size_t)ng * 4, hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const bs_node_request* hrec = reinterpret_cast<const bs_node_request*>(hr.data());
-  for (uint32_t i = 0; i < nrec; ++i) {                     // the host mirror a later bs_nodes_apply starts from
-    const bs_node_request& r = hrec[i];
-    for (uint32_t j = 0; j < L; ++j) c->h_nreq[(size_t)j * N + r.index] = r.requested[j];
-    c->h_rpres[r.index] = r.requested_present;
-  }
+  mirror_node_requests(c, reinterpret_cast<const bs_node_request*>(hr.data()), nrec);
   if (deny) {
     const uint32_t* gl = all ? hg.data() : group;
     for (uint32_t i = 0; i < ng; ++i) c->h_gflags[gl[i]] |= (uint8_t)BS_GROUP_DENIED;
@@ -4608,18 +4499,12 @@ static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const
     launch_preempt_apply(c->stream, c->S, nd, pe, ndirty, assume ? 1u : 0u, dreq, nvall ? &nw : nullptr);
     LAUNCHCHK(c, BS_KERNEL_QUERY);
     if (ndirty) {
-      static_assert(sizeof(bs_node_request) == sizeof(NodeRequest), "node request layout");
-      hipLaunchKernelGGL(k_nodes_assume, dim3(cdiv(ndirty, 256)), dim3(256), 0, c->stream, reinterpret_cast<const NodeRequest*>(dreq), ndirty, L, c->Ncap,
-                         c->d_alloc.as<int64_t>(), c->d_nreq.as<int64_t>(), c->d_rpres.as<uint32_t>(), c->d_nflags.as<uint8_t>(), c->d_left4.as<int64_t>(),
-                         c->d_lglob.as<int64_t>());
+      launch_nodes_assume(c, dreq, ndirty);
       LAUNCHCHK(c, BS_KERNEL_PREPASS);
-      std::vector<bs_node_request> h(ndirty);             // the host mirror a later bs_nodes_apply starts from
+      std::vector<bs_node_request> h(ndirty);
       HIPCHK(c, hipMemcpyAsync(h.data(), dreq, (size_t)ndirty * sizeof(bs_node_request), hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
-      for (const bs_node_request& r : h) {
-        for (uint32_t j = 0; j < L; ++j) c->h_nreq[(size_t)j * N + r.index] = r.requested[j];
-        c->h_rpres[r.index] = r.requested_present;
-      }
+      mirror_node_requests(c, h.data(), ndirty);
       c->bitmap_valid = false;
     }
     if (nvall) {
@@ -4879,24 +4764,16 @@ static int bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t flags, uint3
     o2.out = reinterpret_cast<bs_node_request*>(base + o_rec);
     launch_bound_apply_nodes(c->stream, c->S, a, o2);
     LAUNCHCHK(c, BS_KERNEL_PREPASS);
-    std::vector<uint8_t> hr(8 + rec_cap * sizeof(bs_node_request));   // count + records: the host mirror a later bs_nodes_apply starts from
+    std::vector<uint8_t> hr(8 + rec_cap * sizeof(bs_node_request));   // count + records
     HIPCHK(c, hipMemcpyAsync(hr.data(), base + o_nrec, hr.size(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     uint32_t nrec = 0;
     std::memcpy(&nrec, hr.data(), 4);
     if (nrec > rec_cap) { c->last_error = "bs_bound_apply_ex: more touched nodes than the delta can touch"; return BS_ERR_HIP; }
     if (nrec) {
-      static_assert(sizeof(bs_node_request) == sizeof(NodeRequest), "node request layout");
-      hipLaunchKernelGGL(k_nodes_assume, dim3(cdiv(nrec, 256)), dim3(256), 0, c->stream, reinterpret_cast<const NodeRequest*>(o2.out), nrec, L, c->Ncap,
-                         c->d_alloc.as<int64_t>(), c->d_nreq.as<int64_t>(), c->d_rpres.as<uint32_t>(), c->d_nflags.as<uint8_t>(), c->d_left4.as<int64_t>(),
-                         c->d_lglob.as<int64_t>());
+      launch_nodes_assume(c, o2.out, nrec);
       LAUNCHCHK(c, BS_KERNEL_PREPASS);
-      const bs_node_request* recs = reinterpret_cast<const bs_node_request*>(hr.data() + 8);
-      for (uint32_t i = 0; i < nrec; ++i) {
-        const bs_node_request& r = recs[i];
-        for (uint32_t j = 0; j < L; ++j) c->h_nreq[(size_t)j * N + r.index] = r.requested[j];
-        c->h_rpres[r.index] = r.requested_present;
-      }
+      mirror_node_requests(c, reinterpret_cast<const bs_node_request*>(hr.data() + 8), nrec);
       c->bitmap_valid = false;
     }
   }
