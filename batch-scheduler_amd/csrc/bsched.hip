@@ -29,6 +29,7 @@
 #include "bs_seq_expire.hpp"
 #include "bs_seq_expire_list.hpp"
 #include "bs_launch.hpp"
+#include "bs_carve.hpp"
 #include "bs_hostmem.hpp"
 #include "bs_pod_ranges.hpp"
 #include "bs_preempt.hpp"
@@ -66,7 +67,7 @@ struct FitArena {
 };
 template <typename T> const T* at_dev(const void* base, size_t off) { return reinterpret_cast<const T*>((const uint8_t*)base + off); }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }   // LDS sizing and the two hand-added result blocks (ensure_hout, bs_batch_read)
 // element n of a device array that may not exist yet (null + n is undefined behaviour even if nobody follows the pointer)
 template <class T>
 T* at(T* p, size_t n) { return p ? p + n : nullptr; }
@@ -76,23 +77,28 @@ T* at(T* p, size_t n) { return p ? p + n : nullptr; }
 // The pinned staging buffer uses the same layout (input part only) — and its OWN copy of it (bs_pods_map must not disturb the
 // resident queue).
 struct PodLayout {
-  size_t group = 0, req = 0, pres = 0, cls = 0, owner = 0, flags = 0, in_bytes = 0, pclass = 0, ppair = 0, bytes = 0;
+  Piece<int32_t> group;
+  Piece<int64_t> req;
+  Piece<uint32_t> pres, cls, pclass, ppair;
+  Piece<uint64_t> owner;
+  Piece<uint8_t> flags;
+  size_t in_bytes = 0, bytes = 0;
   uint32_t p = 0;
 };
 PodLayout pod_layout(uint32_t P, uint32_t L) {
   const size_t n = std::max<uint32_t>(P, 1);
   PodLayout l;
-  size_t o = 0;
-  l.group = o; o = align256(o + n * 4);
-  l.req = o; o = align256(o + n * L * 8);
-  l.pres = o; o = align256(o + n * 4);
-  l.cls = o; o = align256(o + n * 4);
-  l.owner = o; o = align256(o + n * 8);
-  l.flags = o; o = align256(o + n);
-  l.in_bytes = o;
-  l.pclass = o; o = align256(o + n * 4);
-  l.ppair = o; o = align256(o + n * 4);
-  l.bytes = o;
+  Carve cv;
+  l.group = cv.take<int32_t>(n);
+  l.req = cv.take<int64_t>(n * L);
+  l.pres = cv.take<uint32_t>(n);
+  l.cls = cv.take<uint32_t>(n);
+  l.owner = cv.take<uint64_t>(n);
+  l.flags = cv.take<uint8_t>(n);
+  l.in_bytes = cv.mark();
+  l.pclass = cv.take<uint32_t>(n);
+  l.ppair = cv.take<uint32_t>(n);
+  l.bytes = cv.mark();
   l.p = P;
   return l;
 }
@@ -136,7 +142,11 @@ struct bs_ctx {
   // groups live in ONE device allocation (one pinned-staged H2D per load); d_info / h_info carry what findMaxPG
   // found for the loaded state back to the host without a stream wait (see resolve_groups)
   DevBuf d_gpack, d_info, d_gdelta;
-  size_t off_gmm = 0, off_gsc = 0, off_gmatched = 0, off_gflags = 0, off_gcls = 0, off_gminres = 0, off_gmrpres = 0, off_gocc = 0, gpack_bytes = 0;
+  Piece<uint32_t> off_gmm, off_gsc, off_gmatched, off_gcls, off_gmrpres;
+  Piece<uint8_t> off_gflags;
+  Piece<int64_t> off_gminres;
+  Piece<uint64_t> off_gocc;
+  size_t gpack_bytes = 0;
   int32_t info_tag = 0, kinfo_tag = 0;
   bool info_pending = false, kinfo_pending = false;
   uint32_t max_group_cls = 0, max_pod_cls = 0;   // largest fit class any HAS_POD group / grouped pod names (checked against C per batch)
@@ -161,7 +171,10 @@ struct bs_ctx {
   uint32_t id_room = 0;              // BS_ID_ROOM: ids beyond the queue length (0 = the default: as many again + 1024)
   uint32_t serial_insert_max = 2048; // more inserted pods than this: re-derive in parallel instead of the insert wave
   uint64_t n_applies = 0, n_rederives = 0;
-  size_t off_pf_code = 0, off_pf_first_k = 0, off_pf_leader = 0, off_fl_code = 0, off_fl_feasible = 0, off_fl_slot = 0, off_admit = 0, off_ready = 0, outpack_bytes = 0;
+  Piece<uint8_t> off_pf_code, off_fl_code, off_ready;
+  Piece<uint32_t> off_pf_first_k, off_fl_feasible, off_fl_slot, off_admit;
+  Piece<int32_t> off_pf_leader;
+  size_t outpack_bytes = 0;
 
   // ---- batch scratch / outputs
   DevBuf d_first_elig, d_first_owner, d_first_reject, d_first_pod, d_cap_epoch;
@@ -207,7 +220,8 @@ struct bs_ctx {
   // bs_seq_expire / bs_seq_waiting_read: the waiting state the last pass left in d_seq (chains, heads, counts) is valid from a successful
   // bs_seq_run until the first call that renumbers what it indexes (queue loads / patches, node loads / APPEND / REMOVE, group loads)
   bool seq_wait_valid = false;
-  size_t seq_o_wait = 0, seq_o_head = 0, seq_o_nwait = 0;
+  Piece<unsigned long long> seq_o_wait;
+  Piece<uint32_t> seq_o_head, seq_o_nwait;
   DevBuf d_sexp;                     // per-call scratch: block totals, slots, rows, dirty list, records
   DevBuf d_sexp_nodes;               // per-node delta [L][N], key bits, dirty words: zero between calls (k_se_nodes re-zeroes what it read)
   uint32_t sexp_n = 0, sexp_l = 0;   // the layout d_sexp_nodes was zeroed for
@@ -438,32 +452,53 @@ NodesDev nodes_dev(const bs_ctx* c) {
 GroupsDev groups_dev(const bs_ctx* c) {
   GroupsDev g{};
   g.g = c->G;
-  uint8_t* pk = c->d_gpack.as<uint8_t>();
-  g.min_member = reinterpret_cast<uint32_t*>(at(pk, c->off_gmm));
-  g.status_scheduled = reinterpret_cast<uint32_t*>(at(pk, c->off_gsc));
-  g.matched = reinterpret_cast<uint32_t*>(at(pk, c->off_gmatched));
-  g.flags = at(pk, c->off_gflags);
-  g.cls = reinterpret_cast<uint32_t*>(at(pk, c->off_gcls));
-  g.minres = reinterpret_cast<int64_t*>(at(pk, c->off_gminres));
-  g.mrpres = reinterpret_cast<uint32_t*>(at(pk, c->off_gmrpres));
-  g.occupied = reinterpret_cast<uint64_t*>(at(pk, c->off_gocc));
+  void* pk = c->d_gpack.p;
+  g.min_member = c->off_gmm.in(pk);
+  g.status_scheduled = c->off_gsc.in(pk);
+  g.matched = c->off_gmatched.in(pk);
+  g.flags = c->off_gflags.in(pk);
+  g.cls = c->off_gcls.in(pk);
+  g.minres = c->off_gminres.in(pk);
+  g.mrpres = c->off_gmrpres.in(pk);
+  g.occupied = c->off_gocc.in(pk);
   return g;
+}
+// The bound-pod table: its nine columns at the offsets of a BoundLayout (bound_layout, bs_bound_nodes.hpp), typed once.  U8 is
+// uint8_t (a table that is written: the staging copy of a load, a compaction target) or const uint8_t; a null base gives null columns.
+template <class U8>
+struct BoundCols {
+  template <class T> using Col = std::conditional_t<std::is_const_v<U8>, const T, T>*;
+  Col<uint32_t> boff, id, pres, nviol;
+  Col<int32_t> prio, group;
+  Col<int64_t> start, req;
+  Col<uint8_t> pdb;
+};
+template <class U8>
+BoundCols<U8> bound_cols(U8* base, const BoundLayout& l) {
+  return {Piece<uint32_t>{l.boff}.in(base), Piece<uint32_t>{l.id}.in(base), Piece<uint32_t>{l.pres}.in(base), Piece<uint32_t>{l.nviol}.in(base), Piece<int32_t>{l.prio}.in(base),
+          Piece<int32_t>{l.group}.in(base), Piece<int64_t>{l.start}.in(base), Piece<int64_t>{l.req}.in(base), Piece<uint8_t>{l.pdb}.in(base)};
+}
+// the seven columns every device struct over the table names (PreemptDev, CommitDev, CompactDev, BoundApplyDev, BoundNodesDev); bpres and
+// bnviol are set from the returned view where the struct has them
+template <class D, class U8>
+BoundCols<U8> bound_dev(D& d, U8* base, const BoundLayout& l) {
+  const BoundCols<U8> t = bound_cols(base, l);
+  d.boff = t.boff; d.bprio = t.prio; d.bstart = t.start; d.bgroup = t.group; d.bid = t.id; d.breq = t.req; d.bpdb = t.pdb;
+  return t;
+}
+// the six input columns of a pod pack, for PodsDev and PodsMut
+template <class D>
+void pod_cols(D& p, const PodLayout& l, void* pk) {
+  p.group = l.group.in(pk); p.req = l.req.in(pk); p.pres = l.pres.in(pk); p.cls = l.cls.in(pk); p.owner = l.owner.in(pk); p.flags = l.flags.in(pk);
 }
 PodsDev pods_dev(const bs_ctx* c) {
   PodsDev p{};
   p.p = c->P;
-  uint8_t* pk = c->d_pack[c->cur_pack].as<uint8_t>();
-  const PodLayout& l = c->lay[c->cur_pack];
-  p.group = reinterpret_cast<int32_t*>(at(pk, l.group));
-  p.req = reinterpret_cast<int64_t*>(at(pk, l.req));
-  p.pres = reinterpret_cast<uint32_t*>(at(pk, l.pres));
-  p.cls = reinterpret_cast<uint32_t*>(at(pk, l.cls));
-  p.owner = reinterpret_cast<uint64_t*>(at(pk, l.owner));
-  p.flags = at(pk, l.flags);
+  pod_cols(p, c->lay[c->cur_pack], c->d_pack[c->cur_pack].p);
   return p;
 }
-uint32_t* pclass_dev(const bs_ctx* c) { uint8_t* p = c->d_pack[c->cur_pack].as<uint8_t>(); return p ? reinterpret_cast<uint32_t*>(p + c->lay[c->cur_pack].pclass) : nullptr; }
-uint32_t* ppair_dev(const bs_ctx* c) { uint8_t* p = c->d_pack[c->cur_pack].as<uint8_t>(); return p ? reinterpret_cast<uint32_t*>(p + c->lay[c->cur_pack].ppair) : nullptr; }
+uint32_t* pclass_dev(const bs_ctx* c) { return c->lay[c->cur_pack].pclass.in(c->d_pack[c->cur_pack].p); }
+uint32_t* ppair_dev(const bs_ctx* c) { return c->lay[c->cur_pack].ppair.in(c->d_pack[c->cur_pack].p); }
 uint32_t* gstat_dev(const bs_ctx* c) { return (c->gstat_cur ? c->d_gstat2 : c->d_gstat).as<uint32_t>(); }
 BatchDev batch_dev(const bs_ctx* c) {
   BatchDev b{};
@@ -534,16 +569,16 @@ BatchDev batch_dev(const bs_ctx* c) {
   b.fd_in = c->fd_in_live ? c->d_fd_in.as<uint32_t>() : nullptr;
   b.fd_flag = c->d_fd_flag.as<uint32_t>();
   b.h_fd = c->h_info.p ? c->h_info.p + 14 : nullptr;
-  uint8_t* ok = c->d_outpack.as<uint8_t>();
-  b.pf_code = at(ok, c->off_pf_code);
-  b.pf_first_k = reinterpret_cast<uint32_t*>(at(ok, c->off_pf_first_k));
-  b.pf_leader = reinterpret_cast<int32_t*>(at(ok, c->off_pf_leader));
-  b.fl_code = at(ok, c->off_fl_code);
-  b.fl_feasible = reinterpret_cast<uint32_t*>(at(ok, c->off_fl_feasible));
-  b.fu_slot = reinterpret_cast<uint32_t*>(at(ok, c->off_fl_slot));     // per-pod Filter slot travels with the other per-pod results
+  void* ok = c->d_outpack.p;
+  b.pf_code = c->off_pf_code.in(ok);
+  b.pf_first_k = c->off_pf_first_k.in(ok);
+  b.pf_leader = c->off_pf_leader.in(ok);
+  b.fl_code = c->off_fl_code.in(ok);
+  b.fl_feasible = c->off_fl_feasible.in(ok);
+  b.fu_slot = c->off_fl_slot.in(ok);     // per-pod Filter slot travels with the other per-pod results
   b.fl_bitmap = c->d_fl_bitmap.as<uint64_t>();
-  b.admit = c->ext_admit ? c->ext_admit : reinterpret_cast<uint32_t*>(at(ok, c->off_admit));
-  b.ready = at(ok, c->off_ready);
+  b.admit = c->ext_admit ? c->ext_admit : c->off_admit.in(ok);
+  b.ready = c->off_ready.in(ok);
   return b;
 }
 BatchParams batch_params(const bs_ctx* c) {
@@ -921,17 +956,17 @@ int reserve_pod_scratch(bs_ctx* c, uint32_t P) {
 // Device layout of everything bs_batch_read returns in its first copy: per-pod arrays | admit[G] | ready[G].
 int layout_out(bs_ctx* c) {
   const size_t n = std::max<uint32_t>(c->P, 1), g = std::max<uint32_t>(c->G, 1);
-  size_t o = 0;
-  c->off_pf_code = o; o = align256(o + n);
-  c->off_pf_first_k = o; o = align256(o + n * 4);
-  c->off_pf_leader = o; o = align256(o + n * 4);
-  c->off_fl_code = o; o = align256(o + n);
-  c->off_fl_feasible = o; o = align256(o + n * 4);
-  c->off_fl_slot = o; o = align256(o + n * 4);
-  c->off_admit = o; o = align256(o + g * 4);
-  c->off_ready = o; o = align256(o + g);
-  c->outpack_bytes = o;
-  HIPCHK(c, c->d_outpack.reserve(o));
+  Carve cv;
+  c->off_pf_code = cv.take<uint8_t>(n);
+  c->off_pf_first_k = cv.take<uint32_t>(n);
+  c->off_pf_leader = cv.take<int32_t>(n);
+  c->off_fl_code = cv.take<uint8_t>(n);
+  c->off_fl_feasible = cv.take<uint32_t>(n);
+  c->off_fl_slot = cv.take<uint32_t>(n);
+  c->off_admit = cv.take<uint32_t>(g);
+  c->off_ready = cv.take<uint8_t>(g);
+  c->outpack_bytes = cv.mark();
+  HIPCHK(c, c->d_outpack.reserve(c->outpack_bytes));
   return BS_OK;
 }
 
@@ -1304,17 +1339,17 @@ int bs_groups_load(bs_ctx* c, const bs_groups_soa* g) {
     return BS_ERR_INVALID;
   const size_t n = std::max<uint32_t>(G, 1);
   // group arrays: one allocation, one pinned-staged transfer, no wait
-  size_t o = 0;
-  c->off_gmm = o; o = align256(o + n * 4);
-  c->off_gsc = o; o = align256(o + n * 4);
-  c->off_gmatched = o; o = align256(o + n * 4);
-  c->off_gflags = o; o = align256(o + n);
-  c->off_gcls = o; o = align256(o + n * 4);
-  c->off_gminres = o; o = align256(o + n * L * 8);
-  c->off_gmrpres = o; o = align256(o + n * 4);
-  c->off_gocc = o; o = align256(o + n * 8);
-  c->gpack_bytes = o;
-  HIPCHK(c, c->d_gpack.reserve(o));
+  Carve cv;
+  c->off_gmm = cv.take<uint32_t>(n);
+  c->off_gsc = cv.take<uint32_t>(n);
+  c->off_gmatched = cv.take<uint32_t>(n);
+  c->off_gflags = cv.take<uint8_t>(n);
+  c->off_gcls = cv.take<uint32_t>(n);
+  c->off_gminres = cv.take<int64_t>(n * L);
+  c->off_gmrpres = cv.take<uint32_t>(n);
+  c->off_gocc = cv.take<uint64_t>(n);
+  c->gpack_bytes = cv.mark();
+  HIPCHK(c, c->d_gpack.reserve(c->gpack_bytes));
   HIPCHK(c, c->d_first_elig.reserve(n * 4));
   HIPCHK(c, c->d_first_owner.reserve(n * 4));
   HIPCHK(c, c->d_first_reject.reserve(n * 4));
@@ -1332,14 +1367,14 @@ int bs_groups_load(bs_ctx* c, const bs_groups_soa* g) {
   if (G) {
     HIPCHK(c, c->h_gstage.reserve(c->gpack_bytes));
     uint8_t* st = c->h_gstage.p;
-    std::memcpy(st + c->off_gmm, g->min_member, (size_t)G * 4);
-    std::memcpy(st + c->off_gsc, g->status_scheduled, (size_t)G * 4);
-    std::memcpy(st + c->off_gmatched, g->matched, (size_t)G * 4);
-    std::memcpy(st + c->off_gflags, g->flags, (size_t)G);
-    std::memcpy(st + c->off_gcls, g->cls, (size_t)G * 4);
-    std::memcpy(st + c->off_gminres, g->min_resources, (size_t)G * L * 8);
-    std::memcpy(st + c->off_gmrpres, g->min_resources_present, (size_t)G * 4);
-    std::memcpy(st + c->off_gocc, g->occupied_by, (size_t)G * 8);
+    std::memcpy(c->off_gmm.in(st), g->min_member, c->off_gmm.bytes());      // G > 0: the pieces hold exactly G groups
+    std::memcpy(c->off_gsc.in(st), g->status_scheduled, c->off_gsc.bytes());
+    std::memcpy(c->off_gmatched.in(st), g->matched, c->off_gmatched.bytes());
+    std::memcpy(c->off_gflags.in(st), g->flags, c->off_gflags.bytes());
+    std::memcpy(c->off_gcls.in(st), g->cls, c->off_gcls.bytes());
+    std::memcpy(c->off_gminres.in(st), g->min_resources, c->off_gminres.bytes());
+    std::memcpy(c->off_gmrpres.in(st), g->min_resources_present, c->off_gmrpres.bytes());
+    std::memcpy(c->off_gocc.in(st), g->occupied_by, c->off_gocc.bytes());
     HIPCHK(c, hipMemcpyAsync(c->d_gpack.p, st, c->gpack_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, c->h_gstage.mark_busy(c->stream));
     for (uint32_t i = 0; i < G; ++i) {
@@ -1409,18 +1444,18 @@ int bs_groups_read(bs_ctx* c, bs_groups_soa* g) {
   if (g->g != c->G) return BS_ERR_INVALID;
   int rc = use_device(c);
   if (rc) return rc;
-  const uint32_t G = c->G, L = c->L;
+  const uint32_t G = c->G;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (G) {
-    const uint8_t* pk = c->d_gpack.as<uint8_t>();
-    HIPCHK(c, hipMemcpy(g->min_member, pk + c->off_gmm, (size_t)G * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(g->status_scheduled, pk + c->off_gsc, (size_t)G * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(g->matched, pk + c->off_gmatched, (size_t)G * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(g->flags, pk + c->off_gflags, (size_t)G, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(g->cls, pk + c->off_gcls, (size_t)G * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(g->min_resources, pk + c->off_gminres, (size_t)G * L * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(g->min_resources_present, pk + c->off_gmrpres, (size_t)G * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(g->occupied_by, pk + c->off_gocc, (size_t)G * 8, hipMemcpyDeviceToHost));
+    const void* pk = c->d_gpack.p;                    // G > 0: the pieces hold exactly G groups
+    HIPCHK(c, hipMemcpy(g->min_member, c->off_gmm.in(pk), c->off_gmm.bytes(), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(g->status_scheduled, c->off_gsc.in(pk), c->off_gsc.bytes(), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(g->matched, c->off_gmatched.in(pk), c->off_gmatched.bytes(), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(g->flags, c->off_gflags.in(pk), c->off_gflags.bytes(), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(g->cls, c->off_gcls.in(pk), c->off_gcls.bytes(), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(g->min_resources, c->off_gminres.in(pk), c->off_gminres.bytes(), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(g->min_resources_present, c->off_gmrpres.in(pk), c->off_gmrpres.bytes(), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(g->occupied_by, c->off_gocc.in(pk), c->off_gocc.bytes(), hipMemcpyDeviceToHost));
   }
   return BS_OK;
 }
@@ -1434,12 +1469,12 @@ int bs_pods_map(bs_ctx* c, uint32_t p, bs_pods_soa* view) {
   c->stage_lay = l;
   uint8_t* st = c->h_stage.p;
   view->p = p;
-  view->group = reinterpret_cast<const int32_t*>(st + l.group);
-  view->req = reinterpret_cast<const int64_t*>(st + l.req);
-  view->req_present = reinterpret_cast<const uint32_t*>(st + l.pres);
-  view->cls = reinterpret_cast<const uint32_t*>(st + l.cls);
-  view->owner = reinterpret_cast<const uint64_t*>(st + l.owner);
-  view->flags = st + l.flags;
+  view->group = l.group.in(st);
+  view->req = l.req.in(st);
+  view->req_present = l.pres.in(st);
+  view->cls = l.cls.in(st);
+  view->owner = l.owner.in(st);
+  view->flags = l.flags.in(st);
   c->map_p = p;
   return BS_OK;
 }
@@ -1492,9 +1527,9 @@ int bs_pods_load(bs_ctx* c, const bs_pods_soa* pods) {
   // do not match the mapping (another p, a stale view) would make the packing copy overlap itself: refused.
   const uint8_t* sb = c->h_stage.p;
   const bool inside = P && sb && (const uint8_t*)pods->group >= sb && (const uint8_t*)pods->group < sb + c->h_stage.cap;
-  const bool mapped = inside && c->map_p == P && (const uint8_t*)pods->group == sb + c->stage_lay.group && (const uint8_t*)pods->req == sb + c->stage_lay.req &&
-                      (const uint8_t*)pods->req_present == sb + c->stage_lay.pres && (const uint8_t*)pods->cls == sb + c->stage_lay.cls &&
-                      (const uint8_t*)pods->owner == sb + c->stage_lay.owner && pods->flags == sb + c->stage_lay.flags;
+  const PodLayout& sl = c->stage_lay;
+  const bool mapped = inside && c->map_p == P && pods->group == sl.group.in(sb) && pods->req == sl.req.in(sb) && pods->req_present == sl.pres.in(sb) &&
+                      pods->cls == sl.cls.in(sb) && pods->owner == sl.owner.in(sb) && pods->flags == sl.flags.in(sb);
   if (inside && !mapped) { c->last_error = "bs_pods_load: pointers into the mapped staging buffer, but not the view bs_pods_map handed out for this p"; return BS_ERR_INVALID; }
   if (!mapped) HIPCHK(c, c->h_stage.reserve(l.in_bytes));   // the previous upload may still be reading the staging buffer
   c->map_p = 0;
@@ -1514,12 +1549,12 @@ int bs_pods_load(bs_ctx* c, const bs_pods_soa* pods) {
   if (P) {
     uint8_t* st = c->h_stage.p;
     if (!mapped) {                                   // (bs_pods_map: the caller marshalled the queue in place)
-      std::memcpy(st + l.group, pods->group, (size_t)P * 4);
-      std::memcpy(st + l.req, pods->req, (size_t)P * L * 8);
-      std::memcpy(st + l.pres, pods->req_present, (size_t)P * 4);
-      std::memcpy(st + l.cls, pods->cls, (size_t)P * 4);
-      std::memcpy(st + l.owner, pods->owner, (size_t)P * 8);
-      std::memcpy(st + l.flags, pods->flags, (size_t)P);
+      std::memcpy(l.group.in(st), pods->group, l.group.bytes());           // P > 0: the pieces hold exactly P pods
+      std::memcpy(l.req.in(st), pods->req, l.req.bytes());
+      std::memcpy(l.pres.in(st), pods->req_present, l.pres.bytes());
+      std::memcpy(l.cls.in(st), pods->cls, l.cls.bytes());
+      std::memcpy(l.owner.in(st), pods->owner, l.owner.bytes());
+      std::memcpy(l.flags.in(st), pods->flags, l.flags.bytes());
     }
     HIPCHK(c, hipMemcpyAsync(c->d_pack[0].p, st, l.in_bytes, hipMemcpyHostToDevice, c->stream));
   }
@@ -1644,40 +1679,39 @@ int bs_pods_apply(bs_ctx* c, const bs_pods_delta* d) {
 
   // ---- the delta goes into pinned memory as ONE tightly packed blob the kernel stages into LDS with one bulk read per block:
   // [remove | insert_at | flag_index | flag_value] (what every gather block needs), then the inserted pods (SoA)
-  auto a16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  size_t o = 0;
-  const size_t o_rem = o; o = a16(o + (size_t)R * 4);
-  const size_t o_at = o; o = a16(o + (size_t)I * 4);
-  const size_t o_fi = o; o = a16(o + (size_t)F * 4);
-  const size_t o_fv = o; o = a16(o + (size_t)F);
-  const size_t lists_bytes = o;
-  const size_t i_group = o; o = a16(o + (size_t)I * 4);
-  const size_t i_req = o; o = a16(o + (size_t)I * L * 8);
-  const size_t i_pres = o; o = a16(o + (size_t)I * 4);
-  const size_t i_cls = o; o = a16(o + (size_t)I * 4);
-  const size_t i_owner = o; o = a16(o + (size_t)I * 8);
-  const size_t i_flags = o; o = a16(o + (size_t)I);
+  Carve cv;                                          // (16-byte pieces)
+  const auto o_rem = cv.take<uint32_t>(R, 16);
+  const auto o_at = cv.take<uint32_t>(I, 16);
+  const auto o_fi = cv.take<uint32_t>(F, 16);
+  const auto o_fv = cv.take<uint8_t>(F, 16);
+  const size_t lists_bytes = cv.mark();
+  const auto i_group = cv.take<int32_t>(I, 16);
+  const auto i_req = cv.take<int64_t>((size_t)I * L, 16);
+  const auto i_pres = cv.take<uint32_t>(I, 16);
+  const auto i_cls = cv.take<uint32_t>(I, 16);
+  const auto i_owner = cv.take<uint64_t>(I, 16);
+  const auto i_flags = cv.take<uint8_t>(I, 16);
   // the previous apply may still be reading the blob.  No event per apply (a record costs the cycle a microsecond of host time):
   // h_dstage.busy is cleared whenever the host has seen something later on the stream complete (the batch's completion word, a
   // stream wait); two applies without that in between wait for the stream here.
-  const size_t blob = o + 16;
+  const size_t blob = cv.mark() + 16;
   HIPCHK(c, c->h_dstage.reserve(blob, std::max<size_t>(blob + blob / 2, 64 << 10)));
   uint8_t* st = c->h_dstage.p;
-  if (R) std::memcpy(st + o_rem, d->remove, (size_t)R * 4);
+  if (R) std::memcpy(o_rem.in(st), d->remove, o_rem.bytes());
   if (I) {
-    uint32_t* at = reinterpret_cast<uint32_t*>(st + o_at);
-    if (d->insert_at) std::memcpy(at, d->insert_at, (size_t)I * 4);
+    uint32_t* at = o_at.in(st);
+    if (d->insert_at) std::memcpy(at, d->insert_at, o_at.bytes());
     else for (uint32_t i = 0; i < I; ++i) at[i] = P - R + i;
-    std::memcpy(st + i_group, in.group, (size_t)I * 4);
-    std::memcpy(st + i_req, in.req, (size_t)I * L * 8);
-    std::memcpy(st + i_pres, in.req_present, (size_t)I * 4);
-    std::memcpy(st + i_cls, in.cls, (size_t)I * 4);
-    std::memcpy(st + i_owner, in.owner, (size_t)I * 8);
-    std::memcpy(st + i_flags, in.flags, (size_t)I);
+    std::memcpy(i_group.in(st), in.group, i_group.bytes());
+    std::memcpy(i_req.in(st), in.req, i_req.bytes());
+    std::memcpy(i_pres.in(st), in.req_present, i_pres.bytes());
+    std::memcpy(i_cls.in(st), in.cls, i_cls.bytes());
+    std::memcpy(i_owner.in(st), in.owner, i_owner.bytes());
+    std::memcpy(i_flags.in(st), in.flags, i_flags.bytes());
     for (uint32_t i = 0; i < I; ++i)
       if (in.group[i] >= 0) c->max_pod_cls = std::max(c->max_pod_cls, in.cls[i]);
   }
-  if (F) { std::memcpy(st + o_fi, d->flag_index, (size_t)F * 4); std::memcpy(st + o_fv, d->flag_value, (size_t)F); }
+  if (F) { std::memcpy(o_fi.in(st), d->flag_index, o_fi.bytes()); std::memcpy(o_fv.in(st), d->flag_value, o_fv.bytes()); }
 
   // ---- ids can be patched when the pairs are current, the directories can be had, the id space has room and the insert
   // wave is not asked to do a parallel job; otherwise: copy only, then derive everything from the new resident queue
@@ -1704,31 +1738,26 @@ int bs_pods_apply(bs_ctx* c, const bs_pods_delta* d) {
   if ((rc = resize_queue(c, Pn))) return rc;
   if (c->pair_cap != old_pair_cap) derive = false;                   // the id space was re-sized: directories are gone
   PodsMut nw{};
-  uint8_t* nb = c->d_pack[np].as<uint8_t>();
-  nw.group = reinterpret_cast<int32_t*>(nb + nl.group);
-  nw.req = reinterpret_cast<int64_t*>(nb + nl.req);
-  nw.pres = reinterpret_cast<uint32_t*>(nb + nl.pres);
-  nw.cls = reinterpret_cast<uint32_t*>(nb + nl.cls);
-  nw.owner = reinterpret_cast<uint64_t*>(nb + nl.owner);
-  nw.flags = nb + nl.flags;
-  nw.pclass = reinterpret_cast<uint32_t*>(nb + nl.pclass);
-  nw.ppair = reinterpret_cast<uint32_t*>(nb + nl.ppair);
+  void* nb = c->d_pack[np].p;
+  pod_cols(nw, nl, nb);
+  nw.pclass = nl.pclass.in(nb);
+  nw.ppair = nl.ppair.in(nb);
   nw.p = Pn;
   PodDeltaDev dd{};
   dd.n_remove = R; dd.n_insert = I; dd.n_flags = F;
-  dd.remove = reinterpret_cast<const uint32_t*>(st + o_rem);
-  dd.insert_at = reinterpret_cast<const uint32_t*>(st + o_at);
-  dd.flag_index = reinterpret_cast<const uint32_t*>(st + o_fi);
-  dd.flag_value = st + o_fv;
+  dd.remove = o_rem.in(st);
+  dd.insert_at = o_at.in(st);
+  dd.flag_index = o_fi.in(st);
+  dd.flag_value = o_fv.in(st);
   dd.ins.p = I;
-  dd.ins.group = reinterpret_cast<const int32_t*>(st + i_group);
-  dd.ins.req = reinterpret_cast<const int64_t*>(st + i_req);
-  dd.ins.pres = reinterpret_cast<const uint32_t*>(st + i_pres);
-  dd.ins.cls = reinterpret_cast<const uint32_t*>(st + i_cls);
-  dd.ins.owner = reinterpret_cast<const uint64_t*>(st + i_owner);
-  dd.ins.flags = st + i_flags;
+  dd.ins.group = i_group.in(st);
+  dd.ins.req = i_req.in(st);
+  dd.ins.pres = i_pres.in(st);
+  dd.ins.cls = i_cls.in(st);
+  dd.ins.owner = i_owner.in(st);
+  dd.ins.flags = i_flags.in(st);
   dd.blob = st;
-  dd.blob_bytes = (uint32_t)std::min<size_t>(o, 0xFFFFFFF0u);
+  dd.blob_bytes = (uint32_t)std::min<size_t>(cv.mark(), 0xFFFFFFF0u);
   dd.lists_bytes = (uint32_t)std::min<size_t>(lists_bytes, 0xFFFFFFF0u);
   const uint32_t gb = cdiv(std::max<uint32_t>(Pn, 1), kApplyBlock);
   uint32_t* g_new = (c->gstat_cur ? c->d_gstat : c->d_gstat2).as<uint32_t>();
@@ -1792,24 +1821,25 @@ int bs_queue_sort(bs_ctx* c, uint32_t p, const int32_t* priority, const int32_t*
   int rc = use_device(c);
   if (rc) return rc;
   const size_t n = p;
-  const size_t o_prio = 0, o_grp = align256(n * 4), o_ts = o_grp + align256(n * 4), o_a = o_ts + align256(n * 8), o_b = o_a + align256(n * 4),
-               o_perm = o_b + align256(n * 4), total = o_perm + align256(n * 4);
-  HIPCHK(c, c->d_sort.reserve(total));
-  uint8_t* base = c->d_sort.as<uint8_t>();
-  HIPCHK(c, hipMemcpyAsync(base + o_prio, priority, n * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(base + o_grp, group, n * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(base + o_ts, queue_ts, n * 8, hipMemcpyHostToDevice, c->stream));
+  Carve cv;
+  const auto o_prio = cv.take<int32_t>(n), o_grp = cv.take<int32_t>(n);
+  const auto o_ts = cv.take<int64_t>(n);
+  const auto o_a = cv.take<uint32_t>(n), o_b = cv.take<uint32_t>(n), o_perm = cv.take<uint32_t>(n);
+  HIPCHK(c, c->d_sort.reserve(cv.mark()));
+  void* base = c->d_sort.p;
+  HIPCHK(c, hipMemcpyAsync(o_prio.in(base), priority, o_prio.bytes(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(o_grp.in(base), group, o_grp.bytes(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(o_ts.in(base), queue_ts, o_ts.bytes(), hipMemcpyHostToDevice, c->stream));
   SortIn in{};
   in.p = p;
   in.g = c->order_g;                                 // groups the order ranks cover; a label beyond it is a lister error
-  in.prio = reinterpret_cast<const int32_t*>(base + o_prio);
-  in.group = reinterpret_cast<const int32_t*>(base + o_grp);
-  in.ts = reinterpret_cast<const int64_t*>(base + o_ts);
+  in.prio = o_prio.in(base);
+  in.group = o_grp.in(base);
+  in.ts = o_ts.in(base);
   in.order_rank = c->d_order_rank.as<uint32_t>();
-  hipLaunchKernelGGL(k_queue_sort, dim3(1), dim3(kSortBlock), 0, c->stream, in, reinterpret_cast<uint32_t*>(base + o_a),
-                     reinterpret_cast<uint32_t*>(base + o_b), reinterpret_cast<uint32_t*>(base + o_perm));
+  hipLaunchKernelGGL(k_queue_sort, dim3(1), dim3(kSortBlock), 0, c->stream, in, o_a.in(base), o_b.in(base), o_perm.in(base));
   LAUNCHCHK(c, BS_KERNEL_PREPASS);
-  HIPCHK(c, hipMemcpyAsync(perm_out, base + o_perm, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(perm_out, o_perm.in(base), o_perm.bytes(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return BS_OK;
 }
@@ -1940,14 +1970,14 @@ static int setup_host_out(bs_ctx* c, uint32_t stages, bool run_filter, BatchDev&
   c->host_tag = c->host_tag == 0x7FFFFFFF ? 1 : c->host_tag + 1;
   prm.host_tag = c->host_tag;
   uint8_t* h = c->h_hout.p;
-  b.h_pf_code = h + c->off_pf_code;
-  b.h_pf_first_k = reinterpret_cast<uint32_t*>(h + c->off_pf_first_k);
-  b.h_pf_leader = reinterpret_cast<int32_t*>(h + c->off_pf_leader);
-  b.h_fl_code = h + c->off_fl_code;
-  b.h_fl_feasible = reinterpret_cast<uint32_t*>(h + c->off_fl_feasible);
-  b.h_fl_slot = reinterpret_cast<uint32_t*>(h + c->off_fl_slot);
-  b.h_admit = reinterpret_cast<uint32_t*>(h + c->off_admit);
-  b.h_ready = h + c->off_ready;
+  b.h_pf_code = c->off_pf_code.in(h);
+  b.h_pf_first_k = c->off_pf_first_k.in(h);
+  b.h_pf_leader = c->off_pf_leader.in(h);
+  b.h_fl_code = c->off_fl_code.in(h);
+  b.h_fl_feasible = c->off_fl_feasible.in(h);
+  b.h_fl_slot = c->off_fl_slot.in(h);
+  b.h_admit = c->off_admit.in(h);
+  b.h_ready = c->off_ready.in(h);
   b.h_feas = reinterpret_cast<uint32_t*>(h + c->off_hfeas);
   b.h_tag = reinterpret_cast<int32_t*>(h + c->off_htag);
   b.h_rows = run_filter ? c->h_hrows.p : nullptr;
@@ -2811,6 +2841,21 @@ int bs_batch_read(bs_ctx* c, const bs_batch_out* out) {
   const bool filtered = c->last_stages & BS_STAGE_FILTER;
   const bool want_pod = P && (out->pf_code || out->pf_first_k || out->pf_leader || out->fl_code || out->fl_feasible || out->fl_slot);
   const bool want_grp = G && (c->last_stages & BS_STAGE_TALLY) && (out->group_admit || out->group_ready);
+  // the caller's arrays out of a host copy of the result pack (the pinned pack of latency mode, or the staged D2H); the admit counters may sit elsewhere
+  auto copy_out = [&](const uint8_t* st, const void* admit) {
+    if (want_pod) {
+      if (out->pf_code) std::memcpy(out->pf_code, c->off_pf_code.in(st), P);
+      if (out->pf_first_k) std::memcpy(out->pf_first_k, c->off_pf_first_k.in(st), (size_t)P * 4);
+      if (out->pf_leader) std::memcpy(out->pf_leader, c->off_pf_leader.in(st), (size_t)P * 4);
+      if (out->fl_code) std::memcpy(out->fl_code, c->off_fl_code.in(st), P);
+      if (out->fl_feasible) std::memcpy(out->fl_feasible, c->off_fl_feasible.in(st), (size_t)P * 4);
+      if (out->fl_slot) std::memcpy(out->fl_slot, c->off_fl_slot.in(st), (size_t)P * 4);
+    }
+    if (want_grp) {
+      if (out->group_admit) std::memcpy(out->group_admit, admit, (size_t)G * 4);
+      if (out->group_ready) std::memcpy(out->group_ready, c->off_ready.in(st), G);
+    }
+  };
   // Filter rows: the slots of the last batch, word-major, compacted to the rows in use
   uint32_t nrows = 0;
   if (out->fl_rows || out->fl_rows_feasible || out->fl_rows_n) {
@@ -2838,18 +2883,7 @@ int bs_batch_read(bs_ctx* c, const bs_batch_out* out) {
     if ((rc = check_handover(c))) return rc;
     c->h_dstage.busy = false;                            // (the batch ran behind every earlier apply)
     const uint8_t* st = c->h_hout.p;
-    if (want_pod) {
-      if (out->pf_code) std::memcpy(out->pf_code, st + c->off_pf_code, P);
-      if (out->pf_first_k) std::memcpy(out->pf_first_k, st + c->off_pf_first_k, (size_t)P * 4);
-      if (out->pf_leader) std::memcpy(out->pf_leader, st + c->off_pf_leader, (size_t)P * 4);
-      if (out->fl_code) std::memcpy(out->fl_code, st + c->off_fl_code, P);
-      if (out->fl_feasible) std::memcpy(out->fl_feasible, st + c->off_fl_feasible, (size_t)P * 4);
-      if (out->fl_slot) std::memcpy(out->fl_slot, st + c->off_fl_slot, (size_t)P * 4);
-    }
-    if (want_grp) {
-      if (out->group_admit) std::memcpy(out->group_admit, st + c->off_admit, (size_t)G * 4);
-      if (out->group_ready) std::memcpy(out->group_ready, st + c->off_ready, G);
-    }
+    copy_out(st, c->off_admit.in(st));
     if ((want_rows || want_rfeas) && nrows <= c->hstride) {
       if (want_rfeas) std::memcpy(out->fl_rows_feasible, st + c->off_hfeas, (size_t)nrows * 4);
       if (want_rows)
@@ -2862,7 +2896,7 @@ int bs_batch_read(bs_ctx* c, const bs_batch_out* out) {
   // ONE wait and at most two copies: the result pack (per-pod arrays | admit | ready, contiguous on the device) and the
   // Filter rows with their feasible counts (a strided window of the slot bitmap; the counts sit behind its last row)
   const bool ext = c->ext_admit != nullptr;
-  const size_t pack_bytes = want_grp ? c->outpack_bytes : c->off_admit;
+  const size_t pack_bytes = want_grp ? c->outpack_bytes : c->off_admit.off;
   const size_t off_xadmit = align256(c->outpack_bytes);
   const size_t off_rows = off_xadmit + align256((size_t)G * 4);
   const bool any_rows = want_rows || want_rfeas;
@@ -2878,18 +2912,7 @@ int bs_batch_read(bs_ctx* c, const bs_batch_out* out) {
   c->h_stage.busy = false;                             // (the stream is idle: the pod upload has left its buffer too)
   c->h_dstage.busy = false;
   if ((rc = check_handover(c))) return rc;
-  if (want_pod) {
-    if (out->pf_code) std::memcpy(out->pf_code, st + c->off_pf_code, P);
-    if (out->pf_first_k) std::memcpy(out->pf_first_k, st + c->off_pf_first_k, (size_t)P * 4);
-    if (out->pf_leader) std::memcpy(out->pf_leader, st + c->off_pf_leader, (size_t)P * 4);
-    if (out->fl_code) std::memcpy(out->fl_code, st + c->off_fl_code, P);
-    if (out->fl_feasible) std::memcpy(out->fl_feasible, st + c->off_fl_feasible, (size_t)P * 4);
-    if (out->fl_slot) std::memcpy(out->fl_slot, st + c->off_fl_slot, (size_t)P * 4);
-  }
-  if (want_grp) {
-    if (out->group_admit) std::memcpy(out->group_admit, st + (ext ? off_xadmit : c->off_admit), (size_t)G * 4);
-    if (out->group_ready) std::memcpy(out->group_ready, st + c->off_ready, G);
-  }
+  copy_out(st, ext ? (const void*)(st + off_xadmit) : c->off_admit.in(st));
   if (want_rfeas) std::memcpy(out->fl_rows_feasible, st + off_rows + (size_t)W * nrows * 8, (size_t)nrows * 4);
   if (want_rows)
     for (uint32_t w = 0; w < W; ++w) std::memcpy(out->fl_rows + (size_t)w * out->fl_rows_cap, st + off_rows + (size_t)w * nrows * 8, (size_t)nrows * 8);
@@ -2921,15 +2944,15 @@ int bs_batch_map(bs_ctx* c, bs_batch_view* v) {
   const uint8_t* st = c->h_hout.p;
   std::memset(v, 0, sizeof(*v));
   v->p = P; v->g = G; v->words = W;
-  v->pf_code = st + c->off_pf_code;
-  v->pf_first_k = reinterpret_cast<const uint32_t*>(st + c->off_pf_first_k);
-  v->pf_leader = reinterpret_cast<const int32_t*>(st + c->off_pf_leader);
-  v->fl_code = st + c->off_fl_code;
-  v->fl_feasible = reinterpret_cast<const uint32_t*>(st + c->off_fl_feasible);
-  v->fl_slot = reinterpret_cast<const uint32_t*>(st + c->off_fl_slot);
+  v->pf_code = c->off_pf_code.in(st);
+  v->pf_first_k = c->off_pf_first_k.in(st);
+  v->pf_leader = c->off_pf_leader.in(st);
+  v->fl_code = c->off_fl_code.in(st);
+  v->fl_feasible = c->off_fl_feasible.in(st);
+  v->fl_slot = c->off_fl_slot.in(st);
   if (c->last_stages & BS_STAGE_TALLY) {
-    v->group_admit = reinterpret_cast<const uint32_t*>(st + c->off_admit);
-    v->group_ready = st + c->off_ready;
+    v->group_admit = c->off_admit.in(st);
+    v->group_ready = c->off_ready.in(st);
   }
   v->fl_rows_n = nrows;
   v->fl_rows_stride = c->hstride;
@@ -3318,28 +3341,28 @@ int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
   out->node_picks = out->node_scans = out->scan_rounds = out->pick_rounds = out->leader_folds = out->table_builds = 0;
   // ---- scratch: one allocation
   const size_t nP = std::max<uint32_t>(P, 1), nG = std::max<uint32_t>(G, 1), cap = std::max<uint32_t>(out->cap, 1), stride = std::max<uint32_t>(c->Ncap, 1);
-  size_t o = 0;
-  const size_t o_sc07 = o; o = align256(o + stride * L * 8);
-  const size_t o_sc10 = o; o = align256(o + stride * L * 8);
-  const size_t o_meta = o; o = align256(o + stride * 4);
-  const size_t o_keys = o; o = align256(o + nG * 8);
-  const size_t o_wait = o; o = align256(o + nP * 8);
-  const size_t o_head = o; o = align256(o + nG * 4);
-  const size_t o_nwait = o; o = align256(o + nG * 4);
-  const size_t o_slot = o; o = align256(o + nG * 4);
-  const size_t o_tfirst = o; o = align256(o + nG * 8);
-  const size_t o_res = o;                                   // results: one D2H
-  const size_t o_code = o; o = align256(o + nP);
-  const size_t o_node = o; o = align256(o + nP * 4);
-  const size_t o_fk = o; o = align256(o + nP * 4);
-  const size_t o_leader = o; o = align256(o + nP * 4);
-  const size_t o_lperm = o; o = align256(o + nP);
-  const size_t o_rg = o; o = align256(o + cap * 4);
-  const size_t o_rp = o; o = align256(o + cap * 4);
-  const size_t o_ft = o; o = align256(o + cap * 8);
-  const size_t o_rt = o; o = align256(o + cap * 8);
-  const size_t o_info = o; o = align256(o + 512);
-  HIPCHK(c, c->d_seq.reserve(o));
+  Carve cv;
+  const auto o_sc07 = cv.take<int64_t>(stride * L);
+  const auto o_sc10 = cv.take<int64_t>(stride * L);
+  const auto o_meta = cv.take<uint32_t>(stride);
+  const auto o_keys = cv.take<unsigned long long>(nG);
+  const auto o_wait = cv.take<unsigned long long>(nP);
+  const auto o_head = cv.take<uint32_t>(nG);
+  const auto o_nwait = cv.take<uint32_t>(nG);
+  const auto o_slot = cv.take<uint32_t>(nG);
+  const auto o_tfirst = cv.take<unsigned long long>(nG);
+  const size_t o_res = cv.mark();                           // results: one D2H
+  const auto o_code = cv.take<uint8_t>(nP);
+  const auto o_node = cv.take<int32_t>(nP);
+  const auto o_fk = cv.take<uint32_t>(nP);
+  const auto o_leader = cv.take<int32_t>(nP);
+  const auto o_lperm = cv.take<uint8_t>(nP);
+  const auto o_rg = cv.take<uint32_t>(cap);
+  const auto o_rp = cv.take<uint32_t>(cap);
+  const auto o_ft = cv.take<unsigned long long>(cap);
+  const auto o_rt = cv.take<unsigned long long>(cap);
+  const auto o_info = cv.take<unsigned long long>(64);
+  HIPCHK(c, c->d_seq.reserve(cv.mark()));
   uint8_t* base = c->d_seq.as<uint8_t>();
   GroupsDev gr = groups_dev(c);
   SeqDev sq{};
@@ -3352,27 +3375,27 @@ int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
   sq.g_minres = const_cast<int64_t*>(gr.minres);
   sq.g_mrpres = const_cast<uint32_t*>(gr.mrpres);
   sq.g_occ = const_cast<uint64_t*>(gr.occupied);
-  sq.left07 = reinterpret_cast<int64_t*>(base + o_sc07);
-  sq.left10 = reinterpret_cast<int64_t*>(base + o_sc10);
-  sq.nmeta = reinterpret_cast<uint32_t*>(base + o_meta);
-  sq.keys = reinterpret_cast<unsigned long long*>(base + o_keys);
-  sq.wait_rec = reinterpret_cast<unsigned long long*>(base + o_wait);
-  sq.head = reinterpret_cast<uint32_t*>(base + o_head);
-  sq.nwait = reinterpret_cast<uint32_t*>(base + o_nwait);
-  sq.slot_of = reinterpret_cast<uint32_t*>(base + o_slot);
-  sq.t_first = reinterpret_cast<unsigned long long*>(base + o_tfirst);
+  sq.left07 = o_sc07.in(base);
+  sq.left10 = o_sc10.in(base);
+  sq.nmeta = o_meta.in(base);
+  sq.keys = o_keys.in(base);
+  sq.wait_rec = o_wait.in(base);
+  sq.head = o_head.in(base);
+  sq.nwait = o_nwait.in(base);
+  sq.slot_of = o_slot.in(base);
+  sq.t_first = o_tfirst.in(base);
   sq.pclass = pclass_dev(c);
-  sq.pf_code = base + o_code;
-  sq.pod_node = reinterpret_cast<int32_t*>(base + o_node);
-  sq.pf_first_k = reinterpret_cast<uint32_t*>(base + o_fk);
-  sq.pf_leader = reinterpret_cast<int32_t*>(base + o_leader);
-  sq.last_permitted = base + o_lperm;
-  sq.released_group = reinterpret_cast<uint32_t*>(base + o_rg);
-  sq.released_pods = reinterpret_cast<uint32_t*>(base + o_rp);
-  sq.first_tick = reinterpret_cast<unsigned long long*>(base + o_ft);
-  sq.ready_tick = reinterpret_cast<unsigned long long*>(base + o_rt);
+  sq.pf_code = o_code.in(base);
+  sq.pod_node = o_node.in(base);
+  sq.pf_first_k = o_fk.in(base);
+  sq.pf_leader = o_leader.in(base);
+  sq.last_permitted = o_lperm.in(base);
+  sq.released_group = o_rg.in(base);
+  sq.released_pods = o_rp.in(base);
+  sq.first_tick = o_ft.in(base);
+  sq.ready_tick = o_rt.in(base);
   sq.cap = out->cap;
-  sq.info = reinterpret_cast<unsigned long long*>(base + o_info);
+  sq.info = o_info.in(base);
   SeqParams prm{};
   prm.S = c->S;
   prm.eph_gate = c->cfg.eph_gate;
@@ -3396,17 +3419,17 @@ int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
   }
   // first-fit cursors per request class (bs_seq.hpp, seq_pick): BS_SEQ_NO_CURSOR=1 = every search starts at the head of the list
   prm.use_cursor = (P && sq.pclass && !(std::getenv("BS_SEQ_NO_CURSOR") && std::atoi(std::getenv("BS_SEQ_NO_CURSOR")))) ? 1u : 0u;
-  HIPCHK(c, hipMemsetAsync(base + o_info, 0, 512, c->stream));
+  HIPCHK(c, hipMemsetAsync(o_info.in(base), 0, o_info.bytes(), c->stream));
   const PodsDev pd = pods_dev(c);
   const NodesDev nd = nodes_dev(c);
   launch_seq(c->stream, c->S, lds, pd, gr, nd, sq, prm);
   LAUNCHCHK(c, BS_KERNEL_QUERY);
   // ---- results: one copy of the whole result block, then the caller's arrays
-  std::vector<uint8_t> res(o - o_res);
+  std::vector<uint8_t> res(cv.mark() - o_res);
   HIPCHK(c, hipMemcpyAsync(res.data(), base + o_res, res.size(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint8_t* rb = res.data() - o_res;
-  const unsigned long long* info = reinterpret_cast<const unsigned long long*>(rb + o_info);
+  const unsigned long long* info = o_info.in(rb);
   int khz = 0;
   if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->cfg.device) != hipSuccess || khz <= 0) khz = 100000;   // 100 MHz
   auto to_ns = [&](unsigned long long ticks) { return (int64_t)((long double)ticks * 1.0e6L / (long double)khz); };
@@ -3432,19 +3455,19 @@ int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
     }
   }
   if (P) {
-    if (out->pf_code) std::memcpy(out->pf_code, rb + o_code, P);
-    if (out->pod_node) std::memcpy(out->pod_node, rb + o_node, (size_t)P * 4);
-    if (out->pf_first_k) std::memcpy(out->pf_first_k, rb + o_fk, (size_t)P * 4);
-    if (out->pf_leader) std::memcpy(out->pf_leader, rb + o_leader, (size_t)P * 4);
-    if (out->last_permitted) { if (prm.filter_deny) std::memcpy(out->last_permitted, rb + o_lperm, P); else std::memset(out->last_permitted, 0, P); }
+    if (out->pf_code) std::memcpy(out->pf_code, o_code.in(rb), P);
+    if (out->pod_node) std::memcpy(out->pod_node, o_node.in(rb), (size_t)P * 4);
+    if (out->pf_first_k) std::memcpy(out->pf_first_k, o_fk.in(rb), (size_t)P * 4);
+    if (out->pf_leader) std::memcpy(out->pf_leader, o_leader.in(rb), (size_t)P * 4);
+    if (out->last_permitted) { if (prm.filter_deny) std::memcpy(out->last_permitted, o_lperm.in(rb), P); else std::memset(out->last_permitted, 0, P); }
     c->sop_leader0 = (int32_t)(uint32_t)info[4] - 1;         // sop.maxFinishedPG as the pass left it
   }
   const uint32_t k = std::min(out->n_released, out->cap);
   if (k) {
-    if (out->released_group) std::memcpy(out->released_group, rb + o_rg, (size_t)k * 4);
-    if (out->released_pods) std::memcpy(out->released_pods, rb + o_rp, (size_t)k * 4);
-    const unsigned long long* ft = reinterpret_cast<const unsigned long long*>(rb + o_ft);
-    const unsigned long long* rt = reinterpret_cast<const unsigned long long*>(rb + o_rt);
+    if (out->released_group) std::memcpy(out->released_group, o_rg.in(rb), (size_t)k * 4);
+    if (out->released_pods) std::memcpy(out->released_pods, o_rp.in(rb), (size_t)k * 4);
+    const unsigned long long* ft = o_ft.in(rb);
+    const unsigned long long* rt = o_rt.in(rb);
     for (uint32_t i = 0; i < k; ++i) {
       if (out->first_ns) out->first_ns[i] = to_ns(ft[i]);
       if (out->ready_ns) out->ready_ns[i] = to_ns(rt[i]);
@@ -3476,7 +3499,7 @@ int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
     if ((rc = analyse_groups(c))) return rc;
     if ((rc = maybe_analyse_epochs(c))) return rc;
   }
-  c->seq_o_wait = o_wait;
+  c->seq_o_wait = o_wait;                                  // (the pieces: seq_expire_dev addresses them in d_seq)
   c->seq_o_head = o_head;
   c->seq_o_nwait = o_nwait;
   c->seq_wait_valid = true;
@@ -3497,11 +3520,10 @@ static int seq_wait_state(bs_ctx* c, const char* who) {
 
 static SeqExpireDev seq_expire_dev(bs_ctx* c) {
   SeqExpireDev a{};
-  uint8_t* base = c->d_seq.as<uint8_t>();
   const GroupsDev gr = groups_dev(c);
-  a.wait_rec = reinterpret_cast<const unsigned long long*>(base + c->seq_o_wait);
-  a.head = reinterpret_cast<uint32_t*>(base + c->seq_o_head);
-  a.nwait = reinterpret_cast<uint32_t*>(base + c->seq_o_nwait);
+  a.wait_rec = c->seq_o_wait.in(c->d_seq.p);
+  a.head = c->seq_o_head.in(c->d_seq.p);
+  a.nwait = c->seq_o_nwait.in(c->d_seq.p);
   a.P = c->P;
   a.G = c->G;
   a.g_matched = const_cast<uint32_t*>(gr.matched);
@@ -3528,56 +3550,60 @@ int bs_seq_expire(bs_ctx* c, uint32_t count, const uint32_t* group, uint32_t fla
   if (!M) return BS_OK;
   const uint32_t rec_cap = std::min(N, P), nblk = cdiv(M, kSeBlock);
   // ---- the per-node scratch: zero between calls
+  Carve nv;
+  const size_t nN = std::max<uint32_t>(N, 1);
+  const auto o_delta = nv.take<unsigned long long>(nN * L);
+  const auto o_nbits = nv.take<uint32_t>(nN);
+  const auto o_dirty = nv.take<uint32_t>(nN);
   {
-    const size_t bytes = align256((size_t)std::max<uint32_t>(N, 1) * L * 8) + 2 * align256((size_t)std::max<uint32_t>(N, 1) * 4);
     const void* was = c->d_sexp_nodes.p;
-    HIPCHK(c, c->d_sexp_nodes.reserve(bytes));
+    HIPCHK(c, c->d_sexp_nodes.reserve(nv.mark()));
     if (!c->sexp_clean || was != c->d_sexp_nodes.p || c->sexp_n != N || c->sexp_l != L) {
-      HIPCHK(c, hipMemsetAsync(c->d_sexp_nodes.p, 0, bytes, c->stream));
+      HIPCHK(c, hipMemsetAsync(c->d_sexp_nodes.p, 0, nv.mark(), c->stream));
       c->sexp_n = N;
       c->sexp_l = L;
     }
     c->sexp_clean = false;                                   // until this call's k_se_nodes is known to have run
   }
-  size_t o = 0;
-  const size_t o_info = o; o = align256(o + 16);
-  const size_t o_list = o; o = align256(o + (size_t)M * 4);
-  const size_t o_bsum = o; o = align256(o + (size_t)nblk * 8);
-  const size_t o_group = o; o = align256(o + (size_t)M * 4);
-  const size_t o_gpods = o; o = align256(o + (size_t)M * 4);
-  const size_t o_gearl = o; o = align256(o + (size_t)M * 4);
-  const size_t o_off = o; o = align256(o + (size_t)M * 4);
-  const size_t o_pod = o; o = align256(o + (size_t)std::max<uint32_t>(P, 1) * 4);
-  const size_t o_node = o; o = align256(o + (size_t)std::max<uint32_t>(P, 1) * 4);
-  const size_t o_dlist = o; o = align256(o + (size_t)std::max<uint32_t>(rec_cap, 1) * 4);
-  const size_t o_rec = o; o = align256(o + (size_t)std::max<uint32_t>(rec_cap, 1) * sizeof(bs_node_request));
-  HIPCHK(c, c->d_sexp.reserve(o));
-  uint8_t* base = c->d_sexp.as<uint8_t>();
-  uint8_t* nb = c->d_sexp_nodes.as<uint8_t>();
+  Carve cv;
+  const auto o_info = cv.take<uint32_t>(4);
+  const auto o_list = cv.take<uint32_t>(M);
+  const auto o_bsum = cv.take<unsigned long long>(nblk);
+  const auto o_group = cv.take<uint32_t>(M);
+  const auto o_gpods = cv.take<uint32_t>(M);
+  const auto o_gearl = cv.take<uint32_t>(M);
+  const auto o_off = cv.take<uint32_t>(M);
+  const auto o_pod = cv.take<uint32_t>(std::max<uint32_t>(P, 1));
+  const auto o_node = cv.take<uint32_t>(std::max<uint32_t>(P, 1));
+  const auto o_dlist = cv.take<uint32_t>(std::max<uint32_t>(rec_cap, 1));
+  const auto o_rec = cv.take<bs_node_request>(std::max<uint32_t>(rec_cap, 1));
+  HIPCHK(c, c->d_sexp.reserve(cv.mark()));
+  void* base = c->d_sexp.p;
+  void* nb = c->d_sexp_nodes.p;
   SeqExpireDev a = seq_expire_dev(c);
   a.M = M;
   a.deny = deny ? 1u : 0u;
-  a.list = all ? nullptr : reinterpret_cast<const uint32_t*>(base + o_list);
-  a.bsum = reinterpret_cast<unsigned long long*>(base + o_bsum);
-  a.info = reinterpret_cast<uint32_t*>(base + o_info);
-  a.o_group = reinterpret_cast<uint32_t*>(base + o_group);
-  a.o_gpods = reinterpret_cast<uint32_t*>(base + o_gpods);
-  a.o_gearlier = reinterpret_cast<uint32_t*>(base + o_gearl);
-  a.o_off = reinterpret_cast<uint32_t*>(base + o_off);
-  a.o_pod = reinterpret_cast<uint32_t*>(base + o_pod);
-  a.o_node = reinterpret_cast<uint32_t*>(base + o_node);
-  a.dlist = reinterpret_cast<uint32_t*>(base + o_dlist);
-  a.delta = reinterpret_cast<unsigned long long*>(nb);
-  a.nbits = reinterpret_cast<uint32_t*>(nb + align256((size_t)std::max<uint32_t>(N, 1) * L * 8));
-  a.dirty = reinterpret_cast<uint32_t*>(nb + align256((size_t)std::max<uint32_t>(N, 1) * L * 8) + align256((size_t)std::max<uint32_t>(N, 1) * 4));
-  bs_node_request* recs = reinterpret_cast<bs_node_request*>(base + o_rec);
-  HIPCHK(c, hipMemsetAsync(base + o_info, 0, 16, c->stream));
-  if (!all) HIPCHK(c, hipMemcpyAsync(base + o_list, group, (size_t)M * 4, hipMemcpyHostToDevice, c->stream));
+  a.list = all ? nullptr : o_list.in(base);
+  a.bsum = o_bsum.in(base);
+  a.info = o_info.in(base);
+  a.o_group = o_group.in(base);
+  a.o_gpods = o_gpods.in(base);
+  a.o_gearlier = o_gearl.in(base);
+  a.o_off = o_off.in(base);
+  a.o_pod = o_pod.in(base);
+  a.o_node = o_node.in(base);
+  a.dlist = o_dlist.in(base);
+  a.delta = o_delta.in(nb);
+  a.nbits = o_nbits.in(nb);
+  a.dirty = o_dirty.in(nb);
+  bs_node_request* recs = o_rec.in(base);
+  HIPCHK(c, hipMemsetAsync(o_info.in(base), 0, o_info.bytes(), c->stream));
+  if (!all) HIPCHK(c, hipMemcpyAsync(o_list.in(base), group, o_list.bytes(), hipMemcpyHostToDevice, c->stream));
   c->first_reach_hint = 0xFFFFFFFFu;                        // (as bs_groups_apply: deny entries decide which pod reaches findMaxPG first)
   launch_seq_expire(c->stream, c->S, a, pods_dev(c), nodes_dev(c), recs, rec_cap);
   LAUNCHCHK(c, BS_KERNEL_PREPASS);
   uint32_t info[4] = {0, 0, 0, 0};
-  HIPCHK(c, hipMemcpyAsync(info, base + o_info, 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(info, o_info.in(base), o_info.bytes(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint32_t ng = info[0], np = info[1], nrec = info[2];
   if (ng > M || np > P || nrec > rec_cap) { c->last_error = "bs_seq_expire: the waiting chains name more than the queue holds"; return BS_ERR_HIP; }
@@ -3593,17 +3619,17 @@ int bs_seq_expire(bs_ctx* c, uint32_t count, const uint32_t* group, uint32_t fla
   }
   const uint32_t kg = std::min(ng, out->group_cap), kp = std::min(np, out->pod_cap);
   if (kg) {
-    HIPCHK(c, hipMemcpyAsync(out->group, base + o_group, (size_t)kg * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->group_pods, base + o_gpods, (size_t)kg * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->group_earlier, base + o_gearl, (size_t)kg * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->group, o_group.in(base), (size_t)kg * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->group_pods, o_gpods.in(base), (size_t)kg * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->group_earlier, o_gearl.in(base), (size_t)kg * 4, hipMemcpyDeviceToHost, c->stream));
   }
   if (kp) {
-    HIPCHK(c, hipMemcpyAsync(out->pod, base + o_pod, (size_t)kp * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->node, base + o_node, (size_t)kp * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->pod, o_pod.in(base), (size_t)kp * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->node, o_node.in(base), (size_t)kp * 4, hipMemcpyDeviceToHost, c->stream));
   }
   if (deny && all && ng) {
     hg.resize(ng);
-    HIPCHK(c, hipMemcpyAsync(hg.data(), base + o_group, (size_t)ng * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hg.data(), o_group.in(base), (size_t)ng * 4, hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   mirror_node_requests(c, reinterpret_cast<const bs_node_request*>(hr.data()), nrec);
@@ -3628,12 +3654,14 @@ int bs_seq_waiting_read(bs_ctx* c, uint32_t p, int32_t* wait_node) {
   if (p != c->P) { c->last_error = "bs_seq_waiting_read: p differs from the queue length"; return BS_ERR_INVALID; }
   if ((rc = use_device(c))) return rc;
   if (!p) return BS_OK;
-  HIPCHK(c, c->d_sexp.reserve(align256((size_t)p * 4)));
-  int32_t* wn = c->d_sexp.as<int32_t>();
-  HIPCHK(c, hipMemsetAsync(wn, 0xFF, (size_t)p * 4, c->stream));
+  Carve cv;
+  const auto o_wn = cv.take<int32_t>(p);
+  HIPCHK(c, c->d_sexp.reserve(cv.mark()));
+  int32_t* wn = o_wn.in(c->d_sexp.p);
+  HIPCHK(c, hipMemsetAsync(wn, 0xFF, o_wn.bytes(), c->stream));
   launch_seq_waiting(c->stream, seq_expire_dev(c), wn);
   LAUNCHCHK(c, BS_KERNEL_PREPASS);
-  HIPCHK(c, hipMemcpyAsync(wait_node, wn, (size_t)p * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(wait_node, wn, o_wn.bytes(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return BS_OK;
 }
@@ -3915,26 +3943,21 @@ int bs_bound_load(bs_ctx* c, const bs_bound_soa* bd) {
   const size_t o = bound_layout(L, N, B, lay);
   c->blay = lay;
   std::vector<uint8_t> h(o, 0);
-  std::memcpy(h.data() + c->blay.boff, cnt.data(), ((size_t)N + 1) * 4);
-  int32_t* prio = reinterpret_cast<int32_t*>(h.data() + c->blay.prio);
-  int64_t* start = reinterpret_cast<int64_t*>(h.data() + c->blay.start);
-  int32_t* grp = reinterpret_cast<int32_t*>(h.data() + c->blay.group);
-  uint32_t* id = reinterpret_cast<uint32_t*>(h.data() + c->blay.id);
-  int64_t* req = reinterpret_cast<int64_t*>(h.data() + c->blay.req);
-  uint32_t* pres = reinterpret_cast<uint32_t*>(h.data() + c->blay.pres);
+  const auto ht = bound_cols(h.data(), lay);
+  std::memcpy(ht.boff, cnt.data(), ((size_t)N + 1) * 4);
   const uint32_t smask = (uint32_t)((1ull << (L - BS_FIXED_LANES)) - 1ull);
   for (uint32_t r = 0; r < B; ++r) {
     const uint32_t i = order[r];
-    pres[r] = bd->req_present[i] & smask;
-    prio[r] = bd->priority[i];
-    start[r] = bd->start_ns[i];
-    grp[r] = bd->group[i];
-    id[r] = i;
+    ht.pres[r] = bd->req_present[i] & smask;
+    ht.prio[r] = bd->priority[i];
+    ht.start[r] = bd->start_ns[i];
+    ht.group[r] = bd->group[i];
+    ht.id[r] = i;
     for (uint32_t l = 0; l < L; ++l) {
       int64_t v = bd->req[(size_t)l * B + i];
       if (l == BS_LANE_PODS) v = 1;                                        // RemovePod: one pod less
       else if (l >= BS_FIXED_LANES && !((bd->req_present[i] >> (l - BS_FIXED_LANES)) & 1u)) v = 0;   // no key: nothing to subtract
-      req[(size_t)l * nB + r] = v;
+      ht.req[(size_t)l * nB + r] = v;
     }
   }
   c->have_bound = false;
@@ -3958,7 +3981,7 @@ int bs_bound_pdb_set(bs_ctx* c, uint32_t b, const uint8_t* violating) {
   const uint32_t B = c->bound_b, N = c->bound_n;
   int rc = use_device(c);
   if (rc) return rc;
-  uint8_t* bb = c->d_bound.as<uint8_t>();
+  const auto bt = bound_cols(c->d_bound.as<uint8_t>(), c->blay);
   const size_t nB = std::max<uint32_t>(B, 1), nN = std::max<uint32_t>(N, 1);
   // the two columns are rebuilt on the host through the id column (the id -> position map; evicted ids are not in it) and copied in
   // stream order, behind whatever preemption call is still running
@@ -3966,8 +3989,8 @@ int bs_bound_pdb_set(bs_ctx* c, uint32_t b, const uint8_t* violating) {
   std::vector<uint32_t> nviol(nN, 0);
   if (violating && B) {
     std::vector<uint32_t> boff((size_t)N + 1), id(B);
-    HIPCHK(c, hipMemcpyAsync(boff.data(), bb + c->blay.boff, ((size_t)N + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(id.data(), bb + c->blay.id, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(boff.data(), bt.boff, ((size_t)N + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(id.data(), bt.id, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (uint32_t k = 0; k < N; ++k)
       for (uint32_t j = boff[k]; j < boff[k + 1] && j < B; ++j) {
@@ -3975,8 +3998,8 @@ int bs_bound_pdb_set(bs_ctx* c, uint32_t b, const uint8_t* violating) {
         nviol[k] += bits[j];
       }
   }
-  HIPCHK(c, hipMemcpyAsync(bb + c->blay.pdb, bits.data(), nB, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(bb + c->blay.nviol, nviol.data(), nN * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(bt.pdb, bits.data(), nB, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(bt.nviol, nviol.data(), nN * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));             // (local buffers)
   return BS_OK;
 }
@@ -4010,12 +4033,9 @@ int pdb_csr_check(bs_ctx* c, const char* who, uint32_t n, const uint32_t* member
 
 // the recompute behind whatever the caller enqueued (count staged pairs go into allowed[] first); waits for it
 int pdb_recompute(bs_ctx* c, uint32_t count, const uint32_t* index, const int32_t* value) {
-  uint8_t* bb = c->d_bound.as<uint8_t>();
   PdbDev a{};
-  a.boff = reinterpret_cast<const uint32_t*>(bb + c->blay.boff);
-  a.bid = reinterpret_cast<const uint32_t*>(bb + c->blay.id);
-  a.bpdb = bb + c->blay.pdb;
-  a.bnviol = reinterpret_cast<uint32_t*>(bb + c->blay.nviol);
+  const auto bt = bound_cols(c->d_bound.as<uint8_t>(), c->blay);
+  a.boff = bt.boff; a.bid = bt.id; a.bpdb = bt.pdb; a.bnviol = bt.nviol;
   a.n = c->bound_n;
   a.moff = c->d_pdb_moff.as<uint32_t>();
   a.member = c->d_pdb_member.as<uint32_t>();
@@ -4126,7 +4146,7 @@ int bs_pdb_read(bs_ctx* c, uint32_t* n_pdb_out, uint32_t* covered_out, int32_t* 
   if (covered_out) *covered_out = c->pdb_covered;
   if (allowed_out && c->pdb_n) HIPCHK(c, hipMemcpy(allowed_out, c->d_pdb_allowed.p, (size_t)c->pdb_n * 4, hipMemcpyDeviceToHost));
   if (node_violating_out && c->bound_n)
-    HIPCHK(c, hipMemcpy(node_violating_out, c->d_bound.as<uint8_t>() + c->blay.nviol, (size_t)c->bound_n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(node_violating_out, bound_cols(c->d_bound.as<const uint8_t>(), c->blay).nviol, (size_t)c->bound_n * 4, hipMemcpyDeviceToHost));
   return BS_OK;
 }
 
@@ -4172,94 +4192,84 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   const PreemptGeom geom = preempt_geom(N, count, c->test_pc_chunk_nodes);   // slot tiles x node chunks (bs_preempt_geom.hpp)
   const uint32_t tiles = geom.tiles, nchunks = geom.nchunks, chunk_nodes = geom.chunk_nodes;
   const size_t nQ = count, nG = std::max<uint32_t>(G, 1), nR = (size_t)nchunks * nQ, nV = std::max<size_t>((size_t)nQ * victim_cap, 1);
-  size_t o = 0;
-  const size_t o_spod = o; o = align256(o + nQ * 4);
-  const size_t o_sprio = o; o = align256(o + nQ * 4);
-  const size_t o_sorig = o; o = align256(o + nQ * 4);
-  const size_t o_gprot = o; o = align256(o + nG);
-  const size_t in_bytes = o;
-  const size_t o_rnode = o; o = align256(o + nR * 4);
-  const size_t o_rnv = o; o = align256(o + nR * 4);
-  const size_t o_rnpv = o; o = align256(o + nR * 4);
-  const size_t o_rtop = o; o = align256(o + nR * 4);
-  const size_t o_rsum = o; o = align256(o + nR * 8);
-  const size_t o_rest = o; o = align256(o + nR * 8);
-  const size_t o_rncand = o; o = align256(o + nR * 4);
-  const size_t o_res = o;                                 // results: one D2H
-  const size_t o_node = o; o = align256(o + nQ * 4);
-  const size_t o_ncand = o; o = align256(o + nQ * 4);
-  const size_t o_nv = o; o = align256(o + nQ * 4);
-  const size_t o_npv = o; o = align256(o + nQ * 4);
-  const size_t o_top = o; o = align256(o + nQ * 4);
-  const size_t o_sum = o; o = align256(o + nQ * 8);
-  const size_t o_est = o; o = align256(o + nQ * 8);
-  const size_t o_vic = o; o = align256(o + nV * 4);
-  HIPCHK(c, c->d_pre.reserve(o));
+  Carve cv;
+  const auto o_spod = cv.take<uint32_t>(nQ);
+  const auto o_sprio = cv.take<int32_t>(nQ);
+  const auto o_sorig = cv.take<uint32_t>(nQ);
+  const auto o_gprot = cv.take<uint8_t>(nG);
+  const size_t in_bytes = cv.mark();
+  const auto o_rnode = cv.take<int32_t>(nR);
+  const auto o_rnv = cv.take<uint32_t>(nR);
+  const auto o_rnpv = cv.take<uint32_t>(nR);
+  const auto o_rtop = cv.take<int32_t>(nR);
+  const auto o_rsum = cv.take<int64_t>(nR);
+  const auto o_rest = cv.take<int64_t>(nR);
+  const auto o_rncand = cv.take<uint32_t>(nR);
+  const size_t o_res = cv.mark();                           // results: one D2H
+  const auto o_node = cv.take<int32_t>(nQ);
+  const auto o_ncand = cv.take<uint32_t>(nQ);
+  const auto o_nv = cv.take<uint32_t>(nQ);
+  const auto o_npv = cv.take<uint32_t>(nQ);
+  const auto o_top = cv.take<int32_t>(nQ);
+  const auto o_sum = cv.take<int64_t>(nQ);
+  const auto o_est = cv.take<int64_t>(nQ);
+  const auto o_vic = cv.take<uint32_t>(nV);
+  HIPCHK(c, c->d_pre.reserve(cv.mark()));
   std::vector<uint8_t> in(in_bytes, 0);
-  uint32_t* spod = reinterpret_cast<uint32_t*>(in.data() + o_spod);
-  int32_t* sprio = reinterpret_cast<int32_t*>(in.data() + o_sprio);
-  uint32_t* sorig = reinterpret_cast<uint32_t*>(in.data() + o_sorig);
   for (uint32_t s = 0; s < count; ++s) {
-    spod[s] = pod_index[perm[s]];
-    sprio[s] = priority[perm[s]];
-    sorig[s] = perm[s];
+    o_spod.in(in.data())[s] = pod_index[perm[s]];
+    o_sprio.in(in.data())[s] = priority[perm[s]];
+    o_sorig.in(in.data())[s] = perm[s];
   }
-  if (G) std::memcpy(in.data() + o_gprot, group_protected, G);
+  if (G) std::memcpy(o_gprot.in(in.data()), group_protected, G);
   uint8_t* base = c->d_pre.as<uint8_t>();
   HIPCHK(c, hipMemcpyAsync(base, in.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
-  const uint8_t* bb = c->d_bound.as<uint8_t>();
   PreemptDev pe{};
-  pe.boff = reinterpret_cast<const uint32_t*>(bb + c->blay.boff);
-  pe.bprio = reinterpret_cast<const int32_t*>(bb + c->blay.prio);
-  pe.bstart = reinterpret_cast<const int64_t*>(bb + c->blay.start);
-  pe.bgroup = reinterpret_cast<const int32_t*>(bb + c->blay.group);
-  pe.bid = reinterpret_cast<const uint32_t*>(bb + c->blay.id);
-  pe.breq = reinterpret_cast<const int64_t*>(bb + c->blay.req);
-  pe.bpdb = bb + c->blay.pdb;
-  pe.bnviol = reinterpret_cast<const uint32_t*>(bb + c->blay.nviol);
+  const auto bt = bound_dev(pe, c->d_bound.as<const uint8_t>(), c->blay);
+  pe.bnviol = bt.nviol;
   pe.bstride = std::max<uint32_t>(c->bound_b, 1);
   pe.q = count;
   pe.nchunks = nchunks;
   pe.chunk_nodes = chunk_nodes;
   pe.cap = victim_cap;
-  pe.spod = reinterpret_cast<const uint32_t*>(base + o_spod);
-  pe.sprio = reinterpret_cast<const int32_t*>(base + o_sprio);
-  pe.sorig = reinterpret_cast<const uint32_t*>(base + o_sorig);
-  pe.gprot = base + o_gprot;
-  pe.r_node = reinterpret_cast<int32_t*>(base + o_rnode);
-  pe.r_nv = reinterpret_cast<uint32_t*>(base + o_rnv);
-  pe.r_npv = reinterpret_cast<uint32_t*>(base + o_rnpv);
-  pe.r_top = reinterpret_cast<int32_t*>(base + o_rtop);
-  pe.r_sum = reinterpret_cast<int64_t*>(base + o_rsum);
-  pe.r_est = reinterpret_cast<int64_t*>(base + o_rest);
-  pe.r_ncand = reinterpret_cast<uint32_t*>(base + o_rncand);
-  pe.o_node = reinterpret_cast<int32_t*>(base + o_node);
-  pe.o_ncand = reinterpret_cast<uint32_t*>(base + o_ncand);
-  pe.o_nv = reinterpret_cast<uint32_t*>(base + o_nv);
-  pe.o_npv = reinterpret_cast<uint32_t*>(base + o_npv);
-  pe.o_top = reinterpret_cast<int32_t*>(base + o_top);
-  pe.o_sum = reinterpret_cast<int64_t*>(base + o_sum);
-  pe.o_est = reinterpret_cast<int64_t*>(base + o_est);
-  pe.o_victims = reinterpret_cast<uint32_t*>(base + o_vic);
+  pe.spod = o_spod.in(base);
+  pe.sprio = o_sprio.in(base);
+  pe.sorig = o_sorig.in(base);
+  pe.gprot = o_gprot.in(base);
+  pe.r_node = o_rnode.in(base);
+  pe.r_nv = o_rnv.in(base);
+  pe.r_npv = o_rnpv.in(base);
+  pe.r_top = o_rtop.in(base);
+  pe.r_sum = o_rsum.in(base);
+  pe.r_est = o_rest.in(base);
+  pe.r_ncand = o_rncand.in(base);
+  pe.o_node = o_node.in(base);
+  pe.o_ncand = o_ncand.in(base);
+  pe.o_nv = o_nv.in(base);
+  pe.o_npv = o_npv.in(base);
+  pe.o_top = o_top.in(base);
+  pe.o_sum = o_sum.in(base);
+  pe.o_est = o_est.in(base);
+  pe.o_victims = o_vic.in(base);
   launch_preempt(c->stream, c->S, dim3(tiles, nchunks), nodes_dev(c), pods_dev(c), pe);
   LAUNCHCHK(c, BS_KERNEL_QUERY);
-  std::vector<uint8_t> res(o - o_res);
+  std::vector<uint8_t> res(cv.mark() - o_res);
   HIPCHK(c, hipMemcpyAsync(res.data(), base + o_res, res.size(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint8_t* rb = res.data() - o_res;
-  std::memcpy(out->node, rb + o_node, nQ * 4);
-  std::memcpy(out->n_victims, rb + o_nv, nQ * 4);
-  c->pre_npv.assign(reinterpret_cast<const uint32_t*>(rb + o_npv), reinterpret_cast<const uint32_t*>(rb + o_npv) + nQ);
+  std::memcpy(out->node, o_node.in(rb), o_node.bytes());
+  std::memcpy(out->n_victims, o_nv.in(rb), o_nv.bytes());
+  c->pre_npv.assign(o_npv.in(rb), o_npv.in(rb) + nQ);
   c->have_pre_npv = true;
   c->have_gang = false;
-  if (out->n_candidates) std::memcpy(out->n_candidates, rb + o_ncand, nQ * 4);
-  if (out->top_priority) std::memcpy(out->top_priority, rb + o_top, nQ * 4);
-  if (out->priority_sum) std::memcpy(out->priority_sum, rb + o_sum, nQ * 8);
-  if (out->earliest_start) std::memcpy(out->earliest_start, rb + o_est, nQ * 8);
+  if (out->n_candidates) std::memcpy(out->n_candidates, o_ncand.in(rb), o_ncand.bytes());
+  if (out->top_priority) std::memcpy(out->top_priority, o_top.in(rb), o_top.bytes());
+  if (out->priority_sum) std::memcpy(out->priority_sum, o_sum.in(rb), o_sum.bytes());
+  if (out->earliest_start) std::memcpy(out->earliest_start, o_est.in(rb), o_est.bytes());
   if (victim_cap) {
     // rows are written up to min(n_victims, cap); the rest of a row is unspecified: zero it for the caller
-    const uint32_t* nv = reinterpret_cast<const uint32_t*>(rb + o_nv);
-    const uint32_t* vic = reinterpret_cast<const uint32_t*>(rb + o_vic);
+    const uint32_t* nv = o_nv.in(rb);
+    const uint32_t* vic = o_vic.in(rb);
     for (size_t q = 0; q < nQ; ++q) {
       const uint32_t k = std::min(nv[q], victim_cap);
       std::memcpy(out->victims + q * victim_cap, vic + q * victim_cap, (size_t)k * 4);
@@ -4351,149 +4361,132 @@ static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const
   const uint32_t tiles = geom.tiles, nchunks = geom.nchunks, chunk_nodes = geom.chunk_nodes;
   const size_t nQ = count, nG = std::max<uint32_t>(G, 1), nR = (size_t)nchunks * nQ, nV = std::max<size_t>((size_t)nQ * victim_cap, 1);
   const size_t nN = std::max<uint32_t>(N, 1), nB = std::max<uint32_t>(B, 1);
-  size_t o = 0;
-  const size_t o_spod = o; o = align256(o + nQ * 4);
-  const size_t o_sprio = o; o = align256(o + nQ * 4);
-  const size_t o_sorig = o; o = align256(o + nQ * 4);
-  const size_t o_gprot = o; o = align256(o + nG);
+  Carve cv;
+  const auto o_spod = cv.take<uint32_t>(nQ);
+  const auto o_sprio = cv.take<int32_t>(nQ);
+  const auto o_sorig = cv.take<uint32_t>(nQ);
+  const auto o_gprot = cv.take<uint8_t>(nG);
   const size_t gQ = gang ? nQ : 0, gB = gang ? nB : 0;    // gang columns: no bytes in bs_preempt_commit's blob
-  const size_t o_gneed = o; o = align256(o + gQ * 4);
-  const size_t o_grlen = o; o = align256(o + gQ * 4);
-  const size_t in_bytes = o;
-  const size_t o_rnode = o; o = align256(o + nR * kPcK * 4);
-  const size_t o_rnv = o; o = align256(o + nR * kPcK * 4);
-  const size_t o_rnpv = o; o = align256(o + nR * kPcK * 4);
-  const size_t o_rtop = o; o = align256(o + nR * kPcK * 4);
-  const size_t o_rsum = o; o = align256(o + nR * kPcK * 8);
-  const size_t o_rest = o; o = align256(o + nR * kPcK * 8);
-  const size_t o_rncand = o; o = align256(o + nR * 4);
-  const size_t o_work = o;                                // zeroed working state
-  const size_t o_dv = o; o = align256(o + (size_t)L * nN * 8);
-  const size_t o_dn = o; o = align256(o + (size_t)L * nN * 8);
-  const size_t o_vbits = o; o = align256(o + nN * 4);
-  const size_t o_nbits = o; o = align256(o + nN * 4);
-  const size_t o_dirty = o; o = align256(o + nN);
-  const size_t o_dead = o; o = align256(o + nB);
-  const size_t o_gtag = o; o = align256(o + gB * 4);
-  const size_t o_gplaced = o; o = align256(o + gQ * 4);
-  const size_t o_gvoided = o; o = align256(o + gQ);
-  const size_t work_bytes = o - o_work;
-  const size_t o_gslog = o; o = align256(o + gQ * 3 * 4);
-  const size_t o_dlist = o; o = align256(o + nQ * 4);
-  const size_t o_nreq = o; o = align256(o + nQ * sizeof(bs_node_request));
-  const size_t o_res = o;                                 // results: one D2H
-  const size_t o_info = o; o = align256(o + 2 * 4);
-  const size_t o_node = o; o = align256(o + nQ * 4);
-  const size_t o_ncand = o; o = align256(o + nQ * 4);
-  const size_t o_nv = o; o = align256(o + nQ * 4);
-  const size_t o_npv = o; o = align256(o + nQ * 4);
-  const size_t o_top = o; o = align256(o + nQ * 4);
-  const size_t o_sum = o; o = align256(o + nQ * 8);
-  const size_t o_est = o; o = align256(o + nQ * 8);
-  const size_t o_vic = o; o = align256(o + nV * 4);
-  HIPCHK(c, c->d_pre.reserve(o));
+  const auto o_gneed = cv.take<uint32_t>(gQ);
+  const auto o_grlen = cv.take<uint32_t>(gQ);
+  const size_t in_bytes = cv.mark();
+  const auto o_rnode = cv.take<int32_t>(nR * kPcK);
+  const auto o_rnv = cv.take<uint32_t>(nR * kPcK);
+  const auto o_rnpv = cv.take<uint32_t>(nR * kPcK);
+  const auto o_rtop = cv.take<int32_t>(nR * kPcK);
+  const auto o_rsum = cv.take<int64_t>(nR * kPcK);
+  const auto o_rest = cv.take<int64_t>(nR * kPcK);
+  const auto o_rncand = cv.take<uint32_t>(nR);
+  const size_t o_work = cv.mark();                          // zeroed working state
+  const auto o_dv = cv.take<int64_t>((size_t)L * nN);
+  const auto o_dn = cv.take<int64_t>((size_t)L * nN);
+  const auto o_vbits = cv.take<uint32_t>(nN);
+  const auto o_nbits = cv.take<uint32_t>(nN);
+  const auto o_dirty = cv.take<uint8_t>(nN);
+  const auto o_dead = cv.take<uint8_t>(nB);
+  const auto o_gtag = cv.take<uint32_t>(gB);
+  const auto o_gplaced = cv.take<uint32_t>(gQ);
+  const auto o_gvoided = cv.take<uint8_t>(gQ);
+  const size_t work_bytes = cv.mark() - o_work;
+  const auto o_gslog = cv.take<uint32_t>(gQ * 3);
+  const auto o_dlist = cv.take<uint32_t>(nQ);
+  const auto o_nreq = cv.take<bs_node_request>(nQ);
+  const size_t o_res = cv.mark();                           // results: one D2H
+  const auto o_info = cv.take<uint32_t>(2);
+  const auto o_node = cv.take<int32_t>(nQ);
+  const auto o_ncand = cv.take<uint32_t>(nQ);
+  const auto o_nv = cv.take<uint32_t>(nQ);
+  const auto o_npv = cv.take<uint32_t>(nQ);
+  const auto o_top = cv.take<int32_t>(nQ);
+  const auto o_sum = cv.take<int64_t>(nQ);
+  const auto o_est = cv.take<int64_t>(nQ);
+  const auto o_vic = cv.take<uint32_t>(nV);
+  HIPCHK(c, c->d_pre.reserve(cv.mark()));
   std::vector<uint8_t> in(in_bytes, 0);
-  uint32_t* spod = reinterpret_cast<uint32_t*>(in.data() + o_spod);
-  int32_t* sprio = reinterpret_cast<int32_t*>(in.data() + o_sprio);
-  uint32_t* sorig = reinterpret_cast<uint32_t*>(in.data() + o_sorig);
   for (uint32_t s = 0; s < count; ++s) {
-    spod[s] = pod_index[perm[s]];
-    sprio[s] = priority[perm[s]];
-    sorig[s] = perm[s];
+    o_spod.in(in.data())[s] = pod_index[perm[s]];
+    o_sprio.in(in.data())[s] = priority[perm[s]];
+    o_sorig.in(in.data())[s] = perm[s];
   }
-  if (G) std::memcpy(in.data() + o_gprot, group_protected, G);
+  if (G) std::memcpy(o_gprot.in(in.data()), group_protected, G);
   if (gang) {
-    std::memcpy(in.data() + o_gneed, g_need.data(), nQ * 4);
-    std::memcpy(in.data() + o_grlen, g_rlen.data(), nQ * 4);
+    std::memcpy(o_gneed.in(in.data()), g_need.data(), o_gneed.bytes());
+    std::memcpy(o_grlen.in(in.data()), g_rlen.data(), o_grlen.bytes());
   }
   uint8_t* base = c->d_pre.as<uint8_t>();
   HIPCHK(c, hipMemcpyAsync(base, in.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(base + o_work, 0, work_bytes, c->stream));
-  const uint8_t* bb = c->d_bound.as<uint8_t>();
   CommitDev pe{};
-  pe.boff = reinterpret_cast<const uint32_t*>(bb + c->blay.boff);
-  pe.bprio = reinterpret_cast<const int32_t*>(bb + c->blay.prio);
-  pe.bstart = reinterpret_cast<const int64_t*>(bb + c->blay.start);
-  pe.bgroup = reinterpret_cast<const int32_t*>(bb + c->blay.group);
-  pe.bid = reinterpret_cast<const uint32_t*>(bb + c->blay.id);
-  pe.breq = reinterpret_cast<const int64_t*>(bb + c->blay.req);
-  pe.bpres = reinterpret_cast<const uint32_t*>(bb + c->blay.pres);
-  pe.bpdb = bb + c->blay.pdb;
-  pe.bnviol = reinterpret_cast<const uint32_t*>(bb + c->blay.nviol);
+  const auto bt = bound_dev(pe, c->d_bound.as<const uint8_t>(), c->blay);
+  pe.bpres = bt.pres;
+  pe.bnviol = bt.nviol;
   pe.bstride = (uint32_t)nB;
   pe.q = count;
   pe.nchunks = nchunks;
   pe.chunk_nodes = chunk_nodes;
   pe.cap = victim_cap;
-  pe.spod = reinterpret_cast<const uint32_t*>(base + o_spod);
-  pe.sprio = reinterpret_cast<const int32_t*>(base + o_sprio);
-  pe.sorig = reinterpret_cast<const uint32_t*>(base + o_sorig);
-  pe.gprot = base + o_gprot;
-  pe.r_node = reinterpret_cast<int32_t*>(base + o_rnode);
-  pe.r_nv = reinterpret_cast<uint32_t*>(base + o_rnv);
-  pe.r_npv = reinterpret_cast<uint32_t*>(base + o_rnpv);
-  pe.r_top = reinterpret_cast<int32_t*>(base + o_rtop);
-  pe.r_sum = reinterpret_cast<int64_t*>(base + o_rsum);
-  pe.r_est = reinterpret_cast<int64_t*>(base + o_rest);
-  pe.r_ncand = reinterpret_cast<uint32_t*>(base + o_rncand);
-  pe.dv = reinterpret_cast<int64_t*>(base + o_dv);
-  pe.dn = reinterpret_cast<int64_t*>(base + o_dn);
-  pe.vbits = reinterpret_cast<uint32_t*>(base + o_vbits);
-  pe.nbits = reinterpret_cast<uint32_t*>(base + o_nbits);
-  pe.dirty = base + o_dirty;
-  pe.dead = base + o_dead;
-  pe.dlist = reinterpret_cast<uint32_t*>(base + o_dlist);
-  pe.info = reinterpret_cast<uint32_t*>(base + o_info);
-  pe.o_node = reinterpret_cast<int32_t*>(base + o_node);
-  pe.o_ncand = reinterpret_cast<uint32_t*>(base + o_ncand);
-  pe.o_nv = reinterpret_cast<uint32_t*>(base + o_nv);
-  pe.o_npv = reinterpret_cast<uint32_t*>(base + o_npv);
-  pe.o_top = reinterpret_cast<int32_t*>(base + o_top);
-  pe.o_sum = reinterpret_cast<int64_t*>(base + o_sum);
-  pe.o_est = reinterpret_cast<int64_t*>(base + o_est);
-  pe.o_victims = reinterpret_cast<uint32_t*>(base + o_vic);
+  pe.spod = o_spod.in(base);
+  pe.sprio = o_sprio.in(base);
+  pe.sorig = o_sorig.in(base);
+  pe.gprot = o_gprot.in(base);
+  pe.r_node = o_rnode.in(base);
+  pe.r_nv = o_rnv.in(base);
+  pe.r_npv = o_rnpv.in(base);
+  pe.r_top = o_rtop.in(base);
+  pe.r_sum = o_rsum.in(base);
+  pe.r_est = o_rest.in(base);
+  pe.r_ncand = o_rncand.in(base);
+  pe.dv = o_dv.in(base);
+  pe.dn = o_dn.in(base);
+  pe.vbits = o_vbits.in(base);
+  pe.nbits = o_nbits.in(base);
+  pe.dirty = o_dirty.in(base);
+  pe.dead = o_dead.in(base);
+  pe.dlist = o_dlist.in(base);
+  pe.info = o_info.in(base);
+  pe.o_node = o_node.in(base);
+  pe.o_ncand = o_ncand.in(base);
+  pe.o_nv = o_nv.in(base);
+  pe.o_npv = o_npv.in(base);
+  pe.o_top = o_top.in(base);
+  pe.o_sum = o_sum.in(base);
+  pe.o_est = o_est.in(base);
+  pe.o_victims = o_vic.in(base);
   const NodesDev nd = nodes_dev(c);
   if (gang) {
     GangDev gd{};
-    gd.s_need = reinterpret_cast<const uint32_t*>(base + o_gneed);
-    gd.s_rlen = reinterpret_cast<const uint32_t*>(base + o_grlen);
-    gd.tag = reinterpret_cast<uint32_t*>(base + o_gtag);
-    gd.slog = reinterpret_cast<uint32_t*>(base + o_gslog);
-    gd.o_placed = reinterpret_cast<uint32_t*>(base + o_gplaced);
-    gd.o_voided = base + o_gvoided;
+    gd.s_need = o_gneed.in(base);
+    gd.s_rlen = o_grlen.in(base);
+    gd.tag = o_gtag.in(base);
+    gd.slog = o_gslog.in(base);
+    gd.o_placed = o_gplaced.in(base);
+    gd.o_voided = o_gvoided.in(base);
     launch_preempt_commit_gang(c->stream, c->S, dim3(tiles, nchunks), nd, pods_dev(c), pe, gd);
   } else {
     launch_preempt_commit(c->stream, c->S, dim3(tiles, nchunks), nd, pods_dev(c), pe);
   }
   LAUNCHCHK(c, BS_KERNEL_QUERY);
-  std::vector<uint8_t> res(o - o_res);
+  std::vector<uint8_t> res(cv.mark() - o_res);
   HIPCHK(c, hipMemcpyAsync(res.data(), base + o_res, res.size(), hipMemcpyDeviceToHost, c->stream));
   std::vector<uint8_t> gres;                              // gang: placed by slot, then voided by preemptor (adjacent in the blob)
   if (gang) {
-    gres.resize(o_work + work_bytes - o_gplaced);
-    HIPCHK(c, hipMemcpyAsync(gres.data(), base + o_gplaced, gres.size(), hipMemcpyDeviceToHost, c->stream));
+    gres.resize(o_work + work_bytes - o_gplaced.off);
+    HIPCHK(c, hipMemcpyAsync(gres.data(), o_gplaced.in(base), gres.size(), hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint8_t* rb = res.data() - o_res;
   if (apply) {
-    const uint32_t* info = reinterpret_cast<const uint32_t*>(rb + o_info);
+    const uint32_t* info = o_info.in(rb);
     const uint32_t ndirty = info[0], nvall = info[1];
-    bs_node_request* dreq = reinterpret_cast<bs_node_request*>(base + o_nreq);
+    bs_node_request* dreq = o_nreq.in(base);
     CompactDev nw{};
     const uint32_t B2 = B - nvall;
     BoundLayout lay{};
     if (nvall) {                                          // the compacted table goes to the second buffer, swapped in below
       HIPCHK(c, c->d_bound2.reserve(bound_layout(L, N, B2, lay)));
-      uint8_t* b2 = c->d_bound2.as<uint8_t>();
-      nw.boff = reinterpret_cast<uint32_t*>(b2 + lay.boff);
-      nw.bprio = reinterpret_cast<int32_t*>(b2 + lay.prio);
-      nw.bstart = reinterpret_cast<int64_t*>(b2 + lay.start);
-      nw.bgroup = reinterpret_cast<int32_t*>(b2 + lay.group);
-      nw.bid = reinterpret_cast<uint32_t*>(b2 + lay.id);
-      nw.breq = reinterpret_cast<int64_t*>(b2 + lay.req);
-      nw.bpres = reinterpret_cast<uint32_t*>(b2 + lay.pres);
-      nw.bpdb = b2 + lay.pdb;
-      nw.bnviol = reinterpret_cast<uint32_t*>(b2 + lay.nviol);
+      const auto nt = bound_dev(nw, c->d_bound2.as<uint8_t>(), lay);
+      nw.bpres = nt.pres;
+      nw.bnviol = nt.nviol;
       nw.bstride = std::max<uint32_t>(B2, 1);
     }
     launch_preempt_apply(c->stream, c->S, nd, pe, ndirty, assume ? 1u : 0u, dreq, nvall ? &nw : nullptr);
@@ -4515,26 +4508,26 @@ static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const
       c->bound_b = B2;
     }
   }
-  std::memcpy(out->node, rb + o_node, nQ * 4);
-  std::memcpy(out->n_victims, rb + o_nv, nQ * 4);
-  c->pre_npv.assign(reinterpret_cast<const uint32_t*>(rb + o_npv), reinterpret_cast<const uint32_t*>(rb + o_npv) + nQ);
+  std::memcpy(out->node, o_node.in(rb), o_node.bytes());
+  std::memcpy(out->n_victims, o_nv.in(rb), o_nv.bytes());
+  c->pre_npv.assign(o_npv.in(rb), o_npv.in(rb) + nQ);
   c->have_pre_npv = true;
   c->have_gang = gang;
   if (gang) {
-    const uint32_t* placed = reinterpret_cast<const uint32_t*>(gres.data());
-    const uint8_t* voided = gres.data() + (o_gvoided - o_gplaced);
+    const uint32_t* placed = o_gplaced.in(gres.data() - o_gplaced.off);
+    const uint8_t* voided = o_gvoided.in(gres.data() - o_gplaced.off);
     c->gang_voided.assign(voided, voided + nQ);
     c->gang_placed.assign(G, 0u);
     for (uint32_t s = 0; s < count; ++s)
       if (g_rlen[s]) c->gang_placed[sgroup[s]] = placed[s];
   }
-  if (out->n_candidates) std::memcpy(out->n_candidates, rb + o_ncand, nQ * 4);
-  if (out->top_priority) std::memcpy(out->top_priority, rb + o_top, nQ * 4);
-  if (out->priority_sum) std::memcpy(out->priority_sum, rb + o_sum, nQ * 8);
-  if (out->earliest_start) std::memcpy(out->earliest_start, rb + o_est, nQ * 8);
+  if (out->n_candidates) std::memcpy(out->n_candidates, o_ncand.in(rb), o_ncand.bytes());
+  if (out->top_priority) std::memcpy(out->top_priority, o_top.in(rb), o_top.bytes());
+  if (out->priority_sum) std::memcpy(out->priority_sum, o_sum.in(rb), o_sum.bytes());
+  if (out->earliest_start) std::memcpy(out->earliest_start, o_est.in(rb), o_est.bytes());
   if (victim_cap) {
-    const uint32_t* nv = reinterpret_cast<const uint32_t*>(rb + o_nv);
-    const uint32_t* vic = reinterpret_cast<const uint32_t*>(rb + o_vic);
+    const uint32_t* nv = o_nv.in(rb);
+    const uint32_t* vic = o_vic.in(rb);
     for (size_t q = 0; q < nQ; ++q) {
       const uint32_t k = std::min(nv[q], victim_cap);
       std::memcpy(out->victims + q * victim_cap, vic + q * victim_cap, (size_t)k * 4);
@@ -4576,9 +4569,9 @@ int bs_bound_read(bs_ctx* c, uint32_t* id_out, uint32_t* node_out) {
   if (rc) return rc;
   std::vector<uint32_t> boff((size_t)N + 1);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint8_t* bb = c->d_bound.as<uint8_t>();
-  HIPCHK(c, hipMemcpy(boff.data(), bb + c->blay.boff, ((size_t)N + 1) * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(id_out, bb + c->blay.id, (size_t)B * 4, hipMemcpyDeviceToHost));
+  const auto bt = bound_cols(c->d_bound.as<const uint8_t>(), c->blay);
+  HIPCHK(c, hipMemcpy(boff.data(), bt.boff, ((size_t)N + 1) * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(id_out, bt.id, (size_t)B * 4, hipMemcpyDeviceToHost));
   for (uint32_t k = 0; k < N; ++k)
     for (uint32_t j = boff[k]; j < boff[k + 1] && j < B; ++j) node_out[j] = k;
   return BS_OK;
@@ -4632,112 +4625,89 @@ static int bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t flags, uint3
   });
   // one blob (8-byte columns first), then the scratch: pos_of (0xff), the zeroed words, the segment starts
   const size_t nI = I, nR = R, nN = std::max<uint32_t>(N, 1);
-  size_t o = 0;
-  const size_t o_start = o; o += nI * 8;
-  const size_t o_req = o; o += nI * L * 8;
-  const size_t o_rem = o; o += nR * 4;
-  const size_t o_node = o; o += nI * 4;
-  const size_t o_prio = o; o += nI * 4;
-  const size_t o_group = o; o += nI * 4;
-  const size_t o_id = o; o += nI * 4;
-  const size_t o_pres = o; o += nI * 4;
-  const size_t o_pdb = o; o += nI;
-  const size_t blob_bytes = o;
-  o = align256(o);
-  const size_t o_posof = o; o = align256(o + (size_t)std::max<uint32_t>(ids, 1) * 4);
-  const size_t o_zero = o;
-  const size_t o_deadw = o; o = align256(o + ((size_t)B / 32 + 1) * 4);
-  const size_t o_dcnt = o; o = align256(o + nN * 4);
-  const size_t o_icnt = o; o = align256(o + nN * 4);
-  const size_t o_err = o; o = align256(o + 4);
-  const size_t o_nrec = o + 248; o = align256(o + 256);    // BS_BOUND_NODES: the record count, the last 8 bytes before the records (one D2H)
-  const size_t zero_bytes = o - o_zero;
+  Carve cv;
+  const auto o_start = cv.take<int64_t>(nI, 1);           // (packed)
+  const auto o_req = cv.take<int64_t>(nI * L, 1);
+  const auto o_rem = cv.take<uint32_t>(nR, 1);
+  const auto o_node = cv.take<uint32_t>(nI, 1);
+  const auto o_prio = cv.take<int32_t>(nI, 1);
+  const auto o_group = cv.take<int32_t>(nI, 1);
+  const auto o_id = cv.take<uint32_t>(nI, 1);
+  const auto o_pres = cv.take<uint32_t>(nI, 1);
+  const auto o_pdb = cv.take<uint8_t>(nI);                 // the last column: the scratch behind it starts at the next 256
+  const size_t blob_bytes = o_pdb.off + o_pdb.bytes();
+  const auto o_posof = cv.take<uint32_t>(std::max<uint32_t>(ids, 1));
+  const size_t o_zero = cv.mark();
+  const auto o_deadw = cv.take<uint32_t>((size_t)B / 32 + 1);
+  const auto o_dcnt = cv.take<uint32_t>(nN);
+  const auto o_icnt = cv.take<uint32_t>(nN);
+  const auto o_err = cv.take<uint32_t>(1);
+  const auto o_gap = cv.take<uint8_t>(256);
+  const Piece<uint32_t> o_nrec{o_gap.off + 248, 2};        // BS_BOUND_NODES: the record count, the last 8 bytes before the records (one D2H)
+  const size_t zero_bytes = cv.mark() - o_zero;
   const size_t rec_cap = with_nodes ? std::min<size_t>(N, nR + nI) : 0;
-  const size_t o_rec = o; o = align256(o + rec_cap * sizeof(bs_node_request));
-  const size_t o_ifirst = o; o = align256(o + nN * 4);
+  const auto o_rec = cv.take<bs_node_request>(rec_cap);
+  const auto o_ifirst = cv.take<uint32_t>(nN);
   // the id space grows with every call, and the table with every net insert: a quarter of headroom, so that a run of calls allocates rarely
-  if (o > c->d_pre.cap) HIPCHK(c, c->d_pre.reserve(o + o / 4));
+  if (cv.mark() > c->d_pre.cap) HIPCHK(c, c->d_pre.reserve(cv.mark() + cv.mark() / 4));
   std::vector<uint8_t> h(std::max<size_t>(blob_bytes, 1), 0);
-  {
-    int64_t* start = reinterpret_cast<int64_t*>(h.data() + o_start);
-    int64_t* req = reinterpret_cast<int64_t*>(h.data() + o_req);
-    uint32_t* node = reinterpret_cast<uint32_t*>(h.data() + o_node);
-    int32_t* prio = reinterpret_cast<int32_t*>(h.data() + o_prio);
-    int32_t* grp = reinterpret_cast<int32_t*>(h.data() + o_group);
-    uint32_t* id = reinterpret_cast<uint32_t*>(h.data() + o_id);
-    uint32_t* pres = reinterpret_cast<uint32_t*>(h.data() + o_pres);
-    uint8_t* pdb = h.data() + o_pdb;
-    if (R) std::memcpy(h.data() + o_rem, d->remove, nR * 4);
-    const uint32_t smask = (uint32_t)((1ull << (L - BS_FIXED_LANES)) - 1ull);
-    for (uint32_t r = 0; r < I; ++r) {                     // stored as bs_bound_load stores them
-      const uint32_t i = order[r];
-      node[r] = d->node[i];
-      prio[r] = d->priority[i];
-      start[r] = d->start_ns[i];
-      grp[r] = d->group[i];
-      id[r] = ids + i;
-      pres[r] = d->req_present[i] & smask;
-      pdb[r] = d->pdb_violating && d->pdb_violating[i] ? 1 : 0;
-      for (uint32_t l = 0; l < L; ++l) {
-        int64_t v = d->req[(size_t)l * I + i];
-        if (l == BS_LANE_PODS) v = 1;
-        else if (l >= BS_FIXED_LANES && !((d->req_present[i] >> (l - BS_FIXED_LANES)) & 1u)) v = 0;
-        req[(size_t)l * nI + r] = v;
-      }
+  uint8_t* hb = h.data();
+  if (R) std::memcpy(o_rem.in(hb), d->remove, o_rem.bytes());
+  const uint32_t smask = (uint32_t)((1ull << (L - BS_FIXED_LANES)) - 1ull);
+  for (uint32_t r = 0; r < I; ++r) {                       // stored as bs_bound_load stores them
+    const uint32_t i = order[r];
+    o_node.in(hb)[r] = d->node[i];
+    o_prio.in(hb)[r] = d->priority[i];
+    o_start.in(hb)[r] = d->start_ns[i];
+    o_group.in(hb)[r] = d->group[i];
+    o_id.in(hb)[r] = ids + i;
+    o_pres.in(hb)[r] = d->req_present[i] & smask;
+    o_pdb.in(hb)[r] = d->pdb_violating && d->pdb_violating[i] ? 1 : 0;
+    for (uint32_t l = 0; l < L; ++l) {
+      int64_t v = d->req[(size_t)l * I + i];
+      if (l == BS_LANE_PODS) v = 1;
+      else if (l >= BS_FIXED_LANES && !((d->req_present[i] >> (l - BS_FIXED_LANES)) & 1u)) v = 0;
+      o_req.in(hb)[(size_t)l * nI + r] = v;
     }
   }
   uint8_t* base = c->d_pre.as<uint8_t>();
   HIPCHK(c, hipMemcpyAsync(base, h.data(), h.size(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(base + o_posof, 0xff, (size_t)std::max<uint32_t>(ids, 1) * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(o_posof.in(base), 0xff, o_posof.bytes(), c->stream));
   HIPCHK(c, hipMemsetAsync(base + o_zero, 0, zero_bytes, c->stream));
   const uint32_t B2 = B - R + I;                           // (when the error word stays clear)
   BoundLayout lay{};
   const size_t table_bytes = bound_layout(L, N, B2, lay);
   if (table_bytes > c->d_bound2.cap) HIPCHK(c, c->d_bound2.reserve(table_bytes + table_bytes / 4));
-  const uint8_t* bb = c->d_bound.as<uint8_t>();
-  uint8_t* b2 = c->d_bound2.as<uint8_t>();
   BoundApplyDev a{};
-  a.boff = reinterpret_cast<const uint32_t*>(bb + c->blay.boff);
-  a.bprio = reinterpret_cast<const int32_t*>(bb + c->blay.prio);
-  a.bstart = reinterpret_cast<const int64_t*>(bb + c->blay.start);
-  a.bgroup = reinterpret_cast<const int32_t*>(bb + c->blay.group);
-  a.breq = reinterpret_cast<const int64_t*>(bb + c->blay.req);
-  a.bid = reinterpret_cast<const uint32_t*>(bb + c->blay.id);
-  a.bpres = reinterpret_cast<const uint32_t*>(bb + c->blay.pres);
-  a.bpdb = bb + c->blay.pdb;
+  const auto bt = bound_dev(a, c->d_bound.as<const uint8_t>(), c->blay);
+  a.bpres = bt.pres;
   a.bstride = std::max<uint32_t>(B, 1);
   a.b = B; a.n = N; a.ids = ids;
   a.n_remove = R; a.n_insert = I;
-  a.rem = reinterpret_cast<const uint32_t*>(base + o_rem);
-  a.inode = reinterpret_cast<const uint32_t*>(base + o_node);
-  a.iprio = reinterpret_cast<const int32_t*>(base + o_prio);
-  a.istart = reinterpret_cast<const int64_t*>(base + o_start);
-  a.igroup = reinterpret_cast<const int32_t*>(base + o_group);
-  a.ireq = reinterpret_cast<const int64_t*>(base + o_req);
-  a.iid = reinterpret_cast<const uint32_t*>(base + o_id);
-  a.ipres = reinterpret_cast<const uint32_t*>(base + o_pres);
-  a.ipdb = base + o_pdb;
-  a.pos_of = reinterpret_cast<uint32_t*>(base + o_posof);
-  a.deadw = reinterpret_cast<uint32_t*>(base + o_deadw);
-  a.dcnt = reinterpret_cast<uint32_t*>(base + o_dcnt);
-  a.icnt = reinterpret_cast<uint32_t*>(base + o_icnt);
-  a.ifirst = reinterpret_cast<uint32_t*>(base + o_ifirst);
-  a.err = reinterpret_cast<uint32_t*>(base + o_err);
+  a.rem = o_rem.in(base);
+  a.inode = o_node.in(base);
+  a.iprio = o_prio.in(base);
+  a.istart = o_start.in(base);
+  a.igroup = o_group.in(base);
+  a.ireq = o_req.in(base);
+  a.iid = o_id.in(base);
+  a.ipres = o_pres.in(base);
+  a.ipdb = o_pdb.in(base);
+  a.pos_of = o_posof.in(base);
+  a.deadw = o_deadw.in(base);
+  a.dcnt = o_dcnt.in(base);
+  a.icnt = o_icnt.in(base);
+  a.ifirst = o_ifirst.in(base);
+  a.err = o_err.in(base);
   CompactDev nw{};
-  nw.boff = reinterpret_cast<uint32_t*>(b2 + lay.boff);
-  nw.bprio = reinterpret_cast<int32_t*>(b2 + lay.prio);
-  nw.bstart = reinterpret_cast<int64_t*>(b2 + lay.start);
-  nw.bgroup = reinterpret_cast<int32_t*>(b2 + lay.group);
-  nw.bid = reinterpret_cast<uint32_t*>(b2 + lay.id);
-  nw.breq = reinterpret_cast<int64_t*>(b2 + lay.req);
-  nw.bpres = reinterpret_cast<uint32_t*>(b2 + lay.pres);
-  nw.bpdb = b2 + lay.pdb;
-  nw.bnviol = reinterpret_cast<uint32_t*>(b2 + lay.nviol);
+  const auto nt = bound_dev(nw, c->d_bound2.as<uint8_t>(), lay);
+  nw.bpres = nt.pres;
+  nw.bnviol = nt.nviol;
   nw.bstride = std::max<uint32_t>(B2, 1);
   launch_bound_apply(c->stream, c->S, a, nw);
   LAUNCHCHK(c, BS_KERNEL_PREPASS);
   uint32_t err = 0;                                        // read before the swap: the merge wrote nothing when it is set
-  HIPCHK(c, hipMemcpyAsync(&err, a.err, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&err, a.err, o_err.bytes(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (err & (kBaErrUnknown | kBaErrDead | kBaErrTwice | kBaErrNode)) {
     c->last_error = (err & kBaErrTwice) ? "bs_bound_apply: a remove id is listed twice"
@@ -4760,12 +4730,12 @@ static int bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t flags, uint3
     o2.rpres = c->d_rpres.as<uint32_t>();
     o2.nstride = c->Ncap;
     o2.cap = (uint32_t)rec_cap;
-    o2.count = reinterpret_cast<uint32_t*>(base + o_nrec);
-    o2.out = reinterpret_cast<bs_node_request*>(base + o_rec);
+    o2.count = o_nrec.in(base);
+    o2.out = o_rec.in(base);
     launch_bound_apply_nodes(c->stream, c->S, a, o2);
     LAUNCHCHK(c, BS_KERNEL_PREPASS);
     std::vector<uint8_t> hr(8 + rec_cap * sizeof(bs_node_request));   // count + records
-    HIPCHK(c, hipMemcpyAsync(hr.data(), base + o_nrec, hr.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hr.data(), o_nrec.in(base), hr.size(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     uint32_t nrec = 0;
     std::memcpy(&nrec, hr.data(), 4);
@@ -4824,52 +4794,45 @@ int bs_bound_nodes_apply(bs_ctx* c, uint32_t count, const uint32_t* kind, const 
   // the removed list (one H2D), then the scratch of this call
   const uint32_t nblk = std::max<uint32_t>(1u, cdiv(std::max(N1, R), 1024u)), ncap = std::min(dropped_cap, B);
   const size_t nR = R, nN = N1;
-  size_t o = 0;
-  const size_t o_rem = o; o = align256(o + nR * 4);
-  const size_t o_len = o; o = align256(o + nN * 4);
-  const size_t o_src = o; o = align256(o + nN * 4);
-  const size_t o_dlen = o; o = align256(o + nR * 4);
-  const size_t o_doff = o; o = align256(o + (nR + 1) * 4);
-  const size_t o_bsum = o; o = align256(o + (size_t)2 * nblk * 4);
-  const size_t o_pair = o; o = align256(o + 8);
-  const size_t o_drop = o; o = align256(o + (size_t)ncap * 4);
-  if (o > c->d_pre.cap) HIPCHK(c, c->d_pre.reserve(o + o / 4));
+  Carve cv;
+  const auto o_rem = cv.take<uint32_t>(nR);
+  const auto o_len = cv.take<uint32_t>(nN);
+  const auto o_src = cv.take<uint32_t>(nN);
+  const auto o_dlen = cv.take<uint32_t>(nR);
+  const auto o_doff = cv.take<uint32_t>(nR + 1);
+  const auto o_bsum = cv.take<uint32_t>((size_t)2 * nblk);
+  const auto o_pair = cv.take<uint32_t>(2);
+  const auto o_drop = cv.take<uint32_t>(ncap);
+  if (cv.mark() > c->d_pre.cap) HIPCHK(c, c->d_pre.reserve(cv.mark() + cv.mark() / 4));
   // the new table holds at most the old entries: sized for them, laid out by k_bn_move for the count the scan finds (boff: N1 + 1 words,
   // nviol: N1 words — appends grow both)
   BoundLayout lay{};
   const size_t table_bytes = bound_layout(L, N1, B, lay);
   if (table_bytes > c->d_bound2.cap) HIPCHK(c, c->d_bound2.reserve(table_bytes + table_bytes / 4));
   uint8_t* base = c->d_pre.as<uint8_t>();
-  if (R) HIPCHK(c, hipMemcpyAsync(base + o_rem, rp.removed.data(), nR * 4, hipMemcpyHostToDevice, c->stream));
-  const uint8_t* bb = c->d_bound.as<uint8_t>();
+  if (R) HIPCHK(c, hipMemcpyAsync(o_rem.in(base), rp.removed.data(), o_rem.bytes(), hipMemcpyHostToDevice, c->stream));
   BoundNodesDev a{};
-  a.boff = reinterpret_cast<const uint32_t*>(bb + c->blay.boff);
-  a.bprio = reinterpret_cast<const int32_t*>(bb + c->blay.prio);
-  a.bstart = reinterpret_cast<const int64_t*>(bb + c->blay.start);
-  a.bgroup = reinterpret_cast<const int32_t*>(bb + c->blay.group);
-  a.breq = reinterpret_cast<const int64_t*>(bb + c->blay.req);
-  a.bid = reinterpret_cast<const uint32_t*>(bb + c->blay.id);
-  a.bpres = reinterpret_cast<const uint32_t*>(bb + c->blay.pres);
-  a.bpdb = bb + c->blay.pdb;
+  const auto bt = bound_dev(a, c->d_bound.as<const uint8_t>(), c->blay);
+  a.bpres = bt.pres;
   a.bstride = std::max<uint32_t>(B, 1);
   a.n0 = N0; a.n1 = N1;
   a.nrem = R; a.old_left = N0 - R;
-  a.rem = reinterpret_cast<const uint32_t*>(base + o_rem);
+  a.rem = o_rem.in(base);
   a.nbase = c->d_bound2.as<uint8_t>();
-  a.nboff = reinterpret_cast<uint32_t*>(a.nbase + lay.boff);
-  a.len = reinterpret_cast<uint32_t*>(base + o_len);
-  a.src = reinterpret_cast<uint32_t*>(base + o_src);
-  a.dlen = reinterpret_cast<uint32_t*>(base + o_dlen);
-  a.doff = reinterpret_cast<uint32_t*>(base + o_doff);
-  a.bsum = reinterpret_cast<uint32_t*>(base + o_bsum);
+  a.nboff = bound_cols(a.nbase, lay).boff;
+  a.len = o_len.in(base);
+  a.src = o_src.in(base);
+  a.dlen = o_dlen.in(base);
+  a.doff = o_doff.in(base);
+  a.bsum = o_bsum.in(base);
   a.nblk = nblk;
-  a.pair = reinterpret_cast<uint32_t*>(base + o_pair);
-  a.dropped = reinterpret_cast<uint32_t*>(base + o_drop);
+  a.pair = o_pair.in(base);
+  a.dropped = o_drop.in(base);
   a.dropped_cap = ncap;
   launch_bound_nodes(c->stream, c->S, a);
   LAUNCHCHK(c, BS_KERNEL_PREPASS);
   uint32_t pair[2] = {0, 0};                               // {new entry count, dropped count}: read before the swap
-  HIPCHK(c, hipMemcpyAsync(pair, a.pair, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(pair, a.pair, o_pair.bytes(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));              // (rp.removed and pair are local buffers)
   if ((uint64_t)pair[0] + pair[1] != B) { c->last_error = "bs_bound_nodes_apply: the resident table's offsets do not add up"; return BS_ERR_HIP; }
   const uint32_t nd = std::min(pair[1], ncap);
@@ -4892,13 +4855,13 @@ int bs_bound_dump(bs_ctx* c, int32_t* priority, int64_t* start_ns, int32_t* grou
   int rc = use_device(c);
   if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint8_t* bb = c->d_bound.as<uint8_t>();
-  if (priority) HIPCHK(c, hipMemcpy(priority, bb + c->blay.prio, B * 4, hipMemcpyDeviceToHost));
-  if (start_ns) HIPCHK(c, hipMemcpy(start_ns, bb + c->blay.start, B * 8, hipMemcpyDeviceToHost));
-  if (group) HIPCHK(c, hipMemcpy(group, bb + c->blay.group, B * 4, hipMemcpyDeviceToHost));
-  if (req) HIPCHK(c, hipMemcpy(req, bb + c->blay.req, B * c->L * 8, hipMemcpyDeviceToHost));   // the lane stride is the entry count
-  if (req_present) HIPCHK(c, hipMemcpy(req_present, bb + c->blay.pres, B * 4, hipMemcpyDeviceToHost));
-  if (pdb) HIPCHK(c, hipMemcpy(pdb, bb + c->blay.pdb, B, hipMemcpyDeviceToHost));
+  const auto bt = bound_cols(c->d_bound.as<const uint8_t>(), c->blay);
+  if (priority) HIPCHK(c, hipMemcpy(priority, bt.prio, B * 4, hipMemcpyDeviceToHost));
+  if (start_ns) HIPCHK(c, hipMemcpy(start_ns, bt.start, B * 8, hipMemcpyDeviceToHost));
+  if (group) HIPCHK(c, hipMemcpy(group, bt.group, B * 4, hipMemcpyDeviceToHost));
+  if (req) HIPCHK(c, hipMemcpy(req, bt.req, B * c->L * 8, hipMemcpyDeviceToHost));   // the lane stride is the entry count
+  if (req_present) HIPCHK(c, hipMemcpy(req_present, bt.pres, B * 4, hipMemcpyDeviceToHost));
+  if (pdb) HIPCHK(c, hipMemcpy(pdb, bt.pdb, B, hipMemcpyDeviceToHost));
   return BS_OK;
 }
 

@@ -46,3 +46,13 @@ def groups_for(sc: dict) -> "soa.Groups":
     g = soa.Groups.empty(sc["groups"], 4 + sc["S"])
     g.min_member[:] = 1
     return g
+
+
+def ungrouped_scene(sc: dict) -> dict:
+    """the scene for a context that holds no groups: every queue pod and every bound pod ungrouped, an empty protected list, and a group
+    state of zero groups from groups_for"""
+    sc["bound"].group[:] = soa.POD_NOT_GROUPED
+    sc["pods"].group[:] = soa.POD_NOT_GROUPED
+    sc["protected"] = np.zeros(0, np.uint8)
+    sc["groups"] = 0
+    return sc

@@ -98,6 +98,16 @@ def test_full_size_cfg3_nodes_1024_preemptors():
     assert np.any(got["n_victims"] > 0) and np.any(got["node"] < 0)
 
 
+
+# ---- the blob's two edges: no row for victims (victim_cap 0), and a context with no groups (the protected column clamped to one byte)
+@pytest.mark.parametrize("cap", [0, 6])
+def test_a_context_with_no_groups(cap):
+    from preempt_scenes import ungrouped_scene
+    sc = ungrouped_scene(random_scene(7400, n=70, per_node=(2, 9), S=2, q=65, groups=4, p=70, fit_density=0.6))
+    got = _run_and_check(sc, cap=cap, where=f"no groups, cap {cap}")
+    assert got["victims"].shape == (65, cap) and np.any(got["n_victims"] > 0)
+
+
 # ---- relations
 def _online_scene(seed, n=400, S=1, q=128):
     sc = random_scene(seed, n=n, per_node=(0, 12), S=S, q=q, groups=3, p=64)

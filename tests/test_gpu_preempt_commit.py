@@ -111,6 +111,23 @@ def test_sparse_fit_flags_every_group_kind_and_extreme_priorities(S):
         _compare_state(ctx, exp, f"sparse S={S}")
 
 
+
+# ---- the blob's two edges: no row for victims (victim_cap 0), and a context with no groups (the protected column clamped to one byte)
+@pytest.mark.parametrize("cap,groups", [(0, 4), (0, 0), (6, 0)])
+def test_no_room_for_victims_and_a_context_with_no_groups(cap, groups):
+    from preempt_scenes import ungrouped_scene
+    sc = commit_scene(8700, n=70, per_node=(2, 9), S=2, q=65, groups=4, p=70, fit_density=0.6)
+    if not groups:
+        sc = ungrouped_scene(sc)
+    exp = _expect(sc, cap, True, True)
+    assert np.any(exp["res"]["n_victims"] > 0), "the scene evicts nobody: APPLY has nothing to write"
+    with _ctx(sc) as ctx:
+        got = ctx.preempt_commit(sc["pod_index"], sc["priority"], sc["protected"], victim_cap=cap, apply=True, assume=True)
+        assert got["victims"].shape == (65, cap)
+        _compare(got, exp["res"], f"cap {cap}, {groups} groups")
+        _compare_state(ctx, exp, f"cap {cap}, {groups} groups")
+
+
 def test_plan_only_changes_nothing_and_equals_apply_outputs():
     nodes, fit, groups, pods, _ = synth.make("tiny", "warm")
     bound, nodes = synth.make_bound(3, nodes.n, groups.g, (0, 20), 1)        # nearly full nodes: the plan evicts

@@ -111,6 +111,17 @@ def test_undo_does_not_depend_on_victim_cap(cap):
     _check(sc, cap, where="cap")
 
 
+
+# ---- 4b. a context with no groups: no gang column has a requirement, the protected column is clamped to one byte
+@pytest.mark.parametrize("cap", [0, 6])
+def test_a_context_with_no_groups(cap):
+    from preempt_scenes import ungrouped_scene
+    sc = ungrouped_scene(gs.gang_scene(8600, n=70, per_node=(2, 9), S=2, q=65, groups=4, p=70))
+    sc["need"] = np.zeros(0, np.uint32)
+    exp = _check(sc, cap, modes=((True, True),), where="no groups")
+    assert np.any(exp["res"]["n_victims"] > 0) and not exp["slot_voided"].any() and exp["group_placed"].size == 0
+
+
 # ---- 5. voided and standing runs on nodes with PDB-violating entries (two-pass reprieve)
 @pytest.mark.parametrize("S", [0, 4])
 def test_pdb_violating_entries_in_voided_and_standing_runs(S):

@@ -349,3 +349,25 @@ def test_seq_pass_cursors_survive_a_queue_patch(bsa, soa, orc):
         queue = pods.take(np.concatenate([keep, late]))
         s = oracle_pass(orc, nodes, fit, groups, queue, soa.STAGE_PREFILTER)
         check_pass(ctx, s, soa, "patched queue")
+
+
+def test_seq_pass_with_no_room_for_released_gangs(bsa, soa, orc):
+    """out->cap = 0 (the wrapper never passes less than 1): the four release arrays are clamped to one element nobody reads; every other
+    result, the count of released gangs and the state the pass leaves are the oracle's"""
+    import ctypes as C
+    nodes, fit, groups, pods = gang_scene(4202, soa, n_nodes=70, n_groups=4, n_pods=70)
+    assert nodes.lanes == 4 + 2
+    s = oracle_pass(orc, nodes, fit, groups, pods, soa.STAGE_PREFILTER)
+    assert s["n_released"] > 0, "the scene releases no gang: the clamped arrays are never written"
+    with load_ctx(bsa, nodes, fit, groups, pods) as ctx:
+        p = pods.p
+        pf, fk, ld, node, lp = np.zeros(p, np.uint8), np.zeros(p, np.uint32), np.zeros(p, np.int32), np.full(p, -1, np.int32), np.zeros(p, np.uint8)
+        u8p, i32p, u32p = (lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32)))
+        o = bsa.capi.SeqOut(u8p(pf), u32p(fk), i32p(ld), i32p(node), 0, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, 0, u8p(lp))
+        ctx._chk(ctx._lib.bs_seq_run(ctx._h, soa.STAGE_PREFILTER, C.byref(o)), "bs_seq_run")
+        assert int(o.n_released) == s["n_released"]
+        for name, got in (("pf_code", pf), ("pf_first_k", fk), ("pf_leader", ld), ("pod_node", node)):
+            assert np.array_equal(got, s[name]), name
+        req, pres = ctx.read_node_requests()
+        assert np.array_equal(req, s["nodes"].requested) and np.array_equal(pres, s["nodes"].requested_present)
+        assert_groups_equal(ctx.read_groups(), s["groups"], soa, "cap 0")
