@@ -16,14 +16,18 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.environ.get("BS_LIB_DIR") or HERE
 PREBUILT_ONLY = bool(os.environ.get("BS_LIB_DIR"))
 LIB_PATH = os.path.join(LIB_DIR, "libbsched.so")
-# translation units -> the headers each one depends on (bs_launch.hpp is the interface between them; DESIGN.md section 4 "Build")
-_COMMON = ["bs_common.hpp", "bs_kernels.hpp", "bs_nodew_layout.hpp", "bs_launch.hpp", "bs_lanes.hpp", "bs_carve.hpp", os.path.join("..", "..", "include", "bsched.h")]
+# translation units -> the headers each one depends on, transitively (tests/test_build_units_cpu.py follows the #includes; DESIGN.md section 4 "Build")
+_COMMON = ["bs_common.hpp", "bs_kernels.hpp", "bs_nodew_layout.hpp", "bs_lanes.hpp", os.path.join("..", "..", "include", "bsched.h")]
+_CTX = _COMMON + ["bs_ctx.hpp", "bs_carve.hpp", "bs_hostmem.hpp", "bs_pod_ranges.hpp"]      # the units that hold entry points
+_FAST = ["bs_launch.hpp", "bs_fast.hpp", "bs_filter_t.hpp"]
+_SEQ = _CTX + ["bs_seq.hpp"]
 UNITS = {
-    "bsched.hip": _COMMON + ["bs_fast.hpp", "bs_filter_t.hpp", "bs_epoch.hpp", "bs_queue.hpp", "bs_fdeny.hpp", "bs_seq.hpp", "bs_seq_expire.hpp", "bs_seq_expire_list.hpp", "bs_sort.hpp", "bs_fit.hpp", "bs_pod_ranges.hpp", "bs_preempt.hpp", "bs_preempt_commit.hpp", "bs_preempt_commit_gang.hpp", "bs_preempt_gang_runs.hpp", "bs_preempt_geom.hpp", "bs_bound_apply.hpp", "bs_bound_nodes.hpp", "bs_bound_nodes_replay.hpp", "bs_pdb.hpp", "bs_hostmem.hpp"],
-    "tu_fast.hip": _COMMON + ["bs_fast.hpp", "bs_filter_t.hpp"],
-    "tu_seq.hip": _COMMON + ["bs_seq.hpp"],
-    "tu_seq_expire.hip": _COMMON + ["bs_seq.hpp", "bs_seq_expire.hpp"],
-    "tu_preempt.hip": _COMMON + ["bs_preempt.hpp", "bs_preempt_commit.hpp", "bs_preempt_commit_gang.hpp", "bs_bound_apply.hpp", "bs_bound_nodes.hpp", "bs_pdb.hpp"],
+    "bsched.hip": _CTX + _FAST + ["bs_epoch.hpp", "bs_queue.hpp", "bs_fdeny.hpp", "bs_sort.hpp", "bs_fit.hpp"],
+    "tu_fast.hip": _COMMON + _FAST,
+    "tu_seq.hip": _SEQ,
+    "tu_seq_expire.hip": _SEQ + ["bs_seq_expire.hpp", "bs_seq_expire_list.hpp"],
+    "tu_preempt.hip": _CTX + ["bs_preempt.hpp", "bs_preempt_commit.hpp", "bs_preempt_commit_gang.hpp", "bs_preempt_gang_runs.hpp", "bs_preempt_geom.hpp", "bs_bound_apply.hpp",
+                              "bs_bound_nodes.hpp", "bs_bound_nodes_replay.hpp", "bs_pdb.hpp"],
 }
 SOURCES = list(UNITS)
 HEADERS = sorted({h for hs in UNITS.values() for h in hs})

@@ -19,30 +19,15 @@
 //                  across the wave; nothing here is 16-byte aligned).  Lane 0 writes the node's PDB count; an appended node writes a zero
 //                  count only.  Behind the new nodes one wave per REMOVED node copies its ids to dropped[doff[t] ..], cut at the cap.
 // The new table's column offsets depend on its entry count, which only the scan knows: k_bn_move computes them from nw.boff[n1] with the
-// function the host uses (bound_layout below), in an allocation the host sized for the OLD entry count (the count cannot grow here).
+// function the host uses (bound_layout, bs_kernels.hpp), in an allocation the host sized for the OLD entry count (the count cannot grow here).
 // S is a template parameter as for every kernel of this code object; the request lanes move through an unrolled loop, load to store.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace bs {
+#include "bs_kernels.hpp"
 
-// the bound table's one allocation for N nodes and B entries: columns at 256-byte offsets, breq lane stride max(B, 1); returns its size
-struct BoundLayout { size_t boff, prio, start, group, id, req, pres, pdb, nviol; };
-__host__ __device__ inline size_t bound_layout(uint32_t L, uint32_t N, uint32_t B, BoundLayout& b) {
-  const size_t nB = B ? B : 1u, nN = N ? N : 1u, m = ~(size_t)255;
-  size_t o = 0;
-  b.boff = o; o = (o + ((size_t)N + 1) * 4 + 255) & m;
-  b.prio = o; o = (o + nB * 4 + 255) & m;
-  b.start = o; o = (o + nB * 8 + 255) & m;
-  b.group = o; o = (o + nB * 4 + 255) & m;
-  b.id = o; o = (o + nB * 4 + 255) & m;
-  b.req = o; o = (o + nB * L * 8 + 255) & m;
-  b.pres = o; o = (o + nB * 4 + 255) & m;      // scalar keys of each entry (bs_preempt_commit sets them on the node)
-  b.pdb = o; o = (o + nB + 255) & m;           // PDB-violating bit of each entry (bs_bound_pdb_set)
-  b.nviol = o; o = (o + nN * 4 + 255) & m;     // entries with the bit per node
-  return o;
-}
+namespace bs {
 
 constexpr uint32_t kBnNone = 0xffffffffu;
 

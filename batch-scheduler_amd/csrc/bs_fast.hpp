@@ -115,8 +115,6 @@ __global__ void k_pod_pairs(PodsDev pods, uint32_t G, const uint32_t* rep, const
 // (read back asynchronously; bs_batch_run waits for it only if it has not arrived yet).
 //   info[0] leader (-1 none)  info[1] panic  info[2] steady table id (-1: none)  info[3] sequence tag
 // ------------------------------------------------------------------------------------------------
-struct GroupDelta { uint32_t index, matched, status_scheduled, flags; };
-
 #if BS_EMIT_MAIN
 __global__ void k_groups_apply(const GroupDelta* d, uint32_t n, uint32_t* matched, uint32_t* status_scheduled, uint8_t* flags) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -127,9 +125,6 @@ __global__ void k_groups_apply(const GroupDelta* d, uint32_t n, uint32_t* matche
   flags[x.index] = (uint8_t)x.flags;
 }
 #endif
-
-constexpr int kInlineDeltas = 48;                  // group deltas that ride in the kernel arguments (no H2D, no staging)
-struct DeltaPack { uint32_t n; GroupDelta d[kInlineDeltas]; };
 
 // [apply up to kInlineDeltas group deltas] -> findMaxPG -> the steady table's descriptor -> info to the host.
 // `info` is pinned host memory the kernel writes directly; the tag goes last with system-scope release.

@@ -77,6 +77,30 @@ struct PodsDev {
 
 struct TableDesc { uint32_t cls; float pct; };
 
+// a group patch (bs_groups_apply; k_leader_info, bs_fast.hpp) as the device reads it
+struct GroupDelta { uint32_t index, matched, status_scheduled, flags; };
+constexpr int kInlineDeltas = 48;                  // group deltas that ride in the kernel arguments (no H2D, no staging)
+struct DeltaPack { uint32_t n; GroupDelta d[kInlineDeltas]; };
+inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }   // host: grid sizes
+
+// the bound-pod table's one allocation for N nodes and B entries (the host's bs_ctx::d_bound; k_bn_move of bs_bound_nodes.hpp lays the
+// remapped table out with it): columns at 256-byte offsets, breq lane stride max(B, 1); returns its size
+struct BoundLayout { size_t boff, prio, start, group, id, req, pres, pdb, nviol; };
+__host__ __device__ inline size_t bound_layout(uint32_t L, uint32_t N, uint32_t B, BoundLayout& b) {
+  const size_t nB = B ? B : 1u, nN = N ? N : 1u, m = ~(size_t)255;
+  size_t o = 0;
+  b.boff = o; o = (o + ((size_t)N + 1) * 4 + 255) & m;
+  b.prio = o; o = (o + nB * 4 + 255) & m;
+  b.start = o; o = (o + nB * 8 + 255) & m;
+  b.group = o; o = (o + nB * 4 + 255) & m;
+  b.id = o; o = (o + nB * 4 + 255) & m;
+  b.req = o; o = (o + nB * L * 8 + 255) & m;
+  b.pres = o; o = (o + nB * 4 + 255) & m;      // scalar keys of each entry (bs_preempt_commit sets them on the node)
+  b.pdb = o; o = (o + nB + 255) & m;           // PDB-violating bit of each entry (bs_bound_pdb_set)
+  b.nviol = o; o = (o + nN * 4 + 255) & m;     // entries with the bit per node
+  return o;
+}
+
 // per-pod stage bits (scratch)
 constexpr uint8_t ST_ELIG = 1;      // passed core.go:89-110 against the batch-start deny flags
 constexpr uint8_t ST_REACH6 = 2;    // (tentatively) reached findMaxPG, core.go:118-123

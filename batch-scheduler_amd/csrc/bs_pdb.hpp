@@ -35,7 +35,6 @@ struct PdbDev {
   uint32_t count;
 };
 
-#ifndef BS_TU_MAIN
 __global__ __launch_bounds__(256) void k_pdb_allowed(PdbDev a) {
   const uint32_t t = blockIdx.x * 256u + threadIdx.x;
   if (t < a.count) a.allowed[a.index[t]] = a.value[t];
@@ -63,6 +62,5 @@ __global__ __launch_bounds__(256) void k_pdb_bits(PdbDev a) {
   }
   if (lane == 0) a.bnviol[k] = viol;
 }
-#endif
 
 }  // namespace bs

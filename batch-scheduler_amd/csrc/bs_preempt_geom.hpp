@@ -1,4 +1,4 @@
-// Launch geometry of the preemption search (bs_preempt_run, bs_preempt_commit; bsched.hip): how the node list is cut into chunks for the
+// Launch geometry of the preemption search (bs_preempt_run, bs_preempt_commit; tu_preempt.hip): how the node list is cut into chunks for the
 // grid (slot tiles, node chunks).  Plain C++ arithmetic, no HIP includes: the CPU tests compile it on its own
 // (tests/test_preempt_geom_cpu.py).  Both entry points call preempt_geom(); nobody restates the arithmetic.
 //

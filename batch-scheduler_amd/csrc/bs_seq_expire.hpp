@@ -56,7 +56,6 @@ struct SeqExpireDev {
   uint32_t N;
 };
 
-#ifndef BS_TU_MAIN
 __device__ __forceinline__ unsigned long long se_entry(const SeqExpireDev& a, uint32_t e, uint32_t& g) {
   g = a.list ? a.list[e] : e;
   const uint32_t cnt = a.nwait[g] & ~kSeqHasRecord;
@@ -206,6 +205,5 @@ __global__ __launch_bounds__(256) void k_se_groups(SeqExpireDev a) {
   a.head[g] = 0u;
   a.nwait[g] = a.nwait[g] & kSeqHasRecord;
 }
-#endif  // !BS_TU_MAIN
 
 }  // namespace bs

@@ -1,11 +1,10 @@
-// bsched.hip — C ABI of include/bsched.h on top of the gfx950 kernels in bs_kernels.hpp.
-//
-// Host responsibilities only: device memory, one HIP stream, launch geometry, event timing,
-// H2D/D2H staging.  Every decision is computed on the GPU; there is no CPU evaluation path here
+// bsched.hip — C ABI of include/bsched.h on top of the gfx950 kernels in bs_kernels.hpp: contexts, loads, the batch and the single queries
+// (the pod-by-pod pass, the Permit timeout and the bound-pod table / preemption calls sit beside their kernels in tu_seq.hip,
+// tu_seq_expire.hip and tu_preempt.hip; bs_ctx.hpp is what the four share).  Host responsibilities only: device memory, one HIP stream, launch
+// geometry, event timing, H2D/D2H staging.  Every decision is computed on the GPU; there is no CPU evaluation path here
 // (the CPU restatement lives in oracle/ and is test infrastructure).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>   // types and enums only: librccl itself is dlopen'ed on demand (hosts without RCCL can still load the library)
 
 #include <algorithm>
 #include <cstdio>
@@ -18,29 +17,14 @@
 #ifndef BS_UNITY
 #define BS_TU_MAIN
 #endif
-#include "bs_kernels.hpp"
+#include "bs_ctx.hpp"
 #include "bs_fast.hpp"
 #include "bs_epoch.hpp"
 #include "bs_sort.hpp"
 #include "bs_fit.hpp"
 #include "bs_queue.hpp"
 #include "bs_fdeny.hpp"
-#include "bs_seq.hpp"
-#include "bs_seq_expire.hpp"
-#include "bs_seq_expire_list.hpp"
 #include "bs_launch.hpp"
-#include "bs_carve.hpp"
-#include "bs_hostmem.hpp"
-#include "bs_pod_ranges.hpp"
-#include "bs_preempt.hpp"
-#include "bs_preempt_commit.hpp"
-#include "bs_preempt_commit_gang.hpp"
-#include "bs_preempt_gang_runs.hpp"
-#include "bs_preempt_geom.hpp"
-#include "bs_bound_apply.hpp"
-#include "bs_bound_nodes.hpp"
-#include "bs_bound_nodes_replay.hpp"
-#include "bs_pdb.hpp"
 #ifdef BS_UNITY   // one translation unit (the probe builds: g_probe / g_seq_scan_ph are per translation unit)
 #include "tu_fast.hip"
 #include "tu_seq.hip"
@@ -48,11 +32,7 @@
 #include "tu_preempt.hip"
 #endif
 
-using namespace bs;
-
 namespace {
-
-struct EventPair { hipEvent_t a, b; uint32_t id; };
 
 // Host-side packing of the fit-builder inputs: every array goes into one byte arena (16-byte aligned
 // pieces) that is uploaded with a single copy.
@@ -66,296 +46,6 @@ struct FitArena {
   }
 };
 template <typename T> const T* at_dev(const void* base, size_t off) { return reinterpret_cast<const T*>((const uint8_t*)base + off); }
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }   // LDS sizing and the two hand-added result blocks (ensure_hout, bs_batch_read)
-// element n of a device array that may not exist yet (null + n is undefined behaviour even if nobody follows the pointer)
-template <class T>
-T* at(T* p, size_t n) { return p ? p + n : nullptr; }
-
-// One pod pack = the arrays of bs_pods_soa for exactly `p` pods (the part a load uploads in ONE copy, `in_bytes`) followed by
-// the per-pod ids the library derives (request class, (group, class) pair): what travels with a pod when the queue is patched.
-// The pinned staging buffer uses the same layout (input part only) — and its OWN copy of it (bs_pods_map must not disturb the
-// resident queue).
-struct PodLayout {
-  Piece<int32_t> group;
-  Piece<int64_t> req;
-  Piece<uint32_t> pres, cls, pclass, ppair;
-  Piece<uint64_t> owner;
-  Piece<uint8_t> flags;
-  size_t in_bytes = 0, bytes = 0;
-  uint32_t p = 0;
-};
-PodLayout pod_layout(uint32_t P, uint32_t L) {
-  const size_t n = std::max<uint32_t>(P, 1);
-  PodLayout l;
-  Carve cv;
-  l.group = cv.take<int32_t>(n);
-  l.req = cv.take<int64_t>(n * L);
-  l.pres = cv.take<uint32_t>(n);
-  l.cls = cv.take<uint32_t>(n);
-  l.owner = cv.take<uint64_t>(n);
-  l.flags = cv.take<uint8_t>(n);
-  l.in_bytes = cv.mark();
-  l.pclass = cv.take<uint32_t>(n);
-  l.ppair = cv.take<uint32_t>(n);
-  l.bytes = cv.mark();
-  l.p = P;
-  return l;
-}
-
-}  // namespace
-
-struct bs_ctx {
-  bs_config cfg{};
-  uint32_t L = 4, S = 0, LP = 4;
-  std::string last_error;
-
-  // ---- nodes
-  bool have_nodes = false, have_fit = false, have_groups = false, have_pods = false;
-  uint32_t N = 0, Ncap = 0, M = 0, C = 0, fit_words = 0;
-  DevBuf d_alloc, d_nreq, d_apres, d_rpres, d_nflags, d_fit, d_kmap, d_m, d_left4, d_lglob;
-  DevBuf d_fitarena, d_fitcols;                  // bs_fit_build inputs / label columns
-  std::vector<int64_t> h_alloc, h_nreq;          // [L][N] mirrors (churn + read-back)
-  std::vector<uint32_t> h_apres, h_rpres, h_kmap;
-  std::vector<uint8_t> h_nflags;
-  std::vector<uint32_t> h_fit;                   // [C][fit_words]
-
-  // ---- groups
-  uint32_t G = 0, n_uncaptured = 0;   // groups without a pod (first-pod capture possible)
-  std::vector<uint32_t> h_gmatched, h_gcls;
-  std::vector<uint8_t> h_gflags;
-  int32_t steady_table = -1;        // the one table every reservation query uses when no capture can occur, -1 unknown
-  // Speculation (bs_batch_run): a group patch re-runs findMaxPG on the device, and the host would have to wait for its answer (the
-  // table id) before it can launch the chain — ~4 us of idle GPU and ~10 us of spinning per cycle.  In a steady state the answer is
-  // nearly always the one of the cycle before, so the chain is launched on THAT and checked when the results are first asked for
-  // (batch_settle): a wrong guess costs one re-run, a right one nothing.
-  int32_t steady_prev = -1;          // steady_table of the last resolved analysis
-  bool spec_active = false;          // the last batch ran on a guessed table that nobody has checked yet
-  int32_t spec_table = -1;
-  uint32_t spec_stages = 0;
-  uint32_t no_spec = 0;              // BS_NO_SPECULATE=1
-  uint64_t n_spec = 0, n_spec_miss = 0;
-  // BS_HOST_PROBE=1: where bs_batch_run's host time goes (ns, accumulated; printed at bs_destroy)
-  uint32_t host_probe = 0;
-  uint64_t hp_ns[6] = {0, 0, 0, 0, 0, 0}, hp_n = 0, hp_t0 = 0, hp_t1 = 0;
-  uint64_t early_filter_min = 200000000ull;   // pod x node pairs from which Filter overlaps the scan
-  // groups live in ONE device allocation (one pinned-staged H2D per load); d_info / h_info carry what findMaxPG
-  // found for the loaded state back to the host without a stream wait (see resolve_groups)
-  DevBuf d_gpack, d_info, d_gdelta;
-  Piece<uint32_t> off_gmm, off_gsc, off_gmatched, off_gcls, off_gmrpres;
-  Piece<uint8_t> off_gflags;
-  Piece<int64_t> off_gminres;
-  Piece<uint64_t> off_gocc;
-  size_t gpack_bytes = 0;
-  int32_t info_tag = 0, kinfo_tag = 0;
-  bool info_pending = false, kinfo_pending = false;
-  uint32_t max_group_cls = 0, max_pod_cls = 0;   // largest fit class any HAS_POD group / grouped pod names (checked against C per batch)
-  uint32_t h_K = 0;                  // request classes of the loaded pods (valid after resolve_pods)
-  uint32_t k_bound = 0;              // while kinfo_pending: an upper bound of the class count the device holds (last known K + pods inserted since)
-
-  // ---- pods
-  uint32_t P = 0;
-  // pods live in ONE device allocation (one H2D per batch from a pinned staging buffer); outputs likewise (one D2H)
-  DevBuf d_pack[2], d_outpack;       // two pod packs: bs_pods_apply compacts from the current one into the other
-  PodLayout lay[2], stage_lay;       // their layouts, and the staging buffer's own
-  uint32_t cur_pack = 0;
-  bool last_use_classes = false;
-  uint32_t map_p = 0;                // pods the staging buffer is currently mapped for (bs_pods_map), 0 = not mapped
-  // queue-resident cycle (bs_pods_apply, bs_queue.hpp)
-  DevBuf d_gstat2, d_cdir, d_pdir, d_ckeys, d_cpres, d_pkeys;
-  uint32_t gstat_cur = 0;            // which of d_gstat / d_gstat2 holds the per-group minima of the resident queue
-  uint32_t pair_cap = 0, dir_slots = 0;   // id space of classes / pairs between two derivations; hash slots of each directory
-  uint32_t ids_used = 0;             // upper bound of the class / pair ids drawn since the last derivation
-  bool rep_valid = false;            // d_cls_rep / d_cls_id / pair ids still name pods of the resident queue (no compaction since)
-  bool dirs_ready = false;           // the directories match the resident queue's classes and pairs
-  uint32_t id_room = 0;              // BS_ID_ROOM: ids beyond the queue length (0 = the default: as many again + 1024)
-  uint32_t serial_insert_max = 2048; // more inserted pods than this: re-derive in parallel instead of the insert wave
-  uint64_t n_applies = 0, n_rederives = 0;
-  Piece<uint8_t> off_pf_code, off_fl_code, off_ready;
-  Piece<uint32_t> off_pf_first_k, off_fl_feasible, off_fl_slot, off_admit;
-  Piece<int32_t> off_pf_leader;
-  size_t outpack_bytes = 0;
-
-  // ---- batch scratch / outputs
-  DevBuf d_first_elig, d_first_owner, d_first_reject, d_first_pod, d_cap_epoch;
-  DevBuf d_epoch, d_nepochs, d_leader_epoch, d_panic_epoch;
-  DevBuf d_tcode, d_stage, d_leader_raw, d_first_row, d_first_row64, d_scan_rec, d_feas_rec, d_chunk_rec, d_qreq_s, d_qflags_s, d_qpos;
-  DevBuf d_needed, d_qcount, d_ticket, d_desc;
-  bool scratch_armed = false;
-  bool side_ready = false;      // desc[] of the steady-state table is in place for the next batch   // per-group minima are INF (k_init ran, or the previous batch's k_tally re-armed them)
-  DevBuf d_tables, d_kp, d_stats, d_fparams, d_fflags, d_chunk_tot, d_blk_scratch, d_gmax, d_chunk_kp;
-  // request slots (see BatchDev): classes of the loaded pods + per-batch slot arrays
-  DevBuf d_cls_slots, d_cls_rep, d_cls_id, d_qtab_s, d_fu_slot, d_uparams, d_uflags, d_uclaim, d_fu_bitmap, d_fu_feas;
-  DevBuf d_nodew;                    // node words of the batch (BatchDev::nodew): 3 tables x (W + 2) word pairs + the two leaders' maxSingle
-  bool batch_void = false;           // the last batch's results must not be handed out (check_handover); cleared by the next bs_batch_run
-  uint32_t tp_tmin = 768;            // BS_TP_TMIN: tiles of Filter slots from which the transposed items take pairs of tiles (x ranks on a sharded context)
-  bool no_nodew = false;             // BS_NO_NODEW=1: the transposed Filter item derives the node-only masks of every block itself (rounds 4-5; A/B switch)
-  uint32_t slot_keep = 0xFFFFFFFFu;   // BS_HASH_SLOT_BITS (tests): directory probes start at hash & slot_keep
-  uint32_t cls_cap = 0, hash_keep = 0x7FFFFFFFu, n_nominres = 0, scan_slots_cap = 0, filter_slots_cap = 0;
-  DevBuf d_fl_bitmap, d_admit, d_ready, d_gcount, d_admit64, d_own_start;
-  bool owner_ready = false;          // own_start[] matches the resident queue and the group count (sharded contexts only)
-  // fast path (bs_fast.hpp)
-  DevBuf d_order_rank, d_sort;         // queue ordering: per-group order ranks; inputs | index ping-pong | permutation
-  uint32_t order_g = 0;
-  DevBuf d_gstat, d_pair_next, d_pair_firstq, d_first_reach, d_qstamp_s, d_fast_reject, d_epoch_group;
-  bool pairs_ready = false;          // d_gstat / pairs match the loaded pods and G
-  bool bitmap_valid = false;         // d_fl_bitmap holds the expanded rows of the last batch
-  bool last_fast = false;
-  bool batch_since_pods = false;     // a batch ran over the loaded pods (its slot mode is the one the rows have)
-  size_t off_hfeas = 0, off_htag = 0; // in h_hout
-  uint32_t hstride = 0;
-  int32_t host_tag = 0;
-  bool last_host_out = false;
-  uint32_t no_fast = 0;
-  // positional three-launch chain (bs_epoch.hpp): analysis of (groups, pods) kept across batches
-  DevBuf d_run_of_epoch, d_run_leader, d_gslot, d_gfirstq;
-  bool epochs_ready = false, einfo_pending = false;
-  int32_t einfo_tag = 0;
-  uint32_t h_R = 0, h_eflags = 0, no_epoch = 0;
-  uint32_t last_chain = 0;           // 0 general chain, 1 steady-state chain, 2 positional chain
-  uint32_t last_rows = 0;            // Filter slot rows of the last positional batch
-  // single-query scratch
-  DevBuf d_sq;
-  DevBuf d_seq;                      // bs_seq_run: scaled allocatables, keys, per-gang / per-pod bookkeeping, results
-  // bs_seq_expire / bs_seq_waiting_read: the waiting state the last pass left in d_seq (chains, heads, counts) is valid from a successful
-  // bs_seq_run until the first call that renumbers what it indexes (queue loads / patches, node loads / APPEND / REMOVE, group loads)
-  bool seq_wait_valid = false;
-  Piece<unsigned long long> seq_o_wait;
-  Piece<uint32_t> seq_o_head, seq_o_nwait;
-  DevBuf d_sexp;                     // per-call scratch: block totals, slots, rows, dirty list, records
-  DevBuf d_sexp_nodes;               // per-node delta [L][N], key bits, dirty words: zero between calls (k_se_nodes re-zeroes what it read)
-  uint32_t sexp_n = 0, sexp_l = 0;   // the layout d_sexp_nodes was zeroed for
-  bool sexp_clean = false;
-  uint32_t table_slots = 0, table_mcap = 0;
-
-  uint32_t rank = 0, nranks = 1;
-  bool reduce_external = false;      // partitioned mode: tally only, the caller reduces and calls bs_batch_finish
-  uint32_t* ext_admit = nullptr;     // caller-owned device memory for the admit counters
-  int32_t sop_leader0 = -1;
-  uint32_t last_stages = 0;
-  // Batch counters.  batch_seq: monotonic, 64 bit (timing sampling, statistics).  stamp_ctr in [0, 65534]: slot stamps are
-  // 1 + stamp_ctr (16 bits in the slot words); when it comes round to 0 the stamped arrays are zeroed, so a slot nobody wrote
-  // for 65535 batches cannot look live again.  key_seq in [1, 0xFFFFFFFE]: the 64-bit atomicMin keys carry ~key_seq in the
-  // high word ("a newer batch always wins", never all-ones = the 'none' the arrays are born with); when it runs out it
-  // restarts at 1 behind a re-fill of the keyed arrays with 'none' (once per 2^32 - 2 batches).
-  uint64_t batch_seq = 0;
-  uint32_t stamp_ctr = 1, key_seq = 1;
-  bool rekey_pending = false;
-  bool batch_pending_finish = false;
-  bool groups_launch_pending = false; // bs_groups_apply left its (inline) deltas + findMaxPG for the next launch: k_pods_apply takes them along, anything else flushes
-  DeltaPack pending_dp{};
-  uint32_t no_fuse_final = 0;        // BS_NO_FUSE_FINAL: launches B and C always as separate launches
-  uint32_t tp_filter = 6;            // BS_TP_FILTER (throughput regime = more than 16 tiles of class slots): 0 = scan and Filter roles in one launch (k_fast_scan_filter: rounds 2-4),
-                                     // 1..4 = k_fast_scan, then k_fast_filter<4,DB> / <2,DB> / <2,!DB> / k_fast_filter_w7 (109 / 93 / 75 / 72 VGPRs),
-                                     // 5 = k_fast_scan, then k_fast_filter_t (the transposed item, bs_filter_t.hpp: 64 VGPRs),
-                                     // 6 / 7 = one launch, Filter role by the transposed item (7: the Filter blocks first),
-                                     // 8 = as 5, the two launches side by side on two streams
-  uint32_t tp_share = 0;             // BS_TP_SHARE: scan shares per tile of class slots when launch B is not the fused form (at most);
-                                     // 0 = 2 in the throughput regime, 64 otherwise (what the sweeps of profiles/r04c_* say)
-  uint32_t tp_fwaves = 0;            // BS_TP_FWAVES: waves the Filter work of that regime is cut for; 0 = 16384 from 65 536 (tile, two node
-                                     // blocks) units on, filter_waves below; an explicit BS_FILTER_WAVES rules
-  bool filter_waves_env = false;
-  uint32_t tp_split = 0;             // BS_TP_SPLIT: the transposed Filter items are cut for tp_split x the launched waves and dealt out tile quad by
-                                     // tile quad (filter_loop_t, by_tile); 0 = 2 on a rank of a sharded context (bs_shard_set), 1 otherwise.
-                                     // Class ids follow the queue (k_pod_class_ids), so all but 1 / nranks of the slot tiles are idle on a rank and
-                                     // return at their first load; the live ones are cut finer so that they spread over more of the launched
-                                     // waves.  cfg4 all-distinct, rank 0 of 8 (profiles/r05_shard_scaling.md): 60 us at x2, 63 at x4, 74 at x8
-                                     // (an item's prologue — requests, bounds, first node block — is ~4 us whatever its length).
-  int fused_blocks_resident = -1;    // whole-chip residency of k_fast_scan_filter_final (blocks), -1 = not asked yet
-  int step_a_resident[2] = {-1, -1};          // ... of k_fast_step_a
-  // The one-launch form of launch A + the scan / Filter roles (k_fast_step_a, then k_fast_final), where it applies (the latency regime: at most 256
-  // classes, 64 table chunks, 4 scalar lanes; the second batch over a queue onwards).  BS_STEP_A=3, the DEFAULT: the whole-step form — the class-slot
-  // form below whose pod blocks go on to the final verdicts inside the same launch (one launch per step; run_fast falls back to form 2 where it does not apply).
-  // BS_STEP_A=2: the class-slot form — class_slots_block publishes every class's slots from the class directory, the pod blocks gate nobody; k_fast_final
-  // follows as a second launch.  BS_STEP_A=1: every pod block publishes (kept as a tested experiment).  BS_STEP_A=0: off.  Step times: BASELINE.md.
-  uint32_t step_a_form = 3;
-  bool step_a_on = true;
-  uint32_t step_shares = 8;          // BS_STEP_SHARES: blocks that share one table chunk's class slots (at most).  8 was the fastest of 2 / 4 / 8 / 16 under BS_STEP_A=2
-                                     // (profiles/r06_step_a_class_slots_shares.txt); the whole-step form has not been swept
-  uint32_t test_timeout_after = 0;   // BS_TEST_HANDOVER_TIMEOUT=n (test hook): the n-th one-launch step reports a timed-out hand-over as the device would
-  uint32_t test_pc_chunk_nodes = 0;  // BS_TEST_PC_CHUNK_NODES=n (test hook): nodes per chunk of the preemption grids (bs_preempt_geom.hpp); 0 = the shipped geometry
-  uint32_t tk_pods = 0, tk_tab = 0;  // values of ticket[8] / ticket[9] the next k_fast_step_a starts from (never reset: wrap-safe differences)
-  uint32_t tk_p1 = 0, tk_done = 0;   // ... of the spread counter at kTkP1 (form 3: the pod blocks' first halves); tk_done: of the counter at kTkDone (large queues: every table / Filter block adds once)
-  // form 3's gang-aligned pod ranges (bs_pod_ranges.hpp): computed by bs_pods_load, dropped by bs_pods_apply (256 pods per block until the next load)
-  bool pod_ranges_on = true;         // BS_POD_RANGES=0: 256 pods per block always (A/B switch)
-  bool ranges_valid = false;         // (also dropped by a bs_groups_load that changes the group count: the local flags are per group)
-  uint32_t nranges = 0;
-  PodRanges h_ranges;
-  std::vector<uint32_t> h_pod_ranges;  // BatchDev::pod_ranges as uploaded (the copy reads it: rewritten only after h_stage.wait)
-  DevBuf d_pod_ranges;
-  bool last_step_a = false;
-  uint32_t scan_share_override = 0, no_fuse_filter = 0, early_forced = 0, target_waves = 8192, filter_waves = 8192, collect_stats = 0;
-  uint32_t general_waves = 4096;     // scan grid cap of the general chain (tools/cold_sweep.py)
-  bs_batch_stats stats{};
-
-  // ---- timing
-  std::vector<EventPair> events;
-  size_t events_used = 0;
-  bs_timing timing{};
-
-  // ---- native RCCL (dlopen'ed on demand; entry points resolved once in bs_comm_init)
-  void* rccl_handle = nullptr;
-  void* comm = nullptr;
-  decltype(&ncclAllReduce) rccl_allreduce = nullptr;
-  decltype(&ncclCommDestroy) rccl_destroy = nullptr;
-  uint32_t launches = 0;             // kernel launches of the last batch
-  // BS_BATCH_FILTER_DENY (bs_fdeny.hpp)
-  DevBuf d_fd_event, d_fd_in, d_fd_flag;
-  bool fd_on = false;                // the run being launched replays Filter's deny entry
-  bool fd_active = false;            // the last batch did, and nobody has looked at its flag words yet (fd_settle)
-  uint32_t first_reach_hint = 0xFFFFFFFFu;   // bs_first_reach_hint (partitioned mode), reset by every queue load / patch
-  bool fd_unsynced = false;          // a BS_BATCH_FILTER_DENY batch was launched and the stream has not been waited for since
-  bool fd_in_live = false;           // a fixed-point re-run: the chains honour d_fd_in
-  uint32_t fd_iter = 0, fd_stages = 0, fd_seq_inv = 0;
-  uint64_t n_fd_reruns = 0;          // fixed-point re-runs so far (bs_batch_stats_get)
-  // preemption (bs_preempt.hpp): the bound-pod table, CSR by node in importance order, in one allocation; per-call scratch
-  bool have_bound = false;
-  uint32_t bound_b = 0, bound_n = 0;  // entries, node count at the load
-  int32_t bound_max_group = -1;      // largest group index the table names (checked against the group count per call)
-  DevBuf d_bound, d_pre;
-  DevBuf d_bound2;                   // bs_preempt_commit's compaction target (swapped with d_bound)
-  BoundLayout blay{};
-  uint32_t bound_ids = 0;            // the id space of bs_bound_pdb_set: entries at the last bs_bound_load plus what bs_bound_apply inserted since
-  std::vector<uint32_t> pre_npv;     // PDB-violating victims per preemptor of the last preemption call (bs_preempt_pdb_read)
-  bool have_pre_npv = false;
-  // bs_preempt_gang_read: slot_voided[count] / group_placed[g] of the last bs_preempt_commit_gang, while it is the last preemption call
-  std::vector<uint8_t> gang_voided;
-  std::vector<uint32_t> gang_placed;
-  bool have_gang = false;
-  // resident PodDisruptionBudgets (bs_pdb.hpp): allowed[pdb_n], and the PDBs of every covered bound-pod id as a CSR by id; dropped by bs_bound_load
-  bool have_pdb = false;
-  uint32_t pdb_n = 0, pdb_covered = 0, pdb_members = 0;   // PDBs, ids the CSR covers, membership entries (= moff[pdb_covered])
-  DevBuf d_pdb_allowed, d_pdb_moff, d_pdb_member;
-
-  // ---- streams, events, pinned host memory.  Declared LAST and in this order: members are destroyed in reverse, so the pinned buffers
-  // and events go first, then stream3, then stream, and only then the DevBufs above (bs_destroy has waited for both streams).
-  Stream stream;
-  Stream stream3;                    // early Filter: runs beside the node scan when no capture can occur
-  Event ev_query, ev_filter;
-  PinnedBuf<int32_t> h_info{PinWait::None, hipHostMallocMapped | hipHostMallocCoherent};   // [16], kernels write it directly: leader, panic, steady table, tag | K of the loaded pods, tag | ...
-  PinnedBuf<> h_gstage{PinWait::Event};   // groups pack, then deltas
-  PinnedBuf<> h_stage{PinWait::Event};    // pod staging; busy until the last H2D out of it is through (bs_pods_load does not wait for it)
-  PinnedBuf<> h_dstage{PinWait::Stream};  // the delta the apply kernel reads in place (no event per apply: bs_pods_apply)
-  PinnedBuf<> h_nstage{PinWait::Event};   // node requests of bs_nodes_assume
-  PinnedBuf<> h_pdbstage{PinWait::Stream};  // bs_pdb_allowed_apply's (index, value) pairs, read in place by k_pdb_allowed
-  // result staging (bs_batch_read) and, in latency mode, the pinned result pack the last launch writes itself
-  PinnedBuf<> h_rstage;
-  PinnedBuf<> h_hout{PinWait::None, hipHostMallocMapped | hipHostMallocCoherent};            // [outpack layout | feas[hstride] | tag]
-  PinnedBuf<uint64_t> h_hrows{PinWait::None, hipHostMallocMapped | hipHostMallocCoherent};   // [W + 1][hstride]
-};
-
-namespace {
-
-const char* kKernelNames[BS_KERNEL_COUNT] = {"prepass", "leader", "query", "tables", "scan", "resolve", "filter", "tally"};
-
-#define HIPCHK(ctx, call)                                                                         \
-  do {                                                                                            \
-    hipError_t _e = (call);                                                                       \
-    if (_e != hipSuccess) {                                                                       \
-      (ctx)->last_error = std::string(#call) + ": " + hipGetErrorString(_e);                      \
-      return BS_ERR_HIP;                                                                          \
-    }                                                                                             \
-  } while (0)
 
 int timer_begin(bs_ctx* c, uint32_t id, size_t* slot, hipStream_t st = nullptr) {
   *slot = (size_t)-1;
@@ -393,15 +83,6 @@ int timer_collect(bs_ctx* c) {
   return BS_OK;
 }
 
-// a failed launch is reported with the kernel group it belongs to (bs_kernel_name)
-#define LAUNCHCHK(ctx, id)                                                                         \
-  do {                                                                                             \
-    hipError_t _e = hipGetLastError();                                                             \
-    if (_e != hipSuccess) {                                                                        \
-      (ctx)->last_error = std::string("launch of kernel group '") + kKernelNames[id] + "': " + hipGetErrorString(_e); \
-      return BS_ERR_HIP;                                                                           \
-    }                                                                                              \
-  } while (0)
 #define TIMED_ON(ctx, id, st, ...)                             \
   do {                                                         \
     size_t _slot;                                              \
@@ -423,81 +104,11 @@ void advance_batch_seq(bs_ctx* c) {
 }
 
 int flush_groups(bs_ctx* c);
-// Every entry point starts here.  A group patch whose launch was deferred (bs_groups_apply) goes out now, unless the caller
-// is the one call that can take it along in its own launch (bs_pods_apply).
-int use_device(bs_ctx* c, bool flush = true) {
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  if (flush && c->groups_launch_pending) return flush_groups(c);
-  return BS_OK;
-}
-
-NodesDev nodes_dev(const bs_ctx* c) {
-  NodesDev nd{};
-  nd.n = c->N;
-  nd.stride = c->Ncap;
-  nd.alloc = c->d_alloc.as<int64_t>();
-  nd.req = c->d_nreq.as<int64_t>();
-  nd.apres = c->d_apres.as<uint32_t>();
-  nd.rpres = c->d_rpres.as<uint32_t>();
-  nd.flags = c->d_nflags.as<uint8_t>();
-  nd.fit = c->d_fit.as<uint32_t>();
-  nd.fit_words = c->fit_words;
-  nd.n_classes = c->C;
-  nd.kmap = c->d_kmap.as<uint32_t>();
-  nd.m = c->M;
-  nd.left4 = c->d_left4.as<int64_t>();
-  nd.lglob = c->d_lglob.as<int64_t>();
-  return nd;
-}
-GroupsDev groups_dev(const bs_ctx* c) {
-  GroupsDev g{};
-  g.g = c->G;
-  void* pk = c->d_gpack.p;
-  g.min_member = c->off_gmm.in(pk);
-  g.status_scheduled = c->off_gsc.in(pk);
-  g.matched = c->off_gmatched.in(pk);
-  g.flags = c->off_gflags.in(pk);
-  g.cls = c->off_gcls.in(pk);
-  g.minres = c->off_gminres.in(pk);
-  g.mrpres = c->off_gmrpres.in(pk);
-  g.occupied = c->off_gocc.in(pk);
-  return g;
-}
-// The bound-pod table: its nine columns at the offsets of a BoundLayout (bound_layout, bs_bound_nodes.hpp), typed once.  U8 is
-// uint8_t (a table that is written: the staging copy of a load, a compaction target) or const uint8_t; a null base gives null columns.
-template <class U8>
-struct BoundCols {
-  template <class T> using Col = std::conditional_t<std::is_const_v<U8>, const T, T>*;
-  Col<uint32_t> boff, id, pres, nviol;
-  Col<int32_t> prio, group;
-  Col<int64_t> start, req;
-  Col<uint8_t> pdb;
-};
-template <class U8>
-BoundCols<U8> bound_cols(U8* base, const BoundLayout& l) {
-  return {Piece<uint32_t>{l.boff}.in(base), Piece<uint32_t>{l.id}.in(base), Piece<uint32_t>{l.pres}.in(base), Piece<uint32_t>{l.nviol}.in(base), Piece<int32_t>{l.prio}.in(base),
-          Piece<int32_t>{l.group}.in(base), Piece<int64_t>{l.start}.in(base), Piece<int64_t>{l.req}.in(base), Piece<uint8_t>{l.pdb}.in(base)};
-}
-// the seven columns every device struct over the table names (PreemptDev, CommitDev, CompactDev, BoundApplyDev, BoundNodesDev); bpres and
-// bnviol are set from the returned view where the struct has them
-template <class D, class U8>
-BoundCols<U8> bound_dev(D& d, U8* base, const BoundLayout& l) {
-  const BoundCols<U8> t = bound_cols(base, l);
-  d.boff = t.boff; d.bprio = t.prio; d.bstart = t.start; d.bgroup = t.group; d.bid = t.id; d.breq = t.req; d.bpdb = t.pdb;
-  return t;
-}
 // the six input columns of a pod pack, for PodsDev and PodsMut
 template <class D>
 void pod_cols(D& p, const PodLayout& l, void* pk) {
   p.group = l.group.in(pk); p.req = l.req.in(pk); p.pres = l.pres.in(pk); p.cls = l.cls.in(pk); p.owner = l.owner.in(pk); p.flags = l.flags.in(pk);
 }
-PodsDev pods_dev(const bs_ctx* c) {
-  PodsDev p{};
-  p.p = c->P;
-  pod_cols(p, c->lay[c->cur_pack], c->d_pack[c->cur_pack].p);
-  return p;
-}
-uint32_t* pclass_dev(const bs_ctx* c) { return c->lay[c->cur_pack].pclass.in(c->d_pack[c->cur_pack].p); }
 uint32_t* ppair_dev(const bs_ctx* c) { return c->lay[c->cur_pack].ppair.in(c->d_pack[c->cur_pack].p); }
 uint32_t* gstat_dev(const bs_ctx* c) { return (c->gstat_cur ? c->d_gstat2 : c->d_gstat).as<uint32_t>(); }
 BatchDev batch_dev(const bs_ctx* c) {
@@ -667,9 +278,7 @@ int upload_nodes(bs_ctx* c, uint32_t lo = 0) {
   // rows contributed by the unchanged nodes [0, base0): kmap is increasing, so a lower bound finds them
   uint32_t m_before = 0;
   if (base0) m_before = (uint32_t)(std::lower_bound(c->h_kmap.begin(), c->h_kmap.end(), base0) - c->h_kmap.begin());
-  NodesDev nd = nodes_dev(c);
-  hipLaunchKernelGGL(k_nodes_derive, dim3(1), dim3(kScanBlock), 0, c->stream, nd, c->d_kmap.as<uint32_t>(), c->d_m.as<uint32_t>(), c->d_left4.as<int64_t>(),
-                     c->d_lglob.as<int64_t>(), base0, m_before);
+  rederive_nodes(c, base0, m_before);
   HIPCHK(c, hipGetLastError());
   uint32_t m = 0;
   HIPCHK(c, hipMemcpyAsync(&m, c->d_m.p, 4, hipMemcpyDeviceToHost, c->stream));
@@ -776,42 +385,6 @@ int build_scratch_table(bs_ctx* c, uint32_t cls, float pct, uint32_t* slot_out) 
   if (nchunks > 1) hipLaunchKernelGGL(k_tables_fix, dim3(1, nchunks - 1), dim3(kTblChunk), 0, c->stream, nodes_dev(c), b2, p, forced);
   HIPCHK(c, hipGetLastError());
   *slot_out = slot;
-  return BS_OK;
-}
-
-// After the group state (or the fit classes) changed: re-arm the general chain's scratch and run findMaxPG for
-// the loaded state (k_leader_info).  For the no-capture case it also decides, on the device, which single table
-// every reservation query of a batch will use — leader with matched > 0 means every other group's pods reserve
-// for it at percent 0.7 against the leader's fit class (core.go:157-161) — and writes that table's descriptor.
-// Leader, panic flag and table id come back through pinned memory; nothing waits here (resolve_groups does, at
-// the next bs_batch_run, and then only if the copy has not landed yet).
-int analyse_groups(bs_ctx* c, bool rearm_scratch = true, const bs_group_delta* deltas = nullptr, uint32_t ndeltas = 0, bool defer = false) {
-  if (c->groups_launch_pending) { int rc = flush_groups(c); if (rc) return rc; }     // an earlier patch is still waiting: it goes first
-  c->steady_table = -1;
-  c->side_ready = false;
-  c->info_pending = false;
-  if (!c->G) { c->scratch_armed = false; return BS_OK; }
-  GroupsDev gr = groups_dev(c);
-  BatchDev b = batch_dev(c);
-  if (rearm_scratch) {
-    hipLaunchKernelGGL(k_init, dim3(cdiv(std::max<uint32_t>(c->G, 8), 256)), dim3(256), 0, c->stream, gr, b);
-    c->scratch_armed = true;
-  }
-  DeltaPack dp;
-  dp.n = ndeltas;
-  static_assert(sizeof(bs_group_delta) == sizeof(GroupDelta), "delta layout");
-  if (ndeltas) std::memcpy(dp.d, deltas, (size_t)ndeltas * sizeof(GroupDelta));
-  c->info_tag++;
-  c->info_pending = true;
-  c->epochs_ready = false;
-  if (defer) {                                       // the launch is left to whoever touches the stream next (k_pods_apply takes it along)
-    c->pending_dp = dp;
-    c->groups_launch_pending = true;
-    return BS_OK;
-  }
-  hipLaunchKernelGGL(k_leader_info, dim3(1), dim3(kLeaderBlock), 0, c->stream, gr, b, (c->have_fit && c->have_nodes) ? c->C : 0u, c->info_tag, c->h_info.p,
-                     dp, const_cast<uint32_t*>(gr.matched), const_cast<uint32_t*>(gr.status_scheduled), const_cast<uint8_t*>(gr.flags));
-  LAUNCHCHK(c, BS_KERNEL_LEADER);
   return BS_OK;
 }
 
@@ -1002,6 +575,111 @@ int analyse_epochs(bs_ctx* c) {
   return BS_OK;
 }
 
+int resolve_epochs(bs_ctx* c) {
+  if (!c->einfo_pending) return BS_OK;
+  int rc = wait_host_tag(c, 11, c->einfo_tag);
+  if (rc) return rc;
+  c->einfo_pending = false;
+  c->h_R = (uint32_t)c->h_info.p[8];
+  c->h_eflags = (uint32_t)c->h_info.p[9];
+  return BS_OK;
+}
+
+}  // namespace
+
+// ---- what the family units call too (declared in bs_ctx.hpp)
+extern "C" { static int fd_settle(bs_ctx* c); }
+namespace bs {
+const char* const kKernelNames[BS_KERNEL_COUNT] = {"prepass", "leader", "query", "tables", "scan", "resolve", "filter", "tally"};
+
+int use_device(bs_ctx* c, bool flush) {
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (flush && c->groups_launch_pending) return flush_groups(c);
+  return BS_OK;
+}
+
+NodesDev nodes_dev(const bs_ctx* c) {
+  NodesDev nd{};
+  nd.n = c->N;
+  nd.stride = c->Ncap;
+  nd.alloc = c->d_alloc.as<int64_t>();
+  nd.req = c->d_nreq.as<int64_t>();
+  nd.apres = c->d_apres.as<uint32_t>();
+  nd.rpres = c->d_rpres.as<uint32_t>();
+  nd.flags = c->d_nflags.as<uint8_t>();
+  nd.fit = c->d_fit.as<uint32_t>();
+  nd.fit_words = c->fit_words;
+  nd.n_classes = c->C;
+  nd.kmap = c->d_kmap.as<uint32_t>();
+  nd.m = c->M;
+  nd.left4 = c->d_left4.as<int64_t>();
+  nd.lglob = c->d_lglob.as<int64_t>();
+  return nd;
+}
+GroupsDev groups_dev(const bs_ctx* c) {
+  GroupsDev g{};
+  g.g = c->G;
+  void* pk = c->d_gpack.p;
+  g.min_member = c->off_gmm.in(pk);
+  g.status_scheduled = c->off_gsc.in(pk);
+  g.matched = c->off_gmatched.in(pk);
+  g.flags = c->off_gflags.in(pk);
+  g.cls = c->off_gcls.in(pk);
+  g.minres = c->off_gminres.in(pk);
+  g.mrpres = c->off_gmrpres.in(pk);
+  g.occupied = c->off_gocc.in(pk);
+  return g;
+}
+PodsDev pods_dev(const bs_ctx* c) {
+  PodsDev p{};
+  p.p = c->P;
+  pod_cols(p, c->lay[c->cur_pack], c->d_pack[c->cur_pack].p);
+  return p;
+}
+uint32_t* pclass_dev(const bs_ctx* c) { return c->lay[c->cur_pack].pclass.in(c->d_pack[c->cur_pack].p); }
+
+// k_nodes_derive from row block base0 on (m_before rows in front of it): kmap, the row count, left4 and the cluster bounds follow the node arrays
+void rederive_nodes(bs_ctx* c, uint32_t base0, uint32_t m_before) {
+  hipLaunchKernelGGL(k_nodes_derive, dim3(1), dim3(kScanBlock), 0, c->stream, nodes_dev(c), c->d_kmap.as<uint32_t>(), c->d_m.as<uint32_t>(), c->d_left4.as<int64_t>(),
+                     c->d_lglob.as<int64_t>(), base0, m_before);
+}
+
+// After the group state (or the fit classes) changed: re-arm the general chain's scratch and run findMaxPG for
+// the loaded state (k_leader_info).  For the no-capture case it also decides, on the device, which single table
+// every reservation query of a batch will use — leader with matched > 0 means every other group's pods reserve
+// for it at percent 0.7 against the leader's fit class (core.go:157-161) — and writes that table's descriptor.
+// Leader, panic flag and table id come back through pinned memory; nothing waits here (resolve_groups does, at
+// the next bs_batch_run, and then only if the copy has not landed yet).
+int analyse_groups(bs_ctx* c, bool rearm_scratch, const bs_group_delta* deltas, uint32_t ndeltas, bool defer) {
+  if (c->groups_launch_pending) { int rc = flush_groups(c); if (rc) return rc; }     // an earlier patch is still waiting: it goes first
+  c->steady_table = -1;
+  c->side_ready = false;
+  c->info_pending = false;
+  if (!c->G) { c->scratch_armed = false; return BS_OK; }
+  GroupsDev gr = groups_dev(c);
+  BatchDev b = batch_dev(c);
+  if (rearm_scratch) {
+    hipLaunchKernelGGL(k_init, dim3(cdiv(std::max<uint32_t>(c->G, 8), 256)), dim3(256), 0, c->stream, gr, b);
+    c->scratch_armed = true;
+  }
+  DeltaPack dp;
+  dp.n = ndeltas;
+  static_assert(sizeof(bs_group_delta) == sizeof(GroupDelta), "delta layout");
+  if (ndeltas) std::memcpy(dp.d, deltas, (size_t)ndeltas * sizeof(GroupDelta));
+  c->info_tag++;
+  c->info_pending = true;
+  c->epochs_ready = false;
+  if (defer) {                                       // the launch is left to whoever touches the stream next (k_pods_apply takes it along)
+    c->pending_dp = dp;
+    c->groups_launch_pending = true;
+    return BS_OK;
+  }
+  hipLaunchKernelGGL(k_leader_info, dim3(1), dim3(kLeaderBlock), 0, c->stream, gr, b, (c->have_fit && c->have_nodes) ? c->C : 0u, c->info_tag, c->h_info.p,
+                     dp, const_cast<uint32_t*>(gr.matched), const_cast<uint32_t*>(gr.status_scheduled), const_cast<uint8_t*>(gr.flags));
+  LAUNCHCHK(c, BS_KERNEL_LEADER);
+  return BS_OK;
+}
+
 // Both sides loaded and the state positional for sure (captures or MinResources defaults possible): analyse now, so the
 // first batch does not wait for it.  (A captured state whose leader has no matched pod is analysed by its first batch.)
 int maybe_analyse_epochs(bs_ctx* c) {
@@ -1028,26 +706,43 @@ void mirror_node_requests(bs_ctx* c, const bs_node_request* records, uint32_t n)
   }
 }
 
-int resolve_epochs(bs_ctx* c) {
-  if (!c->einfo_pending) return BS_OK;
-  int rc = wait_host_tag(c, 11, c->einfo_tag);
-  if (rc) return rc;
-  c->einfo_pending = false;
-  c->h_R = (uint32_t)c->h_info.p[8];
-  c->h_eflags = (uint32_t)c->h_info.p[9];
-  return BS_OK;
-}
-
-}  // namespace
-
-// =================================================================================================
-extern "C" {
-
 // A batch launched on a guessed table (speculation) or with BS_BATCH_FILTER_DENY is only final once fd_settle has looked at it — it may
 // have to run again.  Every call that changes what a batch reads (nodes, fit, groups) or that runs over the state itself (bs_seq_run)
 // settles it FIRST, against the state it was launched on; its results stay readable afterwards.
-static int fd_settle(bs_ctx* c);
-static int settle_pending(bs_ctx* c) { return (c->fd_active || c->spec_active) ? fd_settle(c) : BS_OK; }
+int settle_pending(bs_ctx* c) { return (c->fd_active || c->spec_active) ? fd_settle(c) : BS_OK; }
+
+// a final block of a fused launch gave up waiting for its producers: the batch's results are not to be trusted
+int check_handover(bs_ctx* c) {
+  if (c->h_info.p && ((volatile int32_t*)c->h_info.p)[13]) {   // the insert wave of a queue patch ran out of ids (the accounting should make that impossible)
+    ((volatile int32_t*)c->h_info.p)[13] = 0;
+    c->pairs_ready = false;                            // classes, pairs and directories are derived again from the resident queue
+    c->dirs_ready = false;
+    c->rep_valid = false;
+    c->ids_used = c->pair_cap;
+    const int rc2 = derive_pods(c, false);
+    c->n_rederives++;
+    c->batch_void = true;                              // whatever ran over the overflowed queue is void until the next bs_batch_run
+    c->last_error = "bs_pods_apply: class / pair id space overflowed on the device; the queue was re-derived, run the batch again";
+    return rc2 ? rc2 : BS_ERR_RETRY;
+  }
+  if (c->h_info.p && ((volatile int32_t*)c->h_info.p)[12]) {
+    ((volatile int32_t*)c->h_info.p)[12] = 0;
+    c->no_fuse_final = 1;                              // from now on: separate launches
+    c->batch_void = true;
+    c->last_error = "in-launch hand-over timed out (producer blocks not resident): batch void, run it again (the context now uses separate launches)";
+    return BS_ERR_RETRY;
+  }
+  if (c->batch_void) {                                 // (the word was consumed by an earlier look — bs_seq_run's, or a reader's — and no batch has run since)
+    c->last_error = "the last batch's results are void (hand-over time-out or queue re-derivation, reported earlier): run the batch again";
+    return BS_ERR_RETRY;
+  }
+  return BS_OK;
+}
+
+}  // namespace bs
+
+// =================================================================================================
+extern "C" {
 
 uint32_t bs_abi_version(void) { return BS_ABI_VERSION; }
 
@@ -2773,34 +2468,6 @@ int bs_batch_finish(bs_ctx* c) {
   return BS_OK;
 }
 
-// a final block of a fused launch gave up waiting for its producers: the batch's results are not to be trusted
-static int check_handover(bs_ctx* c) {
-  if (c->h_info.p && ((volatile int32_t*)c->h_info.p)[13]) {   // the insert wave of a queue patch ran out of ids (the accounting should make that impossible)
-    ((volatile int32_t*)c->h_info.p)[13] = 0;
-    c->pairs_ready = false;                            // classes, pairs and directories are derived again from the resident queue
-    c->dirs_ready = false;
-    c->rep_valid = false;
-    c->ids_used = c->pair_cap;
-    const int rc2 = derive_pods(c, false);
-    c->n_rederives++;
-    c->batch_void = true;                              // whatever ran over the overflowed queue is void until the next bs_batch_run
-    c->last_error = "bs_pods_apply: class / pair id space overflowed on the device; the queue was re-derived, run the batch again";
-    return rc2 ? rc2 : BS_ERR_RETRY;
-  }
-  if (c->h_info.p && ((volatile int32_t*)c->h_info.p)[12]) {
-    ((volatile int32_t*)c->h_info.p)[12] = 0;
-    c->no_fuse_final = 1;                              // from now on: separate launches
-    c->batch_void = true;
-    c->last_error = "in-launch hand-over timed out (producer blocks not resident): batch void, run it again (the context now uses separate launches)";
-    return BS_ERR_RETRY;
-  }
-  if (c->batch_void) {                                 // (the word was consumed by an earlier look — bs_seq_run's, or a reader's — and no batch has run since)
-    c->last_error = "the last batch's results are void (hand-over time-out or queue re-derivation, reported earlier): run the batch again";
-    return BS_ERR_RETRY;
-  }
-  return BS_OK;
-}
-
 int bs_batch_sync(bs_ctx* c) {
   if (!c) return BS_ERR_INVALID;
   int rc = use_device(c);
@@ -3309,363 +2976,6 @@ int bs_nodes_read(bs_ctx* c, int64_t* requested, uint32_t* requested_present) {
   return BS_OK;
 }
 
-int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
-  if (!c || !out) return BS_ERR_INVALID;
-  if (!c->have_nodes || !c->have_fit || !c->have_groups || !c->have_pods) {
-    c->last_error = "bs_seq_run needs nodes, fit, groups and pods loaded";
-    return BS_ERR_STATE;
-  }
-  if (!(stages & BS_STAGE_PREFILTER)) { c->last_error = "PREFILTER stage is mandatory"; return BS_ERR_INVALID; }
-  if ((stages & BS_BATCH_FILTER_DENY) && !(stages & BS_STAGE_FILTER)) { c->last_error = "BS_BATCH_FILTER_DENY needs BS_STAGE_FILTER"; return BS_ERR_INVALID; }
-  if (c->nranks > 1 || c->reduce_external) { c->last_error = "bs_seq_run is single-rank only (a sequential pass does not shard)"; return BS_ERR_STATE; }
-  int rc = use_device(c);
-  if (rc) return rc;
-  if ((rc = settle_pending(c))) return rc;
-  const uint32_t P = c->P, G = c->G, N = c->N, C = c->C, L = c->L;
-  if ((G > c->n_uncaptured && c->max_group_cls >= C) || (P && c->max_pod_cls >= C)) {
-    c->last_error = "fit class index out of range (groups.cls / pods.cls vs the loaded fit classes)";
-    return BS_ERR_INVALID;
-  }
-  if (G > 0x7FFFFFF0u) return BS_ERR_CAPACITY;
-  c->seq_wait_valid = false;                                // the pass replaces the waiting state
-  // the first-fit cursors are keyed by the resident queue's request classes: a queue patch whose insert wave ran out of class ids
-  // (h_info[13], set by the device) left them unusable until the queue is re-derived — check_handover does that
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  // An unread batch's error words are looked at here (the id overflow concerns this pass: check_handover re-derives the queue) but they stay
-  // that batch's: batch_void keeps every later read of it failing with BS_ERR_RETRY until bs_batch_run starts a new one.  The pass itself
-  // reads no batch result and goes on.
-  if ((rc = check_handover(c)) && rc != BS_ERR_RETRY) return rc;
-  if (rc == BS_ERR_RETRY) c->last_error.clear();            // (nothing failed for THIS call)
-  out->n_released = 0;
-  out->total_ns = 0;
-  out->node_picks = out->node_scans = out->scan_rounds = out->pick_rounds = out->leader_folds = out->table_builds = 0;
-  // ---- scratch: one allocation
-  const size_t nP = std::max<uint32_t>(P, 1), nG = std::max<uint32_t>(G, 1), cap = std::max<uint32_t>(out->cap, 1), stride = std::max<uint32_t>(c->Ncap, 1);
-  Carve cv;
-  const auto o_sc07 = cv.take<int64_t>(stride * L);
-  const auto o_sc10 = cv.take<int64_t>(stride * L);
-  const auto o_meta = cv.take<uint32_t>(stride);
-  const auto o_keys = cv.take<unsigned long long>(nG);
-  const auto o_wait = cv.take<unsigned long long>(nP);
-  const auto o_head = cv.take<uint32_t>(nG);
-  const auto o_nwait = cv.take<uint32_t>(nG);
-  const auto o_slot = cv.take<uint32_t>(nG);
-  const auto o_tfirst = cv.take<unsigned long long>(nG);
-  const size_t o_res = cv.mark();                           // results: one D2H
-  const auto o_code = cv.take<uint8_t>(nP);
-  const auto o_node = cv.take<int32_t>(nP);
-  const auto o_fk = cv.take<uint32_t>(nP);
-  const auto o_leader = cv.take<int32_t>(nP);
-  const auto o_lperm = cv.take<uint8_t>(nP);
-  const auto o_rg = cv.take<uint32_t>(cap);
-  const auto o_rp = cv.take<uint32_t>(cap);
-  const auto o_ft = cv.take<unsigned long long>(cap);
-  const auto o_rt = cv.take<unsigned long long>(cap);
-  const auto o_info = cv.take<unsigned long long>(64);
-  HIPCHK(c, c->d_seq.reserve(cv.mark()));
-  uint8_t* base = c->d_seq.as<uint8_t>();
-  GroupsDev gr = groups_dev(c);
-  SeqDev sq{};
-  sq.nreq = c->d_nreq.as<int64_t>();
-  sq.rpres = c->d_rpres.as<uint32_t>();
-  sq.g_matched = const_cast<uint32_t*>(gr.matched);
-  sq.g_sc = const_cast<uint32_t*>(gr.status_scheduled);
-  sq.g_flags = const_cast<uint8_t*>(gr.flags);
-  sq.g_cls = const_cast<uint32_t*>(gr.cls);
-  sq.g_minres = const_cast<int64_t*>(gr.minres);
-  sq.g_mrpres = const_cast<uint32_t*>(gr.mrpres);
-  sq.g_occ = const_cast<uint64_t*>(gr.occupied);
-  sq.left07 = o_sc07.in(base);
-  sq.left10 = o_sc10.in(base);
-  sq.nmeta = o_meta.in(base);
-  sq.keys = o_keys.in(base);
-  sq.wait_rec = o_wait.in(base);
-  sq.head = o_head.in(base);
-  sq.nwait = o_nwait.in(base);
-  sq.slot_of = o_slot.in(base);
-  sq.t_first = o_tfirst.in(base);
-  sq.pclass = pclass_dev(c);
-  sq.pf_code = o_code.in(base);
-  sq.pod_node = o_node.in(base);
-  sq.pf_first_k = o_fk.in(base);
-  sq.pf_leader = o_leader.in(base);
-  sq.last_permitted = o_lperm.in(base);
-  sq.released_group = o_rg.in(base);
-  sq.released_pods = o_rp.in(base);
-  sq.first_tick = o_ft.in(base);
-  sq.ready_tick = o_rt.in(base);
-  sq.cap = out->cap;
-  sq.info = o_info.in(base);
-  SeqParams prm{};
-  prm.S = c->S;
-  prm.eph_gate = c->cfg.eph_gate;
-  prm.run_filter = (stages & BS_STAGE_FILTER) ? 1u : 0u;
-  prm.filter_deny = (stages & BS_BATCH_FILTER_DENY) ? 1u : 0u;
-  prm.C = C;
-  prm.sop_leader0 = c->sop_leader0;
-  prm.keys_in_lds = G <= kSeqKeysLds ? 1u : 0u;
-  prm.prune = cdiv(N, 64) <= kSeqPruneTiles ? 1u : 0u;
-  size_t lds = prm.keys_in_lds ? align256((size_t)nG * 8) : 0;
-  {
-    // table summaries: as many slots as the CU's LDS holds behind the static arrays and the key window (one thread per tile: <= 1024 tiles)
-    const size_t T = cdiv(N, 64), per_slot = T * ((size_t)L * 24 + 8), query = 0;
-    const size_t budget = (size_t)160 * 1024 - sizeof(SeqShared) - 2048;
-    uint32_t K = 0;
-    if (T && T <= (size_t)kSeqPruneTiles && budget > lds + query + per_slot) K = (uint32_t)std::min<size_t>(kSeqCacheSlots, (budget - lds - query) / per_slot);
-    if (const char* e = std::getenv("BS_SEQ_CACHE_SLOTS")) K = std::min<uint32_t>(K, (uint32_t)std::max(0, std::atoi(e)));   // tests: 0 = the round scan, 1 = thrash one slot
-    prm.cache_slots = K;
-    prm.cache_off = (uint32_t)lds;
-    if (K) lds += align256(K * per_slot + query + 64);
-  }
-  // first-fit cursors per request class (bs_seq.hpp, seq_pick): BS_SEQ_NO_CURSOR=1 = every search starts at the head of the list
-  prm.use_cursor = (P && sq.pclass && !(std::getenv("BS_SEQ_NO_CURSOR") && std::atoi(std::getenv("BS_SEQ_NO_CURSOR")))) ? 1u : 0u;
-  HIPCHK(c, hipMemsetAsync(o_info.in(base), 0, o_info.bytes(), c->stream));
-  const PodsDev pd = pods_dev(c);
-  const NodesDev nd = nodes_dev(c);
-  launch_seq(c->stream, c->S, lds, pd, gr, nd, sq, prm);
-  LAUNCHCHK(c, BS_KERNEL_QUERY);
-  // ---- results: one copy of the whole result block, then the caller's arrays
-  std::vector<uint8_t> res(cv.mark() - o_res);
-  HIPCHK(c, hipMemcpyAsync(res.data(), base + o_res, res.size(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint8_t* rb = res.data() - o_res;
-  const unsigned long long* info = o_info.in(rb);
-  int khz = 0;
-  if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->cfg.device) != hipSuccess || khz <= 0) khz = 100000;   // 100 MHz
-  auto to_ns = [&](unsigned long long ticks) { return (int64_t)((long double)ticks * 1.0e6L / (long double)khz); };
-  out->n_released = (uint32_t)info[0];
-  out->total_ns = to_ns(info[1]);
-  out->node_picks = info[2];
-  out->node_scans = info[3];
-  out->scan_rounds = info[5];
-  out->pick_rounds = info[6];
-  out->leader_folds = info[7] & ((1ull << 40) - 1ull);
-  out->table_builds = info[7] >> 40;
-  if (const char* e = std::getenv("BS_SEQ_PROBE_PRINT")) {   // probe build: cycles per phase (see bs_seq.hpp)
-    if (std::atoi(e)) std::fprintf(stderr, "seq probe cycles: control %llu capture %llu fold %llu scan %llu pick %llu permit %llu top-barrier %llu\n", info[8], info[9],
-                                   info[10], info[11], info[12], info[13], info[14]);
-    if (std::atoi(e)) std::fprintf(stderr, "  scan rounds (thread 0): issue-next-loads %llu select %llu wave-scans %llu lds-writes %llu barrier %llu fk-check %llu offsets+compare %llu tail %llu\n",
-                                   info[16], info[17], info[18], info[19], info[20], info[21], info[22], info[23]);
-    if (std::atoi(e)) {                                      // the finer split of thread 0's time (BS_SEQ_P in bs_seq.hpp)
-      static const char* nm[17] = {"top-barrier", "group-loads", "control", "scan:drain", "scan:slot", "scan:candidates", "scan:tiles", "scan:barrier+min", "scan:tail",
-                                   "pick:request", "pick:drain", "pick:tiles", "pick:barrier+min", "pick:assume", "summaries", "result-stores", "permit"};
-      std::fprintf(stderr, "  thread 0, cycles:");
-      for (int k2 = 0; k2 < 17; ++k2) std::fprintf(stderr, " %s %llu |", nm[k2], info[32 + k2]);
-      std::fprintf(stderr, "\n");
-    }
-  }
-  if (P) {
-    if (out->pf_code) std::memcpy(out->pf_code, o_code.in(rb), P);
-    if (out->pod_node) std::memcpy(out->pod_node, o_node.in(rb), (size_t)P * 4);
-    if (out->pf_first_k) std::memcpy(out->pf_first_k, o_fk.in(rb), (size_t)P * 4);
-    if (out->pf_leader) std::memcpy(out->pf_leader, o_leader.in(rb), (size_t)P * 4);
-    if (out->last_permitted) { if (prm.filter_deny) std::memcpy(out->last_permitted, o_lperm.in(rb), P); else std::memset(out->last_permitted, 0, P); }
-    c->sop_leader0 = (int32_t)(uint32_t)info[4] - 1;         // sop.maxFinishedPG as the pass left it
-  }
-  const uint32_t k = std::min(out->n_released, out->cap);
-  if (k) {
-    if (out->released_group) std::memcpy(out->released_group, o_rg.in(rb), (size_t)k * 4);
-    if (out->released_pods) std::memcpy(out->released_pods, o_rp.in(rb), (size_t)k * 4);
-    const unsigned long long* ft = o_ft.in(rb);
-    const unsigned long long* rt = o_rt.in(rb);
-    for (uint32_t i = 0; i < k; ++i) {
-      if (out->first_ns) out->first_ns[i] = to_ns(ft[i]);
-      if (out->ready_ns) out->ready_ns[i] = to_ns(rt[i]);
-    }
-  }
-  // ---- the host mirrors and everything derived from the state the pass rewrote
-  if (N && P) {
-    HIPCHK(c, hipMemcpy2D(c->h_nreq.data(), (size_t)N * 8, c->d_nreq.p, (size_t)c->Ncap * 8, (size_t)N * 8, L, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(c->h_rpres.data(), c->d_rpres.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    hipLaunchKernelGGL(k_nodes_derive, dim3(1), dim3(kScanBlock), 0, c->stream, nd, c->d_kmap.as<uint32_t>(), c->d_m.as<uint32_t>(), c->d_left4.as<int64_t>(),
-                       c->d_lglob.as<int64_t>(), 0u, 0u);   // left4 / cluster bounds follow the requests (flags, hence kmap, are unchanged)
-    LAUNCHCHK(c, BS_KERNEL_PREPASS);
-  }
-  c->bitmap_valid = false;
-  if (G && P) {
-    const BatchDev b = batch_dev(c);
-    std::vector<uint32_t> cls(G);
-    HIPCHK(c, hipMemcpy(c->h_gflags.data(), gr.flags, G, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(cls.data(), gr.cls, (size_t)G * 4, hipMemcpyDeviceToHost));
-    (void)b;
-    c->n_uncaptured = 0;
-    c->n_nominres = 0;
-    c->max_group_cls = 0;
-    for (uint32_t i = 0; i < G; ++i) {
-      if (!(c->h_gflags[i] & BS_GROUP_HAS_POD)) c->n_uncaptured++;
-      else c->max_group_cls = std::max(c->max_group_cls, cls[i]);
-      if (!(c->h_gflags[i] & BS_GROUP_HAS_MINRES)) c->n_nominres++;
-    }
-    if ((rc = analyse_groups(c))) return rc;
-    if ((rc = maybe_analyse_epochs(c))) return rc;
-  }
-  c->seq_o_wait = o_wait;                                  // (the pieces: seq_expire_dev addresses them in d_seq)
-  c->seq_o_head = o_head;
-  c->seq_o_nwait = o_nwait;
-  c->seq_wait_valid = true;
-  return BS_OK;
-}
-
-// -------------------------------------------------------------------------------------------------
-// the Permit timeout (bs_seq_expire.hpp): the waiting gangs of the last pass leave their nodes and their groups on the device
-// -------------------------------------------------------------------------------------------------
-static int seq_wait_state(bs_ctx* c, const char* who) {
-  if (c->nranks > 1 || c->reduce_external) { c->last_error = std::string(who) + " is single-rank only (as bs_seq_run)"; return BS_ERR_STATE; }
-  if (!c->seq_wait_valid || !c->have_nodes || !c->have_groups || !c->have_pods) {
-    c->last_error = std::string(who) + ": no valid waiting state (needs a successful bs_seq_run with no queue / node-list / group load or renumbering since)";
-    return BS_ERR_STATE;
-  }
-  return BS_OK;
-}
-
-static SeqExpireDev seq_expire_dev(bs_ctx* c) {
-  SeqExpireDev a{};
-  const GroupsDev gr = groups_dev(c);
-  a.wait_rec = c->seq_o_wait.in(c->d_seq.p);
-  a.head = c->seq_o_head.in(c->d_seq.p);
-  a.nwait = c->seq_o_nwait.in(c->d_seq.p);
-  a.P = c->P;
-  a.G = c->G;
-  a.g_matched = const_cast<uint32_t*>(gr.matched);
-  a.g_flags = const_cast<uint8_t*>(gr.flags);
-  a.N = c->N;
-  return a;
-}
-
-int bs_seq_expire(bs_ctx* c, uint32_t count, const uint32_t* group, uint32_t flags, bs_seq_expire_out* out) {
-  if (!c || !out) return BS_ERR_INVALID;
-  if ((out->group_cap && (!out->group || !out->group_pods || !out->group_earlier)) || (out->pod_cap && (!out->pod || !out->node))) {
-    c->last_error = "bs_seq_expire: a result array is NULL with a capacity above 0";
-    return BS_ERR_INVALID;
-  }
-  int rc = seq_wait_state(c, "bs_seq_expire");
-  if (rc) return rc;
-  if (const int bad = seq_expire_list_check(c->G, count, group, flags)) { c->last_error = seq_expire_list_text(bad); return BS_ERR_INVALID; }
-  if ((rc = use_device(c))) return rc;
-  if ((rc = settle_pending(c))) return rc;
-  out->n_groups = out->n_pods = 0;
-  const bool all = (flags & BS_SEQ_EXPIRE_ALL) != 0, deny = (flags & BS_SEQ_EXPIRE_DENY) != 0;
-  const uint32_t P = c->P, G = c->G, N = c->N, L = c->L;
-  const uint32_t M = all ? G : count;
-  if (!M) return BS_OK;
-  const uint32_t rec_cap = std::min(N, P), nblk = cdiv(M, kSeBlock);
-  // ---- the per-node scratch: zero between calls
-  Carve nv;
-  const size_t nN = std::max<uint32_t>(N, 1);
-  const auto o_delta = nv.take<unsigned long long>(nN * L);
-  const auto o_nbits = nv.take<uint32_t>(nN);
-  const auto o_dirty = nv.take<uint32_t>(nN);
-  {
-    const void* was = c->d_sexp_nodes.p;
-    HIPCHK(c, c->d_sexp_nodes.reserve(nv.mark()));
-    if (!c->sexp_clean || was != c->d_sexp_nodes.p || c->sexp_n != N || c->sexp_l != L) {
-      HIPCHK(c, hipMemsetAsync(c->d_sexp_nodes.p, 0, nv.mark(), c->stream));
-      c->sexp_n = N;
-      c->sexp_l = L;
-    }
-    c->sexp_clean = false;                                   // until this call's k_se_nodes is known to have run
-  }
-  Carve cv;
-  const auto o_info = cv.take<uint32_t>(4);
-  const auto o_list = cv.take<uint32_t>(M);
-  const auto o_bsum = cv.take<unsigned long long>(nblk);
-  const auto o_group = cv.take<uint32_t>(M);
-  const auto o_gpods = cv.take<uint32_t>(M);
-  const auto o_gearl = cv.take<uint32_t>(M);
-  const auto o_off = cv.take<uint32_t>(M);
-  const auto o_pod = cv.take<uint32_t>(std::max<uint32_t>(P, 1));
-  const auto o_node = cv.take<uint32_t>(std::max<uint32_t>(P, 1));
-  const auto o_dlist = cv.take<uint32_t>(std::max<uint32_t>(rec_cap, 1));
-  const auto o_rec = cv.take<bs_node_request>(std::max<uint32_t>(rec_cap, 1));
-  HIPCHK(c, c->d_sexp.reserve(cv.mark()));
-  void* base = c->d_sexp.p;
-  void* nb = c->d_sexp_nodes.p;
-  SeqExpireDev a = seq_expire_dev(c);
-  a.M = M;
-  a.deny = deny ? 1u : 0u;
-  a.list = all ? nullptr : o_list.in(base);
-  a.bsum = o_bsum.in(base);
-  a.info = o_info.in(base);
-  a.o_group = o_group.in(base);
-  a.o_gpods = o_gpods.in(base);
-  a.o_gearlier = o_gearl.in(base);
-  a.o_off = o_off.in(base);
-  a.o_pod = o_pod.in(base);
-  a.o_node = o_node.in(base);
-  a.dlist = o_dlist.in(base);
-  a.delta = o_delta.in(nb);
-  a.nbits = o_nbits.in(nb);
-  a.dirty = o_dirty.in(nb);
-  bs_node_request* recs = o_rec.in(base);
-  HIPCHK(c, hipMemsetAsync(o_info.in(base), 0, o_info.bytes(), c->stream));
-  if (!all) HIPCHK(c, hipMemcpyAsync(o_list.in(base), group, o_list.bytes(), hipMemcpyHostToDevice, c->stream));
-  c->first_reach_hint = 0xFFFFFFFFu;                        // (as bs_groups_apply: deny entries decide which pod reaches findMaxPG first)
-  launch_seq_expire(c->stream, c->S, a, pods_dev(c), nodes_dev(c), recs, rec_cap);
-  LAUNCHCHK(c, BS_KERNEL_PREPASS);
-  uint32_t info[4] = {0, 0, 0, 0};
-  HIPCHK(c, hipMemcpyAsync(info, o_info.in(base), o_info.bytes(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint32_t ng = info[0], np = info[1], nrec = info[2];
-  if (ng > M || np > P || nrec > rec_cap) { c->last_error = "bs_seq_expire: the waiting chains name more than the queue holds"; return BS_ERR_HIP; }
-  c->sexp_clean = true;
-  // ---- the node requests: k_nodes_assume over the records, the host mirror from their copy (as BS_PREEMPT_APPLY and bs_bound_apply_ex)
-  std::vector<uint8_t> hr((size_t)nrec * sizeof(bs_node_request));
-  std::vector<uint32_t> hg;
-  if (nrec) {
-    launch_nodes_assume(c, recs, nrec);
-    LAUNCHCHK(c, BS_KERNEL_PREPASS);
-    HIPCHK(c, hipMemcpyAsync(hr.data(), recs, hr.size(), hipMemcpyDeviceToHost, c->stream));
-    c->bitmap_valid = false;
-  }
-  const uint32_t kg = std::min(ng, out->group_cap), kp = std::min(np, out->pod_cap);
-  if (kg) {
-    HIPCHK(c, hipMemcpyAsync(out->group, o_group.in(base), (size_t)kg * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->group_pods, o_gpods.in(base), (size_t)kg * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->group_earlier, o_gearl.in(base), (size_t)kg * 4, hipMemcpyDeviceToHost, c->stream));
-  }
-  if (kp) {
-    HIPCHK(c, hipMemcpyAsync(out->pod, o_pod.in(base), (size_t)kp * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->node, o_node.in(base), (size_t)kp * 4, hipMemcpyDeviceToHost, c->stream));
-  }
-  if (deny && all && ng) {
-    hg.resize(ng);
-    HIPCHK(c, hipMemcpyAsync(hg.data(), o_group.in(base), (size_t)ng * 4, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  mirror_node_requests(c, reinterpret_cast<const bs_node_request*>(hr.data()), nrec);
-  if (deny) {
-    const uint32_t* gl = all ? hg.data() : group;
-    for (uint32_t i = 0; i < ng; ++i) c->h_gflags[gl[i]] |= (uint8_t)BS_GROUP_DENIED;
-  }
-  out->n_groups = ng;
-  out->n_pods = np;
-  // findMaxPG, the steady table and the epoch analysis follow the group words as after a bs_groups_apply of these values
-  if (ng) {
-    if ((rc = analyse_groups(c, false))) return rc;
-    if ((rc = maybe_analyse_epochs(c))) return rc;
-  }
-  return BS_OK;
-}
-
-int bs_seq_waiting_read(bs_ctx* c, uint32_t p, int32_t* wait_node) {
-  if (!c || (p && !wait_node)) return BS_ERR_INVALID;
-  int rc = seq_wait_state(c, "bs_seq_waiting_read");
-  if (rc) return rc;
-  if (p != c->P) { c->last_error = "bs_seq_waiting_read: p differs from the queue length"; return BS_ERR_INVALID; }
-  if ((rc = use_device(c))) return rc;
-  if (!p) return BS_OK;
-  Carve cv;
-  const auto o_wn = cv.take<int32_t>(p);
-  HIPCHK(c, c->d_sexp.reserve(cv.mark()));
-  int32_t* wn = o_wn.in(c->d_sexp.p);
-  HIPCHK(c, hipMemsetAsync(wn, 0xFF, o_wn.bytes(), c->stream));
-  launch_seq_waiting(c->stream, seq_expire_dev(c), wn);
-  LAUNCHCHK(c, BS_KERNEL_PREPASS);
-  HIPCHK(c, hipMemcpyAsync(wait_node, wn, o_wn.bytes(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return BS_OK;
-}
-
 // -------------------------------------------------------------------------------------------------
 // flat-argument forms (cgo: no Go-allocated struct of Go pointers crosses by pointer): the structs are built HERE, on the C stack
 // -------------------------------------------------------------------------------------------------
@@ -3721,32 +3031,6 @@ int bs_batch_read_flat(bs_ctx* c, uint8_t* pf_code, uint32_t* pf_first_k, int32_
   o.group_admit = group_admit; o.group_ready = group_ready; o.fl_slot = fl_slot; o.fl_rows = fl_rows; o.fl_rows_feasible = fl_rows_feasible;
   o.fl_rows_cap = fl_rows_cap; o.fl_rows_n = fl_rows_n;
   return bs_batch_read(c, &o);
-}
-int bs_seq_run_flat(bs_ctx* c, uint32_t stages, uint8_t* pf_code, uint32_t* pf_first_k, int32_t* pf_leader, int32_t* pod_node, uint32_t cap,
-                    uint32_t* released_group, uint32_t* released_pods, int64_t* first_ns, int64_t* ready_ns, int64_t* scalars_out,
-                    uint8_t* last_permitted) {
-  bs_seq_out o{};
-  o.last_permitted = last_permitted;
-  o.pf_code = pf_code; o.pf_first_k = pf_first_k; o.pf_leader = pf_leader; o.pod_node = pod_node; o.cap = cap; o.released_group = released_group;
-  o.released_pods = released_pods; o.first_ns = first_ns; o.ready_ns = ready_ns;
-  const int rc = bs_seq_run(c, stages, &o);
-  if (scalars_out) {
-    scalars_out[0] = o.n_released; scalars_out[1] = o.total_ns; scalars_out[2] = (int64_t)o.node_picks; scalars_out[3] = (int64_t)o.node_scans;
-    scalars_out[4] = (int64_t)o.scan_rounds; scalars_out[5] = (int64_t)o.pick_rounds; scalars_out[6] = (int64_t)o.leader_folds;
-    scalars_out[7] = (int64_t)o.table_builds;
-  }
-  return rc;
-}
-int bs_seq_expire_flat(bs_ctx* c, uint32_t count, const uint32_t* group, uint32_t flags, uint32_t group_cap, uint32_t* group_out, uint32_t* group_pods,
-                       uint32_t* group_earlier, uint32_t pod_cap, uint32_t* pod, uint32_t* node, uint32_t* counts_out) {
-  if (!counts_out) return BS_ERR_INVALID;
-  bs_seq_expire_out o{};
-  o.group_cap = group_cap; o.group = group_out; o.group_pods = group_pods; o.group_earlier = group_earlier;
-  o.pod_cap = pod_cap; o.pod = pod; o.node = node;
-  const int rc = bs_seq_expire(c, count, group, flags, &o);
-  counts_out[0] = o.n_groups;
-  counts_out[1] = o.n_pods;
-  return rc;
 }
 
 int bs_fit_build_flat(bs_ctx* c, uint32_t n, const uint32_t* name, const uint32_t* label_off, const uint32_t* label_key, const uint32_t* label_val,
@@ -3901,983 +3185,6 @@ int bs_batch_stats_get(bs_ctx* c, bs_batch_stats* out) {
   }
   c->collect_stats = 0;
   return BS_OK;
-}
-
-
-// -------------------------------------------------------------------------------------------------
-// gang-aware preemption (bs_preempt.hpp): the resident bound-pod table and the batched victim search
-// -------------------------------------------------------------------------------------------------
-// (the bound table's one allocation: BoundLayout / bound_layout, bs_bound_nodes.hpp — k_bn_move lays the new table out with the same function)
-
-int bs_bound_load(bs_ctx* c, const bs_bound_soa* bd) {
-  if (!c || !bd) return BS_ERR_INVALID;
-  if (!c->have_nodes) { c->last_error = "bs_bound_load before bs_nodes_load"; return BS_ERR_STATE; }
-  const uint32_t B = bd->b, N = c->N, L = c->L;
-  if (B > BS_BOUND_MAX) { c->last_error = "bound table larger than BS_BOUND_MAX"; return BS_ERR_CAPACITY; }
-  if (B && (!bd->node || !bd->priority || !bd->start_ns || !bd->group || !bd->req || !bd->req_present)) return BS_ERR_INVALID;
-  std::vector<uint32_t> cnt((size_t)N + 1, 0);
-  int32_t gmax = -1;
-  for (uint32_t i = 0; i < B; ++i) {
-    if (bd->node[i] >= N) { c->last_error = "bound pod on a node index >= n"; return BS_ERR_INVALID; }
-    if (bd->group[i] < BS_POD_GROUP_MISSING) { c->last_error = "bound pod group index below BS_POD_GROUP_MISSING"; return BS_ERR_INVALID; }
-    gmax = std::max(gmax, bd->group[i]);
-    ++cnt[bd->node[i] + 1];
-  }
-  for (uint32_t k = 0; k < N; ++k) {
-    if (cnt[k + 1] > BS_BOUND_MAX_PER_NODE) { c->last_error = "more than BS_BOUND_MAX_PER_NODE bound pods on one node"; return BS_ERR_CAPACITY; }
-    cnt[k + 1] += cnt[k];
-  }
-  int rc = use_device(c);
-  if (rc) return rc;
-  // every node's pods in importance order: priority descending, start ascending, caller id ascending
-  std::vector<uint32_t> order(B), fill(cnt.begin(), cnt.end() - 1);
-  for (uint32_t i = 0; i < B; ++i) order[fill[bd->node[i]]++] = i;
-  for (uint32_t k = 0; k < N; ++k)
-    std::sort(order.begin() + cnt[k], order.begin() + cnt[k + 1], [&](uint32_t a, uint32_t b) {
-      if (bd->priority[a] != bd->priority[b]) return bd->priority[a] > bd->priority[b];
-      if (bd->start_ns[a] != bd->start_ns[b]) return bd->start_ns[a] < bd->start_ns[b];
-      return a < b;
-    });
-  const size_t nB = std::max<uint32_t>(B, 1);
-  BoundLayout lay;
-  const size_t o = bound_layout(L, N, B, lay);
-  c->blay = lay;
-  std::vector<uint8_t> h(o, 0);
-  const auto ht = bound_cols(h.data(), lay);
-  std::memcpy(ht.boff, cnt.data(), ((size_t)N + 1) * 4);
-  const uint32_t smask = (uint32_t)((1ull << (L - BS_FIXED_LANES)) - 1ull);
-  for (uint32_t r = 0; r < B; ++r) {
-    const uint32_t i = order[r];
-    ht.pres[r] = bd->req_present[i] & smask;
-    ht.prio[r] = bd->priority[i];
-    ht.start[r] = bd->start_ns[i];
-    ht.group[r] = bd->group[i];
-    ht.id[r] = i;
-    for (uint32_t l = 0; l < L; ++l) {
-      int64_t v = bd->req[(size_t)l * B + i];
-      if (l == BS_LANE_PODS) v = 1;                                        // RemovePod: one pod less
-      else if (l >= BS_FIXED_LANES && !((bd->req_present[i] >> (l - BS_FIXED_LANES)) & 1u)) v = 0;   // no key: nothing to subtract
-      ht.req[(size_t)l * nB + r] = v;
-    }
-  }
-  c->have_bound = false;
-  HIPCHK(c, c->d_bound.reserve(o));
-  HIPCHK(c, hipMemcpyAsync(c->d_bound.p, h.data(), o, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));             // (h is a local buffer)
-  c->bound_b = B;
-  c->bound_ids = B;
-  c->bound_n = N;
-  c->bound_max_group = gmax;
-  c->have_bound = true;                                   // (h was zeroed: every PDB bit is clear)
-  c->have_pdb = false;                                    // the id space restarts: the resident PDB state names the old one
-  c->pdb_n = c->pdb_covered = c->pdb_members = 0;
-  return BS_OK;
-}
-
-int bs_bound_pdb_set(bs_ctx* c, uint32_t b, const uint8_t* violating) {
-  if (!c) return BS_ERR_INVALID;
-  if (!c->have_bound) { c->last_error = "bs_bound_pdb_set before bs_bound_load"; return BS_ERR_STATE; }
-  if (b != c->bound_ids) { c->last_error = "bs_bound_pdb_set: b differs from the last bs_bound_load's entry count"; return BS_ERR_INVALID; }
-  const uint32_t B = c->bound_b, N = c->bound_n;
-  int rc = use_device(c);
-  if (rc) return rc;
-  const auto bt = bound_cols(c->d_bound.as<uint8_t>(), c->blay);
-  const size_t nB = std::max<uint32_t>(B, 1), nN = std::max<uint32_t>(N, 1);
-  // the two columns are rebuilt on the host through the id column (the id -> position map; evicted ids are not in it) and copied in
-  // stream order, behind whatever preemption call is still running
-  std::vector<uint8_t> bits(nB, 0);
-  std::vector<uint32_t> nviol(nN, 0);
-  if (violating && B) {
-    std::vector<uint32_t> boff((size_t)N + 1), id(B);
-    HIPCHK(c, hipMemcpyAsync(boff.data(), bt.boff, ((size_t)N + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(id.data(), bt.id, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (uint32_t k = 0; k < N; ++k)
-      for (uint32_t j = boff[k]; j < boff[k + 1] && j < B; ++j) {
-        bits[j] = id[j] < b && violating[id[j]] ? 1 : 0;
-        nviol[k] += bits[j];
-      }
-  }
-  HIPCHK(c, hipMemcpyAsync(bt.pdb, bits.data(), nB, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(bt.nviol, nviol.data(), nN * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));             // (local buffers)
-  return BS_OK;
-}
-
-// -------------------------------------------------------------------------------------------------
-// resident PodDisruptionBudgets (bs_pdb.hpp): the PDB bits follow the budgets' status on the device
-// -------------------------------------------------------------------------------------------------
-namespace {
-
-// what every bs_pdb_* call refuses before it looks at its arguments
-int pdb_state(bs_ctx* c, const char* who, bool need_pdb) {
-  if (!c->have_bound) { c->last_error = std::string(who) + " before bs_bound_load"; return BS_ERR_STATE; }
-  if (c->nranks > 1 || c->reduce_external) { c->last_error = std::string(who) + " is single-rank only"; return BS_ERR_STATE; }
-  if (need_pdb && !c->have_pdb) { c->last_error = std::string(who) + " without a bs_pdb_load since the last bs_bound_load"; return BS_ERR_STATE; }
-  return BS_OK;
-}
-
-// member_off[n + 1] ascending from 0, every member < n_pdb, and the total within BS_PDB_MEMBERS_MAX on top of `have`
-int pdb_csr_check(bs_ctx* c, const char* who, uint32_t n, const uint32_t* member_off, const uint32_t* member, uint32_t n_pdb, uint32_t have) {
-  if (n && !member_off) return BS_ERR_INVALID;
-  const uint32_t total = n ? member_off[n] : 0u;
-  if (n && member_off[0] != 0u) { c->last_error = std::string(who) + ": member_off does not start at 0"; return BS_ERR_INVALID; }
-  for (uint32_t i = 0; i < n; ++i)
-    if (member_off[i + 1] < member_off[i]) { c->last_error = std::string(who) + ": member_off is not ascending"; return BS_ERR_INVALID; }
-  if ((uint64_t)have + total > BS_PDB_MEMBERS_MAX) { c->last_error = std::string(who) + ": more than BS_PDB_MEMBERS_MAX membership entries"; return BS_ERR_CAPACITY; }
-  if (total && !member) return BS_ERR_INVALID;
-  for (uint32_t x = 0; x < total; ++x)
-    if (member[x] >= n_pdb) { c->last_error = std::string(who) + ": a member index >= n_pdb"; return BS_ERR_INVALID; }
-  return BS_OK;
-}
-
-// the recompute behind whatever the caller enqueued (count staged pairs go into allowed[] first); waits for it
-int pdb_recompute(bs_ctx* c, uint32_t count, const uint32_t* index, const int32_t* value) {
-  PdbDev a{};
-  const auto bt = bound_cols(c->d_bound.as<uint8_t>(), c->blay);
-  a.boff = bt.boff; a.bid = bt.id; a.bpdb = bt.pdb; a.bnviol = bt.nviol;
-  a.n = c->bound_n;
-  a.moff = c->d_pdb_moff.as<uint32_t>();
-  a.member = c->d_pdb_member.as<uint32_t>();
-  a.allowed = c->d_pdb_allowed.as<int32_t>();
-  a.covered = c->pdb_covered;
-  a.index = index;
-  a.value = value;
-  a.count = count;
-  launch_pdb(c->stream, a);
-  LAUNCHCHK(c, BS_KERNEL_PREPASS);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return BS_OK;
-}
-
-// room for `bytes` in a buffer whose first `keep` bytes stay: a buffer that has to grow gets a quarter of headroom (a run of appends
-// allocates rarely, as the bound table does)
-int pdb_grow(bs_ctx* c, DevBuf& buf, size_t bytes, size_t keep) {
-  if (bytes <= buf.cap) return BS_OK;
-  DevBuf nw;
-  HIPCHK(c, nw.reserve(bytes + bytes / 4));
-  if (keep) HIPCHK(c, hipMemcpyAsync(nw.p, buf.p, keep, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::swap(buf.p, nw.p);
-  std::swap(buf.cap, nw.cap);
-  return BS_OK;                                            // (nw frees the old allocation)
-}
-
-}  // namespace
-
-int bs_pdb_load(bs_ctx* c, uint32_t n_pdb, const int32_t* allowed, uint32_t b, const uint32_t* member_off, const uint32_t* member) {
-  if (!c) return BS_ERR_INVALID;
-  int rc = pdb_state(c, "bs_pdb_load", false);
-  if (rc) return rc;
-  if (n_pdb > BS_PDB_MAX) { c->last_error = "bs_pdb_load: more than BS_PDB_MAX PDBs"; return BS_ERR_CAPACITY; }
-  if (b != c->bound_ids) { c->last_error = "bs_pdb_load: b differs from bs_bound_ids"; return BS_ERR_INVALID; }
-  if (n_pdb && !allowed) return BS_ERR_INVALID;
-  if ((rc = pdb_csr_check(c, "bs_pdb_load", b, member_off, member, n_pdb, 0u))) return rc;
-  if ((rc = use_device(c))) return rc;
-  const uint32_t total = b ? member_off[b] : 0u, zero = 0;
-  c->have_pdb = false;
-  HIPCHK(c, c->d_pdb_allowed.reserve((size_t)std::max<uint32_t>(n_pdb, 1) * 4));
-  HIPCHK(c, c->d_pdb_moff.reserve(((size_t)b + 1) * 4));
-  HIPCHK(c, c->d_pdb_member.reserve((size_t)std::max<uint32_t>(total, 1) * 4));
-  if (n_pdb) HIPCHK(c, hipMemcpyAsync(c->d_pdb_allowed.p, allowed, (size_t)n_pdb * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->d_pdb_moff.p, b ? member_off : &zero, ((size_t)b + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  if (total) HIPCHK(c, hipMemcpyAsync(c->d_pdb_member.p, member, (size_t)total * 4, hipMemcpyHostToDevice, c->stream));
-  c->pdb_n = n_pdb;
-  c->pdb_covered = b;
-  c->pdb_members = total;
-  if ((rc = pdb_recompute(c, 0u, nullptr, nullptr))) return rc;   // (waits: the caller's arrays and `zero` are free again)
-  c->have_pdb = true;
-  return BS_OK;
-}
-
-int bs_pdb_members_append(bs_ctx* c, uint32_t first_id, uint32_t n, const uint32_t* member_off, const uint32_t* member) {
-  if (!c) return BS_ERR_INVALID;
-  int rc = pdb_state(c, "bs_pdb_members_append", true);
-  if (rc) return rc;
-  if (first_id != c->pdb_covered) { c->last_error = "bs_pdb_members_append: first_id differs from the number of ids covered so far"; return BS_ERR_INVALID; }
-  if ((uint64_t)first_id + n > c->bound_ids) { c->last_error = "bs_pdb_members_append: first_id + n passes bs_bound_ids"; return BS_ERR_INVALID; }
-  if ((rc = pdb_csr_check(c, "bs_pdb_members_append", n, member_off, member, c->pdb_n, c->pdb_members))) return rc;
-  if ((rc = use_device(c))) return rc;
-  const uint32_t total = n ? member_off[n] : 0u, have = c->pdb_members, cov = c->pdb_covered;
-  if (n) {
-    if ((rc = pdb_grow(c, c->d_pdb_moff, ((size_t)cov + n + 1) * 4, ((size_t)cov + 1) * 4))) return rc;
-    if ((rc = pdb_grow(c, c->d_pdb_member, ((size_t)have + total) * 4, (size_t)have * 4))) return rc;
-    std::vector<uint32_t> off(n);                          // the run's ends, moved behind the entries the CSR holds
-    for (uint32_t i = 0; i < n; ++i) off[i] = have + member_off[i + 1];
-    HIPCHK(c, hipMemcpyAsync(c->d_pdb_moff.as<uint32_t>() + cov + 1, off.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    if (total) HIPCHK(c, hipMemcpyAsync(c->d_pdb_member.as<uint32_t>() + have, member, (size_t)total * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));            // (off is a local buffer)
-    c->pdb_covered = cov + n;
-    c->pdb_members = have + total;
-  }
-  return pdb_recompute(c, 0u, nullptr, nullptr);
-}
-
-int bs_pdb_allowed_apply(bs_ctx* c, uint32_t count, const uint32_t* index, const int32_t* value) {
-  if (!c) return BS_ERR_INVALID;
-  int rc = pdb_state(c, "bs_pdb_allowed_apply", true);
-  if (rc) return rc;
-  if (count == 0) return BS_OK;
-  if (!index || !value) return BS_ERR_INVALID;
-  if (count > c->pdb_n) { c->last_error = "bs_pdb_allowed_apply: more pairs than PDBs (an index is listed twice or is out of range)"; return BS_ERR_INVALID; }
-  std::vector<uint32_t> seen(index, index + count);
-  std::sort(seen.begin(), seen.end());
-  if (seen.back() >= c->pdb_n) { c->last_error = "bs_pdb_allowed_apply: an index >= n_pdb"; return BS_ERR_INVALID; }
-  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { c->last_error = "bs_pdb_allowed_apply: an index is listed twice"; return BS_ERR_INVALID; }
-  if ((rc = use_device(c))) return rc;
-  const size_t bytes = (size_t)count * 8;
-  HIPCHK(c, c->h_pdbstage.reserve(bytes, std::max<size_t>(bytes + bytes / 4, 4096)));
-  std::memcpy(c->h_pdbstage.p, index, (size_t)count * 4);
-  std::memcpy(c->h_pdbstage.p + (size_t)count * 4, value, (size_t)count * 4);
-  HIPCHK(c, c->h_pdbstage.mark_busy(c->stream));
-  rc = pdb_recompute(c, count, reinterpret_cast<const uint32_t*>(c->h_pdbstage.p), reinterpret_cast<const int32_t*>(c->h_pdbstage.p + (size_t)count * 4));
-  if (rc == BS_OK) c->h_pdbstage.busy = false;             // (the recompute waited for the stream)
-  return rc;
-}
-
-int bs_pdb_read(bs_ctx* c, uint32_t* n_pdb_out, uint32_t* covered_out, int32_t* allowed_out, uint32_t* node_violating_out) {
-  if (!c) return BS_ERR_INVALID;
-  int rc = pdb_state(c, "bs_pdb_read", true);
-  if (rc) return rc;
-  if (node_violating_out && c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
-  if ((rc = use_device(c))) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (n_pdb_out) *n_pdb_out = c->pdb_n;
-  if (covered_out) *covered_out = c->pdb_covered;
-  if (allowed_out && c->pdb_n) HIPCHK(c, hipMemcpy(allowed_out, c->d_pdb_allowed.p, (size_t)c->pdb_n * 4, hipMemcpyDeviceToHost));
-  if (node_violating_out && c->bound_n)
-    HIPCHK(c, hipMemcpy(node_violating_out, bound_cols(c->d_bound.as<const uint8_t>(), c->blay).nviol, (size_t)c->bound_n * 4, hipMemcpyDeviceToHost));
-  return BS_OK;
-}
-
-int bs_preempt_pdb_read(bs_ctx* c, uint32_t count, uint32_t* n_pdb_violations) {
-  if (!c) return BS_ERR_INVALID;
-  if (!c->have_pre_npv) { c->last_error = "bs_preempt_pdb_read before a successful bs_preempt_run / bs_preempt_commit"; return BS_ERR_STATE; }
-  if (count != c->pre_npv.size()) { c->last_error = "bs_preempt_pdb_read: count differs from the last preemption call's"; return BS_ERR_INVALID; }
-  if (count == 0) return BS_OK;
-  if (!n_pdb_violations) return BS_ERR_INVALID;
-  std::memcpy(n_pdb_violations, c->pre_npv.data(), (size_t)count * 4);
-  return BS_OK;
-}
-
-int bs_bound_count(const bs_ctx* c, uint32_t* b_out) {
-  if (!c || !b_out) return BS_ERR_INVALID;
-  *b_out = c->have_bound ? c->bound_b : 0u;
-  return BS_OK;
-}
-
-int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority, const uint8_t* group_protected,
-                   uint32_t victim_cap, const bs_preempt_out* out) {
-  if (!c || !out) return BS_ERR_INVALID;
-  if (stages & ~BS_STAGE_PREFILTER) { c->last_error = "bs_preempt_run takes BS_STAGE_PREFILTER only (the plugin's Filter takes no part)"; return BS_ERR_INVALID; }
-  if (!c->have_nodes || !c->have_fit || !c->have_pods || !c->have_bound) {
-    c->last_error = "bs_preempt_run needs nodes, fit, pods and the bound table loaded";
-    return BS_ERR_STATE;
-  }
-  if (c->nranks > 1 || c->reduce_external) { c->last_error = "bs_preempt_run is single-rank only"; return BS_ERR_STATE; }
-  if (c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
-  if (count > BS_PREEMPT_MAX || (uint64_t)count * victim_cap > (1ull << 28)) return BS_ERR_CAPACITY;
-  if (count == 0) { c->pre_npv.clear(); c->have_pre_npv = true; c->have_gang = false; return BS_OK; }
-  if (!pod_index || !priority || !out->node || !out->n_victims || (victim_cap && !out->victims) || (c->G && !group_protected)) return BS_ERR_INVALID;
-  if (c->bound_max_group >= (int32_t)c->G) { c->last_error = "the bound table names a group index >= the loaded group count"; return BS_ERR_INVALID; }
-  const uint32_t P = c->P, N = c->N, G = c->G;
-  for (uint32_t i = 0; i < count; ++i)
-    if (pod_index[i] >= P) { c->last_error = "preemptor pod index >= p"; return BS_ERR_INVALID; }
-  int rc = use_device(c);
-  if (rc) return rc;
-  // slots in priority-descending order (stable): the tile's highest priority bounds its lanes' victim suffixes
-  std::vector<uint32_t> perm(count);
-  for (uint32_t i = 0; i < count; ++i) perm[i] = i;
-  std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return priority[a] > priority[b]; });
-  const PreemptGeom geom = preempt_geom(N, count, c->test_pc_chunk_nodes);   // slot tiles x node chunks (bs_preempt_geom.hpp)
-  const uint32_t tiles = geom.tiles, nchunks = geom.nchunks, chunk_nodes = geom.chunk_nodes;
-  const size_t nQ = count, nG = std::max<uint32_t>(G, 1), nR = (size_t)nchunks * nQ, nV = std::max<size_t>((size_t)nQ * victim_cap, 1);
-  Carve cv;
-  const auto o_spod = cv.take<uint32_t>(nQ);
-  const auto o_sprio = cv.take<int32_t>(nQ);
-  const auto o_sorig = cv.take<uint32_t>(nQ);
-  const auto o_gprot = cv.take<uint8_t>(nG);
-  const size_t in_bytes = cv.mark();
-  const auto o_rnode = cv.take<int32_t>(nR);
-  const auto o_rnv = cv.take<uint32_t>(nR);
-  const auto o_rnpv = cv.take<uint32_t>(nR);
-  const auto o_rtop = cv.take<int32_t>(nR);
-  const auto o_rsum = cv.take<int64_t>(nR);
-  const auto o_rest = cv.take<int64_t>(nR);
-  const auto o_rncand = cv.take<uint32_t>(nR);
-  const size_t o_res = cv.mark();                           // results: one D2H
-  const auto o_node = cv.take<int32_t>(nQ);
-  const auto o_ncand = cv.take<uint32_t>(nQ);
-  const auto o_nv = cv.take<uint32_t>(nQ);
-  const auto o_npv = cv.take<uint32_t>(nQ);
-  const auto o_top = cv.take<int32_t>(nQ);
-  const auto o_sum = cv.take<int64_t>(nQ);
-  const auto o_est = cv.take<int64_t>(nQ);
-  const auto o_vic = cv.take<uint32_t>(nV);
-  HIPCHK(c, c->d_pre.reserve(cv.mark()));
-  std::vector<uint8_t> in(in_bytes, 0);
-  for (uint32_t s = 0; s < count; ++s) {
-    o_spod.in(in.data())[s] = pod_index[perm[s]];
-    o_sprio.in(in.data())[s] = priority[perm[s]];
-    o_sorig.in(in.data())[s] = perm[s];
-  }
-  if (G) std::memcpy(o_gprot.in(in.data()), group_protected, G);
-  uint8_t* base = c->d_pre.as<uint8_t>();
-  HIPCHK(c, hipMemcpyAsync(base, in.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
-  PreemptDev pe{};
-  const auto bt = bound_dev(pe, c->d_bound.as<const uint8_t>(), c->blay);
-  pe.bnviol = bt.nviol;
-  pe.bstride = std::max<uint32_t>(c->bound_b, 1);
-  pe.q = count;
-  pe.nchunks = nchunks;
-  pe.chunk_nodes = chunk_nodes;
-  pe.cap = victim_cap;
-  pe.spod = o_spod.in(base);
-  pe.sprio = o_sprio.in(base);
-  pe.sorig = o_sorig.in(base);
-  pe.gprot = o_gprot.in(base);
-  pe.r_node = o_rnode.in(base);
-  pe.r_nv = o_rnv.in(base);
-  pe.r_npv = o_rnpv.in(base);
-  pe.r_top = o_rtop.in(base);
-  pe.r_sum = o_rsum.in(base);
-  pe.r_est = o_rest.in(base);
-  pe.r_ncand = o_rncand.in(base);
-  pe.o_node = o_node.in(base);
-  pe.o_ncand = o_ncand.in(base);
-  pe.o_nv = o_nv.in(base);
-  pe.o_npv = o_npv.in(base);
-  pe.o_top = o_top.in(base);
-  pe.o_sum = o_sum.in(base);
-  pe.o_est = o_est.in(base);
-  pe.o_victims = o_vic.in(base);
-  launch_preempt(c->stream, c->S, dim3(tiles, nchunks), nodes_dev(c), pods_dev(c), pe);
-  LAUNCHCHK(c, BS_KERNEL_QUERY);
-  std::vector<uint8_t> res(cv.mark() - o_res);
-  HIPCHK(c, hipMemcpyAsync(res.data(), base + o_res, res.size(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint8_t* rb = res.data() - o_res;
-  std::memcpy(out->node, o_node.in(rb), o_node.bytes());
-  std::memcpy(out->n_victims, o_nv.in(rb), o_nv.bytes());
-  c->pre_npv.assign(o_npv.in(rb), o_npv.in(rb) + nQ);
-  c->have_pre_npv = true;
-  c->have_gang = false;
-  if (out->n_candidates) std::memcpy(out->n_candidates, o_ncand.in(rb), o_ncand.bytes());
-  if (out->top_priority) std::memcpy(out->top_priority, o_top.in(rb), o_top.bytes());
-  if (out->priority_sum) std::memcpy(out->priority_sum, o_sum.in(rb), o_sum.bytes());
-  if (out->earliest_start) std::memcpy(out->earliest_start, o_est.in(rb), o_est.bytes());
-  if (victim_cap) {
-    // rows are written up to min(n_victims, cap); the rest of a row is unspecified: zero it for the caller
-    const uint32_t* nv = o_nv.in(rb);
-    const uint32_t* vic = o_vic.in(rb);
-    for (size_t q = 0; q < nQ; ++q) {
-      const uint32_t k = std::min(nv[q], victim_cap);
-      std::memcpy(out->victims + q * victim_cap, vic + q * victim_cap, (size_t)k * 4);
-      std::memset(out->victims + q * victim_cap + k, 0, (size_t)(victim_cap - k) * 4);
-    }
-  }
-  return BS_OK;
-}
-
-int bs_bound_load_flat(bs_ctx* c, uint32_t b, const uint32_t* node, const int32_t* priority, const int64_t* start_ns, const int32_t* group,
-                       const int64_t* req, const uint32_t* req_present) {
-  const bs_bound_soa bd{b, node, priority, start_ns, group, req, req_present};
-  return bs_bound_load(c, &bd);
-}
-
-int bs_preempt_run_flat(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority, const uint8_t* group_protected,
-                        uint32_t victim_cap, int32_t* node, uint32_t* n_candidates, uint32_t* n_victims, uint32_t* victims, int32_t* top_priority,
-                        int64_t* priority_sum, int64_t* earliest_start) {
-  const bs_preempt_out o{node, n_candidates, n_victims, victims, top_priority, priority_sum, earliest_start};
-  return bs_preempt_run(c, stages, count, pod_index, priority, group_protected, victim_cap, &o);
-}
-
-
-// -------------------------------------------------------------------------------------------------
-// preemption plans answered in sequence (bs_preempt_commit.hpp), applied into the resident state on request
-// -------------------------------------------------------------------------------------------------
-// bs_preempt_commit (gang == false: gang_need is not looked at, k_pc_resolve<S> is launched, the blob holds no gang column) and
-// bs_preempt_commit_gang (gang == true: the run check on the sorted slots, k_gang_resolve<S>).  Validation, blob, scan launch, result
-// copy and the APPLY tail are one code path.
-static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
-                               const uint8_t* group_protected, const uint32_t* gang_need, bool gang, uint32_t flags, uint32_t victim_cap,
-                               const bs_preempt_out* out) {
-  if (!c || !out) return BS_ERR_INVALID;
-  if (stages & ~BS_STAGE_PREFILTER) { c->last_error = "bs_preempt_commit takes BS_STAGE_PREFILTER only (the plugin's Filter takes no part)"; return BS_ERR_INVALID; }
-  if (flags & ~(BS_PREEMPT_APPLY | BS_PREEMPT_ASSUME)) { c->last_error = "bs_preempt_commit: unknown flags"; return BS_ERR_INVALID; }
-  if ((flags & BS_PREEMPT_ASSUME) && !(flags & BS_PREEMPT_APPLY)) { c->last_error = "BS_PREEMPT_ASSUME needs BS_PREEMPT_APPLY"; return BS_ERR_INVALID; }
-  if (!c->have_nodes || !c->have_fit || !c->have_pods || !c->have_bound) {
-    c->last_error = "bs_preempt_commit needs nodes, fit, pods and the bound table loaded";
-    return BS_ERR_STATE;
-  }
-  if (c->nranks > 1 || c->reduce_external) { c->last_error = "bs_preempt_commit is single-rank only"; return BS_ERR_STATE; }
-  if (c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
-  if (count > BS_PREEMPT_MAX || (uint64_t)count * victim_cap > (1ull << 28)) return BS_ERR_CAPACITY;
-  if (gang && c->G && !gang_need) { c->last_error = "bs_preempt_commit_gang: gang_need is NULL with g > 0"; return BS_ERR_INVALID; }
-  if (count == 0) {
-    c->pre_npv.clear();
-    c->have_pre_npv = true;
-    c->have_gang = gang;
-    if (gang) { c->gang_voided.clear(); c->gang_placed.assign(c->G, 0u); }
-    return BS_OK;
-  }
-  if (!pod_index || !priority || !out->node || !out->n_victims || (victim_cap && !out->victims) || (c->G && !group_protected)) return BS_ERR_INVALID;
-  if (c->bound_max_group >= (int32_t)c->G) { c->last_error = "the bound table names a group index >= the loaded group count"; return BS_ERR_INVALID; }
-  const uint32_t P = c->P, N = c->N, G = c->G, L = c->L, B = c->bound_b;
-  for (uint32_t i = 0; i < count; ++i)
-    if (pod_index[i] >= P) { c->last_error = "preemptor pod index >= p"; return BS_ERR_INVALID; }
-  {
-    std::vector<uint32_t> seen(pod_index, pod_index + count);
-    std::sort(seen.begin(), seen.end());
-    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { c->last_error = "bs_preempt_commit: a pod index appears twice (a pod is nominated once)"; return BS_ERR_INVALID; }
-  }
-  const bool apply = (flags & BS_PREEMPT_APPLY) != 0, assume = (flags & BS_PREEMPT_ASSUME) != 0;
-  int rc = use_device(c);
-  if (rc) return rc;
-  std::vector<uint32_t> perm(count);
-  for (uint32_t i = 0; i < count; ++i) perm[i] = i;
-  std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return priority[a] > priority[b]; });
-  // gang: the runs of the sorted slots (bs_preempt_gang_runs.hpp).  The pods' group column lives on the device only (bs_pods_apply patches
-  // it there), so it is read back when some group has a requirement; a second run of one group is refused before anything is launched.
-  std::vector<uint32_t> g_need, g_rlen;
-  std::vector<int32_t> sgroup;
-  if (gang) {
-    bool any = false;
-    for (uint32_t g = 0; g < G; ++g) any |= gang_need[g] != 0;
-    sgroup.assign(count, BS_POD_NOT_GROUPED);
-    if (any) {
-      std::vector<int32_t> pgroup(P);
-      HIPCHK(c, hipMemcpyAsync(pgroup.data(), pods_dev(c).group, (size_t)P * 4, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      for (uint32_t s = 0; s < count; ++s) sgroup[s] = pgroup[pod_index[perm[s]]];
-    }
-    if (gang_runs(count, sgroup.data(), G, gang_need, g_need, g_rlen) >= 0) {
-      c->last_error = "bs_preempt_commit_gang: a group with a requirement forms more than one run of slots";
-      return BS_ERR_INVALID;
-    }
-  }
-  if (apply && (rc = settle_pending(c))) return rc;
-  const PreemptGeom geom = preempt_geom(N, count, c->test_pc_chunk_nodes);   // slot tiles x node chunks (bs_preempt_geom.hpp)
-  const uint32_t tiles = geom.tiles, nchunks = geom.nchunks, chunk_nodes = geom.chunk_nodes;
-  const size_t nQ = count, nG = std::max<uint32_t>(G, 1), nR = (size_t)nchunks * nQ, nV = std::max<size_t>((size_t)nQ * victim_cap, 1);
-  const size_t nN = std::max<uint32_t>(N, 1), nB = std::max<uint32_t>(B, 1);
-  Carve cv;
-  const auto o_spod = cv.take<uint32_t>(nQ);
-  const auto o_sprio = cv.take<int32_t>(nQ);
-  const auto o_sorig = cv.take<uint32_t>(nQ);
-  const auto o_gprot = cv.take<uint8_t>(nG);
-  const size_t gQ = gang ? nQ : 0, gB = gang ? nB : 0;    // gang columns: no bytes in bs_preempt_commit's blob
-  const auto o_gneed = cv.take<uint32_t>(gQ);
-  const auto o_grlen = cv.take<uint32_t>(gQ);
-  const size_t in_bytes = cv.mark();
-  const auto o_rnode = cv.take<int32_t>(nR * kPcK);
-  const auto o_rnv = cv.take<uint32_t>(nR * kPcK);
-  const auto o_rnpv = cv.take<uint32_t>(nR * kPcK);
-  const auto o_rtop = cv.take<int32_t>(nR * kPcK);
-  const auto o_rsum = cv.take<int64_t>(nR * kPcK);
-  const auto o_rest = cv.take<int64_t>(nR * kPcK);
-  const auto o_rncand = cv.take<uint32_t>(nR);
-  const size_t o_work = cv.mark();                          // zeroed working state
-  const auto o_dv = cv.take<int64_t>((size_t)L * nN);
-  const auto o_dn = cv.take<int64_t>((size_t)L * nN);
-  const auto o_vbits = cv.take<uint32_t>(nN);
-  const auto o_nbits = cv.take<uint32_t>(nN);
-  const auto o_dirty = cv.take<uint8_t>(nN);
-  const auto o_dead = cv.take<uint8_t>(nB);
-  const auto o_gtag = cv.take<uint32_t>(gB);
-  const auto o_gplaced = cv.take<uint32_t>(gQ);
-  const auto o_gvoided = cv.take<uint8_t>(gQ);
-  const size_t work_bytes = cv.mark() - o_work;
-  const auto o_gslog = cv.take<uint32_t>(gQ * 3);
-  const auto o_dlist = cv.take<uint32_t>(nQ);
-  const auto o_nreq = cv.take<bs_node_request>(nQ);
-  const size_t o_res = cv.mark();                           // results: one D2H
-  const auto o_info = cv.take<uint32_t>(2);
-  const auto o_node = cv.take<int32_t>(nQ);
-  const auto o_ncand = cv.take<uint32_t>(nQ);
-  const auto o_nv = cv.take<uint32_t>(nQ);
-  const auto o_npv = cv.take<uint32_t>(nQ);
-  const auto o_top = cv.take<int32_t>(nQ);
-  const auto o_sum = cv.take<int64_t>(nQ);
-  const auto o_est = cv.take<int64_t>(nQ);
-  const auto o_vic = cv.take<uint32_t>(nV);
-  HIPCHK(c, c->d_pre.reserve(cv.mark()));
-  std::vector<uint8_t> in(in_bytes, 0);
-  for (uint32_t s = 0; s < count; ++s) {
-    o_spod.in(in.data())[s] = pod_index[perm[s]];
-    o_sprio.in(in.data())[s] = priority[perm[s]];
-    o_sorig.in(in.data())[s] = perm[s];
-  }
-  if (G) std::memcpy(o_gprot.in(in.data()), group_protected, G);
-  if (gang) {
-    std::memcpy(o_gneed.in(in.data()), g_need.data(), o_gneed.bytes());
-    std::memcpy(o_grlen.in(in.data()), g_rlen.data(), o_grlen.bytes());
-  }
-  uint8_t* base = c->d_pre.as<uint8_t>();
-  HIPCHK(c, hipMemcpyAsync(base, in.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(base + o_work, 0, work_bytes, c->stream));
-  CommitDev pe{};
-  const auto bt = bound_dev(pe, c->d_bound.as<const uint8_t>(), c->blay);
-  pe.bpres = bt.pres;
-  pe.bnviol = bt.nviol;
-  pe.bstride = (uint32_t)nB;
-  pe.q = count;
-  pe.nchunks = nchunks;
-  pe.chunk_nodes = chunk_nodes;
-  pe.cap = victim_cap;
-  pe.spod = o_spod.in(base);
-  pe.sprio = o_sprio.in(base);
-  pe.sorig = o_sorig.in(base);
-  pe.gprot = o_gprot.in(base);
-  pe.r_node = o_rnode.in(base);
-  pe.r_nv = o_rnv.in(base);
-  pe.r_npv = o_rnpv.in(base);
-  pe.r_top = o_rtop.in(base);
-  pe.r_sum = o_rsum.in(base);
-  pe.r_est = o_rest.in(base);
-  pe.r_ncand = o_rncand.in(base);
-  pe.dv = o_dv.in(base);
-  pe.dn = o_dn.in(base);
-  pe.vbits = o_vbits.in(base);
-  pe.nbits = o_nbits.in(base);
-  pe.dirty = o_dirty.in(base);
-  pe.dead = o_dead.in(base);
-  pe.dlist = o_dlist.in(base);
-  pe.info = o_info.in(base);
-  pe.o_node = o_node.in(base);
-  pe.o_ncand = o_ncand.in(base);
-  pe.o_nv = o_nv.in(base);
-  pe.o_npv = o_npv.in(base);
-  pe.o_top = o_top.in(base);
-  pe.o_sum = o_sum.in(base);
-  pe.o_est = o_est.in(base);
-  pe.o_victims = o_vic.in(base);
-  const NodesDev nd = nodes_dev(c);
-  if (gang) {
-    GangDev gd{};
-    gd.s_need = o_gneed.in(base);
-    gd.s_rlen = o_grlen.in(base);
-    gd.tag = o_gtag.in(base);
-    gd.slog = o_gslog.in(base);
-    gd.o_placed = o_gplaced.in(base);
-    gd.o_voided = o_gvoided.in(base);
-    launch_preempt_commit_gang(c->stream, c->S, dim3(tiles, nchunks), nd, pods_dev(c), pe, gd);
-  } else {
-    launch_preempt_commit(c->stream, c->S, dim3(tiles, nchunks), nd, pods_dev(c), pe);
-  }
-  LAUNCHCHK(c, BS_KERNEL_QUERY);
-  std::vector<uint8_t> res(cv.mark() - o_res);
-  HIPCHK(c, hipMemcpyAsync(res.data(), base + o_res, res.size(), hipMemcpyDeviceToHost, c->stream));
-  std::vector<uint8_t> gres;                              // gang: placed by slot, then voided by preemptor (adjacent in the blob)
-  if (gang) {
-    gres.resize(o_work + work_bytes - o_gplaced.off);
-    HIPCHK(c, hipMemcpyAsync(gres.data(), o_gplaced.in(base), gres.size(), hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint8_t* rb = res.data() - o_res;
-  if (apply) {
-    const uint32_t* info = o_info.in(rb);
-    const uint32_t ndirty = info[0], nvall = info[1];
-    bs_node_request* dreq = o_nreq.in(base);
-    CompactDev nw{};
-    const uint32_t B2 = B - nvall;
-    BoundLayout lay{};
-    if (nvall) {                                          // the compacted table goes to the second buffer, swapped in below
-      HIPCHK(c, c->d_bound2.reserve(bound_layout(L, N, B2, lay)));
-      const auto nt = bound_dev(nw, c->d_bound2.as<uint8_t>(), lay);
-      nw.bpres = nt.pres;
-      nw.bnviol = nt.nviol;
-      nw.bstride = std::max<uint32_t>(B2, 1);
-    }
-    launch_preempt_apply(c->stream, c->S, nd, pe, ndirty, assume ? 1u : 0u, dreq, nvall ? &nw : nullptr);
-    LAUNCHCHK(c, BS_KERNEL_QUERY);
-    if (ndirty) {
-      launch_nodes_assume(c, dreq, ndirty);
-      LAUNCHCHK(c, BS_KERNEL_PREPASS);
-      std::vector<bs_node_request> h(ndirty);
-      HIPCHK(c, hipMemcpyAsync(h.data(), dreq, (size_t)ndirty * sizeof(bs_node_request), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      mirror_node_requests(c, h.data(), ndirty);
-      c->bitmap_valid = false;
-    }
-    if (nvall) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      std::swap(c->d_bound.p, c->d_bound2.p);
-      std::swap(c->d_bound.cap, c->d_bound2.cap);
-      c->blay = lay;
-      c->bound_b = B2;
-    }
-  }
-  std::memcpy(out->node, o_node.in(rb), o_node.bytes());
-  std::memcpy(out->n_victims, o_nv.in(rb), o_nv.bytes());
-  c->pre_npv.assign(o_npv.in(rb), o_npv.in(rb) + nQ);
-  c->have_pre_npv = true;
-  c->have_gang = gang;
-  if (gang) {
-    const uint32_t* placed = o_gplaced.in(gres.data() - o_gplaced.off);
-    const uint8_t* voided = o_gvoided.in(gres.data() - o_gplaced.off);
-    c->gang_voided.assign(voided, voided + nQ);
-    c->gang_placed.assign(G, 0u);
-    for (uint32_t s = 0; s < count; ++s)
-      if (g_rlen[s]) c->gang_placed[sgroup[s]] = placed[s];
-  }
-  if (out->n_candidates) std::memcpy(out->n_candidates, o_ncand.in(rb), o_ncand.bytes());
-  if (out->top_priority) std::memcpy(out->top_priority, o_top.in(rb), o_top.bytes());
-  if (out->priority_sum) std::memcpy(out->priority_sum, o_sum.in(rb), o_sum.bytes());
-  if (out->earliest_start) std::memcpy(out->earliest_start, o_est.in(rb), o_est.bytes());
-  if (victim_cap) {
-    const uint32_t* nv = o_nv.in(rb);
-    const uint32_t* vic = o_vic.in(rb);
-    for (size_t q = 0; q < nQ; ++q) {
-      const uint32_t k = std::min(nv[q], victim_cap);
-      std::memcpy(out->victims + q * victim_cap, vic + q * victim_cap, (size_t)k * 4);
-      std::memset(out->victims + q * victim_cap + k, 0, (size_t)(victim_cap - k) * 4);
-    }
-  }
-  return BS_OK;
-}
-
-int bs_preempt_commit(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority, const uint8_t* group_protected,
-                      uint32_t flags, uint32_t victim_cap, const bs_preempt_out* out) {
-  return preempt_commit_call(c, stages, count, pod_index, priority, group_protected, nullptr, false, flags, victim_cap, out);
-}
-
-int bs_preempt_commit_gang(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
-                           const uint8_t* group_protected, const uint32_t* gang_need, uint32_t flags, uint32_t victim_cap, const bs_preempt_out* out) {
-  return preempt_commit_call(c, stages, count, pod_index, priority, group_protected, gang_need, true, flags, victim_cap, out);
-}
-
-int bs_preempt_gang_read(bs_ctx* c, uint32_t count, uint8_t* slot_voided, uint32_t g, uint32_t* group_placed) {
-  if (!c) return BS_ERR_INVALID;
-  if (!c->have_gang) { c->last_error = "bs_preempt_gang_read: the last preemption call was not a successful bs_preempt_commit_gang"; return BS_ERR_STATE; }
-  if (count != c->gang_voided.size() || g != c->gang_placed.size()) {
-    c->last_error = "bs_preempt_gang_read: count or g differ from the last bs_preempt_commit_gang's";
-    return BS_ERR_INVALID;
-  }
-  if (slot_voided && count) std::memcpy(slot_voided, c->gang_voided.data(), count);
-  if (group_placed && g) std::memcpy(group_placed, c->gang_placed.data(), (size_t)g * 4);
-  return BS_OK;
-}
-
-int bs_bound_read(bs_ctx* c, uint32_t* id_out, uint32_t* node_out) {
-  if (!c) return BS_ERR_INVALID;
-  if (!c->have_bound) { c->last_error = "bs_bound_read before bs_bound_load"; return BS_ERR_STATE; }
-  const uint32_t B = c->bound_b, N = c->bound_n;
-  if (B == 0) return BS_OK;
-  if (!id_out || !node_out) return BS_ERR_INVALID;
-  int rc = use_device(c);
-  if (rc) return rc;
-  std::vector<uint32_t> boff((size_t)N + 1);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const auto bt = bound_cols(c->d_bound.as<const uint8_t>(), c->blay);
-  HIPCHK(c, hipMemcpy(boff.data(), bt.boff, ((size_t)N + 1) * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(id_out, bt.id, (size_t)B * 4, hipMemcpyDeviceToHost));
-  for (uint32_t k = 0; k < N; ++k)
-    for (uint32_t j = boff[k]; j < boff[k + 1] && j < B; ++j) node_out[j] = k;
-  return BS_OK;
-}
-
-// -------------------------------------------------------------------------------------------------
-// the bound table patched in place (bs_bound_apply.hpp): O(delta) on the host, one pass over the table on the device
-// -------------------------------------------------------------------------------------------------
-int bs_bound_ids(const bs_ctx* c, uint32_t* ids_out) {
-  if (!c || !ids_out) return BS_ERR_INVALID;
-  *ids_out = c->have_bound ? c->bound_ids : 0u;
-  return BS_OK;
-}
-
-// flags: 0 = bs_bound_apply; BS_BOUND_NODES = the node requests follow (bs_bound_apply_ex)
-static int bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t flags, uint32_t* first_id_out) {
-  if (!c || !d) return BS_ERR_INVALID;
-  if (flags & ~BS_BOUND_NODES) { c->last_error = "bs_bound_apply_ex: unknown flags"; return BS_ERR_INVALID; }
-  const bool with_nodes = (flags & BS_BOUND_NODES) != 0;
-  if (!c->have_bound) { c->last_error = "bs_bound_apply before bs_bound_load"; return BS_ERR_STATE; }
-  if (with_nodes && !c->have_nodes) { c->last_error = "bs_bound_apply_ex(BS_BOUND_NODES) before bs_nodes_load"; return BS_ERR_STATE; }
-  if (c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
-  const uint32_t R = d->n_remove, I = d->n_insert, N = c->N, L = c->L, B = c->bound_b, ids = c->bound_ids;
-  if (R && !d->remove) return BS_ERR_INVALID;
-  if (I && (!d->node || !d->priority || !d->start_ns || !d->group || !d->req || !d->req_present)) return BS_ERR_INVALID;
-  if (R == 0 && I == 0) {
-    if (first_id_out) *first_id_out = ids;
-    return BS_OK;
-  }
-  int32_t gmax = c->bound_max_group;
-  for (uint32_t i = 0; i < I; ++i) {
-    if (d->node[i] >= N) { c->last_error = "bs_bound_apply: insert on a node index >= n"; return BS_ERR_INVALID; }
-    if (d->group[i] < BS_POD_GROUP_MISSING) { c->last_error = "bs_bound_apply: insert group index below BS_POD_GROUP_MISSING"; return BS_ERR_INVALID; }
-    gmax = std::max(gmax, d->group[i]);
-  }
-  for (uint32_t r = 0; r < R; ++r)
-    if (d->remove[r] >= ids) { c->last_error = "bs_bound_apply: remove id outside the id space"; return BS_ERR_INVALID; }
-  if (R > B) { c->last_error = "bs_bound_apply: more remove ids than live entries (an id is listed twice or is not live)"; return BS_ERR_INVALID; }
-  if ((uint64_t)ids + I > BS_BOUND_MAX) { c->last_error = "bs_bound_apply: the id space would pass BS_BOUND_MAX: reload the table"; return BS_ERR_CAPACITY; }
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (with_nodes && (rc = settle_pending(c))) return rc;   // as bs_nodes_assume: a pending batch is settled against the state it was launched on
-  // the inserts by (node, importance); their ids follow the delta's order, so equal keys keep it
-  std::vector<uint32_t> order(I);
-  for (uint32_t i = 0; i < I; ++i) order[i] = i;
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-    if (d->node[a] != d->node[b]) return d->node[a] < d->node[b];
-    if (d->priority[a] != d->priority[b]) return d->priority[a] > d->priority[b];
-    if (d->start_ns[a] != d->start_ns[b]) return d->start_ns[a] < d->start_ns[b];
-    return a < b;
-  });
-  // one blob (8-byte columns first), then the scratch: pos_of (0xff), the zeroed words, the segment starts
-  const size_t nI = I, nR = R, nN = std::max<uint32_t>(N, 1);
-  Carve cv;
-  const auto o_start = cv.take<int64_t>(nI, 1);           // (packed)
-  const auto o_req = cv.take<int64_t>(nI * L, 1);
-  const auto o_rem = cv.take<uint32_t>(nR, 1);
-  const auto o_node = cv.take<uint32_t>(nI, 1);
-  const auto o_prio = cv.take<int32_t>(nI, 1);
-  const auto o_group = cv.take<int32_t>(nI, 1);
-  const auto o_id = cv.take<uint32_t>(nI, 1);
-  const auto o_pres = cv.take<uint32_t>(nI, 1);
-  const auto o_pdb = cv.take<uint8_t>(nI);                 // the last column: the scratch behind it starts at the next 256
-  const size_t blob_bytes = o_pdb.off + o_pdb.bytes();
-  const auto o_posof = cv.take<uint32_t>(std::max<uint32_t>(ids, 1));
-  const size_t o_zero = cv.mark();
-  const auto o_deadw = cv.take<uint32_t>((size_t)B / 32 + 1);
-  const auto o_dcnt = cv.take<uint32_t>(nN);
-  const auto o_icnt = cv.take<uint32_t>(nN);
-  const auto o_err = cv.take<uint32_t>(1);
-  const auto o_gap = cv.take<uint8_t>(256);
-  const Piece<uint32_t> o_nrec{o_gap.off + 248, 2};        // BS_BOUND_NODES: the record count, the last 8 bytes before the records (one D2H)
-  const size_t zero_bytes = cv.mark() - o_zero;
-  const size_t rec_cap = with_nodes ? std::min<size_t>(N, nR + nI) : 0;
-  const auto o_rec = cv.take<bs_node_request>(rec_cap);
-  const auto o_ifirst = cv.take<uint32_t>(nN);
-  // the id space grows with every call, and the table with every net insert: a quarter of headroom, so that a run of calls allocates rarely
-  if (cv.mark() > c->d_pre.cap) HIPCHK(c, c->d_pre.reserve(cv.mark() + cv.mark() / 4));
-  std::vector<uint8_t> h(std::max<size_t>(blob_bytes, 1), 0);
-  uint8_t* hb = h.data();
-  if (R) std::memcpy(o_rem.in(hb), d->remove, o_rem.bytes());
-  const uint32_t smask = (uint32_t)((1ull << (L - BS_FIXED_LANES)) - 1ull);
-  for (uint32_t r = 0; r < I; ++r) {                       // stored as bs_bound_load stores them
-    const uint32_t i = order[r];
-    o_node.in(hb)[r] = d->node[i];
-    o_prio.in(hb)[r] = d->priority[i];
-    o_start.in(hb)[r] = d->start_ns[i];
-    o_group.in(hb)[r] = d->group[i];
-    o_id.in(hb)[r] = ids + i;
-    o_pres.in(hb)[r] = d->req_present[i] & smask;
-    o_pdb.in(hb)[r] = d->pdb_violating && d->pdb_violating[i] ? 1 : 0;
-    for (uint32_t l = 0; l < L; ++l) {
-      int64_t v = d->req[(size_t)l * I + i];
-      if (l == BS_LANE_PODS) v = 1;
-      else if (l >= BS_FIXED_LANES && !((d->req_present[i] >> (l - BS_FIXED_LANES)) & 1u)) v = 0;
-      o_req.in(hb)[(size_t)l * nI + r] = v;
-    }
-  }
-  uint8_t* base = c->d_pre.as<uint8_t>();
-  HIPCHK(c, hipMemcpyAsync(base, h.data(), h.size(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(o_posof.in(base), 0xff, o_posof.bytes(), c->stream));
-  HIPCHK(c, hipMemsetAsync(base + o_zero, 0, zero_bytes, c->stream));
-  const uint32_t B2 = B - R + I;                           // (when the error word stays clear)
-  BoundLayout lay{};
-  const size_t table_bytes = bound_layout(L, N, B2, lay);
-  if (table_bytes > c->d_bound2.cap) HIPCHK(c, c->d_bound2.reserve(table_bytes + table_bytes / 4));
-  BoundApplyDev a{};
-  const auto bt = bound_dev(a, c->d_bound.as<const uint8_t>(), c->blay);
-  a.bpres = bt.pres;
-  a.bstride = std::max<uint32_t>(B, 1);
-  a.b = B; a.n = N; a.ids = ids;
-  a.n_remove = R; a.n_insert = I;
-  a.rem = o_rem.in(base);
-  a.inode = o_node.in(base);
-  a.iprio = o_prio.in(base);
-  a.istart = o_start.in(base);
-  a.igroup = o_group.in(base);
-  a.ireq = o_req.in(base);
-  a.iid = o_id.in(base);
-  a.ipres = o_pres.in(base);
-  a.ipdb = o_pdb.in(base);
-  a.pos_of = o_posof.in(base);
-  a.deadw = o_deadw.in(base);
-  a.dcnt = o_dcnt.in(base);
-  a.icnt = o_icnt.in(base);
-  a.ifirst = o_ifirst.in(base);
-  a.err = o_err.in(base);
-  CompactDev nw{};
-  const auto nt = bound_dev(nw, c->d_bound2.as<uint8_t>(), lay);
-  nw.bpres = nt.pres;
-  nw.bnviol = nt.nviol;
-  nw.bstride = std::max<uint32_t>(B2, 1);
-  launch_bound_apply(c->stream, c->S, a, nw);
-  LAUNCHCHK(c, BS_KERNEL_PREPASS);
-  uint32_t err = 0;                                        // read before the swap: the merge wrote nothing when it is set
-  HIPCHK(c, hipMemcpyAsync(&err, a.err, o_err.bytes(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (err & (kBaErrUnknown | kBaErrDead | kBaErrTwice | kBaErrNode)) {
-    c->last_error = (err & kBaErrTwice) ? "bs_bound_apply: a remove id is listed twice"
-                  : (err & kBaErrDead)  ? "bs_bound_apply: a remove id is not live (evicted or removed earlier)"
-                                        : "bs_bound_apply: a remove id or an insert node is out of range";
-    return BS_ERR_INVALID;
-  }
-  if (err & kBaErrFull) { c->last_error = "bs_bound_apply: more than BS_BOUND_MAX_PER_NODE bound pods on one node"; return BS_ERR_CAPACITY; }
-  std::swap(c->d_bound.p, c->d_bound2.p);
-  std::swap(c->d_bound.cap, c->d_bound2.cap);
-  c->blay = lay;
-  c->bound_b = B2;
-  c->bound_ids = ids + I;
-  c->bound_max_group = gmax;
-  if (first_id_out) *first_id_out = ids;
-  if (with_nodes && rec_cap) {
-    // the node requests follow: `a` still names the old table (now the second allocation, intact) and the scratch k_ba_mark left
-    BoundNodesReqDev o2{};
-    o2.nreq = c->d_nreq.as<int64_t>();
-    o2.rpres = c->d_rpres.as<uint32_t>();
-    o2.nstride = c->Ncap;
-    o2.cap = (uint32_t)rec_cap;
-    o2.count = o_nrec.in(base);
-    o2.out = o_rec.in(base);
-    launch_bound_apply_nodes(c->stream, c->S, a, o2);
-    LAUNCHCHK(c, BS_KERNEL_PREPASS);
-    std::vector<uint8_t> hr(8 + rec_cap * sizeof(bs_node_request));   // count + records
-    HIPCHK(c, hipMemcpyAsync(hr.data(), o_nrec.in(base), hr.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    uint32_t nrec = 0;
-    std::memcpy(&nrec, hr.data(), 4);
-    if (nrec > rec_cap) { c->last_error = "bs_bound_apply_ex: more touched nodes than the delta can touch"; return BS_ERR_HIP; }
-    if (nrec) {
-      launch_nodes_assume(c, o2.out, nrec);
-      LAUNCHCHK(c, BS_KERNEL_PREPASS);
-      mirror_node_requests(c, reinterpret_cast<const bs_node_request*>(hr.data() + 8), nrec);
-      c->bitmap_valid = false;
-    }
-  }
-  return BS_OK;
-}
-
-int bs_bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t* first_id_out) { return bound_apply(c, d, 0u, first_id_out); }
-
-int bs_bound_apply_ex(bs_ctx* c, const bs_bound_delta* d, uint32_t flags, uint32_t* first_id_out) { return bound_apply(c, d, flags, first_id_out); }
-
-int bs_bound_apply_ex_flat(bs_ctx* c, uint32_t flags, uint32_t n_remove, const uint32_t* remove, uint32_t n_insert, const uint32_t* node,
-                           const int32_t* priority, const int64_t* start_ns, const int32_t* group, const int64_t* req, const uint32_t* req_present,
-                           const uint8_t* pdb_violating, uint32_t* first_id_out) {
-  const bs_bound_delta d{n_remove, remove, n_insert, node, priority, start_ns, group, req, req_present, pdb_violating};
-  return bound_apply(c, &d, flags, first_id_out);
-}
-
-int bs_bound_apply_flat(bs_ctx* c, uint32_t n_remove, const uint32_t* remove, uint32_t n_insert, const uint32_t* node, const int32_t* priority,
-                        const int64_t* start_ns, const int32_t* group, const int64_t* req, const uint32_t* req_present, const uint8_t* pdb_violating,
-                        uint32_t* first_id_out) {
-  const bs_bound_delta d{n_remove, remove, n_insert, node, priority, start_ns, group, req, req_present, pdb_violating};
-  return bs_bound_apply(c, &d, first_id_out);
-}
-
-// -------------------------------------------------------------------------------------------------
-// the bound table follows node-list surgery (bs_bound_nodes.hpp): O(count) on the host, one pass over the table on the device
-// -------------------------------------------------------------------------------------------------
-int bs_bound_nodes_apply(bs_ctx* c, uint32_t count, const uint32_t* kind, const uint32_t* index, uint32_t dropped_cap, uint32_t* dropped_ids,
-                         uint32_t* n_dropped_out) {
-  if (!c) return BS_ERR_INVALID;
-  if (!c->have_bound) { c->last_error = "bs_bound_nodes_apply before bs_bound_load"; return BS_ERR_STATE; }
-  if (c->nranks > 1 || c->reduce_external) { c->last_error = "bs_bound_nodes_apply is single-rank only"; return BS_ERR_STATE; }
-  if ((count && (!kind || !index)) || (dropped_cap && !dropped_ids)) return BS_ERR_INVALID;
-  const uint32_t N0 = c->bound_n, L = c->L, B = c->bound_b;
-  NodeReplay rp;
-  if (bound_nodes_replay(N0, count, kind, index, rp)) {
-    c->last_error = "bs_bound_nodes_apply: a kind outside UPDATE / APPEND / REMOVE, or an index at or beyond the node count at its point of the replay";
-    return BS_ERR_INVALID;
-  }
-  if (rp.n_new != c->N) { c->last_error = "bs_bound_nodes_apply: the replay does not end at the node count: not the list bs_nodes_apply got"; return BS_ERR_STATE; }
-  const uint32_t N1 = rp.n_new, R = (uint32_t)rp.removed.size();
-  if (R == 0 && rp.appended == 0) {                        // updates, or appends removed again: the table stays as it is
-    if (n_dropped_out) *n_dropped_out = 0;
-    return BS_OK;
-  }
-  int rc = use_device(c);
-  if (rc) return rc;
-  // the removed list (one H2D), then the scratch of this call
-  const uint32_t nblk = std::max<uint32_t>(1u, cdiv(std::max(N1, R), 1024u)), ncap = std::min(dropped_cap, B);
-  const size_t nR = R, nN = N1;
-  Carve cv;
-  const auto o_rem = cv.take<uint32_t>(nR);
-  const auto o_len = cv.take<uint32_t>(nN);
-  const auto o_src = cv.take<uint32_t>(nN);
-  const auto o_dlen = cv.take<uint32_t>(nR);
-  const auto o_doff = cv.take<uint32_t>(nR + 1);
-  const auto o_bsum = cv.take<uint32_t>((size_t)2 * nblk);
-  const auto o_pair = cv.take<uint32_t>(2);
-  const auto o_drop = cv.take<uint32_t>(ncap);
-  if (cv.mark() > c->d_pre.cap) HIPCHK(c, c->d_pre.reserve(cv.mark() + cv.mark() / 4));
-  // the new table holds at most the old entries: sized for them, laid out by k_bn_move for the count the scan finds (boff: N1 + 1 words,
-  // nviol: N1 words — appends grow both)
-  BoundLayout lay{};
-  const size_t table_bytes = bound_layout(L, N1, B, lay);
-  if (table_bytes > c->d_bound2.cap) HIPCHK(c, c->d_bound2.reserve(table_bytes + table_bytes / 4));
-  uint8_t* base = c->d_pre.as<uint8_t>();
-  if (R) HIPCHK(c, hipMemcpyAsync(o_rem.in(base), rp.removed.data(), o_rem.bytes(), hipMemcpyHostToDevice, c->stream));
-  BoundNodesDev a{};
-  const auto bt = bound_dev(a, c->d_bound.as<const uint8_t>(), c->blay);
-  a.bpres = bt.pres;
-  a.bstride = std::max<uint32_t>(B, 1);
-  a.n0 = N0; a.n1 = N1;
-  a.nrem = R; a.old_left = N0 - R;
-  a.rem = o_rem.in(base);
-  a.nbase = c->d_bound2.as<uint8_t>();
-  a.nboff = bound_cols(a.nbase, lay).boff;
-  a.len = o_len.in(base);
-  a.src = o_src.in(base);
-  a.dlen = o_dlen.in(base);
-  a.doff = o_doff.in(base);
-  a.bsum = o_bsum.in(base);
-  a.nblk = nblk;
-  a.pair = o_pair.in(base);
-  a.dropped = o_drop.in(base);
-  a.dropped_cap = ncap;
-  launch_bound_nodes(c->stream, c->S, a);
-  LAUNCHCHK(c, BS_KERNEL_PREPASS);
-  uint32_t pair[2] = {0, 0};                               // {new entry count, dropped count}: read before the swap
-  HIPCHK(c, hipMemcpyAsync(pair, a.pair, o_pair.bytes(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));              // (rp.removed and pair are local buffers)
-  if ((uint64_t)pair[0] + pair[1] != B) { c->last_error = "bs_bound_nodes_apply: the resident table's offsets do not add up"; return BS_ERR_HIP; }
-  const uint32_t nd = std::min(pair[1], ncap);
-  if (nd) HIPCHK(c, hipMemcpy(dropped_ids, a.dropped, (size_t)nd * 4, hipMemcpyDeviceToHost));
-  std::swap(c->d_bound.p, c->d_bound2.p);
-  std::swap(c->d_bound.cap, c->d_bound2.cap);
-  bound_layout(L, N1, pair[0], lay);                       // as k_bn_move laid it out
-  c->blay = lay;
-  c->bound_b = pair[0];
-  c->bound_n = N1;
-  if (n_dropped_out) *n_dropped_out = pair[1];
-  return BS_OK;
-}
-
-int bs_bound_dump(bs_ctx* c, int32_t* priority, int64_t* start_ns, int32_t* group, int64_t* req, uint32_t* req_present, uint8_t* pdb) {
-  if (!c) return BS_ERR_INVALID;
-  if (!c->have_bound) { c->last_error = "bs_bound_dump before bs_bound_load"; return BS_ERR_STATE; }
-  const size_t B = c->bound_b;
-  if (B == 0) return BS_OK;
-  int rc = use_device(c);
-  if (rc) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const auto bt = bound_cols(c->d_bound.as<const uint8_t>(), c->blay);
-  if (priority) HIPCHK(c, hipMemcpy(priority, bt.prio, B * 4, hipMemcpyDeviceToHost));
-  if (start_ns) HIPCHK(c, hipMemcpy(start_ns, bt.start, B * 8, hipMemcpyDeviceToHost));
-  if (group) HIPCHK(c, hipMemcpy(group, bt.group, B * 4, hipMemcpyDeviceToHost));
-  if (req) HIPCHK(c, hipMemcpy(req, bt.req, B * c->L * 8, hipMemcpyDeviceToHost));   // the lane stride is the entry count
-  if (req_present) HIPCHK(c, hipMemcpy(req_present, bt.pres, B * 4, hipMemcpyDeviceToHost));
-  if (pdb) HIPCHK(c, hipMemcpy(pdb, bt.pdb, B, hipMemcpyDeviceToHost));
-  return BS_OK;
-}
-
-int bs_preempt_commit_flat(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority, const uint8_t* group_protected,
-                           uint32_t flags, uint32_t victim_cap, int32_t* node, uint32_t* n_candidates, uint32_t* n_victims, uint32_t* victims,
-                           int32_t* top_priority, int64_t* priority_sum, int64_t* earliest_start) {
-  const bs_preempt_out o{node, n_candidates, n_victims, victims, top_priority, priority_sum, earliest_start};
-  return bs_preempt_commit(c, stages, count, pod_index, priority, group_protected, flags, victim_cap, &o);
-}
-
-int bs_preempt_commit_gang_flat(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
-                                const uint8_t* group_protected, const uint32_t* gang_need, uint32_t flags, uint32_t victim_cap, int32_t* node,
-                                uint32_t* n_candidates, uint32_t* n_victims, uint32_t* victims, int32_t* top_priority, int64_t* priority_sum,
-                                int64_t* earliest_start) {
-  const bs_preempt_out o{node, n_candidates, n_victims, victims, top_priority, priority_sum, earliest_start};
-  return bs_preempt_commit_gang(c, stages, count, pod_index, priority, group_protected, gang_need, flags, victim_cap, &o);
 }
 
 }  // extern "C"

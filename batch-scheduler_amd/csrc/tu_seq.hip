@@ -1,14 +1,18 @@
-// tu_seq.hip — translation unit of the sequential pass (bs_seq.hpp: k_seq_pass, six instantiations) and its launch wrapper; see
-// tu_fast.hip for why.
+// tu_seq.hip — translation unit of the sequential pass: its kernel (bs_seq.hpp: k_seq_pass, six instantiations), the file-local launch
+// wrapper and the entry point bs_seq_run (include/bsched.h) with its flat form; see tu_fast.hip for why.
 #ifndef BS_UNITY
 #define BS_TU_SEQ
 #endif
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
 #include "bs_seq.hpp"
-#include "bs_launch.hpp"
+#include "bs_ctx.hpp"
 
 namespace bs {
 
-void launch_seq(hipStream_t stream, uint32_t S, size_t lds, const PodsDev& pd, const GroupsDev& gr, const NodesDev& nd, const SeqDev& sq, const SeqParams& prm) {
+static void launch_seq(hipStream_t stream, uint32_t S, size_t lds, const PodsDev& pd, const GroupsDev& gr, const NodesDev& nd, const SeqDev& sq, const SeqParams& prm) {
   lanes_narrow(S, [&](auto s) {
     constexpr int TS = decltype(s)::value;
     // static LDS (first-fit bounds, reduction slots) + the key window can exceed the default 64 KB of dynamic LDS
@@ -18,3 +22,215 @@ void launch_seq(hipStream_t stream, uint32_t S, size_t lds, const PodsDev& pd, c
 }
 
 }  // namespace bs
+
+extern "C" {
+int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
+  if (!c || !out) return BS_ERR_INVALID;
+  if (!c->have_nodes || !c->have_fit || !c->have_groups || !c->have_pods) {
+    c->last_error = "bs_seq_run needs nodes, fit, groups and pods loaded";
+    return BS_ERR_STATE;
+  }
+  if (!(stages & BS_STAGE_PREFILTER)) { c->last_error = "PREFILTER stage is mandatory"; return BS_ERR_INVALID; }
+  if ((stages & BS_BATCH_FILTER_DENY) && !(stages & BS_STAGE_FILTER)) { c->last_error = "BS_BATCH_FILTER_DENY needs BS_STAGE_FILTER"; return BS_ERR_INVALID; }
+  if (c->nranks > 1 || c->reduce_external) { c->last_error = "bs_seq_run is single-rank only (a sequential pass does not shard)"; return BS_ERR_STATE; }
+  int rc = use_device(c);
+  if (rc) return rc;
+  if ((rc = settle_pending(c))) return rc;
+  const uint32_t P = c->P, G = c->G, N = c->N, C = c->C, L = c->L;
+  if ((G > c->n_uncaptured && c->max_group_cls >= C) || (P && c->max_pod_cls >= C)) {
+    c->last_error = "fit class index out of range (groups.cls / pods.cls vs the loaded fit classes)";
+    return BS_ERR_INVALID;
+  }
+  if (G > 0x7FFFFFF0u) return BS_ERR_CAPACITY;
+  c->seq_wait_valid = false;                                // the pass replaces the waiting state
+  // the first-fit cursors are keyed by the resident queue's request classes: a queue patch whose insert wave ran out of class ids
+  // (h_info[13], set by the device) left them unusable until the queue is re-derived — check_handover does that
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // An unread batch's error words are looked at here (the id overflow concerns this pass: check_handover re-derives the queue) but they stay
+  // that batch's: batch_void keeps every later read of it failing with BS_ERR_RETRY until bs_batch_run starts a new one.  The pass itself
+  // reads no batch result and goes on.
+  if ((rc = check_handover(c)) && rc != BS_ERR_RETRY) return rc;
+  if (rc == BS_ERR_RETRY) c->last_error.clear();            // (nothing failed for THIS call)
+  out->n_released = 0;
+  out->total_ns = 0;
+  out->node_picks = out->node_scans = out->scan_rounds = out->pick_rounds = out->leader_folds = out->table_builds = 0;
+  // ---- scratch: one allocation
+  const size_t nP = std::max<uint32_t>(P, 1), nG = std::max<uint32_t>(G, 1), cap = std::max<uint32_t>(out->cap, 1), stride = std::max<uint32_t>(c->Ncap, 1);
+  Carve cv;
+  const auto o_sc07 = cv.take<int64_t>(stride * L);
+  const auto o_sc10 = cv.take<int64_t>(stride * L);
+  const auto o_meta = cv.take<uint32_t>(stride);
+  const auto o_keys = cv.take<unsigned long long>(nG);
+  const auto o_wait = cv.take<unsigned long long>(nP);
+  const auto o_head = cv.take<uint32_t>(nG);
+  const auto o_nwait = cv.take<uint32_t>(nG);
+  const auto o_slot = cv.take<uint32_t>(nG);
+  const auto o_tfirst = cv.take<unsigned long long>(nG);
+  const size_t o_res = cv.mark();                           // results: one D2H
+  const auto o_code = cv.take<uint8_t>(nP);
+  const auto o_node = cv.take<int32_t>(nP);
+  const auto o_fk = cv.take<uint32_t>(nP);
+  const auto o_leader = cv.take<int32_t>(nP);
+  const auto o_lperm = cv.take<uint8_t>(nP);
+  const auto o_rg = cv.take<uint32_t>(cap);
+  const auto o_rp = cv.take<uint32_t>(cap);
+  const auto o_ft = cv.take<unsigned long long>(cap);
+  const auto o_rt = cv.take<unsigned long long>(cap);
+  const auto o_info = cv.take<unsigned long long>(64);
+  HIPCHK(c, c->d_seq.reserve(cv.mark()));
+  uint8_t* base = c->d_seq.as<uint8_t>();
+  GroupsDev gr = groups_dev(c);
+  SeqDev sq{};
+  sq.nreq = c->d_nreq.as<int64_t>();
+  sq.rpres = c->d_rpres.as<uint32_t>();
+  sq.g_matched = const_cast<uint32_t*>(gr.matched);
+  sq.g_sc = const_cast<uint32_t*>(gr.status_scheduled);
+  sq.g_flags = const_cast<uint8_t*>(gr.flags);
+  sq.g_cls = const_cast<uint32_t*>(gr.cls);
+  sq.g_minres = const_cast<int64_t*>(gr.minres);
+  sq.g_mrpres = const_cast<uint32_t*>(gr.mrpres);
+  sq.g_occ = const_cast<uint64_t*>(gr.occupied);
+  sq.left07 = o_sc07.in(base);
+  sq.left10 = o_sc10.in(base);
+  sq.nmeta = o_meta.in(base);
+  sq.keys = o_keys.in(base);
+  sq.wait_rec = o_wait.in(base);
+  sq.head = o_head.in(base);
+  sq.nwait = o_nwait.in(base);
+  sq.slot_of = o_slot.in(base);
+  sq.t_first = o_tfirst.in(base);
+  sq.pclass = pclass_dev(c);
+  sq.pf_code = o_code.in(base);
+  sq.pod_node = o_node.in(base);
+  sq.pf_first_k = o_fk.in(base);
+  sq.pf_leader = o_leader.in(base);
+  sq.last_permitted = o_lperm.in(base);
+  sq.released_group = o_rg.in(base);
+  sq.released_pods = o_rp.in(base);
+  sq.first_tick = o_ft.in(base);
+  sq.ready_tick = o_rt.in(base);
+  sq.cap = out->cap;
+  sq.info = o_info.in(base);
+  SeqParams prm{};
+  prm.S = c->S;
+  prm.eph_gate = c->cfg.eph_gate;
+  prm.run_filter = (stages & BS_STAGE_FILTER) ? 1u : 0u;
+  prm.filter_deny = (stages & BS_BATCH_FILTER_DENY) ? 1u : 0u;
+  prm.C = C;
+  prm.sop_leader0 = c->sop_leader0;
+  prm.keys_in_lds = G <= kSeqKeysLds ? 1u : 0u;
+  prm.prune = cdiv(N, 64) <= kSeqPruneTiles ? 1u : 0u;
+  size_t lds = prm.keys_in_lds ? align256((size_t)nG * 8) : 0;
+  {
+    // table summaries: as many slots as the CU's LDS holds behind the static arrays and the key window (one thread per tile: <= 1024 tiles)
+    const size_t T = cdiv(N, 64), per_slot = T * ((size_t)L * 24 + 8), query = 0;
+    const size_t budget = (size_t)160 * 1024 - sizeof(SeqShared) - 2048;
+    uint32_t K = 0;
+    if (T && T <= (size_t)kSeqPruneTiles && budget > lds + query + per_slot) K = (uint32_t)std::min<size_t>(kSeqCacheSlots, (budget - lds - query) / per_slot);
+    if (const char* e = std::getenv("BS_SEQ_CACHE_SLOTS")) K = std::min<uint32_t>(K, (uint32_t)std::max(0, std::atoi(e)));   // tests: 0 = the round scan, 1 = thrash one slot
+    prm.cache_slots = K;
+    prm.cache_off = (uint32_t)lds;
+    if (K) lds += align256(K * per_slot + query + 64);
+  }
+  // first-fit cursors per request class (bs_seq.hpp, seq_pick): BS_SEQ_NO_CURSOR=1 = every search starts at the head of the list
+  prm.use_cursor = (P && sq.pclass && !(std::getenv("BS_SEQ_NO_CURSOR") && std::atoi(std::getenv("BS_SEQ_NO_CURSOR")))) ? 1u : 0u;
+  HIPCHK(c, hipMemsetAsync(o_info.in(base), 0, o_info.bytes(), c->stream));
+  const PodsDev pd = pods_dev(c);
+  const NodesDev nd = nodes_dev(c);
+  launch_seq(c->stream, c->S, lds, pd, gr, nd, sq, prm);
+  LAUNCHCHK(c, BS_KERNEL_QUERY);
+  // ---- results: one copy of the whole result block, then the caller's arrays
+  std::vector<uint8_t> res(cv.mark() - o_res);
+  HIPCHK(c, hipMemcpyAsync(res.data(), base + o_res, res.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint8_t* rb = res.data() - o_res;
+  const unsigned long long* info = o_info.in(rb);
+  int khz = 0;
+  if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->cfg.device) != hipSuccess || khz <= 0) khz = 100000;   // 100 MHz
+  auto to_ns = [&](unsigned long long ticks) { return (int64_t)((long double)ticks * 1.0e6L / (long double)khz); };
+  out->n_released = (uint32_t)info[0];
+  out->total_ns = to_ns(info[1]);
+  out->node_picks = info[2];
+  out->node_scans = info[3];
+  out->scan_rounds = info[5];
+  out->pick_rounds = info[6];
+  out->leader_folds = info[7] & ((1ull << 40) - 1ull);
+  out->table_builds = info[7] >> 40;
+  if (const char* e = std::getenv("BS_SEQ_PROBE_PRINT")) {   // probe build: cycles per phase (see bs_seq.hpp)
+    if (std::atoi(e)) std::fprintf(stderr, "seq probe cycles: control %llu capture %llu fold %llu scan %llu pick %llu permit %llu top-barrier %llu\n", info[8], info[9],
+                                   info[10], info[11], info[12], info[13], info[14]);
+    if (std::atoi(e)) std::fprintf(stderr, "  scan rounds (thread 0): issue-next-loads %llu select %llu wave-scans %llu lds-writes %llu barrier %llu fk-check %llu offsets+compare %llu tail %llu\n",
+                                   info[16], info[17], info[18], info[19], info[20], info[21], info[22], info[23]);
+    if (std::atoi(e)) {                                      // the finer split of thread 0's time (BS_SEQ_P in bs_seq.hpp)
+      static const char* nm[17] = {"top-barrier", "group-loads", "control", "scan:drain", "scan:slot", "scan:candidates", "scan:tiles", "scan:barrier+min", "scan:tail",
+                                   "pick:request", "pick:drain", "pick:tiles", "pick:barrier+min", "pick:assume", "summaries", "result-stores", "permit"};
+      std::fprintf(stderr, "  thread 0, cycles:");
+      for (int k2 = 0; k2 < 17; ++k2) std::fprintf(stderr, " %s %llu |", nm[k2], info[32 + k2]);
+      std::fprintf(stderr, "\n");
+    }
+  }
+  if (P) {
+    if (out->pf_code) std::memcpy(out->pf_code, o_code.in(rb), P);
+    if (out->pod_node) std::memcpy(out->pod_node, o_node.in(rb), (size_t)P * 4);
+    if (out->pf_first_k) std::memcpy(out->pf_first_k, o_fk.in(rb), (size_t)P * 4);
+    if (out->pf_leader) std::memcpy(out->pf_leader, o_leader.in(rb), (size_t)P * 4);
+    if (out->last_permitted) { if (prm.filter_deny) std::memcpy(out->last_permitted, o_lperm.in(rb), P); else std::memset(out->last_permitted, 0, P); }
+    c->sop_leader0 = (int32_t)(uint32_t)info[4] - 1;         // sop.maxFinishedPG as the pass left it
+  }
+  const uint32_t k = std::min(out->n_released, out->cap);
+  if (k) {
+    if (out->released_group) std::memcpy(out->released_group, o_rg.in(rb), (size_t)k * 4);
+    if (out->released_pods) std::memcpy(out->released_pods, o_rp.in(rb), (size_t)k * 4);
+    const unsigned long long* ft = o_ft.in(rb);
+    const unsigned long long* rt = o_rt.in(rb);
+    for (uint32_t i = 0; i < k; ++i) {
+      if (out->first_ns) out->first_ns[i] = to_ns(ft[i]);
+      if (out->ready_ns) out->ready_ns[i] = to_ns(rt[i]);
+    }
+  }
+  // ---- the host mirrors and everything derived from the state the pass rewrote
+  if (N && P) {
+    HIPCHK(c, hipMemcpy2D(c->h_nreq.data(), (size_t)N * 8, c->d_nreq.p, (size_t)c->Ncap * 8, (size_t)N * 8, L, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(c->h_rpres.data(), c->d_rpres.p, (size_t)N * 4, hipMemcpyDeviceToHost));
+    rederive_nodes(c);   // left4 / cluster bounds follow the requests (flags, hence kmap, are unchanged)
+    LAUNCHCHK(c, BS_KERNEL_PREPASS);
+  }
+  c->bitmap_valid = false;
+  if (G && P) {
+    std::vector<uint32_t> cls(G);
+    HIPCHK(c, hipMemcpy(c->h_gflags.data(), gr.flags, G, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(cls.data(), gr.cls, (size_t)G * 4, hipMemcpyDeviceToHost));
+    c->n_uncaptured = 0;
+    c->n_nominres = 0;
+    c->max_group_cls = 0;
+    for (uint32_t i = 0; i < G; ++i) {
+      if (!(c->h_gflags[i] & BS_GROUP_HAS_POD)) c->n_uncaptured++;
+      else c->max_group_cls = std::max(c->max_group_cls, cls[i]);
+      if (!(c->h_gflags[i] & BS_GROUP_HAS_MINRES)) c->n_nominres++;
+    }
+    if ((rc = analyse_groups(c))) return rc;
+    if ((rc = maybe_analyse_epochs(c))) return rc;
+  }
+  c->seq_o_wait = o_wait;                                  // (the pieces: seq_expire_dev addresses them in d_seq)
+  c->seq_o_head = o_head;
+  c->seq_o_nwait = o_nwait;
+  c->seq_wait_valid = true;
+  return BS_OK;
+}
+
+int bs_seq_run_flat(bs_ctx* c, uint32_t stages, uint8_t* pf_code, uint32_t* pf_first_k, int32_t* pf_leader, int32_t* pod_node, uint32_t cap,
+                    uint32_t* released_group, uint32_t* released_pods, int64_t* first_ns, int64_t* ready_ns, int64_t* scalars_out,
+                    uint8_t* last_permitted) {
+  bs_seq_out o{};
+  o.last_permitted = last_permitted;
+  o.pf_code = pf_code; o.pf_first_k = pf_first_k; o.pf_leader = pf_leader; o.pod_node = pod_node; o.cap = cap; o.released_group = released_group;
+  o.released_pods = released_pods; o.first_ns = first_ns; o.ready_ns = ready_ns;
+  const int rc = bs_seq_run(c, stages, &o);
+  if (scalars_out) {
+    scalars_out[0] = o.n_released; scalars_out[1] = o.total_ns; scalars_out[2] = (int64_t)o.node_picks; scalars_out[3] = (int64_t)o.node_scans;
+    scalars_out[4] = (int64_t)o.scan_rounds; scalars_out[5] = (int64_t)o.pick_rounds; scalars_out[6] = (int64_t)o.leader_folds;
+    scalars_out[7] = (int64_t)o.table_builds;
+  }
+  return rc;
+}
+}  // extern "C"

@@ -28,6 +28,6 @@ def test_the_header_is_host_only_and_no_host_switch_on_the_lane_count_is_left():
     """bs_lanes.hpp includes no HIP header; no `switch` on S / c->S / c.S / ts remains in the host code of the translation units"""
     text = open(os.path.join(CSRC, "bs_lanes.hpp")).read()
     assert not [h for h in re.findall(r"#include\s*[<\"]([^>\"]+)", text) if "hip" in h]
-    for unit in ("bsched.hip", "tu_fast.hip", "tu_seq.hip", "tu_seq_expire.hip", "tu_preempt.hip"):
+    for unit in ("bsched.hip", "tu_fast.hip", "tu_seq.hip", "tu_seq_expire.hip", "tu_preempt.hip", "bs_ctx.hpp"):
         src = open(os.path.join(CSRC, unit)).read()
         assert not re.search(r"switch\s*\(\s*(S|c->S|c\.S|ts)\b", src), unit

@@ -1,5 +1,5 @@
 """CPU: the launch geometry of the preemption search (batch-scheduler_amd/csrc/bs_preempt_geom.hpp) on its own, compiled with g++.  The
-header is the arithmetic that ships: bs_preempt_run and bs_preempt_commit (bsched.hip) both call preempt_geom().  The driver walks every
+header is the arithmetic that ships: bs_preempt_run and bs_preempt_commit (tu_preempt.hip) both call preempt_geom().  The driver walks every
 (N, tiles) of the grid below and reports, per node count N:
 
   bit 0  the chunks do not cover [0, N) exactly: not (nchunks - 1) * chunk_nodes < N <= nchunks * chunk_nodes (N > 0)

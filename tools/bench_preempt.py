@@ -78,7 +78,7 @@ def one(config: str, q: int, reps: int, warmup: int, commit: bool = False, apply
 
 
 def _table_bytes(L: int, n: int, b: int) -> int:
-    """the size of the bound table's one allocation (csrc/bsched.hip, bound_layout: columns at 256-byte offsets)"""
+    """the size of the bound table's one allocation (csrc/bs_kernels.hpp, bound_layout: columns at 256-byte offsets)"""
     al = lambda x: (x + 255) // 256 * 256                     # noqa: E731
     nb = max(b, 1)
     return sum(al(x) for x in ((n + 1) * 4, nb * 4, nb * 8, nb * 4, nb * 4, nb * L * 8, nb * 4, nb, max(n, 1) * 4))

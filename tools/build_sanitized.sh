@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/build_sanitized.sh [outdir=tools/ubench/san]
 # Host-side hardening builds (never the shipped libraries; same file names in their own directory so that $ORIGIN pairs them):
-#   libbsched.so       host code of csrc/bsched.hip with UBSAN (clang's instrumentation, gcc's libubsan as the runtime: ROCm's clang
+#   libbsched.so       host code of csrc/bsched.hip and the tu_*.hip units (a unity build) with UBSAN (clang's instrumentation, gcc's libubsan as the runtime: ROCm's clang
 #                      ships no ubsan runtime, the handler ABI is the same) + _GLIBCXX_ASSERTIONS (bounds-checked std::vector /
 #                      std::string); device code unchanged.  Findings are printed ("runtime error: ...") and the run goes on, so
 #                      one pass lists them all; tools/r03_san.sh fails if there is any.
