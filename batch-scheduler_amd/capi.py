@@ -41,9 +41,11 @@ ABI_SYMBOLS = [
     "bs_pdb_load", "bs_pdb_members_append", "bs_pdb_allowed_apply", "bs_pdb_read",
     "bs_preempt_commit_gang", "bs_preempt_commit_gang_flat", "bs_preempt_gang_read",
     "bs_seq_expire", "bs_seq_expire_flat", "bs_seq_waiting_read",
+    "bs_wait_load", "bs_wait_count", "bs_wait_ids", "bs_wait_read", "bs_wait_park", "bs_wait_release", "bs_wait_expire", "bs_wait_forget",
 ]
 
 SEQ_EXPIRE_DENY, SEQ_EXPIRE_ALL = 1, 2    # bs_seq_expire flags
+WAIT_MAX = 1 << 24                        # BS_WAIT_MAX: rows and ids of the wait table
 
 BS_BOUND_NODES = soa.BS_BOUND_NODES     # bs_bound_apply_ex: the delta also moves the node requests
 
@@ -232,6 +234,14 @@ def load_library(path: str | None = None):
     L.bs_seq_expire.argtypes = [vp, u32, P(u32), u32, P(SeqExpireOut)]
     L.bs_seq_expire_flat.argtypes = [vp, u32, P(u32), u32, u32, P(u32), P(u32), P(u32), u32, P(u32), P(u32), P(u32)]
     L.bs_seq_waiting_read.argtypes = [vp, u32, P(i32)]
+    L.bs_wait_load.argtypes = [vp, u32, P(u32), P(i32), P(C.c_int64), P(u32)]
+    L.bs_wait_count.argtypes = [vp, P(u32)]
+    L.bs_wait_ids.argtypes = [vp, P(u32)]
+    L.bs_wait_read.argtypes = [vp, P(u32), P(u32), P(i32), P(C.c_int64), P(u32)]
+    L.bs_wait_park.argtypes = [vp, u32, P(u32), P(u32), P(u32), P(u32)]
+    L.bs_wait_release.argtypes = [vp, u32, P(u32), u32, P(u32), P(u32), P(u32), P(u32)]
+    L.bs_wait_expire.argtypes = [vp, u32, P(u32), u32, u32, P(u32), P(u32), P(u32), P(u32), P(u32)]
+    L.bs_wait_forget.argtypes = [vp, u32, P(u32), P(u32)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:
@@ -600,6 +610,84 @@ class Context:
         wn = np.full(max(p, 1), -1, np.int32)
         self._chk(self._lib.bs_seq_waiting_read(self._h, p, wn.ctypes.data_as(C.POINTER(C.c_int32))), "bs_seq_waiting_read")
         return wn[:p]
+
+    # -- the resident Permit-wait table
+    def wait_load(self, node=(), group=(), req=None, req_present=None, w: int | None = None):
+        """bs_wait_load: a fresh table of waiting pods (node [w], group [w], req [L][w], req_present [w]); no arguments: the empty table.
+        w overrides the row count handed to the library (tests of the capacity check)."""
+        nd = np.ascontiguousarray(np.asarray(node, np.uint32).reshape(-1))
+        n = int(nd.size)
+        gr = np.ascontiguousarray(np.asarray(group, np.int32).reshape(-1))
+        rq = np.zeros((self.L, n), np.int64) if req is None else np.ascontiguousarray(np.asarray(req, np.int64).reshape(self.L, n))
+        pr = np.zeros(n, np.uint32) if req_present is None else np.ascontiguousarray(np.asarray(req_present, np.uint32).reshape(-1))
+        assert gr.size == n and pr.size == n
+        pad = lambda a: a if a.size else np.zeros(1, a.dtype)
+        self._chk(self._lib.bs_wait_load(self._h, n if w is None else int(w), _u32p(pad(nd)), pad(gr).ctypes.data_as(C.POINTER(C.c_int32)), _i64p(pad(rq)),
+                                         _u32p(pad(pr))), "bs_wait_load")
+
+    def wait_count(self) -> int:
+        w = C.c_uint32(0)
+        self._chk(self._lib.bs_wait_count(self._h, C.byref(w)), "bs_wait_count")
+        return int(w.value)
+
+    def wait_ids(self) -> int:
+        """bs_wait_ids: the id space — rows at the last wait_load plus what wait_park added since"""
+        w = C.c_uint32(0)
+        self._chk(self._lib.bs_wait_ids(self._h, C.byref(w)), "bs_wait_ids")
+        return int(w.value)
+
+    def wait_read(self) -> dict:
+        """bs_wait_read: the table's columns in table order (ascending id): id, node, group, req [L][count], req_present"""
+        w = self.wait_count()
+        m = max(w, 1)
+        i_, nd, gr, pr = np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros(m, np.int32), np.zeros(m, np.uint32)
+        rq = np.zeros((self.L, m), np.int64) if w == 0 else np.zeros((self.L, w), np.int64)
+        self._chk(self._lib.bs_wait_read(self._h, _u32p(i_), _u32p(nd), gr.ctypes.data_as(C.POINTER(C.c_int32)), _i64p(rq), _u32p(pr)), "bs_wait_read")
+        return dict(id=i_[:w], node=nd[:w], group=gr[:w], req=rq[:, :w], req_present=pr[:w])
+
+    def wait_park(self, cap: int | None = None) -> dict:
+        """bs_wait_park: the last pass's waiting pods move into the table.  Returns first_id, n (the true count) and pod, node (at most cap
+        rows; the default holds everything: the queue length)."""
+        cap = self.pods_count() if cap is None else int(cap)
+        pod, node = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32)
+        first, n = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self._lib.bs_wait_park(self._h, cap, _u32p(pod), _u32p(node), C.byref(first), C.byref(n)), "bs_wait_park")
+        k = min(int(n.value), cap)
+        return dict(first_id=int(first.value), n=int(n.value), pod=pod[:k], node=node[:k])
+
+    def _wait_by_group(self, groups, cap, expire, flags):
+        gl = np.ascontiguousarray(np.asarray(groups, np.uint32).reshape(-1))
+        cap = self.wait_count() if cap is None else int(cap)
+        i_, nd = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32)
+        ge, gu = np.zeros(max(gl.size, 1), np.uint32), np.zeros(max(gl.size, 1), np.uint32)
+        n = C.c_uint32(0)
+        gp = _u32p(gl if gl.size else np.zeros(1, np.uint32))
+        if expire:
+            self._chk(self._lib.bs_wait_expire(self._h, int(gl.size), gp, int(flags), cap, _u32p(i_), _u32p(nd), _u32p(ge), _u32p(gu), C.byref(n)), "bs_wait_expire")
+        else:
+            self._chk(self._lib.bs_wait_release(self._h, int(gl.size), gp, cap, _u32p(i_), _u32p(nd), _u32p(ge), C.byref(n)), "bs_wait_release")
+        k = min(int(n.value), cap)
+        out = dict(n=int(n.value), id=i_[:k], node=nd[:k], group_entries=ge[: gl.size])
+        if expire:
+            out["group_unknown"] = gu[: gl.size]
+        return out
+
+    def wait_release(self, groups, cap: int | None = None) -> dict:
+        """bs_wait_release: the rows of the gangs a later pass released leave the table.  Returns n (true count), id, node (ascending id, at
+        most cap rows; the default holds the whole table) and group_entries in the caller's order."""
+        return self._wait_by_group(groups, cap, False, 0)
+
+    def wait_expire(self, groups, deny: bool = False, cap: int | None = None, flags: int | None = None) -> dict:
+        """bs_wait_expire: the Permit timeout of the listed gangs for the table's rows — they leave the table and their nodes, matched returns
+        to 0, deny=True deny-lists the groups.  As wait_release, plus group_unknown.  flags overrides the flag word built from deny."""
+        return self._wait_by_group(groups, cap, True, (SEQ_EXPIRE_DENY if deny else 0) if flags is None else flags)
+
+    def wait_forget(self, ids) -> np.ndarray:
+        """bs_wait_forget: single rows leave the table and their nodes, matched of their groups falls by 1 each.  Returns the node of each id."""
+        il = np.ascontiguousarray(np.asarray(ids, np.uint32).reshape(-1))
+        out = np.zeros(max(il.size, 1), np.uint32)
+        self._chk(self._lib.bs_wait_forget(self._h, int(il.size), _u32p(il if il.size else np.zeros(1, np.uint32)), _u32p(out)), "bs_wait_forget")
+        return out[: il.size]
 
     def read_node_requests(self):
         """bs_nodes_read: (requested [L][n], requested_present [n]) as the context holds them"""

@@ -195,6 +195,19 @@ struct bs_ctx {
   DevBuf d_sexp_nodes;               // per-node delta [L][N], key bits, dirty words: zero between calls (k_se_nodes re-zeroes what it read)
   uint32_t sexp_n = 0, sexp_l = 0;   // the layout d_sexp_nodes was zeroed for
   bool sexp_clean = false;
+  // the resident Permit-wait table (bs_wait_*, bs_wait.hpp): waiting pods that outlive their pass.  Two allocations of the same layout: the
+  // live one (wait_cur) and the twin a compaction writes into and a growing park copies into; they swap on success.  Valid while the node
+  // count and the group count are the ones it was created for.
+  bool have_wait = false;
+  uint32_t wait_w = 0, wait_ids = 0;   // rows; the id space: rows at the last bs_wait_load plus what bs_wait_park added since
+  uint32_t wait_n = 0, wait_g = 0;     // node count and group count at the load
+  DevBuf d_wait[2];
+  uint32_t wait_cap[2] = {0, 0};       // rows each allocation is laid out for (the req lane stride)
+  uint32_t wait_cur = 0;
+  DevBuf d_wait_scr;                   // per-call scratch: block totals, positions, rows, per-list results, dirty list, records
+  DevBuf d_wait_nodes;                 // per-node delta [L][N], key bits, dirty words: zero between calls (k_wt_nodes re-zeroes what it read)
+  DevBuf d_wait_gmark, d_wait_imark;   // marks by group [G] / by id [id space]: zero between calls (k_wt_finish takes them off)
+  bool wait_nodes_clean = false, wait_gmark_clean = false, wait_imark_clean = false;
   uint32_t table_slots = 0, table_mcap = 0;
 
   uint32_t rank = 0, nranks = 1;

@@ -29,6 +29,7 @@
 #include "tu_fast.hip"
 #include "tu_seq.hip"
 #include "tu_seq_expire.hip"
+#include "tu_wait.hip"
 #include "tu_preempt.hip"
 #endif
 

@@ -569,7 +569,8 @@ int bs_nodes_read(bs_ctx* ctx, int64_t* requested, uint32_t* requested_present);
  *                   requests follows as after bs_nodes_assume.
  *   group state     for every expired group: matched = 0 — EVERY MatchedPodNodes entry is deleted, those of earlier cycles included,
  *                   which have no queue index and whose nodes the library never knew: group_earlier[i] tells the caller how many of
- *                   those it has to take off the nodes itself —; BS_GROUP_DENIED is set with BS_SEQ_EXPIRE_DENY; BS_GROUP_SCHEDULED_LATCH
+ *                   those it has to take off the nodes itself (a caller that keeps them in the resident wait table, bs_wait_park below,
+ *                   expires them with bs_wait_expire instead) —; BS_GROUP_DENIED is set with BS_SEQ_EXPIRE_DENY; BS_GROUP_SCHEDULED_LATCH
  *                   (never cleared, core.go:305) and BS_GROUP_PHASE_CLOSED keep their value; the chain becomes empty, so a second expire
  *                   of the group forgets nothing and changes nothing.  A later bs_batch_run, bs_seq_run or bs_find_max_pg sees what it
  *                   would see after a bs_groups_apply of these values.
@@ -598,6 +599,69 @@ typedef struct bs_seq_expire_out {
 } bs_seq_expire_out;
 int bs_seq_expire(bs_ctx* ctx, uint32_t count, const uint32_t* group, uint32_t flags, bs_seq_expire_out* out);
 int bs_seq_waiting_read(bs_ctx* ctx, uint32_t p, int32_t* wait_node /*[p]*/);  /* node a pod of the last pass still waits on, else -1 */
+
+/* ---- the resident Permit-wait table: waiting pods that outlive their pass -----------------------------------------------------
+ * The waiting state above lasts one cycle: it is keyed by queue index and ends with the next bs_pods_apply.  A gang waits at Permit for
+ * seconds (core.go:284-309: every entry of MatchedPodNodes carries its own TTL, :289-290), a cycle lasts microseconds.  The wait table is
+ * MatchedPodNodes across cycles, minus the clock, which stays with the caller as every TTL here does: one row per waiting pod, resident
+ * on the device beside the pending queue and the bound-pod table.  A cycle then reads
+ *   bs_pods_apply -> bs_seq_run -> bs_wait_release(released_group) -> bs_wait_park -> bind / bs_bound_apply -> next cycle;
+ * on a gang's timeout bs_wait_expire, on a waiting pod's own end bs_wait_forget.
+ *   the table       rows in ascending id.  id: never reused before the next bs_wait_load.  group: 0 <= group < g.  node: < n.  req[L]: as
+ *                   the pass's assume step counted the pod: lanes 0..2 the request, the pods lane 1, a scalar lane the request where the
+ *                   pod's present bit is set, else 0.  req_present: masked to the context's scalar lanes.  At most BS_WAIT_MAX rows and ids.
+ *   validity        the table remembers the node count and the group count it was created for.  While either differs from bs_nodes_count
+ *                   or the loaded group count, every call except bs_wait_load, bs_wait_count and bs_wait_ids answers BS_ERR_STATE.  This
+ *                   is a test of the COUNTS, as for the bound-pod table: list surgery that keeps a count passes it and the rows then name
+ *                   other nodes or groups — the caller's hazard.  The way through list surgery is bs_wait_read, a remap on the host and
+ *                   bs_wait_load; there is no device remap.  Single-rank contexts only (BS_ERR_STATE otherwise, as bs_seq_run).
+ *   bs_wait_load    a fresh snapshot (a restart, or after list surgery).  Needs nodes and groups loaded.  w = 0 is valid and is how a
+ *                   context gets its empty table.  The ids are 0 .. w - 1 and the id space becomes w.  req is [L][w]; the rows are stored
+ *                   as the table stores them (the pods lane becomes 1, a scalar lane without a present bit 0).  Node requests and groups
+ *                   are untouched: the caller's node snapshot already counts these pods.  Validated as a whole: a node >= n, a group
+ *                   outside 0 .. g - 1 (BS_ERR_INVALID), w > BS_WAIT_MAX (BS_ERR_CAPACITY).
+ *   bs_wait_count / bs_wait_ids   rows; the id space.  BS_ERR_STATE before the first bs_wait_load.
+ *   bs_wait_read    the columns of all bs_wait_count rows, in table order; req is [L][count].
+ *   bs_wait_park    needs bs_seq_expire's window open and a table.  Every pod the last pass left waiting moves into the table, in
+ *                   ascending queue index; the k-th gets id ids + k.  Its request lanes and present bits come from the resident queue,
+ *                   its node from the chain.  pod[k] / node[k] report the first min(n, cap) rows, *n_out is the true count,
+ *                   *first_id_out the id space before the call.  The chains become empty as bs_seq_expire leaves them: afterwards
+ *                   bs_seq_waiting_read answers -1 for these pods and a bs_seq_expire of their groups forgets nothing.  matched, the group
+ *                   flags and the node requests do not change: the pods still wait and still hold their room (core.go:303-309).  The
+ *                   queue does not change: the caller removes the parked and the released pods with the bs_pods_apply it issues anyway.
+ *                   All or nothing: ids + n > BS_WAIT_MAX is BS_ERR_CAPACITY with nothing changed.  A second park parks nothing.
+ *   bs_wait_release for the gangs a later pass released (bs_seq_out.released_group): batchscheduler.go:292-333 for the entries the pass
+ *                   could not name.  Every row of a listed group leaves the table by a stable compaction; survivors keep ids and order.
+ *                   The rows (id, node) come back in ascending id; group_entries[i] counts the rows of group[i], in the caller's order.
+ *                   Node requests and group state are not touched: the pass already did matched = 0 and PostBind (core.go:327), and the
+ *                   pods stay on their nodes because they bind there.
+ *   bs_wait_expire  controller.go:322-332 for the table's rows: the twin of bs_seq_expire.  The rows of the listed groups leave the table.
+ *                   Each leaves its node by bs_seq_expire's rule: lanes cpu / memory / ephemeral lose the request, the pods lane loses 1,
+ *                   a scalar lane the row has a present bit for loses the request AND KEEPS its node bit, every other scalar lane keeps
+ *                   its word and its bit.  Sums wrap.  Rows of several gangs on one node leave together.  The derived node data and the
+ *                   host mirror follow as after bs_nodes_assume.  matched = 0 for every listed group, with or without rows;
+ *                   BS_GROUP_DENIED is set with BS_SEQ_EXPIRE_DENY (the only flag: other bits are BS_ERR_INVALID).  group_unknown[i] =
+ *                   matched before the call minus group_entries[i], in uint32 arithmetic: 0 for a caller that parks every cycle.
+ *                   findMaxPG and the epoch analysis follow as after bs_groups_apply.
+ *   bs_wait_forget  one row's own end: its MatchedPodNodes TTL (core.go:289-290), or the pod deleted while it waited.  The ids must be live
+ *                   and distinct.  Each row leaves the table and its node (the rule above); matched of its group falls by 1 per row, in
+ *                   uint32 arithmetic.  There is no deny.  node_out[i] = the node of id[i].
+ *   errors          everything is found on the host, or by a device check that runs before anything resident is written; on any error
+ *                   nothing changes.  BS_ERR_INVALID: a group >= g, a group or an id listed twice, a dead or unknown id, a NULL array
+ *                   with a count or a capacity above 0.  BS_ERR_STATE: no table, stale counts, no window (park), a sharded context.  An
+ *                   empty list is BS_OK and launches nothing.  Host work is proportional to the lists; the device makes one pass over the
+ *                   table.  All calls are synchronous, and their arguments are flat: this form is also the cgo form. */
+#define BS_WAIT_MAX (1u << 24)   /* rows and ids of the wait table */
+int bs_wait_load(bs_ctx* ctx, uint32_t w, const uint32_t* node, const int32_t* group, const int64_t* req /*[L][w]*/, const uint32_t* req_present);
+int bs_wait_count(const bs_ctx* ctx, uint32_t* w_out);
+int bs_wait_ids(const bs_ctx* ctx, uint32_t* ids_out);
+int bs_wait_read(bs_ctx* ctx, uint32_t* id, uint32_t* node, int32_t* group, int64_t* req /*[L][count]*/, uint32_t* req_present);
+int bs_wait_park(bs_ctx* ctx, uint32_t cap, uint32_t* pod, uint32_t* node, uint32_t* first_id_out, uint32_t* n_out);
+int bs_wait_release(bs_ctx* ctx, uint32_t count, const uint32_t* group, uint32_t cap, uint32_t* id, uint32_t* node, uint32_t* group_entries /*[count]*/,
+                    uint32_t* n_out);
+int bs_wait_expire(bs_ctx* ctx, uint32_t count, const uint32_t* group, uint32_t flags, uint32_t cap, uint32_t* id, uint32_t* node,
+                   uint32_t* group_entries /*[count]*/, uint32_t* group_unknown /*[count]*/, uint32_t* n_out);
+int bs_wait_forget(bs_ctx* ctx, uint32_t count, const uint32_t* id, uint32_t* node_out /*[count]*/);
 
 /* ---- gang-aware preemption: the victim search, batched ------------------------------------------------------------------
  * The path of a pod that passed PreFilter and found no node.  The plugin's one hook there is PreFilterExtensions.RemovePod

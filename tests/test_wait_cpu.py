@@ -1,0 +1,299 @@
+"""The resident Permit-wait table (bs_wait_*) on the CPU: the array model of tests/wait_ref.py pinned on tests/seq_expire_ref.expire (park then
+expire == bs_seq_expire's statement, which is itself pinned on the C oracle and the object-level replay), two scheduling cycles against the
+oracle, hand known answers (tests/golden/wait_hand_kats.json), the host-side list checks (csrc/bs_wait_list.hpp) compiled alone under
+ASan + UBSan, and the new translation unit's place in the build.  No GPU."""
+import importlib
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import naive_ref as nv
+import seq_expire_ref as ser
+import wait_ref as wr
+from test_seq_expire_cpu import scene
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+SEEDS = range(240)
+PROPS = ("two_of_one_gang_on_one_node", "two_gangs_on_one_node", "key_created_by_assume", "listed_group_without_entry", "group_enters_with_matched")
+
+
+def park_then_expire(orc, soa, seed):
+    """one scene: model park + model expire of a group list == ser.expire of the same list -> the property counters of this scene"""
+    sc, closed = scene(seed)
+    rng = np.random.default_rng(seed + 9)
+    nodes, fit, groups, pods, gidx = nv.to_soa(sc["nodes"], sc["cache"], sc["pods"], sc["names"], sc["n_classes"], sc["denied"], sc["permitted"])
+    for nm in closed:
+        groups.flags[gidx[nm]] |= soa.GROUP_PHASE_CLOSED
+    s = orc.seq_replay(nodes, fit, groups, pods, soa.STAGE_PREFILTER)
+    wait, created = ser.waiting_after_pass(nodes, fit, groups, pods, s)
+    a = ser.State(s["nodes"].requested, s["nodes"].requested_present, s["groups"].matched, s["groups"].flags, wait)
+    b = a.copy()
+    G, S, N = groups.g, nodes.lanes - 4, nodes.n
+    glist = [int(g) for g in rng.permutation(G)[: int(rng.integers(0, G + 1))]]
+    deny = bool(seed % 2)
+    wpods = [int(i) for i in np.nonzero(wait >= 0)[0] if int(pods.group[i]) in glist]
+    on_node = {}
+    for i in wpods:
+        on_node.setdefault(int(wait[i]), []).append(int(pods.group[i]))
+    prop = dict(
+        two_of_one_gang_on_one_node=any(len(v) != len(set(v)) for v in on_node.values()),
+        two_gangs_on_one_node=any(len(set(v)) > 1 for v in on_node.values()),
+        key_created_by_assume=any((i, s_) in created for i in wpods for s_ in range(S)),
+        listed_group_without_entry=any(not np.any((pods.group == g) & (wait >= 0)) for g in glist),
+        group_enters_with_matched=any(int(groups.matched[g]) > 0 for g in glist),
+    )
+    want = ser.expire(a, pods, groups=glist, deny=deny)
+    tab = wr.load(N, G, S)
+    pk = wr.park(b, tab, pods)
+    assert pk["first_id"] == 0 and pk["n"] == int((wait >= 0).sum()) and np.array_equal(pk["pod"], np.nonzero(wait >= 0)[0])
+    assert np.array_equal(pk["node"], wait[wait >= 0]) and not np.any(b.wait_node >= 0) and tab.w == pk["n"] == tab.ids
+    assert np.array_equal(b.requested, s["nodes"].requested) and np.array_equal(b.matched, s["groups"].matched), "park moves nothing but the record"
+    got = wr.expire(b, tab, glist, deny=deny)
+    assert np.array_equal(got["group_entries"], want["group_pods"]) and np.array_equal(got["group_unknown"], want["group_earlier"]), f"seed {seed}"
+    rows = sorted(zip(pk["pod"][got["id"] - pk["first_id"]].tolist(), got["node"].tolist()))
+    assert rows == sorted(zip(want["pod"].tolist(), want["node"].tolist())), f"seed {seed}: rows"
+    assert np.array_equal(got["id"], np.sort(got["id"])), "rows ascend by id"
+    assert np.array_equal(a.requested, b.requested) and np.array_equal(a.requested_present, b.requested_present), f"seed {seed}: node requests"
+    assert np.array_equal(a.matched, b.matched) and np.array_equal(a.flags, b.flags), f"seed {seed}: group state"
+    assert not np.any(np.isin(tab.group, glist)) and tab.w == pk["n"] - got["n"]
+    return prop
+
+
+def test_park_then_expire_equals_seq_expire_and_the_scenes_cover_the_cases(orc, soa):
+    total = dict.fromkeys(PROPS, 0)
+    for seed in SEEDS:
+        for k, v in park_then_expire(orc, soa, seed).items():
+            total[k] += int(bool(v))
+    print(total)
+    assert len(SEEDS) == 240
+    for k in PROPS:
+        assert total[k] >= 10, (k, total)
+
+
+# ---- two cycles ------------------------------------------------------------------------------------------------------------------------
+def two_cycles(orc, soa, seed):
+    """-> everything test_gpu_wait.py replays on the device: the scenes, the oracle's two passes and the model's results"""
+    nodes, fit, groups, pods1, pods2, completes = wr.two_cycle_scene(soa, seed)
+    S, N, G = nodes.lanes - 4, nodes.n, groups.g
+    s1 = orc.seq_replay(nodes, fit, groups, pods1, soa.STAGE_PREFILTER)
+    st = ser.State.after_pass(nodes, fit, groups, pods1, s1)
+    assert s1["n_released"] == 0
+    wait1 = st.wait_node.copy()
+    tab = wr.load(N, G, S)
+    pk1 = wr.park(st, tab, pods1)
+    queue2 = wr.second_queue(soa, pods1, pk1["pod"], pods2)
+    s2 = orc.seq_replay(s1["nodes"], fit, s1["groups"], queue2, soa.STAGE_PREFILTER, leader=s1["leader"])
+    st2 = ser.State.after_pass(s1["nodes"], fit, s1["groups"], queue2, s2)
+    return dict(nodes=nodes, fit=fit, groups=groups, pods1=pods1, pods2=pods2, completes=completes, s1=s1, s2=s2, wait1=wait1, tab=tab, pk1=pk1, queue2=queue2, st2=st2)
+
+
+@pytest.mark.parametrize("seed", range(64))
+def test_two_cycles_release_names_the_first_cycles_nodes_and_expire_takes_both_cycles_pods_off(seed, orc, soa):
+    c = two_cycles(orc, soa, seed)
+    pods1, queue2, s2, st2, tab, pk1, wait1 = c["pods1"], c["queue2"], c["s2"], c["st2"], c["tab"], c["pk1"], c["wait1"]
+    N, G = c["nodes"].n, c["groups"].g
+    released = s2["released_group"].tolist()
+    before = tab.copy()
+    rel = wr.release(tab, released, N, G)
+    want = [(int(i), int(wait1[i])) for i in np.nonzero(wait1 >= 0)[0] if int(pods1.group[i]) in released]
+    assert list(zip(pk1["pod"][rel["id"] - pk1["first_id"]].tolist(), rel["node"].tolist())) == want, "release: pass 1's (pod -> node) of the released gangs"
+    keep = ~np.isin(before.group, released)
+    assert np.array_equal(tab.id, before.id[keep]) and np.array_equal(tab.node, before.node[keep]) and np.array_equal(tab.req, before.req[:, keep]), "the table keeps the others"
+    # every entry the pass released is either one of its own pods, one the table named, or one that entered the first cycle in matched
+    own = {g: int(((queue2.group == g) & (s2["pod_node"] >= 0)).sum()) for g in released}
+    assert s2["released_pods"].tolist() == [own[g] + int(e) + int(c["groups"].matched[g]) for g, e in zip(released, rel["group_entries"])]
+    # ---- cycle 2's own waiting pods are parked, then a gang that is still short times out
+    wait2 = st2.wait_node.copy()
+    pk2 = wr.park(st2, tab, queue2)
+    assert pk2["first_id"] == pk1["n"] and tab.ids == pk1["n"] + pk2["n"]
+    short = [g for g in range(G) if g not in released and np.any(tab.group == g)]
+    if not short:
+        return
+    h = short[seed % len(short)]
+    ex = wr.expire(st2, tab, [h], deny=True)
+    L = c["nodes"].lanes
+    want_req = s2["nodes"].requested.copy()
+    for podset, wait in ((pods1, wait1), (queue2, wait2)):      # recomputed from the pods' own request arrays, not from the table
+        for i in np.nonzero((wait >= 0) & (podset.group == h))[0]:
+            k = int(wait[i])
+            for j in range(L):
+                if j < 3:
+                    want_req[j, k] = ser.w64(int(want_req[j, k]) - int(podset.req[j, i]))
+                elif j == 3:
+                    want_req[j, k] = ser.w64(int(want_req[j, k]) - 1)
+                elif (int(podset.req_present[i]) >> (j - 4)) & 1:
+                    want_req[j, k] = ser.w64(int(want_req[j, k]) - int(podset.req[j, i]))
+    assert np.array_equal(st2.requested, want_req), "expire: pass 2's node requests minus the gang's requests"
+    assert np.array_equal(st2.requested_present, s2["nodes"].requested_present) and st2.matched[h] == 0 and st2.flags[h] & wr.DENIED
+    assert ex["group_unknown"].tolist() == [int(c["groups"].matched[h])] and ex["n"] == int(((wait1 >= 0) & (pods1.group == h)).sum() + ((wait2 >= 0) & (queue2.group == h)).sum())
+
+
+def test_the_two_cycle_scenes_release_some_gangs_and_leave_others_short(orc, soa):
+    n_rel = n_short = n_both = 0
+    for seed in range(64):
+        c = two_cycles(orc, soa, seed)
+        rel = set(c["s2"]["released_group"].tolist())
+        short = set(c["tab"].group.tolist()) - rel
+        n_rel += bool(rel)
+        n_short += bool(short)
+        n_both += bool(rel and short)
+    assert n_rel >= 40 and n_short >= 40 and n_both >= 30, (n_rel, n_short, n_both)
+
+
+# ---- hand known answers ------------------------------------------------------------------------------------------------------------------
+def _kats():
+    return json.load(open(os.path.join(HERE, "golden", "wait_hand_kats.json")))["cases"]
+
+
+def test_the_hand_scenes_are_small_and_cite_the_reference():
+    cases = _kats()
+    assert len(cases) >= 8
+    text = " ".join(c["cites"] for c in cases)
+    for ref in ("core.go:289-303", "controller.go:322-332", "batchscheduler.go:292-333"):
+        assert ref in text, ref
+    assert all(2 <= len(c["requested"][0]) <= 4 for c in cases)
+    names = [c["name"] for c in cases]
+    assert "forget_takes_matched_through_zero" in names and "expire_matched_exceeds_entries" in names
+
+
+@pytest.mark.parametrize("case", _kats(), ids=lambda c: c["name"])
+def test_hand_known_answers(case):
+    """scenes small enough to do by hand; the expected values were written down from the reference lines each case cites, not from a run"""
+    assert case["cites"]
+    S = case["S"]
+    L = 4 + S
+    N, G = len(case["requested_present"]), len(case["matched"])
+    wn = np.array(case.get("wait_node", []), np.int32)
+    st = ser.State(np.array(case["requested"], np.int64).reshape(L, N), np.array(case["requested_present"], np.uint32), np.array(case["matched"], np.uint32),
+                   np.array(case["flags"], np.uint8), wn)
+    t = case["table"]
+    tab = wr.load(N, G, S, t["node"], t["group"], np.array(t["req"], np.int64).reshape(L, -1), t["req_present"])
+    pods = None
+    if "pods" in case:
+        p = case["pods"]
+        n = len(p["group"])
+        pods = nv.soa.Pods(np.array(p["group"], np.int32), np.array(p["req"], np.int64).reshape(L, n), np.array(p["req_present"], np.uint32), np.zeros(n, np.uint32),
+                           np.zeros(n, np.uint64), np.zeros(n, np.uint8))
+    for op in case["ops"]:
+        if op["op"] == "park":
+            res = wr.park(st, tab, pods)
+        elif op["op"] == "release":
+            res = wr.release(tab, op["groups"], N, G)
+        elif op["op"] == "expire":
+            res = wr.expire(st, tab, op["groups"], deny=op["deny"])
+        else:
+            res = dict(node_out=wr.forget(st, tab, op["ids"]))
+        for k, v in op["result"].items():
+            assert np.asarray(res[k]).tolist() == v, (op["op"], k)
+    e = case["expect"]
+    assert st.requested.tolist() == e["requested"] and st.requested_present.tolist() == e["requested_present"]
+    assert st.matched.tolist() == e["matched"] and st.flags.tolist() == e["flags"]
+    assert tab.id.tolist() == e["table_id"] and tab.node.tolist() == e["table_node"] and tab.group.tolist() == e["table_group"]
+    if "table_req" in e:
+        assert tab.req.tolist() == e["table_req"] and tab.req_present.tolist() == e["table_req_present"]
+    if "wait_node" in e:
+        assert st.wait_node.tolist() == e["wait_node"]
+
+
+def test_the_model_refuses_what_the_header_refuses_and_changes_nothing():
+    st = ser.State(np.zeros((4, 3), np.int64), np.zeros(3, np.uint32), np.array([2, 1], np.uint32), np.zeros(2, np.uint8), np.zeros(0, np.int32))
+    tab = wr.load(3, 2, 0, [0, 2, 1], [0, 1, 0])
+    wr.forget(st, tab, [1])
+    before = (tab.copy(), st.copy())
+    for want, fn in [(wr.INVALID, lambda: wr.release(tab, [0, 2], 3, 2)), (wr.INVALID, lambda: wr.release(tab, [1, 1], 3, 2)),
+                     (wr.INVALID, lambda: wr.expire(st, tab, [0], flags=2)), (wr.INVALID, lambda: wr.forget(st, tab, [1])),
+                     (wr.INVALID, lambda: wr.forget(st, tab, [0, 0])), (wr.INVALID, lambda: wr.forget(st, tab, [3])),
+                     (wr.STATE, lambda: wr.release(tab, [0], 4, 2)), (wr.STATE, lambda: wr.release(None, [0], 3, 2)),
+                     (wr.INVALID, lambda: wr.load(3, 2, 0, [3], [0])), (wr.INVALID, lambda: wr.load(3, 2, 0, [0], [2])),
+                     (wr.CAPACITY, lambda: wr.load(3, 2, 0, w=wr.WAIT_MAX + 1))]:
+        with pytest.raises(wr.WaitError) as e:
+            fn()
+        assert e.value.status == want
+        assert np.array_equal(tab.id, before[0].id) and np.array_equal(st.matched, before[1].matched) and np.array_equal(st.requested, before[1].requested)
+
+
+# ---- the host-side list checks, alone, under sanitizers ---------------------------------------------------------------------------------
+def test_list_checks_under_sanitizers(tmp_path):
+    """csrc/bs_wait_list.hpp compiled alone with tests/native/wait_list_main.cpp under ASan + UBSan, against the rules in Python"""
+    exe = str(tmp_path / "wait_list")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(ROOT, "batch-scheduler_amd", "csrc"), os.path.join(HERE, "native", "wait_list_main.cpp"), "-o", exe], check=True)
+    rng = np.random.default_rng(31)
+    lines, want = [], []
+    for _ in range(400):
+        bound, count = int(rng.integers(0, 9)), int(rng.integers(0, 7))
+        null = int(rng.random() < 0.2)
+        lst = rng.integers(0, bound + 2, size=count).tolist() if rng.random() < 0.5 else rng.permutation(max(bound, 1))[:count].tolist()
+        count = len(lst)
+        lines.append(" ".join(map(str, ["L", bound, null, count, *lst])))
+        if not count:
+            code = 0
+        elif null:
+            code = 2
+        elif any(x >= bound for x in (lst[: bound + 1] if count > bound else lst)):
+            code = 3
+        elif count > bound or len(set(lst)) != len(lst):
+            code = 4
+        else:
+            code = 0
+        want.append(code)
+    for flags in (0, 1, 2, 3, 0x80000000, 0x80000001):
+        lines.append(f"F {flags}")
+        want.append(1 if flags & ~1 else 0)
+    for _ in range(200):
+        n, g, w = int(rng.integers(0, 5)), int(rng.integers(0, 4)), int(rng.integers(0, 6))
+        null = int(rng.random() < 0.15)
+        node = rng.integers(0, n + 1 + (rng.random() < 0.3), size=w).tolist()
+        group = rng.integers(-1 if rng.random() < 0.3 else 0, g + (rng.random() < 0.3) + 1, size=w).tolist()
+        lines.append(" ".join(map(str, ["W", n, g, null, w, *node, *group])))
+        code = 0
+        if w and null:
+            code = 2
+        elif w:
+            for i in range(w):
+                if node[i] >= n:
+                    code = 5
+                    break
+                if group[i] < 0 or group[i] >= g:
+                    code = 6
+                    break
+        want.append(code)
+    out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout.split()
+    assert [int(x) for x in out] == want
+    assert all(want.count(c) >= 5 for c in (0, 2, 3, 4, 5, 6)), [want.count(c) for c in range(7)]
+    # a count far above the bound with every index in range: answered "twice" without a copy of the list
+    out = subprocess.run([exe], input="B 3 3000000000 0 1 2 1\nB 3 3000000000 0 1 2 3\n", capture_output=True, text=True, check=True).stdout.split()
+    assert out == ["4", "3"]
+
+
+# ---- the new unit's place in the build ---------------------------------------------------------------------------------------------------
+def test_the_wait_unit_is_built_linked_and_lists_every_header_it_reaches():
+    build = importlib.import_module("batch-scheduler_amd.build")
+    from test_build_units_cpu import closure, MAIN_HEADERS
+    assert list(build.LATER_UNITS) == ["tu_wait.hip"] and build.ALL_SOURCES == build.SOURCES + ["tu_wait.hip"]
+    reached = closure("tu_wait.hip")
+    assert not reached - {os.path.normpath(h) for h in build.LATER_UNITS["tu_wait.hip"]}, sorted(reached)
+    assert {"bs_wait.hpp", "bs_wait_list.hpp"} <= reached and not MAIN_HEADERS & reached
+    assert not {"bs_wait.hpp", "bs_wait_list.hpp"} & closure("bsched.hip") and not {"bs_wait.hpp"} & closure("tu_seq.hip") and not {"bs_wait.hpp"} & closure("tu_seq_expire.hip")
+    assert '#include "tu_wait.hip"' in open(os.path.join(build.CSRC, "bsched.hip")).read(), "the unity build includes the unit"
+
+
+def test_the_wait_kernels_use_no_scratch_and_live_in_a_unit_of_their_own():
+    """k_wt_move / k_wt_nodes / k_wt_gather <S>, S = 0..12, and the six lane-free kernels: no scratch, one unit, and that unit emits neither
+    k_seq_pass nor a k_se_* kernel"""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources
+    all_k = kernel_resources.resources()
+    res = {k: v for k, v in all_k.items() if "k_wt_" in k}
+    assert len(res) == 3 * 13 + 6, sorted(res)
+    for fam in ("k_wt_move", "k_wt_nodes", "k_wt_gather"):
+        assert sum(fam in k for k in res) == 13, fam
+    for k, v in res.items():
+        assert v["scratch"] == 0, (k, v)
+    units = {v["unit"] for v in res.values()}
+    assert len(units) == 1 and units.isdisjoint({v["unit"] for k, v in all_k.items() if "k_seq_pass" in k or "k_se_" in k})
