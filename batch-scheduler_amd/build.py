@@ -35,7 +35,7 @@ SOURCES = list(UNITS)
 # the units that came after those five, kept in a table of their own: tests/test_build_units_cpu.py holds UNITS and SOURCES to exactly the five
 # above, tests/test_wait_cpu.py holds this table to the include graph in the same way.  Everything below builds and links ALL_UNITS.
 LATER_UNITS = {
-    "tu_wait.hip": _SEQ + ["bs_wait.hpp", "bs_wait_list.hpp"],
+    "tu_wait.hip": _SEQ + ["bs_wait.hpp", "bs_wait_list.hpp", "bs_bound_nodes_replay.hpp"],
 }
 ALL_UNITS = {**UNITS, **LATER_UNITS}
 ALL_SOURCES = list(ALL_UNITS)

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "bs_preempt_commit_gang", "bs_preempt_commit_gang_flat", "bs_preempt_gang_read",
     "bs_seq_expire", "bs_seq_expire_flat", "bs_seq_waiting_read",
     "bs_wait_load", "bs_wait_count", "bs_wait_ids", "bs_wait_read", "bs_wait_park", "bs_wait_release", "bs_wait_expire", "bs_wait_forget",
+    "bs_wait_nodes_apply",
 ]
 
 SEQ_EXPIRE_DENY, SEQ_EXPIRE_ALL = 1, 2    # bs_seq_expire flags
@@ -242,6 +243,7 @@ def load_library(path: str | None = None):
     L.bs_wait_release.argtypes = [vp, u32, P(u32), u32, P(u32), P(u32), P(u32), P(u32)]
     L.bs_wait_expire.argtypes = [vp, u32, P(u32), u32, u32, P(u32), P(u32), P(u32), P(u32), P(u32)]
     L.bs_wait_forget.argtypes = [vp, u32, P(u32), P(u32)]
+    L.bs_wait_nodes_apply.argtypes = [vp, u32, P(u32), P(u32), u32, P(u32), P(u32), P(i32), P(u32)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:
@@ -688,6 +690,23 @@ class Context:
         out = np.zeros(max(il.size, 1), np.uint32)
         self._chk(self._lib.bs_wait_forget(self._h, int(il.size), _u32p(il if il.size else np.zeros(1, np.uint32)), _u32p(out)), "bs_wait_forget")
         return out[: il.size]
+
+    def wait_nodes_apply(self, kind, index, cap: int | None = None):
+        """bs_wait_nodes_apply: the wait table follows the node-list surgery of the apply_node_deltas call(s) before it — kind and index are
+        those deltas' fields, in order.  Rows on removed nodes leave (matched of their groups falls by 1 each), the others keep their ids and
+        get their nodes' new indices.  Returns (ids, old_nodes, groups, n): the dropped rows in ascending id (at most cap; the default holds
+        the whole table) and their true number."""
+        kv = np.ascontiguousarray(np.asarray(kind, np.uint32).reshape(-1))
+        iv = np.ascontiguousarray(np.asarray(index, np.uint32).reshape(-1))
+        assert kv.size == iv.size
+        cap = self.wait_count() if cap is None else int(cap)
+        i_, nd, gr = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.int32)
+        n = C.c_uint32(0)
+        self._chk(self._lib.bs_wait_nodes_apply(self._h, int(kv.size), _u32p(kv) if kv.size else None, _u32p(iv) if iv.size else None, cap,
+                                                _u32p(i_) if cap else None, _u32p(nd) if cap else None,
+                                                gr.ctypes.data_as(C.POINTER(C.c_int32)) if cap else None, C.byref(n)), "bs_wait_nodes_apply")
+        k = min(int(n.value), cap)
+        return i_[:k].copy(), nd[:k].copy(), gr[:k].copy(), int(n.value)
 
     def read_node_requests(self):
         """bs_nodes_read: (requested [L][n], requested_present [n]) as the context holds them"""

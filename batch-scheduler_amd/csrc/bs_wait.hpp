@@ -28,6 +28,14 @@
 //   k_wt_gather<S>  park: one thread per pod of the queue; a waiting pod writes its row at the table's tail (W + its rank in queue order):
 //                   id = ids + rank, the request lanes from the resident queue, the node from the chain; and (pod, node) at row rank.
 //   k_wt_chains     park: every chain becomes empty as k_se_groups leaves it (head 0, the count 0, kSeqHasRecord kept).
+// The table follows node-list surgery (bs_wait_nodes_apply) by a fourth face of the same scan, kWtByNode; its two kernels carry another
+// prefix because the k_wt_* set is counted (tests/test_wait_cpu.py):
+//   k_wn_map        one lane per row: the one binary search of the call.  rem[] holds the removed OLD nodes, ascending; lo = how many lie
+//                   below the row's node k.  nnode[e] = kWtGone when k itself is listed, else k - lo, the node's new index.  k_wt_scan1 /
+//                   k_wt_scan2 and the move read nnode[], they do not search again.
+//   k_wn_move<S>    one thread per row: a survivor is copied to its position in the twin with nnode[e] in the node column; a leaving row
+//                   writes (id, OLD node, group) at its output row and takes 1 off matched of its group (a relaxed agent-scope atomic:
+//                   many rows of one group leave from many blocks).  No marks, no node side: the node is gone.
 #pragma once
 
 #include "bs_seq.hpp"
@@ -35,7 +43,8 @@
 namespace bs {
 
 constexpr uint32_t kWtBlock = 1024;   // entries per scan block
-enum : uint32_t { kWtByGroup = 0, kWtById = 1, kWtPark = 2 };
+enum : uint32_t { kWtByGroup = 0, kWtById = 1, kWtPark = 2, kWtByNode = 3 };
+constexpr uint32_t kWtGone = 0xFFFFFFFFu;   // nnode[e] of a row whose node was removed (a node index stays below the node count)
 enum : uint32_t { kWtKept = 0, kWtLeft = 1, kWtDirty = 2, kWtErr = 3 };   // info words
 enum : uint32_t { kWtErrTwice = 1, kWtErrDead = 2 };
 
@@ -53,7 +62,7 @@ struct WaitDev {
   WaitTab src, dst;                     // the live table, and the twin the compaction writes (park: src only, its tail is written)
   uint32_t W;                           // rows of src
   uint32_t E;                           // entries the scan runs over: W, or the queue length in park mode
-  uint32_t mode;                        // kWtByGroup / kWtById / kWtPark
+  uint32_t mode;                        // kWtByGroup / kWtById / kWtPark / kWtByNode
   // the call
   const uint32_t* list;                 // [M] listed groups or ids
   uint32_t M;
@@ -83,6 +92,11 @@ struct WaitDev {
   uint32_t* nwait;                      // [G]
   int32_t* wnode;                       // [P] filled with -1, then the chains' nodes
   uint32_t P, ids;
+  // by node: the removed OLD nodes, and what k_wn_map decided per row
+  const uint32_t* rem;                  // [R] ascending, distinct
+  uint32_t R;
+  uint32_t* nnode;                      // [W] the row's new node index, kWtGone when its node is removed
+  int32_t* o_group;                     // [W] the third column of the rows
 };
 
 // survives << 32 | leaves
@@ -90,6 +104,8 @@ __device__ __forceinline__ unsigned long long wt_entry(const WaitDev& a, uint32_
   bool leaves;
   if (a.mode == kWtPark) {
     leaves = a.wnode[e] >= 0;
+  } else if (a.mode == kWtByNode) {
+    leaves = a.nnode[e] == kWtGone;
   } else {
     const uint32_t key = a.mode == kWtById ? a.src.id[e] : (uint32_t)a.src.group[e];
     leaves = key < a.mark_n && a.mark[key] != 0u;
@@ -281,6 +297,43 @@ __global__ __launch_bounds__(256) void k_wt_chains(WaitDev a) {
   if (s >= a.G) return;
   a.head[s] = 0u;
   a.nwait[s] = a.nwait[s] & kSeqHasRecord;
+}
+
+__global__ __launch_bounds__(256) void k_wn_map(WaitDev a) {
+  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+  if (e >= a.W) return;
+  const uint32_t k = a.src.node[e];
+  uint32_t lo = 0, hi = a.R;                                // the first j with rem[j] >= k: the removed nodes below k
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (a.rem[mid] < k) lo = mid + 1u;
+    else hi = mid;
+  }
+  a.nnode[e] = (lo < a.R && a.rem[lo] == k) ? kWtGone : k - lo;
+}
+
+template <int S>
+__global__ __launch_bounds__(256) void k_wn_move(WaitDev a) {
+  constexpr int L = 4 + S;
+  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+  if (e >= a.W) return;
+  const unsigned long long at = a.pos[e];
+  const uint32_t id = a.src.id[e], nn = a.nnode[e];
+  const int32_t g = a.src.group[e];
+  if (nn != kWtGone) {                                      // a survivor: the same columns but the node, its position in the twin
+    const uint32_t d = (uint32_t)(at >> 32);
+    if (d >= a.dst.stride) return;
+    a.dst.id[d] = id;
+    a.dst.group[d] = g;
+    a.dst.node[d] = nn;
+    a.dst.pres[d] = a.src.pres[e];
+#pragma unroll
+    for (int l = 0; l < L; ++l) a.dst.req[(size_t)l * a.dst.stride + d] = a.src.req[(size_t)l * a.src.stride + e];
+    return;
+  }
+  const uint32_t row = (uint32_t)at;
+  if (row < a.W) { a.o_key[row] = id; a.o_node[row] = a.src.node[e]; a.o_group[row] = g; }
+  if ((uint32_t)g < a.G) __hip_atomic_fetch_add(&a.g_matched[g], 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 }  // namespace bs

@@ -7,6 +7,7 @@
 #endif
 #include "bs_wait.hpp"
 #include "bs_wait_list.hpp"
+#include "bs_bound_nodes_replay.hpp"
 #include "bs_ctx.hpp"
 
 namespace bs {
@@ -78,6 +79,17 @@ static void launch_wait_remove(hipStream_t stream, uint32_t S, const WaitDev& a,
   hipLaunchKernelGGL(k_wt_finish, dim3(cdiv(a.M, 256)), dim3(256), 0, stream, a);
 }
 
+// the table follows node-list surgery: k_wn_map (the one search per row), the spread scan in its by-node face, k_wn_move<S>
+static void launch_wait_nodes(hipStream_t stream, uint32_t S, const WaitDev& a) {
+  const uint32_t nblk = cdiv(a.W, kWtBlock);
+  hipLaunchKernelGGL(k_wn_map, dim3(cdiv(a.W, 256)), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(k_wt_scan1, dim3(nblk), dim3(kWtBlock), 0, stream, a);
+  hipLaunchKernelGGL(k_wt_scan2, dim3(nblk), dim3(kWtBlock), 0, stream, a);
+  lanes_wide(S, [&](auto s) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wn_move<decltype(s)::value>), dim3(cdiv(a.W, 256)), dim3(256), 0, stream, a);
+  });
+}
+
 // park, first half: the chains as an array, the scan over the queue
 static void launch_wait_park_scan(hipStream_t stream, const WaitDev& a) {
   const uint32_t nblk = cdiv(a.P, kWtBlock);
@@ -106,7 +118,7 @@ static int wait_table_state(bs_ctx* c, const char* who) {
   if (const int rc = wait_single_rank(c, who)) return rc;
   if (!c->have_wait) { c->last_error = std::string(who) + ": no wait table (bs_wait_load first; w = 0 gives the empty one)"; return BS_ERR_STATE; }
   if (!c->have_nodes || !c->have_groups || c->wait_n != c->N || c->wait_g != c->G) {
-    c->last_error = std::string(who) + ": the wait table was created for another node count or group count (bs_wait_read, remap, bs_wait_load)";
+    c->last_error = std::string(who) + ": the wait table was created for another node count or group count (after node-list surgery: bs_wait_nodes_apply; else bs_wait_load)";
     return BS_ERR_STATE;
   }
   return BS_OK;
@@ -274,6 +286,18 @@ int bs_wait_park(bs_ctx* c, uint32_t cap, uint32_t* pod, uint32_t* node, uint32_
   return BS_OK;
 }
 
+// the twin a compaction writes into keeps the table's headroom
+static int wait_twin(bs_ctx* c) {
+  const uint32_t W = c->wait_w, cur = c->wait_cur, other = cur ^ 1u;
+  if (c->d_wait[other].p && c->wait_cap[other] >= std::max(W, c->wait_cap[cur])) return BS_OK;
+  const uint32_t cap = std::max(wait_room(W), c->wait_cap[cur]);
+  c->d_wait[other].release();
+  c->wait_cap[other] = 0;
+  HIPCHK(c, c->d_wait[other].reserve(wait_layout(cap, c->L).bytes));
+  c->wait_cap[other] = cap;
+  return BS_OK;
+}
+
 // The removal core behind bs_wait_release (by group), bs_wait_expire (by group, node side, group state) and bs_wait_forget (by id, node
 // side, matched - 1 per entry).  l_cnt_out / l_out_out: the per-list-position results (entries per group; unknown per group or node per id).
 static int wait_remove(bs_ctx* c, const char* who, uint32_t mode, bool node_side, bool expire, bool deny, uint32_t M, const uint32_t* list, uint32_t cap,
@@ -308,12 +332,7 @@ static int wait_remove(bs_ctx* c, const char* who, uint32_t mode, bool node_side
   const auto o_rec = cv.take<bs_node_request>(std::max<uint32_t>(rec_cap, 1));
   HIPCHK(c, c->d_wait_scr.reserve(cv.mark()));
   const uint32_t cur = c->wait_cur, other = cur ^ 1u;
-  if (!c->d_wait[other].p || c->wait_cap[other] < std::max(W, c->wait_cap[cur])) {   // the twin keeps the table's headroom
-    c->d_wait[other].release();
-    c->wait_cap[other] = 0;
-    HIPCHK(c, c->d_wait[other].reserve(wait_layout(std::max(wait_room(W), c->wait_cap[cur]), L).bytes));
-    c->wait_cap[other] = std::max(wait_room(W), c->wait_cap[cur]);
-  }
+  if ((rc = wait_twin(c))) return rc;
   void* base = c->d_wait_scr.p;
   void* nb = c->d_wait_nodes.p;
   const GroupsDev gr = groups_dev(c);
@@ -432,5 +451,94 @@ int bs_wait_forget(bs_ctx* c, uint32_t count, const uint32_t* id, uint32_t* node
   if (const int bad = wait_list_check(c->wait_ids, count, id)) { c->last_error = std::string("bs_wait_forget: ") + wait_list_text(bad); return BS_ERR_INVALID; }
   if (!count) return BS_OK;
   return wait_remove(c, "bs_wait_forget", kWtById, true, false, false, count, id, 0, nullptr, nullptr, nullptr, node_out, nullptr);
+}
+
+// The table follows the node list: the host replays the deltas on the node count the table was made for (bs_bound_nodes_replay.hpp, the
+// bound table's replay: O(count)) and hands the device the sorted removed OLD nodes; one pass drops the rows on them and renumbers the rest.
+int bs_wait_nodes_apply(bs_ctx* c, uint32_t count, const uint32_t* kind, const uint32_t* index, uint32_t cap, uint32_t* id, uint32_t* node, int32_t* group,
+                        uint32_t* n_out) {
+  if (!c) return BS_ERR_INVALID;
+  if (!n_out || (count && (!kind || !index)) || (cap && (!id || !node || !group))) {
+    c->last_error = "bs_wait_nodes_apply: n_out is NULL, or an array is NULL with a count or capacity above 0";
+    return BS_ERR_INVALID;
+  }
+  int rc = wait_single_rank(c, "bs_wait_nodes_apply");
+  if (rc) return rc;
+  if (!c->have_wait) { c->last_error = "bs_wait_nodes_apply: no wait table (bs_wait_load first; w = 0 gives the empty one)"; return BS_ERR_STATE; }
+  if (!c->have_nodes || !c->have_groups || c->wait_g != c->G) {
+    c->last_error = "bs_wait_nodes_apply: nodes or groups are not loaded, or the wait table was created for another group count";
+    return BS_ERR_STATE;
+  }
+  NodeReplay rp;
+  if (bound_nodes_replay(c->wait_n, count, kind, index, rp)) {
+    c->last_error = "bs_wait_nodes_apply: a kind outside UPDATE / APPEND / REMOVE, or an index at or beyond the node count at its point of the replay";
+    return BS_ERR_INVALID;
+  }
+  if (rp.n_new != c->N) { c->last_error = "bs_wait_nodes_apply: the replay does not end at the node count: not the list bs_nodes_apply got"; return BS_ERR_STATE; }
+  const uint32_t W = c->wait_w, R = (uint32_t)rp.removed.size(), G = c->G;
+  *n_out = 0;
+  if (!R || !W) {                                           // no old node left, or no row to sit on one: nothing moves
+    c->wait_n = rp.n_new;
+    return BS_OK;
+  }
+  if ((rc = use_device(c))) return rc;
+  if ((rc = settle_pending(c))) return rc;
+  Carve cv;
+  const auto o_info = cv.take<uint32_t>(4);
+  const auto o_rem = cv.take<uint32_t>(R);
+  const auto o_nnode = cv.take<uint32_t>(W);
+  const auto o_bsum = cv.take<unsigned long long>(cdiv(W, kWtBlock));
+  const auto o_pos = cv.take<unsigned long long>(W);
+  const auto o_id = cv.take<uint32_t>(W);
+  const auto o_node = cv.take<uint32_t>(W);
+  const auto o_group = cv.take<int32_t>(W);
+  HIPCHK(c, c->d_wait_scr.reserve(cv.mark()));
+  const uint32_t cur = c->wait_cur, other = cur ^ 1u;
+  if ((rc = wait_twin(c))) return rc;
+  void* base = c->d_wait_scr.p;
+  const GroupsDev gr = groups_dev(c);
+  WaitDev a{};
+  a.src = wait_tab(c, cur);
+  a.dst = wait_tab(c, other);
+  a.W = a.E = W;
+  a.mode = kWtByNode;
+  a.rem = o_rem.in(base);
+  a.R = R;
+  a.nnode = o_nnode.in(base);
+  a.bsum = o_bsum.in(base);
+  a.pos = o_pos.in(base);
+  a.info = o_info.in(base);
+  a.o_key = o_id.in(base);
+  a.o_node = o_node.in(base);
+  a.o_group = o_group.in(base);
+  a.N = c->wait_n;
+  a.g_matched = const_cast<uint32_t*>(gr.matched);
+  a.G = G;
+  HIPCHK(c, hipMemsetAsync(a.info, 0, o_info.bytes(), c->stream));
+  HIPCHK(c, hipMemcpyAsync(o_rem.in(base), rp.removed.data(), o_rem.bytes(), hipMemcpyHostToDevice, c->stream));
+  // Everything above wrote this call's scratch only; the twin, matched and the counts change from here on.
+  launch_wait_nodes(c->stream, c->S, a);
+  LAUNCHCHK(c, BS_KERNEL_PREPASS);
+  uint32_t info[4] = {0, 0, 0, 0};
+  HIPCHK(c, hipMemcpyAsync(info, a.info, o_info.bytes(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));               // (rp.removed and info are local buffers)
+  const uint32_t kept = info[kWtKept], left = info[kWtLeft];
+  if (kept + left != W) { c->last_error = "bs_wait_nodes_apply: the scan's totals do not add up to the table"; return BS_ERR_HIP; }
+  c->wait_cur = other;
+  c->wait_w = kept;
+  c->wait_n = rp.n_new;
+  const uint32_t k = std::min(left, cap);
+  if (k) {
+    HIPCHK(c, hipMemcpyAsync(id, a.o_key, (size_t)k * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(node, a.o_node, (size_t)k * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(group, a.o_group, (size_t)k * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  *n_out = left;
+  if (left) {                                               // matched fell: findMaxPG, the steady table and the epoch analysis follow as after bs_groups_apply
+    if ((rc = analyse_groups(c, false))) return rc;
+    if ((rc = maybe_analyse_epochs(c))) return rc;
+  }
+  return BS_OK;
 }
 }  // extern "C"

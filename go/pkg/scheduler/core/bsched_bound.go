@@ -295,3 +295,41 @@ func (g *gpuCore) expireGangs(groups []uint32, deny, all bool, P, G int) (*expir
 	}
 	return e, nil
 }
+
+// droppedWaiters: the rows of the resident wait table that left with their nodes, in ascending id.
+type droppedWaiters struct {
+	n     uint32   // the true count (may exceed the rows asked for)
+	id    []uint32 // the row's id: dead from now on
+	node  []uint32 // the OLD index of the node it waited on
+	group []int32  // its gang: matched of that group fell by one
+}
+
+// waitFollowNodes: bs_wait_nodes_apply — the resident wait table follows node-list surgery.  Called after the bs_nodes_apply call(s) it
+// mirrors, with the kind and index fields of their deltas in order (the shim parks the last pass's waiting pods BEFORE the surgery); the
+// bound table's bs_bound_nodes_apply takes the same two arrays, in either order.  Rows on removed nodes leave and come back here: the
+// shim rejects those WaitingPods (or restores matched with bs_groups_apply to let the entry live to its TTL); every other row keeps its
+// id and names its node by the new index.  rows: how many dropped rows to take back.  The shim has no resident wait cycle yet; when it
+// gets one this is its step between the park and the next pass.
+func (g *gpuCore) waitFollowNodes(kind, index []uint32, rows int) (*droppedWaiters, error) {
+	if len(kind) != len(index) {
+		return nil, fmt.Errorf("waitFollowNodes: %d kinds, %d indices", len(kind), len(index))
+	}
+	_, pKind := u32s(kind)
+	_, pIndex := u32s(index)
+	oid, onode, ogroup := make([]C.uint32_t, rows+1), make([]C.uint32_t, rows+1), make([]C.int32_t, rows+1)
+	var n C.uint32_t
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if rc := C.bs_wait_nodes_apply(g.ctx, C.uint32_t(len(kind)), pKind, pIndex, C.uint32_t(rows), &oid[0], &onode[0], &ogroup[0], &n); rc != C.BS_OK {
+		return nil, fmt.Errorf("bs_wait_nodes_apply: %s (%s)", C.GoString(C.bs_strerror(rc)), C.GoString(C.bs_last_error(g.ctx)))
+	}
+	k := int(n)
+	if k > rows {
+		k = rows
+	}
+	d := &droppedWaiters{n: uint32(n), id: make([]uint32, k), node: make([]uint32, k), group: make([]int32, k)}
+	for i := 0; i < k; i++ {
+		d.id[i], d.node[i], d.group[i] = uint32(oid[i]), uint32(onode[i]), int32(ogroup[i])
+	}
+	return d, nil
+}

@@ -613,8 +613,9 @@ int bs_seq_waiting_read(bs_ctx* ctx, uint32_t p, int32_t* wait_node /*[p]*/);  /
  *   validity        the table remembers the node count and the group count it was created for.  While either differs from bs_nodes_count
  *                   or the loaded group count, every call except bs_wait_load, bs_wait_count and bs_wait_ids answers BS_ERR_STATE.  This
  *                   is a test of the COUNTS, as for the bound-pod table: list surgery that keeps a count passes it and the rows then name
- *                   other nodes or groups — the caller's hazard.  The way through list surgery is bs_wait_read, a remap on the host and
- *                   bs_wait_load; there is no device remap.  Single-rank contexts only (BS_ERR_STATE otherwise, as bs_seq_run).
+ *                   other nodes or groups — the caller's hazard.  The way through node-list surgery is bs_wait_nodes_apply (below), which
+ *                   remaps the table on the device; through group-list surgery it is bs_wait_read, a remap on the host and
+ *                   bs_wait_load.  Single-rank contexts only (BS_ERR_STATE otherwise, as bs_seq_run).
  *   bs_wait_load    a fresh snapshot (a restart, or after list surgery).  Needs nodes and groups loaded.  w = 0 is valid and is how a
  *                   context gets its empty table.  The ids are 0 .. w - 1 and the id space becomes w.  req is [L][w]; the rows are stored
  *                   as the table stores them (the pods lane becomes 1, a scalar lane without a present bit 0).  Node requests and groups
@@ -662,6 +663,43 @@ int bs_wait_release(bs_ctx* ctx, uint32_t count, const uint32_t* group, uint32_t
 int bs_wait_expire(bs_ctx* ctx, uint32_t count, const uint32_t* group, uint32_t flags, uint32_t cap, uint32_t* id, uint32_t* node,
                    uint32_t* group_entries /*[count]*/, uint32_t* group_unknown /*[count]*/, uint32_t* n_out);
 int bs_wait_forget(bs_ctx* ctx, uint32_t count, const uint32_t* id, uint32_t* node_out /*[count]*/);
+
+/* ---- the wait table follows node-list surgery --------------------------------------------------------------------------------
+ * bs_nodes_apply with BS_DELTA_APPEND / BS_DELTA_REMOVE renumbers the nodes; bs_wait_nodes_apply gives the wait table the same delta list
+ * and the table is remapped on the device, instead of a bs_wait_read, a remap on the host and a bs_wait_load of the whole table (which
+ * also resets every id and leaves `matched` to the caller).  Flat arguments: this form is also the cgo form.
+ *   order        after the bs_nodes_apply call or calls it mirrors: kind[d] and index[d] are the `kind` and `index` fields of their
+ *                deltas, concatenated in order.  The caller parks the last pass's waiting pods (bs_wait_park) BEFORE the surgery: an
+ *                APPEND or a REMOVE ends bs_seq_expire's window, as always.  Independent of bs_bound_nodes_apply: either order.
+ *   replay       the list is replayed on the node count the table was made for.  BS_DELTA_UPDATE changes nothing (waiting pods are no
+ *                node property).  BS_DELTA_APPEND adds a node with no rows.  BS_DELTA_REMOVE of an old node drops every row on it, and
+ *                the nodes behind it move down by one; a REMOVE of a node appended earlier in the list cancels that append.
+ *   survivors    keep id, group, request lanes, present bits and order (ascending id); only the node column changes, to the node's new
+ *                index.  bs_wait_ids is unchanged; a dropped id is dead, as one removed by bs_wait_forget is.
+ *   dropped rows bs_wait_forget without its node side, because the node is gone: the row leaves the table by the stable compaction and
+ *                matched of its group falls by 1 per row, in uint32 arithmetic.  No deny flag is set.  findMaxPG and the epoch analysis
+ *                follow as after bs_groups_apply, but only when something was dropped.  Why a drop and not a stale row: the reference
+ *                keeps a MatchedPodNodes entry until its TTL (core.go:289-290) whatever happens to the node, but a row here cannot name
+ *                a node that no longer exists.  Dropping WITH the decrement keeps the invariant the table documents — group_unknown == 0
+ *                for a caller that parks every cycle.  The caller gets the rows back and may restore matched with bs_groups_apply if it
+ *                wants the entry to live to its TTL.
+ *   node requests are never touched: removed nodes are gone, and the survivors still hold their waiting pods.
+ *   outputs      *n_out is the true number of dropped rows; the first min(n, cap) come back in ascending id as (id, OLD node index,
+ *                group).  The result arrays may be NULL when cap == 0.  The resident state is fully applied whatever the cap.
+ *   validity     on success the table's node count becomes the count the replay ended at: the call is legal exactly where the other
+ *                calls are refused for a stale node count (and where surgery kept the count, which it then puts right: the rows are
+ *                remapped).  The group count must still match.
+ *   errors       all are found on the host before anything resident changes; on any error the table, its counts, the id space, matched
+ *                and the flags are as before.  BS_ERR_STATE: no table, a stale group count, nodes not loaded, a replay that ends at a
+ *                count other than bs_nodes_count (not the list bs_nodes_apply got), a sharded or external-reduce context.
+ *                BS_ERR_INVALID: a kind outside the three, an UPDATE or REMOVE index at or beyond the count current at that point of
+ *                the replay, NULL kind or index with count > 0, a NULL result array with cap > 0, NULL n_out.  count == 0 is BS_OK when
+ *                the counts already agree, and changes nothing.
+ *   edges        from an empty table and down to an empty table; down to zero nodes where bs_nodes_apply went there; APPENDs or UPDATEs
+ *                only: nothing moves, the count is updated, nothing is launched.  Synchronous.  Host work is proportional to count; the
+ *                device makes one pass over the table. */
+int bs_wait_nodes_apply(bs_ctx* ctx, uint32_t count, const uint32_t* kind, const uint32_t* index, uint32_t cap, uint32_t* id, uint32_t* node,
+                        int32_t* group, uint32_t* n_out);
 
 /* ---- gang-aware preemption: the victim search, batched ------------------------------------------------------------------
  * The path of a pod that passed PreFilter and found no node.  The plugin's one hook there is PreFilterExtensions.RemovePod

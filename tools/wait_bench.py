@@ -3,7 +3,14 @@ replaces — the caller keeps its own copies of the waiting pods' requests and o
 numpy), hands the touched nodes to bs_nodes_assume and the groups to bs_groups_apply, then waits for the stream.  bs_wait_park is timed
 too, after the same pass.  One untimed park + expire first, so that no figure contains the new kernels' code-object load.  Every figure is
 the wall time of the call(s) as the caller sees them, best and median of `--reps` runs, each on a freshly loaded context that ran the pass
-and parked.  No threshold is set.  Usage: python tools/wait_bench.py [config] [scenario] [--reps N]"""
+and parked.  No threshold is set.  Usage: python tools/wait_bench.py [config] [scenario] [--reps N] [--nodes]
+
+--nodes times bs_wait_nodes_apply instead, on the same table, after a bs_nodes_apply (untimed: both paths need it) of three churn shapes —
+1 node removed, 32 nodes removed, 1 % of the nodes removed plus as many appended; the nodes are drawn by a seeded generator of this tool —
+beside the path the call replaces: bs_wait_read before the surgery, the remap in vectorised numpy (the removed nodes sorted, a searchsorted
+per row), bs_wait_load of the survivors and the bs_groups_apply that takes the dropped rows off `matched`, then the stream.  The replaced
+path's list of removed nodes and its copy of the groups are prepared outside its timed region; the call's replay of the delta list is
+inside its own."""
 import ctypes as C
 import importlib
 import json
@@ -54,6 +61,74 @@ def host_path(ctx, tab, req, pres, grp, gangs, deny, sync):
     return time.perf_counter() - t
 
 
+def node_delta(nodes, kind, index, like=0):
+    """a REMOVE of `index`, or an APPEND of an empty node with the allocatable columns of node `like` that fits every class"""
+    d = capi.NodeDelta()
+    d.kind, d.index = int(kind), int(index)
+    if kind == capi.DELTA_APPEND:
+        for j in range(nodes.lanes):
+            d.allocatable[j], d.requested[j] = int(nodes.allocatable[j, like]), 0
+        d.allocatable_present, d.requested_present, d.flags, d.fit_default, d.n_fit_exceptions = int(nodes.allocatable_present[like]), 0, 0, 1, 0
+    return d
+
+
+def churn(nodes, rng, n_remove, n_append):
+    """-> (deltas, the removed OLD nodes ascending): n_remove random nodes leave in a random order, then n_append nodes are appended"""
+    old = rng.choice(nodes.n, n_remove, replace=False)
+    gone, deltas = [], []
+    for k in old.tolist():
+        deltas.append(node_delta(nodes, capi.DELTA_REMOVE, k - sum(x < k for x in gone)))
+        gone.append(k)
+    deltas += [node_delta(nodes, capi.DELTA_APPEND, 0, int(rng.integers(0, nodes.n))) for _ in range(n_append)]
+    return deltas, np.sort(old).astype(np.int64)
+
+
+def replaced_path(ctx, deltas, rem, grp, sync):
+    """bs_wait_read (before the surgery: afterwards the count is stale), [bs_nodes_apply, untimed], the remap on the host, bs_wait_load,
+    bs_groups_apply for matched; -> (seconds, rows dropped)"""
+    t = time.perf_counter()
+    tab = ctx.wait_read()
+    spent = time.perf_counter() - t
+    ctx.apply_node_deltas(deltas)
+    t = time.perf_counter()
+    node = tab["node"].astype(np.int64)
+    lo = np.searchsorted(rem, node)
+    gone = np.isin(node, rem)
+    keep = ~gone
+    ctx.wait_load((node - lo)[keep], tab["group"][keep], tab["req"][:, keep], tab["req_present"][keep])
+    fell = np.bincount(tab["group"][gone], minlength=grp.g)
+    ctx.apply_group_deltas([(int(g), (int(grp.matched[g]) - int(fell[g])) & 0xFFFFFFFF, int(grp.status_scheduled[g]), int(grp.flags[g])) for g in np.nonzero(fell)[0]])
+    sync()
+    return spent + time.perf_counter() - t, int(gone.sum())
+
+
+def nodes_mode(ctx, nodes, fit, groups, pods, reps, sync, out):
+    rng = np.random.default_rng(5)
+    one_percent = max(nodes.n // 100, 1)
+    fresh(ctx, nodes, fit, groups, pods)
+    d, _ = churn(nodes, rng, 1, 0)
+    ctx.apply_node_deltas(d)
+    ctx.wait_nodes_apply([x.kind for x in d], [x.index for x in d])           # warm-up: the first launch of the k_wn_* kernels loads their code
+    for name, n_remove, n_append in (("1_removed", 1, 0), ("32_removed", 32, 0), ("1pct_removed_and_appended", one_percent, one_percent)):
+        call, host, rows = [], [], 0
+        for _ in range(reps):
+            deltas, rem = churn(nodes, rng, n_remove, n_append)
+            kinds, idx = [x.kind for x in deltas], [x.index for x in deltas]
+            fresh(ctx, nodes, fit, groups, pods)
+            ctx.apply_node_deltas(deltas)
+            t = time.perf_counter()
+            r = ctx.wait_nodes_apply(kinds, idx)
+            call.append(time.perf_counter() - t)
+            fresh(ctx, nodes, fit, groups, pods)
+            spent, dropped = replaced_path(ctx, deltas, rem, ctx.read_groups(), sync)
+            host.append(spent)
+            assert dropped == r[3], (dropped, r[3])
+            rows = r[3]
+        out["modes"][name] = {"removed": n_remove, "appended": n_append, "rows_dropped_last_rep": rows,
+                              "wait_nodes_apply_us_best": min(call) * 1e6, "wait_nodes_apply_us_median": float(np.median(call)) * 1e6,
+                              "read_remap_load_us_best": min(host) * 1e6, "read_remap_load_us_median": float(np.median(host)) * 1e6}
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     config = args[0] if args else "cfg3"
@@ -66,6 +141,13 @@ def main():
     with bsa.Context(scalar_lanes=nodes.lanes - 4) as ctx:
         stream = C.c_void_p(ctx.stream())
         sync = lambda: hip.hipStreamSynchronize(stream)
+        if "--nodes" in sys.argv:
+            fresh(ctx, nodes, fit, groups, pods)
+            tab = ctx.wait_read()
+            out["table_rows"], out["table_gangs"] = int(tab["id"].size), int(np.unique(tab["group"]).size)
+            nodes_mode(ctx, nodes, fit, groups, pods, reps, sync, out)
+            print(json.dumps(out))
+            return
         fresh(ctx, nodes, fit, groups, pods)
         ctx.wait_expire(np.unique(ctx.wait_read()["group"]), deny=True, cap=0)      # warm-up: the first launch of the k_wt_* kernels loads their code object
         park = [fresh(ctx, nodes, fit, groups, pods) for _ in range(reps)]
