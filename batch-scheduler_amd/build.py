@@ -16,8 +16,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.environ.get("BS_LIB_DIR") or HERE
 PREBUILT_ONLY = bool(os.environ.get("BS_LIB_DIR"))
 LIB_PATH = os.path.join(LIB_DIR, "libbsched.so")
-# NOTE: UNITS / SOURCES below are the FIRST FIVE units only, not "what is built": a new unit goes into LATER_UNITS further down, and everything
-# that builds, links or tests staleness goes by ALL_UNITS / ALL_SOURCES.
+# NOTE: UNITS / SOURCES below are the FIRST FIVE units only, not "what is built": later units sit in LATER_UNITS and LIST_UNITS further down, and
+# everything that builds, links or tests staleness goes by BUILD_UNITS / BUILD_SOURCES.
 # translation units -> the headers each one depends on, transitively (tests/test_build_units_cpu.py follows the #includes; DESIGN.md section 4 "Build")
 _COMMON = ["bs_common.hpp", "bs_kernels.hpp", "bs_nodew_layout.hpp", "bs_lanes.hpp", os.path.join("..", "..", "include", "bsched.h")]
 _CTX = _COMMON + ["bs_ctx.hpp", "bs_carve.hpp", "bs_hostmem.hpp", "bs_pod_ranges.hpp"]      # the units that hold entry points
@@ -33,13 +33,21 @@ UNITS = {
 }
 SOURCES = list(UNITS)
 # the units that came after those five, kept in a table of their own: tests/test_build_units_cpu.py holds UNITS and SOURCES to exactly the five
-# above, tests/test_wait_cpu.py holds this table to the include graph in the same way.  Everything below builds and links ALL_UNITS.
+# above, tests/test_wait_cpu.py holds this table to the include graph in the same way.
 LATER_UNITS = {
     "tu_wait.hip": _SEQ + ["bs_wait.hpp", "bs_wait_list.hpp", "bs_bound_nodes_replay.hpp"],
 }
 ALL_UNITS = {**UNITS, **LATER_UNITS}
 ALL_SOURCES = list(ALL_UNITS)
-HEADERS = sorted({h for hs in ALL_UNITS.values() for h in hs})
+# ... and the seventh: tests/test_wait_cpu.py holds LATER_UNITS and ALL_SOURCES to the six names above in turn, so group-list surgery has a
+# table of its own again (tests/test_groups_list_cpu.py holds it to the include graph).  What is compiled, linked and tested for staleness is
+# BUILD_UNITS / BUILD_SOURCES.
+LIST_UNITS = {
+    "tu_groups.hip": _CTX + ["bs_groups_list.hpp", "bs_groups_list_check.hpp"],
+}
+BUILD_UNITS = {**ALL_UNITS, **LIST_UNITS}
+BUILD_SOURCES = list(BUILD_UNITS)
+HEADERS = sorted({h for hs in BUILD_UNITS.values() for h in hs})
 OBJ_DIR = os.path.join(HERE, "build")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]
@@ -82,7 +90,7 @@ def is_stale() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, f) for f in ALL_SOURCES + HEADERS]
+    deps = [os.path.join(CSRC, f) for f in BUILD_SOURCES + HEADERS]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -95,7 +103,7 @@ def _unit_stale(src: str) -> bool:
     if not os.path.exists(o):
         return True
     t = os.path.getmtime(o)
-    return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in [src] + ALL_UNITS[src])
+    return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in [src] + BUILD_UNITS[src])
 
 
 def build(force: bool = False, verbose: bool = False, extra_flags: list[str] | None = None, unity: bool = False) -> str:
@@ -116,11 +124,11 @@ def build(force: bool = False, verbose: bool = False, extra_flags: list[str] | N
         res = subprocess.run(cmd, capture_output=True, text=True)
         if res.returncode != 0:
             raise RuntimeError("hipcc failed:\n" + res.stdout + res.stderr)
-        for src in ALL_SOURCES:                                   # the objects no longer match the library
+        for src in BUILD_SOURCES:                                 # the objects no longer match the library
             if os.path.exists(_obj(src)):
                 os.remove(_obj(src))
         return LIB_PATH
-    todo = [src for src in ALL_SOURCES if force or extra_flags or _unit_stale(src)]
+    todo = [src for src in BUILD_SOURCES if force or extra_flags or _unit_stale(src)]
     procs = []
     for src in todo:
         cmd = [hipcc(), *FLAGS, *(extra_flags or []), "-c", "-o", _obj(src), os.path.join(CSRC, src)]
@@ -140,7 +148,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags: list[str] | N
                 os.remove(_obj(src))
         raise RuntimeError("hipcc failed:\n" + "\n".join(failed))
     tmp = f"{LIB_PATH}.{os.getpid()}.tmp"
-    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp, *[_obj(src) for src in ALL_SOURCES], "-ldl"]
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp, *[_obj(src) for src in BUILD_SOURCES], "-ldl"]
     if verbose:
         print(" ".join(cmd))
     res = subprocess.run(cmd, capture_output=True, text=True)
@@ -148,7 +156,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags: list[str] | N
         raise RuntimeError("link failed:\n" + res.stdout + res.stderr)
     os.replace(tmp, LIB_PATH)
     if extra_flags:
-        for src in ALL_SOURCES:                                   # objects of an experiment build must not be taken for the shipped ones
+        for src in BUILD_SOURCES:                                 # objects of an experiment build must not be taken for the shipped ones
             os.remove(_obj(src))
     return LIB_PATH
 

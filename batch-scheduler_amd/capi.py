@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "bs_seq_expire", "bs_seq_expire_flat", "bs_seq_waiting_read",
     "bs_wait_load", "bs_wait_count", "bs_wait_ids", "bs_wait_read", "bs_wait_park", "bs_wait_release", "bs_wait_expire", "bs_wait_forget",
     "bs_wait_nodes_apply",
+    "bs_groups_list_apply", "bs_groups_list_apply_flat",
 ]
 
 SEQ_EXPIRE_DENY, SEQ_EXPIRE_ALL = 1, 2    # bs_seq_expire flags
@@ -139,6 +140,18 @@ class SeqExpireOut(C.Structure):
 
 
 _lib = None
+
+
+class GroupsListDelta(C.Structure):
+    """bs_groups_list_delta"""
+    _fields_ = [("n_remove", C.c_uint32), ("remove", C.POINTER(C.c_uint32)), ("n_update", C.c_uint32), ("update", C.POINTER(C.c_uint32)),
+                ("rows", soa.GroupsStruct), ("n_append", C.c_uint32)]
+
+
+class GroupsListOut(C.Structure):
+    """bs_groups_list_out"""
+    _fields_ = [("g_new", C.c_uint32), ("n_pods_missing", C.c_uint32), ("n_bound_missing", C.c_uint32), ("n_wait_dropped", C.c_uint32),
+                ("wait_cap", C.c_uint32), ("wait_id", C.POINTER(C.c_uint32)), ("wait_node", C.POINTER(C.c_uint32)), ("wait_group", C.POINTER(C.c_int32))]
 
 
 def load_library(path: str | None = None):
@@ -244,6 +257,9 @@ def load_library(path: str | None = None):
     L.bs_wait_expire.argtypes = [vp, u32, P(u32), u32, u32, P(u32), P(u32), P(u32), P(u32), P(u32)]
     L.bs_wait_forget.argtypes = [vp, u32, P(u32), P(u32)]
     L.bs_wait_nodes_apply.argtypes = [vp, u32, P(u32), P(u32), u32, P(u32), P(u32), P(i32), P(u32)]
+    L.bs_groups_list_apply.argtypes = [vp, P(GroupsListDelta), P(GroupsListOut)]
+    L.bs_groups_list_apply_flat.argtypes = [vp, u32, P(u32), u32, P(u32), u32, P(u32), P(u32), P(u32), P(u8), P(u32), P(C.c_int64), P(u32), P(C.c_uint64),
+                                            u32, u32, P(u32), P(u32), P(i32), P(u32)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:
@@ -339,6 +355,42 @@ class Context:
         st = out.as_struct()
         self._chk(self._lib.bs_groups_read(self._h, C.byref(st)), "bs_groups_read")
         return out
+
+    def groups_list_apply(self, remove=(), update=(), rows: "soa.Groups | None" = None, n_append: int | None = None, wait_cap: int | None = None,
+                          flat: bool = False) -> dict:
+        """bs_groups_list_apply: PodGroups enter and leave the cache.  remove / update: OLD group indices, strictly ascending; rows: the
+        updated groups' new rows in `update` order, then the appended groups (n_append defaults to rows.g - len(update)).  The group list,
+        the queue's group column, the bound table's and the wait table's follow in one call.  Returns the out struct as a dict: g_new,
+        n_pods_missing, n_bound_missing, n_wait_dropped and the dropped wait rows wait_id, wait_node, wait_group (OLD group index; at most
+        wait_cap rows, the default holds the whole table).  flat=True goes through bs_groups_list_apply_flat."""
+        rv = np.ascontiguousarray(np.asarray(remove, np.uint32).reshape(-1))
+        uv = np.ascontiguousarray(np.asarray(update, np.uint32).reshape(-1))
+        rows = soa.Groups.empty(0, self.L) if rows is None else rows
+        assert rows.min_resources.shape[0] == self.L
+        n_append = rows.g - int(uv.size) if n_append is None else int(n_append)
+        if wait_cap is None:
+            w = C.c_uint32(0)
+            wait_cap = int(w.value) if self._lib.bs_wait_count(self._h, C.byref(w)) == 0 else 0
+        cap = int(wait_cap)
+        wi, wn, wg = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.int32)
+        i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        rs = rows.as_struct()
+        if flat:
+            cnt = np.zeros(4, np.uint32)
+            self._chk(self._lib.bs_groups_list_apply_flat(
+                self._h, int(rv.size), _u32p(rv) if rv.size else None, int(uv.size), _u32p(uv) if uv.size else None, rs.g, rs.min_member, rs.status_scheduled,
+                rs.matched, rs.flags, rs.cls, rs.min_resources, rs.min_resources_present, rs.occupied_by, n_append, cap, _u32p(wi) if cap else None,
+                _u32p(wn) if cap else None, i32p(wg) if cap else None, _u32p(cnt)), "bs_groups_list_apply_flat")
+            g_new, pm, bm, wd = (int(x) for x in cnt)
+        else:
+            d = GroupsListDelta(int(rv.size), _u32p(rv) if rv.size else None, int(uv.size), _u32p(uv) if uv.size else None, rs, n_append)
+            o = GroupsListOut(0, 0, 0, 0, cap, _u32p(wi) if cap else None, _u32p(wn) if cap else None, i32p(wg) if cap else None)
+            self._chk(self._lib.bs_groups_list_apply(self._h, C.byref(d), C.byref(o)), "bs_groups_list_apply")
+            g_new, pm, bm, wd = int(o.g_new), int(o.n_pods_missing), int(o.n_bound_missing), int(o.n_wait_dropped)
+        self.g = g_new
+        k = min(wd, cap)
+        return dict(g_new=g_new, n_pods_missing=pm, n_bound_missing=bm, n_wait_dropped=wd, wait_id=wi[:k].copy(), wait_node=wn[:k].copy(),
+                    wait_group=wg[:k].copy())
 
     def apply_group_deltas(self, deltas):
         """deltas: iterable of (index, matched, status_scheduled, flags) — bs_groups_apply."""

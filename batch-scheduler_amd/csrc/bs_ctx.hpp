@@ -54,6 +54,28 @@ inline PodLayout pod_layout(uint32_t P, uint32_t L) {
   return l;
 }
 
+// One group pack = the arrays of bs_groups_soa for exactly `g` groups in one allocation (the live pack, the twin bs_groups_list_apply gathers
+// into, and that call's rows in pinned memory): carved in this order wherever a pack is laid out.
+struct GroupLayout {
+  Piece<uint32_t> mm, sc, matched, cls, mrpres;
+  Piece<uint8_t> flags;
+  Piece<int64_t> minres;
+  Piece<uint64_t> occ;
+};
+inline GroupLayout group_carve(Carve& cv, uint32_t G, uint32_t L) {
+  const size_t n = std::max<uint32_t>(G, 1);
+  GroupLayout l;
+  l.mm = cv.take<uint32_t>(n);
+  l.sc = cv.take<uint32_t>(n);
+  l.matched = cv.take<uint32_t>(n);
+  l.flags = cv.take<uint8_t>(n);
+  l.cls = cv.take<uint32_t>(n);
+  l.minres = cv.take<int64_t>(n * L);
+  l.mrpres = cv.take<uint32_t>(n);
+  l.occ = cv.take<uint64_t>(n);
+  return l;
+}
+
 // Defined in bsched.hip: the kernel groups' names (LAUNCHCHK) and the helpers that the family units call too.  Every entry point starts with
 // use_device: a deferred group patch (bs_groups_apply) goes out now, unless the caller can take it along in its own launch (bs_pods_apply).
 extern const char* const kKernelNames[BS_KERNEL_COUNT];
@@ -66,9 +88,16 @@ uint32_t* pclass_dev(const bs_ctx* c);
 void launch_nodes_assume(bs_ctx* c, const bs_node_request* records, uint32_t n);
 void mirror_node_requests(bs_ctx* c, const bs_node_request* records, uint32_t n);
 void rederive_nodes(bs_ctx* c, uint32_t base0 = 0, uint32_t m_before = 0);
+int group_layout(bs_ctx* c, uint32_t G);
+int group_counts(bs_ctx* c);
 int analyse_groups(bs_ctx* c, bool rearm_scratch = true, const bs_group_delta* deltas = nullptr, uint32_t ndeltas = 0, bool defer = false);
 int maybe_analyse_epochs(bs_ctx* c);
 int check_handover(bs_ctx* c);
+// Defined in tu_wait.hip: the wait table's removal core in its release form (the rows of the listed groups leave by the stable compaction,
+// nothing else is touched), with the rows' groups as a third column: bs_groups_list_apply drops the rows of removed groups through it.
+int wait_release_rows(bs_ctx* c, const char* who, uint32_t count, const uint32_t* group, uint32_t cap, uint32_t* id_out, uint32_t* node_out, int32_t* group_out,
+                      uint32_t* n_out);
+int32_t* wait_group_column(const bs_ctx* c);   // the live table's group column ([wait_w] rows)
 
 }  // namespace bs
 
@@ -111,6 +140,7 @@ struct bs_ctx {
   // groups live in ONE device allocation (one pinned-staged H2D per load); d_info / h_info carry what findMaxPG
   // found for the loaded state back to the host without a stream wait (see resolve_groups)
   DevBuf d_gpack, d_info, d_gdelta;
+  DevBuf d_gpack2, d_glist;          // bs_groups_list_apply: the allocation the new group pack is gathered into (swapped with d_gpack); its per-call scratch
   Piece<uint32_t> off_gmm, off_gsc, off_gmatched, off_gcls, off_gmrpres;
   Piece<uint8_t> off_gflags;
   Piece<int64_t> off_gminres;
@@ -316,6 +346,7 @@ struct bs_ctx {
   Event ev_query, ev_filter;
   PinnedBuf<int32_t> h_info{PinWait::None, hipHostMallocMapped | hipHostMallocCoherent};   // [16], kernels write it directly: leader, panic, steady table, tag | K of the loaded pods, tag | ...
   PinnedBuf<> h_gstage{PinWait::Event};   // groups pack, then deltas
+  PinnedBuf<> h_glstage{PinWait::Stream}; // bs_groups_list_apply's delta (its rows as a group pack, the remove and update lists), read in place by k_gl_gather
   PinnedBuf<> h_stage{PinWait::Event};    // pod staging; busy until the last H2D out of it is through (bs_pods_load does not wait for it)
   PinnedBuf<> h_dstage{PinWait::Stream};  // the delta the apply kernel reads in place (no event per apply: bs_pods_apply)
   PinnedBuf<> h_nstage{PinWait::Event};   // node requests of bs_nodes_assume

@@ -96,7 +96,7 @@ struct WaitDev {
   const uint32_t* rem;                  // [R] ascending, distinct
   uint32_t R;
   uint32_t* nnode;                      // [W] the row's new node index, kWtGone when its node is removed
-  int32_t* o_group;                     // [W] the third column of the rows
+  int32_t* o_group;                     // [W] the third column of the rows (the removal core: NULL unless the caller wants it)
 };
 
 // survives << 32 | leaves
@@ -196,7 +196,11 @@ __global__ __launch_bounds__(256) void k_wt_move(WaitDev a) {
     return;
   }
   const uint32_t row = (uint32_t)at;
-  if (row < a.W) { a.o_key[row] = id; a.o_node[row] = k; }
+  if (row < a.W) {
+    a.o_key[row] = id;
+    a.o_node[row] = k;
+    if (a.o_group) a.o_group[row] = g;                      // (bs_groups_list_apply's release: the group leaves with its rows)
+  }
   if (m - 1u < a.M) {
     if (a.mode == kWtById) a.l_out[m - 1u] = k;
     else __hip_atomic_fetch_add(&a.l_cnt[m - 1u], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

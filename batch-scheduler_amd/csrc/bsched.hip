@@ -30,6 +30,7 @@
 #include "tu_seq.hip"
 #include "tu_seq_expire.hip"
 #include "tu_wait.hip"
+#include "tu_groups.hip"
 #include "tu_preempt.hip"
 #endif
 
@@ -643,6 +644,59 @@ uint32_t* pclass_dev(const bs_ctx* c) { return c->lay[c->cur_pack].pclass.in(c->
 void rederive_nodes(bs_ctx* c, uint32_t base0, uint32_t m_before) {
   hipLaunchKernelGGL(k_nodes_derive, dim3(1), dim3(kScanBlock), 0, c->stream, nodes_dev(c), c->d_kmap.as<uint32_t>(), c->d_m.as<uint32_t>(), c->d_left4.as<int64_t>(),
                      c->d_lglob.as<int64_t>(), base0, m_before);
+}
+
+// bs_groups_list_apply: the context goes over to G groups — what bs_groups_load does for a new count (the group pack's layout, the per-group
+// scratch, what the resident queue derived for another group count, the result layout), stated for a caller that gathers the pack into the twin
+// allocation itself.  bs_groups_load keeps its own statement of these steps; the pack's layout is the same Carve order (group_carve).
+int group_layout(bs_ctx* c, uint32_t G) {
+  const size_t n = std::max<uint32_t>(G, 1);
+  Carve cv;
+  const GroupLayout l = group_carve(cv, G, c->L);
+  c->off_gmm = l.mm;
+  c->off_gsc = l.sc;
+  c->off_gmatched = l.matched;
+  c->off_gflags = l.flags;
+  c->off_gcls = l.cls;
+  c->off_gminres = l.minres;
+  c->off_gmrpres = l.mrpres;
+  c->off_gocc = l.occ;
+  c->gpack_bytes = cv.mark();
+  // (a list that gains a group per event must not reallocate per event: a quarter of headroom when a buffer has to grow)
+  auto grow = [](DevBuf& d, size_t bytes) -> hipError_t { return d.cap >= bytes ? hipSuccess : d.reserve(bytes + bytes / 4); };
+  HIPCHK(c, grow(c->d_first_elig, n * 4));
+  HIPCHK(c, grow(c->d_first_owner, n * 4));
+  HIPCHK(c, grow(c->d_first_reject, n * 4));
+  HIPCHK(c, grow(c->d_first_pod, n * 4));
+  HIPCHK(c, grow(c->d_cap_epoch, n * 4));
+  HIPCHK(c, grow(c->d_leader_epoch, (n + 1) * 4));
+  HIPCHK(c, grow(c->d_panic_epoch, n + 1));
+  if (G != c->G) { c->pairs_ready = false; c->dirs_ready = false; }   // the per-group arrays of the pod load are sized by G
+  if (G != c->G) c->ranges_valid = false;         // (the pod ranges' local flags are per group: 256 pods per block until the next bs_pods_load)
+  c->G = G;
+  return layout_out(c);
+}
+
+// h_gflags, the capture / MinResources-default counts and the largest fit class a captured group names, recounted from the device columns
+int group_counts(bs_ctx* c) {
+  const uint32_t G = c->G;
+  const GroupsDev gr = groups_dev(c);
+  std::vector<uint32_t> cls(G);
+  c->h_gflags.resize(G);
+  if (G) {
+    HIPCHK(c, hipMemcpyAsync(c->h_gflags.data(), gr.flags, G, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cls.data(), gr.cls, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  c->n_uncaptured = 0;
+  c->n_nominres = 0;
+  c->max_group_cls = 0;
+  for (uint32_t i = 0; i < G; ++i) {
+    if (!(c->h_gflags[i] & BS_GROUP_HAS_POD)) c->n_uncaptured++;
+    else c->max_group_cls = std::max(c->max_group_cls, cls[i]);
+    if (!(c->h_gflags[i] & BS_GROUP_HAS_MINRES)) c->n_nominres++;
+  }
+  return BS_OK;
 }
 
 // After the group state (or the fit classes) changed: re-arm the general chain's scratch and run findMaxPG for

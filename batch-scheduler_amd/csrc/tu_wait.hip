@@ -300,8 +300,9 @@ static int wait_twin(bs_ctx* c) {
 
 // The removal core behind bs_wait_release (by group), bs_wait_expire (by group, node side, group state) and bs_wait_forget (by id, node
 // side, matched - 1 per entry).  l_cnt_out / l_out_out: the per-list-position results (entries per group; unknown per group or node per id).
+// group_out (bs_groups_list_apply's release): the rows' groups as a third column beside (id, node).
 static int wait_remove(bs_ctx* c, const char* who, uint32_t mode, bool node_side, bool expire, bool deny, uint32_t M, const uint32_t* list, uint32_t cap,
-                       uint32_t* id_out, uint32_t* node_out, uint32_t* l_cnt_out, uint32_t* l_out_out, uint32_t* n_out) {
+                       uint32_t* id_out, uint32_t* node_out, uint32_t* l_cnt_out, uint32_t* l_out_out, uint32_t* n_out, int32_t* group_out = nullptr) {
   int rc;
   if ((rc = use_device(c))) return rc;
   if (node_side && (rc = settle_pending(c))) return rc;
@@ -328,6 +329,7 @@ static int wait_remove(bs_ctx* c, const char* who, uint32_t mode, bool node_side
   const auto o_pos = cv.take<unsigned long long>(std::max<uint32_t>(W, 1));
   const auto o_id = cv.take<uint32_t>(std::max<uint32_t>(W, 1));
   const auto o_node = cv.take<uint32_t>(std::max<uint32_t>(W, 1));
+  const auto o_group = cv.take<int32_t>(group_out ? std::max<uint32_t>(W, 1) : 0u);
   const auto o_dlist = cv.take<uint32_t>(std::max<uint32_t>(rec_cap, 1));
   const auto o_rec = cv.take<bs_node_request>(std::max<uint32_t>(rec_cap, 1));
   HIPCHK(c, c->d_wait_scr.reserve(cv.mark()));
@@ -354,6 +356,7 @@ static int wait_remove(bs_ctx* c, const char* who, uint32_t mode, bool node_side
   a.info = o_info.in(base);
   a.o_key = o_id.in(base);
   a.o_node = o_node.in(base);
+  a.o_group = group_out ? o_group.in(base) : nullptr;
   a.l_cnt = o_lcnt.in(base);
   a.l_out = o_lout.in(base);
   a.delta = node_side ? o_delta.in(nb) : nullptr;
@@ -399,6 +402,7 @@ static int wait_remove(bs_ctx* c, const char* who, uint32_t mode, bool node_side
   if (k) {
     HIPCHK(c, hipMemcpyAsync(id_out, a.o_key, (size_t)k * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(node_out, a.o_node, (size_t)k * 4, hipMemcpyDeviceToHost, c->stream));
+    if (group_out) HIPCHK(c, hipMemcpyAsync(group_out, a.o_group, (size_t)k * 4, hipMemcpyDeviceToHost, c->stream));
   }
   if (l_cnt_out) HIPCHK(c, hipMemcpyAsync(l_cnt_out, a.l_cnt, o_lcnt.bytes(), hipMemcpyDeviceToHost, c->stream));
   if (l_out_out) HIPCHK(c, hipMemcpyAsync(l_out_out, a.l_out, o_lout.bytes(), hipMemcpyDeviceToHost, c->stream));
@@ -542,3 +546,11 @@ int bs_wait_nodes_apply(bs_ctx* c, uint32_t count, const uint32_t* kind, const u
   return BS_OK;
 }
 }  // extern "C"
+
+namespace bs {
+int wait_release_rows(bs_ctx* c, const char* who, uint32_t count, const uint32_t* group, uint32_t cap, uint32_t* id_out, uint32_t* node_out, int32_t* group_out,
+                      uint32_t* n_out) {
+  return wait_remove(c, who, kWtByGroup, false, false, false, count, group, cap, id_out, node_out, nullptr, nullptr, n_out, group_out);
+}
+int32_t* wait_group_column(const bs_ctx* c) { return wait_tab(c, c->wait_cur).group; }
+}  // namespace bs

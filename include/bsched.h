@@ -322,7 +322,7 @@ int bs_groups_read(bs_ctx* ctx, bs_groups_soa* groups_out); /* caller-sized arra
  * pods to Status.Scheduled (core.go:327), the quorum latch (core.go:305) and the deny TTL (core.go:105,424)
  * flip flag bits.  Each delta REPLACES matched / status_scheduled / flags of group `index`;
  * BS_GROUP_HAS_POD and BS_GROUP_HAS_MINRES must keep their loaded value (a first-pod capture changes cls and
- * MinResources too: use bs_groups_load).  A group index may appear only once per call.  Validated as a whole before
+ * MinResources too: bs_groups_list_apply's UPDATE replaces the whole row, bs_groups_load the whole list).  A group index may appear only once per call.  Validated as a whole before
  * anything is applied.
  * Like bs_groups_load it re-runs findMaxPG on the device and returns without waiting for the GPU. */
 typedef struct bs_group_delta {
@@ -552,7 +552,8 @@ int bs_nodes_read(bs_ctx* ctx, int64_t* requested, uint32_t* requested_present);
  * with the caller, as the 2 s and 20 s TTLs do.
  *   waiting state   where the last pass's waiting pods sit (per gang a chain of (pod, node) the pass keeps resident).  It is valid from
  *                   a successful bs_seq_run until the first call that renumbers what it indexes: bs_pods_load, bs_pods_apply,
- *                   bs_nodes_load, a bs_nodes_apply with an APPEND or a REMOVE, bs_groups_load, the next bs_seq_run (which replaces
+ *                   bs_nodes_load, a bs_nodes_apply with an APPEND or a REMOVE, bs_groups_load, a bs_groups_list_apply that is not refused and
+ *                   whose delta is not empty, the next bs_seq_run (which replaces
  *                   it), bs_destroy.  bs_nodes_assume, a bs_nodes_apply of UPDATEs only, bs_groups_apply, batches, the preemption and
  *                   bound-table calls leave it valid: what this call does to the nodes is a delta and commutes with them.  Outside the
  *                   window, and on sharded / external-reduce contexts (as bs_seq_run), both calls answer BS_ERR_STATE.  The window opens
@@ -606,7 +607,8 @@ int bs_seq_waiting_read(bs_ctx* ctx, uint32_t p, int32_t* wait_node /*[p]*/);  /
  * MatchedPodNodes across cycles, minus the clock, which stays with the caller as every TTL here does: one row per waiting pod, resident
  * on the device beside the pending queue and the bound-pod table.  A cycle then reads
  *   bs_pods_apply -> bs_seq_run -> bs_wait_release(released_group) -> bs_wait_park -> bind / bs_bound_apply -> next cycle;
- * on a gang's timeout bs_wait_expire, on a waiting pod's own end bs_wait_forget.
+ * on a gang's timeout bs_wait_expire, on a waiting pod's own end bs_wait_forget.  A PodGroup that enters or leaves the cache between two
+ * cycles is a bs_groups_list_apply BEHIND the cycle's bs_wait_park: the call ends bs_seq_expire's window, so the caller parks first.
  *   the table       rows in ascending id.  id: never reused before the next bs_wait_load.  group: 0 <= group < g.  node: < n.  req[L]: as
  *                   the pass's assume step counted the pod: lanes 0..2 the request, the pods lane 1, a scalar lane the request where the
  *                   pod's present bit is set, else 0.  req_present: masked to the context's scalar lanes.  At most BS_WAIT_MAX rows and ids.
@@ -614,8 +616,9 @@ int bs_seq_waiting_read(bs_ctx* ctx, uint32_t p, int32_t* wait_node /*[p]*/);  /
  *                   or the loaded group count, every call except bs_wait_load, bs_wait_count and bs_wait_ids answers BS_ERR_STATE.  This
  *                   is a test of the COUNTS, as for the bound-pod table: list surgery that keeps a count passes it and the rows then name
  *                   other nodes or groups — the caller's hazard.  The way through node-list surgery is bs_wait_nodes_apply (below), which
- *                   remaps the table on the device; through group-list surgery it is bs_wait_read, a remap on the host and
- *                   bs_wait_load.  Single-rank contexts only (BS_ERR_STATE otherwise, as bs_seq_run).
+ *                   remaps the table on the device; through group-list surgery it is bs_groups_list_apply (below), which takes the
+ *                   table along with the group list (or bs_wait_read, a remap on the host and bs_wait_load, after a bs_groups_load).
+ *                   Single-rank contexts only (BS_ERR_STATE otherwise, as bs_seq_run).
  *   bs_wait_load    a fresh snapshot (a restart, or after list surgery).  Needs nodes and groups loaded.  w = 0 is valid and is how a
  *                   context gets its empty table.  The ids are 0 .. w - 1 and the id space becomes w.  req is [L][w]; the rows are stored
  *                   as the table stores them (the pods lane becomes 1, a scalar lane without a present bit 0).  Node requests and groups
@@ -700,6 +703,76 @@ int bs_wait_forget(bs_ctx* ctx, uint32_t count, const uint32_t* id, uint32_t* no
  *                device makes one pass over the table. */
 int bs_wait_nodes_apply(bs_ctx* ctx, uint32_t count, const uint32_t* kind, const uint32_t* index, uint32_t cap, uint32_t* id, uint32_t* node,
                         int32_t* group, uint32_t* n_out);
+
+/* ---- group-list surgery: PodGroups enter and leave the cache -----------------------------------------------------------------
+ * bs_groups_apply patches the counters and flag bits of existing groups; the LIST itself changes whenever a job arrives or ends.  A
+ * PodGroup enters the cache when the controller first syncs it (controller.go:194-196, :226); it leaves on delete (:143, :167) and when
+ * its phase becomes Finished or Failed (:305).  bs_groups_list_apply is that event for everything resident that holds a group index: the
+ * group list, the pending queue, the bound-pod table and the wait table change in ONE call, so no half-remapped state exists — instead
+ * of a bs_groups_load of all g groups, a host remap and bs_pods_load of the queue, bs_wait_read / bs_wait_load (every wait id reset) and
+ * a bs_bound_load (every bound id and PDB bit reset).
+ *   delta        remove[n_remove] and update[n_update] are OLD indices, each list strictly ascending.  rows holds rows.g == n_update +
+ *                n_append groups: first the updated groups' new rows in `update` order, then the appended groups.  An index that is both
+ *                updated and removed is removed (bs_pods_apply's rule for flag updates); its row in `rows` is ignored.
+ *   new list     the surviving old groups keep their order: old group i becomes i minus the number of removed indices below i; the
+ *                appended groups follow in the delta's order.  findMaxPG's iteration order is the index order, as before (bs_groups_soa).
+ *                A survivor that is not updated keeps every column AS THE DEVICE HOLDS IT — matched, status_scheduled and the flags that
+ *                passes, expires and committing batches wrote there — not a host copy.  An UPDATE replaces all eight columns of
+ *                bs_groups_soa, BS_GROUP_HAS_POD, BS_GROUP_HAS_MINRES, cls, min_member, MinResources and OccupiedBy included: the case
+ *                bs_groups_apply refuses.
+ *   queue        a pod of a removed group gets BS_POD_GROUP_MISSING: the label is still on the pod and the cache lookup now fails, which
+ *                is what core.go:223-225 and :275-278 then see.  The other grouped pods get their group's new index; a value at or above
+ *                the old g is left as it is (the caller's hazard, as after bs_groups_load).  No pod is added, removed or moved.  Request
+ *                classes stay; pairs, directories, per-group minima and pod ranges are derived again from the resident queue by the next
+ *                bs_batch_run / bs_pods_apply, as after a bs_groups_load that changes g: no bs_pods_load is needed.  One host value is
+ *                not recounted: the largest fit class the queue's grouped pods name still counts the pods of removed groups, where a
+ *                bs_pods_load of the remapped queue would leave them out.  bs_batch_run's refusal "fit class index out of range" is
+ *                therefore the one it gave before the call (the pods and the fit classes are the same), never a new one.
+ *   bound table  the group column is remapped the same way (a removed group: BS_POD_GROUP_MISSING).  Ids, order, PDB bits and the node
+ *                side do not change.  The largest group index the table is held to name follows its group (at most g_new - 1); where it
+ *                was at or above the old g it keeps its value.
+ *   wait table   only when its group count equals the old g (otherwise it is left stale as it is).  The rows of removed groups leave by
+ *                bs_wait_release's stable compaction: no node request and no group is touched — the group is gone.  The reference loses
+ *                MatchedPodNodes with the cache entry and rejects nobody: the pods keep their room until the framework's own timeout, so
+ *                the caller gets the rows back as (id, node, OLD group index), ascending id, and takes them off the nodes when that
+ *                happens.  Survivors keep id, node, request lanes and order; their group column is remapped.  The table's group count
+ *                becomes g_new; bs_wait_ids is unchanged.
+ *   leader       the leader a committing batch or a pass left in the context (sop.maxFinishedPG, core.go:58-59) follows its group; when
+ *                that group is removed it becomes none (the reference keeps a pointer to the deleted entry, core.go:59, which the
+ *                library cannot: a library rule).
+ *   derived      everything bs_groups_load does for a changed g: the per-group buffers and the result layout, the host's view of the
+ *                flags, recounted from the device columns, findMaxPG, the steady table and the positional analysis.  A deferred
+ *                bs_groups_apply patch is applied first, a pending speculative or BS_BATCH_FILTER_DENY batch is settled first.  The call
+ *                ends bs_seq_expire's window (park first).  bs_queue_order_load's ranks are the caller's to reload, as after bs_groups_load.
+ *   result       afterwards bs_groups_read, bs_pods_read, bs_wait_read, bs_bound_read / bs_bound_dump and every later bs_batch_run (all
+ *                outputs; only fl_slot row numbers may differ, as after bs_pods_apply), bs_seq_run, bs_find_max_pg, bs_preempt_run and
+ *                bs_wait_expire equal, bit for bit, those of a context loaded afresh with the new list, the host-remapped queue, wait
+ *                table and bound table.
+ *   outputs      g_new; n_pods_missing / n_bound_missing: queue pods / bound entries that became BS_POD_GROUP_MISSING in this call;
+ *                n_wait_dropped: the true number of dropped wait rows, of which the first min(n, wait_cap) are written.  The resident
+ *                state is fully applied whatever the cap.  On an error `out` is not written.
+ *   errors       the errors below are found on the host before anything resident changes; on any of them nothing changes,
+ *                bs_seq_expire's window and the counts included.  (BS_ERR_HIP / BS_ERR_NOMEM — a failed HIP call or allocation — may
+ *                come after that point, with the window ended, wait rows dropped or the layout switched: reload the state, as after
+ *                the other calls' BS_ERR_HIP.)  BS_ERR_STATE: no groups loaded, a sharded or external-reduce context.  BS_ERR_INVALID: an index at
+ *                or above g, a list that is not strictly ascending, rows.g != n_update + n_append, a NULL array with a count or a
+ *                capacity above 0, a NULL delta or out.  BS_ERR_CAPACITY: more than 2^31 - 1 groups.  An empty delta is BS_OK, changes
+ *                nothing and launches nothing.  Works down to g = 0 and back up from it.  Synchronous.  Host work is proportional to the
+ *                delta (plus the recount of the flags); the device makes one pass over the group pack and one over each of the three
+ *                group columns. */
+typedef struct bs_groups_list_delta {
+  uint32_t n_remove;  const uint32_t* remove;  /* OLD indices, strictly ascending: stable delete            */
+  uint32_t n_update;  const uint32_t* update;  /* OLD indices, strictly ascending: the whole row is replaced */
+  bs_groups_soa rows;                          /* rows.g == n_update + n_append: first the updated groups'  */
+  uint32_t n_append;                           /* new rows in `update` order, then the appended groups       */
+} bs_groups_list_delta;
+typedef struct bs_groups_list_out {            /* every array may be NULL when its cap is 0                  */
+  uint32_t g_new;                              /* group count after the call                                 */
+  uint32_t n_pods_missing, n_bound_missing;    /* queue pods / bound entries that became BS_POD_GROUP_MISSING */
+  uint32_t n_wait_dropped, wait_cap;           /* true count; at most wait_cap rows written                  */
+  uint32_t *wait_id, *wait_node; int32_t* wait_group;   /* dropped wait rows, ascending id, OLD group index  */
+} bs_groups_list_out;
+int bs_groups_list_apply(bs_ctx* ctx, const bs_groups_list_delta* delta, bs_groups_list_out* out);
 
 /* ---- gang-aware preemption: the victim search, batched ------------------------------------------------------------------
  * The path of a pod that passed PreFilter and found no node.  The plugin's one hook there is PreFilterExtensions.RemovePod
@@ -1151,6 +1224,12 @@ int bs_preempt_commit_gang_flat(bs_ctx* ctx, uint32_t stages, uint32_t count, co
                                 const uint8_t* group_protected, const uint32_t* gang_need, uint32_t flags, uint32_t victim_cap,
                                 int32_t* node, uint32_t* n_candidates, uint32_t* n_victims, uint32_t* victims, int32_t* top_priority,
                                 int64_t* priority_sum, int64_t* earliest_start);
+/* bs_groups_list_apply (the delta's and the out struct's fields one by one; counts_out = {g_new, n_pods_missing, n_bound_missing, n_wait_dropped}) */
+int bs_groups_list_apply_flat(bs_ctx* ctx, uint32_t n_remove, const uint32_t* remove, uint32_t n_update, const uint32_t* update, uint32_t rows_g,
+                              const uint32_t* min_member, const uint32_t* status_scheduled, const uint32_t* matched, const uint8_t* flags,
+                              const uint32_t* cls, const int64_t* min_resources, const uint32_t* min_resources_present, const uint64_t* occupied_by,
+                              uint32_t n_append, uint32_t wait_cap, uint32_t* wait_id, uint32_t* wait_node, int32_t* wait_group,
+                              uint32_t* counts_out /*[4]*/);
 
 /* ---- measurement ------------------------------------------------------------------ */
 #define BS_KERNEL_PREPASS   0u
