@@ -947,7 +947,8 @@ int bs_preempt_commit(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32
  * bs_preempt_gang_read reads the last successful bs_preempt_commit_gang: slot_voided[q] = 1 where preemptor q (caller's order) had a
  * node and lost it to its run's quorum; group_placed[g] = placed of the group's run before the decision, 0 for a group without a run.
  * Either pointer may be NULL.  BS_ERR_STATE when the context's last successful preemption call was not bs_preempt_commit_gang;
- * BS_ERR_INVALID when count or g differ from that call's. */
+ * BS_ERR_INVALID when count or g differ from that call's.  The arrays stay those of that call through a later bs_groups_list_apply that
+ * changes g: they are read with the g of the call (group_placed by that call's indices), and the new g is BS_ERR_INVALID. */
 int bs_preempt_commit_gang(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
                            const uint8_t* group_protected, const uint32_t* gang_need /*[g]*/, uint32_t flags, uint32_t victim_cap,
                            const bs_preempt_out* out);

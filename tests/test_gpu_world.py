@@ -1,0 +1,410 @@
+"""Many cycles on ONE context with every resident table in play, against the composite model of tests/world_ref.py.
+
+The single-feature tests pin each entry point; this module pins what crosses them on the host side of the library (csrc/bs_ctx.hpp): the
+count and window guards, the scratch blocks that are "zero between calls" and whose layouts follow N, G and the id spaces, the
+pointer-swapped twins of the group pack, the bound table and the wait table, the lazily re-derived queue state.  After EVERY call the
+cheap reads (groups, queue, node requests, findMaxPG, the wait table, the bound table with its PDB column, the resident PDBs, the
+pass's waiting pods while the window is open, bs_preempt_gang_read) must equal the model bit for bit, every call's own results are
+compared field for field with the reference of that call, a predicted refusal must give the status the header names and change
+nothing, and every 8th step a context loaded afresh from the model's arrays (ids mapped by table order) must answer bs_preempt_run and,
+while no leader is carried, a batch with every stage exactly as the context under test does."""
+import numpy as np
+import pytest
+
+import groups_list_ref as gl
+import preempt_pdb_ref as pp
+import world_ref as wf
+from test_gpu_parity import assert_batch_equal
+
+pytestmark = pytest.mark.gpu
+BOUND_COLUMNS = ("priority", "start_ns", "group", "req", "req_present", "pdb")
+
+
+def status_of(bsa, fn):
+    try:
+        fn()
+    except bsa.BsError as e:
+        return e.status
+    return 0
+
+
+class Runner:
+    """a context and the World beside it: `do` makes one call on both and holds the device against the model"""
+
+    def __init__(self, bsa, soa, orc, sc, tag):
+        self.bsa, self.soa, self.orc, self.tag = bsa, soa, orc, tag
+        self.w = wf.world_of(orc, sc)
+        self.ctx = bsa.Context(scalar_lanes=sc["S"])
+        self.ctx.load_nodes(sc["nodes"], sc["fit"])
+        self.ctx.load_groups(sc["groups"])
+        self.ctx.load_pods(sc["pods"])
+        self.log = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.ctx.close()
+
+    def where(self):
+        return f"{self.tag} step {len(self.log) - 1} {self.log[-1]} after {self.log[:-1]}"
+
+    # ---- the reads ------------------------------------------------------------------------------------------------------------------
+    def check_reads(self):
+        ctx, w, bsa, where = self.ctx, self.w, self.bsa, self.where()
+        r = w.reads()
+        got = ctx.read_groups()
+        for name in gl.COLUMNS:
+            assert np.array_equal(getattr(got, name), getattr(r["groups"], name)), f"{where}: groups.{name}"
+        assert ctx.read_pods().equal(r["pods"]), f"{where}: the queue"
+        req, pres = ctx.read_node_requests()
+        assert np.array_equal(pres, r["node_pres"]), f"{where}: node request keys"
+        bad = np.nonzero(req != r["node_req"])
+        assert bad[0].size == 0, f"{where}: node requests differ first at lane {bad[0][:1]} node {bad[1][:1]}: {req[bad][:1]} vs {r['node_req'][bad][:1]}"
+        assert ctx.find_max_pg() == r["find_max_pg"], f"{where}: findMaxPG"
+        assert (ctx.wait_count(), ctx.wait_ids()) == (r["wait_count"], r["wait_ids"]), f"{where}: wait count, ids"
+        if r["wait"] is None:
+            assert status_of(bsa, ctx.wait_read) == wf.STATE, f"{where}: bs_wait_read with stale counts"
+        else:
+            t = ctx.wait_read()
+            for name, col in r["wait"].items():
+                assert np.array_equal(t[name], col), f"{where}: wait table: {name}"
+        if r["bound"] is None:
+            assert status_of(bsa, ctx.read_bound) == wf.STATE, f"{where}: bs_bound_read before bs_bound_load"
+        else:
+            ids, nodes = ctx.read_bound()
+            tab = r["bound"]
+            assert np.array_equal(ids, tab["id"]) and np.array_equal(nodes, tab["node"]), f"{where}: bs_bound_read"
+            dump = ctx.bound_dump()
+            for name in BOUND_COLUMNS:
+                assert np.array_equal(dump[name], tab[name]), f"{where}: bs_bound_dump: {name}"
+            assert ctx.bound_ids() == r["bound_ids"], f"{where}: bs_bound_ids"
+        if r["pdb"] is None:
+            assert status_of(bsa, ctx.pdb_read) == wf.STATE, f"{where}: bs_pdb_read without resident PDBs or with a stale node count"
+        else:
+            p = ctx.pdb_read()
+            assert (p["n_pdb"], p["covered"]) == (r["pdb"]["n_pdb"], r["pdb"]["covered"]), f"{where}: bs_pdb_read counts"
+            assert np.array_equal(p["allowed"], r["pdb"]["allowed"]) and np.array_equal(p["node_violating"], r["pdb"]["node_violating"]), f"{where}: bs_pdb_read"
+        if r["waiting"] is None:
+            assert status_of(bsa, ctx.seq_waiting_read) == wf.STATE, f"{where}: bs_seq_waiting_read outside the window"
+        else:
+            assert np.array_equal(ctx.seq_waiting_read(), r["waiting"]), f"{where}: bs_seq_waiting_read"
+        if w.gang is not None:                                  # the arrays of the last bs_preempt_commit_gang, under that call's g
+            q, g, voided, placed = w.gang
+            v, p = self.gang_read(q, g)
+            assert np.array_equal(v, voided) and np.array_equal(p, placed), f"{where}: bs_preempt_gang_read"
+            if w.g != g:
+                assert status_of(bsa, lambda: self.gang_read(q, w.g)) == wf.INVALID, f"{where}: bs_preempt_gang_read with the new g"
+
+    def gang_read(self, q, g):
+        import ctypes as C
+        voided, placed = np.zeros(max(q, 1), np.uint8), np.zeros(max(g, 1), np.uint32)
+        self.ctx._chk(self.ctx._lib.bs_preempt_gang_read(self.ctx._h, q, voided.ctypes.data_as(C.POINTER(C.c_uint8)), g,
+                                                         placed.ctypes.data_as(C.POINTER(C.c_uint32))), "bs_preempt_gang_read")
+        return voided[:q], placed[:g]
+
+    # ---- one call ------------------------------------------------------------------------------------------------------------------
+    def do(self, kind, args=None, refused=False, flat=False):
+        """the call on the model, then on the device; -> the model's results"""
+        args = {} if args is None else args
+        self.log.append(("!" if refused else "") + kind)
+        exp = self.w.step(kind, args)
+        where = self.where()
+        assert (exp["status"] != wf.OK) == refused, f"{where}: the model answers {exp['status']}"
+        if refused:
+            st = status_of(self.bsa, lambda: self.call(kind, args, exp, flat))
+            assert st == exp["status"], f"{where}: status {st}, the header says {exp['status']}"
+        else:
+            self.compare(kind, self.call(kind, args, exp, flat), exp, where)
+        self.check_reads()
+        return exp
+
+    def call(self, kind, a, exp, flat):
+        ctx, soa = self.ctx, self.soa
+        if kind == "pods":
+            return ctx.apply_pods(remove=a["remove"], insert=a["insert"])
+        if kind == "groups":
+            return ctx.apply_group_deltas(a["deltas"])
+        if kind == "batch":
+            ctx.run(a["stages"] | (soa.BATCH_COMMIT if a["commit"] else 0))
+            return ctx.read(bitmap=False, rows=False)
+        if kind == "pass":
+            return ctx.seq_run(soa.STAGE_PREFILTER)
+        if kind == "list":
+            return ctx.groups_list_apply(a["remove"], a["update"], a["rows"], a["n_append"], flat=flat)
+        if kind == "nodes":
+            return ctx.apply_node_deltas(exp["deltas"])
+        if kind == "assume":
+            return ctx.assume_nodes(a["reqs"])
+        if kind == "wait_load":
+            return ctx.wait_load(a["node"], a["group"], a["req"], a["req_present"])
+        if kind == "park":
+            return ctx.wait_park()
+        if kind == "release":
+            return ctx.wait_release(a["groups"])
+        if kind == "expire":
+            return ctx.wait_expire(a["groups"], deny=a["deny"])
+        if kind == "forget":
+            return dict(node=ctx.wait_forget(a["ids"]))
+        if kind == "wait_nodes":
+            ids, nodes, groups, n = ctx.wait_nodes_apply(exp["kind"], exp["index"])
+            return dict(n=n, id=ids, node=nodes, group=groups)
+        if kind == "seq_expire":
+            return ctx.seq_expire(a["groups"], deny=a["deny"], all=a["all"], flat=flat)
+        if kind == "bound_load":
+            return ctx.load_bound(a["bound"])
+        if kind == "bound_apply":
+            return dict(first_id=ctx.bound_apply(a["remove"], a["insert"], a["pdb"], flat=flat))
+        if kind == "bound_apply_ex":
+            return dict(first_id=ctx.bound_apply_ex(a["remove"], a["insert"], a["pdb"], flags=a.get("flags", 1), flat=flat))
+        if kind == "bound_nodes":
+            n, ids = ctx.bound_nodes_apply(exp["kind"], exp["index"], dropped_cap=ctx.bound_count())
+            return dict(n_dropped=n, dropped=ids)
+        if kind == "pdb_set":
+            return ctx.bound_pdb_set(a["bits"])
+        if kind == "pdb_load":
+            return ctx.pdb_load(a["allowed"], a["off"], a["member"])
+        if kind == "pdb_append":
+            return ctx.pdb_members_append(exp["first_id"], a["off"], a["member"])
+        if kind == "pdb_allowed":
+            return ctx.pdb_allowed_apply(a["index"], a["value"])
+        if kind == "preempt":
+            return dict(res=ctx.preempt(a["pod_index"], a["priority"], a["protected"], victim_cap=wf.CAP))
+        if kind == "commit":
+            return dict(res=ctx.preempt_commit(a["pod_index"], a["priority"], a["protected"], victim_cap=wf.CAP, apply=a["apply"], assume=a["assume"]))
+        if kind == "commit_gang":
+            return dict(res=ctx.preempt_commit_gang(a["pod_index"], a["priority"], a["protected"], gang_need=a["need"], victim_cap=wf.CAP, apply=a["apply"],
+                                                    assume=a["assume"], flat=flat))
+        raise KeyError(kind)
+
+    def compare(self, kind, got, exp, where):
+        same = lambda names, g=None, e=None: [self._eq((got if g is None else g)[f], (exp if e is None else e)[f], f"{where}: {f}") for f in names]
+        if kind == "batch":
+            assert_batch_equal(got, exp["batch"], where, bitmap=False)
+        elif kind == "pass":
+            same(("pf_code", "pf_first_k", "pf_leader", "pod_node", "released_group", "released_pods", "n_released"), e=exp["seq"])
+        elif kind == "list":
+            same(("g_new", "n_pods_missing", "n_bound_missing", "n_wait_dropped", "wait_id", "wait_node", "wait_group"))
+        elif kind == "park":
+            same(("first_id", "n", "pod", "node"))
+        elif kind == "release":
+            same(("n", "id", "node", "group_entries"))
+        elif kind == "expire":
+            same(("n", "id", "node", "group_entries", "group_unknown"))
+        elif kind == "forget":
+            same(("node",))
+        elif kind == "wait_nodes":
+            same(("n", "id", "node", "group"))
+        elif kind == "seq_expire":
+            same(("n_groups", "n_pods", "group", "group_pods", "group_earlier", "pod", "node"))
+        elif kind in ("bound_apply", "bound_apply_ex"):
+            same(("first_id",))
+        elif kind == "bound_nodes":
+            same(("n_dropped", "dropped"))
+        elif kind in ("preempt", "commit", "commit_gang"):
+            same(pp.FIELDS, g=got["res"], e=exp["res"])
+            if kind == "commit_gang":
+                same(("slot_voided", "group_placed"), g=got["res"])
+
+    @staticmethod
+    def _eq(a, b, what):
+        assert np.array_equal(np.asarray(a), np.asarray(b)), f"{what}: {np.asarray(a).tolist()} vs {np.asarray(b).tolist()}"
+
+    # ---- a context loaded afresh from the model's arrays ------------------------------------------------------------------------------
+    def against_fresh(self):
+        """bs_preempt_run and, while no leader is carried, a batch with every stage: this context and one loaded afresh"""
+        w, soa, where = self.w, self.soa, f"{self.where()}: against a context loaded afresh"
+        if w.pend_w or w.pend_b:
+            return
+        f = w.fresh_arrays()
+        with self.bsa.Context(scalar_lanes=w.S) as b:
+            b.load_nodes(f["nodes"], f["fit"])
+            b.load_groups(f["groups"])
+            b.load_pods(f["pods"])
+            if f["wait"] is not None:
+                t = f["wait"]
+                b.wait_load(t["node"], t["group"], t["req"], t["req_present"])
+                tb = b.wait_read()
+                assert np.array_equal(f["wait_keep"][tb["id"]] if tb["id"].size else tb["id"], t["id"]), f"{where}: wait ids through the map"
+                for name in ("node", "group", "req", "req_present"):
+                    assert np.array_equal(tb[name], t[name]), f"{where}: wait table: {name}"
+            if f["bound"] is not None:
+                keep = f["bound_keep"]
+                b.load_bound(f["bound"])
+                b.bound_pdb_set(f["bound_bits"])
+                (ia, na), (ib, nb) = self.ctx.read_bound(), b.read_bound()
+                assert np.array_equal(keep[ib] if ib.size else ib, ia) and np.array_equal(na, nb), f"{where}: the bound table through the id map"
+                da, db = self.ctx.bound_dump(), b.bound_dump()
+                for name in BOUND_COLUMNS:
+                    assert np.array_equal(da[name], db[name]), f"{where}: bound column {name}"
+                if w.preempt_ok() == wf.OK and w.pods.p:
+                    q = np.arange(min(w.pods.p, 12), dtype=np.uint32)
+                    prio = np.full(q.size, 350, np.int32)
+                    prot = (np.arange(w.g) % 5 == 0).astype(np.uint8)
+                    ra, rb = self.ctx.preempt(q, prio, prot, victim_cap=wf.CAP), wf.map_victims(b.preempt(q, prio, prot, victim_cap=wf.CAP), keep)
+                    for name in pp.FIELDS:
+                        assert np.array_equal(ra[name], rb[name]), f"{where}: bs_preempt_run: {name}"
+                    w.gang = None                               # (the context's last preemption call is this one now)
+            if w.leader < 0 and w.pods.p:
+                ra, rb = self.ctx.batch(soa.STAGE_ALL, bitmap=True), b.batch(soa.STAGE_ALL, bitmap=True)
+                assert_batch_equal(ra, rb, f"{where}: batch", bitmap=False)
+                assert np.array_equal(ra.fl_bitmap, rb.fl_bitmap), f"{where}: batch: Filter bitmap"
+
+
+@pytest.mark.parametrize("seed", range(wf.SEEDS))
+def test_many_cycles_on_one_context(seed, bsa, soa, orc):
+    sc, steps = wf.plan(seed, orc)
+    with Runner(bsa, soa, orc, sc, f"seed {seed}") as r:
+        for i, (kind, args, refused) in enumerate(steps):
+            r.do(kind, args, refused, flat=bool(i % 2))
+            if i % 8 == 7 or i == len(steps) - 1:
+                r.against_fresh()
+
+
+# ---- the header's cycle, scripted --------------------------------------------------------------------------------------------------------
+def _gang_preemptors(w, cap=12):
+    """the pods the last pass left without a node, each gang one run, and what each gang still needs (at most what it sends)"""
+    idx = w.unplaced[:cap]
+    grp = w.pods.group[idx]
+    prio = np.full(idx.size, 5000, np.int32)
+    o = wf.capi.gang_order(grp, prio)
+    idx, grp = idx[o], grp[o]
+    waiting = np.bincount(w.wt.group, minlength=w.g)[: w.g]
+    need = np.minimum(wf.capi.gang_need(w.groups, waiting), np.bincount(grp, minlength=w.g)[: w.g]).astype(np.uint32)
+    return dict(pod_index=idx.astype(np.uint32), priority=prio, protected=np.zeros(w.g, np.uint8), need=need, apply=True, assume=True)
+
+
+def _bind(w, rng):
+    """the pods the last pass released, as bound entries on the nodes they were assumed on (their requests are on the nodes already)"""
+    s, p = w.last, w.pods
+    idx = np.nonzero(s["pod_node"] >= 0)[0]
+    ins = wf.soa.Bound(s["pod_node"][idx].astype(np.uint32), rng.choice(wf.BOUND_PRIO, idx.size).astype(np.int32), rng.integers(50, 99, idx.size).astype(np.int64),
+                       p.group[idx].copy(), p.req[:, idx].copy(), p.req_present[idx].copy())
+    return dict(remove=np.zeros(0, np.uint32), insert=ins, pdb=None, flags=0)
+
+
+def test_the_documented_cycle_with_binding(bsa, soa, orc):
+    """include/bsched.h: bs_pods_apply -> bs_seq_run -> bs_wait_release(released_group) -> bs_wait_park -> bind (bs_bound_apply_ex, flags 0:
+    the pass assumed these pods already) -> bs_preempt_commit_gang(APPLY | ASSUME) for the pods without a node; three cycles on one context.
+    Between cycles 1 and 2 a finished gang leaves the cache and one arrives; between 2 and 3 a node leaves and one arrives, and both
+    tables follow; in cycle 3 the gang that has waited longest times out."""
+    sc = wf.scene(9)
+    rng = np.random.default_rng(99)
+    seen = dict(parked=0, released=0, bound=0, victims=0, voided=0)
+    with Runner(bsa, soa, orc, sc, "the documented cycle") as r:
+        w = r.w
+        r.do("wait_load", dict(node=(), group=(), req=None, req_present=None))
+        r.do("bound_load", dict(bound=sc["bound"]))
+        for cycle in (1, 2, 3):
+            gone = w.placed if w.placed is not None else np.zeros(0, np.int64)
+            arrive = np.sort(rng.integers(0, w.g, 24)).astype(np.int32)
+            r.do("pods", dict(remove=np.asarray(gone, np.uint32), insert=wf.new_pods(rng, w.S, arrive)))
+            s = r.do("pass")["seq"]
+            rel = r.do("release", dict(groups=[int(x) for x in s["released_group"]]))
+            pk = r.do("park", flat=bool(cycle % 2))
+            seen["parked"] += pk["n"]
+            seen["released"] += int(s["n_released"])
+            bind = _bind(w, rng)
+            r.do("bound_apply_ex", bind, flat=bool(cycle % 2))
+            seen["bound"] += bind["insert"].b
+            assert w.unplaced.size, f"cycle {cycle}: every pod found a node"
+            cg = r.do("commit_gang", _gang_preemptors(w), flat=bool(cycle % 2))
+            seen["victims"] += int(cg["res"]["n_victims"].sum())
+            seen["voided"] += int(cg["slot_voided"].sum())
+            if cycle == 1:
+                assert s["n_released"], "cycle 1 releases no gang"
+                r.do("list", dict(remove=[int(s["released_group"][0])], update=[], rows=wf.new_group_rows(rng, w.S, 1), n_append=1))
+            if cycle == 2:
+                on = int(w.wt.node[0])                                          # a node that holds wait rows (and bound entries) leaves
+                r.do("nodes", dict(ops=[(wf.REMOVE, on), (wf.APPEND, 0)]))
+                dropped = r.do("bound_nodes")
+                lost = r.do("wait_nodes")
+                assert dropped["n_dropped"] and lost["n"], "the removed node was empty"
+            if cycle == 3:
+                oldest = int(w.wt.group[0])
+                ex = r.do("expire", dict(groups=[oldest], deny=True))
+                assert ex["n"] > 0 and w.groups.flags[oldest] & soa.GROUP_DENIED
+            r.against_fresh()
+    print(f"the documented cycle: {seen}")
+    assert seen["parked"] >= 3 and seen["released"] and seen["bound"] and seen["victims"], seen
+
+
+# ---- sizes where the scans and copies change shape, reached by calls ---------------------------------------------------------------------------
+def test_tables_cross_their_block_edges_mid_sequence(bsa, soa, orc):
+    """a wait table loaded with 1023 rows grows past 1024 AND past its quarter of headroom in one park (the twin is allocated again and the
+    rows are copied), g goes 255 -> 257 -> 255, a list delta that removes groups brings the table back below 1024 rows, the bound table
+    outgrows its headroom in one bs_bound_apply_ex and is compacted by a commit"""
+    from test_gpu_seq_expire import waiting_scene
+    G, N, S = 255, 16, 1
+    rng = np.random.default_rng(1023)
+    nodes, fit, groups, pods = waiting_scene(soa, [2] * G, n_nodes=N, S=S, pods_cap=110, interleave=True, seed=1023)
+    bound = wf.new_bound(rng, S, 200, N, G)
+    bound.group[:] = np.where(bound.group < 0, 0, bound.group)
+    req, pres = wf.ba.stored(bound, S)
+    for l in range(4 + S):
+        np.add.at(nodes.requested[l], bound.node, req[l])
+    np.bitwise_or.at(nodes.requested_present, bound.node, pres)
+    nodes.allocatable[3] = nodes.requested[3] + 110
+    nodes.allocatable[0] = nodes.requested[0] + 6000                            # room for every queue pod; the preemptors below ask for more than is left
+    sc = dict(S=S, nodes=nodes, fit=fit, groups=groups, pods=pods, bound=bound)
+    with Runner(bsa, soa, orc, sc, "block edges") as r:
+        w = r.w
+        rows = wf.new_pods(rng, S, rng.integers(0, G, 1023))
+        r.do("wait_load", dict(node=rng.integers(0, N, 1023).astype(np.uint32), group=rows.group, req=rows.req, req_present=rows.req_present))
+        r.do("bound_load", dict(bound=bound))
+        # the three scratch blocks that are zero between calls get their first size: marks for 1023 ids and 255 groups, sums for 16 nodes
+        r.do("forget", dict(ids=np.array([3, 1000], np.uint32)))
+        r.do("expire", dict(groups=[7, 200], deny=False))
+        r.do("pass")
+        pk = r.do("park")
+        assert pk["n"] == 510 and w.wt.w > 1023 + 1023 // 4 and w.wt.ids == 1533, "the park stays inside the table's headroom"
+        r.do("forget", dict(ids=np.array([5, 1500, 1279], np.uint32)))            # 1533 ids: the marks by id are allocated again
+        r.do("list", dict(remove=[], update=[], rows=wf.new_group_rows(rng, S, 2), n_append=2), flat=True)
+        assert w.g == 257
+        r.do("expire", dict(groups=[256, 0, 128], deny=True))                   # the per-group marks under the new G
+        r.do("list", dict(remove=[3, 255], update=[], rows=wf.new_group_rows(rng, S, 0), n_append=0))
+        assert w.g == 255
+        ins = wf.new_bound(rng, S, 100, N, w.g)
+        ins.group[:] = np.where(ins.group < 0, 1, ins.group)
+        r.do("bound_apply_ex", dict(remove=w.bt.id[:3].astype(np.uint32), insert=ins, pdb=rng.integers(0, 2, 100).astype(np.uint8)))
+        assert w.bt.count == 297 > 200 + 200 // 4, "the delta stays inside the bound table's headroom"
+        big = wf.new_pods(rng, S, np.full(6, soa.POD_NOT_GROUPED))                # six pods that fit nowhere until bound pods leave
+        big.cls[:] = 0
+        big.req[0] = int((w.nl.alloc[0] - w.nl.req[0]).max()) + 20 + 5 * np.arange(6)
+        r.do("pods", dict(remove=np.zeros(0, np.uint32), insert=big))
+        idx = np.arange(w.pods.p - 6, w.pods.p, dtype=np.uint32)
+        cm = r.do("commit", dict(pod_index=idx, priority=np.full(6, 5000, np.int32), protected=np.zeros(w.g, np.uint8), apply=True, assume=False))
+        assert int(cm["res"]["n_victims"].sum()) >= 6 and w.bt.count <= 297 - 6, "the commit compacts nothing"
+        out = r.do("list", dict(remove=list(range(10, 110)), update=[5], rows=wf.new_group_rows(rng, S, 1), n_append=0), flat=True)
+        assert w.g == 155 and w.wt.w < 1024 and out["n_wait_dropped"] > 500
+        r.do("release", dict(groups=[154, 0]))
+        r.do("list", dict(remove=[], update=[], rows=wf.new_group_rows(rng, S, 170), n_append=170))
+        r.do("nodes", dict(ops=[(wf.APPEND, k % N) for k in range(48)]))
+        r.do("wait_nodes")
+        r.do("bound_nodes")
+        assert (w.g, w.n) == (325, 64)
+        ex = r.do("expire", dict(groups=[324, 20, 0, 100], deny=True))            # 325 groups, 64 nodes: the marks by group and the sums are allocated again
+        assert ex["n"] > 0
+        r.do("forget", dict(ids=w.wt.id[[0, -1]].astype(np.uint32)))
+        r.against_fresh()
+
+
+def test_gang_read_keeps_the_group_count_of_its_call(bsa, soa, orc):
+    """include/bsched.h: bs_preempt_gang_read's arrays are those of the last bs_preempt_commit_gang.  After a bs_groups_list_apply that changes g
+    they are read with the g of that call; the new g is BS_ERR_INVALID"""
+    sc = wf.scene(9)
+    rng = np.random.default_rng(5)
+    with Runner(bsa, soa, orc, sc, "gang read") as r:
+        w = r.w
+        r.do("wait_load", dict(node=(), group=(), req=None, req_present=None))
+        r.do("bound_load", dict(bound=sc["bound"]))
+        r.do("pass")
+        cg = r.do("commit_gang", _gang_preemptors(w))
+        q, g_old = len(cg["res"]["node"]), w.g
+        assert cg["group_placed"].any()
+        r.do("list", dict(remove=[0], update=[], rows=wf.new_group_rows(rng, w.S, 3), n_append=3))
+        assert w.g == g_old + 2
+        voided, placed = r.gang_read(q, g_old)
+        assert np.array_equal(voided, cg["slot_voided"]) and np.array_equal(placed, cg["group_placed"]), "the values of that call, under its g"
+        assert status_of(bsa, lambda: r.gang_read(q, w.g)) == wf.INVALID
+        assert status_of(bsa, lambda: r.gang_read(q + 1, g_old)) == wf.INVALID

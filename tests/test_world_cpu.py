@@ -1,0 +1,237 @@
+"""The plan and the model alone, no GPU (tests/world_ref.py): the twelve fixed seeds are drawn, replayed on a fresh World step by step, and
+what the GPU replay of tests/test_gpu_world.py relies on is asserted here on the model: every row of calls and every hazard pair occurs
+often enough, the structural invariants hold after every step, the references stay inside their domains, a predicted refusal changes
+nothing.
+
+"Kind" is read as a row of the issue's table (queue, groups, list, nodes, wait, window, bound, pdb, preempt): nine rows, at least 2 per
+seed and 30 over all seeds.  (The 25 single entry points cannot each occur 30 times in 12 x 40 steps.)  On top of that every single
+entry point must occur at least 4 times over all seeds."""
+import copy
+
+import numpy as np
+import pytest
+
+import world_ref as wf
+
+SEEDS = list(range(wf.SEEDS))
+HAZARDS = ("a", "b", "c_wait_first", "c_bound_first", "c_refused_between", "d", "e", "f", "g", "h", "leader_moves")
+
+
+def _snapshot(w):
+    """the model's whole state as plain arrays, for "a refusal changes nothing" """
+    r = w.reads()
+    out = {k: copy.deepcopy(v) for k, v in r.items() if k not in ("groups", "pods")}
+    out["groups"], out["pods"] = r["groups"].copy(), r["pods"].copy()
+    out["extra"] = (w.leader, w.bound_max, w.window, list(w.pend_w), list(w.pend_b), None if w.wt is None else (w.wt.n, w.wt.g),
+                    None if w.bt is None else w.bt.n)
+    return out
+
+
+def _same(a, b):
+    if isinstance(a, dict):
+        return a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    if isinstance(a, np.ndarray):
+        return np.array_equal(a, b)
+    if hasattr(a, "min_member"):
+        return all(np.array_equal(getattr(a, c), getattr(b, c)) for c in wf.gl.COLUMNS)
+    if hasattr(a, "equal"):
+        return a.equal(b)
+    return a == b
+
+
+class Hazards:
+    """the hazard pairs as small state machines over the replayed steps; a reload of a table (bs_bound_load, bs_wait_load) resets them"""
+
+    def __init__(self):
+        self.count = dict.fromkeys(HAZARDS, 0)
+        self.e_kinds = set()
+        self.reset()
+
+    def reset(self):
+        self.a = self.b = self.f = self.g = self.h = self.lm = 0
+        self.c = None                      # after node surgery: the *_nodes_apply calls seen so far
+        self.d, self.e = False, None
+
+    def see(self, kind, args, refused, before, w, out):
+        hit = lambda k: self.count.__setitem__(k, self.count[k] + 1)
+        if refused:
+            if self.c is not None and len(self.c) == 1 and kind in wf.WAIT_CALLS + wf.BOUND_CALLS:
+                hit("c_refused_between")
+            return
+        if kind in ("bound_load", "wait_load"):
+            self.reset()
+            return
+        # (a) park, a list delta that removes a group with wait rows and bound entries, a gang commit that applies
+        if kind == "park":
+            self.a = max(self.a, 1)
+        elif kind == "list" and self.a >= 1 and before["hot_removed"]:
+            self.a = 2
+        elif kind == "commit_gang" and self.a == 2 and args["apply"]:
+            hit("a")
+            self.a = 0
+        # (b) pass, commit(APPLY | ASSUME), bs_seq_expire with the window still open
+        if kind == "pass":
+            self.b = 1
+        elif not w.window:
+            self.b = 0
+        elif kind == "commit" and self.b == 1 and args["apply"] and args["assume"]:
+            self.b = 2
+        elif kind == "seq_expire" and self.b == 2:
+            hit("b")
+            self.b = 0
+        # (c) APPEND / REMOVE, then both *_nodes_apply, in both orders
+        if kind == "nodes" and any(k != wf.UPDATE for k, _ in args["ops"]):
+            self.c = [] if self.c is None or len(self.c) == 2 else self.c
+        elif kind in ("wait_nodes", "bound_nodes") and self.c is not None and kind not in self.c:
+            self.c.append(kind)
+            if len(self.c) == 2:
+                hit("c_wait_first" if self.c[0] == "wait_nodes" else "c_bound_first")
+                self.c = None
+        # (d) g changes, then bs_wait_expire / bs_wait_release by group
+        if kind == "list" and out["g_new"] != before["g"]:
+            self.d = True
+        elif kind in ("expire", "release") and self.d:
+            hit("d")
+            self.d = False
+        # (e) the node count grows, then bs_wait_expire / bs_wait_forget / bs_seq_expire
+        if kind == "nodes" and w.n > before["n"]:
+            self.e = set()                 # the calls seen since the count grew: each counts once per growth
+        elif kind in ("expire", "forget", "seq_expire") and self.e is not None and kind not in self.e:
+            hit("e")
+            self.e.add(kind)
+            self.e_kinds.add(kind)
+        # (f) batch, an update-only delta, an append-only delta, batch
+        if kind == "batch":
+            if self.f == 3:
+                hit("f")
+            self.f = 1
+        elif kind == "list":
+            only_update = len(args["update"]) and not len(args["remove"]) and not args["n_append"]
+            only_append = args["n_append"] and not len(args["remove"]) and not len(args["update"])
+            self.f = 2 if self.f == 1 and only_update else 3 if self.f == 2 and only_append else self.f if self.f and (only_update or only_append) else 0
+        # (g) commit with APPLY, bs_bound_apply_ex, bs_pdb_allowed_apply, commit
+        if kind in ("commit", "commit_gang"):
+            if self.g == 3:
+                hit("g")
+                self.g = 0
+            if args["apply"]:
+                self.g = 1
+        elif kind == "bound_apply_ex" and self.g == 1 and args["insert"] is not None:
+            self.g = 2
+        elif kind == "pdb_allowed" and self.g == 2:
+            self.g = 3
+        # (not in the issue's list; a stale carried leader showed in one seed only without it) a group below the leader leaves, so the leader's
+        # index moves with its group; then a batch or a pass, whose pf_leader starts from it
+        if kind == "list" and 0 <= w.leader != before["leader"]:
+            self.lm = 1
+        elif kind in ("batch", "pass") and self.lm:
+            hit("leader_moves")
+            self.lm = 0
+        # (h) a pass that leaves a leader, the leader's group removed, a batch, a pass
+        if kind == "pass":
+            if self.h == 3:
+                hit("h")
+            self.h = 1 if w.leader >= 0 else 0
+        elif kind == "list" and self.h == 1 and before["leader"] >= 0 and w.leader < 0:
+            self.h = 2
+        elif kind == "batch" and self.h == 2:
+            self.h = 3
+
+
+@pytest.fixture(scope="module")
+def replayed(orc):
+    """every seed drawn and replayed once: per seed the counts, the hazards, and what the steps showed"""
+    hz = Hazards()
+    seeds = []
+    for seed in SEEDS:
+        sc, steps = wf.plan(seed, orc)
+        assert len(steps) == wf.STEPS
+        w = wf.world_of(orc, sc)
+        hz.reset()
+        kinds, rows, refusals = {}, dict.fromkeys(wf.ROWS, 0), 0
+        shared_node = evicted_waiting = False
+        n_seen, victims = {w.n}, 0
+        for i, (kind, args, refused) in enumerate(steps):
+            where = f"seed {seed} step {i} {kind}"
+            before = dict(g=w.g, n=w.n, leader=w.leader, hot_removed=False)
+            if kind == "list" and w.wt is not None and w.bt is not None:
+                before["hot_removed"] = any(np.any(w.wt.group == x) and np.any(w.bt.group == x) for x in args["remove"])
+            snap = _snapshot(w) if refused else None
+            out = w.step(kind, args)                                            # (a reference that leaves its domain raises here)
+            assert (out["status"] != wf.OK) == refused, f"{where}: status {out['status']}"
+            if refused:
+                assert _same(snap, _snapshot(w)), f"{where}: a refused call changed the model"
+                refusals += 1
+            else:
+                kinds[kind] = kinds.get(kind, 0) + 1
+                rows[wf.ROW_OF[kind]] += 1
+            w.invariants()
+            hz.see(kind, args, refused, before, w, out)
+            n_seen.add(w.n)
+            if w.wt is not None and w.wt.w:
+                pairs = {(int(a), int(b)) for a, b in zip(w.wt.node, w.wt.group)}
+                shared_node |= len(pairs) > len({a for a, _ in pairs})
+            if not refused and kind in ("commit", "commit_gang") and args["apply"]:
+                victims += int(out["res"]["n_victims"].sum())
+                if w.wt is not None and out["victim_groups"].size:
+                    evicted_waiting |= bool(np.isin(out["victim_groups"], w.wt.group).any())
+        seeds.append(dict(seed=seed, S=sc["S"], kinds=kinds, rows=rows, refusals=refusals, shared_node=shared_node, evicted_waiting=evicted_waiting,
+                          n_seen=n_seen, victims=victims, g0=sc["groups"].g, p0=sc["pods"].p, b0=sc["bound"].b))
+    total_rows = {r: sum(s["rows"][r] for s in seeds) for r in wf.ROWS}
+    total_kinds = {k: sum(s["kinds"].get(k, 0) for s in seeds) for k in wf.ROW_OF}
+    print("\nrows over all seeds:", total_rows)
+    print("entry points over all seeds:", total_kinds)
+    print("hazard pairs over all seeds:", hz.count, "(e) through", sorted(hz.e_kinds))
+    for s in seeds:
+        print(f"seed {s['seed']}: S={s['S']} g0={s['g0']} p0={s['p0']} b0={s['b0']} n {min(s['n_seen'])}..{max(s['n_seen'])} refusals {s['refusals']} "
+              f"victims {s['victims']} rows {s['rows']}")
+    return dict(seeds=seeds, rows=total_rows, kinds=total_kinds, hazards=hz)
+
+
+def test_the_scenes_are_the_sizes_the_issue_names(replayed):
+    seeds = replayed["seeds"]
+    assert {s["S"] for s in seeds} == {0, 1, 2, 12}
+    for s in seeds:
+        assert 24 <= s["g0"] <= 40 and s["p0"] <= 200 and 0 <= s["b0"] <= 300
+    assert any(min(s["n_seen"]) <= 4 < max(s["n_seen"]) for s in seeds), "no seed takes its node count across 4"
+    assert any(min(s["n_seen"]) <= 64 < max(s["n_seen"]) for s in seeds), "no seed takes its node count across 64"
+    assert sum(1 for s in seeds if 12 <= min(s["n_seen"]) and max(s["n_seen"]) <= 40) >= 8, "the other seeds stay at 12 - 40 nodes"
+    assert {s["b0"] for s in seeds} >= {0, 300}
+
+
+def test_every_row_of_calls_occurs_often_enough(replayed):
+    for s in replayed["seeds"]:
+        for row, c in s["rows"].items():
+            assert c >= 2, f"seed {s['seed']}: {row} occurs {c} times"
+    for row, c in replayed["rows"].items():
+        assert c >= 30, f"{row} occurs {c} times over all seeds"
+    for k, c in replayed["kinds"].items():
+        assert c >= 4, f"entry point {k} occurs {c} times over all seeds"
+
+
+def test_a_sixth_of_the_steps_are_refusals(replayed):
+    for s in replayed["seeds"]:
+        assert 6 <= s["refusals"] <= 9, f"seed {s['seed']}: {s['refusals']} refusals in {wf.STEPS} steps"
+
+
+def test_every_hazard_pair_occurs_three_times(replayed):
+    hz = replayed["hazards"]
+    for k, c in hz.count.items():
+        assert c >= 3, f"hazard pair ({k}) occurs {c} times: {hz.count}"
+    assert hz.e_kinds == {"expire", "forget", "seq_expire"}, f"(e) is reached through {hz.e_kinds} only"
+
+
+def test_gangs_share_nodes_and_a_commit_evicts_beside_a_waiting_pod(replayed):
+    for s in replayed["seeds"]:
+        assert s["shared_node"], f"seed {s['seed']}: never wait rows of two groups on one node"
+    assert any(s["evicted_waiting"] for s in replayed["seeds"]), "no commit evicts a victim that shares its group with a wait row"
+    assert sum(s["victims"] for s in replayed["seeds"]) >= 30, "the commits evict next to nothing"
+
+
+def test_the_plan_is_a_function_of_the_seed(orc):
+    a, b = wf.plan(3, orc)[1], wf.plan(3, orc)[1]
+    assert [(k, r) for k, _, r in a] == [(k, r) for k, _, r in b]
+    assert all(_same({x: v for x, v in s[1].items() if not hasattr(v, "as_struct")}, {x: v for x, v in t[1].items() if not hasattr(v, "as_struct")})
+               for s, t in zip(a, b))

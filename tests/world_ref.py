@@ -1,0 +1,965 @@
+"""One model of everything a context holds (TEST INFRASTRUCTURE): the queue, the group list and the leader, the node list and its requests,
+the Permit-wait table, bs_seq_expire's window, the bound-pod table with its ids and PDB bits, the resident PDBs.  `World` adds no arithmetic
+of its own: every transition hands the world's arrays to the reference that already states the call (tests/*_ref.py, the oracle) and takes
+them back.  What two references would each keep a copy of has ONE home here:
+
+  node requests     World.nl.req / .rpres   (handed to seq_expire_ref.State and bound_apply_nodes_ref.State as views, to the preemption
+                                             references as a soa.Nodes over the same arrays)
+  group columns     World.groups            (matched and flags are handed to the wait references as views)
+  bound group column  World.bt.group        (handed to groups_list_ref.list_apply and taken back; nobody else keeps one)
+  wait rows         World.wt                (wait_ref.Table)
+
+`World.step(kind, args)` applies one call and returns what the call returns, or {"status": code} for a call the header refuses (the validity
+paragraphs of include/bsched.h: stale counts, the window) — a refused call changes nothing here.  `plan(seed)` draws scenes and operation
+sequences on a World of its own, so that whoever replays the steps on a fresh World (tests/test_world_cpu.py) or on a World beside a device
+context (tests/test_gpu_world.py) sees the same sequence."""
+from __future__ import annotations
+
+import importlib
+
+import numpy as np
+
+import bound_apply_nodes_ref as ban
+import bound_apply_ref as ba
+import bound_nodes_ref as bn
+import groups_list_ref as gl
+import pdb_resident_ref as pdr
+import preempt_gang_ref as pg
+import preempt_pdb_ref as pp
+import seq_expire_ref as ser
+import wait_nodes_ref as wnr
+import wait_ref as wr
+
+bsa = importlib.import_module("batch-scheduler_amd")
+soa, capi = bsa.soa, bsa.capi
+
+OK, INVALID, STATE = 0, -1, -4
+UPDATE, APPEND, REMOVE = bn.UPDATE, bn.APPEND, bn.REMOVE
+CAP = 16                                   # victim_cap of every preemption call
+# the rows of the table in the issue ("kinds"), and the entry points of each
+ROWS = {
+    "queue": ("pods",),
+    "groups": ("groups", "batch", "pass"),
+    "list": ("list",),
+    "nodes": ("nodes", "assume"),
+    "wait": ("wait_load", "park", "release", "expire", "forget", "wait_nodes"),
+    "window": ("seq_expire",),
+    "bound": ("bound_load", "bound_apply", "bound_apply_ex", "bound_nodes", "pdb_set"),
+    "pdb": ("pdb_load", "pdb_append", "pdb_allowed"),
+    "preempt": ("preempt", "commit", "commit_gang"),
+}
+ROW_OF = {k: row for row, ks in ROWS.items() for k in ks}
+WAIT_CALLS = ("park", "release", "expire", "forget")
+BOUND_CALLS = ("bound_apply", "bound_apply_ex", "pdb_set", "pdb_load", "pdb_append", "pdb_allowed", "preempt", "commit", "commit_gang")
+
+
+def id_map_by_table_order(ids) -> np.ndarray:
+    """the ids of a table loaded afresh with these live rows listed in ascending id: fresh id k is the k-th smallest live id.
+    -> keep [count]: keep[fresh id] = this table's id (monotone)"""
+    return np.sort(np.asarray(ids, np.int64))
+
+
+def map_victims(res: dict, keep) -> dict:
+    """a preemption result of a table loaded afresh, restated in the ids of the table it was loaded from"""
+    out = dict(res)
+    cap = res["victims"].shape[1]
+    live = np.arange(cap)[None] < np.minimum(res["n_victims"], cap)[:, None]
+    out["victims"] = np.where(live, keep[res["victims"]] if len(keep) else 0, 0).astype(np.uint32)
+    return out
+
+
+class World:
+    def __init__(self, orc, nodes, fit, groups, pods):
+        self.orc = orc
+        self.S = nodes.lanes - 4
+        self.nl = bn.NodeList(nodes, fit)
+        self.groups, self.pods, self.leader = groups.copy(), pods.copy(), -1
+        self.wt = None                     # wait_ref.Table
+        self.wait_node = None              # the window: per queue pod the node it waits on, or None while the window is shut
+        self.bt = None                     # bound_apply_ref.Table
+        self.bound_max = -1                # the largest group index the bound table is held to name
+        self.pm = None                     # pdb_resident_ref.Model
+        self.pend_w, self.pend_b = [], []  # node deltas (kind, index) the wait table / the bound table has not followed yet
+        self.gang = None                   # the last successful preemption call, when it was bs_preempt_commit_gang: (q, g, voided, placed)
+        self.placed = None                 # queue pods the last pass gave a node (until the queue changes): what a caller binds or parks
+        self.unplaced = None               # queue pods that passed PreFilter in the last pass and found no node: the preemptors
+        self.last = None                   # the last pass's record, while the queue is the one it ran on
+
+    # ---- counts and validity, as the header states them -------------------------------------------------------------------------------
+    @property
+    def n(self) -> int:
+        return self.nl.n
+
+    @property
+    def g(self) -> int:
+        return int(self.groups.g)
+
+    @property
+    def window(self) -> bool:
+        return self.wait_node is not None
+
+    def wait_ok(self) -> bool:
+        return self.wt is not None and self.wt.n == self.n and self.wt.g == self.g
+
+    def bound_ok(self) -> bool:
+        return self.bt is not None and self.bt.n == self.n
+
+    def preempt_ok(self) -> int:
+        if not self.bound_ok():
+            return STATE
+        return INVALID if self.bound_max >= self.g else OK
+
+    def nodes(self):
+        """a soa.Nodes over the world's own arrays (no copy)"""
+        return self.nl.nodes()
+
+    def fit(self):
+        return self.nl.fit()
+
+    def _st(self):
+        """seq_expire_ref.State over the world's own arrays: what the wait references change is changed here"""
+        st = object.__new__(ser.State)
+        st.requested, st.requested_present = self.nl.req, self.nl.rpres
+        st.matched, st.flags = self.groups.matched, self.groups.flags
+        st.wait_node = self.wait_node if self.wait_node is not None else np.full(self.pods.p, -1, np.int32)
+        return st
+
+    def _bound_state(self):
+        """bound_apply_nodes_ref.State over the world's table and node requests"""
+        s = object.__new__(ban.State)
+        s.S, s.n, s.t, s.req, s.pres = self.S, self.n, self.bt, self.nl.req, self.nl.rpres
+        return s
+
+    def _shut(self):
+        self.wait_node = None
+
+    def _queue_changed(self):
+        self._shut()
+        self.placed = self.unplaced = self.last = None
+
+    def _recompute_bits(self):
+        self.bt.pdb = self.pm.bits(self.bt.ids)[self.bt.id.astype(np.int64)].astype(np.uint8)
+
+    # ---- what the cheap reads return ------------------------------------------------------------------------------------------------
+    def reads(self) -> dict:
+        """everything bs_*_read returns now; a read the header refuses in this state is None"""
+        leader, _, panic = self.orc.find_max_pg(self.groups)
+        out = dict(groups=self.groups, pods=self.pods, node_req=self.nl.req, node_pres=self.nl.rpres, find_max_pg=(leader, panic),
+                   wait=None, wait_count=None, wait_ids=None, bound=None, bound_ids=None, pdb=None,
+                   waiting=None if self.wait_node is None else self.wait_node)
+        if self.wt is not None:
+            out["wait_count"], out["wait_ids"] = self.wt.w, self.wt.ids
+            if self.wait_ok():
+                out["wait"] = self.wt.columns()
+        if self.bt is not None:
+            out["bound"], out["bound_ids"] = self.bt.table(), self.bt.ids
+            if self.pm is not None and self.bound_ok():
+                t = out["bound"]
+                nv = np.bincount(t["node"].astype(np.int64), weights=t["pdb"], minlength=self.n).astype(np.uint32)[: self.n]
+                out["pdb"] = dict(n_pdb=self.pm.n_pdb, covered=self.pm.covered, allowed=self.pm.allowed, node_violating=nv)
+        return out
+
+    def invariants(self):
+        """structural invariants that hold after every step"""
+        g, n = self.g, self.n
+        cols = [("queue", self.pods.group)]
+        if self.wt is not None:
+            cols.append(("wait", self.wt.group))
+            assert np.all(np.diff(self.wt.id.astype(np.int64)) > 0), "wait ids ascend strictly"
+            assert self.wt.w == 0 or int(self.wt.id[-1]) < self.wt.ids
+            if self.wt.n == n:
+                assert np.all(self.wt.node < n), "a wait row names a node >= n"
+            assert np.all(self.wt.group >= 0), "a wait row without a group"
+        if self.bt is not None:
+            cols.append(("bound", self.bt.group))
+            assert np.unique(self.bt.id).size == self.bt.count, "bound ids are unique"
+            assert self.bt.count == 0 or int(self.bt.id.max()) < self.bt.ids
+            if self.bt.n == n:
+                assert np.all(self.bt.node < n), "a bound entry names a node >= n"
+            assert int(self.bt.group.max(initial=-2)) <= self.bound_max or self.bt.count == 0 or int(self.bt.group.max()) < 0, "bound_max_group bounds the bound column"
+        for name, col in cols:
+            col = np.asarray(col, np.int64)
+            assert np.all((col < g) & (col >= gl.MISSING)), f"{name}: a group index that is neither a sentinel nor < g"
+        if self.wait_node is not None:
+            assert self.wait_node.size == self.pods.p and np.all(self.wait_node < n)
+
+    # ---- the calls --------------------------------------------------------------------------------------------------------------------
+    def step(self, kind: str, a: dict) -> dict:
+        """one call: -> its results with status 0, or {"status": code} and nothing changed"""
+        out = getattr(self, "_" + kind)(**a)
+        out = {} if out is None else out
+        out.setdefault("status", OK)
+        return out
+
+    def _pods(self, remove=(), insert=None):
+        self.pods = self.pods.patched(remove=remove, insert=insert, insert_at=None)
+        self._queue_changed()
+
+    def _groups(self, deltas):
+        for i, m, s, f in deltas:
+            self.groups.matched[i], self.groups.status_scheduled[i], self.groups.flags[i] = m, s, f
+
+    def _batch(self, stages, commit):
+        sop = self.orc.Sop(self.orc.Snapshot(self.nodes(), self.fit()), self.groups).carry(self.leader)
+        exp = sop.batch(self.pods, stages, bitmap=False)
+        if commit:
+            self.groups, self.leader = sop.groups, sop.leader
+        return dict(batch=exp)
+
+    def _pass(self):
+        nodes, fit = self.nodes().copy(), self.fit()
+        s = self.orc.seq_replay(nodes, fit, self.groups, self.pods, soa.STAGE_PREFILTER, leader=self.leader)
+        wait, _ = ser.waiting_after_pass(nodes, fit, self.groups, self.pods, s)
+        self.nl.req, self.nl.rpres = s["nodes"].requested.copy(), s["nodes"].requested_present.copy()
+        self.groups, self.leader, self.wait_node = s["groups"], s["leader"], wait
+        self.placed = np.nonzero((s["pod_node"] >= 0) | (wait >= 0))[0]
+        grouped = (self.pods.group >= 0) & (self.pods.group < self.g)
+        self.unplaced = np.nonzero((s["pf_code"] < 16) & (s["pod_node"] < 0) & (wait < 0) & grouped)[0]
+        self.last = s
+        return dict(seq=s)
+
+    def _list(self, remove, update, rows, n_append):
+        g = self.g
+        code = gl.check(g, remove, update, rows.g, n_append)
+        if code != gl.OK:
+            return dict(status=INVALID)
+        if not len(remove) and not len(update) and not n_append:
+            return dict(g_new=g, n_pods_missing=0, n_bound_missing=0, n_wait_dropped=0, wait_id=np.zeros(0, np.uint32), wait_node=np.zeros(0, np.uint32),
+                        wait_group=np.zeros(0, np.int32))
+        wait = self.wt.columns() if self.wt is not None and self.wt.g == g else None
+        m = gl.list_apply(self.groups, remove, update, rows, self.pods.group, None if self.bt is None else self.bt.group, wait, self.leader)
+        self.groups, self.leader = m["groups"], m["leader"]
+        self.pods.group[:] = m["pod_group"]
+        if self.bt is not None:
+            self.bt.group = m["bound_group"]
+            self.bound_max = gl.max_group(self.bound_max, g, remove)
+        if wait is not None:
+            t = self.wt
+            t.id, t.node, t.group, t.req, t.req_present = (m["wait"][k] for k in ("id", "node", "group", "req", "req_present"))
+            t.g = m["g_new"]
+        self._shut()
+        self.last = None                   # (its released_group names old indices)
+        d = m["dropped"]
+        return dict(g_new=m["g_new"], n_pods_missing=m["n_pods_missing"], n_bound_missing=m["n_bound_missing"], n_wait_dropped=len(d[0]),
+                    wait_id=d[0], wait_node=d[1], wait_group=d[2])
+
+    def _nodes(self, ops):
+        """ops: [(UPDATE, index) | (APPEND, like) | (REMOVE, index)] -> the bs_node_delta list"""
+        deltas = [self.nl.update(i) if k == UPDATE else self.nl.append(i) if k == APPEND else self.nl.remove(i) for k, i in ops]
+        pairs = [(int(d.kind), int(d.index)) for d in deltas]
+        if any(k != UPDATE for k, _ in pairs):
+            self._shut()
+            self.last = None               # (its pod_node names old indices)
+        if self.wt is not None:
+            self.pend_w += pairs
+        if self.bt is not None:
+            self.pend_b += pairs
+        return dict(deltas=deltas)
+
+    def _assume(self, reqs):
+        for idx, lanes, pres in reqs:
+            self.nl.req[:, idx], self.nl.rpres[idx] = lanes, pres
+
+    # -- the wait table
+    def _wait_load(self, node, group, req, req_present):
+        self.wt = wr.load(self.n, self.g, self.S, node, group, req, req_present)
+        self.pend_w = []
+
+    def _park(self):
+        if not self.wait_ok() or not self.window:
+            return dict(status=STATE)
+        return wr.park(self._st(), self.wt, self.pods)
+
+    def _by_group(self, fn, groups):
+        if not self.wait_ok():
+            return dict(status=STATE)
+        try:
+            return fn(groups)
+        except wr.WaitError as e:
+            return dict(status=e.status)
+
+    def _release(self, groups):
+        return self._by_group(lambda gs: wr.release(self.wt, gs, self.n, self.g), groups)
+
+    def _expire(self, groups, deny):
+        return self._by_group(lambda gs: wr.expire(self._st(), self.wt, gs, deny=deny), groups)
+
+    def _forget(self, ids):
+        return self._by_group(lambda il: dict(node=wr.forget(self._st(), self.wt, il)), ids)
+
+    def _wait_nodes(self):
+        kind, index = [k for k, _ in self.pend_w], [i for _, i in self.pend_w]
+        if self.wt is None or self.wt.g != self.g:
+            return dict(status=STATE, kind=kind, index=index)
+        out = wnr.nodes_apply(self.wt, self.groups.matched, kind, index, n_expected=self.n, g=self.g)
+        self.pend_w = []
+        return dict(out, kind=kind, index=index)
+
+    # -- bs_seq_expire
+    def _seq_expire(self, groups, deny, all):
+        if not self.window:
+            return dict(status=STATE)
+        return ser.expire(self._st(), self.pods, groups=groups, deny=deny, all=all)
+
+    # -- the bound table
+    def _bound_load(self, bound):
+        self.bt = ba.Table(bound, self.S, self.n)
+        self.bound_max = int(bound.group.max(initial=-1)) if bound.b else -1
+        self.pm, self.pend_b = None, []
+
+    def _bound_delta(self, remove, insert, pdb, flags):
+        if not self.bound_ok():
+            return dict(status=STATE)
+        try:
+            first = self._bound_state().apply_ex(remove, insert, pdb, flags)
+        except ba.ApplyError as e:
+            return dict(status=e.status)
+        if insert is not None and insert.b:
+            self.bound_max = max(self.bound_max, int(insert.group.max()))
+        return dict(first_id=first)
+
+    def _bound_apply(self, remove, insert, pdb):
+        return self._bound_delta(remove, insert, pdb, 0)
+
+    def _bound_apply_ex(self, remove, insert, pdb, flags=ban.BOUND_NODES):
+        return self._bound_delta(remove, insert, pdb, flags)
+
+    def _bound_nodes(self):
+        kind, index = [k for k, _ in self.pend_b], [i for _, i in self.pend_b]
+        if self.bt is None:
+            return dict(status=STATE, kind=kind, index=index)
+        _, dropped, _ = bn.nodes_apply(self.bt, kind, index, n_expected=self.n)
+        self.pend_b = []
+        return dict(n_dropped=int(dropped.size), dropped=dropped, kind=kind, index=index)
+
+    def _pdb_set(self, bits):
+        if self.bt is None:
+            return dict(status=STATE)
+        self.bt.set_pdb(bits)
+
+    def _pdb_load(self, allowed, off, member):
+        if self.bt is None:
+            return dict(status=STATE)
+        assert len(off) - 1 == self.bt.ids
+        self.pm = pdr.Model(allowed, off, member)
+        self._recompute_bits()
+
+    def _pdb_append(self, off, member):
+        if self.bt is None or self.pm is None:
+            return dict(status=STATE)
+        first = self.pm.covered
+        assert first + len(off) - 1 <= self.bt.ids
+        self.pm.append(off, member)
+        self._recompute_bits()
+        return dict(first_id=first)
+
+    def _pdb_allowed(self, index, value):
+        if self.bt is None or self.pm is None:
+            return dict(status=STATE)
+        self.pm.allowed_apply(index, value)
+        self._recompute_bits()
+
+    # -- preemption
+    def _prep(self):
+        eq, keep, bits = self.bt.equivalent()
+        return eq, keep, pp.PdbPrep(self.nodes(), eq, self.S, bits)
+
+    def _preempt(self, pod_index, priority, protected):
+        code = self.preempt_ok()
+        if code:
+            return dict(status=code)
+        eq, keep, prep = self._prep()
+        self.gang = None
+        return dict(res=map_victims(pp.preempt_pdb_np(prep, self.fit(), self.pods, pod_index, priority, protected, CAP), keep))
+
+    def _written(self, r, keep, apply):
+        """what BS_PREEMPT_APPLY leaves: the node requests and the surviving entries"""
+        if apply:
+            self.nl.req, self.nl.rpres = r["req"].astype(np.int64), r["pres"].astype(np.uint32)
+            self.bt._keep(np.isin(self.bt.id, keep[r["bound_id"].astype(np.int64)] if len(keep) else []))
+
+    def _commit(self, pod_index, priority, protected, apply, assume):
+        code = self.preempt_ok()
+        if code:
+            return dict(status=code)
+        eq, keep, prep = self._prep()
+        r = pp.commit_pdb_np(prep, self.fit(), self.pods, eq, pod_index, priority, protected, CAP, apply, assume)
+        victims = [int(keep[v]) for i in range(len(pod_index)) for v in r["res"]["victims"][i, : min(int(r["res"]["n_victims"][i]), CAP)]]
+        vgroups = self.bt.group[np.isin(self.bt.id, victims)].copy()
+        self._written(r, keep, apply)
+        self.gang = None
+        return dict(res=map_victims(r["res"], keep), victim_groups=vgroups)
+
+    def _commit_gang(self, pod_index, priority, protected, need, apply, assume):
+        code = self.preempt_ok()
+        if code:
+            return dict(status=code)
+        eq, keep, prep = self._prep()
+        r = pg.gang_np(prep, self.fit(), self.pods, eq, np.asarray(pod_index), np.asarray(priority), protected, need, CAP, apply, assume)
+        victims = [int(keep[v]) for i in range(len(pod_index)) for v in r["res"]["victims"][i, : min(int(r["res"]["n_victims"][i]), CAP)]]
+        vgroups = self.bt.group[np.isin(self.bt.id, victims)].copy()
+        self._written(r, keep, apply)
+        self.gang = (len(pod_index), self.g, r["slot_voided"].copy(), r["group_placed"].copy())
+        return dict(res=map_victims(r["res"], keep), slot_voided=r["slot_voided"], group_placed=r["group_placed"], victim_groups=vgroups)
+
+    # ---- a context loaded afresh from the model's arrays --------------------------------------------------------------------------------
+    def fresh_arrays(self) -> dict:
+        """what a second context is loaded with: the bound and wait ids restart, so both come with their id maps (by table order)"""
+        out = dict(nodes=self.nodes().copy(), fit=self.fit(), groups=self.groups.copy(), pods=self.pods.copy(), wait=None, bound=None)
+        if self.wait_ok():
+            out["wait"], out["wait_keep"] = self.wt.columns(), id_map_by_table_order(self.wt.id)
+        if self.bound_ok():
+            eq, keep, bits = self.bt.equivalent()
+            assert np.array_equal(keep, id_map_by_table_order(self.bt.id))
+            out["bound"], out["bound_keep"], out["bound_bits"] = eq, keep, bits
+        return out
+
+
+# ======================================================================================================================================
+# scenes
+# ======================================================================================================================================
+N_START = [5, 63, 12, 40, 17, 33, 24, 13, 38, 29, 21, 36]       # seed 0 crosses 4 nodes downwards, seed 1 crosses 64 upwards
+SCALARS = [0, 1, 2, 12]
+BOUND_PRIO = np.array([0, 100, 200, 300])
+
+
+def new_pods(rng, S, groups_of, cls_max=2):
+    """queue pods as test_gpu_seq_expire.waiting_scene draws them, for the given group column"""
+    group = np.asarray(groups_of, np.int32)
+    P, L = group.size, 4 + S
+    req = np.zeros((L, P), np.int64)
+    req[0] = rng.integers(1, 20, P)
+    req[1] = rng.integers(1, 1 << 20, P)
+    pres = (rng.integers(0, 1 << S, P) if S else np.zeros(P, np.int64)).astype(np.uint32)
+    req[4:] = rng.integers(1, 4, (S, P)) * ((pres[None, :] >> np.arange(S, dtype=np.uint32)[:, None]) & 1)
+    return soa.Pods(group, req, pres, rng.integers(0, cls_max, P).astype(np.uint32), np.zeros(P, np.uint64), np.zeros(P, np.uint8))
+
+
+def new_bound(rng, S, b, n, g, nodes=None):
+    """bound entries: mostly grouped (an ungrouped or unknown-group entry of low priority keeps grouped preemptors off its whole node)"""
+    grp = rng.integers(0, g, b).astype(np.int32)
+    u = rng.random(b)
+    grp[u < 0.03] = soa.POD_NOT_GROUPED
+    grp[(u >= 0.03) & (u < 0.05)] = soa.POD_GROUP_MISSING
+    req = np.zeros((4 + S, b), np.int64)
+    req[0], req[1] = rng.integers(1, 50, b), rng.integers(1, 1 << 20, b)
+    pres = (rng.integers(0, 1 << S, b) if S else np.zeros(b, np.int64)).astype(np.uint32)
+    req[4:] = rng.integers(1, 4, (S, b)) * ((pres[None, :] >> np.arange(S, dtype=np.uint32)[:, None]) & 1)
+    node = rng.integers(0, n, b) if nodes is None else np.asarray(nodes)
+    return soa.Bound(node.astype(np.uint32), rng.choice(BOUND_PRIO, b).astype(np.int32), rng.integers(0, 50, b).astype(np.int64), grp, req, pres)
+
+
+def new_group_rows(rng, S, k):
+    """group rows as waiting_scene makes them: no captured pod, no MinResources; a quorum of 2 .. 6"""
+    rows = soa.Groups.empty(k, 4 + S)
+    rows.min_member[:] = rng.integers(2, 7, k)
+    return rows
+
+
+def scene(seed: int) -> dict:
+    """a gang scene built like test_gpu_seq_expire.waiting_scene: 24 - 40 gangs of 1 - 6 queue pods (at most 200), nodes whose pods lane
+    leaves room for about half of the queue, so a pass leaves pods waiting at Permit AND pods without a node; about a third of the gangs
+    can reach their quorum inside one pass.  0 - 300 bound entries whose requests the node requests already count."""
+    from test_gpu_seq_expire import waiting_scene
+    rng = np.random.default_rng(77000 + seed)
+    n, S = N_START[seed % len(N_START)], SCALARS[seed % 4]
+    G = int(rng.integers(24, 41))
+    lens = rng.integers(1, 7, G)
+    while lens.sum() > 200:
+        lens[int(rng.integers(0, G))] = 1
+    matched0 = rng.integers(0, 2, G)
+    nodes, fit, groups, pods = waiting_scene(soa, [int(x) for x in lens], n_nodes=n, S=S, pods_cap=110, interleave=bool(seed % 2),
+                                             matched0=[int(x) for x in matched0], seed=77100 + seed)
+    full = rng.random(G) < 0.35                                                 # these gangs reach their quorum when every member finds a node
+    groups.min_member[full] = (lens + matched0)[full]
+    pods.cls[:] = rng.integers(0, 2, pods.p)
+    fitb = np.ones((2, n), bool)
+    fitb[1] = rng.random(n) < 0.8
+    fit = soa.FitMasks.from_bool(fitb)
+    b = [0, 300, 120, 40][seed % 4] if seed < 4 else int(rng.integers(0, 301))
+    bound = new_bound(rng, S, b, n, G)
+    req, pres = ba.stored(bound, S)
+    with np.errstate(over="ignore"):
+        for l in range(4 + S):
+            np.add.at(nodes.requested[l], bound.node, req[l])
+        np.bitwise_or.at(nodes.requested_present, bound.node, pres)
+    # PreFilter sums every lane over the cluster, a pod needs ONE node: nodes with cpu and no pod slot left beside nodes with pod slots and
+    # little cpu keep the sums roomy (gangs pass PreFilter) while first fit runs out of nodes (pods without a node, whose preemption
+    # frees a pod slot on a cpu-rich node)
+    slots = rng.random(n) < 0.4
+    slots[int(rng.integers(0, n))] = True
+    slots[int((np.nonzero(slots)[0][0] + 1) % n)] = False
+    nodes.allocatable[3] = nodes.requested[3] + np.where(slots, 110, rng.integers(0, 2, n))
+    nodes.allocatable[0] = np.where(slots, nodes.requested[0] + (rng.uniform(0.5, 1.5, n) * 6 * pods.p / slots.sum()).astype(np.int64), nodes.allocatable[0])
+    return dict(seed=seed, S=S, nodes=nodes, fit=fit, groups=groups, pods=pods, bound=bound, gprio=rng.choice([50, 150, 250, 350, 5000], 64).astype(np.int32))
+
+
+def world_of(orc, sc) -> World:
+    return World(orc, sc["nodes"], sc["fit"], sc["groups"], sc["pods"])
+
+
+# ======================================================================================================================================
+# the plan
+# ======================================================================================================================================
+STEPS, SEEDS = 40, 12
+DEBUG = False
+# the hazard pairs of tests/test_world_cpu.py as call sequences; (kind, hint) asks the drawer for a particular shape of the call
+MOTIFS = {
+    "a": ["pass", "park", ("list", "hot"), ("commit_gang", "apply")],
+    "b": ["pods", "pass", ("commit", "assume"), ("seq_expire", "one"), "seq_expire"],
+    "c": [("nodes", "shrink"), "bound_nodes", ("refuse", "stale_wait"), "wait_nodes", "bound_apply", "pdb_set"],
+    "d": [("list", "resize"), ("expire", "any"), ("list", "resize"), "release"],
+    "e": [("nodes", "grow"), "wait_nodes", ("refuse", "stale_bound"), "bound_nodes", ("expire", "any"), "forget", "pass", ("seq_expire", "one"), "seq_expire"],
+    "f": [("batch", "plain"), ("list", "update"), "groups", ("list", "append"), ("batch", "plain")],
+    "h": ["pass", ("list", "below"), ("batch", "plain"), ("list", "leader"), ("batch", "commit"), "pods", "pass"],
+}
+MOTIF_ORDER = ["c", "e", "f", "h"]                          # (a, b and g are in every seed's first cycle; d comes about by itself)
+# the first cycle is the header's: pass, preemption for the pods without a node, the released gangs leave Permit and bind, the others park;
+# then a gang leaves the cache and the next preemption runs on what all that left behind.  An item that is not applicable is left out
+OPENING = ["pass", "pdb_load", ("commit", "assume"), ("seq_expire", "one"), ("release", "released"), ("bound_apply_ex", "bind"), "park", "pdb_allowed",
+           ("list", "hot"), ("commit_gang", "apply"), "pods"]
+REFUSALS = ["stale_wait", "stale_bound", "window", "list_order", "forget_dead", "expire_twice"]
+
+
+class Drawer:
+    """draws the arguments of one call on the world as it is; None when the call is not applicable now (the plan draws again)"""
+
+    def __init__(self, w: World, sc: dict, rng):
+        self.w, self.sc, self.rng = w, sc, rng
+        self.serial = 0
+
+    def draw(self, kind, hint=None):
+        w = self.w
+        if (w.pend_w or w.pend_b) and kind in WAIT_CALLS + BOUND_CALLS + ("list", "wait_load", "bound_load", "seq_expire", "pass", "pods", "assume"):
+            return None                    # between node-list surgery and the two *_nodes_apply only those, group patches, batches and refusals
+        return getattr(self, "d_" + kind)(hint)
+
+    # -- queue, groups
+    def d_pods(self, hint):
+        w, rng = self.w, self.rng
+        remove = w.placed if w.placed is not None and rng.random() < 0.8 else rng.choice(w.pods.p, min(w.pods.p, int(rng.integers(0, 6))), replace=False)
+        remove = np.sort(np.asarray(remove, np.int64))
+        k = int(min(rng.integers(4, 30), 200 - (w.pods.p - remove.size)))
+        grp = rng.integers(0, w.g, max(k, 0)).astype(np.int32)
+        u = rng.random(grp.size)
+        grp[u < 0.04] = soa.POD_NOT_GROUPED
+        grp[(u >= 0.04) & (u < 0.06)] = soa.POD_GROUP_MISSING
+        return dict(remove=remove.astype(np.uint32), insert=new_pods(rng, w.S, np.sort(grp)) if k > 0 else None)
+
+    def d_groups(self, hint):
+        w, rng = self.w, self.rng
+        deltas = []
+        if rng.random() < 0.5:             # the deny entries' TTL ran out
+            return dict(deltas=[(int(i), int(w.groups.matched[i]), int(w.groups.status_scheduled[i]), int(w.groups.flags[i]) & ~soa.GROUP_DENIED)
+                                for i in np.nonzero(w.groups.flags & soa.GROUP_DENIED)[0]] or [(0, int(w.groups.matched[0]), int(w.groups.status_scheduled[0]), int(w.groups.flags[0]))])
+        for i in rng.choice(w.g, 3, replace=False):
+            m = int(rng.integers(0, int(w.groups.min_member[i]) + 2))
+            f = (int(w.groups.flags[i]) & 0x16) | int(rng.random() < 0.1) | (soa.GROUP_DENIED * int(rng.random() < 0.2))
+            deltas.append((int(i), m, int(w.groups.status_scheduled[i]), f))
+        return dict(deltas=deltas)
+
+    def d_batch(self, hint):
+        commit = hint == "commit" or (hint is None and self.rng.random() < 0.3)
+        return dict(stages=soa.STAGE_ALL, commit=bool(commit))
+
+    def d_pass(self, hint):
+        return dict() if self.w.pods.p else None
+
+    def d_list(self, hint):
+        w, rng = self.w, self.rng
+        g = w.g
+        room_down, room_up = g - 24, 40 - g
+        remove, update, n_append = [], [], 0
+        if hint == "hot":                  # a group with wait rows AND bound entries leaves
+            if w.wt is None or w.bt is None:
+                return None
+            hot = np.intersect1d(w.wt.group, w.bt.group[w.bt.group >= 0])
+            if not hot.size:
+                return None
+            remove = [int(rng.choice(hot))]
+            n_append = 1 if room_down < 1 else int(rng.integers(0, 2))
+        elif hint == "leader":
+            if w.leader < 0:
+                return None
+            remove, n_append = [int(w.leader)], (1 if room_down < 1 else 0)
+        elif hint == "below":              # a group below the leader leaves: the leader the context carries moves down with its group
+            if w.leader < 1:
+                return None
+            remove, n_append = [int(rng.integers(0, w.leader))], (1 if room_down < 1 else 0)
+        elif hint == "update":
+            update = sorted(rng.choice(g, 2, replace=False).tolist())
+        elif hint == "append":
+            if room_up < 1:
+                return None
+            n_append = int(rng.integers(1, min(room_up, 3) + 1))
+        else:                              # "resize" changes g; None is anything
+            k = int(rng.integers(0 if hint is None else 1, 4))
+            remove = sorted(rng.choice(g, k, replace=False).tolist())
+            update = sorted(rng.choice(g, int(rng.integers(0, 3)), replace=False).tolist()) if hint is None else []
+            if remove and update and rng.random() < 0.3:
+                update = sorted(set(update) | {remove[0]})
+            n_append = int(rng.integers(0, 4))
+            while g - len(remove) + n_append > 40:
+                n_append -= 1
+            while g - len(remove) + n_append < 24:
+                n_append += 1
+            if hint == "resize" and n_append == len(remove):
+                n_append += 1 if g - len(remove) + n_append < 40 else -1
+        if g - len(remove) + n_append < 24 or g - len(remove) + n_append > 40:
+            return None
+        return dict(remove=remove, update=update, rows=new_group_rows(rng, w.S, len(update) + n_append), n_append=n_append)
+
+    # -- nodes
+    def d_nodes(self, hint):
+        w, rng = self.w, self.rng
+        n, lo = w.n, 3
+        hi = 66 if self.sc["nodes"].n > 60 else 40
+        ops = []
+        if hint is None:
+            hint = str(rng.choice(["shrink", "grow", "update", "swap"]))
+        like = lambda: int(rng.integers(0, self.sc["nodes"].n))
+        if hint == "grow" and n + 1 <= hi:
+            ops = [(APPEND, like()) for _ in range(min(hi - n, 3) if hi > 60 else int(rng.integers(1, min(hi - n, 3) + 1)))]
+            if rng.random() < 0.4:
+                ops.insert(0, (UPDATE, int(rng.integers(0, n))))
+        elif hint == "shrink" and n - 1 >= lo:
+            ops = [(REMOVE, int(rng.integers(0, n)))]
+            if n - 2 >= lo and hi <= 60 and rng.random() < 0.5:
+                ops.append((REMOVE, int(rng.integers(0, n - 1))))
+        elif hint == "swap":
+            ops = [(REMOVE, int(rng.integers(0, n))), (APPEND, like())]
+        elif hint == "update":
+            ops = [(UPDATE, int(rng.integers(0, n))) for _ in range(2)]
+        return dict(ops=ops) if ops else None
+
+    def d_assume(self, hint):
+        w, rng = self.w, self.rng
+        reqs = []
+        for k in rng.choice(w.n, min(3, w.n), replace=False):
+            lanes = w.nl.req[:, k].copy()
+            lanes[0] = max(int(lanes[0]) + int(rng.integers(-200, 30)), 0)      # pods the table does not hold ended, or started
+            lanes[1] += int(rng.integers(0, 1 << 16))
+            pres = int(w.nl.rpres[k])
+            if w.S and rng.random() < 0.5:
+                lanes[4] = (lanes[4] if pres & 1 else 0) + 1
+                pres |= 1
+            reqs.append((int(k), [int(x) for x in lanes], pres))
+        return dict(reqs=reqs)
+
+    # -- the wait table
+    def d_wait_load(self, hint):
+        w, rng = self.w, self.rng
+        k = int(rng.integers(0, 30))
+        pods = new_pods(rng, w.S, rng.integers(0, w.g, k))
+        return dict(node=rng.integers(0, w.n, k).astype(np.uint32), group=pods.group, req=pods.req, req_present=pods.req_present)
+
+    def d_park(self, hint):
+        w = self.w
+        return dict() if w.wait_ok() and w.window and np.any(w.wait_node >= 0) else None
+
+    def _wait_groups(self, hint):
+        w, rng = self.w, self.rng
+        if not w.wait_ok() or not w.wt.w:
+            return None
+        have = np.unique(w.wt.group)
+        gs = rng.permutation(have)[: int(rng.integers(1, 4))].tolist()
+        if rng.random() < 0.3:
+            gs.append(int(rng.choice(np.setdiff1d(np.arange(w.g), gs))))       # a listed group without rows
+        return [int(x) for x in gs]
+
+    def d_release(self, hint):
+        w = self.w
+        if hint == "released":             # the cycle's call: the gangs the pass released, with or without rows in the table
+            if not w.wait_ok() or w.last is None or not w.last["n_released"]:
+                return None
+            return dict(groups=[int(x) for x in w.last["released_group"]])
+        gs = self._wait_groups(hint)
+        return None if gs is None else dict(groups=gs)
+
+    def d_expire(self, hint):
+        gs = self._wait_groups(hint)
+        return None if gs is None else dict(groups=gs, deny=bool(self.rng.random() < 0.5))
+
+    def d_forget(self, hint):
+        w, rng = self.w, self.rng
+        if not w.wait_ok() or not w.wt.w:
+            return None
+        return dict(ids=rng.permutation(w.wt.id)[: int(rng.integers(1, 4))].astype(np.uint32))
+
+    def d_wait_nodes(self, hint):
+        return dict() if self.w.wt is not None and self.w.pend_w else None
+
+    def d_seq_expire(self, hint):
+        w, rng = self.w, self.rng
+        if not w.window:
+            return None
+        if not np.any(w.wait_node >= 0):   # nobody waits: a listed group is expired all the same (matched = 0); the motifs want more
+            return dict(groups=[int(rng.integers(0, w.g))], deny=False, all=False) if hint is None and w.last is not None else None
+        if hint is None and rng.random() < 0.15:
+            return dict(groups=None, deny=bool(rng.random() < 0.5), all=True)
+        have = np.unique(w.pods.group[w.wait_node >= 0])
+        return dict(groups=[int(x) for x in rng.permutation(have)[: 1 if hint == "one" else int(rng.integers(1, 4))]], deny=bool(rng.random() < 0.5), all=False)
+
+    # -- the bound table
+    def d_bound_load(self, hint):
+        w, rng = self.w, self.rng
+        if w.bt is None:
+            return dict(bound=self.sc["bound"])
+        return dict(bound=new_bound(rng, w.S, int(rng.integers(0, 301)), w.n, w.g))
+
+    def _bound_delta(self, hint):
+        w, rng = self.w, self.rng
+        if not w.bound_ok():
+            return None
+        live = w.bt.id
+        remove = rng.permutation(live)[: int(rng.integers(0, min(live.size, 5) + 1))].astype(np.uint32)
+        k = int(rng.integers(1 if hint == "insert" else 0, 9))
+        insert, pdb = None, None
+        if k:
+            insert = new_bound(rng, w.S, k, w.n, w.g)
+            pdb = rng.integers(0, 2, k).astype(np.uint8) if rng.random() < 0.5 else None
+        if not k and not remove.size:
+            return None
+        return dict(remove=remove, insert=insert, pdb=pdb)
+
+    def d_bound_apply(self, hint):
+        return self._bound_delta(hint)
+
+    def d_bound_apply_ex(self, hint):
+        w, rng = self.w, self.rng
+        if hint == "bind":                 # the cycle's bind: the pods the last pass released leave Permit and are bound where they sit
+            if not w.bound_ok():
+                return None
+            s = w.last
+            idx = np.nonzero(s["pod_node"] >= 0)[0] if s is not None else np.zeros(0, np.int64)
+            if not idx.size:
+                return self._bound_delta("insert")
+            p = w.pods
+            ins = soa.Bound(s["pod_node"][idx].astype(np.uint32), rng.choice(BOUND_PRIO, idx.size).astype(np.int32), rng.integers(50, 99, idx.size).astype(np.int64),
+                            p.group[idx].copy(), p.req[:, idx].copy(), p.req_present[idx].copy())
+            return dict(remove=np.zeros(0, np.uint32), insert=ins, pdb=None)
+        return self._bound_delta(hint)
+
+    def d_bound_nodes(self, hint):
+        return dict() if self.w.bt is not None and self.w.pend_b else None
+
+    def d_pdb_set(self, hint):
+        w = self.w
+        return dict(bits=self.rng.integers(0, 2, w.bt.ids).astype(np.uint8)) if w.bound_ok() else None
+
+    def d_pdb_load(self, hint):
+        w, rng = self.w, self.rng
+        if not w.bound_ok():
+            return None
+        n_pdb = int(rng.integers(1, 9))
+        off, member = pdr.random_members(rng, w.bt.ids, n_pdb)
+        return dict(allowed=pdr.random_allowed(rng, n_pdb), off=off, member=member)
+
+    def d_pdb_append(self, hint):
+        w, rng = self.w, self.rng
+        if not w.bound_ok() or w.pm is None or w.pm.covered >= w.bt.ids:
+            return None
+        c = int(rng.integers(1, w.bt.ids - w.pm.covered + 1))
+        off, member = pdr.random_members(rng, c, w.pm.n_pdb, sizes=(0, 1, 3))
+        return dict(off=off, member=member)
+
+    def d_pdb_allowed(self, hint):
+        w, rng = self.w, self.rng
+        if not w.bound_ok() or w.pm is None:
+            return None
+        idx = rng.permutation(w.pm.n_pdb)[: int(rng.integers(1, w.pm.n_pdb + 1))].astype(np.uint32)
+        return dict(index=idx, value=pdr.random_allowed(rng, idx.size, 0.4))
+
+    # -- preemption
+    def _preemptors(self, gang):
+        w, rng = self.w, self.rng
+        if w.preempt_ok() != OK or not w.pods.p:
+            return None
+        pool = w.unplaced if w.unplaced is not None and w.unplaced.size else np.nonzero(w.pods.group >= 0)[0]
+        if not pool.size:
+            return None
+        idx = np.sort(rng.permutation(pool)[: int(rng.integers(1, 13))])
+        grp = w.pods.group[idx]
+        prio = np.where(grp >= 0, self.sc["gprio"][np.clip(grp, 0, 63)], 350).astype(np.int32)
+        if gang:
+            o = capi.gang_order(grp, prio)
+            idx, prio = idx[o], prio[o]
+        prot = (rng.random(w.g) < 0.1).astype(np.uint8)
+        return dict(pod_index=idx.astype(np.uint32), priority=prio, protected=prot)
+
+    def d_preempt(self, hint):
+        return self._preemptors(False)
+
+    def d_commit(self, hint):
+        a = self._preemptors(False)
+        if a is None:
+            return None
+        u = self.rng.random()
+        apply = hint in ("apply", "assume") or u < 0.6
+        assume = hint == "assume" or (hint is None and apply and u < 0.3)
+        return dict(a, apply=bool(apply), assume=bool(assume))
+
+    def d_commit_gang(self, hint):
+        w, rng = self.w, self.rng
+        a = self._preemptors(True)
+        if a is None:
+            return None
+        grp = w.pods.group[a["pod_index"]]
+        need = np.zeros(w.g, np.uint32)
+        for x in np.unique(grp[grp >= 0]):
+            c = int((grp == x).sum())
+            need[x] = rng.choice([0, 1, c, c + 1])                              # no requirement, an easy one, everybody, one more than there are
+        u = rng.random()
+        apply = hint == "apply" or u < 0.6
+        return dict(a, need=need, apply=bool(apply), assume=bool(apply and u < 0.3))
+
+    # -- calls the header refuses
+    def d_refuse(self, hint):
+        """-> (kind, args) of a call the model predicts a refusal for, or None"""
+        w, rng = self.w, self.rng
+        if hint == "stale_wait":
+            if w.wt is None or w.wt.n == w.n:
+                return None
+            if w.wt.w and rng.random() < 0.7:
+                gs = [int(w.wt.group[0])]
+                return ("expire", dict(groups=gs, deny=True)) if rng.random() < 0.5 else ("release", dict(groups=gs))
+            return ("forget", dict(ids=w.wt.id[:1].astype(np.uint32))) if w.wt.w else ("park", dict())
+        if hint == "stale_bound":
+            if w.bt is None or w.bt.n == w.n:
+                return None
+            u = rng.random()
+            if u < 0.4:
+                return "bound_apply_ex", dict(remove=w.bt.id[:1].astype(np.uint32), insert=None, pdb=None)
+            pi = np.zeros(1, np.uint32)
+            if u < 0.7:
+                return "preempt", dict(pod_index=pi, priority=np.full(1, 350, np.int32), protected=np.zeros(w.g, np.uint8))
+            return "commit", dict(pod_index=pi, priority=np.full(1, 350, np.int32), protected=np.zeros(w.g, np.uint8), apply=True, assume=False)
+        if hint == "window":
+            if w.window or w.pend_w:
+                return None
+            if w.wait_ok() and rng.random() < 0.5:
+                return "park", dict()
+            return "seq_expire", dict(groups=[0], deny=False, all=False)
+        if hint == "list_order":
+            a, b = sorted(rng.choice(w.g, 2, replace=False).tolist())
+            return "list", dict(remove=[b, a] if rng.random() < 0.5 else [a, a], update=[], rows=new_group_rows(rng, w.S, 0), n_append=0)
+        if hint == "forget_dead":
+            if not w.wait_ok() or w.wt.w < 2 or w.pend_w or w.pend_b:
+                return None
+            dead = np.setdiff1d(np.arange(w.wt.ids), w.wt.id)
+            bad = int(rng.choice(dead)) if dead.size else w.wt.ids
+            return "forget", dict(ids=np.array([int(w.wt.id[0]), bad], np.uint32))
+        if hint == "expire_twice":
+            if not w.wait_ok() or w.wt.w < 2 or w.pend_w or w.pend_b:
+                return None
+            x = int(w.wt.group[0])
+            return "expire", dict(groups=[x, x], deny=True)
+        raise KeyError(hint)
+
+
+def plan(seed: int, orc):
+    """-> (scene, steps): steps = [(kind, args, refused)] drawn on a World of the plan's own.  The first two calls load the (empty) wait
+    table and the bound table.  Then three motifs per seed, in rotation over the seeds, with single calls between them: the single call
+    is of the row of calls (ROWS) this seed has used least so far, and within the row the entry point used least.  Every sixth step is a
+    call the model predicts a refusal for.  A call that is not applicable is drawn again as another call, never skipped; the two refusals
+    the device finds are followed by a successful call of the same removal core."""
+    sc = scene(seed)
+    w = world_of(orc, sc)
+    rng = np.random.default_rng(88000 + seed)
+    dr = Drawer(w, sc, rng)
+    steps, queue = [], []
+    used = dict.fromkeys(ROW_OF, 0)
+    want = 2 if seed % 4 == 0 else 3       # calls of every row: 2 in every seed, 30 over the twelve
+
+    def do(kind, args, refused=False):
+        out = w.step(kind, args)
+        assert (out["status"] != OK) == refused, f"seed {seed} step {len(steps)} {kind}: status {out['status']} drawn as {'a refusal' if refused else 'a call'}"
+        if not refused:
+            used[kind] += 1
+        steps.append((kind, args, refused))
+
+    def single():
+        """the least used row's least used entry point that is applicable now"""
+        row_used = {r: sum(used[k] for k in ROWS[r]) for r in ROWS}
+        if len(steps) > 12 and rng.random() < 0.06:                              # a table loaded afresh in mid-sequence: its ids restart
+            k = "wait_load" if used["wait_load"] <= used["bound_load"] else "bound_load"
+            a = dr.draw(k)
+            if a is not None:
+                return [(k, a)]
+        score = lambda k: (min(row_used[ROW_OF[k]], want), used[k] > 0, row_used[ROW_OF[k]] + used[k], rng.random())   # a row `want` times, then an entry point once
+        for k in sorted(ROW_OF, key=score):
+            a = dr.draw(k)
+            if a is not None:
+                return [(k, a)]
+            if k == "seq_expire" and not w.window and dr.draw("pass") is not None:
+                return ["pass", "seq_expire"]                                   # the window is shut or nobody waits: a pass opens it
+        raise AssertionError(f"seed {seed}: no call is applicable at step {len(steps)}")
+
+    def room_for(motif):
+        """the steps left hold the motif, the refusals due, and what the rows lack of `want` calls each once the motif has run"""
+        after = {r: sum(used[k] for k in ROWS[r]) for r in ROWS}
+        for item in motif:
+            k = item if isinstance(item, str) else item[0]
+            if k in ROW_OF:
+                after[ROW_OF[k]] += 1
+        left = STEPS - len(steps)
+        return left >= len(motif) + left // 6 + 1 + sum(max(0, want - c) for c in after.values())
+
+    do("wait_load", dict(node=(), group=(), req=None, req_present=None))
+    do("bound_load", dict(bound=sc["bound"]))
+    motifs = [MOTIF_ORDER[(seed + 2 * k) % len(MOTIF_ORDER)] for k in range(3)]
+    on_device = {"forget_dead", "expire_twice"}                                  # each once per seed: they cost a second call
+    if sc["nodes"].n <= 5 and "c" not in motifs:
+        motifs[0] = "c"                    # this seed takes its node count down across 4
+    if sc["nodes"].n > 60 and "e" not in motifs:
+        motifs[0] = "e"                    # and this one up across 64
+    after = None                           # a successful call owed after a refusal the device found
+    gap = 0
+    queue, opening = list(OPENING), True   # the first cycle: its pass leaves gangs waiting that share nodes
+    while len(steps) < STEPS:
+        if after is not None:
+            kind, after = after, None
+            a = dr.draw(kind)
+            assert a is not None, f"seed {seed}: the {kind} owed after a refusal on the device is not applicable"
+            do(kind, a)
+            continue
+        if len(steps) % 6 == 5 and 6 * sum(r for _, _, r in steps) < len(steps) + 1:       # a sixth, the motifs' own refusals included
+            order = list(rng.permutation(REFUSALS))
+            if w.pend_w or w.pend_b:
+                order = ["stale_wait", "stale_bound"] + order
+            for r in order:
+                got = dr.d_refuse(r) if r not in ("forget_dead", "expire_twice") or r in on_device else None
+                if got is not None:
+                    do(got[0], got[1], refused=True)
+                    after = {"forget_dead": "forget", "expire_twice": "expire"}.get(r)
+                    on_device.discard(r)
+                    break
+            else:
+                raise AssertionError(f"seed {seed}: no refusal is applicable at step {len(steps)}")
+            continue
+        if not queue:
+            opening = False
+            if w.pend_w or w.pend_b:       # node-list surgery is followed first, in either order
+                queue = [str(k) for k in rng.permutation(["wait_nodes", "bound_nodes"])]
+            elif motifs and gap >= 1 and room_for(MOTIFS[motifs[0]]):
+                DEBUG and print(f"seed {seed} step {len(steps)}: motif {motifs[0]}")
+                queue, gap = list(MOTIFS[motifs.pop(0)]), 0                     # (there is room for it and for what the rows still lack)
+            else:
+                queue, gap = single(), gap + 1
+        item = queue.pop(0)
+        if isinstance(item, tuple) and isinstance(item[1], dict):
+            do(*item)
+            continue
+        kind, hint = (item, None) if isinstance(item, str) else item
+        if kind == "refuse":
+            got = dr.d_refuse(hint)
+            if got is not None:
+                do(got[0], got[1], refused=True)
+            continue
+        a = dr.draw(kind, hint)
+        if a is None:                      # not applicable: the rest of the motif goes with it, other calls are drawn
+            DEBUG and print(f"seed {seed} step {len(steps)}: {item} is not applicable, dropped with {queue}")
+            queue = queue if opening else []
+            continue
+        do(kind, a)
+    return sc, steps
