@@ -17,7 +17,7 @@ LIB_DIR = os.environ.get("BS_LIB_DIR") or HERE
 PREBUILT_ONLY = bool(os.environ.get("BS_LIB_DIR"))
 LIB_PATH = os.path.join(LIB_DIR, "libbsched.so")
 # NOTE: UNITS / SOURCES below are the FIRST FIVE units only, not "what is built": later units sit in LATER_UNITS and LIST_UNITS further down, and
-# everything that builds, links or tests staleness goes by BUILD_UNITS / BUILD_SOURCES.
+# everything that builds, links or tests staleness goes by LINK_UNITS / LINK_SOURCES.
 # translation units -> the headers each one depends on, transitively (tests/test_build_units_cpu.py follows the #includes; DESIGN.md section 4 "Build")
 _COMMON = ["bs_common.hpp", "bs_kernels.hpp", "bs_nodew_layout.hpp", "bs_lanes.hpp", os.path.join("..", "..", "include", "bsched.h")]
 _CTX = _COMMON + ["bs_ctx.hpp", "bs_carve.hpp", "bs_hostmem.hpp", "bs_pod_ranges.hpp"]      # the units that hold entry points
@@ -47,7 +47,15 @@ LIST_UNITS = {
 }
 BUILD_UNITS = {**ALL_UNITS, **LIST_UNITS}
 BUILD_SOURCES = list(BUILD_UNITS)
-HEADERS = sorted({h for hs in BUILD_UNITS.values() for h in hs})
+# ... and the eighth: tests/test_groups_list_cpu.py holds BUILD_SOURCES to the seven names above, so bs_bound_bind's unit has a table of its
+# own (tests/test_bound_bind_cpu.py holds it to the include graph).  What is compiled, linked and tested for staleness is LINK_UNITS /
+# LINK_SOURCES.
+BIND_UNITS = {
+    "tu_bind.hip": _CTX + ["bs_bound_bind.hpp", "bs_bound_bind_check.hpp", "bs_bound_apply.hpp", "bs_preempt_commit.hpp", "bs_preempt.hpp"],
+}
+LINK_UNITS = {**BUILD_UNITS, **BIND_UNITS}
+LINK_SOURCES = list(LINK_UNITS)
+HEADERS = sorted({h for hs in LINK_UNITS.values() for h in hs})
 OBJ_DIR = os.path.join(HERE, "build")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]
@@ -90,7 +98,7 @@ def is_stale() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, f) for f in BUILD_SOURCES + HEADERS]
+    deps = [os.path.join(CSRC, f) for f in LINK_SOURCES + HEADERS]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -103,7 +111,7 @@ def _unit_stale(src: str) -> bool:
     if not os.path.exists(o):
         return True
     t = os.path.getmtime(o)
-    return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in [src] + BUILD_UNITS[src])
+    return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in [src] + LINK_UNITS[src])
 
 
 def build(force: bool = False, verbose: bool = False, extra_flags: list[str] | None = None, unity: bool = False) -> str:
@@ -124,11 +132,11 @@ def build(force: bool = False, verbose: bool = False, extra_flags: list[str] | N
         res = subprocess.run(cmd, capture_output=True, text=True)
         if res.returncode != 0:
             raise RuntimeError("hipcc failed:\n" + res.stdout + res.stderr)
-        for src in BUILD_SOURCES:                                 # the objects no longer match the library
+        for src in LINK_SOURCES:                                 # the objects no longer match the library
             if os.path.exists(_obj(src)):
                 os.remove(_obj(src))
         return LIB_PATH
-    todo = [src for src in BUILD_SOURCES if force or extra_flags or _unit_stale(src)]
+    todo = [src for src in LINK_SOURCES if force or extra_flags or _unit_stale(src)]
     procs = []
     for src in todo:
         cmd = [hipcc(), *FLAGS, *(extra_flags or []), "-c", "-o", _obj(src), os.path.join(CSRC, src)]
@@ -148,7 +156,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags: list[str] | N
                 os.remove(_obj(src))
         raise RuntimeError("hipcc failed:\n" + "\n".join(failed))
     tmp = f"{LIB_PATH}.{os.getpid()}.tmp"
-    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp, *[_obj(src) for src in BUILD_SOURCES], "-ldl"]
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp, *[_obj(src) for src in LINK_SOURCES], "-ldl"]
     if verbose:
         print(" ".join(cmd))
     res = subprocess.run(cmd, capture_output=True, text=True)
@@ -156,7 +164,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags: list[str] | N
         raise RuntimeError("link failed:\n" + res.stdout + res.stderr)
     os.replace(tmp, LIB_PATH)
     if extra_flags:
-        for src in BUILD_SOURCES:                                 # objects of an experiment build must not be taken for the shipped ones
+        for src in LINK_SOURCES:                                 # objects of an experiment build must not be taken for the shipped ones
             os.remove(_obj(src))
     return LIB_PATH
 

@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "bs_wait_load", "bs_wait_count", "bs_wait_ids", "bs_wait_read", "bs_wait_park", "bs_wait_release", "bs_wait_expire", "bs_wait_forget",
     "bs_wait_nodes_apply",
     "bs_groups_list_apply", "bs_groups_list_apply_flat",
+    "bs_bound_bind",
 ]
 
 SEQ_EXPIRE_DENY, SEQ_EXPIRE_ALL = 1, 2    # bs_seq_expire flags
@@ -260,6 +261,7 @@ def load_library(path: str | None = None):
     L.bs_groups_list_apply.argtypes = [vp, P(GroupsListDelta), P(GroupsListOut)]
     L.bs_groups_list_apply_flat.argtypes = [vp, u32, P(u32), u32, P(u32), u32, P(u32), P(u32), P(u32), P(u8), P(u32), P(C.c_int64), P(u32), P(C.c_uint64),
                                             u32, u32, P(u32), P(u32), P(i32), P(u32)]
+    L.bs_bound_bind.argtypes = [vp, u32, P(u32), u32, P(u32), P(i32), P(C.c_int64), P(u8), P(u32), P(u32)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:
@@ -905,6 +907,26 @@ class Context:
             self._chk(self._lib.bs_bound_apply(self._h, C.byref(d), C.byref(first)), "bs_bound_apply")
         self._bound_ids = int(first.value) + ni
         return int(first.value)
+
+    def bound_bind(self, wait_ids, pod_index, priority, start_ns, pdb=None) -> dict:
+        """bs_bound_bind: the listed rows of the wait table and the listed pods the last pass placed enter the resident bound table on the
+        device (row i: the wait ids first, then the pods; priority[i], start_ns[i], pdb[i] != 0: PDB-violating, None = clear) and the wait
+        rows leave their table.  Returns dict(first_id=the id of row 0, node=the node each row bound on)."""
+        wl = np.ascontiguousarray(np.asarray([] if wait_ids is None else wait_ids, np.uint32).reshape(-1))
+        pl = np.ascontiguousarray(np.asarray([] if pod_index is None else pod_index, np.uint32).reshape(-1))
+        n = int(wl.size + pl.size)
+        pr = np.ascontiguousarray(np.asarray(priority, np.int32).reshape(-1))
+        st = np.ascontiguousarray(np.asarray(start_ns, np.int64).reshape(-1))
+        assert pr.size == n and st.size == n, "priority and start_ns are per row: the wait rows first, then the pods"
+        pv = None if pdb is None or n == 0 else np.ascontiguousarray(np.asarray(pdb).reshape(-1) != 0, np.uint8)
+        assert pv is None or pv.size == n
+        node = np.zeros(max(n, 1), np.uint32)
+        first = C.c_uint32()
+        self._chk(self._lib.bs_bound_bind(self._h, int(wl.size), _u32p(wl) if wl.size else None, int(pl.size), _u32p(pl) if pl.size else None,
+                                          pr.ctypes.data_as(C.POINTER(C.c_int32)) if n else None, _i64p(st) if n else None,
+                                          pv.ctypes.data_as(C.POINTER(C.c_uint8)) if pv is not None else None, _u32p(node), C.byref(first)),
+                  "bs_bound_bind")
+        return dict(first_id=int(first.value), node=node[:n].copy())
 
     def bound_nodes_apply(self, kind, index, dropped_cap: int = 0):
         """bs_bound_nodes_apply: the resident bound table follows the node-list surgery of the apply_node_deltas call(s) before it — kind

@@ -5,6 +5,7 @@
 #include <rccl/rccl.h>   // types and enums only: librccl itself is dlopen'ed on demand (hosts without RCCL can still load the library)
 
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -98,6 +99,43 @@ int check_handover(bs_ctx* c);
 int wait_release_rows(bs_ctx* c, const char* who, uint32_t count, const uint32_t* group, uint32_t cap, uint32_t* id_out, uint32_t* node_out, int32_t* group_out,
                       uint32_t* n_out);
 int32_t* wait_group_column(const bs_ctx* c);   // the live table's group column ([wait_w] rows)
+// Defined in tu_wait.hip: the wait core's launch sequence in its by-id release form (mode by id, no node side, no forget, no expire), cut
+// where bs_bound_bind puts its own kernels: wait_bind_front launches k_wt_mark -> k_wt_scan1 -> k_wt_scan2 over the listed ids (and k_wt_walk
+// when `walk`: the pass's chains as wnode[P]) and names what those left on the device; wait_bind_back launches k_wt_move<S> -> k_wt_finish
+// (the twin and this call's scratch only; the marks come off on every path).  Nothing waits for the stream.  After the caller's one wait:
+// wait_bind_waited (the marks are clean again), wait_bind_verdict over the info words it read back (BS_OK, or the refusal with last_error
+// set), and on success wait_bind_commit (the twin becomes the table).
+struct WaitBind {
+  const uint32_t *id = nullptr, *node = nullptr, *pres = nullptr;   // the live table's columns, W rows
+  const int32_t* group = nullptr;
+  const int64_t* req = nullptr;                                     // [L][stride]
+  uint32_t stride = 1, W = 0;
+  const uint32_t* mark = nullptr;                                   // [mark_n] list position + 1 of a listed id
+  uint32_t mark_n = 0;
+  uint32_t* info = nullptr;                                         // the core's four info words
+  const uint32_t* err = nullptr;                                    // the error word among them
+  const int32_t* wnode = nullptr;                                   // [P] the node of a pod that waits in the pass's chains, else -1 (walk only)
+  uint32_t n_wait = 0;
+  std::vector<uint8_t> core;                                        // the core's own device struct of this call
+};
+int wait_bind_state(bs_ctx* c, const char* who);   // BS_OK, or why the wait table cannot be used now (bs_wait_release's test)
+int wait_bind_front(bs_ctx* c, const char* who, uint32_t n_wait, const uint32_t* wait_id, bool walk, WaitBind& wb);
+int wait_bind_back(bs_ctx* c, const WaitBind& wb);
+void wait_bind_waited(bs_ctx* c, const WaitBind& wb);
+int wait_bind_verdict(bs_ctx* c, const char* who, const WaitBind& wb, const uint32_t info[4]);
+void wait_bind_commit(bs_ctx* c, const WaitBind& wb, const uint32_t info[4]);
+// Defined in tu_preempt.hip: the back half of every patch of the bound table, for a delta block that is on the device already.  `a` names the
+// delta (remove ids, the inserts sorted by (node, importance)) and the scratch in d_pre; the call sizes the second allocation for
+// b - n_remove + n_insert entries, points `a` at the live table, launches k_ba_scatter .. k_ba_merge, waits once, judges the error word
+// and swaps the allocations (table, entry count, id space + n_insert, the group maximum).  hooks (NULL: none): before_wait enqueues the
+// caller's own launches and copies behind the merge; verdict runs after the wait and before the error word is judged: the caller's own
+// error words (non-zero: returned, nothing is swapped) and the group maximum where only the device knows it.
+struct BoundApplyDev;
+struct BoundBlockHooks {
+  std::function<int()> before_wait;
+  std::function<int(uint32_t ba_err, int32_t& gmax)> verdict;
+};
+int bound_apply_block(bs_ctx* c, const char* who, BoundApplyDev& a, int32_t gmax, const BoundBlockHooks* hooks = nullptr);
 
 }  // namespace bs
 
@@ -221,6 +259,7 @@ struct bs_ctx {
   bool seq_wait_valid = false;
   Piece<unsigned long long> seq_o_wait;
   Piece<uint32_t> seq_o_head, seq_o_nwait;
+  Piece<int32_t> seq_o_node;         // the pass's pod_node block (bs_bound_bind reads a placed pod's node there)
   DevBuf d_sexp;                     // per-call scratch: block totals, slots, rows, dirty list, records
   DevBuf d_sexp_nodes;               // per-node delta [L][N], key bits, dirty words: zero between calls (k_se_nodes re-zeroes what it read)
   uint32_t sexp_n = 0, sexp_l = 0;   // the layout d_sexp_nodes was zeroed for

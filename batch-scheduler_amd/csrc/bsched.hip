@@ -32,6 +32,7 @@
 #include "tu_wait.hip"
 #include "tu_groups.hip"
 #include "tu_preempt.hip"
+#include "tu_bind.hip"
 #endif
 
 namespace {

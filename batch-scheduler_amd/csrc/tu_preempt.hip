@@ -130,6 +130,48 @@ BoundCols<U8> bound_dev(D& d, U8* base, const BoundLayout& l) {
 
 }  // namespace
 
+// the back half of every patch of the bound table (bs_ctx.hpp): the second allocation, the merge chain over a delta block that is on the
+// device, the one wait, the error word, the swap
+int bs::bound_apply_block(bs_ctx* c, const char* who, BoundApplyDev& a, int32_t gmax, const BoundBlockHooks* hooks) {
+  const uint32_t N = c->N, L = c->L, B = c->bound_b, ids = c->bound_ids, R = a.n_remove, I = a.n_insert;
+  const uint32_t B2 = B - R + I;                           // (when the error word stays clear)
+  BoundLayout lay{};
+  const size_t table_bytes = bound_layout(L, N, B2, lay);
+  if (table_bytes > c->d_bound2.cap) HIPCHK(c, c->d_bound2.reserve(table_bytes + table_bytes / 4));
+  const auto bt = bound_dev(a, c->d_bound.as<const uint8_t>(), c->blay);
+  a.bpres = bt.pres;
+  a.bstride = std::max<uint32_t>(B, 1);
+  a.b = B; a.n = N; a.ids = ids;
+  CompactDev nw{};
+  const auto nt = bound_dev(nw, c->d_bound2.as<uint8_t>(), lay);
+  nw.bpres = nt.pres;
+  nw.bnviol = nt.nviol;
+  nw.bstride = std::max<uint32_t>(B2, 1);
+  launch_bound_apply(c->stream, c->S, a, nw);
+  LAUNCHCHK(c, BS_KERNEL_PREPASS);
+  if (hooks && hooks->before_wait)
+    if (const int rc = hooks->before_wait()) return rc;
+  uint32_t err = 0;                                        // read before the swap: the merge wrote nothing when it is set
+  HIPCHK(c, hipMemcpyAsync(&err, a.err, sizeof err, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (hooks && hooks->verdict)
+    if (const int rc = hooks->verdict(err, gmax)) return rc;
+  if (err & (kBaErrUnknown | kBaErrDead | kBaErrTwice | kBaErrNode)) {
+    c->last_error = std::string(who) + ((err & kBaErrTwice) ? ": a remove id is listed twice"
+                                        : (err & kBaErrDead) ? ": a remove id is not live (evicted or removed earlier)"
+                                                             : ": a remove id or an insert node is out of range");
+    return BS_ERR_INVALID;
+  }
+  if (err & kBaErrFull) { c->last_error = std::string(who) + ": more than BS_BOUND_MAX_PER_NODE bound pods on one node"; return BS_ERR_CAPACITY; }
+  std::swap(c->d_bound.p, c->d_bound2.p);
+  std::swap(c->d_bound.cap, c->d_bound2.cap);
+  c->blay = lay;
+  c->bound_b = B2;
+  c->bound_ids = ids + I;
+  c->bound_max_group = gmax;
+  return BS_OK;
+}
+
 extern "C" {
 int bs_bound_load(bs_ctx* c, const bs_bound_soa* bd) {
   if (!c || !bd) return BS_ERR_INVALID;
@@ -895,15 +937,7 @@ static int bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t flags, uint3
   HIPCHK(c, hipMemcpyAsync(base, h.data(), h.size(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(o_posof.in(base), 0xff, o_posof.bytes(), c->stream));
   HIPCHK(c, hipMemsetAsync(base + o_zero, 0, zero_bytes, c->stream));
-  const uint32_t B2 = B - R + I;                           // (when the error word stays clear)
-  BoundLayout lay{};
-  const size_t table_bytes = bound_layout(L, N, B2, lay);
-  if (table_bytes > c->d_bound2.cap) HIPCHK(c, c->d_bound2.reserve(table_bytes + table_bytes / 4));
   BoundApplyDev a{};
-  const auto bt = bound_dev(a, c->d_bound.as<const uint8_t>(), c->blay);
-  a.bpres = bt.pres;
-  a.bstride = std::max<uint32_t>(B, 1);
-  a.b = B; a.n = N; a.ids = ids;
   a.n_remove = R; a.n_insert = I;
   a.rem = o_rem.in(base);
   a.inode = o_node.in(base);
@@ -920,29 +954,7 @@ static int bound_apply(bs_ctx* c, const bs_bound_delta* d, uint32_t flags, uint3
   a.icnt = o_icnt.in(base);
   a.ifirst = o_ifirst.in(base);
   a.err = o_err.in(base);
-  CompactDev nw{};
-  const auto nt = bound_dev(nw, c->d_bound2.as<uint8_t>(), lay);
-  nw.bpres = nt.pres;
-  nw.bnviol = nt.nviol;
-  nw.bstride = std::max<uint32_t>(B2, 1);
-  launch_bound_apply(c->stream, c->S, a, nw);
-  LAUNCHCHK(c, BS_KERNEL_PREPASS);
-  uint32_t err = 0;                                        // read before the swap: the merge wrote nothing when it is set
-  HIPCHK(c, hipMemcpyAsync(&err, a.err, o_err.bytes(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (err & (kBaErrUnknown | kBaErrDead | kBaErrTwice | kBaErrNode)) {
-    c->last_error = (err & kBaErrTwice) ? "bs_bound_apply: a remove id is listed twice"
-                  : (err & kBaErrDead)  ? "bs_bound_apply: a remove id is not live (evicted or removed earlier)"
-                                        : "bs_bound_apply: a remove id or an insert node is out of range";
-    return BS_ERR_INVALID;
-  }
-  if (err & kBaErrFull) { c->last_error = "bs_bound_apply: more than BS_BOUND_MAX_PER_NODE bound pods on one node"; return BS_ERR_CAPACITY; }
-  std::swap(c->d_bound.p, c->d_bound2.p);
-  std::swap(c->d_bound.cap, c->d_bound2.cap);
-  c->blay = lay;
-  c->bound_b = B2;
-  c->bound_ids = ids + I;
-  c->bound_max_group = gmax;
+  if ((rc = bound_apply_block(c, "bs_bound_apply", a, gmax))) return rc;
   if (first_id_out) *first_id_out = ids;
   if (with_nodes && rec_cap) {
     // the node requests follow: `a` still names the old table (now the second allocation, intact) and the scratch k_ba_mark left

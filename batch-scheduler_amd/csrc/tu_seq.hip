@@ -214,6 +214,7 @@ int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
   c->seq_o_wait = o_wait;                                  // (the pieces: seq_expire_dev addresses them in d_seq)
   c->seq_o_head = o_head;
   c->seq_o_nwait = o_nwait;
+  c->seq_o_node = o_node;
   c->seq_wait_valid = true;
   return BS_OK;
 }

@@ -10,6 +10,8 @@
 #include "bs_bound_nodes_replay.hpp"
 #include "bs_ctx.hpp"
 
+#include <cstring>
+
 namespace bs {
 
 // the table's one allocation for `cap` rows: columns at 256-byte offsets, req lane stride max(cap, 1)
@@ -553,4 +555,109 @@ int wait_release_rows(bs_ctx* c, const char* who, uint32_t count, const uint32_t
   return wait_remove(c, who, kWtByGroup, false, false, false, count, group, cap, id_out, node_out, nullptr, nullptr, n_out, group_out);
 }
 int32_t* wait_group_column(const bs_ctx* c) { return wait_tab(c, c->wait_cur).group; }
+
+// ---- the removal core's launch sequence cut in two for bs_bound_bind (bs_ctx.hpp): by id, no node side, no forget, no expire
+static WaitDev wait_bind_core(const WaitBind& wb) {
+  WaitDev a{};
+  std::memcpy(&a, wb.core.data(), sizeof a);
+  return a;
+}
+int wait_bind_state(bs_ctx* c, const char* who) { return wait_table_state(c, who); }
+int wait_bind_front(bs_ctx* c, const char* who, uint32_t n_wait, const uint32_t* wait_id, bool walk, WaitBind& wb) {
+  int rc;
+  const uint32_t W = n_wait ? c->wait_w : 0u, P = walk ? c->P : 0u, G = c->G;
+  if (n_wait && !W) { c->last_error = std::string(who) + ": an id is not in the table"; return BS_ERR_INVALID; }
+  const uint32_t mark_n = c->wait_ids;
+  if (n_wait) HIPCHK(c, wait_zeroed(c, c->d_wait_imark, (size_t)(c->d_wait_imark.cap / 4 >= mark_n ? mark_n : wait_room(mark_n)) * 4, c->wait_imark_clean));
+  Carve cv;
+  const auto o_info = cv.take<uint32_t>(4);
+  const auto o_list = cv.take<uint32_t>(n_wait);
+  const auto o_lcnt = cv.take<uint32_t>(n_wait);
+  const auto o_lout = cv.take<uint32_t>(n_wait);
+  const auto o_bsum = cv.take<unsigned long long>(cdiv(std::max<uint32_t>(W, 1), kWtBlock));
+  const auto o_pos = cv.take<unsigned long long>(std::max<uint32_t>(W, 1));
+  const auto o_id = cv.take<uint32_t>(std::max<uint32_t>(W, 1));
+  const auto o_node = cv.take<uint32_t>(std::max<uint32_t>(W, 1));
+  const auto o_wnode = cv.take<int32_t>(std::max<uint32_t>(P, 1));
+  if (cv.mark() > c->d_wait_scr.cap) HIPCHK(c, c->d_wait_scr.reserve(cv.mark() + cv.mark() / 4));
+  if (n_wait && (rc = wait_twin(c))) return rc;
+  void* base = c->d_wait_scr.p;
+  WaitDev a{};
+  if (n_wait) {
+    a.src = wait_tab(c, c->wait_cur);
+    a.dst = wait_tab(c, c->wait_cur ^ 1u);
+  }
+  a.W = a.E = W;
+  a.mode = kWtById;
+  a.list = o_list.in(base);
+  a.M = n_wait;
+  a.mark = c->d_wait_imark.as<uint32_t>();
+  a.mark_n = n_wait ? mark_n : 0u;
+  a.bsum = o_bsum.in(base);
+  a.pos = o_pos.in(base);
+  a.info = o_info.in(base);
+  a.o_key = o_id.in(base);
+  a.o_node = o_node.in(base);
+  a.l_cnt = o_lcnt.in(base);
+  a.l_out = o_lout.in(base);
+  a.N = c->N;
+  a.G = G;
+  a.wnode = o_wnode.in(base);
+  a.P = P;
+  HIPCHK(c, hipMemsetAsync(a.info, 0, o_info.bytes(), c->stream));
+  if (n_wait) {
+    HIPCHK(c, hipMemcpyAsync(o_list.in(base), wait_id, o_list.bytes(), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_wt_mark, dim3(cdiv(n_wait, 256)), dim3(256), 0, c->stream, a);
+    const uint32_t nblk = cdiv(W, kWtBlock);
+    hipLaunchKernelGGL(k_wt_scan1, dim3(nblk), dim3(kWtBlock), 0, c->stream, a);
+    hipLaunchKernelGGL(k_wt_scan2, dim3(nblk), dim3(kWtBlock), 0, c->stream, a);
+  }
+  if (walk && P) {
+    a.wait_rec = c->seq_o_wait.in(c->d_seq.p);
+    a.head = c->seq_o_head.in(c->d_seq.p);
+    a.nwait = c->seq_o_nwait.in(c->d_seq.p);
+    HIPCHK(c, hipMemsetAsync(a.wnode, 0xFF, o_wnode.bytes(), c->stream));
+    if (G) hipLaunchKernelGGL(k_wt_walk, dim3(cdiv(G, 256)), dim3(256), 0, c->stream, a);
+  }
+  LAUNCHCHK(c, BS_KERNEL_PREPASS);
+  wb.id = a.src.id; wb.node = a.src.node; wb.pres = a.src.pres; wb.group = a.src.group; wb.req = a.src.req;
+  wb.stride = n_wait ? a.src.stride : 1u;
+  wb.W = W;
+  wb.mark = a.mark;
+  wb.mark_n = a.mark_n;
+  wb.info = a.info;
+  wb.err = a.info + kWtErr;
+  wb.wnode = a.wnode;
+  wb.n_wait = n_wait;
+  wb.core.resize(sizeof a);
+  std::memcpy(wb.core.data(), &a, sizeof a);
+  return BS_OK;
+}
+int wait_bind_back(bs_ctx* c, const WaitBind& wb) {
+  if (!wb.n_wait) return BS_OK;
+  const WaitDev a = wait_bind_core(wb);
+  lanes_wide(c->S, [&](auto s) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wt_move<decltype(s)::value>), dim3(cdiv(a.W, 256)), dim3(256), 0, c->stream, a);
+  });
+  hipLaunchKernelGGL(k_wt_finish, dim3(cdiv(a.M, 256)), dim3(256), 0, c->stream, a);
+  LAUNCHCHK(c, BS_KERNEL_PREPASS);
+  return BS_OK;
+}
+void wait_bind_waited(bs_ctx* c, const WaitBind& wb) {
+  if (wb.n_wait) c->wait_imark_clean = true;
+}
+int wait_bind_verdict(bs_ctx* c, const char* who, const WaitBind& wb, const uint32_t info[4]) {
+  if (!wb.n_wait) return BS_OK;
+  if (info[kWtErr]) {
+    c->last_error = std::string(who) + ((info[kWtErr] & kWtErrTwice) ? ": a wait id is listed twice" : ": a wait id is not in the table");
+    return BS_ERR_INVALID;
+  }
+  if (info[kWtKept] + info[kWtLeft] != wb.W || info[kWtLeft] != wb.n_wait) { c->last_error = std::string(who) + ": the scan's totals do not add up to the table"; return BS_ERR_HIP; }
+  return BS_OK;
+}
+void wait_bind_commit(bs_ctx* c, const WaitBind& wb, const uint32_t info[4]) {
+  if (!wb.n_wait) return;
+  c->wait_cur ^= 1u;
+  c->wait_w = info[kWtKept];
+}
 }  // namespace bs

@@ -333,3 +333,55 @@ func (g *gpuCore) waitFollowNodes(kind, index []uint32, rows int) (*droppedWaite
 	}
 	return d, nil
 }
+
+// boundRows: what bs_bound_bind reports for the rows it bound, in the call's order (wait rows first, then queue pods).
+type boundRows struct {
+	firstID uint32   // row i is bound-pod id firstID + i from now on
+	node    []uint32 // the node each row bound on
+}
+
+// bindReleased: bs_bound_bind — the pods that leave Permit enter the resident bound table on the device.  The flat prototype is
+//
+//	int bs_bound_bind(bs_ctx*, uint32_t n_wait, const uint32_t* wait_id, uint32_t n_pod, const uint32_t* pod_index,
+//	                  const int32_t* priority, const int64_t* start_ns, const uint8_t* pdb_violating, uint32_t* node_out, uint32_t* first_id_out)
+//
+// waitIDs: the wait-table ids of the released gangs' rows (the shim keys its WaitingPod map by them); podIndex: the queue indices of the
+// pods the last seqPass placed and released.  priority, startNs and pdb are per row, the wait rows first; pdb may be nil.  Nodes, groups,
+// request lanes and key bits are read where they are resident, the wait rows leave their table, node requests stay as the assume step left
+// them.  In the cycle it stands between the pass and the park:
+//
+//	seqPass -> bindReleased(ids of the released gangs, placed pods) -> bs_wait_park -> bs_pods_apply (bound and parked pods leave the queue)
+//
+// and replaces bs_wait_release + marshalling + applyBoundEvents(moveNodes = false) for these pods.  The shim has no resident wait cycle
+// yet; when it gets one this is its bind step.
+func (g *gpuCore) bindReleased(waitIDs, podIndex []uint32, priority []int32, startNs []int64, pdb []uint8) (*boundRows, error) {
+	n := len(waitIDs) + len(podIndex)
+	if len(priority) != n || len(startNs) != n || (pdb != nil && len(pdb) != n) {
+		return nil, fmt.Errorf("bindReleased: %d rows, %d priorities, %d start times, %d pdb bits", n, len(priority), len(startNs), len(pdb))
+	}
+	_, pWait := u32s(waitIDs)
+	_, pPod := u32s(podIndex)
+	_, pPrio := i32s(priority)
+	start, bits, out := make([]C.int64_t, n+1), make([]C.uint8_t, n+1), make([]C.uint32_t, n+1)
+	for i := 0; i < n; i++ {
+		start[i] = C.int64_t(startNs[i])
+		if pdb != nil {
+			bits[i] = C.uint8_t(pdb[i])
+		}
+	}
+	var pBits *C.uint8_t
+	if pdb != nil {
+		pBits = &bits[0]
+	}
+	var first C.uint32_t
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if rc := C.bs_bound_bind(g.ctx, C.uint32_t(len(waitIDs)), pWait, C.uint32_t(len(podIndex)), pPod, pPrio, &start[0], pBits, &out[0], &first); rc != C.BS_OK {
+		return nil, fmt.Errorf("bs_bound_bind: %s (%s)", C.GoString(C.bs_strerror(rc)), C.GoString(C.bs_last_error(g.ctx)))
+	}
+	r := &boundRows{firstID: uint32(first), node: make([]uint32, n)}
+	for i := 0; i < n; i++ {
+		r.node[i] = uint32(out[i])
+	}
+	return r, nil
+}

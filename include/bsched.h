@@ -1054,6 +1054,49 @@ int bs_bound_dump(bs_ctx* ctx, int32_t* priority, int64_t* start_ns, int32_t* gr
 int bs_bound_nodes_apply(bs_ctx* ctx, uint32_t count, const uint32_t* kind, const uint32_t* index, uint32_t dropped_cap, uint32_t* dropped_ids,
                          uint32_t* n_dropped_out);
 
+/* ---- pods that leave Permit enter the bound table on the device ---------------------------------------------------------------
+ * The cycle is bs_pods_apply -> bs_seq_run -> bs_wait_release(released_group) -> bs_wait_park -> bind -> next cycle.  A pod that binds is
+ * the one event whose data the library holds already: a row of the wait table has node, group, request lanes and present bits as
+ * columns, and a pod the last pass placed has its lanes in the resident queue and its node in the pass's result block.  bs_bound_bind
+ * moves such rows into the bound table without a host copy (the reference binds a released gang's pods where Permit assumed them:
+ * core.go:284-309 keeps the pod -> node map, core.go:327 is PostBind); the caller supplies what the library cannot know: priority, start
+ * time and the PDB bit.  The arguments are flat: this form is also the cgo form.
+ *   rows:    row i is wait_id[i] for i < n_wait, then pod_index[i - n_wait].  A wait row brings the table's node, group, req[L] and
+ *            req_present columns as stored.  A queue pod brings its node from the last pass's result block (bs_seq_run's pod_node), its
+ *            group as the queue stores it, sentinels included, and its request lanes by bs_wait_park's rule: lanes 0..2 the request,
+ *            the pods lane 1, a scalar lane the request where the present bit is set and 0 otherwise, req_present masked to the
+ *            context's scalar lanes.  Both are what bs_bound_load stores.
+ *   bound:   exactly bs_bound_apply of an insert-only delta of these rows in this order: row i gets id ids + i, the id space grows by
+ *            n_wait + n_pod, *first_id_out = ids (NULL ok); every node's list stays in importance order (priority descending, start
+ *            ascending, id ascending), an inserted row goes behind every survivor at equal (priority, start) and inserted rows keep the
+ *            call's order among themselves; a surviving entry keeps its PDB bit, row i takes pdb_violating[i] (NULL: every bit clear),
+ *            the per-node violating counts are recounted; the largest group index the table is held to name becomes the maximum of its
+ *            old value and the inserted groups'.  Resident PDB state is untouched: an uncovered id has no PDB at the next recompute.
+ *   wait:    the listed rows leave by the stable compaction into the twin, in bs_wait_release's form: no node request and no group word
+ *            changes (the pass that released the gang did matched = 0 and PostBind, and the pods stay on the nodes they bind on).
+ *            Survivors keep id, columns and order; bs_wait_ids is unchanged; a bound id is dead, as one removed by bs_wait_forget is.
+ *   else:    untouched: node requests (the assume step counted these pods: bs_bound_apply_ex's nominee rule), the groups, findMaxPG
+ *            and the epoch analysis, the queue (the caller removes bound pods with the bs_pods_apply it issues anyway), the pass's
+ *            chains, and bs_seq_expire's window, which stays open.
+ *   outputs: node_out[i] (NULL ok) = the node row i bound on.
+ *   errors:  all or nothing: every error is found on the host, or by device checks that run before anything resident is written, and both
+ *            tables are swapped or neither; on any error the bound table, its id space and bits, the wait table and its marks are as
+ *            before.  BS_ERR_STATE: before bs_bound_load; the bound table's node count differs from bs_nodes_count; n_wait > 0 without
+ *            a wait table or with one made for other node / group counts (bs_wait_release's test); n_pod > 0 outside the window of a
+ *            successful bs_seq_run (bs_wait_park's test); a sharded or external-reduce context.  BS_ERR_INVALID: a NULL required array
+ *            with a count above 0; a wait id at or above bs_wait_ids, dead, or listed twice; a pod index at or above the queue length,
+ *            or listed twice; a pod the last pass gave no node (pod_node < 0); a pod that still waits in the pass's chains (what
+ *            bs_seq_waiting_read reports as >= 0): a waiting pod is parked, not bound.  BS_ERR_CAPACITY: the id space would pass
+ *            BS_BOUND_MAX, or a node would hold more than BS_BOUND_MAX_PER_NODE entries (exactly the limit is fine).
+ *   edges:   an empty call is BS_OK, launches nothing and sets *first_id_out = ids.  Works from an empty bound table and down to an
+ *            empty wait table.  Synchronous.
+ *   hazard:  not checked, because the library cannot see it: a pod that bs_wait_park parked and that is ALSO listed by its queue index
+ *            (park empties the chains, so the index no longer reads as waiting) then sits in both tables.  List a parked pod by its
+ *            wait id only. */
+int bs_bound_bind(bs_ctx* ctx, uint32_t n_wait, const uint32_t* wait_id, uint32_t n_pod, const uint32_t* pod_index,
+                  const int32_t* priority, const int64_t* start_ns, const uint8_t* pdb_violating, uint32_t* node_out,
+                  uint32_t* first_id_out);
+
 /* ---- resident PodDisruptionBudgets: the PDB bits follow the budgets' status on the device ------------------------------------
  * bs_bound_pdb_set takes finished bits: the caller matches every bound pod against every exhausted PDB whenever a budget crosses zero.
  * The two inputs of a bit change at different rates, so here they arrive apart.  WHICH PDBs select a pod (namespace and selector, D1) is
