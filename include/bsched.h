@@ -566,6 +566,9 @@ int bs_nodes_read(bs_ctx* ctx, int64_t* requested, uint32_t* requested_present);
  *   node requests   each forgotten pod leaves the node it was assumed on by NodeInfo.RemovePod, the exact inverse of the pass's assume
  *                   step: lanes cpu / memory / ephemeral lose the request, the pods lane loses 1, a scalar lane the pod has a present
  *                   bit for loses the request AND KEEPS its node bit, every other scalar lane keeps its word and its bit.  Sums wrap.
+ *                   Where the node no longer has the key (bs_nodes_assume or a bs_nodes_apply UPDATE rewrote the node since the pass),
+ *                   RemovePod's map rule holds, as in bs_preempt_commit step 2: the lane counts as 0 before the request is taken off,
+ *                   and the node's bit becomes set.
  *                   Several forgotten pods on one node, of one gang or of several, leave together.  Everything derived from the node
  *                   requests follows as after bs_nodes_assume.
  *   group state     for every expired group: matched = 0 — EVERY MatchedPodNodes entry is deleted, those of earlier cycles included,
@@ -642,7 +645,9 @@ int bs_seq_waiting_read(bs_ctx* ctx, uint32_t p, int32_t* wait_node /*[p]*/);  /
  *   bs_wait_expire  controller.go:322-332 for the table's rows: the twin of bs_seq_expire.  The rows of the listed groups leave the table.
  *                   Each leaves its node by bs_seq_expire's rule: lanes cpu / memory / ephemeral lose the request, the pods lane loses 1,
  *                   a scalar lane the row has a present bit for loses the request AND KEEPS its node bit, every other scalar lane keeps
- *                   its word and its bit.  Sums wrap.  Rows of several gangs on one node leave together.  The derived node data and the
+ *                   its word and its bit.  Sums wrap.  A row may carry a key its node lacks (a loaded row, or a node that bs_nodes_assume or
+ *                   a bs_nodes_apply UPDATE rewrote): then, as there, the lane counts as 0 before the request is taken off and the node's
+ *                   bit becomes set; bs_wait_forget does the same.  Rows of several gangs on one node leave together.  The derived node data and the
  *                   host mirror follow as after bs_nodes_assume.  matched = 0 for every listed group, with or without rows;
  *                   BS_GROUP_DENIED is set with BS_SEQ_EXPIRE_DENY (the only flag: other bits are BS_ERR_INVALID).  group_unknown[i] =
  *                   matched before the call minus group_entries[i], in uint32 arithmetic: 0 for a caller that parks every cycle.

@@ -123,6 +123,9 @@ def expire(st: State, pods, groups=None, deny=False, all=False):
             st.requested[3, k] = w64(int(st.requested[3, k]) - 1)
             for sc in range(S):
                 if (pres >> sc) & 1:                              # the lane loses the request, its node bit stays
+                    if not (int(st.requested_present[k]) >> sc) & 1:     # (a key the node lost since the pass: 0 before, the bit set)
+                        st.requested[4 + sc, k] = 0
+                        st.requested_present[k] |= np.uint32(1 << sc)
                     st.requested[4 + sc, k] = w64(int(st.requested[4 + sc, k]) - int(pods.req[4 + sc, i]))
             out["pod"].append(i)
             out["node"].append(k)

@@ -157,6 +157,8 @@ class Runner:
             return dict(first_id=ctx.bound_apply(a["remove"], a["insert"], a["pdb"], flat=flat))
         if kind == "bound_apply_ex":
             return dict(first_id=ctx.bound_apply_ex(a["remove"], a["insert"], a["pdb"], flags=a.get("flags", 1), flat=flat))
+        if kind == "bind":
+            return ctx.bound_bind(a["wait_ids"], a["pod_index"], a["priority"], a["start_ns"], a["pdb"])
         if kind == "bound_nodes":
             n, ids = ctx.bound_nodes_apply(exp["kind"], exp["index"], dropped_cap=ctx.bound_count())
             return dict(n_dropped=n, dropped=ids)
@@ -199,6 +201,8 @@ class Runner:
             same(("n_groups", "n_pods", "group", "group_pods", "group_earlier", "pod", "node"))
         elif kind in ("bound_apply", "bound_apply_ex"):
             same(("first_id",))
+        elif kind == "bind":
+            same(("first_id", "node"))
         elif kind == "bound_nodes":
             same(("n_dropped", "dropped"))
         elif kind in ("preempt", "commit", "commit_gang"):
@@ -283,16 +287,31 @@ def _bind(w, rng):
     return dict(remove=np.zeros(0, np.uint32), insert=ins, pdb=None, flags=0)
 
 
-def test_the_documented_cycle_with_binding(bsa, soa, orc):
-    """include/bsched.h: bs_pods_apply -> bs_seq_run -> bs_wait_release(released_group) -> bs_wait_park -> bind (bs_bound_apply_ex, flags 0:
-    the pass assumed these pods already) -> bs_preempt_commit_gang(APPLY | ASSUME) for the pods without a node; three cycles on one context.
-    Between cycles 1 and 2 a finished gang leaves the cache and one arrives; between 2 and 3 a node leaves and one arrives, and both
-    tables follow; in cycle 3 the gang that has waited longest times out."""
+def _cycle_bind(w, dr, rng, row_rng):
+    """the header's bind: the lists are the drawer's ("cycle": every wait row of a gang the pass released, every pod it placed); the pods'
+    priorities and starts are drawn as _bind draws them, the rows' from a stream of their own, so that the old way can bind the same"""
+    a = dr.draw("bind", "cycle")
+    assert a is not None, "the pass placed nobody"
+    wl, pl = np.sort(a["wait_ids"]), np.sort(a["pod_index"])
+    pods = _bind(w, rng)["insert"]
+    assert np.array_equal(pl, np.nonzero(w.last["pod_node"] >= 0)[0])
+    prio = np.concatenate([row_rng.choice(wf.BOUND_PRIO, wl.size).astype(np.int32), pods.priority])
+    start = np.concatenate([row_rng.choice(wf.BIND_START, wl.size).astype(np.int64), pods.start_ns])
+    wl = row_rng.permutation(wl).astype(np.uint32)                               # (not ascending: the table's order is not the call's)
+    return dict(wait_ids=wl, pod_index=pl.astype(np.uint32), priority=prio, start_ns=start, pdb=None)
+
+
+def _documented_cycle(bsa, soa, orc, how):
+    """three cycles on one context; -> (seen, what the context holds at the end: the bound table through its id map, the wait table, the
+    node requests).  how: "apply_ex" binds the placed pods through bs_bound_apply_ex(flags 0) after bs_wait_release and bs_wait_park;
+    "bind" follows the header: bs_bound_bind takes the released gangs' wait rows and the placed pods, then bs_wait_park; "old_way" is
+    "apply_ex" with the released gangs' wait rows marshalled through the host as well, which is what bs_bound_bind replaced."""
     sc = wf.scene(9)
-    rng = np.random.default_rng(99)
-    seen = dict(parked=0, released=0, bound=0, victims=0, voided=0)
-    with Runner(bsa, soa, orc, sc, "the documented cycle") as r:
+    rng, row_rng = np.random.default_rng(99), np.random.default_rng(98)
+    seen = dict(parked=0, released=0, bound=0, victims=0, voided=0, rows=0)
+    with Runner(bsa, soa, orc, sc, f"the documented cycle ({how})") as r:
         w = r.w
+        dr = wf.Drawer(w, sc, np.random.default_rng(97))
         r.do("wait_load", dict(node=(), group=(), req=None, req_present=None))
         r.do("bound_load", dict(bound=sc["bound"]))
         for cycle in (1, 2, 3):
@@ -300,13 +319,30 @@ def test_the_documented_cycle_with_binding(bsa, soa, orc):
             arrive = np.sort(rng.integers(0, w.g, 24)).astype(np.int32)
             r.do("pods", dict(remove=np.asarray(gone, np.uint32), insert=wf.new_pods(rng, w.S, arrive)))
             s = r.do("pass")["seq"]
-            rel = r.do("release", dict(groups=[int(x) for x in s["released_group"]]))
-            pk = r.do("park", flat=bool(cycle % 2))
+            if how == "bind":
+                a = _cycle_bind(w, dr, rng, row_rng)
+                r.do("bind", a, flat=bool(cycle % 2))
+                seen["bound"] += a["pod_index"].size
+                seen["rows"] += a["wait_ids"].size
+                pk = r.do("park", flat=bool(cycle % 2))
+            else:
+                a = _cycle_bind(w, dr, rng, row_rng) if how == "old_way" else None    # (before the release: the rows are still there)
+                rows = wf.bbr.rows(w.wt, a["wait_ids"], w.pods, s["pod_node"], (), w.S) if a is not None else None
+                r.do("release", dict(groups=[int(x) for x in s["released_group"]]))
+                pk = r.do("park", flat=bool(cycle % 2))
+                if how == "old_way":
+                    n = a["wait_ids"].size
+                    bind = _bind(w, np.random.default_rng(0))
+                    p = bind["insert"]
+                    bind["insert"] = soa.Bound(np.concatenate([rows[0], p.node]), a["priority"], a["start_ns"], np.concatenate([rows[1], p.group]),
+                                               np.concatenate([rows[2], p.req], axis=1), np.concatenate([rows[3], p.req_present]))
+                    seen["rows"] += n
+                else:
+                    bind = _bind(w, rng)
+                r.do("bound_apply_ex", bind, flat=bool(cycle % 2))
+                seen["bound"] += bind["insert"].b - (a["wait_ids"].size if a is not None else 0)
             seen["parked"] += pk["n"]
             seen["released"] += int(s["n_released"])
-            bind = _bind(w, rng)
-            r.do("bound_apply_ex", bind, flat=bool(cycle % 2))
-            seen["bound"] += bind["insert"].b
             assert w.unplaced.size, f"cycle {cycle}: every pod found a node"
             cg = r.do("commit_gang", _gang_preemptors(w), flat=bool(cycle % 2))
             seen["victims"] += int(cg["res"]["n_victims"].sum())
@@ -325,15 +361,46 @@ def test_the_documented_cycle_with_binding(bsa, soa, orc):
                 ex = r.do("expire", dict(groups=[oldest], deny=True))
                 assert ex["n"] > 0 and w.groups.flags[oldest] & soa.GROUP_DENIED
             r.against_fresh()
-    print(f"the documented cycle: {seen}")
+        (ids, nodes), dump, req = r.ctx.read_bound(), r.ctx.bound_dump(), r.ctx.read_node_requests()
+        o = np.argsort(ids, kind="stable")                                      # (fresh id k is the k-th smallest id: id_map_by_table_order)
+        assert np.array_equal(ids[o], wf.id_map_by_table_order(w.bt.id))
+        held = dict(bound_node=nodes[o], wait=r.ctx.wait_read(), node_req=req[0], node_pres=req[1], wait_ids=r.ctx.wait_ids(),
+                    **{f"bound_{f}": dump[f][..., o] for f in BOUND_COLUMNS})
+        # ... and in table order, ids included: both forms insert the same rows in the same order, so the order inside a node (importance, ties) is the same too
+        held["table"] = dict(id=ids, node=nodes, **{f: dump[f] for f in BOUND_COLUMNS})
+    print(f"the documented cycle ({how}): {seen}")
+    return seen, held
+
+
+@pytest.mark.parametrize("how", ["apply_ex", "bind"])
+def test_the_documented_cycle_with_binding(how, bsa, soa, orc):
+    """include/bsched.h: bs_pods_apply -> bs_seq_run -> bind -> bs_preempt_commit_gang(APPLY | ASSUME) for the pods without a node; three cycles on
+    one context.  "apply_ex": bs_wait_release(released_group) -> bs_wait_park -> bs_bound_apply_ex (flags 0: the pass assumed these pods
+    already).  "bind": bs_bound_bind (the released gangs' wait rows and the placed pods; no release, the rows leave with the bind) ->
+    bs_wait_park.  Between cycles 1 and 2 a finished gang leaves the cache and one arrives; between 2 and 3 a node leaves and one arrives,
+    and both tables follow; in cycle 3 the gang that has waited longest times out.  After the third cycle the context that bound through
+    bs_bound_bind and one that bound the same rows and pods the old way (bs_wait_release, bs_bound_apply_ex) hold the same bound table up to
+    ids, the same wait table and the same node requests."""
+    seen, held = _documented_cycle(bsa, soa, orc, how)
     assert seen["parked"] >= 3 and seen["released"] and seen["bound"] and seen["victims"], seen
+    if how == "bind":
+        assert seen["rows"], "no wait row of a released gang was bound"
+        seen_old, held_old = _documented_cycle(bsa, soa, orc, "old_way")
+        assert seen_old == seen
+        for k, v in held.items():
+            if isinstance(v, dict):
+                for f, col in v.items():
+                    assert np.array_equal(col, held_old[k][f]), f"bind against the old way: {k}: {f}"
+            else:
+                assert np.array_equal(v, held_old[k]), f"bind against the old way: {k}"
 
 
 # ---- sizes where the scans and copies change shape, reached by calls ---------------------------------------------------------------------------
 def test_tables_cross_their_block_edges_mid_sequence(bsa, soa, orc):
     """a wait table loaded with 1023 rows grows past 1024 AND past its quarter of headroom in one park (the twin is allocated again and the
     rows are copied), g goes 255 -> 257 -> 255, a list delta that removes groups brings the table back below 1024 rows, the bound table
-    outgrows its headroom in one bs_bound_apply_ex and is compacted by a commit"""
+    outgrows its headroom in one bs_bound_apply_ex and is compacted by a commit; then bs_bound_bind crosses the same edges
+    (_binds_across_the_edges)"""
     from test_gpu_seq_expire import waiting_scene
     G, N, S = 255, 16, 1
     rng = np.random.default_rng(1023)
@@ -387,6 +454,102 @@ def test_tables_cross_their_block_edges_mid_sequence(bsa, soa, orc):
         assert ex["n"] > 0
         r.do("forget", dict(ids=w.wt.id[[0, -1]].astype(np.uint32)))
         r.against_fresh()
+        _binds_across_the_edges(r, sc, rng)
+
+
+def _binds_across_the_edges(r, sc, rng):
+    """bs_bound_bind at the same edges, in one window: the marks by id were allocated for 1533 ids with a quarter of headroom, the bound
+    table's twin for the 297 entries of the bs_bound_apply_ex above with a quarter of headroom.  A bind of wait rows uses the marks as they
+    are; the park of the same window takes bs_wait_ids past their allocation and the table past 1024 rows; the second bind of the window
+    lists the youngest row, so the marks are allocated again inside it; the third takes the wait table below 1024 rows and the bound
+    table past its headroom, so the twin is allocated again inside it."""
+    w = r.w
+    dr = wf.Drawer(w, sc, rng)
+    # (wait_room: no earlier allocation of the marks is larger.  The twin is reserved in bytes, padded columns and per-node words included, with
+    # a quarter on top: in entries that is about 297 + 297 // 4, so the third bind is held to twice the 297, well past any rounding)
+    marks, twin = w.wt.ids + w.wt.ids // 4, 2 * 297
+    assert w.wt.ids == 1533 and w.wt.w < 1024 and w.bt.count <= 297
+    r.do("pods", dict(remove=np.arange(w.pods.p, dtype=np.uint32), insert=wf.new_pods(rng, w.S, np.repeat(np.arange(320, dtype=np.int32), 2), cls_max=1)))
+    r.do("pass")
+    free = rng.permutation(np.nonzero(w.last["pod_node"] >= 0)[0])
+    assert free.size >= 12 and int((w.wait_node >= 0).sum()) > marks - w.wt.ids, "the pass releases some gangs and leaves more pods waiting than the marks have room for"
+    r.do("bind", dr._bind_args(rng.permutation(w.wt.id)[:5], free[:4]))
+    pk = r.do("park")
+    assert w.wt.ids > marks and w.wt.w > 1024 and w.wt.ids < (1 << 24), "the park takes the ids past the marks' allocation and the table past 1024 rows"
+    r.do("bind", dr._bind_args([int(w.wt.id[-1]), int(w.wt.id[0]), pk["first_id"]], free[4:8]), flat=True)
+    assert w.bt.count <= 297 + 297 // 8, "the first two binds stay well inside the twin's headroom"
+    rows, count = w.wt.w, w.bt.count
+    r.do("bind", dr._bind_args(rng.permutation(w.wt.id)[: rows - 1000], free[8:]))
+    assert w.wt.w == 1000 < 1024 < rows and w.bt.count > twin > count
+    r.do("forget", dict(ids=w.wt.id[[0, -1]].astype(np.uint32)))                   # the marks were left clean, under their new size
+    r.do("seq_expire", dict(groups=None, deny=False, all=True))                  # the window is still open: nobody waits in it any more
+    r.against_fresh()
+
+
+def test_a_bind_raises_the_largest_group_the_preemption_calls_check(bsa, soa, orc):
+    """include/bsched.h: after bs_bound_bind the largest group index the table is held to name is the maximum of its old value and the
+    inserted groups'; the preemption calls answer BS_ERR_INVALID while it is at or above the loaded group count.  While the tables stay
+    consistent that value stays below g (a bind's groups are below g, bs_groups_list_apply takes it along), so the fuzz never sees the
+    refusal.  Here the table starts empty, so the value is the bind's own maximum m, found on the device: with m + 1 groups (a list delta
+    removes the groups above m) the preemption calls run, with a list of m groups loaded they refuse."""
+    sc = wf.scene(0)
+    assert sc["bound"].b == 0
+    with Runner(bsa, soa, orc, sc, "the largest bound group") as r:
+        w = r.w
+        dr = wf.Drawer(w, sc, np.random.default_rng(3))
+        r.do("wait_load", dict(node=(), group=(), req=None, req_present=None))
+        r.do("bound_load", dict(bound=sc["bound"]))
+        r.do("pass")
+        r.do("bind", dr.draw("bind", "cycle"))
+        m = w.bound_max
+        assert m == int(w.bt.group.max()) and 0 < m < w.g - 1, "the bind names a group, and not the last one"
+        r.do("list", dict(remove=list(range(m + 1, w.g)), update=[], rows=wf.new_group_rows(dr.rng, w.S, 0), n_append=0))
+        assert (w.g, w.bound_max) == (m + 1, m)
+        keep = np.nonzero((w.pods.group >= 0) & (w.pods.group < m))[0][:4]
+        r.do("pods", dict(remove=np.setdiff1d(np.arange(w.pods.p), keep).astype(np.uint32), insert=None))
+        pre = dict(pod_index=np.arange(keep.size, dtype=np.uint32), priority=np.full(keep.size, 5000, np.int32), protected=np.zeros(w.g, np.uint8))
+        r.do("preempt", pre)                                                    # m < g: the call runs
+        g = w.groups
+        short = soa.Groups(*[np.ascontiguousarray(getattr(g, c)[..., :m]) for c in gl.COLUMNS])
+        r.ctx.load_groups(short)                                                # the table names group m, the list ends at m - 1
+        for what, fn in [("bs_preempt_run", lambda: r.ctx.preempt(pre["pod_index"], pre["priority"], pre["protected"][:m], victim_cap=wf.CAP)),
+                         ("bs_preempt_commit", lambda: r.ctx.preempt_commit(pre["pod_index"], pre["priority"], pre["protected"][:m], victim_cap=wf.CAP, apply=False, assume=False))]:
+            assert status_of(bsa, fn) == wf.INVALID, f"{what} with {m} groups while the bound table names group {m}"
+
+
+def test_a_pod_leaves_a_node_that_lacks_its_scalar_key(bsa, soa, orc):
+    """include/bsched.h, bs_seq_expire and bs_wait_expire / bs_wait_forget: a leaving pod whose scalar key the node does not have (a loaded
+    row, or a node that bs_nodes_assume rewrote) goes by RemovePod's map rule: the lane counts as 0 before the request is taken off and the
+    node's bit becomes set.  Lanes whose key the pod does not have keep word and bit."""
+    sc = wf.scene(2)
+    S = sc["S"]
+    assert S == 2
+    rng = np.random.default_rng(11)
+    with Runner(bsa, soa, orc, sc, "a key the node lacks") as r:
+        w = r.w
+        bare = lambda k: dict(reqs=[(int(k), [int(x) for x in w.nl.req[:4, k]] + [77] * S, 0)])     # no key; the words are stale
+        r.do("wait_load", dict(node=(), group=(), req=None, req_present=None))
+        r.do("assume", bare(0))
+        rows = wf.new_pods(rng, S, [0, 1, 1, 2])
+        rows.req_present[:] = [1, 3, 2, 0]
+        rows.req[4:] = [[5, 6, 0, 0], [0, 7, 8, 0]]
+        r.do("wait_load", dict(node=np.zeros(4, np.uint32), group=rows.group, req=rows.req, req_present=rows.req_present))
+        r.do("expire", dict(groups=[0, 2], deny=False))                          # key 0 is created; lane 5 keeps its stale word
+        assert int(w.nl.rpres[0]) == 1 and w.nl.req[4:, 0].tolist() == [-5, 77]
+        r.do("forget", dict(ids=np.array([2, 1], np.uint32)))                   # key 1 is created by two rows at once, key 0 is there now
+        assert int(w.nl.rpres[0]) == 3 and w.nl.req[4:, 0].tolist() == [-11, -15]
+        # the pass's own pods: a node is rewritten without keys between the pass and bs_seq_expire
+        r.do("pass")
+        i = int(np.nonzero((w.wait_node >= 0) & (w.pods.req_present != 0))[0][0])
+        k, grp = int(w.wait_node[i]), int(w.pods.group[i])
+        r.do("assume", bare(k))
+        ex = r.do("seq_expire", dict(groups=[grp], deny=False, all=False))
+        gone = ex["pod"][ex["node"] == k]
+        keys = int(np.bitwise_or.reduce(w.pods.req_present[gone]))
+        assert i in gone and int(w.nl.rpres[k]) == keys
+        for s in range(S):
+            want = -int(w.pods.req[4 + s, gone].sum()) if (keys >> s) & 1 else 77
+            assert int(w.nl.req[4 + s, k]) == want, f"lane {4 + s} of node {k}"
 
 
 def test_gang_read_keeps_the_group_count_of_its_call(bsa, soa, orc):

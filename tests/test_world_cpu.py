@@ -4,8 +4,9 @@ often enough, the structural invariants hold after every step, the references st
 nothing.
 
 "Kind" is read as a row of the issue's table (queue, groups, list, nodes, wait, window, bound, pdb, preempt): nine rows, at least 2 per
-seed and 30 over all seeds.  (The 25 single entry points cannot each occur 30 times in 12 x 40 steps.)  On top of that every single
-entry point must occur at least 4 times over all seeds."""
+seed and 30 over all seeds.  (The 26 single entry points cannot each occur 30 times in 12 x 56 steps.)  On top of that every single
+entry point must occur at least 4 times over all seeds.  bs_bound_bind has hazard pairs and counts of its own
+(test_bind_meets_the_other_tables_often_enough)."""
 import copy
 
 import numpy as np
@@ -14,7 +15,12 @@ import pytest
 import world_ref as wf
 
 SEEDS = list(range(wf.SEEDS))
-HAZARDS = ("a", "b", "c_wait_first", "c_bound_first", "c_refused_between", "d", "e", "f", "g", "h", "leader_moves")
+HAZARDS = ("a", "b", "c_wait_first", "c_bound_first", "c_refused_between", "d", "e", "f", "g", "h", "leader_moves",
+           # bs_bound_bind's cross-call state against the other tables' calls
+           "bind_preempt_bind", "bind_in_window_expire", "bind_then_list_then_preempt", "refused_bind_then_wait_call", "bind_then_nodes_follow",
+           "bind_uncovered_then_pdb")
+PREEMPT_CALLS = ("preempt", "commit", "commit_gang")
+BIND_REFUSALS = ("bind_stale", "bind_window", "bind_waits", "bind_dead")
 
 
 def _snapshot(w):
@@ -24,7 +30,23 @@ def _snapshot(w):
     out["groups"], out["pods"] = r["groups"].copy(), r["pods"].copy()
     out["extra"] = (w.leader, w.bound_max, w.window, list(w.pend_w), list(w.pend_b), None if w.wt is None else (w.wt.n, w.wt.g),
                     None if w.bt is None else w.bt.n)
+    # what bs_bound_bind reads beyond the reads: the pass's result block, and the live wait ids while the counts are stale (with wait_ids: the dead ones)
+    out["bind"] = (None if w.last is None else w.last["pod_node"].copy(), None if w.pass_wait is None else w.pass_wait.copy(),
+                   None if w.wt is None else w.wt.id.copy())
     return out
+
+
+def _bind_refusal(w, args, status):
+    """which of the plan's four refused binds this one is, from the state it meets (tests/world_ref.py, Drawer.d_refuse)"""
+    if status == wf.STATE:
+        stale = w.bt is not None and (w.bt.n != w.n or (w.wt is not None and w.wt.n != w.n))
+        return "bind_stale" if stale else "bind_window" if len(args["pod_index"]) and not w.window else None
+    if status == wf.INVALID and len(args["wait_ids"]) and w.window:
+        if any(w.wait_node[int(p)] >= 0 for p in args["pod_index"]):
+            return "bind_waits"
+        if not np.all(np.isin(args["wait_ids"], w.wt.id)) and np.any(np.isin(args["wait_ids"], w.wt.id)) and len(args["pod_index"]):
+            return "bind_dead"
+    return None
 
 
 def _same(a, b):
@@ -47,10 +69,13 @@ class Hazards:
     def __init__(self):
         self.count = dict.fromkeys(HAZARDS, 0)
         self.e_kinds = set()
+        self.blp_outcome = {wf.OK: 0, wf.INVALID: 0}   # what the preemption call of bind_then_list_then_preempt was predicted to answer
         self.reset()
 
     def reset(self):
         self.a = self.b = self.f = self.g = self.h = self.lm = 0
+        self.bpb = self.bwe = self.blp = self.rbw = self.bnf = self.bup = 0
+        self.bnf_seen = set()
         self.c = None                      # after node surgery: the *_nodes_apply calls seen so far
         self.d, self.e = False, None
 
@@ -59,6 +84,12 @@ class Hazards:
         if refused:
             if self.c is not None and len(self.c) == 1 and kind in wf.WAIT_CALLS + wf.BOUND_CALLS:
                 hit("c_refused_between")
+            if kind == "bind" and before["bind_refusal"] in ("bind_waits", "bind_dead") and len(args["wait_ids"]):
+                self.rbw = 1               # found on the device after the marks by id were set
+            if kind in PREEMPT_CALLS and self.blp == 2 and out["status"] == wf.INVALID:
+                hit("bind_then_list_then_preempt")
+                self.blp_outcome[wf.INVALID] += 1
+                self.blp = 0
             return
         if kind in ("bound_load", "wait_load"):
             self.reset()
@@ -129,6 +160,52 @@ class Hazards:
         elif kind in ("batch", "pass") and self.lm:
             hit("leader_moves")
             self.lm = 0
+        # bind, a preemption call (the scratch buffer bind carves its blocks from), bind; no bound reload between them
+        if kind == "bind":
+            if self.bpb == 2:
+                hit("bind_preempt_bind")
+            self.bpb = 1
+        elif kind in PREEMPT_CALLS and self.bpb:
+            self.bpb = 2
+        # a bind with pods, then bs_seq_expire in the window the bind kept open
+        if kind == "pass" or not w.window:
+            self.bwe = 0
+        elif kind == "bind" and len(args["pod_index"]):
+            self.bwe = 1
+        elif kind == "seq_expire" and self.bwe:
+            hit("bind_in_window_expire")
+            self.bwe = 0
+        # a bind that raises the largest group the bound table is held to name, a list delta that removes a group, a preemption call
+        if kind == "bind" and w.bound_max > before["bound_max"]:
+            self.blp = 1
+        elif kind == "list" and self.blp == 1 and len(args["remove"]):
+            self.blp = 2
+        elif kind in PREEMPT_CALLS and self.blp == 2:
+            hit("bind_then_list_then_preempt")
+            self.blp_outcome[wf.OK] += 1
+            self.blp = 0
+        # a bind the device refused after the marks were set, then a successful call of the wait core
+        if kind in ("forget", "release", "expire") and self.rbw:
+            hit("refused_bind_then_wait_call")
+            self.rbw = 0
+        # a bind with wait ids (both twins flipped), node-list surgery, both *_nodes_apply
+        if kind == "bind" and len(args["wait_ids"]):
+            self.bnf = 1
+        elif kind == "nodes" and self.bnf == 1 and any(k != wf.UPDATE for k, _ in args["ops"]):
+            self.bnf, self.bnf_seen = 2, set()
+        elif kind in ("wait_nodes", "bound_nodes") and self.bnf == 2:
+            self.bnf_seen.add(kind)
+            if len(self.bnf_seen) == 2:
+                hit("bind_then_nodes_follow")
+                self.bnf = 0
+        # a bind while resident PDBs exist (its ids are not covered), then a recompute
+        if kind == "pdb_load":
+            self.bup = 0
+        elif kind == "bind" and before["pdb_resident"]:
+            self.bup = 1
+        elif kind in ("pdb_allowed", "pdb_append") and self.bup:
+            hit("bind_uncovered_then_pdb")
+            self.bup = 0
         # (h) a pass that leaves a leader, the leader's group removed, a batch, a pass
         if kind == "pass":
             if self.h == 3:
@@ -153,9 +230,20 @@ def replayed(orc):
         kinds, rows, refusals = {}, dict.fromkeys(wf.ROWS, 0), 0
         shared_node = evicted_waiting = False
         n_seen, victims = {w.n}, 0
+        binds = dict(ok=0, wait=0, pods=0, both=0, empties_wait=0, from_empty=0, sentinel=0, stale_pods_only=0, **dict.fromkeys(BIND_REFUSALS, 0))
         for i, (kind, args, refused) in enumerate(steps):
             where = f"seed {seed} step {i} {kind}"
-            before = dict(g=w.g, n=w.n, leader=w.leader, hot_removed=False)
+            before = dict(g=w.g, n=w.n, leader=w.leader, hot_removed=False, bound_max=w.bound_max, pdb_resident=w.pm is not None, bind_refusal=None)
+            if kind == "bind":
+                nw, npod = len(args["wait_ids"]), len(args["pod_index"])
+                if not refused:
+                    binds["ok"] += 1
+                    binds["wait"] += nw > 0
+                    binds["pods"] += npod > 0
+                    binds["both"] += nw > 0 and npod > 0
+                    binds["empties_wait"] += nw > 0 and nw == w.wt.w
+                    binds["from_empty"] += w.bt.count == 0
+                    binds["sentinel"] += bool(npod and np.any(w.pods.group[args["pod_index"]] < 0))
             if kind == "list" and w.wt is not None and w.bt is not None:
                 before["hot_removed"] = any(np.any(w.wt.group == x) and np.any(w.bt.group == x) for x in args["remove"])
             snap = _snapshot(w) if refused else None
@@ -164,6 +252,11 @@ def replayed(orc):
             if refused:
                 assert _same(snap, _snapshot(w)), f"{where}: a refused call changed the model"
                 refusals += 1
+                if kind == "bind":                                              # (nothing changed: the state the call met is still there)
+                    r = before["bind_refusal"] = _bind_refusal(w, args, out["status"])
+                    assert r is not None, f"{where}: a refused bind that is none of {BIND_REFUSALS}"
+                    binds[r] += 1
+                    binds["stale_pods_only"] += r == "bind_stale" and not len(args["wait_ids"])
             else:
                 kinds[kind] = kinds.get(kind, 0) + 1
                 rows[wf.ROW_OF[kind]] += 1
@@ -178,16 +271,19 @@ def replayed(orc):
                 if w.wt is not None and out["victim_groups"].size:
                     evicted_waiting |= bool(np.isin(out["victim_groups"], w.wt.group).any())
         seeds.append(dict(seed=seed, S=sc["S"], kinds=kinds, rows=rows, refusals=refusals, shared_node=shared_node, evicted_waiting=evicted_waiting,
-                          n_seen=n_seen, victims=victims, g0=sc["groups"].g, p0=sc["pods"].p, b0=sc["bound"].b))
+                          n_seen=n_seen, victims=victims, g0=sc["groups"].g, p0=sc["pods"].p, b0=sc["bound"].b, binds=binds))
     total_rows = {r: sum(s["rows"][r] for s in seeds) for r in wf.ROWS}
     total_kinds = {k: sum(s["kinds"].get(k, 0) for s in seeds) for k in wf.ROW_OF}
     print("\nrows over all seeds:", total_rows)
     print("entry points over all seeds:", total_kinds)
     print("hazard pairs over all seeds:", hz.count, "(e) through", sorted(hz.e_kinds))
+    total_binds = {k: sum(s["binds"][k] for s in seeds) for k in seeds[0]["binds"]}
+    print("binds over all seeds:", total_binds, "per seed:", [s["binds"]["ok"] for s in seeds])
+    print("bind_then_list_then_preempt: the preemption call predicted OK / INVALID:", hz.blp_outcome[wf.OK], "/", hz.blp_outcome[wf.INVALID])
     for s in seeds:
         print(f"seed {s['seed']}: S={s['S']} g0={s['g0']} p0={s['p0']} b0={s['b0']} n {min(s['n_seen'])}..{max(s['n_seen'])} refusals {s['refusals']} "
               f"victims {s['victims']} rows {s['rows']}")
-    return dict(seeds=seeds, rows=total_rows, kinds=total_kinds, hazards=hz)
+    return dict(seeds=seeds, rows=total_rows, kinds=total_kinds, hazards=hz, binds=total_binds)
 
 
 def test_the_scenes_are_the_sizes_the_issue_names(replayed):
@@ -221,6 +317,24 @@ def test_every_hazard_pair_occurs_three_times(replayed):
     for k, c in hz.count.items():
         assert c >= 3, f"hazard pair ({k}) occurs {c} times: {hz.count}"
     assert hz.e_kinds == {"expire", "forget", "seq_expire"}, f"(e) is reached through {hz.e_kinds} only"
+
+
+def test_bind_meets_the_other_tables_often_enough(replayed):
+    """the counts of bs_bound_bind over the twelve seeds.  Of the two outcomes of bind_then_list_then_preempt's preemption call only BS_OK can
+    occur in a plan whose tables stay consistent: a bind's rows come from the wait table and the queue, whose group columns are below g, so it
+    raises the bound table's largest group to g - 1 at most, and a list delta takes a value below g to g_new - 1 at most
+    (groups_list_ref.max_group).  BS_ERR_INVALID would need a bound entry that names a group at or above g, which World.invariants rules out."""
+    hz, b = replayed["hazards"], replayed["binds"]
+    for s in replayed["seeds"]:
+        assert s["binds"]["ok"] >= 1, f"seed {s['seed']}: no successful bind"
+    assert b["wait"] >= 8 and b["pods"] >= 8 and b["both"] >= 4, b
+    assert b["empties_wait"] >= 1, "no bind empties the wait table"
+    assert b["from_empty"] >= 1, "no bind runs from an empty bound table"
+    assert b["sentinel"] >= 1, "no bind lists a pod whose group is a sentinel"
+    for r in BIND_REFUSALS:
+        assert b[r] >= 2, f"the refusal {r} occurs {b[r]} times: {b}"
+    assert b["stale_pods_only"] >= 1, "bind_stale never lists pods only"
+    assert hz.blp_outcome[wf.OK] >= 1, hz.blp_outcome
 
 
 def test_gangs_share_nodes_and_a_commit_evicts_beside_a_waiting_pod(replayed):

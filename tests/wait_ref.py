@@ -116,7 +116,8 @@ def _group_list(tab, groups):
 
 def _leave(st, tab, rows):
     """NodeInfo.RemovePod for table rows: lanes 0..2 minus the request, the pods lane minus 1, a scalar lane the row has a present bit for
-    loses the request and keeps its node bit, other scalar lanes keep word and bit; wrapping int64"""
+    loses the request and keeps its node bit, other scalar lanes keep word and bit; a key the node lacks counts as 0 and its bit becomes
+    set (RemovePod's map rule); wrapping int64"""
     for e in rows:
         k, pres = int(tab.node[e]), int(tab.req_present[e])
         for j in range(3):
@@ -124,6 +125,9 @@ def _leave(st, tab, rows):
         st.requested[3, k] = ser.w64(int(st.requested[3, k]) - 1)
         for s in range(tab.S):
             if (pres >> s) & 1:
+                if not (int(st.requested_present[k]) >> s) & 1:
+                    st.requested[4 + s, k] = 0
+                    st.requested_present[k] |= np.uint32(1 << s)
                 st.requested[4 + s, k] = ser.w64(int(st.requested[4 + s, k]) - int(tab.req[4 + s, e]))
 
 

@@ -10,9 +10,10 @@ them back.  What two references would each keep a copy of has ONE home here:
   wait rows         World.wt                (wait_ref.Table)
 
 `World.step(kind, args)` applies one call and returns what the call returns, or {"status": code} for a call the header refuses (the validity
-paragraphs of include/bsched.h: stale counts, the window) — a refused call changes nothing here.  `plan(seed)` draws scenes and operation
-sequences on a World of its own, so that whoever replays the steps on a fresh World (tests/test_world_cpu.py) or on a World beside a device
-context (tests/test_gpu_world.py) sees the same sequence."""
+paragraphs of include/bsched.h: stale counts, the window) — a refused call changes nothing here.  bs_bound_bind is `_bind`:
+bound_bind_ref.bind over the bound table, the wait table, the queue and the last pass's results at once.  `plan(seed)` draws scenes and
+operation sequences on a World of its own, so that whoever replays the steps on a fresh World (tests/test_world_cpu.py) or on a World
+beside a device context (tests/test_gpu_world.py) sees the same sequence."""
 from __future__ import annotations
 
 import importlib
@@ -21,6 +22,7 @@ import numpy as np
 
 import bound_apply_nodes_ref as ban
 import bound_apply_ref as ba
+import bound_bind_ref as bbr
 import bound_nodes_ref as bn
 import groups_list_ref as gl
 import pdb_resident_ref as pdr
@@ -44,13 +46,13 @@ ROWS = {
     "nodes": ("nodes", "assume"),
     "wait": ("wait_load", "park", "release", "expire", "forget", "wait_nodes"),
     "window": ("seq_expire",),
-    "bound": ("bound_load", "bound_apply", "bound_apply_ex", "bound_nodes", "pdb_set"),
+    "bound": ("bound_load", "bound_apply", "bound_apply_ex", "bind", "bound_nodes", "pdb_set"),
     "pdb": ("pdb_load", "pdb_append", "pdb_allowed"),
     "preempt": ("preempt", "commit", "commit_gang"),
 }
 ROW_OF = {k: row for row, ks in ROWS.items() for k in ks}
 WAIT_CALLS = ("park", "release", "expire", "forget")
-BOUND_CALLS = ("bound_apply", "bound_apply_ex", "pdb_set", "pdb_load", "pdb_append", "pdb_allowed", "preempt", "commit", "commit_gang")
+BOUND_CALLS = ("bound_apply", "bound_apply_ex", "bind", "pdb_set", "pdb_load", "pdb_append", "pdb_allowed", "preempt", "commit", "commit_gang")
 
 
 def id_map_by_table_order(ids) -> np.ndarray:
@@ -84,6 +86,7 @@ class World:
         self.placed = None                 # queue pods the last pass gave a node (until the queue changes): what a caller binds or parks
         self.unplaced = None               # queue pods that passed PreFilter in the last pass and found no node: the preemptors
         self.last = None                   # the last pass's record, while the queue is the one it ran on
+        self.pass_wait = None              # the pass's own wait_node as of the pass (bs_wait_park and bs_seq_expire empty World.wait_node)
 
     # ---- counts and validity, as the header states them -------------------------------------------------------------------------------
     @property
@@ -135,7 +138,7 @@ class World:
 
     def _queue_changed(self):
         self._shut()
-        self.placed = self.unplaced = self.last = None
+        self.placed = self.unplaced = self.last = self.pass_wait = None
 
     def _recompute_bits(self):
         self.bt.pdb = self.pm.bits(self.bt.ids)[self.bt.id.astype(np.int64)].astype(np.uint8)
@@ -215,7 +218,7 @@ class World:
         self.placed = np.nonzero((s["pod_node"] >= 0) | (wait >= 0))[0]
         grouped = (self.pods.group >= 0) & (self.pods.group < self.g)
         self.unplaced = np.nonzero((s["pf_code"] < 16) & (s["pod_node"] < 0) & (wait < 0) & grouped)[0]
-        self.last = s
+        self.last, self.pass_wait = s, wait.copy()
         return dict(seq=s)
 
     def _list(self, remove, update, rows, n_append):
@@ -238,7 +241,7 @@ class World:
             t.id, t.node, t.group, t.req, t.req_present = (m["wait"][k] for k in ("id", "node", "group", "req", "req_present"))
             t.g = m["g_new"]
         self._shut()
-        self.last = None                   # (its released_group names old indices)
+        self.last = self.pass_wait = None  # (its released_group names old indices)
         d = m["dropped"]
         return dict(g_new=m["g_new"], n_pods_missing=m["n_pods_missing"], n_bound_missing=m["n_bound_missing"], n_wait_dropped=len(d[0]),
                     wait_id=d[0], wait_node=d[1], wait_group=d[2])
@@ -249,7 +252,7 @@ class World:
         pairs = [(int(d.kind), int(d.index)) for d in deltas]
         if any(k != UPDATE for k, _ in pairs):
             self._shut()
-            self.last = None               # (its pod_node names old indices)
+            self.last = self.pass_wait = None          # (its pod_node names old indices)
         if self.wt is not None:
             self.pend_w += pairs
         if self.bt is not None:
@@ -323,6 +326,18 @@ class World:
 
     def _bound_apply_ex(self, remove, insert, pdb, flags=ban.BOUND_NODES):
         return self._bound_delta(remove, insert, pdb, flags)
+
+    def _bind(self, wait_ids, pod_index, priority, start_ns, pdb):
+        """bs_bound_bind: bound_bind_ref.bind over the world's own tables.  Node requests, group words, leader, queue and window stay; the
+        resident PDB state stays too, as for an insert of bs_bound_apply (the given bits stand until the next recompute)"""
+        s = self.last
+        try:
+            out = bbr.bind(self.bt, self.wt, self.n, self.g, wait_ids, pod_index, priority, start_ns, pdb, pods=self.pods,
+                           pod_node=None if s is None else s["pod_node"], wait_node=self.wait_node, window=self.window)
+        except bbr.BindError as e:
+            return dict(status=e.status)
+        self.bound_max = bbr.max_group(self.bound_max, self.bt.group[self.bt.id >= out["first_id"]])
+        return out
 
     def _bound_nodes(self):
         kind, index = [k for k, _ in self.pend_b], [i for _, i in self.pend_b]
@@ -421,6 +436,7 @@ class World:
 N_START = [5, 63, 12, 40, 17, 33, 24, 13, 38, 29, 21, 36]       # seed 0 crosses 4 nodes downwards, seed 1 crosses 64 upwards
 SCALARS = [0, 1, 2, 12]
 BOUND_PRIO = np.array([0, 100, 200, 300])
+BIND_START = np.array([7, 25, 60])                              # (a loaded entry starts at 0 .. 49: 7 and 25 tie with survivors)
 
 
 def new_pods(rng, S, groups_of, cls_max=2):
@@ -501,24 +517,36 @@ def world_of(orc, sc) -> World:
 # ======================================================================================================================================
 # the plan
 # ======================================================================================================================================
-STEPS, SEEDS = 40, 12
+STEPS, SEEDS = 56, 12
 DEBUG = False
 # the hazard pairs of tests/test_world_cpu.py as call sequences; (kind, hint) asks the drawer for a particular shape of the call
 MOTIFS = {
     "a": ["pass", "park", ("list", "hot"), ("commit_gang", "apply")],
     "b": ["pods", "pass", ("commit", "assume"), ("seq_expire", "one"), "seq_expire"],
-    "c": [("nodes", "shrink"), "bound_nodes", ("refuse", "stale_wait"), "wait_nodes", "bound_apply", "pdb_set"],
+    "c": [("nodes", "shrink"), ("refuse", "bind_stale"), "bound_nodes", ("refuse", "stale_wait"), "wait_nodes", "bound_apply", "pdb_set"],
     "d": [("list", "resize"), ("expire", "any"), ("list", "resize"), "release"],
-    "e": [("nodes", "grow"), "wait_nodes", ("refuse", "stale_bound"), "bound_nodes", ("expire", "any"), "forget", "pass", ("seq_expire", "one"), "seq_expire"],
+    "e": [("nodes", "grow"), ("refuse", "bind_stale"), "wait_nodes", ("refuse", "stale_bound"), "bound_nodes", ("expire", "any"), "forget", "pass", ("seq_expire", "one"), "seq_expire"],
     "f": [("batch", "plain"), ("list", "update"), "groups", ("list", "append"), ("batch", "plain")],
     "h": ["pass", ("list", "below"), ("batch", "plain"), ("list", "leader"), ("batch", "commit"), "pods", "pass"],
+    # bs_bound_bind between the other tables' calls: its blocks in the preemption calls' scratch while the id space grows; the window it
+    # keeps open, both twins flipped, bound_max_group raised and lowered; bound ids the resident PDBs do not cover
+    # (the two refusals the kernels find are in the motifs where their state is sure to exist: a dead id after a bind of wait rows, a pod
+    # that still waits between a pass and its park; each is made once per seed and is followed by the forget it owes)
+    "i": ["pass", ("bind", "both"), ("refuse", "bind_dead"), "preempt", ("bind", "wait"), ("commit", "apply"), ("bind", "pods")],
+    "j": [("list", "room"), "pods", "pass", ("bind", "pods"), ("refuse", "bind_waits"), ("seq_expire", "one"), "park", ("bind", "wait"), ("list", "hot"), ("commit_gang", "apply")],
+    "k": ["pdb_load", ("bind", "both"), "pdb_allowed", "pdb_append", "preempt"],
 }
 MOTIF_ORDER = ["c", "e", "f", "h"]                          # (a, b and g are in every seed's first cycle; d comes about by itself)
+MOTIF_ORDER_BIND = ["i", "j", "k"]                          # two of each list per seed, in turn
 # the first cycle is the header's: pass, preemption for the pods without a node, the released gangs leave Permit and bind, the others park;
 # then a gang leaves the cache and the next preemption runs on what all that left behind.  An item that is not applicable is left out
 OPENING = ["pass", "pdb_load", ("commit", "assume"), ("seq_expire", "one"), ("release", "released"), ("bound_apply_ex", "bind"), "park", "pdb_allowed",
            ("list", "hot"), ("commit_gang", "apply"), "pods"]
-REFUSALS = ["stale_wait", "stale_bound", "window", "list_order", "forget_dead", "expire_twice"]
+# odd seeds bind in the header's new form: bs_bound_bind takes the released gangs' wait rows with it, so no bs_wait_release goes before it
+OPENING_BIND = [x for x in OPENING if x != ("release", "released")]
+OPENING_BIND[OPENING_BIND.index(("bound_apply_ex", "bind"))] = ("bind", "cycle")
+REFUSALS = ["stale_wait", "stale_bound", "window", "list_order", "forget_dead", "expire_twice", "bind_stale", "bind_window", "bind_waits", "bind_dead"]
+ON_DEVICE = ("forget_dead", "expire_twice", "bind_waits", "bind_dead")          # found by the kernels: each once per seed, each followed by a successful call
 
 
 class Drawer:
@@ -527,6 +555,8 @@ class Drawer:
     def __init__(self, w: World, sc: dict, rng):
         self.w, self.sc, self.rng = w, sc, rng
         self.serial = 0
+        self.taken, self.taken_of = set(), None
+        self.owed = None                   # (kind, args) of the successful call a refusal found on the device is followed by
 
     def draw(self, kind, hint=None):
         w = self.w
@@ -544,7 +574,11 @@ class Drawer:
         u = rng.random(grp.size)
         grp[u < 0.04] = soa.POD_NOT_GROUPED
         grp[(u >= 0.04) & (u < 0.06)] = soa.POD_GROUP_MISSING
-        return dict(remove=remove.astype(np.uint32), insert=new_pods(rng, w.S, np.sort(grp)) if k > 0 else None)
+        grp = np.sort(grp)
+        if w.bt is not None and -1 <= w.bound_max < w.g - 1:
+            # gangs the bound table does not name yet, in front of the other arrivals (first fit runs out of nodes): their bind raises its largest group
+            grp[: 4] = np.sort(rng.integers(w.bound_max + 1, w.g, grp[: 4].size))
+        return dict(remove=remove.astype(np.uint32), insert=new_pods(rng, w.S, grp) if k > 0 else None)
 
     def d_groups(self, hint):
         w, rng = self.w, self.rng
@@ -592,6 +626,9 @@ class Drawer:
             if room_up < 1:
                 return None
             n_append = int(rng.integers(1, min(room_up, 3) + 1))
+        elif hint == "room":               # new gangs at the top that no table names yet; at 40 groups one leaves for them
+            remove = [] if room_up >= 1 else [int(rng.integers(0, g))]
+            n_append = int(rng.integers(1, min(room_up + len(remove), 2) + 1))
         else:                              # "resize" changes g; None is anything
             k = int(rng.integers(0 if hint is None else 1, 4))
             remove = sorted(rng.choice(g, k, replace=False).tolist())
@@ -737,8 +774,63 @@ class Drawer:
             p = w.pods
             ins = soa.Bound(s["pod_node"][idx].astype(np.uint32), rng.choice(BOUND_PRIO, idx.size).astype(np.int32), rng.integers(50, 99, idx.size).astype(np.int64),
                             p.group[idx].copy(), p.req[:, idx].copy(), p.req_present[idx].copy())
+            self._take(idx)
             return dict(remove=np.zeros(0, np.uint32), insert=ins, pdb=None)
         return self._bound_delta(hint)
+
+    def _bindable(self):
+        """the queue pods a bind may list now: the last pass placed them, they did not wait when the pass ended (a pod the pass left waiting
+        and bs_wait_park parked since reads as not waiting: the header's unchecked hazard), and no earlier bind of this window took them"""
+        w = self.w
+        if not w.window or w.last is None:
+            return np.zeros(0, np.int64)
+        free = np.nonzero((w.last["pod_node"] >= 0) & (w.pass_wait < 0))[0]
+        return np.array([int(p) for p in free if int(p) not in self._taken()], np.int64)
+
+    def _taken(self):
+        """the queue pods the binds drawn since the last pass listed (every drawn call is made, and succeeds)"""
+        if self.taken_of is not self.w.last:
+            self.taken, self.taken_of = set(), self.w.last
+        return self.taken
+
+    def _take(self, pods):
+        self._taken().update(int(p) for p in pods)
+
+    def _bind_args(self, wl, pl):
+        """priorities of the bound table's four, starts from three values (ties with survivors and among the rows), bits half the time"""
+        rng = self.rng
+        n = len(wl) + len(pl)
+        return dict(wait_ids=np.asarray(wl, np.uint32), pod_index=np.asarray(pl, np.uint32), priority=rng.choice(BOUND_PRIO, n).astype(np.int32),
+                    start_ns=rng.choice(BIND_START, n).astype(np.int64), pdb=rng.integers(0, 2, n).astype(np.uint8) if rng.random() < 0.5 else None)
+
+    def d_bind(self, hint):
+        """"wait": rows of the wait table by id, shuffled; "pods": pods the last pass placed; "both"; "cycle": the header's bind, every wait
+        row of a gang the last pass released and every pod it placed.  A hint that asks for rows there are none of takes the other kind"""
+        w, rng = self.w, self.rng
+        if not w.bound_ok():
+            return None
+        rows = w.wt.id if w.wait_ok() else np.zeros(0, np.uint32)
+        free = self._bindable()
+        if hint == "cycle":
+            rel = w.last["released_group"] if w.last is not None and w.last["n_released"] else []
+            wl = rng.permutation(rows[np.isin(w.wt.group, rel)]) if rows.size else rows
+            pl = rng.permutation(free)
+        else:
+            hint = str(rng.choice(["wait", "pods", "both", "both"])) if hint is None else hint
+            kw = rows.size if rng.random() < 0.25 else int(rng.integers(1, min(rows.size, 8) + 1)) if rows.size else 0
+            kp = free.size if rng.random() < 0.3 else int(rng.integers(1, min(free.size, 6) + 1)) if free.size else 0
+            if hint == "wait" and kw:
+                kp = 0
+            if hint == "pods" and kp:
+                kw = 0
+            # rows that raise the largest group the bound table names, and pods without a group, go first: they are few
+            rows = rows[np.argsort(w.wt.group <= w.bound_max, kind="stable")] if rows.size else rows
+            free = free[np.argsort((w.pods.group[free] >= 0) & (w.pods.group[free] <= w.bound_max), kind="stable")]
+            wl, pl = rng.permutation(rows[:kw]), rng.permutation(free[:kp])
+        if not len(wl) and not len(pl):
+            return None
+        self._take(pl)
+        return self._bind_args(wl, pl)
 
     def d_bound_nodes(self, hint):
         return dict() if self.w.bt is not None and self.w.pend_b else None
@@ -817,6 +909,7 @@ class Drawer:
     def d_refuse(self, hint):
         """-> (kind, args) of a call the model predicts a refusal for, or None"""
         w, rng = self.w, self.rng
+        self.owed = None
         if hint == "stale_wait":
             if w.wt is None or w.wt.n == w.n:
                 return None
@@ -854,15 +947,44 @@ class Drawer:
                 return None
             x = int(w.wt.group[0])
             return "expire", dict(groups=[x, x], deny=True)
+        if hint == "bind_stale":           # between node-list surgery and the *_nodes_apply calls; with only pods listed too (surgery shut the window)
+            if w.bt is None or (w.bt.n == w.n and (w.wt is None or w.wt.n == w.n)):
+                return None
+            live = w.wt is not None and w.wt.w and (w.bt.n == w.n or rng.random() < 0.5)
+            if not live and not w.pods.p:
+                return None
+            return "bind", self._bind_args(w.wt.id[:1], []) if live else self._bind_args([], [int(rng.integers(0, w.pods.p))])
+        if hint == "bind_window":
+            if w.window or not w.bound_ok() or w.pend_w or w.pend_b or not w.pods.p:
+                return None
+            return "bind", self._bind_args([], [int(rng.integers(0, w.pods.p))])
+        if hint in ("bind_waits", "bind_dead"):
+            if not w.bound_ok() or not w.wait_ok() or not w.wt.w or not w.window or w.pend_w or w.pend_b:
+                return None
+            live = int(rng.choice(w.wt.id))
+            free = self._bindable()
+            if hint == "bind_waits":       # a pod the pass left waiting that nobody has parked or expired: the kernels find it, after the marks were set
+                waits = np.nonzero(w.wait_node >= 0)[0]
+                if not waits.size:
+                    return None
+                got = "bind", self._bind_args([live], [int(p) for p in free[:1]] + [int(rng.choice(waits))])
+            else:                          # a dead id beside a live one and a pod that would bind
+                dead = np.setdiff1d(np.arange(w.wt.ids), w.wt.id)
+                if not dead.size or not free.size:
+                    return None
+                got = "bind", self._bind_args([live, int(rng.choice(dead))], [int(rng.choice(free))])
+            self.owed = ("forget", dict(ids=np.array([live], np.uint32)))
+            return got
         raise KeyError(hint)
 
 
 def plan(seed: int, orc):
     """-> (scene, steps): steps = [(kind, args, refused)] drawn on a World of the plan's own.  The first two calls load the (empty) wait
-    table and the bound table.  Then three motifs per seed, in rotation over the seeds, with single calls between them: the single call
-    is of the row of calls (ROWS) this seed has used least so far, and within the row the entry point used least.  Every sixth step is a
-    call the model predicts a refusal for.  A call that is not applicable is drawn again as another call, never skipped; the two refusals
-    the device finds are followed by a successful call of the same removal core."""
+    table and the bound table.  Then four motifs per seed (two of MOTIF_ORDER, two of MOTIF_ORDER_BIND, in rotation over the seeds), with
+    single calls between them: the single call is of the row of calls (ROWS) this seed has used least so far, and within the row the entry
+    point used least.  Every sixth step is a call the model predicts a refusal for.  A call that is not applicable is drawn again as
+    another call, never skipped; the four refusals the device finds (ON_DEVICE) are each followed by a successful call of the same
+    removal core: a refused bind by the forget of the live id it listed."""
     sc = scene(seed)
     w = world_of(orc, sc)
     rng = np.random.default_rng(88000 + seed)
@@ -907,31 +1029,33 @@ def plan(seed: int, orc):
 
     do("wait_load", dict(node=(), group=(), req=None, req_present=None))
     do("bound_load", dict(bound=sc["bound"]))
-    motifs = [MOTIF_ORDER[(seed + 2 * k) % len(MOTIF_ORDER)] for k in range(3)]
-    on_device = {"forget_dead", "expire_twice"}                                  # each once per seed: they cost a second call
+    motifs = [MOTIF_ORDER[seed % 4], MOTIF_ORDER_BIND[seed % 3], MOTIF_ORDER[(seed + 2) % 4], MOTIF_ORDER_BIND[(seed + 1) % 3]]
+    on_device = set(ON_DEVICE)                                                   # each once per seed: they cost a second call
     if sc["nodes"].n <= 5 and "c" not in motifs:
         motifs[0] = "c"                    # this seed takes its node count down across 4
     if sc["nodes"].n > 60 and "e" not in motifs:
         motifs[0] = "e"                    # and this one up across 64
     after = None                           # a successful call owed after a refusal the device found
     gap = 0
-    queue, opening = list(OPENING), True   # the first cycle: its pass leaves gangs waiting that share nodes
+    # the first cycle: its pass leaves gangs waiting that share nodes.  (Seed 0 binds in the new form too: its bound table is the empty one)
+    queue, opening = list(OPENING_BIND if seed % 2 or not sc["bound"].b else OPENING), True
     while len(steps) < STEPS:
         if after is not None:
             kind, after = after, None
-            a = dr.draw(kind)
+            a = dr.draw(kind) if isinstance(kind, str) else kind[1]
+            kind = kind if isinstance(kind, str) else kind[0]
             assert a is not None, f"seed {seed}: the {kind} owed after a refusal on the device is not applicable"
             do(kind, a)
             continue
         if len(steps) % 6 == 5 and 6 * sum(r for _, _, r in steps) < len(steps) + 1:       # a sixth, the motifs' own refusals included
             order = list(rng.permutation(REFUSALS))
             if w.pend_w or w.pend_b:
-                order = ["stale_wait", "stale_bound"] + order
+                order = [str(x) for x in rng.permutation(["stale_wait", "stale_bound", "bind_stale"])] + order
             for r in order:
-                got = dr.d_refuse(r) if r not in ("forget_dead", "expire_twice") or r in on_device else None
+                got = dr.d_refuse(r) if r not in ON_DEVICE or r in on_device else None
                 if got is not None:
                     do(got[0], got[1], refused=True)
-                    after = {"forget_dead": "forget", "expire_twice": "expire"}.get(r)
+                    after = dr.owed or {"forget_dead": "forget", "expire_twice": "expire"}.get(r)
                     on_device.discard(r)
                     break
             else:
@@ -952,9 +1076,11 @@ def plan(seed: int, orc):
             continue
         kind, hint = (item, None) if isinstance(item, str) else item
         if kind == "refuse":
-            got = dr.d_refuse(hint)
+            got = dr.d_refuse(hint) if hint not in ON_DEVICE or hint in on_device else None
             if got is not None:
                 do(got[0], got[1], refused=True)
+                after = dr.owed
+                on_device.discard(hint)
             continue
         a = dr.draw(kind, hint)
         if a is None:                      # not applicable: the rest of the motif goes with it, other calls are drawn
