@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libbsched.so")
 # everything that builds, links or tests staleness goes by LINK_UNITS / LINK_SOURCES.
 # translation units -> the headers each one depends on, transitively (tests/test_build_units_cpu.py follows the #includes; DESIGN.md section 4 "Build")
 _COMMON = ["bs_common.hpp", "bs_kernels.hpp", "bs_nodew_layout.hpp", "bs_lanes.hpp", os.path.join("..", "..", "include", "bsched.h")]
-_CTX = _COMMON + ["bs_ctx.hpp", "bs_carve.hpp", "bs_hostmem.hpp", "bs_pod_ranges.hpp"]      # the units that hold entry points
+_CTX = _COMMON + ["bs_ctx.hpp", "bs_carve.hpp", "bs_layouts.hpp", "bs_hostmem.hpp", "bs_pod_ranges.hpp"]      # the units that hold entry points
 _FAST = ["bs_launch.hpp", "bs_fast.hpp", "bs_filter_t.hpp"]
 _SEQ = _CTX + ["bs_seq.hpp"]
 UNITS = {

@@ -1,10 +1,12 @@
 // bs_ctx.hpp — the context behind the C ABI of include/bsched.h, and what the translation units that implement that ABI share: bsched.hip
-// (contexts, loads, the batch) and the family units tu_seq.hip, tu_seq_expire.hip and tu_preempt.hip (their entry points beside their kernels).
+// (contexts, loads, the batch) and the family units tu_seq.hip, tu_seq_expire.hip, tu_preempt.hip, tu_wait.hip, tu_groups.hip and tu_bind.hip
+// (their entry points beside their kernels).
 // Host code only: no kernel, and no header of a kernel family (the field types come from bs_kernels.hpp and the plain host headers).
 #pragma once
 #include <rccl/rccl.h>   // types and enums only: librccl itself is dlopen'ed on demand (hosts without RCCL can still load the library)
 
 #include <algorithm>
+#include <cstring>
 #include <functional>
 #include <string>
 #include <vector>
@@ -13,6 +15,7 @@
 #include "bs_hostmem.hpp"
 #include "bs_kernels.hpp"
 #include "bs_lanes.hpp"
+#include "bs_layouts.hpp"
 #include "bs_pod_ranges.hpp"
 
 namespace bs {
@@ -24,57 +27,24 @@ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }   // LDS s
 template <class T>
 T* at(T* p, size_t n) { return p ? p + n : nullptr; }
 
-// One pod pack = the arrays of bs_pods_soa for exactly `p` pods (the part a load uploads in ONE copy, `in_bytes`) followed by
-// the per-pod ids the library derives (request class, (group, class) pair): what travels with a pod when the queue is patched.
-// The pinned staging buffer uses the same layout (input part only) — and its OWN copy of it (bs_pods_map must not disturb the
-// resident queue).
-struct PodLayout {
-  Piece<int32_t> group;
-  Piece<int64_t> req;
-  Piece<uint32_t> pres, cls, pclass, ppair;
-  Piece<uint64_t> owner;
-  Piece<uint8_t> flags;
-  size_t in_bytes = 0, bytes = 0;
-  uint32_t p = 0;
-};
-inline PodLayout pod_layout(uint32_t P, uint32_t L) {
-  const size_t n = std::max<uint32_t>(P, 1);
-  PodLayout l;
-  Carve cv;
-  l.group = cv.take<int32_t>(n);
-  l.req = cv.take<int64_t>(n * L);
-  l.pres = cv.take<uint32_t>(n);
-  l.cls = cv.take<uint32_t>(n);
-  l.owner = cv.take<uint64_t>(n);
-  l.flags = cv.take<uint8_t>(n);
-  l.in_bytes = cv.mark();
-  l.pclass = cv.take<uint32_t>(n);
-  l.ppair = cv.take<uint32_t>(n);
-  l.bytes = cv.mark();
-  l.p = P;
-  return l;
+// The eight columns of a group pack, for GroupsDev and GlPack
+template <class D>
+void group_cols(D& d, const GroupLayout& l, void* pk) {
+  d.min_member = l.mm.in(pk); d.status_scheduled = l.sc.in(pk); d.matched = l.matched.in(pk); d.flags = l.flags.in(pk);
+  d.cls = l.cls.in(pk); d.minres = l.minres.in(pk); d.mrpres = l.mrpres.in(pk); d.occupied = l.occ.in(pk);
 }
-
-// One group pack = the arrays of bs_groups_soa for exactly `g` groups in one allocation (the live pack, the twin bs_groups_list_apply gathers
-// into, and that call's rows in pinned memory): carved in this order wherever a pack is laid out.
-struct GroupLayout {
-  Piece<uint32_t> mm, sc, matched, cls, mrpres;
-  Piece<uint8_t> flags;
-  Piece<int64_t> minres;
-  Piece<uint64_t> occ;
-};
-inline GroupLayout group_carve(Carve& cv, uint32_t G, uint32_t L) {
-  const size_t n = std::max<uint32_t>(G, 1);
-  GroupLayout l;
-  l.mm = cv.take<uint32_t>(n);
-  l.sc = cv.take<uint32_t>(n);
-  l.matched = cv.take<uint32_t>(n);
-  l.flags = cv.take<uint8_t>(n);
-  l.cls = cv.take<uint32_t>(n);
-  l.minres = cv.take<int64_t>(n * L);
-  l.mrpres = cv.take<uint32_t>(n);
-  l.occ = cv.take<uint64_t>(n);
-  return l;
+// ... and beside the caller's arrays of a bs_groups_soa: f(piece, array) column by column, until one returns non-zero
+template <class F>
+int group_soa_cols(const GroupLayout& l, const bs_groups_soa& r, F f) {
+  int rc;
+  if ((rc = f(l.mm, r.min_member)) || (rc = f(l.sc, r.status_scheduled)) || (rc = f(l.matched, r.matched)) || (rc = f(l.flags, r.flags)) ||
+      (rc = f(l.cls, r.cls)) || (rc = f(l.minres, r.min_resources)) || (rc = f(l.mrpres, r.min_resources_present)) || (rc = f(l.occ, r.occupied_by)))
+    return rc;
+  return 0;
+}
+// the rows of `r` into a pack laid out by `l` at `st` (host memory).  l.g > 0 rows: every piece holds exactly l.g of them
+inline void stage_group_rows(const GroupLayout& l, void* st, const bs_groups_soa& r) {
+  if (l.g) group_soa_cols(l, r, [st](auto piece, const auto* rows) { std::memcpy(piece.in(st), rows, piece.bytes()); return 0; });
 }
 
 // Defined in bsched.hip: the kernel groups' names (LAUNCHCHK) and the helpers that the family units call too.  Every entry point starts with
@@ -82,6 +52,7 @@ inline GroupLayout group_carve(Carve& cv, uint32_t G, uint32_t L) {
 extern const char* const kKernelNames[BS_KERNEL_COUNT];
 int use_device(bs_ctx* c, bool flush = true);
 int settle_pending(bs_ctx* c);
+int begin_reload(bs_ctx* c);   // use_device, settle_pending, steady_prev dropped: how bs_nodes_load, bs_fit_load / _build, bs_groups_load and bs_groups_list_apply open
 NodesDev nodes_dev(const bs_ctx* c);
 GroupsDev groups_dev(const bs_ctx* c);
 PodsDev pods_dev(const bs_ctx* c);
@@ -89,7 +60,7 @@ uint32_t* pclass_dev(const bs_ctx* c);
 void launch_nodes_assume(bs_ctx* c, const bs_node_request* records, uint32_t n);
 void mirror_node_requests(bs_ctx* c, const bs_node_request* records, uint32_t n);
 void rederive_nodes(bs_ctx* c, uint32_t base0 = 0, uint32_t m_before = 0);
-int group_layout(bs_ctx* c, uint32_t G);
+int group_layout(bs_ctx* c, uint32_t G, bool headroom);
 int group_counts(bs_ctx* c);
 int analyse_groups(bs_ctx* c, bool rearm_scratch = true, const bs_group_delta* deltas = nullptr, uint32_t ndeltas = 0, bool defer = false);
 int maybe_analyse_epochs(bs_ctx* c);
@@ -136,6 +107,7 @@ struct BoundBlockHooks {
   std::function<int(uint32_t ba_err, int32_t& gmax)> verdict;
 };
 int bound_apply_block(bs_ctx* c, const char* who, BoundApplyDev& a, int32_t gmax, const BoundBlockHooks* hooks = nullptr);
+int32_t* bound_group_column(const bs_ctx* c);   // the live table's group column ([bound_b] entries)
 
 }  // namespace bs
 
@@ -179,11 +151,7 @@ struct bs_ctx {
   // found for the loaded state back to the host without a stream wait (see resolve_groups)
   DevBuf d_gpack, d_info, d_gdelta;
   DevBuf d_gpack2, d_glist;          // bs_groups_list_apply: the allocation the new group pack is gathered into (swapped with d_gpack); its per-call scratch
-  Piece<uint32_t> off_gmm, off_gsc, off_gmatched, off_gcls, off_gmrpres;
-  Piece<uint8_t> off_gflags;
-  Piece<int64_t> off_gminres;
-  Piece<uint64_t> off_gocc;
-  size_t gpack_bytes = 0;
+  GroupLayout glay;                  // the live pack's layout (group_layout)
   int32_t info_tag = 0, kinfo_tag = 0;
   bool info_pending = false, kinfo_pending = false;
   uint32_t max_group_cls = 0, max_pod_cls = 0;   // largest fit class any HAS_POD group / grouped pod names (checked against C per batch)
@@ -208,10 +176,7 @@ struct bs_ctx {
   uint32_t id_room = 0;              // BS_ID_ROOM: ids beyond the queue length (0 = the default: as many again + 1024)
   uint32_t serial_insert_max = 2048; // more inserted pods than this: re-derive in parallel instead of the insert wave
   uint64_t n_applies = 0, n_rederives = 0;
-  Piece<uint8_t> off_pf_code, off_fl_code, off_ready;
-  Piece<uint32_t> off_pf_first_k, off_fl_feasible, off_fl_slot, off_admit;
-  Piece<int32_t> off_pf_leader;
-  size_t outpack_bytes = 0;
+  OutLayout olay;                    // the result pack's layout (layout_out), shared by d_outpack, h_hout and h_rstage
 
   // ---- batch scratch / outputs
   DevBuf d_first_elig, d_first_owner, d_first_reject, d_first_pod, d_cap_epoch;

@@ -184,15 +184,15 @@ BatchDev batch_dev(const bs_ctx* c) {
   b.fd_flag = c->d_fd_flag.as<uint32_t>();
   b.h_fd = c->h_info.p ? c->h_info.p + 14 : nullptr;
   void* ok = c->d_outpack.p;
-  b.pf_code = c->off_pf_code.in(ok);
-  b.pf_first_k = c->off_pf_first_k.in(ok);
-  b.pf_leader = c->off_pf_leader.in(ok);
-  b.fl_code = c->off_fl_code.in(ok);
-  b.fl_feasible = c->off_fl_feasible.in(ok);
-  b.fu_slot = c->off_fl_slot.in(ok);     // per-pod Filter slot travels with the other per-pod results
+  b.pf_code = c->olay.pf_code.in(ok);
+  b.pf_first_k = c->olay.pf_first_k.in(ok);
+  b.pf_leader = c->olay.pf_leader.in(ok);
+  b.fl_code = c->olay.fl_code.in(ok);
+  b.fl_feasible = c->olay.fl_feasible.in(ok);
+  b.fu_slot = c->olay.fl_slot.in(ok);     // per-pod Filter slot travels with the other per-pod results
   b.fl_bitmap = c->d_fl_bitmap.as<uint64_t>();
-  b.admit = c->ext_admit ? c->ext_admit : c->off_admit.in(ok);
-  b.ready = c->off_ready.in(ok);
+  b.admit = c->ext_admit ? c->ext_admit : c->olay.admit.in(ok);
+  b.ready = c->olay.ready.in(ok);
   return b;
 }
 BatchParams batch_params(const bs_ctx* c) {
@@ -531,18 +531,8 @@ int reserve_pod_scratch(bs_ctx* c, uint32_t P) {
 
 // Device layout of everything bs_batch_read returns in its first copy: per-pod arrays | admit[G] | ready[G].
 int layout_out(bs_ctx* c) {
-  const size_t n = std::max<uint32_t>(c->P, 1), g = std::max<uint32_t>(c->G, 1);
-  Carve cv;
-  c->off_pf_code = cv.take<uint8_t>(n);
-  c->off_pf_first_k = cv.take<uint32_t>(n);
-  c->off_pf_leader = cv.take<int32_t>(n);
-  c->off_fl_code = cv.take<uint8_t>(n);
-  c->off_fl_feasible = cv.take<uint32_t>(n);
-  c->off_fl_slot = cv.take<uint32_t>(n);
-  c->off_admit = cv.take<uint32_t>(g);
-  c->off_ready = cv.take<uint8_t>(g);
-  c->outpack_bytes = cv.mark();
-  HIPCHK(c, c->d_outpack.reserve(c->outpack_bytes));
+  c->olay = out_layout(c->P, c->G);
+  HIPCHK(c, c->d_outpack.reserve(c->olay.bytes));
   return BS_OK;
 }
 
@@ -622,15 +612,7 @@ NodesDev nodes_dev(const bs_ctx* c) {
 GroupsDev groups_dev(const bs_ctx* c) {
   GroupsDev g{};
   g.g = c->G;
-  void* pk = c->d_gpack.p;
-  g.min_member = c->off_gmm.in(pk);
-  g.status_scheduled = c->off_gsc.in(pk);
-  g.matched = c->off_gmatched.in(pk);
-  g.flags = c->off_gflags.in(pk);
-  g.cls = c->off_gcls.in(pk);
-  g.minres = c->off_gminres.in(pk);
-  g.mrpres = c->off_gmrpres.in(pk);
-  g.occupied = c->off_gocc.in(pk);
+  group_cols(g, c->glay, c->d_gpack.p);
   return g;
 }
 PodsDev pods_dev(const bs_ctx* c) {
@@ -647,24 +629,15 @@ void rederive_nodes(bs_ctx* c, uint32_t base0, uint32_t m_before) {
                      c->d_lglob.as<int64_t>(), base0, m_before);
 }
 
-// bs_groups_list_apply: the context goes over to G groups — what bs_groups_load does for a new count (the group pack's layout, the per-group
-// scratch, what the resident queue derived for another group count, the result layout), stated for a caller that gathers the pack into the twin
-// allocation itself.  bs_groups_load keeps its own statement of these steps; the pack's layout is the same Carve order (group_carve).
-int group_layout(bs_ctx* c, uint32_t G) {
+// The context goes over to G groups: the group pack's layout, the per-group scratch, what the resident queue derived for another group count,
+// the result layout.  The pack's allocation is the caller's (bs_groups_load uploads into d_gpack, bs_groups_list_apply gathers into the twin).
+// headroom: a buffer that has to grow takes a quarter more than it needs (a list that gains a group per event must not reallocate per event);
+// a load reserves exactly.
+int group_layout(bs_ctx* c, uint32_t G, bool headroom) {
   const size_t n = std::max<uint32_t>(G, 1);
   Carve cv;
-  const GroupLayout l = group_carve(cv, G, c->L);
-  c->off_gmm = l.mm;
-  c->off_gsc = l.sc;
-  c->off_gmatched = l.matched;
-  c->off_gflags = l.flags;
-  c->off_gcls = l.cls;
-  c->off_gminres = l.minres;
-  c->off_gmrpres = l.mrpres;
-  c->off_gocc = l.occ;
-  c->gpack_bytes = cv.mark();
-  // (a list that gains a group per event must not reallocate per event: a quarter of headroom when a buffer has to grow)
-  auto grow = [](DevBuf& d, size_t bytes) -> hipError_t { return d.cap >= bytes ? hipSuccess : d.reserve(bytes + bytes / 4); };
+  c->glay = group_carve(cv, G, c->L);
+  auto grow = [headroom](DevBuf& d, size_t bytes) -> hipError_t { return d.reserve(headroom && d.cap < bytes ? bytes + bytes / 4 : bytes); };
   HIPCHK(c, grow(c->d_first_elig, n * 4));
   HIPCHK(c, grow(c->d_first_owner, n * 4));
   HIPCHK(c, grow(c->d_first_reject, n * 4));
@@ -678,7 +651,19 @@ int group_layout(bs_ctx* c, uint32_t G) {
   return layout_out(c);
 }
 
-// h_gflags, the capture / MinResources-default counts and the largest fit class a captured group names, recounted from the device columns
+// the capture / MinResources-default counts and the largest fit class a captured group names, over the flags and classes of G groups
+static void count_groups(bs_ctx* c, const uint8_t* flags, const uint32_t* cls, uint32_t G) {
+  c->n_uncaptured = 0;
+  c->n_nominres = 0;
+  c->max_group_cls = 0;
+  for (uint32_t i = 0; i < G; ++i) {
+    if (!(flags[i] & BS_GROUP_HAS_POD)) c->n_uncaptured++;
+    else c->max_group_cls = std::max(c->max_group_cls, cls[i]);
+    if (!(flags[i] & BS_GROUP_HAS_MINRES)) c->n_nominres++;
+  }
+}
+
+// h_gflags and those counts, recounted from the device columns
 int group_counts(bs_ctx* c) {
   const uint32_t G = c->G;
   const GroupsDev gr = groups_dev(c);
@@ -689,14 +674,7 @@ int group_counts(bs_ctx* c) {
     HIPCHK(c, hipMemcpyAsync(cls.data(), gr.cls, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
-  c->n_uncaptured = 0;
-  c->n_nominres = 0;
-  c->max_group_cls = 0;
-  for (uint32_t i = 0; i < G; ++i) {
-    if (!(c->h_gflags[i] & BS_GROUP_HAS_POD)) c->n_uncaptured++;
-    else c->max_group_cls = std::max(c->max_group_cls, cls[i]);
-    if (!(c->h_gflags[i] & BS_GROUP_HAS_MINRES)) c->n_nominres++;
-  }
+  count_groups(c, c->h_gflags.data(), cls.data(), G);
   return BS_OK;
 }
 
@@ -766,6 +744,16 @@ void mirror_node_requests(bs_ctx* c, const bs_node_request* records, uint32_t n)
 // have to run again.  Every call that changes what a batch reads (nodes, fit, groups) or that runs over the state itself (bs_seq_run)
 // settles it FIRST, against the state it was launched on; its results stay readable afterwards.
 int settle_pending(bs_ctx* c) { return (c->fd_active || c->spec_active) ? fd_settle(c) : BS_OK; }
+// How every call opens that reloads nodes, fit classes or groups: the device (a deferred group patch goes out first), the settle, and no
+// guess carried over: a guess must name a table of the state that is being loaded, not of the one before (behind the settle, whose
+// resolve_groups writes the field).
+int begin_reload(bs_ctx* c) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if ((rc = settle_pending(c))) return rc;
+  c->steady_prev = -1;
+  return BS_OK;
+}
 
 // a final block of a fused launch gave up waiting for its producers: the batch's results are not to be trusted
 int check_handover(bs_ctx* c) {
@@ -912,10 +900,8 @@ int bs_destroy(bs_ctx* c) {
 int bs_nodes_load(bs_ctx* c, const bs_nodes_soa* nodes) {
   if (c) c->seq_wait_valid = false;                 // node indices are renumbered
   if (!c || !nodes) return BS_ERR_INVALID;
-  int rc = use_device(c);
+  int rc = begin_reload(c);
   if (rc) return rc;
-  if ((rc = settle_pending(c))) return rc;
-  c->steady_prev = -1;                              // (a guess must name a table of the state that is being loaded, not of the one before; behind the settle, whose resolve_groups writes the field)
   const uint32_t N = nodes->n, L = c->L;
   if (N && (!nodes->allocatable || !nodes->requested || !nodes->allocatable_present || !nodes->requested_present || !nodes->flags))
     return BS_ERR_INVALID;
@@ -939,10 +925,8 @@ int bs_nodes_count(const bs_ctx* c, uint32_t* n_out) {
 int bs_fit_load(bs_ctx* c, uint32_t n_classes, const uint32_t* fit_bits) {
   if (!c || n_classes == 0 || !fit_bits) return BS_ERR_INVALID;
   if (!c->have_nodes) { c->last_error = "bs_fit_load before bs_nodes_load"; return BS_ERR_STATE; }
-  int rc = use_device(c);
+  int rc = begin_reload(c);
   if (rc) return rc;
-  if ((rc = settle_pending(c))) return rc;
-  c->steady_prev = -1;                              // (a guess must name a table of the state that is being loaded, not of the one before; behind the settle, whose resolve_groups writes the field)
   c->C = n_classes;
   c->fit_words = cdiv(c->N, 32);
   c->h_fit.assign(fit_bits, fit_bits + (size_t)n_classes * c->fit_words);
@@ -955,10 +939,8 @@ int bs_fit_build(bs_ctx* c, const bs_node_labels* nl, const bs_fit_templates* tp
   if (!c || !nl || !tp || tp->c == 0) return BS_ERR_INVALID;
   if (!c->have_nodes) { c->last_error = "bs_fit_build before bs_nodes_load"; return BS_ERR_STATE; }
   if (nl->n != c->N) { c->last_error = "bs_fit_build: label table size differs from the snapshot"; return BS_ERR_INVALID; }
-  int rc = use_device(c);
+  int rc = begin_reload(c);
   if (rc) return rc;
-  if ((rc = settle_pending(c))) return rc;
-  c->steady_prev = -1;                              // (a guess must name a table of the state that is being loaded, not of the one before; behind the settle, whose resolve_groups writes the field)
   const uint32_t N = c->N, C = tp->c;
   const uint32_t nlab = N ? nl->label_off[N] : 0, ntaint = N ? nl->taint_off[N] : 0;
   const uint32_t nsel = tp->sel_off[C], nterm = tp->term_off[C], ntol = tp->tol_off[C];
@@ -1079,60 +1061,23 @@ int bs_fit_read(bs_ctx* c, uint32_t* out) {
 int bs_groups_load(bs_ctx* c, const bs_groups_soa* g) {
   if (!c || !g) return BS_ERR_INVALID;
   c->seq_wait_valid = false;                        // group indices are renumbered
-  int rc = use_device(c);
+  int rc = begin_reload(c);
   if (rc) return rc;
-  if ((rc = settle_pending(c))) return rc;
-  c->steady_prev = -1;                              // (a guess must name a table of the state that is being loaded, not of the one before; behind the settle, whose resolve_groups writes the field)
   c->first_reach_hint = 0xFFFFFFFFu;                // (which pod reaches findMaxPG first depends on the groups' deny entries and OccupiedBy)
-  const uint32_t G = g->g, L = c->L;
+  const uint32_t G = g->g;
   if (G && (!g->min_member || !g->status_scheduled || !g->matched || !g->flags || !g->cls || !g->min_resources || !g->min_resources_present ||
             !g->occupied_by))
     return BS_ERR_INVALID;
-  const size_t n = std::max<uint32_t>(G, 1);
+  if ((rc = group_layout(c, G, false))) return rc;
   // group arrays: one allocation, one pinned-staged transfer, no wait
-  Carve cv;
-  c->off_gmm = cv.take<uint32_t>(n);
-  c->off_gsc = cv.take<uint32_t>(n);
-  c->off_gmatched = cv.take<uint32_t>(n);
-  c->off_gflags = cv.take<uint8_t>(n);
-  c->off_gcls = cv.take<uint32_t>(n);
-  c->off_gminres = cv.take<int64_t>(n * L);
-  c->off_gmrpres = cv.take<uint32_t>(n);
-  c->off_gocc = cv.take<uint64_t>(n);
-  c->gpack_bytes = cv.mark();
-  HIPCHK(c, c->d_gpack.reserve(c->gpack_bytes));
-  HIPCHK(c, c->d_first_elig.reserve(n * 4));
-  HIPCHK(c, c->d_first_owner.reserve(n * 4));
-  HIPCHK(c, c->d_first_reject.reserve(n * 4));
-  HIPCHK(c, c->d_first_pod.reserve(n * 4));
-  HIPCHK(c, c->d_cap_epoch.reserve(n * 4));
-  HIPCHK(c, c->d_leader_epoch.reserve((n + 1) * 4));
-  HIPCHK(c, c->d_panic_epoch.reserve(n + 1));
-  if (G != c->G) { c->pairs_ready = false; c->dirs_ready = false; }   // the per-group arrays of the pod load are sized by G
-  if (G != c->G) c->ranges_valid = false;         // (the pod ranges' local flags are per group: 256 pods per block until the next bs_pods_load)
-  c->G = G;
-  if ((rc = layout_out(c))) return rc;
-  c->n_uncaptured = 0;
-  c->n_nominres = 0;
-  c->max_group_cls = 0;
+  HIPCHK(c, c->d_gpack.reserve(c->glay.bytes));
+  count_groups(c, g->flags, g->cls, G);
   if (G) {
-    HIPCHK(c, c->h_gstage.reserve(c->gpack_bytes));
+    HIPCHK(c, c->h_gstage.reserve(c->glay.bytes));
     uint8_t* st = c->h_gstage.p;
-    std::memcpy(c->off_gmm.in(st), g->min_member, c->off_gmm.bytes());      // G > 0: the pieces hold exactly G groups
-    std::memcpy(c->off_gsc.in(st), g->status_scheduled, c->off_gsc.bytes());
-    std::memcpy(c->off_gmatched.in(st), g->matched, c->off_gmatched.bytes());
-    std::memcpy(c->off_gflags.in(st), g->flags, c->off_gflags.bytes());
-    std::memcpy(c->off_gcls.in(st), g->cls, c->off_gcls.bytes());
-    std::memcpy(c->off_gminres.in(st), g->min_resources, c->off_gminres.bytes());
-    std::memcpy(c->off_gmrpres.in(st), g->min_resources_present, c->off_gmrpres.bytes());
-    std::memcpy(c->off_gocc.in(st), g->occupied_by, c->off_gocc.bytes());
-    HIPCHK(c, hipMemcpyAsync(c->d_gpack.p, st, c->gpack_bytes, hipMemcpyHostToDevice, c->stream));
+    stage_group_rows(c->glay, st, *g);
+    HIPCHK(c, hipMemcpyAsync(c->d_gpack.p, st, c->glay.bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, c->h_gstage.mark_busy(c->stream));
-    for (uint32_t i = 0; i < G; ++i) {
-      if (!(g->flags[i] & BS_GROUP_HAS_POD)) c->n_uncaptured++;
-      else c->max_group_cls = std::max(c->max_group_cls, g->cls[i]);
-      if (!(g->flags[i] & BS_GROUP_HAS_MINRES)) c->n_nominres++;
-    }
     c->h_gflags.assign(g->flags, g->flags + G);
   } else {
     c->h_gflags.clear();
@@ -1176,7 +1121,7 @@ int bs_groups_apply(bs_ctx* c, const bs_group_delta* deltas, uint32_t count) {
     return maybe_analyse_epochs(c);                  // (positional state: flushes the patch, the analysis reads the patched groups)
   }
   const size_t bytes = (size_t)count * sizeof(bs_group_delta);
-  HIPCHK(c, c->h_gstage.reserve(std::max(bytes, c->gpack_bytes)));
+  HIPCHK(c, c->h_gstage.reserve(std::max(bytes, c->glay.bytes)));
   HIPCHK(c, c->d_gdelta.reserve(bytes));
   std::memcpy(c->h_gstage.p, deltas, bytes);
   HIPCHK(c, hipMemcpyAsync(c->d_gdelta.p, c->h_gstage.p, bytes, hipMemcpyHostToDevice, c->stream));
@@ -1199,14 +1144,10 @@ int bs_groups_read(bs_ctx* c, bs_groups_soa* g) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (G) {
     const void* pk = c->d_gpack.p;                    // G > 0: the pieces hold exactly G groups
-    HIPCHK(c, hipMemcpy(g->min_member, c->off_gmm.in(pk), c->off_gmm.bytes(), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(g->status_scheduled, c->off_gsc.in(pk), c->off_gsc.bytes(), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(g->matched, c->off_gmatched.in(pk), c->off_gmatched.bytes(), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(g->flags, c->off_gflags.in(pk), c->off_gflags.bytes(), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(g->cls, c->off_gcls.in(pk), c->off_gcls.bytes(), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(g->min_resources, c->off_gminres.in(pk), c->off_gminres.bytes(), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(g->min_resources_present, c->off_gmrpres.in(pk), c->off_gmrpres.bytes(), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(g->occupied_by, c->off_gocc.in(pk), c->off_gocc.bytes(), hipMemcpyDeviceToHost));
+    return group_soa_cols(c->glay, *g, [&](auto piece, auto* rows) -> int {
+      HIPCHK(c, hipMemcpy(rows, piece.in(pk), piece.bytes(), hipMemcpyDeviceToHost));
+      return BS_OK;
+    });
   }
   return BS_OK;
 }
@@ -1697,7 +1638,7 @@ static int reserve_slots(bs_ctx* c, bool run_filter) {
 // Layout = the device result pack (layout_out) | feas[hstride] | completion word; rows [W + 1][hstride] beside it.
 static int ensure_hout(bs_ctx* c) {
   const uint32_t hs = std::min<uint32_t>(c->filter_slots_cap, 1024u);
-  const size_t off_feas = align256(c->outpack_bytes), off_tag = off_feas + align256((size_t)hs * 4), need = off_tag + 256;
+  const size_t off_feas = align256(c->olay.bytes), off_tag = off_feas + align256((size_t)hs * 4), need = off_tag + 256;
   const size_t need_rows = (size_t)(cdiv(c->N, 64) + 1) * hs * 8;
   if (need > c->h_hout.cap) {
     HIPCHK(c, c->h_hout.reserve(need));
@@ -1721,14 +1662,14 @@ static int setup_host_out(bs_ctx* c, uint32_t stages, bool run_filter, BatchDev&
   c->host_tag = c->host_tag == 0x7FFFFFFF ? 1 : c->host_tag + 1;
   prm.host_tag = c->host_tag;
   uint8_t* h = c->h_hout.p;
-  b.h_pf_code = c->off_pf_code.in(h);
-  b.h_pf_first_k = c->off_pf_first_k.in(h);
-  b.h_pf_leader = c->off_pf_leader.in(h);
-  b.h_fl_code = c->off_fl_code.in(h);
-  b.h_fl_feasible = c->off_fl_feasible.in(h);
-  b.h_fl_slot = c->off_fl_slot.in(h);
-  b.h_admit = c->off_admit.in(h);
-  b.h_ready = c->off_ready.in(h);
+  b.h_pf_code = c->olay.pf_code.in(h);
+  b.h_pf_first_k = c->olay.pf_first_k.in(h);
+  b.h_pf_leader = c->olay.pf_leader.in(h);
+  b.h_fl_code = c->olay.fl_code.in(h);
+  b.h_fl_feasible = c->olay.fl_feasible.in(h);
+  b.h_fl_slot = c->olay.fl_slot.in(h);
+  b.h_admit = c->olay.admit.in(h);
+  b.h_ready = c->olay.ready.in(h);
   b.h_feas = reinterpret_cast<uint32_t*>(h + c->off_hfeas);
   b.h_tag = reinterpret_cast<int32_t*>(h + c->off_htag);
   b.h_rows = run_filter ? c->h_hrows.p : nullptr;
@@ -2567,16 +2508,16 @@ int bs_batch_read(bs_ctx* c, const bs_batch_out* out) {
   // the caller's arrays out of a host copy of the result pack (the pinned pack of latency mode, or the staged D2H); the admit counters may sit elsewhere
   auto copy_out = [&](const uint8_t* st, const void* admit) {
     if (want_pod) {
-      if (out->pf_code) std::memcpy(out->pf_code, c->off_pf_code.in(st), P);
-      if (out->pf_first_k) std::memcpy(out->pf_first_k, c->off_pf_first_k.in(st), (size_t)P * 4);
-      if (out->pf_leader) std::memcpy(out->pf_leader, c->off_pf_leader.in(st), (size_t)P * 4);
-      if (out->fl_code) std::memcpy(out->fl_code, c->off_fl_code.in(st), P);
-      if (out->fl_feasible) std::memcpy(out->fl_feasible, c->off_fl_feasible.in(st), (size_t)P * 4);
-      if (out->fl_slot) std::memcpy(out->fl_slot, c->off_fl_slot.in(st), (size_t)P * 4);
+      if (out->pf_code) std::memcpy(out->pf_code, c->olay.pf_code.in(st), P);
+      if (out->pf_first_k) std::memcpy(out->pf_first_k, c->olay.pf_first_k.in(st), (size_t)P * 4);
+      if (out->pf_leader) std::memcpy(out->pf_leader, c->olay.pf_leader.in(st), (size_t)P * 4);
+      if (out->fl_code) std::memcpy(out->fl_code, c->olay.fl_code.in(st), P);
+      if (out->fl_feasible) std::memcpy(out->fl_feasible, c->olay.fl_feasible.in(st), (size_t)P * 4);
+      if (out->fl_slot) std::memcpy(out->fl_slot, c->olay.fl_slot.in(st), (size_t)P * 4);
     }
     if (want_grp) {
       if (out->group_admit) std::memcpy(out->group_admit, admit, (size_t)G * 4);
-      if (out->group_ready) std::memcpy(out->group_ready, c->off_ready.in(st), G);
+      if (out->group_ready) std::memcpy(out->group_ready, c->olay.ready.in(st), G);
     }
   };
   // Filter rows: the slots of the last batch, word-major, compacted to the rows in use
@@ -2606,7 +2547,7 @@ int bs_batch_read(bs_ctx* c, const bs_batch_out* out) {
     if ((rc = check_handover(c))) return rc;
     c->h_dstage.busy = false;                            // (the batch ran behind every earlier apply)
     const uint8_t* st = c->h_hout.p;
-    copy_out(st, c->off_admit.in(st));
+    copy_out(st, c->olay.admit.in(st));
     if ((want_rows || want_rfeas) && nrows <= c->hstride) {
       if (want_rfeas) std::memcpy(out->fl_rows_feasible, st + c->off_hfeas, (size_t)nrows * 4);
       if (want_rows)
@@ -2619,8 +2560,8 @@ int bs_batch_read(bs_ctx* c, const bs_batch_out* out) {
   // ONE wait and at most two copies: the result pack (per-pod arrays | admit | ready, contiguous on the device) and the
   // Filter rows with their feasible counts (a strided window of the slot bitmap; the counts sit behind its last row)
   const bool ext = c->ext_admit != nullptr;
-  const size_t pack_bytes = want_grp ? c->outpack_bytes : c->off_admit.off;
-  const size_t off_xadmit = align256(c->outpack_bytes);
+  const size_t pack_bytes = want_grp ? c->olay.bytes : c->olay.admit.off;
+  const size_t off_xadmit = align256(c->olay.bytes);
   const size_t off_rows = off_xadmit + align256((size_t)G * 4);
   const bool any_rows = want_rows || want_rfeas;
   const size_t rows_h = any_rows ? (size_t)W + 1 : 0, rows_bytes = rows_h * nrows * 8;
@@ -2635,7 +2576,7 @@ int bs_batch_read(bs_ctx* c, const bs_batch_out* out) {
   c->h_stage.busy = false;                             // (the stream is idle: the pod upload has left its buffer too)
   c->h_dstage.busy = false;
   if ((rc = check_handover(c))) return rc;
-  copy_out(st, ext ? (const void*)(st + off_xadmit) : c->off_admit.in(st));
+  copy_out(st, ext ? (const void*)(st + off_xadmit) : c->olay.admit.in(st));
   if (want_rfeas) std::memcpy(out->fl_rows_feasible, st + off_rows + (size_t)W * nrows * 8, (size_t)nrows * 4);
   if (want_rows)
     for (uint32_t w = 0; w < W; ++w) std::memcpy(out->fl_rows + (size_t)w * out->fl_rows_cap, st + off_rows + (size_t)w * nrows * 8, (size_t)nrows * 8);
@@ -2667,15 +2608,15 @@ int bs_batch_map(bs_ctx* c, bs_batch_view* v) {
   const uint8_t* st = c->h_hout.p;
   std::memset(v, 0, sizeof(*v));
   v->p = P; v->g = G; v->words = W;
-  v->pf_code = c->off_pf_code.in(st);
-  v->pf_first_k = c->off_pf_first_k.in(st);
-  v->pf_leader = c->off_pf_leader.in(st);
-  v->fl_code = c->off_fl_code.in(st);
-  v->fl_feasible = c->off_fl_feasible.in(st);
-  v->fl_slot = c->off_fl_slot.in(st);
+  v->pf_code = c->olay.pf_code.in(st);
+  v->pf_first_k = c->olay.pf_first_k.in(st);
+  v->pf_leader = c->olay.pf_leader.in(st);
+  v->fl_code = c->olay.fl_code.in(st);
+  v->fl_feasible = c->olay.fl_feasible.in(st);
+  v->fl_slot = c->olay.fl_slot.in(st);
   if (c->last_stages & BS_STAGE_TALLY) {
-    v->group_admit = c->off_admit.in(st);
-    v->group_ready = c->off_ready.in(st);
+    v->group_admit = c->olay.admit.in(st);
+    v->group_ready = c->olay.ready.in(st);
   }
   v->fl_rows_n = nrows;
   v->fl_rows_stride = c->hstride;

@@ -13,15 +13,12 @@
 
 namespace bs {
 
-// the columns of a pack laid out by group_carve (bs_ctx.hpp) for `g` groups at `base`
+// the columns of a pack laid out by group_carve (bs_layouts.hpp) for `g` groups at `base`
 static GlPack gl_pack(const GroupLayout& l, void* base, uint32_t g) {
-  return GlPack{l.mm.in(base), l.sc.in(base), l.matched.in(base), l.flags.in(base), l.cls.in(base), l.minres.in(base), l.mrpres.in(base), l.occ.in(base),
-                std::max<uint32_t>(g, 1)};
-}
-// the context's live pack under its current layout
-static GlPack gl_live(const bs_ctx* c, void* base) {
-  return GlPack{c->off_gmm.in(base), c->off_gsc.in(base), c->off_gmatched.in(base), c->off_gflags.in(base), c->off_gcls.in(base), c->off_gminres.in(base),
-                c->off_gmrpres.in(base), c->off_gocc.in(base), std::max<uint32_t>(c->G, 1)};
+  GlPack k{};
+  group_cols(k, l, base);
+  k.stride = std::max<uint32_t>(g, 1);
+  return k;
 }
 
 // the one pass over the group pack: the map, and every row of the new pack
@@ -60,11 +57,9 @@ int bs_groups_list_apply(bs_ctx* c, const bs_groups_list_delta* d, bs_groups_lis
     return BS_OK;
   }
   // ---- everything is valid: from here on the resident state changes
-  int rc = use_device(c);                                   // (a deferred bs_groups_apply patch goes out first, onto the old pack)
+  int rc = begin_reload(c);                                 // (a deferred bs_groups_apply patch goes out first, onto the old pack)
   if (rc) return rc;
-  if ((rc = settle_pending(c))) return rc;
   c->seq_wait_valid = false;                                // group indices are renumbered
-  c->steady_prev = -1;
   c->first_reach_hint = 0xFFFFFFFFu;
   // ---- the wait table's rows of removed groups leave by the removal core's release form, while the context still holds the old count
   const bool wait_follows = c->have_wait && c->wait_g == g_old;
@@ -80,16 +75,7 @@ int bs_groups_list_apply(bs_ctx* c, const bs_groups_list_delta* d, bs_groups_lis
   const auto o_upd = bv.take<uint32_t>(U);
   HIPCHK(c, c->h_glstage.reserve(std::max<size_t>(bv.mark(), 256), std::max<size_t>(bv.mark() + bv.mark() / 4, 4096)));
   uint8_t* st = c->h_glstage.p;
-  if (n_rows) {
-    std::memcpy(rl.mm.in(st), r.min_member, (size_t)n_rows * 4);
-    std::memcpy(rl.sc.in(st), r.status_scheduled, (size_t)n_rows * 4);
-    std::memcpy(rl.matched.in(st), r.matched, (size_t)n_rows * 4);
-    std::memcpy(rl.flags.in(st), r.flags, (size_t)n_rows);
-    std::memcpy(rl.cls.in(st), r.cls, (size_t)n_rows * 4);
-    std::memcpy(rl.minres.in(st), r.min_resources, (size_t)n_rows * L * 8);
-    std::memcpy(rl.mrpres.in(st), r.min_resources_present, (size_t)n_rows * 4);
-    std::memcpy(rl.occ.in(st), r.occupied_by, (size_t)n_rows * 8);
-  }
+  stage_group_rows(rl, st, r);
   if (R) std::memcpy(o_rem.in(st), d->remove, o_rem.bytes());
   if (U) std::memcpy(o_upd.in(st), d->update, o_upd.bytes());
   // ---- scratch: the map and the three count words
@@ -102,11 +88,11 @@ int bs_groups_list_apply(bs_ctx* c, const bs_groups_list_delta* d, bs_groups_lis
   HIPCHK(c, hipMemsetAsync(cnt, 0, o_cnt.bytes(), c->stream));
   // ---- the new pack: the old one under the old layout, the twin under the new one (a quarter of headroom, as the bound and wait tables have)
   GlDev a{};
-  a.src = gl_live(c, c->d_gpack.p);
+  a.src = gl_pack(c->glay, c->d_gpack.p, c->G);
   a.g_old = g_old;
-  if ((rc = group_layout(c, g_new))) return rc;             // the context's layout, count and per-group scratch are now those of g_new
-  if (c->gpack_bytes > c->d_gpack2.cap) HIPCHK(c, c->d_gpack2.reserve(c->gpack_bytes + c->gpack_bytes / 4));
-  a.dst = gl_live(c, c->d_gpack2.p);
+  if ((rc = group_layout(c, g_new, true))) return rc;       // the context's layout, count and per-group scratch are now those of g_new
+  if (c->glay.bytes > c->d_gpack2.cap) HIPCHK(c, c->d_gpack2.reserve(c->glay.bytes + c->glay.bytes / 4));
+  a.dst = gl_pack(c->glay, c->d_gpack2.p, c->G);
   a.rows = gl_pack(rl, st, n_rows);
   a.g_new = g_new;
   a.rem = o_rem.in(st);
@@ -126,8 +112,7 @@ int bs_groups_list_apply(bs_ctx* c, const bs_groups_list_delta* d, bs_groups_lis
     c->dirs_ready = false;                                  // from the resident queue by the paths a changed group count already takes
     c->ranges_valid = false;
     if (c->have_pods && c->P) launch_gl_remap(c->stream, c->lay[c->cur_pack].group.in(c->d_pack[c->cur_pack].p), c->P, map, g_old, cnt + 0);
-    if (c->have_bound && c->bound_b)
-      launch_gl_remap(c->stream, reinterpret_cast<int32_t*>(c->d_bound.as<uint8_t>() + c->blay.group), c->bound_b, map, g_old, cnt + 1);
+    if (c->have_bound && c->bound_b) launch_gl_remap(c->stream, bound_group_column(c), c->bound_b, map, g_old, cnt + 1);
     if (wait_follows && c->wait_w) launch_gl_remap(c->stream, wait_group_column(c), c->wait_w, map, g_old, cnt + 2);
     LAUNCHCHK(c, BS_KERNEL_PREPASS);
     if (c->have_bound) c->bound_max_group = groups_list_max_group(c->bound_max_group, g_old, R, d->remove);

@@ -130,6 +130,8 @@ BoundCols<U8> bound_dev(D& d, U8* base, const BoundLayout& l) {
 
 }  // namespace
 
+int32_t* bs::bound_group_column(const bs_ctx* c) { return bound_cols(c->d_bound.as<uint8_t>(), c->blay).group; }
+
 // the back half of every patch of the bound table (bs_ctx.hpp): the second allocation, the merge chain over a delta block that is on the
 // device, the one wait, the error word, the swap
 int bs::bound_apply_block(bs_ctx* c, const char* who, BoundApplyDev& a, int32_t gmax, const BoundBlockHooks* hooks) {
