@@ -29,7 +29,7 @@ UNITS = {
     "tu_seq.hip": _SEQ,
     "tu_seq_expire.hip": _SEQ + ["bs_seq_expire.hpp", "bs_seq_expire_list.hpp"],
     "tu_preempt.hip": _CTX + ["bs_preempt.hpp", "bs_preempt_commit.hpp", "bs_preempt_commit_gang.hpp", "bs_preempt_gang_runs.hpp", "bs_preempt_geom.hpp", "bs_bound_apply.hpp",
-                              "bs_bound_nodes.hpp", "bs_bound_nodes_replay.hpp", "bs_pdb.hpp"],
+                              "bs_bound_nodes.hpp", "bs_bound_nodes_replay.hpp", "bs_pdb.hpp", "bs_nominated.hpp", "bs_nominated_check.hpp"],
 }
 SOURCES = list(UNITS)
 # the units that came after those five, kept in a table of their own: tests/test_build_units_cpu.py holds UNITS and SOURCES to exactly the five

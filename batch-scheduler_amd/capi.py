@@ -45,10 +45,13 @@ ABI_SYMBOLS = [
     "bs_wait_nodes_apply",
     "bs_groups_list_apply", "bs_groups_list_apply_flat",
     "bs_bound_bind",
+    "bs_nominated_load", "bs_nominated_count", "bs_nominated_ids", "bs_nominated_read", "bs_nominated_apply", "bs_preempt_nominated_read",
 ]
 
 SEQ_EXPIRE_DENY, SEQ_EXPIRE_ALL = 1, 2    # bs_seq_expire flags
 WAIT_MAX = 1 << 24                        # BS_WAIT_MAX: rows and ids of the wait table
+NOM_MAX = 1 << 16                         # BS_NOM_MAX: live rows of the nominated-pod table (its id space goes up to 2^24)
+NOM_NONE = 0xFFFFFFFF                     # bs_preempt_nominated_read: the preemptor got no row
 
 BS_BOUND_NODES = soa.BS_BOUND_NODES     # bs_bound_apply_ex: the delta also moves the node requests
 
@@ -261,6 +264,12 @@ def load_library(path: str | None = None):
     L.bs_groups_list_apply.argtypes = [vp, P(GroupsListDelta), P(GroupsListOut)]
     L.bs_groups_list_apply_flat.argtypes = [vp, u32, P(u32), u32, P(u32), u32, P(u32), P(u32), P(u32), P(u8), P(u32), P(C.c_int64), P(u32), P(C.c_uint64),
                                             u32, u32, P(u32), P(u32), P(i32), P(u32)]
+    L.bs_nominated_load.argtypes = [vp, u32, P(u32), P(i32), P(C.c_int64), P(u32)]
+    L.bs_nominated_count.argtypes = [vp, P(u32)]
+    L.bs_nominated_ids.argtypes = [vp, P(u32)]
+    L.bs_nominated_read.argtypes = [vp, P(u32), P(u32), P(i32), P(C.c_int64), P(u32)]
+    L.bs_nominated_apply.argtypes = [vp, u32, P(u32), u32, P(u32), P(u32), P(i32), P(u32)]
+    L.bs_preempt_nominated_read.argtypes = [vp, u32, P(u32)]
     L.bs_bound_bind.argtypes = [vp, u32, P(u32), u32, P(u32), P(i32), P(C.c_int64), P(u8), P(u32), P(u32)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
@@ -762,6 +771,62 @@ class Context:
         k = min(int(n.value), cap)
         return i_[:k].copy(), nd[:k].copy(), gr[:k].copy(), int(n.value)
 
+    # -- the resident nominated-pod table
+    def nominated_load(self, node=(), priority=(), req=None, req_present=None, m: int | None = None):
+        """bs_nominated_load: a fresh table of nominees (node [m], priority [m], req [L][m], req_present [m]); no arguments: the empty table.
+        m overrides the row count handed to the library (tests of the capacity check)."""
+        nd = np.ascontiguousarray(np.asarray(node, np.uint32).reshape(-1))
+        n = int(nd.size)
+        pr = np.ascontiguousarray(np.asarray(priority, np.int32).reshape(-1))
+        rq = np.zeros((self.L, n), np.int64) if req is None else np.ascontiguousarray(np.asarray(req, np.int64).reshape(self.L, n))
+        ps = np.zeros(n, np.uint32) if req_present is None else np.ascontiguousarray(np.asarray(req_present, np.uint32).reshape(-1))
+        assert pr.size == n and ps.size == n
+        pad = lambda a: a if a.size else np.zeros(1, a.dtype)
+        self._chk(self._lib.bs_nominated_load(self._h, n if m is None else int(m), _u32p(pad(nd)), pad(pr).ctypes.data_as(C.POINTER(C.c_int32)),
+                                              _i64p(pad(rq)), _u32p(pad(ps))), "bs_nominated_load")
+
+    def nominated_count(self) -> int:
+        m = C.c_uint32(0)
+        self._chk(self._lib.bs_nominated_count(self._h, C.byref(m)), "bs_nominated_count")
+        return int(m.value)
+
+    def nominated_ids(self) -> int:
+        """bs_nominated_ids: the id space — rows at the last nominated_load plus what was inserted since"""
+        m = C.c_uint32(0)
+        self._chk(self._lib.bs_nominated_ids(self._h, C.byref(m)), "bs_nominated_ids")
+        return int(m.value)
+
+    def nominated_read(self) -> dict:
+        """bs_nominated_read: the table's columns in table order (ascending id): id, node, priority, req [L][count], req_present"""
+        w = self.nominated_count()
+        m = max(w, 1)
+        i_, nd, pr, ps = np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros(m, np.int32), np.zeros(m, np.uint32)
+        rq = np.zeros((self.L, m), np.int64)
+        self._chk(self._lib.bs_nominated_read(self._h, _u32p(i_), _u32p(nd), pr.ctypes.data_as(C.POINTER(C.c_int32)), _i64p(rq), _u32p(ps)), "bs_nominated_read")
+        return dict(id=i_[:w], node=nd[:w], priority=pr[:w], req=rq[:, :w], req_present=ps[:w])
+
+    def nominated_apply(self, remove=(), pod_index=(), node=(), priority=(), n_remove: int | None = None, n_insert: int | None = None) -> int:
+        """bs_nominated_apply: the listed ids leave the table; then one row per (pod_index[k], node[k], priority[k]) is appended, its request
+        gathered on the device from the resident queue.  Returns the first new id.  n_remove / n_insert override the counts handed to the
+        library (tests of the refusals); an empty list is passed as NULL."""
+        rm = np.ascontiguousarray(np.asarray(remove, np.uint32).reshape(-1))
+        pi = np.ascontiguousarray(np.asarray(pod_index, np.uint32).reshape(-1))
+        nd = np.ascontiguousarray(np.asarray(node, np.uint32).reshape(-1))
+        pr = np.ascontiguousarray(np.asarray(priority, np.int32).reshape(-1))
+        assert pi.size == nd.size == pr.size
+        first = C.c_uint32(0)
+        self._chk(self._lib.bs_nominated_apply(self._h, int(rm.size) if n_remove is None else int(n_remove), _u32p(rm) if rm.size else None,
+                                               int(pi.size) if n_insert is None else int(n_insert), _u32p(pi) if pi.size else None,
+                                               _u32p(nd) if nd.size else None, pr.ctypes.data_as(C.POINTER(C.c_int32)) if pr.size else None,
+                                               C.byref(first)), "bs_nominated_apply")
+        return int(first.value)
+
+    def preempt_nominated_read(self, count: int) -> np.ndarray:
+        """bs_preempt_nominated_read: the row id per preemptor of the last preemption call with nominate=True, NOM_NONE where none"""
+        out = np.zeros(max(int(count), 1), np.uint32)
+        self._chk(self._lib.bs_preempt_nominated_read(self._h, int(count), _u32p(out)), "bs_preempt_nominated_read")
+        return out[: int(count)]
+
     def read_node_requests(self):
         """bs_nodes_read: (requested [L][n], requested_present [n]) as the context holds them"""
         req = np.zeros((self.L, max(self.n, 1)), np.int64) if self.n == 0 else np.zeros((self.L, self.n), np.int64)
@@ -802,26 +867,32 @@ class Context:
         return self._preempt_call(None, pod_index, priority, group_protected, victim_cap, stages)
 
     def preempt_commit(self, pod_index, priority, group_protected=None, victim_cap: int = 16, apply: bool = False, assume: bool = False,
-                       stages: int = soa.STAGE_PREFILTER) -> dict:
+                       stages: int = soa.STAGE_PREFILTER, nominate: bool = False) -> dict:
         """bs_preempt_commit: the preemptors answered in sequence (priority descending, stable), each seeing the earlier slots' victims
         gone and their preemptors nominated; apply=True writes the evictions into the bound table and the node requests, assume=True
-        (with apply) also adds each nominee's request to its node.  Returns the dict `preempt` returns."""
-        flags = (soa.PREEMPT_APPLY if apply else 0) | (soa.PREEMPT_ASSUME if assume else 0)
-        return self._preempt_call(flags, pod_index, priority, group_protected, victim_cap, stages)
+        (with apply) also adds each nominee's request to its node; nominate=True (with apply, without assume) appends each nominee to the
+        nominated-pod table instead, and the dict gains nominated_id [count] (NOM_NONE where none).  Returns the dict `preempt` returns."""
+        flags = (soa.PREEMPT_APPLY if apply else 0) | (soa.PREEMPT_ASSUME if assume else 0) | (soa.PREEMPT_NOMINATE if nominate else 0)
+        res = self._preempt_call(flags, pod_index, priority, group_protected, victim_cap, stages)
+        if nominate:
+            res["nominated_id"] = self.preempt_nominated_read(len(res["node"]))
+        return res
 
     def preempt_commit_gang(self, pod_index, priority, group_protected=None, gang_need=None, victim_cap: int = 16, apply: bool = False,
-                            assume: bool = False, stages: int = soa.STAGE_PREFILTER, flat: bool = False) -> dict:
+                            assume: bool = False, stages: int = soa.STAGE_PREFILTER, flat: bool = False, nominate: bool = False) -> dict:
         """bs_preempt_commit_gang: preempt_commit, with each gang's quorum decided inside the pass: gang_need[g] members of group g must
         get a node in this call (the module's gang_need builds it; gang_order makes each gang one run), or the gang's slots are voided
         and their evictions taken back before the later slots are answered.  Returns preempt_commit's dict plus slot_voided [count]
         and group_placed [g] (bs_preempt_gang_read).  flat=True goes through bs_preempt_commit_gang_flat."""
-        flags = (soa.PREEMPT_APPLY if apply else 0) | (soa.PREEMPT_ASSUME if assume else 0)
+        flags = (soa.PREEMPT_APPLY if apply else 0) | (soa.PREEMPT_ASSUME if assume else 0) | (soa.PREEMPT_NOMINATE if nominate else 0)
         need = None if gang_need is None else np.ascontiguousarray(np.asarray(gang_need, np.uint32).reshape(-1))
         res = self._preempt_call(flags, pod_index, priority, group_protected, victim_cap, stages, gang=(need, flat))
         q, g = len(res["node"]), 0 if need is None else int(need.size)
         voided, placed = np.zeros(max(q, 1), np.uint8), np.zeros(max(g, 1), np.uint32)
         self._chk(self._lib.bs_preempt_gang_read(self._h, q, voided.ctypes.data_as(C.POINTER(C.c_uint8)), g, _u32p(placed)), "bs_preempt_gang_read")
         res["slot_voided"], res["group_placed"] = voided[:q], placed[:g]
+        if nominate:
+            res["nominated_id"] = self.preempt_nominated_read(q)
         return res
 
     def _preempt_call(self, flags, pod_index, priority, group_protected, victim_cap, stages, gang=None) -> dict:

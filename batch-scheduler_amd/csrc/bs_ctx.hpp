@@ -342,6 +342,18 @@ struct bs_ctx {
   bool have_pdb = false;
   uint32_t pdb_n = 0, pdb_covered = 0, pdb_members = 0;   // PDBs, ids the CSR covers, membership entries (= moff[pdb_covered])
   DevBuf d_pdb_allowed, d_pdb_moff, d_pdb_member;
+  // the resident nominated-pod table (bs_nominated_*, bs_nominated.hpp).  Two allocations of one layout, as the wait table: the live one
+  // (nom_cur) and the twin every bs_nominated_apply writes into; they swap on success.  Valid while the node count is the one it was made for.
+  bool have_nom = false;
+  uint32_t nom_w = 0, nom_ids = 0;     // rows; the id space: rows at the last bs_nominated_load plus what was inserted since
+  uint32_t nom_n = 0;                  // node count at the load
+  DevBuf d_nom[2];
+  uint32_t nom_cap[2] = {0, 0};        // rows each allocation is laid out for (the req lane stride, nnext's length)
+  uint32_t nom_ncap[2] = {0, 0};       // ... and nodes (nhead's length)
+  uint32_t nom_cur = 0;
+  std::vector<uint32_t> nom_live;      // the table's ids, ascending: what bs_nominated_apply checks its remove list against before any launch
+  std::vector<uint32_t> pre_nom;       // row id per preemptor of the last BS_PREEMPT_NOMINATE call (bs_preempt_nominated_read)
+  bool have_pre_nom = false;
 
   // ---- streams, events, pinned host memory.  Declared LAST and in this order: members are destroyed in reverse, so the pinned buffers
   // and events go first, then stream3, then stream, and only then the DevBufs above (bs_destroy has waited for both streams).

@@ -25,6 +25,55 @@
 
 namespace bs {
 
+__device__ __forceinline__ int64_t pre_readlane64(int64_t v, uint32_t i) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)i);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), (int)i);
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// The resident nominated-pod table (bs_nominated.hpp) as the victim search reads it: one chain per node through the rows on it.  All null
+// without a table or without rows.  The rows are static within a call.  The kernels get a POINTER to the view (it lives in the table's
+// allocation; null = no rows): five fields in the kernel arguments cost every instantiation nine scalar registers for its whole life, and
+// the pick and resolve kernels have none to spare.  Through the pointer the fields are scalar loads that live for the walk only.
+constexpr uint32_t kNmNone = 0xFFFFFFFFu;
+struct NomView {
+  const uint32_t* nhead;    // [n] first row on the node, kNmNone = none
+  const uint32_t* nnext;    // [cap] next row on the same node
+  const int32_t* nprio;     // [cap]
+  const int64_t* nreq;      // [L][nstride] as AddPod counts the row
+  uint32_t nstride;
+};
+
+// Rule N (include/bsched.h): the rows on node k with priority >= P are added into the LOCAL cur (wrapping sums; the order of a chain does
+// not matter).  The sum is never stored: the working deltas of a plan, k_pc_nodes' vectors, the gang rollback and the host mirror do not
+// see it.  In the scan kernels k is wave-uniform and P is the lane's.  Without rows: one uniform branch.
+template <int S>
+__device__ __forceinline__ void pre_nominees(const NomView* view, uint32_t k, int32_t P, int64_t (&cur)[4 + S]) {
+  if (!view) return;
+  const NomView nm = *view;
+  for (uint32_t r = nm.nhead[k]; r != kNmNone; r = nm.nnext[r]) {
+    if (nm.nprio[r] < P) continue;
+#pragma unroll
+    for (int l = 0; l < 4 + S; ++l) cur[l] = wadd(cur[l], nm.nreq[(size_t)l * nm.nstride + r]);
+  }
+}
+
+// ... where a whole wave works on one node for one preemptor (k and P wave-uniform: k_preempt_pick, stage D of the resolve kernels) and is
+// about to reduce part[] = the potential victims' requests, which it SUBTRACTS from cur: lane l < L loads request lane l of each
+// qualifying row (one load a row) and takes it off its own part[l] (wrapping sums: cur - (victims - rows) = cur - victims + rows,
+// exactly).  The walk rides the reduction that is there: one register pair of its own, no broadcast.
+template <int S>
+__device__ __forceinline__ void pre_nominees_part(const NomView* view, uint32_t k, int32_t P, uint32_t lane, int64_t (&part)[4 + S]) {
+  if (!view) return;
+  const NomView nm = *view;
+  for (uint32_t r = nm.nhead[k]; r != kNmNone; r = nm.nnext[r]) {
+    if (nm.nprio[r] < P) continue;
+    const int64_t v = lane < (uint32_t)(4 + S) ? nm.nreq[(size_t)lane * nm.nstride + r] : 0;
+#pragma unroll
+    for (int l = 0; l < 4 + S; ++l) part[l] = wsub(part[l], (int)lane == l ? v : 0);
+  }
+}
+
 // what both launches read (device pointers; the bound table is resident, the rest belongs to one bs_preempt_run)
 struct PreemptDev {
   // bound table, CSR by node, importance order within a node (priority descending, start ascending, caller id ascending)
@@ -60,6 +109,7 @@ struct PreemptDev {
   int64_t* o_sum;
   int64_t* o_est;
   uint32_t* o_victims;      // [q][cap]
+  const NomView* nm;        // the nominated-pod table (rule N), null without rows
 };
 
 // pick key of one candidate node (pickOneNodeForPreemption): node < 0 = no candidate
@@ -135,12 +185,6 @@ __device__ __forceinline__ void pre_pod(const PodsDev& pd, uint32_t pi, int64_t 
   rpq = pd.pres[pi];
 }
 
-__device__ __forceinline__ int64_t pre_readlane64(int64_t v, uint32_t i) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)i);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), (int)i);
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
 // step 5, the reprieve, on the entries [js, b1) of one node from the state `cur` with every potential victim (priority < P) removed;
 // fills kk's victim fields.  pdb = the node holds a violating pod: the entries are offered in two predicated passes, the violating
 // ones first (importance order inside a pass), as upstream's selectVictimsOnNode reprieves violatingVictims before
@@ -209,6 +253,7 @@ __global__ __launch_bounds__(64) void k_preempt_scan(NodesDev nd, PodsDev pd, Pr
     int64_t al[L], cur[L];
     uint32_t apres;
     pre_node<S>(nd, k, al, cur, apres);
+    pre_nominees<S>(pe.nm, k, P, cur);                                                // rule N
     // steps 2-4: remove every potential victim (priority < P), each through the policy of PreemptRemovePod
     bool refused = false;
     for (uint32_t j = js; j < b1; ++j) {
@@ -290,6 +335,7 @@ __global__ __launch_bounds__(64) void k_preempt_pick(NodesDev nd, PodsDev pd, Pr
   int64_t part[L];
 #pragma unroll
   for (int l = 0; l < L; ++l) part[l] = 0;
+  pre_nominees_part<S>(pe.nm, k, P, lane, part);               // rule N
   for (uint32_t j = js + lane; j < b1; j += 64u) {
 #pragma unroll
     for (int l = 0; l < L; ++l) part[l] = wadd(part[l], pe.breq[(size_t)l * pe.bstride + j]);

@@ -80,6 +80,7 @@ struct CommitDev {
   int64_t* o_sum;
   int64_t* o_est;
   uint32_t* o_victims;      // [q][cap]
+  const NomView* nm;        // the nominated-pod table (rule N), null without rows; static within the call
 };
 
 // APPLY: the compacted table (a second allocation; the old one is CommitDev's)
@@ -141,6 +142,7 @@ __global__ __launch_bounds__(64) void k_pc_scan(NodesDev nd, PodsDev pd, CommitD
     int64_t al[L], cur[L];
     uint32_t apres;
     pre_node<S>(nd, k, al, cur, apres);
+    pre_nominees<S>(pe.nm, k, P, cur);                                // rule N
     bool refused = false;
     for (uint32_t j = js; j < b1; ++j) {
       const int32_t pj = pe.bprio[j];
@@ -189,6 +191,7 @@ __device__ bool pc_eval(const NodesDev& nd, const CommitDev& pe, uint32_t k, int
   uint32_t apres;
   if (dirty) {                                                   // the base state's answer, as the records counted it
     pre_node<S>(nd, k, al, cur, apres);
+    pre_nominees<S>(pe.nm, k, P, cur);                          // rule N: the scan counted the rows too
     bool refused = false;
     for (uint32_t j = js; j < b1; ++j) {
       const int32_t vg = pe.bgroup[j];
@@ -199,6 +202,7 @@ __device__ bool pc_eval(const NodesDev& nd, const CommitDev& pe, uint32_t k, int
     if (!refused && pre_holds<S>(cur, al, apres, rq, rpq)) dcand -= 1;
   }
   pre_node<S>(nd, k, al, cur, apres);
+  pre_nominees<S>(pe.nm, k, P, cur);                            // rule N (local: dv / dn never hold the rows)
   if (dirty) {
 #pragma unroll
     for (int l = 0; l < L; ++l) cur[l] = wadd(wsub(cur[l], pc_ld64(pe.dv + (size_t)l * nd.n + k)), pc_ld64(pe.dn + (size_t)l * nd.n + k));
@@ -370,6 +374,7 @@ __global__ __launch_bounds__(pc_threads<S>()) void k_pc_resolve(NodesDev nd, Pod
 #pragma unroll
           for (int l = 0; l < L; ++l) part[l] = wadd(part[l], pe.breq[(size_t)l * pe.bstride + j]);
         }
+        pre_nominees_part<S>(pe.nm, k, P, lane, part);          // rule N
 #pragma unroll
         for (int l = 0; l < L; ++l) {
           int64_t v = part[l];

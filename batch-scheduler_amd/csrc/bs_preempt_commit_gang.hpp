@@ -255,6 +255,7 @@ __global__ __launch_bounds__(pc_threads<S>()) void k_gang_resolve(NodesDev nd, P
 #pragma unroll
           for (int l = 0; l < L; ++l) part[l] = wadd(part[l], pe.breq[(size_t)l * pe.bstride + j]);
         }
+        pre_nominees_part<S>(pe.nm, k, P, lane, part);          // rule N
 #pragma unroll
         for (int l = 0; l < L; ++l) {
           int64_t v = part[l];

@@ -1,7 +1,7 @@
 // tu_preempt.hip — translation unit of everything over the bound-pod table.  Kernels: the preemption victim search (bs_preempt.hpp: k_preempt_scan /
 // k_preempt_pick), the sequential plans (bs_preempt_commit.hpp: k_pc_*), the table's patch (bs_bound_apply.hpp: k_ba_*) and its remap after node-list
 // surgery (bs_bound_nodes.hpp: k_bn_*), one instantiation per scalar-lane count 0..BS_MAX_SCALARS, and the resident PodDisruptionBudgets (bs_pdb.hpp:
-// k_pdb_*, no templates).  Host: their file-local launch wrappers and the entry points bs_bound_*, bs_pdb_*, bs_preempt_* (include/bsched.h).
+// k_pdb_*, no templates), and the resident nominated-pod table (bs_nominated.hpp: k_nm_*).  Host: their file-local launch wrappers and the entry points bs_bound_*, bs_pdb_*, bs_nominated_*, bs_preempt_* (include/bsched.h).
 #ifndef BS_UNITY
 #define BS_TU_PREEMPT
 #endif
@@ -11,12 +11,15 @@
 #include "bs_bound_apply.hpp"
 #include "bs_bound_nodes.hpp"
 #include "bs_pdb.hpp"
+#include "bs_nominated.hpp"
 #include "bs_preempt_gang_runs.hpp"
 #include "bs_preempt_geom.hpp"
 #include "bs_bound_nodes_replay.hpp"
+#include "bs_nominated_check.hpp"
 #include "bs_ctx.hpp"
 
 #include <cstring>
+#include <iterator>
 #include <type_traits>
 
 namespace {
@@ -126,6 +129,156 @@ BoundCols<U8> bound_dev(D& d, U8* base, const BoundLayout& l) {
   const BoundCols<U8> t = bound_cols(base, l);
   d.boff = t.boff; d.bprio = t.prio; d.bstart = t.start; d.bgroup = t.group; d.bid = t.id; d.breq = t.req; d.bpdb = t.pdb;
   return t;
+}
+
+// -------------------------------------------------------------------------------------------------
+// the resident nominated-pod table (bs_nominated.hpp)
+// -------------------------------------------------------------------------------------------------
+// the table's one allocation for `cap` rows on n nodes: columns at 256-byte offsets, req lane stride max(cap, 1)
+struct NomLayout {
+  Piece<uint32_t> id, node;
+  Piece<int32_t> prio;
+  Piece<uint32_t> pres;
+  Piece<int64_t> req;
+  Piece<uint32_t> nhead, nnext;
+  Piece<NomView> view;                 // what the victim search reads, written with the chains
+  size_t bytes = 0;
+  uint32_t stride = 1;
+};
+NomLayout nom_layout(uint32_t cap, uint32_t n, uint32_t L) {
+  const size_t rows = std::max<uint32_t>(cap, 1);
+  NomLayout l;
+  Carve cv;
+  l.id = cv.take<uint32_t>(rows);
+  l.node = cv.take<uint32_t>(rows);
+  l.prio = cv.take<int32_t>(rows);
+  l.pres = cv.take<uint32_t>(rows);
+  l.req = cv.take<int64_t>(rows * L);
+  l.nhead = cv.take<uint32_t>(std::max<uint32_t>(n, 1));
+  l.nnext = cv.take<uint32_t>(rows);
+  l.view = cv.take<NomView>(1);
+  l.bytes = cv.mark();
+  l.stride = (uint32_t)rows;
+  return l;
+}
+NomTab nom_tab(const bs_ctx* c, uint32_t which) {
+  const NomLayout l = nom_layout(c->nom_cap[which], c->nom_ncap[which], c->L);
+  void* b = c->d_nom[which].p;
+  return NomTab{l.id.in(b), l.node.in(b), l.prio.in(b), l.pres.in(b), l.req.in(b), l.nhead.in(b), l.nnext.in(b), l.stride};
+}
+// allocation `which` is laid out for at least `rows` rows on the context's nodes afterwards (a quarter of headroom, as the wait table);
+// what it held is lost when the layout changes
+hipError_t nom_reserve(bs_ctx* c, uint32_t which, uint32_t rows) {
+  if (c->d_nom[which].p && c->nom_cap[which] >= rows && c->nom_ncap[which] == c->N) return hipSuccess;
+  const uint32_t cap = std::max<uint32_t>(rows + rows / 4, 256);
+  const hipError_t e = c->d_nom[which].reserve(nom_layout(cap, c->N, c->L).bytes);
+  if (e == hipSuccess) { c->nom_cap[which] = cap; c->nom_ncap[which] = c->N; }
+  return e;
+}
+// what the victim search reads: null without a table or without rows (the callers have refused a stale table that holds rows)
+const NomView* nom_view(const bs_ctx* c) {
+  if (!c->have_nom || c->nom_w == 0) return nullptr;
+  const uint32_t cur = c->nom_cur;
+  return nom_layout(c->nom_cap[cur], c->nom_ncap[cur], c->L).view.in((const void*)c->d_nom[cur].p);
+}
+// the chains of allocation `which` over `rows` rows: nhead filled with kNmNone, then k_nm_chains, which also writes the view of that table
+// (a table without rows has no view: nom_view answers null for it)
+hipError_t launch_nom_chains(bs_ctx* c, uint32_t which, uint32_t rows) {
+  const NomTab t = nom_tab(c, which);
+  NomView* dv = nom_layout(c->nom_cap[which], c->nom_ncap[which], c->L).view.in(c->d_nom[which].p);
+  const hipError_t e = hipMemsetAsync(t.nhead, 0xff, (size_t)std::max<uint32_t>(c->N, 1) * 4, c->stream);
+  if (e == hipSuccess && rows) hipLaunchKernelGGL(k_nm_chains, dim3(cdiv(rows, 256)), dim3(256), 0, c->stream, t, dv, rows, c->N);
+  return e;
+}
+// k_nm_mark -> k_nm_move<S> (one workgroup) -> k_nm_gather<S>; the chains follow (launch_nom_chains)
+void launch_nom_apply(hipStream_t stream, uint32_t S, const NomDev& a, const PodsDev& pd) {
+  if (a.n_remove) hipLaunchKernelGGL(k_nm_mark, dim3(cdiv(a.n_remove, 256)), dim3(256), 0, stream, a);
+  lanes_wide(S, [&](auto s) {
+    constexpr int V = decltype(s)::value;
+    if (a.W) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nm_move<V>), dim3(1), dim3(kNmWindow), 0, stream, a);
+    if (a.n_insert) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nm_gather<V>), dim3(cdiv(a.n_insert, 256)), dim3(256), 0, stream, a, pd);
+  });
+}
+int nom_single_rank(bs_ctx* c, const char* who) {
+  if (c->nranks > 1 || c->reduce_external) { c->last_error = std::string(who) + " is single-rank only (as bs_preempt_run)"; return BS_ERR_STATE; }
+  return BS_OK;
+}
+// the table exists and was made for the node count the context holds now
+int nom_state(bs_ctx* c, const char* who) {
+  if (const int rc = nom_single_rank(c, who)) return rc;
+  if (!c->have_nom) { c->last_error = std::string(who) + ": no nominated-pod table (bs_nominated_load first; m = 0 gives the empty one)"; return BS_ERR_STATE; }
+  if (!c->have_nodes || c->nom_n != c->N) {
+    c->last_error = std::string(who) + ": the nominated-pod table was made for another node count (bs_nominated_read before the surgery, a remap on the host, bs_nominated_load)";
+    return BS_ERR_STATE;
+  }
+  return BS_OK;
+}
+// what the three preemption calls refuse: rows of a table that was made for another node count
+int nom_preempt_state(bs_ctx* c, const char* who) {
+  if (c->have_nom && c->nom_w && c->nom_n != c->N) {
+    c->last_error = std::string(who) + ": the nominated-pod table holds rows and was made for another node count: reload it";
+    return BS_ERR_STATE;
+  }
+  return BS_OK;
+}
+int nom_refusal(bs_ctx* c, const char* who, int bad) {
+  c->last_error = std::string(who) + ": " + nom_check_text(bad);
+  return nom_check_is_capacity(bad) ? BS_ERR_CAPACITY : BS_ERR_INVALID;
+}
+// bs_nominated_apply behind its checks (and BS_PREEMPT_NOMINATE's append): the listed rows leave by the stable compaction into the twin,
+// the inserts are gathered from the resident queue behind the survivors, the chains are rebuilt, the twin becomes the table.  One wait.
+int nom_apply_rows(bs_ctx* c, uint32_t R, const uint32_t* remove_id, uint32_t I, const uint32_t* pod_index, const uint32_t* node,
+                   const int32_t* priority) {
+  const uint32_t W = c->nom_w, W2 = W - R, W3 = W2 + I, cur = c->nom_cur, other = cur ^ 1u, ids = c->nom_ids;
+  HIPCHK(c, hipStreamSynchronize(c->stream));               // (nothing of an earlier call still reads the twin)
+  HIPCHK(c, nom_reserve(c, other, W3));
+  const size_t nR = R, nI = I;
+  Carve cv;
+  const auto o_rem = cv.take<uint32_t>(nR, 4);              // (packed: one H2D)
+  const auto o_pod = cv.take<uint32_t>(nI, 4);
+  const auto o_node = cv.take<uint32_t>(nI, 4);
+  const auto o_prio = cv.take<int32_t>(nI, 4);
+  const size_t blob_bytes = cv.mark();
+  const auto o_flag = cv.take<uint8_t>(std::max<uint32_t>(W, 1));
+  if (cv.mark() > c->d_pre.cap) HIPCHK(c, c->d_pre.reserve(cv.mark() + cv.mark() / 4));
+  std::vector<uint8_t> h(std::max<size_t>(blob_bytes, 1), 0);
+  if (R) std::memcpy(o_rem.in(h.data()), remove_id, o_rem.bytes());
+  if (I) {
+    std::memcpy(o_pod.in(h.data()), pod_index, o_pod.bytes());
+    std::memcpy(o_node.in(h.data()), node, o_node.bytes());
+    std::memcpy(o_prio.in(h.data()), priority, o_prio.bytes());
+  }
+  uint8_t* base = c->d_pre.as<uint8_t>();
+  HIPCHK(c, hipMemcpyAsync(base, h.data(), h.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(o_flag.in(base), 0, o_flag.bytes(), c->stream));
+  NomDev a{};
+  a.src = nom_tab(c, cur);
+  a.dst = nom_tab(c, other);
+  a.W = W; a.W2 = W2; a.N = c->N;
+  a.rem = o_rem.in(base);
+  a.n_remove = R;
+  a.ipod = o_pod.in(base);
+  a.inode = o_node.in(base);
+  a.iprio = o_prio.in(base);
+  a.n_insert = I;
+  a.ids = ids;
+  a.flag = o_flag.in(base);
+  launch_nom_apply(c->stream, c->S, a, pods_dev(c));
+  HIPCHK(c, launch_nom_chains(c, other, W3));
+  LAUNCHCHK(c, BS_KERNEL_PREPASS);
+  HIPCHK(c, hipStreamSynchronize(c->stream));               // (h is a local buffer)
+  if (R) {
+    std::vector<uint32_t> gone(remove_id, remove_id + R), left;
+    std::sort(gone.begin(), gone.end());
+    left.reserve(W3);
+    std::set_difference(c->nom_live.begin(), c->nom_live.end(), gone.begin(), gone.end(), std::back_inserter(left));
+    c->nom_live.swap(left);
+  }
+  for (uint32_t k = 0; k < I; ++k) c->nom_live.push_back(ids + k);
+  c->nom_cur = other;
+  c->nom_w = W3;
+  c->nom_ids = ids + I;
+  return BS_OK;
 }
 
 }  // namespace
@@ -426,6 +579,112 @@ int bs_preempt_pdb_read(bs_ctx* c, uint32_t count, uint32_t* n_pdb_violations) {
   return BS_OK;
 }
 
+int bs_preempt_nominated_read(bs_ctx* c, uint32_t count, uint32_t* id_out) {
+  if (!c) return BS_ERR_INVALID;
+  if (!c->have_pre_nom) { c->last_error = "bs_preempt_nominated_read: the last successful preemption call did not carry BS_PREEMPT_NOMINATE"; return BS_ERR_STATE; }
+  if (count != c->pre_nom.size()) { c->last_error = "bs_preempt_nominated_read: count differs from the last preemption call's"; return BS_ERR_INVALID; }
+  if (count == 0) return BS_OK;
+  if (!id_out) return BS_ERR_INVALID;
+  std::memcpy(id_out, c->pre_nom.data(), (size_t)count * 4);
+  return BS_OK;
+}
+
+// -------------------------------------------------------------------------------------------------
+// the resident nominated-pod table (bs_nominated.hpp): pods nominated by earlier cycles, counted by every fit test of the victim search
+// -------------------------------------------------------------------------------------------------
+int bs_nominated_load(bs_ctx* c, uint32_t m, const uint32_t* node, const int32_t* priority, const int64_t* req, const uint32_t* req_present) {
+  if (!c) return BS_ERR_INVALID;
+  int rc = nom_single_rank(c, "bs_nominated_load");
+  if (rc) return rc;
+  if (!c->have_nodes) { c->last_error = "bs_nominated_load before bs_nodes_load"; return BS_ERR_STATE; }
+  if (const int bad = nom_load_check(c->N, m, node, priority, req, req_present, BS_NOM_MAX)) return nom_refusal(c, "bs_nominated_load", bad);
+  if ((rc = use_device(c))) return rc;
+  const uint32_t L = c->L, other = c->nom_cur ^ 1u;
+  HIPCHK(c, hipStreamSynchronize(c->stream));               // (nothing of an earlier call still reads the twin)
+  HIPCHK(c, nom_reserve(c, other, m));
+  const NomLayout l = nom_layout(c->nom_cap[other], c->nom_ncap[other], L);
+  if (m) {
+    // the columns as the table stores them: ids 0 .. m - 1, the pods lane 1, a scalar lane without a present bit 0
+    std::vector<uint8_t> st(l.nhead.off);                   // (the chains are made on the device)
+    const uint32_t smask = c->S ? (uint32_t)((1ull << c->S) - 1ull) : 0u;
+    for (uint32_t i = 0; i < m; ++i) {
+      l.id.in(st.data())[i] = i;
+      l.node.in(st.data())[i] = node[i];
+      l.prio.in(st.data())[i] = priority[i];
+      l.pres.in(st.data())[i] = req_present[i] & smask;
+    }
+    for (uint32_t j = 0; j < L; ++j)
+      for (uint32_t i = 0; i < m; ++i) {
+        int64_t v = req[(size_t)j * m + i];
+        if (j == BS_LANE_PODS) v = 1;
+        else if (j >= BS_FIXED_LANES && !((req_present[i] & smask) >> (j - BS_FIXED_LANES) & 1u)) v = 0;
+        l.req.in(st.data())[(size_t)j * l.stride + i] = v;
+      }
+    HIPCHK(c, hipMemcpyAsync(c->d_nom[other].p, st.data(), st.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_nom_chains(c, other, m));
+    LAUNCHCHK(c, BS_KERNEL_PREPASS);
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // (st is a local buffer)
+  }
+  c->nom_cur = other;
+  c->have_nom = true;
+  c->nom_w = c->nom_ids = m;
+  c->nom_n = c->N;
+  c->nom_live.resize(m);
+  for (uint32_t i = 0; i < m; ++i) c->nom_live[i] = i;
+  return BS_OK;
+}
+
+int bs_nominated_count(const bs_ctx* c, uint32_t* m_out) {
+  if (!c || !m_out) return BS_ERR_INVALID;
+  if (!c->have_nom) return BS_ERR_STATE;
+  *m_out = c->nom_w;
+  return BS_OK;
+}
+
+int bs_nominated_ids(const bs_ctx* c, uint32_t* ids_out) {
+  if (!c || !ids_out) return BS_ERR_INVALID;
+  if (!c->have_nom) return BS_ERR_STATE;
+  *ids_out = c->nom_ids;
+  return BS_OK;
+}
+
+int bs_nominated_read(bs_ctx* c, uint32_t* id, uint32_t* node, int32_t* priority, int64_t* req, uint32_t* req_present) {
+  if (!c) return BS_ERR_INVALID;
+  int rc = nom_state(c, "bs_nominated_read");
+  if (rc) return rc;
+  const uint32_t W = c->nom_w;
+  if (W && (!id || !node || !priority || !req || !req_present)) { c->last_error = "bs_nominated_read: a column is NULL and the table has rows"; return BS_ERR_INVALID; }
+  if ((rc = use_device(c))) return rc;
+  if (!W) return BS_OK;
+  const NomTab t = nom_tab(c, c->nom_cur);
+  HIPCHK(c, hipMemcpyAsync(id, t.id, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(node, t.node, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(priority, t.prio, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(req_present, t.pres, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
+  for (uint32_t j = 0; j < c->L; ++j)
+    HIPCHK(c, hipMemcpyAsync(req + (size_t)j * W, t.req + (size_t)j * t.stride, (size_t)W * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return BS_OK;
+}
+
+int bs_nominated_apply(bs_ctx* c, uint32_t n_remove, const uint32_t* remove_id, uint32_t n_insert, const uint32_t* pod_index, const uint32_t* node,
+                       const int32_t* priority, uint32_t* first_id_out) {
+  if (!c) return BS_ERR_INVALID;
+  int rc = nom_state(c, "bs_nominated_apply");
+  if (rc) return rc;
+  if (n_insert && !c->have_pods) { c->last_error = "bs_nominated_apply: inserts need the pods loaded (the rows are gathered from the resident queue)"; return BS_ERR_STATE; }
+  if (const int bad = nom_apply_check(c->nom_live.data(), c->nom_w, c->nom_ids, n_remove, remove_id, n_insert, pod_index, node, priority, c->P, c->N,
+                                      BS_NOM_MAX, kNomMaxIds))
+    return nom_refusal(c, "bs_nominated_apply", bad);
+  const uint32_t ids = c->nom_ids;
+  if (n_remove || n_insert) {
+    if ((rc = use_device(c))) return rc;
+    if ((rc = nom_apply_rows(c, n_remove, remove_id, n_insert, pod_index, node, priority))) return rc;
+  }
+  if (first_id_out) *first_id_out = ids;
+  return BS_OK;
+}
+
 int bs_bound_count(const bs_ctx* c, uint32_t* b_out) {
   if (!c || !b_out) return BS_ERR_INVALID;
   *b_out = c->have_bound ? c->bound_b : 0u;
@@ -442,8 +701,9 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   }
   if (c->nranks > 1 || c->reduce_external) { c->last_error = "bs_preempt_run is single-rank only"; return BS_ERR_STATE; }
   if (c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
+  if (const int nrc = nom_preempt_state(c, "bs_preempt_run")) return nrc;
   if (count > BS_PREEMPT_MAX || (uint64_t)count * victim_cap > (1ull << 28)) return BS_ERR_CAPACITY;
-  if (count == 0) { c->pre_npv.clear(); c->have_pre_npv = true; c->have_gang = false; return BS_OK; }
+  if (count == 0) { c->pre_npv.clear(); c->have_pre_npv = true; c->have_gang = false; c->have_pre_nom = false; return BS_OK; }
   if (!pod_index || !priority || !out->node || !out->n_victims || (victim_cap && !out->victims) || (c->G && !group_protected)) return BS_ERR_INVALID;
   if (c->bound_max_group >= (int32_t)c->G) { c->last_error = "the bound table names a group index >= the loaded group count"; return BS_ERR_INVALID; }
   const uint32_t P = c->P, N = c->N, G = c->G;
@@ -517,6 +777,7 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   pe.o_sum = o_sum.in(base);
   pe.o_est = o_est.in(base);
   pe.o_victims = o_vic.in(base);
+  pe.nm = nom_view(c);
   launch_preempt(c->stream, c->S, dim3(tiles, nchunks), nodes_dev(c), pods_dev(c), pe);
   LAUNCHCHK(c, BS_KERNEL_QUERY);
   std::vector<uint8_t> res(cv.mark() - o_res);
@@ -528,6 +789,7 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   c->pre_npv.assign(o_npv.in(rb), o_npv.in(rb) + nQ);
   c->have_pre_npv = true;
   c->have_gang = false;
+  c->have_pre_nom = false;
   if (out->n_candidates) std::memcpy(out->n_candidates, o_ncand.in(rb), o_ncand.bytes());
   if (out->top_priority) std::memcpy(out->top_priority, o_top.in(rb), o_top.bytes());
   if (out->priority_sum) std::memcpy(out->priority_sum, o_sum.in(rb), o_sum.bytes());
@@ -569,21 +831,34 @@ static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const
                                const bs_preempt_out* out) {
   if (!c || !out) return BS_ERR_INVALID;
   if (stages & ~BS_STAGE_PREFILTER) { c->last_error = "bs_preempt_commit takes BS_STAGE_PREFILTER only (the plugin's Filter takes no part)"; return BS_ERR_INVALID; }
-  if (flags & ~(BS_PREEMPT_APPLY | BS_PREEMPT_ASSUME)) { c->last_error = "bs_preempt_commit: unknown flags"; return BS_ERR_INVALID; }
+  if (flags & ~(BS_PREEMPT_APPLY | BS_PREEMPT_ASSUME | BS_PREEMPT_NOMINATE)) { c->last_error = "bs_preempt_commit: unknown flags"; return BS_ERR_INVALID; }
   if ((flags & BS_PREEMPT_ASSUME) && !(flags & BS_PREEMPT_APPLY)) { c->last_error = "BS_PREEMPT_ASSUME needs BS_PREEMPT_APPLY"; return BS_ERR_INVALID; }
+  if ((flags & BS_PREEMPT_NOMINATE) && !(flags & BS_PREEMPT_APPLY)) { c->last_error = "BS_PREEMPT_NOMINATE needs BS_PREEMPT_APPLY"; return BS_ERR_INVALID; }
+  if ((flags & BS_PREEMPT_NOMINATE) && (flags & BS_PREEMPT_ASSUME)) {
+    c->last_error = "BS_PREEMPT_NOMINATE with BS_PREEMPT_ASSUME: the nominee would count twice";
+    return BS_ERR_INVALID;
+  }
+  const bool nominate = (flags & BS_PREEMPT_NOMINATE) != 0;
   if (!c->have_nodes || !c->have_fit || !c->have_pods || !c->have_bound) {
     c->last_error = "bs_preempt_commit needs nodes, fit, pods and the bound table loaded";
     return BS_ERR_STATE;
   }
   if (c->nranks > 1 || c->reduce_external) { c->last_error = "bs_preempt_commit is single-rank only"; return BS_ERR_STATE; }
   if (c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
+  if (const int nrc = nom_preempt_state(c, "bs_preempt_commit")) return nrc;
+  if (nominate)
+    if (const int nrc = nom_state(c, "BS_PREEMPT_NOMINATE")) return nrc;
   if (count > BS_PREEMPT_MAX || (uint64_t)count * victim_cap > (1ull << 28)) return BS_ERR_CAPACITY;
+  if (nominate)                                           // against count, before any launch: all or nothing
+    if (const int bad = nom_nominate_check(c->nom_w, c->nom_ids, count, BS_NOM_MAX, kNomMaxIds)) return nom_refusal(c, "BS_PREEMPT_NOMINATE", bad);
   if (gang && c->G && !gang_need) { c->last_error = "bs_preempt_commit_gang: gang_need is NULL with g > 0"; return BS_ERR_INVALID; }
   if (count == 0) {
     c->pre_npv.clear();
     c->have_pre_npv = true;
     c->have_gang = gang;
     if (gang) { c->gang_voided.clear(); c->gang_placed.assign(c->G, 0u); }
+    c->pre_nom.clear();
+    c->have_pre_nom = nominate;
     return BS_OK;
   }
   if (!pod_index || !priority || !out->node || !out->n_victims || (victim_cap && !out->victims) || (c->G && !group_protected)) return BS_ERR_INVALID;
@@ -717,6 +992,7 @@ static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const
   pe.o_sum = o_sum.in(base);
   pe.o_est = o_est.in(base);
   pe.o_victims = o_vic.in(base);
+  pe.nm = nom_view(c);
   const NodesDev nd = nodes_dev(c);
   if (gang) {
     GangDev gd{};
@@ -773,6 +1049,22 @@ static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const
       c->bound_b = B2;
     }
   }
+  if (nominate) {
+    // every slot that holds a node (gang: not voided, its node is -1 otherwise) is appended to the table, in the caller's order
+    const int32_t* rnode = o_node.in(rb);
+    std::vector<uint32_t> npod, nnode;
+    std::vector<int32_t> nprio;
+    c->pre_nom.assign(nQ, 0xFFFFFFFFu);
+    for (uint32_t i = 0; i < count; ++i)
+      if (rnode[i] >= 0) {
+        c->pre_nom[i] = c->nom_ids + (uint32_t)npod.size();
+        npod.push_back(pod_index[i]);
+        nnode.push_back((uint32_t)rnode[i]);
+        nprio.push_back(priority[i]);
+      }
+    if (!npod.empty() && (rc = nom_apply_rows(c, 0u, nullptr, (uint32_t)npod.size(), npod.data(), nnode.data(), nprio.data()))) return rc;
+  }
+  c->have_pre_nom = nominate;
   std::memcpy(out->node, o_node.in(rb), o_node.bytes());
   std::memcpy(out->n_victims, o_nv.in(rb), o_nv.bytes());
   c->pre_npv.assign(o_npv.in(rb), o_npv.in(rb) + nQ);

@@ -1,0 +1,121 @@
+// +build cgo
+
+/*
+The resident nominated-pod table (include/bsched.h "the resident nominated-pod table"; INTEGRATION.md, preemption): pods that preempted
+in an earlier cycle and have not bound yet.  The victim search of the three preemption calls counts them as upstream's
+addNominatedPods does (rule N): for a preemptor of priority P, the rows on the node with priority >= P.  The shim keeps the row id
+beside the pod's UID (preemptNominatedRead after a plan with BS_PREEMPT_NOMINATE) and removes a preemptor's OWN row before the pod is
+searched for again: the table holds other pods' nominations.  Nothing here is compiled in this repository's image (no Go toolchain);
+the calls' behaviour is pinned by tests/test_gpu_nominated.py through the same entry points, which take flat arguments only.
+*/
+package core
+
+/*
+#include "bsched.h"
+*/
+import "C"
+
+import "fmt"
+
+// nominatedRow is one nominee as loadNominated takes it and readNominated returns it.
+type nominatedRow struct {
+	id         uint32 // readNominated only: ids are 0 .. m-1 after a load
+	node       uint32
+	priority   int32
+	req        []int64 // one value per lane of the context
+	reqPresent uint32
+}
+
+// loadNominated: a snapshot (a restart, or after node-list surgery with the rows' nodes remapped by the caller).  No rows: the empty
+// table, which BS_PREEMPT_NOMINATE needs before its first call.
+func (g *gpuCore) loadNominated(rows []nominatedRow, lanes int) error {
+	m := len(rows)
+	node, pres := make([]C.uint32_t, m), make([]C.uint32_t, m)
+	prio, req := make([]C.int32_t, m), make([]C.int64_t, m*lanes)
+	for i, r := range rows {
+		node[i], prio[i], pres[i] = C.uint32_t(r.node), C.int32_t(r.priority), C.uint32_t(r.reqPresent)
+		for l := 0; l < lanes && l < len(r.req); l++ {
+			req[l*m+i] = C.int64_t(r.req[l]) // [L][m]
+		}
+	}
+	var pNode, pPres *C.uint32_t
+	var pPrio *C.int32_t
+	var pReq *C.int64_t
+	if m > 0 {
+		pNode, pPrio, pReq, pPres = &node[0], &prio[0], &req[0], &pres[0]
+	}
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if rc := C.bs_nominated_load(g.ctx, C.uint32_t(m), pNode, pPrio, pReq, pPres); rc != C.BS_OK {
+		return g.pdbErr("bs_nominated_load", rc)
+	}
+	return nil
+}
+
+// applyNominated: the rows with the ids in removed leave (nominees that bound, were deleted, or are about to be searched for again);
+// then one row per (podIndex[k], node[k], priority[k]) arrives, its request gathered on the device from the resident queue.  Returns
+// the id of the first new row; row k gets first + k.
+func (g *gpuCore) applyNominated(removed, podIndex, node []uint32, priority []int32) (uint32, error) {
+	if len(podIndex) != len(node) || len(podIndex) != len(priority) {
+		return 0, fmt.Errorf("applyNominated: %d pod indices, %d nodes, %d priorities", len(podIndex), len(node), len(priority))
+	}
+	_, pRem := u32s(removed)
+	_, pPod := u32s(podIndex)
+	_, pNode := u32s(node)
+	_, pPrio := i32s(priority)
+	var first C.uint32_t
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if rc := C.bs_nominated_apply(g.ctx, C.uint32_t(len(removed)), pRem, C.uint32_t(len(podIndex)), pPod, pNode, pPrio, &first); rc != C.BS_OK {
+		return 0, g.pdbErr("bs_nominated_apply", rc)
+	}
+	return uint32(first), nil
+}
+
+// readNominated: the table in table order (ascending id), for reconciliation and for the remap after node-list surgery.
+func (g *gpuCore) readNominated(lanes int) ([]nominatedRow, error) {
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	var m C.uint32_t
+	if rc := C.bs_nominated_count(g.ctx, &m); rc != C.BS_OK {
+		return nil, g.pdbErr("bs_nominated_count", rc)
+	}
+	n := int(m)
+	if n == 0 {
+		return nil, nil
+	}
+	id, node, pres := make([]C.uint32_t, n), make([]C.uint32_t, n), make([]C.uint32_t, n)
+	prio, req := make([]C.int32_t, n), make([]C.int64_t, n*lanes)
+	if rc := C.bs_nominated_read(g.ctx, &id[0], &node[0], &prio[0], &req[0], &pres[0]); rc != C.BS_OK {
+		return nil, g.pdbErr("bs_nominated_read", rc)
+	}
+	rows := make([]nominatedRow, n)
+	for i := range rows {
+		rows[i] = nominatedRow{id: uint32(id[i]), node: uint32(node[i]), priority: int32(prio[i]), reqPresent: uint32(pres[i]), req: make([]int64, lanes)}
+		for l := 0; l < lanes; l++ {
+			rows[i].req[l] = int64(req[l*n+i])
+		}
+	}
+	return rows, nil
+}
+
+// noNominatedRow is what preemptNominatedRead reports for a preemptor that got no node (or whose gang was voided).
+const noNominatedRow = ^uint32(0)
+
+// preemptNominatedRead: after a plan with BS_PREEMPT_NOMINATE, the row id of each preemptor in the caller's order.
+func (g *gpuCore) preemptNominatedRead(count int) ([]uint32, error) {
+	if count == 0 {
+		return nil, nil
+	}
+	out := make([]C.uint32_t, count)
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if rc := C.bs_preempt_nominated_read(g.ctx, C.uint32_t(count), &out[0]); rc != C.BS_OK {
+		return nil, g.pdbErr("bs_preempt_nominated_read", rc)
+	}
+	ids := make([]uint32, count)
+	for i, x := range out {
+		ids[i] = uint32(x)
+	}
+	return ids, nil
+}

@@ -826,8 +826,21 @@ int bs_groups_list_apply(bs_ctx* ctx, const bs_groups_list_delta* delta, bs_grou
  *   D3. pickOneNodeForPreemption: victim-free node first; then fewest NumPDBViolations; then lowest victims.Pods[0] priority; then the
  *       smallest priority sum, the fewest victims, the latest GetEarliestPodStartTime; then the first left.
  *   D4. A pod of priority >= the preemptor's is no potential victim; its PDBs are never looked at.
+ *   D5. podFitsOnNode calls addNominatedPods before it tests: every pod nominated on the node with
+ *       GetPodPriority(p) >= GetPodPriority(pod) && p.UID != pod.UID is added to a copy of the NodeInfo (AddPod).  Equal priority counts.
+ *   N.  (rule N, D5 on the resident table of bs_nominated_load below.)  For a preemptor of priority P on node k, the requests every fit
+ *       test of steps 4 and 5 sees are the node's working requests plus every row of the nominated-pod table on k with
+ *       row.priority >= P (signed int32; equal priority counts).  A row is added as AddPod: lanes 0..2 plus the request, the pods lane
+ *       plus 1, the scalar lanes plus the row's value; sums wrap.  A nominee is never a victim and never goes through the policy of
+ *       step 3.  Rows on flagged and unfit nodes count too, which is moot: step 1 skips those nodes.  With no table, or an empty one,
+ *       every answer is what it was without this rule.  The sum exists inside the fit tests only: node requests, and what
+ *       BS_PREEMPT_APPLY / BS_PREEMPT_ASSUME write, never contain a row.
+ *       Library rule N1: upstream runs podFitsOnNode a second time without the nominees; with sums that do not wrap the first test
+ *       implies the second, and where they wrap this library's answer is the first test's.
+ *       Library rule N2: the table holds OTHER pods' nominations.  Upstream leaves the pod's own nomination out by UID; the queue has
+ *       no UID, so a preemptor's own row is the caller's to remove beforehand (one bs_nominated_apply for the batch).
  * Restrictions: BS_STAGE_FILTER is refused (BS_ERR_INVALID: the plugin's Filter takes no part in the fit test; the shipped config
- * does not enable Filter).  No nominated pods from earlier calls.  podEligibleToPreemptOthers (PreemptionPolicy Never, terminating pods on the
+ * does not enable Filter).  Pods nominated by earlier calls count through the resident table below (rule N).  podEligibleToPreemptOthers (PreemptionPolicy Never, terminating pods on the
  * nominated node) is the caller's business, and so is the choice of preemptors: upstream preempts only for a pod that passed
  * PreFilter and then found no node (a PreFilter rejection is not a FitError).  Sharded contexts: BS_ERR_STATE, as bs_seq_run.
  * The call is a what-if: node requests, groups and the queue are left as they were.  Synchronous. */
@@ -914,10 +927,19 @@ int bs_preempt_pdb_read(bs_ctx* ctx, uint32_t count, uint32_t* n_pdb_violations)
  *   6. errors: whatever bs_preempt_run refuses, with the same code; also a pod_index that appears twice (a pod is nominated once) and
  *      BS_PREEMPT_ASSUME without BS_PREEMPT_APPLY (BS_ERR_INVALID).  Everything is validated before anything is launched; on any error
  *      no resident state changes.  Group state, the queue and the fit masks are never touched: a gang that loses pods keeps its
- *      Status.Scheduled (updating it is the controller's job).  No nominated pods from earlier calls; sharded contexts:
- *      BS_ERR_STATE.  Synchronous. */
-#define BS_PREEMPT_APPLY  1u   /* write the evictions into the bound table and the node requests */
-#define BS_PREEMPT_ASSUME 2u   /* with APPLY: also add each nominee's request to its node          */
+ *      Status.Scheduled (updating it is the controller's job).  Pods nominated by earlier calls: rule N, in every fit test of every slot, on top of
+ *      the working state of 2 (the rows are static within a call).  Sharded contexts: BS_ERR_STATE.  Synchronous.
+ *   7. BS_PREEMPT_NOMINATE (only with APPLY; with ASSUME it is BS_ERR_INVALID: a nominee would count twice): after the evictions are
+ *      written, every slot that holds a node (bs_preempt_commit_gang: every slot that is not voided) is appended to the nominated-pod
+ *      table, in the caller's order with ascending ids: the node from the result, the priority from the call, the request lanes and
+ *      present bits from the resident queue.  Node requests do not get the nominee: a later preemptor of HIGHER priority passes over
+ *      it, which BS_PREEMPT_ASSUME cannot express.  Needs a table that is valid for the node count (bs_nominated_load; BS_ERR_STATE);
+ *      more than BS_NOM_MAX rows or 2^24 ids, judged against `count` before anything is launched: BS_ERR_CAPACITY, nothing changes.
+ *      bs_preempt_nominated_read(count, id_out): the row id per preemptor of the last successful preemption call, 0xFFFFFFFF where the
+ *      slot got no row; BS_ERR_STATE when that call did not carry the flag, BS_ERR_INVALID when count differs from that call's. */
+#define BS_PREEMPT_APPLY    1u   /* write the evictions into the bound table and the node requests */
+#define BS_PREEMPT_ASSUME   2u   /* with APPLY: also add each nominee's request to its node          */
+#define BS_PREEMPT_NOMINATE 4u   /* with APPLY, without ASSUME: append each nominee to the nominated-pod table */
 int bs_preempt_commit(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
                       const uint8_t* group_protected, uint32_t flags, uint32_t victim_cap, const bs_preempt_out* out);
 /* ---- preemption plans that void gangs which miss their quorum ----------------------------------------------------------------
@@ -958,6 +980,45 @@ int bs_preempt_commit_gang(bs_ctx* ctx, uint32_t stages, uint32_t count, const u
                            const uint8_t* group_protected, const uint32_t* gang_need /*[g]*/, uint32_t flags, uint32_t victim_cap,
                            const bs_preempt_out* out);
 int bs_preempt_gang_read(bs_ctx* ctx, uint32_t count, uint8_t* slot_voided /*[count]*/, uint32_t g, uint32_t* group_placed /*[g]*/);
+int bs_preempt_nominated_read(bs_ctx* ctx, uint32_t count, uint32_t* id_out /*[count]*/);
+
+/* ---- the resident nominated-pod table: pods that preempted in an earlier cycle and have not bound yet ---------------------------
+ * What rule N reads.  Nominees are NOT in the node requests: that is the point of the table (BS_PREEMPT_ASSUME puts them there, where
+ * they block preemptors of higher priority too and cannot be told from bound pods).  All calls take flat arguments (the cgo form), are
+ * synchronous and single-rank (BS_ERR_STATE on a sharded or external-reduce context, as bs_preempt_run).
+ *   the table       rows in ascending id; an id is never reused before the next bs_nominated_load.  node: < n.  priority: the nominee's.
+ *                   req[L]: as AddPod counts it and as the wait table stores a row: lanes 0..2 the request, the pods lane 1, a scalar
+ *                   lane the request where the present bit is set, else 0.  req_present: masked to the context's scalar lanes.  At most
+ *                   BS_NOM_MAX live rows; the id space goes up to 2^24.  Rows hold no group index and carry their own copy of the
+ *                   request: bs_groups_list_apply and bs_pods_apply do not concern the table.
+ *   validity        the table remembers the node count it was made for.  While that differs from bs_nodes_count, every call except
+ *                   bs_nominated_load, _count and _ids answers BS_ERR_STATE, and with a non-empty table so do bs_preempt_run,
+ *                   bs_preempt_commit and bs_preempt_commit_gang.  The way through node-list surgery is bs_nominated_read before it, a
+ *                   remap on the host, and bs_nominated_load after it (a remap on the device is not provided).  As for the bound table,
+ *                   the test is one of the COUNT.
+ *   bs_nominated_load   a snapshot; needs nodes loaded (BS_ERR_STATE).  m = 0 is valid and yields the empty table.  ids are 0 .. m - 1.
+ *                   Validated as a whole: m > BS_NOM_MAX is BS_ERR_CAPACITY; a node >= n, or a NULL column with m > 0, BS_ERR_INVALID.
+ *                   Node requests are untouched.
+ *   bs_nominated_count / bs_nominated_ids   rows; the id space.  BS_ERR_STATE before the first bs_nominated_load.
+ *   bs_nominated_read   the rows in table order (ascending id): id[m], node[m], priority[m], req[L][m], req_present[m].  The arrays may
+ *                   be NULL when the table is empty.
+ *   bs_nominated_apply  the n_remove listed ids, which must be live and distinct, leave by a stable compaction; then n_insert rows are
+ *                   appended with ids bs_nominated_ids + k, node[k] and priority[k] from the call, the request lanes and present bits
+ *                   gathered on the device from the resident queue at pod_index[k] (no host copy of rows, as bs_bound_bind).
+ *                   *first_id_out (may be NULL) = the first new id.  Everything is checked on the host before anything is launched; on
+ *                   any error nothing changes.  BS_ERR_INVALID: a remove id that is dead, unknown or repeated, pod_index >= p,
+ *                   node >= n, NULL with a count.  BS_ERR_CAPACITY: more than BS_NOM_MAX rows afterwards, or ids past 2^24 (reload:
+ *                   a load starts a new id space).  BS_ERR_STATE: no table, a stale node count, pods not loaded with n_insert > 0.
+ *                   Both counts 0 is BS_OK and launches nothing.
+ * Out of scope: bs_batch_run and bs_seq_run do not see the table (the queue has no priority column); a caller that wants nominees to
+ * hold their room against the pass keeps BS_PREEMPT_ASSUME.  Filter-aware preemption.  A device remap after node-list surgery. */
+#define BS_NOM_MAX (1u << 16)   /* live rows of the nominated-pod table (its id space: 2^24) */
+int bs_nominated_load(bs_ctx* ctx, uint32_t m, const uint32_t* node, const int32_t* priority, const int64_t* req /*[L][m]*/, const uint32_t* req_present);
+int bs_nominated_count(const bs_ctx* ctx, uint32_t* m_out);
+int bs_nominated_ids(const bs_ctx* ctx, uint32_t* ids_out);
+int bs_nominated_read(bs_ctx* ctx, uint32_t* id, uint32_t* node, int32_t* priority, int64_t* req /*[L][m]*/, uint32_t* req_present);
+int bs_nominated_apply(bs_ctx* ctx, uint32_t n_remove, const uint32_t* remove_id, uint32_t n_insert, const uint32_t* pod_index, const uint32_t* node,
+                       const int32_t* priority, uint32_t* first_id_out);
 /* The live bound table in table order: node ascending, importance order within a node; bs_bound_count entries.  id_out[i] = the
  * entry's id (its index at the last bs_bound_load), node_out[i] = its node.  BS_ERR_STATE before bs_bound_load; the arrays may be NULL
  * when the table is empty. */

@@ -34,7 +34,18 @@ bsa = importlib.import_module("batch-scheduler_amd")
 soa, synth = bsa.soa, bsa.synth
 
 
-def one(config: str, q: int, reps: int, warmup: int, commit: bool = False, apply: bool = False, pdb: float = 0.0) -> dict:
+def load_nominated(ctx, fraction: float, n: int, pods, prio, L: int) -> int:
+    """--nominated: `fraction` of the nodes hold one row of the resident nominated-pod table each (bs_nominated_load); the rows' requests
+    are those of queue pods, their priorities are drawn from the preemptors' (so a row counts for some preemptors and not for others).
+    Returns the row count."""
+    rng = np.random.default_rng(20260921 ^ 0x40B)
+    node = np.nonzero(rng.random(n) < fraction)[0].astype(np.uint32)
+    src = rng.integers(0, pods.p, size=node.size)
+    ctx.nominated_load(node, np.asarray(prio)[rng.integers(0, len(prio), size=node.size)], pods.req[:L, src], pods.req_present[src])
+    return int(node.size)
+
+
+def one(config: str, q: int, reps: int, warmup: int, commit: bool = False, apply: bool = False, pdb: float = 0.0, nominated: float = 0.0) -> dict:
     cfg = synth.CONFIGS[config]
     n, S = cfg["nodes"], cfg["scalars"]
     bound, nodes = synth.make_bound(20260921, n, cfg["groups"], (20, 110), S)
@@ -52,6 +63,7 @@ def one(config: str, q: int, reps: int, warmup: int, commit: bool = False, apply
         ctx.load_bound(bound)
         if bits is not None:
             ctx.bound_pdb_set(bits)
+        rows = load_nominated(ctx, nominated, n, pods, prio, 4 + S) if nominated > 0 else 0
         def call():
             if not commit:
                 return ctx.preempt(pidx, prio, prot, victim_cap=16)
@@ -74,6 +86,8 @@ def one(config: str, q: int, reps: int, warmup: int, commit: bool = False, apply
         row.update(pdb=pdb, pdb_violations=int(r["n_pdb_violations"].sum()))
     if commit:
         row.update(flags="APPLY" if apply else "0", evicted=int(r["n_victims"].sum()))
+    if nominated > 0:
+        row.update(nominated=nominated, nominated_rows=rows)
     return row
 
 
@@ -341,7 +355,7 @@ def pdb_resident_rows(config: str, reps: int, warmup: int, host_reps: int = 2) -
                  pdb_set_over_allowed_apply=round(med(t_set) / med(t_apply), 2))]
 
 
-def gang_rows(config: str, q: int, fraction: float, reps: int, warmup: int) -> list:
+def gang_rows(config: str, q: int, fraction: float, reps: int, warmup: int, nominated: float = 0.0) -> list:
     capi = bsa.capi
     cfg = synth.CONFIGS[config]
     n, S = cfg["nodes"], cfg["scalars"]
@@ -364,6 +378,7 @@ def gang_rows(config: str, q: int, fraction: float, reps: int, warmup: int) -> l
         ctx.load_groups(groups)
         ctx.load_pods(pods)
         ctx.load_bound(bound)
+        nom_rows = load_nominated(ctx, nominated, n, pods, prio, 4 + S) if nominated > 0 else 0
         # what each gang places when every run stands; a share of the gangs that place something then ask for one more than that
         one_each = np.zeros(cfg["groups"], np.uint32)
         one_each[np.unique(grp[grp >= 0])] = 1
@@ -394,7 +409,8 @@ def gang_rows(config: str, q: int, fraction: float, reps: int, warmup: int) -> l
     plain, g0, g1 = float(np.median(five)), float(np.median(ts["gang0"])), float(np.median(ts["gang"]))
     return [dict(config=config, nodes=n, bound=int(bound.b), preemptors=q, runs=runs, missed_runs=missed, voided_slots=voided, fraction=fraction,
                  plain_ms=round(plain, 4), plain_five=[round(x, 4) for x in five], plain_spread_ms=round(max(five) - min(five), 4),
-                 gang_need0_ms=round(g0, 4), gang_ms=round(g1, 4), need0_over_plain=round(g0 / plain, 4), gang_over_plain=round(g1 / plain, 4))]
+                 gang_need0_ms=round(g0, 4), gang_ms=round(g1, 4), need0_over_plain=round(g0 / plain, 4), gang_over_plain=round(g1 / plain, 4),
+                 **(dict(nominated=nominated, nominated_rows=nom_rows) if nominated > 0 else {}))]
 
 
 def main():
@@ -410,9 +426,11 @@ def main():
     ap.add_argument("--pdb-resident", action="store_true", help="bs_pdb_allowed_apply of 8 indices, vs pdb.violating_bits + bs_bound_pdb_set")
     ap.add_argument("--gang", type=float, default=None, metavar="FRACTION", help="bs_preempt_commit_gang on cfg3 (need 0, and FRACTION of the runs missing "
                     "their quorum) beside bs_preempt_commit")
+    ap.add_argument("--nominated", type=float, default=0.0, metavar="FRACTION", help="share of the nodes that hold one row of the nominated-pod table "
+                    "(priorities drawn from the preemptors'); with the default scene, --commit and --gang")
     a = ap.parse_args()
     if a.gang is not None:
-        rows = [r for q in (64, 1024) for r in gang_rows("cfg3", q, a.gang, a.reps, a.warmup)]
+        rows = [r for q in (64, 1024) for r in gang_rows("cfg3", q, a.gang, a.reps, a.warmup, a.nominated)]
         print(json.dumps(dict(metric="bs_preempt_commit_gang ms per call", rows=rows)))
         return
     if a.pdb_resident:
@@ -432,10 +450,10 @@ def main():
         print(json.dumps(dict(metric="bs_bound_apply ms per call", rows=rows)))
         return
     if a.commit:
-        rows = [one(c, q, a.reps, a.warmup, True, ap_, a.pdb) for c in ("cfg3", "cfg4") for q in (64, 1024) for ap_ in (False, True)]
+        rows = [one(c, q, a.reps, a.warmup, True, ap_, a.pdb, a.nominated) for c in ("cfg3", "cfg4") for q in (64, 1024) for ap_ in (False, True)]
         print(json.dumps(dict(metric="bs_preempt_commit ms per call", rows=rows)))
         return
-    rows = [one(c, q, a.reps, a.warmup, pdb=a.pdb) for c in ("cfg3", "cfg4") for q in (64, 1024)]
+    rows = [one(c, q, a.reps, a.warmup, pdb=a.pdb, nominated=a.nominated) for c in ("cfg3", "cfg4") for q in (64, 1024)]
     print(json.dumps(dict(metric="bs_preempt_run ms per call", rows=rows)))
 
 
