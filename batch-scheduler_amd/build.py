@@ -6,6 +6,7 @@ fallback: if hipcc is missing or the build fails this raises.
 from __future__ import annotations
 
 import os
+import re
 import shutil
 import subprocess
 
@@ -16,46 +17,33 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.environ.get("BS_LIB_DIR") or HERE
 PREBUILT_ONLY = bool(os.environ.get("BS_LIB_DIR"))
 LIB_PATH = os.path.join(LIB_DIR, "libbsched.so")
-# NOTE: UNITS / SOURCES below are the FIRST FIVE units only, not "what is built": later units sit in LATER_UNITS and LIST_UNITS further down, and
-# everything that builds, links or tests staleness goes by LINK_UNITS / LINK_SOURCES.
-# translation units -> the headers each one depends on, transitively (tests/test_build_units_cpu.py follows the #includes; DESIGN.md section 4 "Build")
-_COMMON = ["bs_common.hpp", "bs_kernels.hpp", "bs_nodew_layout.hpp", "bs_lanes.hpp", os.path.join("..", "..", "include", "bsched.h")]
-_CTX = _COMMON + ["bs_ctx.hpp", "bs_carve.hpp", "bs_layouts.hpp", "bs_hostmem.hpp", "bs_pod_ranges.hpp"]      # the units that hold entry points
-_FAST = ["bs_launch.hpp", "bs_fast.hpp", "bs_filter_t.hpp"]
-_SEQ = _CTX + ["bs_seq.hpp"]
-UNITS = {
-    "bsched.hip": _CTX + _FAST + ["bs_epoch.hpp", "bs_queue.hpp", "bs_fdeny.hpp", "bs_sort.hpp", "bs_fit.hpp"],
-    "tu_fast.hip": _COMMON + _FAST,
-    "tu_seq.hip": _SEQ,
-    "tu_seq_expire.hip": _SEQ + ["bs_seq_expire.hpp", "bs_seq_expire_list.hpp"],
-    "tu_preempt.hip": _CTX + ["bs_preempt.hpp", "bs_preempt_commit.hpp", "bs_preempt_commit_gang.hpp", "bs_preempt_gang_runs.hpp", "bs_preempt_geom.hpp", "bs_bound_apply.hpp",
-                              "bs_bound_nodes.hpp", "bs_bound_nodes_replay.hpp", "bs_pdb.hpp", "bs_nominated.hpp", "bs_nominated_check.hpp"],
-}
-SOURCES = list(UNITS)
-# the units that came after those five, kept in a table of their own: tests/test_build_units_cpu.py holds UNITS and SOURCES to exactly the five
-# above, tests/test_wait_cpu.py holds this table to the include graph in the same way.
-LATER_UNITS = {
-    "tu_wait.hip": _SEQ + ["bs_wait.hpp", "bs_wait_list.hpp", "bs_bound_nodes_replay.hpp"],
-}
-ALL_UNITS = {**UNITS, **LATER_UNITS}
-ALL_SOURCES = list(ALL_UNITS)
-# ... and the seventh: tests/test_wait_cpu.py holds LATER_UNITS and ALL_SOURCES to the six names above in turn, so group-list surgery has a
-# table of its own again (tests/test_groups_list_cpu.py holds it to the include graph).  What is compiled, linked and tested for staleness is
-# BUILD_UNITS / BUILD_SOURCES.
-LIST_UNITS = {
-    "tu_groups.hip": _CTX + ["bs_groups_list.hpp", "bs_groups_list_check.hpp"],
-}
-BUILD_UNITS = {**ALL_UNITS, **LIST_UNITS}
-BUILD_SOURCES = list(BUILD_UNITS)
-# ... and the eighth: tests/test_groups_list_cpu.py holds BUILD_SOURCES to the seven names above, so bs_bound_bind's unit has a table of its
-# own (tests/test_bound_bind_cpu.py holds it to the include graph).  What is compiled, linked and tested for staleness is LINK_UNITS /
-# LINK_SOURCES.
-BIND_UNITS = {
-    "tu_bind.hip": _CTX + ["bs_bound_bind.hpp", "bs_bound_bind_check.hpp", "bs_bound_apply.hpp", "bs_preempt_commit.hpp", "bs_preempt.hpp"],
-}
-LINK_UNITS = {**BUILD_UNITS, **BIND_UNITS}
-LINK_SOURCES = list(LINK_UNITS)
-HEADERS = sorted({h for hs in LINK_UNITS.values() for h in hs})
+# The translation units, bsched.hip first (under -DBS_UNITY it includes the others, in this order).  A new unit is one more name here.
+SOURCES = ["bsched.hip", "tu_fast.hip", "tu_seq.hip", "tu_seq_expire.hip", "tu_wait.hip", "tu_groups.hip", "tu_bound.hip", "tu_nominated.hip",
+           "tu_preempt.hip", "tu_bind.hip"]
+_INCLUDE = re.compile(r'^\s*#\s*include\s*"([^"]+)"', re.M)
+
+
+def closure(unit: str) -> set[str]:
+    """Every header `unit` reaches through quoted #includes, transitively, as normalised paths relative to csrc/.  Includes inside #if
+    blocks count too (more than a build may read: the safe side for staleness); the .hip includes exist under BS_UNITY only."""
+    seen, todo = set(), [unit]
+    while todo:
+        here = todo.pop()
+        with open(os.path.join(CSRC, here)) as f:
+            text = f.read()
+        for inc in _INCLUDE.findall(text):
+            if inc.endswith(".hip"):
+                continue
+            rel = os.path.normpath(os.path.join(os.path.dirname(here), inc))
+            if rel not in seen:
+                seen.add(rel)
+                todo.append(rel)
+    return seen
+
+
+# unit -> the headers it is recompiled for, read from the sources (DESIGN.md section 4 "Build")
+UNITS = {src: sorted(closure(src)) for src in SOURCES}
+HEADERS = sorted({h for hs in UNITS.values() for h in hs})
 OBJ_DIR = os.path.join(HERE, "build")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]
@@ -98,7 +86,7 @@ def is_stale() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, f) for f in LINK_SOURCES + HEADERS]
+    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -111,7 +99,7 @@ def _unit_stale(src: str) -> bool:
     if not os.path.exists(o):
         return True
     t = os.path.getmtime(o)
-    return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in [src] + LINK_UNITS[src])
+    return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in [src] + UNITS[src])
 
 
 def build(force: bool = False, verbose: bool = False, extra_flags: list[str] | None = None, unity: bool = False) -> str:
@@ -132,11 +120,11 @@ def build(force: bool = False, verbose: bool = False, extra_flags: list[str] | N
         res = subprocess.run(cmd, capture_output=True, text=True)
         if res.returncode != 0:
             raise RuntimeError("hipcc failed:\n" + res.stdout + res.stderr)
-        for src in LINK_SOURCES:                                 # the objects no longer match the library
+        for src in SOURCES:                                 # the objects no longer match the library
             if os.path.exists(_obj(src)):
                 os.remove(_obj(src))
         return LIB_PATH
-    todo = [src for src in LINK_SOURCES if force or extra_flags or _unit_stale(src)]
+    todo = [src for src in SOURCES if force or extra_flags or _unit_stale(src)]
     procs = []
     for src in todo:
         cmd = [hipcc(), *FLAGS, *(extra_flags or []), "-c", "-o", _obj(src), os.path.join(CSRC, src)]
@@ -156,7 +144,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags: list[str] | N
                 os.remove(_obj(src))
         raise RuntimeError("hipcc failed:\n" + "\n".join(failed))
     tmp = f"{LIB_PATH}.{os.getpid()}.tmp"
-    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp, *[_obj(src) for src in LINK_SOURCES], "-ldl"]
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp, *[_obj(src) for src in SOURCES], "-ldl"]
     if verbose:
         print(" ".join(cmd))
     res = subprocess.run(cmd, capture_output=True, text=True)
@@ -164,7 +152,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags: list[str] | N
         raise RuntimeError("link failed:\n" + res.stdout + res.stderr)
     os.replace(tmp, LIB_PATH)
     if extra_flags:
-        for src in LINK_SOURCES:                                 # objects of an experiment build must not be taken for the shipped ones
+        for src in SOURCES:                                 # objects of an experiment build must not be taken for the shipped ones
             os.remove(_obj(src))
     return LIB_PATH
 

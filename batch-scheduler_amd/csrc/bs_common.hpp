@@ -10,16 +10,16 @@
 #include "../../include/bsched.h"
 
 // Which translation unit emits the NON-template kernels of the shared headers (a template kernel is emitted where it is instantiated):
-// bsched.hip (BS_TU_MAIN) everything but the two Filter kernels tu_fast.hip launches; tu_fast.hip (BS_TU_FAST) those two; tu_seq.hip,
-// tu_seq_expire.hip (BS_TU_SEQ) and tu_preempt.hip (BS_TU_PREEMPT) none: their entry points reach k_nodes_assume / k_nodes_derive through bsched.hip's
+// bsched.hip (BS_TU_MAIN) everything but the two Filter kernels tu_fast.hip launches; tu_fast.hip (BS_TU_FAST) those two; every other unit
+// (BS_TU_FAMILY: a kernel family with its entry points) none: its entry points reach k_nodes_assume / k_nodes_derive through bsched.hip's
 // helpers (bs_ctx.hpp); a unity build (-DBS_UNITY: none of the macros) all of them.  A family header's own non-template kernels (bs_seq_expire.hpp,
-// bs_pdb.hpp) need no switch: one unit includes the header.
-#if defined(BS_TU_FAST) || defined(BS_TU_SEQ) || defined(BS_TU_PREEMPT)
+// bs_pdb.hpp, bs_nominated.hpp) need no switch: one unit includes the header.
+#if defined(BS_TU_FAST) || defined(BS_TU_FAMILY)
 #define BS_EMIT_MAIN 0
 #else
 #define BS_EMIT_MAIN 1
 #endif
-#if defined(BS_TU_MAIN) || defined(BS_TU_SEQ) || defined(BS_TU_PREEMPT)
+#if defined(BS_TU_MAIN) || defined(BS_TU_FAMILY)
 #define BS_EMIT_FAST 0
 #else
 #define BS_EMIT_FAST 1

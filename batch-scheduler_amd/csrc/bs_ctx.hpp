@@ -1,6 +1,6 @@
 // bs_ctx.hpp — the context behind the C ABI of include/bsched.h, and what the translation units that implement that ABI share: bsched.hip
-// (contexts, loads, the batch) and the family units tu_seq.hip, tu_seq_expire.hip, tu_preempt.hip, tu_wait.hip, tu_groups.hip and tu_bind.hip
-// (their entry points beside their kernels).
+// (contexts, loads, the batch) and the family units, every other tu_*.hip but tu_fast.hip (their entry points beside their kernels; what one
+// family unit offers another is declared below, under the unit that defines it).
 // Host code only: no kernel, and no header of a kernel family (the field types come from bs_kernels.hpp and the plain host headers).
 #pragma once
 #include <rccl/rccl.h>   // types and enums only: librccl itself is dlopen'ed on demand (hosts without RCCL can still load the library)
@@ -95,7 +95,7 @@ int wait_bind_back(bs_ctx* c, const WaitBind& wb);
 void wait_bind_waited(bs_ctx* c, const WaitBind& wb);
 int wait_bind_verdict(bs_ctx* c, const char* who, const WaitBind& wb, const uint32_t info[4]);
 void wait_bind_commit(bs_ctx* c, const WaitBind& wb, const uint32_t info[4]);
-// Defined in tu_preempt.hip: the back half of every patch of the bound table, for a delta block that is on the device already.  `a` names the
+// Defined in tu_bound.hip: the back half of every patch of the bound table, for a delta block that is on the device already.  `a` names the
 // delta (remove ids, the inserts sorted by (node, importance)) and the scratch in d_pre; the call sizes the second allocation for
 // b - n_remove + n_insert entries, points `a` at the live table, launches k_ba_scatter .. k_ba_merge, waits once, judges the error word
 // and swaps the allocations (table, entry count, id space + n_insert, the group maximum).  hooks (NULL: none): before_wait enqueues the
@@ -108,6 +108,23 @@ struct BoundBlockHooks {
 };
 int bound_apply_block(bs_ctx* c, const char* who, BoundApplyDev& a, int32_t gmax, const BoundBlockHooks* hooks = nullptr);
 int32_t* bound_group_column(const bs_ctx* c);   // the live table's group column ([bound_b] entries)
+// Defined in tu_bound.hip: how the table's two allocations trade places, for every call that rewrites the table (the patch above, the plans'
+// compaction in tu_preempt.hip, bs_bound_nodes_apply).  bound_twin lays the second allocation out for b entries on n nodes (`lay`) and makes
+// room for them: exactly, or with a quarter of headroom whenever it has to grow; with `nw`, that struct names the second allocation's columns
+// as a compaction target.  bound_swap, after the wait: the second allocation becomes the table (pointer, capacity, layout, entry count).
+struct CompactDev;
+hipError_t bound_twin(bs_ctx* c, uint32_t n, uint32_t b, bool headroom, BoundLayout& lay, CompactDev* nw = nullptr);
+void bound_swap(bs_ctx* c, const BoundLayout& lay, uint32_t b);
+// Defined in tu_nominated.hip: what the preemption calls use the nominated-pod table through.  nom_view: what the victim search reads (null
+// without a table or without rows); nom_state: BS_OK, or why the table cannot be patched now; nom_preempt_state: BS_OK, or the refusal of
+// rows made for another node count; nom_refusal: a check code of bs_nominated_check.hpp as last_error and status; nom_apply_rows:
+// bs_nominated_apply behind its checks (BS_PREEMPT_NOMINATE's append).
+struct NomView;
+const NomView* nom_view(const bs_ctx* c);
+int nom_state(bs_ctx* c, const char* who);
+int nom_preempt_state(bs_ctx* c, const char* who);
+int nom_refusal(bs_ctx* c, const char* who, int bad);
+int nom_apply_rows(bs_ctx* c, uint32_t R, const uint32_t* remove_id, uint32_t I, const uint32_t* pod_index, const uint32_t* node, const int32_t* priority);
 
 }  // namespace bs
 

@@ -1,6 +1,6 @@
 // bs_launch.hpp — what bsched.hip calls across translation units: the launch wrappers and residency queries of the steady-state chain's
 // second launch, which live beside their kernels in tu_fast.hip so that the library builds in parallel and a change to that family recompiles
-// that unit only (tu_seq.hip, tu_seq_expire.hip and tu_preempt.hip hold their entry points themselves: their wrappers are file-local).
+// that unit only (the family units hold their entry points themselves: their wrappers are file-local).
 // Kernels in the shared headers are `inline __global__`: each translation unit emits exactly the kernels it launches.
 // A wrapper picks the instantiation for the context's scalar-lane count by one of the three rules of bs_lanes.hpp.
 #pragma once

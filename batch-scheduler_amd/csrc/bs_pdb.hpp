@@ -10,7 +10,7 @@
 //                  ORing allowed[m] <= 0 (signed).  One byte store per lane, coalesced across the wave; the step's ballot is counted, and
 //                  lane 0 stores the node's violating count.  A node with an empty list stores a zero count.  Only live entries are
 //                  visited: the walk goes through the table, so the rows of dead ids are never read.
-// Neither kernel depends on the scalar-lane count, so they are no templates: tu_preempt.hip alone emits them (a unity build includes it).
+// Neither kernel depends on the scalar-lane count, so they are no templates: tu_bound.hip alone emits them (a unity build includes it).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,6 +1,8 @@
 // bsched.hip — C ABI of include/bsched.h on top of the gfx950 kernels in bs_kernels.hpp: contexts, loads, the batch and the single queries
-// (the pod-by-pod pass, the Permit timeout and the bound-pod table / preemption calls sit beside their kernels in tu_seq.hip,
-// tu_seq_expire.hip and tu_preempt.hip; bs_ctx.hpp is what the four share).  Host responsibilities only: device memory, one HIP stream, launch
+// (every other call sits beside its kernels in a family unit: the pod-by-pod pass in tu_seq.hip, the Permit timeout in tu_seq_expire.hip, the
+// wait table in tu_wait.hip, group-list surgery in tu_groups.hip, the bound-pod table and its PDB column in tu_bound.hip, the nominated-pod
+// table in tu_nominated.hip, preemption in tu_preempt.hip, bs_bound_bind in tu_bind.hip; bs_ctx.hpp is what they share; tu_fast.hip holds the
+// two Filter kernels of the batch).  Host responsibilities only: device memory, one HIP stream, launch
 // geometry, event timing, H2D/D2H staging.  Every decision is computed on the GPU; there is no CPU evaluation path here
 // (the CPU restatement lives in oracle/ and is test infrastructure).
 #include <dlfcn.h>
@@ -31,6 +33,8 @@
 #include "tu_seq_expire.hip"
 #include "tu_wait.hip"
 #include "tu_groups.hip"
+#include "tu_bound.hip"
+#include "tu_nominated.hip"
 #include "tu_preempt.hip"
 #include "tu_bind.hip"
 #endif

@@ -1,9 +1,9 @@
 // tu_bind.hip — translation unit of bs_bound_bind (include/bsched.h): the kernels of bs_bound_bind.hpp (k_bb_*, once per scalar-lane count
 // 0..BS_MAX_SCALARS), their file-local launch wrappers and the entry point.  The wait core's launches stay in tu_wait.hip (wait_bind_*), the
-// bound table's merge chain and its swap in tu_preempt.hip (bound_apply_block): this unit emits no k_wt_* and no k_ba_* kernel.
-// Like tu_seq.hip it emits none of the shared headers' non-template kernels (BS_TU_SEQ, bs_common.hpp).
+// bound table's merge chain and its swap in tu_bound.hip (bound_apply_block): this unit emits no k_wt_* and no k_ba_* kernel.
+// A family unit: it emits none of the shared headers' non-template kernels (BS_TU_FAMILY, bs_common.hpp).
 #ifndef BS_UNITY
-#define BS_TU_SEQ
+#define BS_TU_FAMILY
 #endif
 #include "bs_bound_bind.hpp"
 #include "bs_bound_bind_check.hpp"

@@ -1,9 +1,9 @@
 // tu_groups.hip — translation unit of group-list surgery (bs_groups_list.hpp: k_gl_gather once per scalar-lane count 0..BS_MAX_SCALARS,
 // k_gl_remap), its file-local launch wrappers and the entry points bs_groups_list_apply[_flat] (include/bsched.h).  A unit of its own for
 // tu_wait.hip's reason: code added to a unit has changed k_seq_pass's instructions before.
-// Like tu_seq.hip it emits none of the shared headers' non-template kernels (BS_TU_SEQ, bs_common.hpp).
+// A family unit: it emits none of the shared headers' non-template kernels (BS_TU_FAMILY, bs_common.hpp).
 #ifndef BS_UNITY
-#define BS_TU_SEQ
+#define BS_TU_FAMILY
 #endif
 #include <cstring>
 

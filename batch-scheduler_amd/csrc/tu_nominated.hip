@@ -1,0 +1,261 @@
+// tu_nominated.hip — translation unit of the resident nominated-pod table: pods nominated by earlier cycles, counted by every fit test of the
+// victim search.  Kernels (bs_nominated.hpp): k_nm_mark and k_nm_chains (no templates: this unit alone includes that header), k_nm_move<S> and
+// k_nm_gather<S>, once per scalar-lane count 0..BS_MAX_SCALARS.  Host: the table's layout, its file-local launch wrappers, the entry points
+// bs_nominated_* (include/bsched.h), and what the preemption calls of tu_preempt.hip use the table through (bs_ctx.hpp): nom_view, nom_state,
+// nom_preempt_state, nom_refusal, nom_apply_rows.
+#ifndef BS_UNITY
+#define BS_TU_FAMILY
+#endif
+#include "bs_nominated.hpp"
+#include "bs_nominated_check.hpp"
+#include "bs_ctx.hpp"
+
+#include <cstring>
+#include <iterator>
+
+namespace {
+
+// the table's one allocation for `cap` rows on n nodes: columns at 256-byte offsets, req lane stride max(cap, 1)
+struct NomLayout {
+  Piece<uint32_t> id, node;
+  Piece<int32_t> prio;
+  Piece<uint32_t> pres;
+  Piece<int64_t> req;
+  Piece<uint32_t> nhead, nnext;
+  Piece<NomView> view;                 // what the victim search reads, written with the chains
+  size_t bytes = 0;
+  uint32_t stride = 1;
+};
+NomLayout nom_layout(uint32_t cap, uint32_t n, uint32_t L) {
+  const size_t rows = std::max<uint32_t>(cap, 1);
+  NomLayout l;
+  Carve cv;
+  l.id = cv.take<uint32_t>(rows);
+  l.node = cv.take<uint32_t>(rows);
+  l.prio = cv.take<int32_t>(rows);
+  l.pres = cv.take<uint32_t>(rows);
+  l.req = cv.take<int64_t>(rows * L);
+  l.nhead = cv.take<uint32_t>(std::max<uint32_t>(n, 1));
+  l.nnext = cv.take<uint32_t>(rows);
+  l.view = cv.take<NomView>(1);
+  l.bytes = cv.mark();
+  l.stride = (uint32_t)rows;
+  return l;
+}
+NomTab nom_tab(const bs_ctx* c, uint32_t which) {
+  const NomLayout l = nom_layout(c->nom_cap[which], c->nom_ncap[which], c->L);
+  void* b = c->d_nom[which].p;
+  return NomTab{l.id.in(b), l.node.in(b), l.prio.in(b), l.pres.in(b), l.req.in(b), l.nhead.in(b), l.nnext.in(b), l.stride};
+}
+// allocation `which` is laid out for at least `rows` rows on the context's nodes afterwards (a quarter of headroom, as the wait table);
+// what it held is lost when the layout changes
+hipError_t nom_reserve(bs_ctx* c, uint32_t which, uint32_t rows) {
+  if (c->d_nom[which].p && c->nom_cap[which] >= rows && c->nom_ncap[which] == c->N) return hipSuccess;
+  const uint32_t cap = std::max<uint32_t>(rows + rows / 4, 256);
+  const hipError_t e = c->d_nom[which].reserve(nom_layout(cap, c->N, c->L).bytes);
+  if (e == hipSuccess) { c->nom_cap[which] = cap; c->nom_ncap[which] = c->N; }
+  return e;
+}
+// the chains of allocation `which` over `rows` rows: nhead filled with kNmNone, then k_nm_chains, which also writes the view of that table
+// (a table without rows has no view: nom_view answers null for it)
+hipError_t launch_nom_chains(bs_ctx* c, uint32_t which, uint32_t rows) {
+  const NomTab t = nom_tab(c, which);
+  NomView* dv = nom_layout(c->nom_cap[which], c->nom_ncap[which], c->L).view.in(c->d_nom[which].p);
+  const hipError_t e = hipMemsetAsync(t.nhead, 0xff, (size_t)std::max<uint32_t>(c->N, 1) * 4, c->stream);
+  if (e == hipSuccess && rows) hipLaunchKernelGGL(k_nm_chains, dim3(cdiv(rows, 256)), dim3(256), 0, c->stream, t, dv, rows, c->N);
+  return e;
+}
+// k_nm_mark -> k_nm_move<S> (one workgroup) -> k_nm_gather<S>; the chains follow (launch_nom_chains)
+void launch_nom_apply(hipStream_t stream, uint32_t S, const NomDev& a, const PodsDev& pd) {
+  if (a.n_remove) hipLaunchKernelGGL(k_nm_mark, dim3(cdiv(a.n_remove, 256)), dim3(256), 0, stream, a);
+  lanes_wide(S, [&](auto s) {
+    constexpr int V = decltype(s)::value;
+    if (a.W) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nm_move<V>), dim3(1), dim3(kNmWindow), 0, stream, a);
+    if (a.n_insert) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nm_gather<V>), dim3(cdiv(a.n_insert, 256)), dim3(256), 0, stream, a, pd);
+  });
+}
+int nom_single_rank(bs_ctx* c, const char* who) {
+  if (c->nranks > 1 || c->reduce_external) { c->last_error = std::string(who) + " is single-rank only (as bs_preempt_run)"; return BS_ERR_STATE; }
+  return BS_OK;
+}
+
+}  // namespace
+
+// what the victim search reads: null without a table or without rows (the callers have refused a stale table that holds rows)
+const NomView* bs::nom_view(const bs_ctx* c) {
+  if (!c->have_nom || c->nom_w == 0) return nullptr;
+  const uint32_t cur = c->nom_cur;
+  return nom_layout(c->nom_cap[cur], c->nom_ncap[cur], c->L).view.in((const void*)c->d_nom[cur].p);
+}
+// the table exists and was made for the node count the context holds now
+int bs::nom_state(bs_ctx* c, const char* who) {
+  if (const int rc = nom_single_rank(c, who)) return rc;
+  if (!c->have_nom) { c->last_error = std::string(who) + ": no nominated-pod table (bs_nominated_load first; m = 0 gives the empty one)"; return BS_ERR_STATE; }
+  if (!c->have_nodes || c->nom_n != c->N) {
+    c->last_error = std::string(who) + ": the nominated-pod table was made for another node count (bs_nominated_read before the surgery, a remap on the host, bs_nominated_load)";
+    return BS_ERR_STATE;
+  }
+  return BS_OK;
+}
+// what the three preemption calls refuse: rows of a table that was made for another node count
+int bs::nom_preempt_state(bs_ctx* c, const char* who) {
+  if (c->have_nom && c->nom_w && c->nom_n != c->N) {
+    c->last_error = std::string(who) + ": the nominated-pod table holds rows and was made for another node count: reload it";
+    return BS_ERR_STATE;
+  }
+  return BS_OK;
+}
+int bs::nom_refusal(bs_ctx* c, const char* who, int bad) {
+  c->last_error = std::string(who) + ": " + nom_check_text(bad);
+  return nom_check_is_capacity(bad) ? BS_ERR_CAPACITY : BS_ERR_INVALID;
+}
+// bs_nominated_apply behind its checks (and BS_PREEMPT_NOMINATE's append): the listed rows leave by the stable compaction into the twin,
+// the inserts are gathered from the resident queue behind the survivors, the chains are rebuilt, the twin becomes the table.  One wait.
+int bs::nom_apply_rows(bs_ctx* c, uint32_t R, const uint32_t* remove_id, uint32_t I, const uint32_t* pod_index, const uint32_t* node,
+                       const int32_t* priority) {
+  const uint32_t W = c->nom_w, W2 = W - R, W3 = W2 + I, cur = c->nom_cur, other = cur ^ 1u, ids = c->nom_ids;
+  HIPCHK(c, hipStreamSynchronize(c->stream));               // (nothing of an earlier call still reads the twin)
+  HIPCHK(c, nom_reserve(c, other, W3));
+  const size_t nR = R, nI = I;
+  Carve cv;
+  const auto o_rem = cv.take<uint32_t>(nR, 4);              // (packed: one H2D)
+  const auto o_pod = cv.take<uint32_t>(nI, 4);
+  const auto o_node = cv.take<uint32_t>(nI, 4);
+  const auto o_prio = cv.take<int32_t>(nI, 4);
+  const size_t blob_bytes = cv.mark();
+  const auto o_flag = cv.take<uint8_t>(std::max<uint32_t>(W, 1));
+  if (cv.mark() > c->d_pre.cap) HIPCHK(c, c->d_pre.reserve(cv.mark() + cv.mark() / 4));
+  std::vector<uint8_t> h(std::max<size_t>(blob_bytes, 1), 0);
+  if (R) std::memcpy(o_rem.in(h.data()), remove_id, o_rem.bytes());
+  if (I) {
+    std::memcpy(o_pod.in(h.data()), pod_index, o_pod.bytes());
+    std::memcpy(o_node.in(h.data()), node, o_node.bytes());
+    std::memcpy(o_prio.in(h.data()), priority, o_prio.bytes());
+  }
+  uint8_t* base = c->d_pre.as<uint8_t>();
+  HIPCHK(c, hipMemcpyAsync(base, h.data(), h.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(o_flag.in(base), 0, o_flag.bytes(), c->stream));
+  NomDev a{};
+  a.src = nom_tab(c, cur);
+  a.dst = nom_tab(c, other);
+  a.W = W; a.W2 = W2; a.N = c->N;
+  a.rem = o_rem.in(base);
+  a.n_remove = R;
+  a.ipod = o_pod.in(base);
+  a.inode = o_node.in(base);
+  a.iprio = o_prio.in(base);
+  a.n_insert = I;
+  a.ids = ids;
+  a.flag = o_flag.in(base);
+  launch_nom_apply(c->stream, c->S, a, pods_dev(c));
+  HIPCHK(c, launch_nom_chains(c, other, W3));
+  LAUNCHCHK(c, BS_KERNEL_PREPASS);
+  HIPCHK(c, hipStreamSynchronize(c->stream));               // (h is a local buffer)
+  if (R) {
+    std::vector<uint32_t> gone(remove_id, remove_id + R), left;
+    std::sort(gone.begin(), gone.end());
+    left.reserve(W3);
+    std::set_difference(c->nom_live.begin(), c->nom_live.end(), gone.begin(), gone.end(), std::back_inserter(left));
+    c->nom_live.swap(left);
+  }
+  for (uint32_t k = 0; k < I; ++k) c->nom_live.push_back(ids + k);
+  c->nom_cur = other;
+  c->nom_w = W3;
+  c->nom_ids = ids + I;
+  return BS_OK;
+}
+
+extern "C" {
+int bs_nominated_load(bs_ctx* c, uint32_t m, const uint32_t* node, const int32_t* priority, const int64_t* req, const uint32_t* req_present) {
+  if (!c) return BS_ERR_INVALID;
+  int rc = nom_single_rank(c, "bs_nominated_load");
+  if (rc) return rc;
+  if (!c->have_nodes) { c->last_error = "bs_nominated_load before bs_nodes_load"; return BS_ERR_STATE; }
+  if (const int bad = nom_load_check(c->N, m, node, priority, req, req_present, BS_NOM_MAX)) return nom_refusal(c, "bs_nominated_load", bad);
+  if ((rc = use_device(c))) return rc;
+  const uint32_t L = c->L, other = c->nom_cur ^ 1u;
+  HIPCHK(c, hipStreamSynchronize(c->stream));               // (nothing of an earlier call still reads the twin)
+  HIPCHK(c, nom_reserve(c, other, m));
+  const NomLayout l = nom_layout(c->nom_cap[other], c->nom_ncap[other], L);
+  if (m) {
+    // the columns as the table stores them: ids 0 .. m - 1, the pods lane 1, a scalar lane without a present bit 0
+    std::vector<uint8_t> st(l.nhead.off);                   // (the chains are made on the device)
+    const uint32_t smask = c->S ? (uint32_t)((1ull << c->S) - 1ull) : 0u;
+    for (uint32_t i = 0; i < m; ++i) {
+      l.id.in(st.data())[i] = i;
+      l.node.in(st.data())[i] = node[i];
+      l.prio.in(st.data())[i] = priority[i];
+      l.pres.in(st.data())[i] = req_present[i] & smask;
+    }
+    for (uint32_t j = 0; j < L; ++j)
+      for (uint32_t i = 0; i < m; ++i) {
+        int64_t v = req[(size_t)j * m + i];
+        if (j == BS_LANE_PODS) v = 1;
+        else if (j >= BS_FIXED_LANES && !((req_present[i] & smask) >> (j - BS_FIXED_LANES) & 1u)) v = 0;
+        l.req.in(st.data())[(size_t)j * l.stride + i] = v;
+      }
+    HIPCHK(c, hipMemcpyAsync(c->d_nom[other].p, st.data(), st.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_nom_chains(c, other, m));
+    LAUNCHCHK(c, BS_KERNEL_PREPASS);
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // (st is a local buffer)
+  }
+  c->nom_cur = other;
+  c->have_nom = true;
+  c->nom_w = c->nom_ids = m;
+  c->nom_n = c->N;
+  c->nom_live.resize(m);
+  for (uint32_t i = 0; i < m; ++i) c->nom_live[i] = i;
+  return BS_OK;
+}
+
+int bs_nominated_count(const bs_ctx* c, uint32_t* m_out) {
+  if (!c || !m_out) return BS_ERR_INVALID;
+  if (!c->have_nom) return BS_ERR_STATE;
+  *m_out = c->nom_w;
+  return BS_OK;
+}
+
+int bs_nominated_ids(const bs_ctx* c, uint32_t* ids_out) {
+  if (!c || !ids_out) return BS_ERR_INVALID;
+  if (!c->have_nom) return BS_ERR_STATE;
+  *ids_out = c->nom_ids;
+  return BS_OK;
+}
+
+int bs_nominated_read(bs_ctx* c, uint32_t* id, uint32_t* node, int32_t* priority, int64_t* req, uint32_t* req_present) {
+  if (!c) return BS_ERR_INVALID;
+  int rc = nom_state(c, "bs_nominated_read");
+  if (rc) return rc;
+  const uint32_t W = c->nom_w;
+  if (W && (!id || !node || !priority || !req || !req_present)) { c->last_error = "bs_nominated_read: a column is NULL and the table has rows"; return BS_ERR_INVALID; }
+  if ((rc = use_device(c))) return rc;
+  if (!W) return BS_OK;
+  const NomTab t = nom_tab(c, c->nom_cur);
+  HIPCHK(c, hipMemcpyAsync(id, t.id, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(node, t.node, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(priority, t.prio, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(req_present, t.pres, (size_t)W * 4, hipMemcpyDeviceToHost, c->stream));
+  for (uint32_t j = 0; j < c->L; ++j)
+    HIPCHK(c, hipMemcpyAsync(req + (size_t)j * W, t.req + (size_t)j * t.stride, (size_t)W * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return BS_OK;
+}
+
+int bs_nominated_apply(bs_ctx* c, uint32_t n_remove, const uint32_t* remove_id, uint32_t n_insert, const uint32_t* pod_index, const uint32_t* node,
+                       const int32_t* priority, uint32_t* first_id_out) {
+  if (!c) return BS_ERR_INVALID;
+  int rc = nom_state(c, "bs_nominated_apply");
+  if (rc) return rc;
+  if (n_insert && !c->have_pods) { c->last_error = "bs_nominated_apply: inserts need the pods loaded (the rows are gathered from the resident queue)"; return BS_ERR_STATE; }
+  if (const int bad = nom_apply_check(c->nom_live.data(), c->nom_w, c->nom_ids, n_remove, remove_id, n_insert, pod_index, node, priority, c->P, c->N,
+                                      BS_NOM_MAX, kNomMaxIds))
+    return nom_refusal(c, "bs_nominated_apply", bad);
+  const uint32_t ids = c->nom_ids;
+  if (n_remove || n_insert) {
+    if ((rc = use_device(c))) return rc;
+    if ((rc = nom_apply_rows(c, n_remove, remove_id, n_insert, pod_index, node, priority))) return rc;
+  }
+  if (first_id_out) *first_id_out = ids;
+  return BS_OK;
+}
+}  // extern "C"

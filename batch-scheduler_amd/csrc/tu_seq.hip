@@ -1,7 +1,7 @@
 // tu_seq.hip — translation unit of the sequential pass: its kernel (bs_seq.hpp: k_seq_pass, six instantiations), the file-local launch
 // wrapper and the entry point bs_seq_run (include/bsched.h) with its flat form; see tu_fast.hip for why.
 #ifndef BS_UNITY
-#define BS_TU_SEQ
+#define BS_TU_FAMILY
 #endif
 #include <cstdio>
 #include <cstdlib>

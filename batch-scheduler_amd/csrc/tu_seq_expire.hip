@@ -2,9 +2,9 @@
 // lane-templated kernels once per scalar-lane count 0..BS_MAX_SCALARS), its file-local launch wrappers and the entry points bs_seq_expire /
 // bs_seq_waiting_read (include/bsched.h).  A unit of its own, not tu_seq.hip: with these kernels in the pass's unit one instantiation of
 // k_seq_pass came out with other instructions (profiles/seq_expire_isa_diff.txt).
-// Like tu_seq.hip it emits none of the shared headers' non-template kernels (BS_TU_SEQ, bs_common.hpp).
+// A family unit: it emits none of the shared headers' non-template kernels (BS_TU_FAMILY, bs_common.hpp).
 #ifndef BS_UNITY
-#define BS_TU_SEQ
+#define BS_TU_FAMILY
 #endif
 #include "bs_seq_expire.hpp"
 #include "bs_seq_expire_list.hpp"

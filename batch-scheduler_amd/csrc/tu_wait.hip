@@ -1,9 +1,9 @@
 // tu_wait.hip — translation unit of the resident Permit-wait table (bs_wait.hpp: k_wt_*, the lane-templated kernels once per scalar-lane
 // count 0..BS_MAX_SCALARS), its file-local launch wrappers and the entry points bs_wait_* (include/bsched.h).  A unit of its own for
 // tu_seq_expire.hip's reason: code added to a unit has changed k_seq_pass's instructions before.
-// Like tu_seq.hip it emits none of the shared headers' non-template kernels (BS_TU_SEQ, bs_common.hpp).
+// A family unit: it emits none of the shared headers' non-template kernels (BS_TU_FAMILY, bs_common.hpp).
 #ifndef BS_UNITY
-#define BS_TU_SEQ
+#define BS_TU_FAMILY
 #endif
 #include "bs_wait.hpp"
 #include "bs_wait_list.hpp"

@@ -245,9 +245,9 @@ def test_argument_checks_under_sanitizers(tmp_path):
 def test_the_bind_unit_is_built_linked_and_lists_every_header_it_reaches():
     build = importlib.import_module("batch-scheduler_amd.build")
     from test_build_units_cpu import closure
-    assert list(build.BIND_UNITS) == ["tu_bind.hip"] and build.LINK_SOURCES == build.BUILD_SOURCES + ["tu_bind.hip"]
+    assert "tu_bind.hip" in build.SOURCES
     reached = closure("tu_bind.hip")
-    assert not reached - {os.path.normpath(h) for h in build.BIND_UNITS["tu_bind.hip"]}, sorted(reached)
+    assert not reached - {os.path.normpath(h) for h in build.UNITS["tu_bind.hip"]}, sorted(reached)
     assert {"bs_bound_bind.hpp", "bs_bound_bind_check.hpp", "bs_bound_apply.hpp"} <= reached and "bs_wait.hpp" not in reached
     assert set(build.HEADERS) >= {"bs_bound_bind.hpp", "bs_bound_bind_check.hpp"}
     assert '#include "tu_bind.hip"' in open(os.path.join(build.CSRC, "bsched.hip")).read(), "the unity build includes the unit"

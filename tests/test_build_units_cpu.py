@@ -1,52 +1,89 @@
-"""build.UNITS against the real include graph of csrc/.  The library is built unit by unit, and a unit is recompiled when one of the headers
-build.py lists for it is newer than its object: a header the list lacks means a silently stale library, and a header the main unit does not
-need means a 2-minute rebuild where 5 seconds would do.  Reads source text only.  No GPU, no compiler."""
+"""build.SOURCES / build.UNITS against csrc/.  The library is built unit by unit, and a unit is recompiled when one of the headers it reaches
+is newer than its object; build.py reads those headers from the #include lines (build.closure), so the one list a person keeps is
+SOURCES.  Held here: that list against the files and the unity includes, staleness on a made-up tree, and which unit may reach which
+header family (a header the main unit does not need means a 2-minute rebuild where 5 seconds would do).  Reads source text only, but for the
+placement test at the end, which reads the built library.  No GPU."""
 import importlib
 import os
 import re
+import sys
 
 build = importlib.import_module("batch-scheduler_amd.build")
+closure = build.closure
 CSRC = build.CSRC
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAMILY_HEADERS = {"bs_preempt.hpp", "bs_preempt_commit.hpp", "bs_preempt_commit_gang.hpp", "bs_bound_apply.hpp", "bs_pdb.hpp", "bs_seq.hpp",
-                  "bs_seq_expire.hpp", "bs_seq_expire_list.hpp"}
+                  "bs_seq_expire.hpp", "bs_seq_expire_list.hpp", "bs_bound_nodes.hpp", "bs_bound_nodes_replay.hpp", "bs_nominated.hpp",
+                  "bs_nominated_check.hpp", "bs_wait.hpp", "bs_wait_list.hpp", "bs_groups_list.hpp", "bs_groups_list_check.hpp",
+                  "bs_bound_bind.hpp", "bs_bound_bind_check.hpp", "bs_bound_cols.hpp"}
 MAIN_HEADERS = {"bs_fast.hpp", "bs_filter_t.hpp", "bs_epoch.hpp", "bs_queue.hpp"}
 
 
-def closure(unit):
-    """every header the unit reaches through quoted #includes, as paths relative to csrc/ (the .hip includes exist under BS_UNITY only)"""
-    seen, todo = set(), [unit]
-    while todo:
-        here = todo.pop()
-        text = open(os.path.join(CSRC, here)).read()
-        for inc in re.findall(r'^\s*#\s*include\s*"([^"]+)"', text, re.M):
-            if inc.endswith(".hip"):
-                continue
-            rel = os.path.normpath(os.path.join(os.path.dirname(here), inc))
-            assert os.path.exists(os.path.join(CSRC, rel)), (here, inc)
-            if rel not in seen:
-                seen.add(rel)
-                todo.append(rel)
-    return seen
+def test_the_one_list_names_every_unit_and_the_table_is_the_include_graph():
+    assert sorted(build.SOURCES) == sorted(f for f in os.listdir(CSRC) if f.endswith(".hip")) and len(set(build.SOURCES)) == len(build.SOURCES)
+    assert build.SOURCES[0] == "bsched.hip"
+    unity = re.search(r"^#ifdef BS_UNITY\b.*?\n(.*?)^#endif", open(os.path.join(CSRC, "bsched.hip")).read(), re.M | re.S).group(1)
+    assert re.findall(r'^\s*#\s*include\s*"([^"]+\.hip)"', unity, re.M) == build.SOURCES[1:], "the unity build includes every other unit, in the list's order"
+    assert list(build.UNITS) == build.SOURCES
+    for unit in build.SOURCES:
+        assert build.UNITS[unit] == sorted(closure(unit)), unit
+        for h in build.UNITS[unit]:
+            assert h == os.path.normpath(h) and os.path.exists(os.path.join(CSRC, h)), (unit, h)
+    assert build.HEADERS == sorted({h for hs in build.UNITS.values() for h in hs})
 
 
-CLOSURE = {unit: closure(unit) for unit in build.UNITS}
+def test_a_newer_header_makes_stale_exactly_the_units_that_reach_it(tmp_path, monkeypatch):
+    """a.hip -> y.hpp -> x.hpp and b.hip -> x.hpp, on a tree of its own: a.hip reaches x.hpp through y.hpp only, b.hip never reaches y.hpp
+    (were the chain x.hpp -> y.hpp, b.hip would reach both and no header could make a.hip alone stale).  What "every header a unit reaches is
+    listed for it" stood for."""
+    csrc, obj = tmp_path / "csrc", tmp_path / "build"
+    csrc.mkdir()
+    obj.mkdir()
+    (csrc / "a.hip").write_text('#include "y.hpp"\n#ifdef BS_UNITY\n#include "b.hip"\n#endif\n')
+    (csrc / "b.hip").write_text('#if defined(SOMETHING)\n  #  include "x.hpp"\n#endif\n')
+    (csrc / "y.hpp").write_text('#pragma once\n#include <vector>\n#include "x.hpp"\n')
+    (csrc / "x.hpp").write_text("#pragma once\n")
+    monkeypatch.setattr(build, "CSRC", str(csrc))
+    monkeypatch.setattr(build, "OBJ_DIR", str(obj))
+    monkeypatch.setattr(build, "LIB_PATH", str(tmp_path / "libbsched.so"))
+    monkeypatch.setattr(build, "SOURCES", ["a.hip", "b.hip"])
+    monkeypatch.setattr(build, "UNITS", {src: sorted(build.closure(src)) for src in build.SOURCES})
+    monkeypatch.setattr(build, "HEADERS", sorted({h for hs in build.UNITS.values() for h in hs}))
+    assert build.UNITS == {"a.hip": ["x.hpp", "y.hpp"], "b.hip": ["x.hpp"]}
 
+    def at(path, t):
+        os.utime(path, (t, t))
 
-def test_every_header_a_unit_reaches_is_listed_for_it():
-    assert list(build.UNITS) == build.SOURCES == ["bsched.hip", "tu_fast.hip", "tu_seq.hip", "tu_seq_expire.hip", "tu_preempt.hip"]
-    for unit, listed in build.UNITS.items():
-        missing = CLOSURE[unit] - {os.path.normpath(h) for h in listed}
-        assert not missing, (unit, sorted(missing))
+    for f in ("a.hip", "b.hip", "x.hpp", "y.hpp"):
+        at(csrc / f, 1000)
+    assert build._unit_stale("a.hip") and build._unit_stale("b.hip") and build.is_stale(), "no object, no library"
+    for f in ("a.o", "b.o"):
+        (obj / f).write_bytes(b"")
+        at(obj / f, 2000)
+    (tmp_path / "libbsched.so").write_bytes(b"")
+    at(tmp_path / "libbsched.so", 2000)
+    assert not build._unit_stale("a.hip") and not build._unit_stale("b.hip") and not build.is_stale()
+    at(csrc / "y.hpp", 3000)
+    assert build._unit_stale("a.hip") and not build._unit_stale("b.hip") and build.is_stale()
+    at(csrc / "y.hpp", 1000)
+    at(csrc / "x.hpp", 3000)
+    assert build._unit_stale("a.hip") and build._unit_stale("b.hip") and build.is_stale()
+    at(csrc / "x.hpp", 1000)
+    at(csrc / "b.hip", 3000)
+    assert not build._unit_stale("a.hip") and build._unit_stale("b.hip") and build.is_stale()
 
 
 def test_the_main_unit_depends_on_no_family_header():
     assert not FAMILY_HEADERS & set(build.UNITS["bsched.hip"])
-    assert not FAMILY_HEADERS & CLOSURE["bsched.hip"]
+    assert not FAMILY_HEADERS & closure("bsched.hip")
+    assert FAMILY_HEADERS <= set(build.HEADERS), "every name above is a header some unit reaches"
 
 
 def test_the_family_units_depend_on_no_header_of_the_batch_chains():
-    for unit in ("tu_preempt.hip", "tu_seq.hip", "tu_seq_expire.hip"):
-        assert not MAIN_HEADERS & CLOSURE[unit], unit
+    for unit in build.SOURCES:
+        if unit not in ("bsched.hip", "tu_fast.hip"):
+            assert not MAIN_HEADERS & closure(unit), unit
+    assert MAIN_HEADERS <= closure("bsched.hip")
 
 
 def test_no_header_fences_itself_against_the_main_unit():
@@ -54,3 +91,46 @@ def test_no_header_fences_itself_against_the_main_unit():
     for name in sorted(os.listdir(CSRC)):
         lines = [l for l in open(os.path.join(CSRC, name)).read().splitlines() if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", l) and "BS_TU_MAIN" in l]
         assert len(lines) == (1 if name == "bs_common.hpp" else 0), (name, lines)
+
+
+def test_every_family_unit_says_so_with_the_one_macro():
+    """bsched.hip defines BS_TU_MAIN, tu_fast.hip BS_TU_FAST, every other unit BS_TU_FAMILY, each outside a unity build only; no other
+    BS_TU_* name is left anywhere in csrc/"""
+    want = {"bsched.hip": "BS_TU_MAIN", "tu_fast.hip": "BS_TU_FAST"}
+    for unit in build.SOURCES:
+        text = open(os.path.join(CSRC, unit)).read()
+        assert re.findall(r"^#ifndef BS_UNITY\n#define (BS_TU_\w+)\n#endif$", text, re.M) == [want.get(unit, "BS_TU_FAMILY")], unit
+    for name in sorted(os.listdir(CSRC)):
+        assert set(re.findall(r"\bBS_TU_\w+", open(os.path.join(CSRC, name)).read())) <= {"BS_TU_MAIN", "BS_TU_FAST", "BS_TU_FAMILY"}, name
+
+
+def test_the_kernels_over_the_bound_table_live_in_three_units_by_family():
+    """the victim search and the plans | the bound table's patch, its remap and its PDB column | the nominated-pod table: each family's
+    kernels in one unit, three units in all, none of them the unit of k_seq_pass, k_wt_* or k_bb_*, and no kernel with scratch"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources
+    all_k = kernel_resources.resources()
+    families = {"tu_preempt.hip": ("k_preempt_scan", "k_preempt_pick", "k_pc_scan", "k_pc_resolve", "k_pc_nodes", "k_pc_boff", "k_pc_compact", "k_gang_resolve"),
+                "tu_bound.hip": ("k_ba_scatter", "k_ba_mark", "k_ba_boff", "k_ba_merge", "k_ba_nodes", "k_bn_len", "k_bn_scan1", "k_bn_scan2", "k_bn_move", "k_pdb_allowed",
+                                 "k_pdb_bits"),
+                "tu_nominated.hip": ("k_nm_mark", "k_nm_chains", "k_nm_move", "k_nm_gather")}
+    lane_free = {"k_pdb_allowed", "k_pdb_bits", "k_nm_mark", "k_nm_chains"}
+    placed = {}
+    for unit, fams in families.items():
+        units = set()
+        for fam in fams:
+            res = {k: v for k, v in all_k.items() if re.search(rf"\d+{fam}(I|E)", k)}
+            assert len(res) == (1 if fam in lane_free else 13), (fam, sorted(res))
+            for k, v in res.items():
+                assert v["scratch"] == 0, (k, v)
+            units |= {v["unit"] for v in res.values()}
+        assert len(units) == 1, (unit, units)
+        placed[unit] = units.pop()
+    assert len(set(placed.values())) == 3, placed
+    named = {k for k in all_k if re.search(r"\d+k_(preempt|pc|gang|ba|bn|pdb|nm)_", k)}
+    assert len(named) == sum(1 if f in lane_free else 13 for fams in families.values() for f in fams), "no kernel of these prefixes is left out above"
+    others = {v["unit"] for k, v in all_k.items() if "k_seq_pass" in k or "k_wt_" in k or "k_bb_" in k or "k_se_" in k or "k_gl_" in k}
+    assert others.isdisjoint(placed.values())
+    # the source says the same: the headers whose non-template kernels have no emit switch are reached by one unit each
+    for header, unit in (("bs_pdb.hpp", "tu_bound.hip"), ("bs_nominated.hpp", "tu_nominated.hip")):
+        assert [u for u in build.SOURCES if header in build.UNITS[u]] == [unit], header

@@ -1,5 +1,6 @@
 """csrc/bs_carve.hpp, the running offset that hands out the typed pieces of every host-side scratch layout, compiled alone with
 tests/native/carve_main.cpp under ASan + UBSan and held against the rule written out here.  No GPU."""
+import importlib
 import os
 import re
 import subprocess
@@ -7,6 +8,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "batch-scheduler_amd", "csrc")
+build = importlib.import_module("batch-scheduler_amd.build")
 
 
 def test_offsets_and_totals_under_sanitizers(tmp_path):
@@ -40,13 +42,13 @@ def test_offsets_and_totals_under_sanitizers(tmp_path):
 
 
 def test_the_header_is_host_only_and_no_hand_written_offset_table_is_left():
-    """bs_carve.hpp includes no HIP header; the host code (the eight translation units and bs_ctx.hpp) no longer advances an offset by hand, and
+    """bs_carve.hpp includes no HIP header; the host code (every translation unit, bs_ctx.hpp and bs_bound_cols.hpp) no longer advances an offset by hand, and
     casts no `base + o_x` / `base + c->blay.x`, a base written as `buf.as<uint8_t>()` included"""
     text = open(os.path.join(CSRC, "bs_carve.hpp")).read()
     assert not [h for h in re.findall(r"#include\s*[<\"]([^>\"]+)", text) if "hip" in h]
     cast = r"reinterpret_cast<[^>]*>\(\s*[\w.<>()\-]+\s*\+\s*(?:o_\w+|c->blay\.\w*)"
     assert re.findall(cast, "reinterpret_cast<int32_t*>(c->d_bound.as<uint8_t>() + c->blay.group)")      # (the form the narrower pattern let through)
-    for unit in ("bsched.hip", "tu_fast.hip", "tu_seq.hip", "tu_seq_expire.hip", "tu_preempt.hip", "tu_wait.hip", "tu_groups.hip", "tu_bind.hip", "bs_ctx.hpp"):
+    for unit in build.SOURCES + ["bs_ctx.hpp", "bs_bound_cols.hpp"]:
         src = open(os.path.join(CSRC, unit)).read()
         assert "o = align256(o +" not in src, unit
         assert not re.findall(cast, src), unit

@@ -168,10 +168,10 @@ def test_hand_written_known_answers():
 def test_the_groups_unit_is_built_linked_and_lists_every_header_it_reaches():
     build = importlib.import_module("batch-scheduler_amd.build")
     from test_build_units_cpu import closure, MAIN_HEADERS
-    assert list(build.LIST_UNITS) == ["tu_groups.hip"] and build.BUILD_SOURCES == build.ALL_SOURCES + ["tu_groups.hip"]
+    assert "tu_groups.hip" in build.SOURCES
     assert set(build.HEADERS) >= {"bs_groups_list.hpp", "bs_groups_list_check.hpp"}
     reached = closure("tu_groups.hip")
-    assert not reached - {os.path.normpath(h) for h in build.LIST_UNITS["tu_groups.hip"]}, sorted(reached)
+    assert not reached - {os.path.normpath(h) for h in build.UNITS["tu_groups.hip"]}, sorted(reached)
     assert {"bs_groups_list.hpp", "bs_groups_list_check.hpp"} <= reached and not MAIN_HEADERS & reached
     assert not {"bs_wait.hpp", "bs_seq.hpp"} & reached, "the unit reaches the wait table through bs_ctx.hpp's two declarations only"
     for unit in ("bsched.hip", "tu_seq.hip", "tu_wait.hip"):

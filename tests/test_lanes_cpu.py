@@ -1,5 +1,6 @@
 """csrc/bs_lanes.hpp, the three rules by which a context's scalar-lane count picks a kernel instantiation, compiled alone with
 tests/native/lanes_main.cpp under ASan + UBSan and held against the rules written out here.  No GPU."""
+import importlib
 import os
 import re
 import subprocess
@@ -7,6 +8,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "batch-scheduler_amd", "csrc")
+build = importlib.import_module("batch-scheduler_amd.build")
 
 
 def test_the_three_rules_under_sanitizers(tmp_path):
@@ -28,6 +30,6 @@ def test_the_header_is_host_only_and_no_host_switch_on_the_lane_count_is_left():
     """bs_lanes.hpp includes no HIP header; no `switch` on S / c->S / c.S / ts remains in the host code of the translation units"""
     text = open(os.path.join(CSRC, "bs_lanes.hpp")).read()
     assert not [h for h in re.findall(r"#include\s*[<\"]([^>\"]+)", text) if "hip" in h]
-    for unit in ("bsched.hip", "tu_fast.hip", "tu_seq.hip", "tu_seq_expire.hip", "tu_preempt.hip", "bs_ctx.hpp"):
+    for unit in build.SOURCES + ["bs_ctx.hpp", "bs_bound_cols.hpp"]:
         src = open(os.path.join(CSRC, unit)).read()
         assert not re.search(r"switch\s*\(\s*(S|c->S|c\.S|ts)\b", src), unit

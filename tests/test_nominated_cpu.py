@@ -326,12 +326,13 @@ def test_argument_checks_under_sanitizers(tmp_path):
 # ---- where the new code sits -----------------------------------------------------------------------------------------------------------
 def test_the_new_headers_are_listed_with_the_unit_that_includes_them():
     build = bsa.build
-    assert {"bs_nominated.hpp", "bs_nominated_check.hpp"} <= set(build.UNITS["tu_preempt.hip"])
-    src = open(os.path.join(ROOT, "batch-scheduler_amd", "csrc", "tu_preempt.hip")).read()
+    assert {"bs_nominated.hpp", "bs_nominated_check.hpp"} <= set(build.UNITS["tu_nominated.hip"])
+    src = open(os.path.join(ROOT, "batch-scheduler_amd", "csrc", "tu_nominated.hip")).read()
     assert '#include "bs_nominated.hpp"' in src and '#include "bs_nominated_check.hpp"' in src
     check = open(os.path.join(ROOT, "batch-scheduler_amd", "csrc", "bs_nominated_check.hpp")).read()
     assert "hip" not in check.split("#pragma once")[1].lower(), "the check header is plain C++"
-    for other in ("tu_bind.hip", "tu_wait.hip", "bsched.hip"):
+    assert "bs_nominated.hpp" not in build.UNITS["tu_preempt.hip"], "the preemption calls reach the table through bs_ctx.hpp's declarations only"
+    for other in ("tu_preempt.hip", "tu_bound.hip", "tu_bind.hip", "tu_wait.hip", "bsched.hip"):
         assert "bs_nominated.hpp" not in open(os.path.join(ROOT, "batch-scheduler_amd", "csrc", other)).read(), "the k_nm_* kernels are emitted by one unit"
 
 

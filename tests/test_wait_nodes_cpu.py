@@ -247,7 +247,7 @@ def test_the_churn_cycle_scene_drops_rows_uses_appended_nodes_and_releases_a_gan
 def test_the_by_node_kernels_use_no_scratch_and_live_in_the_wait_unit():
     """k_wn_map and k_wn_move<S>, S = 0..12: no scratch, in the unit of the k_wt_* kernels, which still emits neither k_seq_pass nor a k_se_* kernel"""
     build = importlib.import_module("batch-scheduler_amd.build")
-    assert "bs_bound_nodes_replay.hpp" in build.LATER_UNITS["tu_wait.hip"], "the unit lists the replay header it reuses"
+    assert "bs_bound_nodes_replay.hpp" in build.UNITS["tu_wait.hip"], "the unit lists the replay header it reuses"
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_resources
     all_k = kernel_resources.resources()

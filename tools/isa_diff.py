@@ -4,7 +4,10 @@ the kernels are compared by name.  Usage: python tools/isa_diff.py OLD.so NEW.so
 that differs; exit status 1 when a kernel differs or is in one library only.
 
 objdump prints the zero fill behind the last s_endpgm of a section as a line `...`: it belongs to whichever kernel the compiler emitted
-last, which changes with the order of instantiation and says nothing about the kernel, so the line is dropped."""
+last, which changes with the order of instantiation and says nothing about the kernel, so the line is dropped.  The same holds for the
+run of `s_nop 0` that pads the end of a code object's .text section (where the non-template kernels sit): it lands on whichever of them is
+last in its unit, so moving a kernel family to another unit moves the padding; no kernel's own code ends in `s_nop 0`, and a trailing run
+of them is dropped from every kernel."""
 import hashlib
 import os
 import re
@@ -42,6 +45,8 @@ def kernels(lib):
                 if cur and ins and ins != "...":
                     text[cur].append(ins)
             for k, v in text.items():
+                while v and v[-1] == "s_nop 0":
+                    v.pop()
                 out[k] = hashlib.md5("\n".join(v).encode()).hexdigest()[:12] + ":" + str(len(v))
     return out
 
