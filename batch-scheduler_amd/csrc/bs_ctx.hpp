@@ -298,12 +298,13 @@ struct bs_ctx {
   int step_a_resident[2] = {-1, -1};          // ... of k_fast_step_a
   // The one-launch form of launch A + the scan / Filter roles (k_fast_step_a, then k_fast_final), where it applies (the latency regime: at most 256
   // classes, 64 table chunks, 4 scalar lanes; the second batch over a queue onwards).  BS_STEP_A=3, the DEFAULT: the whole-step form — the class-slot
-  // form below whose pod blocks go on to the final verdicts inside the same launch (one launch per step; run_fast falls back to form 2 where it does not apply).
+  // form below whose pod blocks go on to the final verdicts inside the same launch (one launch per step; form 2 where it does not apply).  Which form a step takes, its grid and its ticket advances:
+  // step_a_plan (bs_step_geom.hpp).
   // BS_STEP_A=2: the class-slot form — class_slots_block publishes every class's slots from the class directory, the pod blocks gate nobody; k_fast_final
   // follows as a second launch.  BS_STEP_A=1: every pod block publishes (kept as a tested experiment).  BS_STEP_A=0: off.  Step times: BASELINE.md.
   uint32_t step_a_form = 3;
   bool step_a_on = true;
-  uint32_t step_shares = 8;          // BS_STEP_SHARES: blocks that share one table chunk's class slots (at most).  8 was the fastest of 2 / 4 / 8 / 16 under BS_STEP_A=2
+  uint32_t step_shares = 8;          // BS_STEP_SHARES: blocks that share one table chunk's class slots (at most; step_a_plan's nshares, bs_step_geom.hpp).  8 was the fastest of 2 / 4 / 8 / 16 under BS_STEP_A=2
                                      // (profiles/r06_step_a_class_slots_shares.txt); the whole-step form has not been swept
   uint32_t test_timeout_after = 0;   // BS_TEST_HANDOVER_TIMEOUT=n (test hook): the n-th one-launch step reports a timed-out hand-over as the device would
   uint32_t test_pc_chunk_nodes = 0;  // BS_TEST_PC_CHUNK_NODES=n (test hook): nodes per chunk of the preemption grids (bs_preempt_geom.hpp); 0 = the shipped geometry
@@ -377,7 +378,7 @@ struct bs_ctx {
   Stream stream;
   Stream stream3;                    // early Filter: runs beside the node scan when no capture can occur
   Event ev_query, ev_filter;
-  PinnedBuf<int32_t> h_info{PinWait::None, hipHostMallocMapped | hipHostMallocCoherent};   // [16], kernels write it directly: leader, panic, steady table, tag | K of the loaded pods, tag | ...
+  PinnedBuf<int32_t> h_info{PinWait::None, hipHostMallocMapped | hipHostMallocCoherent};   // [16], kernels write it directly; its words by name: enum HInfo (bs_kernels.hpp, the device stores use it too)
   PinnedBuf<> h_gstage{PinWait::Event};   // groups pack, then deltas
   PinnedBuf<> h_glstage{PinWait::Stream}; // bs_groups_list_apply's delta (its rows as a group pack, the remove and update lists), read in place by k_gl_gather
   PinnedBuf<> h_stage{PinWait::Event};    // pod staging; busy until the last H2D out of it is through (bs_pods_load does not wait for it)
@@ -389,6 +390,11 @@ struct bs_ctx {
   PinnedBuf<> h_hout{PinWait::None, hipHostMallocMapped | hipHostMallocCoherent};            // [outpack layout | feas[hstride] | tag]
   PinnedBuf<uint64_t> h_hrows{PinWait::None, hipHostMallocMapped | hipHostMallocCoherent};   // [W + 1][hstride]
 };
+
+// h_info's words by name (volatile: a kernel may be writing them); hinfo_at: the word's address for a kernel (nullptr before the block exists)
+inline int32_t hinfo_get(const bs_ctx* c, HInfo w) { return static_cast<volatile const int32_t*>(c->h_info.p)[w]; }
+inline void hinfo_set(bs_ctx* c, HInfo w, int32_t v) { static_cast<volatile int32_t*>(c->h_info.p)[w] = v; }
+inline int32_t* hinfo_at(const bs_ctx* c, HInfo w) { return c->h_info.p ? c->h_info.p + w : nullptr; }
 
 #define HIPCHK(ctx, call)                                                                         \
   do {                                                                                            \

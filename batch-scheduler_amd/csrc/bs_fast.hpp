@@ -80,7 +80,7 @@ __global__ void k_pod_pairs(PodsDev pods, uint32_t G, const uint32_t* rep, const
                             int32_t* hinfo, uint32_t* gcount) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i == 0 && hinfo) {
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(&hinfo[4]), ((unsigned long long)(uint32_t)tag << 32) | *kcount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // K + its tag in one store
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(&hinfo[kHiK]), ((unsigned long long)(uint32_t)tag << 32) | *kcount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // K + its tag in one store
   }
   {
     const int32_t gq = i < pods.p ? pods.group[i] : -1;
@@ -704,7 +704,6 @@ __device__ __forceinline__ void test_chaos_delay() {
   for (uint32_t s = 0; s < (h & 15u); ++s) __builtin_amdgcn_s_sleep(127);
 #endif
 }
-constexpr uint32_t kStepSlotsMax = 256;        // class slots the one-launch form handles (the latency regime: K <= 256)
 __device__ __forceinline__ bool step_wait(const uint32_t* word, uint32_t base, uint32_t need, int32_t* h_err) {
   uint32_t spins = 0;
   while ((uint32_t)(ld_agent(word) - base) < need) {
@@ -720,10 +719,7 @@ __device__ __forceinline__ bool step_wait(const uint32_t* word, uint32_t base, u
 // kGatherDirectBlocks pod blocks), counted in after their atomics have drained; a small queue's results are tagged words (scan_rec / feas_rec), no counter.
 constexpr uint32_t kScanRecChunks = 64;  // BatchDev::scan_rec[chunk][slot]: tag << 32 | the slot's first row inside the chunk (BS_INF: none) — one writer per word
 constexpr uint32_t kFeasRecGroups = 32;  // BatchDev::feas_rec[group of 4 node runs][slot]: tag << 32 | feasible nodes of the slot in those runs — one writer per word
-#ifndef BS_GATHER_DIRECT
-#define BS_GATHER_DIRECT 8
-#endif
-constexpr uint32_t kGatherDirectBlocks = BS_GATHER_DIRECT;   // up to this many pod blocks poll the result words directly (fast_final_block<true>)
+// (kStepSlotsMax, kGatherDirectBlocks / BS_GATHER_DIRECT: bs_step_geom.hpp, with the grid and the ticket advances that depend on them)
 constexpr uint32_t kRecStride = 32;      // 64-bit words per chunk record (BatchDev::chunk_rec): [2 j], [2 j + 1] = tag << 32 | low / high half of lane j's total; [16 + s] = tag << 32 | first row of key s
 constexpr uint32_t kTkSlots = 32, kTkTab = 48, kTkP1 = 64, kTkDone = 64 + 16 * 16, kTkWays = 16, kTkWords = 64 + 2 * 16 * 16;
 __device__ __forceinline__ void spread_add(uint32_t* words, uint32_t who) {
@@ -1006,7 +1002,7 @@ __device__ __forceinline__ void table_scan_block(const NodesDev& nd, const Batch
       // a scalar key that is not in the running sum yet at this row: only a slot that asks for nothing of it can pass (core.go:686-697)
       const uint32_t nab = ~(qf[u] >> 16) & smask;
       unsigned long long m = (qf[u] & 0x80000000u) ? 0ull : __ballot(valid && (nab & ~keyrow) == 0u);
-      static_assert(TS >= 0 && TS <= 4, "k_fast_step_a is instantiated for 0..4 scalar lanes (run_fast: step_a_possible)");
+      static_assert(TS >= 0 && TS <= 4, "k_fast_step_a is instantiated for 0..4 scalar lanes (bs_step_geom.hpp: step_a_possible)");
 #if BS_SCAN_BALLOT
       // one v_cmp_ge_i64 -> SGPR mask per resource lane, ANDed: no EXEC write, the four slots' compares are independent of each other
 #pragma unroll

@@ -35,6 +35,7 @@
 
 #include "bs_common.hpp"
 #include "bs_nodew_layout.hpp"
+#include "bs_step_geom.hpp"
 
 namespace bs {
 
@@ -81,7 +82,22 @@ struct TableDesc { uint32_t cls; float pct; };
 struct GroupDelta { uint32_t index, matched, status_scheduled, flags; };
 constexpr int kInlineDeltas = 48;                  // group deltas that ride in the kernel arguments (no H2D, no staging)
 struct DeltaPack { uint32_t n; GroupDelta d[kInlineDeltas]; };
-inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }   // host: grid sizes
+
+// The words of the context's pinned info block (bs_ctx::h_info, int32[16]) that kernels write and the host reads by name (bs_ctx.hpp: hinfo_get /
+// hinfo_set / hinfo_at).  Words 0 and 1 (leader, panic) travel with kHiSteadyTable in k_leader_info's block of four and are not read on the host.
+enum HInfo : int {
+  kHiSteadyTable = 2,    // findMaxPG's steady table id (-1: none)           } k_leader_info
+  kHiGroupTag = 3,       // ... and the tag that says the three are there    }
+  kHiK = 4,              // K of the resident queue and its tag, ONE 64-bit store (k_pod_pairs, k_pods_apply)
+  kHiKTag = 5,
+  kHiRuns = 8,           // leader runs, epoch flags, (unused), tag: k_epoch_views' block of four
+  kHiEpochFlags = 9,
+  kHiEpochTag = 11,
+  kHiHandoverErr = 12,   // an in-launch wait ran out (BatchDev::h_err)
+  kHiIdOverflow = 13,    // the insert wave of a queue patch ran out of ids
+  kHiFdFound = 14,       // BS_BATCH_FILTER_DENY: a pod somebody needed was turned away | the events differ from the ones given (BatchDev::h_fd[2])
+  kHiFdChanged = 15,
+};
 
 // the bound-pod table's one allocation for N nodes and B entries (the host's bs_ctx::d_bound; k_bn_move of bs_bound_nodes.hpp lays the
 // remapped table out with it): columns at 256-byte offsets, breq lane stride max(B, 1); returns its size
@@ -174,7 +190,7 @@ struct BatchDev {
   //   nodew[nodew_ref_lane(stride, t, j)]  the maxSingle the pairs of table t < 2 were built from (int64), [nodew_ref_flags(stride, t)] bit 0: built, bit 1: scalar MinResources
   uint64_t* nodew;
   uint32_t nodew_stride;
-  uint32_t tiles2_min;      // the transposed Filter items take PAIRS of tiles from this many tiles of Filter slots on (filter_loop_t; run_fast: BS_TP_TMIN x ranks)
+  uint32_t tiles2_min;      // the transposed Filter items take PAIRS of tiles from this many tiles of Filter slots on (filter_loop_t; launch_b_plan: BS_TP_TMIN x ranks)
   // ---- steady-state fast path (bs_fast.hpp): nothing here is reset per batch
   uint32_t* qstamp_s;       // [scan slots] batch stamp of the slot's last writer (slot live iff == prm.stamp)
   const uint32_t* first_pod_s;    // [G] min pod index of the group                               } derived from the pods alone
@@ -910,7 +926,6 @@ __global__ void k_query(PodsDev pods, GroupsDev gr, BatchDev b, BatchParams prm)
 // Block (slot, chunk) scans its 256 rows and records the chunk totals; the fix-up pass adds the sum
 // of the preceding chunks.  kp[s] = first row at which the running sum owns scalar key s.
 // ------------------------------------------------------------------------------------------------
-constexpr int kTblChunk = 256;
 static_assert(kTblChunk == (int)kNodewBlockThreads, "node_words_block runs in launch A's blocks: one thread per node (bs_nodew_layout.hpp)");
 
 // table id t: fit class t % C, percent 1 for t < C (core.go:140), 0.7 otherwise (core.go:161);
@@ -1574,7 +1589,7 @@ __device__ __forceinline__ void scan_loop(const BatchDev& b, const BatchParams& 
       // (throughput regime) the wave's first item with a slot in use: two words per lane are looked at before anything else is asked
       // for.  A wave whose items are all idle — the tiles of other ranks' request classes under bs_shard_set: class ids follow the
       // queue (k_pod_class_ids), so 7 tiles of 8 are idle on a rank of 8 — leaves without the first fetch (~60 KB), and a rank can
-      // cut its live tiles into as many shares as its part of the job allows (run_fast: share_b).
+      // cut its live tiles into as many shares as its part of the job allows (launch_b_plan: share_b).
       while (w_live < items) {
         const uint32_t rest = w_live / ntl, tile = t_lo + (w_live - rest * ntl);
         const uint32_t ps = tile * 64u + (uint32_t)lane;

@@ -45,7 +45,7 @@ inline auto lanes_narrow(uint32_t s, F&& f) {
 }
 
 // the families that have no generic-lane instantiation: V = min(S, kLanesUnrolled).  Their callers never come with more lanes
-// (step_a_possible, and run_fast's test in front of launch_fast_bt, both in bsched.hip); the clamp only keeps a stray S inside the set.
+// (step_a_possible, and launch_b_plan's test for the transposed one-launch form, both in bs_step_geom.hpp); the clamp only keeps a stray S inside the set.
 template <class F>
 inline auto lanes_clamped(uint32_t s, F&& f) {
   return lanes_pick<kLanesUnrolled>(s, f, std::make_integer_sequence<int, kLanesUnrolled>{});

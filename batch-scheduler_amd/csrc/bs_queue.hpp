@@ -342,10 +342,10 @@ __global__ __launch_bounds__(kApplyBlock) void k_pods_apply(PodsDev old, const u
     }
     BS_STAMP(0, 6);
     if (derive && threadIdx.x == 0 && hinfo) {
-      // K and the tag that says "K is there" in ONE 64-bit store (hinfo[4], hinfo[5]: 8-byte aligned): nothing to order, so no system-scope release
+      // K and the tag that says "K is there" in ONE 64-bit store (hinfo[kHiK], hinfo[kHiKTag]: 8-byte aligned): nothing to order, so no system-scope release
       // (an L2 write-back of everything the block's XCD holds dirty, 1.4 us at the end of the cycle's first launch)
       const uint32_t kc = __hip_atomic_load(q.kcount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(reinterpret_cast<unsigned long long*>(&hinfo[4]), ((unsigned long long)(uint32_t)tag << 32) | kc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(reinterpret_cast<unsigned long long*>(&hinfo[kHiK]), ((unsigned long long)(uint32_t)tag << 32) | kc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     BS_STAMP(0, 7);
     return;

@@ -182,11 +182,11 @@ BatchDev batch_dev(const bs_ctx* c) {
   b.first_reach64 = c->d_first_reach.as<unsigned long long>();
   b.fast_reject = c->d_fast_reject.as<uint32_t>();
   b.epoch_group = c->d_epoch_group.as<uint32_t>();
-  b.h_err = c->h_info.p ? c->h_info.p + 12 : nullptr;
+  b.h_err = hinfo_at(c, kHiHandoverErr);
   b.fd_event = c->d_fd_event.as<unsigned long long>();
   b.fd_in = c->fd_in_live ? c->d_fd_in.as<uint32_t>() : nullptr;
   b.fd_flag = c->d_fd_flag.as<uint32_t>();
-  b.h_fd = c->h_info.p ? c->h_info.p + 14 : nullptr;
+  b.h_fd = hinfo_at(c, kHiFdFound);
   void* ok = c->d_outpack.p;
   b.pf_code = c->olay.pf_code.in(ok);
   b.pf_first_k = c->olay.pf_first_k.in(ok);
@@ -344,12 +344,14 @@ void launch_tables_nofix(bs_ctx* c, dim3 grid, const NodesDev& nd, const BatchDe
   });
 }
 
-static FastLaunch fast_launch(const bs_ctx* c) {
-  FastLaunch f{c->stream, c->S, c->M, c->P, c->filter_waves, c->filter_slots_cap, c->tp_filter, c->cfg.device};
+// filter_waves: the context's, or launch B's effective count in the throughput regime (launch_b_plan, bs_step_geom.hpp)
+static FastLaunch fast_launch(const bs_ctx* c, uint32_t filter_waves) {
+  FastLaunch f{c->stream, c->S, c->M, c->P, filter_waves, c->filter_slots_cap, c->tp_filter, c->cfg.device};
   const uint32_t mul = c->tp_split ? c->tp_split : ((!c->reduce_external && c->nranks > 1u) ? 2u : 1u);
-  if (mul > 1u) f.filter_split = (uint32_t)std::min<uint64_t>((uint64_t)c->filter_waves * mul, 1u << 22);
+  if (mul > 1u) f.filter_split = (uint32_t)std::min<uint64_t>((uint64_t)filter_waves * mul, 1u << 22);
   return f;
 }
+static FastLaunch fast_launch(const bs_ctx* c) { return fast_launch(c, c->filter_waves); }
 static int fused_residency(bs_ctx* c) {
   if (c->fused_blocks_resident < 0) c->fused_blocks_resident = fused_residency_query(fast_launch(c));
   return c->fused_blocks_resident;
@@ -358,16 +360,9 @@ static int fused_residency(bs_ctx* c) {
 void launch_filter(bs_ctx* c, hipStream_t st, const PodsDev& pd, const NodesDev& nd, const BatchDev& b, bool use_classes) {
   const uint32_t W = cdiv(c->N, 64), ptiles = cdiv(c->P, 64);
   if (!ptiles || !W) return;
-  const uint32_t waves = std::min<uint32_t>(c->filter_waves, 2 * ptiles * std::max<uint32_t>(1, cdiv(W, 2)));
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_filter<2>), dim3(cdiv(waves, 4)), dim3(256), 0, st, pd, nd, b, c->filter_waves, use_classes ? 1u : 0u,
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_filter<2>), dim3(filter_blocks(c->filter_waves, 2 * ptiles, W)), dim3(256), 0, st, pd, nd, b, c->filter_waves, use_classes ? 1u : 0u,
                      c->filter_slots_cap, c->collect_stats);
 }
-
-// Cap on the shares (blocks of four waves, a quarter of every group's rows each) that deal the live 64-row groups of one tile
-// of class slots among themselves.  Measured (tools/share_sweep.sh, cfg3, step in us at 8 / 16 / 32 / 64 shares): tail 23.7 / 24.2 /
-// 23.8 / 24.2, busy 23.3 / 23.4 / 23.7 / 23.8, warm 23.5 / 24.2 / 27.4 / 28.6 — a share that has no group of its own still pays
-// the launch's first round trip, and with many live groups the shares re-read each other's results: eight is enough.
-uint32_t pick_scan_share(const bs_ctx* c) { return c->scan_share_override ? c->scan_share_override : 8u; }
 
 // Build the running-sum table for (cls, pct) in the scratch slot (last one) — single queries.
 int build_scratch_table(bs_ctx* c, uint32_t cls, float pct, uint32_t* slot_out) {
@@ -421,20 +416,20 @@ int wait_host_tag(bs_ctx* c, int tag_at, int32_t tag, const int32_t* base = null
 
 int resolve_groups(bs_ctx* c) {
   if (!c->info_pending) return BS_OK;
-  int rc = wait_host_tag(c, 3, c->info_tag);
+  int rc = wait_host_tag(c, kHiGroupTag, c->info_tag);
   if (rc) return rc;
   c->info_pending = false;
-  c->steady_table = (c->n_uncaptured == 0 && c->h_info.p[2] >= 0) ? c->h_info.p[2] : -1;
+  c->steady_table = c->n_uncaptured == 0 ? std::max(hinfo_get(c, kHiSteadyTable), -1) : -1;
   c->steady_prev = c->steady_table;
   return BS_OK;
 }
 
 int resolve_pods(bs_ctx* c) {
   if (!c->kinfo_pending) return BS_OK;
-  int rc = wait_host_tag(c, 5, c->kinfo_tag);
+  int rc = wait_host_tag(c, kHiKTag, c->kinfo_tag);
   if (rc) return rc;
   c->kinfo_pending = false;
-  c->h_K = (uint32_t)c->h_info.p[4];
+  c->h_K = (uint32_t)hinfo_get(c, kHiK);
   c->k_bound = c->h_K;
   return BS_OK;
 }
@@ -564,7 +559,7 @@ int analyse_epochs(bs_ctx* c) {
   hipLaunchKernelGGL(k_epochs2_b, dim3(cdiv(P, kScanBlock)), dim3(kScanBlock), 0, c->stream, pd, gr, b);
   hipLaunchKernelGGL(k_leader_scan, dim3(1), dim3(kLeaderBlock), 0, c->stream, gr, b);
   c->einfo_tag++;
-  hipLaunchKernelGGL(k_epoch_views, dim3(1), dim3(kLeaderBlock), 0, c->stream, pd, gr, b, ep, c->C, c->einfo_tag, c->h_info.p + 8);
+  hipLaunchKernelGGL(k_epoch_views, dim3(1), dim3(kLeaderBlock), 0, c->stream, pd, gr, b, ep, c->C, c->einfo_tag, hinfo_at(c, kHiRuns));
   LAUNCHCHK(c, BS_KERNEL_LEADER);
   c->einfo_pending = true;
   c->epochs_ready = true;
@@ -574,11 +569,11 @@ int analyse_epochs(bs_ctx* c) {
 
 int resolve_epochs(bs_ctx* c) {
   if (!c->einfo_pending) return BS_OK;
-  int rc = wait_host_tag(c, 11, c->einfo_tag);
+  int rc = wait_host_tag(c, kHiEpochTag, c->einfo_tag);
   if (rc) return rc;
   c->einfo_pending = false;
-  c->h_R = (uint32_t)c->h_info.p[8];
-  c->h_eflags = (uint32_t)c->h_info.p[9];
+  c->h_R = (uint32_t)hinfo_get(c, kHiRuns);
+  c->h_eflags = (uint32_t)hinfo_get(c, kHiEpochFlags);
   return BS_OK;
 }
 
@@ -761,8 +756,8 @@ int begin_reload(bs_ctx* c) {
 
 // a final block of a fused launch gave up waiting for its producers: the batch's results are not to be trusted
 int check_handover(bs_ctx* c) {
-  if (c->h_info.p && ((volatile int32_t*)c->h_info.p)[13]) {   // the insert wave of a queue patch ran out of ids (the accounting should make that impossible)
-    ((volatile int32_t*)c->h_info.p)[13] = 0;
+  if (c->h_info.p && hinfo_get(c, kHiIdOverflow)) {   // the insert wave of a queue patch ran out of ids (the accounting should make that impossible)
+    hinfo_set(c, kHiIdOverflow, 0);
     c->pairs_ready = false;                            // classes, pairs and directories are derived again from the resident queue
     c->dirs_ready = false;
     c->rep_valid = false;
@@ -773,8 +768,8 @@ int check_handover(bs_ctx* c) {
     c->last_error = "bs_pods_apply: class / pair id space overflowed on the device; the queue was re-derived, run the batch again";
     return rc2 ? rc2 : BS_ERR_RETRY;
   }
-  if (c->h_info.p && ((volatile int32_t*)c->h_info.p)[12]) {
-    ((volatile int32_t*)c->h_info.p)[12] = 0;
+  if (c->h_info.p && hinfo_get(c, kHiHandoverErr)) {
+    hinfo_set(c, kHiHandoverErr, 0);
     c->no_fuse_final = 1;                              // from now on: separate launches
     c->batch_void = true;
     c->last_error = "in-launch hand-over timed out (producer blocks not resident): batch void, run it again (the context now uses separate launches)";
@@ -1282,7 +1277,7 @@ static QueueDirs queue_dirs(const bs_ctx* c) {
   q.pair_head = reinterpret_cast<unsigned long long*>(c->d_gstat.as<uint32_t>() + (((size_t)3 * c->G + 1) & ~(size_t)1));
   q.pair_next = c->d_pair_next.as<unsigned long long>();
   q.pcap = c->pair_cap;
-  q.overflow = c->h_info.p ? c->h_info.p + 13 : nullptr;
+  q.overflow = hinfo_at(c, kHiIdOverflow);
   return q;
 }
 
@@ -1684,14 +1679,13 @@ static int setup_host_out(bs_ctx* c, uint32_t stages, bool run_filter, BatchDev&
 // BS_BATCH_FILTER_DENY | BS_BATCH_COMMIT, after the stream has been waited for: did the device gate this run's commit kernels off
 // (its flag word is non-zero: the run is not the fixed point, fd_resolve runs the batch again)?
 static bool fd_commit_gated(const bs_ctx* c) {
-  volatile const int32_t* hf = c->h_info.p + 14;
-  return c->fd_on && (hf[0] || hf[1]);
+  return c->fd_on && (hinfo_get(c, kHiFdFound) || hinfo_get(c, kHiFdChanged));
 }
-// ... or because one of the batch's in-launch waits ran out (k_fast_commit reads the same word, h_info[12]): the batch will be answered with BS_ERR_RETRY
+// ... or because one of the batch's in-launch waits ran out (k_fast_commit reads the same word, kHiHandoverErr): the batch will be answered with BS_ERR_RETRY
 // by whoever asks for its results (check_handover), so it leaves the group state and the carried leader as it found them — "run the batch again" holds
 // for a committing batch too
 static bool handover_commit_gated(const bs_ctx* c) {
-  return c->h_info.p && ((volatile const int32_t*)c->h_info.p)[12] != 0;
+  return c->h_info.p && hinfo_get(c, kHiHandoverErr) != 0;
 }
 
 // BS_BATCH_FILTER_DENY: the two launches behind a chain's last one (bs_fdeny.hpp).  tail: this chain left tally and completion
@@ -1724,213 +1718,64 @@ static inline uint64_t host_ns() {
   clock_gettime(CLOCK_MONOTONIC, &ts);
   return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
 }
-// k_fast_step_a (bs_fast.hpp): the one-launch form of launch A + the scan / Filter roles — the latency regime only (K known on the
-// host and <= 256 class slots, <= 64 table chunks), no instrumentation that needs the legacy launches (work counters, per-launch stamps),
-// and a context that has not seen an in-launch hand-over time out.  BS_STEP_A=0 switches it off (bs_ctx::step_a_form).
-static bool step_a_possible(const bs_ctx* c, uint32_t stages, uint32_t k, uint32_t nchunks) {
-  return c->step_a_on && !c->no_fuse_final && k > 0 && k <= kStepSlotsMax && nchunks <= 64 && c->M > 0 && c->P > 0 && !c->collect_stats &&
-         c->cfg.enable_timing < 2 && c->S <= 4;
-}
 static int step_a_residency(bs_ctx* c, bool whole) {
   int& r = c->step_a_resident[whole ? 1 : 0];
   if (r < 0) r = step_a_residency_query(fast_launch(c), whole);
   return r;
 }
 
-// The steady-state chain (bs_fast.hpp): three launches, nothing reset, no wait.
-static int run_fast(bs_ctx* c, uint32_t stages) {
-  int rc;
-  const uint32_t P = c->P, G = c->G, N = c->N;
-  const uint32_t W = cdiv(N, 64);
-  const bool run_filter = stages & BS_STAGE_FILTER;
-  const bool commit = stages & BS_BATCH_COMMIT;
-  NodesDev nd = nodes_dev(c);
-  GroupsDev gr = groups_dev(c);
-  PodsDev pd = pods_dev(c);
-  BatchDev b = batch_dev(c);
+// BatchParams of the two three-launch chains; stamped = false (the general chain, which resets its slots per batch): the fields only those
+// chains read (stamp, seq_inv, do_tally, do_ready) stay 0
+static BatchParams chain_params(const bs_ctx* c, uint32_t stages, bool use_classes, bool stamped = true) {
   BatchParams prm = batch_params(c);
-  prm.run_filter = run_filter;
-  prm.use_classes = 1;
-  prm.fuse_filter = run_filter ? 1u : 0u;
+  prm.run_filter = (stages & BS_STAGE_FILTER) ? 1u : 0u;
+  prm.use_classes = use_classes ? 1u : 0u;
+  prm.fuse_filter = prm.run_filter;
   prm.scan_slots_cap = c->scan_slots_cap;
   prm.filter_slots_cap = c->filter_slots_cap;
+  if (!stamped) return prm;
   prm.stamp = 1u + c->stamp_ctr;
   prm.seq_inv = ~c->key_seq;
-  prm.commit = commit ? 1u : 0u;
   prm.do_tally = (stages & BS_STAGE_TALLY) ? 1u : 0u;
   prm.do_ready = (prm.do_tally && c->nranks == 1 && !c->reduce_external) ? 1u : 0u;
-  if ((rc = setup_host_out(c, stages, run_filter, b, prm))) return rc;
-  const uint32_t side_slot = (uint32_t)c->steady_table;
-  const uint32_t nchunks = std::max<uint32_t>(1, cdiv(c->M, 256));
-  BatchDev bt = b;                                   // the batch view shifted to the steady table's slot (slot index 0)
-  bt.tables = b.tables + (size_t)side_slot * prm.mcap * prm.LP;
-  bt.kp = b.kp + (size_t)side_slot * 16;
-  bt.chunk_tot = b.chunk_tot + (size_t)side_slot * cdiv(c->Ncap, 256) * 16;
-  bt.chunk_kp = b.chunk_kp + (size_t)side_slot * cdiv(c->Ncap, 256) * 16;
-  bt.gmax = b.gmax + (size_t)side_slot * cdiv(c->Ncap, 64) * prm.LP;
-  const TableDesc* forced = b.desc + side_slot;
-  if (commit && G) HIPCHK(c, hipMemsetAsync(c->d_fast_reject.p, 0xFF, (size_t)G * 4, c->stream));
+  return prm;
+}
 
-  // K is known on the host once its copy from the pod load / queue patch has landed — never waited for here; when it is, the
-  // kernels need not fetch it in front of everything else
-  if (c->kinfo_pending && ((volatile int32_t*)c->h_info.p)[5] == c->kinfo_tag && (rc = resolve_pods(c))) return rc;
-  prm.k_host = c->kinfo_pending ? 0u : c->h_K;
-  const uint64_t hp1 = c->host_probe ? host_ns() : 0;
-  // ---- launch A and the scan / Filter roles of launch B as ONE launch (k_fast_step_a; round 6: its class-slot form is the default), then k_fast_final
-  // K not on the host yet (the queue was patched a moment ago and nobody has waited for the patch's word): the whole-step form sizes its grid for a
-  // BOUND of the class count (last known K + pods inserted since) and its blocks read K on the device; the other forms want it known
-  const bool k_known = !c->kinfo_pending;
-  const uint32_t k_step = k_known ? prm.k_host : ((c->step_a_form >= 3u && c->dirs_ready) ? c->k_bound : 0u);
-  if (step_a_possible(c, stages, k_step, nchunks) && (c->step_a_form == 1u || c->dirs_ready || (c->batch_since_pods && c->pairs_ready && c->rep_valid && c->have_groups))) {
-    const uint32_t K = k_step;
-    const uint32_t nshares = std::max<uint32_t>(1, std::min<uint32_t>(c->step_shares, cdiv(K, 8)));
-    const uint32_t fblocks = run_filter ? cdiv(std::min<uint32_t>(c->filter_waves, cdiv(2 * K, 64) * std::max<uint32_t>(1, cdiv(W, 2))), 4) : 0u;
-    // the class-slot form needs the class directory (ckeys / cpres: class id -> request lanes).  It is built once per derivation of the queue — like bs_pods_apply's first call — and only when the
-    // queue's classes and pairs are already resolved on the host (pairs_ready / rep_valid: the pod load's class count has landed; never waited for here): a caller that re-uploads its queue and
-    // scores it at once takes the two-launch chain and pays neither the directory kernel nor a stream wait.  So the FIRST batch over a fresh queue is of either form (both equal the oracle).
-    uint32_t pb = 0;
-    if (c->step_a_form >= 2u) {
-      if (!c->dirs_ready && c->batch_since_pods && c->pairs_ready && c->rep_valid && c->have_groups && (rc = build_dirs(c))) return rc;
-      if (c->dirs_ready) pb = cdiv(K, kTblChunk);
-    }
-    // form 3: the pod blocks go on to the final verdicts inside the same launch (fast_final_block<true>) — one launch for the whole step; its table rows
-    // are the nodes in list order (skipped nodes are rows that add nothing), not the compacted rows
-    const uint32_t nch_nodes = std::max<uint32_t>(1, cdiv(N, 256));
-    const uint32_t whole = (c->step_a_form >= 3u && pb && nch_nodes <= 64 && c->d_first_row64.p && c->d_scan_rec.p && c->d_feas_rec.p && c->d_chunk_rec.p) ? 1u : 0u;
-    const uint32_t nchunks_s = whole ? nch_nodes : nchunks;
-    // the whole-step form's pod blocks take bs_pods_load's gang-aligned ranges (bs_pod_ranges.hpp) when the queue is still the loaded one; a gang inside
-    // one range is closed in LDS by its block (tally_tail_whole) wherever the returning-atomic quorum would run: tally with ready, no Filter-deny pass
-    const bool ranges = whole && c->ranges_valid && c->nranges && c->d_pod_ranges.p;
-    const uint32_t qb = ranges ? c->nranges : cdiv(P, kTblChunk);
-    if (ranges) b.pod_ranges = c->d_pod_ranges.as<uint32_t>();
-    const uint32_t grid = qb + pb + nchunks_s * nshares + fblocks;
-    if ((k_known || whole) && (int)grid <= step_a_residency(c, whole != 0)) {
-      TIMED(c, BS_KERNEL_QUERY, {
-        launch_fast_step_a(fast_launch(c), dim3(grid), pd, gr, nd, b, bt, prm, forced, nchunks_s, qb, nshares, fblocks, c->tk_pods, c->tk_tab, pb,
-                           c->d_ckeys.as<int64_t>(), c->d_cpres.as<uint32_t>(), c->pair_cap, whole, c->tk_p1, c->tk_done, side_slot - c->C);
-      });
-      c->tk_pods += pb ? pb : qb;
-      if (!whole) c->tk_tab += nchunks_s;                              // (the whole-step form hands the chunk totals over as tagged words: no ticket)
-      if (whole) {
-        c->tk_p1 += qb;
-        if (qb > kGatherDirectBlocks) c->tk_done += nchunks_s * nshares + fblocks;   // (a small queue's producers leave tagged words, no counter)
-      } else {
-        TIMED(c, BS_KERNEL_RESOLVE, hipLaunchKernelGGL(k_fast_final, dim3(cdiv(P, 256)), dim3(256), 0, c->stream, pd, gr, nd, b, prm, cdiv(P, kTblChunk)));
-      }
-      c->launches = whole ? 1 : 2;
-      c->last_step_a = true;
-      if (c->test_timeout_after && --c->test_timeout_after == 0 && c->h_info.p) {      // test hook: what a block whose wait ran out does (bs_fast.hpp, kSpinBound)
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        ((volatile int32_t*)c->h_info.p)[12] = 1;
-      }
-      if (prm.filter_deny && (rc = launch_filter_deny(c, pd, gr, nd, b, prm, true))) return rc;
-      if (commit) {
-        if (prm.filter_deny && (rc = launch_filter_deny_marks(c, b, prm, b.fast_reject))) return rc;
-        if (G) hipLaunchKernelGGL(k_fast_commit, dim3(cdiv(G, 256)), dim3(256), 0, c->stream, pd, b, const_cast<uint8_t*>(gr.flags),
-                                  const_cast<uint64_t*>(gr.occupied), G, prm.filter_deny ? b.fd_flag : nullptr);
-        LAUNCHCHK(c, BS_KERNEL_RESOLVE);
-        int32_t last = -1;
-        HIPCHK(c, hipMemcpyAsync(&last, b.pf_leader + (P - 1), 4, hipMemcpyDeviceToHost, c->stream));
-        if (G) HIPCHK(c, hipMemcpyAsync(c->h_gflags.data(), gr.flags, G, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (!fd_commit_gated(c) && !handover_commit_gated(c)) c->sop_leader0 = last;
-        c->launches++;
-      }
-      return batch_collective(c, stages, gr, b);
-    }
-  }
-  c->last_step_a = false;
-  // the throughput regime (more than 16 tiles of class slots) is known before launch A: when launch B will take the transposed Filter item,
-  // launch A's grid carries the node-word blocks (node_words_block) behind the table chunks
-  const uint32_t k_est = std::min<uint32_t>(P, c->kinfo_pending ? std::max<uint32_t>(2 * c->h_K, 1024) : std::max<uint32_t>(c->h_K, 1));
-  const bool node_words = run_filter && cdiv(k_est, 64) > 16 && c->tp_filter >= 5u && !c->no_nodew && c->d_nodew.p;
-  if (node_words) {
-    b.nodew = bt.nodew = c->d_nodew.as<uint64_t>();
-    b.nodew_stride = bt.nodew_stride = nodew_stride(N);
-    b.tiles2_min = bt.tiles2_min = c->tp_tmin * std::max<uint32_t>(1u, c->nranks);
-  }
-  // ---- launch A: per-pod decisions, scan / Filter slots | chunk-local running sums of the table
-  TIMED(c, BS_KERNEL_QUERY, {
-    const uint32_t qb = cdiv(P, kTblChunk);
-    const dim3 qg(qb + nchunks + (node_words ? nodew_blocks(N) : 0u)), blk(kTblChunk);
-    lanes_narrow(c->S, [&](auto s) {
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fast_query_tables<decltype(s)::value>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb);
-    });
-  });
-  const uint64_t hp2 = c->host_probe ? host_ns() : 0;
-  bool fused = false, tp_split = false;
-  uint64_t hp3 = 0;
-  // ---- launch B: node scan over the class slots | Filter evaluation over the Filter slots
-  // The work loops size themselves on the device (the class count lives there); the grid only has to be large enough.
-  TIMED(c, BS_KERNEL_SCAN, {
-    const uint32_t nseg = pick_scan_share(c);
-    // few tiles (the latency regime): one scan item (tile of 64 class slots x share) per BLOCK, its four waves take a quarter of
-    // every group's rows each; many tiles (thousands of distinct requests): one item per wave, 4 per block
-    const uint32_t tiles = cdiv(k_est, 64);
-    const bool throughput = tiles > 16;
-    // scan shares per tile when an item is one wave's: thousands of tiles are parallelism enough, and every item pays the table's
-    // first fetch (cfg3 all-distinct 48.5 -> 38.5 us, cfg4 with the transposed Filter role 220 -> 192 us from 64 / 8 shares to 2)
-    const uint32_t share_b = c->tp_share ? c->tp_share : (throughput ? 2u : 64u);
-    // the Filter work of the transposed item is cut for twice the waves from 65 536 (tile, two node blocks) units on (half of the
-    // slot tiles belong to the carried leader and are usually idle: 8192 items leave half of the wave slots without work there)
-    struct FwGuard { bs_ctx* c; uint32_t saved; ~FwGuard() { c->filter_waves = saved; } } fw_guard{c, c->filter_waves};
-    if (throughput && c->tp_filter >= 5u && !c->filter_waves_env)
-      c->filter_waves = c->tp_fwaves ? c->tp_fwaves
-                                     : ((uint64_t)cdiv(2 * k_est, 64) * std::max<uint32_t>(1, cdiv(W, 2)) >= 65536u ? std::max<uint32_t>(c->filter_waves, 16384u) : c->filter_waves);
-    const uint32_t fblocks = run_filter ? cdiv(std::min<uint32_t>(c->filter_waves, cdiv(2 * k_est, 64) * std::max<uint32_t>(1, cdiv(W, 2))), 4) : 0u;
-    auto scan_grid = [&](uint32_t nsub) {
-      const uint32_t items = tiles * std::min<uint32_t>(nsub == 4u ? nseg : share_b, cdiv(c->M, 64));
-      return std::max<uint32_t>(1, std::min<uint32_t>(cdiv(c->target_waves, 4), nsub == 4u ? items : cdiv(items, 4)));
-    };
-    // the fused form (final blocks wait for the producers INSIDE the launch) only in the latency regime, and only when every block
-    // of its grid is resident at once (see fused_residency); BS_NO_FUSE_FINAL=1 forces the separate launches
-    fused = tiles <= 16 && !c->no_fuse_final && (int)(scan_grid(4u) + fblocks + cdiv(P, 256)) <= fused_residency(c);
-    prm.scan_nsub = fused ? 4u : 1u;
-    const uint32_t scan_blocks = scan_grid(prm.scan_nsub);
-    hp3 = c->host_probe ? host_ns() : 0;
-    if (fused) {
-      // ---- ... and launch C in the same launch: final codes, Filter code / slot / feasible count per pod, admit counts, quorum
-      const dim3 grid(scan_blocks + fblocks + cdiv(P, 256));
-      launch_fast_bc(fast_launch(c), grid, pd, gr, nd, b, bt, prm, nseg, scan_blocks, fblocks);
-    } else if (c->tp_filter == 8u && fblocks && throughput) {
-      // the two roles as launches of their own, SIDE BY SIDE: the scan on the side stream (its items are chains of dependent loads,
-      // its 130-odd VGPRs its own business), the transposed Filter item at seven waves per SIMD on the main one; both read what launch
-      // A wrote and write disjoint outputs for the final launch, which waits for both
-      FastLaunch side = fast_launch(c);
-      side.stream = c->stream3;
-      HIPCHK(c, hipEventRecord(c->ev_query, c->stream));
-      HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_query, 0));
-      launch_fast_scan(side, dim3(scan_blocks), bt, prm, share_b);
-      HIPCHK(c, hipEventRecord(c->ev_filter, c->stream3));
-      launch_fast_filter(fast_launch(c), dim3(fblocks), pd, nd, bt, prm);
-      HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_filter, 0));
-      tp_split = true;
-    } else if (c->tp_filter >= 6u && fblocks && throughput && c->S <= 4u) {
-      // both roles in one launch, the Filter role by the transposed item (the default of the throughput regime)
-      launch_fast_bt(fast_launch(c), dim3(scan_blocks + fblocks), nd, bt, prm, share_b, scan_blocks);
-    } else if (c->tp_filter && fblocks && throughput) {
-      // the throughput regime with the two roles as launches of their own: the scan at its register footprint, the Filter loop at a
-      // leaner one (more resident waves); same stream, the scan first — its items are dependent-load chains that would otherwise sit
-      // in the wave slots the Filter loop can fill
-      launch_fast_scan(fast_launch(c), dim3(scan_blocks), bt, prm, share_b);
-      launch_fast_filter(fast_launch(c), dim3(fblocks), pd, nd, bt, prm);
-      tp_split = true;
-    } else {
-      launch_fast_b(fast_launch(c), dim3(scan_blocks + fblocks), pd, nd, bt, prm, share_b, scan_blocks);
-    }
-  });
-  if (c->host_probe) {
-    const uint64_t hp4 = host_ns();
-    c->hp_ns[0] += c->hp_t1 - c->hp_t0; c->hp_ns[1] += hp1 - c->hp_t1; c->hp_ns[2] += hp2 - hp1; c->hp_ns[3] += hp3 - hp2; c->hp_ns[4] += hp4 - hp3;
-    c->hp_n++;
-  }
-  c->launches = 2;
-  if (!fused) {                                      // the throughput regime (or a grid the chip cannot hold at once): launch C on its own
-    TIMED(c, BS_KERNEL_RESOLVE, hipLaunchKernelGGL(k_fast_final, dim3(cdiv(P, 256)), dim3(256), 0, c->stream, pd, gr, nd, b, prm, cdiv(P, kTblChunk)));
-    c->launches = tp_split ? 4 : 3;
-  }
+// the batch view shifted to one table's slot (slot index 0 == slot)
+static BatchDev table_view(const bs_ctx* c, const BatchDev& b, const BatchParams& prm, uint32_t slot) {
+  BatchDev bt = b;
+  bt.tables = b.tables + (size_t)slot * prm.mcap * prm.LP;
+  bt.kp = b.kp + (size_t)slot * 16;
+  bt.chunk_tot = b.chunk_tot + (size_t)slot * cdiv(c->Ncap, 256) * 16;
+  bt.chunk_kp = b.chunk_kp + (size_t)slot * cdiv(c->Ncap, 256) * 16;
+  bt.gmax = b.gmax + (size_t)slot * cdiv(c->Ncap, 64) * prm.LP;
+  return bt;
+}
+
+// what bs_step_geom.hpp decides from: the context as plain values (dirs_ready is refreshed by run_fast behind build_dirs)
+static StepIn step_in(const bs_ctx* c, bool run_filter) {
+  StepIn in{};
+  in.P = c->P; in.G = c->G; in.N = c->N; in.M = c->M; in.S = c->S; in.W = cdiv(c->N, 64);
+  in.kinfo_pending = c->kinfo_pending; in.h_K = c->h_K; in.k_bound = c->k_bound; in.k_host = c->kinfo_pending ? 0u : c->h_K;
+  in.step_a_form = c->step_a_form; in.step_a_on = c->step_a_on; in.step_shares = c->step_shares;
+  in.filter_waves = c->filter_waves; in.filter_waves_env = c->filter_waves_env;
+  in.tp_filter = c->tp_filter; in.tp_share = c->tp_share; in.tp_fwaves = c->tp_fwaves; in.tp_tmin = c->tp_tmin;
+  in.target_waves = c->target_waves; in.scan_share = c->scan_share_override; in.nranks = c->nranks;
+  in.run_filter = run_filter; in.dirs_ready = c->dirs_ready;
+  in.ranges_valid = c->ranges_valid && c->d_pod_ranges.p; in.nranges = c->nranges;
+  in.whole_bufs = c->d_first_row64.p && c->d_scan_rec.p && c->d_feas_rec.p && c->d_chunk_rec.p;
+  in.no_fuse_final = c->no_fuse_final; in.no_nodew = c->no_nodew; in.have_nodew = c->d_nodew.p != nullptr;
+  in.collect_stats = c->collect_stats; in.enable_timing = c->cfg.enable_timing;
+  return in;
+}
+
+// Behind the last launch of a steady-state step: Filter's deny pass, the commit kernel with the carried leader and the group flags brought
+// home, and the collective.
+static int fast_commit_tail(bs_ctx* c, uint32_t stages, const PodsDev& pd, const GroupsDev& gr, const NodesDev& nd, const BatchDev& b, const BatchParams& prm) {
+  int rc;
+  const uint32_t P = c->P, G = c->G;
   if (prm.filter_deny && (rc = launch_filter_deny(c, pd, gr, nd, b, prm, true))) return rc;
-  if (commit) {
+  if (prm.commit) {
     if (prm.filter_deny && (rc = launch_filter_deny_marks(c, b, prm, b.fast_reject))) return rc;
     if (G) hipLaunchKernelGGL(k_fast_commit, dim3(cdiv(G, 256)), dim3(256), 0, c->stream, pd, b, const_cast<uint8_t*>(gr.flags),
                               const_cast<uint64_t*>(gr.occupied), G, prm.filter_deny ? b.fd_flag : nullptr);
@@ -1943,6 +1788,142 @@ static int run_fast(bs_ctx* c, uint32_t stages) {
     c->launches++;
   }
   return batch_collective(c, stages, gr, b);
+}
+
+// Launch B of the steady-state chain in the form the plan names: node scan over the class slots | Filter evaluation over the Filter slots
+static int launch_b(bs_ctx* c, const LaunchBPlan& pl, const FastLaunch& fl, const PodsDev& pd, const GroupsDev& gr, const NodesDev& nd, const BatchDev& b,
+                    const BatchDev& bt, const BatchParams& prm) {
+  switch (pl.form) {
+    case LaunchB::kFused:
+      // ... and launch C in the same launch: final codes, Filter code / slot / feasible count per pod, admit counts, quorum
+      launch_fast_bc(fl, dim3(pl.fused_grid), pd, gr, nd, b, bt, prm, pl.nseg, pl.scan_blocks, pl.fblocks);
+      break;
+    case LaunchB::kTwoStreams: {
+      // the two roles as launches of their own, SIDE BY SIDE: the scan on the side stream (its items are chains of dependent loads,
+      // its 130-odd VGPRs its own business), the transposed Filter item at seven waves per SIMD on the main one; both read what launch
+      // A wrote and write disjoint outputs for the final launch, which waits for both
+      FastLaunch side = fl;
+      side.stream = c->stream3;
+      HIPCHK(c, hipEventRecord(c->ev_query, c->stream));
+      HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_query, 0));
+      launch_fast_scan(side, dim3(pl.scan_blocks), bt, prm, pl.share_b);
+      HIPCHK(c, hipEventRecord(c->ev_filter, c->stream3));
+      launch_fast_filter(fl, dim3(pl.fblocks), pd, nd, bt, prm);
+      HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_filter, 0));
+      break;
+    }
+    case LaunchB::kTransposed:
+      // both roles in one launch, the Filter role by the transposed item (the default of the throughput regime)
+      launch_fast_bt(fl, dim3(pl.scan_blocks + pl.fblocks), nd, bt, prm, pl.share_b, pl.scan_blocks);
+      break;
+    case LaunchB::kScanThenFilter:
+      // the throughput regime with the two roles as launches of their own: the scan at its register footprint, the Filter loop at a
+      // leaner one (more resident waves); same stream, the scan first — its items are dependent-load chains that would otherwise sit
+      // in the wave slots the Filter loop can fill
+      launch_fast_scan(fl, dim3(pl.scan_blocks), bt, prm, pl.share_b);
+      launch_fast_filter(fl, dim3(pl.fblocks), pd, nd, bt, prm);
+      break;
+    case LaunchB::kPlain:
+      launch_fast_b(fl, dim3(pl.scan_blocks + pl.fblocks), pd, nd, bt, prm, pl.share_b, pl.scan_blocks);
+      break;
+  }
+  return BS_OK;
+}
+
+// The steady-state chain (bs_fast.hpp): nothing reset, no wait.  WHICH launches, their grids and what they add to the tickets: the two plans
+// of bs_step_geom.hpp; here are the device views, the two residency questions, the launches and the timers.
+static int run_fast(bs_ctx* c, uint32_t stages) {
+  int rc;
+  const uint32_t P = c->P, G = c->G, N = c->N;
+  const bool run_filter = stages & BS_STAGE_FILTER;
+  NodesDev nd = nodes_dev(c);
+  GroupsDev gr = groups_dev(c);
+  PodsDev pd = pods_dev(c);
+  BatchDev b = batch_dev(c);
+  BatchParams prm = chain_params(c, stages, true);
+  prm.commit = (stages & BS_BATCH_COMMIT) ? 1u : 0u;
+  if ((rc = setup_host_out(c, stages, run_filter, b, prm))) return rc;
+  const uint32_t side_slot = (uint32_t)c->steady_table;
+  const uint32_t nchunks = table_chunks(c->M);
+  BatchDev bt = table_view(c, b, prm, side_slot);    // the steady table's slot
+  const TableDesc* forced = b.desc + side_slot;
+  if (prm.commit && G) HIPCHK(c, hipMemsetAsync(c->d_fast_reject.p, 0xFF, (size_t)G * 4, c->stream));
+
+  // K is known on the host once its copy from the pod load / queue patch has landed — never waited for here; when it is, the
+  // kernels need not fetch it in front of everything else
+  if (c->kinfo_pending && hinfo_get(c, kHiKTag) == c->kinfo_tag && (rc = resolve_pods(c))) return rc;
+  StepIn in = step_in(c, run_filter);
+  prm.k_host = in.k_host;
+  const uint64_t hp1 = c->host_probe ? host_ns() : 0;
+  // ---- launch A and the scan / Filter roles of launch B as ONE launch (k_fast_step_a), then k_fast_final unless the pod blocks go on to the verdicts
+  // The class-slot forms need the class directory (ckeys / cpres: class id -> request lanes).  It is built once per derivation of the queue — like bs_pods_apply's first call — and only when the
+  // queue's classes and pairs are already resolved on the host (pairs_ready / rep_valid: the pod load's class count has landed; never waited for here): a caller that re-uploads its queue and
+  // scores it at once takes the two-launch chain and pays neither the directory kernel nor a stream wait.  So the FIRST batch over a fresh queue is of either form (both equal the oracle).
+  const uint32_t K = step_k(in);
+  const bool dirs_buildable = c->batch_since_pods && c->pairs_ready && c->rep_valid && c->have_groups;
+  if (step_a_possible(in, K, nchunks) && (c->step_a_form == 1u || c->dirs_ready || dirs_buildable)) {
+    if (c->step_a_form >= 2u && !c->dirs_ready && dirs_buildable && (rc = build_dirs(c))) return rc;
+    in.dirs_ready = c->dirs_ready;
+    const StepAPlan pa = step_a_plan(in, K);
+    // the whole-step form's pod blocks take bs_pods_load's gang-aligned ranges (bs_pod_ranges.hpp) when the queue is still the loaded one; a gang inside
+    // one range is closed in LDS by its block (tally_tail_whole) wherever the returning-atomic quorum would run: tally with ready, no Filter-deny pass
+    if (pa.ranges) b.pod_ranges = c->d_pod_ranges.as<uint32_t>();
+    if (pa.ready && (int)pa.grid <= step_a_residency(c, pa.whole)) {
+      TIMED(c, BS_KERNEL_QUERY, {
+        launch_fast_step_a(fast_launch(c), dim3(pa.grid), pd, gr, nd, b, bt, prm, forced, pa.nchunks, pa.qb, pa.nshares, pa.fblocks, c->tk_pods, c->tk_tab, pa.pb,
+                           c->d_ckeys.as<int64_t>(), c->d_cpres.as<uint32_t>(), c->pair_cap, pa.whole ? 1u : 0u, c->tk_p1, c->tk_done, side_slot - c->C);
+      });
+      c->tk_pods += pa.tk_pods;
+      c->tk_tab += pa.tk_tab;
+      c->tk_p1 += pa.tk_p1;
+      c->tk_done += pa.tk_done;
+      if (!pa.whole) TIMED(c, BS_KERNEL_RESOLVE, hipLaunchKernelGGL(k_fast_final, dim3(cdiv(P, 256)), dim3(256), 0, c->stream, pd, gr, nd, b, prm, cdiv(P, kTblChunk)));
+      c->launches = pa.launches;
+      c->last_step_a = true;
+      if (c->test_timeout_after && --c->test_timeout_after == 0 && c->h_info.p) {      // test hook: what a block whose wait ran out does (bs_fast.hpp, kSpinBound)
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        hinfo_set(c, kHiHandoverErr, 1);
+      }
+      return fast_commit_tail(c, stages, pd, gr, nd, b, prm);
+    }
+  }
+  c->last_step_a = false;
+  // the throughput regime (more than 16 tiles of class slots) is known before launch A: when launch B will take the transposed Filter item,
+  // launch A's grid carries the node-word blocks (node_words_block) behind the table chunks
+  LaunchBPlan pl = launch_b_plan(in);
+  if (pl.node_words) {
+    b.nodew = bt.nodew = c->d_nodew.as<uint64_t>();
+    b.nodew_stride = bt.nodew_stride = nodew_stride(N);
+    b.tiles2_min = bt.tiles2_min = pl.tiles2_min;
+  }
+  // ---- launch A: per-pod decisions, scan / Filter slots | chunk-local running sums of the table
+  TIMED(c, BS_KERNEL_QUERY, {
+    const uint32_t qb = cdiv(P, kTblChunk);
+    const dim3 qg(qb + nchunks + (pl.node_words ? nodew_blocks(N) : 0u)), blk(kTblChunk);
+    lanes_narrow(c->S, [&](auto s) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fast_query_tables<decltype(s)::value>), qg, blk, 0, c->stream, pd, gr, nd, b, bt, prm, forced, nchunks, qb);
+    });
+  });
+  const uint64_t hp2 = c->host_probe ? host_ns() : 0;
+  uint64_t hp3 = 0;
+  // ---- launch B: node scan over the class slots | Filter evaluation over the Filter slots
+  // The work loops size themselves on the device (the class count lives there); the grid only has to be large enough.
+  TIMED(c, BS_KERNEL_SCAN, {
+    // the fused form waits inside itself: only when every block of its grid is resident at once (see fused_residency)
+    if (pl.form == LaunchB::kFused && (int)pl.fused_grid > fused_residency(c)) pl = launch_b_plan(in, false);
+    prm.scan_nsub = pl.scan_nsub;
+    hp3 = c->host_probe ? host_ns() : 0;
+    if ((rc = launch_b(c, pl, fast_launch(c, pl.filter_waves), pd, gr, nd, b, bt, prm))) return rc;
+  });
+  if (c->host_probe) {
+    const uint64_t hp4 = host_ns();
+    c->hp_ns[0] += c->hp_t1 - c->hp_t0; c->hp_ns[1] += hp1 - c->hp_t1; c->hp_ns[2] += hp2 - hp1; c->hp_ns[3] += hp3 - hp2; c->hp_ns[4] += hp4 - hp3;
+    c->hp_n++;
+  }
+  // the throughput regime (or a grid the chip cannot hold at once): launch C on its own
+  if (pl.form != LaunchB::kFused) TIMED(c, BS_KERNEL_RESOLVE, hipLaunchKernelGGL(k_fast_final, dim3(cdiv(P, 256)), dim3(256), 0, c->stream, pd, gr, nd, b, prm, cdiv(P, kTblChunk)));
+  c->launches = pl.launches;
+  return fast_commit_tail(c, stages, pd, gr, nd, b, prm);
 }
 
 // The positional chain (bs_epoch.hpp): three launches for batches in which captures, MinResources defaults or a leader
@@ -1992,16 +1973,7 @@ static int run_epoch(bs_ctx* c, uint32_t stages, bool* taken) {
   GroupsDev gr = groups_dev(c);
   PodsDev pd = pods_dev(c);
   BatchDev b = batch_dev(c);
-  BatchParams prm = batch_params(c);
-  prm.run_filter = run_filter;
-  prm.use_classes = 0;
-  prm.fuse_filter = run_filter ? 1u : 0u;
-  prm.scan_slots_cap = c->scan_slots_cap;
-  prm.filter_slots_cap = c->filter_slots_cap;
-  prm.stamp = 1u + c->stamp_ctr;
-  prm.seq_inv = ~c->key_seq;
-  prm.do_tally = (stages & BS_STAGE_TALLY) ? 1u : 0u;
-  prm.do_ready = (prm.do_tally && c->nranks == 1 && !c->reduce_external) ? 1u : 0u;
+  BatchParams prm = chain_params(c, stages, false);
   EpochDev ep{};
   ep.run_of_epoch = c->d_run_of_epoch.as<uint32_t>();
   ep.run_leader = c->d_run_leader.as<int32_t>();
@@ -2033,7 +2005,7 @@ static int run_epoch(bs_ctx* c, uint32_t stages, bool* taken) {
     const uint32_t nseg = c->scan_share_override ? c->scan_share_override
                                                  : std::max<uint32_t>(2, std::min<uint32_t>(64, wave_cap / (2 * std::max<uint32_t>(tiles, 1))));
     const uint32_t scan_blocks = std::max<uint32_t>(1, cdiv(std::min<uint32_t>(wave_cap, 2 * std::max<uint32_t>(tiles, 1) * std::min<uint32_t>(nseg, cdiv(c->M, 64))), 4));
-    const uint32_t fblocks = run_filter ? std::max<uint32_t>(1, cdiv(std::min<uint32_t>(c->filter_waves, cdiv(filter_slots, 64) * std::max<uint32_t>(1, cdiv(W, 2))), 4)) : 0u;
+    const uint32_t fblocks = run_filter ? std::max<uint32_t>(1, filter_blocks(c->filter_waves, cdiv(filter_slots, 64), W)) : 0u;
     const dim3 grid(scan_blocks + fblocks);
     lanes_wide(c->S, [&](auto s) {
       hipLaunchKernelGGL(HIP_KERNEL_NAME(k_epoch_scan_filter<decltype(s)::value>), grid, dim3(256), 0, c->stream, pd, nd, b, prm, ep, c->M, nseg, c->G, scan_blocks,
@@ -2068,8 +2040,8 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
     const size_t g1 = std::max<uint32_t>(c->G, 1);
     if ((rc = reserve_filled(c, c->d_fd_event, g1 * 8, 0xFF)) || (rc = reserve_filled(c, c->d_fd_in, g1 * 4, 0xFF)) || (rc = reserve_filled(c, c->d_fd_flag, 16, 0))) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_fd_flag.p, 0, 4, c->stream));
-    ((volatile int32_t*)c->h_info.p)[14] = 0;
-    ((volatile int32_t*)c->h_info.p)[15] = 0;
+    hinfo_set(c, kHiFdFound, 0);
+    hinfo_set(c, kHiFdChanged, 0);
   }
   const uint32_t P = c->P, G = c->G, N = c->N, C = c->C;
   // fit-class indices address fit rows and running-sum tables on the device: out of range = refuse the batch
@@ -2080,7 +2052,7 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
   // findMaxPG's answer for the patched groups: taken if it has landed; guessed (last cycle's table) if it has not and the state is a
   // steady one — the guess is checked when the results are first asked for (batch_settle)
   c->spec_active = false;
-  if (c->info_pending && ((volatile int32_t*)c->h_info.p)[3] != c->info_tag && !c->no_spec && c->steady_prev >= 0 && (uint32_t)c->steady_prev < 2 * c->C && c->n_uncaptured == 0 &&
+  if (c->info_pending && hinfo_get(c, kHiGroupTag) != c->info_tag && !c->no_spec && c->steady_prev >= 0 && (uint32_t)c->steady_prev < 2 * c->C && c->n_uncaptured == 0 &&
       c->n_nominres == 0 && !(stages & BS_BATCH_COMMIT) && c->cfg.enable_timing < 2 && !c->collect_stats && c->nranks == 1 && !c->reduce_external &&
       c->fd_iter == 0 && !c->groups_launch_pending && !c->ext_admit) {
     c->steady_table = c->steady_prev;
@@ -2102,8 +2074,6 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
   const uint32_t W = cdiv(N, 64);
   const bool run_filter = stages & BS_STAGE_FILTER;
   if ((rc = reserve_slots(c, run_filter))) return rc;
-  const uint32_t scan_cap = c->scan_slots_cap, filter_cap = c->filter_slots_cap;
-  (void)W;
   // slot stamps are 1 + stamp_ctr: when the stamp starts over, a slot nobody wrote for 65535 batches would look live again
   if (c->stamp_ctr == 0) {
     if (c->d_qstamp_s.p) HIPCHK(c, hipMemsetAsync(c->d_qstamp_s.p, 0, c->d_qstamp_s.cap, c->stream));
@@ -2167,8 +2137,7 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
   GroupsDev gr = groups_dev(c);
   PodsDev pd = pods_dev(c);
   BatchDev b = batch_dev(c);
-  BatchParams prm = batch_params(c);
-  prm.run_filter = run_filter;
+  BatchParams prm = chain_params(c, stages, use_classes, false);
   const uint32_t tiles_est = cdiv(std::max<uint32_t>(P, 1), 64);
   // J waves share the live 64-row groups of one tile (k_scan deals them round-robin).  Measured on the cold batches
   // (tools/cold_sweep.py): almost every query ends inside the first one or two live groups, and every extra share is a
@@ -2176,9 +2145,6 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
   // 319 us (cfg4 cold).  So: at most two shares, and a grid that just covers tiles x tables.
   const uint32_t nseg = c->scan_share_override ? c->scan_share_override : 2u;
   const dim3 blk(256);
-  prm.use_classes = use_classes ? 1u : 0u;
-  prm.scan_slots_cap = scan_cap;
-  prm.filter_slots_cap = filter_cap;
   bool commit_dirty = false;
   const uint32_t side_slot = inline_tables ? (uint32_t)c->steady_table : 0u;
   prm.early_filter = early_filter ? 1u : 0u;
@@ -2191,16 +2157,8 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
   const uint32_t nchunks = std::max<uint32_t>(1, cdiv(c->M, 256));
   uint32_t launches = 0;
   // one known table: it is built inside the first two launches (k_prepass_tables / k_query_tables)
-  BatchDev bt = b;                                                       // the batch view shifted to the table's slot (slot index 0)
-  const TableDesc* forced = nullptr;
-  if (inline_tables) {
-    bt.tables = b.tables + (size_t)side_slot * prm.mcap * prm.LP;
-    bt.kp = b.kp + (size_t)side_slot * 16;
-    bt.chunk_tot = b.chunk_tot + (size_t)side_slot * cdiv(c->Ncap, 256) * 16;
-    bt.gmax = b.gmax + (size_t)side_slot * cdiv(c->Ncap, 64) * prm.LP;
-    bt.chunk_kp = b.chunk_kp + (size_t)side_slot * cdiv(c->Ncap, 256) * 16;
-    forced = b.desc + side_slot;
-  }
+  const BatchDev bt = table_view(c, b, prm, side_slot);                  // (slot 0 = the view itself when there is no such table)
+  const TableDesc* forced = inline_tables ? b.desc + side_slot : nullptr;
 
   // ---- per-batch resets + eligibility (+ findMaxPG when no first-pod capture can occur)
   TIMED(c, BS_KERNEL_PREPASS, {
@@ -2269,16 +2227,14 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
     const uint32_t tiles_guess = std::max(cdiv(G, 64), std::min(tiles_est, cdiv(G, 64) * 4)) + 1;
     const uint32_t scan_blocks = std::max<uint32_t>(1, cdiv(std::min<uint32_t>(c->general_waves, tiles_guess * tsplit * std::min<uint32_t>(nseg, cdiv(c->M, 64))), 4));
     if (fuse_filter) {
-      const uint32_t fblocks = cdiv(std::min<uint32_t>(c->filter_waves, 2 * cdiv(P, 64) * std::max<uint32_t>(1, cdiv(W, 2))), 4);
-      TIMED(c, BS_KERNEL_SCAN, launch_scan_filter(c, scan_blocks, fblocks, pd, nd, b, prm, c->M, nseg, P, G, tsplit, local));
+      TIMED(c, BS_KERNEL_SCAN, launch_scan_filter(c, scan_blocks, filter_blocks(c->filter_waves, 2 * cdiv(P, 64), W), pd, nd, b, prm, c->M, nseg, P, G, tsplit, local));
     } else {
       TIMED(c, BS_KERNEL_SCAN, launch_scan(c, dim3(scan_blocks), b, prm, c->M, nseg, P, G, tsplit, local));
     }
     launches++;
   } else if (fuse_filter) {
     // no schedulable node: nothing to scan, Filter still has its slots to evaluate
-    const uint32_t fblocks = cdiv(std::min<uint32_t>(c->filter_waves, 2 * cdiv(P, 64) * std::max<uint32_t>(1, cdiv(W, 2))), 4);
-    TIMED(c, BS_KERNEL_SCAN, launch_scan_filter(c, 1u, fblocks, pd, nd, b, prm, 0u, 1u, P, G, 1u, false));
+    TIMED(c, BS_KERNEL_SCAN, launch_scan_filter(c, 1u, filter_blocks(c->filter_waves, 2 * cdiv(P, 64), W), pd, nd, b, prm, 0u, 1u, P, G, 1u, false));
     launches++;
   }
   // ---- REJECT codes, deny replay, stale-leader propagation, Filter parameters
@@ -2353,8 +2309,8 @@ static int batch_run_inner(bs_ctx* c, uint32_t stages) {
 // The results of a run that is thrown away (a wrong guess, a superseded fixed-point iteration) take their hand-over error word with them:
 // the re-run reports its own.  The lesson is kept: separate launches from now on.
 static void discard_handover(bs_ctx* c) {
-  if (c->h_info.p && ((volatile int32_t*)c->h_info.p)[12]) {
-    ((volatile int32_t*)c->h_info.p)[12] = 0;
+  if (c->h_info.p && hinfo_get(c, kHiHandoverErr)) {
+    hinfo_set(c, kHiHandoverErr, 0);
     c->no_fuse_final = 1;
   }
 }
@@ -2363,8 +2319,7 @@ static int fd_resolve(bs_ctx* c) {
   if (!c->fd_active) return BS_OK;
   c->fd_active = false;
   c->fd_unsynced = false;                            // (every caller has waited for the batch)
-  volatile int32_t* hf = c->h_info.p + 14;
-  if (!hf[0]) return BS_OK;
+  if (!hinfo_get(c, kHiFdFound)) return BS_OK;
   int rc = BS_OK;
   bool settled = false;
   const uint32_t stages = c->fd_stages;
@@ -2383,7 +2338,7 @@ static int fd_resolve(bs_ctx* c) {
     if (rc == BS_OK) rc = hipStreamSynchronize(c->stream) == hipSuccess ? BS_OK : BS_ERR_HIP;
     c->n_fd_reruns++;
     if (rc) break;
-    settled = !hf[1];
+    settled = !hinfo_get(c, kHiFdChanged);
   }
   c->fd_in_live = false;
   c->fd_iter = 0;

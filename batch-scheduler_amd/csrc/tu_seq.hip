@@ -44,7 +44,7 @@ int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
   if (G > 0x7FFFFFF0u) return BS_ERR_CAPACITY;
   c->seq_wait_valid = false;                                // the pass replaces the waiting state
   // the first-fit cursors are keyed by the resident queue's request classes: a queue patch whose insert wave ran out of class ids
-  // (h_info[13], set by the device) left them unusable until the queue is re-derived — check_handover does that
+  // (kHiIdOverflow of h_info, set by the device) left them unusable until the queue is re-derived — check_handover does that
   HIPCHK(c, hipStreamSynchronize(c->stream));
   // An unread batch's error words are looked at here (the id overflow concerns this pass: check_handover re-derives the queue) but they stay
   // that batch's: batch_void keeps every later read of it failing with BS_ERR_RETRY until bs_batch_run starts a new one.  The pass itself

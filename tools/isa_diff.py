@@ -24,7 +24,8 @@ def kernels(lib):
     out = {}
     with tempfile.TemporaryDirectory() as d:
         fat = os.path.join(d, "fat")
-        subprocess.run([f"{LLVM}/llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", lib], check=True)
+        # (an output file of its own: with the input alone, objcopy writes its copy back over the library)
+        subprocess.run([f"{LLVM}/llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", lib, os.path.join(d, "copy")], check=True)
         blob = open(fat, "rb").read()
         starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
         for n, a in enumerate(starts):
