@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "bs_groups_list_apply", "bs_groups_list_apply_flat",
     "bs_bound_bind",
     "bs_nominated_load", "bs_nominated_count", "bs_nominated_ids", "bs_nominated_read", "bs_nominated_apply", "bs_preempt_nominated_read",
+    "bs_nominated_nodes_apply",
 ]
 
 SEQ_EXPIRE_DENY, SEQ_EXPIRE_ALL = 1, 2    # bs_seq_expire flags
@@ -270,6 +271,7 @@ def load_library(path: str | None = None):
     L.bs_nominated_read.argtypes = [vp, P(u32), P(u32), P(i32), P(C.c_int64), P(u32)]
     L.bs_nominated_apply.argtypes = [vp, u32, P(u32), u32, P(u32), P(u32), P(i32), P(u32)]
     L.bs_preempt_nominated_read.argtypes = [vp, u32, P(u32)]
+    L.bs_nominated_nodes_apply.argtypes = [vp, u32, P(u32), P(u32), u32, P(u32), P(u32), P(i32), P(u32)]
     L.bs_bound_bind.argtypes = [vp, u32, P(u32), u32, P(u32), P(i32), P(C.c_int64), P(u8), P(u32), P(u32)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
@@ -820,6 +822,23 @@ class Context:
                                                _u32p(nd) if nd.size else None, pr.ctypes.data_as(C.POINTER(C.c_int32)) if pr.size else None,
                                                C.byref(first)), "bs_nominated_apply")
         return int(first.value)
+
+    def nominated_nodes_apply(self, kind, index, cap: int | None = None):
+        """bs_nominated_nodes_apply: the nominated-pod table follows the node-list surgery of the apply_node_deltas call(s) before it — kind
+        and index are those deltas' fields, in order.  Rows on removed nodes leave (their ids are dead), the others keep their ids and get
+        their nodes' new indices.  Returns (ids, old_nodes, priorities, n): the dropped rows in ascending id (at most cap; the default
+        holds the whole table) and their true number."""
+        kv = np.ascontiguousarray(np.asarray(kind, np.uint32).reshape(-1))
+        iv = np.ascontiguousarray(np.asarray(index, np.uint32).reshape(-1))
+        assert kv.size == iv.size
+        cap = self.nominated_count() if cap is None else int(cap)
+        i_, nd, pr = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.int32)
+        n = C.c_uint32(0)
+        self._chk(self._lib.bs_nominated_nodes_apply(self._h, int(kv.size), _u32p(kv) if kv.size else None, _u32p(iv) if iv.size else None, cap,
+                                                     _u32p(i_) if cap else None, _u32p(nd) if cap else None,
+                                                     pr.ctypes.data_as(C.POINTER(C.c_int32)) if cap else None, C.byref(n)), "bs_nominated_nodes_apply")
+        k = min(int(n.value), cap)
+        return i_[:k].copy(), nd[:k].copy(), pr[:k].copy(), int(n.value)
 
     def preempt_nominated_read(self, count: int) -> np.ndarray:
         """bs_preempt_nominated_read: the row id per preemptor of the last preemption call with nominate=True, NOM_NONE where none"""

@@ -18,6 +18,12 @@
 //                   resident queue at pod_index[k] (as k_wt_gather stores a waiting pod), appended behind the survivors.
 //   k_nm_chains     one thread per row of the new table: nnext[row] = exchange(nhead[node], row) (nhead was filled with kNmNone); thread 0
 //                   writes the NomView of the new table beside it.
+// The table follows node-list surgery (bs_nominated_nodes_apply) by one more kernel into the twin; k_nm_chains then runs for the new count:
+//   k_nn_move<S>    k_nm_move's walk with another test: the host hands over the sorted OLD nodes that leave (bs_bound_nodes_replay.hpp);
+//                   every thread makes the one binary search of its row's node k in that list (lo = removed nodes below k: the row is gone
+//                   when rem[lo] == k, else its node becomes k - lo).  A survivor goes to base + rank with the new node; a dropped row
+//                   goes to output row e - (survivors in front of it) as (id, OLD node, priority); thread 0 leaves the two counts.  It
+//                   carries another prefix because tests/test_nominated_cpu.py counts the k_nm_* set.
 // The victim search reads the table through NomView and pre_nominees<S> (bs_preempt.hpp); with no table, or an empty one, the view is null.
 // Lanes are indexed by unrolled constants only (no scratch in any instantiation).
 #pragma once
@@ -124,6 +130,71 @@ __global__ __launch_bounds__(256) void k_nm_gather(NomDev a, PodsDev pd) {
     else if (l == 3) v = 1;
     else if ((pres >> (l - 4)) & 1u) v = pd.req[(size_t)l * pd.p + p];
     a.dst.req[(size_t)l * a.dst.stride + d] = v;
+  }
+}
+
+// bs_nominated_nodes_apply: the live table, the twin, the removed OLD nodes and where the dropped rows go
+struct NomNodesDev {
+  NomTab src, dst;
+  uint32_t W;               // rows of src
+  const uint32_t* rem;      // [R] OLD node indices that leave, ascending, distinct (one H2D block)
+  uint32_t R;
+  uint32_t* o_id;           // [W] the dropped rows in ascending id: id, OLD node, priority
+  uint32_t* o_node;
+  int32_t* o_prio;
+  uint32_t* info;           // [2] survivors, dropped rows
+};
+
+template <int S>
+__global__ __launch_bounds__(kNmWindow) void k_nn_move(NomNodesDev a) {
+  constexpr int L = 4 + S;
+  constexpr uint32_t kWaves = kNmWindow / 64;
+  __shared__ uint32_t s_cnt[kWaves];
+  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+  uint32_t base = 0;                                        // survivors in the windows before this one (every thread keeps it)
+  for (uint32_t w0 = 0; w0 < a.W; w0 += kNmWindow) {
+    const uint32_t e = w0 + t;
+    const bool in = e < a.W;
+    const uint32_t k = in ? a.src.node[e] : 0u;
+    uint32_t lo = 0, hi = in ? a.R : 0u;                    // removed nodes below k
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (a.rem[mid] < k) lo = mid + 1u;
+      else hi = mid;
+    }
+    const bool gone = in && lo < a.R && a.rem[lo] == k;
+    const bool keep = in && !gone;
+    const uint64_t m = __ballot(keep);
+    if (lane == 0) s_cnt[wave] = (uint32_t)__builtin_popcountll(m);
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (uint32_t x = 0; x < kWaves; ++x) {
+      const uint32_t c = s_cnt[x];
+      before += x < wave ? c : 0u;
+      total += c;
+    }
+    const uint32_t d = base + before + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));   // survivors in front of row e
+    if (keep && d < a.dst.stride) {
+      a.dst.id[d] = a.src.id[e];
+      a.dst.node[d] = k - lo;
+      a.dst.prio[d] = a.src.prio[e];
+      a.dst.pres[d] = a.src.pres[e];
+#pragma unroll
+      for (int l = 0; l < L; ++l) a.dst.req[(size_t)l * a.dst.stride + d] = a.src.req[(size_t)l * a.src.stride + e];
+    }
+    if (gone) {                                             // (d <= e: the output row lies inside [0, W))
+      const uint32_t r = e - d;
+      a.o_id[r] = a.src.id[e];
+      a.o_node[r] = k;
+      a.o_prio[r] = a.src.prio[e];
+    }
+    base += total;
+    __syncthreads();                                        // s_cnt is rewritten by the next window
+  }
+  if (t == 0) {
+    a.info[0] = base;
+    a.info[1] = a.W - base;
   }
 }
 

@@ -1,13 +1,14 @@
 // tu_nominated.hip — translation unit of the resident nominated-pod table: pods nominated by earlier cycles, counted by every fit test of the
-// victim search.  Kernels (bs_nominated.hpp): k_nm_mark and k_nm_chains (no templates: this unit alone includes that header), k_nm_move<S> and
-// k_nm_gather<S>, once per scalar-lane count 0..BS_MAX_SCALARS.  Host: the table's layout, its file-local launch wrappers, the entry points
-// bs_nominated_* (include/bsched.h), and what the preemption calls of tu_preempt.hip use the table through (bs_ctx.hpp): nom_view, nom_state,
-// nom_preempt_state, nom_refusal, nom_apply_rows.
+// victim search.  Kernels (bs_nominated.hpp): k_nm_mark and k_nm_chains (no templates: this unit alone includes that header), k_nm_move<S>,
+// k_nm_gather<S> and k_nn_move<S> (the table follows node-list surgery), once per scalar-lane count 0..BS_MAX_SCALARS.  Host: the table's
+// layout, its file-local launch wrappers, the entry points bs_nominated_* (include/bsched.h), and what the preemption calls of
+// tu_preempt.hip use the table through (bs_ctx.hpp): nom_view, nom_state, nom_preempt_state, nom_refusal, nom_apply_rows.
 #ifndef BS_UNITY
 #define BS_TU_FAMILY
 #endif
 #include "bs_nominated.hpp"
 #include "bs_nominated_check.hpp"
+#include "bs_nominated_nodes_check.hpp"
 #include "bs_ctx.hpp"
 
 #include <cstring>
@@ -74,6 +75,10 @@ void launch_nom_apply(hipStream_t stream, uint32_t S, const NomDev& a, const Pod
     if (a.n_insert) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nm_gather<V>), dim3(cdiv(a.n_insert, 256)), dim3(256), 0, stream, a, pd);
   });
 }
+// the table follows node-list surgery: k_nn_move<S> (one workgroup); the chains follow (launch_nom_chains)
+void launch_nom_nodes(hipStream_t stream, uint32_t S, const NomNodesDev& a) {
+  lanes_wide(S, [&](auto s) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_move<decltype(s)::value>), dim3(1), dim3(kNmWindow), 0, stream, a); });
+}
 int nom_single_rank(bs_ctx* c, const char* who) {
   if (c->nranks > 1 || c->reduce_external) { c->last_error = std::string(who) + " is single-rank only (as bs_preempt_run)"; return BS_ERR_STATE; }
   return BS_OK;
@@ -92,7 +97,7 @@ int bs::nom_state(bs_ctx* c, const char* who) {
   if (const int rc = nom_single_rank(c, who)) return rc;
   if (!c->have_nom) { c->last_error = std::string(who) + ": no nominated-pod table (bs_nominated_load first; m = 0 gives the empty one)"; return BS_ERR_STATE; }
   if (!c->have_nodes || c->nom_n != c->N) {
-    c->last_error = std::string(who) + ": the nominated-pod table was made for another node count (bs_nominated_read before the surgery, a remap on the host, bs_nominated_load)";
+    c->last_error = std::string(who) + ": the nominated-pod table was made for another node count (after node-list surgery: bs_nominated_nodes_apply; else bs_nominated_load)";
     return BS_ERR_STATE;
   }
   return BS_OK;
@@ -100,7 +105,7 @@ int bs::nom_state(bs_ctx* c, const char* who) {
 // what the three preemption calls refuse: rows of a table that was made for another node count
 int bs::nom_preempt_state(bs_ctx* c, const char* who) {
   if (c->have_nom && c->nom_w && c->nom_n != c->N) {
-    c->last_error = std::string(who) + ": the nominated-pod table holds rows and was made for another node count: reload it";
+    c->last_error = std::string(who) + ": the nominated-pod table holds rows and was made for another node count (after node-list surgery: bs_nominated_nodes_apply; else bs_nominated_load)";
     return BS_ERR_STATE;
   }
   return BS_OK;
@@ -256,6 +261,84 @@ int bs_nominated_apply(bs_ctx* c, uint32_t n_remove, const uint32_t* remove_id, 
     if ((rc = nom_apply_rows(c, n_remove, remove_id, n_insert, pod_index, node, priority))) return rc;
   }
   if (first_id_out) *first_id_out = ids;
+  return BS_OK;
+}
+
+// The table follows the node list: the host replays the deltas on the node count the table was made for (bs_nominated_nodes_check.hpp over
+// bs_bound_nodes_replay.hpp: O(count)) and hands the device the sorted removed OLD nodes; one pass into the twin, which nom_reserve lays
+// out for the node count the context holds now, drops the rows on them and renumbers the rest; the chains are made for the new count.
+// A list that only grew takes the same path with an empty removed list: nhead's length belongs to the layout.  Two waits: the survivors'
+// count sizes the chains' launch, then the dropped rows come back.
+int bs_nominated_nodes_apply(bs_ctx* c, uint32_t count, const uint32_t* kind, const uint32_t* index, uint32_t cap, uint32_t* id, uint32_t* node,
+                             int32_t* priority, uint32_t* n_out) {
+  if (!c) return BS_ERR_INVALID;
+  if (nom_nodes_null(count, kind, index, cap, id, node, priority, n_out)) {
+    c->last_error = std::string("bs_nominated_nodes_apply: ") + nom_nodes_check_text(kNomNodesNull);
+    return BS_ERR_INVALID;
+  }
+  int rc = nom_single_rank(c, "bs_nominated_nodes_apply");
+  if (rc) return rc;
+  if (!c->have_nom) { c->last_error = "bs_nominated_nodes_apply: no nominated-pod table (bs_nominated_load first; m = 0 gives the empty one)"; return BS_ERR_STATE; }
+  if (!c->have_nodes) { c->last_error = "bs_nominated_nodes_apply: nodes are not loaded"; return BS_ERR_STATE; }
+  NodeReplay rp;
+  if (const int bad = nom_nodes_check(c->nom_n, c->N, count, kind, index, cap, id, node, priority, n_out, rp)) {
+    c->last_error = std::string("bs_nominated_nodes_apply: ") + nom_nodes_check_text(bad);
+    return nom_nodes_check_is_state(bad) ? BS_ERR_STATE : BS_ERR_INVALID;
+  }
+  const uint32_t W = c->nom_w, R = (uint32_t)rp.removed.size();
+  *n_out = 0;
+  if (!nom_nodes_moves(W, c->nom_n, rp)) {                  // no row, or no old node left and the count kept: nothing is launched
+    c->nom_n = rp.n_new;
+    return BS_OK;
+  }
+  if ((rc = use_device(c))) return rc;
+  const uint32_t cur = c->nom_cur, other = cur ^ 1u;
+  HIPCHK(c, hipStreamSynchronize(c->stream));               // (nothing of an earlier call still reads the twin)
+  HIPCHK(c, nom_reserve(c, other, W));
+  Carve cv;
+  const auto o_rem = cv.take<uint32_t>(R, 4);               // (the call's one H2D block)
+  const auto o_info = cv.take<uint32_t>(2);
+  const auto o_id = cv.take<uint32_t>(W);
+  const auto o_node = cv.take<uint32_t>(W);
+  const auto o_prio = cv.take<int32_t>(W);
+  if (cv.mark() > c->d_pre.cap) HIPCHK(c, c->d_pre.reserve(cv.mark() + cv.mark() / 4));
+  uint8_t* base = c->d_pre.as<uint8_t>();
+  if (R) HIPCHK(c, hipMemcpyAsync(o_rem.in(base), rp.removed.data(), o_rem.bytes(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(o_info.in(base), 0, o_info.bytes(), c->stream));
+  NomNodesDev a{};
+  a.src = nom_tab(c, cur);
+  a.dst = nom_tab(c, other);
+  a.W = W;
+  a.rem = o_rem.in(base);
+  a.R = R;
+  a.o_id = o_id.in(base);
+  a.o_node = o_node.in(base);
+  a.o_prio = o_prio.in(base);
+  a.info = o_info.in(base);
+  // Everything above wrote this call's scratch only (and laid the twin out); the live table is read, never written.
+  launch_nom_nodes(c->stream, c->S, a);
+  LAUNCHCHK(c, BS_KERNEL_PREPASS);
+  uint32_t info[2] = {0, 0};
+  HIPCHK(c, hipMemcpyAsync(info, a.info, sizeof info, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));               // (rp.removed and info are local buffers)
+  const uint32_t kept = info[0], left = info[1];
+  if (kept + left != W || kept > c->nom_cap[other]) { c->last_error = "bs_nominated_nodes_apply: the counts do not add up to the table"; return BS_ERR_HIP; }
+  HIPCHK(c, launch_nom_chains(c, other, kept));
+  LAUNCHCHK(c, BS_KERNEL_PREPASS);
+  std::vector<uint32_t> gone(left);                         // every dropped id: the host's list of live ids follows
+  const uint32_t k = std::min(left, cap);
+  if (left) HIPCHK(c, hipMemcpyAsync(gone.data(), a.o_id, (size_t)left * 4, hipMemcpyDeviceToHost, c->stream));
+  if (k) {
+    HIPCHK(c, hipMemcpyAsync(node, a.o_node, (size_t)k * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(priority, a.o_prio, (size_t)k * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (k) std::memcpy(id, gone.data(), (size_t)k * 4);
+  nom_nodes_live_drop(c->nom_live, gone.data(), gone.size());
+  c->nom_cur = other;
+  c->nom_w = kept;
+  c->nom_n = rp.n_new;
+  *n_out = left;
   return BS_OK;
 }
 }  // extern "C"

@@ -26,7 +26,7 @@ type nominatedRow struct {
 	reqPresent uint32
 }
 
-// loadNominated: a snapshot (a restart, or after node-list surgery with the rows' nodes remapped by the caller).  No rows: the empty
+// loadNominated: a snapshot (a restart; node-list surgery goes through nominatedFollowNodes and keeps the ids).  No rows: the empty
 // table, which BS_PREEMPT_NOMINATE needs before its first call.
 func (g *gpuCore) loadNominated(rows []nominatedRow, lanes int) error {
 	m := len(rows)
@@ -72,7 +72,7 @@ func (g *gpuCore) applyNominated(removed, podIndex, node []uint32, priority []in
 	return uint32(first), nil
 }
 
-// readNominated: the table in table order (ascending id), for reconciliation and for the remap after node-list surgery.
+// readNominated: the table in table order (ascending id), for reconciliation.
 func (g *gpuCore) readNominated(lanes int) ([]nominatedRow, error) {
 	g.mu.Lock()
 	defer g.mu.Unlock()
@@ -97,6 +97,43 @@ func (g *gpuCore) readNominated(lanes int) ([]nominatedRow, error) {
 		}
 	}
 	return rows, nil
+}
+
+// droppedNominees: the rows of the nominated-pod table that left with their nodes, in ascending id.
+type droppedNominees struct {
+	id       []uint32 // the row's id: dead from now on
+	node     []uint32 // the OLD index of the node it was nominated on
+	priority []int32
+}
+
+// nominatedFollowNodes: bs_nominated_nodes_apply — the nominated-pod table follows node-list surgery on the device.  Called after the
+// bs_nodes_apply call(s) it mirrors, with the kind and index fields of their deltas in order; bs_bound_nodes_apply and
+// bs_wait_nodes_apply take the same two arrays, in any order among the three.  Rows on removed nodes leave and come back here: the shim
+// clears those pods' NominatedNodeName and forgets their row ids; every other row keeps its id (the UID -> row id map stays valid) and
+// names its node by the new index.  Every dropped row is taken back: the table holds at most BS_NOM_MAX rows.
+func (g *gpuCore) nominatedFollowNodes(kind, index []uint32) (*droppedNominees, error) {
+	if len(kind) != len(index) {
+		return nil, fmt.Errorf("nominatedFollowNodes: %d kinds, %d indices", len(kind), len(index))
+	}
+	_, pKind := u32s(kind)
+	_, pIndex := u32s(index)
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	var m, n C.uint32_t
+	if rc := C.bs_nominated_count(g.ctx, &m); rc != C.BS_OK {
+		return nil, g.pdbErr("bs_nominated_count", rc)
+	}
+	rows := int(m)
+	oid, onode, oprio := make([]C.uint32_t, rows+1), make([]C.uint32_t, rows+1), make([]C.int32_t, rows+1)
+	if rc := C.bs_nominated_nodes_apply(g.ctx, C.uint32_t(len(kind)), pKind, pIndex, C.uint32_t(rows), &oid[0], &onode[0], &oprio[0], &n); rc != C.BS_OK {
+		return nil, g.pdbErr("bs_nominated_nodes_apply", rc)
+	}
+	k := int(n)
+	d := &droppedNominees{id: make([]uint32, k), node: make([]uint32, k), priority: make([]int32, k)}
+	for i := 0; i < k; i++ {
+		d.id[i], d.node[i], d.priority[i] = uint32(oid[i]), uint32(onode[i]), int32(oprio[i])
+	}
+	return d, nil
 }
 
 // noNominatedRow is what preemptNominatedRead reports for a preemptor that got no node (or whose gang was voided).

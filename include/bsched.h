@@ -993,9 +993,10 @@ int bs_preempt_nominated_read(bs_ctx* ctx, uint32_t count, uint32_t* id_out /*[c
  *                   request: bs_groups_list_apply and bs_pods_apply do not concern the table.
  *   validity        the table remembers the node count it was made for.  While that differs from bs_nodes_count, every call except
  *                   bs_nominated_load, _count and _ids answers BS_ERR_STATE, and with a non-empty table so do bs_preempt_run,
- *                   bs_preempt_commit and bs_preempt_commit_gang.  The way through node-list surgery is bs_nominated_read before it, a
- *                   remap on the host, and bs_nominated_load after it (a remap on the device is not provided).  As for the bound table,
- *                   the test is one of the COUNT.
+ *                   bs_preempt_commit and bs_preempt_commit_gang.  The way through node-list surgery is bs_nominated_nodes_apply (below),
+ *                   which remaps the table on the device and is legal exactly while the other calls refuse the count.  As for the bound
+ *                   table, the test is one of the COUNT: surgery that keeps the count (a REMOVE and an APPEND in one batch) passes it
+ *                   with the rows on the wrong nodes, and bs_nominated_nodes_apply is what puts them right.
  *   bs_nominated_load   a snapshot; needs nodes loaded (BS_ERR_STATE).  m = 0 is valid and yields the empty table.  ids are 0 .. m - 1.
  *                   Validated as a whole: m > BS_NOM_MAX is BS_ERR_CAPACITY; a node >= n, or a NULL column with m > 0, BS_ERR_INVALID.
  *                   Node requests are untouched.
@@ -1011,7 +1012,8 @@ int bs_preempt_nominated_read(bs_ctx* ctx, uint32_t count, uint32_t* id_out /*[c
  *                   a load starts a new id space).  BS_ERR_STATE: no table, a stale node count, pods not loaded with n_insert > 0.
  *                   Both counts 0 is BS_OK and launches nothing.
  * Out of scope: bs_batch_run and bs_seq_run do not see the table (the queue has no priority column); a caller that wants nominees to
- * hold their room against the pass keeps BS_PREEMPT_ASSUME.  Filter-aware preemption.  A device remap after node-list surgery. */
+ * hold their room against the pass keeps BS_PREEMPT_ASSUME.  Filter-aware preemption.
+ * (A device remap after node-list surgery is bs_nominated_nodes_apply, below.) */
 #define BS_NOM_MAX (1u << 16)   /* live rows of the nominated-pod table (its id space: 2^24) */
 int bs_nominated_load(bs_ctx* ctx, uint32_t m, const uint32_t* node, const int32_t* priority, const int64_t* req /*[L][m]*/, const uint32_t* req_present);
 int bs_nominated_count(const bs_ctx* ctx, uint32_t* m_out);
@@ -1019,6 +1021,42 @@ int bs_nominated_ids(const bs_ctx* ctx, uint32_t* ids_out);
 int bs_nominated_read(bs_ctx* ctx, uint32_t* id, uint32_t* node, int32_t* priority, int64_t* req /*[L][m]*/, uint32_t* req_present);
 int bs_nominated_apply(bs_ctx* ctx, uint32_t n_remove, const uint32_t* remove_id, uint32_t n_insert, const uint32_t* pod_index, const uint32_t* node,
                        const int32_t* priority, uint32_t* first_id_out);
+
+/* ---- the nominated-pod table follows node-list surgery --------------------------------------------------------------------------
+ * bs_nodes_apply with BS_DELTA_APPEND / BS_DELTA_REMOVE renumbers the nodes; bs_nominated_nodes_apply gives the nominated-pod table the
+ * same delta list and the table is remapped on the device, instead of a bs_nominated_read, a remap on the host and a bs_nominated_load of
+ * the whole table (which restarts the id space: the caller's UID -> row id map and every id of bs_preempt_nominated_read would be void).
+ * Flat arguments: this form is also the cgo form.
+ *   order        after the bs_nodes_apply call or calls it mirrors: kind[d] and index[d] are the `kind` and `index` fields of their
+ *                deltas, concatenated in order.  Independent of bs_bound_nodes_apply and bs_wait_nodes_apply: any order among the three.
+ *   replay       the list is replayed on the node count the table was made for.  BS_DELTA_UPDATE changes nothing (nominees are no node
+ *                property).  BS_DELTA_APPEND adds a node with no rows.  BS_DELTA_REMOVE of an old node drops every row on it, and the
+ *                nodes behind it move down by one; a REMOVE of a node appended earlier in the list cancels that append (no row can name
+ *                such a node: bs_nominated_apply and BS_PREEMPT_NOMINATE are refused while the count is stale).
+ *   survivors    keep id, priority, request lanes, present bits and order (ascending id); only the node column changes, to the node's
+ *                new index.  bs_nominated_ids is unchanged.
+ *   dropped rows leave the table by the stable compaction.  A dropped id is dead exactly as one removed by bs_nominated_apply: naming it
+ *                later is BS_ERR_INVALID.  Nothing else is touched: nominees are not in the node requests, and rows hold no group.  Why
+ *                a drop and not a stale row: upstream's addNominatedPods runs for the nodes of the snapshot only, so a nominee on a
+ *                deleted node counts for nothing; a row here cannot name a node that no longer exists.
+ *   outputs      *n_out is the true number of dropped rows; the first min(n, cap) come back in ascending id as (id, OLD node index,
+ *                priority).  The result arrays may be NULL when cap == 0.  The resident state is fully applied whatever the cap.
+ *   validity     on success the table's node count becomes the count the replay ended at: the call is legal exactly where the other
+ *                calls are refused for a stale node count (and where surgery kept the count, which it then puts right: the rows are
+ *                remapped).
+ *   errors       all are found on the host before anything resident changes; on any error the table, its ids and its node count are as
+ *                before.  BS_ERR_STATE: no table, nodes not loaded, a replay that ends at a count other than bs_nodes_count (not the
+ *                list bs_nodes_apply got), a sharded or external-reduce context.  BS_ERR_INVALID: a kind outside the three, an UPDATE
+ *                or REMOVE index at or beyond the count current at that point of the replay, NULL kind or index with count > 0, a NULL
+ *                result array with cap > 0, NULL n_out, NULL ctx.  count == 0 is BS_OK when the counts already agree, and launches
+ *                nothing.
+ *   edges        from an empty table and down to an empty table; down to zero nodes where bs_nodes_apply went there.  An empty table,
+ *                or UPDATEs only (no old node leaves and the count stays): nothing is launched, the count is updated.  APPENDs only is
+ *                NOT such a case: the victim search reads one chain head per node, so a table with rows is written again with heads
+ *                for the new count although no row moves.  Synchronous.  Host work is proportional to count plus the dropped rows
+ *                (and one pass over the ids the context keeps, when rows were dropped); the device makes one pass over the table. */
+int bs_nominated_nodes_apply(bs_ctx* ctx, uint32_t count, const uint32_t* kind, const uint32_t* index, uint32_t cap, uint32_t* id, uint32_t* node,
+                             int32_t* priority, uint32_t* n_out);
 /* The live bound table in table order: node ascending, importance order within a node; bs_bound_count entries.  id_out[i] = the
  * entry's id (its index at the last bs_bound_load), node_out[i] = its node.  BS_ERR_STATE before bs_bound_load; the arrays may be NULL
  * when the table is empty. */

@@ -16,7 +16,11 @@ PDBs, the bits recomputed on the device) and, in the same process, the path it r
 pdb.violating_bits over string records of every bound pod, then bs_bound_pdb_set.  --gang FRACTION times bs_preempt_commit_gang (plan only)
 on cfg3 at 64 and 1024 preemptors listed in gang_order, with every need 0 and with needs drawn so that FRACTION of the runs that place
 a member miss their quorum by one (a run that places nobody misses its need of 1 anyway; the row reports the runs that missed in all), beside bs_preempt_commit on the same list in the same process: the plain call five times over (median of --reps calls
-each; their spread is the yardstick's noise), the three calls taking turns."""
+each; their spread is the yardstick's noise), the three calls taking turns.  --nominated-nodes times bs_nominated_nodes_apply (the
+nominated-pod table follows node-list surgery) on the cfg3 node list with a table of 4096 rows, for 1 node removed, 32 removed, and 1 % of
+the nodes removed with as many appended, beside the path it replaces on the same context: bs_nominated_read (before the surgery), a numpy
+remap of the node column, bs_nominated_load; bs_nodes_apply itself is untimed (both paths need it) and every timed call starts from the
+table as loaded."""
 from __future__ import annotations
 
 import argparse
@@ -413,6 +417,81 @@ def gang_rows(config: str, q: int, fraction: float, reps: int, warmup: int, nomi
                  **(dict(nominated=nominated, nominated_rows=nom_rows) if nominated > 0 else {}))]
 
 
+def nominated_nodes_rows(reps: int, warmup: int, table_rows: int = 4096) -> list:
+    capi = bsa.capi
+    cfg = synth.CONFIGS["cfg3"]
+    n, S = cfg["nodes"], cfg["scalars"]
+    _, nodes = synth.make_bound(20260921, n, cfg["groups"], (20, 110), S)
+    fit = synth.make_fit(20260921, n, cfg["classes"])
+    pods, _, prio = synth.make_preemptors(20260921, 64, 4096, cfg["groups"], S, cfg["classes"])
+    rng = np.random.default_rng(20260921 ^ 0x40B)
+    src = rng.integers(0, pods.p, size=table_rows)
+    t_node = rng.integers(0, n, size=table_rows).astype(np.uint32)
+    t_prio, t_req, t_pres = np.asarray(prio)[rng.integers(0, len(prio), size=table_rows)], pods.req[: 4 + S, src], pods.req_present[src]
+
+    def delta(kind, index):
+        d = capi.NodeDelta()
+        d.kind, d.index, d.fit_default = kind, int(index), 1
+        if kind == capi.DELTA_APPEND:                          # a copy of node 0, empty
+            for j in range(4 + S):
+                d.allocatable[j] = int(nodes.allocatable[j, 0])
+            d.allocatable_present = int(nodes.allocatable_present[0])
+        return d
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    rows = []
+    with bsa.Context(scalar_lanes=S, device=0) as ctx:
+        for case, n_rem, n_app in (("1 node removed", 1, 0), ("32 nodes removed", 32, 0), ("1 % removed, as many appended", n // 100, n // 100)):
+            def reload():
+                ctx.load_nodes(nodes, fit)
+                ctx.nominated_load(t_node, t_prio, t_req, t_pres)
+
+            def surgery():
+                """one list surgery from the node list as loaded (untimed) -> (kinds, indices, new index of every old node or -1)"""
+                labels = np.arange(n)
+                deltas = []
+                for _ in range(n_rem):
+                    i = int(rng.integers(0, labels.size))
+                    labels = np.delete(labels, i)
+                    deltas.append(delta(capi.DELTA_REMOVE, i))
+                deltas += [delta(capi.DELTA_APPEND, 0) for _ in range(n_app)]
+                ctx.apply_node_deltas(deltas)
+                new_of_old = np.full(n, -1, np.int64)
+                new_of_old[labels] = np.arange(labels.size)
+                return [d.kind for d in deltas], [d.index for d in deltas], new_of_old
+
+            t_call, t_read, t_remap, t_load, dropped = [], [], [], [], 0
+            for it in range(warmup + reps):
+                reload()                                       # the path the call replaces: read, [surgery], remap on the host, load
+                ms_read, cols = timed(ctx.nominated_read)
+                kinds, idx, new_of_old = surgery()
+
+                def remap():
+                    new = new_of_old[cols["node"]]
+                    keep = new >= 0
+                    return new[keep].astype(np.uint32), cols["priority"][keep], np.ascontiguousarray(cols["req"][:, keep]), cols["req_present"][keep]
+                ms_remap, host = timed(remap)
+                ms_load, _ = timed(lambda: ctx.nominated_load(*host))
+                reload()                                       # the call
+                kinds, idx, new_of_old = surgery()
+                ms_call, out = timed(lambda: ctx.nominated_nodes_apply(kinds, idx))
+                assert out[3] == int((new_of_old[t_node] < 0).sum()) and ctx.nominated_count() == table_rows - out[3]
+                dropped += out[3]
+                if it >= warmup:
+                    t_call.append(ms_call), t_read.append(ms_read), t_remap.append(ms_remap), t_load.append(ms_load)
+            med = lambda v: float(np.median(v))                    # noqa: E731
+            host_ms = med(np.array(t_read) + np.array(t_remap) + np.array(t_load))
+            rows.append(dict(config="cfg3", nodes=n, table_rows=table_rows, case=case, removed=n_rem, appended=n_app,
+                             nodes_apply_ms=round(med(t_call), 4), nodes_apply_ms_min=round(min(t_call), 4), read_remap_load_ms=round(host_ms, 4),
+                             read_ms=round(med(t_read), 4), remap_ms=round(med(t_remap), 4), load_ms=round(med(t_load), 4),
+                             dropped_per_call=round(dropped / (warmup + reps), 1), read_remap_load_over_nodes_apply=round(host_ms / med(t_call), 2)))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -428,7 +507,12 @@ def main():
                     "their quorum) beside bs_preempt_commit")
     ap.add_argument("--nominated", type=float, default=0.0, metavar="FRACTION", help="share of the nodes that hold one row of the nominated-pod table "
                     "(priorities drawn from the preemptors'); with the default scene, --commit and --gang")
+    ap.add_argument("--nominated-nodes", action="store_true", help="bs_nominated_nodes_apply on cfg3 with 4096 rows (1 node removed, 32 removed, 1 %% "
+                    "removed with as many appended), vs bs_nominated_read + a numpy remap + bs_nominated_load")
     a = ap.parse_args()
+    if a.nominated_nodes:
+        print(json.dumps(dict(metric="bs_nominated_nodes_apply ms per call", rows=nominated_nodes_rows(a.reps, a.warmup))))
+        return
     if a.gang is not None:
         rows = [r for q in (64, 1024) for r in gang_rows("cfg3", q, a.gang, a.reps, a.warmup, a.nominated)]
         print(json.dumps(dict(metric="bs_preempt_commit_gang ms per call", rows=rows)))
