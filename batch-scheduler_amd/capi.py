@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "bs_bound_bind",
     "bs_nominated_load", "bs_nominated_count", "bs_nominated_ids", "bs_nominated_read", "bs_nominated_apply", "bs_preempt_nominated_read",
     "bs_nominated_nodes_apply",
+    "bs_preempt_cleared_read",
 ]
 
 SEQ_EXPIRE_DENY, SEQ_EXPIRE_ALL = 1, 2    # bs_seq_expire flags
@@ -271,6 +272,7 @@ def load_library(path: str | None = None):
     L.bs_nominated_read.argtypes = [vp, P(u32), P(u32), P(i32), P(C.c_int64), P(u32)]
     L.bs_nominated_apply.argtypes = [vp, u32, P(u32), u32, P(u32), P(u32), P(i32), P(u32)]
     L.bs_preempt_nominated_read.argtypes = [vp, u32, P(u32)]
+    L.bs_preempt_cleared_read.argtypes = [vp, u32, P(u32), P(u32), P(i32), P(u32), P(u32)]
     L.bs_nominated_nodes_apply.argtypes = [vp, u32, P(u32), P(u32), u32, P(u32), P(u32), P(i32), P(u32)]
     L.bs_bound_bind.argtypes = [vp, u32, P(u32), u32, P(u32), P(i32), P(C.c_int64), P(u8), P(u32), P(u32)]
     for name in ABI_SYMBOLS:
@@ -846,6 +848,23 @@ class Context:
         self._chk(self._lib.bs_preempt_nominated_read(self._h, int(count), _u32p(out)), "bs_preempt_nominated_read")
         return out[: int(count)]
 
+    def preempt_cleared_read(self, cap: int | None = None) -> dict:
+        """bs_preempt_cleared_read: the rows of the nominated-pod table the last preemption call with clear_lower=True cleared, in ascending
+        id: id, node, priority, by (the caller-order index of the preemptor that stands first on the row's node), and n, the true count
+        (the columns hold min(n, cap) rows; cap None reads them all; cap 0 passes NULL columns)."""
+        n = C.c_uint32(0)
+        if cap is None:
+            self._chk(self._lib.bs_preempt_cleared_read(self._h, 0, None, None, None, None, C.byref(n)), "bs_preempt_cleared_read")
+            cap = int(n.value)
+        cap = int(cap)
+        m = max(cap, 1)
+        i_, nd, pr, by = np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros(m, np.int32), np.zeros(m, np.uint32)
+        self._chk(self._lib.bs_preempt_cleared_read(self._h, cap, _u32p(i_) if cap else None, _u32p(nd) if cap else None,
+                                                    pr.ctypes.data_as(C.POINTER(C.c_int32)) if cap else None, _u32p(by) if cap else None,
+                                                    C.byref(n)), "bs_preempt_cleared_read")
+        k = min(int(n.value), cap)
+        return dict(id=i_[:k].copy(), node=nd[:k].copy(), priority=pr[:k].copy(), by=by[:k].copy(), n=int(n.value))
+
     def read_node_requests(self):
         """bs_nodes_read: (requested [L][n], requested_present [n]) as the context holds them"""
         req = np.zeros((self.L, max(self.n, 1)), np.int64) if self.n == 0 else np.zeros((self.L, self.n), np.int64)
@@ -886,24 +905,36 @@ class Context:
         return self._preempt_call(None, pod_index, priority, group_protected, victim_cap, stages)
 
     def preempt_commit(self, pod_index, priority, group_protected=None, victim_cap: int = 16, apply: bool = False, assume: bool = False,
-                       stages: int = soa.STAGE_PREFILTER, nominate: bool = False) -> dict:
+                       stages: int = soa.STAGE_PREFILTER, nominate: bool = False, clear_lower: bool = False) -> dict:
         """bs_preempt_commit: the preemptors answered in sequence (priority descending, stable), each seeing the earlier slots' victims
         gone and their preemptors nominated; apply=True writes the evictions into the bound table and the node requests, assume=True
         (with apply) also adds each nominee's request to its node; nominate=True (with apply, without assume) appends each nominee to the
-        nominated-pod table instead, and the dict gains nominated_id [count] (NOM_NONE where none).  Returns the dict `preempt` returns."""
+        nominated-pod table instead, and the dict gains nominated_id [count] (NOM_NONE where none).  clear_lower=True (rule C): a slot
+        that stands on a node clears the lower-priority rows of the nominated-pod table on it for the later slots (and, with apply, out
+        of the table); the dict gains cleared = {id, node, priority, by}.  Returns the dict `preempt` returns."""
         flags = (soa.PREEMPT_APPLY if apply else 0) | (soa.PREEMPT_ASSUME if assume else 0) | (soa.PREEMPT_NOMINATE if nominate else 0)
+        flags |= soa.PREEMPT_CLEAR_LOWER if clear_lower else 0
         res = self._preempt_call(flags, pod_index, priority, group_protected, victim_cap, stages)
         if nominate:
             res["nominated_id"] = self.preempt_nominated_read(len(res["node"]))
+        if clear_lower:
+            res["cleared"] = self._cleared()
         return res
 
+    def _cleared(self) -> dict:
+        c = self.preempt_cleared_read()
+        return {f: c[f] for f in ("id", "node", "priority", "by")}
+
     def preempt_commit_gang(self, pod_index, priority, group_protected=None, gang_need=None, victim_cap: int = 16, apply: bool = False,
-                            assume: bool = False, stages: int = soa.STAGE_PREFILTER, flat: bool = False, nominate: bool = False) -> dict:
+                            assume: bool = False, stages: int = soa.STAGE_PREFILTER, flat: bool = False, nominate: bool = False,
+                            clear_lower: bool = False) -> dict:
         """bs_preempt_commit_gang: preempt_commit, with each gang's quorum decided inside the pass: gang_need[g] members of group g must
         get a node in this call (the module's gang_need builds it; gang_order makes each gang one run), or the gang's slots are voided
         and their evictions taken back before the later slots are answered.  Returns preempt_commit's dict plus slot_voided [count]
-        and group_placed [g] (bs_preempt_gang_read).  flat=True goes through bs_preempt_commit_gang_flat."""
+        and group_placed [g] (bs_preempt_gang_read).  flat=True goes through bs_preempt_commit_gang_flat.  clear_lower: as preempt_commit's
+        (a voided run's clearings are taken back)."""
         flags = (soa.PREEMPT_APPLY if apply else 0) | (soa.PREEMPT_ASSUME if assume else 0) | (soa.PREEMPT_NOMINATE if nominate else 0)
+        flags |= soa.PREEMPT_CLEAR_LOWER if clear_lower else 0
         need = None if gang_need is None else np.ascontiguousarray(np.asarray(gang_need, np.uint32).reshape(-1))
         res = self._preempt_call(flags, pod_index, priority, group_protected, victim_cap, stages, gang=(need, flat))
         q, g = len(res["node"]), 0 if need is None else int(need.size)
@@ -912,6 +943,8 @@ class Context:
         res["slot_voided"], res["group_placed"] = voided[:q], placed[:g]
         if nominate:
             res["nominated_id"] = self.preempt_nominated_read(q)
+        if clear_lower:
+            res["cleared"] = self._cleared()
         return res
 
     def _preempt_call(self, flags, pod_index, priority, group_protected, victim_cap, stages, gang=None) -> dict:

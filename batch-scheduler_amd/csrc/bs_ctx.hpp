@@ -17,6 +17,7 @@
 #include "bs_lanes.hpp"
 #include "bs_layouts.hpp"
 #include "bs_pod_ranges.hpp"
+#include "bs_preempt_clear_list.hpp"
 
 namespace bs {
 
@@ -118,13 +119,17 @@ void bound_swap(bs_ctx* c, const BoundLayout& lay, uint32_t b);
 // Defined in tu_nominated.hip: what the preemption calls use the nominated-pod table through.  nom_view: what the victim search reads (null
 // without a table or without rows); nom_state: BS_OK, or why the table cannot be patched now; nom_preempt_state: BS_OK, or the refusal of
 // rows made for another node count; nom_refusal: a check code of bs_nominated_check.hpp as last_error and status; nom_apply_rows:
-// bs_nominated_apply behind its checks (BS_PREEMPT_NOMINATE's append).
+// bs_nominated_apply behind its checks (BS_PREEMPT_NOMINATE's append; BS_PREEMPT_CLEAR_LOWER's removals ride the same rewrite);
+// nom_clear_list: k_nc_list on the context's stream behind a BS_PREEMPT_CLEAR_LOWER resolve — thr / first are that resolve's working
+// state ([n], bs_preempt_clear.hpp), sorig its slot-to-caller column; the live table's rows below their node's threshold go to cols
+// ([4][max(rows, 1)]: id, node, priority, by) compacted in ascending id, their number to *count.  Launch only: the caller waits.
 struct NomView;
 const NomView* nom_view(const bs_ctx* c);
 int nom_state(bs_ctx* c, const char* who);
 int nom_preempt_state(bs_ctx* c, const char* who);
 int nom_refusal(bs_ctx* c, const char* who, int bad);
 int nom_apply_rows(bs_ctx* c, uint32_t R, const uint32_t* remove_id, uint32_t I, const uint32_t* pod_index, const uint32_t* node, const int32_t* priority);
+void nom_clear_list(bs_ctx* c, const uint32_t* thr, const uint32_t* first, const uint32_t* sorig, uint32_t* cols, uint32_t* count);
 
 }  // namespace bs
 
@@ -372,6 +377,7 @@ struct bs_ctx {
   std::vector<uint32_t> nom_live;      // the table's ids, ascending: what bs_nominated_apply checks its remove list against before any launch
   std::vector<uint32_t> pre_nom;       // row id per preemptor of the last BS_PREEMPT_NOMINATE call (bs_preempt_nominated_read)
   bool have_pre_nom = false;
+  ClearedRows pre_clr;                 // the rows the last BS_PREEMPT_CLEAR_LOWER call cleared (bs_preempt_cleared_read; bs_preempt_clear_list.hpp)
 
   // ---- streams, events, pinned host memory.  Declared LAST and in this order: members are destroyed in reverse, so the pinned buffers
   // and events go first, then stream3, then stream, and only then the DevBufs above (bs_destroy has waited for both streams).

@@ -198,6 +198,61 @@ __global__ __launch_bounds__(kNmWindow) void k_nn_move(NomNodesDev a) {
   }
 }
 
+// BS_PREEMPT_CLEAR_LOWER (include/bsched.h, rule C): the rows a plan cleared, listed behind its resolve (k_nc_resolve, bs_preempt_clear.hpp).
+// thr[k] is the biased threshold word of node k (priority ^ 0x80000000, 0 = nobody stands on the node), first[k] the first standing
+// slot + 1, sorig the slot's position in the caller's arrays.
+struct NomClearDev {
+  NomTab src;               // the live table (read only)
+  uint32_t W, N;
+  const uint32_t* thr;      // [n]
+  const uint32_t* first;    // [n]
+  const uint32_t* sorig;    // [q]
+  uint32_t* o_id;           // [W] the cleared rows in ascending id: id, node, priority, the preemptor that cleared them
+  uint32_t* o_node;
+  int32_t* o_prio;
+  uint32_t* o_by;
+  uint32_t* o_count;        // [1]
+};
+
+//   k_nc_list       k_nm_move's walk (ONE workgroup, windows of 1024, a running base) with another test and nothing moved: row e is cleared
+//                   iff its priority is below its node's threshold (unsigned compare of the biased words); a cleared row goes to output
+//                   row base + (cleared rows in front of it inside the window); thread 0 leaves the count.  No lanes: one instantiation.
+//                   (The prefix is not k_nm_: tests/test_nominated_cpu.py counts that set.)
+__global__ __launch_bounds__(kNmWindow) void k_nc_list(NomClearDev a) {
+  constexpr uint32_t kWaves = kNmWindow / 64;
+  __shared__ uint32_t s_cnt[kWaves];
+  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+  uint32_t base = 0;                                        // cleared rows in the windows before this one (every thread keeps it)
+  for (uint32_t w0 = 0; w0 < a.W; w0 += kNmWindow) {
+    const uint32_t e = w0 + t;
+    const bool in = e < a.W;
+    const uint32_t k = in ? a.src.node[e] : 0u;
+    const int32_t p = in ? a.src.prio[e] : 0;
+    const bool gone = in && k < a.N && ((uint32_t)p ^ 0x80000000u) < a.thr[k];
+    const uint64_t m = __ballot(gone);
+    if (lane == 0) s_cnt[wave] = (uint32_t)__builtin_popcountll(m);
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (uint32_t x = 0; x < kWaves; ++x) {
+      const uint32_t c = s_cnt[x];
+      before += x < wave ? c : 0u;
+      total += c;
+    }
+    if (gone) {                                             // (d <= e: the output row lies inside [0, W))
+      const uint32_t d = base + before + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+      const uint32_t f = a.first[k];                        // (a raised threshold has a first slot)
+      a.o_id[d] = a.src.id[e];
+      a.o_node[d] = k;
+      a.o_prio[d] = p;
+      a.o_by[d] = f ? a.sorig[f - 1u] : 0xFFFFFFFFu;
+    }
+    base += total;
+    __syncthreads();                                        // s_cnt is rewritten by the next window
+  }
+  if (t == 0) a.o_count[0] = base;
+}
+
 // rows of the table `t` (the new one): every row pushes itself onto its node's chain; the first thread writes the view of `t` the victim
 // search reads (it lives in t's allocation)
 __global__ __launch_bounds__(256) void k_nm_chains(NomTab t, NomView* view, uint32_t rows, uint32_t n) {

@@ -1,8 +1,9 @@
 // tu_nominated.hip — translation unit of the resident nominated-pod table: pods nominated by earlier cycles, counted by every fit test of the
 // victim search.  Kernels (bs_nominated.hpp): k_nm_mark and k_nm_chains (no templates: this unit alone includes that header), k_nm_move<S>,
-// k_nm_gather<S> and k_nn_move<S> (the table follows node-list surgery), once per scalar-lane count 0..BS_MAX_SCALARS.  Host: the table's
+// k_nm_gather<S> and k_nn_move<S> (the table follows node-list surgery), once per scalar-lane count 0..BS_MAX_SCALARS, and k_nc_list (the
+// rows a BS_PREEMPT_CLEAR_LOWER plan cleared; no lanes).  Host: the table's
 // layout, its file-local launch wrappers, the entry points bs_nominated_* (include/bsched.h), and what the preemption calls of
-// tu_preempt.hip use the table through (bs_ctx.hpp): nom_view, nom_state, nom_preempt_state, nom_refusal, nom_apply_rows.
+// tu_preempt.hip use the table through (bs_ctx.hpp): nom_view, nom_state, nom_preempt_state, nom_refusal, nom_apply_rows, nom_clear_list.
 #ifndef BS_UNITY
 #define BS_TU_FAMILY
 #endif
@@ -113,6 +114,23 @@ int bs::nom_preempt_state(bs_ctx* c, const char* who) {
 int bs::nom_refusal(bs_ctx* c, const char* who, int bad) {
   c->last_error = std::string(who) + ": " + nom_check_text(bad);
   return nom_check_is_capacity(bad) ? BS_ERR_CAPACITY : BS_ERR_INVALID;
+}
+// k_nc_list behind a BS_PREEMPT_CLEAR_LOWER resolve (the caller has found the table live and with rows: its nom_view was not null)
+void bs::nom_clear_list(bs_ctx* c, const uint32_t* thr, const uint32_t* first, const uint32_t* sorig, uint32_t* cols, uint32_t* count) {
+  const size_t rows = std::max<uint32_t>(c->nom_w, 1);
+  NomClearDev a{};
+  a.src = nom_tab(c, c->nom_cur);
+  a.W = c->nom_w;
+  a.N = c->N;
+  a.thr = thr;
+  a.first = first;
+  a.sorig = sorig;
+  a.o_id = cols;
+  a.o_node = cols + rows;
+  a.o_prio = reinterpret_cast<int32_t*>(cols + 2 * rows);
+  a.o_by = cols + 3 * rows;
+  a.o_count = count;
+  hipLaunchKernelGGL(k_nc_list, dim3(1), dim3(kNmWindow), 0, c->stream, a);
 }
 // bs_nominated_apply behind its checks (and BS_PREEMPT_NOMINATE's append): the listed rows leave by the stable compaction into the twin,
 // the inserts are gathered from the resident queue behind the survivors, the chains are rebuilt, the twin becomes the table.  One wait.

@@ -1,6 +1,7 @@
 // tu_preempt.hip — translation unit of preemption over the bound-pod table.  Kernels: the victim search (bs_preempt.hpp: k_preempt_scan /
-// k_preempt_pick), the sequential plans (bs_preempt_commit.hpp: k_pc_*) and the gang plans (bs_preempt_commit_gang.hpp: k_gang_resolve), one
-// instantiation per scalar-lane count 0..BS_MAX_SCALARS.  Host: their file-local launch wrappers, the entry points bs_preempt_run, _commit and
+// k_preempt_pick), the sequential plans (bs_preempt_commit.hpp: k_pc_*), the gang plans (bs_preempt_commit_gang.hpp: k_gang_resolve) and the
+// plans that clear lower-priority nominations (bs_preempt_clear.hpp: k_nc_resolve), one instantiation per scalar-lane count
+// 0..BS_MAX_SCALARS.  Host: their file-local launch wrappers, the entry points bs_preempt_run, _commit and
 // _commit_gang (include/bsched.h) and the read-backs of what those calls leave in the context.  The bound table's own calls are tu_bound.hip's
 // (the columns: bs_bound_cols.hpp; the swap: bound_twin / bound_swap), the nominated-pod table's are tu_nominated.hip's (nom_*, bs_ctx.hpp;
 // NomView is bs_preempt.hpp's): this unit includes the kernel header of neither table's own kernels, k_pdb_* and k_nm_*.
@@ -10,6 +11,7 @@
 #include "bs_preempt.hpp"
 #include "bs_preempt_commit.hpp"
 #include "bs_preempt_commit_gang.hpp"
+#include "bs_preempt_clear.hpp"
 #include "bs_preempt_gang_runs.hpp"
 #include "bs_preempt_geom.hpp"
 #include "bs_nominated_check.hpp"
@@ -47,6 +49,17 @@ void launch_preempt_commit_gang(hipStream_t stream, uint32_t S, dim3 scan_grid, 
   });
 }
 
+// BS_PREEMPT_CLEAR_LOWER with rows in the table, either call: k_pc_scan<S> as above, then k_nc_resolve<S> (bs_preempt_commit hands it
+// all-zero run columns)
+void launch_preempt_commit_clear(hipStream_t stream, uint32_t S, dim3 scan_grid, const NodesDev& nd, const PodsDev& pd, const CommitDev& pe,
+                                 const GangDev& gd, const ClearDev& cd) {
+  lanes_wide(S, [&](auto s) {
+    constexpr int V = decltype(s)::value;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pc_scan<V>), scan_grid, dim3(64), 0, stream, nd, pd, pe);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nc_resolve<V>), dim3(1), dim3(pc_threads<V>()), 0, stream, nd, pd, pe, gd, cd);
+  });
+}
+
 // what BS_PREEMPT_APPLY launches after a plan: k_pc_nodes<S> (ndirty records into reqs), k_pc_boff<S> + k_pc_compact<S> when nw is set
 template <int S>
 void launch_preempt_apply_s(hipStream_t stream, const NodesDev& nd, const CommitDev& pe, uint32_t ndirty, uint32_t assume, bs_node_request* reqs,
@@ -77,7 +90,7 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   if (c->bound_n != c->N) { c->last_error = "the bound table was loaded for another node list: reload it"; return BS_ERR_STATE; }
   if (const int nrc = nom_preempt_state(c, "bs_preempt_run")) return nrc;
   if (count > BS_PREEMPT_MAX || (uint64_t)count * victim_cap > (1ull << 28)) return BS_ERR_CAPACITY;
-  if (count == 0) { c->pre_npv.clear(); c->have_pre_npv = true; c->have_gang = false; c->have_pre_nom = false; return BS_OK; }
+  if (count == 0) { c->pre_npv.clear(); c->have_pre_npv = true; c->have_gang = false; c->have_pre_nom = false; c->pre_clr.reset(false); return BS_OK; }
   if (!pod_index || !priority || !out->node || !out->n_victims || (victim_cap && !out->victims) || (c->G && !group_protected)) return BS_ERR_INVALID;
   if (c->bound_max_group >= (int32_t)c->G) { c->last_error = "the bound table names a group index >= the loaded group count"; return BS_ERR_INVALID; }
   const uint32_t P = c->P, N = c->N, G = c->G;
@@ -164,6 +177,7 @@ int bs_preempt_run(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* p
   c->have_pre_npv = true;
   c->have_gang = false;
   c->have_pre_nom = false;
+  c->pre_clr.reset(false);
   if (out->n_candidates) std::memcpy(out->n_candidates, o_ncand.in(rb), o_ncand.bytes());
   if (out->top_priority) std::memcpy(out->top_priority, o_top.in(rb), o_top.bytes());
   if (out->priority_sum) std::memcpy(out->priority_sum, o_sum.in(rb), o_sum.bytes());
@@ -193,20 +207,21 @@ int bs_preempt_run_flat(bs_ctx* c, uint32_t stages, uint32_t count, const uint32
 // -------------------------------------------------------------------------------------------------
 // bs_preempt_commit (gang == false: gang_need is not looked at, k_pc_resolve<S> is launched, the blob holds no gang column) and
 // bs_preempt_commit_gang (gang == true: the run check on the sorted slots, k_gang_resolve<S>).  Validation, blob, scan launch, result
-// copy and the APPLY tail are one code path.
+// copy and the APPLY tail are one code path.  BS_PREEMPT_CLEAR_LOWER (rule C) with rows in the table: k_nc_resolve<S> for either call (the
+// gang columns are carved for both then, all zero for bs_preempt_commit), k_nc_list behind it, and the cleared list in the result copy.
 static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
                                const uint8_t* group_protected, const uint32_t* gang_need, bool gang, uint32_t flags, uint32_t victim_cap,
                                const bs_preempt_out* out) {
   if (!c || !out) return BS_ERR_INVALID;
   if (stages & ~BS_STAGE_PREFILTER) { c->last_error = "bs_preempt_commit takes BS_STAGE_PREFILTER only (the plugin's Filter takes no part)"; return BS_ERR_INVALID; }
-  if (flags & ~(BS_PREEMPT_APPLY | BS_PREEMPT_ASSUME | BS_PREEMPT_NOMINATE)) { c->last_error = "bs_preempt_commit: unknown flags"; return BS_ERR_INVALID; }
+  if (flags & ~(BS_PREEMPT_APPLY | BS_PREEMPT_ASSUME | BS_PREEMPT_NOMINATE | BS_PREEMPT_CLEAR_LOWER)) { c->last_error = "bs_preempt_commit: unknown flags"; return BS_ERR_INVALID; }
   if ((flags & BS_PREEMPT_ASSUME) && !(flags & BS_PREEMPT_APPLY)) { c->last_error = "BS_PREEMPT_ASSUME needs BS_PREEMPT_APPLY"; return BS_ERR_INVALID; }
   if ((flags & BS_PREEMPT_NOMINATE) && !(flags & BS_PREEMPT_APPLY)) { c->last_error = "BS_PREEMPT_NOMINATE needs BS_PREEMPT_APPLY"; return BS_ERR_INVALID; }
   if ((flags & BS_PREEMPT_NOMINATE) && (flags & BS_PREEMPT_ASSUME)) {
     c->last_error = "BS_PREEMPT_NOMINATE with BS_PREEMPT_ASSUME: the nominee would count twice";
     return BS_ERR_INVALID;
   }
-  const bool nominate = (flags & BS_PREEMPT_NOMINATE) != 0;
+  const bool nominate = (flags & BS_PREEMPT_NOMINATE) != 0, clear = (flags & BS_PREEMPT_CLEAR_LOWER) != 0;
   if (!c->have_nodes || !c->have_fit || !c->have_pods || !c->have_bound) {
     c->last_error = "bs_preempt_commit needs nodes, fit, pods and the bound table loaded";
     return BS_ERR_STATE;
@@ -227,6 +242,7 @@ static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const
     if (gang) { c->gang_voided.clear(); c->gang_placed.assign(c->G, 0u); }
     c->pre_nom.clear();
     c->have_pre_nom = nominate;
+    c->pre_clr.reset(clear);
     return BS_OK;
   }
   if (!pod_index || !priority || !out->node || !out->n_victims || (victim_cap && !out->victims) || (c->G && !group_protected)) return BS_ERR_INVALID;
@@ -269,12 +285,17 @@ static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const
   const uint32_t tiles = geom.tiles, nchunks = geom.nchunks, chunk_nodes = geom.chunk_nodes;
   const size_t nQ = count, nG = std::max<uint32_t>(G, 1), nR = (size_t)nchunks * nQ, nV = std::max<size_t>((size_t)nQ * victim_cap, 1);
   const size_t nN = std::max<uint32_t>(N, 1), nB = std::max<uint32_t>(B, 1);
+  // rule C: k_nc_resolve runs only with the flag AND rows in the table (the refusals above have found the table made for this node list)
+  const NomView* const nmv = nom_view(c);
+  const bool nc = clear && nmv != nullptr;
+  const size_t nW = nc ? std::max<uint32_t>(c->nom_w, 1) : 0;   // (k_nc_list's columns: no bytes in today's blobs)
   Carve cv;
   const auto o_spod = cv.take<uint32_t>(nQ);
   const auto o_sprio = cv.take<int32_t>(nQ);
   const auto o_sorig = cv.take<uint32_t>(nQ);
   const auto o_gprot = cv.take<uint8_t>(nG);
-  const size_t gQ = gang ? nQ : 0, gB = gang ? nB : 0;    // gang columns: no bytes in bs_preempt_commit's blob
+  const size_t gQ = (gang || nc) ? nQ : 0, gB = (gang || nc) ? nB : 0;   // gang columns: no bytes in bs_preempt_commit's blob (k_nc_resolve reads them)
+  const size_t cQ = nc ? nQ : 0, cN = nc ? nN : 0;        // rule C's working state
   const auto o_gneed = cv.take<uint32_t>(gQ);
   const auto o_grlen = cv.take<uint32_t>(gQ);
   const size_t in_bytes = cv.mark();
@@ -295,8 +316,11 @@ static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const
   const auto o_gtag = cv.take<uint32_t>(gB);
   const auto o_gplaced = cv.take<uint32_t>(gQ);
   const auto o_gvoided = cv.take<uint8_t>(gQ);
+  const auto o_cthr = cv.take<uint32_t>(cN);
+  const auto o_cfirst = cv.take<uint32_t>(cN);
   const size_t work_bytes = cv.mark() - o_work;
   const auto o_gslog = cv.take<uint32_t>(gQ * 3);
+  const auto o_clog = cv.take<uint32_t>(cQ * 2);
   const auto o_dlist = cv.take<uint32_t>(nQ);
   const auto o_nreq = cv.take<bs_node_request>(nQ);
   const size_t o_res = cv.mark();                           // results: one D2H
@@ -309,6 +333,8 @@ static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const
   const auto o_sum = cv.take<int64_t>(nQ);
   const auto o_est = cv.take<int64_t>(nQ);
   const auto o_vic = cv.take<uint32_t>(nV);
+  const auto o_ccount = cv.take<uint32_t>(nc ? 1 : 0);     // rule C: the cleared list rides the result copy
+  const auto o_ccols = cv.take<uint32_t>(nW * 4);
   HIPCHK(c, c->d_pre.reserve(cv.mark()));
   std::vector<uint8_t> in(in_bytes, 0);
   for (uint32_t s = 0; s < count; ++s) {
@@ -360,9 +386,9 @@ static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const
   pe.o_sum = o_sum.in(base);
   pe.o_est = o_est.in(base);
   pe.o_victims = o_vic.in(base);
-  pe.nm = nom_view(c);
+  pe.nm = nmv;
   const NodesDev nd = nodes_dev(c);
-  if (gang) {
+  if (gang || nc) {
     GangDev gd{};
     gd.s_need = o_gneed.in(base);
     gd.s_rlen = o_grlen.in(base);
@@ -370,7 +396,16 @@ static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const
     gd.slog = o_gslog.in(base);
     gd.o_placed = o_gplaced.in(base);
     gd.o_voided = o_gvoided.in(base);
-    launch_preempt_commit_gang(c->stream, c->S, dim3(tiles, nchunks), nd, pods_dev(c), pe, gd);
+    if (nc) {
+      ClearDev cd{};
+      cd.thr = o_cthr.in(base);
+      cd.first = o_cfirst.in(base);
+      cd.clog = o_clog.in(base);
+      launch_preempt_commit_clear(c->stream, c->S, dim3(tiles, nchunks), nd, pods_dev(c), pe, gd, cd);
+      nom_clear_list(c, cd.thr, cd.first, pe.sorig, o_ccols.in(base), o_ccount.in(base));
+    } else {
+      launch_preempt_commit_gang(c->stream, c->S, dim3(tiles, nchunks), nd, pods_dev(c), pe, gd);
+    }
   } else {
     launch_preempt_commit(c->stream, c->S, dim3(tiles, nchunks), nd, pods_dev(c), pe);
   }
@@ -384,6 +419,21 @@ static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint8_t* rb = res.data() - o_res;
+  // rule C: what k_nc_list wrote, judged against the ids the context keeps before anything acts on it
+  ClearedRows cleared;
+  cleared.reset(clear);
+  if (nc) {
+    const uint32_t W = c->nom_w, n_clr = *o_ccount.in(rb);
+    const uint32_t* cols = o_ccols.in(rb);
+    if (const int bad = clear_list_check(n_clr, cols, cols + nW, cols + 3 * nW, c->nom_live.data(), W, N, count)) {
+      c->last_error = std::string("BS_PREEMPT_CLEAR_LOWER: ") + clear_check_text(bad);
+      return BS_ERR_HIP;
+    }
+    cleared.id.assign(cols, cols + n_clr);
+    cleared.node.assign(cols + nW, cols + nW + n_clr);
+    cleared.priority.assign(reinterpret_cast<const int32_t*>(cols + 2 * nW), reinterpret_cast<const int32_t*>(cols + 2 * nW) + n_clr);
+    cleared.by.assign(cols + 3 * nW, cols + 3 * nW + n_clr);
+  }
   if (apply) {
     const uint32_t* info = o_info.in(rb);
     const uint32_t ndirty = info[0], nvall = info[1];
@@ -408,11 +458,11 @@ static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const
       bound_swap(c, lay, B2);
     }
   }
+  std::vector<uint32_t> npod, nnode;
+  std::vector<int32_t> nprio;
   if (nominate) {
     // every slot that holds a node (gang: not voided, its node is -1 otherwise) is appended to the table, in the caller's order
     const int32_t* rnode = o_node.in(rb);
-    std::vector<uint32_t> npod, nnode;
-    std::vector<int32_t> nprio;
     c->pre_nom.assign(nQ, 0xFFFFFFFFu);
     for (uint32_t i = 0; i < count; ++i)
       if (rnode[i] >= 0) {
@@ -421,9 +471,14 @@ static int preempt_commit_call(bs_ctx* c, uint32_t stages, uint32_t count, const
         nnode.push_back((uint32_t)rnode[i]);
         nprio.push_back(priority[i]);
       }
-    if (!npod.empty() && (rc = nom_apply_rows(c, 0u, nullptr, (uint32_t)npod.size(), npod.data(), nnode.data(), nprio.data()))) return rc;
   }
+  // one table rewrite: the cleared rows leave (APPLY: their ids are dead from here on), the nominees are appended behind the survivors
+  const uint32_t n_gone = apply ? (uint32_t)cleared.id.size() : 0u;
+  if ((n_gone || !npod.empty()) &&
+      (rc = nom_apply_rows(c, n_gone, cleared.id.data(), (uint32_t)npod.size(), npod.data(), nnode.data(), nprio.data())))
+    return rc;
   c->have_pre_nom = nominate;
+  c->pre_clr = std::move(cleared);
   std::memcpy(out->node, o_node.in(rb), o_node.bytes());
   std::memcpy(out->n_victims, o_nv.in(rb), o_nv.bytes());
   c->pre_npv.assign(o_npv.in(rb), o_npv.in(rb) + nQ);
@@ -507,6 +562,15 @@ int bs_preempt_nominated_read(bs_ctx* c, uint32_t count, uint32_t* id_out) {
   if (count == 0) return BS_OK;
   if (!id_out) return BS_ERR_INVALID;
   std::memcpy(id_out, c->pre_nom.data(), (size_t)count * 4);
+  return BS_OK;
+}
+
+int bs_preempt_cleared_read(bs_ctx* c, uint32_t cap, uint32_t* id, uint32_t* node, int32_t* priority, uint32_t* by, uint32_t* n_out) {
+  if (!c) return BS_ERR_INVALID;
+  if (const int bad = clear_read(c->pre_clr, cap, id, node, priority, by, n_out)) {
+    c->last_error = std::string("bs_preempt_cleared_read: ") + clear_check_text(bad);
+    return bad == kClrState ? BS_ERR_STATE : BS_ERR_INVALID;
+  }
   return BS_OK;
 }
 }  // extern "C"

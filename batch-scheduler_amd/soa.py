@@ -39,6 +39,7 @@ STAGE_PREFILTER, STAGE_FILTER, STAGE_TALLY, STAGE_ALL, BATCH_COMMIT, BATCH_HOST_
 BATCH_FILTER_DENY = 0x400        # Filter's deny entry (core.go:183-185) replayed inside the batch
 PREEMPT_APPLY, PREEMPT_ASSUME = 1, 2   # bs_preempt_commit flags: write the evictions in; also add the nominees (with APPLY)
 PREEMPT_NOMINATE = 4                   # ... with APPLY, without ASSUME: append the nominees to the nominated-pod table instead
+PREEMPT_CLEAR_LOWER = 8                # ... rule C: a standing slot clears the lower-priority rows of the nominated-pod table on its node
 BS_BOUND_NODES = 1                     # bs_bound_apply_ex flag: the delta also moves the node requests (RemovePod / AddPod)
 
 PF_NAMES = {0: "PASS_NOT_GROUPED", 1: "PASS_LAST_PERMITTED", 2: "PASS_NO_MAX", 3: "PASS_FIRST_FITS",

@@ -936,10 +936,36 @@ int bs_preempt_pdb_read(bs_ctx* ctx, uint32_t count, uint32_t* n_pdb_violations)
  *      it, which BS_PREEMPT_ASSUME cannot express.  Needs a table that is valid for the node count (bs_nominated_load; BS_ERR_STATE);
  *      more than BS_NOM_MAX rows or 2^24 ids, judged against `count` before anything is launched: BS_ERR_CAPACITY, nothing changes.
  *      bs_preempt_nominated_read(count, id_out): the row id per preemptor of the last successful preemption call, 0xFFFFFFFF where the
- *      slot got no row; BS_ERR_STATE when that call did not carry the flag, BS_ERR_INVALID when count differs from that call's. */
+ *      slot got no row; BS_ERR_STATE when that call did not carry the flag, BS_ERR_INVALID when count differs from that call's.
+ *   8. BS_PREEMPT_CLEAR_LOWER (rule C; with any legal combination of the flags above, 0 included; bs_preempt_commit_gang and the _flat
+ *      forms take it too; bs_preempt_run has no flags).  Upstream's Preempt() asks getLowerPriorityNominatedPods(pod, node) after
+ *      pickOneNodeForPreemption and clears those pods' NominatedNodeName ("lower priority pods nominated to run on this node may no
+ *      longer fit"); they go back to the active queue.  Here:
+ *        rule C      when slot t (priority P_t) STANDS on node k — it got the node and, in bs_preempt_commit_gang, its run is not
+ *                    voided — every row of the nominated-pod table on k with row.priority < P_t is CLEARED (signed int32, strict: a row
+ *                    of equal priority stays).  A cleared row counts in no fit test of any later slot of the call: rule N skips it.
+ *        same thing  T[k] = the priority of the first standing slot on k in slot order (the highest of all takers of k), INT32_MIN
+ *                    while nobody stands on k; slot s on node k adds the rows with priority >= max(P_s, T[k]).
+ *        unchanged   a slot's own answer never depends on its own clearing (rows below P_s never counted for it); slot 0's answer is
+ *                    bs_preempt_run's; the rows BS_PREEMPT_NOMINATE appends in this call are never cleared by this call.
+ *        gang runs   a voided run's clearings are taken back with its evictions and nominations: the next slot sees T[k] as before
+ *                    the run's first slot.  A row that an earlier standing slot had cleared stays cleared.
+ *        no APPLY    the plan reflects the clearing and the report below is filled; nothing resident changes.
+ *        APPLY       the cleared rows leave the table by the stable compaction, in the table rewrite that appends NOMINATE's rows;
+ *                    a cleared id is dead exactly as one removed by bs_nominated_apply; the ids of bs_preempt_nominated_read are not
+ *                    affected.  NOMINATE's capacity check is still judged against `count` before any launch, with no credit for rows
+ *                    about to be cleared.
+ *        no rows     without a table, or with an empty one, the flag is accepted, nothing is cleared, and the answers and the
+ *                    launches are exactly those without the flag.
+ *      Errors are found before any launch, as in 6; on any error nothing resident changes and the last report stays.
+ *      bs_preempt_cleared_read: the cleared rows of the last successful preemption call, in ascending id: (id, node, priority, by),
+ *      by = the caller-order index of the preemptor that stands first, in slot order, on the row's node.  *n_out = the true count; the
+ *      first min(n, cap) rows come back; the arrays may be NULL when cap == 0.  BS_ERR_STATE when that call did not carry the flag (or
+ *      there was none); BS_ERR_INVALID for NULL n_out or ctx.  The caller deletes NominatedNodeName of those pods and requeues them. */
 #define BS_PREEMPT_APPLY    1u   /* write the evictions into the bound table and the node requests */
 #define BS_PREEMPT_ASSUME   2u   /* with APPLY: also add each nominee's request to its node          */
 #define BS_PREEMPT_NOMINATE 4u   /* with APPLY, without ASSUME: append each nominee to the nominated-pod table */
+#define BS_PREEMPT_CLEAR_LOWER 8u /* rule C: a standing slot clears the lower-priority rows of the nominated-pod table on its node */
 int bs_preempt_commit(bs_ctx* ctx, uint32_t stages, uint32_t count, const uint32_t* pod_index, const int32_t* priority,
                       const uint8_t* group_protected, uint32_t flags, uint32_t victim_cap, const bs_preempt_out* out);
 /* ---- preemption plans that void gangs which miss their quorum ----------------------------------------------------------------
@@ -981,6 +1007,8 @@ int bs_preempt_commit_gang(bs_ctx* ctx, uint32_t stages, uint32_t count, const u
                            const bs_preempt_out* out);
 int bs_preempt_gang_read(bs_ctx* ctx, uint32_t count, uint8_t* slot_voided /*[count]*/, uint32_t g, uint32_t* group_placed /*[g]*/);
 int bs_preempt_nominated_read(bs_ctx* ctx, uint32_t count, uint32_t* id_out /*[count]*/);
+int bs_preempt_cleared_read(bs_ctx* ctx, uint32_t cap, uint32_t* id /*[cap]*/, uint32_t* node /*[cap]*/, int32_t* priority /*[cap]*/,
+                            uint32_t* by /*[cap]*/, uint32_t* n_out);
 
 /* ---- the resident nominated-pod table: pods that preempted in an earlier cycle and have not bound yet ---------------------------
  * What rule N reads.  Nominees are NOT in the node requests: that is the point of the table (BS_PREEMPT_ASSUME puts them there, where

@@ -20,7 +20,9 @@ each; their spread is the yardstick's noise), the three calls taking turns.  --n
 nominated-pod table follows node-list surgery) on the cfg3 node list with a table of 4096 rows, for 1 node removed, 32 removed, and 1 % of
 the nodes removed with as many appended, beside the path it replaces on the same context: bs_nominated_read (before the surgery), a numpy
 remap of the node column, bs_nominated_load; bs_nodes_apply itself is untimed (both paths need it) and every timed call starts from the
-table as loaded."""
+table as loaded.  --commit --clear times bs_preempt_commit with BS_PREEMPT_CLEAR_LOWER beside the same call without the flag, on one context
+with a populated nominated-pod table (--nominated FRACTION, 0.5 when not given), the two calls taking turns, with flags 0 and with
+BS_PREEMPT_APPLY (nodes, bound table and nominated-pod table reloaded, untimed, before every APPLY call); the row reports the cleared rows."""
 from __future__ import annotations
 
 import argparse
@@ -93,6 +95,44 @@ def one(config: str, q: int, reps: int, warmup: int, commit: bool = False, apply
     if nominated > 0:
         row.update(nominated=nominated, nominated_rows=rows)
     return row
+
+
+def clear_rows(config: str, q: int, reps: int, warmup: int, apply: bool, nominated: float) -> dict:
+    """--commit --clear: the flagged call and the flag-less call in turns on the scene of `one` (commit) with a populated table"""
+    cfg = synth.CONFIGS[config]
+    n, S = cfg["nodes"], cfg["scalars"]
+    bound, nodes = synth.make_bound(20260921, n, cfg["groups"], (20, 110), S)
+    fit = synth.make_fit(20260921, n, cfg["classes"])
+    pods, _, prio = synth.make_preemptors(20260921, q, 4096, cfg["groups"], S, cfg["classes"])
+    pidx = np.random.default_rng(20260921).permutation(4096)[:q].astype(np.uint32)
+    groups = soa.Groups.empty(cfg["groups"], 4 + S)
+    prot = (synth.Stream(20260921, 99).uniform(cfg["groups"]) < 0.3).astype(np.uint8)
+    ts = {False: [], True: []}
+    with bsa.Context(scalar_lanes=S, device=0) as ctx:
+        ctx.load_nodes(nodes, fit)
+        ctx.load_groups(groups)
+        ctx.load_pods(pods)
+        ctx.load_bound(bound)
+        rows = load_nominated(ctx, nominated, n, pods, prio, 4 + S)
+        res, ts_started = {}, False
+        for it in range(warmup + reps):
+            for flagged in ((False, True) if it % 2 == 0 else (True, False)):
+                if apply and ts_started:                     # (the first call of all starts from the state as loaded above)
+                    ctx.load_nodes(nodes, fit)
+                    ctx.load_bound(bound)
+                    load_nominated(ctx, nominated, n, pods, prio, 4 + S)
+                ts_started = True
+                t0 = time.perf_counter()
+                res[flagged] = ctx.preempt_commit(pidx, prio, prot, victim_cap=16, apply=apply, clear_lower=flagged)
+                if it >= warmup:
+                    ts[flagged].append((time.perf_counter() - t0) * 1e3)
+    med = lambda v: round(float(np.median(v)), 4)            # noqa: E731
+    r0, r1 = res[False], res[True]
+    return dict(config=config, nodes=n, bound=int(bound.b), preemptors=q, flags="APPLY" if apply else "0", nominated=nominated, nominated_rows=rows,
+                ms=med(ts[False]), ms_min=round(float(min(ts[False])), 4), clear_ms=med(ts[True]), clear_ms_min=round(float(min(ts[True])), 4),
+                clear_over_plain=round(med(ts[True]) / med(ts[False]), 3), cleared=int(r1["cleared"]["id"].size),
+                placed=int((r0["node"] >= 0).sum()), clear_placed=int((r1["node"] >= 0).sum()), evicted=int(r0["n_victims"].sum()),
+                clear_evicted=int(r1["n_victims"].sum()))
 
 
 def _table_bytes(L: int, n: int, b: int) -> int:
@@ -507,6 +547,7 @@ def main():
                     "their quorum) beside bs_preempt_commit")
     ap.add_argument("--nominated", type=float, default=0.0, metavar="FRACTION", help="share of the nodes that hold one row of the nominated-pod table "
                     "(priorities drawn from the preemptors'); with the default scene, --commit and --gang")
+    ap.add_argument("--clear", action="store_true", help="with --commit: BS_PREEMPT_CLEAR_LOWER beside the flag-less call on a populated nominated-pod table")
     ap.add_argument("--nominated-nodes", action="store_true", help="bs_nominated_nodes_apply on cfg3 with 4096 rows (1 node removed, 32 removed, 1 %% "
                     "removed with as many appended), vs bs_nominated_read + a numpy remap + bs_nominated_load")
     a = ap.parse_args()
@@ -532,6 +573,10 @@ def main():
     if a.bound_apply:
         rows = [r for c in ("cfg3", "cfg4") for r in bound_apply_rows(c, a.bound_apply, a.reps, a.warmup)]
         print(json.dumps(dict(metric="bs_bound_apply ms per call", rows=rows)))
+        return
+    if a.commit and a.clear:
+        rows = [clear_rows(c, q, a.reps, a.warmup, ap_, a.nominated or 0.5) for c in ("cfg3", "cfg4") for q in (64, 1024) for ap_ in (False, True)]
+        print(json.dumps(dict(metric="bs_preempt_commit with BS_PREEMPT_CLEAR_LOWER ms per call", rows=rows)))
         return
     if a.commit:
         rows = [one(c, q, a.reps, a.warmup, True, ap_, a.pdb, a.nominated) for c in ("cfg3", "cfg4") for q in (64, 1024) for ap_ in (False, True)]
