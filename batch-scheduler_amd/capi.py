@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "bs_nominated_load", "bs_nominated_count", "bs_nominated_ids", "bs_nominated_read", "bs_nominated_apply", "bs_preempt_nominated_read",
     "bs_nominated_nodes_apply",
     "bs_preempt_cleared_read",
+    "bs_seq_run_nominated", "bs_seq_run_nominated_flat", "bs_seq_nominated_read",
 ]
 
 SEQ_EXPIRE_DENY, SEQ_EXPIRE_ALL = 1, 2    # bs_seq_expire flags
@@ -275,6 +276,10 @@ def load_library(path: str | None = None):
     L.bs_preempt_cleared_read.argtypes = [vp, u32, P(u32), P(u32), P(i32), P(u32), P(u32)]
     L.bs_nominated_nodes_apply.argtypes = [vp, u32, P(u32), P(u32), u32, P(u32), P(u32), P(i32), P(u32)]
     L.bs_bound_bind.argtypes = [vp, u32, P(u32), u32, P(u32), P(i32), P(C.c_int64), P(u8), P(u32), P(u32)]
+    L.bs_seq_run_nominated.argtypes = [vp, u32, u32, P(i32), P(u32), P(SeqOut)]
+    L.bs_seq_run_nominated_flat.argtypes = [vp, u32, u32, P(i32), P(u32), P(u8), P(u32), P(i32), P(i32), u32, P(u32), P(u32), P(C.c_int64), P(C.c_int64),
+                                            P(C.c_int64), P(u8)]
+    L.bs_seq_nominated_read.argtypes = [vp, u32, P(u32), P(u32), P(u32), P(u32)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:
@@ -632,6 +637,11 @@ class Context:
     def seq_run(self, stages: int = soa.STAGE_PREFILTER, cap: int | None = None) -> dict:
         """bs_seq_run: the reference's pod-by-pod cycle (PreFilter -> node choice -> assume -> Permit -> release) over the
         resident queue, on the device.  The context's node requests and group state are what the pass left."""
+        return self._seq_pass(stages, cap, None, False)
+
+    def _seq_pass(self, stages: int, cap, nominated, flat: bool) -> dict:
+        """the result arrays of a sequential pass and the call: bs_seq_run (nominated None), else bs_seq_run_nominated with
+        nominated = (p, priority, own_id), through its flat form when flat"""
         p, cap = self.pods_count(), max(self.g if cap is None else cap, 1)
         n = max(p, 1)
         pf, fk = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
@@ -641,11 +651,43 @@ class Context:
         lp = np.zeros(n, np.uint8)
         o = SeqOut(pf.ctypes.data_as(C.POINTER(C.c_uint8)), _u32p(fk), ld.ctypes.data_as(C.POINTER(C.c_int32)), node.ctypes.data_as(C.POINTER(C.c_int32)),
                    cap, _u32p(rg), _u32p(rp), _i64p(t0), _i64p(t1), 0, 0, 0, 0, 0, 0, 0, 0, lp.ctypes.data_as(C.POINTER(C.c_uint8)))
-        self._chk(self._lib.bs_seq_run(self._h, stages, C.byref(o)), "bs_seq_run")
+        if nominated is None:
+            self._chk(self._lib.bs_seq_run(self._h, stages, C.byref(o)), "bs_seq_run")
+        elif flat:
+            sc = np.zeros(8, np.int64)
+            self._chk(self._lib.bs_seq_run_nominated_flat(self._h, stages, *nominated, o.pf_code, o.pf_first_k, o.pf_leader, o.pod_node, cap, o.released_group,
+                                                          o.released_pods, o.first_ns, o.ready_ns, _i64p(sc), o.last_permitted), "bs_seq_run_nominated_flat")
+            (o.n_released, o.total_ns, o.node_picks, o.node_scans, o.scan_rounds, o.pick_rounds, o.leader_folds, o.table_builds) = (int(v) for v in sc)
+        else:
+            self._chk(self._lib.bs_seq_run_nominated(self._h, stages, *nominated, C.byref(o)), "bs_seq_run_nominated")
         k = min(int(o.n_released), cap)
         return dict(pf_code=pf[:p], pf_first_k=fk[:p], pf_leader=ld[:p], pod_node=node[:p], last_permitted=lp[:p], released_group=rg[:k], released_pods=rp[:k],
                     first_ns=t0[:k], ready_ns=t1[:k], n_released=int(o.n_released), total_ns=int(o.total_ns), node_picks=int(o.node_picks),
                     node_scans=int(o.node_scans), scan_rounds=int(o.scan_rounds), pick_rounds=int(o.pick_rounds), leader_folds=int(o.leader_folds), table_builds=int(o.table_builds))
+
+    def seq_run_nominated(self, priority, own_id=None, stages: int = soa.STAGE_PREFILTER, cap: int | None = None, p: int | None = None,
+                          flat: bool = False) -> dict:
+        """bs_seq_run_nominated: seq_run with the resident nominated-pod table in the node choice (rule S).  priority[i]: the priority of
+        queue pod i (None: a NULL array); own_id[i]: the id of the table row that IS pod i, NOM_NONE where it has none (None: a NULL
+        array, nobody has one).  Rows whose pods were assumed leave the table (seq_nominated_read lists them).  p overrides the queue
+        length handed to the library (tests of the refusals)."""
+        pr = None if priority is None else np.ascontiguousarray(np.asarray(priority, np.int32).reshape(-1))
+        ow = None if own_id is None else np.ascontiguousarray(np.asarray(own_id, np.uint32).reshape(-1))
+        n = self.pods_count() if p is None else int(p)
+        assert p is not None or ((pr is None or pr.size == n) and (ow is None or ow.size == n))
+        pp = None if pr is None else (pr if pr.size else np.zeros(1, np.int32)).ctypes.data_as(C.POINTER(C.c_int32))
+        op = None if ow is None else _u32p(ow if ow.size else np.zeros(1, np.uint32))
+        return self._seq_pass(stages, cap, (n, pp, op), flat)
+
+    def seq_nominated_read(self, cap: int | None = None) -> dict:
+        """bs_seq_nominated_read: the rows the last seq_run_nominated consumed, ascending id: n (the true count), id, pod (queue index), node
+        (at most cap rows; the default holds every row the table had room for)."""
+        cap = NOM_MAX if cap is None else int(cap)
+        i_, pd, nd = (np.zeros(max(cap, 1), np.uint32) for _ in range(3))
+        n = C.c_uint32(0)
+        self._chk(self._lib.bs_seq_nominated_read(self._h, cap, _u32p(i_), _u32p(pd), _u32p(nd), C.byref(n)), "bs_seq_nominated_read")
+        k = min(int(n.value), cap)
+        return dict(n=int(n.value), id=i_[:k].copy(), pod=pd[:k].copy(), node=nd[:k].copy())
 
     def seq_expire(self, groups=None, deny: bool = False, all: bool = False, group_cap: int | None = None, pod_cap: int | None = None,
                    flat: bool = False, flags: int | None = None) -> dict:

@@ -130,6 +130,11 @@ int nom_preempt_state(bs_ctx* c, const char* who);
 int nom_refusal(bs_ctx* c, const char* who, int bad);
 int nom_apply_rows(bs_ctx* c, uint32_t R, const uint32_t* remove_id, uint32_t I, const uint32_t* pod_index, const uint32_t* node, const int32_t* priority);
 void nom_clear_list(bs_ctx* c, const uint32_t* thr, const uint32_t* first, const uint32_t* sorig, uint32_t* cols, uint32_t* count);
+// ... and what the sequential pass under rule S (bs_seq_run_nominated, tu_seq.hip) uses it through, beside nom_state and nom_view.  The pass
+// keeps the consumed bytes in its own scratch (zeroed before its launch) and translates ids to rows by nom_live, which is the table's order.
+// nom_drop_flagged: the rows whose byte in the DEVICE array flag[rows] is set leave by the stable compaction into the twin (k_nm_move<S> ->
+// k_nm_chains, bs_nominated_apply's tail), the twin becomes the table and nom_live loses `gone`, the same rows' ids, ascending.  One wait.
+int nom_drop_flagged(bs_ctx* c, const uint8_t* flag, const std::vector<uint32_t>& gone);
 
 }  // namespace bs
 
@@ -247,6 +252,9 @@ struct bs_ctx {
   Piece<unsigned long long> seq_o_wait;
   Piece<uint32_t> seq_o_head, seq_o_nwait;
   Piece<int32_t> seq_o_node;         // the pass's pod_node block (bs_bound_bind reads a placed pod's node there)
+  // bs_seq_nominated_read: the rows the last pass consumed (ascending id), valid while the last pass was a successful bs_seq_run_nominated
+  bool seq_nom_valid = false;
+  std::vector<uint32_t> seq_nom_id, seq_nom_pod, seq_nom_node;
   DevBuf d_sexp;                     // per-call scratch: block totals, slots, rows, dirty list, records
   DevBuf d_sexp_nodes;               // per-node delta [L][N], key bits, dirty words: zero between calls (k_se_nodes re-zeroes what it read)
   uint32_t sexp_n = 0, sexp_l = 0;   // the layout d_sexp_nodes was zeroed for

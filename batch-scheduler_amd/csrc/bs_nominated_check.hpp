@@ -70,6 +70,37 @@ inline int nom_nominate_check(uint32_t w, uint32_t ids, uint32_t count, uint32_t
   return kNomOk;
 }
 
+// bs_seq_run_nominated: own_id[p] (NULL: nobody has a row) names, per queue pod, the row that IS the pod, or `none`.  Every id that is
+// not `none` must be live and named by one pod only (kNomIdUnknown / kNomIdDead / kNomIdTwice).  own_row[p] = the row's index in the table
+// (live[] is the table's order), `none` where the pod has no row; left untouched on a refusal.
+inline int nom_own_check(const uint32_t* live, uint32_t w, uint32_t ids, uint32_t p, const uint32_t* own_id, uint32_t none, std::vector<uint32_t>& own_row) {
+  std::vector<uint32_t> rows(p, none);
+  if (own_id) {
+    std::vector<uint8_t> named(w, 0);
+    for (uint32_t i = 0; i < p; ++i) {
+      const uint32_t id = own_id[i];
+      if (id == none) continue;
+      if (id >= ids) return kNomIdUnknown;
+      const uint32_t* at = std::lower_bound(live, live + w, id);
+      if (at == live + w || *at != id) return kNomIdDead;
+      const uint32_t r = (uint32_t)(at - live);
+      if (named[r]) return kNomIdTwice;
+      named[r] = 1;
+      rows[i] = r;
+    }
+  }
+  own_row.swap(rows);
+  return kNomOk;
+}
+inline const char* nom_own_check_text(int code) {
+  switch (code) {
+    case kNomIdUnknown: return "an own id is at or above bs_nominated_ids";
+    case kNomIdDead: return "an own id is not in the table (removed, cleared or consumed earlier)";
+    case kNomIdTwice: return "an own id is named by two pods";
+  }
+  return "ok";
+}
+
 inline const char* nom_check_text(int code) {
   switch (code) {
     case kNomOk: return "ok";

@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "bs_kernels.hpp"
+#include "bs_nom_view.hpp"
 
 namespace bs {
 
@@ -31,18 +32,7 @@ __device__ __forceinline__ int64_t pre_readlane64(int64_t v, uint32_t i) {
   return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
-// The resident nominated-pod table (bs_nominated.hpp) as the victim search reads it: one chain per node through the rows on it.  All null
-// without a table or without rows.  The rows are static within a call.  The kernels get a POINTER to the view (it lives in the table's
-// allocation; null = no rows): five fields in the kernel arguments cost every instantiation nine scalar registers for its whole life, and
-// the pick and resolve kernels have none to spare.  Through the pointer the fields are scalar loads that live for the walk only.
-constexpr uint32_t kNmNone = 0xFFFFFFFFu;
-struct NomView {
-  const uint32_t* nhead;    // [n] first row on the node, kNmNone = none
-  const uint32_t* nnext;    // [cap] next row on the same node
-  const int32_t* nprio;     // [cap]
-  const int64_t* nreq;      // [L][nstride] as AddPod counts the row
-  uint32_t nstride;
-};
+// (NomView, the resident nominated-pod table as the victim search reads it, and kNmNone: bs_nom_view.hpp, shared with the sequential pass)
 
 // Rule N (include/bsched.h): the rows on node k with priority >= P are added into the LOCAL cur (wrapping sums; the order of a chain does
 // not matter).  The sum is never stored: the working deltas of a plan, k_pc_nodes' vectors, the gang rollback and the host mirror do not

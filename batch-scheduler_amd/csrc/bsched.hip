@@ -30,6 +30,7 @@
 #ifdef BS_UNITY   // one translation unit (the probe builds: g_probe / g_seq_scan_ph are per translation unit)
 #include "tu_fast.hip"
 #include "tu_seq.hip"
+#include "tu_seq_nom.hip"
 #include "tu_seq_expire.hip"
 #include "tu_wait.hip"
 #include "tu_groups.hip"

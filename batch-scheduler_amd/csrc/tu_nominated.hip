@@ -3,7 +3,8 @@
 // k_nm_gather<S> and k_nn_move<S> (the table follows node-list surgery), once per scalar-lane count 0..BS_MAX_SCALARS, and k_nc_list (the
 // rows a BS_PREEMPT_CLEAR_LOWER plan cleared; no lanes).  Host: the table's
 // layout, its file-local launch wrappers, the entry points bs_nominated_* (include/bsched.h), and what the preemption calls of
-// tu_preempt.hip use the table through (bs_ctx.hpp): nom_view, nom_state, nom_preempt_state, nom_refusal, nom_apply_rows, nom_clear_list.
+// tu_preempt.hip use the table through (bs_ctx.hpp): nom_view, nom_state, nom_preempt_state, nom_refusal, nom_apply_rows, nom_clear_list;
+// and what the sequential pass of bs_seq_run_nominated (tu_seq.hip) takes its consumed rows off the table with: nom_drop_flagged.
 #ifndef BS_UNITY
 #define BS_TU_FAMILY
 #endif
@@ -185,6 +186,31 @@ int bs::nom_apply_rows(bs_ctx* c, uint32_t R, const uint32_t* remove_id, uint32_
   c->nom_cur = other;
   c->nom_w = W3;
   c->nom_ids = ids + I;
+  return BS_OK;
+}
+
+// the sequential pass consumed rows (rule S): flag[] is the pass's own device array over the live table's rows, `gone` the same rows' ids
+int bs::nom_drop_flagged(bs_ctx* c, const uint8_t* flag, const std::vector<uint32_t>& gone) {
+  const uint32_t W = c->nom_w, R = (uint32_t)gone.size(), cur = c->nom_cur, other = cur ^ 1u;
+  if (!R) return BS_OK;
+  if (R > W) { c->last_error = "nominated-pod table: more consumed rows than rows"; return BS_ERR_HIP; }
+  HIPCHK(c, hipStreamSynchronize(c->stream));               // (nothing of an earlier call still reads the twin)
+  HIPCHK(c, nom_reserve(c, other, W - R));
+  NomDev a{};
+  a.src = nom_tab(c, cur);
+  a.dst = nom_tab(c, other);
+  a.W = W; a.W2 = W - R; a.N = c->N;
+  a.flag = const_cast<uint8_t*>(flag);                      // (k_nm_move reads it; no k_nm_mark: n_remove is 0)
+  launch_nom_apply(c->stream, c->S, a, pods_dev(c));
+  HIPCHK(c, launch_nom_chains(c, other, W - R));
+  LAUNCHCHK(c, BS_KERNEL_PREPASS);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<uint32_t> left;
+  left.reserve(W - R);
+  std::set_difference(c->nom_live.begin(), c->nom_live.end(), gone.begin(), gone.end(), std::back_inserter(left));
+  c->nom_live.swap(left);
+  c->nom_cur = other;
+  c->nom_w = W - R;
   return BS_OK;
 }
 

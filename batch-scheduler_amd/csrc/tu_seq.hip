@@ -1,5 +1,7 @@
-// tu_seq.hip — translation unit of the sequential pass: its kernel (bs_seq.hpp: k_seq_pass, six instantiations), the file-local launch
-// wrapper and the entry point bs_seq_run (include/bsched.h) with its flat form; see tu_fast.hip for why.
+// tu_seq.hip — translation unit of the sequential pass: its kernel (bs_seq.hpp: k_seq_pass<TS>, six instantiations; k_seq_pass<TS, true>, the
+// same six under rule S, are emitted by tu_seq_nom.hip), the file-local launch wrapper and the entry points bs_seq_run and bs_seq_run_nominated (include/bsched.h) with
+// their flat forms, and bs_seq_nominated_read; see tu_fast.hip for why.  The nominated-pod table is reached through bs_ctx.hpp's declarations
+// (tu_nominated.hip defines them): this unit does not include bs_nominated.hpp and emits no k_nm_* kernel.
 #ifndef BS_UNITY
 #define BS_TU_FAMILY
 #endif
@@ -9,6 +11,7 @@
 
 #include "bs_seq.hpp"
 #include "bs_ctx.hpp"
+#include "bs_nominated_check.hpp"
 
 namespace bs {
 
@@ -16,16 +19,20 @@ static void launch_seq(hipStream_t stream, uint32_t S, size_t lds, const PodsDev
   lanes_narrow(S, [&](auto s) {
     constexpr int TS = decltype(s)::value;
     // static LDS (first-fit bounds, reduction slots) + the key window can exceed the default 64 KB of dynamic LDS
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_seq_pass<TS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    void (*kn)(PodsDev, GroupsDev, NodesDev, SeqDev, SeqParams) = &k_seq_pass<TS>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seq_pass<TS>), dim3(1), dim3(kSeqBlock), lds, stream, pd, gr, nd, sq, prm);
   });
 }
 
-}  // namespace bs
+// what bs_seq_run_nominated hands the pass: the caller's priorities and, per pod, the ROW of its own nomination (kNmNone: none)
+struct SeqNomCall {
+  const int32_t* priority;
+  const std::vector<uint32_t>* own_row;
+};
 
-extern "C" {
-int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
-  if (!c || !out) return BS_ERR_INVALID;
+// what both entry points refuse on the host before anything else
+static int seq_refusals(bs_ctx* c, uint32_t stages) {
   if (!c->have_nodes || !c->have_fit || !c->have_groups || !c->have_pods) {
     c->last_error = "bs_seq_run needs nodes, fit, groups and pods loaded";
     return BS_ERR_STATE;
@@ -33,6 +40,13 @@ int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
   if (!(stages & BS_STAGE_PREFILTER)) { c->last_error = "PREFILTER stage is mandatory"; return BS_ERR_INVALID; }
   if ((stages & BS_BATCH_FILTER_DENY) && !(stages & BS_STAGE_FILTER)) { c->last_error = "BS_BATCH_FILTER_DENY needs BS_STAGE_FILTER"; return BS_ERR_INVALID; }
   if (c->nranks > 1 || c->reduce_external) { c->last_error = "bs_seq_run is single-rank only (a sequential pass does not shard)"; return BS_ERR_STATE; }
+  return BS_OK;
+}
+
+}  // namespace bs
+
+// bs_seq_run's body behind the refusals above; nc: null = no table (bs_seq_run), else rule S
+static int seq_run_impl(bs_ctx* c, uint32_t stages, bs_seq_out* out, const SeqNomCall* nc) {
   int rc = use_device(c);
   if (rc) return rc;
   if ((rc = settle_pending(c))) return rc;
@@ -43,6 +57,7 @@ int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
   }
   if (G > 0x7FFFFFF0u) return BS_ERR_CAPACITY;
   c->seq_wait_valid = false;                                // the pass replaces the waiting state
+  c->seq_nom_valid = false;                                 // ... and is the context's last pass
   // the first-fit cursors are keyed by the resident queue's request classes: a queue patch whose insert wave ran out of class ids
   // (kHiIdOverflow of h_info, set by the device) left them unusable until the queue is re-derived — check_handover does that
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -77,6 +92,13 @@ int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
   const auto o_ft = cv.take<unsigned long long>(cap);
   const auto o_rt = cv.take<unsigned long long>(cap);
   const auto o_info = cv.take<unsigned long long>(64);
+  // rule S: the consumed bytes and the per-row result words ride the result block; the call's two per-pod arrays are one H2D block
+  const uint32_t W = nc ? c->nom_w : 0u;
+  const auto o_cflag = cv.take<uint8_t>(nc ? std::max<uint32_t>(W, 1) : 0);
+  const auto o_cpod = cv.take<uint32_t>(nc ? std::max<uint32_t>(W, 1) : 0);
+  const auto o_cnode = cv.take<uint32_t>(nc ? std::max<uint32_t>(W, 1) : 0);
+  const size_t o_res_end = cv.mark();
+  const auto o_pin = cv.take<uint32_t>(nc ? 2 * nP : 0);    // priority[P], own_row[P]
   HIPCHK(c, c->d_seq.reserve(cv.mark()));
   uint8_t* base = c->d_seq.as<uint8_t>();
   GroupsDev gr = groups_dev(c);
@@ -124,7 +146,7 @@ int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
   {
     // table summaries: as many slots as the CU's LDS holds behind the static arrays and the key window (one thread per tile: <= 1024 tiles)
     const size_t T = cdiv(N, 64), per_slot = T * ((size_t)L * 24 + 8), query = 0;
-    const size_t budget = (size_t)160 * 1024 - sizeof(SeqShared) - 2048;
+    const size_t budget = (size_t)160 * 1024 - sizeof(SeqShared) - 2048 - (nc ? align256(sizeof(SeqNomShared)) : 0);
     uint32_t K = 0;
     if (T && T <= (size_t)kSeqPruneTiles && budget > lds + query + per_slot) K = (uint32_t)std::min<size_t>(kSeqCacheSlots, (budget - lds - query) / per_slot);
     if (const char* e = std::getenv("BS_SEQ_CACHE_SLOTS")) K = std::min<uint32_t>(K, (uint32_t)std::max(0, std::atoi(e)));   // tests: 0 = the round scan, 1 = thrash one slot
@@ -135,12 +157,34 @@ int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
   // first-fit cursors per request class (bs_seq.hpp, seq_pick): BS_SEQ_NO_CURSOR=1 = every search starts at the head of the list
   prm.use_cursor = (P && sq.pclass && !(std::getenv("BS_SEQ_NO_CURSOR") && std::atoi(std::getenv("BS_SEQ_NO_CURSOR")))) ? 1u : 0u;
   HIPCHK(c, hipMemsetAsync(o_info.in(base), 0, o_info.bytes(), c->stream));
+  SeqNom nom{};
+  std::vector<uint32_t> pin;
+  if (nc) {
+    nom.view = nom_view(c);
+    nom.rows = W;
+    nom.consumed = o_cflag.in(base);
+    nom.c_pod = o_cpod.in(base);
+    nom.c_node = o_cnode.in(base);
+    nom.pprio = reinterpret_cast<const int32_t*>(o_pin.in(base));
+    nom.pown = o_pin.in(base) + nP;
+    nom.lds_off = (uint32_t)lds;
+    lds += align256(sizeof(SeqNomShared));
+    pin.assign(2 * nP, kNmNone);
+    if (P) {
+      std::memcpy(pin.data(), nc->priority, (size_t)P * 4);
+      std::memcpy(pin.data() + nP, nc->own_row->data(), (size_t)P * 4);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // (nothing of an earlier call still reads the block)
+    HIPCHK(c, hipMemcpy(o_pin.in(base), pin.data(), o_pin.bytes(), hipMemcpyHostToDevice));   // synchronous: pin is a local buffer and a later error returns at once
+    HIPCHK(c, hipMemsetAsync(o_cflag.in(base), 0, o_cflag.bytes(), c->stream));
+  }
   const PodsDev pd = pods_dev(c);
   const NodesDev nd = nodes_dev(c);
-  launch_seq(c->stream, c->S, lds, pd, gr, nd, sq, prm);
+  if (nc) launch_seq_nominated(c->stream, c->S, lds, pd, gr, nd, sq, prm, nom);   // (tu_seq_nom.hip: the NOM instantiations)
+  else launch_seq(c->stream, c->S, lds, pd, gr, nd, sq, prm);
   LAUNCHCHK(c, BS_KERNEL_QUERY);
   // ---- results: one copy of the whole result block, then the caller's arrays
-  std::vector<uint8_t> res(cv.mark() - o_res);
+  std::vector<uint8_t> res(o_res_end - o_res);
   HIPCHK(c, hipMemcpyAsync(res.data(), base + o_res, res.size(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint8_t* rb = res.data() - o_res;
@@ -211,12 +255,83 @@ int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
     if ((rc = analyse_groups(c))) return rc;
     if ((rc = maybe_analyse_epochs(c))) return rc;
   }
+  if (nc) {
+    // ---- consume (D6): the rows whose pods were assumed leave the table by the stable compaction; their ids are dead
+    const uint8_t* cf = o_cflag.in(rb);
+    const uint32_t* cp = o_cpod.in(rb);
+    const uint32_t* cn = o_cnode.in(rb);
+    std::vector<uint32_t> id, pod, node;
+    for (uint32_t r = 0; r < W; ++r)
+      if (cf[r]) { id.push_back(c->nom_live[r]); pod.push_back(cp[r]); node.push_back(cn[r]); }
+    if ((rc = nom_drop_flagged(c, o_cflag.in(base), id))) return rc;
+    c->seq_nom_id.swap(id);
+    c->seq_nom_pod.swap(pod);
+    c->seq_nom_node.swap(node);
+    c->seq_nom_valid = true;
+  }
   c->seq_o_wait = o_wait;                                  // (the pieces: seq_expire_dev addresses them in d_seq)
   c->seq_o_head = o_head;
   c->seq_o_nwait = o_nwait;
   c->seq_o_node = o_node;
   c->seq_wait_valid = true;
   return BS_OK;
+}
+
+extern "C" {
+int bs_seq_run(bs_ctx* c, uint32_t stages, bs_seq_out* out) {
+  if (!c || !out) return BS_ERR_INVALID;
+  if (const int rc = seq_refusals(c, stages)) return rc;
+  return seq_run_impl(c, stages, out, nullptr);
+}
+
+int bs_seq_run_nominated(bs_ctx* c, uint32_t stages, uint32_t p, const int32_t* priority, const uint32_t* own_id, bs_seq_out* out) {
+  if (!c || !out) return BS_ERR_INVALID;
+  if (const int rc = seq_refusals(c, stages)) return rc;
+  if (stages & BS_STAGE_FILTER) {
+    c->last_error = "bs_seq_run_nominated: BS_STAGE_FILTER is refused (the plugin's Filter takes no part in the fit test under nominees, as in bs_preempt_run)";
+    return BS_ERR_INVALID;
+  }
+  if (p != c->P) { c->last_error = "bs_seq_run_nominated: p is not the resident queue's length (bs_pods_count)"; return BS_ERR_INVALID; }
+  if (p && !priority) { c->last_error = "bs_seq_run_nominated: priority is NULL and the queue has pods"; return BS_ERR_INVALID; }
+  if (const int rc = nom_state(c, "bs_seq_run_nominated")) return rc;
+  std::vector<uint32_t> own_row;
+  if (const int bad = nom_own_check(c->nom_live.data(), c->nom_w, c->nom_ids, p, own_id, BS_NOM_NONE, own_row)) {
+    c->last_error = std::string("bs_seq_run_nominated: ") + nom_own_check_text(bad);
+    return BS_ERR_INVALID;
+  }
+  static_assert(BS_NOM_NONE == kNmNone, "an own id of BS_NOM_NONE becomes the row index the kernel skips nothing for");
+  const SeqNomCall nc{priority, &own_row};
+  return seq_run_impl(c, stages, out, &nc);
+}
+
+int bs_seq_nominated_read(bs_ctx* c, uint32_t cap, uint32_t* id, uint32_t* pod, uint32_t* node, uint32_t* n_out) {
+  if (!c || !n_out) return BS_ERR_INVALID;
+  if (!c->seq_nom_valid) { c->last_error = "bs_seq_nominated_read: the context's last pass was not a successful bs_seq_run_nominated"; return BS_ERR_STATE; }
+  const uint32_t n = (uint32_t)c->seq_nom_id.size(), k = std::min(n, cap);
+  if (k && (!id || !pod || !node)) { c->last_error = "bs_seq_nominated_read: an output array is NULL with rows to report"; return BS_ERR_INVALID; }
+  if (k) {
+    std::memcpy(id, c->seq_nom_id.data(), (size_t)k * 4);
+    std::memcpy(pod, c->seq_nom_pod.data(), (size_t)k * 4);
+    std::memcpy(node, c->seq_nom_node.data(), (size_t)k * 4);
+  }
+  *n_out = n;
+  return BS_OK;
+}
+
+int bs_seq_run_nominated_flat(bs_ctx* c, uint32_t stages, uint32_t p, const int32_t* priority, const uint32_t* own_id, uint8_t* pf_code, uint32_t* pf_first_k,
+                              int32_t* pf_leader, int32_t* pod_node, uint32_t cap, uint32_t* released_group, uint32_t* released_pods, int64_t* first_ns,
+                              int64_t* ready_ns, int64_t* scalars_out, uint8_t* last_permitted) {
+  bs_seq_out o{};
+  o.last_permitted = last_permitted;
+  o.pf_code = pf_code; o.pf_first_k = pf_first_k; o.pf_leader = pf_leader; o.pod_node = pod_node; o.cap = cap; o.released_group = released_group;
+  o.released_pods = released_pods; o.first_ns = first_ns; o.ready_ns = ready_ns;
+  const int rc = bs_seq_run_nominated(c, stages, p, priority, own_id, &o);
+  if (scalars_out) {
+    scalars_out[0] = o.n_released; scalars_out[1] = o.total_ns; scalars_out[2] = (int64_t)o.node_picks; scalars_out[3] = (int64_t)o.node_scans;
+    scalars_out[4] = (int64_t)o.scan_rounds; scalars_out[5] = (int64_t)o.pick_rounds; scalars_out[6] = (int64_t)o.leader_folds;
+    scalars_out[7] = (int64_t)o.table_builds;
+  }
+  return rc;
 }
 
 int bs_seq_run_flat(bs_ctx* c, uint32_t stages, uint8_t* pf_code, uint32_t* pf_first_k, int32_t* pf_leader, int32_t* pod_node, uint32_t cap,

@@ -156,3 +156,60 @@ func (g *gpuCore) preemptNominatedRead(count int) ([]uint32, error) {
 	}
 	return ids, nil
 }
+
+// consumedNominee is one row the nominated pass took off the table: the pod at queue index pod, whose row id was id, was assumed on node.
+type consumedNominee struct {
+	id, pod, node uint32
+}
+
+// seqPassNominated: seqPass with the nominated-pod table in the node choice (bs_seq_run_nominated, rule S of include/bsched.h): what
+// upstream's podFitsOnNode does for every pod of the normal cycle.  priority[i] is the priority of queue pod i; ownRow[i] is the row id the
+// shim keeps beside the pod's UID (preemptNominatedRead), noNominatedRow where the pod was never nominated; nil means nobody was.  A pod
+// of priority P sees, on each node, the rows with priority >= P other than its own.  The rows of the pods the pass assumed — on whatever
+// node, released or still waiting at Permit — have left the table when the call returns and come back in `consumed` (ascending id): the
+// shim forgets those row ids (SchedulingQueue.DeleteNominatedPodIfExists); no bs_nominated_apply is needed for them.  The plugin's Filter
+// stage is refused, as in the preemption calls.  Afterwards the context is where seqPass leaves it: bs_wait_park, bs_seq_expire and
+// bs_bound_bind follow as usual.
+func (g *gpuCore) seqPassNominated(priority []int32, ownRow []uint32) (*seqResult, []consumedNominee, error) {
+	P := len(priority)
+	if ownRow != nil && len(ownRow) != P {
+		return nil, nil, fmt.Errorf("seqPassNominated: %d own rows for %d pods", len(ownRow), P)
+	}
+	cap := g.groups + 1
+	r := &seqResult{pfCode: make([]C.uint8_t, P+1), podNode: make([]C.int32_t, P+1), releasedGroup: make([]C.uint32_t, cap),
+		releasedPods: make([]C.uint32_t, cap), readyNs: make([]C.int64_t, cap), lastPermitted: make([]C.uint8_t, P+1)}
+	firstNs := make([]C.int64_t, cap)
+	var scalars [8]C.int64_t
+	prio, own := make([]C.int32_t, P+1), make([]C.uint32_t, P+1)
+	for i := range priority {
+		prio[i] = C.int32_t(priority[i])
+		own[i] = C.uint32_t(noNominatedRow)
+		if ownRow != nil {
+			own[i] = C.uint32_t(ownRow[i])
+		}
+	}
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if rc := C.bs_seq_run_nominated_flat(g.ctx, C.uint32_t(C.BS_STAGE_PREFILTER), C.uint32_t(P), &prio[0], &own[0], &r.pfCode[0], nil, nil,
+		&r.podNode[0], C.uint32_t(cap), &r.releasedGroup[0], &r.releasedPods[0], &firstNs[0], &r.readyNs[0], &scalars[0],
+		&r.lastPermitted[0]); rc != C.BS_OK {
+		return nil, nil, g.pdbErr("bs_seq_run_nominated_flat", rc)
+	}
+	r.nReleased = int(scalars[0])
+	var n C.uint32_t
+	if rc := C.bs_seq_nominated_read(g.ctx, 0, nil, nil, nil, &n); rc != C.BS_OK {
+		return nil, nil, g.pdbErr("bs_seq_nominated_read", rc)
+	}
+	if n == 0 {
+		return r, nil, nil
+	}
+	id, pod, node := make([]C.uint32_t, n), make([]C.uint32_t, n), make([]C.uint32_t, n)
+	if rc := C.bs_seq_nominated_read(g.ctx, n, &id[0], &pod[0], &node[0], &n); rc != C.BS_OK {
+		return nil, nil, g.pdbErr("bs_seq_nominated_read", rc)
+	}
+	gone := make([]consumedNominee, n)
+	for i := range gone {
+		gone[i] = consumedNominee{uint32(id[i]), uint32(pod[i]), uint32(node[i])}
+	}
+	return r, gone, nil
+}

@@ -839,6 +839,7 @@ int bs_groups_list_apply(bs_ctx* ctx, const bs_groups_list_delta* delta, bs_grou
  *       implies the second, and where they wrap this library's answer is the first test's.
  *       Library rule N2: the table holds OTHER pods' nominations.  Upstream leaves the pod's own nomination out by UID; the queue has
  *       no UID, so a preemptor's own row is the caller's to remove beforehand (one bs_nominated_apply for the batch).
+ *   S.  (rule S and D6: D5 in the normal scheduling cycle, and the row a placed pod gives up — stated at bs_seq_run_nominated below.)
  * Restrictions: BS_STAGE_FILTER is refused (BS_ERR_INVALID: the plugin's Filter takes no part in the fit test; the shipped config
  * does not enable Filter).  Pods nominated by earlier calls count through the resident table below (rule N).  podEligibleToPreemptOthers (PreemptionPolicy Never, terminating pods on the
  * nominated node) is the caller's business, and so is the choice of preemptors: upstream preempts only for a pod that passed
@@ -1039,8 +1040,9 @@ int bs_preempt_cleared_read(bs_ctx* ctx, uint32_t cap, uint32_t* id /*[cap]*/, u
  *                   node >= n, NULL with a count.  BS_ERR_CAPACITY: more than BS_NOM_MAX rows afterwards, or ids past 2^24 (reload:
  *                   a load starts a new id space).  BS_ERR_STATE: no table, a stale node count, pods not loaded with n_insert > 0.
  *                   Both counts 0 is BS_OK and launches nothing.
- * Out of scope: bs_batch_run and bs_seq_run do not see the table (the queue has no priority column); a caller that wants nominees to
- * hold their room against the pass keeps BS_PREEMPT_ASSUME.  Filter-aware preemption.
+ * Out of scope: bs_batch_run and bs_seq_run do not see the table (the queue has no priority column).  For the batch form that is final:
+ * the frozen-snapshot pre-screen stays a pre-screen.  The sequential pass sees it through bs_seq_run_nominated (rule S, below), which takes
+ * the priorities with the call: nominees hold their room against that pass without BS_PREEMPT_ASSUME.  Filter-aware preemption.
  * (A device remap after node-list surgery is bs_nominated_nodes_apply, below.) */
 #define BS_NOM_MAX (1u << 16)   /* live rows of the nominated-pod table (its id space: 2^24) */
 int bs_nominated_load(bs_ctx* ctx, uint32_t m, const uint32_t* node, const int32_t* priority, const int64_t* req /*[L][m]*/, const uint32_t* req_present);
@@ -1085,6 +1087,40 @@ int bs_nominated_apply(bs_ctx* ctx, uint32_t n_remove, const uint32_t* remove_id
  *                (and one pass over the ids the context keeps, when rows were dropped); the device makes one pass over the table. */
 int bs_nominated_nodes_apply(bs_ctx* ctx, uint32_t count, const uint32_t* kind, const uint32_t* index, uint32_t cap, uint32_t* id, uint32_t* node,
                              int32_t* priority, uint32_t* n_out);
+
+/* ---- the sequential pass honours the nominated-pod table: bs_seq_run_nominated ---------------------------------------------------
+ * Upstream's podFitsOnNode calls addNominatedPods (D5 above) for EVERY pod it schedules, not only inside the victim search: that is what
+ * keeps the room a preemption freed for the pod it was freed for.  bs_seq_run_nominated is bs_seq_run with the resident table in its
+ * node choice.  priority[i] is the priority of resident-queue pod i (the queue has no such column); own_id[i] is the id of the table row
+ * that IS pod i, or BS_NOM_NONE; a NULL own_id means nobody has one.  p must be bs_pods_count.
+ *   S.  (rule S.)  For pod i of priority P the node choice is bs_seq_run's first fit in list order, unchanged: the same skip rule (node
+ *       flags, checkFit bit), the same holds() rule, no preference for the nominated node.  The requests node k is tested with are its
+ *       current requests, as the earlier pods of this pass left them, plus every LIVE row of the table on k with row.priority >= P
+ *       (signed int32; equal priority counts) that is not pod i's own row.  A row is added as rule N adds it (AddPod): all L lanes,
+ *       wrapping.  Pods lane: requested + (sum of the rows' pods lanes) + 1 <= allocatable.  A requested scalar s: want <= allocatable -
+ *       ((requested key present ? requested : 0) + sum of the rows' lane s); the allocatable key is still required.  Rows never enter the
+ *       node requests: the assume step writes the pod's own request only, and bs_nodes_read after the pass holds no row.
+ *       Library rule S1: PreFilter is untouched.  The plugin's cluster sums (core.go:595-632) read the plugin's own NodeInfo, which
+ *       addNominatedPods never modifies (it works on a copy for the fit test): every pf_code, pf_first_k and pf_leader is what bs_seq_run
+ *       reports for the same sequence of assumes.
+ *   D6. (recalled upstream, v1.17.5, not vendored.)  scheduleOne -> assume -> SchedulingQueue.DeleteNominatedPodIfExists: when pod i with
+ *       own row r is assumed on ANY node, r stops being live for every later pod of the pass — whether or not i's gang reaches its quorum
+ *       and whether or not the node is the nominated one.  After the pass r leaves the table by the stable compaction and its id is dead
+ *       exactly as after bs_nominated_apply.  A pod that is not assumed (a PreFilter rejection, no node found, a missing group) keeps its
+ *       row.
+ *   bs_seq_nominated_read   the consumed rows of the last successful bs_seq_run_nominated in ascending id, as (id, queue index of the
+ *       pod, node it was assumed on); *n_out the true count, the first min(n, cap) rows are written.  BS_ERR_STATE when the context's
+ *       last pass was not that call.
+ *   after the call  the context is in the state bs_seq_run leaves: bs_seq_expire, bs_seq_waiting_read, bs_wait_park and bs_bound_bind work as
+ *       after bs_seq_run.  With an empty table and no own ids every output and all resident state equal bs_seq_run's.
+ *   errors      all found on the host before any launch; nothing resident changes.  Everything bs_seq_run refuses, with the same code.
+ *       BS_ERR_INVALID: BS_STAGE_FILTER (and with it BS_BATCH_FILTER_DENY), for the reason bs_preempt_run gives; p != bs_pods_count; a
+ *       NULL priority with p > 0; an own id that is dead, unknown, or named by two pods.  BS_ERR_STATE: no table, or a table whose node
+ *       count is stale; a sharded or external-reduce context. */
+#define BS_NOM_NONE 0xFFFFFFFFu
+int bs_seq_run_nominated(bs_ctx* ctx, uint32_t stages, uint32_t p, const int32_t* priority /*[p]*/, const uint32_t* own_id /*[p] or NULL*/,
+                         bs_seq_out* out);
+int bs_seq_nominated_read(bs_ctx* ctx, uint32_t cap, uint32_t* id, uint32_t* pod, uint32_t* node, uint32_t* n_out);
 /* The live bound table in table order: node ascending, importance order within a node; bs_bound_count entries.  id_out[i] = the
  * entry's id (its index at the last bs_bound_load), node_out[i] = its node.  BS_ERR_STATE before bs_bound_load; the arrays may be NULL
  * when the table is empty. */
@@ -1362,6 +1398,10 @@ int bs_batch_read_flat(bs_ctx* ctx, uint8_t* pf_code, uint32_t* pf_first_k, int3
 int bs_seq_run_flat(bs_ctx* ctx, uint32_t stages, uint8_t* pf_code, uint32_t* pf_first_k, int32_t* pf_leader, int32_t* pod_node, uint32_t cap,
                     uint32_t* released_group, uint32_t* released_pods, int64_t* first_ns, int64_t* ready_ns, int64_t* scalars_out,
                     uint8_t* last_permitted);
+/* bs_seq_run_nominated: bs_seq_run_flat's arguments with the call's two arrays in front of the results */
+int bs_seq_run_nominated_flat(bs_ctx* ctx, uint32_t stages, uint32_t p, const int32_t* priority, const uint32_t* own_id, uint8_t* pf_code,
+                              uint32_t* pf_first_k, int32_t* pf_leader, int32_t* pod_node, uint32_t cap, uint32_t* released_group,
+                              uint32_t* released_pods, int64_t* first_ns, int64_t* ready_ns, int64_t* scalars_out, uint8_t* last_permitted);
 /* bs_fit_build: node tables, then the template tables; `ex_*` = bs_fit_templates.exprs, `fd_*` = bs_fit_templates.fields */
 int bs_fit_build_flat(bs_ctx* ctx, uint32_t n, const uint32_t* name, const uint32_t* label_off, const uint32_t* label_key, const uint32_t* label_val,
                       const int64_t* label_int, const uint8_t* label_int_ok, const uint32_t* taint_off, const uint32_t* taint_key,
