@@ -49,12 +49,14 @@ ABI_SYMBOLS = [
     "bs_nominated_nodes_apply",
     "bs_preempt_cleared_read",
     "bs_seq_run_nominated", "bs_seq_run_nominated_flat", "bs_seq_nominated_read",
+    "bs_seq_run_scored", "bs_seq_run_scored_flat", "bs_seq_score_read",
 ]
 
 SEQ_EXPIRE_DENY, SEQ_EXPIRE_ALL = 1, 2    # bs_seq_expire flags
 WAIT_MAX = 1 << 24                        # BS_WAIT_MAX: rows and ids of the wait table
 NOM_MAX = 1 << 16                         # BS_NOM_MAX: live rows of the nominated-pod table (its id space goes up to 2^24)
 NOM_NONE = 0xFFFFFFFF                     # bs_preempt_nominated_read: the preemptor got no row
+SCORE_WEIGHT_MAX = 65536                  # BS_SCORE_WEIGHT_MAX: each weight of bs_seq_score
 
 BS_BOUND_NODES = soa.BS_BOUND_NODES     # bs_bound_apply_ex: the delta also moves the node requests
 
@@ -137,6 +139,11 @@ class SeqOut(C.Structure):
                 ("n_released", C.c_uint32), ("total_ns", C.c_int64), ("node_picks", C.c_uint64), ("node_scans", C.c_uint64),
                 ("scan_rounds", C.c_uint64), ("pick_rounds", C.c_uint64), ("leader_folds", C.c_uint64), ("table_builds", C.c_uint64),
                 ("last_permitted", C.POINTER(C.c_uint8))]
+
+
+class SeqScore(C.Structure):
+    """bs_seq_score: the weights of rule P (each at most SCORE_WEIGHT_MAX)"""
+    _fields_ = [("w_least", C.c_uint32), ("w_most", C.c_uint32), ("w_balanced", C.c_uint32)]
 
 
 class SeqExpireOut(C.Structure):
@@ -280,6 +287,10 @@ def load_library(path: str | None = None):
     L.bs_seq_run_nominated_flat.argtypes = [vp, u32, u32, P(i32), P(u32), P(u8), P(u32), P(i32), P(i32), u32, P(u32), P(u32), P(C.c_int64), P(C.c_int64),
                                             P(C.c_int64), P(u8)]
     L.bs_seq_nominated_read.argtypes = [vp, u32, P(u32), P(u32), P(u32), P(u32)]
+    L.bs_seq_run_scored.argtypes = [vp, u32, P(SeqScore), P(SeqOut)]
+    L.bs_seq_run_scored_flat.argtypes = [vp, u32, u32, u32, u32, P(u8), P(u32), P(i32), P(i32), u32, P(u32), P(u32), P(C.c_int64), P(C.c_int64),
+                                         P(C.c_int64), P(u8)]
+    L.bs_seq_score_read.argtypes = [vp, u32, P(u32), P(u32)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:
@@ -639,9 +650,9 @@ class Context:
         resident queue, on the device.  The context's node requests and group state are what the pass left."""
         return self._seq_pass(stages, cap, None, False)
 
-    def _seq_pass(self, stages: int, cap, nominated, flat: bool) -> dict:
+    def _seq_pass(self, stages: int, cap, nominated, flat: bool, weights=None) -> dict:
         """the result arrays of a sequential pass and the call: bs_seq_run (nominated None), else bs_seq_run_nominated with
-        nominated = (p, priority, own_id), through its flat form when flat"""
+        nominated = (p, priority, own_id), through its flat form when flat; weights = (w_least, w_most, w_balanced): bs_seq_run_scored"""
         p, cap = self.pods_count(), max(self.g if cap is None else cap, 1)
         n = max(p, 1)
         pf, fk = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
@@ -651,7 +662,15 @@ class Context:
         lp = np.zeros(n, np.uint8)
         o = SeqOut(pf.ctypes.data_as(C.POINTER(C.c_uint8)), _u32p(fk), ld.ctypes.data_as(C.POINTER(C.c_int32)), node.ctypes.data_as(C.POINTER(C.c_int32)),
                    cap, _u32p(rg), _u32p(rp), _i64p(t0), _i64p(t1), 0, 0, 0, 0, 0, 0, 0, 0, lp.ctypes.data_as(C.POINTER(C.c_uint8)))
-        if nominated is None:
+        if weights is not None and flat:
+            sc = np.zeros(8, np.int64)
+            self._chk(self._lib.bs_seq_run_scored_flat(self._h, stages, *weights, o.pf_code, o.pf_first_k, o.pf_leader, o.pod_node, cap, o.released_group,
+                                                       o.released_pods, o.first_ns, o.ready_ns, _i64p(sc), o.last_permitted), "bs_seq_run_scored_flat")
+            (o.n_released, o.total_ns, o.node_picks, o.node_scans, o.scan_rounds, o.pick_rounds, o.leader_folds, o.table_builds) = (int(v) for v in sc)
+        elif weights is not None:
+            w = SeqScore(*weights)
+            self._chk(self._lib.bs_seq_run_scored(self._h, stages, C.byref(w), C.byref(o)), "bs_seq_run_scored")
+        elif nominated is None:
             self._chk(self._lib.bs_seq_run(self._h, stages, C.byref(o)), "bs_seq_run")
         elif flat:
             sc = np.zeros(8, np.int64)
@@ -688,6 +707,21 @@ class Context:
         self._chk(self._lib.bs_seq_nominated_read(self._h, cap, _u32p(i_), _u32p(pd), _u32p(nd), C.byref(n)), "bs_seq_nominated_read")
         k = min(int(n.value), cap)
         return dict(n=int(n.value), id=i_[:k].copy(), pod=pd[:k].copy(), node=nd[:k].copy())
+
+    def seq_run_scored(self, weights, stages: int = soa.STAGE_PREFILTER, cap: int | None = None, flat: bool = False) -> dict:
+        """bs_seq_run_scored: seq_run with the node choice of rule P — among the nodes seq_run's rule accepts, the one with the largest
+        w_least * least + w_most * most + w_balanced * balanced, ties to the lowest index.  weights = (w_least, w_most, w_balanced), each at
+        most SCORE_WEIGHT_MAX; (0, 0, 0) is seq_run.  seq_score_read reports the chosen totals."""
+        wl, wm, wb = (int(v) for v in weights)
+        return self._seq_pass(stages, cap, None, flat, (wl, wm, wb))
+
+    def seq_score_read(self, p: int | None = None) -> dict:
+        """bs_seq_score_read: per queue pod of the last seq_run_scored the chosen node's total (0: no node) and n_fit, the number of nodes
+        the node rule accepted (0: the choice was not reached).  p overrides the queue length handed to the library (tests)."""
+        n = self.pods_count() if p is None else int(p)
+        total, n_fit = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        self._chk(self._lib.bs_seq_score_read(self._h, n, _u32p(total), _u32p(n_fit)), "bs_seq_score_read")
+        return dict(total=total[:n], n_fit=n_fit[:n])
 
     def seq_expire(self, groups=None, deny: bool = False, all: bool = False, group_cap: int | None = None, pod_cap: int | None = None,
                    flat: bool = False, flags: int | None = None) -> dict:

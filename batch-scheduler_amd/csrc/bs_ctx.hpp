@@ -255,6 +255,10 @@ struct bs_ctx {
   // bs_seq_nominated_read: the rows the last pass consumed (ascending id), valid while the last pass was a successful bs_seq_run_nominated
   bool seq_nom_valid = false;
   std::vector<uint32_t> seq_nom_id, seq_nom_pod, seq_nom_node;
+  // bs_seq_score_read: total[P] | n_fit[P] of the last pass, valid while that pass was a successful bs_seq_run_scored over seq_score_p pods
+  DevBuf d_seq_score;
+  bool seq_score_valid = false;
+  uint32_t seq_score_p = 0;
   DevBuf d_sexp;                     // per-call scratch: block totals, slots, rows, dirty list, records
   DevBuf d_sexp_nodes;               // per-node delta [L][N], key bits, dirty words: zero between calls (k_se_nodes re-zeroes what it read)
   uint32_t sexp_n = 0, sexp_l = 0;   // the layout d_sexp_nodes was zeroed for

@@ -36,6 +36,7 @@
 
 #include "bs_kernels.hpp"
 #include "bs_nom_view.hpp"
+#include "bs_seq_score.hpp"
 
 namespace bs {
 
@@ -146,6 +147,21 @@ struct SeqNomShared {
   uint32_t grow;                 // a row may GROW the room some pod sees (a negative or huge lane, a sum that could wrap): the pass runs without cursors
   uint32_t wild[kSeqPruneTiles / 32];   // tiles whose first-fit bounds are never used: a row sum there may GROW the room (negative or huge lanes)
 };
+// bs_seq_run_scored (include/bsched.h, rule P): what the scored instantiations k_seq_scored get on top.  The node choice is a FULL search:
+// of the nodes bs_seq_run's rule accepts, the one with the largest total (bs_seq_score.hpp), ties to the lowest index.  Nothing else moves.
+constexpr int kSeqScoredFullLanes = 4;     // scalar lanes up to which k_seq_scored keeps everything in registers (see seq_pick_scored; = kLanesUnrolled)
+struct SeqScore {
+  uint32_t w_least, w_most, w_balanced;
+  uint32_t* total;               // [P] zeroed before the launch: the chosen node's total
+  uint32_t* n_fit;               // [P] zeroed before the launch: nodes the rule accepted
+  uint32_t lds_off;              // byte offset of SeqScoreShared in dynamic LDS (behind the key window and the table summaries)
+};
+// scored-only LDS state, in the DYNAMIC part as SeqNomShared is
+struct SeqScoreShared {
+  unsigned long long key[kSeqWaves];   // each wave's best candidate: total << 32 | (0xFFFFFFFF - node), 0 = none
+  uint32_t nfit[kSeqWaves];            // candidates the wave counted
+};
+
 // the rows the fit test adds to node k for a pod of priority P (AddPod per row: all L lanes, wrapping)
 template <int TS>
 __device__ __forceinline__ void seq_nominees(const NomView& nm, const uint8_t* consumed, uint32_t head, int32_t P, uint32_t own, Shape<TS> sh,
@@ -878,6 +894,206 @@ __device__ __forceinline__ uint32_t seq_pick(const NodesDev& nd, const SeqDev& s
   return found;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The scored node choice + the assume step (rule P; bs_seq_run_scored).  seq_pick's tile walk — thread t votes for tile chunk + t, wave w
+// visits its 64 tiles of a chunk with a lane per node — as a FULL search: no early stop, no cursor, no start tile.  The per-tile bounds
+// still skip tiles (a tile they exclude holds no candidate: neither the maximum nor the count can change).  The fit test is seq_pick's
+// flag-less one, word for word.  Every lane keeps the best candidate it has seen over all its wave's tiles as a 64-bit key
+// total << 32 | (0xFFFFFFFF - node) — the largest total, then the lowest index — and, beside it, that node's values as the assume step needs
+// them; keys are reduced over the wave, then over the waves through LDS (one barrier), and the lane that owns the winner assumes from its
+// own registers.  Returns the node (BS_INF none), wave-uniform, identical in every wave; total_out / nfit_out likewise.
+// The assume step is seq_pick's, restated on the kept values (a shared function would change seq_pick's instructions).
+// ---------------------------------------------------------------------------------------------------------------------
+template <int TS>
+__device__ __forceinline__ uint32_t seq_pick_scored(const NodesDev& nd, const SeqDev& sq, const SeqParams& prm, SeqShared& sh_, SeqScoreShared& ss, const SeqPick& q,
+                                                    const SeqScore& sco, const uint32_t (&slot_key)[kSeqCacheSlots], bool drained, SeqAssumed& out,
+                                                    unsigned long long& tiles_looked, uint32_t& total_out, uint32_t& nfit_out, uint32_t pw) {
+  const Shape<TS> sh(prm.S);
+  const uint32_t L = sh.L(), S = sh.S();
+  // The instantiations for more than kSeqScoredFullLanes scalar lanes are built LEAN, so that they need no scratch memory: such a search
+  // keeps the key and the node's words only and the winning lane fetches its node's lanes behind the decision (one lane, one trip), and it
+  // reads the pod's scalar request lanes from the staged window in LDS (pw) where it needs them instead of holding up to twelve more
+  // wave-uniform int64 (q.preq[4..] is not filled for it).
+  constexpr bool kLean = TS > kSeqScoredFullLanes;
+  auto preq_s = [&](uint32_t j) -> int64_t {
+    if constexpr (kLean) return sh_.pw_req[j][pw]; else return q.preq[j];
+  };
+  const int lane = lane_id(), w = (int)uni32((uint32_t)wave_id());
+  const uint32_t N = nd.n;
+  out.ap = out.rp = out.fitbits = 0;
+  total_out = 0;
+  nfit_out = 0;
+  if (!drained) __syncthreads();                                            // the assume steps of earlier pods have landed before a tile is read
+  if (!N || q.pcls >= nd.n_classes || q.fl >= 16u) return BS_INF;          // (ERR_PG_NOT_FOUND / the nil-leader panic: Filter fails everywhere)
+  const bool fl_all = q.fl != BS_FL_EVALUATED;                              // Filter passes on every node
+  const uint32_t ntiles = (N + 63u) >> 6;
+  const uint32_t* fitrow = nd.fit + (size_t)q.pcls * nd.fit_words;
+  unsigned long long best = 0ull;                                           // this lane's best candidate and its node's values
+  int64_t b_al[BS_MAX_LANES], b_rq[BS_MAX_LANES], b_l07[BS_MAX_LANES], b_l10[BS_MAX_LANES];
+#pragma unroll
+  for (uint32_t j = 0; j < BS_MAX_LANES; ++j) { b_al[j] = 0; b_rq[j] = 0; b_l07[j] = 0; b_l10[j] = 0; }
+  uint32_t b_ap = 0, b_rp = 0, b_fbits = 0, b_meta = 0;
+  uint32_t cnt = 0;                                                         // candidates this wave has seen (wave-uniform)
+  for (uint32_t chunk = 0; chunk < ntiles; chunk += kSeqBlock) {
+    const uint32_t t = chunk + threadIdx.x;
+    bool cand = t < ntiles;
+    if (cand && prm.prune) {
+      cand = !(q.preq[0] > 0 && sh_.pmax[0][t] < q.preq[0]) && !(q.preq[1] > 0 && sh_.pmax[1][t] < q.preq[1]);
+      if (q.preq[0] > 0 && q.preq[1] > 0) cand = cand && !(sh_.pmax[2][t] < seq_joint(q.preq[0], q.preq[1]));
+    }
+    unsigned long long cm = __ballot(cand);
+    while (cm) {
+      const uint32_t tile = chunk + ((uint32_t)w << 6) + (uint32_t)(__ffsll((long long)cm) - 1);
+      cm &= cm - 1ull;
+      tiles_looked++;
+      const uint32_t n = (tile << 6) + (uint32_t)lane;
+      const bool valid = n < N;
+      const uint32_t nn = valid ? n : N - 1u;
+      const uint32_t fl = nd.flags[nn];
+      const uint32_t ap = nd.apres[nn], rp = sq.rpres[nn];
+      const uint32_t fw = fitrow[nn >> 5];
+      uint32_t fws[kSeqCacheSlots];
+#pragma unroll
+      for (uint32_t c = 0; c < kSeqCacheSlots; ++c)
+        fws[c] = (c < prm.cache_slots && slot_key[c] != BS_INF) ? nd.fit[(size_t)(slot_key[c] >> 1) * nd.fit_words + (nn >> 5)] : 0u;
+      int64_t al[BS_MAX_LANES], rq[BS_MAX_LANES], l07[BS_MAX_LANES], l10[BS_MAX_LANES];
+#pragma unroll
+      for (uint32_t j = 0; j < BS_MAX_LANES; ++j) {
+        al[j] = 0; rq[j] = 0; l07[j] = 0; l10[j] = 0;
+        if (j < L) {
+          al[j] = nd.alloc[(size_t)j * nd.stride + nn];
+          rq[j] = sq.nreq[(size_t)j * nd.stride + nn];
+          if constexpr (!kLean) {
+            l07[j] = sq.left07[(size_t)j * nd.stride + nn];     // (for the assume step: no second round trip behind the decision)
+            l10[j] = sq.left10[(size_t)j * nd.stride + nn];
+          }
+        }
+      }
+      const uint32_t meta = sq.nmeta[nn];
+      uint32_t fbits = 0;
+#pragma unroll
+      for (uint32_t c = 0; c < kSeqCacheSlots; ++c) fbits |= ((fws[c] >> (nn & 31u)) & 1u) << c;
+      const bool sched = valid && fl == 0u;
+      bool ok = sched && ((fw >> (nn & 31u)) & 1u);
+      const int64_t f0 = wsub(al[0], rq[0]), f1 = wsub(al[1], rq[1]);
+      if (!fl_all) {                                         // computeResourceSatisfied on this node (core.go:545-563)
+        bool c2 = !(q.ff & 1u), c3h = !(q.ff & 2u);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int64_t left = wsub(al[j], rq[j]);                                                   // getLeftResource :460-463
+          c2 = c2 && left >= q.FR[j];
+          c3h = c3h && left >= q.FM[j];
+        }
+        ok = ok && (c2 || !c3h);                                                                     // case 2 | case 3
+      }
+#pragma unroll
+      for (int j = 0; j < 3; ++j) ok = ok && !(q.preq[j] > 0 && q.preq[j] > wsub(al[j], rq[j]));
+      ok = ok && !(wadd(rq[3], 1) > al[3]);
+#pragma unroll
+      for (uint32_t s = 0; s < BS_MAX_SCALARS; ++s) {
+        if (s < S && ((q.ppres >> s) & 1u) && preq_s(4 + s) > 0) {
+          const int64_t r0 = ((rp >> s) & 1u) ? rq[4 + s] : 0;
+          ok = ok && ((ap >> s) & 1u) && !(preq_s(4 + s) > wsub(al[4 + s], r0));
+        }
+      }
+      if (ok) {                                              // rule P: R = requested + request (wrapping), cpu and memory only
+        const uint32_t total = score_total(al[0], score_wadd(rq[0], q.preq[0]), al[1], score_wadd(rq[1], q.preq[1]), sco.w_least, sco.w_most, sco.w_balanced);
+        const unsigned long long key = ((unsigned long long)total << 32) | (unsigned long long)(0xFFFFFFFFu - n);
+        if (key > best) {
+          best = key;
+          if constexpr (!kLean) {
+#pragma unroll
+            for (uint32_t j = 0; j < BS_MAX_LANES; ++j) { b_al[j] = al[j]; b_rq[j] = rq[j]; b_l07[j] = l07[j]; b_l10[j] = l10[j]; }
+          }
+          b_ap = ap; b_rp = rp; b_fbits = fbits; b_meta = meta;
+        }
+      }
+      const unsigned long long m = __ballot(ok);
+      cnt += (uint32_t)__popcll(m);
+      if (!m && prm.prune && !((sh_.tight[tile >> 5] >> (tile & 31u)) & 1u)) {   // looked at in vain: tighten the tile's bounds to what is really there
+        const long long m0 = readlane63_i64(wave_max_i64_lane63(sched ? (long long)f0 : INT64_MIN));
+        const long long m1 = readlane63_i64(wave_max_i64_lane63(sched ? (long long)f1 : INT64_MIN));
+        const long long m2 = readlane63_i64(wave_max_i64_lane63(sched ? seq_joint(f0, f1) : INT64_MIN));
+        if (lane == 0) { sh_.pmax[0][tile] = m0; sh_.pmax[1][tile] = m1; sh_.pmax[2][tile] = m2; atomicOr(&sh_.tight[tile >> 5], 1u << (tile & 31u)); }
+      }
+    }
+  }
+  // ---- the wave's best (one lane owns it: the node is part of the key), then the block's
+  const unsigned long long wbest = wave_max_u64_all(best);
+  const bool owner = best != 0ull && best == wbest;
+  if (owner) { ss.key[w] = best; sh_.asm_ap[0][w] = b_ap; sh_.asm_rp[0][w] = b_rp; sh_.asm_fit[0][w] = b_fbits; }
+  if (lane == 0) { if (wbest == 0ull) ss.key[w] = 0ull; ss.nfit[w] = cnt; }
+  lds_barrier();
+  unsigned long long top = 0ull;
+  uint32_t ww = 0, nf = 0;
+#pragma unroll
+  for (int x = 0; x < kSeqWaves; ++x) {
+    const unsigned long long k = ss.key[x];
+    if (k > top) { top = k; ww = (uint32_t)x; }
+    nf += ss.nfit[x];
+  }
+  top = uni64(top);
+  ww = uni32(ww);
+  nfit_out = uni32(nf);
+  if (top == 0ull) return BS_INF;
+  const uint32_t found = 0xFFFFFFFFu - (uint32_t)top;
+  total_out = (uint32_t)(top >> 32);
+  out.ap = sh_.asm_ap[0][ww]; out.rp = sh_.asm_rp[0][ww]; out.fitbits = sh_.asm_fit[0][ww];
+  if (owner && best == top) {
+    // ---- assume (NodeInfo.AddPod): requested += request, pods lane + 1; the left arrays and the meta word follow
+    const uint32_t at = found;
+    if constexpr (kLean) {
+#pragma unroll
+      for (uint32_t j = 0; j < BS_MAX_LANES; ++j) {
+        if (j < L) {
+          b_al[j] = nd.alloc[(size_t)j * nd.stride + at];
+          b_rq[j] = sq.nreq[(size_t)j * nd.stride + at];
+          b_l07[j] = sq.left07[(size_t)j * nd.stride + at];
+          b_l10[j] = sq.left10[(size_t)j * nd.stride + at];
+        }
+      }
+    }
+    uint32_t nrp = b_rp;
+#pragma unroll
+    for (uint32_t j = 0; j < BS_MAX_LANES; ++j) {
+      if (j < L) {
+        int64_t nr = b_rq[j];
+        bool touched = false;
+        if (j < 3) { nr = wadd(b_rq[j], q.preq[j]); touched = true; }
+        else if (j == 3) { nr = wadd(b_rq[j], 1); touched = true; }
+        else if ((q.ppres >> (j - 4)) & 1u) {
+          nr = wadd(((b_rp >> (j - 4)) & 1u) ? b_rq[j] : 0, preq_s(j));
+          nrp |= 1u << (j - 4);
+          touched = true;
+        }
+        if (touched) {
+          sq.nreq[(size_t)j * nd.stride + at] = nr;
+          if (j < 4 || ((b_rp >> (j - 4)) & 1u)) {             // left = scaled allocatable - requested: it moves by what requested moves by
+            const int64_t dlt = wsub(nr, b_rq[j]);
+            sq.left07[(size_t)j * nd.stride + at] = wsub(b_l07[j], dlt);
+            sq.left10[(size_t)j * nd.stride + at] = wsub(b_l10[j], dlt);
+          } else {                                             // a scalar key the node's requests did not have: the lane starts to exist
+            sq.left07[(size_t)j * nd.stride + at] = wsub(scale_f32(b_al[j], 0.7f), nr);
+            sq.left10[(size_t)j * nd.stride + at] = wsub(scale_f32(b_al[j], 1.0f), nr);
+          }
+        }
+      }
+    }
+    if (nrp != b_rp) {
+      sq.rpres[at] = nrp;
+      sq.nmeta[at] = (b_meta & 0xFu) | ((b_ap & nrp) << 4);
+    }
+    if (prm.prune) {                                       // a negative request frees capacity: the bounds must stay upper bounds
+      const int64_t n0 = wsub(b_al[0], wadd(b_rq[0], q.preq[0])), n1 = wsub(b_al[1], wadd(b_rq[1], q.preq[1]));
+      if (n0 > sh_.pmax[0][at >> 6]) sh_.pmax[0][at >> 6] = n0;
+      if (n1 > sh_.pmax[1][at >> 6]) sh_.pmax[1][at >> 6] = n1;
+      if (seq_joint(n0, n1) > sh_.pmax[2][at >> 6]) sh_.pmax[2][at >> 6] = seq_joint(n0, n1);
+      atomicAnd(&sh_.tight[at >> 11], ~(1u << ((at >> 6) & 31u)));     // the node that held a maximum may be the one that just filled up
+    }
+  }
+  return found;
+}
+
 // findMaxPG (core.go:701-739) over the keys.  Wave-uniform result: leader (-1 none), panic.
 __device__ __forceinline__ void seq_find_max(const GroupsDev& gr, const SeqDev& sq, const SeqParams& prm, SeqShared& sh_, const unsigned long long* lkeys,
                                              int32_t& leader, bool& panic, unsigned long long& top_out) {
@@ -999,12 +1215,13 @@ __device__ __forceinline__ void seq_group_zero(SeqGroup& o, Shape<TS> sh) {
   res_zero(o.mr, sh);
 }
 
-// The pass: its body is bs_seq_pass.inc, included by both kernels.  NOM = false is bs_seq_run's kernel: six instantiations (bs_lanes.hpp,
+// The pass: its body is bs_seq_pass.inc, included by all three kernel templates.  NOM = false is bs_seq_run's kernel: six instantiations (bs_lanes.hpp,
 // lanes_narrow), name and arguments as they always were.
 template <int TS>
 __global__ __launch_bounds__(kSeqBlock, 1) void k_seq_pass(PodsDev pods, GroupsDev gr, NodesDev nd, SeqDev sq, SeqParams prm) {
-  constexpr bool NOM = false;
+  constexpr bool NOM = false, SCORE = false;
   const SeqNom nom{};                                        // (named by the discarded NOM-only lines)
+  const SeqScore sco{};                                      // (... and by the discarded SCORE-only ones)
 #include "bs_seq_pass.inc"
 }
 // bs_seq_run_nominated's: k_seq_pass<TS, true>, rule S on top, the same six lane counts (an overload: a defaulted second parameter would
@@ -1012,8 +1229,25 @@ __global__ __launch_bounds__(kSeqBlock, 1) void k_seq_pass(PodsDev pods, GroupsD
 template <int TS, bool NOM>
 __global__ __launch_bounds__(kSeqBlock, 1) void k_seq_pass(PodsDev pods, GroupsDev gr, NodesDev nd, SeqDev sq, SeqParams prm, SeqNom nom) {
   static_assert(NOM, "the flag-less pass is k_seq_pass<TS>");
+  constexpr bool SCORE = false;
+  const SeqScore sco{};
 #include "bs_seq_pass.inc"
 }
+// bs_seq_run_scored's: the third inclusion, rule P in the node choice (SCORE = true, NOM = false); emitted by tu_seq_score.hip.  It reads and
+// writes no first-fit cursor.  One instantiation per lane count a context can have, 0 .. BS_MAX_SCALARS (bs_lanes.hpp, lanes_wide), and no
+// generic-lane one: the body at TS = -1 branches on every lane of every unrolled loop and keeps more wave-uniform state than the SGPR spill
+// lanes hold — 24 bytes of scratch memory before the scored search is even part of it —, and the library admits scratch in k_seq_pass alone
+// (tests/test_kernel_resources.py).  With the lane count fixed, and built lean above kSeqScoredFullLanes, every instantiation is free of it.
+template <int TS>
+__global__ __launch_bounds__(kSeqBlock, 1) void k_seq_scored(PodsDev pods, GroupsDev gr, NodesDev nd, SeqDev sq, SeqParams prm, SeqScore sco) {
+  static_assert(TS >= 0, "the scored pass has fixed-lane instantiations only");
+  constexpr bool NOM = false, SCORE = true;
+  const SeqNom nom{};
+#include "bs_seq_pass.inc"
+}
+// the launch of k_seq_scored<TS> for S scalar lanes (defined in tu_seq_score.hip; called by tu_seq.hip)
+void launch_seq_scored(hipStream_t stream, uint32_t S, size_t lds, const PodsDev& pd, const GroupsDev& gr, const NodesDev& nd, const SeqDev& sq, const SeqParams& prm,
+                       const SeqScore& sco);
 // the launch of k_seq_pass<TS, true> for S scalar lanes (defined in tu_seq_nom.hip, the unit that emits those kernels; called by tu_seq.hip)
 void launch_seq_nominated(hipStream_t stream, uint32_t S, size_t lds, const PodsDev& pd, const GroupsDev& gr, const NodesDev& nd, const SeqDev& sq, const SeqParams& prm,
                           const SeqNom& nom);

@@ -1,8 +1,13 @@
-// bs_seq_pass.inc — the body of k_seq_pass (bs_seq.hpp), included once by each of its two kernel templates: k_seq_pass<TS> (bs_seq_run) with
-// `constexpr bool NOM = false`, k_seq_pass<TS, true> (bs_seq_run_nominated, rule S) with NOM = true and the kernel argument `nom`.  Every
-// NOM-only line sits behind `if constexpr (NOM)`.  A shared __device__ function would be the usual form; the flag-less kernels then come
+// bs_seq_pass.inc — the body of k_seq_pass (bs_seq.hpp), included once by each of its three kernel templates: k_seq_pass<TS> (bs_seq_run) with
+// `constexpr bool NOM = false`, k_seq_pass<TS, true> (bs_seq_run_nominated, rule S) with NOM = true and the kernel argument `nom`,
+// k_seq_scored<TS> (bs_seq_run_scored, rule P) with SCORE = true and the kernel argument `sco`.  Every NOM-only line sits behind
+// `if constexpr (NOM)`, every scored-only line behind `if constexpr (SCORE)`; what the scored pass must not touch (the first-fit cursors,
+// `mono`) behind `if constexpr (!SCORE)`.  A shared __device__ function would be the usual form; the flag-less kernels then come
 // out as other instructions than before (inlining a by-reference body is not the same input to the optimiser), and bs_seq_run's kernels
 // are required to stay instruction-identical.  Kernel parameters in scope: pods, gr, nd, sq, prm.
+  // The scored kernels for more than kSeqScoredFullLanes scalar lanes are built lean (no scratch memory): no table summaries in LDS (every
+  // PreFilter scan walks the list in rounds, as with prm.cache_slots == 0) and no wave-uniform copy of the pod's scalar request lanes (seq_pick_scored).
+  constexpr bool kLeanScored = SCORE && TS > kSeqScoredFullLanes;
   extern __shared__ unsigned long long s_keys[];             // [G] when prm.keys_in_lds
   __shared__ SeqShared sh_;
   const Shape<TS> sh(prm.S);
@@ -117,6 +122,7 @@
   uint32_t slot_key[kSeqCacheSlots], slot_age[kSeqCacheSlots], age_ctr = 0;
 #pragma unroll
   for (uint32_t c = 0; c < kSeqCacheSlots; ++c) { slot_key[c] = BS_INF; slot_age[c] = 0; }
+  if constexpr (!SCORE)
   for (uint32_t e = threadIdx.x; e < kSeqCursors; e += kSeqBlock) { sh_.cur_kn[e] = 0ull; sh_.cur_fc[e] = 0u; }   // (ordered by the barrier in front of the loop)
   uint32_t hit_par = 0;                                      // which of the two early-stop words the next search uses
   bool mono = true;                                          // no assumed request has freed capacity so far: the first-fit cursors hold
@@ -338,7 +344,7 @@
       if (stores_pending) { __syncthreads(); stores_pending = false; }
       BS_SEQ_P(3);
       drained = true;
-      if (prm.cache_slots) {
+      if (!kLeanScored && prm.cache_slots) {
         const uint32_t key = (tcls << 1) | (pct07 ? 1u : 0u);
         uint32_t sel = BS_INF;
 #pragma unroll
@@ -385,6 +391,10 @@
       q.ppres = uni32(sh_.pw_pres[pw]);
 #pragma unroll
       for (uint32_t j = 0; j < BS_MAX_LANES; ++j) q.preq[j] = j < L ? (int64_t)uni64((uint64_t)sh_.pw_req[j][pw]) : 0;
+      if constexpr (kLeanScored) {                           // (the lean search reads the scalar lanes from the staged window itself)
+#pragma unroll
+        for (uint32_t j = 4; j < BS_MAX_LANES; ++j) q.preq[j] = 0;
+      }
       if (prm.filter_deny && grouped) {
         // ---- Filter's TTL writes (core.go:170-191), every node of the list offered (the batch form's rule, bs_batch_run): a node whose
         // Filter fails — getLeftResource nil (:545-548) or neither case 2 nor case 3 (:562-563) — deny-lists the group (:183-185) for the
@@ -420,6 +430,14 @@
         if (passed && t0) sq.last_permitted[i] = 1;
       }
       SeqAssumed as;
+      if constexpr (SCORE) {
+        // rule P: the candidate with the largest total, ties to the lowest index — a full search, so no cursor and no `mono`
+        uint32_t sc_total = 0, sc_nfit = 0;
+        at = seq_pick_scored<TS>(nd, sq, prm, sh_, *reinterpret_cast<SeqScoreShared*>(reinterpret_cast<unsigned char*>(s_keys) + sco.lds_off), q, sco, slot_key,
+                                 drained || !stores_pending, as, n_tiles, sc_total, sc_nfit, pw);
+        if (!drained) stores_pending = false;                // (the search drained them itself)
+        if (threadIdx.x == kSeqResultThread) { sco.total[i] = sc_total; sco.n_fit[i] = sc_nfit; }
+      } else {
       // first-fit cursor of the pod's request class (pods of a gang share a template: the search of the next one starts where this
       // one's ended).  Exact while (a) no assumed request has a negative lane — then free capacity only shrinks and a node that
       // could not hold this request cannot hold it later —, (b) the plugin's Filter does not gate the choice (its verdict moves
@@ -469,12 +487,13 @@
         for (uint32_t j = 0; j < BS_MAX_LANES; ++j)
           if (j < L && j != 3 && q.preq[j] < 0 && (j < 3 || ((q.ppres >> (j - 4)) & 1u))) mono = false;   // capacity was FREED: cursors are history
       }
+      }
       n_pick++;
       if (at != BS_INF) {
         stores_pending = true;
         // ---- the table summaries follow the assume step: the node's left values moved by the pod's request in every table the
         // node counts in (it is schedulable — no flag — so it is a row and has no taint error; what is left is the class's fit bit)
-        if (prm.cache_slots) {
+        if (!kLeanScored && prm.cache_slots) {
           int64_t dlt[BS_MAX_LANES];
           bool drop = false;                                 // a bound would break: negative request, or a scalar key the node's requests did not have
 #pragma unroll

@@ -1,6 +1,7 @@
 // tu_seq.hip — translation unit of the sequential pass: its kernel (bs_seq.hpp: k_seq_pass<TS>, six instantiations; k_seq_pass<TS, true>, the
-// same six under rule S, are emitted by tu_seq_nom.hip), the file-local launch wrapper and the entry points bs_seq_run and bs_seq_run_nominated (include/bsched.h) with
-// their flat forms, and bs_seq_nominated_read; see tu_fast.hip for why.  The nominated-pod table is reached through bs_ctx.hpp's declarations
+// same six under rule S, are emitted by tu_seq_nom.hip, k_seq_scored<TS>, the six under rule P, by tu_seq_score.hip), the file-local
+// launch wrapper and the entry points bs_seq_run, bs_seq_run_nominated and bs_seq_run_scored (include/bsched.h) with their flat forms,
+// bs_seq_nominated_read and bs_seq_score_read; see tu_fast.hip for why.  The nominated-pod table is reached through bs_ctx.hpp's declarations
 // (tu_nominated.hip defines them): this unit does not include bs_nominated.hpp and emits no k_nm_* kernel.
 #ifndef BS_UNITY
 #define BS_TU_FAMILY
@@ -45,8 +46,8 @@ static int seq_refusals(bs_ctx* c, uint32_t stages) {
 
 }  // namespace bs
 
-// bs_seq_run's body behind the refusals above; nc: null = no table (bs_seq_run), else rule S
-static int seq_run_impl(bs_ctx* c, uint32_t stages, bs_seq_out* out, const SeqNomCall* nc) {
+// bs_seq_run's body behind the refusals above; nc: null = no table (bs_seq_run), else rule S; score: null = first fit, else rule P
+static int seq_run_impl(bs_ctx* c, uint32_t stages, bs_seq_out* out, const SeqNomCall* nc, const bs_seq_score* score = nullptr) {
   int rc = use_device(c);
   if (rc) return rc;
   if ((rc = settle_pending(c))) return rc;
@@ -58,6 +59,7 @@ static int seq_run_impl(bs_ctx* c, uint32_t stages, bs_seq_out* out, const SeqNo
   if (G > 0x7FFFFFF0u) return BS_ERR_CAPACITY;
   c->seq_wait_valid = false;                                // the pass replaces the waiting state
   c->seq_nom_valid = false;                                 // ... and is the context's last pass
+  c->seq_score_valid = false;
   // the first-fit cursors are keyed by the resident queue's request classes: a queue patch whose insert wave ran out of class ids
   // (kHiIdOverflow of h_info, set by the device) left them unusable until the queue is re-derived — check_handover does that
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -146,9 +148,10 @@ static int seq_run_impl(bs_ctx* c, uint32_t stages, bs_seq_out* out, const SeqNo
   {
     // table summaries: as many slots as the CU's LDS holds behind the static arrays and the key window (one thread per tile: <= 1024 tiles)
     const size_t T = cdiv(N, 64), per_slot = T * ((size_t)L * 24 + 8), query = 0;
-    const size_t budget = (size_t)160 * 1024 - sizeof(SeqShared) - 2048 - (nc ? align256(sizeof(SeqNomShared)) : 0);
+    const size_t budget = (size_t)160 * 1024 - sizeof(SeqShared) - 2048 - (nc ? align256(sizeof(SeqNomShared)) : 0) - (score ? align256(sizeof(SeqScoreShared)) : 0);
     uint32_t K = 0;
     if (T && T <= (size_t)kSeqPruneTiles && budget > lds + query + per_slot) K = (uint32_t)std::min<size_t>(kSeqCacheSlots, (budget - lds - query) / per_slot);
+    if (score && c->S > (uint32_t)kSeqScoredFullLanes) K = 0;   // (the lean scored kernels keep no table summaries: bs_seq_pass.inc)
     if (const char* e = std::getenv("BS_SEQ_CACHE_SLOTS")) K = std::min<uint32_t>(K, (uint32_t)std::max(0, std::atoi(e)));   // tests: 0 = the round scan, 1 = thrash one slot
     prm.cache_slots = K;
     prm.cache_off = (uint32_t)lds;
@@ -178,9 +181,21 @@ static int seq_run_impl(bs_ctx* c, uint32_t stages, bs_seq_out* out, const SeqNo
     HIPCHK(c, hipMemcpy(o_pin.in(base), pin.data(), o_pin.bytes(), hipMemcpyHostToDevice));   // synchronous: pin is a local buffer and a later error returns at once
     HIPCHK(c, hipMemsetAsync(o_cflag.in(base), 0, o_cflag.bytes(), c->stream));
   }
+  SeqScore sco{};
+  if (score) {
+    // rule P: the weights, the two per-pod result arrays (context-owned, sized with the queue, zero where the choice is not reached)
+    HIPCHK(c, c->d_seq_score.reserve(2 * nP * sizeof(uint32_t)));
+    HIPCHK(c, hipMemsetAsync(c->d_seq_score.p, 0, 2 * nP * sizeof(uint32_t), c->stream));
+    sco.w_least = score->w_least; sco.w_most = score->w_most; sco.w_balanced = score->w_balanced;
+    sco.total = c->d_seq_score.as<uint32_t>();
+    sco.n_fit = sco.total + nP;
+    sco.lds_off = (uint32_t)lds;
+    lds += align256(sizeof(SeqScoreShared));
+  }
   const PodsDev pd = pods_dev(c);
   const NodesDev nd = nodes_dev(c);
-  if (nc) launch_seq_nominated(c->stream, c->S, lds, pd, gr, nd, sq, prm, nom);   // (tu_seq_nom.hip: the NOM instantiations)
+  if (score) launch_seq_scored(c->stream, c->S, lds, pd, gr, nd, sq, prm, sco);   // (tu_seq_score.hip: the scored instantiations)
+  else if (nc) launch_seq_nominated(c->stream, c->S, lds, pd, gr, nd, sq, prm, nom);   // (tu_seq_nom.hip: the NOM instantiations)
   else launch_seq(c->stream, c->S, lds, pd, gr, nd, sq, prm);
   LAUNCHCHK(c, BS_KERNEL_QUERY);
   // ---- results: one copy of the whole result block, then the caller's arrays
@@ -274,6 +289,7 @@ static int seq_run_impl(bs_ctx* c, uint32_t stages, bs_seq_out* out, const SeqNo
   c->seq_o_nwait = o_nwait;
   c->seq_o_node = o_node;
   c->seq_wait_valid = true;
+  if (score) { c->seq_score_p = P; c->seq_score_valid = true; }
   return BS_OK;
 }
 
@@ -304,6 +320,30 @@ int bs_seq_run_nominated(bs_ctx* c, uint32_t stages, uint32_t p, const int32_t* 
   return seq_run_impl(c, stages, out, &nc);
 }
 
+int bs_seq_run_scored(bs_ctx* c, uint32_t stages, const bs_seq_score* score, bs_seq_out* out) {
+  if (!c || !out) return BS_ERR_INVALID;
+  if (const int rc = seq_refusals(c, stages)) return rc;
+  if (!score) { c->last_error = "bs_seq_run_scored: score is NULL"; return BS_ERR_INVALID; }
+  static_assert(BS_SCORE_WEIGHT_MAX == kScoreWeightMax, "the header's bound is the one bs_seq_score.hpp's total rests on");
+  if (score->w_least > BS_SCORE_WEIGHT_MAX || score->w_most > BS_SCORE_WEIGHT_MAX || score->w_balanced > BS_SCORE_WEIGHT_MAX) {
+    c->last_error = "bs_seq_run_scored: a weight is above BS_SCORE_WEIGHT_MAX";
+    return BS_ERR_INVALID;
+  }
+  return seq_run_impl(c, stages, out, nullptr, score);
+}
+
+int bs_seq_score_read(bs_ctx* c, uint32_t p, uint32_t* total, uint32_t* n_fit) {
+  if (!c) return BS_ERR_INVALID;
+  if (!c->seq_score_valid) { c->last_error = "bs_seq_score_read: the context's last pass was not a successful bs_seq_run_scored"; return BS_ERR_STATE; }
+  if (p != c->seq_score_p) { c->last_error = "bs_seq_score_read: p is not the queue length of that pass"; return BS_ERR_INVALID; }
+  if (const int rc = use_device(c)) return rc;
+  const uint32_t* d = c->d_seq_score.as<uint32_t>();
+  const size_t nP = std::max<uint32_t>(p, 1);
+  if (p && total) HIPCHK(c, hipMemcpy(total, d, (size_t)p * 4, hipMemcpyDeviceToHost));
+  if (p && n_fit) HIPCHK(c, hipMemcpy(n_fit, d + nP, (size_t)p * 4, hipMemcpyDeviceToHost));
+  return BS_OK;
+}
+
 int bs_seq_nominated_read(bs_ctx* c, uint32_t cap, uint32_t* id, uint32_t* pod, uint32_t* node, uint32_t* n_out) {
   if (!c || !n_out) return BS_ERR_INVALID;
   if (!c->seq_nom_valid) { c->last_error = "bs_seq_nominated_read: the context's last pass was not a successful bs_seq_run_nominated"; return BS_ERR_STATE; }
@@ -326,6 +366,23 @@ int bs_seq_run_nominated_flat(bs_ctx* c, uint32_t stages, uint32_t p, const int3
   o.pf_code = pf_code; o.pf_first_k = pf_first_k; o.pf_leader = pf_leader; o.pod_node = pod_node; o.cap = cap; o.released_group = released_group;
   o.released_pods = released_pods; o.first_ns = first_ns; o.ready_ns = ready_ns;
   const int rc = bs_seq_run_nominated(c, stages, p, priority, own_id, &o);
+  if (scalars_out) {
+    scalars_out[0] = o.n_released; scalars_out[1] = o.total_ns; scalars_out[2] = (int64_t)o.node_picks; scalars_out[3] = (int64_t)o.node_scans;
+    scalars_out[4] = (int64_t)o.scan_rounds; scalars_out[5] = (int64_t)o.pick_rounds; scalars_out[6] = (int64_t)o.leader_folds;
+    scalars_out[7] = (int64_t)o.table_builds;
+  }
+  return rc;
+}
+
+int bs_seq_run_scored_flat(bs_ctx* c, uint32_t stages, uint32_t w_least, uint32_t w_most, uint32_t w_balanced, uint8_t* pf_code, uint32_t* pf_first_k,
+                           int32_t* pf_leader, int32_t* pod_node, uint32_t cap, uint32_t* released_group, uint32_t* released_pods, int64_t* first_ns,
+                           int64_t* ready_ns, int64_t* scalars_out, uint8_t* last_permitted) {
+  bs_seq_out o{};
+  o.last_permitted = last_permitted;
+  o.pf_code = pf_code; o.pf_first_k = pf_first_k; o.pf_leader = pf_leader; o.pod_node = pod_node; o.cap = cap; o.released_group = released_group;
+  o.released_pods = released_pods; o.first_ns = first_ns; o.ready_ns = ready_ns;
+  const bs_seq_score score{w_least, w_most, w_balanced};
+  const int rc = bs_seq_run_scored(c, stages, &score, &o);
   if (scalars_out) {
     scalars_out[0] = o.n_released; scalars_out[1] = o.total_ns; scalars_out[2] = (int64_t)o.node_picks; scalars_out[3] = (int64_t)o.node_scans;
     scalars_out[4] = (int64_t)o.scan_rounds; scalars_out[5] = (int64_t)o.pick_rounds; scalars_out[6] = (int64_t)o.leader_folds;

@@ -1121,6 +1121,50 @@ int bs_nominated_nodes_apply(bs_ctx* ctx, uint32_t count, const uint32_t* kind, 
 int bs_seq_run_nominated(bs_ctx* ctx, uint32_t stages, uint32_t p, const int32_t* priority /*[p]*/, const uint32_t* own_id /*[p] or NULL*/,
                          bs_seq_out* out);
 int bs_seq_nominated_read(bs_ctx* ctx, uint32_t cap, uint32_t* id, uint32_t* pod, uint32_t* node, uint32_t* n_out);
+
+/* ---- the sequential pass with a scored node choice: bs_seq_run_scored ---------------------------------------------------------------
+ * bs_seq_run's FIRST FIT is a placeholder no cluster runs: the reference's Score is a constant (core.go:262-265), so upstream's default
+ * priorities decide the node — LeastRequested + BalancedResourceAllocation, or MostRequested where pods are packed.  The placement feeds
+ * back into the plugin (the per-node left values PreFilter sums, core.go:595-632), into which gang reaches its quorum first and into which
+ * nodes a preemption later has to empty.  bs_seq_run_scored is bs_seq_run with ONE step replaced.
+ *   For pod i let C be the set of nodes bs_seq_run's node rule accepts — no BS_NODE_* flag, the checkFit bit of the pod's class set, the
+ *   plugin's Filter passes when BS_STAGE_FILTER is on (Filter only narrows C), holds().  bs_seq_run takes the first member of C; the scored
+ *   pass takes the member with the largest `total` (rule P), ties to the LOWEST node index.  The tie rule is a library rule: upstream's
+ *   selectHost draws at random among the maxima, as its preemption node pick does.  If C is empty the pod gets no node, exactly as now.
+ *   D7. (rule P; recalled upstream, v1.17.5, not vendored.)  Only the cpu lane (0) and the memory lane (1) score.  For node k and lane j:
+ *       A = allocatable[j][k]; R = requested[j][k] + request_i[j], requested as the earlier pods of this pass left it, the sum wrapping in
+ *       int64.  The lane is IN DOMAIN iff 0 < A < 2^53 and 0 <= R <= A.
+ *           least_j = ((A - R) * 100) / A   (int64, truncating)      out of domain: 0
+ *           most_j  = (R * 100) / A                                   out of domain: 0
+ *           frac_j  = (double)R / (double)A                           out of domain: 1.0
+ *       least = (least_0 + least_1) / 2.  most = (most_0 + most_1) / 2.  balanced = 0 when frac_0 >= 1.0 || frac_1 >= 1.0, otherwise
+ *       balanced = (int64)((1.0 - fabs(frac_0 - frac_1)) * 100.0), truncated toward zero.  The double arithmetic is IEEE-754 binary64, round
+ *       to nearest, every operation rounded on its own (no fused multiply-add).
+ *       total = w_least * least + w_most * most + w_balanced * balanced; each weight is at most BS_SCORE_WEIGHT_MAX, so total < 2^32.
+ *       Why the domain: upstream returns 0 for capacity == 0 and for requested > capacity; 2^53 makes both conversions to double exact and
+ *       keeps (A - R) * 100 inside int64.  Negative, wrapped and huge values therefore score 0.  Such a node is still a candidate if it holds
+ *       the pod; it then competes on its index alone.
+ *       Library rule P1: the lanes are the context's real `requested`, not upstream's NonZeroRequest — no 100 mCPU / 200 MB default is put
+ *       in the place of a zero request.  A caller who wants the defaults puts them into the requests it loads.
+ *       Library rule P2: with all three weights 0 every candidate ties at 0 and the lowest index wins: the pass is then bs_seq_run, bit for
+ *       bit, in every result array, in the released gangs and in all resident state (the work counters of bs_seq_out count a full search).
+ *   Everything except the choice is untouched: PreFilter, Filter's TTL writes under BS_BATCH_FILTER_DENY, assume, Permit, release, PostBind
+ *   and the state the context is left in.  `stages` takes the three forms bs_seq_run takes.
+ *   bs_seq_score_read   reports on the context's last successful scored pass: total[i] is the chosen node's total, 0 where pod i got no node
+ *       or never reached the node choice (a PreFilter rejection, a missing group); n_fit[i] is |C|, 0 where the choice was not reached.
+ *       Either pointer may be NULL.  p must be that pass's queue length.
+ *   after the call  the context is in the state bs_seq_run leaves: bs_seq_expire, bs_seq_waiting_read, bs_wait_park and bs_bound_bind work as
+ *       after bs_seq_run.  bs_seq_nominated_read answers BS_ERR_STATE, as after any pass that is not its own.
+ *   errors      all found on the host before any launch; nothing resident changes.  Everything bs_seq_run refuses, with the same code.
+ *       BS_ERR_INVALID: a NULL score, a weight above BS_SCORE_WEIGHT_MAX.  bs_seq_score_read: BS_ERR_STATE when the last successful pass was
+ *       not bs_seq_run_scored, BS_ERR_INVALID when p differs from that pass's.
+ *   Out of scope: the scored choice together with the nominated-pod table (a pass under rules S and P at once: six more instantiations of
+ *   the persistent kernel and a product of two rule sets — a step of its own once this one is measured); scoring in bs_batch_run (the
+ *   frozen-snapshot pre-screen chooses no node); upstream priorities that read labels, images or other pods (no resource arithmetic). */
+#define BS_SCORE_WEIGHT_MAX 65536u
+typedef struct bs_seq_score { uint32_t w_least, w_most, w_balanced; } bs_seq_score;
+int bs_seq_run_scored(bs_ctx* ctx, uint32_t stages, const bs_seq_score* score, bs_seq_out* out);
+int bs_seq_score_read(bs_ctx* ctx, uint32_t p, uint32_t* total /*[p]*/, uint32_t* n_fit /*[p]*/);
 /* The live bound table in table order: node ascending, importance order within a node; bs_bound_count entries.  id_out[i] = the
  * entry's id (its index at the last bs_bound_load), node_out[i] = its node.  BS_ERR_STATE before bs_bound_load; the arrays may be NULL
  * when the table is empty. */
@@ -1402,6 +1446,10 @@ int bs_seq_run_flat(bs_ctx* ctx, uint32_t stages, uint8_t* pf_code, uint32_t* pf
 int bs_seq_run_nominated_flat(bs_ctx* ctx, uint32_t stages, uint32_t p, const int32_t* priority, const uint32_t* own_id, uint8_t* pf_code,
                               uint32_t* pf_first_k, int32_t* pf_leader, int32_t* pod_node, uint32_t cap, uint32_t* released_group,
                               uint32_t* released_pods, int64_t* first_ns, int64_t* ready_ns, int64_t* scalars_out, uint8_t* last_permitted);
+/* bs_seq_run_scored: bs_seq_run_flat's result arguments behind the three weights of bs_seq_score */
+int bs_seq_run_scored_flat(bs_ctx* ctx, uint32_t stages, uint32_t w_least, uint32_t w_most, uint32_t w_balanced, uint8_t* pf_code,
+                           uint32_t* pf_first_k, int32_t* pf_leader, int32_t* pod_node, uint32_t cap, uint32_t* released_group,
+                           uint32_t* released_pods, int64_t* first_ns, int64_t* ready_ns, int64_t* scalars_out, uint8_t* last_permitted);
 /* bs_fit_build: node tables, then the template tables; `ex_*` = bs_fit_templates.exprs, `fd_*` = bs_fit_templates.fields */
 int bs_fit_build_flat(bs_ctx* ctx, uint32_t n, const uint32_t* name, const uint32_t* label_off, const uint32_t* label_key, const uint32_t* label_val,
                       const int64_t* label_int, const uint8_t* label_int_ok, const uint32_t* taint_off, const uint32_t* taint_key,

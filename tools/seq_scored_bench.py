@@ -1,0 +1,57 @@
+"""bs_seq_run_scored timed beside bs_seq_run on a synthetic configuration, one context, one process: bs_seq_run, bs_seq_run_scored with the
+weights (0, 0, 0) — the same placements through the full search — and with (1, 0, 1), least requested + balanced.  Every repetition
+reloads nodes, groups and pods, so every pass starts from the same state; one untimed pass of each form first, so that no figure contains
+a code-object load.  The figure is the kernel's own clock (bs_seq_out.total_ns), median and best of `--reps` timed passes (default 7),
+with each form's spread (max - min) so that a ratio can be read against the noise of the same run.  Prints one JSON line.
+Usage: python tools/seq_scored_bench.py [config] [scenario] [--reps N]"""
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+bsa = importlib.import_module("batch-scheduler_amd")
+soa = bsa.soa
+
+
+def opt(name, default):
+    return int(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+
+
+def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--") and not a.isdigit()]
+    config = args[0] if args else "cfg3"
+    scenario = args[1] if len(args) > 1 else "tail"
+    reps = opt("--reps", 7)
+    nodes, fit, groups, pods, _ = bsa.synth.make(config, scenario)
+    pods = pods.take(np.argsort(pods.group, kind="stable"))           # Compare order
+    out = {"config": f"{config}/{scenario}", "pods": int(pods.p), "nodes": int(nodes.n), "groups": int(groups.g), "reps": reps, "forms": {}}
+    with bsa.Context(scalar_lanes=nodes.lanes - 4) as ctx:
+        forms = (("seq_run", None), ("scored_0_0_0", (0, 0, 0)), ("scored_1_0_1", (1, 0, 1)))
+        for name, weights in forms:
+            dev, r = [], None
+            for rep in range(reps + 1):                                # (the first one is the warm-up)
+                ctx.load_nodes(nodes, fit)
+                ctx.load_groups(groups)
+                ctx.load_pods(pods)
+                r = ctx.seq_run(soa.STAGE_PREFILTER) if weights is None else ctx.seq_run_scored(weights)
+                if rep:
+                    dev.append(r["total_ns"])
+            wait = ctx.seq_waiting_read()
+            used = np.unique(np.concatenate([r["pod_node"][r["pod_node"] >= 0], wait[wait >= 0]]))
+            out["forms"][name] = {"kernel_ms_median": float(np.median(dev)) / 1e6, "kernel_ms_best": min(dev) / 1e6, "kernel_ms_spread": (max(dev) - min(dev)) / 1e6,
+                                  "pods_released": int((r["pod_node"] >= 0).sum()), "pods_waiting": int((wait >= 0).sum()), "nodes_used": int(used.size),
+                                  "node_picks": r["node_picks"], "node_scans": r["node_scans"]}
+            if weights is not None:
+                s = ctx.seq_score_read()
+                out["forms"][name]["n_fit_mean"] = float(s["n_fit"][s["n_fit"] > 0].mean()) if (s["n_fit"] > 0).any() else 0.0
+        base = out["forms"]["seq_run"]["kernel_ms_median"]
+        out["ratio_to_seq_run_kernel_median"] = {k: v["kernel_ms_median"] / base for k, v in out["forms"].items()}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
