@@ -4,7 +4,8 @@ The single-feature tests pin each entry point; this module pins what crosses the
 count and window guards, the scratch blocks that are "zero between calls" and whose layouts follow N, G and the id spaces, the
 pointer-swapped twins of the group pack, the bound table and the wait table, the lazily re-derived queue state.  After EVERY call the
 cheap reads (groups, queue, node requests, findMaxPG, the wait table, the bound table with its PDB column, the resident PDBs, the
-pass's waiting pods while the window is open, bs_preempt_gang_read) must equal the model bit for bit, every call's own results are
+pass's waiting pods while the window is open, bs_preempt_gang_read, the nominated-pod table with its count and id space, the reports of
+the last pass and of the last preemption call) must equal the model bit for bit, every call's own results are
 compared field for field with the reference of that call, a predicted refusal must give the status the header names and change
 nothing, and every 8th step a context loaded afresh from the model's arrays (ids mapped by table order) must answer bs_preempt_run and,
 while no leader is carried, a batch with every stage exactly as the context under test does."""
@@ -18,6 +19,8 @@ from test_gpu_parity import assert_batch_equal
 
 pytestmark = pytest.mark.gpu
 BOUND_COLUMNS = ("priority", "start_ns", "group", "req", "req_present", "pdb")
+NOM_COLUMNS = ("id", "node", "priority", "req", "req_present")
+SEQ_FIELDS = ("pf_code", "pf_first_k", "pf_leader", "pod_node", "released_group", "released_pods", "n_released")
 
 
 def status_of(bsa, fn):
@@ -95,6 +98,42 @@ class Runner:
             assert np.array_equal(v, voided) and np.array_equal(p, placed), f"{where}: bs_preempt_gang_read"
             if w.g != g:
                 assert status_of(bsa, lambda: self.gang_read(q, w.g)) == wf.INVALID, f"{where}: bs_preempt_gang_read with the new g"
+        # the nominated-pod table: count and id space from the first load on, the columns while its node count is the list's
+        if r["nom_count"] is None:
+            assert status_of(bsa, ctx.nominated_count) == wf.STATE and status_of(bsa, ctx.nominated_ids) == wf.STATE, f"{where}: bs_nominated_count before a load"
+        else:
+            assert (ctx.nominated_count(), ctx.nominated_ids()) == (r["nom_count"], r["nom_ids"]), f"{where}: nominated count, ids"
+            if r["nom"] is None:
+                assert status_of(bsa, ctx.nominated_read) == wf.STATE, f"{where}: bs_nominated_read with a stale node count"
+            else:
+                t = ctx.nominated_read()
+                for name in NOM_COLUMNS:
+                    assert np.array_equal(t[name], r["nom"][name]), f"{where}: nominated table: {name}"
+        # the reports of the last pass ...
+        if r["seq_nominated"] is None:
+            assert status_of(bsa, ctx.seq_nominated_read) == wf.STATE, f"{where}: bs_seq_nominated_read after a pass that is not its own"
+        else:
+            c = ctx.seq_nominated_read()
+            for name in ("n", "id", "pod", "node"):
+                assert np.array_equal(c[name], r["seq_nominated"][name]), f"{where}: bs_seq_nominated_read: {name}"
+        if r["seq_score"] is None:
+            assert status_of(bsa, ctx.seq_score_read) == wf.STATE, f"{where}: bs_seq_score_read after a pass that is not its own"
+        else:
+            sc = ctx.seq_score_read(p=r["seq_score"]["p"])                       # (readable with that pass's p while it is the last pass)
+            assert np.array_equal(sc["total"], r["seq_score"]["total"]) and np.array_equal(sc["n_fit"], r["seq_score"]["n_fit"]), f"{where}: bs_seq_score_read"
+            if w.pods.p != r["seq_score"]["p"]:
+                assert status_of(bsa, ctx.seq_score_read) == wf.INVALID, f"{where}: bs_seq_score_read with the new queue length"
+        # ... and of the last successful preemption call
+        if r["pre_nominated"] is None:
+            assert status_of(bsa, lambda: ctx.preempt_nominated_read(1)) == wf.STATE, f"{where}: bs_preempt_nominated_read after a call without the flag"
+        else:
+            assert np.array_equal(ctx.preempt_nominated_read(len(r["pre_nominated"])), r["pre_nominated"]), f"{where}: bs_preempt_nominated_read"
+        if r["pre_cleared"] is None:
+            assert status_of(bsa, ctx.preempt_cleared_read) == wf.STATE, f"{where}: bs_preempt_cleared_read after a call without the flag"
+        else:
+            c = ctx.preempt_cleared_read()
+            for name in ("id", "node", "priority", "by"):
+                assert np.array_equal(c[name], r["pre_cleared"][name]), f"{where}: bs_preempt_cleared_read: {name}"
 
     def gang_read(self, q, g):
         import ctypes as C
@@ -130,6 +169,17 @@ class Runner:
             return ctx.read(bitmap=False, rows=False)
         if kind == "pass":
             return ctx.seq_run(soa.STAGE_PREFILTER)
+        if kind == "pass_nom":
+            return ctx.seq_run_nominated(a["priority"], a["own_id"], stages=soa.STAGE_PREFILTER | (soa.STAGE_FILTER if a.get("filter") else 0), flat=flat)
+        if kind == "pass_scored":
+            return ctx.seq_run_scored(a["weights"], flat=flat)
+        if kind == "nom_load":
+            return ctx.nominated_load(a["node"], a["priority"], a["req"], a["req_present"])
+        if kind == "nom_apply":
+            return dict(first_id=ctx.nominated_apply(a["remove"], a["pod_index"], a["node"], a["priority"]))
+        if kind == "nom_nodes":
+            ids, nodes, prio, n = ctx.nominated_nodes_apply(exp["kind"], exp["index"])
+            return dict(n=n, id=ids, node=nodes, priority=prio)
         if kind == "list":
             return ctx.groups_list_apply(a["remove"], a["update"], a["rows"], a["n_append"], flat=flat)
         if kind == "nodes":
@@ -173,18 +223,27 @@ class Runner:
         if kind == "preempt":
             return dict(res=ctx.preempt(a["pod_index"], a["priority"], a["protected"], victim_cap=wf.CAP))
         if kind == "commit":
-            return dict(res=ctx.preempt_commit(a["pod_index"], a["priority"], a["protected"], victim_cap=wf.CAP, apply=a["apply"], assume=a["assume"]))
+            return dict(res=ctx.preempt_commit(a["pod_index"], a["priority"], a["protected"], victim_cap=wf.CAP, apply=a["apply"], assume=a["assume"],
+                                               nominate=a.get("nominate", False), clear_lower=a.get("clear_lower", False)))
         if kind == "commit_gang":
             return dict(res=ctx.preempt_commit_gang(a["pod_index"], a["priority"], a["protected"], gang_need=a["need"], victim_cap=wf.CAP, apply=a["apply"],
-                                                    assume=a["assume"], flat=flat))
+                                                    assume=a["assume"], flat=flat, nominate=a.get("nominate", False), clear_lower=a.get("clear_lower", False)))
         raise KeyError(kind)
 
     def compare(self, kind, got, exp, where):
         same = lambda names, g=None, e=None: [self._eq((got if g is None else g)[f], (exp if e is None else e)[f], f"{where}: {f}") for f in names]
         if kind == "batch":
             assert_batch_equal(got, exp["batch"], where, bitmap=False)
-        elif kind == "pass":
-            same(("pf_code", "pf_first_k", "pf_leader", "pod_node", "released_group", "released_pods", "n_released"), e=exp["seq"])
+        elif kind in ("pass", "pass_nom", "pass_scored"):
+            same(SEQ_FIELDS, e=exp["seq"])
+            if kind == "pass_nom":
+                same(("n", "id", "pod", "node"), g=self.ctx.seq_nominated_read(), e=exp["consumed"])
+            if kind == "pass_scored":
+                same(("total", "n_fit"), g=self.ctx.seq_score_read())
+        elif kind == "nom_apply":
+            same(("first_id",))
+        elif kind == "nom_nodes":
+            same(("n", "id", "node", "priority"))
         elif kind == "list":
             same(("g_new", "n_pods_missing", "n_bound_missing", "n_wait_dropped", "wait_id", "wait_node", "wait_group"))
         elif kind == "park":
@@ -209,6 +268,10 @@ class Runner:
             same(pp.FIELDS, g=got["res"], e=exp["res"])
             if kind == "commit_gang":
                 same(("slot_voided", "group_placed"), g=got["res"])
+            if "nominated_id" in exp:
+                same(("nominated_id",), g=got["res"])
+            if "cleared" in exp:
+                same(("id", "node", "priority", "by"), g=got["res"]["cleared"], e=exp["cleared"])
 
     @staticmethod
     def _eq(a, b, what):
@@ -218,7 +281,7 @@ class Runner:
     def against_fresh(self):
         """bs_preempt_run and, while no leader is carried, a batch with every stage: this context and one loaded afresh"""
         w, soa, where = self.w, self.soa, f"{self.where()}: against a context loaded afresh"
-        if w.pend_w or w.pend_b:
+        if w.pend_w or w.pend_b or w.pend_n:
             return
         f = w.fresh_arrays()
         with self.bsa.Context(scalar_lanes=w.S) as b:
@@ -232,6 +295,13 @@ class Runner:
                 assert np.array_equal(f["wait_keep"][tb["id"]] if tb["id"].size else tb["id"], t["id"]), f"{where}: wait ids through the map"
                 for name in ("node", "group", "req", "req_present"):
                     assert np.array_equal(tb[name], t[name]), f"{where}: wait table: {name}"
+            if f["nom"] is not None:                                # (before the preemption call below: rule N on both sides)
+                t = f["nom"]
+                b.nominated_load(t["node"], t["priority"], t["req"], t["req_present"])
+                tb = b.nominated_read()
+                assert np.array_equal(f["nom_keep"][tb["id"]] if tb["id"].size else tb["id"], t["id"]), f"{where}: nominated ids through the map"
+                for name in NOM_COLUMNS[1:]:
+                    assert np.array_equal(tb[name], t[name]), f"{where}: nominated table: {name}"
             if f["bound"] is not None:
                 keep = f["bound_keep"]
                 b.load_bound(f["bound"])
@@ -248,7 +318,7 @@ class Runner:
                     ra, rb = self.ctx.preempt(q, prio, prot, victim_cap=wf.CAP), wf.map_victims(b.preempt(q, prio, prot, victim_cap=wf.CAP), keep)
                     for name in pp.FIELDS:
                         assert np.array_equal(ra[name], rb[name]), f"{where}: bs_preempt_run: {name}"
-                    w.gang = None                               # (the context's last preemption call is this one now)
+                    w.gang = w.pre_nom = w.pre_clr = None      # (the context's last preemption call is this one now)
             if w.leader < 0 and w.pods.p:
                 ra, rb = self.ctx.batch(soa.STAGE_ALL, bitmap=True), b.batch(soa.STAGE_ALL, bitmap=True)
                 assert_batch_equal(ra, rb, f"{where}: batch", bitmap=False)
