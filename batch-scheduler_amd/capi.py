@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "bs_preempt_cleared_read",
     "bs_seq_run_nominated", "bs_seq_run_nominated_flat", "bs_seq_nominated_read",
     "bs_seq_run_scored", "bs_seq_run_scored_flat", "bs_seq_score_read",
+    "bs_seq_run_scored_nominated", "bs_seq_run_scored_nominated_flat",
 ]
 
 SEQ_EXPIRE_DENY, SEQ_EXPIRE_ALL = 1, 2    # bs_seq_expire flags
@@ -291,6 +292,9 @@ def load_library(path: str | None = None):
     L.bs_seq_run_scored_flat.argtypes = [vp, u32, u32, u32, u32, P(u8), P(u32), P(i32), P(i32), u32, P(u32), P(u32), P(C.c_int64), P(C.c_int64),
                                          P(C.c_int64), P(u8)]
     L.bs_seq_score_read.argtypes = [vp, u32, P(u32), P(u32)]
+    L.bs_seq_run_scored_nominated.argtypes = [vp, u32, u32, P(i32), P(u32), P(SeqScore), P(SeqOut)]
+    L.bs_seq_run_scored_nominated_flat.argtypes = [vp, u32, u32, P(i32), P(u32), u32, u32, u32, P(u8), P(u32), P(i32), P(i32), u32, P(u32), P(u32), P(C.c_int64),
+                                                   P(C.c_int64), P(C.c_int64), P(u8)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:
@@ -652,7 +656,8 @@ class Context:
 
     def _seq_pass(self, stages: int, cap, nominated, flat: bool, weights=None) -> dict:
         """the result arrays of a sequential pass and the call: bs_seq_run (nominated None), else bs_seq_run_nominated with
-        nominated = (p, priority, own_id), through its flat form when flat; weights = (w_least, w_most, w_balanced): bs_seq_run_scored"""
+        nominated = (p, priority, own_id), through its flat form when flat; weights = (w_least, w_most, w_balanced): bs_seq_run_scored; both:
+        bs_seq_run_scored_nominated"""
         p, cap = self.pods_count(), max(self.g if cap is None else cap, 1)
         n = max(p, 1)
         pf, fk = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
@@ -662,7 +667,17 @@ class Context:
         lp = np.zeros(n, np.uint8)
         o = SeqOut(pf.ctypes.data_as(C.POINTER(C.c_uint8)), _u32p(fk), ld.ctypes.data_as(C.POINTER(C.c_int32)), node.ctypes.data_as(C.POINTER(C.c_int32)),
                    cap, _u32p(rg), _u32p(rp), _i64p(t0), _i64p(t1), 0, 0, 0, 0, 0, 0, 0, 0, lp.ctypes.data_as(C.POINTER(C.c_uint8)))
-        if weights is not None and flat:
+        if weights is not None and nominated is not None and flat:
+            sc = np.zeros(8, np.int64)
+            self._chk(self._lib.bs_seq_run_scored_nominated_flat(self._h, stages, *nominated, *weights, o.pf_code, o.pf_first_k, o.pf_leader, o.pod_node, cap,
+                                                                 o.released_group, o.released_pods, o.first_ns, o.ready_ns, _i64p(sc), o.last_permitted),
+                      "bs_seq_run_scored_nominated_flat")
+            (o.n_released, o.total_ns, o.node_picks, o.node_scans, o.scan_rounds, o.pick_rounds, o.leader_folds, o.table_builds) = (int(v) for v in sc)
+        elif weights is not None and nominated is not None:
+            w = None if weights == "null" else SeqScore(*weights)
+            self._chk(self._lib.bs_seq_run_scored_nominated(self._h, stages, *nominated, None if w is None else C.byref(w), C.byref(o)),
+                      "bs_seq_run_scored_nominated")
+        elif weights is not None and flat:
             sc = np.zeros(8, np.int64)
             self._chk(self._lib.bs_seq_run_scored_flat(self._h, stages, *weights, o.pf_code, o.pf_first_k, o.pf_leader, o.pod_node, cap, o.released_group,
                                                        o.released_pods, o.first_ns, o.ready_ns, _i64p(sc), o.last_permitted), "bs_seq_run_scored_flat")
@@ -697,6 +712,21 @@ class Context:
         pp = None if pr is None else (pr if pr.size else np.zeros(1, np.int32)).ctypes.data_as(C.POINTER(C.c_int32))
         op = None if ow is None else _u32p(ow if ow.size else np.zeros(1, np.uint32))
         return self._seq_pass(stages, cap, (n, pp, op), flat)
+
+    def seq_run_scored_nominated(self, weights, priority, own_id=None, stages: int = soa.STAGE_PREFILTER, cap: int | None = None, p: int | None = None,
+                                 flat: bool = False) -> dict:
+        """bs_seq_run_scored_nominated: seq_run_scored with rule S in its candidate set and the consume behind its choice (rule SP).  The
+        nominated-pod table narrows the candidates and never moves a score; weights as in seq_run_scored (None: a NULL score, tests of
+        the refusals), priority / own_id / p as in seq_run_nominated.  seq_score_read and seq_nominated_read both answer for this pass."""
+        pr = None if priority is None else np.ascontiguousarray(np.asarray(priority, np.int32).reshape(-1))
+        ow = None if own_id is None else np.ascontiguousarray(np.asarray(own_id, np.uint32).reshape(-1))
+        n = self.pods_count() if p is None else int(p)
+        assert p is not None or ((pr is None or pr.size == n) and (ow is None or ow.size == n))
+        pp = None if pr is None else (pr if pr.size else np.zeros(1, np.int32)).ctypes.data_as(C.POINTER(C.c_int32))
+        op = None if ow is None else _u32p(ow if ow.size else np.zeros(1, np.uint32))
+        assert not (weights is None and flat), "the flat form has no NULL score"
+        w = "null" if weights is None else tuple(int(v) for v in weights)
+        return self._seq_pass(stages, cap, (n, pp, op), flat, w)
 
     def seq_nominated_read(self, cap: int | None = None) -> dict:
         """bs_seq_nominated_read: the rows the last seq_run_nominated consumed, ascending id: n (the true count), id, pod (queue index), node

@@ -174,6 +174,16 @@ __device__ __forceinline__ void seq_nominees(const NomView& nm, const uint8_t* c
   }
 }
 
+// ... and the same sum for ONE lane j (the lean scored search under rule SP: a walk per lane the pod asks for, nothing kept)
+__device__ __forceinline__ int64_t seq_nominees_lane(const NomView& nm, const uint8_t* consumed, uint32_t head, int32_t P, uint32_t own, uint32_t j) {
+  int64_t add = 0;
+  for (uint32_t r = head; r != kNmNone; r = nm.nnext[r]) {
+    if (nm.nprio[r] < P || r == own || __hip_atomic_load(&consumed[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) continue;
+    add = wadd(add, nm.nreq[(size_t)j * nm.nstride + r]);
+  }
+  return add;
+}
+
 // ---- wave-uniform loads of state this kernel itself writes: vector loads, value moved to SGPRs ---------------------
 __device__ __forceinline__ uint32_t seq_raw32(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ uint32_t seq_raw8(const uint8_t* p) { return (uint32_t)__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -904,10 +914,14 @@ __device__ __forceinline__ uint32_t seq_pick(const NodesDev& nd, const SeqDev& s
 // own registers.  Returns the node (BS_INF none), wave-uniform, identical in every wave; total_out / nfit_out likewise.
 // The assume step is seq_pick's, restated on the kept values (a shared function would change seq_pick's instructions).
 // ---------------------------------------------------------------------------------------------------------------------
-template <int TS>
+// Under NOM (rule SP; bs_seq_run_scored_nominated) the fit test is rule S's: a node with a row chain adds the live rows the pod sees to its
+// requests, exactly as seq_pick<TS, true> does, and nothing else moves — the key and score_total are fed the RAW al / rq (D8: no row enters
+// a score).  The lean form does not keep the row sums: it walks the chain once per lane the pod asks for, tests, and discards.
+template <int TS, bool NOM = false>
 __device__ __forceinline__ uint32_t seq_pick_scored(const NodesDev& nd, const SeqDev& sq, const SeqParams& prm, SeqShared& sh_, SeqScoreShared& ss, const SeqPick& q,
                                                     const SeqScore& sco, const uint32_t (&slot_key)[kSeqCacheSlots], bool drained, SeqAssumed& out,
-                                                    unsigned long long& tiles_looked, uint32_t& total_out, uint32_t& nfit_out, uint32_t pw) {
+                                                    unsigned long long& tiles_looked, uint32_t& total_out, uint32_t& nfit_out, uint32_t pw,
+                                                    const SeqPickNom& pn = SeqPickNom{}) {
   const Shape<TS> sh(prm.S);
   const uint32_t L = sh.L(), S = sh.S();
   // The instantiations for more than kSeqScoredFullLanes scalar lanes are built LEAN, so that they need no scratch memory: such a search
@@ -986,6 +1000,49 @@ __device__ __forceinline__ uint32_t seq_pick_scored(const NodesDev& nd, const Se
         }
         ok = ok && (c2 || !c3h);                                                                     // case 2 | case 3
       }
+      bool plain = true;                                     // the node has no row chain: the flag-less fit test
+      if constexpr (NOM) {
+        const uint32_t head = (valid && pn.nom->view) ? pn.nom->view->nhead[nn] : kNmNone;
+        if (head != kNmNone) {                               // rule S: requests plus the live rows the pod sees (a LOCAL sum; the score below stays raw)
+          plain = false;
+          const NomView nm = *pn.nom->view;
+          if constexpr (!kLean) {
+            int64_t add[BS_MAX_LANES];
+#pragma unroll
+            for (uint32_t j = 0; j < BS_MAX_LANES; ++j) add[j] = 0;
+            seq_nominees<TS>(nm, pn.nom->consumed, head, pn.prio, pn.own, sh, add);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) ok = ok && !(q.preq[j] > 0 && q.preq[j] > wsub(al[j], wadd(rq[j], add[j])));
+            ok = ok && !(wadd(wadd(rq[3], add[3]), 1) > al[3]);
+#pragma unroll
+            for (uint32_t s = 0; s < BS_MAX_SCALARS; ++s) {
+              if (s < S && ((q.ppres >> s) & 1u) && q.preq[4 + s] > 0) {
+                const int64_t r0 = wadd(((rp >> s) & 1u) ? rq[4 + s] : 0, add[4 + s]);
+                ok = ok && ((ap >> s) & 1u) && !(q.preq[4 + s] > wsub(al[4 + s], r0));
+              }
+            }
+          } else {
+            // one walk of the chain per lane the pod asks for (the pods lane always): chains are short and rows are rare
+#pragma unroll
+            for (uint32_t j = 0; j < BS_MAX_LANES; ++j) {
+              if (j < L) {
+                const int64_t pr = j < 4 ? q.preq[j] : preq_s(j);
+                const bool asks = j == 3 || (pr > 0 && (j < 3 || ((q.ppres >> (j - 4)) & 1u)));
+                if (asks) {
+                  const int64_t add = seq_nominees_lane(nm, pn.nom->consumed, head, pn.prio, pn.own, j);
+                  if (j < 3) ok = ok && !(pr > wsub(al[j], wadd(rq[j], add)));
+                  else if (j == 3) ok = ok && !(wadd(wadd(rq[3], add), 1) > al[3]);
+                  else {
+                    const int64_t r0 = wadd(((rp >> (j - 4)) & 1u) ? rq[j] : 0, add);
+                    ok = ok && ((ap >> (j - 4)) & 1u) && !(pr > wsub(al[j], r0));
+                  }
+                }
+              }
+            }
+          }
+        }
+      }
+      if (plain) {
 #pragma unroll
       for (int j = 0; j < 3; ++j) ok = ok && !(q.preq[j] > 0 && q.preq[j] > wsub(al[j], rq[j]));
       ok = ok && !(wadd(rq[3], 1) > al[3]);
@@ -995,6 +1052,7 @@ __device__ __forceinline__ uint32_t seq_pick_scored(const NodesDev& nd, const Se
           const int64_t r0 = ((rp >> s) & 1u) ? rq[4 + s] : 0;
           ok = ok && ((ap >> s) & 1u) && !(preq_s(4 + s) > wsub(al[4 + s], r0));
         }
+      }
       }
       if (ok) {                                              // rule P: R = requested + request (wrapping), cpu and memory only
         const uint32_t total = score_total(al[0], score_wadd(rq[0], q.preq[0]), al[1], score_wadd(rq[1], q.preq[1]), sco.w_least, sco.w_most, sco.w_balanced);
@@ -1014,7 +1072,11 @@ __device__ __forceinline__ uint32_t seq_pick_scored(const NodesDev& nd, const Se
         const long long m0 = readlane63_i64(wave_max_i64_lane63(sched ? (long long)f0 : INT64_MIN));
         const long long m1 = readlane63_i64(wave_max_i64_lane63(sched ? (long long)f1 : INT64_MIN));
         const long long m2 = readlane63_i64(wave_max_i64_lane63(sched ? seq_joint(f0, f1) : INT64_MIN));
+        if constexpr (NOM) {                                 // (not a wild tile's: its bounds stay open, see the prologue of the pass)
+          if (lane == 0 && !((pn.ns->wild[tile >> 5] >> (tile & 31u)) & 1u)) { sh_.pmax[0][tile] = m0; sh_.pmax[1][tile] = m1; sh_.pmax[2][tile] = m2; atomicOr(&sh_.tight[tile >> 5], 1u << (tile & 31u)); }
+        } else {
         if (lane == 0) { sh_.pmax[0][tile] = m0; sh_.pmax[1][tile] = m1; sh_.pmax[2][tile] = m2; atomicOr(&sh_.tight[tile >> 5], 1u << (tile & 31u)); }
+        }
       }
     }
   }
@@ -1215,7 +1277,7 @@ __device__ __forceinline__ void seq_group_zero(SeqGroup& o, Shape<TS> sh) {
   res_zero(o.mr, sh);
 }
 
-// The pass: its body is bs_seq_pass.inc, included by all three kernel templates.  NOM = false is bs_seq_run's kernel: six instantiations (bs_lanes.hpp,
+// The pass: its body is bs_seq_pass.inc, included by all four kernel templates.  NOM = false is bs_seq_run's kernel: six instantiations (bs_lanes.hpp,
 // lanes_narrow), name and arguments as they always were.
 template <int TS>
 __global__ __launch_bounds__(kSeqBlock, 1) void k_seq_pass(PodsDev pods, GroupsDev gr, NodesDev nd, SeqDev sq, SeqParams prm) {
@@ -1245,6 +1307,18 @@ __global__ __launch_bounds__(kSeqBlock, 1) void k_seq_scored(PodsDev pods, Group
   const SeqNom nom{};
 #include "bs_seq_pass.inc"
 }
+// bs_seq_run_scored_nominated's: the fourth inclusion, rules S and P at once (rule SP: NOM = true, SCORE = true); emitted by
+// tu_seq_score_nom.hip.  A name of its own (the kernel lists that count k_seq_scored and k_seq_pass by name stay what they were); the same
+// thirteen lane counts as k_seq_scored, lean above kSeqScoredFullLanes, and no generic-lane one for the reason given above.
+template <int TS>
+__global__ __launch_bounds__(kSeqBlock, 1) void k_seq_sp(PodsDev pods, GroupsDev gr, NodesDev nd, SeqDev sq, SeqParams prm, SeqNom nom, SeqScore sco) {
+  static_assert(TS >= 0, "the scored pass has fixed-lane instantiations only");
+  constexpr bool NOM = true, SCORE = true;
+#include "bs_seq_pass.inc"
+}
+// the launch of k_seq_sp<TS> for S scalar lanes (defined in tu_seq_score_nom.hip; called by tu_seq.hip)
+void launch_seq_scored_nominated(hipStream_t stream, uint32_t S, size_t lds, const PodsDev& pd, const GroupsDev& gr, const NodesDev& nd, const SeqDev& sq,
+                                 const SeqParams& prm, const SeqNom& nom, const SeqScore& sco);
 // the launch of k_seq_scored<TS> for S scalar lanes (defined in tu_seq_score.hip; called by tu_seq.hip)
 void launch_seq_scored(hipStream_t stream, uint32_t S, size_t lds, const PodsDev& pd, const GroupsDev& gr, const NodesDev& nd, const SeqDev& sq, const SeqParams& prm,
                        const SeqScore& sco);

@@ -1,6 +1,7 @@
-// bs_seq_pass.inc — the body of k_seq_pass (bs_seq.hpp), included once by each of its three kernel templates: k_seq_pass<TS> (bs_seq_run) with
+// bs_seq_pass.inc — the body of k_seq_pass (bs_seq.hpp), included once by each of its four kernel templates: k_seq_pass<TS> (bs_seq_run) with
 // `constexpr bool NOM = false`, k_seq_pass<TS, true> (bs_seq_run_nominated, rule S) with NOM = true and the kernel argument `nom`,
-// k_seq_scored<TS> (bs_seq_run_scored, rule P) with SCORE = true and the kernel argument `sco`.  Every NOM-only line sits behind
+// k_seq_scored<TS> (bs_seq_run_scored, rule P) with SCORE = true and the kernel argument `sco`, k_seq_sp<TS>
+// (bs_seq_run_scored_nominated, rule SP) with both flags and both arguments.  Every NOM-only line sits behind
 // `if constexpr (NOM)`, every scored-only line behind `if constexpr (SCORE)`; what the scored pass must not touch (the first-fit cursors,
 // `mono`) behind `if constexpr (!SCORE)`.  A shared __device__ function would be the usual form; the flag-less kernels then come
 // out as other instructions than before (inlining a by-reference body is not the same input to the optimiser), and bs_seq_run's kernels
@@ -32,8 +33,10 @@
   if constexpr (NOM) {
     ns = reinterpret_cast<SeqNomShared*>(reinterpret_cast<unsigned char*>(s_keys) + nom.lds_off);
     if (threadIdx.x < kSeqPruneTiles / 32) ns->wild[threadIdx.x] = 0;
+    if constexpr (!SCORE) {                                  // (grow and cur_prio[] serve the first-fit cursors alone)
     if (t0) ns->grow = 0u;
     for (uint32_t e = threadIdx.x; e < kSeqCursors; e += kSeqBlock) ns->cur_prio[e] = 0;
+    }
     __syncthreads();                                         // (wild[] is or-ed into by the loop below)
   }
   for (uint32_t base = 0; base < N; base += kSeqBlock) {
@@ -81,7 +84,7 @@
       }
     }
   }
-  if constexpr (NOM) {
+  if constexpr (NOM && !SCORE) {
     // The first-fit cursors rest on "the room a pod sees only shrinks": with every assume step, and from a pod of priority Pc to one of
     // P <= Pc, who sees every row that pod saw and more.  A row takes room only if its lanes are not negative and no sum wraps.  That holds
     // when every row asks for 0 <= v < 2^40 on EVERY lane (at most 2^16 rows: a sum stays below 2^56) and, on every schedulable node that
@@ -144,7 +147,7 @@
   bool wl_ok = true;                                         // ... and the list holds ALL of them (nothing waited before the group became current)
   const unsigned long long clk0 = (unsigned long long)wall_clock64();
   BS_SEQ_FULL_BARRIER();
-  if constexpr (NOM) mono = uni32(ns->grow) == 0u;           // (see the prologue: a row that may grow the room switches the cursors off)
+  if constexpr (NOM && !SCORE) mono = uni32(ns->grow) == 0u;           // (see the prologue: a row that may grow the room switches the cursors off)
 #ifdef BS_SEQ_PROBE
   unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl = (unsigned long long)__builtin_readcyclecounter();
   if (t0) { for (int k = 0; k < 32; ++k) sh_.ph2[k] = 0; sh_.tl2 = tl; }
@@ -433,8 +436,20 @@
       if constexpr (SCORE) {
         // rule P: the candidate with the largest total, ties to the lowest index — a full search, so no cursor and no `mono`
         uint32_t sc_total = 0, sc_nfit = 0;
+        if constexpr (NOM) {
+          // rule SP: rule S decides the candidates, rule P the choice among them (raw lanes, D8), D6 the consume behind it
+          SeqPickNom pn{};
+          pn.nom = &nom; pn.ns = ns; pn.prio = (int32_t)uni32((uint32_t)ns->pw_prio[pw]); pn.own = uni32(ns->pw_own[pw]);
+          at = seq_pick_scored<TS, true>(nd, sq, prm, sh_, *reinterpret_cast<SeqScoreShared*>(reinterpret_cast<unsigned char*>(s_keys) + sco.lds_off), q, sco,
+                                         slot_key, drained || !stores_pending, as, n_tiles, sc_total, sc_nfit, pw, pn);
+          // consume (D6), no cursor to clear.  Thread 0's store is invisible to no later pod: every search reads consumed[] behind a
+          // __syncthreads that follows this store — the one `stores_pending` asks for (set below by this very assume step) in front of the
+          // next pod's scan, or else the one at the head of seq_pick_scored (`drained` false, stores_pending true).
+          if (at != BS_INF && pn.own != kNmNone && t0) { nom.consumed[pn.own] = 1; nom.c_pod[pn.own] = i; nom.c_node[pn.own] = at; }
+        } else {
         at = seq_pick_scored<TS>(nd, sq, prm, sh_, *reinterpret_cast<SeqScoreShared*>(reinterpret_cast<unsigned char*>(s_keys) + sco.lds_off), q, sco, slot_key,
                                  drained || !stores_pending, as, n_tiles, sc_total, sc_nfit, pw);
+        }
         if (!drained) stores_pending = false;                // (the search drained them itself)
         if (threadIdx.x == kSeqResultThread) { sco.total[i] = sc_total; sco.n_fit[i] = sc_nfit; }
       } else {

@@ -32,6 +32,7 @@
 #include "tu_seq.hip"
 #include "tu_seq_nom.hip"
 #include "tu_seq_score.hip"
+#include "tu_seq_score_nom.hip"
 #include "tu_seq_expire.hip"
 #include "tu_wait.hip"
 #include "tu_groups.hip"

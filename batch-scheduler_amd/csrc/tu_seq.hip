@@ -1,6 +1,7 @@
 // tu_seq.hip — translation unit of the sequential pass: its kernel (bs_seq.hpp: k_seq_pass<TS>, six instantiations; k_seq_pass<TS, true>, the
-// same six under rule S, are emitted by tu_seq_nom.hip, k_seq_scored<TS>, the six under rule P, by tu_seq_score.hip), the file-local
-// launch wrapper and the entry points bs_seq_run, bs_seq_run_nominated and bs_seq_run_scored (include/bsched.h) with their flat forms,
+// same six under rule S, are emitted by tu_seq_nom.hip, k_seq_scored<TS>, the thirteen under rule P, by tu_seq_score.hip, k_seq_sp<TS>,
+// the thirteen under rule SP, by tu_seq_score_nom.hip), the file-local launch wrapper and the entry points bs_seq_run, bs_seq_run_nominated,
+// bs_seq_run_scored and bs_seq_run_scored_nominated (include/bsched.h) with their flat forms,
 // bs_seq_nominated_read and bs_seq_score_read; see tu_fast.hip for why.  The nominated-pod table is reached through bs_ctx.hpp's declarations
 // (tu_nominated.hip defines them): this unit does not include bs_nominated.hpp and emits no k_nm_* kernel.
 #ifndef BS_UNITY
@@ -194,7 +195,8 @@ static int seq_run_impl(bs_ctx* c, uint32_t stages, bs_seq_out* out, const SeqNo
   }
   const PodsDev pd = pods_dev(c);
   const NodesDev nd = nodes_dev(c);
-  if (score) launch_seq_scored(c->stream, c->S, lds, pd, gr, nd, sq, prm, sco);   // (tu_seq_score.hip: the scored instantiations)
+  if (score && nc) launch_seq_scored_nominated(c->stream, c->S, lds, pd, gr, nd, sq, prm, nom, sco);   // (tu_seq_score_nom.hip: rule SP)
+  else if (score) launch_seq_scored(c->stream, c->S, lds, pd, gr, nd, sq, prm, sco);   // (tu_seq_score.hip: the scored instantiations)
   else if (nc) launch_seq_nominated(c->stream, c->S, lds, pd, gr, nd, sq, prm, nom);   // (tu_seq_nom.hip: the NOM instantiations)
   else launch_seq(c->stream, c->S, lds, pd, gr, nd, sq, prm);
   LAUNCHCHK(c, BS_KERNEL_QUERY);
@@ -332,9 +334,35 @@ int bs_seq_run_scored(bs_ctx* c, uint32_t stages, const bs_seq_score* score, bs_
   return seq_run_impl(c, stages, out, nullptr, score);
 }
 
+int bs_seq_run_scored_nominated(bs_ctx* c, uint32_t stages, uint32_t p, const int32_t* priority, const uint32_t* own_id, const bs_seq_score* score,
+                                bs_seq_out* out) {
+  // the refusals of bs_seq_run_nominated in its order, then those of bs_seq_run_scored: all before any launch, nothing resident changes
+  if (!c || !out) return BS_ERR_INVALID;
+  if (const int rc = seq_refusals(c, stages)) return rc;
+  if (stages & BS_STAGE_FILTER) {
+    c->last_error = "bs_seq_run_scored_nominated: BS_STAGE_FILTER is refused (the plugin's Filter takes no part in the fit test under nominees, as in bs_preempt_run)";
+    return BS_ERR_INVALID;
+  }
+  if (p != c->P) { c->last_error = "bs_seq_run_scored_nominated: p is not the resident queue's length (bs_pods_count)"; return BS_ERR_INVALID; }
+  if (p && !priority) { c->last_error = "bs_seq_run_scored_nominated: priority is NULL and the queue has pods"; return BS_ERR_INVALID; }
+  if (const int rc = nom_state(c, "bs_seq_run_scored_nominated")) return rc;
+  std::vector<uint32_t> own_row;
+  if (const int bad = nom_own_check(c->nom_live.data(), c->nom_w, c->nom_ids, p, own_id, BS_NOM_NONE, own_row)) {
+    c->last_error = std::string("bs_seq_run_scored_nominated: ") + nom_own_check_text(bad);
+    return BS_ERR_INVALID;
+  }
+  if (!score) { c->last_error = "bs_seq_run_scored_nominated: score is NULL"; return BS_ERR_INVALID; }
+  if (score->w_least > BS_SCORE_WEIGHT_MAX || score->w_most > BS_SCORE_WEIGHT_MAX || score->w_balanced > BS_SCORE_WEIGHT_MAX) {
+    c->last_error = "bs_seq_run_scored_nominated: a weight is above BS_SCORE_WEIGHT_MAX";
+    return BS_ERR_INVALID;
+  }
+  const SeqNomCall nc{priority, &own_row};
+  return seq_run_impl(c, stages, out, &nc, score);
+}
+
 int bs_seq_score_read(bs_ctx* c, uint32_t p, uint32_t* total, uint32_t* n_fit) {
   if (!c) return BS_ERR_INVALID;
-  if (!c->seq_score_valid) { c->last_error = "bs_seq_score_read: the context's last pass was not a successful bs_seq_run_scored"; return BS_ERR_STATE; }
+  if (!c->seq_score_valid) { c->last_error = "bs_seq_score_read: the context's last pass was not a successful bs_seq_run_scored or bs_seq_run_scored_nominated"; return BS_ERR_STATE; }
   if (p != c->seq_score_p) { c->last_error = "bs_seq_score_read: p is not the queue length of that pass"; return BS_ERR_INVALID; }
   if (const int rc = use_device(c)) return rc;
   const uint32_t* d = c->d_seq_score.as<uint32_t>();
@@ -346,7 +374,7 @@ int bs_seq_score_read(bs_ctx* c, uint32_t p, uint32_t* total, uint32_t* n_fit) {
 
 int bs_seq_nominated_read(bs_ctx* c, uint32_t cap, uint32_t* id, uint32_t* pod, uint32_t* node, uint32_t* n_out) {
   if (!c || !n_out) return BS_ERR_INVALID;
-  if (!c->seq_nom_valid) { c->last_error = "bs_seq_nominated_read: the context's last pass was not a successful bs_seq_run_nominated"; return BS_ERR_STATE; }
+  if (!c->seq_nom_valid) { c->last_error = "bs_seq_nominated_read: the context's last pass was not a successful bs_seq_run_nominated or bs_seq_run_scored_nominated"; return BS_ERR_STATE; }
   const uint32_t n = (uint32_t)c->seq_nom_id.size(), k = std::min(n, cap);
   if (k && (!id || !pod || !node)) { c->last_error = "bs_seq_nominated_read: an output array is NULL with rows to report"; return BS_ERR_INVALID; }
   if (k) {
@@ -366,6 +394,24 @@ int bs_seq_run_nominated_flat(bs_ctx* c, uint32_t stages, uint32_t p, const int3
   o.pf_code = pf_code; o.pf_first_k = pf_first_k; o.pf_leader = pf_leader; o.pod_node = pod_node; o.cap = cap; o.released_group = released_group;
   o.released_pods = released_pods; o.first_ns = first_ns; o.ready_ns = ready_ns;
   const int rc = bs_seq_run_nominated(c, stages, p, priority, own_id, &o);
+  if (scalars_out) {
+    scalars_out[0] = o.n_released; scalars_out[1] = o.total_ns; scalars_out[2] = (int64_t)o.node_picks; scalars_out[3] = (int64_t)o.node_scans;
+    scalars_out[4] = (int64_t)o.scan_rounds; scalars_out[5] = (int64_t)o.pick_rounds; scalars_out[6] = (int64_t)o.leader_folds;
+    scalars_out[7] = (int64_t)o.table_builds;
+  }
+  return rc;
+}
+
+int bs_seq_run_scored_nominated_flat(bs_ctx* c, uint32_t stages, uint32_t p, const int32_t* priority, const uint32_t* own_id, uint32_t w_least, uint32_t w_most,
+                                     uint32_t w_balanced, uint8_t* pf_code, uint32_t* pf_first_k, int32_t* pf_leader, int32_t* pod_node, uint32_t cap,
+                                     uint32_t* released_group, uint32_t* released_pods, int64_t* first_ns, int64_t* ready_ns, int64_t* scalars_out,
+                                     uint8_t* last_permitted) {
+  bs_seq_out o{};
+  o.last_permitted = last_permitted;
+  o.pf_code = pf_code; o.pf_first_k = pf_first_k; o.pf_leader = pf_leader; o.pod_node = pod_node; o.cap = cap; o.released_group = released_group;
+  o.released_pods = released_pods; o.first_ns = first_ns; o.ready_ns = ready_ns;
+  const bs_seq_score score{w_least, w_most, w_balanced};
+  const int rc = bs_seq_run_scored_nominated(c, stages, p, priority, own_id, &score, &o);
   if (scalars_out) {
     scalars_out[0] = o.n_released; scalars_out[1] = o.total_ns; scalars_out[2] = (int64_t)o.node_picks; scalars_out[3] = (int64_t)o.node_scans;
     scalars_out[4] = (int64_t)o.scan_rounds; scalars_out[5] = (int64_t)o.pick_rounds; scalars_out[6] = (int64_t)o.leader_folds;

@@ -213,3 +213,66 @@ func (g *gpuCore) seqPassNominated(priority []int32, ownRow []uint32) (*seqResul
 	}
 	return r, gone, nil
 }
+
+// scoreWeights are the three weights of rule P (bs_seq_score): least requested, most requested, balanced allocation.
+type scoreWeights struct {
+	least, most, balanced uint32
+}
+
+// seqPassScoredNominated: seqPassNominated with the scored node choice (bs_seq_run_scored_nominated, rule SP of include/bsched.h): the
+// pass a nominating cycle ends in.  The nominated-pod table decides which nodes are candidates (rule S: a pod of priority P sees the rows
+// with priority >= P other than its own), rule P's total over the node's own requests decides among them — no row enters a score (D8) —,
+// ties go to the lowest index.  priority, ownRow and `consumed` are seqPassNominated's.  total[i] is the chosen node's total and nFit[i]
+// the number of candidates of queue pod i (bs_seq_score_read), 0 where the choice was not reached.
+func (g *gpuCore) seqPassScoredNominated(w scoreWeights, priority []int32, ownRow []uint32) (r *seqResult, consumed []consumedNominee,
+	total, nFit []uint32, err error) {
+	P := len(priority)
+	if ownRow != nil && len(ownRow) != P {
+		return nil, nil, nil, nil, fmt.Errorf("seqPassScoredNominated: %d own rows for %d pods", len(ownRow), P)
+	}
+	cap := g.groups + 1
+	r = &seqResult{pfCode: make([]C.uint8_t, P+1), podNode: make([]C.int32_t, P+1), releasedGroup: make([]C.uint32_t, cap),
+		releasedPods: make([]C.uint32_t, cap), readyNs: make([]C.int64_t, cap), lastPermitted: make([]C.uint8_t, P+1)}
+	firstNs := make([]C.int64_t, cap)
+	var scalars [8]C.int64_t
+	prio, own := make([]C.int32_t, P+1), make([]C.uint32_t, P+1)
+	for i := range priority {
+		prio[i] = C.int32_t(priority[i])
+		own[i] = C.uint32_t(noNominatedRow)
+		if ownRow != nil {
+			own[i] = C.uint32_t(ownRow[i])
+		}
+	}
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if rc := C.bs_seq_run_scored_nominated_flat(g.ctx, C.uint32_t(C.BS_STAGE_PREFILTER), C.uint32_t(P), &prio[0], &own[0], C.uint32_t(w.least),
+		C.uint32_t(w.most), C.uint32_t(w.balanced), &r.pfCode[0], nil, nil, &r.podNode[0], C.uint32_t(cap), &r.releasedGroup[0],
+		&r.releasedPods[0], &firstNs[0], &r.readyNs[0], &scalars[0], &r.lastPermitted[0]); rc != C.BS_OK {
+		return nil, nil, nil, nil, g.pdbErr("bs_seq_run_scored_nominated_flat", rc)
+	}
+	r.nReleased = int(scalars[0])
+	ct, cf := make([]C.uint32_t, P+1), make([]C.uint32_t, P+1)
+	if rc := C.bs_seq_score_read(g.ctx, C.uint32_t(P), &ct[0], &cf[0]); rc != C.BS_OK {
+		return nil, nil, nil, nil, g.pdbErr("bs_seq_score_read", rc)
+	}
+	total, nFit = make([]uint32, P), make([]uint32, P)
+	for i := 0; i < P; i++ {
+		total[i], nFit[i] = uint32(ct[i]), uint32(cf[i])
+	}
+	var n C.uint32_t
+	if rc := C.bs_seq_nominated_read(g.ctx, 0, nil, nil, nil, &n); rc != C.BS_OK {
+		return nil, nil, nil, nil, g.pdbErr("bs_seq_nominated_read", rc)
+	}
+	if n == 0 {
+		return r, nil, total, nFit, nil
+	}
+	id, pod, node := make([]C.uint32_t, n), make([]C.uint32_t, n), make([]C.uint32_t, n)
+	if rc := C.bs_seq_nominated_read(g.ctx, n, &id[0], &pod[0], &node[0], &n); rc != C.BS_OK {
+		return nil, nil, nil, nil, g.pdbErr("bs_seq_nominated_read", rc)
+	}
+	consumed = make([]consumedNominee, n)
+	for i := range consumed {
+		consumed[i] = consumedNominee{uint32(id[i]), uint32(pod[i]), uint32(node[i])}
+	}
+	return r, consumed, total, nFit, nil
+}

@@ -1110,7 +1110,7 @@ int bs_nominated_nodes_apply(bs_ctx* ctx, uint32_t count, const uint32_t* kind, 
  *       row.
  *   bs_seq_nominated_read   the consumed rows of the last successful bs_seq_run_nominated in ascending id, as (id, queue index of the
  *       pod, node it was assumed on); *n_out the true count, the first min(n, cap) rows are written.  BS_ERR_STATE when the context's
- *       last pass was not that call.
+ *       last pass was not that call (or bs_seq_run_scored_nominated, which consumes by the same rule).
  *   after the call  the context is in the state bs_seq_run leaves: bs_seq_expire, bs_seq_waiting_read, bs_wait_park and bs_bound_bind work as
  *       after bs_seq_run.  With an empty table and no own ids every output and all resident state equal bs_seq_run's.
  *   errors      all found on the host before any launch; nothing resident changes.  Everything bs_seq_run refuses, with the same code.
@@ -1157,14 +1157,50 @@ int bs_seq_nominated_read(bs_ctx* ctx, uint32_t cap, uint32_t* id, uint32_t* pod
  *       after bs_seq_run.  bs_seq_nominated_read answers BS_ERR_STATE, as after any pass that is not its own.
  *   errors      all found on the host before any launch; nothing resident changes.  Everything bs_seq_run refuses, with the same code.
  *       BS_ERR_INVALID: a NULL score, a weight above BS_SCORE_WEIGHT_MAX.  bs_seq_score_read: BS_ERR_STATE when the last successful pass was
- *       not bs_seq_run_scored, BS_ERR_INVALID when p differs from that pass's.
- *   Out of scope: the scored choice together with the nominated-pod table (a pass under rules S and P at once: six more instantiations of
- *   the persistent kernel and a product of two rule sets — a step of its own once this one is measured); scoring in bs_batch_run (the
- *   frozen-snapshot pre-screen chooses no node); upstream priorities that read labels, images or other pods (no resource arithmetic). */
+ *       not bs_seq_run_scored (or bs_seq_run_scored_nominated), BS_ERR_INVALID when p differs from that pass's.
+ *   Out of scope: the scored choice together with the nominated-pod table is not this call's — bs_seq_run_scored does not see the table; the
+ *   pass under rules S and P at once is bs_seq_run_scored_nominated (rule SP, below); scoring in bs_batch_run (the frozen-snapshot
+ *   pre-screen chooses no node); upstream priorities that read labels, images or other pods (no resource arithmetic). */
 #define BS_SCORE_WEIGHT_MAX 65536u
 typedef struct bs_seq_score { uint32_t w_least, w_most, w_balanced; } bs_seq_score;
 int bs_seq_run_scored(bs_ctx* ctx, uint32_t stages, const bs_seq_score* score, bs_seq_out* out);
 int bs_seq_score_read(bs_ctx* ctx, uint32_t p, uint32_t* total /*[p]*/, uint32_t* n_fit /*[p]*/);
+
+/* ---- the sequential pass under rules S and P at once: bs_seq_run_scored_nominated ----------------------------------------------------
+ * A cluster that runs bs_preempt_commit with BS_PREEMPT_NOMINATE and then schedules the next cycle needs both rules in ONE pass: with
+ * bs_seq_run_nominated it gets first-fit placements, which no cluster has; with bs_seq_run_scored lower-priority pods are scored straight
+ * into the room the last cycle's victims were evicted for, the preemptor finds its node full again and preempts a second time.
+ * bs_seq_run_scored_nominated is bs_seq_run_scored with rule S in its candidate set and D6's consume behind its choice.  priority, own_id
+ * and p are bs_seq_run_nominated's, score is bs_seq_run_scored's.
+ *   SP. (rule SP.)  For pod i of priority P with own row `own`:
+ *       Candidate set.  C is the set of nodes rule S accepts; nothing about that test is new: the same skip rule (node flags, checkFit bit),
+ *       holds() evaluated on the node's current requests plus every LIVE row on the node with row.priority >= P that is not pod i's own
+ *       row.  The row sums follow rule S exactly, wrapping: the pods-lane form requested + sum + 1 <= allocatable, the scalar form with
+ *       the allocatable key still required.
+ *       Score.  The pod takes the member of C with the largest `total` of rule P (D7), ties to the LOWEST node index.  `total` is computed
+ *       from the node's RAW lanes, R = requested[j][k] + request_i[j].  No row enters a score.
+ *   D8. (recalled upstream, v1.17.5, not vendored.)  addNominatedPods works on a COPY of the NodeInfo inside podFitsOnNode;
+ *       PrioritizeNodes reads the snapshot's NodeInfo, which holds no nominated pod.  Nominees therefore narrow the candidates and never
+ *       move a score.
+ *       Assume writes the pod's own request only, as in rule S: bs_nodes_read after the pass holds no row.
+ *       D6 applies unchanged: a pod with an own row that is assumed on ANY node consumes that row for every later pod of the pass; the row
+ *       leaves the table by the stable compaction after the pass and its id is dead.
+ *       S1 applies unchanged: PreFilter never sees a row.
+ *       Library rule SP1: with all three weights 0 the pass is bs_seq_run_nominated, bit for bit: every result array, the released gangs,
+ *       the consumed rows, the table afterwards and all resident state (the work counters of bs_seq_out count a full search, as in P2).
+ *       Library rule SP2: with a table that is empty but loaded (bs_nominated_load with m = 0) and no own id the pass is bs_seq_run_scored,
+ *       bit for bit, bs_seq_score_read included.
+ *   bs_seq_score_read   answers for this pass: total[i] is the chosen node's total, n_fit[i] is |C| under rule S, 0 where the choice was
+ *       not reached.
+ *   bs_seq_nominated_read   answers for this pass: the consumed rows in ascending id, as (id, pod, node).
+ *       Both answers stay valid until the context's next pass; after any other pass the two reads behave as stated at their own calls.
+ *   after the call  the context is in the state bs_seq_run leaves: bs_seq_expire, bs_seq_waiting_read, bs_wait_park and bs_bound_bind work as
+ *       after bs_seq_run.
+ *   errors      all found on the host before any launch; nothing resident changes.  Everything bs_seq_run_nominated refuses, with the same
+ *       code (BS_STAGE_FILTER and BS_BATCH_FILTER_DENY among them, for the reason given there), then everything bs_seq_run_scored
+ *       refuses, with the same code: a NULL score, a weight above BS_SCORE_WEIGHT_MAX. */
+int bs_seq_run_scored_nominated(bs_ctx* ctx, uint32_t stages, uint32_t p, const int32_t* priority /*[p]*/, const uint32_t* own_id /*[p] or NULL*/,
+                                const bs_seq_score* score, bs_seq_out* out);
 /* The live bound table in table order: node ascending, importance order within a node; bs_bound_count entries.  id_out[i] = the
  * entry's id (its index at the last bs_bound_load), node_out[i] = its node.  BS_ERR_STATE before bs_bound_load; the arrays may be NULL
  * when the table is empty. */
@@ -1450,6 +1486,11 @@ int bs_seq_run_nominated_flat(bs_ctx* ctx, uint32_t stages, uint32_t p, const in
 int bs_seq_run_scored_flat(bs_ctx* ctx, uint32_t stages, uint32_t w_least, uint32_t w_most, uint32_t w_balanced, uint8_t* pf_code,
                            uint32_t* pf_first_k, int32_t* pf_leader, int32_t* pod_node, uint32_t cap, uint32_t* released_group,
                            uint32_t* released_pods, int64_t* first_ns, int64_t* ready_ns, int64_t* scalars_out, uint8_t* last_permitted);
+/* bs_seq_run_scored_nominated: bs_seq_run_nominated_flat's two arrays, then bs_seq_run_scored_flat's three weights, then the results */
+int bs_seq_run_scored_nominated_flat(bs_ctx* ctx, uint32_t stages, uint32_t p, const int32_t* priority, const uint32_t* own_id, uint32_t w_least,
+                                     uint32_t w_most, uint32_t w_balanced, uint8_t* pf_code, uint32_t* pf_first_k, int32_t* pf_leader, int32_t* pod_node,
+                                     uint32_t cap, uint32_t* released_group, uint32_t* released_pods, int64_t* first_ns, int64_t* ready_ns,
+                                     int64_t* scalars_out, uint8_t* last_permitted);
 /* bs_fit_build: node tables, then the template tables; `ex_*` = bs_fit_templates.exprs, `fd_*` = bs_fit_templates.fields */
 int bs_fit_build_flat(bs_ctx* ctx, uint32_t n, const uint32_t* name, const uint32_t* label_off, const uint32_t* label_key, const uint32_t* label_val,
                       const int64_t* label_int, const uint8_t* label_int_ok, const uint32_t* taint_off, const uint32_t* taint_key,

@@ -3,7 +3,13 @@ weights (0, 0, 0) — the same placements through the full search — and with (
 reloads nodes, groups and pods, so every pass starts from the same state; one untimed pass of each form first, so that no figure contains
 a code-object load.  The figure is the kernel's own clock (bs_seq_out.total_ns), median and best of `--reps` timed passes (default 7),
 with each form's spread (max - min) so that a ratio can be read against the noise of the same run.  Prints one JSON line.
-Usage: python tools/seq_scored_bench.py [config] [scenario] [--reps N]"""
+
+--nominated FRACTION times bs_seq_run_scored_nominated (rule SP) beside bs_seq_run_scored instead, on the same scene and weights, in the
+same process: a nominated-pod table is loaded in front of every pass in which that share of the nodes carries one row (half of the node's
+free cpu, a priority drawn from the queue's four) and that share of the queue owns a row (the pod's own request on a random node); each
+fraction in the comma-separated list gives one entry, for the weights (0, 0, 0) and (1, 0, 1).  Fraction 0 is the empty table: what the
+NOM branches cost when nothing is nominated.
+Usage: python tools/seq_scored_bench.py [config] [scenario] [--reps N] [--nominated F[,F...]]"""
 import importlib
 import json
 import os
@@ -21,11 +27,67 @@ def opt(name, default):
     return int(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
 
 
+PRIOS = (0, 10, 20, 30)
+
+
+def table(nodes, pods, frac, seed=7):
+    """(node, priority, req [L][m], req_present), the queue's priorities [p] and own ids [p] for --nominated frac"""
+    rng = np.random.default_rng(seed)
+    N, P, L = int(nodes.n), int(pods.p), int(nodes.lanes)
+    carry = rng.permutation(N)[: int(round(frac * N))]
+    owners = np.sort(rng.permutation(P)[: int(round(frac * P))])
+    m = carry.size + owners.size
+    prio = rng.choice(PRIOS, size=P).astype(np.int32)
+    node = np.concatenate([carry, rng.integers(0, max(N, 1), size=owners.size)]).astype(np.uint32)
+    rprio = np.concatenate([rng.choice(PRIOS, size=carry.size), prio[owners]]).astype(np.int32)
+    req, pres = np.zeros((L, m), np.int64), np.zeros(m, np.uint32)
+    req[0, : carry.size] = np.maximum(nodes.allocatable[0, carry] - nodes.requested[0, carry], 0) // 2
+    req[:, carry.size:] = pods.req[:, owners]
+    req[3] = 1
+    pres[carry.size:] = pods.req_present[owners]
+    own = np.full(P, bsa.capi.NOM_NONE, np.uint32)
+    own[owners] = np.arange(carry.size, m, dtype=np.uint32)
+    return (node, rprio, req, pres), prio, own
+
+
+def nominated(config, scenario, reps, fracs):
+    nodes, fit, groups, pods, _ = bsa.synth.make(config, scenario)
+    pods = pods.take(np.argsort(pods.group, kind="stable"))           # Compare order
+    out = {"config": f"{config}/{scenario}", "pods": int(pods.p), "nodes": int(nodes.n), "groups": int(groups.g), "reps": reps, "runs": []}
+    with bsa.Context(scalar_lanes=nodes.lanes - 4) as ctx:
+        for frac in fracs:
+            tab, prio, own = table(nodes, pods, frac)
+            for weights in ((0, 0, 0), (1, 0, 1)):
+                run = {"nominated": frac, "rows": int(tab[0].size), "own": int((own != bsa.capi.NOM_NONE).sum()), "weights": list(weights), "forms": {}}
+                for name in ("scored", "scored_nominated"):
+                    dev, r = [], None
+                    for rep in range(reps + 1):                        # (the first one is the warm-up)
+                        ctx.load_nodes(nodes, fit)
+                        ctx.load_groups(groups)
+                        ctx.load_pods(pods)
+                        ctx.nominated_load(*tab)
+                        r = ctx.seq_run_scored(weights) if name == "scored" else ctx.seq_run_scored_nominated(weights, prio, own)
+                        if rep:
+                            dev.append(r["total_ns"])
+                    wait = ctx.seq_waiting_read()
+                    s = ctx.seq_score_read()
+                    run["forms"][name] = {"kernel_ms_median": float(np.median(dev)) / 1e6, "kernel_ms_best": min(dev) / 1e6, "kernel_ms_spread": (max(dev) - min(dev)) / 1e6,
+                                          "pods_released": int((r["pod_node"] >= 0).sum()), "pods_waiting": int((wait >= 0).sum()), "node_picks": r["node_picks"],
+                                          "pick_rounds": r["pick_rounds"], "n_fit_mean": float(s["n_fit"][s["n_fit"] > 0].mean()) if (s["n_fit"] > 0).any() else 0.0}
+                    if name == "scored_nominated":
+                        run["forms"][name]["rows_consumed"] = int(ctx.seq_nominated_read()["n"])
+                run["ratio_kernel_median"] = run["forms"]["scored_nominated"]["kernel_ms_median"] / run["forms"]["scored"]["kernel_ms_median"]
+                out["runs"].append(run)
+    print(json.dumps(out))
+
+
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("--") and not a.isdigit()]
+    args = [a for a in sys.argv[1:] if not a.startswith("--") and not a.isdigit() and not a.replace(",", "").replace(".", "").isdigit()]
     config = args[0] if args else "cfg3"
     scenario = args[1] if len(args) > 1 else "tail"
     reps = opt("--reps", 7)
+    if "--nominated" in sys.argv:
+        return nominated(config, scenario, reps, [float(f) for f in sys.argv[sys.argv.index("--nominated") + 1].split(",")])
     nodes, fit, groups, pods, _ = bsa.synth.make(config, scenario)
     pods = pods.take(np.argsort(pods.group, kind="stable"))           # Compare order
     out = {"config": f"{config}/{scenario}", "pods": int(pods.p), "nodes": int(nodes.n), "groups": int(groups.g), "reps": reps, "forms": {}}
