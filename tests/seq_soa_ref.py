@@ -29,12 +29,13 @@ def w64(v: int) -> int:
     return v - (1 << 64) if v >> 63 else v
 
 
-def holds(alloc, apres: int, have, hpres: int, r, pres: int, S: int) -> bool:
-    """bs_oracle_seq.c, holds(): alloc / have are the node's allocatable and requested lanes as Python ints, apres / hpres their key bits"""
+def holds(alloc, apres: int, have, hpres: int, r, pres: int, S: int, mutate=None) -> bool:
+    """bs_oracle_seq.c, holds(): alloc / have are the node's allocatable and requested lanes as Python ints, apres / hpres their key bits
+    (mutate: see MUTANTS)"""
     for j in range(3):
-        if r[j] > 0 and r[j] > w64(alloc[j] - have[j]):
+        if (r[j] > 0 or mutate == "zero_binds") and r[j] > w64(alloc[j] - have[j]):
             return False
-    if have[3] + 1 > alloc[3]:
+    if have[3] + 1 > alloc[3] or (mutate == "pods_lane_lt" and have[3] + 1 == alloc[3]):
         return False
     for s in range(S):
         if not (pres >> s) & 1 or r[4 + s] <= 0:
@@ -53,6 +54,7 @@ class Work:
     def __init__(self, nodes, S):
         self.nodes, self.S, self.L = nodes, S, 4 + S
         self.E, self.r, self.pres = [], None, 0         # the eligible nodes of the pod at hand (flags, checkFit), its request, its key bits
+        self.mutate = None
 
     def alloc(self, k):
         return [int(self.nodes.allocatable[j, k]) for j in range(self.L)]
@@ -63,7 +65,7 @@ class Work:
     def holds(self, k, have=None, hpres=None) -> bool:
         nd = self.nodes
         return holds(self.alloc(k), int(nd.allocatable_present[k]), self.have(k) if have is None else have,
-                     int(nd.requested_present[k]) if hpres is None else hpres, self.r, self.pres, self.S)
+                     int(nd.requested_present[k]) if hpres is None else hpres, self.r, self.pres, self.S, self.mutate)
 
 
 def first_fit(i, C, work):
@@ -138,9 +140,18 @@ class ScoredChoice:
         return C[tot.index(top)]
 
 
-def seq_pass(orc, nodes, fit, groups, pods, leader, choose) -> dict:
+# single-rule changes of the assume / Permit / release block below (tests/test_seq_hand_cpu.py: every one of them has to disagree with a
+# hand-derived answer of tests/golden/seq_hand_kats.json).  seq_pass(..., mutate=None) is the pass itself.
+MUTANTS = ("quorum_gt", "quorum_signed", "release_this_pass", "postbind_one", "close_gt", "closed_releases", "no_latch_closed", "matched_kept",
+           "nonode_counted", "rollback_unreleased", "pods_lane_not_bumped", "pods_lane_lt", "zero_binds", "flags_ignored", "fitbit_ignored",
+           "no_present_bit", "last_fit")
+
+
+def seq_pass(orc, nodes, fit, groups, pods, leader, choose, mutate=None) -> dict:
     """-> what orc.seq_replay returns (without its timings), plus assumed [p] (the node every pod was assumed on, -1 none) and wait_node [p]
-    as seq_expire_ref.waiting_after_pass states it.  Works on copies of nodes and groups."""
+    as seq_expire_ref.waiting_after_pass states it.  Works on copies of nodes and groups.  mutate: one name of MUTANTS, the pass with that one
+    rule changed (a wrong pass on purpose)."""
+    assert mutate is None or mutate in MUTANTS, mutate
     nodes = nodes.copy()
     snap = orc.Snapshot(nodes, fit)
     sop = orc.Sop(snap, groups).carry(leader)
@@ -149,11 +160,12 @@ def seq_pass(orc, nodes, fit, groups, pods, leader, choose) -> dict:
     L = 4 + S
     fitb = fit.to_bool()
     work = Work(nodes, S)
+    work.mutate = mutate
     pf, fk, ld = np.zeros(P, np.uint8), np.zeros(P, np.uint32), np.zeros(P, np.int32)
     pod_node, assumed = np.full(P, -1, np.int32), np.full(P, -1, np.int32)
     waiting = {}                                            # group -> the pods of this pass that wait at Permit
     rel_group, rel_pods, slot_of = [], [], {}
-    open_nodes = [k for k in range(N) if not nodes.flags[k]]
+    open_nodes = [k for k in range(N) if not nodes.flags[k] or mutate == "flags_ignored"]
     for i in range(P):
         gi = int(pods.group[i])
         grouped = 0 <= gi < G
@@ -166,44 +178,66 @@ def seq_pass(orc, nodes, fit, groups, pods, leader, choose) -> dict:
         r = [int(pods.req[j, i]) for j in range(L)]
         pres, cls = int(pods.req_present[i]), int(pods.cls[i])
         work.r, work.pres = r, pres
-        work.E = [k for k in open_nodes if cls < fit.n_classes and fitb[cls, k]]
+        work.E = [k for k in open_nodes if (cls < fit.n_classes and fitb[cls, k]) or mutate == "fitbit_ignored"]
         C = [k for k in work.E if work.holds(k)]
-        at = choose(i, C, work)
-        if at < 0:
+        at = choose(i, C[::-1] if mutate == "last_fit" else C, work)
+        if at < 0 and not (mutate == "nonode_counted" and grouped):
             continue
-        for j in range(3):
+        for j in range(3 if at >= 0 else 0):
             nodes.requested[j, at] = w64(int(nodes.requested[j, at]) + r[j])
-        nodes.requested[3, at] = w64(int(nodes.requested[3, at]) + 1)
-        for s in range(S):
+        if at >= 0 and mutate != "pods_lane_not_bumped":
+            nodes.requested[3, at] = w64(int(nodes.requested[3, at]) + 1)
+        for s in range(S if at >= 0 else 0):
             if (pres >> s) & 1:
                 if not (int(nodes.requested_present[at]) >> s) & 1:
                     nodes.requested[4 + s, at] = 0
                 nodes.requested[4 + s, at] = w64(int(nodes.requested[4 + s, at]) + r[4 + s])
-                nodes.requested_present[at] |= np.uint32(1 << s)
+                if mutate != "no_present_bit":
+                    nodes.requested_present[at] |= np.uint32(1 << s)
         assumed[i] = at
         if not grouped:
             pod_node[i] = at
             continue
         gr.matched[gi] = (int(gr.matched[gi]) + 1) & 0xFFFFFFFF
         waiting.setdefault(gi, []).append(i)
-        if not orc.permit_ready(int(gr.matched[gi]), int(gr.min_member[gi]), int(gr.status_scheduled[gi])):
+        m1, mm, sc0 = int(gr.matched[gi]), int(gr.min_member[gi]), int(gr.status_scheduled[gi])
+        if mutate == "quorum_gt":
+            ready = m1 > ((mm - sc0) & 0xFFFFFFFF)
+        elif mutate == "quorum_signed":
+            ready = m1 >= mm - sc0
+        else:
+            ready = orc.permit_ready(m1, mm, sc0)
+        if not ready:
             continue
-        gr.flags[gi] |= GROUP_SCHEDULED_LATCH
-        if int(gr.flags[gi]) & GROUP_PHASE_CLOSED:
+        is_closed = bool(int(gr.flags[gi]) & GROUP_PHASE_CLOSED)
+        if not (is_closed and mutate == "no_latch_closed"):
+            gr.flags[gi] |= GROUP_SCHEDULED_LATCH
+        if is_closed and mutate != "closed_releases":
             continue
-        k = int(gr.matched[gi])
-        for w in waiting.pop(gi):
+        here = waiting.pop(gi)
+        k = len(here) if mutate == "release_this_pass" else m1
+        for w in here:
             pod_node[w] = assumed[w]
-        gr.matched[gi] = 0
-        gr.status_scheduled[gi] = (int(gr.status_scheduled[gi]) + k) & 0xFFFFFFFF
-        if int(gr.status_scheduled[gi]) >= int(gr.min_member[gi]):
+        if mutate != "matched_kept":
+            gr.matched[gi] = 0
+        gr.status_scheduled[gi] = (sc0 + (1 if mutate == "postbind_one" else k)) & 0xFFFFFFFF
+        if int(gr.status_scheduled[gi]) >= mm + (1 if mutate == "close_gt" else 0):
             gr.flags[gi] |= GROUP_PHASE_CLOSED
         if gi in slot_of:
-            rel_pods[slot_of[gi]] += k
+            rel_pods[slot_of[gi]] = (rel_pods[slot_of[gi]] + k) & 0xFFFFFFFF      # (a uint32 on the device and in the C oracle)
         else:
             slot_of[gi] = len(rel_group)
             rel_group.append(gi)
             rel_pods.append(k)
+    if mutate == "rollback_unreleased":
+        for i in (w for ws in waiting.values() for w in ws if assumed[w] >= 0):
+            at = int(assumed[i])
+            for j in range(3):
+                nodes.requested[j, at] = w64(int(nodes.requested[j, at]) - int(pods.req[j, i]))
+            nodes.requested[3, at] = w64(int(nodes.requested[3, at]) - 1)
+            for s in range(S):
+                if (int(pods.req_present[i]) >> s) & 1:
+                    nodes.requested[4 + s, at] = w64(int(nodes.requested[4 + s, at]) - int(pods.req[4 + s, i]))
     grouped = (pods.group >= 0) & (pods.group < G)
     wait = np.where(grouped & (assumed >= 0) & (pod_node < 0), assumed, -1).astype(np.int32)
     return dict(pf_code=pf, pf_first_k=fk, pf_leader=ld, pod_node=pod_node, released_group=np.array(rel_group, np.uint32),
