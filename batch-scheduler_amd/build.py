@@ -18,7 +18,7 @@ LIB_DIR = os.environ.get("BS_LIB_DIR") or HERE
 PREBUILT_ONLY = bool(os.environ.get("BS_LIB_DIR"))
 LIB_PATH = os.path.join(LIB_DIR, "libbsched.so")
 # The translation units, bsched.hip first (under -DBS_UNITY it includes the others, in this order).  A new unit is one more name here.
-SOURCES = ["bsched.hip", "tu_fast.hip", "tu_seq.hip", "tu_seq_nom.hip", "tu_seq_score.hip", "tu_seq_score_nom.hip", "tu_seq_expire.hip", "tu_wait.hip", "tu_groups.hip", "tu_bound.hip",
+SOURCES = ["bsched.hip", "tu_fast.hip", "tu_seq.hip", "tu_seq_nom.hip", "tu_seq_score.hip", "tu_seq_score_nom.hip", "tu_seq_sample.hip", "tu_seq_sample_nom.hip", "tu_seq_expire.hip", "tu_wait.hip", "tu_groups.hip", "tu_bound.hip",
            "tu_nominated.hip", "tu_preempt.hip", "tu_bind.hip"]
 _INCLUDE = re.compile(r'^\s*#\s*include\s*"([^"]+)"', re.M)
 

@@ -51,6 +51,8 @@ ABI_SYMBOLS = [
     "bs_seq_run_nominated", "bs_seq_run_nominated_flat", "bs_seq_nominated_read",
     "bs_seq_run_scored", "bs_seq_run_scored_flat", "bs_seq_score_read",
     "bs_seq_run_scored_nominated", "bs_seq_run_scored_nominated_flat",
+    "bs_seq_sample_size", "bs_seq_run_scored_sampled", "bs_seq_run_scored_sampled_flat", "bs_seq_run_scored_nominated_sampled",
+    "bs_seq_run_scored_nominated_sampled_flat", "bs_seq_sample_read",
 ]
 
 SEQ_EXPIRE_DENY, SEQ_EXPIRE_ALL = 1, 2    # bs_seq_expire flags
@@ -145,6 +147,11 @@ class SeqOut(C.Structure):
 class SeqScore(C.Structure):
     """bs_seq_score: the weights of rule P (each at most SCORE_WEIGHT_MAX)"""
     _fields_ = [("w_least", C.c_uint32), ("w_most", C.c_uint32), ("w_balanced", C.c_uint32)]
+
+
+class SeqSample(C.Structure):
+    """bs_seq_sample: rule F's K (0 or >= N: every candidate) and the cursor the pass starts at (taken mod N)"""
+    _fields_ = [("num_to_find", C.c_uint32), ("start", C.c_uint32)]
 
 
 class SeqExpireOut(C.Structure):
@@ -295,6 +302,15 @@ def load_library(path: str | None = None):
     L.bs_seq_run_scored_nominated.argtypes = [vp, u32, u32, P(i32), P(u32), P(SeqScore), P(SeqOut)]
     L.bs_seq_run_scored_nominated_flat.argtypes = [vp, u32, u32, P(i32), P(u32), u32, u32, u32, P(u8), P(u32), P(i32), P(i32), u32, P(u32), P(u32), P(C.c_int64),
                                                    P(C.c_int64), P(C.c_int64), P(u8)]
+    L.bs_seq_sample_size.argtypes = [u32, i32]
+    L.bs_seq_sample_size.restype = u32
+    L.bs_seq_run_scored_sampled.argtypes = [vp, u32, P(SeqScore), P(SeqSample), P(SeqOut)]
+    L.bs_seq_run_scored_sampled_flat.argtypes = [vp, u32, u32, u32, u32, u32, u32, P(u8), P(u32), P(i32), P(i32), u32, P(u32), P(u32), P(C.c_int64),
+                                                 P(C.c_int64), P(C.c_int64), P(u8)]
+    L.bs_seq_run_scored_nominated_sampled.argtypes = [vp, u32, u32, P(i32), P(u32), P(SeqScore), P(SeqSample), P(SeqOut)]
+    L.bs_seq_run_scored_nominated_sampled_flat.argtypes = [vp, u32, u32, P(i32), P(u32), u32, u32, u32, u32, u32, P(u8), P(u32), P(i32), P(i32), u32, P(u32),
+                                                           P(u32), P(C.c_int64), P(C.c_int64), P(C.c_int64), P(u8)]
+    L.bs_seq_sample_read.argtypes = [vp, u32, P(u32), P(u32), P(u32)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:
@@ -654,10 +670,10 @@ class Context:
         resident queue, on the device.  The context's node requests and group state are what the pass left."""
         return self._seq_pass(stages, cap, None, False)
 
-    def _seq_pass(self, stages: int, cap, nominated, flat: bool, weights=None) -> dict:
+    def _seq_pass(self, stages: int, cap, nominated, flat: bool, weights=None, sample=None) -> dict:
         """the result arrays of a sequential pass and the call: bs_seq_run (nominated None), else bs_seq_run_nominated with
         nominated = (p, priority, own_id), through its flat form when flat; weights = (w_least, w_most, w_balanced): bs_seq_run_scored; both:
-        bs_seq_run_scored_nominated"""
+        bs_seq_run_scored_nominated; sample = (num_to_find, start) on top of weights: the two sampled forms (rule F), "null": a NULL sample"""
         p, cap = self.pods_count(), max(self.g if cap is None else cap, 1)
         n = max(p, 1)
         pf, fk = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
@@ -667,7 +683,23 @@ class Context:
         lp = np.zeros(n, np.uint8)
         o = SeqOut(pf.ctypes.data_as(C.POINTER(C.c_uint8)), _u32p(fk), ld.ctypes.data_as(C.POINTER(C.c_int32)), node.ctypes.data_as(C.POINTER(C.c_int32)),
                    cap, _u32p(rg), _u32p(rp), _i64p(t0), _i64p(t1), 0, 0, 0, 0, 0, 0, 0, 0, lp.ctypes.data_as(C.POINTER(C.c_uint8)))
-        if weights is not None and nominated is not None and flat:
+        if sample is not None and flat:
+            sc = np.zeros(8, np.int64)
+            res = (o.pf_code, o.pf_first_k, o.pf_leader, o.pod_node, cap, o.released_group, o.released_pods, o.first_ns, o.ready_ns, _i64p(sc), o.last_permitted)
+            if nominated is not None:
+                self._chk(self._lib.bs_seq_run_scored_nominated_sampled_flat(self._h, stages, *nominated, *weights, *sample, *res), "bs_seq_run_scored_nominated_sampled_flat")
+            else:
+                self._chk(self._lib.bs_seq_run_scored_sampled_flat(self._h, stages, *weights, *sample, *res), "bs_seq_run_scored_sampled_flat")
+            (o.n_released, o.total_ns, o.node_picks, o.node_scans, o.scan_rounds, o.pick_rounds, o.leader_folds, o.table_builds) = (int(v) for v in sc)
+        elif sample is not None:
+            w = None if weights == "null" else SeqScore(*weights)
+            sm = None if sample == "null" else SeqSample(*sample)
+            wp, sp = (None if w is None else C.byref(w)), (None if sm is None else C.byref(sm))
+            if nominated is not None:
+                self._chk(self._lib.bs_seq_run_scored_nominated_sampled(self._h, stages, *nominated, wp, sp, C.byref(o)), "bs_seq_run_scored_nominated_sampled")
+            else:
+                self._chk(self._lib.bs_seq_run_scored_sampled(self._h, stages, wp, sp, C.byref(o)), "bs_seq_run_scored_sampled")
+        elif weights is not None and nominated is not None and flat:
             sc = np.zeros(8, np.int64)
             self._chk(self._lib.bs_seq_run_scored_nominated_flat(self._h, stages, *nominated, *weights, o.pf_code, o.pf_first_k, o.pf_leader, o.pod_node, cap,
                                                                  o.released_group, o.released_pods, o.first_ns, o.ready_ns, _i64p(sc), o.last_permitted),
@@ -744,6 +776,47 @@ class Context:
         most SCORE_WEIGHT_MAX; (0, 0, 0) is seq_run.  seq_score_read reports the chosen totals."""
         wl, wm, wb = (int(v) for v in weights)
         return self._seq_pass(stages, cap, None, flat, (wl, wm, wb))
+
+    @staticmethod
+    def _sample_arg(weights, sample, flat):
+        assert not ((weights is None or sample is None) and flat), "the flat forms have no NULL score and no NULL sample"
+        w = "null" if weights is None else tuple(int(v) for v in weights)
+        s = "null" if sample is None else tuple(int(v) & 0xFFFFFFFF for v in sample)
+        assert w == "null" or len(w) == 3
+        assert s == "null" or len(s) == 2
+        return w, s
+
+    def seq_run_scored_sampled(self, weights, sample, stages: int = soa.STAGE_PREFILTER, cap: int | None = None, flat: bool = False) -> dict:
+        """bs_seq_run_scored_sampled: seq_run_scored with upstream's node sampling (rule F).  sample = (num_to_find, start): the walk of
+        every pod starts at a cursor that rotates from pod to pod (the first at start mod N), stops behind num_to_find candidates (0 or
+        >= N: all) and scores those; ties go to the smallest visit position.  None for weights / sample: a NULL pointer (tests of the
+        refusals).  seq_score_read (n_fit = the candidates kept) and seq_sample_read answer for this pass."""
+        w, s = self._sample_arg(weights, sample, flat)
+        return self._seq_pass(stages, cap, None, flat, w, s)
+
+    def seq_run_scored_nominated_sampled(self, weights, sample, priority, own_id=None, stages: int = soa.STAGE_PREFILTER, cap: int | None = None,
+                                         p: int | None = None, flat: bool = False) -> dict:
+        """bs_seq_run_scored_nominated_sampled: seq_run_scored_nominated with rule F's walk over rule S's candidates.  sample as in
+        seq_run_scored_sampled, the other arguments as in seq_run_scored_nominated.  seq_score_read, seq_sample_read and
+        seq_nominated_read all answer for this pass."""
+        pr = None if priority is None else np.ascontiguousarray(np.asarray(priority, np.int32).reshape(-1))
+        ow = None if own_id is None else np.ascontiguousarray(np.asarray(own_id, np.uint32).reshape(-1))
+        n = self.pods_count() if p is None else int(p)
+        assert p is not None or ((pr is None or pr.size == n) and (ow is None or ow.size == n))
+        pp = None if pr is None else (pr if pr.size else np.zeros(1, np.int32)).ctypes.data_as(C.POINTER(C.c_int32))
+        op = None if ow is None else _u32p(ow if ow.size else np.zeros(1, np.uint32))
+        w, s = self._sample_arg(weights, sample, flat)
+        return self._seq_pass(stages, cap, (n, pp, op), flat, w, s)
+
+    def seq_sample_read(self, p: int | None = None) -> dict:
+        """bs_seq_sample_read: per queue pod of the last sampled pass the cursor its walk began at (0: the choice was not reached) and the
+        nodes it visited, and next_start, the cursor behind the last pod — the next pass's sample start.  p overrides the queue length
+        handed to the library (tests)."""
+        n = self.pods_count() if p is None else int(p)
+        start, visited = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        nxt = C.c_uint32(0)
+        self._chk(self._lib.bs_seq_sample_read(self._h, n, _u32p(start), _u32p(visited), C.byref(nxt)), "bs_seq_sample_read")
+        return dict(start=start[:n], visited=visited[:n], next_start=int(nxt.value))
 
     def seq_score_read(self, p: int | None = None) -> dict:
         """bs_seq_score_read: per queue pod of the last seq_run_scored the chosen node's total (0: no node) and n_fit, the number of nodes
@@ -1278,3 +1351,9 @@ def comm_unique_id() -> bytes:
     if rc != 0:
         raise BsError(rc, "bs_comm_unique_id")
     return bytes(buf)
+
+
+def seq_sample_size(n: int, percentage: int = 0) -> int:
+    """bs_seq_sample_size: upstream's numFeasibleNodesToFind (D9 of include/bsched.h) for n nodes under percentageOfNodesToScore = percentage
+    (0 or less: the adaptive default)."""
+    return int(load_library().bs_seq_sample_size(int(n), int(percentage)))

@@ -259,6 +259,10 @@ struct bs_ctx {
   DevBuf d_seq_score;
   bool seq_score_valid = false;
   uint32_t seq_score_p = 0;
+  // bs_seq_sample_read: start[P] | visited[P] | next_start of the last pass, valid while that pass was a successful sampled one (rule F) over
+  // seq_score_p pods; every other pass clears the flag
+  DevBuf d_seq_sample;
+  bool seq_sample_valid = false;
   DevBuf d_sexp;                     // per-call scratch: block totals, slots, rows, dirty list, records
   DevBuf d_sexp_nodes;               // per-node delta [L][N], key bits, dirty words: zero between calls (k_se_nodes re-zeroes what it read)
   uint32_t sexp_n = 0, sexp_l = 0;   // the layout d_sexp_nodes was zeroed for

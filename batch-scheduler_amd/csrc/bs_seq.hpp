@@ -37,6 +37,7 @@
 #include "bs_kernels.hpp"
 #include "bs_nom_view.hpp"
 #include "bs_seq_score.hpp"
+#include "bs_seq_sample.hpp"
 
 namespace bs {
 
@@ -160,6 +161,26 @@ struct SeqScore {
 struct SeqScoreShared {
   unsigned long long key[kSeqWaves];   // each wave's best candidate: total << 32 | (0xFFFFFFFF - node), 0 = none
   uint32_t nfit[kSeqWaves];            // candidates the wave counted
+};
+// bs_seq_run_scored_sampled / bs_seq_run_scored_nominated_sampled (include/bsched.h, rule F): what the sampled instantiations k_seq_sampled /
+// k_seq_sampled_nom get on top of SeqScore.  The node choice is an ORDERED walk from a cursor that rotates from pod to pod; it stops behind
+// the K-th candidate (at the (K+1)-th, which is not kept) and scores the K it kept.  See seq_pick_sampled.
+struct SeqSample {
+  uint32_t K;                    // nodes to find, normalised (sample_k): 1 .. N, N = every candidate
+  uint32_t s0;                   // the cursor of the first pod (sample_start)
+  uint32_t* start;               // [P] zeroed before the launch: the cursor the pod's walk began at
+  uint32_t* visited;             // [P] zeroed before the launch: V, the nodes the pod's walk visited
+  uint32_t* next;                // [1] zeroed before the launch: the cursor behind the last pod
+  uint32_t lds_off;              // byte offset of SeqSampleShared in dynamic LDS (behind SeqScoreShared)
+};
+// sampled-only LDS state, in the DYNAMIC part as SeqScoreShared is.  cnt[b][w]: the members of C wave w found in its tile of a round of parity
+// b — written by lane 0 of wave w in front of the round's barrier, read by every wave behind it; the next writer of the same word is wave w two
+// rounds later, behind the next round's barrier, which every reader of this round has reached by then.  vstop: the visit position of the
+// (K+1)-th member — written by lane 0 of the one wave whose tile holds it, in the round that stops the walk, read by every wave behind the
+// barrier of the block reduction that follows the walk.
+struct SeqSampleShared {
+  uint32_t cnt[2][kSeqWaves];
+  uint32_t vstop;
 };
 
 // the rows the fit test adds to node k for a pod of priority P (AddPod per row: all L lanes, wrapping)
@@ -1156,6 +1177,296 @@ __device__ __forceinline__ uint32_t seq_pick_scored(const NodesDev& nd, const Se
   return found;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The sampled node choice + the assume step (rule F; bs_seq_run_scored_sampled, and under NOM bs_seq_run_scored_nominated_sampled).
+// Upstream's findNodesThatFit does not look at every node: it walks the list from a cursor that rotates from pod to pod and stops once it has
+// K feasible nodes.  seq_pick_scored deals 64 tiles of a chunk to each wave and never stops; this is an ORDERED walk with a block-uniform
+// early stop.  The walk goes over SLOTS of 64 lanes in visit order: slot u is tile (t_s + u) mod ntiles, t_s the tile that holds the cursor
+// s; when s is not a tile's first node that tile has two slots — slot 0 with the lanes from s & 63 on, and one more slot behind the
+// last tile with the lanes in front of it.  Inside a slot the lane order is the visit order, from slot to slot the visit position grows.
+// A ROUND is kSeqWaves consecutive slots, wave w takes slot kSeqWaves * r + w.  Per round every wave tests its tile (seq_pick_scored's fit
+// test, word for word, the lean form included), publishes the number of members it found (SeqSampleShared::cnt, double-buffered by round
+// parity), and behind ONE lds_barrier every wave forms, from the same kSeqWaves words, the members in front of its own slot and the round's
+// total.  A lane keeps its candidate only if its rank (1-based, in visit order) is at most K.  The walk stops in the round whose total
+// takes the count past K: the wave whose slot holds the (K+1)-th member finds its lane (the r-th set bit of its ballot) and publishes that
+// member's visit position V; without a stop V = N.  The stop is decided by every wave from the same LDS words behind the same barrier, so
+// every wave runs the same number of rounds and reaches every barrier.  The per-tile bounds still skip tiles — a tile they exclude holds no
+// member, so neither the kept set nor V moves —, and a tile looked at in vain is tightened only when all of it was visited.
+// The key is total << 32 | (0xFFFFFFFF - visit position): the largest total, then the smallest visit position; the reduction and the assume
+// step are seq_pick_scored's.  Returns the node (BS_INF none), wave-uniform, identical in every wave; total_out, nfit_out (= |C'|) and
+// visited_out (= V) likewise.  With K = N and s = 0 the visit position is the node index and nothing stops: the choice is seq_pick_scored's.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int TS, bool NOM>
+__device__ __forceinline__ uint32_t seq_pick_sampled(const NodesDev& nd, const SeqDev& sq, const SeqParams& prm, SeqShared& sh_, SeqScoreShared& ss, SeqSampleShared& sm,
+                                                     const SeqPick& q, const SeqScore& sco, uint32_t K, uint32_t s, const uint32_t (&slot_key)[kSeqCacheSlots],
+                                                     bool drained, SeqAssumed& out, unsigned long long& tiles_looked, uint32_t& total_out, uint32_t& nfit_out,
+                                                     uint32_t& visited_out, uint32_t pw, const SeqPickNom& pn) {
+  const Shape<TS> sh(prm.S);
+  const uint32_t L = sh.L(), S = sh.S();
+  constexpr bool kLean = TS > kSeqScoredFullLanes;           // (see seq_pick_scored)
+  auto preq_s = [&](uint32_t j) -> int64_t {
+    if constexpr (kLean) return sh_.pw_req[j][pw]; else return q.preq[j];
+  };
+  const int lane = lane_id(), w = (int)uni32((uint32_t)wave_id());
+  const uint32_t N = nd.n;
+  out.ap = out.rp = out.fitbits = 0;
+  total_out = 0;
+  nfit_out = 0;
+  visited_out = N;                                                          // no stop, and the two early exits below: C is empty, the walk saw every node
+  if (!drained) __syncthreads();                                            // the assume steps of earlier pods have landed before a tile is read
+  if (!N || q.pcls >= nd.n_classes || q.fl >= 16u) return BS_INF;          // (ERR_PG_NOT_FOUND / the nil-leader panic: Filter fails everywhere)
+  const bool fl_all = q.fl != BS_FL_EVALUATED;                              // Filter passes on every node
+  const uint32_t ntiles = (N + 63u) >> 6;
+  const uint32_t* fitrow = nd.fit + (size_t)q.pcls * nd.fit_words;
+  const uint32_t ts = s >> 6, off = s & 63u;                                // the cursor's tile and lane
+  const uint32_t slots = ntiles + (off ? 1u : 0u), rounds = (slots + (uint32_t)kSeqWaves - 1u) / (uint32_t)kSeqWaves;
+  unsigned long long best = 0ull;                                           // this lane's best KEPT candidate and its node's values
+  int64_t b_al[BS_MAX_LANES], b_rq[BS_MAX_LANES], b_l07[BS_MAX_LANES], b_l10[BS_MAX_LANES];
+#pragma unroll
+  for (uint32_t j = 0; j < BS_MAX_LANES; ++j) { b_al[j] = 0; b_rq[j] = 0; b_l07[j] = 0; b_l10[j] = 0; }
+  uint32_t b_ap = 0, b_rp = 0, b_fbits = 0, b_meta = 0;
+  uint32_t base = 0;                                                        // members of C in front of the round (block-uniform)
+  bool stop = false;                                                        // the (K+1)-th member has been met (block-uniform)
+  for (uint32_t r = 0; r < rounds && !stop; ++r) {
+    const uint32_t b = r & 1u;
+    const uint32_t u = r * (uint32_t)kSeqWaves + (uint32_t)w;               // this wave's slot
+    const bool in_walk = u < slots;
+    uint32_t tile = in_walk ? ts + u : 0u;
+    if (tile >= ntiles) tile -= ntiles;                                     // (u <= ntiles, ts < ntiles: one subtraction)
+    const bool head = off != 0u && u == 0u, tail = u == ntiles;             // the two visits of the cursor's tile (a tail slot exists only with off != 0)
+    bool cand = in_walk;
+    if (cand && prm.prune) {
+      cand = !(q.preq[0] > 0 && sh_.pmax[0][tile] < q.preq[0]) && !(q.preq[1] > 0 && sh_.pmax[1][tile] < q.preq[1]);
+      if (q.preq[0] > 0 && q.preq[1] > 0) cand = cand && !(sh_.pmax[2][tile] < seq_joint(q.preq[0], q.preq[1]));
+    }
+    cand = __ballot(cand) != 0ull;                                          // (wave-uniform by construction; said to the compiler)
+    bool ok = false;
+    uint32_t n = 0, ap = 0, rp = 0, fbits = 0, meta = 0;
+    int64_t al[BS_MAX_LANES], rq[BS_MAX_LANES], l07[BS_MAX_LANES], l10[BS_MAX_LANES];
+#pragma unroll
+    for (uint32_t j = 0; j < BS_MAX_LANES; ++j) { al[j] = 0; rq[j] = 0; l07[j] = 0; l10[j] = 0; }
+    unsigned long long m = 0ull;
+    if (cand) {
+      tiles_looked++;
+      n = (tile << 6) + (uint32_t)lane;
+      const bool valid = n < N;
+      const uint32_t nn = valid ? n : N - 1u;
+      const uint32_t fl = nd.flags[nn];
+      ap = nd.apres[nn];
+      rp = sq.rpres[nn];
+      const uint32_t fw = fitrow[nn >> 5];
+      uint32_t fws[kSeqCacheSlots];
+#pragma unroll
+      for (uint32_t c = 0; c < kSeqCacheSlots; ++c)
+        fws[c] = (c < prm.cache_slots && slot_key[c] != BS_INF) ? nd.fit[(size_t)(slot_key[c] >> 1) * nd.fit_words + (nn >> 5)] : 0u;
+#pragma unroll
+      for (uint32_t j = 0; j < BS_MAX_LANES; ++j) {
+        if (j < L) {
+          al[j] = nd.alloc[(size_t)j * nd.stride + nn];
+          rq[j] = sq.nreq[(size_t)j * nd.stride + nn];
+          if constexpr (!kLean) {
+            l07[j] = sq.left07[(size_t)j * nd.stride + nn];     // (for the assume step: no second round trip behind the decision)
+            l10[j] = sq.left10[(size_t)j * nd.stride + nn];
+          }
+        }
+      }
+      meta = sq.nmeta[nn];
+#pragma unroll
+      for (uint32_t c = 0; c < kSeqCacheSlots; ++c) fbits |= ((fws[c] >> (nn & 31u)) & 1u) << c;
+      const bool sched = valid && fl == 0u;
+      ok = sched && ((fw >> (nn & 31u)) & 1u);
+      const int64_t f0 = wsub(al[0], rq[0]), f1 = wsub(al[1], rq[1]);
+      if (!fl_all) {                                         // computeResourceSatisfied on this node (core.go:545-563)
+        bool c2 = !(q.ff & 1u), c3h = !(q.ff & 2u);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int64_t left = wsub(al[j], rq[j]);                                                   // getLeftResource :460-463
+          c2 = c2 && left >= q.FR[j];
+          c3h = c3h && left >= q.FM[j];
+        }
+        ok = ok && (c2 || !c3h);                                                                     // case 2 | case 3
+      }
+      bool plain = true;                                     // the node has no row chain: the flag-less fit test
+      if constexpr (NOM) {
+        const uint32_t head_r = (valid && pn.nom->view) ? pn.nom->view->nhead[nn] : kNmNone;
+        if (head_r != kNmNone) {                             // rule S: requests plus the live rows the pod sees (a LOCAL sum; the score below stays raw)
+          plain = false;
+          const NomView nm = *pn.nom->view;
+          if constexpr (!kLean) {
+            int64_t add[BS_MAX_LANES];
+#pragma unroll
+            for (uint32_t j = 0; j < BS_MAX_LANES; ++j) add[j] = 0;
+            seq_nominees<TS>(nm, pn.nom->consumed, head_r, pn.prio, pn.own, sh, add);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) ok = ok && !(q.preq[j] > 0 && q.preq[j] > wsub(al[j], wadd(rq[j], add[j])));
+            ok = ok && !(wadd(wadd(rq[3], add[3]), 1) > al[3]);
+#pragma unroll
+            for (uint32_t s2 = 0; s2 < BS_MAX_SCALARS; ++s2) {
+              if (s2 < S && ((q.ppres >> s2) & 1u) && q.preq[4 + s2] > 0) {
+                const int64_t r0 = wadd(((rp >> s2) & 1u) ? rq[4 + s2] : 0, add[4 + s2]);
+                ok = ok && ((ap >> s2) & 1u) && !(q.preq[4 + s2] > wsub(al[4 + s2], r0));
+              }
+            }
+          } else {
+            // one walk of the chain per lane the pod asks for (the pods lane always): chains are short and rows are rare
+#pragma unroll
+            for (uint32_t j = 0; j < BS_MAX_LANES; ++j) {
+              if (j < L) {
+                const int64_t pr = j < 4 ? q.preq[j] : preq_s(j);
+                const bool asks = j == 3 || (pr > 0 && (j < 3 || ((q.ppres >> (j - 4)) & 1u)));
+                if (asks) {
+                  const int64_t add = seq_nominees_lane(nm, pn.nom->consumed, head_r, pn.prio, pn.own, j);
+                  if (j < 3) ok = ok && !(pr > wsub(al[j], wadd(rq[j], add)));
+                  else if (j == 3) ok = ok && !(wadd(wadd(rq[3], add), 1) > al[3]);
+                  else {
+                    const int64_t r0 = wadd(((rp >> (j - 4)) & 1u) ? rq[j] : 0, add);
+                    ok = ok && ((ap >> (j - 4)) & 1u) && !(pr > wsub(al[j], r0));
+                  }
+                }
+              }
+            }
+          }
+        }
+      }
+      if (plain) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) ok = ok && !(q.preq[j] > 0 && q.preq[j] > wsub(al[j], rq[j]));
+      ok = ok && !(wadd(rq[3], 1) > al[3]);
+#pragma unroll
+      for (uint32_t s2 = 0; s2 < BS_MAX_SCALARS; ++s2) {
+        if (s2 < S && ((q.ppres >> s2) & 1u) && preq_s(4 + s2) > 0) {
+          const int64_t r0 = ((rp >> s2) & 1u) ? rq[4 + s2] : 0;
+          ok = ok && ((ap >> s2) & 1u) && !(preq_s(4 + s2) > wsub(al[4 + s2], r0));
+        }
+      }
+      }
+      const unsigned long long all = __ballot(ok);           // over every valid lane of the tile: what "looked at in vain" means
+      if (head) ok = ok && (uint32_t)lane >= off;            // the cursor's tile, first visit: the lanes from the cursor on
+      if (tail) ok = ok && (uint32_t)lane < off;             // ... and its second, at the end of the walk: the lanes in front of it
+      m = __ballot(ok);
+      if (!all && !head && !tail && prm.prune && !((sh_.tight[tile >> 5] >> (tile & 31u)) & 1u)) {   // looked at in vain: tighten the tile's bounds to what is really there
+        const long long m0 = readlane63_i64(wave_max_i64_lane63(sched ? (long long)f0 : INT64_MIN));
+        const long long m1 = readlane63_i64(wave_max_i64_lane63(sched ? (long long)f1 : INT64_MIN));
+        const long long m2 = readlane63_i64(wave_max_i64_lane63(sched ? seq_joint(f0, f1) : INT64_MIN));
+        if constexpr (NOM) {                                 // (not a wild tile's: its bounds stay open, see the prologue of the pass)
+          if (lane == 0 && !((pn.ns->wild[tile >> 5] >> (tile & 31u)) & 1u)) { sh_.pmax[0][tile] = m0; sh_.pmax[1][tile] = m1; sh_.pmax[2][tile] = m2; atomicOr(&sh_.tight[tile >> 5], 1u << (tile & 31u)); }
+        } else {
+          if (lane == 0) { sh_.pmax[0][tile] = m0; sh_.pmax[1][tile] = m1; sh_.pmax[2][tile] = m2; atomicOr(&sh_.tight[tile >> 5], 1u << (tile & 31u)); }
+        }
+      }
+    }
+    // ---- the count exchange: the members in front of this wave's slot, and the round's total
+    const uint32_t cw = sample_popc64(m);
+    if (lane == 0) sm.cnt[b][w] = cw;
+    lds_barrier();
+    uint32_t before = base, round_total = 0;
+#pragma unroll
+    for (int x = 0; x < kSeqWaves; ++x) {
+      const uint32_t c = sm.cnt[b][x];
+      if (x < w) before += c;
+      round_total += c;
+    }
+    before = uni32(before);
+    round_total = uni32(round_total);
+    if (ok) {                                                // rule F: the first K members in visit order are kept, the rest is not
+      const uint32_t rank = before + sample_popc64(m & ((1ull << lane) - 1ull)) + 1u;
+      if (rank <= K) {                                       // rule P on the kept: R = requested + request (wrapping), cpu and memory only
+        const uint32_t total = score_total(al[0], score_wadd(rq[0], q.preq[0]), al[1], score_wadd(rq[1], q.preq[1]), sco.w_least, sco.w_most, sco.w_balanced);
+        const unsigned long long key = ((unsigned long long)total << 32) | (unsigned long long)(0xFFFFFFFFu - sample_pos(s, n, N));
+        if (key > best) {
+          best = key;
+          if constexpr (!kLean) {
+#pragma unroll
+            for (uint32_t j = 0; j < BS_MAX_LANES; ++j) { b_al[j] = al[j]; b_rq[j] = rq[j]; b_l07[j] = l07[j]; b_l10[j] = l10[j]; }
+          }
+          b_ap = ap; b_rp = rp; b_fbits = fbits; b_meta = meta;
+        }
+      }
+    }
+    // ---- the stop: the same words, the same arithmetic, in every wave
+    stop = round_total > K - base;                           // (base <= K while the walk goes on)
+    if (stop && before <= K && K - before < cw) {            // this wave's slot holds the (K+1)-th member: it is not kept, the walk ends in front of it
+      const uint32_t ln = sample_nth_bit(m, K - before + 1u);
+      if (lane == 0) sm.vstop = sample_pos(s, (tile << 6) + ln, N);
+    }
+    base += round_total;
+  }
+  // ---- the wave's best (one lane owns it: the visit position is part of the key), then the block's
+  const unsigned long long wbest = wave_max_u64_all(best);
+  const bool owner = best != 0ull && best == wbest;
+  if (owner) { ss.key[w] = best; sh_.asm_ap[0][w] = b_ap; sh_.asm_rp[0][w] = b_rp; sh_.asm_fit[0][w] = b_fbits; }
+  if (lane == 0 && wbest == 0ull) ss.key[w] = 0ull;
+  lds_barrier();
+  unsigned long long top = 0ull;
+  uint32_t ww = 0;
+#pragma unroll
+  for (int x = 0; x < kSeqWaves; ++x) {
+    const unsigned long long k = ss.key[x];
+    if (k > top) { top = k; ww = (uint32_t)x; }
+  }
+  top = uni64(top);
+  ww = uni32(ww);
+  nfit_out = stop ? K : base;
+  if (stop) visited_out = uni32(sm.vstop);
+  if (top == 0ull) return BS_INF;
+  const uint32_t found = sample_node(s, 0xFFFFFFFFu - (uint32_t)top, N);
+  total_out = (uint32_t)(top >> 32);
+  out.ap = sh_.asm_ap[0][ww]; out.rp = sh_.asm_rp[0][ww]; out.fitbits = sh_.asm_fit[0][ww];
+  if (owner && best == top) {
+    // ---- assume (NodeInfo.AddPod): requested += request, pods lane + 1; the left arrays and the meta word follow
+    const uint32_t at = found;
+    if constexpr (kLean) {
+#pragma unroll
+      for (uint32_t j = 0; j < BS_MAX_LANES; ++j) {
+        if (j < L) {
+          b_al[j] = nd.alloc[(size_t)j * nd.stride + at];
+          b_rq[j] = sq.nreq[(size_t)j * nd.stride + at];
+          b_l07[j] = sq.left07[(size_t)j * nd.stride + at];
+          b_l10[j] = sq.left10[(size_t)j * nd.stride + at];
+        }
+      }
+    }
+    uint32_t nrp = b_rp;
+#pragma unroll
+    for (uint32_t j = 0; j < BS_MAX_LANES; ++j) {
+      if (j < L) {
+        int64_t nr = b_rq[j];
+        bool touched = false;
+        if (j < 3) { nr = wadd(b_rq[j], q.preq[j]); touched = true; }
+        else if (j == 3) { nr = wadd(b_rq[j], 1); touched = true; }
+        else if ((q.ppres >> (j - 4)) & 1u) {
+          nr = wadd(((b_rp >> (j - 4)) & 1u) ? b_rq[j] : 0, preq_s(j));
+          nrp |= 1u << (j - 4);
+          touched = true;
+        }
+        if (touched) {
+          sq.nreq[(size_t)j * nd.stride + at] = nr;
+          if (j < 4 || ((b_rp >> (j - 4)) & 1u)) {             // left = scaled allocatable - requested: it moves by what requested moves by
+            const int64_t dlt = wsub(nr, b_rq[j]);
+            sq.left07[(size_t)j * nd.stride + at] = wsub(b_l07[j], dlt);
+            sq.left10[(size_t)j * nd.stride + at] = wsub(b_l10[j], dlt);
+          } else {                                             // a scalar key the node's requests did not have: the lane starts to exist
+            sq.left07[(size_t)j * nd.stride + at] = wsub(scale_f32(b_al[j], 0.7f), nr);
+            sq.left10[(size_t)j * nd.stride + at] = wsub(scale_f32(b_al[j], 1.0f), nr);
+          }
+        }
+      }
+    }
+    if (nrp != b_rp) {
+      sq.rpres[at] = nrp;
+      sq.nmeta[at] = (b_meta & 0xFu) | ((b_ap & nrp) << 4);
+    }
+    if (prm.prune) {                                       // a negative request frees capacity: the bounds must stay upper bounds
+      const int64_t n0 = wsub(b_al[0], wadd(b_rq[0], q.preq[0])), n1 = wsub(b_al[1], wadd(b_rq[1], q.preq[1]));
+      if (n0 > sh_.pmax[0][at >> 6]) sh_.pmax[0][at >> 6] = n0;
+      if (n1 > sh_.pmax[1][at >> 6]) sh_.pmax[1][at >> 6] = n1;
+      if (seq_joint(n0, n1) > sh_.pmax[2][at >> 6]) sh_.pmax[2][at >> 6] = seq_joint(n0, n1);
+      atomicAnd(&sh_.tight[at >> 11], ~(1u << ((at >> 6) & 31u)));     // the node that held a maximum may be the one that just filled up
+    }
+  }
+  return found;
+}
+
 // findMaxPG (core.go:701-739) over the keys.  Wave-uniform result: leader (-1 none), panic.
 __device__ __forceinline__ void seq_find_max(const GroupsDev& gr, const SeqDev& sq, const SeqParams& prm, SeqShared& sh_, const unsigned long long* lkeys,
                                              int32_t& leader, bool& panic, unsigned long long& top_out) {
@@ -1281,9 +1592,10 @@ __device__ __forceinline__ void seq_group_zero(SeqGroup& o, Shape<TS> sh) {
 // lanes_narrow), name and arguments as they always were.
 template <int TS>
 __global__ __launch_bounds__(kSeqBlock, 1) void k_seq_pass(PodsDev pods, GroupsDev gr, NodesDev nd, SeqDev sq, SeqParams prm) {
-  constexpr bool NOM = false, SCORE = false;
+  constexpr bool NOM = false, SCORE = false, SAMPLE = false;
   const SeqNom nom{};                                        // (named by the discarded NOM-only lines)
   const SeqScore sco{};                                      // (... and by the discarded SCORE-only ones)
+  const SeqSample smp{};                                     // (... and by the discarded SAMPLE-only ones)
 #include "bs_seq_pass.inc"
 }
 // bs_seq_run_nominated's: k_seq_pass<TS, true>, rule S on top, the same six lane counts (an overload: a defaulted second parameter would
@@ -1291,8 +1603,9 @@ __global__ __launch_bounds__(kSeqBlock, 1) void k_seq_pass(PodsDev pods, GroupsD
 template <int TS, bool NOM>
 __global__ __launch_bounds__(kSeqBlock, 1) void k_seq_pass(PodsDev pods, GroupsDev gr, NodesDev nd, SeqDev sq, SeqParams prm, SeqNom nom) {
   static_assert(NOM, "the flag-less pass is k_seq_pass<TS>");
-  constexpr bool SCORE = false;
+  constexpr bool SCORE = false, SAMPLE = false;
   const SeqScore sco{};
+  const SeqSample smp{};
 #include "bs_seq_pass.inc"
 }
 // bs_seq_run_scored's: the third inclusion, rule P in the node choice (SCORE = true, NOM = false); emitted by tu_seq_score.hip.  It reads and
@@ -1303,8 +1616,9 @@ __global__ __launch_bounds__(kSeqBlock, 1) void k_seq_pass(PodsDev pods, GroupsD
 template <int TS>
 __global__ __launch_bounds__(kSeqBlock, 1) void k_seq_scored(PodsDev pods, GroupsDev gr, NodesDev nd, SeqDev sq, SeqParams prm, SeqScore sco) {
   static_assert(TS >= 0, "the scored pass has fixed-lane instantiations only");
-  constexpr bool NOM = false, SCORE = true;
+  constexpr bool NOM = false, SCORE = true, SAMPLE = false;
   const SeqNom nom{};
+  const SeqSample smp{};
 #include "bs_seq_pass.inc"
 }
 // bs_seq_run_scored_nominated's: the fourth inclusion, rules S and P at once (rule SP: NOM = true, SCORE = true); emitted by
@@ -1313,9 +1627,34 @@ __global__ __launch_bounds__(kSeqBlock, 1) void k_seq_scored(PodsDev pods, Group
 template <int TS>
 __global__ __launch_bounds__(kSeqBlock, 1) void k_seq_sp(PodsDev pods, GroupsDev gr, NodesDev nd, SeqDev sq, SeqParams prm, SeqNom nom, SeqScore sco) {
   static_assert(TS >= 0, "the scored pass has fixed-lane instantiations only");
-  constexpr bool NOM = true, SCORE = true;
+  constexpr bool NOM = true, SCORE = true, SAMPLE = false;
+  const SeqSample smp{};
 #include "bs_seq_pass.inc"
 }
+// bs_seq_run_scored_sampled's: the fifth inclusion, rule F over rule P (SCORE = true, SAMPLE = true: the node choice is seq_pick_sampled); emitted
+// by tu_seq_sample.hip.  The same thirteen lane counts as k_seq_scored, lean above kSeqScoredFullLanes, no generic-lane one.  The name holds
+// none of k_seq_pass, k_seq_scored, k_seq_sp: the kernel lists that count those families by name stay what they were.
+template <int TS>
+__global__ __launch_bounds__(kSeqBlock, 1) void k_seq_sampled(PodsDev pods, GroupsDev gr, NodesDev nd, SeqDev sq, SeqParams prm, SeqScore sco, SeqSample smp) {
+  static_assert(TS >= 0, "the sampled pass has fixed-lane instantiations only");
+  constexpr bool NOM = false, SCORE = true, SAMPLE = true;
+  const SeqNom nom{};
+#include "bs_seq_pass.inc"
+}
+// bs_seq_run_scored_nominated_sampled's: the sixth inclusion, rule F over rule SP (all three flags); emitted by tu_seq_sample_nom.hip
+template <int TS>
+__global__ __launch_bounds__(kSeqBlock, 1) void k_seq_sampled_nom(PodsDev pods, GroupsDev gr, NodesDev nd, SeqDev sq, SeqParams prm, SeqNom nom, SeqScore sco,
+                                                                  SeqSample smp) {
+  static_assert(TS >= 0, "the sampled pass has fixed-lane instantiations only");
+  constexpr bool NOM = true, SCORE = true, SAMPLE = true;
+#include "bs_seq_pass.inc"
+}
+// the launch of k_seq_sampled<TS> for S scalar lanes (defined in tu_seq_sample.hip; called by tu_seq.hip)
+void launch_seq_sampled(hipStream_t stream, uint32_t S, size_t lds, const PodsDev& pd, const GroupsDev& gr, const NodesDev& nd, const SeqDev& sq, const SeqParams& prm,
+                        const SeqScore& sco, const SeqSample& smp);
+// the launch of k_seq_sampled_nom<TS> for S scalar lanes (defined in tu_seq_sample_nom.hip; called by tu_seq.hip)
+void launch_seq_sampled_nominated(hipStream_t stream, uint32_t S, size_t lds, const PodsDev& pd, const GroupsDev& gr, const NodesDev& nd, const SeqDev& sq,
+                                  const SeqParams& prm, const SeqNom& nom, const SeqScore& sco, const SeqSample& smp);
 // the launch of k_seq_sp<TS> for S scalar lanes (defined in tu_seq_score_nom.hip; called by tu_seq.hip)
 void launch_seq_scored_nominated(hipStream_t stream, uint32_t S, size_t lds, const PodsDev& pd, const GroupsDev& gr, const NodesDev& nd, const SeqDev& sq,
                                  const SeqParams& prm, const SeqNom& nom, const SeqScore& sco);

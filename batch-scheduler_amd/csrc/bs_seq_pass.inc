@@ -1,7 +1,9 @@
 // bs_seq_pass.inc — the body of k_seq_pass (bs_seq.hpp), included once by each of its four kernel templates: k_seq_pass<TS> (bs_seq_run) with
 // `constexpr bool NOM = false`, k_seq_pass<TS, true> (bs_seq_run_nominated, rule S) with NOM = true and the kernel argument `nom`,
 // k_seq_scored<TS> (bs_seq_run_scored, rule P) with SCORE = true and the kernel argument `sco`, k_seq_sp<TS>
-// (bs_seq_run_scored_nominated, rule SP) with both flags and both arguments.  Every NOM-only line sits behind
+// (bs_seq_run_scored_nominated, rule SP) with both flags and both arguments; and by the two sampled templates k_seq_sampled<TS> and
+// k_seq_sampled_nom<TS> (rule F over rule P and over rule SP) with SCORE and SAMPLE = true and the kernel argument `smp`; every
+// sampled-only line sits behind `if constexpr (SAMPLE)`.  Every NOM-only line sits behind
 // `if constexpr (NOM)`, every scored-only line behind `if constexpr (SCORE)`; what the scored pass must not touch (the first-fit cursors,
 // `mono`) behind `if constexpr (!SCORE)`.  A shared __device__ function would be the usual form; the flag-less kernels then come
 // out as other instructions than before (inlining a by-reference body is not the same input to the optimiser), and bs_seq_run's kernels
@@ -127,6 +129,8 @@
   for (uint32_t c = 0; c < kSeqCacheSlots; ++c) { slot_key[c] = BS_INF; slot_age[c] = 0; }
   if constexpr (!SCORE)
   for (uint32_t e = threadIdx.x; e < kSeqCursors; e += kSeqBlock) { sh_.cur_kn[e] = 0ull; sh_.cur_fc[e] = 0u; }   // (ordered by the barrier in front of the loop)
+  uint32_t smp_cur = 0;                                      // rule F: the cursor of the next walk, wave-uniform and the same in every wave
+  if constexpr (SAMPLE) smp_cur = smp.s0;
   uint32_t hit_par = 0;                                      // which of the two early-stop words the next search uses
   bool mono = true;                                          // no assumed request has freed capacity so far: the first-fit cursors hold
   bool stores_pending = true;                                // an assume step (or the prologue) stored node state nobody has waited for yet
@@ -436,6 +440,21 @@
       if constexpr (SCORE) {
         // rule P: the candidate with the largest total, ties to the lowest index — a full search, so no cursor and no `mono`
         uint32_t sc_total = 0, sc_nfit = 0;
+        if constexpr (SAMPLE) {
+          // rule F: the candidates of the form underneath (rule P's, or rule S's under NOM), walked in visit order from the cursor; the first K
+          // are kept and scored, the walk ends at the (K+1)-th; the cursor moves by the nodes visited.  D6's consume as in rule SP.
+          SeqPickNom pn{};
+          if constexpr (NOM) { pn.nom = &nom; pn.ns = ns; pn.prio = (int32_t)uni32((uint32_t)ns->pw_prio[pw]); pn.own = uni32(ns->pw_own[pw]); }
+          uint32_t sm_visited = 0;
+          at = seq_pick_sampled<TS, NOM>(nd, sq, prm, sh_, *reinterpret_cast<SeqScoreShared*>(reinterpret_cast<unsigned char*>(s_keys) + sco.lds_off),
+                                         *reinterpret_cast<SeqSampleShared*>(reinterpret_cast<unsigned char*>(s_keys) + smp.lds_off), q, sco, smp.K, smp_cur, slot_key,
+                                         drained || !stores_pending, as, n_tiles, sc_total, sc_nfit, sm_visited, pw, pn);
+          if constexpr (NOM) {
+            if (at != BS_INF && pn.own != kNmNone && t0) { nom.consumed[pn.own] = 1; nom.c_pod[pn.own] = i; nom.c_node[pn.own] = at; }
+          }
+          if (threadIdx.x == kSeqResultThread) { smp.start[i] = smp_cur; smp.visited[i] = sm_visited; }
+          smp_cur = sample_step(smp_cur, sm_visited, N);     // (every wave holds the cursor: V is block-uniform)
+        } else
         if constexpr (NOM) {
           // rule SP: rule S decides the candidates, rule P the choice among them (raw lanes, D8), D6 the consume behind it
           SeqPickNom pn{};
@@ -648,6 +667,9 @@
     BS_SEQ_P(16);
   }
   BS_SEQ_FULL_BARRIER();
+  if constexpr (SAMPLE) {
+    if (threadIdx.x == kSeqResultThread) smp.next[0] = smp_cur;      // the cursor behind the last pod: the caller hands it to the next pass
+  }
   if (t0) {
     sq.info[0] = n_released;
     sq.info[1] = (unsigned long long)wall_clock64() - clk0;

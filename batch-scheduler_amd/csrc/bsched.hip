@@ -33,6 +33,8 @@
 #include "tu_seq_nom.hip"
 #include "tu_seq_score.hip"
 #include "tu_seq_score_nom.hip"
+#include "tu_seq_sample.hip"
+#include "tu_seq_sample_nom.hip"
 #include "tu_seq_expire.hip"
 #include "tu_wait.hip"
 #include "tu_groups.hip"

@@ -1,8 +1,9 @@
 // tu_seq.hip — translation unit of the sequential pass: its kernel (bs_seq.hpp: k_seq_pass<TS>, six instantiations; k_seq_pass<TS, true>, the
 // same six under rule S, are emitted by tu_seq_nom.hip, k_seq_scored<TS>, the thirteen under rule P, by tu_seq_score.hip, k_seq_sp<TS>,
-// the thirteen under rule SP, by tu_seq_score_nom.hip), the file-local launch wrapper and the entry points bs_seq_run, bs_seq_run_nominated,
-// bs_seq_run_scored and bs_seq_run_scored_nominated (include/bsched.h) with their flat forms,
-// bs_seq_nominated_read and bs_seq_score_read; see tu_fast.hip for why.  The nominated-pod table is reached through bs_ctx.hpp's declarations
+// the thirteen under rule SP, by tu_seq_score_nom.hip, k_seq_sampled<TS> and k_seq_sampled_nom<TS>, the two families under rule F, by
+// tu_seq_sample.hip and tu_seq_sample_nom.hip), the file-local launch wrapper and the entry points bs_seq_run, bs_seq_run_nominated,
+// bs_seq_run_scored, bs_seq_run_scored_nominated and the two sampled forms (include/bsched.h) with their flat forms,
+// bs_seq_nominated_read, bs_seq_score_read and bs_seq_sample_read; see tu_fast.hip for why.  The nominated-pod table is reached through bs_ctx.hpp's declarations
 // (tu_nominated.hip defines them): this unit does not include bs_nominated.hpp and emits no k_nm_* kernel.
 #ifndef BS_UNITY
 #define BS_TU_FAMILY
@@ -47,8 +48,10 @@ static int seq_refusals(bs_ctx* c, uint32_t stages) {
 
 }  // namespace bs
 
-// bs_seq_run's body behind the refusals above; nc: null = no table (bs_seq_run), else rule S; score: null = first fit, else rule P
-static int seq_run_impl(bs_ctx* c, uint32_t stages, bs_seq_out* out, const SeqNomCall* nc, const bs_seq_score* score = nullptr) {
+// bs_seq_run's body behind the refusals above; nc: null = no table (bs_seq_run), else rule S; score: null = first fit, else rule P; sample (with
+// score only): null = the full search, else rule F
+static int seq_run_impl(bs_ctx* c, uint32_t stages, bs_seq_out* out, const SeqNomCall* nc, const bs_seq_score* score = nullptr,
+                        const bs_seq_sample* sample = nullptr) {
   int rc = use_device(c);
   if (rc) return rc;
   if ((rc = settle_pending(c))) return rc;
@@ -61,6 +64,7 @@ static int seq_run_impl(bs_ctx* c, uint32_t stages, bs_seq_out* out, const SeqNo
   c->seq_wait_valid = false;                                // the pass replaces the waiting state
   c->seq_nom_valid = false;                                 // ... and is the context's last pass
   c->seq_score_valid = false;
+  c->seq_sample_valid = false;
   // the first-fit cursors are keyed by the resident queue's request classes: a queue patch whose insert wave ran out of class ids
   // (kHiIdOverflow of h_info, set by the device) left them unusable until the queue is re-derived — check_handover does that
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -149,7 +153,8 @@ static int seq_run_impl(bs_ctx* c, uint32_t stages, bs_seq_out* out, const SeqNo
   {
     // table summaries: as many slots as the CU's LDS holds behind the static arrays and the key window (one thread per tile: <= 1024 tiles)
     const size_t T = cdiv(N, 64), per_slot = T * ((size_t)L * 24 + 8), query = 0;
-    const size_t budget = (size_t)160 * 1024 - sizeof(SeqShared) - 2048 - (nc ? align256(sizeof(SeqNomShared)) : 0) - (score ? align256(sizeof(SeqScoreShared)) : 0);
+    const size_t budget = (size_t)160 * 1024 - sizeof(SeqShared) - 2048 - (nc ? align256(sizeof(SeqNomShared)) : 0) - (score ? align256(sizeof(SeqScoreShared)) : 0) -
+                          (sample ? align256(sizeof(SeqSampleShared)) : 0);
     uint32_t K = 0;
     if (T && T <= (size_t)kSeqPruneTiles && budget > lds + query + per_slot) K = (uint32_t)std::min<size_t>(kSeqCacheSlots, (budget - lds - query) / per_slot);
     if (score && c->S > (uint32_t)kSeqScoredFullLanes) K = 0;   // (the lean scored kernels keep no table summaries: bs_seq_pass.inc)
@@ -193,9 +198,26 @@ static int seq_run_impl(bs_ctx* c, uint32_t stages, bs_seq_out* out, const SeqNo
     sco.lds_off = (uint32_t)lds;
     lds += align256(sizeof(SeqScoreShared));
   }
+  SeqSample smp{};
+  if (sample) {
+    // rule F: K and the first cursor, normalised; the two per-pod result arrays and the cursor behind the last pod (context-owned, zero
+    // where the choice is not reached)
+    const size_t words = 2 * nP + 1;
+    HIPCHK(c, c->d_seq_sample.reserve(words * sizeof(uint32_t)));
+    HIPCHK(c, hipMemsetAsync(c->d_seq_sample.p, 0, words * sizeof(uint32_t), c->stream));
+    smp.K = sample_k(sample->num_to_find, N);
+    smp.s0 = sample_start(sample->start, N);
+    smp.start = c->d_seq_sample.as<uint32_t>();
+    smp.visited = smp.start + nP;
+    smp.next = smp.start + 2 * nP;
+    smp.lds_off = (uint32_t)lds;
+    lds += align256(sizeof(SeqSampleShared));
+  }
   const PodsDev pd = pods_dev(c);
   const NodesDev nd = nodes_dev(c);
-  if (score && nc) launch_seq_scored_nominated(c->stream, c->S, lds, pd, gr, nd, sq, prm, nom, sco);   // (tu_seq_score_nom.hip: rule SP)
+  if (sample && nc) launch_seq_sampled_nominated(c->stream, c->S, lds, pd, gr, nd, sq, prm, nom, sco, smp);   // (tu_seq_sample_nom.hip: rule F over rule SP)
+  else if (sample) launch_seq_sampled(c->stream, c->S, lds, pd, gr, nd, sq, prm, sco, smp);   // (tu_seq_sample.hip: rule F over rule P)
+  else if (score && nc) launch_seq_scored_nominated(c->stream, c->S, lds, pd, gr, nd, sq, prm, nom, sco);   // (tu_seq_score_nom.hip: rule SP)
   else if (score) launch_seq_scored(c->stream, c->S, lds, pd, gr, nd, sq, prm, sco);   // (tu_seq_score.hip: the scored instantiations)
   else if (nc) launch_seq_nominated(c->stream, c->S, lds, pd, gr, nd, sq, prm, nom);   // (tu_seq_nom.hip: the NOM instantiations)
   else launch_seq(c->stream, c->S, lds, pd, gr, nd, sq, prm);
@@ -292,6 +314,7 @@ static int seq_run_impl(bs_ctx* c, uint32_t stages, bs_seq_out* out, const SeqNo
   c->seq_o_node = o_node;
   c->seq_wait_valid = true;
   if (score) { c->seq_score_p = P; c->seq_score_valid = true; }
+  if (sample) c->seq_sample_valid = true;
   return BS_OK;
 }
 
@@ -360,6 +383,71 @@ int bs_seq_run_scored_nominated(bs_ctx* c, uint32_t stages, uint32_t p, const in
   return seq_run_impl(c, stages, out, &nc, score);
 }
 
+// what both sampled forms refuse behind their parents' refusals
+static int seq_sample_refusals(bs_ctx* c, uint32_t stages, const bs_seq_sample* sample, const char* who) {
+  if (!sample) { c->last_error = std::string(who) + ": sample is NULL"; return BS_ERR_INVALID; }
+  if (stages & BS_BATCH_FILTER_DENY) {
+    c->last_error = std::string(who) + ": BS_BATCH_FILTER_DENY is refused (Filter's TTL writes are defined over every node offered; a sampled walk offers the visited nodes only)";
+    return BS_ERR_INVALID;
+  }
+  return BS_OK;
+}
+
+uint32_t bs_seq_sample_size(uint32_t n, int32_t percentage) { return sample_size(n, percentage); }
+
+int bs_seq_run_scored_sampled(bs_ctx* c, uint32_t stages, const bs_seq_score* score, const bs_seq_sample* sample, bs_seq_out* out) {
+  // the refusals of bs_seq_run_scored in its order, then the sampled form's own: all before any launch, nothing resident changes
+  if (!c || !out) return BS_ERR_INVALID;
+  if (const int rc = seq_refusals(c, stages)) return rc;
+  if (!score) { c->last_error = "bs_seq_run_scored_sampled: score is NULL"; return BS_ERR_INVALID; }
+  if (score->w_least > BS_SCORE_WEIGHT_MAX || score->w_most > BS_SCORE_WEIGHT_MAX || score->w_balanced > BS_SCORE_WEIGHT_MAX) {
+    c->last_error = "bs_seq_run_scored_sampled: a weight is above BS_SCORE_WEIGHT_MAX";
+    return BS_ERR_INVALID;
+  }
+  if (const int rc = seq_sample_refusals(c, stages, sample, "bs_seq_run_scored_sampled")) return rc;
+  return seq_run_impl(c, stages, out, nullptr, score, sample);
+}
+
+int bs_seq_run_scored_nominated_sampled(bs_ctx* c, uint32_t stages, uint32_t p, const int32_t* priority, const uint32_t* own_id, const bs_seq_score* score,
+                                        const bs_seq_sample* sample, bs_seq_out* out) {
+  // the refusals of bs_seq_run_scored_nominated in its order, then the sampled form's own
+  if (!c || !out) return BS_ERR_INVALID;
+  if (const int rc = seq_refusals(c, stages)) return rc;
+  if (stages & BS_STAGE_FILTER) {
+    c->last_error = "bs_seq_run_scored_nominated_sampled: BS_STAGE_FILTER is refused (the plugin's Filter takes no part in the fit test under nominees, as in bs_preempt_run)";
+    return BS_ERR_INVALID;
+  }
+  if (p != c->P) { c->last_error = "bs_seq_run_scored_nominated_sampled: p is not the resident queue's length (bs_pods_count)"; return BS_ERR_INVALID; }
+  if (p && !priority) { c->last_error = "bs_seq_run_scored_nominated_sampled: priority is NULL and the queue has pods"; return BS_ERR_INVALID; }
+  if (const int rc = nom_state(c, "bs_seq_run_scored_nominated_sampled")) return rc;
+  std::vector<uint32_t> own_row;
+  if (const int bad = nom_own_check(c->nom_live.data(), c->nom_w, c->nom_ids, p, own_id, BS_NOM_NONE, own_row)) {
+    c->last_error = std::string("bs_seq_run_scored_nominated_sampled: ") + nom_own_check_text(bad);
+    return BS_ERR_INVALID;
+  }
+  if (!score) { c->last_error = "bs_seq_run_scored_nominated_sampled: score is NULL"; return BS_ERR_INVALID; }
+  if (score->w_least > BS_SCORE_WEIGHT_MAX || score->w_most > BS_SCORE_WEIGHT_MAX || score->w_balanced > BS_SCORE_WEIGHT_MAX) {
+    c->last_error = "bs_seq_run_scored_nominated_sampled: a weight is above BS_SCORE_WEIGHT_MAX";
+    return BS_ERR_INVALID;
+  }
+  if (const int rc = seq_sample_refusals(c, stages, sample, "bs_seq_run_scored_nominated_sampled")) return rc;
+  const SeqNomCall nc{priority, &own_row};
+  return seq_run_impl(c, stages, out, &nc, score, sample);
+}
+
+int bs_seq_sample_read(bs_ctx* c, uint32_t p, uint32_t* start, uint32_t* visited, uint32_t* next_start) {
+  if (!c) return BS_ERR_INVALID;
+  if (!c->seq_sample_valid) { c->last_error = "bs_seq_sample_read: the context's last pass was not a successful sampled pass (bs_seq_run_scored_sampled or bs_seq_run_scored_nominated_sampled)"; return BS_ERR_STATE; }
+  if (p != c->seq_score_p) { c->last_error = "bs_seq_sample_read: p is not the queue length of that pass"; return BS_ERR_INVALID; }
+  if (const int rc = use_device(c)) return rc;
+  const uint32_t* d = c->d_seq_sample.as<uint32_t>();
+  const size_t nP = std::max<uint32_t>(p, 1);
+  if (p && start) HIPCHK(c, hipMemcpy(start, d, (size_t)p * 4, hipMemcpyDeviceToHost));
+  if (p && visited) HIPCHK(c, hipMemcpy(visited, d + nP, (size_t)p * 4, hipMemcpyDeviceToHost));
+  if (next_start) HIPCHK(c, hipMemcpy(next_start, d + 2 * nP, 4, hipMemcpyDeviceToHost));
+  return BS_OK;
+}
+
 int bs_seq_score_read(bs_ctx* c, uint32_t p, uint32_t* total, uint32_t* n_fit) {
   if (!c) return BS_ERR_INVALID;
   if (!c->seq_score_valid) { c->last_error = "bs_seq_score_read: the context's last pass was not a successful bs_seq_run_scored or bs_seq_run_scored_nominated"; return BS_ERR_STATE; }
@@ -412,6 +500,43 @@ int bs_seq_run_scored_nominated_flat(bs_ctx* c, uint32_t stages, uint32_t p, con
   o.released_pods = released_pods; o.first_ns = first_ns; o.ready_ns = ready_ns;
   const bs_seq_score score{w_least, w_most, w_balanced};
   const int rc = bs_seq_run_scored_nominated(c, stages, p, priority, own_id, &score, &o);
+  if (scalars_out) {
+    scalars_out[0] = o.n_released; scalars_out[1] = o.total_ns; scalars_out[2] = (int64_t)o.node_picks; scalars_out[3] = (int64_t)o.node_scans;
+    scalars_out[4] = (int64_t)o.scan_rounds; scalars_out[5] = (int64_t)o.pick_rounds; scalars_out[6] = (int64_t)o.leader_folds;
+    scalars_out[7] = (int64_t)o.table_builds;
+  }
+  return rc;
+}
+
+int bs_seq_run_scored_sampled_flat(bs_ctx* c, uint32_t stages, uint32_t w_least, uint32_t w_most, uint32_t w_balanced, uint32_t num_to_find, uint32_t start,
+                                   uint8_t* pf_code, uint32_t* pf_first_k, int32_t* pf_leader, int32_t* pod_node, uint32_t cap, uint32_t* released_group,
+                                   uint32_t* released_pods, int64_t* first_ns, int64_t* ready_ns, int64_t* scalars_out, uint8_t* last_permitted) {
+  bs_seq_out o{};
+  o.last_permitted = last_permitted;
+  o.pf_code = pf_code; o.pf_first_k = pf_first_k; o.pf_leader = pf_leader; o.pod_node = pod_node; o.cap = cap; o.released_group = released_group;
+  o.released_pods = released_pods; o.first_ns = first_ns; o.ready_ns = ready_ns;
+  const bs_seq_score score{w_least, w_most, w_balanced};
+  const bs_seq_sample sample{num_to_find, start};
+  const int rc = bs_seq_run_scored_sampled(c, stages, &score, &sample, &o);
+  if (scalars_out) {
+    scalars_out[0] = o.n_released; scalars_out[1] = o.total_ns; scalars_out[2] = (int64_t)o.node_picks; scalars_out[3] = (int64_t)o.node_scans;
+    scalars_out[4] = (int64_t)o.scan_rounds; scalars_out[5] = (int64_t)o.pick_rounds; scalars_out[6] = (int64_t)o.leader_folds;
+    scalars_out[7] = (int64_t)o.table_builds;
+  }
+  return rc;
+}
+
+int bs_seq_run_scored_nominated_sampled_flat(bs_ctx* c, uint32_t stages, uint32_t p, const int32_t* priority, const uint32_t* own_id, uint32_t w_least,
+                                             uint32_t w_most, uint32_t w_balanced, uint32_t num_to_find, uint32_t start, uint8_t* pf_code, uint32_t* pf_first_k,
+                                             int32_t* pf_leader, int32_t* pod_node, uint32_t cap, uint32_t* released_group, uint32_t* released_pods,
+                                             int64_t* first_ns, int64_t* ready_ns, int64_t* scalars_out, uint8_t* last_permitted) {
+  bs_seq_out o{};
+  o.last_permitted = last_permitted;
+  o.pf_code = pf_code; o.pf_first_k = pf_first_k; o.pf_leader = pf_leader; o.pod_node = pod_node; o.cap = cap; o.released_group = released_group;
+  o.released_pods = released_pods; o.first_ns = first_ns; o.ready_ns = ready_ns;
+  const bs_seq_score score{w_least, w_most, w_balanced};
+  const bs_seq_sample sample{num_to_find, start};
+  const int rc = bs_seq_run_scored_nominated_sampled(c, stages, p, priority, own_id, &score, &sample, &o);
   if (scalars_out) {
     scalars_out[0] = o.n_released; scalars_out[1] = o.total_ns; scalars_out[2] = (int64_t)o.node_picks; scalars_out[3] = (int64_t)o.node_scans;
     scalars_out[4] = (int64_t)o.scan_rounds; scalars_out[5] = (int64_t)o.pick_rounds; scalars_out[6] = (int64_t)o.leader_folds;

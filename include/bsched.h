@@ -1201,6 +1201,57 @@ int bs_seq_score_read(bs_ctx* ctx, uint32_t p, uint32_t* total /*[p]*/, uint32_t
  *       refuses, with the same code: a NULL score, a weight above BS_SCORE_WEIGHT_MAX. */
 int bs_seq_run_scored_nominated(bs_ctx* ctx, uint32_t stages, uint32_t p, const int32_t* priority /*[p]*/, const uint32_t* own_id /*[p] or NULL*/,
                                 const bs_seq_score* score, bs_seq_out* out);
+
+/* ---- upstream's node sampling and rotating start: the two sampled forms of the scored pass ------------------------------------------------
+ * The scored passes above put every pod on the GLOBAL maximum of its candidates.  No cluster of more than 100 nodes running default settings
+ * does that: upstream's findNodesThatFit starts at a cursor that rotates from pod to pod (nextStartNodeIndex), stops once
+ * numFeasibleNodesToFind feasible nodes are found — 500 of 5 000, 1 000 of 20 000 — and scores those only.  The difference feeds back into
+ * everything behind the choice, as said of first fit above.  bs_seq_run_scored_sampled is bs_seq_run_scored, and
+ * bs_seq_run_scored_nominated_sampled is bs_seq_run_scored_nominated, with ONE step replaced: which candidates are scored.
+ *   D9. (recalled upstream, v1.17.5, not vendored: numFeasibleNodesToFind.)  bs_seq_sample_size(n, percentage): if n < 100 or
+ *       percentage >= 100, all n.  Otherwise a = percentage; if a <= 0 then a = 50 - n / 125, raised to 5 when below 5.  The result is
+ *       n * a / 100, raised to 100 when below 100.  All divisions truncate; computed in 64 bits.  (0 %, 1000) -> 420, (40 %, 1000) -> 400,
+ *       (0 %, 6000) -> 300, (0 %, 5000) -> 500.  Pure arithmetic: no context.
+ *   F. (rule F.)  The pass keeps a cursor s, with s_0 = sample.start mod N.  K = sample.num_to_find, where 0 or any value >= N means N.
+ *       For a pod that reaches the node choice the nodes are visited in the order (s + v) mod N, v = 0 .. N - 1.  C is exactly the candidate
+ *       set of the form underneath: rule P's C (with the plugin's Filter narrowing it when BS_STAGE_FILTER is on) or, in the nominated form,
+ *       rule S's C.  Nothing about the fit test is new.  Let c_1 < c_2 < ... be the visit positions of C's members.
+ *       If |C| > K the walk stops at the (K+1)-th member, which is not kept (upstream's `length > numNodesToFind` fires on that node and
+ *       un-counts it): C' = {c_1 .. c_K} and V = c_(K+1), the number of nodes in front of that member; failed nodes between the K-th and the
+ *       (K+1)-th member count as visited.  Otherwise C' = C and V = N.
+ *       The pod takes the member of C' with the largest `total` of rule P (D7, raw lanes, D8 unchanged), ties to the SMALLEST VISIT POSITION.
+ *       That is a library rule, as "lowest index" was: upstream draws at random.
+ *       s <- (s + V) mod N: a pod with no candidate leaves the cursor where it was.  A pod that does not reach the choice (a PreFilter
+ *       rejection, a missing group) has V = 0 and does not move the cursor.  A pod whose Filter fails everywhere counts as C empty: V = N.
+ *       Everything else is untouched: PreFilter (S1), assume, Permit, release, PostBind, and D6's consume.
+ *       Library rule F1: with K >= N (or 0) and start = 0 the pass is its parent form — bs_seq_run_scored, bs_seq_run_scored_nominated — bit
+ *       for bit: every result array, the released gangs, bs_seq_score_read, the consumed rows and all resident state (the work counters of
+ *       bs_seq_out are exempt, as in P2).
+ *       Library rule F2: with weights (0, 0, 0) the pod takes the first member of C in visit order: first fit from a rotating start.
+ *       Library rule F3: upstream's 16 parallel workers make the stop point fuzzy; this is the one-worker reading.
+ *   bs_seq_sample_read  reports on the context's last successful sampled pass: start[i] = the cursor pod i's walk began at, 0 where the
+ *       choice was not reached; visited[i] = V_i; *next_start = the cursor behind the last pod.  The caller hands it to the next pass as
+ *       sample.start: the context keeps no cursor between passes.  Any pointer may be NULL.  p must be that pass's queue length.
+ *   bs_seq_score_read   answers for a sampled pass with n_fit[i] = |C'|; bs_seq_nominated_read answers for the nominated sampled form.
+ *   after the call  the context is in the state bs_seq_run leaves.
+ *   errors      all found on the host before any launch; nothing resident changes.  Everything the parent form refuses on its arguments and
+ *       on what the context has loaded (NULL pointers, stages, shards, p, priority, the table, own ids, score, weights), with the same code
+ *       and in the same order; then BS_ERR_INVALID for a NULL sample; then BS_ERR_INVALID for BS_BATCH_FILTER_DENY, on both forms.  What
+ *       every pass checks while it sets up — the device, a pending batch, fit class indices against the loaded classes, BS_ERR_CAPACITY,
+ *       the queue hand-over — comes behind these two, with the parent's codes.  The reason for the last refusal: this
+ *       library's TTL writes are defined as "every node of the list offered", while upstream under sampling calls Filter on the visited
+ *       nodes only — a different rule, out of scope here.  `stages` is otherwise the parent's: the plain sampled form takes
+ *       BS_STAGE_PREFILTER and BS_STAGE_PREFILTER | BS_STAGE_FILTER, the nominated form refuses BS_STAGE_FILTER as its parent does.
+ *       bs_seq_sample_read: BS_ERR_STATE when the last successful pass was not a sampled one, BS_ERR_INVALID when p differs from that
+ *       pass's.
+ *   Out of scope: sampling under BS_BATCH_FILTER_DENY, in bs_seq_run (first fit) and in bs_batch_run; upstream's random tie draw and its
+ *   16-worker race. */
+typedef struct bs_seq_sample { uint32_t num_to_find; uint32_t start; } bs_seq_sample;
+uint32_t bs_seq_sample_size(uint32_t n, int32_t percentage);
+int bs_seq_run_scored_sampled(bs_ctx* ctx, uint32_t stages, const bs_seq_score* score, const bs_seq_sample* sample, bs_seq_out* out);
+int bs_seq_run_scored_nominated_sampled(bs_ctx* ctx, uint32_t stages, uint32_t p, const int32_t* priority /*[p]*/, const uint32_t* own_id /*[p] or NULL*/,
+                                        const bs_seq_score* score, const bs_seq_sample* sample, bs_seq_out* out);
+int bs_seq_sample_read(bs_ctx* ctx, uint32_t p, uint32_t* start /*[p]*/, uint32_t* visited /*[p]*/, uint32_t* next_start);
 /* The live bound table in table order: node ascending, importance order within a node; bs_bound_count entries.  id_out[i] = the
  * entry's id (its index at the last bs_bound_load), node_out[i] = its node.  BS_ERR_STATE before bs_bound_load; the arrays may be NULL
  * when the table is empty. */
@@ -1491,6 +1542,16 @@ int bs_seq_run_scored_nominated_flat(bs_ctx* ctx, uint32_t stages, uint32_t p, c
                                      uint32_t w_most, uint32_t w_balanced, uint8_t* pf_code, uint32_t* pf_first_k, int32_t* pf_leader, int32_t* pod_node,
                                      uint32_t cap, uint32_t* released_group, uint32_t* released_pods, int64_t* first_ns, int64_t* ready_ns,
                                      int64_t* scalars_out, uint8_t* last_permitted);
+/* the two sampled forms: the parent's flat arguments with bs_seq_sample's two words behind the weights */
+int bs_seq_run_scored_sampled_flat(bs_ctx* ctx, uint32_t stages, uint32_t w_least, uint32_t w_most, uint32_t w_balanced, uint32_t num_to_find,
+                                   uint32_t start, uint8_t* pf_code, uint32_t* pf_first_k, int32_t* pf_leader, int32_t* pod_node, uint32_t cap,
+                                   uint32_t* released_group, uint32_t* released_pods, int64_t* first_ns, int64_t* ready_ns, int64_t* scalars_out,
+                                   uint8_t* last_permitted);
+int bs_seq_run_scored_nominated_sampled_flat(bs_ctx* ctx, uint32_t stages, uint32_t p, const int32_t* priority, const uint32_t* own_id,
+                                             uint32_t w_least, uint32_t w_most, uint32_t w_balanced, uint32_t num_to_find, uint32_t start,
+                                             uint8_t* pf_code, uint32_t* pf_first_k, int32_t* pf_leader, int32_t* pod_node, uint32_t cap,
+                                             uint32_t* released_group, uint32_t* released_pods, int64_t* first_ns, int64_t* ready_ns,
+                                             int64_t* scalars_out, uint8_t* last_permitted);
 /* bs_fit_build: node tables, then the template tables; `ex_*` = bs_fit_templates.exprs, `fd_*` = bs_fit_templates.fields */
 int bs_fit_build_flat(bs_ctx* ctx, uint32_t n, const uint32_t* name, const uint32_t* label_off, const uint32_t* label_key, const uint32_t* label_val,
                       const int64_t* label_int, const uint8_t* label_int_ok, const uint32_t* taint_off, const uint32_t* taint_key,

@@ -9,7 +9,13 @@ same process: a nominated-pod table is loaded in front of every pass in which th
 free cpu, a priority drawn from the queue's four) and that share of the queue owns a row (the pod's own request on a random node); each
 fraction in the comma-separated list gives one entry, for the weights (0, 0, 0) and (1, 0, 1).  Fraction 0 is the empty table: what the
 NOM branches cost when nothing is nominated.
-Usage: python tools/seq_scored_bench.py [config] [scenario] [--reps N] [--nominated F[,F...]]"""
+
+--sample K[,K...] times bs_seq_run_scored_sampled (rule F: upstream's node sampling from a rotating start) beside bs_seq_run_scored
+instead, on the same scene, in the same process, for the weights (0, 0, 0) and (1, 0, 1): one entry per K of the list (0 = all), each
+pass from cursor 0, with the mean of `visited` over the pods that reached the node choice, how many of those had no candidate at all
+(their walks see all N nodes) and the mean over the others.  bs_seq_sample_size(nodes, 0) is what a
+cluster with default settings would pass.
+Usage: python tools/seq_scored_bench.py [config] [scenario] [--reps N] [--nominated F[,F...]] [--sample K[,K...]]"""
 import importlib
 import json
 import os
@@ -81,11 +87,55 @@ def nominated(config, scenario, reps, fracs):
     print(json.dumps(out))
 
 
+def sampled(config, scenario, reps, ks):
+    nodes, fit, groups, pods, _ = bsa.synth.make(config, scenario)
+    pods = pods.take(np.argsort(pods.group, kind="stable"))           # Compare order
+    out = {"config": f"{config}/{scenario}", "pods": int(pods.p), "nodes": int(nodes.n), "groups": int(groups.g), "reps": reps,
+           "default_sample_size": bsa.capi.seq_sample_size(int(nodes.n), 0), "runs": []}
+    with bsa.Context(scalar_lanes=nodes.lanes - 4) as ctx:
+        for weights in ((0, 0, 0), (1, 0, 1)):
+            run = {"weights": list(weights), "forms": {}}
+            for name, k in [("scored", None)] + [(f"sampled_{k}", k) for k in ks]:
+                dev, r = [], None
+                for rep in range(reps + 1):                            # (the first one is the warm-up)
+                    ctx.load_nodes(nodes, fit)
+                    ctx.load_groups(groups)
+                    ctx.load_pods(pods)
+                    r = ctx.seq_run_scored(weights) if k is None else ctx.seq_run_scored_sampled(weights, (k, 0))
+                    if rep:
+                        dev.append(r["total_ns"])
+                wait = ctx.seq_waiting_read()
+                s = ctx.seq_score_read()
+                used = np.unique(np.concatenate([r["pod_node"][r["pod_node"] >= 0], wait[wait >= 0]]))
+                form = {"kernel_ms_median": float(np.median(dev)) / 1e6, "kernel_ms_best": min(dev) / 1e6, "kernel_ms_spread": (max(dev) - min(dev)) / 1e6,
+                        "pods_released": int((r["pod_node"] >= 0).sum()), "pods_waiting": int((wait >= 0).sum()), "nodes_used": int(used.size),
+                        "node_picks": r["node_picks"], "pick_rounds": r["pick_rounds"],
+                        "n_fit_mean": float(s["n_fit"][s["n_fit"] > 0].mean()) if (s["n_fit"] > 0).any() else 0.0}
+                if k is not None:
+                    c = ctx.seq_sample_read()
+                    reached = (c["visited"] > 0)                       # (N > 0: a pod that reached the node choice visited at least one node)
+                    empty = reached & (s["n_fit"] == 0)                # ... and found no candidate: its walk saw all N nodes
+                    placed = reached & ~empty
+                    form["num_to_find"] = k
+                    form["pods_reached"] = int(reached.sum())
+                    form["pods_without_candidate"] = int(empty.sum())
+                    form["visited_mean"] = float(c["visited"][reached].mean()) if reached.any() else 0.0
+                    form["visited_mean_with_candidate"] = float(c["visited"][placed].mean()) if placed.any() else 0.0
+                    form["next_start"] = c["next_start"]
+                run["forms"][name] = form
+            base = run["forms"]["scored"]["kernel_ms_median"]
+            run["ratio_to_scored_kernel_median"] = {n: f["kernel_ms_median"] / base for n, f in run["forms"].items()}
+            out["runs"].append(run)
+    print(json.dumps(out))
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--") and not a.isdigit() and not a.replace(",", "").replace(".", "").isdigit()]
     config = args[0] if args else "cfg3"
     scenario = args[1] if len(args) > 1 else "tail"
     reps = opt("--reps", 7)
+    if "--sample" in sys.argv:
+        return sampled(config, scenario, reps, [int(k) for k in sys.argv[sys.argv.index("--sample") + 1].split(",")])
     if "--nominated" in sys.argv:
         return nominated(config, scenario, reps, [float(f) for f in sys.argv[sys.argv.index("--nominated") + 1].split(",")])
     nodes, fit, groups, pods, _ = bsa.synth.make(config, scenario)
